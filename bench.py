@@ -20,8 +20,18 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, relays
 the JSON line) and exits non-zero if any rank does.  `FRMAP_BENCH_BACKEND=gloo` rehearses the N > 1 control
 flow on a box with fewer GPUs than ranks (ranks share devices; the collective runs over gloo on host copies).
 
+A plain run sets up, runs the settle and warm-up steps, times exactly `--steps` steps, writes the last timed step's outputs
+when `--dump-outputs DIR` is given, and prints the result line.  Everything else it can measure or check (roofline, cpu_baseline,
+fp16_value / u8_input_value, scale_ref; shard_check / local_only at N > 1) runs only under `--full`; without it those fields are
+null or absent.
+
+`--dump-outputs DIR` writes what the timed step returns to its caller, from the last timed step (rank 0: the gathered records of
+every rank at N > 1): `DIR/top1_index.npy` (float64; the matched gallery row, or the unknown id) and `DIR/top1_distance.npy`
+(float32), one entry per face.  The inputs, weights and gallery are seeded, so the same arguments give the same inputs in every run.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with:
-  roofline      — the dominant kernel (conv3x3_pp_kernel<BF16>: the 3×3 stride-1 implicit-GEMM
+  ms_per_step   — wall time of the timed region ÷ `--steps` (host clock, synchronised at both ends).
+  roofline      — (--full) the dominant kernel (conv3x3_pp_kernel<BF16>: the 3×3 stride-1 implicit-GEMM
                   convolutions of layers 2-4): algorithmic FLOPs per launch ÷ its average launch duration,
                   measured with HIP events on the launch stream in an instrumented pass after the timed region
                   ('cnn' / 'arcface': the model handle's own per-launch trace, frmap_model_trace; other families: the per-op wrappers)
@@ -31,14 +41,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with:
                   algorithmic FLOPs / bytes, measured µs and roof time max(FLOP/peak, bytes/8 TB/s);
                   `frac_layerwise` = Σ roof time ÷ measured.  `traffic` is the STORED rocprofv3 PMC measurement
                   (profiles/*.json; PMC counters cannot be read from inside the process).
-  cpu_baseline  — the CPU oracle (oracle/face_oracle.py, fp32 PyTorch restatement of the reference's forward)
+  cpu_baseline  — (--full) the CPU oracle (oracle/face_oracle.py, fp32 PyTorch restatement of the reference's forward)
                   timed on this box's host cores on a bounded sample (rank 0, N = 1 only).
-  fp16_value    — the same step in fp16 (the precision the north-star's 1e-3 / identical-top-1 tolerance is stated
+  fp16_value    — (--full) the same step in fp16 (the precision the north-star's 1e-3 / identical-top-1 tolerance is stated
                   for), timed after the bf16 region in the same process (N = 1 only).
   settle_steps  — untimed steps run BEFORE the W warm-up steps (clock / power-state ramp of a fresh process).
   step_ms       — median / p10 / p90 / min / max of the per-step durations of the timed region (HIP events between the steps).
-  scale_ref     — (N = 1) the N > 1 workload's per-GPU shape on this one GPU: the like-for-like denominator of a scaling curve.
-  shard_check / local_only — (N > 1) identical inputs gave bit-identical records on every rank (the run aborts otherwise); the same
+  scale_ref     — (--full, N = 1) the N > 1 workload's per-GPU shape on this one GPU: the like-for-like denominator of a scaling curve.
+  shard_check / local_only — (--full, N > 1) identical inputs gave bit-identical records on every rank (the run aborts otherwise); the same
                   per-GPU step without the collective.
 """
 from __future__ import annotations
@@ -94,10 +104,38 @@ def parse(argv=None):
                     help="f32: fp32 NCHW crops (the reference's tensor layout, headline); u8: uint8 HWC crops normalised inside the stem")
     ap.add_argument("--streams", type=int, default=2, help="split the per-GPU batch over this many concurrent HIP streams")
     ap.add_argument("--graph", type=int, default=1, help="1: replay the step from a captured HIP graph (0: eager launches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp16 / uint8-input side measurements")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks after the timed steps: roofline + per-kernel table, CPU baseline, "
+                         "fp16 / uint8-input variants, scale_ref (N = 1); shard_check before and local_only after the timed steps (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", dest="dump_outputs",
+                    help="write the last timed step's outputs (top-1 index and distance per face) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fp16 / uint8-input / scale_ref side measurements")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``name -> numpy array`` as ``out_dir/<name>.npy``.  All arrays share their leading (per-face) axis; if together they
+    exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of faces is taken from each and its face numbers go to
+    ``sample_index.npy``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_face = sum(a.nbytes for a in arrays.values()) / max(n, 1)
+    keep = int(DUMP_LIMIT_BYTES // max(per_face + 8, 1))
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -493,10 +531,11 @@ def worker(args) -> int:
             if int(flag.item()) == 0:
                 overlap = False  # (every rank takes the same decision)
 
-    def timed_region(step_fn, settle, warmup, steps, collective, per_step=None):
+    def timed_region(step_fn, settle, warmup, steps, collective, per_step=None, last=None):
         """settle + warmup untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize on both sides.
         `per_step` (a list): receives the duration of every timed step in ms, from HIP events recorded on the launch stream
-        between the steps (an event record is a host-side enqueue; nothing waits inside the region)."""
+        between the steps (an event record is a host-side enqueue; nothing waits inside the region).
+        `last` (a list): receives what the last timed step returned."""
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if per_step is not None else None
         with torch.no_grad():
             for _ in range(max(settle, 0)):      # a fixed COUNT: every rank must issue the same number of collectives
@@ -511,7 +550,7 @@ def worker(args) -> int:
             if evs:
                 evs[0].record()
             for i in range(steps):
-                step_fn()
+                out = step_fn()
                 if evs:
                     evs[i + 1].record()
             torch.cuda.synchronize()
@@ -520,6 +559,8 @@ def worker(args) -> int:
             el = time.perf_counter() - t0
         if evs:
             per_step.extend(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
+        if last is not None:
+            last.append(out)
         return el
 
     # N > 1: before anything is timed, every rank runs the SAME faces (one seed) through the same step and the gathered
@@ -527,7 +568,7 @@ def worker(args) -> int:
     # because every rank runs the same per-rank batch size, hence the same tile layouts and fp32 summation order; results
     # of DIFFERENT batch sizes agree only to rounding, tests/test_properties_gpu.py.)
     shard_check = None
-    if world > 1:
+    if world > 1 and args.full:
         gen_s = torch.Generator(device=dev)
         gen_s.manual_seed(seeds[1] + 4242)
         if args.input == "u8":
@@ -548,8 +589,12 @@ def worker(args) -> int:
                        "faces": B, "condition": "equal per-rank batch size (same tile layouts / fp32 summation order)"}
         del x_same, rec_same
 
-    per_step_ms = []
-    local_elapsed = timed_region(step, args.settle_steps, args.warmup, args.steps, world > 1, per_step_ms)
+    per_step_ms, last_out = [], []
+    local_elapsed = timed_region(step, args.settle_steps, args.warmup, args.steps, world > 1, per_step_ms, last_out)
+    if args.dump_outputs and rank == 0:
+        ids_last, dist_last = last_out[0]
+        dump_outputs(args.dump_outputs, {"top1_index": ids_last.cpu().numpy().astype("float64"),
+                                         "top1_distance": dist_last.cpu().numpy().astype("float32")})
     elapsed_t = torch.tensor([local_elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(elapsed_t, op=dist.ReduceOp.MAX)
@@ -560,7 +605,7 @@ def worker(args) -> int:
     # N > 1: the same per-GPU step WITHOUT the collective, all ranks at once (same power / thermal conditions as the
     # timed region): value / (N * local_only) isolates what the all-gather and rank skew cost
     local_only = None
-    if world > 1:
+    if world > 1 and args.full:
         t_loc = timed_region(lambda: local_records(), 20, args.warmup, args.steps, True)
         v = torch.tensor([B * args.steps / t_loc], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         vmin = v.clone()
@@ -570,7 +615,7 @@ def worker(args) -> int:
 
     # ---------------- roofline: per-kernel instrumented pass (not part of `value`) ----------------
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         import frmap_amd.face_models as fm
         import frmap_amd.matching as mt_
         assert fm.ops is ops and mt_.ops is ops
@@ -640,7 +685,7 @@ def worker(args) -> int:
 
     # ---------------- side measurements (N = 1, rank 0; outside the timed region) ----------------
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras and model_type in ("cnn", "arcface"):
+    if rank == 0 and world == 1 and args.full and not args.no_extras and model_type in ("cnn", "arcface"):
         try:
             if args.dtype == "bf16":
                 m16, _ = build_model(torch.float16)
@@ -664,7 +709,7 @@ def worker(args) -> int:
     # `--gpus N > 1` measures configs[3] (arcface, 1024 faces per GPU, 10 000 IDs); this line's `value` is configs[1].  A
     # scaling curve must divide like by like: value(N) / (N * scale_ref.value).
     scale_ref = None
-    if (rank == 0 and world == 1 and not args.no_extras and args.model is None and args.batch is None and args.gallery is None
+    if (rank == 0 and world == 1 and args.full and not args.no_extras and args.model is None and args.batch is None and args.gallery is None
             and args.input == "f32"):
         try:
             m4 = frmap_amd.get_model("arcface", 36)
@@ -689,7 +734,7 @@ def worker(args) -> int:
 
     # ---------------- CPU baseline: the oracle on the host cores (bounded sample) -----------------
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import face_oracle as fo
         # the GPU box exposes 256 logical CPUs but a 1-GPU job owns a 16-core share; more threads
         # than that only oversubscribe the quota (measured: 256 threads -> 3.8 faces/s)

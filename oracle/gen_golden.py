@@ -198,6 +198,39 @@ def gen_match(ref_cf):
     np.savez_compressed(os.path.join(GOLD, "match.npz"), **out)
 
 
+def gen_reference_answers(ref, ref_cf):
+    """The reference classes' outputs on the weights bench.py runs (seeded init + committed BatchNorm statistics,
+    ``synth.calibrated_state_dict``: bit-identical wherever they are rebuilt) and the reference compare_faces' answers on
+    ``weights.compare_faces_cases()``: what tests/test_oracle_golden.py holds the oracle to without the reference present."""
+    out = {}
+    for mt in ("baseline", "cnn", "arcface", "siamese", "hybrid", "attention"):
+        model = ref.get_model(mt, NUM_CLASSES)
+        shapes = {k: (tuple(v.shape), v.dtype) for k, v in model.state_dict().items()}
+        sd = synth.calibrated_state_dict(mt, shapes, weights.SEEDS[mt][0])
+        model.load_state_dict(sd, strict=True)
+        model.eval()
+        x = weights.golden_inputs(mt, 4)
+        with torch.no_grad():
+            out[f"{mt}_embedding"] = _np(model.get_embedding(x))
+            err = (fo.EMBEDDING[mt](sd, x) - model.get_embedding(x)).abs().max().item()
+            if mt == "siamese":
+                o1, o2 = model(x[:2], x[2:])
+                out[f"{mt}_forward_out1"], out[f"{mt}_forward_out2"] = _np(o1), _np(o2)
+            else:
+                out[f"{mt}_forward"] = _np(model(x))
+        print(f"{mt:9s} oracle-vs-reference max|Δ| embedding (committed BN statistics) = {err:.3e}")
+        assert err < 2e-5, (mt, err)
+    np.savez_compressed(os.path.join(GOLD, "reference_classes.npz"), **out)
+    answers = {}
+    for label, probe, refs, thresh in weights.compare_faces_cases():
+        answers[label] = list(ref_cf(probe, refs, thresh))
+        assert _same_answer(fo.compare_faces(probe, refs, thresh), answers[label]), label
+    doc = {"answers_by": "the reference's own compare_faces (src/app.py:50-64), executed in the build container",
+           "inputs": "oracle.weights.compare_faces_cases()", "answers": answers}
+    with open(os.path.join(GOLD, "reference_compare_faces.json"), "w") as f:
+        json.dump(doc, f, indent=0)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(8)
@@ -210,7 +243,10 @@ def main():
         gen_arcmargin(ref)
     if not only or "ensemble" in only:
         gen_ensemble(ref)
-    gen_models(ref, only or None)
+    if not only or "answers" in only:
+        gen_reference_answers(ref, ref_loader.reference_compare_faces())
+    if not only or only - {"ensemble", "answers"}:
+        gen_models(ref, only or None)
     print("golden vectors written to", GOLD)
 
 

@@ -40,3 +40,24 @@ def calibrated_state_dict(model_type: str,
 
 def golden_inputs(model_type: str, n: int = N_GOLDEN) -> torch.Tensor:
     return synth.randn(SEEDS[model_type][1], (n, 3, 224, 224), tag="x")
+
+
+def compare_faces_cases():
+    """(label, probe [1, D] or None, refs, thresh): the calls on which the reference's compare_faces answers are recorded
+    (tests/golden/reference_compare_faces.json) - random galleries, exact duplicate rows (first strict minimum), thresholds
+    either side of the best distance, the None / empty sentinels."""
+    cases = []
+    for G, D, seed in ((1, 512, 11), (7, 512, 12), (36, 512, 13), (50, 256, 14)):
+        gal = synth.unit_rows(seed, G, D)
+        if G >= 7:
+            gal[5] = gal[2]                                    # exact duplicate rows: index 2 must win over 5
+        refs = [{"name": f"id{i % 4}", "embedding": gal[i:i + 1]} for i in range(G)]
+        probes = torch.cat([gal[: min(G, 6)] + 0.01 * synth.randn(seed + 100, (min(G, 6), D), "p"), synth.unit_rows(seed + 200, 4, D, "q")])
+        for b in range(probes.shape[0]):
+            for thresh in (0.05, 1.0, 1e9):
+                cases.append((f"G{G}_D{D}_probe{b}_t{thresh:g}", probes[b:b + 1], refs, thresh))
+        if G >= 7:
+            cases.append((f"G{G}_D{D}_row5_duplicates_row2", gal[5:6], refs, 1.0))
+    cases.append(("probe_none", None, [{"name": "a", "embedding": torch.zeros(1, 4)}], 1.0))
+    cases.append(("refs_empty", torch.zeros(1, 4), [], 1.0))
+    return cases

@@ -108,3 +108,32 @@ def test_committed_bn_statistics_equal_the_test_weights(mt, calibrated_sd):
             assert torch.equal(sd_test[k], sd_bench[k]), k
     with pytest.raises(FileNotFoundError):
         synth.calibrated_state_dict("hybrid", {}, 1)
+
+
+def test_full_and_dump_outputs_options(tmp_path, monkeypatch):
+    """A plain run times the steps and prints the line; the side measurements and checks are behind --full.  --dump-outputs writes
+    every array as DIR/<name>.npy, or the same seeded sample of faces from each when they would exceed the size limit."""
+    import numpy as np
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path), "--steps", "7"])
+    assert a.full is True and a.dump_outputs == str(tmp_path) and a.steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    for gate in ("args.full and not args.no_roofline", "args.full and not args.no_extras and model_type", "args.full and not args.no_cpu_baseline",
+                 "world > 1 and args.full:\n        gen_s", "world > 1 and args.full:\n        t_loc"):
+        assert gate in src, gate
+    ids, dist = np.arange(10, dtype=np.float64), np.linspace(0, 1, 10, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), {"top1_index": ids, "top1_distance": dist})
+    assert sorted(os.listdir(tmp_path / "all")) == ["top1_distance.npy", "top1_index.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "top1_index.npy"), ids)
+    assert np.load(tmp_path / "all" / "top1_distance.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (12 + 8))             # room for 3 faces of 12 B (+ 8 B of sample index)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"top1_index": ids, "top1_distance": dist})
+    idx = np.load(tmp_path / "s1" / "sample_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 3 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "top1_index.npy"), ids[idx.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "s1" / "top1_distance.npy"), dist[idx.astype(int)])
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "sample_index.npy"))   # fixed seed: the same sample every time
