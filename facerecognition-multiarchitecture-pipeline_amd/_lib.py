@@ -14,7 +14,7 @@ import threading
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # FRMAP_LIB: load another build of the library (A/B variants made by tools; must have the same ABI) instead of the in-tree one
 LIB_PATH = os.environ.get("FRMAP_LIB") or os.path.join(_PKG_DIR, "libfrmap_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lock = threading.Lock()
 _lib = None
@@ -76,6 +76,9 @@ PROTOTYPES = {
     "frmap_head_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_top1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
+    "frmap_match_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "frmap_match_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "frmap_match_topk_packed": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "frmap_gap_norm_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _f, _i, _i, _i, _i, _i, _vp]),
     "frmap_cosine_logits": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "frmap_arcmargin_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
@@ -89,6 +92,8 @@ PROTOTYPES = {
     "frmap_model_match_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "frmap_model_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "frmap_model_embed_and_match": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frmap_model_search_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "frmap_model_embed_and_search": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frmap_model_trace": (_i, [_vp, _i]),
     "frmap_model_trace_read": (_i, [_vp, _vp, _i]),
     "frmap_model_destroy": (None, [_vp]),

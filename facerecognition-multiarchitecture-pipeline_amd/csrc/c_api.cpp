@@ -55,5 +55,5 @@ int frmap_batch_invariant() {
 }
 extern "C" int frmap_set_batch_invariant(int on) { g_invariant = on < 0 ? -1 : (on != 0); return 0; }
 
-extern "C" int frmap_abi_version(void) { return 9; }
+extern "C" int frmap_abi_version(void) { return 10; }
 extern "C" const char* frmap_last_error(void) { return g_err; }

@@ -46,10 +46,10 @@ struct ConvParams {
   const void* ds_w;    // packed like a 1x1 conv: [Cout/64][ds_Cin/32][1][64][4][8]
   int ds_Hi, ds_Wi, ds_Cin, ds_stride, ds_chunks;
   FrmapPoolOrder pool;  // conv_igemm_kernel<..., POOL = true>: pool-major pixel order of the fused 2x2 max-pool
-  // conv1x1_kernel<..., MATCH = true>: the GEMM is probes x gallery rows, the epilogue keeps each probe's arg-min distance
+  // conv1x1_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR>: the GEMM is probes x gallery rows, the epilogue keeps each probe's arg-min distance
   const float* m_stat_a;           // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
   const float* m_stat_w;           // [G][4] of the fp32 gallery rows
-  MatchRec* m_recs;                // [Cout / 64][M] candidate records (frmap_common.h), one writer each
+  void* m_recs;                    // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
   int m_G, m_D;                    // real gallery rows (Cout is padded to 64), embedding width
 };
 
@@ -1010,11 +1010,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_fast_kernel(const ConvParams
 // 64 x 128 weights (16 KB) per stage, 64 MFMAs per wave per stage, both operands of the next stage
 // prefetched into registers under the current stage's MFMAs.  Split-K as in frmap_linear_mfma.
 // ================================================================================================
-// MATCH = true: top-1 gallery match (head_match.hip, frmap_match_top1_packed).  The "pixels" are the probes and the
+// MM = MATCH_TOP1: top-1 gallery match (head_match.hip, frmap_match_top1_packed); MATCH_TOPR: the top-k search's records (frmap_match_topk_packed).  The "pixels" are the probes and the
 // "channels" the gallery rows, both split into fp16 (hi, lo) pairs laid out so that one K = 3 D GEMM accumulates
 // a_hi.g_hi + a_hi.g_lo + a_lo.g_hi in fp32 (= the fp32 dot product to ~2^-22); the epilogue forms the squared
 // F.pairwise_distance from it as gemm_nt_f32_kernel<MODE_DIST> does and writes one candidate record per probe and 64-row slot.
-template <typename TT, int CKS, bool MATCH = false>
+template <typename TT, int CKS, int MM = MATCH_NONE>
 __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
   constexpr int BM = 256, MI = 4, NI = 4, NIT = BM * 4 / 256;
   using vec8 = typename TT::vec8;
@@ -1087,8 +1087,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = TT::mfma(wf[ni], pf[mi], acc[mi][ni]);
     }
   }
-  if constexpr (MATCH) {
-    match_epilogue_records<MI>(acc, m0 + wave * 64, p.M, nt << 6, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.m_recs, lane);
+  if constexpr (MM != MATCH_NONE) {
+    match_epilogue<MM, MI>(acc, m0 + wave * 64, p.M, nt << 6, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.m_recs, lane);
     return;
   }
   __syncthreads();
@@ -1100,9 +1100,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
                               (const typename TT::elem*)p.res, (typename TT::elem*)p.out, p.relu, lane);
 }
 
-template <typename TT, int CKS, bool MATCH = false>
+template <typename TT, int CKS, int MM = MATCH_NONE>
 static int launch_1x1(const ConvParams& p, hipStream_t st) {
-  auto kern = conv1x1_kernel<TT, CKS, MATCH>;
+  auto kern = conv1x1_kernel<TT, CKS, MM>;
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
   int lds = CKS * (256 * 64 + 4096);
   const int scratch = 4 * 16 * (4 * 64 + 16);
@@ -1460,11 +1460,11 @@ extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, cons
 // power-of-two scale, whose inverse is the third float of its statistics record.
 // ------------------------------------------------------------------------------------------------
 int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                           MatchRec* recs, int B, int G, int D, hipStream_t st) {
+                           void* recs, int B, int G, int D, hipStream_t st, int topr) {
   const int K3 = 3 * D, Gpad = (G + 255) / 256 * 256;   // (the packed gallery is padded to 256 rows: frmap_match_gallery_pack_bytes)
   FRMAP_REQUIRE(K3 % 32 == 0, "match: D=%d must be a multiple of 32", D);
   {
-    const int rc = frmap_match_gemm_pp(probes3, gallery_packed, stat_a, stat_w, recs, B, G, Gpad, D, st);
+    const int rc = frmap_match_gemm_pp(probes3, gallery_packed, stat_a, stat_w, recs, B, G, Gpad, D, st, topr);
     if (rc < 0) return rc;
     if (rc == 1) return 0;
   }
@@ -1480,10 +1480,16 @@ int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, cons
   p.nblocks = ((B + 255) / 256) * (Gpad / 64);
   p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_recs = recs; p.m_G = G; p.m_D = D;
   const int c32 = K3 / 32;
-  if (c32 % 4 == 0) { p.nchunks = c32 / 4; return launch_1x1<F16, 4, true>(p, st); }
-  if (c32 % 2 == 0) { p.nchunks = c32 / 2; return launch_1x1<F16, 2, true>(p, st); }
+  if (topr) {
+    if (c32 % 4 == 0) { p.nchunks = c32 / 4; return launch_1x1<F16, 4, MATCH_TOPR>(p, st); }
+    if (c32 % 2 == 0) { p.nchunks = c32 / 2; return launch_1x1<F16, 2, MATCH_TOPR>(p, st); }
+    p.nchunks = c32;
+    return launch_1x1<F16, 1, MATCH_TOPR>(p, st);
+  }
+  if (c32 % 4 == 0) { p.nchunks = c32 / 4; return launch_1x1<F16, 4, MATCH_TOP1>(p, st); }
+  if (c32 % 2 == 0) { p.nchunks = c32 / 2; return launch_1x1<F16, 2, MATCH_TOP1>(p, st); }
   p.nchunks = c32;
-  return launch_1x1<F16, 1, true>(p, st);
+  return launch_1x1<F16, 1, MATCH_TOP1>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -54,10 +54,10 @@ struct PPParams {
   // fused MaxPool2d(2, 2) (PL = true): each wave's 112-pixel slice (whole row pairs) is walked in pool-major order
   int Wo2;         // Wi / 2
   FrmapDiv dWo2;
-  // conv1x1_pp_kernel<..., MATCH = true> (top-1 gallery match, head_match.hip): per-row statistics and the arg-min keys
+  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR> (gallery match, head_match.hip): per-row statistics and the arg-min keys
   const float* m_stat_a;        // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
   const float* m_stat_w;        // [G][4] of the fp32 gallery rows
-  MatchRec* m_recs;             // [Cout / 64][M] candidate records (frmap_common.h), one writer each
+  void* m_recs;                 // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
   int m_G, m_D;
 };
 
@@ -506,10 +506,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p) {
 // KS = 2: 224 px x 128 ch with the two wave groups splitting K (own buffers; accumulators merged through LDS) for outputs with
 // few tiles (Linear 2048 -> 512 over 12 544 tokens: 224 tiles instead of 112).
 // ================================================================================================
-// MATCH = true: the epilogue of conv1x1_kernel<..., MATCH> (conv_igemm.hip): the GEMM is probes x gallery rows in split fp16
+// MM = MATCH_TOP1: the epilogue of conv1x1_kernel<..., MATCH_TOP1> (conv_igemm.hip): the GEMM is probes x gallery rows in split fp16
 // operands, each lane forms the expanded squared F.pairwise_distance of its 16 gallery rows with its error band, the column's
 // four lanes meet through two shuffles, one candidate record per probe and 64-row slot (match_epilogue_records).
-template <typename TT, int MI, int WM, int KS, bool MATCH = false>
+// MM = MATCH_TOPR: the same GEMM with the top-k search's records (match_epilogue_topr: R = 4 rows per slot + the rest bound).
+template <typename TT, int MI, int WM, int KS, int MM = MATCH_NONE>
 __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const PPParams p) {
   constexpr int NI = 4, WN = KS == 2 ? 2 : 8 / WM;
   constexpr int CAP = (KS == 2 ? 2 : WM) * MI * 16;          // pixels of a tile
@@ -638,9 +639,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const PPParams p) {
     __syncthreads();
     if (grp == 1) return;
   }
-  if constexpr (MATCH) {
-    match_epilogue_records<MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
-                               p.m_recs, lane);
+  if constexpr (MM != MATCH_NONE) {
+    match_epilogue<MM, MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
+                           p.m_recs, lane);
     return;
   }
   conv_epilogue<TT, MI, NI>(acc, smem + (KS == 2 ? q : wave) * (16 * (NI * 64 + 16)), m0 + mslice * (MI * 16), mend, p.Cout,
@@ -1094,10 +1095,10 @@ int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shi
 // 1x1 conv / Linear launcher (conv1x1_pp_kernel): 1 = launched, 0 = shape not taken, < 0 = error; in == nullptr: plan only
 // (returns the layout: 1 = 224 px x 256 ch, 2 = 448 px x 128 ch, 3 = 224 px x 128 ch split-K)
 // ------------------------------------------------------------------------------------------------
-template <typename TT, int WM, int KS, bool MATCH = false>
+template <typename TT, int WM, int KS, int MM = MATCH_NONE>
 static int pp1_launch(const PPParams& p, hipStream_t st) {
   constexpr int MI = 7;
-  auto kern = conv1x1_pp_kernel<TT, MI, WM, KS, MATCH>;
+  auto kern = conv1x1_pp_kernel<TT, MI, WM, KS, MM>;
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
   constexpr int CAP = (KS == 2 ? 2 : WM) * MI * 16, GW = 8 / KS, NGP = (CAP / 16 + GW - 1) / GW;
   const int wb = (KS == 2 ? 2 : 8 / WM) * 64 * 64;
@@ -1174,10 +1175,10 @@ int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, c
   return rc ? rc : 1;
 }
 
-// top-1 match GEMM on the same kernel (see frmap_match_gemm_f16x3 in conv_igemm.hip): G padded to 256 rows, K3 = 3 D.
-// 1 = launched, 0 = not taken
+// match GEMM on the same kernel (see frmap_match_gemm_f16x3 in conv_igemm.hip): G padded to 256 rows, K3 = 3 D.
+// topr = 0: top-1 records (MatchRec), 1: top-R records (MatchRecK).  1 = launched, 0 = not taken
 int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                        MatchRec* recs, int B, int G, int Gpad, int D, hipStream_t st) {
+                        void* recs, int B, int G, int Gpad, int D, hipStream_t st, int topr) {
   static int on = -1;
   if (on < 0) on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_MATCH_PP", 1);
   const int K3 = 3 * D;
@@ -1198,7 +1199,8 @@ int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const f
   p.tile_px = wide ? 448 : 224;
   p.mtiles = (B + p.tile_px - 1) / p.tile_px;
   p.ntiles = Gpad / (wide ? 128 : 256);
-  const int rc = wide ? pp1_launch<F16, 4, 1, true>(p, st) : pp1_launch<F16, 2, 1, true>(p, st);
+  const int rc = topr ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
+                      : (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st));
   return rc ? rc : 1;
 }
 

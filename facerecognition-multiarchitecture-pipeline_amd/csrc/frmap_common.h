@@ -143,6 +143,99 @@ __device__ __forceinline__ void match_epilogue_records(const f32x4_t (&acc)[MI][
 }
 
 // ------------------------------------------------------------------------------------------------
+// Top-k gallery search behind the same GEMMs: per probe and 64-row slot, the R = 4 smallest lower bounds L of the slot (ascending,
+// first row first among equal L) with their rows and upper bounds U, and `rest` = the (R+1)-th smallest L, a lower bound on every
+// row of the slot that is not listed.  Error bounds as match_epilogue_records.  match_topk_finalize_kernel (head_match.hip) takes
+// tau = the k-th smallest listed U (per distinct label in identity mode) and re-scores exactly every listed row with L <= tau and
+// every row of a slot whose rest <= tau.  An identity enrolled up to R times in one slot never forces a whole-slot re-score.
+// ------------------------------------------------------------------------------------------------
+enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2 };
+constexpr int MATCH_R = 4;
+struct __attribute__((aligned(16))) MatchRecK {   // 64 bytes
+  float lo[MATCH_R];
+  int idx[MATCH_R];   // -1: none
+  float up[MATCH_R];
+  float rest;
+  int pad[3];
+};
+
+// insert (L, n, U) into an ascending R-list; what falls off (or L itself) lowers `rest`.  Strict compares: an equal L goes after,
+// and a NaN L is never listed nor counted.
+__device__ __forceinline__ void match_topr_insert(float (&lo)[MATCH_R], int (&ix)[MATCH_R], float (&up)[MATCH_R], float& rest,
+                                                  float L, int n, float U) {
+  rest = fminf(rest, L < lo[MATCH_R - 1] ? lo[MATCH_R - 1] : L);
+#pragma unroll
+  for (int j = MATCH_R - 1; j >= 0; --j) {
+    const bool shift = j > 0 && L < lo[j - 1];          // the entry above moves down into slot j
+    const bool here = L < lo[j] && !shift;              // L lands in slot j
+    if (j > 0 && shift) { lo[j] = lo[j - 1]; ix[j] = ix[j - 1]; up[j] = up[j - 1]; }
+    else if (here) { lo[j] = L; ix[j] = n; up[j] = U; }
+  }
+}
+
+template <int MI>
+__device__ __forceinline__ void match_epilogue_topr(const f32x4_t (&acc)[MI][4], int b_base, int b_end, int n0, int G, int D, int M,
+                                                    const float* __restrict__ stat_a, const float* __restrict__ stat_w,
+                                                    MatchRecK* __restrict__ recs, int lane) {
+  const int lr = lane & 15, g = lane >> 4;
+  const float eps = 1e-6f, kf = (float)D, keps = kf * eps * eps, kap = match_kappa(3 * D);
+  MatchRecK* out = recs + (size_t)(n0 >> 6) * M;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int b = b_base + mi * 16 + lr;
+    const f32x4_t sa = *(const f32x4_t*)(stat_a + 4 * (size_t)min(b, M - 1));
+    const float a2 = sa[0], as = sa[1], ai = sa[2], ab = sa[3] + keps;
+    float lo[MATCH_R], up[MATCH_R], rest = INFINITY;
+    int ix[MATCH_R];
+#pragma unroll
+    for (int j = 0; j < MATCH_R; ++j) { lo[j] = INFINITY; up[j] = INFINITY; ix[j] = -1; }
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = n0 + ni * 16 + 4 * g + j;
+        const f32x4_t sw = *(const f32x4_t*)(stat_w + 4 * (size_t)min(n, G - 1));
+        const float d2 = a2 + sw[0] - 2.f * (acc[mi][ni][j] * ai * sw[2]) + 2.f * eps * (as - sw[1]) + keps;
+        const float dl = kap * (ab + sw[3]);
+        const float L = n < G ? d2 - dl : INFINITY, U = n < G ? d2 + dl : INFINITY;
+        match_topr_insert(lo, ix, up, rest, L, n, U);   // rows ascend inside the lane
+      }
+    }
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+      float olo[MATCH_R], oup[MATCH_R];
+      int oix[MATCH_R];
+#pragma unroll
+      for (int j = 0; j < MATCH_R; ++j) {
+        olo[j] = __shfl_xor(lo[j], o, 64); oup[j] = __shfl_xor(up[j], o, 64); oix[j] = __shfl_xor(ix[j], o, 64);
+      }
+      rest = fminf(rest, __shfl_xor(rest, o, 64));
+#pragma unroll
+      for (int j = 0; j < MATCH_R; ++j) match_topr_insert(lo, ix, up, rest, olo[j], oix[j], oup[j]);
+    }
+    if (g == 0 && b < b_end) {
+      MatchRecK r;
+#pragma unroll
+      for (int j = 0; j < MATCH_R; ++j) { r.lo[j] = lo[j]; r.idx[j] = ix[j]; r.up[j] = up[j]; }
+      r.rest = rest; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+      out[b] = r;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// the epilogue of a match GEMM in mode MM (MATCH_TOP1: MatchRec records, MATCH_TOPR: MatchRecK records, same [slot][M] layout)
+template <int MM, int MI>
+__device__ __forceinline__ void match_epilogue(const f32x4_t (&acc)[MI][4], int b_base, int b_end, int n0, int G, int D, int M,
+                                               const float* __restrict__ stat_a, const float* __restrict__ stat_w, void* recs,
+                                               int lane) {
+  if constexpr (MM == MATCH_TOP1)
+    match_epilogue_records<MI>(acc, b_base, b_end, n0, G, D, M, stat_a, stat_w, (MatchRec*)recs, lane);
+  else
+    match_epilogue_topr<MI>(acc, b_base, b_end, n0, G, D, M, stat_a, stat_w, (MatchRecK*)recs, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Shared conv epilogue.  After the K loop a lane holds, per 16x16 MFMA tile (mi, ni), 4 consecutive
 // output channels (ni*16 + g*4 ..+3) of ONE pixel (mi*16 + lr).  Storing that directly is 8 bytes
 // per lane scattered over 16 pixel rows per instruction (32-byte fragments of 128-byte lines).
@@ -362,11 +455,14 @@ int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shi
 // 1x1 conv / Linear on the LDS-DMA ping-pong pipeline (conv1x1_pp_kernel): 1 = launched, 0 = not taken, < 0 = error
 int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
                      int Wi, int Cin, int Cout, int stride, int relu, int dtype, hipStream_t st);
+// match GEMMs: topr = 0 writes MatchRec records (top-1), topr = 1 MatchRecK records (top-k search)
 int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                        MatchRec* recs, int B, int G, int Gpad, int D, hipStream_t st);
-// top-1 match GEMM on the 1x1 MFMA kernel (conv_igemm.hip), see frmap_match_top1_packed
+                        void* recs, int B, int G, int Gpad, int D, hipStream_t st, int topr);
+// match GEMM on the 1x1 MFMA kernel (conv_igemm.hip), see frmap_match_top1_packed / frmap_match_topk_packed
 int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                           MatchRec* recs, int B, int G, int D, hipStream_t st);
+                           void* recs, int B, int G, int D, hipStream_t st, int topr);
+// label_out[0 .. n) = -1 (frmap_match_topk's k = 1 entry-mode outputs; head_match.hip)
+int frmap_match_topk_fill_labels(int32_t* label_out, int n, hipStream_t st);
 #define FRMAP_REQUIRE(cond, ...)        \
   do {                                  \
     if (!(cond)) {                      \

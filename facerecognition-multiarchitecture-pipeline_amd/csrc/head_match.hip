@@ -3,6 +3,7 @@
 //   frmap_linear_f32        nn.Linear (+ folded BatchNorm1d) (+ReLU)   face_models.py:32-33,75,467-468,488,678
 //   frmap_l2_normalize_f32  F.normalize(p=2, dim=1, eps)               face_models.py:179,525,590
 //   frmap_match_top1        compare_faces' arg-min over the gallery    app.py:58-63
+//   frmap_match_topk        the k nearest rows / identities, exact      (top-k search)
 //   frmap_cosine_logits     class-centre cosine logits + arg-max       hyperparameter_tuning.py:1038-1046
 //   frmap_arcmargin_eval    ArcMarginProduct.forward, eval mode        face_models.py:351-429
 //
@@ -1008,7 +1009,7 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
   MatchRec* recs = (MatchRec*)workspace;
   float* stat_a = (float*)(recs + (size_t)nslots * B);
   hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, stat_a, (_Float16*)probe_split, B, D);
-  const int rc = frmap_match_gemm_f16x3(probe_split, gallery_packed, stat_a, stat_w, recs, B, G, D, st);
+  const int rc = frmap_match_gemm_f16x3(probe_split, gallery_packed, stat_a, stat_w, recs, B, G, D, st, 0);
   if (rc) return rc;
   hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)recs, nslots, 64,
                      idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D);
@@ -1019,6 +1020,228 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
 extern "C" size_t frmap_match_workspace_bytes(int B, int G) {
   const size_t b = B > 0 ? (size_t)B : 0, g = G > 0 ? (size_t)G : 0;
   return 16 * b * (4 * ((g + 127) / 128)) + 16 * b + 8 * g + 256;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Exact top-k search (frmap_match_topk[_packed]): the k gallery rows (entry mode) or identities (identity mode: per label, the
+// min over its rows; its representative is the first row attaining it) nearest to each probe under the exact distance of
+// match_exact_d2, ordered by (d2, row).  Rows whose distance is NaN or +inf are never listed; missing entries are
+// (idx -1, dist +inf, label -1).
+//
+// One wave per probe keeps a sorted k-list, one entry per lane (k <= 64): lane i < k holds the i-th smallest key (d, row)
+// and its label; empty entries are (+inf, INT_MAX, -1).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool topk_less(double d1, int r1, double d2, int r2) { return d1 < d2 || (d1 == d2 && r1 < r2); }
+
+// insert the wave-uniform (d, row, lab).  BY_LABEL: one entry per label, replaced only by a smaller key (a strictly smaller
+// d, or an equal d at a lower row); lanes [pos, hi) move down by one, the entry that falls off is lane hi - 1's.
+template <bool BY_LABEL>
+__device__ __forceinline__ void topk_insert(double& ld, int& lr, int& ll, double d, int row, int lab, int k, int lane) {
+  int hi = k;
+  if (BY_LABEL) {
+    const unsigned long long same = __ballot(lane < k && ll == lab);
+    if (same) {
+      const int e = __ffsll((long long)same) - 1;
+      if (!topk_less(d, row, __shfl(ld, e, 64), __shfl(lr, e, 64))) return;
+      hi = e + 1;
+    }
+  }
+  const int pos = __popcll(__ballot(lane < k && topk_less(ld, lr, d, row)));
+  if (pos >= hi) return;
+  const double ud = __shfl_up(ld, 1, 64);
+  const int ur = __shfl_up(lr, 1, 64), ul = __shfl_up(ll, 1, 64);
+  if (lane > pos && lane < hi) { ld = ud; lr = ur; ll = ul; }
+  if (lane == pos) { ld = d; lr = row; ll = lab; }
+}
+
+template <bool BY_LABEL>
+__device__ __forceinline__ void topk_write(double ld, int lr, int ll, int b, int k, int lane, int32_t* __restrict__ idx_out,
+                                           float* __restrict__ dist_out, int32_t* __restrict__ label_out) {
+  if (lane < k) {
+    const bool any = lr != 0x7FFFFFFF;
+    idx_out[(size_t)b * k + lane] = any ? lr : -1;
+    dist_out[(size_t)b * k + lane] = any ? (float)sqrt(ld) : INFINITY;
+    if (label_out) label_out[(size_t)b * k + lane] = (BY_LABEL && any) ? ll : -1;
+  }
+}
+
+// Small or unprepared galleries: one wave per probe scores every row exactly, in row order.
+template <bool BY_LABEL>
+__global__ void match_topk_scan_kernel(const float* __restrict__ emb, const float* __restrict__ gal, const int32_t* __restrict__ labels,
+                                       int32_t* __restrict__ idx_out, float* __restrict__ dist_out, int32_t* __restrict__ label_out,
+                                       int B, int G, int D, int k) {
+  const int b = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* a = emb + (size_t)b * D;
+  double ld = INFINITY, kth = INFINITY;
+  int lr = 0x7FFFFFFF, ll = -1;
+  for (int g = 0; g < G; ++g) {
+    const double d = match_exact_d2(a, gal + (size_t)g * D, D, lane);
+    if (d < INFINITY && d <= kth) {
+      topk_insert<BY_LABEL>(ld, lr, ll, d, g, BY_LABEL ? labels[g] : -1, k, lane);
+      kth = __shfl(ld, k - 1, 64);
+    }
+  }
+  topk_write<BY_LABEL>(ld, lr, ll, b, k, lane, idx_out, dist_out, label_out);
+}
+
+// Prepared galleries: the records of conv1x1_[pp_]kernel<..., MATCH_TOPR> (frmap_common.h: MatchRecK [nslots][B]).
+//   tau = the k-th smallest listed U (identity mode: the k-th smallest, over distinct labels, of the per-label min of listed U);
+//         +inf when the records name fewer than k rows (labels).
+//   re-score with match_exact_d2 every listed row with L <= tau, and every row of a slot whose rest bound is <= tau.
+// Why this is exact: the k listed rows (distinct labels) behind tau have exact d2 <= their U <= tau, so the k-th answer has
+// d2 <= tau; a row with exact d2 <= tau has L <= d2 <= tau, so it is either listed with L <= tau or unlisted in a slot whose
+// rest <= its L <= tau - re-scored either way (in identity mode every row attaining its identity's min is among them, so the
+// first one is found).  The running k-th exact key tightens the bound as the list fills: a row with L > the k-th exact d2 can
+// change nothing.  Slots are visited in ascending order but the k-list orders by (d2, row) itself, so the visiting order
+// does not matter.
+template <bool BY_LABEL>
+__global__ void match_topk_finalize_kernel(const float* __restrict__ emb, const float* __restrict__ gal, const int32_t* __restrict__ labels,
+                                           const MatchRecK* __restrict__ recs, int nslots, int32_t* __restrict__ idx_out,
+                                           float* __restrict__ dist_out, int32_t* __restrict__ label_out, int B, int G, int D, int k) {
+  const int b = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const float* a = emb + (size_t)b * D;
+  MatchRecK none;
+#pragma unroll
+  for (int j = 0; j < MATCH_R; ++j) { none.lo[j] = INFINITY; none.idx[j] = -1; none.up[j] = INFINITY; }
+  none.rest = INFINITY;
+  // tau: a k-list of upper bounds
+  double ld = INFINITY, kth = INFINITY;
+  int lr = 0x7FFFFFFF, ll = -1;
+  for (int s0 = 0; s0 < nslots; s0 += 64) {
+    const MatchRecK r = s0 + lane < nslots ? recs[(size_t)(s0 + lane) * B + b] : none;
+#pragma unroll
+    for (int j = 0; j < MATCH_R; ++j) {
+      unsigned long long mask = __ballot(r.idx[j] >= 0 && (double)r.up[j] <= kth);
+      while (mask) {
+        const int l = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const int row = __shfl(r.idx[j], l, 64);
+        const double u = (double)__shfl(r.up[j], l, 64);
+        if (u <= kth) {
+          topk_insert<BY_LABEL>(ld, lr, ll, u, row, BY_LABEL ? labels[row] : -1, k, lane);
+          kth = __shfl(ld, k - 1, 64);
+        }
+      }
+    }
+  }
+  const double tau = kth;
+  // exact re-score into the answer's k-list
+  ld = INFINITY; kth = INFINITY; lr = 0x7FFFFFFF; ll = -1;
+  auto score = [&](int row) {
+    const double d = match_exact_d2(a, gal + (size_t)row * D, D, lane);
+    if (d < INFINITY && d <= kth) {
+      topk_insert<BY_LABEL>(ld, lr, ll, d, row, BY_LABEL ? labels[row] : -1, k, lane);
+      kth = __shfl(ld, k - 1, 64);
+    }
+  };
+  for (int s0 = 0; s0 < nslots; s0 += 64) {
+    const MatchRecK r = s0 + lane < nslots ? recs[(size_t)(s0 + lane) * B + b] : none;
+    const double bound = fmin(tau, kth);
+    const bool full = (double)r.rest <= bound;
+    unsigned long long mask = __ballot(full);
+    while (mask) {
+      const int l = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int g0 = (s0 + l) * 64, g1 = min(g0 + 64, G);
+      for (int g = g0; g < g1; ++g) score(g);
+    }
+#pragma unroll
+    for (int j = 0; j < MATCH_R; ++j) {
+      mask = __ballot(!full && r.idx[j] >= 0 && (double)r.lo[j] <= fmin(tau, kth));
+      while (mask) {
+        const int l = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const double lo = (double)__shfl(r.lo[j], l, 64);
+        const int row = __shfl(r.idx[j], l, 64);
+        if (lo <= fmin(tau, kth)) score(row);
+      }
+    }
+  }
+  topk_write<BY_LABEL>(ld, lr, ll, b, k, lane, idx_out, dist_out, label_out);
+}
+
+__global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+static size_t align256_sz(size_t n) { return (n + 255) / 256 * 256; }
+
+// workspace of frmap_match_topk[_packed]: [ top-R records [Gpad / 64][B] | probe statistics [B][4] ] or, for k = 1 in entry mode,
+// the top-1 path's own workspace (frmap_match_workspace_bytes) - whichever is larger - then the probes' fp16 split [B][3 D].
+extern "C" size_t frmap_match_topk_workspace_bytes(int B, int G, int D, int k) {
+  (void)k;
+  const size_t b = B > 0 ? (size_t)B : 0, g = G > 0 ? (size_t)G : 0, d = D > 0 ? (size_t)D : 0;
+  const size_t recs = align256_sz(sizeof(MatchRecK) * b * ((g + 255) / 256 * 4)) + align256_sz(16 * b);
+  const size_t top1 = align256_sz(frmap_match_workspace_bytes(B, G));
+  return (recs > top1 ? recs : top1) + align256_sz(2 * b * 3 * d) + 256;
+}
+
+static int topk_check(const char* what, const float* emb, const float* gallery, int32_t* idx_out, float* dist_out, void* workspace,
+                      int B, int G, int D, int k) {
+  FRMAP_REQUIRE(emb && idx_out && dist_out && workspace, "%s: null pointer", what);
+  FRMAP_REQUIRE(k >= 1 && k <= 64, "%s: k=%d out of range (1 <= k <= 64)", what, k);
+  FRMAP_REQUIRE(B > 0 && D > 0 && D % 4 == 0 && G >= 0, "%s: bad shape B=%d G=%d D=%d", what, B, G, D);
+  FRMAP_REQUIRE(G == 0 || gallery, "%s: null gallery", what);
+  return 0;
+}
+
+// k = 1 in entry mode IS the top-1 match (same kernels, so bit-identical outputs); label_out gets -1
+int frmap_match_topk_fill_labels(int32_t* label_out, int n, hipStream_t st) {
+  if (label_out) hipLaunchKernelGGL(fill_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, label_out, n, -1);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int frmap_match_topk(const float* emb, const float* gallery, const int32_t* labels, int32_t* idx_out, float* dist_out,
+                                int32_t* label_out, void* workspace, int B, int G, int D, int k, void* stream) {
+  if (int rc = topk_check("match_topk", emb, gallery, idx_out, dist_out, workspace, B, G, D, k)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (k == 1 && !labels) {
+    const int rc = frmap_match_top1(emb, gallery, idx_out, dist_out, nullptr, nullptr, INFINITY, workspace, B, G, D, stream);
+    return rc ? rc : frmap_match_topk_fill_labels(label_out, B, st);
+  }
+  if (labels)
+    hipLaunchKernelGGL(match_topk_scan_kernel<true>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels, idx_out, dist_out,
+                       label_out, B, G, D, k);
+  else
+    hipLaunchKernelGGL(match_topk_scan_kernel<false>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels, idx_out, dist_out,
+                       label_out, B, G, D, k);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int frmap_match_topk_packed(const float* emb, const float* gallery, const void* gallery_packed, const float* stat_w,
+                                       const int32_t* labels, int32_t* idx_out, float* dist_out, int32_t* label_out,
+                                       void* workspace, int B, int G, int D, int k, void* stream) {
+  if (int rc = topk_check("match_topk_packed", emb, gallery, idx_out, dist_out, workspace, B, G, D, k)) return rc;
+  FRMAP_REQUIRE(gallery_packed && stat_w, "match_topk_packed: null pointer");
+  FRMAP_REQUIRE(G > 0 && D % 32 == 0, "match_topk_packed: bad shape B=%d G=%d D=%d (G > 0, D %% 32 == 0)", B, G, D);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t recs_b = align256_sz(sizeof(MatchRecK) * (size_t)B * ((G + 255) / 256 * 4));
+  const size_t top1_b = align256_sz(frmap_match_workspace_bytes(B, G));
+  void* split = (char*)workspace + ((recs_b + align256_sz(16 * (size_t)B)) > top1_b ? recs_b + align256_sz(16 * (size_t)B) : top1_b);
+  if (k == 1 && !labels) {
+    const int rc = frmap_match_top1_packed(emb, gallery, gallery_packed, stat_w, idx_out, dist_out, nullptr, nullptr, INFINITY,
+                                           workspace, split, B, G, D, stream);
+    return rc ? rc : frmap_match_topk_fill_labels(label_out, B, st);
+  }
+  const int nslots = (G + 255) / 256 * 4;
+  MatchRecK* recs = (MatchRecK*)workspace;
+  float* stat_a = (float*)((char*)workspace + recs_b);
+  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, stat_a, (_Float16*)split, B, D);
+  const int rc = frmap_match_gemm_f16x3(split, gallery_packed, stat_a, stat_w, recs, B, G, D, st, 1);
+  if (rc) return rc;
+  if (labels)
+    hipLaunchKernelGGL(match_topk_finalize_kernel<true>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels,
+                       (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
+  else
+    hipLaunchKernelGGL(match_topk_finalize_kernel<false>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels,
+                       (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits_out, int32_t* argmax_out,

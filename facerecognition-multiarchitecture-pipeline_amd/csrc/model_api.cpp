@@ -469,22 +469,14 @@ extern "C" int frmap_model_forward(frmap_model* m, const void* x, int x_kind, in
   return frmap_linear_f32(emb, m->cls_wn, nullptr, m->cls_b, (float*)out, B, 512, m->num_classes, 0, r.st);   // :576-580
 }
 
-extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
-                                           const void* gallery_packed, const float* gallery_stat, int G, float thresh,
-                                           int normalize, int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out,
-                                           int32_t* packed_out, float* emb_out, void* workspace, void* stream) {
-  if (int rc = check_ready(m, "model_embed_and_match")) return rc;
-  FRMAP_REQUIRE(x && idx_out && dist_out && workspace, "model_embed_and_match: null pointer");
-  FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_match: a bare trunk has no embedding");
-  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_match: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
-  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_match: bad input kind %d", x_kind);
-  Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
+// The embedding compare_faces matches (src/app.py:44,50-57) for every model kind but the 'cnn' small-gallery fused path: written to
+// emb_out (or a workspace slot) and returned in *emb.  0, or the error code with the error text set.
+static int model_match_embedding(Run& r, const void* x, int x_kind, int H, int W, int normalize, float* emb_out, char* ws, float** emb_ptr) {
+  frmap_model* m = r.m;
+  const int B = r.B;
   const size_t slot = act_slot_bytes(B, H, W);
-  char* ws = (char*)workspace;
-  char* match_ws = ws + frmap_model_workspace_bytes(m, B, H, W);
   if (m->kind >= KIND_BASELINE) {
     // the family forward fills the embedding the matcher needs: its unit-norm copy when `normalize`, else what get_embedding returns
-    const int D = frmap_model_embedding_dim(m);
     const size_t model_ws = frmap_model_workspace_bytes(m, B, H, W);
     float* e0 = (float*)(ws + model_ws - 2 * align256((size_t)B * 512 * sizeof(float)) - 256);
     float* e1 = e0 + align256((size_t)B * 512 * sizeof(float)) / sizeof(float);
@@ -503,25 +495,14 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
     } else {
       frmap_family_forward(r, x, x_kind, H, W, FRMAP_OUT_EMBEDDING, emb, nullptr, ws, nullptr);   // (already unit-norm)
     }
-    if (r.rc) return r.rc;
-    if (gallery_packed && gallery_stat && G >= 512 && D % 32 == 0) {
-      void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
-      return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
-                                     match_ws, split, B, G, D, r.st);
-    }
-    return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
+    *emb_ptr = emb;
+    return r.rc;
   }
   float* scratch0 = (float*)(ws + 3 * slot);
   float* scratch1 = (float*)(ws + 3 * slot + align256((size_t)B * 512 * sizeof(float)));
   const MapOut map = trunk_features(r, x, x_kind, H, W, ws, slot, nullptr);
   if (r.rc) return r.rc;
   const int HW = map.h * map.w;
-  if (m->kind == KIND_CNN && G <= 64) {
-    // pool + (normalise) + compare_faces' scan in one launch, one workgroup per face
-    Traced t(r, "gap_norm_match_kernel<%s>", 2.0 * B * 512 * G, 2.0 * B * HW * 512 + 4.0 * G * 512 + 16.0 * B);
-    return frmap_gap_norm_match(map.p, gallery, emb_out, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, normalize ? 1 : 0,
-                                1e-12f, B, HW, 512, G, m->dtype, r.st);
-  }
   float* emb = emb_out ? emb_out : scratch0;
   if (m->kind == KIND_CNN) {
     r.rc = frmap_avgpool_global(map.p, normalize ? scratch1 : emb, B, HW, 512, m->dtype, r.st);
@@ -530,15 +511,91 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
     Traced t(r, "gap_linear_norm_kernel<%s>", 2.0 * B * 512 * 512, 2.0 * B * HW * 512 + 4.0 * 512 * 512 + 4.0 * B * 512);
     r.rc = frmap_gap_linear_norm(map.p, m->emb_wt, m->bn_scale, m->bn_shift, nullptr, emb, 1e-12f, B, HW, 512, 512, 0, m->dtype, r.st);
   }
-  if (r.rc) return r.rc;
+  *emb_ptr = emb;
+  return r.rc;
+}
+
+extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
+                                           const void* gallery_packed, const float* gallery_stat, int G, float thresh,
+                                           int normalize, int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out,
+                                           int32_t* packed_out, float* emb_out, void* workspace, void* stream) {
+  if (int rc = check_ready(m, "model_embed_and_match")) return rc;
+  FRMAP_REQUIRE(x && idx_out && dist_out && workspace, "model_embed_and_match: null pointer");
+  FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_match: a bare trunk has no embedding");
+  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_match: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
+  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_match: bad input kind %d", x_kind);
+  Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
+  char* match_ws = (char*)workspace + frmap_model_workspace_bytes(m, B, H, W);
+  const int D = m->kind >= KIND_BASELINE ? frmap_model_embedding_dim(m) : 512;
+  if (m->kind == KIND_CNN && G <= 64) {
+    // pool + (normalise) + compare_faces' scan in one launch, one workgroup per face
+    const size_t slot = act_slot_bytes(B, H, W);
+    const MapOut map = trunk_features(r, x, x_kind, H, W, (char*)workspace, slot, nullptr);
+    if (r.rc) return r.rc;
+    const int HW = map.h * map.w;
+    Traced t(r, "gap_norm_match_kernel<%s>", 2.0 * B * 512 * G, 2.0 * B * HW * 512 + 4.0 * G * 512 + 16.0 * B);
+    return frmap_gap_norm_match(map.p, gallery, emb_out, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, normalize ? 1 : 0,
+                                1e-12f, B, HW, 512, G, m->dtype, r.st);
+  }
+  float* emb = nullptr;
+  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
+  if (m->kind >= KIND_BASELINE) {
+    if (gallery_packed && gallery_stat && G >= 512 && D % 32 == 0) {
+      void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
+      return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
+                                     match_ws, split, B, G, D, r.st);
+    }
+    return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
+  }
   if (gallery_packed && gallery_stat && G >= 512) {
     void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
-    Traced t(r, "match_top1 (conv1x1_pp_kernel<F16, MATCH> + finalize)", 6.0 * B * 512 * G, 4.0 * B * 512 + 6.0 * G * 512 + 16.0 * B);
+    Traced t(r, "match_top1 (conv1x1_pp_kernel<F16, MATCH> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 16.0 * B);
     return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
-                                   match_ws, split, B, G, 512, r.st);
+                                   match_ws, split, B, G, D, r.st);
   }
-  Traced t(r, "match_top1 (gemm_nt_f32_kernel + finalize)", 2.0 * B * 512 * G, 4.0 * B * 512 + 4.0 * G * 512 + 16.0 * B);
-  return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, 512, r.st);
+  Traced t(r, "match_top1 (gemm_nt_f32_kernel + finalize)", 2.0 * B * D * G, 4.0 * B * D + 4.0 * G * D + 16.0 * B);
+  return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
+}
+
+extern "C" size_t frmap_model_search_workspace_bytes(const frmap_model* m, int B, int H, int W, int G, int k) {
+  if (!m || B <= 0) return 0;
+  const size_t a = frmap_model_match_workspace_bytes(m, B, H, W, G);
+  const size_t b = frmap_model_workspace_bytes(m, B, H, W) + align256(frmap_match_topk_workspace_bytes(B, G, frmap_model_embedding_dim(m), k));
+  return a > b ? a : b;
+}
+
+extern "C" int frmap_model_embed_and_search(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
+                                            const void* gallery_packed, const float* gallery_stat, const int32_t* labels, int G,
+                                            int k, int normalize, int32_t* idx_out, float* dist_out, int32_t* label_out,
+                                            float* emb_out, void* workspace, void* stream) {
+  if (int rc = check_ready(m, "model_embed_and_search")) return rc;
+  FRMAP_REQUIRE(x && idx_out && dist_out && workspace, "model_embed_and_search: null pointer");
+  FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_search: a bare trunk has no embedding");
+  FRMAP_REQUIRE(k >= 1 && k <= 64, "model_embed_and_search: k=%d out of range (1 <= k <= 64)", k);
+  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_search: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
+  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_search: bad input kind %d", x_kind);
+  if (k == 1 && !labels) {   // the top-1 step itself: same embedding, same match, bit for bit
+    const int rc = frmap_model_embed_and_match(m, x, x_kind, B, H, W, gallery, gallery_packed, gallery_stat, G, INFINITY, normalize,
+                                               idx_out, dist_out, nullptr, nullptr, emb_out, workspace, stream);
+    if (rc || !label_out) return rc;
+    return frmap_match_topk_fill_labels(label_out, B, (hipStream_t)stream);
+  }
+  Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
+  char* match_ws = (char*)workspace + frmap_model_workspace_bytes(m, B, H, W);
+  const int D = frmap_model_embedding_dim(m);
+  if (m->kind == KIND_HYBRID) {   // (checked before anything is launched)
+    int th = ((H + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1, tw = ((W + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1;
+    for (int i = 0; i < 3; ++i) { th = (th - 1) / 2 + 1; tw = (tw - 1) / 2 + 1; }
+    FRMAP_REQUIRE(th * tw == 49, "model_embed_and_search: HybridNet expects a 49-token feature map (224x224 input), got %d", th * tw);
+  }
+  float* emb = nullptr;
+  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
+  if (gallery_packed && gallery_stat && G >= 512 && D % 32 == 0) {
+    Traced t(r, "match_topk (conv1x1_pp_kernel<F16, MATCH_TOPR> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 64.0 * B * k);
+    return frmap_match_topk_packed(emb, gallery, gallery_packed, gallery_stat, labels, idx_out, dist_out, label_out, match_ws, B, G, D, k, r.st);
+  }
+  Traced t(r, "match_topk (exact scan)", 2.0 * B * D * G, 4.0 * B * D + 4.0 * G * D + 8.0 * B * k);
+  return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, match_ws, B, G, D, k, r.st);
 }
 
 extern "C" int frmap_model_trace(frmap_model* m, int enable) {

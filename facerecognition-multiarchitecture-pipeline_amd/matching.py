@@ -17,6 +17,7 @@ The per-entry Python loop of the reference becomes one fp32 MFMA kernel
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -46,7 +47,49 @@ class Gallery:
         self.names = list(names)
         self._buf = emb.to(device).contiguous()          # [capacity][D]; rows >= len(names) are spare
         self._pack = None
+        self._label_names, self._label_of, self._label_ids = [], {}, []
+        self._labels_dev = None                          # [capacity] int32, built on first use of `labels`
+        self._number_labels(self.names)
         self._refresh_pack()
+
+    def _number_labels(self, names) -> None:
+        for n in names:
+            lab = self._label_of.get(n)
+            if lab is None:
+                lab = self._label_of[n] = len(self._label_names)
+                self._label_names.append(n)
+            self._label_ids.append(lab)
+
+    def _labels_current(self) -> None:
+        # derived from `names`: renumber if someone replaced or edited the list behind our back
+        if len(self._label_ids) != len(self.names) or (self.names and self._label_names[self._label_ids[-1]] != self.names[-1]):
+            self._label_names, self._label_of, self._label_ids, self._labels_dev = [], {}, [], None
+            self._number_labels(self.names)
+
+    @property
+    def label_names(self) -> List[str]:
+        """The distinct names in order of first appearance: ``label_names[labels[i]] == names[i]``."""
+        self._labels_current()
+        return self._label_names
+
+    @property
+    def label_ids(self) -> List[int]:
+        """Host copy of `labels`."""
+        self._labels_current()
+        return self._label_ids
+
+    @property
+    def labels(self) -> torch.Tensor:
+        """int32 [G] labels on the gallery's device: each name numbered by its first appearance (the reference's `save_refs` appends
+        one entry per capture, so a person can own several rows); the key of `search_batch(..., by="name")`."""
+        self._labels_current()
+        G = len(self.names)
+        if self._labels_dev is None or self._labels_dev.shape[0] < G or self._labels_dev.device != self._buf.device:
+            cap = max(self._buf.shape[0], G)
+            host = torch.full((cap,), -1, dtype=torch.int32)
+            host[:G] = torch.tensor(self._label_ids, dtype=torch.int32)
+            self._labels_dev = host.to(self._buf.device)
+        return self._labels_dev[:G]
 
     @property
     def matrix(self) -> torch.Tensor:
@@ -80,7 +123,7 @@ class Gallery:
             D = e.numel()
         if e.numel() != D:
             raise ValueError(f"Gallery.append: embedding has {e.numel()} values, the gallery rows have {D}")
-        with torch.cuda.device(self._buf.device):
+        with (torch.cuda.device(self._buf.device) if self._buf.is_cuda else contextlib.nullcontext()):
             if G == self._buf.shape[0]:
                 cap = max(2 * G, 16)
                 cap = (cap + 255) // 256 * 256 if cap >= ops.MATCH_MFMA_MIN_G // 2 else cap
@@ -88,7 +131,14 @@ class Gallery:
                 grown[:G] = self._buf[:G]
                 self._buf, self._pack = grown, None
             self._buf[G].copy_(e.to(self._buf.device), non_blocking=True)
+            self._labels_current()
             self.names.append(name)
+            self._number_labels((name,))
+            if self._labels_dev is not None:
+                if self._labels_dev.shape[0] > G:
+                    self._labels_dev[G].fill_(self._label_ids[G])    # one element; the buffer grows with the rows' capacity
+                else:
+                    self._labels_dev = None
             if self._wants_pack():
                 if self._pack is not None and self._pack.src_ptr == self._buf.data_ptr() and self._pack.G == G:
                     self._pack.update_rows(self.matrix, G, G + 1)
@@ -162,6 +212,42 @@ def _as_gallery(refs, device) -> Gallery:
 def match_batch(emb: torch.Tensor, gallery: Gallery) -> Tuple[torch.Tensor, torch.Tensor]:
     """B×D device embeddings → (int32[B] first-arg-min index, fp32[B] distance), on the device."""
     return ops.match_top1(emb.to(torch.float32), gallery.matrix, prepared=gallery.prepared)
+
+
+def search_batch(emb: torch.Tensor, gallery, k: int, by: str = "entry"):
+    """B×D device embeddings → the k nearest gallery entries (``by="entry"``) or people (``by="name"``: one row per name, its nearest
+    enrolment) under compare_faces' exact distance: ``(idx int32[B, k], dist fp32[B, k], label int32[B, k] | None)`` on the device,
+    ascending, ``(-1, inf, -1)`` past the last candidate.  ``gallery``: a `Gallery` or the reference's refs list."""
+    if by not in ("entry", "name"):
+        raise ValueError(f"search_batch: by must be 'entry' or 'name', got {by!r}")
+    g = _as_gallery(gallery, emb.device if isinstance(emb, torch.Tensor) and emb.is_cuda else "cuda")
+    e = emb.to(torch.float32)
+    if e.dim() == 1:
+        e = e.unsqueeze(0)
+    labels = g.labels if by == "name" else None
+    return ops.match_topk(e, g.matrix if len(g) else None, k, labels=labels, prepared=g.prepared if len(g) else None)
+
+
+def compare_faces_topk(emb, refs, thresh, k: int, by: str = "entry"):
+    """compare_faces' candidate list: at most ``k`` ``(name, dist, idx)`` with ``dist <= thresh``, ascending by (dist, idx).
+    ``by="name"`` lists each person once (their nearest enrolment).  ``refs``: a refs list or a `Gallery`.  Element 0 is
+    compare_faces' answer whenever that is a name (distances are the exact float64-summed ones; on galleries of <= 64 rows
+    compare_faces sums in fp32 and the two can differ in the last bit), and the list is empty when it says "Unknown".
+    One device -> host copy."""
+    if emb is None or refs is None or len(refs) == 0:
+        return []
+    dev = emb.device if emb.is_cuda else torch.device("cuda")
+    g = _as_gallery(refs, dev)
+    e = emb.detach().reshape(1, -1).to(device=dev, dtype=torch.float32)
+    idx, dist, _ = search_batch(e, g, k, by=by)
+    rec = torch.stack((idx[0], dist[0].view(torch.int32))).cpu()      # the one host copy: [2, k]
+    out = []
+    for i, bits in zip(rec[0].tolist(), rec[1].tolist()):
+        d = float(np.array([bits], dtype=np.int32).view(np.float32)[0])
+        if i < 0 or not d <= thresh:
+            break
+        out.append((g.names[i], d, i))
+    return out
 
 
 def get_embedding(face_img, model):

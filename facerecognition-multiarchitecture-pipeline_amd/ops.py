@@ -582,6 +582,57 @@ def match_top1(emb: torch.Tensor, gallery: torch.Tensor, thresh: Optional[float]
     return (idx, dist) if thresh is None else (idx, dist, ids)
 
 
+MATCH_TOPK_MAX = 64
+
+
+def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, labels: Optional[torch.Tensor] = None,
+               prepared: Optional[MatchPack] = None):
+    """Exact top-k gallery search: per probe the ``k`` rows nearest under ``||(e - g) + 1e-6||_2`` (the distance of
+    `match_top1`: fp32 elements, float64 sum of squares), ordered by (distance, row).  With ``labels`` (int32 [G], values >= 0)
+    the k nearest IDENTITIES instead: an identity's distance is the min over its rows, its row the first one attaining it.
+    Returns ``(idx int32[B, k], dist fp32[B, k], label int32[B, k] | None)``; missing entries (k > G, NaN / inf rows) are
+    ``(-1, +inf, -1)``.  k = 1 without labels is `match_top1` (bit-identical).  Path choice as `match_top1`: ``prepared`` galleries of
+    >= `MATCH_MFMA_MIN_G` rows with D % 32 == 0 run on the fp16 MFMA GEMM + exact re-score, everything else on an exact scan."""
+    emb = _dev(emb, "match_topk.emb", torch.float32)
+    if emb.dim() != 2:
+        raise ValueError("match_topk: emb must be [B, D]")
+    B, D = emb.shape
+    k = int(k)
+    if not 1 <= k <= MATCH_TOPK_MAX:
+        raise ValueError(f"match_topk: k={k} out of range (1 <= k <= {MATCH_TOPK_MAX})")
+    G = int(gallery.shape[0]) if gallery is not None else 0
+    gptr = lptr = 0
+    if G > 0:
+        gallery = _dev(gallery, "match_topk.gallery", torch.float32)
+        if gallery.shape[1] != D:
+            raise ValueError(f"match_topk: embedding dim {D} != gallery dim {gallery.shape[1]}")
+        gptr = gallery.data_ptr()
+    if labels is not None:
+        labels = _dev(labels, "match_topk.labels", torch.int32)
+        if tuple(labels.shape) != (G,):
+            raise ValueError(f"match_topk: labels must be int32 [{G}], got {tuple(labels.shape)}")
+        lptr = labels.data_ptr() if G > 0 else 0
+    idx = torch.empty((B, k), dtype=torch.int32, device=emb.device)
+    dist = torch.empty((B, k), dtype=torch.float32, device=emb.device)
+    lab = torch.empty((B, k), dtype=torch.int32, device=emb.device) if labels is not None else None
+    lib = _lib.load()
+    ws = torch.empty((lib.frmap_match_topk_workspace_bytes(B, G, D, k),), dtype=torch.uint8, device=emb.device)
+    if labels is not None and G == 0:
+        lptr = ws.data_ptr()          # (identity mode on an empty gallery: a non-null labels pointer keeps the mode)
+    lbp = lab.data_ptr() if lab is not None else 0
+    if prepared is not None and G >= MATCH_MFMA_MIN_G and D % 32 == 0:
+        if not prepared.matches(gallery):
+            raise ValueError("match_topk: `prepared` was built from a different (or since modified) gallery")
+        prepared.wait_ready()
+        _lib.check(lib.frmap_match_topk_packed(emb.data_ptr(), gptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lptr,
+                                               idx.data_ptr(), dist.data_ptr(), lbp, ws.data_ptr(), B, G, D, k, _stream()),
+                   "match_topk_packed")
+    else:
+        _lib.check(lib.frmap_match_topk(emb.data_ptr(), gptr, lptr, idx.data_ptr(), dist.data_ptr(), lbp, ws.data_ptr(),
+                                        B, G, D, k, _stream()), "match_topk")
+    return idx, dist, lab
+
+
 def gap_linear_norm(fmap: torch.Tensor, wt: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
                     eps: float = 1e-12, want_pre: bool = False, relu: bool = False):
     """ArcFaceNet head in one launch (`face_models.py:573-590`): global average pool of the NHWC trunk map [B,H,W,K] ->
@@ -665,7 +716,7 @@ def arcmargin_eval(x: torch.Tensor, w: torch.Tensor, label: torch.Tensor, s: flo
 for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_small_cin", "stem7x7_maxpool", "stem7x7_maxpool_u8", "conv_igemm",
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
-              "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "gap_norm_match", "cosine_logits",
+              "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
               "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
@@ -772,6 +823,45 @@ class ModelHandle:
                                                              emb.data_ptr() if emb is not None else 0, ws.data_ptr(), _stream()),
                        "model_embed_and_match")
         return idx, dist, ids, pk, emb
+
+    def embed_and_search(self, x: torch.Tensor, gallery: Optional[torch.Tensor], prepared, k: int, labels: Optional[torch.Tensor] = None,
+                         normalize: bool = False, want_emb: bool = False):
+        """One C call: forward + exact top-k search (`match_topk`).  Returns (idx [B, k], dist [B, k], label [B, k] | None, emb | None)."""
+        x = _dev(x, "model_embed_and_search.x")
+        kind, B, H, W = self._geometry(x)
+        k = int(k)
+        if not 1 <= k <= MATCH_TOPK_MAX:
+            raise ValueError(f"embed_and_search: k={k} out of range (1 <= k <= {MATCH_TOPK_MAX})")
+        G = int(gallery.shape[0]) if gallery is not None else 0
+        with torch.cuda.device(x.device):
+            gptr = ppk = pst = lptr = 0
+            if G:
+                gallery = _dev(gallery, "model_embed_and_search.gallery", torch.float32)
+                if gallery.shape[1] != self.embedding_dim:
+                    raise ValueError(f"embed_and_search: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
+                gptr = gallery.data_ptr()
+                if prepared is not None and G >= MATCH_MFMA_MIN_G:
+                    if not prepared.matches(gallery):
+                        raise ValueError("embed_and_search: `prepared` was built from a different (or since modified) gallery")
+                    prepared.wait_ready()
+                    ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
+            if labels is not None:
+                labels = _dev(labels, "model_embed_and_search.labels", torch.int32)
+                if tuple(labels.shape) != (G,):
+                    raise ValueError(f"embed_and_search: labels must be int32 [{G}]")
+            idx = torch.empty((B, k), dtype=torch.int32, device=x.device)
+            dist = torch.empty((B, k), dtype=torch.float32, device=x.device)
+            lab = torch.empty((B, k), dtype=torch.int32, device=x.device) if labels is not None else None
+            emb = torch.empty((B, self.embedding_dim), dtype=torch.float32, device=x.device) if want_emb else None
+            ws = torch.empty((self._lib.frmap_model_search_workspace_bytes(self._h, B, H, W, G, k),), dtype=torch.uint8, device=x.device)
+            if labels is not None:
+                lptr = labels.data_ptr() if G else ws.data_ptr()
+            _lib.check(self._lib.frmap_model_embed_and_search(self._h, x.data_ptr(), kind, B, H, W, gptr, ppk, pst, lptr, G, k,
+                                                              int(bool(normalize)), idx.data_ptr(), dist.data_ptr(),
+                                                              lab.data_ptr() if lab is not None else 0,
+                                                              emb.data_ptr() if emb is not None else 0, ws.data_ptr(), _stream()),
+                       "model_embed_and_search")
+        return idx, dist, lab, emb
 
     def trace(self, enable: bool) -> None:
         _lib.check(self._lib.frmap_model_trace(self._h, int(bool(enable))), "model_trace")

@@ -336,6 +336,28 @@ int frmap_match_top1_packed(const float* emb, const float* gallery, const void* 
                             int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out, int32_t* packed_out,
                             float thresh, void* workspace, void* probe_split, int B, int G, int D, void* stream);
 
+/* Exact top-k gallery search: for each probe the k nearest gallery rows (entry mode, labels == NULL) or identities
+ * (identity mode, labels = int32[G] >= 0: an identity's distance is the min over its rows, its representative the FIRST row
+ * attaining that min) under the exact distance of frmap_match_top1: elements (e_i - g_i) + 1e-6 in fp32, squares summed in
+ * float64, dist = (float)sqrt.  Ordered by (distance, row) ascending (ties go to the lower row, as in the reference loop).
+ *   idx_out int32[B][k], dist_out fp32[B][k], label_out (optional) int32[B][k] (the label in identity mode, -1 in entry mode).
+ *   Rows whose distance is NaN or +inf are never listed; positions past the last listable row / identity are
+ *   (idx -1, dist +inf, label -1), which covers k > G and G == 0.  1 <= k <= 64, D % 4 == 0.
+ *   k == 1 in entry mode runs frmap_match_top1 / frmap_match_top1_packed: bit-identical idx and dist.
+ *   frmap_match_topk scans every row exactly (one wave per probe): for small galleries, or galleries without a pack.
+ *   frmap_match_topk_packed: a gallery prepared by frmap_match_pack_gallery[_rows] (D % 32 == 0, G > 0) on the fp16 MFMA GEMM,
+ *   whose epilogue keeps per probe and 64-row slot the 4 smallest lower bounds (rows + upper bounds) and a bound on the rest of
+ *   the slot; every row that could be among the k nearest within the rounding bound is re-scored exactly.
+ *   workspace: frmap_match_topk_workspace_bytes(B, G, D, k) bytes (records + statistics + the probes' fp16 split; device,
+ *   caller-owned, 256-byte aligned).  Nothing is allocated or synchronised; every launch goes to `stream` (graph-capturable).
+ *   Bad k, shape or pointer arguments are rejected before any launch. */
+size_t frmap_match_topk_workspace_bytes(int B, int G, int D, int k);
+int frmap_match_topk(const float* emb, const float* gallery, const int32_t* labels, int32_t* idx_out, float* dist_out,
+                     int32_t* label_out, void* workspace, int B, int G, int D, int k, void* stream);
+int frmap_match_topk_packed(const float* emb, const float* gallery, const void* gallery_packed, const float* stat_w,
+                            const int32_t* labels, int32_t* idx_out, float* dist_out, int32_t* label_out,
+                            void* workspace, int B, int G, int D, int k, void* stream);
+
 /* The tail of the ResNet-18 ('cnn') embed-and-match step for small galleries in ONE launch, one workgroup per face:
  * AdaptiveAvgPool2d(1) of the trunk map (face_models.py:100) -> optional F.normalize(eps) -> compare_faces' scan
  * (src/app.py:58-64) exactly as frmap_match_top1 does it for G <= 64.
@@ -396,6 +418,12 @@ int frmap_arcmargin_eval(const float* x, const float* w, const int64_t* label, f
  *                            (frmap_match_pack_gallery; may be NULL) put galleries of >= 512 rows on the MFMA pipe; 'cnn' with
  *                            G <= 64 pools, normalises and matches in one launch.  emb_out: optional fp32 [B][512].
  *                            workspace: frmap_model_match_workspace_bytes(m, B, H, W, G).
+ *   frmap_model_embed_and_search  forward + exact top-k search (frmap_match_topk[_packed]): the embedding as
+ *                            frmap_model_embed_and_match forms it (normalised if asked), then the k nearest rows (labels == NULL)
+ *                            or identities (labels int32[G]) of the fp32 gallery [G][D]; outputs as frmap_match_topk.  k == 1 with
+ *                            labels == NULL is frmap_model_embed_and_match (same idx and dist).  gallery_packed / gallery_stat
+ *                            (may be NULL) put galleries of >= 512 rows on the MFMA pipe.  emb_out: optional fp32 [B][D].
+ *                            workspace: frmap_model_search_workspace_bytes(m, B, H, W, G, k).
  *   frmap_model_trace / _trace_read  per-launch HIP-event timing of subsequent forwards (kernel label, algorithmic FLOPs and
  *                            bytes, microseconds) for roofline reports; read synchronises the recorded events and clears them.
  * ------------------------------------------------------------------------------------------- */
@@ -425,6 +453,11 @@ int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_kind, int B
                                 const void* gallery_packed, const float* gallery_stat, int G, float thresh, int normalize,
                                 int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out, int32_t* packed_out,
                                 float* emb_out, void* workspace, void* stream);
+size_t frmap_model_search_workspace_bytes(const frmap_model* m, int B, int H, int W, int G, int k);
+int frmap_model_embed_and_search(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
+                                 const void* gallery_packed, const float* gallery_stat, const int32_t* labels, int G,
+                                 int k, int normalize, int32_t* idx_out, float* dist_out, int32_t* label_out,
+                                 float* emb_out, void* workspace, void* stream);
 int frmap_model_trace(frmap_model* m, int enable);
 int frmap_model_trace_read(frmap_model* m, frmap_trace_record* out, int max_records);
 void frmap_model_destroy(frmap_model* m);
