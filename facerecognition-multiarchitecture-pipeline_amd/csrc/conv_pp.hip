@@ -60,6 +60,25 @@ struct PPParams {
   void* m_recs;                 // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
   int m_G, m_D;
 };
+// conv1x1_pp_kernel<..., MATCH_HIST> (verification counts) takes these: exact operands, labels, the threshold table, the counts.
+// A type of its own, so that every other instantiation keeps PPParams' layout (and its kernarg offsets) unchanged.
+struct PPHistParams : PPParams {
+  const float* h_A;             // fp32 [M][D] (the probes)
+  const float* h_B;             // fp32 [G][D] (the gallery rows)
+  const int32_t* h_lab_a;
+  const int32_t* h_lab_b;
+  const float* h_tab;           // t [T] | lo [T] | hi [T]
+  unsigned long long* h_hist;   // [2][T + 1]
+  unsigned long long* h_rescored;
+  int h_row0, h_T;
+};
+template <int MM> struct PPArg { using type = PPParams; };
+template <> struct PPArg<MATCH_HIST> { using type = PPHistParams; };
+// self-mode verification counts: about half the tiles (those on or below the diagonal) exit at once.  pp_xcd_remap gives each XCD
+// one contiguous band of tile rows, so the top band's XCD would keep ~all of its work while the bottom band's has ~none; there the
+// tiles are dealt round-robin instead (block b runs on XCD b % 8), which gives every XCD the same share of live tiles.
+__device__ __forceinline__ bool pp_hist_self(const PPParams&) { return false; }
+__device__ __forceinline__ bool pp_hist_self(const PPHistParams& p) { return p.h_row0 >= 0; }
 
 __device__ __attribute__((aligned(4096))) unsigned int g_pp_zero[1024];
 
@@ -510,8 +529,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p) {
 // operands, each lane forms the expanded squared F.pairwise_distance of its 16 gallery rows with its error band, the column's
 // four lanes meet through two shuffles, one candidate record per probe and 64-row slot (match_epilogue_records).
 // MM = MATCH_TOPR: the same GEMM with the top-k search's records (match_epilogue_topr: R = 4 rows per slot + the rest bound).
+// MM = MATCH_HIST: verification counts (match_epilogue_hist): certain pairs binned in LDS, the rest queued per wave in LDS and
+// re-scored exactly by the wave itself (verify_drain_queue), then one 64-bit atomicAdd per non-zero bin of the workgroup.  In self
+// mode a tile with no pair above the diagonal exits before its first DMA.
 template <typename TT, int MI, int WM, int KS, int MM = MATCH_NONE>
-__global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const PPParams p) {
+__global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg<MM>::type p) {
   constexpr int NI = 4, WN = KS == 2 ? 2 : 8 / WM;
   constexpr int CAP = (KS == 2 ? 2 : WM) * MI * 16;          // pixels of a tile
   constexpr int BN = WN * 64, WB = BN * 64;
@@ -534,9 +556,12 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const PPParams p) {
   const int gbase = KS == 2 ? grp * GSZ : 0;
   const int lr = lane & 15, g = lane >> 4;
 
-  const int L = pp_xcd_remap(blockIdx.x, gridDim.x);
+  const int L = pp_hist_self(p) ? (int)blockIdx.x : pp_xcd_remap(blockIdx.x, gridDim.x);
   const int mt = L / p.ntiles, nt = L - mt * p.ntiles;
   const int m0 = mt * p.tile_px, mend = min(m0 + p.tile_px, p.M);
+  if constexpr (MM == MATCH_HIST) {
+    if (p.h_row0 >= 0 && nt * BN + BN - 1 <= p.h_row0 + m0) return;   // (whole workgroup, before any DMA or barrier)
+  }
   const int nst = p.nchunks / KS;            // k-steps this group walks (KS = 2: chunk = grp + 2 * step)
 
   // ---- per-lane DMA sources: gather piece e of this wave = piece (gw + GW * e) of the image: lane -> tile pixel piece * 16 + lane / 4
@@ -639,7 +664,25 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const PPParams p) {
     __syncthreads();
     if (grp == 1) return;
   }
-  if constexpr (MM != MATCH_NONE) {
+  if constexpr (MM == MATCH_HIST) {
+    unsigned* hist = (unsigned*)(smem + VERIFY_LDS_HIST);
+    float* tl = (float*)(smem + VERIFY_LDS_T);
+    const int T = p.h_T, nb = 2 * (T + 1);
+    for (int i = tid; i < nb; i += 512) hist[i] = 0u;
+    for (int i = tid; i < 3 * T; i += 512) tl[(i / T) * VERIFY_MAX_T + i % T] = p.h_tab[i];
+    __syncthreads();
+    const int b_base = m0 + mslice * (MI * 16), n0 = nt * BN + wn * 64;
+    unsigned short* queue = (unsigned short*)(smem + VERIFY_LDS_Q) + wave * VERIFY_QCAP;
+    const int cnt = match_epilogue_hist<MI>(acc, b_base, mend, n0, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.h_lab_a, p.h_lab_b,
+                                            p.h_row0, (const float*)(smem + VERIFY_LDS_LO), (const float*)(smem + VERIFY_LDS_HI),
+                                            hist, queue, T, lane);
+    verify_drain_queue(queue, cnt, b_base, n0, p.h_A, p.h_B, p.h_lab_a, p.h_lab_b, p.m_D, tl, hist, T, lane);
+    if (lane == 0 && cnt) atomicAdd(p.h_rescored, (unsigned long long)cnt);
+    __syncthreads();
+    for (int i = tid; i < nb; i += 512)
+      if (hist[i]) atomicAdd(p.h_hist + i, (unsigned long long)hist[i]);
+    return;
+  } else if constexpr (MM != MATCH_NONE) {
     match_epilogue<MM, MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
                            p.m_recs, lane);
     return;
@@ -1096,7 +1139,7 @@ int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shi
 // (returns the layout: 1 = 224 px x 256 ch, 2 = 448 px x 128 ch, 3 = 224 px x 128 ch split-K)
 // ------------------------------------------------------------------------------------------------
 template <typename TT, int WM, int KS, int MM = MATCH_NONE>
-static int pp1_launch(const PPParams& p, hipStream_t st) {
+static int pp1_launch(const typename PPArg<MM>::type& p, hipStream_t st) {
   constexpr int MI = 7;
   auto kern = conv1x1_pp_kernel<TT, MI, WM, KS, MM>;
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
@@ -1107,6 +1150,7 @@ static int pp1_launch(const PPParams& p, hipStream_t st) {
   const int xch = KS == 2 ? 4 * MI * 4 * 1024 : 0;
   if (lds < scratch) lds = scratch;
   if (lds < xch) lds = xch;
+  if (MM == MATCH_HIST && lds < VERIFY_LDS_GEMM) lds = VERIFY_LDS_GEMM;
   hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -1201,6 +1245,35 @@ int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const f
   p.ntiles = Gpad / (wide ? 128 : 256);
   const int rc = topr ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
                       : (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st));
+  return rc ? rc : 1;
+}
+
+// verification counts on the same GEMM (conv1x1_pp_kernel<F16, ..., MATCH_HIST>): the probes are A (P rows), the packed gallery B
+int frmap_verify_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
+                         const FrmapVerifyGemm& v, int P, int Q, int D, hipStream_t st) {
+  static int on = -1;
+  if (on < 0) on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_MATCH_PP", 1);
+  const int K3 = 3 * D, Gpad = (Q + 255) / 256 * 256;
+  if (!on || K3 % 32 || K3 > 16384 || P <= 0 || Q <= 0 || v.T < 1 || v.T > VERIFY_MAX_T) return 0;
+  PPHistParams p;
+  memset(&p, 0, sizeof(p));
+  p.in = probes3; p.wpk = gallery_packed;
+  p.N = P; p.Hi = 1; p.Wi = 1; p.Cin = K3; p.Cout = Gpad;
+  p.M = P; p.HoWo = 1; p.Hp = 1; p.Wp = 1;
+  p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
+  p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u); p.dWo2 = frmap_div_make(1u);
+  p.nchunks = K3 / 32; p.ds_stride = 1;
+  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_G = Q; p.m_D = D;
+  p.h_A = v.A; p.h_B = v.B; p.h_lab_a = v.lab_a; p.h_lab_b = v.lab_b; p.h_tab = v.tab; p.h_hist = v.hist; p.h_rescored = v.rescored;
+  p.h_row0 = v.row0; p.h_T = v.T;
+  // tile choice as frmap_match_gemm_pp
+  const long long t1 = ((P + 223) / 224) * (long long)(Gpad / 256), t2 = ((P + 447) / 448) * (long long)(Gpad / 128);
+  const long long r1 = (t1 + 255) / 256, r2 = (t2 + 255) / 256;
+  const bool wide = r2 < r1 || (r2 == r1 && t2 > t1);
+  p.tile_px = wide ? 448 : 224;
+  p.mtiles = (P + p.tile_px - 1) / p.tile_px;
+  p.ntiles = Gpad / (wide ? 128 : 256);
+  const int rc = wide ? pp1_launch<F16, 4, 1, MATCH_HIST>(p, st) : pp1_launch<F16, 2, 1, MATCH_HIST>(p, st);
   return rc ? rc : 1;
 }
 

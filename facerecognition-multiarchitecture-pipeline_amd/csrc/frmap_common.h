@@ -149,7 +149,7 @@ __device__ __forceinline__ void match_epilogue_records(const f32x4_t (&acc)[MI][
 // tau = the k-th smallest listed U (per distinct label in identity mode) and re-scores exactly every listed row with L <= tau and
 // every row of a slot whose rest <= tau.  An identity enrolled up to R times in one slot never forces a whole-slot re-score.
 // ------------------------------------------------------------------------------------------------
-enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2 };
+enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2, MATCH_HIST = 3 };   // MATCH_HIST: verification counts
 constexpr int MATCH_R = 4;
 struct __attribute__((aligned(16))) MatchRecK {   // 64 bytes
   float lo[MATCH_R];
@@ -221,6 +221,181 @@ __device__ __forceinline__ void match_epilogue_topr(const f32x4_t (&acc)[MI][4],
       out[b] = r;
     }
     __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ||(a - g) + eps||_2^2 the way F.pairwise_distance forms its elements (fp32 subtract, fp32 add of eps), squares summed in
+// float64 by the whole wave: the result does not depend on a summation order, identical rows give identical values, and it
+// is within 2^-24 of what any fp32 summation of the same 512 squares returns.  Every lane gets the sum.
+__device__ __forceinline__ double match_exact_d2(const float* __restrict__ a, const float* __restrict__ g, int D, int lane) {
+  double s2 = 0.0;
+  for (int k = lane * 4; k < D; k += 256) {
+    const f32x4_t av = *(const f32x4_t*)(a + k), gv = *(const f32x4_t*)(g + k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float d = (av[j] - gv[j]) + 1e-6f;
+      s2 += (double)d * (double)d;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+  return s2;
+}
+
+// NB pairs at once, each summed in exactly match_exact_d2's order (bit-identical results); the NB loads of a k-step are in flight
+// together, which is what a wave that re-scores a queue of unrelated pairs (L2 latency, no reuse) needs.
+template <int NB>
+__device__ __forceinline__ void match_exact_d2_n(const float* const (&a)[NB], const float* const (&g)[NB], int D, int lane,
+                                                 double (&out)[NB]) {
+#pragma unroll
+  for (int q = 0; q < NB; ++q) out[q] = 0.0;
+  for (int k = lane * 4; k < D; k += 256) {
+    f32x4_t av[NB], gv[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) { av[q] = *(const f32x4_t*)(a[q] + k); gv[q] = *(const f32x4_t*)(g[q] + k); }
+#pragma unroll
+    for (int q = 0; q < NB; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float d = (av[q][j] - gv[q][j]) + 1e-6f;
+        out[q] += (double)d * (double)d;
+      }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int q = 0; q < NB; ++q) out[q] += __shfl_xor(out[q], o, 64);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Verification counts (frmap_verify_counts[_packed], head_match.hip): every counted pair (i, j) of A x B falls in bin
+// k = the first threshold with (float)sqrt(d2) <= t_k (T if none: NaN / inf / beyond the grid), per class (0 = genuine, 1 = impostor).
+// Bins are counted per workgroup in LDS (u32 [2][T + 1]) and flushed with one 64-bit atomicAdd per non-zero bin.
+// ------------------------------------------------------------------------------------------------
+constexpr int VERIFY_MAX_T = 2048;
+// LDS layout of the verify workgroups (bytes): histogram u32 [2][T + 1] | t [T] | lo [T] | hi [T] | the GEMM path's per-wave queues
+constexpr int VERIFY_LDS_HIST = 0;
+constexpr int VERIFY_LDS_T = 16400;                               // >= 8 * (VERIFY_MAX_T + 1), 16-aligned
+constexpr int VERIFY_LDS_LO = VERIFY_LDS_T + 4 * VERIFY_MAX_T;
+constexpr int VERIFY_LDS_HI = VERIFY_LDS_LO + 4 * VERIFY_MAX_T;
+constexpr int VERIFY_LDS_Q = VERIFY_LDS_HI + 4 * VERIFY_MAX_T;
+constexpr int VERIFY_QCAP = 7 * 16 * 64;                          // pairs of one match-GEMM wave (MI = 7): the queue never overflows
+constexpr int VERIFY_LDS_GEMM = VERIFY_LDS_Q + 8 * VERIFY_QCAP * 2;
+
+// first k in [0, T) with v <= tab[k] (tab ascending), T if none (NaN: T)
+__device__ __forceinline__ int verify_bin(const float* tab, int T, float v) {
+  int lo = 0, hi = T;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (v <= tab[mid]) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+// bin NB pairs whose exact d2 every lane holds: lane q < NB takes pair q (valid[q] false: skipped)
+template <int NB>
+__device__ __forceinline__ void verify_bin_pairs(const double (&d2)[NB], const bool (&valid)[NB], const bool (&gen)[NB],
+                                                 const float* t_lds, unsigned* hist_lds, int T, int lane) {
+  double d = 0.0;
+  bool v = false, ge = false;
+#pragma unroll
+  for (int q = 0; q < NB; ++q)
+    if (lane == q) { d = d2[q]; v = valid[q]; ge = gen[q]; }
+  if (v) {
+    const float dist = (float)sqrt(d);
+    atomicAdd(hist_lds + (ge ? 0 : T + 1) + verify_bin(t_lds, T, dist), 1u);
+  }
+}
+
+// Epilogue of conv1x1_pp_kernel<..., MATCH_HIST>: pair (probe b = A row, gallery row n = B row) has L <= d2 <= U (bounds as
+// match_epilogue_topr).  With the host's brackets (d2 <= lo_k => dist <= t_k, d2 > hi_k => dist > t_k, both ascending) the pair's
+// bin is certain when kU = the first k with U <= lo_k has L > hi_{kU - 1} (or kU = 0), with L and U finite: then d2 <= lo_kU and
+// d2 > hi_k for every k < kU.  Certain pairs are binned at once; the others go to this wave's LDS queue (u16 = the pair's place in
+// the wave's 112 x 64 block) and are re-scored with match_exact_d2 by verify_drain_queue.  Returns the queue length (wave-uniform).
+template <int MI>
+__device__ __forceinline__ int match_epilogue_hist(const f32x4_t (&acc)[MI][4], int b_base, int b_end, int n0, int G, int D, int M,
+                                                   const float* __restrict__ stat_a, const float* __restrict__ stat_w,
+                                                   const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b, int row0,
+                                                   const float* lo_lds, const float* hi_lds, unsigned* hist_lds,
+                                                   unsigned short* queue, int T, int lane) {
+  const int lr = lane & 15, g = lane >> 4;
+  const float eps = 1e-6f, kf = (float)D, keps = kf * eps * eps, kap = match_kappa(3 * D);
+  int cnt = 0;
+  // a lane's certain pairs mostly land in the same bin as the one before (every lane of the wave, often in the same bin): runs
+  // are merged in registers and added with one LDS atomic per run instead of one per pair (64-way serialised on a shared bin)
+  int rk = 0;
+  unsigned rn = 0u;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int b = b_base + mi * 16 + lr;
+    const f32x4_t sa = *(const f32x4_t*)(stat_a + 4 * (size_t)min(b, M - 1));
+    const float a2 = sa[0], as = sa[1], ai = sa[2], ab = sa[3] + keps;
+    const int la = lab_a[min(b, M - 1)];
+    const int nmin = row0 >= 0 ? row0 + b + 1 : 0;   // self mode: only rows after the probe's own
+    // re-read the gallery rows' statistics and labels per probe row: opaque copies of the pointers keep the compiler from merging
+    // the 16 rows' loads of all MI probe rows into one set held across the whole epilogue (~80 registers next to acc)
+    const float* sw_p = stat_w;
+    const int32_t* lb_p = lab_b;
+    asm volatile("" : "+s"(sw_p), "+s"(lb_p));
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = n0 + ni * 16 + 4 * g + j;
+        const f32x4_t sw = *(const f32x4_t*)(sw_p + 4 * (size_t)min(n, G - 1));
+        const float d2 = a2 + sw[0] - 2.f * (acc[mi][ni][j] * ai * sw[2]) + 2.f * eps * (as - sw[1]) + keps;
+        const float dl = kap * (ab + sw[3]);
+        const float L = d2 - dl, U = d2 + dl;
+        const bool valid = n < G && b < b_end && n >= nmin;
+        bool sure = false;
+        if (valid) {
+          const int k = verify_bin(lo_lds, T, U);
+          sure = __builtin_isfinite(L) && __builtin_isfinite(U) && (k == 0 || L > hi_lds[k - 1]);
+          if (sure) {
+            const int key = (la == lb_p[min(n, G - 1)] ? 0 : T + 1) + k;
+            if (key != rk) {
+              if (rn) atomicAdd(hist_lds + rk, rn);
+              rk = key; rn = 0u;
+            }
+            ++rn;
+          }
+        }
+        const unsigned long long m = __ballot(valid && !sure);
+        if (valid && !sure) {
+          const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          queue[pos] = (unsigned short)(((mi * 16 + lr) << 6) | (ni * 16 + 4 * g + j));
+        }
+        cnt += __popcll(m);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (rn) atomicAdd(hist_lds + rk, rn);
+  return cnt;
+}
+
+// re-score this wave's queued pairs exactly, 8 at a time, and bin them
+__device__ __forceinline__ void verify_drain_queue(const unsigned short* queue, int cnt, int b_base, int n0, const float* __restrict__ A,
+                                                   const float* __restrict__ B, const int32_t* __restrict__ lab_a,
+                                                   const int32_t* __restrict__ lab_b, int D, const float* t_lds, unsigned* hist_lds,
+                                                   int T, int lane) {
+  constexpr int NB = 8;
+  for (int q0 = 0; q0 < cnt; q0 += NB) {
+    const float* pa[NB];
+    const float* pb[NB];
+    bool valid[NB], gen[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      valid[q] = q0 + q < cnt;
+      const int e = queue[valid[q] ? q0 + q : q0];
+      const int b = b_base + (e >> 6), n = n0 + (e & 63);
+      pa[q] = A + (size_t)b * D; pb[q] = B + (size_t)n * D;
+      gen[q] = lab_a[b] == lab_b[n];
+    }
+    double d2[NB];
+    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
+    verify_bin_pairs<NB>(d2, valid, gen, t_lds, hist_lds, T, lane);
   }
 }
 
@@ -461,6 +636,21 @@ int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const f
 // match GEMM on the 1x1 MFMA kernel (conv_igemm.hip), see frmap_match_top1_packed / frmap_match_topk_packed
 int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
                            void* recs, int B, int G, int D, hipStream_t st, int topr);
+// verification counts on the match GEMM (conv1x1_pp_kernel<..., MATCH_HIST>): 1 = launched, 0 = not taken, < 0 = error.
+// tab: t [T] | lo [T] | hi [T] (fp32, device); hist: u64 [2][T + 1] accumulated into; rescored: u64 += pairs re-scored exactly
+struct FrmapVerifyGemm {
+  const float* A;           // fp32 [P][D]
+  const float* B;           // fp32 [Q][D]
+  const int32_t* lab_a;
+  const int32_t* lab_b;
+  const float* tab;
+  unsigned long long* hist;
+  unsigned long long* rescored;
+  int row0;                 // -1: cross mode; else A = rows [row0, row0 + P) of B, pairs with row0 + i < j
+  int T;
+};
+int frmap_verify_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
+                         const FrmapVerifyGemm& v, int P, int Q, int D, hipStream_t st);
 // label_out[0 .. n) = -1 (frmap_match_topk's k = 1 entry-mode outputs; head_match.hip)
 int frmap_match_topk_fill_labels(int32_t* label_out, int n, hipStream_t st);
 #define FRMAP_REQUIRE(cond, ...)        \

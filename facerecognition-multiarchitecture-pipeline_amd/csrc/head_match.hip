@@ -4,6 +4,7 @@
 //   frmap_l2_normalize_f32  F.normalize(p=2, dim=1, eps)               face_models.py:179,525,590
 //   frmap_match_top1        compare_faces' arg-min over the gallery    app.py:58-63
 //   frmap_match_topk        the k nearest rows / identities, exact      (top-k search)
+//   frmap_verify_counts     exact genuine / impostor pair counts per threshold (verification ROC)
 //   frmap_cosine_logits     class-centre cosine logits + arg-max       hyperparameter_tuning.py:1038-1046
 //   frmap_arcmargin_eval    ArcMarginProduct.forward, eval mode        face_models.py:351-429
 //
@@ -294,23 +295,7 @@ __global__ void fill_u64_kernel(unsigned long long* p, int n, unsigned long long
   if (i < n) p[i] = v;
 }
 
-// ||(a - g) + eps||_2^2 the way F.pairwise_distance forms its elements (fp32 subtract, fp32 add of eps), squares summed in
-// float64 by the whole wave: the result does not depend on a summation order, identical rows give identical values, and it
-// is within 2^-24 of what any fp32 summation of the same 512 squares returns.  Every lane gets the sum.
-__device__ __forceinline__ double match_exact_d2(const float* __restrict__ a, const float* __restrict__ g, int D, int lane) {
-  double s2 = 0.0;
-  for (int k = lane * 4; k < D; k += 256) {
-    const f32x4_t av = *(const f32x4_t*)(a + k), gv = *(const f32x4_t*)(g + k);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = (av[j] - gv[j]) + 1e-6f;
-      s2 += (double)d * (double)d;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-  return s2;
-}
+// match_exact_d2 (the exact distance every re-score uses) lives in frmap_common.h.
 
 // One wave per probe.  Reads the probe's candidate records (frmap_common.h: MatchRec [nslots][B], slot = slot_w consecutive
 // gallery rows), takes ug = min over slots of `up`, and re-scores with the exact distance every slot whose lo1 <= ug: the
@@ -1242,6 +1227,192 @@ extern "C" int frmap_match_topk_packed(const float* emb, const float* gallery, c
                        (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
   FRMAP_LAUNCH_CHECK();
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Verification counts (frmap_verify_counts[_packed]): for every counted pair (i, j) of A x B (cross mode: all; self mode: A = rows
+// [row0, row0 + P) of B, pairs with row0 + i < j) and every threshold t_k, whether (float)sqrt(match_exact_d2) <= t_k, split by
+// genuine (label_a[i] == label_b[j]) and impostor.  Pairs are counted per bin (first k with dist <= t_k, T if none) and the
+// finalize turns the bins into cumulative counts, so every output is an exact integer independent of path, tiling and launch order.
+// workspace: bins u64 [2][T + 1] | rescored u64, bad-threshold flag | table t [T], lo [T], hi [T] | probe statistics [P][4] | probe
+// split fp16 [P][3 D].
+// ------------------------------------------------------------------------------------------------
+struct VerifyWs {
+  unsigned long long* hist;
+  unsigned long long* misc;   // [0] pairs re-scored, [1] 1 = the thresholds broke the contract
+  float* tab;
+  float* stat_a;
+  void* split;
+};
+static VerifyWs verify_ws(void* ws, int P, int D, int T) {
+  VerifyWs w;
+  char* c = (char*)ws;
+  w.hist = (unsigned long long*)c; c += align256_sz(16 * (size_t)(T + 1));
+  w.misc = (unsigned long long*)c; c += 256;
+  w.tab = (float*)c; c += align256_sz(12 * (size_t)T);
+  w.stat_a = (float*)c; c += align256_sz(16 * (size_t)P);
+  w.split = c;
+  return w;
+}
+
+// one workgroup: zero the bins, check the thresholds (finite, >= 0, strictly ascending) and bracket each one in d2 space:
+//   lo_k = the largest fp32 <= t_k^2:          d2 <= lo_k  =>  sqrt(d2) <= t_k (t_k^2 is exact in float64)  =>  (float)sqrt(d2) <= t_k
+//   hi_k = the smallest fp32 >= next_up(t_k)^2: d2 > hi_k   =>  sqrt(d2) >= next_up(t_k)                    =>  (float)sqrt(d2) > t_k
+__global__ __launch_bounds__(1024) void verify_prep_kernel(const float* __restrict__ thr, int T, float* __restrict__ tab,
+                                                           unsigned long long* __restrict__ hist, unsigned long long* __restrict__ misc) {
+  __shared__ int bad;
+  const int tid = threadIdx.x;
+  if (tid == 0) bad = 0;
+  for (int i = tid; i < 2 * (T + 1); i += 1024) hist[i] = 0ull;
+  __syncthreads();
+  for (int k = tid; k < T; k += 1024) {
+    const float t = thr[k];
+    const bool ok = __builtin_isfinite(t) && t >= 0.f && (k == 0 || t > thr[k - 1]);
+    if (!ok) atomicOr(&bad, 1);
+    const float u = nextafterf(t, INFINITY);
+    tab[k] = t;
+    tab[T + k] = __double2float_rd((double)t * (double)t);
+    tab[2 * T + k] = __double2float_ru((double)u * (double)u);
+  }
+  __syncthreads();
+  if (tid == 0) { misc[0] = 0ull; misc[1] = (unsigned long long)bad; }
+}
+
+// Exact scan: one workgroup = VS_PB rows of A x VS_QB rows of B; each wave scores 8 pairs at a time with match_exact_d2's arithmetic
+// and bins them in the workgroup's LDS histogram.
+constexpr int VS_PB = 8, VS_QB = 512;
+__global__ __launch_bounds__(256) void verify_scan_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                          const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b,
+                                                          int P, int Q, int D, int row0, const float* __restrict__ tab, int T,
+                                                          unsigned long long* __restrict__ hist_g) {
+  __shared__ unsigned hist[2 * (VERIFY_MAX_T + 1)];
+  __shared__ float tl[VERIFY_MAX_T];
+  const int i0 = blockIdx.x * VS_PB, j0 = blockIdx.y * VS_QB;
+  const int jlast = min(j0 + VS_QB, Q) - 1;
+  if (row0 >= 0 && jlast <= row0 + i0) return;     // self mode: nothing above the diagonal here
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = 2 * (T + 1);
+  for (int i = tid; i < nb; i += 256) hist[i] = 0u;
+  for (int i = tid; i < T; i += 256) tl[i] = tab[i];
+  __syncthreads();
+  constexpr int NB = 8;
+  for (int base = wave * NB; base < VS_PB * VS_QB; base += 4 * NB) {
+    const float* pa[NB];
+    const float* pb[NB];
+    bool valid[NB], gen[NB], any = false;
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int i = i0 + (base + q) / VS_QB, j = j0 + (base + q) % VS_QB;
+      valid[q] = i < P && j < Q && (row0 < 0 || row0 + i < j);
+      any |= valid[q];
+      const int ic = min(i, P - 1), jc = min(j, Q - 1);
+      pa[q] = A + (size_t)ic * D; pb[q] = B + (size_t)jc * D;
+      gen[q] = lab_a[ic] == lab_b[jc];
+    }
+    if (!any) continue;                               // (wave-uniform)
+    double d2[NB];
+    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
+    verify_bin_pairs<NB>(d2, valid, gen, tl, hist, T, lane);
+  }
+  __syncthreads();
+  for (int i = tid; i < nb; i += 256)
+    if (hist[i]) atomicAdd(hist_g + i, (unsigned long long)hist[i]);
+}
+
+// accepted[c][k] = sum of bins 0 .. k of class c (one workgroup per class, 2 bins per thread, Hillis-Steele over the threads);
+// every output all-ones when the thresholds broke the contract
+__global__ __launch_bounds__(1024) void verify_finalize_kernel(const unsigned long long* __restrict__ hist,
+                                                               const unsigned long long* __restrict__ misc, int T,
+                                                               unsigned long long* __restrict__ accepted,
+                                                               unsigned long long* __restrict__ rescored_out) {
+  __shared__ unsigned long long s[1024];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const unsigned long long* h = hist + (size_t)c * (T + 1);
+  const int k0 = 2 * tid;
+  const unsigned long long v0 = k0 < T ? h[k0] : 0ull, v1 = k0 + 1 < T ? h[k0 + 1] : 0ull;
+  s[tid] = v0 + v1;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const unsigned long long add = tid >= o ? s[tid - o] : 0ull;
+    __syncthreads();
+    s[tid] += add;
+    __syncthreads();
+  }
+  const unsigned long long before = tid ? s[tid - 1] : 0ull;
+  const bool bad = misc[1] != 0ull;
+  if (k0 < T) accepted[(size_t)c * T + k0] = bad ? ~0ull : before + v0;
+  if (k0 + 1 < T) accepted[(size_t)c * T + k0 + 1] = bad ? ~0ull : before + v0 + v1;
+  if (c == 0 && tid == 0 && rescored_out) *rescored_out = bad ? ~0ull : misc[0];
+}
+
+extern "C" size_t frmap_verify_workspace_bytes(int P, int Q, int D, int T) {
+  (void)Q;
+  const size_t p = P > 0 ? (size_t)P : 0, d = D > 0 ? (size_t)D : 0;
+  const size_t t = T < 1 ? 1 : T > VERIFY_MAX_T ? VERIFY_MAX_T : (size_t)T;
+  return align256_sz(16 * (t + 1)) + 256 + align256_sz(12 * t) + align256_sz(16 * p) + align256_sz(6 * p * d) + 256;
+}
+
+static int verify_check(const char* what, const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q,
+                        int D, int a_row0, const float* thresholds, int T, uint64_t* accepted_out, void* workspace) {
+  FRMAP_REQUIRE(thresholds && accepted_out && workspace, "%s: null pointer", what);
+  FRMAP_REQUIRE(T >= 1 && T <= VERIFY_MAX_T, "%s: T=%d thresholds out of range (1 <= T <= %d)", what, T, VERIFY_MAX_T);
+  FRMAP_REQUIRE(P >= 0 && Q >= 0 && D > 0 && D % 4 == 0, "%s: bad shape P=%d Q=%d D=%d (D %% 4 == 0)", what, P, Q, D);
+  FRMAP_REQUIRE(P == 0 || (a && label_a), "%s: null A or its labels", what);
+  FRMAP_REQUIRE(Q == 0 || (b && label_b), "%s: null B or its labels", what);
+  FRMAP_REQUIRE(a_row0 == -1 || (a_row0 >= 0 && (long long)a_row0 + P <= Q),
+                "%s: a_row0=%d with P=%d is not a block of B's %d rows (-1: cross mode)", what, a_row0, P, Q);
+  return 0;
+}
+
+static int verify_finish(const VerifyWs& w, int T, uint64_t* accepted_out, uint64_t* rescored_out, hipStream_t st) {
+  hipLaunchKernelGGL(verify_finalize_kernel, dim3(2), dim3(1024), 0, st, (const unsigned long long*)w.hist,
+                     (const unsigned long long*)w.misc, T, (unsigned long long*)accepted_out, (unsigned long long*)rescored_out);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+static int verify_scan(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D, int a_row0,
+                       const VerifyWs& w, int T, hipStream_t st) {
+  if (P > 0 && Q > 0)
+    hipLaunchKernelGGL(verify_scan_kernel, dim3((P + VS_PB - 1) / VS_PB, (Q + VS_QB - 1) / VS_QB), dim3(256), 0, st, a, b, label_a,
+                       label_b, P, Q, D, a_row0, (const float*)w.tab, T, w.hist);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int frmap_verify_counts(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D,
+                                   int a_row0, const float* thresholds, int T, uint64_t* accepted_out, uint64_t* rescored_out,
+                                   void* workspace, void* stream) {
+  if (int rc = verify_check("verify_counts", a, label_a, P, b, label_b, Q, D, a_row0, thresholds, T, accepted_out, workspace)) return rc;
+  FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "verify_counts: Q=%d too large for one call (shard B)", Q);
+  hipStream_t st = (hipStream_t)stream;
+  const VerifyWs w = verify_ws(workspace, P, D, T);
+  hipLaunchKernelGGL(verify_prep_kernel, dim3(1), dim3(1024), 0, st, thresholds, T, w.tab, w.hist, w.misc);
+  if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) return rc;
+  return verify_finish(w, T, accepted_out, rescored_out, st);
+}
+
+extern "C" int frmap_verify_counts_packed(const float* a, const int32_t* label_a, int P, const float* b, const void* b_packed,
+                                          const float* stat_w, const int32_t* label_b, int Q, int D, int a_row0, const float* thresholds,
+                                          int T, uint64_t* accepted_out, uint64_t* rescored_out, void* workspace, void* stream) {
+  if (int rc = verify_check("verify_counts_packed", a, label_a, P, b, label_b, Q, D, a_row0, thresholds, T, accepted_out, workspace))
+    return rc;
+  FRMAP_REQUIRE(b_packed && stat_w, "verify_counts_packed: null pointer");
+  FRMAP_REQUIRE(Q > 0 && D % 32 == 0, "verify_counts_packed: bad shape Q=%d D=%d (Q > 0, D %% 32 == 0)", Q, D);
+  FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "verify_counts_packed: Q=%d too large for one call (shard B)", Q);
+  hipStream_t st = (hipStream_t)stream;
+  const VerifyWs w = verify_ws(workspace, P, D, T);
+  hipLaunchKernelGGL(verify_prep_kernel, dim3(1), dim3(1024), 0, st, thresholds, T, w.tab, w.hist, w.misc);
+  int taken = 0;
+  if (P > 0) {
+    hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(P)), dim3(256), 0, st, a, w.stat_a, (_Float16*)w.split, P, D);
+    FrmapVerifyGemm v = {a, b, label_a, label_b, w.tab, w.hist, w.misc, a_row0, T};
+    taken = frmap_verify_gemm_pp(w.split, b_packed, w.stat_a, stat_w, v, P, Q, D, st);
+    if (taken < 0) return taken;
+  }
+  if (!taken)
+    if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) return rc;
+  return verify_finish(w, T, accepted_out, rescored_out, st);
 }
 
 extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits_out, int32_t* argmax_out,

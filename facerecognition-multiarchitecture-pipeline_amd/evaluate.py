@@ -144,6 +144,103 @@ def classification_metrics(all_targets: np.ndarray, all_predictions: np.ndarray,
     return m
 
 
+FAR_TARGETS = (1e-1, 1e-2, 1e-3, 1e-4)
+
+
+def pair_totals(labels, other_labels=None) -> Tuple[int, int]:
+    """(genuine, impostor) pair counts from the label histograms, exact: self mode (``other_labels=None``) counts every unordered
+    pair of ``labels`` once, cross mode every (i, j) of ``labels`` x ``other_labels``."""
+    la = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels, dtype=np.int64).reshape(-1)
+    if other_labels is None:
+        _, n = np.unique(la, return_counts=True)
+        genuine = sum(int(c) * (int(c) - 1) // 2 for c in n)
+        return genuine, len(la) * (len(la) - 1) // 2 - genuine
+    lb = np.asarray(other_labels.cpu() if isinstance(other_labels, torch.Tensor) else other_labels, dtype=np.int64).reshape(-1)
+    ua, na = np.unique(la, return_counts=True)
+    nb = dict(zip(*(x.tolist() for x in np.unique(lb, return_counts=True))))
+    genuine = sum(int(c) * nb.get(int(u), 0) for u, c in zip(ua.tolist(), na.tolist()))
+    return genuine, len(la) * len(lb) - genuine
+
+
+def metrics_from_counts(thresholds, accepted, genuine_pairs: int, impostor_pairs: int, far_targets=FAR_TARGETS) -> dict:
+    """The verification metrics of exact counts (`ops.verify_counts`): ``accepted`` [2, T] = genuine / impostor pairs accepted at
+    each threshold.  tar[k] = G_k / genuine_pairs, far[k] = I_k / impostor_pairs; ``roc_auc`` = trapezoid over (0, 0),
+    (far_k, tar_k)..., (1, 1); ``eer`` / ``eer_threshold``: linear interpolation at the first k with far_k >= 1 - tar_k (NaN if none);
+    ``tar_at_far``: per target, (the largest threshold with far_k <= target, its TAR) or None; ``best_accuracy`` / ``best_threshold``:
+    the grid threshold that classifies the most pairs right (first of equals)."""
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    acc = np.asarray(accepted.cpu() if isinstance(accepted, torch.Tensor) else accepted, dtype=np.float64).reshape(2, -1)
+    G, I = int(genuine_pairs), int(impostor_pairs)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tar = acc[0] / G if G else np.full(t.shape, np.nan)
+        far = acc[1] / I if I else np.full(t.shape, np.nan)
+    roc_auc = float(np.trapezoid(np.concatenate(([0.0], tar, [1.0])), np.concatenate(([0.0], far, [1.0])))) if G and I else float("nan")
+    eer = eer_t = float("nan")
+    if G and I:
+        diff = far - (1.0 - tar)
+        hit = np.nonzero(diff >= 0)[0]
+        if hit.size:
+            k = int(hit[0])
+            if k == 0:
+                eer, eer_t = float((far[0] + 1.0 - tar[0]) / 2), float(t[0])
+            else:
+                a = -diff[k - 1] / (diff[k] - diff[k - 1])
+                eer = float((1.0 - tar[k - 1]) + a * ((1.0 - tar[k]) - (1.0 - tar[k - 1])))
+                eer_t = float(t[k - 1] + a * (t[k] - t[k - 1]))
+    tar_at_far = {}
+    for f in far_targets:
+        ok = np.nonzero(far <= f)[0] if I else np.zeros(0, np.int64)
+        tar_at_far[f] = (float(t[ok[-1]]), float(tar[ok[-1]])) if ok.size else None
+    total = G + I
+    best_acc, best_t = float("nan"), float("nan")
+    if total:
+        right = acc[0] + (I - acc[1])
+        kb = int(np.argmax(right))
+        best_acc, best_t = float(right[kb] / total), float(t[kb])
+    return {"thresholds": t, "genuine_pairs": G, "impostor_pairs": I, "tar": tar, "far": far, "roc_auc": roc_auc, "eer": eer,
+            "eer_threshold": eer_t, "tar_at_far": tar_at_far, "best_accuracy": best_acc, "best_threshold": best_t}
+
+
+def default_thresholds(emb: torch.Tensor, other: Optional[torch.Tensor] = None, n: int = 1024) -> np.ndarray:
+    """``n`` fp32 thresholds evenly spaced on [0, 2 max ||row||_2 + 1e-3] (rows with a non-finite norm ignored), duplicates dropped:
+    every finite pair distance lies inside.  One device reduction and one scalar copy."""
+    rows = emb if other is None else torch.cat((emb.reshape(-1, emb.shape[-1]), other.reshape(-1, emb.shape[-1])))
+    norms = torch.linalg.vector_norm(rows.to(torch.float32), dim=1) if rows.numel() else torch.zeros(1, device=rows.device)
+    top = float(torch.where(torch.isfinite(norms), norms, torch.zeros_like(norms)).max()) if norms.numel() else 0.0
+    return np.unique(np.linspace(0.0, 2.0 * top + 1e-3, n).astype(np.float32))
+
+
+def verification_metrics(emb: torch.Tensor, labels, thresholds=None, other: Optional[torch.Tensor] = None, other_labels=None,
+                         far_targets=FAR_TARGETS, prepared=None) -> dict:
+    """The verification ROC of labelled embeddings, from EXACT pair counts on the GPU (`ops.verify_counts`): every unordered pair of
+    ``emb`` (or, with ``other``, every pair of ``emb`` x ``other``) is genuine (same label) or impostor, accepted at t iff its distance
+    ``||(a - b) + 1e-6||_2`` (the one `matching.search_batch` reports) is <= t.  Returns `metrics_from_counts`'s dict.  ``thresholds``:
+    ascending, finite, >= 0, at most `ops.VERIFY_MAX_THRESHOLDS` (default: `default_thresholds`).  Sets of >= `ops.MATCH_MFMA_MIN_G`
+    rows with D % 32 == 0 run on the MFMA path (packed here unless ``prepared`` is given)."""
+    e = emb.to(torch.float32)
+    dev = e.device
+    la = torch.as_tensor(np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels, dtype=np.int32)).to(dev)
+    b = lb = None
+    if other is not None:
+        b = other.to(device=dev, dtype=torch.float32)
+        lb = torch.as_tensor(np.asarray(other_labels.cpu() if isinstance(other_labels, torch.Tensor) else other_labels,
+                                        dtype=np.int32)).to(dev)
+    if thresholds is None:
+        thresholds = default_thresholds(e, b)
+    t = np.asarray(thresholds.cpu() if isinstance(thresholds, torch.Tensor) else thresholds, dtype=np.float32).reshape(-1)
+    target = e if b is None else b
+    if prepared is None and target.shape[0] >= ops.MATCH_MFMA_MIN_G and target.shape[1] % 32 == 0:
+        target = target.contiguous()
+        if b is None:
+            e = target
+        else:
+            b = target
+        prepared = ops.match_prepare(target)
+    counts = ops.verify_counts(e, la, t, b, lb, prepared=prepared)
+    G, I = pair_totals(la, lb)
+    return metrics_from_counts(t, counts.cpu().numpy(), G, I, far_targets)
+
+
 def evaluate_model(model, model_type: str, test_data, class_names: Optional[Sequence[str]] = None,
                    out_dir: Optional[str] = None, model_name: Optional[str] = None, dataset_name: str = "test",
                    batch_size: int = 32, arcface_classifier: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,

@@ -250,6 +250,21 @@ def compare_faces_topk(emb, refs, thresh, k: int, by: str = "entry"):
     return out
 
 
+def threshold_for_far(gallery, far: float, thresholds=None) -> Tuple[Optional[float], Optional[float]]:
+    """The largest threshold (of ``thresholds``, default `evaluate.default_thresholds`) at which at most a fraction ``far`` of the
+    impostor pairs of ``gallery`` (a `Gallery` or a refs list; identities = `Gallery.labels`) would be accepted, and the share of
+    genuine pairs accepted there: ``(threshold, tar)``, or ``(None, None)`` when no threshold qualifies.  Exact counts over every
+    unordered pair of enrolments (`ops.verify_counts`, self mode).  The threshold can be passed straight to `compare_faces`
+    (distances are compared the same way; on galleries of <= 64 rows compare_faces sums in fp32 and can differ in the last bit)."""
+    from . import evaluate
+    g = _as_gallery(gallery, "cuda")
+    if len(g) < 2:
+        raise ValueError("threshold_for_far: the gallery needs at least two enrolments")
+    m = evaluate.verification_metrics(g.matrix, g.labels, thresholds, far_targets=(float(far),), prepared=g.prepared)
+    hit = m["tar_at_far"][float(far)]
+    return (None, None) if hit is None else hit
+
+
 def get_embedding(face_img, model):
     """`app.py:32-48`: BGR uint8 crop → RGB → Resize((160,160)) → ToTensor → Normalize(0.5, 0.5) →
     ``model(x)`` on the model's device under ``no_grad``; ``None`` for an empty crop or on ANY

@@ -9,6 +9,7 @@ from __future__ import annotations
 import functools
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -631,6 +632,92 @@ def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, label
         _lib.check(lib.frmap_match_topk(emb.data_ptr(), gptr, lptr, idx.data_ptr(), dist.data_ptr(), lbp, ws.data_ptr(),
                                         B, G, D, k, _stream()), "match_topk")
     return idx, dist, lab
+
+
+VERIFY_MAX_THRESHOLDS = 2048
+
+
+def verify_thresholds(thresholds, device) -> torch.Tensor:
+    """fp32 [T] device tensor of ``thresholds`` after checking the contract of `verify_counts` on the host (finite, >= 0, strictly
+    ascending as fp32, 1 <= T <= `VERIFY_MAX_THRESHOLDS`).  A device tensor is checked through one host copy, except while a graph
+    is being captured: there the library's own device-side check stands (a violating call writes -1 to every count)."""
+    if isinstance(thresholds, torch.Tensor) and thresholds.is_cuda:
+        t = _dev(thresholds, "verify_counts.thresholds", torch.float32).reshape(-1)
+        host = None if torch.cuda.is_current_stream_capturing() else t.cpu().numpy()
+    else:
+        host = np.asarray(thresholds.cpu() if isinstance(thresholds, torch.Tensor) else thresholds, dtype=np.float32).reshape(-1)
+        t = None
+    if host is not None:
+        T = host.shape[0]
+        if not 1 <= T <= VERIFY_MAX_THRESHOLDS:
+            raise ValueError(f"verify_counts: {T} thresholds (1 <= T <= {VERIFY_MAX_THRESHOLDS})")
+        if not np.isfinite(host).all() or (host < 0).any():
+            raise ValueError("verify_counts: thresholds must be finite and >= 0")
+        if T > 1 and not (np.diff(host) > 0).all():
+            raise ValueError("verify_counts: thresholds must be strictly ascending")
+        if t is None:
+            t = torch.from_numpy(np.ascontiguousarray(host)).to(device)
+    return t
+
+
+def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Optional[torch.Tensor] = None,
+                  labels_b: Optional[torch.Tensor] = None, *, a_row0: Optional[int] = None, prepared: Optional[MatchPack] = None,
+                  return_rescored: bool = False):
+    """Exact verification counts: int64 [2, T] on the device, row 0 = genuine pairs (equal labels), row 1 = impostor pairs whose
+    distance ``(float) sqrt(d2)`` (the distance `match_topk` reports) is ``<= thresholds[k]``; NaN / inf distances are never accepted.
+    ``b=None``: self mode over ``a`` (every unordered pair once).  ``b`` with ``a_row0``: self mode, ``a`` = rows
+    [a_row0, a_row0 + len(a)) of ``b`` (pairs with a_row0 + i < j: shards over a_row0 sum to the whole).  ``b`` alone: cross mode,
+    every (i, j).  ``thresholds``: finite, >= 0, strictly ascending, at most `VERIFY_MAX_THRESHOLDS`.  Path choice as `match_topk`:
+    a ``prepared`` B (`match_prepare(b)`) of >= `MATCH_MFMA_MIN_G` rows with D % 32 == 0 runs on the fp16 MFMA GEMM whose epilogue
+    bins the certain pairs and re-scores the rest exactly; everything else on an exact scan.  Same counts either way.
+    ``return_rescored``: also return int64 [1] = the pairs the GEMM path re-scored.
+    Outside graph capture the thresholds are checked on the host (`verify_thresholds`): host values are uploaded with a blocking
+    copy and device values read back, so each call synchronises the stream once.  A caller that repeats calls on fixed device
+    thresholds and wants them asynchronous calls the C entry points (`frmap_verify_counts[_packed]`) after checking them once."""
+    a = _dev(a, "verify_counts.a", torch.float32)
+    if a.dim() != 2:
+        raise ValueError("verify_counts: a must be [P, D]")
+    P, D = int(a.shape[0]), int(a.shape[1])
+    la = _dev(labels_a, "verify_counts.labels_a").to(torch.int32).reshape(-1)
+    if la.shape[0] != P:
+        raise ValueError(f"verify_counts: labels_a must hold {P} labels, got {la.shape[0]}")
+    if b is None:
+        if labels_b is not None or a_row0 not in (None, 0):
+            raise ValueError("verify_counts: self mode over `a` (b=None) takes no labels_b / a_row0")
+        b, lb, row0 = a, la, 0
+    else:
+        b = _dev(b, "verify_counts.b", torch.float32)
+        if b.dim() != 2 or int(b.shape[1]) != D:
+            raise ValueError(f"verify_counts: b must be [Q, {D}]")
+        if labels_b is None:
+            raise ValueError("verify_counts: labels_b is required with b")
+        lb = _dev(labels_b, "verify_counts.labels_b").to(torch.int32).reshape(-1)
+        if lb.shape[0] != b.shape[0]:
+            raise ValueError(f"verify_counts: labels_b must hold {int(b.shape[0])} labels, got {lb.shape[0]}")
+        row0 = -1 if a_row0 is None else int(a_row0)
+        if a_row0 is not None and not (row0 >= 0 and row0 + P <= int(b.shape[0])):
+            raise ValueError(f"verify_counts: a_row0={row0} with {P} rows is not a block of b's {int(b.shape[0])} rows")
+    Q = int(b.shape[0])
+    thr = verify_thresholds(thresholds, a.device)
+    T = int(thr.shape[0])
+    lib = _lib.load()
+    out = torch.empty((2, T), dtype=torch.int64, device=a.device)
+    resc = torch.empty((1,), dtype=torch.int64, device=a.device) if return_rescored else None
+    ws = torch.empty((lib.frmap_verify_workspace_bytes(P, Q, D, T),), dtype=torch.uint8, device=a.device)
+    aptr, laptr = (a.data_ptr(), la.data_ptr()) if P else (0, 0)
+    bptr, lbptr = (b.data_ptr(), lb.data_ptr()) if Q else (0, 0)
+    rptr = resc.data_ptr() if resc is not None else 0
+    if prepared is not None and Q >= MATCH_MFMA_MIN_G and D % 32 == 0:
+        if not prepared.matches(b):
+            raise ValueError("verify_counts: `prepared` was built from a different (or since modified) b")
+        prepared.wait_ready()
+        _lib.check(lib.frmap_verify_counts_packed(aptr, laptr, P, bptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lbptr,
+                                                  Q, D, row0, thr.data_ptr(), T, out.data_ptr(), rptr, ws.data_ptr(), _stream()),
+                   "verify_counts_packed")
+    else:
+        _lib.check(lib.frmap_verify_counts(aptr, laptr, P, bptr, lbptr, Q, D, row0, thr.data_ptr(), T, out.data_ptr(), rptr,
+                                           ws.data_ptr(), _stream()), "verify_counts")
+    return (out, resc) if return_rescored else out
 
 
 def gap_linear_norm(fmap: torch.Tensor, wt: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],

@@ -358,6 +358,31 @@ int frmap_match_topk_packed(const float* emb, const float* gallery, const void* 
                             const int32_t* labels, int32_t* idx_out, float* dist_out, int32_t* label_out,
                             void* workspace, int B, int G, int D, int k, void* stream);
 
+/* Exact verification counts (the verification ROC of a set of labelled embeddings).  A = fp32 [P][D] with int32 labels [P],
+ * B = fp32 [Q][D] with int32 labels [Q]; `thresholds` = fp32 [T] on the device, finite, >= 0 and strictly ascending,
+ * 1 <= T <= 2048.  The distance of a pair is the one frmap_match_topk reports: dist(i, j) = (float) sqrt(d2), d2 = the squares of
+ * the fp32 elements (a - b) + 1e-6 summed in float64.  A pair is accepted at t iff dist <= t (NaN / inf never), genuine iff
+ * label_a[i] == label_b[j], impostor otherwise.  Counted pairs: a_row0 = -1 (cross mode): every (i, j); a_row0 >= 0 (self mode:
+ * A is rows [a_row0, a_row0 + P) of B): the pairs with a_row0 + i < j, so a_row0 = 0 with A = B counts every unordered pair once
+ * and shards over a_row0 sum to the whole.
+ *   accepted_out: uint64 [2][T] = genuine / impostor pairs accepted at each t_k.  Exact integers, overwritten, independent of
+ *                 path, tiling and launch order.  The totals follow from the label histograms.
+ *   rescored_out: optional uint64 [1] = pairs re-scored exactly after the GEMM's error band straddled a threshold (0 on the scan).
+ *   workspace:    frmap_verify_workspace_bytes(P, Q, D, T) bytes (device, caller-owned, 256-byte aligned).
+ * frmap_verify_counts scores every counted pair exactly (small inputs, D % 32 != 0, B without a pack).
+ * frmap_verify_counts_packed: B prepared by frmap_match_pack_gallery (D % 32 == 0, Q > 0) runs on the fp16 MFMA GEMM; its epilogue
+ * bins every pair whose error band lies inside one threshold interval and re-scores the rest exactly.
+ * Shapes, T, pointers and a_row0 are checked before any launch.  The threshold VALUES live on the device and are checked there
+ * (nothing is synchronised, so the call can be graph-captured): a call whose thresholds break the contract writes all-ones
+ * (UINT64_MAX) to every output. */
+size_t frmap_verify_workspace_bytes(int P, int Q, int D, int T);
+int frmap_verify_counts(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D,
+                        int a_row0, const float* thresholds, int T, uint64_t* accepted_out, uint64_t* rescored_out,
+                        void* workspace, void* stream);
+int frmap_verify_counts_packed(const float* a, const int32_t* label_a, int P, const float* b, const void* b_packed,
+                               const float* stat_w, const int32_t* label_b, int Q, int D, int a_row0, const float* thresholds,
+                               int T, uint64_t* accepted_out, uint64_t* rescored_out, void* workspace, void* stream);
+
 /* The tail of the ResNet-18 ('cnn') embed-and-match step for small galleries in ONE launch, one workgroup per face:
  * AdaptiveAvgPool2d(1) of the trunk map (face_models.py:100) -> optional F.normalize(eps) -> compare_faces' scan
  * (src/app.py:58-64) exactly as frmap_match_top1 does it for G <= 64.
