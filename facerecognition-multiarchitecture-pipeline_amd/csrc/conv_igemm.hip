@@ -46,11 +46,6 @@ struct ConvParams {
   const void* ds_w;    // packed like a 1x1 conv: [Cout/64][ds_Cin/32][1][64][4][8]
   int ds_Hi, ds_Wi, ds_Cin, ds_stride, ds_chunks;
   FrmapPoolOrder pool;  // conv_igemm_kernel<..., POOL = true>: pool-major pixel order of the fused 2x2 max-pool
-  // conv1x1_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR>: the GEMM is probes x gallery rows, the epilogue keeps each probe's arg-min distance
-  const float* m_stat_a;           // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
-  const float* m_stat_w;           // [G][4] of the fp32 gallery rows
-  void* m_recs;                    // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
-  int m_G, m_D;                    // real gallery rows (Cout is padded to 64), embedding width
 };
 
 // 64 zero bytes: out-of-image (padding) pixels LOAD from here instead of branching around the load —
@@ -1010,11 +1005,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_fast_kernel(const ConvParams
 // 64 x 128 weights (16 KB) per stage, 64 MFMAs per wave per stage, both operands of the next stage
 // prefetched into registers under the current stage's MFMAs.  Split-K as in frmap_linear_mfma.
 // ================================================================================================
-// MM = MATCH_TOP1: top-1 gallery match (head_match.hip, frmap_match_top1_packed); MATCH_TOPR: the top-k search's records (frmap_match_topk_packed).  The "pixels" are the probes and the
-// "channels" the gallery rows, both split into fp16 (hi, lo) pairs laid out so that one K = 3 D GEMM accumulates
-// a_hi.g_hi + a_hi.g_lo + a_lo.g_hi in fp32 (= the fp32 dot product to ~2^-22); the epilogue forms the squared
-// F.pairwise_distance from it as gemm_nt_f32_kernel<MODE_DIST> does and writes one candidate record per probe and 64-row slot.
-template <typename TT, int CKS, int MM = MATCH_NONE>
+template <typename TT, int CKS>
 __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
   constexpr int BM = 256, MI = 4, NI = 4, NIT = BM * 4 / 256;
   using vec8 = typename TT::vec8;
@@ -1087,10 +1078,6 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = TT::mfma(wf[ni], pf[mi], acc[mi][ni]);
     }
   }
-  if constexpr (MM != MATCH_NONE) {
-    match_epilogue<MM, MI>(acc, m0 + wave * 64, p.M, nt << 6, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.m_recs, lane);
-    return;
-  }
   __syncthreads();
   if (p.ksplit > 1)
     conv_epilogue_partial<MI, NI>(acc, smem + wave * (16 * (NI * 64 + 16)), m0 + wave * 64, p.M, p.Cout, nt << 6,
@@ -1100,9 +1087,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
                               (const typename TT::elem*)p.res, (typename TT::elem*)p.out, p.relu, lane);
 }
 
-template <typename TT, int CKS, int MM = MATCH_NONE>
+template <typename TT, int CKS>
 static int launch_1x1(const ConvParams& p, hipStream_t st) {
-  auto kern = conv1x1_kernel<TT, CKS, MM>;
+  auto kern = conv1x1_kernel<TT, CKS>;
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
   int lds = CKS * (256 * 64 + 4096);
   const int scratch = 4 * 16 * (4 * 64 + 16);
@@ -1452,44 +1439,6 @@ extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, cons
   const int lds = p.halo_bytes + wbytes;
   if (BM == 256) return dtype == FRMAP_BF16 ? launch<BF16, 256, 3, 1, true>(p, lds, st) : launch<F16, 256, 3, 1, true>(p, lds, st);
   return dtype == FRMAP_BF16 ? launch<BF16, 128, 3, 1, true>(p, lds, st) : launch<F16, 128, 3, 1, true>(p, lds, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Top-1 match GEMM (frmap_match_top1_packed): probes3 = fp16 [B][3 D] rows (a_hi | a_hi | a_lo), gallery_packed = the
-// gallery's (g_hi | g_lo | g_hi) rows in conv-weight order (match_pack_gallery_kernel); every row carries its own
-// power-of-two scale, whose inverse is the third float of its statistics record.
-// ------------------------------------------------------------------------------------------------
-int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                           void* recs, int B, int G, int D, hipStream_t st, int topr) {
-  const int K3 = 3 * D, Gpad = (G + 255) / 256 * 256;   // (the packed gallery is padded to 256 rows: frmap_match_gallery_pack_bytes)
-  FRMAP_REQUIRE(K3 % 32 == 0, "match: D=%d must be a multiple of 32", D);
-  {
-    const int rc = frmap_match_gemm_pp(probes3, gallery_packed, stat_a, stat_w, recs, B, G, Gpad, D, st, topr);
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-  }
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = probes3; p.wpk = gallery_packed;
-  p.N = B; p.Hi = 1; p.Wi = 1; p.Cin = K3; p.Ho = 1; p.Wo = 1; p.Cout = Gpad;
-  p.stride = 1; p.pad = 0;
-  p.M = B; p.HoWo = 1; p.Hp = 1; p.Wp = 1;
-  p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
-  p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u);
-  p.ksplit = 1;
-  p.nblocks = ((B + 255) / 256) * (Gpad / 64);
-  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_recs = recs; p.m_G = G; p.m_D = D;
-  const int c32 = K3 / 32;
-  if (topr) {
-    if (c32 % 4 == 0) { p.nchunks = c32 / 4; return launch_1x1<F16, 4, MATCH_TOPR>(p, st); }
-    if (c32 % 2 == 0) { p.nchunks = c32 / 2; return launch_1x1<F16, 2, MATCH_TOPR>(p, st); }
-    p.nchunks = c32;
-    return launch_1x1<F16, 1, MATCH_TOPR>(p, st);
-  }
-  if (c32 % 4 == 0) { p.nchunks = c32 / 4; return launch_1x1<F16, 4, MATCH_TOP1>(p, st); }
-  if (c32 % 2 == 0) { p.nchunks = c32 / 2; return launch_1x1<F16, 2, MATCH_TOP1>(p, st); }
-  p.nchunks = c32;
-  return launch_1x1<F16, 1, MATCH_TOP1>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------

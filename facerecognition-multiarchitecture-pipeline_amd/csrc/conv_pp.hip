@@ -54,11 +54,11 @@ struct PPParams {
   // fused MaxPool2d(2, 2) (PL = true): each wave's 112-pixel slice (whole row pairs) is walked in pool-major order
   int Wo2;         // Wi / 2
   FrmapDiv dWo2;
-  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR> (gallery match, head_match.hip): per-row statistics and the arg-min keys
+  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR / MATCH_HIST> (gallery match, frmap_match_gemm): per-row statistics, records
   const float* m_stat_a;        // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
   const float* m_stat_w;        // [G][4] of the fp32 gallery rows
-  void* m_recs;                 // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
-  int m_G, m_D;
+  void* m_records;              // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
+  int m_G, m_D;                 // real gallery rows (Cout is padded to 256), embedding width
 };
 // conv1x1_pp_kernel<..., MATCH_HIST> (verification counts) takes these: exact operands, labels, the threshold table, the counts.
 // A type of its own, so that every other instantiation keeps PPParams' layout (and its kernarg offsets) unchanged.
@@ -525,9 +525,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p) {
 // KS = 2: 224 px x 128 ch with the two wave groups splitting K (own buffers; accumulators merged through LDS) for outputs with
 // few tiles (Linear 2048 -> 512 over 12 544 tokens: 224 tiles instead of 112).
 // ================================================================================================
-// MM = MATCH_TOP1: the epilogue of conv1x1_kernel<..., MATCH_TOP1> (conv_igemm.hip): the GEMM is probes x gallery rows in split fp16
-// operands, each lane forms the expanded squared F.pairwise_distance of its 16 gallery rows with its error band, the column's
-// four lanes meet through two shuffles, one candidate record per probe and 64-row slot (match_epilogue_records).
+// MM = MATCH_TOP1: top-1 gallery match (frmap_match_gemm): the GEMM is probes x gallery rows in split fp16 operands, each lane
+// forms the expanded squared F.pairwise_distance of its 16 gallery rows with its error band, the column's four lanes meet
+// through two shuffles, one candidate record per probe and 64-row slot (match_epilogue_records).
 // MM = MATCH_TOPR: the same GEMM with the top-k search's records (match_epilogue_topr: R = 4 rows per slot + the rest bound).
 // MM = MATCH_HIST: verification counts (match_epilogue_hist): certain pairs binned in LDS, the rest queued per wave in LDS and
 // re-scored exactly by the wave itself (verify_drain_queue), then one 64-bit atomicAdd per non-zero bin of the workgroup.  In self
@@ -684,7 +684,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg
     return;
   } else if constexpr (MM != MATCH_NONE) {
     match_epilogue<MM, MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
-                           p.m_recs, lane);
+                           p.m_records, lane);
     return;
   }
   conv_epilogue<TT, MI, NI>(acc, smem + (KS == 2 ? q : wave) * (16 * (NI * 64 + 16)), m0 + mslice * (MI * 16), mend, p.Cout,
@@ -1219,43 +1219,20 @@ int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, c
   return rc ? rc : 1;
 }
 
-// match GEMM on the same kernel (see frmap_match_gemm_f16x3 in conv_igemm.hip): G padded to 256 rows, K3 = 3 D.
-// topr = 0: top-1 records (MatchRec), 1: top-R records (MatchRecK).  1 = launched, 0 = not taken
-int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                        void* recs, int B, int G, int Gpad, int D, hipStream_t st, int topr) {
-  static int on = -1;
-  if (on < 0) on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_MATCH_PP", 1);
-  const int K3 = 3 * D;
-  if (!on || Gpad % 256 || K3 % 32 || K3 > 16384 || B <= 0) return 0;
-  PPParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = probes3; p.wpk = gallery_packed;
-  p.N = B; p.Hi = 1; p.Wi = 1; p.Cin = K3; p.Cout = Gpad;
-  p.M = B; p.HoWo = 1; p.Hp = 1; p.Wp = 1;
-  p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
-  p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u); p.dWo2 = frmap_div_make(1u);
-  p.nchunks = K3 / 32; p.ds_stride = 1;
-  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_recs = recs; p.m_G = G; p.m_D = D;
-  // 224 probes x 256 gallery rows per tile, or 448 x 128 when that fills the CUs better (one round either way at 1024 probes)
-  const long long t1 = ((B + 223) / 224) * (long long)(Gpad / 256), t2 = ((B + 447) / 448) * (long long)(Gpad / 128);
-  const long long r1 = (t1 + 255) / 256, r2 = (t2 + 255) / 256;   // rounds on 256 CUs (a tile costs the same in both layouts)
-  const bool wide = r2 < r1 || (r2 == r1 && t2 > t1);             // same rounds: the layout that occupies more CUs
-  p.tile_px = wide ? 448 : 224;
-  p.mtiles = (B + p.tile_px - 1) / p.tile_px;
-  p.ntiles = Gpad / (wide ? 128 : 256);
-  const int rc = topr ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
-                      : (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st));
-  return rc ? rc : 1;
-}
-
-// verification counts on the same GEMM (conv1x1_pp_kernel<F16, ..., MATCH_HIST>): the probes are A (P rows), the packed gallery B
-int frmap_verify_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                         const FrmapVerifyGemm& v, int P, int Q, int D, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_MATCH_PP", 1);
-  const int K3 = 3 * D, Gpad = (Q + 255) / 256 * 256;
-  if (!on || K3 % 32 || K3 > 16384 || P <= 0 || Q <= 0 || v.T < 1 || v.T > VERIFY_MAX_T) return 0;
-  PPHistParams p;
+// ------------------------------------------------------------------------------------------------
+// The split-fp16 match GEMM of the packed match entry points (head_match.hip) on the same kernel: probes3 = fp16 [P][3 D] rows
+// (a_hi | a_hi | a_lo), gallery_packed = the G gallery rows (g_hi | g_lo | g_hi) in conv-weight order, padded to Gpad = 256-row
+// groups (match_pack_gallery_kernel), K3 = 3 D; every row carries its own power-of-two scale, whose inverse is the third float of
+// its statistics record.  mode MATCH_TOP1 / MATCH_TOPR: `out` = MatchRec / MatchRecK records [Gpad / 64][P]; MATCH_HIST: `out` =
+// the FrmapVerifyGemm.  1 = launched, 0 = shape not taken, < 0 = error; probes3 == nullptr: plan only.
+// ------------------------------------------------------------------------------------------------
+int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
+                     int P, int G, int D, hipStream_t st) {
+  const int K3 = 3 * D, Gpad = (G + 255) / 256 * 256;
+  const FrmapVerifyGemm* v = mode == MATCH_HIST ? (const FrmapVerifyGemm*)out : nullptr;
+  if (K3 % 32 || K3 > 16384 || P <= 0 || G <= 0 || (v && (v->T < 1 || v->T > VERIFY_MAX_T))) return 0;
+  if (!probes3) return 1;
+  PPHistParams p;   // (MATCH_TOP1 / MATCH_TOPR launch its PPParams part)
   memset(&p, 0, sizeof(p));
   p.in = probes3; p.wpk = gallery_packed;
   p.N = P; p.Hi = 1; p.Wi = 1; p.Cin = K3; p.Cout = Gpad;
@@ -1263,17 +1240,23 @@ int frmap_verify_gemm_pp(const void* probes3, const void* gallery_packed, const 
   p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
   p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u); p.dWo2 = frmap_div_make(1u);
   p.nchunks = K3 / 32; p.ds_stride = 1;
-  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_G = Q; p.m_D = D;
-  p.h_A = v.A; p.h_B = v.B; p.h_lab_a = v.lab_a; p.h_lab_b = v.lab_b; p.h_tab = v.tab; p.h_hist = v.hist; p.h_rescored = v.rescored;
-  p.h_row0 = v.row0; p.h_T = v.T;
-  // tile choice as frmap_match_gemm_pp
+  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_G = G; p.m_D = D;
+  if (v) {
+    p.h_A = v->A; p.h_B = v->B; p.h_lab_a = v->lab_a; p.h_lab_b = v->lab_b; p.h_tab = v->tab; p.h_hist = v->hist;
+    p.h_rescored = v->rescored; p.h_row0 = v->row0; p.h_T = v->T;
+  } else {
+    p.m_records = out;
+  }
+  // 224 probes x 256 gallery rows per tile, or 448 x 128 when that fills the CUs better (one round either way at 1024 probes)
   const long long t1 = ((P + 223) / 224) * (long long)(Gpad / 256), t2 = ((P + 447) / 448) * (long long)(Gpad / 128);
-  const long long r1 = (t1 + 255) / 256, r2 = (t2 + 255) / 256;
-  const bool wide = r2 < r1 || (r2 == r1 && t2 > t1);
+  const long long r1 = (t1 + 255) / 256, r2 = (t2 + 255) / 256;   // rounds on 256 CUs (a tile costs the same in both layouts)
+  const bool wide = r2 < r1 || (r2 == r1 && t2 > t1);             // same rounds: the layout that occupies more CUs
   p.tile_px = wide ? 448 : 224;
   p.mtiles = (P + p.tile_px - 1) / p.tile_px;
   p.ntiles = Gpad / (wide ? 128 : 256);
-  const int rc = wide ? pp1_launch<F16, 4, 1, MATCH_HIST>(p, st) : pp1_launch<F16, 2, 1, MATCH_HIST>(p, st);
+  const int rc = mode == MATCH_TOPR ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
+                 : mode == MATCH_TOP1 ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st))
+                                      : (wide ? pp1_launch<F16, 4, 1, MATCH_HIST>(p, st) : pp1_launch<F16, 2, 1, MATCH_HIST>(p, st));
   return rc ? rc : 1;
 }
 

@@ -90,7 +90,7 @@ struct __attribute__((aligned(16))) MatchRec {
 __device__ __forceinline__ float match_kappa(int terms) { return (float)(2 * terms + 64) * 5.9604644775390625e-8f; }
 __device__ __forceinline__ float match_band(float s2, float kf) { return s2 + 2e-6f * sqrtf(kf * s2); }
 
-// Epilogue of the split-fp16 match GEMMs (conv1x1_kernel<.., MATCH>, conv1x1_pp_kernel<.., MATCH>): after the K loop lane
+// Epilogue of the split-fp16 match GEMM (conv1x1_pp_kernel<.., MATCH_TOP1>, frmap_match_gemm): after the K loop lane
 // (lr, g) holds, per MFMA tile (mi, ni), the scaled dot products of probe b_base + mi * 16 + lr with gallery rows
 // n0 + ni * 16 + 4 g + j.  The wave's 64 gallery rows are one slot (n0 / 64); records are laid out [slot][M].
 // Row statistics (match_row_prep_kernel): (sum x^2, sum x, 1 / row scale, band(x)).
@@ -143,7 +143,7 @@ __device__ __forceinline__ void match_epilogue_records(const f32x4_t (&acc)[MI][
 }
 
 // ------------------------------------------------------------------------------------------------
-// Top-k gallery search behind the same GEMMs: per probe and 64-row slot, the R = 4 smallest lower bounds L of the slot (ascending,
+// Top-k gallery search behind the same GEMM: per probe and 64-row slot, the R = 4 smallest lower bounds L of the slot (ascending,
 // first row first among equal L) with their rows and upper bounds U, and `rest` = the (R+1)-th smallest L, a lower bound on every
 // row of the slot that is not listed.  Error bounds as match_epilogue_records.  match_topk_finalize_kernel (head_match.hip) takes
 // tau = the k-th smallest listed U (per distinct label in identity mode) and re-scores exactly every listed row with L <= tau and
@@ -630,13 +630,7 @@ int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shi
 // 1x1 conv / Linear on the LDS-DMA ping-pong pipeline (conv1x1_pp_kernel): 1 = launched, 0 = not taken, < 0 = error
 int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
                      int Wi, int Cin, int Cout, int stride, int relu, int dtype, hipStream_t st);
-// match GEMMs: topr = 0 writes MatchRec records (top-1), topr = 1 MatchRecK records (top-k search)
-int frmap_match_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                        void* recs, int B, int G, int Gpad, int D, hipStream_t st, int topr);
-// match GEMM on the 1x1 MFMA kernel (conv_igemm.hip), see frmap_match_top1_packed / frmap_match_topk_packed
-int frmap_match_gemm_f16x3(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                           void* recs, int B, int G, int D, hipStream_t st, int topr);
-// verification counts on the match GEMM (conv1x1_pp_kernel<..., MATCH_HIST>): 1 = launched, 0 = not taken, < 0 = error.
+// what the verification counts' match GEMM (MATCH_HIST) takes besides the operands:
 // tab: t [T] | lo [T] | hi [T] (fp32, device); hist: u64 [2][T + 1] accumulated into; rescored: u64 += pairs re-scored exactly
 struct FrmapVerifyGemm {
   const float* A;           // fp32 [P][D]
@@ -649,8 +643,11 @@ struct FrmapVerifyGemm {
   int row0;                 // -1: cross mode; else A = rows [row0, row0 + P) of B, pairs with row0 + i < j
   int T;
 };
-int frmap_verify_gemm_pp(const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w,
-                         const FrmapVerifyGemm& v, int P, int Q, int D, hipStream_t st);
+// The split-fp16 match GEMM (conv1x1_pp_kernel<F16, ..., mode>, conv_pp.hip) of P probes against a packed gallery of G rows:
+// mode MATCH_TOP1 / MATCH_TOPR writes MatchRec / MatchRecK records to `out` ([Gpad / 64][P]); MATCH_HIST takes a FrmapVerifyGemm*
+// as `out`.  1 = launched, 0 = shape not taken (nothing launched), < 0 = error; probes3 == nullptr: plan only.
+int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
+                     int P, int G, int D, hipStream_t st);
 // label_out[0 .. n) = -1 (frmap_match_topk's k = 1 entry-mode outputs; head_match.hip)
 int frmap_match_topk_fill_labels(int32_t* label_out, int n, hipStream_t st);
 #define FRMAP_REQUIRE(cond, ...)        \

@@ -981,6 +981,16 @@ extern "C" int frmap_match_pack_gallery_rows(const float* gallery, void* packed_
   return match_pack_rows(gallery, packed_out, stat_w_out, row_lo, row_hi, G, D, (hipStream_t)stream);
 }
 
+// The packed entry points' GEMM step: probe statistics [P][4] and fp16 split [P][3 D] (match_row_prep_kernel), then the split-fp16
+// GEMM in `mode` (frmap_match_gemm).  1 = launched, < 0 = error, 0 = the GEMM does not take the shape and nothing was launched:
+// the entry point then answers as its unpacked twin does, from the workspace it was given (same exact re-score, same answer).
+static int match_packed_gemm(int mode, const float* a, const void* packed, const float* stat_w, float* stat_a, void* split, void* out,
+                             int P, int G, int D, hipStream_t st) {
+  if (!frmap_match_gemm(mode, nullptr, packed, stat_a, stat_w, out, P, G, D, st)) return 0;
+  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(P)), dim3(256), 0, st, a, stat_a, (_Float16*)split, P, D);
+  return frmap_match_gemm(mode, split, packed, stat_a, stat_w, out, P, G, D, st);
+}
+
 // frmap_match_top1 for a prepared gallery (same outputs, same contract).  workspace: frmap_match_workspace_bytes(B, G)
 // bytes; probe_split: B * 3 * D fp16 scratch.
 extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, const void* gallery_packed, const float* stat_w,
@@ -993,9 +1003,9 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
   const int nslots = (G + 255) / 256 * 4;
   MatchRec* recs = (MatchRec*)workspace;
   float* stat_a = (float*)(recs + (size_t)nslots * B);
-  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, stat_a, (_Float16*)probe_split, B, D);
-  const int rc = frmap_match_gemm_f16x3(probe_split, gallery_packed, stat_a, stat_w, recs, B, G, D, st, 0);
-  if (rc) return rc;
+  const int rc = match_packed_gemm(MATCH_TOP1, emb, gallery_packed, stat_w, stat_a, probe_split, recs, B, G, D, st);
+  if (rc < 0) return rc;
+  if (!rc) return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, workspace, B, G, D, stream);
   hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)recs, nslots, 64,
                      idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D);
   FRMAP_LAUNCH_CHECK();
@@ -1070,7 +1080,7 @@ __global__ void match_topk_scan_kernel(const float* __restrict__ emb, const floa
   topk_write<BY_LABEL>(ld, lr, ll, b, k, lane, idx_out, dist_out, label_out);
 }
 
-// Prepared galleries: the records of conv1x1_[pp_]kernel<..., MATCH_TOPR> (frmap_common.h: MatchRecK [nslots][B]).
+// Prepared galleries: the records of conv1x1_pp_kernel<..., MATCH_TOPR> (frmap_common.h: MatchRecK [nslots][B]).
 //   tau = the k-th smallest listed U (identity mode: the k-th smallest, over distinct labels, of the per-label min of listed U);
 //         +inf when the records name fewer than k rows (labels).
 //   re-score with match_exact_d2 every listed row with L <= tau, and every row of a slot whose rest bound is <= tau.
@@ -1216,9 +1226,9 @@ extern "C" int frmap_match_topk_packed(const float* emb, const float* gallery, c
   const int nslots = (G + 255) / 256 * 4;
   MatchRecK* recs = (MatchRecK*)workspace;
   float* stat_a = (float*)((char*)workspace + recs_b);
-  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, stat_a, (_Float16*)split, B, D);
-  const int rc = frmap_match_gemm_f16x3(split, gallery_packed, stat_a, stat_w, recs, B, G, D, st, 1);
-  if (rc) return rc;
+  const int rc = match_packed_gemm(MATCH_TOPR, emb, gallery_packed, stat_w, stat_a, split, recs, B, G, D, st);
+  if (rc < 0) return rc;
+  if (!rc) return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, workspace, B, G, D, k, stream);
   if (labels)
     hipLaunchKernelGGL(match_topk_finalize_kernel<true>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels,
                        (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
@@ -1403,13 +1413,9 @@ extern "C" int frmap_verify_counts_packed(const float* a, const int32_t* label_a
   hipStream_t st = (hipStream_t)stream;
   const VerifyWs w = verify_ws(workspace, P, D, T);
   hipLaunchKernelGGL(verify_prep_kernel, dim3(1), dim3(1024), 0, st, thresholds, T, w.tab, w.hist, w.misc);
-  int taken = 0;
-  if (P > 0) {
-    hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(P)), dim3(256), 0, st, a, w.stat_a, (_Float16*)w.split, P, D);
-    FrmapVerifyGemm v = {a, b, label_a, label_b, w.tab, w.hist, w.misc, a_row0, T};
-    taken = frmap_verify_gemm_pp(w.split, b_packed, w.stat_a, stat_w, v, P, Q, D, st);
-    if (taken < 0) return taken;
-  }
+  FrmapVerifyGemm v = {a, b, label_a, label_b, w.tab, w.hist, w.misc, a_row0, T};
+  const int taken = match_packed_gemm(MATCH_HIST, a, b_packed, stat_w, w.stat_a, w.split, &v, P, Q, D, st);
+  if (taken < 0) return taken;
   if (!taken)
     if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) return rc;
   return verify_finish(w, T, accepted_out, rescored_out, st);

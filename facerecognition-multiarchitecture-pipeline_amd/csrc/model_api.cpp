@@ -515,6 +515,9 @@ static int model_match_embedding(Run& r, const void* x, int x_kind, int H, int W
   return r.rc;
 }
 
+// the caller's gallery pack is used for galleries of >= 512 rows with D % 32 == 0 (the Python side: ops.wants_pack)
+static inline bool match_use_pack(int G, int D) { return G >= 512 && D % 32 == 0; }
+
 extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
                                            const void* gallery_packed, const float* gallery_stat, int G, float thresh,
                                            int normalize, int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out,
@@ -540,14 +543,14 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
   float* emb = nullptr;
   if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
   if (m->kind >= KIND_BASELINE) {
-    if (gallery_packed && gallery_stat && G >= 512 && D % 32 == 0) {
+    if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
       void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
       return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
                                      match_ws, split, B, G, D, r.st);
     }
     return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
   }
-  if (gallery_packed && gallery_stat && G >= 512) {
+  if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
     void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
     Traced t(r, "match_top1 (conv1x1_pp_kernel<F16, MATCH> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 16.0 * B);
     return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
@@ -590,7 +593,7 @@ extern "C" int frmap_model_embed_and_search(frmap_model* m, const void* x, int x
   }
   float* emb = nullptr;
   if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
-  if (gallery_packed && gallery_stat && G >= 512 && D % 32 == 0) {
+  if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
     Traced t(r, "match_topk (conv1x1_pp_kernel<F16, MATCH_TOPR> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 64.0 * B * k);
     return frmap_match_topk_packed(emb, gallery, gallery_packed, gallery_stat, labels, idx_out, dist_out, label_out, match_ws, B, G, D, k, r.st);
   }

@@ -229,7 +229,7 @@ def verification_metrics(emb: torch.Tensor, labels, thresholds=None, other: Opti
         thresholds = default_thresholds(e, b)
     t = np.asarray(thresholds.cpu() if isinstance(thresholds, torch.Tensor) else thresholds, dtype=np.float32).reshape(-1)
     target = e if b is None else b
-    if prepared is None and target.shape[0] >= ops.MATCH_MFMA_MIN_G and target.shape[1] % 32 == 0:
+    if prepared is None and ops.wants_pack(target.shape[0], target.shape[1]):
         target = target.contiguous()
         if b is None:
             e = target

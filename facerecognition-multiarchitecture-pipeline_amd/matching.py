@@ -26,7 +26,6 @@ import torch
 
 from . import gallery_io, ops
 
-_MFMA_MATCH = os.environ.get("FRMAP_MATCH_MFMA", "1") != "0"   # A/B switch: 0 = large galleries on the fp32 GEMM
 REC_THRESH = 1.0                       # `app.py:20`
 REF_DIR = "face_references"            # `app.py:23`
 REF_FILE = os.path.join(REF_DIR, "face_references.pkl")   # `app.py:24`
@@ -96,7 +95,7 @@ class Gallery:
         return self._buf[: len(self.names)]
 
     def _wants_pack(self) -> bool:
-        return len(self.names) >= ops.MATCH_MFMA_MIN_G and self._buf.shape[1] % 32 == 0 and _MFMA_MATCH
+        return ops.wants_pack(len(self.names), self._buf.shape[1])
 
     def _refresh_pack(self) -> None:
         # built HERE (construction / enrolment time, on the caller's stream) and guarded by an event - not lazily on whichever

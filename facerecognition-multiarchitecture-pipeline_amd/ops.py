@@ -526,6 +526,23 @@ class MatchPack:
 MATCH_MFMA_MIN_G = 512   # galleries at least this large take the MFMA path when a MatchPack is supplied
 
 
+def wants_pack(G: int, D: int) -> bool:
+    """Whether a gallery of G rows of width D runs on the MFMA path (and so is worth a `MatchPack`)."""
+    return G >= MATCH_MFMA_MIN_G and D % 32 == 0
+
+
+def _usable_pack(prepared: Optional[MatchPack], gallery: torch.Tensor, D: int, what: str) -> Optional[MatchPack]:
+    """``prepared`` if this call takes the packed entry point (`wants_pack`), else None; checked against ``gallery``, waited for."""
+    if prepared is None or gallery is None or not wants_pack(int(gallery.shape[0]), D):
+        return None
+    if not prepared.matches(gallery):
+        raise ValueError(f"{what}: `prepared` was built from a different (or since modified) gallery")
+    if D != prepared.D:
+        raise ValueError(f"{what}: embedding dim {D} != prepared gallery dim {prepared.D}")
+    prepared.wait_ready()
+    return prepared
+
+
 @_on_operand_device
 def match_prepare(gallery: torch.Tensor) -> MatchPack:
     return MatchPack(gallery)
@@ -540,44 +557,26 @@ def match_top1(emb: torch.Tensor, gallery: torch.Tensor, thresh: Optional[float]
     emb = _dev(emb, "match_top1.emb", torch.float32)
     B, D = emb.shape
     G = int(gallery.shape[0]) if gallery is not None else 0
-    if prepared is not None and G >= MATCH_MFMA_MIN_G and D % 32 == 0:
-        gallery = _dev(gallery, "match_top1.gallery", torch.float32)
-        if not prepared.matches(gallery):
-            raise ValueError("match_top1: `prepared` was built from a different (or since modified) gallery")
-        idx = torch.empty((B,), dtype=torch.int32, device=emb.device)
-        dist = torch.empty((B,), dtype=torch.float32, device=emb.device)
-        if D != prepared.D:
-            raise ValueError(f"match_top1: embedding dim {D} != prepared gallery dim {prepared.D}")
-        prepared.wait_ready()
-        ws = _match_workspace(B, G, emb.device)       # candidate records + per-probe statistics
-        split = torch.empty((B, 3 * D), dtype=torch.float16, device=emb.device)
-        ids = torch.empty((B,), dtype=torch.int32, device=emb.device) if thresh is not None else None
-        pk = _packed_buf(packed, B, emb.device)
-        _lib.check(_lib.load().frmap_match_top1_packed(emb.data_ptr(), gallery.data_ptr(), prepared.packed.data_ptr(),
-                                                       prepared.stat_w.data_ptr(), idx.data_ptr(), dist.data_ptr(),
-                                                       ids.data_ptr() if ids is not None else 0,
-                                                       pk.data_ptr() if pk is not None else 0,
-                                                       float(thresh) if thresh is not None else float("inf"), ws.data_ptr(),
-                                                       split.data_ptr(), B, G, D, _stream()), "match_top1_packed")
-        if pk is not None:
-            return idx, dist, ids, pk
-        return (idx, dist) if thresh is None else (idx, dist, ids)
     gptr = 0
     if G > 0:
         gallery = _dev(gallery, "match_top1.gallery", torch.float32)
         if gallery.shape[1] != D:
             raise ValueError(f"match_top1: embedding dim {D} != gallery dim {gallery.shape[1]}")
         gptr = gallery.data_ptr()
+    prepared = _usable_pack(prepared, gallery, D, "match_top1")
     idx = torch.empty((B,), dtype=torch.int32, device=emb.device)
     dist = torch.empty((B,), dtype=torch.float32, device=emb.device)
-    ws = _match_workspace(B, G, emb.device)
+    ws = _match_workspace(B, G, emb.device)       # candidate records + per-probe statistics
     ids = torch.empty((B,), dtype=torch.int32, device=emb.device) if thresh is not None else None
     pk = _packed_buf(packed, B, emb.device)
-    _lib.check(_lib.load().frmap_match_top1(emb.data_ptr(), gptr, idx.data_ptr(), dist.data_ptr(),
-                                            ids.data_ptr() if ids is not None else 0,
-                                            pk.data_ptr() if pk is not None else 0,
-                                            float(thresh) if thresh is not None else float("inf"), ws.data_ptr(),
-                                            B, G, D, _stream()), "match_top1")
+    outs = (idx.data_ptr(), dist.data_ptr(), ids.data_ptr() if ids is not None else 0, pk.data_ptr() if pk is not None else 0,
+            float(thresh) if thresh is not None else float("inf"), ws.data_ptr())
+    if prepared is not None:
+        split = torch.empty((B, 3 * D), dtype=torch.float16, device=emb.device)
+        _lib.check(_lib.load().frmap_match_top1_packed(emb.data_ptr(), gptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(),
+                                                       *outs, split.data_ptr(), B, G, D, _stream()), "match_top1_packed")
+    else:
+        _lib.check(_lib.load().frmap_match_top1(emb.data_ptr(), gptr, *outs, B, G, D, _stream()), "match_top1")
     if pk is not None:
         return idx, dist, ids, pk
     return (idx, dist) if thresh is None else (idx, dist, ids)
@@ -621,10 +620,8 @@ def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, label
     if labels is not None and G == 0:
         lptr = ws.data_ptr()          # (identity mode on an empty gallery: a non-null labels pointer keeps the mode)
     lbp = lab.data_ptr() if lab is not None else 0
-    if prepared is not None and G >= MATCH_MFMA_MIN_G and D % 32 == 0:
-        if not prepared.matches(gallery):
-            raise ValueError("match_topk: `prepared` was built from a different (or since modified) gallery")
-        prepared.wait_ready()
+    prepared = _usable_pack(prepared, gallery, D, "match_topk")
+    if prepared is not None:
         _lib.check(lib.frmap_match_topk_packed(emb.data_ptr(), gptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lptr,
                                                idx.data_ptr(), dist.data_ptr(), lbp, ws.data_ptr(), B, G, D, k, _stream()),
                    "match_topk_packed")
@@ -707,10 +704,8 @@ def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Option
     aptr, laptr = (a.data_ptr(), la.data_ptr()) if P else (0, 0)
     bptr, lbptr = (b.data_ptr(), lb.data_ptr()) if Q else (0, 0)
     rptr = resc.data_ptr() if resc is not None else 0
-    if prepared is not None and Q >= MATCH_MFMA_MIN_G and D % 32 == 0:
-        if not prepared.matches(b):
-            raise ValueError("verify_counts: `prepared` was built from a different (or since modified) b")
-        prepared.wait_ready()
+    prepared = _usable_pack(prepared, b, D, "verify_counts")
+    if prepared is not None:
         _lib.check(lib.frmap_verify_counts_packed(aptr, laptr, P, bptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lbptr,
                                                   Q, D, row0, thr.data_ptr(), T, out.data_ptr(), rptr, ws.data_ptr(), _stream()),
                    "verify_counts_packed")
@@ -893,10 +888,7 @@ class ModelHandle:
                 if gallery.shape[1] != self.embedding_dim:
                     raise ValueError(f"embed_and_match: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
                 gptr = gallery.data_ptr()
-                if prepared is not None and G >= MATCH_MFMA_MIN_G:
-                    if not prepared.matches(gallery):
-                        raise ValueError("embed_and_match: `prepared` was built from a different (or since modified) gallery")
-                    prepared.wait_ready()
+                if _usable_pack(prepared, gallery, self.embedding_dim, "embed_and_match") is not None:
                     ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
             idx = torch.empty((B,), dtype=torch.int32, device=x.device)
             dist = torch.empty((B,), dtype=torch.float32, device=x.device)
@@ -927,10 +919,7 @@ class ModelHandle:
                 if gallery.shape[1] != self.embedding_dim:
                     raise ValueError(f"embed_and_search: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
                 gptr = gallery.data_ptr()
-                if prepared is not None and G >= MATCH_MFMA_MIN_G:
-                    if not prepared.matches(gallery):
-                        raise ValueError("embed_and_search: `prepared` was built from a different (or since modified) gallery")
-                    prepared.wait_ready()
+                if _usable_pack(prepared, gallery, self.embedding_dim, "embed_and_search") is not None:
                     ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
             if labels is not None:
                 labels = _dev(labels, "model_embed_and_search.labels", torch.int32)
