@@ -82,6 +82,10 @@ PROTOTYPES = {
     "frmap_verify_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "frmap_verify_counts": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "frmap_verify_counts_packed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "frmap_match_radius_workspace_bytes": (_sz, [_i, _i, _i]),
+    "frmap_match_radius": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, C.c_longlong, _vp, _vp, _vp]),
+    "frmap_match_radius_packed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, C.c_longlong, _vp,
+                                       _vp, _vp]),
     "frmap_gap_norm_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _f, _i, _i, _i, _i, _i, _vp]),
     "frmap_cosine_logits": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "frmap_arcmargin_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),

@@ -54,7 +54,7 @@ struct PPParams {
   // fused MaxPool2d(2, 2) (PL = true): each wave's 112-pixel slice (whole row pairs) is walked in pool-major order
   int Wo2;         // Wi / 2
   FrmapDiv dWo2;
-  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR / MATCH_HIST> (gallery match, frmap_match_gemm): per-row statistics, records
+  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR / MATCH_HIST / MATCH_JOIN> (gallery match, frmap_match_gemm): per-row statistics, records
   const float* m_stat_a;        // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
   const float* m_stat_w;        // [G][4] of the fp32 gallery rows
   void* m_records;              // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
@@ -72,13 +72,26 @@ struct PPHistParams : PPParams {
   unsigned long long* h_rescored;
   int h_row0, h_T;
 };
+// conv1x1_pp_kernel<..., MATCH_JOIN> (threshold search): exact operands, labels and filter, the threshold's bracket, the pair list.
+struct PPJoinParams : PPParams {
+  const float* j_A;             // fp32 [M][D] (the probes)
+  const float* j_B;             // fp32 [G][D] (the gallery rows)
+  const int32_t* j_lab_a;       // (null when j_filter == 0)
+  const int32_t* j_lab_b;
+  RadiusOut j_out;
+  unsigned long long* j_rescored;
+  float j_hi;                   // the smallest fp32 >= next_up(thresh)^2
+  int j_row0, j_filter;
+};
 template <int MM> struct PPArg { using type = PPParams; };
 template <> struct PPArg<MATCH_HIST> { using type = PPHistParams; };
-// self-mode verification counts: about half the tiles (those on or below the diagonal) exit at once.  pp_xcd_remap gives each XCD
+template <> struct PPArg<MATCH_JOIN> { using type = PPJoinParams; };
+// self-mode verification counts and threshold search: about half the tiles (those on or below the diagonal) exit at once.  pp_xcd_remap gives each XCD
 // one contiguous band of tile rows, so the top band's XCD would keep ~all of its work while the bottom band's has ~none; there the
 // tiles are dealt round-robin instead (block b runs on XCD b % 8), which gives every XCD the same share of live tiles.
 __device__ __forceinline__ bool pp_hist_self(const PPParams&) { return false; }
 __device__ __forceinline__ bool pp_hist_self(const PPHistParams& p) { return p.h_row0 >= 0; }
+__device__ __forceinline__ bool pp_hist_self(const PPJoinParams& p) { return p.j_row0 >= 0; }
 
 __device__ __attribute__((aligned(4096))) unsigned int g_pp_zero[1024];
 
@@ -532,6 +545,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p) {
 // MM = MATCH_HIST: verification counts (match_epilogue_hist): certain pairs binned in LDS, the rest queued per wave in LDS and
 // re-scored exactly by the wave itself (verify_drain_queue), then one 64-bit atomicAdd per non-zero bin of the workgroup.  In self
 // mode a tile with no pair above the diagonal exits before its first DMA.
+// MM = MATCH_JOIN: threshold search (match_epilogue_join): pairs certainly beyond the threshold are dropped, the rest queued per
+// wave in LDS, re-scored exactly by the wave itself and the accepted ones listed (radius_drain_queue).  Self mode as MATCH_HIST.
 template <typename TT, int MI, int WM, int KS, int MM = MATCH_NONE>
 __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg<MM>::type p) {
   constexpr int NI = 4, WN = KS == 2 ? 2 : 8 / WM;
@@ -561,6 +576,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg
   const int m0 = mt * p.tile_px, mend = min(m0 + p.tile_px, p.M);
   if constexpr (MM == MATCH_HIST) {
     if (p.h_row0 >= 0 && nt * BN + BN - 1 <= p.h_row0 + m0) return;   // (whole workgroup, before any DMA or barrier)
+  }
+  if constexpr (MM == MATCH_JOIN) {
+    if (p.j_row0 >= 0 && nt * BN + BN - 1 <= p.j_row0 + m0) return;
   }
   const int nst = p.nchunks / KS;            // k-steps this group walks (KS = 2: chunk = grp + 2 * step)
 
@@ -681,6 +699,16 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg
     __syncthreads();
     for (int i = tid; i < nb; i += 512)
       if (hist[i]) atomicAdd(p.h_hist + i, (unsigned long long)hist[i]);
+    return;
+  } else if constexpr (MM == MATCH_JOIN) {
+    // (every wave is past its last read of the LDS tiles and no DMA is in flight: a queue and an output buffer per wave take their place)
+    const int b_base = m0 + mslice * (MI * 16), n0 = nt * BN + wn * 64;
+    unsigned short* queue = (unsigned short*)smem + wave * VERIFY_QCAP;
+    const int cnt = match_epilogue_join<MI>(acc, b_base, mend, n0, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.j_lab_a, p.j_lab_b,
+                                            p.j_row0, p.j_filter, p.j_hi, queue, lane);
+    int* obuf = (int*)(smem + 8 * VERIFY_QCAP * 2 + wave * RADIUS_OB_BYTES);
+    radius_drain_queue(queue, cnt, b_base, n0, p.j_A, p.j_B, p.m_D, p.j_out, obuf, lane);
+    if (lane == 0 && cnt) atomicAdd(p.j_rescored, (unsigned long long)cnt);
     return;
   } else if constexpr (MM != MATCH_NONE) {
     match_epilogue<MM, MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
@@ -1151,6 +1179,7 @@ static int pp1_launch(const typename PPArg<MM>::type& p, hipStream_t st) {
   if (lds < scratch) lds = scratch;
   if (lds < xch) lds = xch;
   if (MM == MATCH_HIST && lds < VERIFY_LDS_GEMM) lds = VERIFY_LDS_GEMM;
+  if (MM == MATCH_JOIN && lds < 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES)) lds = 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES);   // queues | output buffers
   hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -1224,7 +1253,8 @@ int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, c
 // (a_hi | a_hi | a_lo), gallery_packed = the G gallery rows (g_hi | g_lo | g_hi) in conv-weight order, padded to Gpad = 256-row
 // groups (match_pack_gallery_kernel), K3 = 3 D; every row carries its own power-of-two scale, whose inverse is the third float of
 // its statistics record.  mode MATCH_TOP1 / MATCH_TOPR: `out` = MatchRec / MatchRecK records [Gpad / 64][P]; MATCH_HIST: `out` =
-// the FrmapVerifyGemm.  1 = launched, 0 = shape not taken, < 0 = error; probes3 == nullptr: plan only.
+// the FrmapVerifyGemm; MATCH_JOIN: `out` = the FrmapRadiusGemm.  1 = launched, 0 = shape not taken, < 0 = error; probes3 == nullptr:
+// plan only.
 // ------------------------------------------------------------------------------------------------
 int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
                      int P, int G, int D, hipStream_t st) {
@@ -1254,6 +1284,17 @@ int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, 
   p.tile_px = wide ? 448 : 224;
   p.mtiles = (P + p.tile_px - 1) / p.tile_px;
   p.ntiles = Gpad / (wide ? 128 : 256);
+  if (mode == MATCH_JOIN) {
+    const FrmapRadiusGemm* r = (const FrmapRadiusGemm*)out;
+    PPJoinParams pj;
+    memset(&pj, 0, sizeof(pj));
+    static_cast<PPParams&>(pj) = p;
+    pj.m_records = nullptr;
+    pj.j_A = r->A; pj.j_B = r->B; pj.j_lab_a = r->lab_a; pj.j_lab_b = r->lab_b; pj.j_out = r->out; pj.j_rescored = r->rescored;
+    pj.j_hi = r->hi; pj.j_row0 = r->row0; pj.j_filter = r->filter;
+    const int rcj = wide ? pp1_launch<F16, 4, 1, MATCH_JOIN>(pj, st) : pp1_launch<F16, 2, 1, MATCH_JOIN>(pj, st);
+    return rcj ? rcj : 1;
+  }
   const int rc = mode == MATCH_TOPR ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
                  : mode == MATCH_TOP1 ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st))
                                       : (wide ? pp1_launch<F16, 4, 1, MATCH_HIST>(p, st) : pp1_launch<F16, 2, 1, MATCH_HIST>(p, st));

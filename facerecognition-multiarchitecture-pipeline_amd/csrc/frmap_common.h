@@ -149,7 +149,7 @@ __device__ __forceinline__ void match_epilogue_records(const f32x4_t (&acc)[MI][
 // tau = the k-th smallest listed U (per distinct label in identity mode) and re-scores exactly every listed row with L <= tau and
 // every row of a slot whose rest <= tau.  An identity enrolled up to R times in one slot never forces a whole-slot re-score.
 // ------------------------------------------------------------------------------------------------
-enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2, MATCH_HIST = 3 };   // MATCH_HIST: verification counts
+enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2, MATCH_HIST = 3, MATCH_JOIN = 4 };   // MATCH_HIST: verification counts, MATCH_JOIN: threshold search
 constexpr int MATCH_R = 4;
 struct __attribute__((aligned(16))) MatchRecK {   // 64 bytes
   float lo[MATCH_R];
@@ -399,6 +399,143 @@ __device__ __forceinline__ void verify_drain_queue(const unsigned short* queue, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Threshold search (frmap_match_radius[_packed], head_match.hip): every counted pair (i, j) of A x B (modes as the verification
+// counts) with (float)sqrt(match_exact_d2) <= thresh is listed once as (i, j, dist); count[i] and total are exact whatever the
+// capacity of the list.  NaN / inf distances are never accepted (thresh is finite).
+// ------------------------------------------------------------------------------------------------
+struct RadiusOut {
+  int32_t* count;              // [P] accepted pairs per row of A (zeroed by radius_prep_kernel)
+  unsigned long long* total;   // [1] accepted pairs = list slots reserved so far
+  int32_t* pair;               // [capacity][2] = (i, j); null with capacity 0
+  float* dist;                 // [capacity]
+  long long capacity;
+  float thresh;
+};
+
+// whether the labels let a pair through: 0 = all pairs, 1 = equal labels only, 2 = different labels only
+__device__ __forceinline__ bool radius_filter_ok(int filter, int la, int lb) { return filter == 0 || (la == lb) == (filter == 1); }
+
+// A wave collects its accepted pairs in its own LDS buffer (RADIUS_OB entries: (i, j) int2 [RADIUS_OB] | dist fp32 [RADIUS_OB]) and
+// reserves list slots once per full buffer, not once per batch: a slot reservation is a returning atomic on ONE address for the whole
+// device, and at 1 % of 134 M pairs accepted, one per 8-pair batch made the call 2.5x the time of the same GEMM without it.
+constexpr int RADIUS_OB = 256;
+constexpr int RADIUS_OB_BYTES = RADIUS_OB * 12;
+
+// write out the wave's w buffered pairs: ONE atomic reserves their slots, then the lanes copy (i, j, dist) where the slot lies inside
+// the list (whole lines: consecutive lanes, consecutive slots)
+__device__ __forceinline__ void radius_flush(const RadiusOut& o, const int* obuf, int& w, int lane) {
+  if (!w) return;                                  // (wave-uniform)
+  unsigned long long base = 0ull;
+  if (lane == 0) base = atomicAdd(o.total, (unsigned long long)w);
+  base = __shfl(base, 0, 64);
+  __builtin_amdgcn_wave_barrier();                 // (the buffer was written by other lanes of this wave)
+  for (int e = lane; e < w; e += 64) {
+    const long long slot = (long long)base + e;
+    if (slot < o.capacity) {
+      *(int2*)(o.pair + 2 * slot) = ((const int2*)obuf)[e];
+      o.dist[slot] = ((const float*)(obuf + 2 * RADIUS_OB))[e];
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  w = 0;
+}
+
+// NB pairs whose exact d2 every lane holds: lane q < NB takes pair q.  The accepted ones bump their row's count and join the wave's
+// buffer (w entries so far, wave-uniform), which is flushed before it could overflow; the caller flushes what is left at its end.
+template <int NB>
+__device__ __forceinline__ void radius_emit(const double (&d2)[NB], const bool (&valid)[NB], const int (&pi)[NB], const int (&pj)[NB],
+                                            const RadiusOut& o, int* obuf, int& w, int lane) {
+  double d = 0.0;
+  bool v = false;
+  int i = 0, j = 0;
+#pragma unroll
+  for (int q = 0; q < NB; ++q)
+    if (lane == q) { d = d2[q]; v = valid[q]; i = pi[q]; j = pj[q]; }
+  const float dist = (float)sqrt(d);
+  const bool hit = v && dist <= o.thresh;          // (NaN compares false)
+  const unsigned long long m = __ballot(hit);
+  if (!m) return;                                  // (wave-uniform)
+  if (hit) {
+    atomicAdd(o.count + i, 1);
+    const int pos = w + __popcll(m & ((1ull << lane) - 1ull));
+    ((int2*)obuf)[pos] = make_int2(i, j);
+    ((float*)(obuf + 2 * RADIUS_OB))[pos] = dist;
+  }
+  w += __popcll(m);
+  if (w > RADIUS_OB - NB) radius_flush(o, obuf, w, lane);
+}
+
+// Epilogue of conv1x1_pp_kernel<..., MATCH_JOIN>: bounds L <= d2 <= U as match_epilogue_hist.  With hi = the smallest fp32 >=
+// next_up(thresh)^2, a pair with L > hi has (float)sqrt(d2) > thresh and is dropped at once, like a pair outside the problem, on or
+// below the diagonal (self mode) or filtered out by its labels.  Every other pair - surely accepted or undecided: the list carries
+// the exact distance, so both need the exact d2 - goes to this wave's LDS queue (the layout of match_epilogue_hist's: it holds the
+// wave's whole 112 x 64 block).  A NaN bound is never > hi: such a pair is re-scored and rejected there.  Returns the queue length.
+template <int MI>
+__device__ __forceinline__ int match_epilogue_join(const f32x4_t (&acc)[MI][4], int b_base, int b_end, int n0, int G, int D, int M,
+                                                   const float* __restrict__ stat_a, const float* __restrict__ stat_w,
+                                                   const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b, int row0,
+                                                   int filter, float hi, unsigned short* queue, int lane) {
+  const int lr = lane & 15, g = lane >> 4;
+  const float eps = 1e-6f, kf = (float)D, keps = kf * eps * eps, kap = match_kappa(3 * D);
+  int cnt = 0;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int b = b_base + mi * 16 + lr;
+    const f32x4_t sa = *(const f32x4_t*)(stat_a + 4 * (size_t)min(b, M - 1));
+    const float a2 = sa[0], as = sa[1], ai = sa[2], ab = sa[3] + keps;
+    const int la = filter ? lab_a[min(b, M - 1)] : 0;
+    const int nmin = row0 >= 0 ? row0 + b + 1 : 0;   // self mode: only rows after the probe's own
+    const float* sw_p = stat_w;                      // (opaque copies: see match_epilogue_hist)
+    const int32_t* lb_p = lab_b;
+    asm volatile("" : "+s"(sw_p), "+s"(lb_p));
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int n = n0 + ni * 16 + 4 * g + j;
+        const f32x4_t sw = *(const f32x4_t*)(sw_p + 4 * (size_t)min(n, G - 1));
+        const float d2 = a2 + sw[0] - 2.f * (acc[mi][ni][j] * ai * sw[2]) + 2.f * eps * (as - sw[1]) + keps;
+        const float L = d2 - kap * (ab + sw[3]);
+        bool keep = n < G && b < b_end && n >= nmin && !(L > hi);
+        if (filter && keep) keep = radius_filter_ok(filter, la, lb_p[min(n, G - 1)]);
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+          const int pos = cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+          queue[pos] = (unsigned short)(((mi * 16 + lr) << 6) | (ni * 16 + 4 * g + j));
+        }
+        cnt += __popcll(m);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return cnt;
+}
+
+// re-score this wave's queued pairs exactly, 8 at a time, and list the accepted ones
+__device__ __forceinline__ void radius_drain_queue(const unsigned short* queue, int cnt, int b_base, int n0, const float* __restrict__ A,
+                                                   const float* __restrict__ B, int D, const RadiusOut& o, int* obuf, int lane) {
+  constexpr int NB = 8;
+  int w = 0;
+  for (int q0 = 0; q0 < cnt; q0 += NB) {
+    const float* pa[NB];
+    const float* pb[NB];
+    bool valid[NB];
+    int pi[NB], pj[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      valid[q] = q0 + q < cnt;
+      const int e = queue[valid[q] ? q0 + q : q0];
+      pi[q] = b_base + (e >> 6); pj[q] = n0 + (e & 63);
+      pa[q] = A + (size_t)pi[q] * D; pb[q] = B + (size_t)pj[q] * D;
+    }
+    double d2[NB];
+    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
+    radius_emit<NB>(d2, valid, pi, pj, o, obuf, w, lane);
+  }
+  radius_flush(o, obuf, w, lane);
+}
+
 // the epilogue of a match GEMM in mode MM (MATCH_TOP1: MatchRec records, MATCH_TOPR: MatchRecK records, same [slot][M] layout)
 template <int MM, int MI>
 __device__ __forceinline__ void match_epilogue(const f32x4_t (&acc)[MI][4], int b_base, int b_end, int n0, int G, int D, int M,
@@ -643,9 +780,21 @@ struct FrmapVerifyGemm {
   int row0;                 // -1: cross mode; else A = rows [row0, row0 + P) of B, pairs with row0 + i < j
   int T;
 };
+// what the threshold search's match GEMM (MATCH_JOIN) takes besides the operands
+struct FrmapRadiusGemm {
+  const float* A;           // fp32 [P][D]
+  const float* B;           // fp32 [Q][D]
+  const int32_t* lab_a;     // may be null when filter == 0
+  const int32_t* lab_b;
+  RadiusOut out;
+  unsigned long long* rescored;   // u64 += pairs re-scored exactly
+  float hi;                 // the smallest fp32 >= next_up(thresh)^2
+  int row0;                 // as FrmapVerifyGemm
+  int filter;               // 0 = all pairs, 1 = equal labels only, 2 = different labels only
+};
 // The split-fp16 match GEMM (conv1x1_pp_kernel<F16, ..., mode>, conv_pp.hip) of P probes against a packed gallery of G rows:
 // mode MATCH_TOP1 / MATCH_TOPR writes MatchRec / MatchRecK records to `out` ([Gpad / 64][P]); MATCH_HIST takes a FrmapVerifyGemm*
-// as `out`.  1 = launched, 0 = shape not taken (nothing launched), < 0 = error; probes3 == nullptr: plan only.
+// as `out`, MATCH_JOIN a FrmapRadiusGemm*.  1 = launched, 0 = shape not taken (nothing launched), < 0 = error; probes3 == nullptr: plan only.
 int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
                      int P, int G, int D, hipStream_t st);
 // label_out[0 .. n) = -1 (frmap_match_topk's k = 1 entry-mode outputs; head_match.hip)

@@ -5,6 +5,7 @@
 //   frmap_match_top1        compare_faces' arg-min over the gallery    app.py:58-63
 //   frmap_match_topk        the k nearest rows / identities, exact      (top-k search)
 //   frmap_verify_counts     exact genuine / impostor pair counts per threshold (verification ROC)
+//   frmap_match_radius      every pair within a threshold, with its exact distance (watch lists, duplicate enrolments: app.py:428-436)
 //   frmap_cosine_logits     class-centre cosine logits + arg-max       hyperparameter_tuning.py:1038-1046
 //   frmap_arcmargin_eval    ArcMarginProduct.forward, eval mode        face_models.py:351-429
 //
@@ -1419,6 +1420,146 @@ extern "C" int frmap_verify_counts_packed(const float* a, const int32_t* label_a
   if (!taken)
     if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) return rc;
   return verify_finish(w, T, accepted_out, rescored_out, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Threshold search (frmap_match_radius[_packed]): WHICH pairs the verification counts accept at one threshold.  Every counted pair
+// (i, j) of A x B (cross / self mode as above; pair_filter 0 = all, 1 = equal labels, 2 = different labels) with
+// (float)sqrt(match_exact_d2) <= thresh is listed once as (i, j, dist), in no particular order; count_out[i] and total_out are exact
+// whatever the capacity.  workspace: rescored u64 (when the caller passes no rescored_out) | probe statistics [P][4] | probe split
+// fp16 [P][3 D].
+// ------------------------------------------------------------------------------------------------
+struct RadiusWs {
+  unsigned long long* misc;
+  float* stat_a;
+  void* split;
+};
+static RadiusWs radius_ws(void* ws, int P) {
+  RadiusWs w;
+  char* c = (char*)ws;
+  w.misc = (unsigned long long*)c; c += 256;
+  w.stat_a = (float*)c; c += align256_sz(16 * (size_t)P);
+  w.split = c;
+  return w;
+}
+
+__global__ void radius_prep_kernel(int32_t* __restrict__ count, int P, unsigned long long* __restrict__ total,
+                                   unsigned long long* __restrict__ rescored) {
+  const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
+  for (int i = i0; i < P; i += gridDim.x * blockDim.x) count[i] = 0;
+  if (i0 == 0) { *total = 0ull; *rescored = 0ull; }
+}
+
+// Exact scan, the shape of verify_scan_kernel: one workgroup = VS_PB rows of A x VS_QB rows of B, each wave scores 8 pairs at a time
+// with match_exact_d2's arithmetic and lists the accepted ones (radius_emit, the GEMM path's own emit step).
+__global__ __launch_bounds__(256) void radius_scan_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                          const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b,
+                                                          int P, int Q, int D, int row0, int filter, RadiusOut o) {
+  const int i0 = blockIdx.x * VS_PB, j0 = blockIdx.y * VS_QB;
+  const int jlast = min(j0 + VS_QB, Q) - 1;
+  if (row0 >= 0 && jlast <= row0 + i0) return;     // self mode: nothing above the diagonal here
+  __shared__ int s_obuf[4][3 * RADIUS_OB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int* obuf = s_obuf[wave];
+  int w = 0;
+  constexpr int NB = 8;
+  for (int base = wave * NB; base < VS_PB * VS_QB; base += 4 * NB) {
+    const float* pa[NB];
+    const float* pb[NB];
+    bool valid[NB], any = false;
+    int pi[NB], pj[NB];
+#pragma unroll
+    for (int q = 0; q < NB; ++q) {
+      const int i = i0 + (base + q) / VS_QB, j = j0 + (base + q) % VS_QB;
+      valid[q] = i < P && j < Q && (row0 < 0 || row0 + i < j);
+      const int ic = min(i, P - 1), jc = min(j, Q - 1);
+      if (filter && valid[q]) valid[q] = radius_filter_ok(filter, lab_a[ic], lab_b[jc]);
+      any |= valid[q];
+      pi[q] = ic; pj[q] = jc;
+      pa[q] = A + (size_t)ic * D; pb[q] = B + (size_t)jc * D;
+    }
+    if (!any) continue;                               // (wave-uniform)
+    double d2[NB];
+    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
+    radius_emit<NB>(d2, valid, pi, pj, o, obuf, w, lane);
+  }
+  radius_flush(o, obuf, w, lane);
+}
+
+extern "C" size_t frmap_match_radius_workspace_bytes(int P, int Q, int D) {
+  (void)Q;
+  const size_t p = P > 0 ? (size_t)P : 0, d = D > 0 ? (size_t)D : 0;
+  return 256 + align256_sz(16 * p) + align256_sz(6 * p * d) + 256;
+}
+
+static int radius_check(const char* what, const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q,
+                        int D, int a_row0, float thresh, int pair_filter, int32_t* count_out, uint64_t* total_out, int32_t* pair_out,
+                        float* dist_out, long long capacity, void* workspace) {
+  FRMAP_REQUIRE(total_out && workspace, "%s: null pointer", what);
+  FRMAP_REQUIRE(__builtin_isfinite(thresh) && thresh >= 0.f, "%s: thresh must be finite and >= 0", what);
+  FRMAP_REQUIRE(pair_filter >= 0 && pair_filter <= 2, "%s: pair_filter=%d (0 all, 1 equal labels, 2 different labels)", what, pair_filter);
+  FRMAP_REQUIRE(P >= 0 && Q >= 0 && D > 0 && D % 4 == 0, "%s: bad shape P=%d Q=%d D=%d (D %% 4 == 0)", what, P, Q, D);
+  FRMAP_REQUIRE(P == 0 || (a && count_out && (label_a || !pair_filter)), "%s: null A, its labels or count_out", what);
+  FRMAP_REQUIRE(Q == 0 || (b && (label_b || !pair_filter)), "%s: null B or its labels", what);
+  FRMAP_REQUIRE(capacity >= 0 && (capacity == 0 || (pair_out && dist_out)), "%s: capacity=%lld needs pair_out and dist_out", what, capacity);
+  FRMAP_REQUIRE(a_row0 == -1 || (a_row0 >= 0 && (long long)a_row0 + P <= Q),
+                "%s: a_row0=%d with P=%d is not a block of B's %d rows (-1: cross mode)", what, a_row0, P, Q);
+  FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "%s: Q=%d too large for one call (shard B)", what, Q);
+  return 0;
+}
+
+static int radius_prep(int32_t* count_out, int P, uint64_t* total_out, unsigned long long* resc, hipStream_t st) {
+  const int blocks = P > 256 * 1024 ? 1024 : P > 256 ? (P + 255) / 256 : 1;
+  hipLaunchKernelGGL(radius_prep_kernel, dim3(blocks), dim3(256), 0, st, count_out, P, (unsigned long long*)total_out, resc);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+static int radius_scan(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D, int a_row0,
+                       int pair_filter, const RadiusOut& o, hipStream_t st) {
+  if (P > 0 && Q > 0)
+    hipLaunchKernelGGL(radius_scan_kernel, dim3((P + VS_PB - 1) / VS_PB, (Q + VS_QB - 1) / VS_QB), dim3(256), 0, st, a, b, label_a,
+                       label_b, P, Q, D, a_row0, pair_filter, o);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int frmap_match_radius(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D,
+                                  int a_row0, float thresh, int pair_filter, int32_t* count_out, uint64_t* total_out, int32_t* pair_out,
+                                  float* dist_out, long long capacity, uint64_t* rescored_out, void* workspace, void* stream) {
+  if (int rc = radius_check("match_radius", a, label_a, P, b, label_b, Q, D, a_row0, thresh, pair_filter, count_out, total_out, pair_out,
+                            dist_out, capacity, workspace))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const RadiusWs w = radius_ws(workspace, P);
+  if (int rc = radius_prep(count_out, P, total_out, rescored_out ? (unsigned long long*)rescored_out : w.misc, st)) return rc;
+  const RadiusOut o = {count_out, (unsigned long long*)total_out, pair_out, dist_out, capacity, thresh};
+  return radius_scan(a, label_a, P, b, label_b, Q, D, a_row0, pair_filter, o, st);
+}
+
+extern "C" int frmap_match_radius_packed(const float* a, const int32_t* label_a, int P, const float* b, const void* b_packed,
+                                         const float* stat_w, const int32_t* label_b, int Q, int D, int a_row0, float thresh,
+                                         int pair_filter, int32_t* count_out, uint64_t* total_out, int32_t* pair_out, float* dist_out,
+                                         long long capacity, uint64_t* rescored_out, void* workspace, void* stream) {
+  if (int rc = radius_check("match_radius_packed", a, label_a, P, b, label_b, Q, D, a_row0, thresh, pair_filter, count_out, total_out,
+                            pair_out, dist_out, capacity, workspace))
+    return rc;
+  FRMAP_REQUIRE(b_packed && stat_w, "match_radius_packed: null pointer");
+  FRMAP_REQUIRE(Q > 0 && D % 32 == 0, "match_radius_packed: bad shape Q=%d D=%d (Q > 0, D %% 32 == 0)", Q, D);
+  hipStream_t st = (hipStream_t)stream;
+  const RadiusWs w = radius_ws(workspace, P);
+  unsigned long long* resc = rescored_out ? (unsigned long long*)rescored_out : w.misc;
+  if (int rc = radius_prep(count_out, P, total_out, resc, st)) return rc;
+  const RadiusOut o = {count_out, (unsigned long long*)total_out, pair_out, dist_out, capacity, thresh};
+  // the bracket of verify_prep_kernel, for one threshold known on the host: d2 > hi => sqrt(d2) >= next_up(thresh) => dist > thresh
+  const double u = (double)nextafterf(thresh, INFINITY), u2 = u * u;
+  float hi = (float)u2;
+  if ((double)hi < u2) hi = nextafterf(hi, INFINITY);
+  FrmapRadiusGemm r = {a, b, label_a, label_b, o, resc, hi, a_row0, pair_filter};
+  const int taken = match_packed_gemm(MATCH_JOIN, a, b_packed, stat_w, w.stat_a, w.split, &r, P, Q, D, st);
+  if (taken < 0) return taken;
+  if (!taken) return radius_scan(a, label_a, P, b, label_b, Q, D, a_row0, pair_filter, o, st);
+  return 0;
 }
 
 extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits_out, int32_t* argmax_out,

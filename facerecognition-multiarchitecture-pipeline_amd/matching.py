@@ -249,6 +249,102 @@ def compare_faces_topk(emb, refs, thresh, k: int, by: str = "entry"):
     return out
 
 
+def csr_by_dist(pairs: torch.Tensor, dists: torch.Tensor, counts: torch.Tensor):
+    """A pair list ``(pairs [n, 2] = (i, j), dists [n], counts [B])`` in any order -> CSR ``(offsets int64 [B + 1], rows int32 [n],
+    dists fp32 [n])`` with probe i's segment ``[offsets[i], offsets[i + 1])`` ordered by (dist, row): two stable sorts (by (dist, j),
+    then by i).  Distances are >= 0 and never NaN, so their bit patterns order as the values do."""
+    offsets = torch.zeros((counts.shape[0] + 1,), dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts.to(torch.int64), 0, out=offsets[1:])
+    if pairs.shape[0] > 1:
+        key = (dists.view(torch.int32).to(torch.int64) << 32) | pairs[:, 1].to(torch.int64)
+        o1 = torch.argsort(key)
+        o2 = torch.sort(pairs[o1, 0], stable=True).indices
+        order = o1[o2]
+        pairs, dists = pairs[order], dists[order]
+    return offsets, pairs[:, 1].contiguous(), dists.contiguous()
+
+
+def search_radius(emb: torch.Tensor, gallery, thresh: float):
+    """B x D device embeddings -> EVERY gallery entry within ``thresh`` of each probe under compare_faces' exact distance (where
+    `search_batch` lists the k nearest): CSR ``(offsets int64 [B + 1], rows int32 [n], dists fp32 [n])`` on the device, probe b's
+    entries at ``[offsets[b], offsets[b + 1])`` ordered by (dist, row) - the order of `search_batch`.  ``gallery``: a `Gallery` or
+    the reference's refs list.  One synchronisation (the size of the answer)."""
+    g = _as_gallery(gallery, emb.device if isinstance(emb, torch.Tensor) and emb.is_cuda else "cuda")
+    e = emb.to(torch.float32)
+    if e.dim() == 1:
+        e = e.unsqueeze(0)
+    b = g.matrix if len(g) else torch.empty((0, e.shape[1]), dtype=torch.float32, device=e.device)
+    pairs, dists, counts = ops.match_radius(e, thresh, b, prepared=g.prepared if len(g) else None)
+    return csr_by_dist(pairs, dists, counts)
+
+
+def compare_faces_all(emb, refs, thresh):
+    """compare_faces' full answer: EVERY ``(name, dist, idx)`` with ``dist <= thresh`` (`app.py:50-64` names only the nearest one),
+    ascending by (dist, idx); ``[]`` for a ``None`` embedding, empty refs or a bad threshold - never raises.  When non-empty its first
+    element is compare_faces' answer (distances are the exact float64-summed ones; on galleries of <= 64 rows compare_faces sums in
+    fp32 and the two can differ in the last bit).  ``refs``: a refs list or a `Gallery`."""
+    if emb is None or refs is None or len(refs) == 0:
+        return []
+    try:
+        dev = emb.device if emb.is_cuda else torch.device("cuda")
+        g = _as_gallery(refs, dev)
+        e = emb.detach().reshape(1, -1).to(device=dev, dtype=torch.float32)
+        _, rows, dists = search_radius(e, g, min(float(thresh), 3.4028234663852886e38))   # (inf: every finite distance)
+        rec = torch.stack((rows, dists.view(torch.int32))).cpu().numpy()      # the one host copy of the answer: [2, n]
+    except (ValueError, TypeError):
+        return []
+    return [(g.names[int(i)], float(d), int(i)) for i, d in zip(rec[0], rec[1].view(np.float32))]
+
+
+def duplicate_pairs(gallery, thresh: float, which: str = "all", labels: Optional[torch.Tensor] = None):
+    """The enrolment pairs of a gallery within ``thresh`` of each other (`app.py:428-436` appends without de-duplicating):
+    ``(pairs int32 [n, 2] with i < j, dists fp32 [n])`` on the device, sorted by (i, j).  ``gallery``: a `Gallery` (its own `labels`
+    and prepared pack are used) or an fp32 [N, D] device tensor (then ``labels`` for ``which`` = "same" / "different": pairs of one /
+    of two identities - the pairs behind a false-accept rate are ``which="different"``)."""
+    if isinstance(gallery, Gallery):
+        if labels is not None:
+            raise ValueError("duplicate_pairs: a Gallery supplies its own labels")
+        x, prep = gallery.matrix, gallery.prepared
+        labels = gallery.labels if which != "all" else None
+    else:
+        x, prep = gallery, None
+    pairs, dists, _ = ops.match_radius(x, thresh, labels_a=labels, which=which, prepared=prep)
+    return pairs, dists
+
+
+def components_of_pairs(n: int, pairs) -> np.ndarray:
+    """Connected components of the graph on ``n`` nodes with edges ``pairs`` ([m, 2] host integers): int64 [n] cluster ids, clusters
+    numbered 0, 1, ... in order of their lowest node.  Union-find, the lower root always wins, so a root IS its cluster's lowest node."""
+    parent = list(range(n))
+
+    def find(v):
+        root = v
+        while parent[root] != root:
+            root = parent[root]
+        while parent[v] != root:
+            parent[v], v = root, parent[v]
+        return root
+
+    for i, j in np.asarray(pairs, dtype=np.int64).reshape(-1, 2).tolist():
+        ri, rj = find(i), find(j)
+        if ri != rj:
+            parent[max(ri, rj)] = min(ri, rj)
+    roots = np.fromiter((find(v) for v in range(n)), dtype=np.int64, count=n)
+    number = np.cumsum(roots == np.arange(n)) - 1          # a root's rank among the roots, in node order
+    return number[roots].astype(np.int64)
+
+
+def cluster_embeddings(emb: torch.Tensor, thresh: float) -> torch.Tensor:
+    """Group unlabelled embeddings (a photo collection): int64 [N] cluster ids on the host = the connected components of the graph
+    that joins two rows when their exact distance is <= ``thresh`` (single linkage), numbered by each cluster's lowest row.  The pair
+    list comes from the device (`duplicate_pairs`); the union-find over it runs on the host."""
+    x = emb.to(torch.float32)
+    if x.dim() != 2:
+        raise ValueError("cluster_embeddings: emb must be [N, D]")
+    pairs, _ = duplicate_pairs(x, thresh)
+    return torch.from_numpy(components_of_pairs(int(x.shape[0]), pairs.cpu().numpy()))
+
+
 def threshold_for_far(gallery, far: float, thresholds=None) -> Tuple[Optional[float], Optional[float]]:
     """The largest threshold (of ``thresholds``, default `evaluate.default_thresholds`) at which at most a fraction ``far`` of the
     impostor pairs of ``gallery`` (a `Gallery` or a refs list; identities = `Gallery.labels`) would be accepted, and the share of

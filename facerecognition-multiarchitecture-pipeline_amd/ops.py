@@ -715,6 +715,100 @@ def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Option
     return (out, resc) if return_rescored else out
 
 
+_RADIUS_WHICH = {"all": 0, "same": 1, "different": 2}
+
+
+def match_radius(a: torch.Tensor, thresh: float, b: Optional[torch.Tensor] = None, *, labels_a: Optional[torch.Tensor] = None,
+                 labels_b: Optional[torch.Tensor] = None, which: str = "all", a_row0: Optional[int] = None,
+                 prepared: Optional[MatchPack] = None, capacity: Optional[int] = None, return_rescored: bool = False):
+    """Exact threshold search: every counted pair (i, j) whose distance ``(float) sqrt(d2)`` (the one `match_topk` reports and
+    `verify_counts` thresholds) is ``<= thresh``; NaN / inf distances are never listed.  Modes as `verify_counts`: ``b=None`` is self
+    mode over ``a`` (every unordered pair once, i < j); ``b`` with ``a_row0`` is self mode with ``a`` = rows [a_row0, a_row0 + len(a))
+    of ``b`` (pairs with a_row0 + i < j; i indexes ``a``, j indexes ``b``; shards over a_row0 partition the whole); ``b`` alone is
+    cross mode.  ``which``: "all", or "same" / "different" = pairs of equal / different labels only (then labels are required).
+    ``thresh``: a finite host float >= 0.
+
+    ``capacity=None``: a count-only call, one read of the total (the call's one synchronisation), then the fill: returns
+    ``(pairs int32 [n, 2], dists fp32 [n], counts int32 [P])`` sorted by (i, j); ``counts[i]`` = accepted pairs of row i.
+    ``capacity=<int>``: ONE asynchronous call (graph-capturable) into fresh buffers of that many slots: returns
+    ``(pairs int32 [capacity, 2], dists fp32 [capacity], counts int32 [P], total int64 [1])``, the first ``min(total, capacity)``
+    slots filled in no particular order; ``counts`` and ``total`` are exact whatever the capacity (0: count only).
+    ``return_rescored``: also int64 [1] = the pairs the GEMM path scored exactly, appended to either result.
+    Path choice as `verify_counts`: a ``prepared`` B of >= `MATCH_MFMA_MIN_G` rows with D % 32 == 0 runs on the fp16 MFMA GEMM, whose
+    epilogue drops the pairs certainly beyond the threshold and re-scores the rest; everything else on an exact scan.  Same answer."""
+    a = _dev(a, "match_radius.a", torch.float32)
+    if a.dim() != 2:
+        raise ValueError("match_radius: a must be [P, D]")
+    P, D = int(a.shape[0]), int(a.shape[1])
+    if which not in _RADIUS_WHICH:
+        raise ValueError(f"match_radius: which must be 'all', 'same' or 'different', got {which!r}")
+    filt = _RADIUS_WHICH[which]
+    thresh = float(thresh)
+    if not 0.0 <= thresh <= float(np.finfo(np.float32).max):          # (NaN fails both; the library takes an fp32)
+        raise ValueError(f"match_radius: thresh must be finite and >= 0, got {thresh}")
+
+    def labels(t, n, what):
+        if t is None:
+            if filt:
+                raise ValueError(f"match_radius: which={which!r} needs {what}")
+            return None
+        t = _dev(t, f"match_radius.{what}").to(torch.int32).reshape(-1)
+        if t.shape[0] != n:
+            raise ValueError(f"match_radius: {what} must hold {n} labels, got {t.shape[0]}")
+        return t
+
+    la = labels(labels_a, P, "labels_a")
+    if b is None:
+        if labels_b is not None or a_row0 not in (None, 0):
+            raise ValueError("match_radius: self mode over `a` (b=None) takes no labels_b / a_row0")
+        b, lb, row0 = a, la, 0
+    else:
+        b = _dev(b, "match_radius.b", torch.float32)
+        if b.dim() != 2 or int(b.shape[1]) != D:
+            raise ValueError(f"match_radius: b must be [Q, {D}]")
+        lb = labels(labels_b, int(b.shape[0]), "labels_b")
+        row0 = -1 if a_row0 is None else int(a_row0)
+        if a_row0 is not None and not (row0 >= 0 and row0 + P <= int(b.shape[0])):
+            raise ValueError(f"match_radius: a_row0={row0} with {P} rows is not a block of b's {int(b.shape[0])} rows")
+    Q = int(b.shape[0])
+    if capacity is not None and int(capacity) < 0:
+        raise ValueError(f"match_radius: capacity={capacity} must be >= 0")
+    lib = _lib.load()
+    dev = a.device
+    counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int64, device=dev)
+    resc = torch.empty((1,), dtype=torch.int64, device=dev) if return_rescored else None
+    ws = torch.empty((lib.frmap_match_radius_workspace_bytes(P, Q, D),), dtype=torch.uint8, device=dev)
+    aptr, laptr = (a.data_ptr(), la.data_ptr() if la is not None else 0) if P else (0, 0)
+    bptr, lbptr = (b.data_ptr(), lb.data_ptr() if lb is not None else 0) if Q else (0, 0)
+    rptr = resc.data_ptr() if resc is not None else 0
+    prepared = _usable_pack(prepared, b, D, "match_radius")
+
+    def call(cap):
+        pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+        dists = torch.empty((cap,), dtype=torch.float32, device=dev)
+        outs = (counts.data_ptr() if P else 0, total.data_ptr(), pairs.data_ptr() if cap else 0, dists.data_ptr() if cap else 0, cap,
+                rptr, ws.data_ptr(), _stream())
+        if prepared is not None:
+            _lib.check(lib.frmap_match_radius_packed(aptr, laptr, P, bptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lbptr,
+                                                     Q, D, row0, thresh, filt, *outs), "match_radius_packed")
+        else:
+            _lib.check(lib.frmap_match_radius(aptr, laptr, P, bptr, lbptr, Q, D, row0, thresh, filt, *outs), "match_radius")
+        return pairs, dists
+
+    tail = (resc,) if return_rescored else ()
+    if capacity is not None:
+        pairs, dists = call(int(capacity))
+        return (pairs, dists, counts, total) + tail
+    call(0)
+    n = int(total.item())
+    pairs, dists = call(n)
+    if n > 1:                     # order by (i, j): one sort of the packed 64-bit key
+        order = torch.argsort((pairs[:, 0].to(torch.int64) << 32) | pairs[:, 1].to(torch.int64))
+        pairs, dists = pairs[order], dists[order]
+    return (pairs, dists, counts) + tail
+
+
 def gap_linear_norm(fmap: torch.Tensor, wt: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
                     eps: float = 1e-12, want_pre: bool = False, relu: bool = False):
     """ArcFaceNet head in one launch (`face_models.py:573-590`): global average pool of the NHWC trunk map [B,H,W,K] ->

@@ -383,6 +383,32 @@ int frmap_verify_counts_packed(const float* a, const int32_t* label_a, int P, co
                                const float* stat_w, const int32_t* label_b, int Q, int D, int a_row0, const float* thresholds,
                                int T, uint64_t* accepted_out, uint64_t* rescored_out, void* workspace, void* stream);
 
+/* Exact threshold search: WHICH pairs lie within a threshold (every enrolment a watch list should report for a probe, where
+ * src/app.py:50-64 names only the nearest one; the duplicate pairs of a gallery that src/app.py:428-436 appends to without
+ * de-duplicating; the impostor pairs behind a false-accept rate).  Operands, distance, a_row0 (cross / self mode, shards) as the
+ * verification counts.  A counted pair (i, j) - i indexes A, j indexes B - is accepted iff dist(i, j) <= thresh (NaN / inf never)
+ * and pair_filter lets it through: 0 = all pairs (labels may be NULL), 1 = equal labels only, 2 = different labels only.
+ *   thresh:       finite, >= 0 (a host value: checked before any launch).
+ *   count_out:    int32 [P]  = accepted pairs of row i of A;  total_out: uint64 [1] = accepted pairs.  Both exact whatever `capacity`.
+ *   pair_out:     int32 [capacity][2] = (i, j);  dist_out: fp32 [capacity] = dist(i, j).  total <= capacity: slots [0, total) hold
+ *                 every accepted pair exactly once, in no particular order; otherwise the first `capacity` slots hold distinct
+ *                 accepted pairs.  capacity = 0 with NULL pair_out / dist_out is a count-only call.
+ *   rescored_out: optional uint64 [1] = pairs the GEMM path scored exactly (0 on the scan).
+ *   workspace:    frmap_match_radius_workspace_bytes(P, Q, D) bytes (device, caller-owned, 256-byte aligned).
+ * frmap_match_radius scores every counted pair exactly.  frmap_match_radius_packed: B prepared by frmap_match_pack_gallery
+ * (D % 32 == 0, Q > 0) runs on the fp16 MFMA GEMM, whose epilogue drops every pair whose error band lies beyond the threshold and
+ * scores the rest exactly; a shape the GEMM does not take is answered as frmap_match_radius answers it.  Same outputs either way.
+ * Nothing is allocated or synchronised; every launch goes to `stream` (graph-capturable).  Bad arguments are rejected (-1) before
+ * any launch. */
+size_t frmap_match_radius_workspace_bytes(int P, int Q, int D);
+int frmap_match_radius(const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q, int D,
+                       int a_row0, float thresh, int pair_filter, int32_t* count_out, uint64_t* total_out, int32_t* pair_out,
+                       float* dist_out, long long capacity, uint64_t* rescored_out, void* workspace, void* stream);
+int frmap_match_radius_packed(const float* a, const int32_t* label_a, int P, const float* b, const void* b_packed,
+                              const float* stat_w, const int32_t* label_b, int Q, int D, int a_row0, float thresh,
+                              int pair_filter, int32_t* count_out, uint64_t* total_out, int32_t* pair_out, float* dist_out,
+                              long long capacity, uint64_t* rescored_out, void* workspace, void* stream);
+
 /* The tail of the ResNet-18 ('cnn') embed-and-match step for small galleries in ONE launch, one workgroup per face:
  * AdaptiveAvgPool2d(1) of the trunk map (face_models.py:100) -> optional F.normalize(eps) -> compare_faces' scan
  * (src/app.py:58-64) exactly as frmap_match_top1 does it for G <= 64.
