@@ -893,6 +893,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_pp_kernel(const PPParams p) 
 // output row, + extra (s1: 3 = one row above, one below; s2 half-resolution maps: 2) - evaluated exactly as the kernels
 // do, over one period of the tile start positions
 static int pp_max_rows(long long M, int tile_px, int howo, int wo, int hp, int extra) {
+  // batch-invariant planning: the bound of an unbounded batch (every phase a tile start can have against the image grid: howo
+  // full tiles), so that whether a layer takes these kernels, and with how many halo pieces, follows from the per-image geometry
+  // alone.  With the actual M a tile that spans several small images (5 x 5 maps: 8 per tile) needed fewer rows at B = 1 than at
+  // B = 8, and a 160 x 160 input's last stride-2 layer ran on this kernel for one face and on another for eight.
+  if (frmap_batch_invariant()) M = (long long)howo * tile_px;
   // (memoised: the planner runs on every launch, the scan is up to one image's worth of tile starts)
   static std::mutex mu;
   static std::map<std::array<long long, 6>, int> memo;

@@ -24,6 +24,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
+from . import frames as _frames
 from . import gallery_io, ops
 
 REC_THRESH = 1.0                       # `app.py:20`
@@ -432,6 +433,81 @@ def embed_and_match(model, x: torch.Tensor, gallery, thresh: float = REC_THRESH,
         return ops.match_top1(emb.to(torch.float32), g.matrix, thresh, packed=packed, prepared=g.prepared)[3]
     _idx, dist, ids = ops.match_top1(emb.to(torch.float32), g.matrix, thresh, prepared=g.prepared)
     return ids, dist
+
+
+def _box_crops(model, frame, boxes, probs, size, det_thresh):
+    """clip_boxes + one crop launch: (uint8 [n, h, w, 3] RGB crops on the model's device, kept box indices)."""
+    from . import resize as _resize
+    shape = frame.shape
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError("expected one H×W×3 uint8 BGR frame")
+    rois, kept = _frames.clip_boxes(boxes, probs, shape, det_thresh)
+    dev = next(model.parameters()).device
+    return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
+
+
+def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
+                det_thresh: float = _frames.DET_THRESH):
+    """The embed half of the reference's frame loop (`app.py:224-241`) for all boxes of one frame at once: `frames.clip_boxes` →
+    one crop + BGR→RGB + Resize launch on the frame (`resize.crop_resize_u8`; a host frame is uploaded once) → ToTensor +
+    Normalize → ONE ``model(x)`` under ``no_grad``.  ``frame``: H×W×3 uint8 BGR (cv2), host or device; ``boxes`` / ``probs``: the
+    detector's output.  Returns ``(embeddings [n, D] on the device, kept int64 [n])``: row i is what
+    ``get_embedding(frame[y1:y2, x1:x2], model)`` returns for box ``kept[i]`` (to the bit under `ops.set_batch_invariant`; to
+    rounding otherwise, as for any batch); boxes below ``det_thresh`` or empty after clipping are absent."""
+    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh)
+    if u8.shape[0] == 0:
+        return torch.empty((0, 0), dtype=torch.float32, device=u8.device), kept
+    x = ops.normalize_u8(u8, mean, std)[0]
+    with torch.no_grad():
+        emb = model(x)
+    return (emb.unsqueeze(0) if emb.dim() == 1 else emb), kept
+
+
+def identify_boxes(model, frame, boxes, refs, thresh=REC_THRESH, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
+                   det_thresh: float = _frames.DET_THRESH, what: str = "forward", normalize: bool = False):
+    """From a frame and a detector's boxes to names: `embed_boxes`, one `ops.match_top1` against the gallery, ONE device → host
+    copy.  Returns ``(results, kept)``: for box ``kept[i]``, ``results[i]`` is the ``(name, dist, ref_idx)`` triple
+    ``compare_faces(get_embedding(frame[y1:y2, x1:x2], model), refs, thresh)`` returns, ``("Unknown", dist, None)`` above the
+    threshold and ``("Unknown", inf, None)`` for empty ``refs`` included.  ``refs``: the reference's list or a `Gallery`.
+
+    ``what="forward"`` matches ``model(x)``, as the reference's loop does; ``what="embedding"`` matches ``model.get_embedding(x)``
+    (L2-normalised first if ``normalize``), what `embed_and_match` matches - and for a model with a model handle whose input
+    normalisation (`set_input_normalization`) is ``mean`` / ``std`` the uint8 crops go straight into `frmap_model_embed_and_match`
+    (`FRMAP_INPUT_U8_HWC`): no fp32 input pass."""
+    if what not in ("forward", "embedding"):
+        raise ValueError(f"identify_boxes: what must be 'forward' or 'embedding', got {what!r}")
+    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh)
+    n = u8.shape[0]
+    if n == 0:
+        return [], kept
+    if refs is None or len(refs) == 0:
+        return [("Unknown", float('inf'), None)] * n, kept
+    g = _as_gallery(refs, u8.device)
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    h = model.model_handle() if what == "embedding" and hasattr(model, "model_handle") else None
+    with torch.no_grad():
+        if h is not None and (model.input_mean, model.input_std) == (mean, std):
+            rec = h.embed_and_match(model._check_input(u8), g.matrix, g.prepared, float("inf"), normalize, packed=True)[3]
+        else:
+            x = ops.normalize_u8(u8, mean, std)[0]
+            if what == "forward":
+                emb = model(x)
+            else:
+                emb = model.get_embedding(x)
+            emb = (emb.unsqueeze(0) if emb.dim() == 1 else emb).to(torch.float32)
+            if what == "embedding" and normalize:
+                emb = ops.l2_normalize(emb, 1e-12)
+            rec = ops.match_top1(emb, g.matrix, float("inf"), packed=True, prepared=g.prepared)[3]
+    rec = rec.cpu()                                           # the one host copy: int32 [n, 2] = (index, bits of the distance)
+    out = []
+    for i, d in zip(rec[:, 0].tolist(), rec.view(torch.float32)[:, 1].tolist()):
+        if i < 0:                                             # every distance NaN (see compare_faces)
+            out.append(("Unknown", float('inf'), None))
+        elif d <= thresh:
+            out.append((g.names[i], d, i))
+        else:
+            out.append(("Unknown", d, None))
+    return out, kept
 
 
 class GraphedEmbedMatch:

@@ -20,6 +20,7 @@ from . import _lib
 PRECISION_BITS = 32 - 8 - 2
 ITEM_DTYPE = np.dtype([("src_off", "<u8"), ("H", "<i4"), ("W", "<i4"), ("bx_off", "<i4"), ("kx_off", "<i4"), ("ksx", "<i4"),
                        ("by_off", "<i4"), ("ky_off", "<i4"), ("ksy", "<i4")])   # FrmapResizeItem (csrc/resize.hip), 40 bytes
+FRAME_DTYPE = np.dtype([("base", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])   # FrmapFrame (csrc/crop_resize.hip), 24 bytes
 
 
 @functools.lru_cache(maxsize=512)
@@ -119,4 +120,84 @@ def resize_bilinear_u8(images: Sequence, size: Tuple[int, int] = (224, 224), dev
         _lib.check(_lib.load().frmap_resize_bilinear_u8(pool.data_ptr(), items_d.data_ptr(), tab_d.data_ptr(), out.data_ptr(),
                                                         len(arrs), out_h, out_w, rows_per_block, lds_rows,
                                                         torch.cuda.current_stream().cuda_stream), "resize_bilinear_u8")
+    return out
+
+
+def _device_frames(frames, device) -> list:
+    """``frames`` (one [H,W,3] / [F,H,W,3] uint8 tensor or array, or a sequence of [H,W,3] ones) -> a list of [H,W,3] uint8 device
+    tensors with unit channel stride and 3-byte pixels (rows may be padded: a view of a wider buffer is taken as it is).  A host
+    frame, or a host stack of frames, is uploaded once."""
+    if isinstance(frames, (list, tuple)):
+        out = []
+        for f in frames:
+            out.extend(_device_frames(f, device))
+        return out
+    t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3 or min(t.shape) < 1:
+        raise ValueError("crop_resize_u8: frames must be uint8 [H, W, 3] or [F, H, W, 3]")
+    if not t.is_cuda:
+        t = t.to(device, non_blocking=True)
+    if t.stride(-1) != 1 or t.stride(-2) != 3 or t.stride(-3) < 3 * t.shape[-2]:
+        t = t.contiguous()
+    return [t] if t.dim() == 3 else list(t.unbind(0))
+
+
+def crop_resize_u8(frames, rois, size: Tuple[int, int] = (160, 160), bgr: bool = False, device="cuda") -> torch.Tensor:
+    """Crops of frames, resized on the device: uint8 ``[N, size[0], size[1], 3]`` RGB, crop i bit-identical to
+    ``PIL.Image.fromarray(rgb_frame[y1:y2, x1:x2]).resize(size[::-1], Image.BILINEAR)`` - the reference's
+    ``frame[y1:y2, x1:x2]`` + ``[:, :, ::-1]`` + ``Resize`` (`src/app.py:234, 32-39`) for all boxes of a detector in one launch.
+
+    ``frames``: uint8 ``[H, W, 3]`` or ``[F, H, W, 3]`` tensor / array, or a sequence of ``[H, W, 3]`` frames of any sizes, on the host
+    (uploaded once, not once per crop) or on the device (used in place, padded rows included).  ``rois``: host integers ``[N, 4]`` =
+    ``(x1, y1, x2, y2)`` in frame 0, or ``[N, 5]`` with a leading frame index; a ROI that is empty or leaves its frame raises
+    ``ValueError``.  ``bgr``: the frames are BGR (cv2) and come out RGB.  The filter taps are computed by the kernel
+    (`frmap_crop_resize_u8`): no table per box size is built on the host.  A ROI more than 100x taller than wide whose height shrinks
+    takes Pillow's other pass order and goes through `resize_bilinear_u8` on its slice."""
+    out_h, out_w = int(size[0]), int(size[1])
+    if out_h < 1 or out_w < 1:
+        raise ValueError("crop_resize_u8: size must be positive")
+    r = rois.detach().cpu().numpy() if isinstance(rois, torch.Tensor) else np.asarray(rois)
+    if r.size == 0:
+        r = np.zeros((0, 4), np.int64)                   # (an empty list has no integer dtype to check)
+    if r.ndim != 2 or r.shape[1] not in (4, 5) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("crop_resize_u8: rois must be integers of shape [N, 4] or [N, 5]")
+    r = r.astype(np.int64)
+    if r.shape[1] == 4:
+        r = np.concatenate([np.zeros((r.shape[0], 1), np.int64), r], 1)
+    fr = _device_frames(frames, device)
+    dev = fr[0].device
+    if any(f.device != dev for f in fr):
+        raise ValueError("crop_resize_u8: frames live on different devices")
+    N = r.shape[0]
+    if N == 0:
+        return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    fi, x1, y1, x2, y2 = r.T
+    if fi.min() < 0 or fi.max() >= len(fr):
+        raise ValueError(f"crop_resize_u8: frame index outside [0, {len(fr)})")
+    Hs, Ws = np.array([f.shape[0] for f in fr])[fi], np.array([f.shape[1] for f in fr])[fi]
+    bad = (x1 < 0) | (y1 < 0) | (x2 > Ws) | (y2 > Hs) | (x2 <= x1) | (y2 <= y1)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"crop_resize_u8: ROI {i} {tuple(int(v) for v in r[i, 1:])} is empty or leaves its {int(Ws[i])}x{int(Hs[i])} frame")
+    h, w = y2 - y1, x2 - x1
+    tall = (h > 100 * w) & (out_h < h)
+    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    keep = np.flatnonzero(~tall)
+    if keep.size:
+        desc = np.zeros(len(fr), FRAME_DTYPE)
+        for j, f in enumerate(fr):
+            desc[j] = (f.data_ptr(), f.shape[0], f.shape[1], f.stride(0))
+        nd = desc.nbytes // 4
+        host = np.concatenate([desc.view(np.int32), r[keep].astype(np.int32).reshape(-1)])     # one upload: frames | rois
+        tab = torch.from_numpy(host).to(dev, non_blocking=True)
+        dst = out if keep.size == N else torch.empty((keep.size, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().frmap_crop_resize_u8(tab.data_ptr(), len(fr), tab.data_ptr() + 4 * nd, dst.data_ptr(), int(keep.size),
+                                                        out_h, out_w, int(h[keep].max()), int(w[keep].max()), int(bool(bgr)),
+                                                        torch.cuda.current_stream().cuda_stream), "crop_resize_u8")
+        if dst is not out:
+            out[torch.from_numpy(keep).to(dev)] = dst
+    for i in np.flatnonzero(tall):
+        a = fr[fi[i]][y1[i]:y2[i], x1[i]:x2[i]].cpu().numpy()
+        out[int(i)] = resize_bilinear_u8([a[:, :, ::-1] if bgr else a], (out_h, out_w), dev)[0]
     return out

@@ -74,6 +74,33 @@ int frmap_normalize_u8_hwc(const unsigned char* img_u8, float* out_nchw_f32, voi
 int frmap_resize_bilinear_u8(const unsigned char* src_pool, const void* items, const int* tables, unsigned char* out,
                              int B, int out_h, int out_w, int rows_per_block, int lds_rows, void* stream);
 
+/* Face crops from device-resident frames in one launch: `frame[y1:y2, x1:x2]` (src/app.py:234), the BGR -> RGB flip and
+ * `transforms.Resize` of get_embedding (src/app.py:32-39), for every box of a detector at once.  Output i is bit-identical to
+ * PIL.Image.fromarray(rgb_frame[y1:y2, x1:x2]).resize((out_w, out_h), BILINEAR): the integer arithmetic of
+ * frmap_resize_bilinear_u8, with the filter taps computed ON THE DEVICE (Pillow's precompute_coeffs + normalize_coeffs_8bpc in
+ * float64, Pillow's operation order, nothing fused) - no host tables, no host work per box size, nothing synchronised.
+ *   frames : n_frames records  struct { uint64 base; int32 H, W; int64 pitch; }   (24 bytes, device memory)
+ *            base = device address of pixel (0, 0) of an HWC uint8 frame, pitch = bytes per row (>= 3 * W)
+ *   rois   : N records  int32 { frame, x1, y1, x2, y2 }   (20 bytes, device memory): rows [y1, y2), columns [x1, x2) of that
+ *            frame, 0 <= x1 < x2 <= W, 0 <= y1 < y2 <= H.  Device data: NOT validated by this call (the Python wrapper does it
+ *            before the upload); the kernel skips a record that breaks the contract or exceeds max_roi_* and leaves its output
+ *            unwritten, so nothing is read outside a frame.
+ *   bgr    : != 0: the frames are BGR (cv2), swapped to RGB on read
+ *   out    : N x out_h x out_w x 3 uint8 RGB
+ *   max_roi_h, max_roi_w : host-side upper bounds of the ROI sizes (the frame size always serves); they size the launch: one
+ *            workgroup resizes up to 8 output rows, fewer when the input rows those touch would not fit LDS.
+ * Supported reduction: the LDS need (4 * out_w * (5 c + 5) bytes for a c-fold reduction at one row per workgroup) must fit
+ * 160 KB - every ROI that shrinks by at most 32x per axis to an output at most 224 wide does; beyond that the call is rejected.
+ * Not covered: Pillow resizes an image more than 100x taller than wide whose height shrinks in the other order (height first);
+ * the Python wrapper routes such ROIs through frmap_resize_bilinear_u8.  N < 0, null pointers and bad shapes are rejected before
+ * any launch; N == 0 returns 0 and launches nothing. */
+int frmap_crop_resize_u8(const void* frames, int n_frames, const int32_t* rois, unsigned char* out, int N, int out_h,
+                         int out_w, int max_roi_h, int max_roi_w, int bgr, void* stream);
+/* The filter taps the crop kernel computes, from the same function compiled for the CPU (HOST pointers; no GPU needed):
+ * ksize_out = taps per output sample (ceil(max(in / out, 1)) * 2 + 1); bounds_out int32 [out_size][2] = (first input sample,
+ * taps); coeffs_out int32 [out_size][ksize], zero past a sample's taps.  bounds_out and coeffs_out may both be NULL (ksize only). */
+int frmap_resize_coeffs_host(int in_size, int out_size, int32_t* bounds_out, int32_t* coeffs_out, int* ksize_out);
+
 /* ---------------------------------------------------------------------------------------------
  * Conv weight packing.  `w_oihw` = fp32 [Cout][Cin][KH][KW] with the BatchNorm scale already
  * folded in (w * gamma/sqrt(var+eps)); output is the kernel's LDS-image order in `dtype`.
