@@ -8,17 +8,9 @@
 // frame, so (input size, output size) pairs almost never repeat and a host table per pair costs more than the resize.  Each
 // workgroup computes the taps it needs into LDS with the shared float64 function of resize_coeffs.h (all out_w columns, its own
 // rows_per_block rows: a few thousand float64 operations), so the call needs nothing from the host but the ROI records.
+#include "frame_records.h"
 #include "frmap_common.h"
 #include "resize_coeffs.h"
-
-struct FrmapFrame {            // mirrored by resize.py (24 bytes)
-  unsigned long long base;     // device address of pixel (0, 0); HWC uint8, 3 bytes per pixel
-  int H, W;
-  long long pitch;             // bytes from one row to the next, >= 3 * W
-};
-struct FrmapRoi {              // mirrored by resize.py (20 bytes)
-  int frame, x1, y1, x2, y2;   // rows [y1, y2), columns [x1, x2) of frames[frame]
-};
 
 __device__ __forceinline__ int crop_clip8(int v) {
   v >>= FRMAP_RESIZE_PRECISION_BITS;
@@ -111,8 +103,6 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const FrmapFrame* _
   }
 }
 
-static constexpr int CROP_LDS_MAX = 160 * 1024;
-
 extern "C" int frmap_crop_resize_u8(const void* frames, int n_frames, const int32_t* rois, unsigned char* out, int N, int out_h,
                                     int out_w, int max_roi_h, int max_roi_w, int bgr, void* stream) {
   FRMAP_REQUIRE(N >= 0, "crop_resize_u8: N = %d", N);
@@ -121,26 +111,14 @@ extern "C" int frmap_crop_resize_u8(const void* frames, int n_frames, const int3
   FRMAP_REQUIRE(n_frames > 0 && out_h > 0 && out_w > 0 && out_h <= 65536 && out_w <= 65536 && max_roi_h > 0 && max_roi_w > 0 &&
                     max_roi_h <= (1 << 24) && max_roi_w <= (1 << 24),
                 "crop_resize_u8: bad shape");
-  // Launch shape from the size bounds alone.  ceil(max(scale, 1)) per axis gives the tap count 2 c + 1; the input rows r output
-  // rows touch at scale s are at most ceil(r s) + 2 ceil(max(s, 1)) + 2 (and never more than the ROI has).
-  const long long cx = max_roi_w > out_w ? (max_roi_w + out_w - 1) / out_w : 1, cy = max_roi_h > out_h ? (max_roi_h + out_h - 1) / out_h : 1;
-  const long long ksx = 2 * cx + 1, ksy = 2 * cy + 1;
-  auto window = [&](long long r) {
-    const long long w = (r * max_roi_h + out_h - 1) / out_h + 2 * cy + 2;
-    return w < max_roi_h ? w : (long long)max_roi_h;
-  };
-  auto lds_bytes = [&](long long r) { return 4 * (window(r) * out_w + out_w * (ksx + 2) + r * (ksy + 2)); };
-  int rows_per_block = out_h < 8 ? out_h : 8;
-  while (rows_per_block > 1 && lds_bytes(rows_per_block) > 64 * 1024) rows_per_block /= 2;   // 64 KB: two workgroups per CU
-  const long long lds = lds_bytes(rows_per_block);
-  FRMAP_REQUIRE(lds <= CROP_LDS_MAX, "crop_resize_u8: ROIs of up to %d x %d to %d x %d need %lld bytes of LDS for one output row (limit %d)",
-                max_roi_h, max_roi_w, out_h, out_w, lds, CROP_LDS_MAX);
-  const int groups = (out_h + rows_per_block - 1) / rows_per_block;
-  FRMAP_REQUIRE((long long)N * groups <= 0x7fffffffLL, "crop_resize_u8: %d ROIs x %d row groups exceed the grid", N, groups);
-  if (frmap_big_lds((const void*)crop_resize_u8_kernel, CROP_LDS_MAX)) return -2;
-  hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(N * groups)), dim3(256), (size_t)lds, (hipStream_t)stream,
-                     (const FrmapFrame*)frames, n_frames, (const FrmapRoi*)rois, out, out_h, out_w, rows_per_block, groups,
-                     (int)window(rows_per_block), (int)ksx, (int)ksy, bgr ? 1 : 0);
+  const FrmapCropPlan p = frmap_crop_plan(out_h, out_w, max_roi_h, max_roi_w);
+  FRMAP_REQUIRE(p.lds <= FRMAP_CROP_LDS_MAX, "crop_resize_u8: ROIs of up to %d x %d to %d x %d need %lld bytes of LDS for one output row (limit %d)",
+                max_roi_h, max_roi_w, out_h, out_w, p.lds, FRMAP_CROP_LDS_MAX);
+  FRMAP_REQUIRE((long long)N * p.groups <= 0x7fffffffLL, "crop_resize_u8: %d ROIs x %d row groups exceed the grid", N, p.groups);
+  if (frmap_big_lds((const void*)crop_resize_u8_kernel, FRMAP_CROP_LDS_MAX)) return -2;
+  hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(N * p.groups)), dim3(256), (size_t)p.lds, (hipStream_t)stream,
+                     (const FrmapFrame*)frames, n_frames, (const FrmapRoi*)rois, out, out_h, out_w, p.rows_per_block, p.groups,
+                     p.lds_rows, p.ksx, p.ksy, bgr ? 1 : 0);
   FRMAP_LAUNCH_CHECK();
   return 0;
 }

@@ -435,26 +435,44 @@ def embed_and_match(model, x: torch.Tensor, gallery, thresh: float = REC_THRESH,
     return ids, dist
 
 
-def _box_crops(model, frame, boxes, probs, size, det_thresh):
-    """clip_boxes + one crop launch: (uint8 [n, h, w, 3] RGB crops on the model's device, kept box indices)."""
+def _box_crops(model, frame, boxes, probs, size, det_thresh, landmarks=None, margin=0.0):
+    """clip_boxes + one crop launch: (uint8 [n, h, w, 3] RGB crops on the model's device, kept box indices).  With ``landmarks`` /
+    ``margin``: margin_boxes first, and the crops are cut out of the frame rotated about each face's eye centre."""
     from . import resize as _resize
     shape = frame.shape
     if len(shape) != 3 or shape[2] != 3:
         raise ValueError("expected one H×W×3 uint8 BGR frame")
-    rois, kept = _frames.clip_boxes(boxes, probs, shape, det_thresh)
     dev = next(model.parameters()).device
-    return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
+    if landmarks is None and margin == 0.0:
+        rois, kept = _frames.clip_boxes(boxes, probs, shape, det_thresh)
+        return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
+    rois, kept = _frames.clip_boxes(_frames.margin_boxes(boxes, margin, shape), probs, shape, det_thresh)
+    if landmarks is None:
+        return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
+    if boxes is not None and len(landmarks) != len(boxes):
+        raise ValueError(f"landmarks: {len(landmarks)} sets for {len(boxes)} boxes")
+    mats = np.zeros((len(kept), 6), np.float64)
+    for j, i in enumerate(kept.tolist()):
+        mats[j] = _frames.rotation_matrix(*_frames.eye_rotation(landmarks[i]))
+    return _resize.align_crop_resize_u8(frame, rois, mats, size, bgr=True, device=dev), kept
 
 
 def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
-                det_thresh: float = _frames.DET_THRESH):
+                det_thresh: float = _frames.DET_THRESH, landmarks=None, margin: float = 0.0):
     """The embed half of the reference's frame loop (`app.py:224-241`) for all boxes of one frame at once: `frames.clip_boxes` →
     one crop + BGR→RGB + Resize launch on the frame (`resize.crop_resize_u8`; a host frame is uploaded once) → ToTensor +
     Normalize → ONE ``model(x)`` under ``no_grad``.  ``frame``: H×W×3 uint8 BGR (cv2), host or device; ``boxes`` / ``probs``: the
     detector's output.  Returns ``(embeddings [n, D] on the device, kept int64 [n])``: row i is what
     ``get_embedding(frame[y1:y2, x1:x2], model)`` returns for box ``kept[i]`` (to the bit under `ops.set_batch_invariant`; to
-    rounding otherwise, as for any batch); boxes below ``det_thresh`` or empty after clipping are absent."""
-    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh)
+    rounding otherwise, as for any batch); boxes below ``det_thresh`` or empty after clipping are absent.
+
+    Aligned crops (the reference's dataset step, `src/data_prep.py:69-106, 138-150`): ``landmarks`` ``[n, >= 2, 2]`` - the
+    detector's points per box, eyes first, as ``mtcnn.detect(..., landmarks=True)`` returns them - and ``margin`` (the reference's
+    ``face_margin``).  Then `frames.margin_boxes` → `frames.clip_boxes` → per kept box `frames.eye_rotation` +
+    `frames.rotation_matrix` → one `resize.align_crop_resize_u8` launch: each crop is cut out of the frame rotated about that
+    face's eye centre until the eye line is level, resampled as PILLOW does (``Image.rotate(angle, BILINEAR, center=c)``,
+    ``.crop``, ``.resize``), not as the reference's cv2 calls do.  ``margin`` alone widens the boxes of the unrotated frame."""
+    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh, landmarks, margin)
     if u8.shape[0] == 0:
         return torch.empty((0, 0), dtype=torch.float32, device=u8.device), kept
     x = ops.normalize_u8(u8, mean, std)[0]
@@ -464,7 +482,8 @@ def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, 
 
 
 def identify_boxes(model, frame, boxes, refs, thresh=REC_THRESH, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
-                   det_thresh: float = _frames.DET_THRESH, what: str = "forward", normalize: bool = False):
+                   det_thresh: float = _frames.DET_THRESH, what: str = "forward", normalize: bool = False, landmarks=None,
+                   margin: float = 0.0):
     """From a frame and a detector's boxes to names: `embed_boxes`, one `ops.match_top1` against the gallery, ONE device → host
     copy.  Returns ``(results, kept)``: for box ``kept[i]``, ``results[i]`` is the ``(name, dist, ref_idx)`` triple
     ``compare_faces(get_embedding(frame[y1:y2, x1:x2], model), refs, thresh)`` returns, ``("Unknown", dist, None)`` above the
@@ -473,10 +492,10 @@ def identify_boxes(model, frame, boxes, refs, thresh=REC_THRESH, probs=None, siz
     ``what="forward"`` matches ``model(x)``, as the reference's loop does; ``what="embedding"`` matches ``model.get_embedding(x)``
     (L2-normalised first if ``normalize``), what `embed_and_match` matches - and for a model with a model handle whose input
     normalisation (`set_input_normalization`) is ``mean`` / ``std`` the uint8 crops go straight into `frmap_model_embed_and_match`
-    (`FRMAP_INPUT_U8_HWC`): no fp32 input pass."""
+    (`FRMAP_INPUT_U8_HWC`): no fp32 input pass.  ``landmarks`` / ``margin``: eye-aligned crops with a margin, as `embed_boxes`."""
     if what not in ("forward", "embedding"):
         raise ValueError(f"identify_boxes: what must be 'forward' or 'embedding', got {what!r}")
-    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh)
+    u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh, landmarks, margin)
     n = u8.shape[0]
     if n == 0:
         return [], kept

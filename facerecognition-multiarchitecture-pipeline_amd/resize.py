@@ -142,6 +142,43 @@ def _device_frames(frames, device) -> list:
     return [t] if t.dim() == 3 else list(t.unbind(0))
 
 
+def _frames_and_rois(what: str, frames, rois, size, device):
+    """The argument checks `crop_resize_u8` and `align_crop_resize_u8` share: ``(out_h, out_w, device frames, their device,
+    rois int64 [N, 5])``, every ROI inside its frame; ``ValueError`` otherwise."""
+    out_h, out_w = int(size[0]), int(size[1])
+    if out_h < 1 or out_w < 1:
+        raise ValueError(f"{what}: size must be positive")
+    r = rois.detach().cpu().numpy() if isinstance(rois, torch.Tensor) else np.asarray(rois)
+    if r.size == 0:
+        r = np.zeros((0, 4), np.int64)                   # (an empty list has no integer dtype to check)
+    if r.ndim != 2 or r.shape[1] not in (4, 5) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"{what}: rois must be integers of shape [N, 4] or [N, 5]")
+    r = r.astype(np.int64)
+    if r.shape[1] == 4:
+        r = np.concatenate([np.zeros((r.shape[0], 1), np.int64), r], 1)
+    fr = _device_frames(frames, device)
+    dev = fr[0].device
+    if any(f.device != dev for f in fr):
+        raise ValueError(f"{what}: frames live on different devices")
+    if r.shape[0]:
+        fi, x1, y1, x2, y2 = r.T
+        if fi.min() < 0 or fi.max() >= len(fr):
+            raise ValueError(f"{what}: frame index outside [0, {len(fr)})")
+        Hs, Ws = np.array([f.shape[0] for f in fr])[fi], np.array([f.shape[1] for f in fr])[fi]
+        bad = (x1 < 0) | (y1 < 0) | (x2 > Ws) | (y2 > Hs) | (x2 <= x1) | (y2 <= y1)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"{what}: ROI {i} {tuple(int(v) for v in r[i, 1:])} is empty or leaves its {int(Ws[i])}x{int(Hs[i])} frame")
+    return out_h, out_w, fr, dev, r
+
+
+def _frame_records(fr) -> np.ndarray:
+    desc = np.zeros(len(fr), FRAME_DTYPE)
+    for j, f in enumerate(fr):
+        desc[j] = (f.data_ptr(), f.shape[0], f.shape[1], f.stride(0))
+    return desc
+
+
 def crop_resize_u8(frames, rois, size: Tuple[int, int] = (160, 160), bgr: bool = False, device="cuda") -> torch.Tensor:
     """Crops of frames, resized on the device: uint8 ``[N, size[0], size[1], 3]`` RGB, crop i bit-identical to
     ``PIL.Image.fromarray(rgb_frame[y1:y2, x1:x2]).resize(size[::-1], Image.BILINEAR)`` - the reference's
@@ -153,40 +190,17 @@ def crop_resize_u8(frames, rois, size: Tuple[int, int] = (160, 160), bgr: bool =
     ``ValueError``.  ``bgr``: the frames are BGR (cv2) and come out RGB.  The filter taps are computed by the kernel
     (`frmap_crop_resize_u8`): no table per box size is built on the host.  A ROI more than 100x taller than wide whose height shrinks
     takes Pillow's other pass order and goes through `resize_bilinear_u8` on its slice."""
-    out_h, out_w = int(size[0]), int(size[1])
-    if out_h < 1 or out_w < 1:
-        raise ValueError("crop_resize_u8: size must be positive")
-    r = rois.detach().cpu().numpy() if isinstance(rois, torch.Tensor) else np.asarray(rois)
-    if r.size == 0:
-        r = np.zeros((0, 4), np.int64)                   # (an empty list has no integer dtype to check)
-    if r.ndim != 2 or r.shape[1] not in (4, 5) or not np.issubdtype(r.dtype, np.integer):
-        raise ValueError("crop_resize_u8: rois must be integers of shape [N, 4] or [N, 5]")
-    r = r.astype(np.int64)
-    if r.shape[1] == 4:
-        r = np.concatenate([np.zeros((r.shape[0], 1), np.int64), r], 1)
-    fr = _device_frames(frames, device)
-    dev = fr[0].device
-    if any(f.device != dev for f in fr):
-        raise ValueError("crop_resize_u8: frames live on different devices")
+    out_h, out_w, fr, dev, r = _frames_and_rois("crop_resize_u8", frames, rois, size, device)
     N = r.shape[0]
     if N == 0:
         return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     fi, x1, y1, x2, y2 = r.T
-    if fi.min() < 0 or fi.max() >= len(fr):
-        raise ValueError(f"crop_resize_u8: frame index outside [0, {len(fr)})")
-    Hs, Ws = np.array([f.shape[0] for f in fr])[fi], np.array([f.shape[1] for f in fr])[fi]
-    bad = (x1 < 0) | (y1 < 0) | (x2 > Ws) | (y2 > Hs) | (x2 <= x1) | (y2 <= y1)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"crop_resize_u8: ROI {i} {tuple(int(v) for v in r[i, 1:])} is empty or leaves its {int(Ws[i])}x{int(Hs[i])} frame")
     h, w = y2 - y1, x2 - x1
     tall = (h > 100 * w) & (out_h < h)
     out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     keep = np.flatnonzero(~tall)
     if keep.size:
-        desc = np.zeros(len(fr), FRAME_DTYPE)
-        for j, f in enumerate(fr):
-            desc[j] = (f.data_ptr(), f.shape[0], f.shape[1], f.stride(0))
+        desc = _frame_records(fr)
         nd = desc.nbytes // 4
         host = np.concatenate([desc.view(np.int32), r[keep].astype(np.int32).reshape(-1)])     # one upload: frames | rois
         tab = torch.from_numpy(host).to(dev, non_blocking=True)
@@ -200,4 +214,61 @@ def crop_resize_u8(frames, rois, size: Tuple[int, int] = (160, 160), bgr: bool =
     for i in np.flatnonzero(tall):
         a = fr[fi[i]][y1[i]:y2[i], x1[i]:x2[i]].cpu().numpy()
         out[int(i)] = resize_bilinear_u8([a[:, :, ::-1] if bgr else a], (out_h, out_w), dev)[0]
+    return out
+
+
+def align_crop_resize_u8(frames, rois, matrices, size: Tuple[int, int] = (160, 160), bgr: bool = False, device="cuda") -> torch.Tensor:
+    """Crops of ROTATED frames, resized on the device in one launch, with no rotated frame in memory: uint8
+    ``[N, size[0], size[1], 3]`` RGB, crop i bit-identical to
+
+        ``Image.fromarray(rgb_frame).rotate(angle_i, resample=Image.BILINEAR, center=center_i)``      (same size, fill 0)
+        ``.crop((x1, y1, x2, y2)).resize(size[::-1], Image.BILINEAR)``
+
+    where ``matrices[i] = frames.rotation_matrix(angle_i, center_i)`` - the reference's eye alignment (`src/data_prep.py:69-87`:
+    rotate the whole image about the point between the eyes, `frames.eye_rotation`), margin box (`frames.margin_boxes`), crop and
+    resize (`:144-150`).  DEPARTURE from the reference: it resamples with `cv2.warpAffine` / `cv2.resize`; this function takes the
+    angle, the centre and the "rotate the frame, then crop" order from it and the resampling from Pillow, as every image operation
+    of this package does - its output is Pillow's to the bit, not cv2's.
+
+    ``frames``, ``rois``, ``bgr``: as `crop_resize_u8` (the ROI is in the rotated frame, which has the frame's size; same
+    ``ValueError``s).  ``matrices``: float64 ``[N, 6]``, Pillow's output -> input affine matrix per ROI; a shape mismatch or a
+    non-finite entry raises ``ValueError``.  Frames, ROIs and matrices go up in one upload; the kernel (`frmap_align_crop_resize_u8`)
+    warps each source pixel where a filter tap reads it.  A ROI more than 100x taller than wide whose height shrinks takes Pillow's
+    other pass order: its rotated crop is made by the kernel at its own size and resized by `resize_bilinear_u8`."""
+    out_h, out_w, fr, dev, r = _frames_and_rois("align_crop_resize_u8", frames, rois, size, device)
+    N = r.shape[0]
+    m = np.ascontiguousarray(matrices.detach().cpu().numpy() if isinstance(matrices, torch.Tensor) else matrices, dtype=np.float64)
+    if m.size == 0:
+        m = m.reshape(0, 6)
+    if m.shape != (N, 6):
+        raise ValueError(f"align_crop_resize_u8: matrices must have shape [{N}, 6], one per ROI, got {tuple(m.shape)}")
+    if not np.isfinite(m).all():
+        raise ValueError(f"align_crop_resize_u8: matrix {int(np.flatnonzero(~np.isfinite(m).all(1))[0])} has a non-finite entry")
+    if N == 0:
+        return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    h, w = r[:, 4] - r[:, 2], r[:, 3] - r[:, 1]
+    tall = (h > 100 * w) & (out_h < h)
+    desc = _frame_records(fr).view(np.uint8)
+
+    def launch(sel, dst, oh, ow):
+        # one upload: frames | matrices | rois (the records are 24 and 48 bytes, so the doubles stay 8-byte aligned)
+        host = np.concatenate([desc, m[sel].view(np.uint8).reshape(-1), r[sel].astype(np.int32).view(np.uint8).reshape(-1)])
+        tab = torch.from_numpy(host).to(dev, non_blocking=True)
+        p_m = tab.data_ptr() + desc.nbytes
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().frmap_align_crop_resize_u8(tab.data_ptr(), len(fr), p_m + 48 * len(sel), p_m, dst.data_ptr(), len(sel),
+                                                              oh, ow, int(h[sel].max()), int(w[sel].max()), int(bool(bgr)),
+                                                              torch.cuda.current_stream().cuda_stream), "align_crop_resize_u8")
+
+    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    keep = np.flatnonzero(~tall)
+    if keep.size:
+        dst = out if keep.size == N else torch.empty((keep.size, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+        launch(keep, dst, out_h, out_w)
+        if dst is not out:
+            out[torch.from_numpy(keep).to(dev)] = dst
+    for i in np.flatnonzero(tall):
+        crop = torch.empty((1, int(h[i]), int(w[i]), 3), dtype=torch.uint8, device=dev)
+        launch(np.array([i]), crop, int(h[i]), int(w[i]))       # size == ROI size: the rotated crop itself (RGB already)
+        out[int(i)] = resize_bilinear_u8([crop[0]], (out_h, out_w), dev)[0]
     return out

@@ -101,6 +101,29 @@ int frmap_crop_resize_u8(const void* frames, int n_frames, const int32_t* rois, 
  * taps); coeffs_out int32 [out_size][ksize], zero past a sample's taps.  bounds_out and coeffs_out may both be NULL (ksize only). */
 int frmap_resize_coeffs_host(int in_size, int out_size, int32_t* bounds_out, int32_t* coeffs_out, int* ksize_out);
 
+/* Eye-aligned face crops in one launch: frmap_crop_resize_u8 on the frame ROTATED about a point (the reference's dataset step,
+ * src/data_prep.py:69-87, 144-150: rotate the whole image until the eye line is level, crop the box, resize), without a rotated
+ * frame ever written to memory.  The geometry is the reference's; the RESAMPLING IS PILLOW'S, NOT cv2's (the reference calls
+ * cv2.warpAffine / cv2.resize, which sample another grid with fixed-point weights): output i is bit-identical to
+ *   PIL.Image.fromarray(rgb_frame).rotate(angle, resample=BILINEAR, center=c).crop((x1, y1, x2, y2)).resize((out_w, out_h), BILINEAR)
+ *   frames, rois, out, bgr, max_roi_h, max_roi_w : as frmap_crop_resize_u8; the ROI is in the rotated frame's coordinates (the
+ *            rotated frame has the frame's size; what rotates in from outside is 0)
+ *   mats   : N x 6 float64 (device memory, 8-byte aligned): Image.rotate's output -> input matrix (a, b, c, d, e, f) of each face,
+ *            computed by the host (Pillow rounds cos / sin to 15 decimals; frames.rotation_matrix in the Python package).  Source
+ *            position of output pixel (x, y): (a (x + 0.5) + b (y + 0.5) + c, d (x + 0.5) + e (y + 0.5) + f), float64, unfused.
+ * With out_h x out_w equal to the ROI's size the output is the rotated crop itself.  Device records are NOT validated by this call:
+ * the kernel skips a record whose ROI or frame index breaks the contract, whose matrix holds a non-finite entry or whose window
+ * exceeds max_roi_*, and leaves its output unwritten; every source index is clamped, so nothing is read outside a frame.  Supported
+ * reductions, the tall-ROI exception and the host-side rejections are those of frmap_crop_resize_u8. */
+int frmap_align_crop_resize_u8(const void* frames, int n_frames, const int32_t* rois, const double* mats, unsigned char* out, int N,
+                               int out_h, int out_w, int max_roi_h, int max_roi_w, int bgr, void* stream);
+/* The rotated crop the kernel resizes, from the same function compiled for the CPU (HOST pointers; no GPU needed): rows [y1, y2),
+ * columns [x1, x2) of Image.rotate's output for the H x W frame (3 bytes per pixel, `pitch` bytes per row) and the matrix mat6,
+ * written as [y2 - y1][x2 - x1][3] RGB (bgr != 0: the frame is BGR).  Null pointers, a ROI that is empty or leaves the frame and a
+ * non-finite matrix are rejected. */
+int frmap_align_warp_host(const unsigned char* frame, int H, int W, long long pitch, const double* mat6, int x1, int y1, int x2,
+                          int y2, int bgr, unsigned char* out);
+
 /* ---------------------------------------------------------------------------------------------
  * Conv weight packing.  `w_oihw` = fp32 [Cout][Cin][KH][KW] with the BatchNorm scale already
  * folded in (w * gamma/sqrt(var+eps)); output is the kernel's LDS-image order in `dtype`.
