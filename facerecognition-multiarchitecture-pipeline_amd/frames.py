@@ -1,15 +1,24 @@
 """The host side of the reference's per-frame loop (`src/app.py:181-241`): from a detector's boxes to the integer crops
 `matching.embed_boxes` / `matching.identify_boxes` cut out of the frame on the device - and, for aligned crops, the geometry of
-the reference's dataset step (`src/data_prep.py:69-106`): the eye-line rotation, its matrix, the margin rule.  Pure host code;
-the detector itself (MTCNN) and the IoU tracker (`app.py:126-147, 202-221`) are outside this package."""
+the reference's dataset step (`src/data_prep.py:69-106`): the eye-line rotation, its matrix, the margin rule - and the loop's IoU
+tracker (`app.py:126-147, 183-247`: `box_iou`, `track_boxes`), the readable statement of the rule `ops.track_step` runs for many
+streams in one launch.  Pure host code; the detector itself (MTCNN) is outside this package.
+
+The tracker departs from the reference in two places.  (a) The IoU is float64 arithmetic on the detector's float32 coordinates,
+nothing fused: the reference mixes `np.float32` rows with Python floats from `tolist()`, so which of its operations run in float32
+depends on which operand a `max` returned and on the NumPy major version; the two can differ only where an IoU lies within
+float32 rounding of the threshold or of a competing IoU.  (b) The state keeps only boxes that received an id: the reference
+rebuilds `prev_boxes` from every confident box but `face_ids` only from boxes with an id, so a confident box that is empty after
+clipping puts its two lists out of step (wrong ids later, or an `IndexError` its loop swallows with the frame)."""
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 DET_THRESH = 0.9                       # `app.py:18`
+TRACKING_THRESHOLD = 0.3               # `app.py:29`
 
 
 def clip_boxes(boxes, probs, frame_shape: Sequence[int], det_thresh: float = DET_THRESH) -> Tuple[np.ndarray, np.ndarray]:
@@ -80,3 +89,90 @@ def margin_boxes(boxes, margin: float, frame_shape: Sequence[int]) -> Optional[n
         margin_y = int((y2 - y1) * margin)
         out.append((max(0, x1 - margin_x), max(0, y1 - margin_y), min(W, x2 + margin_x), min(H, y2 + margin_y)))
     return np.asarray(out, dtype=np.float64).reshape(-1, 4)
+
+
+def box_iou(a, b) -> float:
+    """`calc_iou` (`app.py:126-147`) of two raw boxes ``(x1, y1, x2, y2)`` in Python floats (float64): intersection corners by
+    max / min, 0 when they cross, else ``inter / (a1 + a2 - inter)`` if that union is positive, else 0."""
+    x1_1, y1_1, x2_1, y2_1 = [float(v) for v in a]
+    x1_2, y1_2, x2_2, y2_2 = [float(v) for v in b]
+    x_left, y_top = max(x1_1, x1_2), max(y1_1, y1_2)
+    x_right, y_bottom = min(x2_1, x2_2), min(y2_1, y2_2)
+    if x_right < x_left or y_bottom < y_top:
+        return 0.0
+    inter = (x_right - x_left) * (y_bottom - y_top)
+    union = (x2_1 - x1_1) * (y2_1 - y1_1) + (x2_2 - x1_2) * (y2_2 - y1_2) - inter
+    return inter / union if union > 0 else 0.0
+
+
+class TrackState(NamedTuple):
+    """One stream's tracker state: the previous step's tracked boxes (raw, float32 ``[P, 4]``), their ids (int64 ``[P]``) and the
+    next id to hand out (the reference's ``prev_boxes``, ``face_ids``, ``face_id_counter``)."""
+    boxes: np.ndarray
+    ids: np.ndarray
+    next_id: int
+
+
+def new_track_state() -> TrackState:
+    return TrackState(np.zeros((0, 4), np.float32), np.zeros(0, np.int64), 0)
+
+
+def _tracked_roi(box, prob, H: int, W: int, det_thresh):
+    """`clip_boxes`' verdict on one float32 box: its integer crop, or ``None`` when the box is skipped - below the threshold (in
+    float32), a non-finite coordinate or probability (`clip_boxes` raises on those), or an empty crop."""
+    if prob is not None and (not math.isfinite(prob) or np.float32(prob) < np.float32(det_thresh)):
+        return None
+    if not all(math.isfinite(v) for v in box):
+        return None
+    x1, y1, x2, y2 = [int(v) for v in box]
+    x1, y1 = max(0, x1), max(0, y1)
+    x2, y2 = min(W, x2), min(H, y2)
+    if x2 <= x1 or y2 <= y1:
+        return None
+    return x1, y1, x2, y2
+
+
+def track_boxes(state: Optional[TrackState], boxes, probs, frame_shape: Sequence[int], det_thresh: float = DET_THRESH,
+                iou_thresh: float = TRACKING_THRESHOLD) -> Tuple[np.ndarray, TrackState]:
+    """One step of the reference's tracker (`app.py:183-247`) for one stream: ``(ids int64 [n], new_state)``, ``ids[i]`` the
+    ``face_id`` of box i or -1 for a box the loop skips.  ``state``: what the previous call returned (``None``: a fresh one);
+    ``boxes`` / ``probs``: the detector's output, taken as float32 (``probs = None``: every box is confident; ``boxes = None`` or
+    empty: nothing is returned and the state is left as it is - tracks survive empty frames, `:244`).
+
+    The boxes are walked in the detector's order.  Box i is skipped when ``probs[i] < det_thresh`` (compared in float32, as
+    `clip_boxes` does on a detector's float32 probabilities: one equal to ``float32(det_thresh)`` is kept), when a coordinate or the
+    probability is not finite, or when its `clip_boxes` crop is empty.  Otherwise the previous boxes not yet matched in this step
+    are scanned in ascending order and j replaces the best so far when ``box_iou(box_i, prev_j) > best`` (which starts at 0) and
+    ``> iou_thresh``: the first maximum wins, ties go to the lowest j.  A winner hands over its id and becomes matched; without one
+    the box takes ``next_id``.  The new state holds the raw boxes and ids of the boxes that received an id, in order (departure
+    (b) of the module docstring); ``next_id`` is never reset."""
+    if state is None:
+        state = new_track_state()
+    n = 0 if boxes is None else len(boxes)
+    if n == 0:
+        return np.zeros(0, np.int64), state
+    b32 = np.asarray(boxes, dtype=np.float32).reshape(n, 4)
+    p32 = None if probs is None else np.asarray(probs, dtype=np.float32).reshape(n)
+    H, W = int(frame_shape[0]), int(frame_shape[1])
+    prev = [[float(v) for v in pb] for pb in state.boxes]
+    matched = [False] * len(prev)
+    next_id = int(state.next_id)
+    ids = np.full(n, -1, np.int64)
+    for i in range(n):
+        if _tracked_roi(b32[i].tolist(), None if p32 is None else float(p32[i]), H, W, det_thresh) is None:
+            continue
+        best, best_j = 0.0, -1
+        for j, pb in enumerate(prev):
+            if matched[j]:
+                continue
+            iou = box_iou(b32[i], pb)
+            if iou > best and iou > iou_thresh:
+                best, best_j = iou, j
+        if best_j >= 0:
+            ids[i] = state.ids[best_j]
+            matched[best_j] = True
+        else:
+            ids[i] = next_id
+            next_id += 1
+    got = ids >= 0
+    return ids, TrackState(b32[got].copy(), ids[got].copy(), next_id)

@@ -435,26 +435,92 @@ def embed_and_match(model, x: torch.Tensor, gallery, thresh: float = REC_THRESH,
     return ids, dist
 
 
+def _frame_list(frames) -> list:
+    """``[S, H, W, 3]`` (array or tensor) or a sequence of H×W×3 frames -> the list of frames, each checked to be H×W×3."""
+    fl = list(frames.unbind(0) if isinstance(frames, torch.Tensor) else frames) if getattr(frames, "ndim", 0) == 4 else list(frames)
+    for f in fl:
+        if len(f.shape) != 3 or f.shape[2] != 3:
+            raise ValueError("expected H×W×3 uint8 BGR frames")
+    return fl
+
+
+def _per_stream(arg, S: int, what: str) -> list:
+    if arg is None:
+        return [None] * S
+    if len(arg) != S:
+        raise ValueError(f"{what}: {len(arg)} entries for {S} streams")
+    return list(arg)
+
+
+def _stream_rois(frames, boxes, probs, det_thresh, landmarks, margin):
+    """The host half of the crops: per frame `frames.clip_boxes` (after `frames.margin_boxes`, and with the eye matrices, when
+    asked for).  ``(rois int32 [N, 5] with the frame index first, the kept box indices per frame, matrices float64 [N, 6] or
+    None)``, rows in frame order.  ``frames``: a list of H×W×3 frames; ``boxes`` / ``probs`` / ``landmarks``: one entry per frame
+    (``landmarks = None``: no alignment for any frame)."""
+    plain = landmarks is None and margin == 0.0
+    rois, kepts, mats = [], [], []
+    for s, frame in enumerate(frames):
+        shape = frame.shape
+        r, kept = _frames.clip_boxes(boxes[s] if plain else _frames.margin_boxes(boxes[s], margin, shape), probs[s], shape, det_thresh)
+        if landmarks is not None and boxes[s] is not None:
+            lm = landmarks[s]
+            if lm is None or len(lm) != len(boxes[s]):
+                raise ValueError(f"landmarks: {0 if lm is None else len(lm)} sets for {len(boxes[s])} boxes")
+            mats.extend(_frames.rotation_matrix(*_frames.eye_rotation(lm[i])) for i in kept.tolist())
+        rois.append(np.concatenate([np.full((len(kept), 1), s, np.int32), r], 1))
+        kepts.append(kept)
+    return np.concatenate(rois), kepts, (None if landmarks is None else np.asarray(mats, np.float64).reshape(-1, 6))
+
+
+def _launch_crops(model, frames, r5, mats, size):
+    """ONE crop launch over all frames: uint8 ``[N, h, w, 3]`` RGB crops on the model's device."""
+    from . import resize as _resize
+    dev = next(model.parameters()).device
+    if mats is None:
+        return _resize.crop_resize_u8(frames, r5, size, bgr=True, device=dev)
+    return _resize.align_crop_resize_u8(frames, r5, mats, size, bgr=True, device=dev)
+
+
 def _box_crops(model, frame, boxes, probs, size, det_thresh, landmarks=None, margin=0.0):
     """clip_boxes + one crop launch: (uint8 [n, h, w, 3] RGB crops on the model's device, kept box indices).  With ``landmarks`` /
     ``margin``: margin_boxes first, and the crops are cut out of the frame rotated about each face's eye centre."""
-    from . import resize as _resize
     shape = frame.shape
     if len(shape) != 3 or shape[2] != 3:
         raise ValueError("expected one H×W×3 uint8 BGR frame")
-    dev = next(model.parameters()).device
-    if landmarks is None and margin == 0.0:
-        rois, kept = _frames.clip_boxes(boxes, probs, shape, det_thresh)
-        return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
-    rois, kept = _frames.clip_boxes(_frames.margin_boxes(boxes, margin, shape), probs, shape, det_thresh)
-    if landmarks is None:
-        return _resize.crop_resize_u8(frame, rois, size, bgr=True, device=dev), kept
-    if boxes is not None and len(landmarks) != len(boxes):
-        raise ValueError(f"landmarks: {len(landmarks)} sets for {len(boxes)} boxes")
-    mats = np.zeros((len(kept), 6), np.float64)
-    for j, i in enumerate(kept.tolist()):
-        mats[j] = _frames.rotation_matrix(*_frames.eye_rotation(landmarks[i]))
-    return _resize.align_crop_resize_u8(frame, rois, mats, size, bgr=True, device=dev), kept
+    r5, kepts, mats = _stream_rois([frame], [boxes], [probs], det_thresh, None if landmarks is None else [landmarks], margin)
+    return _launch_crops(model, frame, r5, mats, size), kepts[0]
+
+
+def _match_records(model, u8, g, mean, std, what, normalize):
+    """ONE model call on the uint8 crops and ONE match against the gallery: the int32 ``[n, 2]`` records (index, bits of the
+    distance) on the device, nothing thresholded."""
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    h = model.model_handle() if what == "embedding" and hasattr(model, "model_handle") else None
+    with torch.no_grad():
+        if h is not None and (model.input_mean, model.input_std) == (mean, std):
+            return h.embed_and_match(model._check_input(u8), g.matrix, g.prepared, float("inf"), normalize, packed=True)[3]
+        x = ops.normalize_u8(u8, mean, std)[0]
+        if what == "forward":
+            emb = model(x)
+        else:
+            emb = model.get_embedding(x)
+        emb = (emb.unsqueeze(0) if emb.dim() == 1 else emb).to(torch.float32)
+        if what == "embedding" and normalize:
+            emb = ops.l2_normalize(emb, 1e-12)
+        return ops.match_top1(emb, g.matrix, float("inf"), packed=True, prepared=g.prepared)[3]
+
+
+def _record_results(idx, dist, g, thresh) -> list:
+    """`compare_faces`' triples from the host copy of match records."""
+    out = []
+    for i, d in zip(idx, dist):
+        if i < 0:                                             # every distance NaN (see compare_faces)
+            out.append(("Unknown", float('inf'), None))
+        elif d <= thresh:
+            out.append((g.names[i], d, i))
+        else:
+            out.append(("Unknown", d, None))
+    return out
 
 
 def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
@@ -473,12 +539,16 @@ def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, 
     face's eye centre until the eye line is level, resampled as PILLOW does (``Image.rotate(angle, BILINEAR, center=c)``,
     ``.crop``, ``.resize``), not as the reference's cv2 calls do.  ``margin`` alone widens the boxes of the unrotated frame."""
     u8, kept = _box_crops(model, frame, boxes, probs, size, det_thresh, landmarks, margin)
+    return _embed_crops(model, u8, mean, std), kept
+
+
+def _embed_crops(model, u8, mean, std):
     if u8.shape[0] == 0:
-        return torch.empty((0, 0), dtype=torch.float32, device=u8.device), kept
+        return torch.empty((0, 0), dtype=torch.float32, device=u8.device)
     x = ops.normalize_u8(u8, mean, std)[0]
     with torch.no_grad():
         emb = model(x)
-    return (emb.unsqueeze(0) if emb.dim() == 1 else emb), kept
+    return emb.unsqueeze(0) if emb.dim() == 1 else emb
 
 
 def identify_boxes(model, frame, boxes, refs, thresh=REC_THRESH, probs=None, size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5),
@@ -502,31 +572,212 @@ def identify_boxes(model, frame, boxes, refs, thresh=REC_THRESH, probs=None, siz
     if refs is None or len(refs) == 0:
         return [("Unknown", float('inf'), None)] * n, kept
     g = _as_gallery(refs, u8.device)
-    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
-    h = model.model_handle() if what == "embedding" and hasattr(model, "model_handle") else None
-    with torch.no_grad():
-        if h is not None and (model.input_mean, model.input_std) == (mean, std):
-            rec = h.embed_and_match(model._check_input(u8), g.matrix, g.prepared, float("inf"), normalize, packed=True)[3]
+    rec = _match_records(model, u8, g, mean, std, what, normalize).cpu()   # the one host copy: int32 [n, 2] = (index, bits of the distance)
+    return _record_results(rec[:, 0].tolist(), rec.view(torch.float32)[:, 1].tolist(), g, thresh), kept
+
+
+class StreamTracker:
+    """The reference's face tracker (`app.py:183-247`; the rule is `frames.track_boxes`) for ``n_streams`` independent streams -
+    cameras, or clips stepped together - with the per-stream state (previous boxes, their ids, the id counter) resident on the
+    device and ONE launch per step (`ops.track_step`).  ``max_boxes``: the most detections a stream may have in one frame (up to
+    256); a step with more raises ``ValueError`` before anything is uploaded: nothing is ever truncated.  ``device="cpu"`` keeps
+    the state on the host and steps it with the same rule compiled for the CPU (`ops.track_step_host`): no GPU needed."""
+
+    def __init__(self, n_streams: int, max_boxes: int = 64, device: Union[str, torch.device] = "cuda",
+                 det_thresh: float = _frames.DET_THRESH, iou_thresh: float = _frames.TRACKING_THRESHOLD):
+        self.n_streams, self.max_boxes = int(n_streams), int(max_boxes)
+        self.device = torch.device(device)
+        self.det_thresh, self.iou_thresh = float(det_thresh), float(iou_thresh)
+        if self.device.type == "cpu":
+            self.state = ops.track_state_host(self.n_streams, self.max_boxes)
         else:
-            x = ops.normalize_u8(u8, mean, std)[0]
-            if what == "forward":
-                emb = model(x)
-            else:
-                emb = model.get_embedding(x)
-            emb = (emb.unsqueeze(0) if emb.dim() == 1 else emb).to(torch.float32)
-            if what == "embedding" and normalize:
-                emb = ops.l2_normalize(emb, 1e-12)
-            rec = ops.match_top1(emb, g.matrix, float("inf"), packed=True, prepared=g.prepared)[3]
-    rec = rec.cpu()                                           # the one host copy: int32 [n, 2] = (index, bits of the distance)
+            self.state = ops.track_state(self.n_streams, self.max_boxes, self.device)
+        self.counts = np.zeros(self.n_streams, np.int32)      # of the last step
+
+    def pad(self, boxes, probs, frame_shapes):
+        """The step's host arrays ``(boxes float32 [S, M, 4], probs float32 [S, M] or None, counts int32 [S], frame_hw int32
+        [S, 2])``: views of ONE buffer (`pad.buffer`-style: the first array's ``base``), so that a single upload carries them."""
+        S, M = self.n_streams, self.max_boxes
+        boxes = _per_stream(boxes, S, "StreamTracker: boxes")
+        probs = _per_stream(probs, S, "StreamTracker: probs")
+        if len(frame_shapes) in (2, 3) and all(isinstance(v, (int, np.integer)) for v in frame_shapes):
+            frame_shapes = [frame_shapes] * S                  # one (H, W[, C]) for every stream
+        if len(frame_shapes) != S:
+            raise ValueError(f"StreamTracker: {len(frame_shapes)} frame shapes for {S} streams")
+        counts = np.array([0 if b is None else len(b) for b in boxes], np.int32)
+        if counts.size and counts.max() > M:
+            raise ValueError(f"StreamTracker: stream {int(counts.argmax())} has {int(counts.max())} boxes, max_boxes is {M}")
+        any_probs = any(p is not None for p, c in zip(probs, counts) if c)
+        buf = np.zeros(S * M * 5 + S * 3, np.float32)          # boxes | probs | counts | frame_hw, 4-byte words
+        b_pad = buf[:S * M * 4].reshape(S, M, 4)
+        p_pad = buf[S * M * 4:S * M * 5].reshape(S, M)
+        c_pad = buf[S * M * 5:S * M * 5 + S].view(np.int32)
+        hw = buf[S * M * 5 + S:].view(np.int32).reshape(S, 2)
+        c_pad[:] = counts
+        for s in range(S):
+            hw[s] = (int(frame_shapes[s][0]), int(frame_shapes[s][1]))
+            if counts[s]:
+                b_pad[s, :counts[s]] = np.asarray(boxes[s], dtype=np.float32).reshape(counts[s], 4)
+                if probs[s] is not None:
+                    p_pad[s, :counts[s]] = np.asarray(probs[s], dtype=np.float32).reshape(counts[s])
+                elif any_probs:
+                    p_pad[s, :counts[s]] = np.finfo(np.float32).max   # no probabilities for this stream: every box is confident
+        return b_pad, (p_pad if any_probs else None), c_pad, hw
+
+    def step(self, boxes, probs=None, frame_shapes=None):
+        """One step of every stream.  ``boxes`` / ``probs``: one entry per stream, the detector's ``[n, 4]`` boxes and ``[n]``
+        probabilities (taken as float32; ``None``: no detection / every box confident); ``frame_shapes``: ``(H, W[, C])`` per stream,
+        or one for all.  Pads, uploads ONCE, launches ONCE on the current stream.  Returns ``(ids int32 [S, max_boxes], rois
+        int32 [S, max_boxes, 4])`` on the tracker's device (numpy arrays for ``device="cpu"``): `ops.track_step`'s outputs, nothing
+        synchronised; `unpad` cuts a host copy of ``ids`` back to the streams' lengths."""
+        if frame_shapes is None:
+            raise ValueError("StreamTracker.step: frame_shapes is required (the crop rule depends on the frame size)")
+        b_pad, p_pad, c_pad, hw = self.pad(boxes, probs, frame_shapes)
+        self.counts = c_pad.copy()
+        if self.device.type == "cpu":
+            return ops.track_step_host(self.state, b_pad, p_pad, c_pad, hw, self.det_thresh, self.iou_thresh)
+        S, M = self.n_streams, self.max_boxes
+        d = torch.from_numpy(b_pad.base).to(self.device, non_blocking=True)
+        return ops.track_step(self.state, d[:S * M * 4].view(S, M, 4), None if p_pad is None else d[S * M * 4:S * M * 5].view(S, M),
+                              d[S * M * 5:S * M * 5 + S].view(torch.int32), d[S * M * 5 + S:].view(torch.int32).view(S, 2),
+                              self.det_thresh, self.iou_thresh)
+
+    def unpad(self, ids) -> List[np.ndarray]:
+        """Per stream, the int64 ``[n]`` ids of the last step's boxes (-1: skipped) from its padded ``ids`` (copied to the host if
+        it is a device tensor, which synchronises)."""
+        a = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        return [a[s, :self.counts[s]].astype(np.int64) for s in range(self.n_streams)]
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget every track and restart the ids at 0, for one stream or (``None``) for all."""
+        if stream is None:
+            self.state[:] = 0
+        else:
+            if not 0 <= stream < self.n_streams:
+                raise ValueError(f"StreamTracker.reset: stream {stream} of {self.n_streams}")
+            self.state[8 * stream:8 * stream + 8] = 0
+
+    def next_ids(self) -> List[int]:
+        """The reference's ``face_id_counter`` of every stream (one small device → host copy)."""
+        meta = self.state[:8 * self.n_streams]
+        meta = meta.cpu().numpy() if isinstance(meta, torch.Tensor) else meta
+        return meta.view(np.int32).reshape(-1, 2)[:, 1].tolist()
+
+
+def _stream_step(who, model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin):
+    """What `embed_streams` and `identify_streams` share: the host's clip, the tracker's launch (if any) and the one crop launch.
+    ``(uint8 crops [N, h, w, 3], kept indices per stream, padded device ids or None)``."""
+    fl = _frame_list(frames)
+    S = len(fl)
+    if S == 0:
+        raise ValueError(f"{who}: no frames")
+    boxes, probs = _per_stream(boxes, S, f"{who}: boxes"), _per_stream(probs, S, f"{who}: probs")
+    landmarks = None if landmarks is None else _per_stream(landmarks, S, f"{who}: landmarks")
+    if tracker is not None:
+        if tracker.n_streams != S:
+            raise ValueError(f"{who}: {S} frames for a tracker of {tracker.n_streams} streams")
+        if det_thresh is not None and float(det_thresh) != tracker.det_thresh:
+            raise ValueError(f"{who}: det_thresh = {det_thresh}, but the tracker skips boxes below {tracker.det_thresh}")
+        det_thresh = tracker.det_thresh
+        dev = next(model.parameters()).device
+        if tracker.device.type != dev.type or tracker.device.index not in (None, dev.index):
+            raise ValueError(f"{who}: the tracker lives on {tracker.device}, the model on {dev}")
+        # the tracker compares float32 probabilities: `clip_boxes` gets the same float32 values, so that both keep the same boxes,
+        # and a probability that is not finite (which `clip_boxes` would keep and the tracker skip) is refused here
+        probs = [None if p is None else np.asarray(p, dtype=np.float32) for p in probs]
+        for s, p in enumerate(probs):
+            if p is not None and not np.isfinite(p).all():
+                raise ValueError(f"{who}: stream {s} has a probability that is not finite")
+    elif det_thresh is None:
+        det_thresh = _frames.DET_THRESH
+    # everything that can raise on the host - bad arguments above, `clip_boxes` on a non-finite coordinate here - raises before
+    # the tracker's state moves
+    r5, kepts, mats = _stream_rois(fl, boxes, probs, det_thresh, landmarks, margin)
+    ids = None
+    if tracker is not None:
+        ids = tracker.step(boxes, probs, [f.shape for f in fl])[0]
+    whole = getattr(frames, "ndim", 0) == 4                    # a stack goes up (or is used in place) whole
+    return _launch_crops(model, frames if whole else fl, r5, mats, size), kepts, ids
+
+
+def _face_ids(tracker, ids_host, kepts, margin) -> list:
+    """Per stream, the track id of every kept box.  The tracker's skip rule is `frames.clip_boxes`' on the unwidened box, so with
+    ``margin == 0`` the boxes with an id are the kept boxes: checked, not assumed.  With ``margin > 0`` the crop box is widened
+    and the tracker still sees the raw box: a box may be cropped yet carry -1, but only if its unwidened crop is empty."""
     out = []
-    for i, d in zip(rec[:, 0].tolist(), rec.view(torch.float32)[:, 1].tolist()):
-        if i < 0:                                             # every distance NaN (see compare_faces)
-            out.append(("Unknown", float('inf'), None))
-        elif d <= thresh:
-            out.append((g.names[i], d, i))
-        else:
-            out.append(("Unknown", d, None))
-    return out, kept
+    for s, kept in enumerate(kepts):
+        row = ids_host[s].astype(np.int64)
+        if margin == 0.0 and not np.array_equal(np.flatnonzero(row[:tracker.counts[s]] >= 0), kept):
+            raise RuntimeError(f"stream {s}: the tracker gave ids to boxes {np.flatnonzero(row >= 0).tolist()}, clip_boxes kept "
+                               f"{kept.tolist()} (an internal disagreement; the tracker's state has moved)")
+        out.append(row[kept])
+    return out
+
+
+def embed_streams(model, frames, boxes, probs=None, tracker: Optional[StreamTracker] = None, size=(160, 160), mean=(.5, .5, .5),
+                  std=(.5, .5, .5), det_thresh: Optional[float] = None, landmarks=None, margin: float = 0.0):
+    """`embed_boxes` for S frames - S camera streams, or S frames of a clip - in one step: per stream `frames.clip_boxes` on the
+    host, then ONE tracker launch (if ``tracker``), ONE crop launch over all frames and ONE ``model(x)``.  Arguments as
+    `identify_streams`.  Returns ``(embeddings [N, D] on the device, kept, offsets int64 [S + 1], ids)``: stream s owns rows
+    ``offsets[s] : offsets[s + 1]``, row ``offsets[s] + i`` is box ``kept[s][i]`` of its frame - what `embed_boxes` returns for that
+    frame (to the bit under `ops.set_batch_invariant`); ``ids``: the tracker's padded int32 ``[S, max_boxes]`` ids on the device
+    (`StreamTracker.unpad`), or ``None``.  A frame with no kept box contributes no rows; with no rows at all no model is called."""
+    u8, kepts, ids = _stream_step("embed_streams", model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin)
+    offsets = np.concatenate([[0], np.cumsum([len(k) for k in kepts])]).astype(np.int64)
+    return _embed_crops(model, u8, mean, std), kepts, offsets, ids
+
+
+def identify_streams(model, frames, boxes, refs, tracker: Optional[StreamTracker] = None, thresh=REC_THRESH, probs=None,
+                     size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5), what: str = "forward", normalize: bool = False,
+                     landmarks=None, margin: float = 0.0, det_thresh: Optional[float] = None):
+    """The reference's frame loop (`app.py:181-247`) between the detector and the names, as ONE step over S streams - S cameras,
+    or S frames of a clip: per stream `frames.clip_boxes` (with `frames.margin_boxes` and the eye matrices as `identify_boxes`
+    does them), then one tracker launch (if ``tracker``), ONE crop launch over all frames (`resize.crop_resize_u8` /
+    `align_crop_resize_u8`, the ROI's frame field set to the stream), ONE model call, ONE match and ONE device → host copy that
+    carries the match records and the track ids.  A model reaches its rate at hundreds of faces and a frame holds a handful: S
+    calls of `identify_boxes` pay S times the launch latency for what this does once.
+
+    ``frames``: a sequence of H×W×3 uint8 BGR frames of any sizes, or ``[S, H, W, 3]``, host or device.  ``boxes`` / ``probs`` /
+    ``landmarks``: one entry per stream (``None``: no detection in that frame; ``probs=None`` / ``landmarks=None``: none for any
+    stream).  ``tracker``: a `StreamTracker` of S streams on the model's device, stepped once; its ``det_thresh`` is the step's
+    (``det_thresh``, if given, must equal it; without a tracker it defaults to `frames.DET_THRESH`).  With a tracker the
+    probabilities are taken as float32 - what a detector returns and what the tracker compares; a float64 probability within
+    float32 rounding of the threshold is judged as its float32 value - and must be finite: ``ValueError`` otherwise, raised like
+    every other rejection before the tracker's state has moved.  Everything else as `identify_boxes`.
+
+    Returns, per stream, ``(results, kept, face_ids)``: ``results`` and ``kept`` exactly what `identify_boxes` returns for that
+    frame (to the bit under `ops.set_batch_invariant`), ``face_ids`` int64 ``[len(kept)]``: the reference's ``face_id`` of box
+    ``kept[i]`` ("Unknown #id"), or ``None`` without a tracker.  With ``margin > 0`` the tracker's skip rule still uses the
+    unwidened box: a box may be cropped yet carry ``face_id = -1``, but only if its unwidened crop is empty.  A frame with no kept
+    box contributes no rows; a step with no rows at all makes no model call."""
+    if what not in ("forward", "embedding"):
+        raise ValueError(f"identify_streams: what must be 'forward' or 'embedding', got {what!r}")
+    u8, kepts, ids = _stream_step("identify_streams", model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin)
+    n = u8.shape[0]
+    rec = None
+    if n and refs is not None and len(refs):
+        g = _as_gallery(refs, u8.device)
+        rec = _match_records(model, u8, g, mean, std, what, normalize).reshape(-1)
+    face_ids = [None] * len(kepts)
+    if tracker is not None and n:
+        # the one host copy: the int32 match records [n, 2] (if any) and the padded ids [S, max_boxes] behind them
+        both = (ids.reshape(-1) if rec is None else torch.cat([rec, ids.reshape(-1)])).cpu()
+        face_ids = _face_ids(tracker, both[both.numel() - ids.numel():].view(ids.shape).numpy(), kepts, margin)
+        rec = None if rec is None else both[:2 * n]
+    elif tracker is not None:
+        face_ids = [np.zeros(0, np.int64) for _ in kepts]
+    elif rec is not None:
+        rec = rec.cpu()
+    if rec is None:
+        flat = [("Unknown", float('inf'), None)] * n
+    else:
+        rec = rec.view(n, 2)
+        flat = _record_results(rec[:, 0].tolist(), rec.view(torch.float32)[:, 1].tolist(), g, thresh)
+    out, at = [], 0
+    for kept, fid in zip(kepts, face_ids):
+        out.append((flat[at:at + len(kept)], kept, fid))
+        at += len(kept)
+    return out
 
 
 class GraphedEmbedMatch:

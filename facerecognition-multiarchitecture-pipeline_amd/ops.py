@@ -888,12 +888,133 @@ def arcmargin_eval(x: torch.Tensor, w: torch.Tensor, label: torch.Tensor, s: flo
     return out, mm
 
 
+# ------------------------------------------------------------------------------------------------
+# the frame loop's IoU tracker over many streams (`frmap_track_*`, csrc/track.hip; the rule is `frames.track_boxes`)
+# ------------------------------------------------------------------------------------------------
+TRACK_MAX_BOXES = 256
+
+
+def track_state_bytes(n_streams: int, max_boxes: int) -> int:
+    """Bytes of a tracker state buffer; ``ValueError`` outside the supported sizes (``1 <= max_boxes <= 256``)."""
+    if n_streams < 0 or not 1 <= max_boxes <= TRACK_MAX_BOXES:
+        raise ValueError(f"track_state: n_streams = {n_streams}, max_boxes = {max_boxes} (supported: n_streams >= 0, 1 <= max_boxes <= "
+                         f"{TRACK_MAX_BOXES})")
+    return int(_lib.load().frmap_track_state_bytes(int(n_streams), int(max_boxes)))
+
+
+def track_state(n_streams: int, max_boxes: int, device="cuda") -> torch.Tensor:
+    """A fresh state for `track_step`: a zeroed uint8 buffer on ``device`` (``"cpu"``: for `track_step_host`, as a tensor)."""
+    return torch.zeros(max(track_state_bytes(n_streams, max_boxes), 16), dtype=torch.uint8, device=device)
+
+
+def track_state_host(n_streams: int, max_boxes: int) -> np.ndarray:
+    """A fresh state for `track_step_host`: a zeroed, 16-byte aligned uint8 array."""
+    raw = np.zeros(max(track_state_bytes(n_streams, max_boxes), 16) + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    return raw[off:off + raw.size - 16]
+
+
+def _track_views(a: np.ndarray, S: int, M: int):
+    """The three arrays of a host state buffer as views: ``(meta int32 [S, 2] = (P, next_id), boxes float32 [S, M, 4], ids int32
+    [S, M])``.  The one place where Python knows the layout (csrc/track_rule.h): the ids end the buffer, the boxes precede them,
+    and the library says where the buffer ends."""
+    total = track_state_bytes(S, M)
+    i_off = total - 4 * S * M
+    b_off = i_off - 16 * S * M
+    if a.size < total:
+        raise ValueError(f"track state holds {a.size} bytes, {S} streams of {M} boxes need {total}")
+    return (a[:8 * S].view(np.int32).reshape(S, 2), a[b_off:i_off].view(np.float32).reshape(S, M, 4),
+            a[i_off:total].view(np.int32).reshape(S, M))
+
+
+def track_state_unpack(buf, n_streams: int, max_boxes: int):
+    """The streams of a state buffer (device tensor or host array; a device buffer is copied to the host, which synchronises) as a
+    list of `frames.TrackState`: what `frames.track_boxes` would hold for each stream."""
+    from . import frames as _frames
+    a = buf.detach().cpu().numpy() if isinstance(buf, torch.Tensor) else np.asarray(buf)
+    meta, boxes, ids = _track_views(np.ascontiguousarray(a).view(np.uint8).reshape(-1), int(n_streams), int(max_boxes))
+    return [_frames.TrackState(boxes[s, :meta[s, 0]].copy(), ids[s, :meta[s, 0]].astype(np.int64), int(meta[s, 1]))
+            for s in range(int(n_streams))]
+
+
+def track_state_pack(states, max_boxes: int) -> np.ndarray:
+    """The inverse of `track_state_unpack`: a host state buffer (as `track_state_host`) holding the given `frames.TrackState` of
+    every stream (``None``: a fresh one) - to carry tracks of `frames.track_boxes` on to `track_step`, or to restore saved ones."""
+    S, M = len(states), int(max_boxes)
+    a = track_state_host(S, M)
+    meta, boxes, ids = _track_views(a, S, M)
+    for s, st in enumerate(states):
+        if st is None:
+            continue
+        P = len(st.ids)
+        if P > M:
+            raise ValueError(f"track_state_pack: stream {s} holds {P} boxes, max_boxes is {M}")
+        meta[s] = (P, st.next_id)
+        boxes[s, :P] = np.asarray(st.boxes, np.float32).reshape(P, 4)
+        ids[s, :P] = st.ids
+    return a
+
+
+def track_step(state: torch.Tensor, boxes: torch.Tensor, probs: Optional[torch.Tensor], counts: torch.Tensor,
+               frame_hw: torch.Tensor, det_thresh: float = 0.9, iou_thresh: float = 0.3) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One tracker step of S streams in one launch on the current stream (`frmap_track_step`): ``(ids int32 [S, max_boxes], rois
+    int32 [S, max_boxes, 4])``.  Device tensors: ``state`` from `track_state` (updated in place), ``boxes`` float32 ``[S, max_boxes,
+    4]``, ``probs`` float32 ``[S, max_boxes]`` or ``None`` (every box confident), ``counts`` int32 ``[S]``, ``frame_hw`` int32
+    ``[S, 2]`` = (H, W).  ``ids`` is the `frames.track_boxes` id of each box, -1 for skipped boxes and beyond ``counts[s]``; ``rois``
+    the `frames.clip_boxes` crop of every box with an id, 0 elsewhere.  ``counts`` is device data: the kernel clamps it to
+    ``[0, max_boxes]``; a caller that has it on the host checks it there (`matching.StreamTracker` does)."""
+    boxes = _dev(boxes, "track_step.boxes", torch.float32)
+    probs = None if probs is None else _dev(probs, "track_step.probs", torch.float32)
+    counts = _dev(counts, "track_step.counts", torch.int32)
+    frame_hw = _dev(frame_hw, "track_step.frame_hw", torch.int32)
+    state = _dev(state, "track_step.state", torch.uint8)
+    if boxes.dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"track_step: boxes must be float32 [S, max_boxes, 4], got {tuple(boxes.shape)}")
+    S, M = int(boxes.shape[0]), int(boxes.shape[1])
+    if (probs is not None and tuple(probs.shape) != (S, M)) or tuple(counts.shape) != (S,) or tuple(frame_hw.shape) != (S, 2):
+        raise ValueError("track_step: probs [S, max_boxes], counts [S] and frame_hw [S, 2] must match boxes")
+    if state.numel() < track_state_bytes(S, M):
+        raise ValueError(f"track_step: state holds {state.numel()} bytes, {S} streams of {M} boxes need {track_state_bytes(S, M)}")
+    ids = torch.empty((S, M), dtype=torch.int32, device=boxes.device)
+    rois = torch.empty((S, M, 4), dtype=torch.int32, device=boxes.device)
+    _lib.check(_lib.load().frmap_track_step(state.data_ptr(), boxes.data_ptr(), 0 if probs is None else probs.data_ptr(),
+                                            counts.data_ptr(), frame_hw.data_ptr(), S, M, float(det_thresh), float(iou_thresh),
+                                            ids.data_ptr(), rois.data_ptr(), _stream()), "track_step")
+    return ids, rois
+
+
+def track_step_host(state: np.ndarray, boxes, probs, counts, frame_hw, det_thresh: float = 0.9,
+                    iou_thresh: float = 0.3) -> Tuple[np.ndarray, np.ndarray]:
+    """`track_step` on the CPU over numpy arrays (`frmap_track_step_host`: the kernel's rule compiled for the host; no GPU).
+    ``state``: a writable uint8 array from `track_state_host`, updated in place.  A ``counts[s]`` outside ``[0, max_boxes]`` or an
+    unsupported ``max_boxes`` raises ``ValueError`` with the state untouched."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+    probs = None if probs is None else np.ascontiguousarray(probs, dtype=np.float32)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    frame_hw = np.ascontiguousarray(frame_hw, dtype=np.int32)
+    if len(boxes.shape) != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"track_step_host: boxes must be float32 [S, max_boxes, 4], got {boxes.shape}")
+    S, M = boxes.shape[:2]
+    if (probs is not None and probs.shape != (S, M)) or counts.shape != (S,) or frame_hw.shape != (S, 2):
+        raise ValueError("track_step_host: probs [S, max_boxes], counts [S] and frame_hw [S, 2] must match boxes")
+    if not (isinstance(state, np.ndarray) and state.dtype == np.uint8 and state.flags.c_contiguous and state.flags.writeable):
+        raise ValueError("track_step_host: state must be a writable contiguous uint8 array (track_state_host)")
+    if 1 <= M <= TRACK_MAX_BOXES and state.size < track_state_bytes(S, M):    # (an unsupported max_boxes is the library's to refuse)
+        raise ValueError(f"track_step_host: state holds {state.size} bytes, {S} streams of {M} boxes need {track_state_bytes(S, M)}")
+    ids = np.empty((S, M), np.int32)
+    rois = np.empty((S, M, 4), np.int32)
+    _lib.check(_lib.load().frmap_track_step_host(state.ctypes.data, boxes.ctypes.data, None if probs is None else probs.ctypes.data,
+                                                 counts.ctypes.data, frame_hw.ctypes.data, S, M, float(det_thresh), float(iou_thresh),
+                                                 ids.ctypes.data, rois.ctypes.data), "track_step_host")
+    return ids, rois
+
+
 # every tensor-taking wrapper launches on its operands' device (see _on_operand_device)
 for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_small_cin", "stem7x7_maxpool", "stem7x7_maxpool_u8", "conv_igemm",
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
               "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
-              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm"):
+              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
 

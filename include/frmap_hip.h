@@ -124,6 +124,48 @@ int frmap_align_crop_resize_u8(const void* frames, int n_frames, const int32_t* 
 int frmap_align_warp_host(const unsigned char* frame, int H, int W, long long pitch, const double* mat6, int x1, int y1, int x2,
                           int y2, int bgr, unsigned char* out);
 
+/* The frame loop's IoU tracker (src/app.py:126-147, 183-247: process_webcam's face_id that survives from frame to frame), one
+ * launch for n_streams independent streams (cameras, or clips stepped together), the per-stream state resident on the device.
+ * One step of one stream, given its n = counts[s] detections in the detector's order and its frame's size (H, W):
+ *   - n == 0: the state is left exactly as it is (tracks survive a frame without detections);
+ *   - detection i is SKIPPED (id -1) when probs[i] < det_thresh compared in float32 (a probability equal to (float)det_thresh is
+ *     kept), when a coordinate or the probability is not finite, or when its integer crop - truncate toward zero, max(0, .),
+ *     min(W or H, .): frames.clip_boxes' rule - has x2 <= x1 or y2 <= y1;
+ *   - otherwise the previous boxes j = 0 .. P - 1 not yet matched in this step are scanned in ascending order and j replaces the
+ *     best so far when iou(box_i, prev_j) > best (which starts at 0) and > iou_thresh: ties go to the lowest j.  A winner gives
+ *     its id and becomes matched; without one the detection takes id = next_id, and next_id grows by one;
+ *   - the new state is the raw boxes and ids of the detections that received an id, in order (none: empty); next_id is never
+ *     reset (ids stay below 2^31 per stream).
+ * iou is calc_iou's operation order on the RAW boxes.  DEPARTURES from the reference: (a) the IoU arithmetic is float64 on the
+ * float32 inputs with nothing fused - the reference mixes np.float32 rows with Python floats, so the precision of each of its
+ * operations depends on which operand a max() returned and on the NumPy version; the two can differ only where an IoU lies within
+ * float32 rounding of the threshold or of a competing IoU; (b) the state keeps only boxes that received an id - the reference
+ * rebuilds its box list from every confident box and its id list from the boxes with an id, so a confident box with an empty crop
+ * puts its two lists out of step.
+ *
+ * State buffer (frmap_track_state_bytes(n_streams, max_boxes) bytes, 16-byte aligned, caller-owned; 0 for unsupported sizes):
+ * int32 meta[n_streams][2] = (P, next_id) at byte 0; float32 boxes[n_streams][max_boxes][4] at the next multiple of 16 bytes
+ * after the meta records; int32 ids[n_streams][max_boxes] right after the boxes.  All-zero bytes are a fresh state (P = 0,
+ * next_id = 0); zeroing one stream's meta record resets that stream.
+ *   boxes    : float32 [n_streams][max_boxes][4] = (x1, y1, x2, y2) as the detector returns them, 16-byte aligned
+ *   probs    : float32 [n_streams][max_boxes], or NULL: every box is confident (as clip_boxes' probs = None)
+ *   counts   : int32 [n_streams]; frame_hw : int32 [n_streams][2] = (H, W)
+ *   ids_out  : int32 [n_streams][max_boxes]: the id, -1 for skipped detections and for slots beyond counts[s]
+ *   rois_out : int32 [n_streams][max_boxes][4], 16-byte aligned: the integer crop (x1, y1, x2, y2) of every detection that got an id,
+ *              0 in every other slot
+ * Supported: 1 <= max_boxes <= 256; anything else, n_streams < 0 and null or misaligned pointers are rejected before any launch,
+ * nothing is ever truncated.  counts is DEVICE data this call never sees: the kernel clamps it to [0, max_boxes] (and the state's
+ * P likewise) and never reads or writes outside its stream's slots; a caller that builds counts on the host rejects
+ * counts[s] > max_boxes there (the Python package does).  One wavefront per stream; no atomics. */
+size_t frmap_track_state_bytes(int n_streams, int max_boxes);
+int frmap_track_step(void* state, const float* boxes, const float* probs, const int32_t* counts, const int32_t* frame_hw,
+                     int n_streams, int max_boxes, double det_thresh, double iou_thresh, int32_t* ids_out, int32_t* rois_out,
+                     void* stream);
+/* The same step from the same rule compiled for the CPU (HOST pointers, no stream; no GPU needed).  counts[s] outside
+ * [0, max_boxes] is rejected, like every other bad argument, before anything is written. */
+int frmap_track_step_host(void* state, const float* boxes, const float* probs, const int32_t* counts, const int32_t* frame_hw,
+                          int n_streams, int max_boxes, double det_thresh, double iou_thresh, int32_t* ids_out, int32_t* rois_out);
+
 /* ---------------------------------------------------------------------------------------------
  * Conv weight packing.  `w_oihw` = fp32 [Cout][Cin][KH][KW] with the BatchNorm scale already
  * folded in (w * gamma/sqrt(var+eps)); output is the kernel's LDS-image order in `dtype`.
