@@ -43,6 +43,9 @@ PROTOTYPES = {
     "frmap_track_state_bytes": (_sz, [_i, _i]),
     "frmap_track_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "frmap_track_step_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    "frmap_track_fuse_state_bytes": (_sz, [_i, _i, _i]),
+    "frmap_track_fuse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "frmap_track_fuse_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "frmap_gap_linear_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp]),
     "frmap_conv_small_cin_pool2": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "frmap_conv_igemm_pool2_supported": (_i, [_i, _i, _i, _i, _i]),

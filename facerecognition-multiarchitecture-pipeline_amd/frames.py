@@ -2,7 +2,8 @@
 `matching.embed_boxes` / `matching.identify_boxes` cut out of the frame on the device - and, for aligned crops, the geometry of
 the reference's dataset step (`src/data_prep.py:69-106`): the eye-line rotation, its matrix, the margin rule - and the loop's IoU
 tracker (`app.py:126-147, 183-247`: `box_iou`, `track_boxes`), the readable statement of the rule `ops.track_step` runs for many
-streams in one launch.  Pure host code; the detector itself (MTCNN) is outside this package.
+streams in one launch - and the templates of its tracks (`fuse_tracks`: a track's embeddings pooled into a decayed sum and a
+weight, the rule `ops.track_fuse` runs).  Pure host code; the detector itself (MTCNN) is outside this package.
 
 The tracker departs from the reference in two places.  (a) The IoU is float64 arithmetic on the detector's float32 coordinates,
 nothing fused: the reference mixes `np.float32` rows with Python floats from `tolist()`, so which of its operations run in float32
@@ -176,3 +177,88 @@ def track_boxes(state: Optional[TrackState], boxes, probs, frame_shape: Sequence
             next_id += 1
     got = ids >= 0
     return ids, TrackState(b32[got].copy(), ids[got].copy(), next_id)
+
+
+class TemplateState(NamedTuple):
+    """One stream's track templates: per slot the track id (int64 ``[P]``), the weight (float32 ``[P]``) and the decayed sum of
+    the track's embeddings (float32 ``[P, D]``).  After a step the slots are the detections that received an id, in detection
+    order: `TrackState.ids` of the tracker after the same step."""
+    ids: np.ndarray
+    weights: np.ndarray
+    sums: np.ndarray
+
+
+def new_template_state(dim: int = 0) -> TemplateState:
+    return TemplateState(np.zeros(0, np.int64), np.zeros(0, np.float32), np.zeros((0, dim), np.float32))
+
+
+def fuse_tracks(state: Optional[TemplateState], ids, emb, det, decay: float = 1.0):
+    """One step of the track templates for one stream, the readable statement of the rule `ops.track_fuse` runs for many streams
+    in one launch: ``(fused float32 [r, D], frames float32 [r], new_state)``.  ``state``: what the previous call returned
+    (``None``: a fresh one); ``ids``: the tracker's ids of this step's ``n`` detections (`track_boxes`; -1: skipped); ``emb``:
+    float32 ``[r, D]``, the embeddings computed at this step; ``det``: int ``[r]``, the detection each row belongs to - not every
+    detection needs a row; ``decay``: ``0 < decay <= 1``, taken as float32.
+
+    ``n == 0`` leaves the state as it is (tracks survive empty frames, as in the tracker).  Otherwise the new state has one slot
+    per detection with ``id >= 0``, in detection order; ids of the old state that are absent are dropped.  A detection whose id
+    is in the old state and whose row holds only finite values pools it: ``w' = fl(fl(decay w) + 1)``, ``sum' = fl(fl(decay sum)
+    + e)`` - float32, product then sum, two roundings; an id that is new starts at ``w' = 1``, ``sum' = e``.  Without a row, or
+    with a row that holds an infinity or a NaN, the old slot is carried over unchanged (a new id: ``w' = 0``, ``sum' = 0``): one
+    bad frame does not poison a track.  Row ``i`` comes back as the template ``sum' / w'`` (float32 division) of its track with
+    ``frames[i] = w'`` - with ``decay = 1`` the number of embeddings pooled -; a row whose detection has ``id < 0``, that is not
+    finite, or whose slot has ``w' == 0`` comes back as it came, with ``frames[i] = 0``.
+
+    ``ValueError``, before anything is computed, for a ``det`` outside ``[0, n)`` and for two rows of the same detection."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = len(ids)
+    emb = np.asarray(emb, dtype=np.float32)
+    det = np.asarray(det, dtype=np.int64).reshape(-1)
+    if emb.ndim != 2 or emb.shape[0] != len(det):
+        raise ValueError(f"fuse_tracks: emb must be float32 [r, D] with one detection index per row, got {emb.shape} and {len(det)}")
+    d32 = np.float32(decay)
+    if not (np.float32(0) < d32 <= np.float32(1)):
+        raise ValueError(f"fuse_tracks: decay = {decay} is outside (0, 1]")
+    if len(det) and (det.min() < 0 or det.max() >= n):
+        raise ValueError(f"fuse_tracks: a row names a detection outside [0, {n})")
+    if len(np.unique(det)) != len(det):
+        raise ValueError("fuse_tracks: two rows name the same detection")
+    D = emb.shape[1]
+    if state is None:
+        state = new_template_state(D)
+    fused, frames = emb.copy(), np.zeros(len(det), np.float32)
+    if n == 0:
+        return fused, frames, state
+    if len(state.ids) and state.sums.shape[1] != D:
+        raise ValueError(f"fuse_tracks: the state holds sums of {state.sums.shape[1]} values, the rows have {D}")
+    row_of = {int(i): r for r, i in enumerate(det)}
+    old = {}
+    for j, tid in enumerate(state.ids.tolist()):
+        old.setdefault(tid, j)                                # (ids of a state are distinct; the lowest slot if they were not)
+    new_ids, new_w, new_sums = [], [], []
+    one = np.float32(1)
+    for i in range(n):
+        tid = int(ids[i])
+        if tid < 0:
+            continue
+        j = old.get(tid)
+        r = row_of.get(i)
+        if r is not None and np.isfinite(emb[r]).all():
+            if j is None:
+                w2, s2 = one, emb[r].copy()
+            else:
+                with np.errstate(all="ignore"):               # (a sum may overflow; the rule says what comes out, not that it is useful)
+                    w2 = np.float32(np.float32(d32 * state.weights[j]) + one)
+                    s2 = (d32 * state.sums[j]).astype(np.float32) + emb[r]
+            if w2 != 0:
+                with np.errstate(all="ignore"):
+                    fused[r] = s2 / w2
+                frames[r] = w2
+        elif j is not None:
+            w2, s2 = state.weights[j], state.sums[j].copy()
+        else:
+            w2, s2 = np.float32(0), np.zeros(D, np.float32)
+        new_ids.append(tid)
+        new_w.append(w2)
+        new_sums.append(s2)
+    return fused, frames, TemplateState(np.asarray(new_ids, np.int64), np.asarray(new_w, np.float32),
+                                        np.asarray(new_sums, np.float32).reshape(len(new_ids), D))

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import weakref
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -499,15 +500,22 @@ def _match_records(model, u8, g, mean, std, what, normalize):
     with torch.no_grad():
         if h is not None and (model.input_mean, model.input_std) == (mean, std):
             return h.embed_and_match(model._check_input(u8), g.matrix, g.prepared, float("inf"), normalize, packed=True)[3]
-        x = ops.normalize_u8(u8, mean, std)[0]
-        if what == "forward":
-            emb = model(x)
-        else:
-            emb = model.get_embedding(x)
-        emb = (emb.unsqueeze(0) if emb.dim() == 1 else emb).to(torch.float32)
-        if what == "embedding" and normalize:
-            emb = ops.l2_normalize(emb, 1e-12)
+        emb = _probe_rows(model, u8, mean, std, what, normalize)
         return ops.match_top1(emb, g.matrix, float("inf"), packed=True, prepared=g.prepared)[3]
+
+
+def _probe_rows(model, u8, mean, std, what, normalize):
+    """The embed-then-match route's probes: ToTensor + Normalize, ONE model call, float32 ``[n, D]`` rows (L2-normalised for
+    ``what="embedding"`` with ``normalize``)."""
+    x = ops.normalize_u8(u8, mean, std)[0]
+    if what == "forward":
+        emb = model(x)
+    else:
+        emb = model.get_embedding(x)
+    emb = (emb.unsqueeze(0) if emb.dim() == 1 else emb).to(torch.float32)
+    if what == "embedding" and normalize:
+        emb = ops.l2_normalize(emb, 1e-12)
+    return emb
 
 
 def _record_results(idx, dist, g, thresh) -> list:
@@ -593,6 +601,8 @@ class StreamTracker:
         else:
             self.state = ops.track_state(self.n_streams, self.max_boxes, self.device)
         self.counts = np.zeros(self.n_streams, np.int32)      # of the last step
+        self.device_counts = None                             # the same on the tracker's device (what `ops.track_fuse` clamps)
+        self._templates = weakref.WeakSet()                   # `TrackTemplates` that follow this tracker's ids
 
     def pad(self, boxes, probs, frame_shapes):
         """The step's host arrays ``(boxes float32 [S, M, 4], probs float32 [S, M] or None, counts int32 [S], frame_hw int32
@@ -635,9 +645,11 @@ class StreamTracker:
         b_pad, p_pad, c_pad, hw = self.pad(boxes, probs, frame_shapes)
         self.counts = c_pad.copy()
         if self.device.type == "cpu":
+            self.device_counts = self.counts
             return ops.track_step_host(self.state, b_pad, p_pad, c_pad, hw, self.det_thresh, self.iou_thresh)
         S, M = self.n_streams, self.max_boxes
         d = torch.from_numpy(b_pad.base).to(self.device, non_blocking=True)
+        self.device_counts = d[S * M * 5:S * M * 5 + S].view(torch.int32)
         return ops.track_step(self.state, d[:S * M * 4].view(S, M, 4), None if p_pad is None else d[S * M * 4:S * M * 5].view(S, M),
                               d[S * M * 5:S * M * 5 + S].view(torch.int32), d[S * M * 5 + S:].view(torch.int32).view(S, 2),
                               self.det_thresh, self.iou_thresh)
@@ -649,13 +661,16 @@ class StreamTracker:
         return [a[s, :self.counts[s]].astype(np.int64) for s in range(self.n_streams)]
 
     def reset(self, stream: Optional[int] = None) -> None:
-        """Forget every track and restart the ids at 0, for one stream or (``None``) for all."""
+        """Forget every track and restart the ids at 0, for one stream or (``None``) for all - and with them the templates of
+        every `TrackTemplates` built on this tracker: the ids they are kept under start again."""
         if stream is None:
             self.state[:] = 0
         else:
             if not 0 <= stream < self.n_streams:
                 raise ValueError(f"StreamTracker.reset: stream {stream} of {self.n_streams}")
             self.state[8 * stream:8 * stream + 8] = 0
+        for tpl in list(self._templates):
+            tpl.reset(stream)
 
     def next_ids(self) -> List[int]:
         """The reference's ``face_id_counter`` of every stream (one small device → host copy)."""
@@ -664,9 +679,64 @@ class StreamTracker:
         return meta.view(np.int32).reshape(-1, 2)[:, 1].tolist()
 
 
-def _stream_step(who, model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin):
-    """What `embed_streams` and `identify_streams` share: the host's clip, the tracker's launch (if any) and the one crop launch.
-    ``(uint8 crops [N, h, w, 3], kept indices per stream, padded device ids or None)``."""
+class TrackTemplates:
+    """The templates of a `StreamTracker`'s tracks: per track (``face_id``) the decayed sum of its embeddings and their weight,
+    resident on the tracker's device and updated in ONE launch per step (`ops.track_fuse`; the rule is `frames.fuse_tracks`).  The
+    state mirrors the tracker's slot for slot - after a step a stream's slots are the detections that received an id, in order -
+    so a track that the tracker drops is dropped here, and an id never comes back.  ``dim``: the length of an embedding;
+    ``decay``: ``0 < decay <= 1``, the weight an embedding loses per step (1: the plain mean).  ``tracker.reset`` clears the
+    templates with the tracks.  On a ``device="cpu"`` tracker the same rule runs compiled for the CPU (`ops.track_fuse_host`)."""
+
+    def __init__(self, tracker: StreamTracker, dim: int, decay: float = 1.0):
+        if not isinstance(tracker, StreamTracker):
+            raise ValueError("TrackTemplates: tracker must be the StreamTracker whose ids the templates follow")
+        if not (0.0 < float(np.float32(decay)) <= 1.0):
+            raise ValueError(f"TrackTemplates: decay = {decay} is outside (0, 1]")
+        self.tracker, self.dim, self.decay = tracker, int(dim), float(decay)
+        self.device = tracker.device
+        if self.device.type == "cpu":
+            self.state = ops.track_fuse_state_host(tracker.n_streams, tracker.max_boxes, self.dim)
+        else:
+            self.state = ops.track_fuse_state(tracker.n_streams, tracker.max_boxes, self.dim, self.device)
+        tracker._templates.add(self)
+
+    def step(self, ids, emb, rows):
+        """Pool this step's embeddings: ``ids`` = the padded ids `StreamTracker.step` just returned, ``emb`` float32 ``[N, D]`` on
+        the tracker's device, ``rows`` a HOST int32 ``[N, 2]`` = (stream, detection index) of every row.  ``rows`` is checked
+        against the step's counts on the host (``ValueError`` before any state moves), uploaded, and ONE launch returns ``(fused
+        [N, D], frames [N])`` (`ops.track_fuse`), nothing synchronised."""
+        tr = self.tracker
+        if tr.device_counts is None:
+            raise ValueError("TrackTemplates.step: the tracker has not stepped yet")
+        if tuple(emb.shape[1:]) != (self.dim,):
+            raise ValueError(f"TrackTemplates.step: embeddings of shape {tuple(emb.shape)}, the templates hold {self.dim} values")
+        if self.device.type == "cpu":
+            emb = emb.detach().numpy() if isinstance(emb, torch.Tensor) else emb
+            return ops.track_fuse_host(self.state, ids, tr.counts, emb, rows, self.decay)
+        return ops.track_fuse(self.state, ids, tr.device_counts, emb, rows, self.decay, host_counts=tr.counts)
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget the templates of one stream or (``None``) of all."""
+        if stream is None:
+            self.state[:] = 0
+        else:
+            if not 0 <= stream < self.tracker.n_streams:
+                raise ValueError(f"TrackTemplates.reset: stream {stream} of {self.tracker.n_streams}")
+            self.state[8 * stream:8 * stream + 8] = 0
+
+    def unpack(self):
+        """Per stream the `frames.TemplateState` (ids, weights, sums) the device holds (a device -> host copy, which synchronises)."""
+        return ops.track_fuse_state_unpack(self.state, self.tracker.n_streams, self.tracker.max_boxes, self.dim)
+
+
+def _stream_prepare(who, model, frames, boxes, probs, tracker, det_thresh, landmarks, margin, templates=None):
+    """Everything of a stream step that can raise on the host, before any state moves: the arguments, and `clip_boxes` per
+    stream.  ``(frames as a list, boxes, probs, rois int32 [N, 5], kept indices per stream, eye matrices or None)``."""
+    if templates is not None:
+        if tracker is None:
+            raise ValueError(f"{who}: templates are kept per track id - they need the tracker they were built on")
+        if not isinstance(templates, TrackTemplates) or templates.tracker is not tracker:
+            raise ValueError(f"{who}: templates must be a TrackTemplates built on this tracker")
     fl = _frame_list(frames)
     S = len(fl)
     if S == 0:
@@ -692,12 +762,41 @@ def _stream_step(who, model, frames, boxes, probs, tracker, size, det_thresh, la
         det_thresh = _frames.DET_THRESH
     # everything that can raise on the host - bad arguments above, `clip_boxes` on a non-finite coordinate here - raises before
     # the tracker's state moves
-    r5, kepts, mats = _stream_rois(fl, boxes, probs, det_thresh, landmarks, margin)
+    return fl, boxes, probs, _stream_rois(fl, boxes, probs, det_thresh, landmarks, margin)
+
+
+def _stream_step(who, model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin):
+    """What `embed_streams` and `identify_streams` share: the host's clip, the tracker's launch (if any) and the one crop launch.
+    ``(uint8 crops [N, h, w, 3], kept indices per stream, padded device ids or None)``."""
+    fl, boxes, probs, (r5, kepts, mats) = _stream_prepare(who, model, frames, boxes, probs, tracker, det_thresh, landmarks, margin)
     ids = None
     if tracker is not None:
         ids = tracker.step(boxes, probs, [f.shape for f in fl])[0]
     whole = getattr(frames, "ndim", 0) == 4                    # a stack goes up (or is used in place) whole
     return _launch_crops(model, frames if whole else fl, r5, mats, size), kepts, ids
+
+
+def _template_step(who, model, frames, boxes, probs, tracker, templates, size, det_thresh, landmarks, margin, embed):
+    """A stream step with templates: the host's clip, the one crop launch, ``embed(crops)`` = the one model call, the tracker's
+    launch and the one `ops.track_fuse` launch.  The crops depend on the host's clip alone, not on the tracker, so the model
+    runs BEFORE the tracker here: only its output says how long an embedding is, and a length the templates do not hold is
+    refused while the tracker's state has not moved.  ``(embeddings [N, D], fused [N, D], frames [N], kept indices per stream,
+    padded device ids)``."""
+    fl, boxes, probs, (r5, kepts, mats) = _stream_prepare(who, model, frames, boxes, probs, tracker, det_thresh, landmarks, margin,
+                                                          templates)
+    whole = getattr(frames, "ndim", 0) == 4
+    u8 = _launch_crops(model, frames if whole else fl, r5, mats, size)
+    if u8.shape[0]:
+        emb = embed(u8)
+        if emb.dim() != 2 or emb.shape[1] != templates.dim:
+            raise ValueError(f"{who}: the model returns embeddings of shape {tuple(emb.shape)}, the templates hold {templates.dim} values")
+        emb = emb.to(torch.float32)
+    else:
+        emb = torch.empty((0, templates.dim), dtype=torch.float32, device=u8.device)
+    ids = tracker.step(boxes, probs, [f.shape for f in fl])[0]
+    rows = np.concatenate([np.stack([np.full(len(k), s, np.int32), k.astype(np.int32)], 1) for s, k in enumerate(kepts)])
+    fused, nframes = templates.step(ids, emb, rows)
+    return emb, fused, nframes, kepts, ids
 
 
 def _face_ids(tracker, ids_host, kepts, margin) -> list:
@@ -715,13 +814,25 @@ def _face_ids(tracker, ids_host, kepts, margin) -> list:
 
 
 def embed_streams(model, frames, boxes, probs=None, tracker: Optional[StreamTracker] = None, size=(160, 160), mean=(.5, .5, .5),
-                  std=(.5, .5, .5), det_thresh: Optional[float] = None, landmarks=None, margin: float = 0.0):
+                  std=(.5, .5, .5), det_thresh: Optional[float] = None, landmarks=None, margin: float = 0.0,
+                  templates: Optional[TrackTemplates] = None):
     """`embed_boxes` for S frames - S camera streams, or S frames of a clip - in one step: per stream `frames.clip_boxes` on the
     host, then ONE tracker launch (if ``tracker``), ONE crop launch over all frames and ONE ``model(x)``.  Arguments as
     `identify_streams`.  Returns ``(embeddings [N, D] on the device, kept, offsets int64 [S + 1], ids)``: stream s owns rows
     ``offsets[s] : offsets[s + 1]``, row ``offsets[s] + i`` is box ``kept[s][i]`` of its frame - what `embed_boxes` returns for that
     frame (to the bit under `ops.set_batch_invariant`); ``ids``: the tracker's padded int32 ``[S, max_boxes]`` ids on the device
-    (`StreamTracker.unpad`), or ``None``.  A frame with no kept box contributes no rows; with no rows at all no model is called."""
+    (`StreamTracker.unpad`), or ``None``.  A frame with no kept box contributes no rows; with no rows at all no model is called.
+
+    ``templates``: a `TrackTemplates` built on ``tracker``: after the model ONE `ops.track_fuse` launch pools every row into its
+    track's template, and the return value grows to ``(embeddings, kept, offsets, ids, fused [N, D], frames [N])``: row i of
+    ``fused`` is the template of row i's track after this step, ``frames[i]`` its weight (0: the row came back as it is - see
+    `frames.fuse_tracks`).  Refused with ``ValueError`` before the tracker's state moves: ``templates`` without ``tracker`` or
+    built on another one, and a model whose embeddings are not ``templates.dim`` long."""
+    if templates is not None:
+        emb, fused, nframes, kepts, ids = _template_step("embed_streams", model, frames, boxes, probs, tracker, templates, size, det_thresh,
+                                                         landmarks, margin, lambda u8: _embed_crops(model, u8, mean, std))
+        offsets = np.concatenate([[0], np.cumsum([len(k) for k in kepts])]).astype(np.int64)
+        return emb, kepts, offsets, ids, fused, nframes
     u8, kepts, ids = _stream_step("embed_streams", model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin)
     offsets = np.concatenate([[0], np.cumsum([len(k) for k in kepts])]).astype(np.int64)
     return _embed_crops(model, u8, mean, std), kepts, offsets, ids
@@ -729,7 +840,8 @@ def embed_streams(model, frames, boxes, probs=None, tracker: Optional[StreamTrac
 
 def identify_streams(model, frames, boxes, refs, tracker: Optional[StreamTracker] = None, thresh=REC_THRESH, probs=None,
                      size=(160, 160), mean=(.5, .5, .5), std=(.5, .5, .5), what: str = "forward", normalize: bool = False,
-                     landmarks=None, margin: float = 0.0, det_thresh: Optional[float] = None):
+                     landmarks=None, margin: float = 0.0, det_thresh: Optional[float] = None,
+                     templates: Optional[TrackTemplates] = None):
     """The reference's frame loop (`app.py:181-247`) between the detector and the names, as ONE step over S streams - S cameras,
     or S frames of a clip: per stream `frames.clip_boxes` (with `frames.margin_boxes` and the eye matrices as `identify_boxes`
     does them), then one tracker launch (if ``tracker``), ONE crop launch over all frames (`resize.crop_resize_u8` /
@@ -749,9 +861,27 @@ def identify_streams(model, frames, boxes, refs, tracker: Optional[StreamTracker
     frame (to the bit under `ops.set_batch_invariant`), ``face_ids`` int64 ``[len(kept)]``: the reference's ``face_id`` of box
     ``kept[i]`` ("Unknown #id"), or ``None`` without a tracker.  With ``margin > 0`` the tracker's skip rule still uses the
     unwidened box: a box may be cropped yet carry ``face_id = -1``, but only if its unwidened crop is empty.  A frame with no kept
-    box contributes no rows; a step with no rows at all makes no model call."""
+    box contributes no rows; a step with no rows at all makes no model call.
+
+    ``templates``: a `TrackTemplates` built on ``tracker`` - identify the TRACK, not only the frame.  The step then takes the
+    embed-then-match route (never `frmap_model_embed_and_match`): one crop launch, ONE model call, the tracker's launch, ONE
+    `ops.track_fuse` launch that pools every probe into its track's template (`frames.fuse_tracks`), `ops.l2_normalize` of the
+    templates when ``normalize``, ONE `ops.match_top1` over the 2N stacked probes - the per-frame rows first, the templates behind
+    them - and ONE device -> host copy.  Returns, per stream, ``(results, kept, face_ids, track_results, track_frames)``.  ``kept``
+    and ``face_ids`` are those of the same call without ``templates``; ``results`` is identical bit for bit WHERE THAT CALL TAKES
+    THE EMBED-THEN-MATCH ROUTE TOO (the match re-scores exactly, so a probe's record does not depend on the batch it is in).  A
+    model-handle model called with ``what="embedding"`` and its own input normalisation as ``mean`` / ``std`` runs without
+    templates as one `frmap_model_embed_and_match` call on the uint8 crops - another route to the same embedding, whose records
+    are not promised to equal this one's to the bit.  ``track_results[i]`` is the `compare_faces` triple of the template of box ``kept[i]``'s track after this
+    step, and ``track_frames[i]`` (float32) its weight - with ``decay = 1`` the number of frames pooled; 0 where the template is
+    the frame's own embedding (a box without an id, or a non-finite embedding).  Refused with ``ValueError`` before the
+    tracker's state moves: ``templates`` without ``tracker`` or built on another one, and a model whose output is not
+    ``templates.dim`` long."""
     if what not in ("forward", "embedding"):
         raise ValueError(f"identify_streams: what must be 'forward' or 'embedding', got {what!r}")
+    if templates is not None:
+        return _identify_tracks(model, frames, boxes, refs, tracker, templates, thresh, probs, size, mean, std, what, normalize,
+                                landmarks, margin, det_thresh)
     u8, kepts, ids = _stream_step("identify_streams", model, frames, boxes, probs, tracker, size, det_thresh, landmarks, margin)
     n = u8.shape[0]
     rec = None
@@ -777,6 +907,43 @@ def identify_streams(model, frames, boxes, refs, tracker: Optional[StreamTracker
     for kept, fid in zip(kepts, face_ids):
         out.append((flat[at:at + len(kept)], kept, fid))
         at += len(kept)
+    return out
+
+
+def _identify_tracks(model, frames, boxes, refs, tracker, templates, thresh, probs, size, mean, std, what, normalize, landmarks,
+                     margin, det_thresh):
+    """`identify_streams` with templates: see there."""
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+
+    def embed(u8):
+        with torch.no_grad():
+            return _probe_rows(model, u8, mean, std, what, normalize)
+    emb, fused, nframes, kepts, ids = _template_step("identify_streams", model, frames, boxes, probs, tracker, templates, size,
+                                                     det_thresh, landmarks, margin, embed)
+    n = emb.shape[0]
+    face_ids = [np.zeros(0, np.int64) for _ in kepts]
+    flat = [("Unknown", float('inf'), None)] * (2 * n)
+    host_frames = np.zeros(0, np.float32)
+    if n:
+        parts = []
+        if refs is not None and len(refs):
+            g = _as_gallery(refs, emb.device)
+            if what == "embedding" and normalize:
+                fused = ops.l2_normalize(fused, 1e-12)
+            parts.append(ops.match_top1(torch.cat([emb, fused]), g.matrix, float("inf"), packed=True, prepared=g.prepared)[3].reshape(-1))
+        # the one host copy: the int32 match records [2 n, 2] (if any), the bits of the weights [n] and the padded ids [S, max_boxes]
+        both = torch.cat(parts + [nframes.view(torch.int32), ids.reshape(-1)]).cpu()
+        at = both.numel() - ids.numel()
+        face_ids = _face_ids(tracker, both[at:].view(ids.shape).numpy(), kepts, margin)
+        host_frames = both[at - n:at].view(torch.float32).numpy()
+        if parts:
+            rec = both[:4 * n].view(2 * n, 2)
+            flat = _record_results(rec[:, 0].tolist(), rec.view(torch.float32)[:, 1].tolist(), g, thresh)
+    out, at = [], 0
+    for kept, fid in zip(kepts, face_ids):
+        k = len(kept)
+        out.append((flat[at:at + k], kept, fid, flat[n + at:n + at + k], host_frames[at:at + k].copy()))
+        at += k
     return out
 
 

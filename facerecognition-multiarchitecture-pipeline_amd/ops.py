@@ -1009,12 +1009,155 @@ def track_step_host(state: np.ndarray, boxes, probs, counts, frame_hw, det_thres
     return ids, rois
 
 
+# ------------------------------------------------------------------------------------------------
+# track templates: a track's embeddings pooled on the device (`frmap_track_fuse*`, csrc/track_fuse.hip; the rule is
+# `frames.fuse_tracks`)
+# ------------------------------------------------------------------------------------------------
+TRACK_FUSE_MAX_DIM = 4096
+
+
+def track_fuse_state_bytes(n_streams: int, max_boxes: int, dim: int) -> int:
+    """Bytes of a template state buffer; ``ValueError`` outside the supported sizes (``1 <= max_boxes <= 256``, ``1 <= dim <= 4096``)."""
+    if n_streams < 0 or not 1 <= max_boxes <= TRACK_MAX_BOXES or not 1 <= dim <= TRACK_FUSE_MAX_DIM:
+        raise ValueError(f"track_fuse_state: n_streams = {n_streams}, max_boxes = {max_boxes}, dim = {dim} (supported: n_streams >= 0, "
+                         f"1 <= max_boxes <= {TRACK_MAX_BOXES}, 1 <= dim <= {TRACK_FUSE_MAX_DIM})")
+    return int(_lib.load().frmap_track_fuse_state_bytes(int(n_streams), int(max_boxes), int(dim)))
+
+
+def track_fuse_state(n_streams: int, max_boxes: int, dim: int, device="cuda") -> torch.Tensor:
+    """A fresh state for `track_fuse`: a zeroed uint8 buffer on ``device``."""
+    return torch.zeros(max(track_fuse_state_bytes(n_streams, max_boxes, dim), 16), dtype=torch.uint8, device=device)
+
+
+def track_fuse_state_host(n_streams: int, max_boxes: int, dim: int) -> np.ndarray:
+    """A fresh state for `track_fuse_host`: a zeroed, 16-byte aligned uint8 array."""
+    raw = np.zeros(max(track_fuse_state_bytes(n_streams, max_boxes, dim), 16) + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    return raw[off:off + raw.size - 16]
+
+
+def track_fuse_state_unpack(buf, n_streams: int, max_boxes: int, dim: int):
+    """The streams of a template state buffer (device tensor or host array; a device buffer is copied to the host, which
+    synchronises) as a list of `frames.TemplateState`: what `frames.fuse_tracks` would hold for each stream.  The one place where
+    Python knows the layout (csrc/track_fuse_rule.h): the sums end the buffer, the weights and the ids precede them, two banks of
+    ``max_boxes`` slots per stream, and a stream's meta record ``(P, bank)`` says which bank is current."""
+    from . import frames as _frames
+    S, M, D = int(n_streams), int(max_boxes), int(dim)
+    a = buf.detach().cpu().numpy() if isinstance(buf, torch.Tensor) else np.asarray(buf)
+    a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    total, pitch = track_fuse_state_bytes(S, M, D), (D + 3) & ~3
+    if a.size < total:
+        raise ValueError(f"template state holds {a.size} bytes, {S} streams of {M} boxes of {D} values need {total}")
+    s_off = total - 8 * S * M * pitch
+    w_off = s_off - 8 * S * M
+    i_off = w_off - 8 * S * M
+    meta = a[:8 * S].view(np.int32).reshape(S, 2)
+    ids = a[i_off:w_off].view(np.int32).reshape(S, 2, M)
+    w = a[w_off:s_off].view(np.float32).reshape(S, 2, M)
+    sums = a[s_off:total].view(np.float32).reshape(S, 2, M, pitch)
+    out = []
+    for s in range(S):
+        P, b = min(max(int(meta[s, 0]), 0), M), int(meta[s, 1]) & 1
+        out.append(_frames.TemplateState(ids[s, b, :P].astype(np.int64), w[s, b, :P].copy(), sums[s, b, :P, :D].copy()))
+    return out
+
+
+def _fuse_check_rows(what: str, rows: np.ndarray, counts: np.ndarray, S: int) -> None:
+    """The host's check of ``rows`` against the step's host ``counts``: what `frmap_track_fuse_host` refuses, refused before a launch."""
+    if rows.shape[0] == 0:
+        return
+    st, det = rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64)
+    if st.min() < 0 or st.max() >= S:
+        raise ValueError(f"{what}: a row names a stream outside [0, {S})")
+    if det.min() < 0 or (det >= counts.astype(np.int64)[st]).any():
+        raise ValueError(f"{what}: a row names a detection outside [0, counts[stream])")
+    if len(np.unique(st * (int(det.max()) + 1) + det)) != len(det):
+        raise ValueError(f"{what}: two rows name the same detection")
+
+
+def track_fuse(state: torch.Tensor, ids: torch.Tensor, counts: torch.Tensor, emb: torch.Tensor, rows, decay: float = 1.0,
+               host_counts=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One template step of S streams in one launch on the current stream (`frmap_track_fuse`): ``(fused float32 [N, D], frames
+    float32 [N])``.  Device tensors: ``state`` from `track_fuse_state` (updated in place), ``ids`` int32 ``[S, max_boxes]`` and
+    ``counts`` int32 ``[S]`` of this step's `track_step`, ``emb`` float32 ``[N, D]``.  ``rows``: int32 ``[N, 2]`` = (stream,
+    detection index) of every row of ``emb``.  Given as a HOST array together with ``host_counts`` (the step's counts on the host)
+    it is checked here - a detection index ``>= counts[stream]``, a stream outside ``[0, S)``, two rows of one detection:
+    ``ValueError`` before anything is launched - and uploaded; a device tensor is data the host never saw: the kernel clamps
+    ``counts``, passes a row that names no detection through and touches no other stream's slots whatever ``rows`` holds.
+    ``fused[r]`` is the template of row r's track after this step and ``frames[r]`` its weight; rows that are passed through
+    (`frames.fuse_tracks`) come back as they came with ``frames[r] = 0``."""
+    state = _dev(state, "track_fuse.state", torch.uint8)
+    ids = _dev(ids, "track_fuse.ids", torch.int32)
+    counts = _dev(counts, "track_fuse.counts", torch.int32)
+    emb = _dev(emb, "track_fuse.emb", torch.float32)
+    if ids.dim() != 2 or emb.dim() != 2 or tuple(counts.shape) != (ids.shape[0],):
+        raise ValueError(f"track_fuse: ids must be int32 [S, max_boxes], counts [S] and emb float32 [N, D]; got {tuple(ids.shape)}, "
+                         f"{tuple(counts.shape)} and {tuple(emb.shape)}")
+    S, M = int(ids.shape[0]), int(ids.shape[1])
+    N, D = int(emb.shape[0]), int(emb.shape[1])
+    if not (0.0 < float(np.float32(decay)) <= 1.0):
+        raise ValueError(f"track_fuse: decay = {decay} is outside (0, 1]")
+    if state.numel() < track_fuse_state_bytes(S, M, D):
+        raise ValueError(f"track_fuse: state holds {state.numel()} bytes, {S} streams of {M} boxes of {D} values need "
+                         f"{track_fuse_state_bytes(S, M, D)}")
+    if not isinstance(rows, torch.Tensor):
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)
+        if rows.shape[0] != N:
+            raise ValueError(f"track_fuse: {rows.shape[0]} rows for {N} embeddings")
+        if host_counts is None:
+            raise ValueError("track_fuse: host rows are checked against host_counts, the step's counts on the host")
+        host_counts = np.asarray(host_counts).reshape(-1)
+        if host_counts.shape != (S,) or (host_counts < 0).any() or (host_counts > M).any():
+            raise ValueError("track_fuse: host_counts must be [S] values in [0, max_boxes]")
+        _fuse_check_rows("track_fuse", rows, host_counts, S)
+        rows = torch.from_numpy(rows).to(emb.device, non_blocking=True)
+    rows = _dev(rows, "track_fuse.rows", torch.int32)
+    if tuple(rows.shape) != (N, 2):
+        raise ValueError(f"track_fuse: rows must be int32 [{N}, 2], got {tuple(rows.shape)}")
+    if N > S * M:
+        raise ValueError(f"track_fuse: {N} rows for {S} streams of {M} boxes")
+    fused = torch.empty((N, D), dtype=torch.float32, device=emb.device)
+    nframes = torch.empty((N,), dtype=torch.float32, device=emb.device)
+    _lib.check(_lib.load().frmap_track_fuse(state.data_ptr(), ids.data_ptr(), counts.data_ptr(), emb.data_ptr() if N else 0,
+                                            rows.data_ptr() if N else 0, N, S, M, D, float(decay), fused.data_ptr() if N else 0,
+                                            nframes.data_ptr() if N else 0, _stream()), "track_fuse")
+    return fused, nframes
+
+
+def track_fuse_host(state: np.ndarray, ids, counts, emb, rows, decay: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+    """`track_fuse` on the CPU over numpy arrays (`frmap_track_fuse_host`: the kernel's rule compiled for the host; no GPU).
+    ``state``: a writable uint8 array from `track_fuse_state_host`, updated in place.  A count outside ``[0, max_boxes]``, a row
+    that names no detection of this step, two rows of one detection, an unsupported size or ``decay`` raise ``ValueError`` with the
+    state untouched."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    emb = np.ascontiguousarray(emb, dtype=np.float32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)
+    if ids.ndim != 2 or emb.ndim != 2 or counts.shape != (ids.shape[0],) or rows.shape[0] != emb.shape[0]:
+        raise ValueError(f"track_fuse_host: ids must be int32 [S, max_boxes], counts [S], emb float32 [N, D] and rows [N, 2]; got "
+                         f"{ids.shape}, {counts.shape}, {emb.shape} and {rows.shape}")
+    S, M = ids.shape
+    N, D = emb.shape
+    if not (isinstance(state, np.ndarray) and state.dtype == np.uint8 and state.flags.c_contiguous and state.flags.writeable):
+        raise ValueError("track_fuse_host: state must be a writable contiguous uint8 array (track_fuse_state_host)")
+    if 1 <= M <= TRACK_MAX_BOXES and 1 <= D <= TRACK_FUSE_MAX_DIM and state.size < track_fuse_state_bytes(S, M, D):
+        raise ValueError(f"track_fuse_host: state holds {state.size} bytes, {S} streams of {M} boxes of {D} values need "
+                         f"{track_fuse_state_bytes(S, M, D)}")
+    fused = np.empty((N, D), np.float32)
+    nframes = np.empty((N,), np.float32)
+    _lib.check(_lib.load().frmap_track_fuse_host(state.ctypes.data, ids.ctypes.data, counts.ctypes.data, emb.ctypes.data if N else None,
+                                                 rows.ctypes.data if N else None, N, S, M, D, float(decay),
+                                                 fused.ctypes.data if N else None, nframes.ctypes.data if N else None),
+               "track_fuse_host")
+    return fused, nframes
+
+
 # every tensor-taking wrapper launches on its operands' device (see _on_operand_device)
 for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_small_cin", "stem7x7_maxpool", "stem7x7_maxpool_u8", "conv_igemm",
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
               "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
-              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step"):
+              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
 

@@ -166,6 +166,41 @@ int frmap_track_step(void* state, const float* boxes, const float* probs, const 
 int frmap_track_step_host(void* state, const float* boxes, const float* probs, const int32_t* counts, const int32_t* frame_hw,
                           int n_streams, int max_boxes, double det_thresh, double iou_thresh, int32_t* ids_out, int32_t* rois_out);
 
+/* Track templates: the embeddings of a track (a face_id of frmap_track_step) pooled on the device, one launch per step for
+ * n_streams streams between the model and the match.  Per stream the state is a list of slots (id, weight w, sum[dim]); one step
+ * of one stream, given the tracker's ids of this step (ids[s][0 .. counts[s]), -1 = skipped), the step's embedding rows emb
+ * [n_rows][dim] and rows [n_rows][2] = (stream, detection index) of each row:
+ *   - counts[s] == 0: the state is left exactly as it is;
+ *   - otherwise the new state has one slot per detection with id >= 0, in detection order (the tracker's own state after that
+ *     step, slot for slot); old ids that are absent are dropped;
+ *   - a detection whose id is in the old state and that has a row of finite values: w' = fl(fl(decay w) + 1), sum'[d] =
+ *     fl(fl(decay sum[d]) + e[d]) - float32, two roundings, nothing fused; an id that is new: w' = 1, sum' = e;
+ *   - without a row, or with a row that holds an infinity or a NaN, the old slot is carried over unchanged (a new id: w' = 0,
+ *     sum' = 0);
+ *   - fused[r] = sum' / w' (correctly rounded) and frames_out[r] = w' for the row of such a detection; a row whose detection has
+ *     id < 0, that is not finite or whose slot has w' == 0 is copied to fused[r] bit for bit, with frames_out[r] = 0.
+ * State buffer (frmap_track_fuse_state_bytes(n_streams, max_boxes, dim) bytes, 16-byte aligned, caller-owned; 0 for unsupported
+ * sizes): int32 meta[n_streams][2] = (P, current bank) at byte 0; then, from the next multiple of 16 bytes, int32
+ * ids[n_streams][2][max_boxes], float32 w[n_streams][2][max_boxes] and float32 sum[n_streams][2][max_boxes][dim rounded up to 4]:
+ * two banks of slots per stream - a step reads the current one and writes the other, because a track's slot moves with the
+ * detector's order.  All-zero bytes are a fresh state; zeroing one stream's meta record resets that stream.
+ *   ids, counts : the tracker's int32 [n_streams][max_boxes] and [n_streams] of this step
+ *   emb, fused  : float32 [n_rows][dim], 16-byte aligned, distinct; frames_out: float32 [n_rows]; rows: int32, 8-byte aligned
+ *   decay       : 0 < decay <= 1 (1: the plain mean of the track's embeddings)
+ * Supported: 1 <= max_boxes <= 256, 1 <= dim <= 4096, n_rows <= n_streams * max_boxes; anything else is rejected before any
+ * launch.  counts, ids and rows are DEVICE data this call never sees: the kernel clamps counts (and the state's P), lets a row take
+ * part only if it names a detection of its stream below that count, and never touches another stream's slots; a row that names no
+ * detection is passed through, and of two rows that name the same detection one (either) is pooled and the other passed through - a
+ * caller that builds rows on the host rejects both there (the Python package does).  One workgroup per stream; no atomics. */
+size_t frmap_track_fuse_state_bytes(int n_streams, int max_boxes, int dim);
+int frmap_track_fuse(void* state, const int32_t* ids, const int32_t* counts, const float* emb, const int32_t* rows, int n_rows,
+                     int n_streams, int max_boxes, int dim, float decay, float* fused, float* frames_out, void* stream);
+/* The same step from the same rule compiled for the CPU (HOST pointers, no stream; no GPU needed).  A count outside
+ * [0, max_boxes], a row that names a stream outside [0, n_streams) or a detection outside [0, counts[stream]) and two rows that
+ * name the same detection are rejected, like every other bad argument, before anything is written. */
+int frmap_track_fuse_host(void* state, const int32_t* ids, const int32_t* counts, const float* emb, const int32_t* rows, int n_rows,
+                          int n_streams, int max_boxes, int dim, float decay, float* fused, float* frames_out);
+
 /* ---------------------------------------------------------------------------------------------
  * Conv weight packing.  `w_oihw` = fp32 [Cout][Cin][KH][KW] with the BatchNorm scale already
  * folded in (w * gamma/sqrt(var+eps)); output is the kernel's LDS-image order in `dtype`.
