@@ -7,9 +7,14 @@ OUT=../libfrmap_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-unused-value"
 objs=()
 pids=()
-for f in conv_igemm.hip conv_pp.hip conv_small_cin.hip stem_pool.hip stem_s2d.hip layout_pool.hip transformer.hip head_match.hip resize.hip crop_resize.hip align_crop.hip track.hip track_fuse.hip c_api.cpp model_api.cpp model_families.cpp; do
+for f in conv_igemm.hip conv_pp.hip conv_small_cin.hip stem_pool.hip stem_s2d.hip layout_pool.hip transformer.hip head_match.hip resize.hip crop_resize.hip align_crop.hip track.hip track_fuse.hip c_api.cpp conv_plan.cpp model_api.cpp model_families.cpp; do
   o="build_${f%.*}.o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ frmap_common.h -nt "$o" ] || [ model_api.h -nt "$o" ] || [ resize_coeffs.h -nt "$o" ] || [ frame_records.h -nt "$o" ] || [ track_rule.h -nt "$o" ] || [ track_twin.h -nt "$o" ] || [ track_fuse_rule.h -nt "$o" ] || [ track_fuse_twin.h -nt "$o" ] || [ ../../include/frmap_hip.h -nt "$o" ]; then
+  stale=0
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ]; then stale=1; fi
+  for h in *.h ../../include/frmap_hip.h; do   # any header newer than the object
+    if [ "$h" -nt "$o" ]; then stale=1; fi
+  done
+  if [ "$stale" = 1 ]; then
     echo "hipcc $f"
     rm -f "$o"
     if [[ "$f" == *.cpp ]]; then
@@ -25,7 +30,7 @@ done
 # is a vector-memory access the count does not know about (stale LDS could be read).  Every *_pp_kernel must therefore compile
 # without scratch: check the resource-usage remarks of conv_pp.hip (one extra, parallel, compile; FRMAP_SKIP_SPILL_CHECK=1 skips it).
 spill_pid=""
-if [ "${FRMAP_SKIP_SPILL_CHECK:-0}" != "1" ] && { [ ! -f .pp_spill_ok ] || [ conv_pp.hip -nt .pp_spill_ok ] || [ frmap_common.h -nt .pp_spill_ok ]; }; then
+if [ "${FRMAP_SKIP_SPILL_CHECK:-0}" != "1" ] && { [ ! -f .pp_spill_ok ] || [ conv_pp.hip -nt .pp_spill_ok ] || [ frmap_common.h -nt .pp_spill_ok ] || [ conv_plan.h -nt .pp_spill_ok ]; }; then
   ( $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -c conv_pp.hip -o /dev/null 2> .pp_remarks.txt || exit 1
     python3 - <<'PY' || exit 1
 import re, sys

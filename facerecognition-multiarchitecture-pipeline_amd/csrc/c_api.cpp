@@ -53,6 +53,13 @@ int frmap_batch_invariant() {
   if (env < 0) { const char* e = getenv("FRMAP_BATCH_INVARIANT"); env = (e && atoi(e) != 0) ? 1 : 0; }
   return env;
 }
+int frmap_cu_count() {
+  static const int cus = [] {
+    int dev = 0, v = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }();
+  return cus;
+}
 extern "C" int frmap_set_batch_invariant(int on) { g_invariant = on < 0 ? -1 : (on != 0); return 0; }
 
 extern "C" int frmap_abi_version(void) { return 10; }

@@ -1087,367 +1087,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvParams p) {
                               (const typename TT::elem*)p.res, (typename TT::elem*)p.out, p.relu, lane);
 }
 
-template <typename TT, int CKS>
-static int launch_1x1(const ConvParams& p, hipStream_t st) {
-  auto kern = conv1x1_kernel<TT, CKS>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  int lds = CKS * (256 * 64 + 4096);
-  const int scratch = 4 * 16 * (4 * 64 + 16);
-  if (lds < scratch) lds = scratch;
-  hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-// p.nchunks must hold Cin/32 on entry; picks the stage width and rewrites it in stages
-static int dispatch_1x1(ConvParams& p, int dtype, hipStream_t st) {
-  const int c32 = p.Cin / 32;
-  if (c32 % 4 == 0) {
-    p.nchunks = c32 / 4;
-    return dtype == FRMAP_BF16 ? launch_1x1<BF16, 4>(p, st) : launch_1x1<F16, 4>(p, st);
-  }
-  if (c32 % 2 == 0) {
-    p.nchunks = c32 / 2;
-    return dtype == FRMAP_BF16 ? launch_1x1<BF16, 2>(p, st) : launch_1x1<F16, 2>(p, st);
-  }
-  p.nchunks = c32;
-  return dtype == FRMAP_BF16 ? launch_1x1<BF16, 1>(p, st) : launch_1x1<F16, 1>(p, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------------
-static int halo_rows_bound(int BM, int Ho, int Wo, int Hp, int stride, int KS) {
-  // most output rows / image crossings BM consecutive flattened pixels can touch
-  const int rows = (BM + Wo - 2) / Wo + 1;
-  const int cross = (BM + Ho * Wo - 2) / (Ho * Wo);
-  const int cross_step = Hp - (Ho - 1) * stride;  // padded-row jump from last row of n to first of n+1
-  const int x = cross < rows - 1 ? cross : rows - 1;
-  int gdiff = (rows - 1 - x) * stride + x * (cross_step > stride ? cross_step : stride);
-  return gdiff + KS;
-}
-
-template <typename TT, int BM, int KS, int SWZ, bool POOL = false>
-static int launch(const ConvParams& p, int lds_bytes, hipStream_t st) {
-  auto kern = conv_igemm_kernel<TT, BM, KS, SWZ, POOL>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  const int scratch = 4 * 16 * (4 * 64 + 16);  // epilogue transpose region (4 waves)
-  if (lds_bytes < scratch) lds_bytes = scratch;
-  hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds_bytes, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-// conv3x3_c64_wave_kernel: one 8-wave workgroup per CU (per channel tile), each wave walks 8x8 patches
-template <int NCH, bool POOL>
-static int launch_wave(const ConvParams& p, int dtype, hipStream_t st) {
-  const int ntiles = p.Cout / 64, total = p.N * (p.Hi / 8) * (p.Wi / 8);
-  int cus = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
-  int per = cus / ntiles;
-  if (per < 1) per = 1;
-  if (per > (total + 7) / 8) per = (total + 7) / 8;
-  const int grid = per * ntiles;
-  const int ldsw = NCH * 9 * 4096 + 8 * (10 * 16 * 64);
-  const void* kern = dtype == FRMAP_BF16 ? (const void*)conv3x3_c64_wave_kernel<BF16, NCH, POOL> : (const void*)conv3x3_c64_wave_kernel<F16, NCH, POOL>;
-  if (frmap_big_lds(kern, 160 * 1024)) return -2;
-  if (dtype == FRMAP_BF16)
-    hipLaunchKernelGGL((conv3x3_c64_wave_kernel<BF16, NCH, POOL>), dim3(grid), dim3(512), ldsw, st, p);
-  else
-    hipLaunchKernelGGL((conv3x3_c64_wave_kernel<F16, NCH, POOL>), dim3(grid), dim3(512), ldsw, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-struct DsArgs {  // fused projection shortcut (conv3x3_fast_kernel<TT, true>); in == nullptr: none
-  const void* in;
-  const void* w;
-  int Hi, Wi, Cin, stride;
-};
-
-// does a 3x3 stride-1 layer (with this shortcut) take conv3x3_fast_kernel<TT, true>?
-static bool conv_ds_ok(int B, int Hi, int Wi, int Cin, int Cout, const DsArgs& d);
-
-static int conv_igemm_impl(const void* in, const void* w_packed, const float* shift, const void* residual,
-                           void* out, int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int pad,
-                           int relu, int dtype, const DsArgs& ds, void* stream) {
-  FRMAP_REQUIRE(in && w_packed && shift && out, "conv_igemm: null pointer");
-  FRMAP_REQUIRE(K == 1 || K == 3, "conv_igemm: kernel size %d not supported (1 or 3)", K);
-  FRMAP_REQUIRE(stride == 1 || stride == 2, "conv_igemm: stride %d not supported", stride);
-  FRMAP_REQUIRE((K == 3 && pad == 1) || (K == 1 && pad == 0), "conv_igemm: pad %d with K=%d not supported", pad, K);
-  FRMAP_REQUIRE(Cin > 0 && Cin % 32 == 0, "conv_igemm: Cin=%d must be a multiple of 32", Cin);
-  FRMAP_REQUIRE(Cout > 0 && Cout % 64 == 0, "conv_igemm: Cout=%d must be a multiple of 64", Cout);
-  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm: bad dtype %d", dtype);
-  FRMAP_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "conv_igemm: empty input");
-  const int Ho = (Hi + 2 * pad - K) / stride + 1, Wo = (Wi + 2 * pad - K) / stride + 1;
-  FRMAP_REQUIRE(Ho > 0 && Wo > 0, "conv_igemm: empty output");
-  const long long Mll = (long long)B * Ho * Wo;
-  FRMAP_REQUIRE(Mll < (1ll << 31), "conv_igemm: too many output pixels");
-  FRMAP_REQUIRE(Wi + 2 * pad < 32768 && Hi + 2 * pad < 32768, "conv_igemm: image too large");
-
-  ConvParams p;
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = residual; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
-  p.stride = stride; p.pad = pad; p.relu = relu;
-  p.M = (int)Mll; p.HoWo = Ho * Wo; p.Hp = Hi + 2 * pad; p.Wp = Wi + 2 * pad;
-  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)p.Wo);
-  p.nchunks = Cin / 32;
-  p.ksplit = 1;
-  p.slab = nullptr;
-  p.ds_in = ds.in; p.ds_w = ds.w; p.ds_Hi = ds.Hi; p.ds_Wi = ds.Wi; p.ds_Cin = ds.Cin; p.ds_stride = ds.stride;
-  p.ds_chunks = ds.in ? ds.Cin / 32 : 0;
-  if (ds.in) FRMAP_REQUIRE(conv_ds_ok(B, Hi, Wi, Cin, Cout, ds) && !residual && K == 3 && stride == 1,
-                           "conv_igemm_ds: this shape does not take the fused-shortcut kernel (check frmap_conv_igemm_ds_supported)");
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("FRMAP_CONV_DEBUG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int wbytes = K * K * 4096;
-  const int ntiles = Cout / 64;
-
-  if (K == 1) {
-    const int BM = 256;
-    p.halo_bytes = BM * 64;
-    p.nblocks = ((p.M + BM - 1) / BM) * ntiles;
-    if (p.dbg == 0 && Cin >= 128) {
-      // wide layers: the LDS-DMA ping-pong pipeline when it has enough tiles (conv_pp.hip)
-      const int rc = frmap_conv1x1_pp(in, w_packed, shift, residual, out, B, Hi, Wi, Cin, Cout, stride, relu, dtype, st);
-      if (rc < 0) return rc;
-      if (rc == 1) return 0;
-      return dispatch_1x1(p, dtype, st);  // wide stages pay once there are several of them
-    }
-    const int lds = p.halo_bytes + wbytes;
-    return dtype == FRMAP_BF16 ? launch<BF16, 256, 1, 1>(p, lds, st) : launch<F16, 256, 1, 1>(p, lds, st);
-  }
-  // 3x3 stride 2, even input sizes: the LDS-DMA ping-pong kernel with space-to-depth addressing when it takes the shape
-  if (stride == 2 && p.dbg == 0) {
-    const int rc = frmap_conv3x3s2_pp(in, w_packed, shift, residual, out, B, Hi, Wi, Cin, Cout, relu, dtype, st);
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-  }
-  // 3x3 stride 2 (even input height): row-parity split staging, two workgroups per CU
-  if (stride == 2 && Hi % 2 == 0 && p.dbg == 0) {
-    const int rows = (256 + Wo - 2) / Wo + 1, cross = (256 + Ho * Wo - 2) / (Ho * Wo);
-    const int x = cross < rows - 1 ? cross : rows - 1;
-    const int step = p.Hp / 2 - (Ho - 1);
-    long long hbs = (long long)((rows - 1 - x) + x * (step > 1 ? step : 1) + 2) * p.Wp * 64;
-    hbs = (hbs + 1023) & ~1023ll;
-    if (hbs + 6 * 4096 <= 80 * 1024 && hbs / 64 < 65536) {
-      p.halo_bytes = (int)hbs;
-      p.nblocks = ((p.M + 255) / 256) * ntiles;
-      const int lds = (int)hbs + 6 * 4096;
-      const void* kern = dtype == FRMAP_BF16 ? (const void*)conv3x3s2_split_kernel<BF16> : (const void*)conv3x3s2_split_kernel<F16>;
-      if (frmap_big_lds(kern, 160 * 1024)) return -2;
-      static int s2fast = -1;
-      if (s2fast < 0) { const char* e = getenv("FRMAP_CONV_S2FAST"); s2fast = e ? atoi(e) : 1; }
-      const bool fast2 = s2fast && hbs / 16 <= 12 * 256 && (long long)(256 / (Ho * Wo) + 3) * Hi * Wi * Cin * 2 < (1ll << 31);
-      if (fast2) {
-        const void* k2 = dtype == FRMAP_BF16 ? (const void*)conv3x3s2_fast_kernel<BF16> : (const void*)conv3x3s2_fast_kernel<F16>;
-        if (frmap_big_lds(k2, 160 * 1024)) return -2;
-        if (dtype == FRMAP_BF16)
-          hipLaunchKernelGGL(conv3x3s2_fast_kernel<BF16>, dim3(p.nblocks), dim3(256), lds, st, p);
-        else
-          hipLaunchKernelGGL(conv3x3s2_fast_kernel<F16>, dim3(p.nblocks), dim3(256), lds, st, p);
-      } else if (dtype == FRMAP_BF16)
-        hipLaunchKernelGGL(conv3x3s2_split_kernel<BF16>, dim3(p.nblocks), dim3(256), lds, st, p);
-      else
-        hipLaunchKernelGGL(conv3x3s2_split_kernel<F16>, dim3(p.nblocks), dim3(256), lds, st, p);
-      FRMAP_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  // 3x3 stride 1 with Cin >= 128: the LDS-DMA ping-pong kernel (conv_pp.hip) when it takes the shape
-  if (stride == 1 && p.dbg == 0) {
-    const FrmapPPShortcut sc = {ds.in, ds.w, ds.Hi, ds.Wi, ds.Cin, ds.stride};
-    const int rc = frmap_conv3x3_pp(in, w_packed, shift, residual, out, B, Hi, Wi, Cin, Cout, relu, dtype, st, ds.in ? &sc : nullptr);
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-  }
-  // 3x3: pick the pixel tile so the halo fits; prefer 256 pixels
-  int BM = 256;
-  long long hb = (long long)halo_rows_bound(256, Ho, Wo, p.Hp, stride, 3) * p.Wp * 64;
-  if (hb + wbytes > 160 * 1024) {
-    BM = 128;
-    hb = (long long)halo_rows_bound(128, Ho, Wo, p.Hp, stride, 3) * p.Wp * 64;
-  }
-  hb = (hb + 1023) & ~1023ll;
-  FRMAP_REQUIRE(hb + wbytes <= 160 * 1024, "conv_igemm: input rows too wide for LDS (W=%d)", Wi);
-  FRMAP_REQUIRE(hb / 64 < 65536, "conv_igemm: halo too large");
-  p.halo_bytes = (int)hb;
-  p.nblocks = ((p.M + BM - 1) / BM) * ntiles;
-  const int lds = p.halo_bytes + wbytes;
-  // register-prefetch persistent kernel when the whole halo is <= 10 pieces per thread (and no ablation flag)
-  const bool fastk = BM == 256 && stride == 1 && p.dbg == 0 && hb / 16 <= 10 * 256 && lds <= 80 * 1024 &&
-                     (long long)(256 / (Ho * Wo) + 3) * Hi * Wi * Cin * 2 < (1ll << 31);
-  {
-    static int wres = -1;
-    if (wres < 0) { const char* e = getenv("FRMAP_CONV_WRES"); wres = e ? atoi(e) : 1; }
-    if (wres && !ds.in && stride == 1 && p.dbg == 0 && Cin == 64 && Hi % 8 == 0 && Wi % 8 == 0 &&
-        (long long)Hi * Wi * Cin * 2 < (1ll << 31) && (long long)8 * Wo * Cout * 2 < (1ll << 31)) {
-      return launch_wave<2, false>(p, dtype, st);
-    }
-  }
-  if (ds.in) FRMAP_REQUIRE(fastk, "conv_igemm_ds: layer does not take the register-prefetch kernel");
-  if (fastk) {
-    const int grid = p.nblocks;
-    typedef void (*kern_t)(const ConvParams);
-    static const kern_t kerns[4] = {conv3x3_fast_kernel<BF16, false>, conv3x3_fast_kernel<BF16, true>,
-                                    conv3x3_fast_kernel<F16, false>, conv3x3_fast_kernel<F16, true>};
-    const int ki = (dtype == FRMAP_BF16 ? 0 : 2) + (ds.in ? 1 : 0);
-    if (frmap_big_lds((const void*)kerns[ki], 160 * 1024)) return -2;
-    const int scratch = 4 * 16 * (4 * 64 + 16);
-    const int ldsf = lds < scratch ? scratch : lds;
-    hipLaunchKernelGGL(kerns[ki], dim3(grid), dim3(256), ldsf, st, p);
-    FRMAP_LAUNCH_CHECK();
-    return 0;
-  }
-#define FRMAP_DISPATCH(TT)                                                                   \
-  (BM == 256 ? (stride == 1 ? launch<TT, 256, 3, 1>(p, lds, st) : launch<TT, 256, 3, 2>(p, lds, st)) \
-             : (stride == 1 ? launch<TT, 128, 3, 1>(p, lds, st) : launch<TT, 128, 3, 2>(p, lds, st)))
-  return dtype == FRMAP_BF16 ? FRMAP_DISPATCH(BF16) : FRMAP_DISPATCH(F16);
-#undef FRMAP_DISPATCH
-}
-
-static bool conv_ds_ok(int B, int Hi, int Wi, int Cin, int Cout, const DsArgs& d) {
-  if (!d.in || !d.w || d.Cin <= 0 || d.Cin % 32 || d.Cin / 32 > Cin / 32 || d.stride < 1) return false;
-  if ((d.Hi - 1) / d.stride + 1 != Hi || (d.Wi - 1) / d.stride + 1 != Wi) return false;  // 1x1, pad 0: Ho = (H-1)/s + 1
-  const int Hp = Hi + 2, Wp = Wi + 2;
-  long long hb = (long long)halo_rows_bound(256, Hi, Wi, Hp, 1, 3) * Wp * 64;
-  hb = (hb + 1023) & ~1023ll;
-  const long long lds = hb + 9 * 4096;
-  return hb >= 256 * 64 && hb / 16 <= 10 * 256 && lds <= 80 * 1024 && hb / 64 < 65536 &&
-         (long long)(256 / (Hi * Wi) + 3) * Hi * Wi * Cin * 2 < (1ll << 31) &&
-         (long long)(256 / (Hi * Wi) + 3) * d.Hi * d.Wi * d.Cin * 2 < (1ll << 31);
-}
-
-extern "C" int frmap_conv_igemm(const void* in, const void* w_packed, const float* shift, const void* residual,
-                                void* out, int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int pad,
-                                int relu, int dtype, void* stream) {
-  const DsArgs none = {nullptr, nullptr, 0, 0, 0, 0};
-  return conv_igemm_impl(in, w_packed, shift, residual, out, B, Hi, Wi, Cin, Cout, K, stride, pad, relu, dtype, none, stream);
-}
-
-extern "C" int frmap_conv3x3_pp_layout(int B, int Hi, int Wi, int Cin, int Cout);
-
-// 1 = the fused-shortcut kernel takes the shape.  FRMAP_DS_UNFUSE_SMALL=1 (A/B switch) answers 0 where the
-// second-generation kernel (conv_pp.hip, no shortcut stages yet) would take the plain 3x3 layer and the maps are small
-// (14x14 / 7x7), so the caller runs the shortcut as its own 1x1 launch and feeds it as the residual.
-extern "C" int frmap_conv_igemm_ds_supported(int B, int Hi, int Wi, int Cin, int Cout, int ds_Hi, int ds_Wi, int ds_Cin,
-                                             int ds_stride) {
-  static int on = -1, unfuse_small = 0;
-  if (on < 0) {
-    const char* e = getenv("FRMAP_CONV_DSFUSE");
-    on = e ? atoi(e) : 1;
-    const char* e2 = getenv("FRMAP_DS_UNFUSE_SMALL");
-    unfuse_small = e2 ? atoi(e2) : 0;   // measured a wash end to end (eager +0.2 %, graph replay -3 %): off by default
-  }
-  if (!on || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64) return 0;
-  const DsArgs d = {(const void*)1, (const void*)1, ds_Hi, ds_Wi, ds_Cin, ds_stride};
-  if (!conv_ds_ok(B, Hi, Wi, Cin, Cout, d)) return 0;
-  if (unfuse_small && Hi * Wi <= 256 && frmap_conv3x3_pp_layout(B, Hi, Wi, Cin, Cout) != 0) return 0;
-  return 1;
-}
-
-extern "C" int frmap_conv_igemm_ds(const void* in, const void* w_packed, const float* shift, const void* ds_in,
-                                   const void* ds_w_packed, void* out, int B, int Hi, int Wi, int Cin, int Cout,
-                                   int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride, int relu, int dtype, void* stream) {
-  FRMAP_REQUIRE(ds_in && ds_w_packed, "conv_igemm_ds: null shortcut pointer");
-  const DsArgs d = {ds_in, ds_w_packed, ds_Hi, ds_Wi, ds_Cin, ds_stride};
-  return conv_igemm_impl(in, w_packed, shift, nullptr, out, B, Hi, Wi, Cin, Cout, 3, 1, 1, relu, dtype, d, stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// conv3x3 s1 p1 + shift (+ReLU) + MaxPool2d(2, 2) in one launch (face_models.py:38-40: BaselineNet's
-// `self.pool(F.relu(self.bnK(self.convK(x))))`; :121-141: SiameseNet's conv -> BN -> ReLU -> MaxPool2d(2)).  The conv
-// map never reaches HBM: out = [B][Hi/2][Wi/2][Cout].
-// ------------------------------------------------------------------------------------------------
-static int pool_rows_bound(int BM, int Ho, int Wo, int Hp) {
-  const int nw = BM / 4, Wo2 = Wo / 2, Win = (Ho / 2) * Wo2;
-  const int pairs = (nw + Wo2 - 2) / Wo2 + 1;      // window rows BM/4 consecutive windows can touch
-  const int cross = (nw + Win - 2) / Win;          // image crossings (each adds the Hp - Ho = 2 padding rows)
-  const int x = cross < pairs - 1 ? cross : pairs - 1;
-  return 2 * pairs + 2 * x + 2;
-}
-
-// which fused form takes the shape: 3 = ping-pong kernel (conv_pp.hip), 2 = wave-autonomous kernel (Cin 32 / 64, 8-aligned
-// maps), 1 = the generic kernel, 0 = none (odd sizes, rows too wide for LDS)
-static int pool2_form(int B, int Hi, int Wi, int Cin, int Cout) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Hi % 2 || Wi % 2 || Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64) return 0;
-  if ((long long)B * Hi * Wi >= (1ll << 31) || Wi + 2 >= 32768 || Hi + 2 >= 32768) return 0;
-  static int wres = -1, minc = 128;
-  if (wres < 0) { const char* e = getenv("FRMAP_POOL_WAVE"); wres = e ? atoi(e) : 1; const char* e2 = getenv("FRMAP_PP_POOL_MIN_CIN"); minc = e2 ? atoi(e2) : 128; }
-  if (Cin >= minc && frmap_conv3x3_pp_pool(nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, 0, FRMAP_BF16, nullptr) == 1) return 3;
-  if (wres && (Cin == 32 || Cin == 64) && Hi % 8 == 0 && Wi % 8 == 0 && (long long)Hi * Wi * Cin * 2 < (1ll << 31) &&
-      (long long)4 * (Wi / 2) * Cout * 2 < (1ll << 31))
-    return 2;
-  const long long hb = (long long)pool_rows_bound(128, Hi, Wi, Hi + 2) * (Wi + 2) * 64;
-  return (hb + 9 * 4096 <= 160 * 1024 && hb / 64 < 65536) ? 1 : 0;
-}
-
-// 1 = fusing is expected to win (a fast fused form takes the shape, or the layer is narrow enough that the generic fused
-// kernel beats conv + pool launches); frmap_conv_igemm_pool2 itself runs every shape pool2_form() accepts.
-extern "C" int frmap_conv_igemm_pool2_supported(int B, int Hi, int Wi, int Cin, int Cout) {
-  const int f = pool2_form(B, Hi, Wi, Cin, Cout);
-  return f >= 2 || (f == 1 && Cin <= 96);
-}
-extern "C" int frmap_conv_igemm_pool2_form(int B, int Hi, int Wi, int Cin, int Cout) { return pool2_form(B, Hi, Wi, Cin, Cout); }
-
-extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, const float* shift, void* out, int B, int Hi,
-                                      int Wi, int Cin, int Cout, int relu, int dtype, void* stream) {
-  FRMAP_REQUIRE(in && w_packed && shift && out, "conv_igemm_pool2: null pointer");
-  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm_pool2: bad dtype %d", dtype);
-  FRMAP_REQUIRE(relu == 0 || relu == 1, "conv_igemm_pool2: activation %d does not commute with the max", relu);
-  const int form = pool2_form(B, Hi, Wi, Cin, Cout);
-  FRMAP_REQUIRE(form != 0,
-                "conv_igemm_pool2: shape B=%d %dx%d Cin=%d Cout=%d not taken (even H and W, Cin %% 32 == 0, Cout %% 64 == 0, rows fit LDS)",
-                B, Hi, Wi, Cin, Cout);
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = nullptr; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Hi; p.Wo = Wi; p.Cout = Cout;
-  p.stride = 1; p.pad = 1; p.relu = relu;
-  p.M = B * Hi * Wi; p.HoWo = Hi * Wi; p.Hp = Hi + 2; p.Wp = Wi + 2;
-  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)p.Wo);
-  p.nchunks = Cin / 32; p.ksplit = 1; p.slab = nullptr; p.dbg = 0;
-  p.pool.Wo2 = Wi / 2; p.pool.Win = (Hi / 2) * (Wi / 2);
-  p.pool.dWo2 = frmap_div_make((uint32_t)p.pool.Wo2); p.pool.dWin = frmap_div_make((uint32_t)p.pool.Win);
-  hipStream_t st = (hipStream_t)stream;
-  if (form == 3) {
-    const int rc = frmap_conv3x3_pp_pool(in, w_packed, shift, out, B, Hi, Wi, Cin, Cout, relu, dtype, st);
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-  }
-  // Cin = 32 / 64 on 8-aligned maps: the weights-resident wave-autonomous kernel, pooled epilogue (BaselineNet conv2, conv3)
-  if (form == 2) return Cin == 64 ? launch_wave<2, true>(p, dtype, st) : launch_wave<1, true>(p, dtype, st);
-  const int wbytes = 9 * 4096, ntiles = Cout / 64;
-  int BM = 256;
-  long long hb = (long long)pool_rows_bound(256, Hi, Wi, p.Hp) * p.Wp * 64;
-  if (hb + wbytes > 80 * 1024) {   // two workgroups per CU when the smaller tile allows it
-    BM = 128;
-    hb = (long long)pool_rows_bound(128, Hi, Wi, p.Hp) * p.Wp * 64;
-  }
-  hb = (hb + 1023) & ~1023ll;
-  p.halo_bytes = (int)hb;
-  p.nblocks = ((p.M + BM - 1) / BM) * ntiles;
-  const int lds = p.halo_bytes + wbytes;
-  if (BM == 256) return dtype == FRMAP_BF16 ? launch<BF16, 256, 3, 1, true>(p, lds, st) : launch<F16, 256, 3, 1, true>(p, lds, st);
-  return dtype == FRMAP_BF16 ? launch<BF16, 128, 3, 1, true>(p, lds, st) : launch<F16, 128, 3, 1, true>(p, lds, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Wide nn.Linear (+ folded BatchNorm1d) (+ReLU/GELU) (+residual) on the MFMA kernel above (1x1 over
-// H = W = 1), with split-K when the output has too few tiles to fill the GPU (SiameseNet fc.1:
-// 256 x 18432 -> 1024 is 16 tiles but 576 channel chunks).  Partials: each K-slice workgroup
-// stores its fp32 tile to its own slab (plain coalesced stores, deterministic), a second kernel
-// sums the slabs and applies shift / residual / activation.
-// ------------------------------------------------------------------------------------------------
+// sums the split-K slabs of frmap_linear_mfma and applies shift / residual / activation
 template <typename TT>
 __global__ void splitk_finalize_kernel(const float* __restrict__ slab, int ksplit, const float* __restrict__ shift,
                                        const typename TT::elem* __restrict__ res, typename TT::elem* __restrict__ out,
@@ -1477,17 +1117,153 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ slab, int kspli
   }
 }
 
-static int linear_ksplit(int M, int K, int N) {
-  // (batch-invariant planning: the split - and with it the fp32 summation order - is that of a single row tile for every M)
-  const int tiles = (frmap_batch_invariant() ? 1 : (M + 255) / 256) * (N / 64), nchunks = K / 32;
-  int ks = 384 / (tiles > 0 ? tiles : 1);
-  if (ks > nchunks / 4) ks = nchunks / 4;
-  return ks < 2 ? 1 : ks;
+// ------------------------------------------------------------------------------------------------
+// host side: conv_plan.h decides which kernel runs; this only validates, fills ConvParams and launches
+// ------------------------------------------------------------------------------------------------
+static ConvPlan plan_of(const ConvLayer& L) { return conv_plan(L, conv_tuning(), frmap_cu_count(), frmap_batch_invariant() != 0); }
+ConvPlan frmap_conv_plan(const ConvLayer& L) { return plan_of(L); }
+
+struct ConvPtrs {  // shortcut: ds_in / ds_w (FUSE_SHORTCUT); split-K: slab
+  const void* in; const void* w; const float* shift; const void* res; void* out;
+  const void* ds_in; const void* ds_w; float* slab;
+};
+
+// the kernel arguments of a planned layer (every field, whichever kernel reads it)
+static ConvParams conv_params(const ConvLayer& L, const ConvPlan& q, const ConvPtrs& a, int relu, int dbg) {
+  ConvParams p{};
+  p.in = a.in; p.wpk = a.w; p.shift = a.shift; p.res = a.res; p.out = a.out;
+  p.N = L.B; p.Hi = L.Hi; p.Wi = L.Wi; p.Cin = L.Cin; p.Ho = L.Ho(); p.Wo = L.Wo(); p.Cout = L.Cout;
+  p.stride = L.stride; p.pad = L.pad; p.relu = relu;
+  p.M = L.B * p.Ho * p.Wo; p.HoWo = p.Ho * p.Wo; p.Hp = L.Hi + 2 * L.pad; p.Wp = q.Wp;
+  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
+  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)p.Wo);
+  p.nchunks = L.Cin / 32 / (q.kernel == CK_1X1 ? q.CKS : 1);   // conv1x1_kernel counts stages of CKS chunks
+  p.halo_bytes = q.halo_bytes; p.nblocks = q.nblocks;
+  p.ksplit = q.ksplit; p.slab = a.slab; p.dbg = dbg;
+  if (L.fuse == FUSE_SHORTCUT) {
+    p.ds_in = a.ds_in; p.ds_w = a.ds_w; p.ds_Hi = L.ds_Hi; p.ds_Wi = L.ds_Wi; p.ds_Cin = L.ds_Cin; p.ds_stride = L.ds_stride;
+    p.ds_chunks = L.ds_Cin / 32;
+  }
+  if (L.fuse == FUSE_POOL2) {
+    p.pool.Wo2 = L.Wi / 2; p.pool.Win = (L.Hi / 2) * (L.Wi / 2);
+    p.pool.dWo2 = frmap_div_make((uint32_t)p.pool.Wo2); p.pool.dWin = frmap_div_make((uint32_t)p.pool.Win);
+  }
+  return p;
 }
 
+typedef void (*conv_kern_t)(const ConvParams);
+template <typename TT>
+static conv_kern_t conv_kernel(const ConvPlan& q) {
+  switch (q.kernel) {
+    case CK_IGEMM:
+      if (q.POOL) return q.BM == 256 ? conv_igemm_kernel<TT, 256, 3, 1, true> : conv_igemm_kernel<TT, 128, 3, 1, true>;
+      if (q.KS == 1) return conv_igemm_kernel<TT, 256, 1, 1>;
+      if (q.BM == 256) return q.SWZ == 1 ? conv_igemm_kernel<TT, 256, 3, 1> : conv_igemm_kernel<TT, 256, 3, 2>;
+      return q.SWZ == 1 ? conv_igemm_kernel<TT, 128, 3, 1> : conv_igemm_kernel<TT, 128, 3, 2>;
+    case CK_1X1: return q.CKS == 4 ? conv1x1_kernel<TT, 4> : (q.CKS == 2 ? conv1x1_kernel<TT, 2> : conv1x1_kernel<TT, 1>);
+    case CK_WAVE:
+      if (!q.POOL) return conv3x3_c64_wave_kernel<TT, 2, false>;
+      return q.NCH == 2 ? conv3x3_c64_wave_kernel<TT, 2, true> : conv3x3_c64_wave_kernel<TT, 1, true>;
+    case CK_FAST: return q.DS ? conv3x3_fast_kernel<TT, true> : conv3x3_fast_kernel<TT, false>;
+    case CK_S2_SPLIT: return conv3x3s2_split_kernel<TT>;
+    case CK_S2_FAST: return conv3x3s2_fast_kernel<TT>;
+    default: return nullptr;
+  }
+}
+
+static int conv_launch(const ConvPlan& q, const ConvParams& p, int dtype, hipStream_t st) {
+  const conv_kern_t kern = dtype == FRMAP_BF16 ? conv_kernel<BF16>(q) : conv_kernel<F16>(q);
+  FRMAP_REQUIRE(kern, "conv_igemm: no kernel for plan %d", q.kernel);
+  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
+  hipLaunchKernelGGL(kern, dim3(q.nblocks), dim3(q.kernel == CK_WAVE ? 512 : 256), q.lds_bytes, st, p);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+// launch a planned layer, here or in conv_pp.hip
+static int conv_run(const ConvLayer& L, const ConvPlan& q, const ConvPtrs& a, int relu, int dtype, hipStream_t st) {
+  if (q.kernel >= CK_PP) return frmap_conv_pp_launch(L, q, a.in, a.w, a.shift, a.res, a.out, a.ds_in, a.ds_w, relu, dtype, st);
+  return conv_launch(q, conv_params(L, q, a, relu, L.fuse == FUSE_POOL2 ? 0 : conv_tuning().debug), dtype, st);
+}
+
+static int conv_igemm_impl(const ConvLayer& L, const ConvPtrs& a, int relu, int dtype, void* stream) {
+  FRMAP_REQUIRE(a.in && a.w && a.shift && a.out, "conv_igemm: null pointer");
+  FRMAP_REQUIRE(L.K == 1 || L.K == 3, "conv_igemm: kernel size %d not supported (1 or 3)", L.K);
+  FRMAP_REQUIRE(L.stride == 1 || L.stride == 2, "conv_igemm: stride %d not supported", L.stride);
+  FRMAP_REQUIRE((L.K == 3 && L.pad == 1) || (L.K == 1 && L.pad == 0), "conv_igemm: pad %d with K=%d not supported", L.pad, L.K);
+  FRMAP_REQUIRE(L.Cin > 0 && L.Cin % 32 == 0, "conv_igemm: Cin=%d must be a multiple of 32", L.Cin);
+  FRMAP_REQUIRE(L.Cout > 0 && L.Cout % 64 == 0, "conv_igemm: Cout=%d must be a multiple of 64", L.Cout);
+  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm: bad dtype %d", dtype);
+  FRMAP_REQUIRE(L.B > 0 && L.Hi > 0 && L.Wi > 0, "conv_igemm: empty input");
+  FRMAP_REQUIRE(L.Ho() > 0 && L.Wo() > 0, "conv_igemm: empty output");
+  FRMAP_REQUIRE((long long)L.B * L.Ho() * L.Wo() < (1ll << 31), "conv_igemm: too many output pixels");
+  FRMAP_REQUIRE(L.Wi + 2 * L.pad < 32768 && L.Hi + 2 * L.pad < 32768, "conv_igemm: image too large");
+  const ConvPlan q = plan_of(L);
+  FRMAP_REQUIRE(q.taken(), "%s", q.error);
+  return conv_run(L, q, a, relu, dtype, (hipStream_t)stream);
+}
+
+extern "C" int frmap_conv_igemm(const void* in, const void* w_packed, const float* shift, const void* residual,
+                                void* out, int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int pad,
+                                int relu, int dtype, void* stream) {
+  const ConvLayer L = {B, Hi, Wi, Cin, Cout, K, stride, pad, residual ? FUSE_RESIDUAL : FUSE_NONE, 0, 0, 0, 0};
+  return conv_igemm_impl(L, ConvPtrs{in, w_packed, shift, residual, out, nullptr, nullptr, nullptr}, relu, dtype, stream);
+}
+
+extern "C" int frmap_conv_igemm_ds_supported(int B, int Hi, int Wi, int Cin, int Cout, int ds_Hi, int ds_Wi, int ds_Cin,
+                                             int ds_stride) {
+  const ConvLayer L = {B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_SHORTCUT, ds_Hi, ds_Wi, ds_Cin, ds_stride};
+  return conv_ds_supported(L, conv_tuning(), frmap_batch_invariant() != 0);
+}
+
+extern "C" int frmap_conv_igemm_ds(const void* in, const void* w_packed, const float* shift, const void* ds_in,
+                                   const void* ds_w_packed, void* out, int B, int Hi, int Wi, int Cin, int Cout,
+                                   int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride, int relu, int dtype, void* stream) {
+  FRMAP_REQUIRE(ds_in && ds_w_packed, "conv_igemm_ds: null shortcut pointer");
+  const ConvLayer L = {B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_SHORTCUT, ds_Hi, ds_Wi, ds_Cin, ds_stride};
+  return conv_igemm_impl(L, ConvPtrs{in, w_packed, shift, nullptr, out, ds_in, ds_w_packed, nullptr}, relu, dtype, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// conv3x3 s1 p1 + shift (+ReLU) + MaxPool2d(2, 2) in one launch (face_models.py:38-40: BaselineNet's
+// `self.pool(F.relu(self.bnK(self.convK(x))))`; :121-141: SiameseNet's conv -> BN -> ReLU -> MaxPool2d(2)).  The conv
+// map never reaches HBM: out = [B][Hi/2][Wi/2][Cout].
+// ------------------------------------------------------------------------------------------------
+// which fused form takes the shape: 3 = ping-pong kernel (conv_pp.hip), 2 = wave-autonomous kernel (Cin 32 / 64, 8-aligned
+// maps), 1 = the generic kernel, 0 = none (odd sizes, rows too wide for LDS)
+extern "C" int frmap_conv_igemm_pool2_form(int B, int Hi, int Wi, int Cin, int Cout) {
+  return plan_of(ConvLayer{B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_POOL2, 0, 0, 0, 0}).layout;
+}
+// 1 = fusing is expected to win (a fast fused form takes the shape, or the layer is narrow enough that the generic fused
+// kernel beats conv + pool launches); frmap_conv_igemm_pool2 itself runs every shape the form query accepts.
+extern "C" int frmap_conv_igemm_pool2_supported(int B, int Hi, int Wi, int Cin, int Cout) {
+  const int f = frmap_conv_igemm_pool2_form(B, Hi, Wi, Cin, Cout);
+  return f >= 2 || (f == 1 && Cin <= 96);
+}
+
+extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, const float* shift, void* out, int B, int Hi,
+                                      int Wi, int Cin, int Cout, int relu, int dtype, void* stream) {
+  FRMAP_REQUIRE(in && w_packed && shift && out, "conv_igemm_pool2: null pointer");
+  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm_pool2: bad dtype %d", dtype);
+  FRMAP_REQUIRE(relu == 0 || relu == 1, "conv_igemm_pool2: activation %d does not commute with the max", relu);
+  const ConvLayer L = {B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_POOL2, 0, 0, 0, 0};
+  const ConvPlan q = plan_of(L);
+  FRMAP_REQUIRE(q.taken(),
+                "conv_igemm_pool2: shape B=%d %dx%d Cin=%d Cout=%d not taken (even H and W, Cin %% 32 == 0, Cout %% 64 == 0, rows fit LDS)",
+                B, Hi, Wi, Cin, Cout);
+  return conv_run(L, q, ConvPtrs{in, w_packed, shift, nullptr, out, nullptr, nullptr, nullptr}, relu, dtype, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Wide nn.Linear (+ folded BatchNorm1d) (+ReLU/GELU) (+residual) on the MFMA kernel above (1x1 over
+// H = W = 1), with split-K when the output has too few tiles to fill the GPU (SiameseNet fc.1:
+// 256 x 18432 -> 1024 is 16 tiles but 576 channel chunks).  Partials: each K-slice workgroup
+// stores its fp32 tile to its own slab (plain coalesced stores, deterministic), splitk_finalize_kernel
+// sums the slabs and applies shift / residual / activation.
+// ------------------------------------------------------------------------------------------------
 extern "C" size_t frmap_linear_mfma_workspace_bytes(int M, int K, int N) {
   if (M <= 0 || K <= 0 || N <= 0) return 0;
-  const int ks = linear_ksplit(M, K, N);
+  const int ks = linear_ksplit(M, K, N, frmap_batch_invariant() != 0);
   return ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
 }
 
@@ -1496,37 +1272,22 @@ extern "C" int frmap_linear_mfma(const void* x, const void* w_packed, const floa
   FRMAP_REQUIRE(x && w_packed && shift && out, "linear_mfma: null pointer");
   FRMAP_REQUIRE(M > 0 && K > 0 && K % 32 == 0 && N > 0 && N % 64 == 0, "linear_mfma: need K %% 32 == 0 and N %% 64 == 0 (M=%d K=%d N=%d)", M, K, N);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "linear_mfma: bad dtype");
-  const int ks = linear_ksplit(M, K, N);
+  const int ks = linear_ksplit(M, K, N, frmap_batch_invariant() != 0);
   if (ks == 1) return frmap_conv_igemm(x, w_packed, shift, residual, out, M, 1, 1, K, N, 1, 1, 0, act, dtype, stream);
   FRMAP_REQUIRE(workspace, "linear_mfma: workspace required (frmap_linear_mfma_workspace_bytes)");
-  ConvParams p;
-  p.in = x; p.wpk = w_packed; p.shift = shift; p.res = nullptr; p.out = out;
-  p.N = M; p.Hi = 1; p.Wi = 1; p.Cin = K; p.Ho = 1; p.Wo = 1; p.Cout = N;
-  p.stride = 1; p.pad = 0; p.relu = 0;
-  p.M = M; p.HoWo = 1; p.Hp = 1; p.Wp = 1;
-  p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
-  p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u);
-  p.nchunks = K / 32; p.ksplit = ks; p.slab = (float*)workspace; p.dbg = 0;
-  p.halo_bytes = 256 * 64;
-  p.nblocks = ((M + 255) / 256) * (N / 64) * ks;
+  const ConvLayer L = {M, 1, 1, K, N, 1, 1, 0, FUSE_NONE, 0, 0, 0, 0};
+  const ConvPlan q = plan_1x1(L, ks);   // K slices are counted in kernel stages (up to 128 channels each)
+  if (q.ksplit < 2) return frmap_conv_igemm(x, w_packed, shift, residual, out, M, 1, 1, K, N, 1, 1, 0, act, dtype, stream);
   hipStream_t st = (hipStream_t)stream;
-  // K slices are counted in kernel stages (up to 128 channels each)
-  {
-    const int c32 = K / 32, cks = c32 % 4 == 0 ? 4 : (c32 % 2 == 0 ? 2 : 1);
-    if (p.ksplit > c32 / cks) p.ksplit = c32 / cks;
-    p.nblocks = ((M + 255) / 256) * (N / 64) * p.ksplit;
-  }
-  if (p.ksplit < 2) return frmap_conv_igemm(x, w_packed, shift, residual, out, M, 1, 1, K, N, 1, 1, 0, act, dtype, stream);
-  int rc = dispatch_1x1(p, dtype, st);
+  const int rc = conv_launch(q, conv_params(L, q, ConvPtrs{x, w_packed, shift, nullptr, out, nullptr, nullptr, (float*)workspace}, 0, 0), dtype, st);
   if (rc) return rc;
-  const int ks_used = p.ksplit;
   const size_t MN = (size_t)M * N;
   const int blocks = (int)((MN / 4 + 255) / 256 < 4096 ? (MN / 4 + 255) / 256 : 4096);
   if (dtype == FRMAP_BF16)
-    hipLaunchKernelGGL(splitk_finalize_kernel<BF16>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, ks_used, shift,
+    hipLaunchKernelGGL(splitk_finalize_kernel<BF16>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, q.ksplit, shift,
                        (const __bf16*)residual, (__bf16*)out, MN, N, act);
   else
-    hipLaunchKernelGGL(splitk_finalize_kernel<F16>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, ks_used, shift,
+    hipLaunchKernelGGL(splitk_finalize_kernel<F16>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, q.ksplit, shift,
                        (const _Float16*)residual, (_Float16*)out, MN, N, act);
   FRMAP_LAUNCH_CHECK();
   return 0;

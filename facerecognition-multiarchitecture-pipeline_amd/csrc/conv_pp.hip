@@ -29,9 +29,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <array>
-#include <map>
-#include <mutex>
 #include <utility>
 
 struct PPParams {
@@ -887,370 +884,97 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_pp_kernel(const PPParams p) 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side: conv_plan.h decides layout and instantiation; this fills PPParams and launches
 // ------------------------------------------------------------------------------------------------
-// most halo rows any tile touches: rows of the stacked padded maps (hp rows per image) between the tile's first and last
-// output row, + extra (s1: 3 = one row above, one below; s2 half-resolution maps: 2) - evaluated exactly as the kernels
-// do, over one period of the tile start positions
-static int pp_max_rows(long long M, int tile_px, int howo, int wo, int hp, int extra) {
-  // batch-invariant planning: the bound of an unbounded batch (every phase a tile start can have against the image grid: howo
-  // full tiles), so that whether a layer takes these kernels, and with how many halo pieces, follows from the per-image geometry
-  // alone.  With the actual M a tile that spans several small images (5 x 5 maps: 8 per tile) needed fewer rows at B = 1 than at
-  // B = 8, and a 160 x 160 input's last stride-2 layer ran on this kernel for one face and on another for eight.
-  if (frmap_batch_invariant()) M = (long long)howo * tile_px;
-  // (memoised: the planner runs on every launch, the scan is up to one image's worth of tile starts)
-  static std::mutex mu;
-  static std::map<std::array<long long, 6>, int> memo;
-  const std::array<long long, 6> key = {M, tile_px, howo, wo, hp, extra};
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = memo.find(key);
-    if (it != memo.end()) return it->second;
-  }
-  int best = 0;
-  const long long mtiles = (M + tile_px - 1) / tile_px;
-  const long long lim = mtiles < howo ? mtiles : howo;
-  for (long long mt = 0; mt < lim; ++mt) {
-    const long long m0 = mt * tile_px, mend = (m0 + tile_px < M ? m0 + tile_px : M) - 1;
-    const long long n0 = m0 / howo, n1 = mend / howo;
-    const int oy0 = (int)((m0 - n0 * howo) / wo), oy1 = (int)((mend - n1 * howo) / wo);
-    const int rows = (int)(n1 - n0) * hp + oy1 - oy0 + extra;
-    if (rows > best) best = rows;
-  }
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (memo.size() > 4096) memo.clear();
-    memo[key] = best;
-  }
-  return best;
-}
+// run-time overrides of the planner's tuning (A/B hooks; -1 = not set: environment / heuristic decides)
+extern "C" int frmap_conv_pp_tuning(int enable, int tile_px, int bn) { conv_tuning().set_tuning(enable, tile_px, bn); return 0; }
+extern "C" int frmap_conv_pp_pitch(int v) { conv_tuning().h_pitch = v; return 0; }   // conflict-free halo pitch on (1) / off (0)
+extern "C" int frmap_conv_pp_ds(int v) { conv_tuning().h_ds = v; return 0; }         // fused-shortcut form on (1) / off (0)
+extern "C" int frmap_conv_pp_im(int v) { conv_tuning().h_im = v; return 0; }
+extern "C" int frmap_conv_pp_ri(int v) { conv_tuning().h_ri = v; return 0; }         // fragment reads interleaved with the MFMAs where the layout allows
 
-static int pp_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-// run-time overrides (frmap_conv_pp_tuning): -1 = not set (environment / heuristic decides)
-static int g_pp_on = -1, g_pp_px = -1, g_pp_bn = -1, g_pp_ks = -1, g_pp_ds = -1, g_pp_pitch = -1;
-extern "C" int frmap_conv_pp_pitch(int v) { g_pp_pitch = v; return 0; }   // A/B hook: conflict-free halo pitch on (1) / off (0)
-extern "C" int frmap_conv_pp_ds(int v) { g_pp_ds = v; return 0; }   // A/B hook: fused-shortcut form on (1) / off (0)
-
-extern "C" int frmap_conv_pp_tuning(int enable, int tile_px, int bn) {
-  g_pp_on = enable;
-  g_pp_px = tile_px;
-  g_pp_bn = bn == 1282 ? 128 : bn;   // (1282: the 128-channel tile with the two wave groups splitting K)
-  g_pp_ks = bn == 1282 ? 2 : (bn == 128 || bn == 256 ? 1 : -1);
-  return 0;
-}
-
-static int g_pp_im = -1;   // -1: environment FRMAP_PP_IM (default 0: measured 4-6 % SLOWER than issuing the DMA in the LOAD segments)
-extern "C" int frmap_conv_pp_im(int v) { g_pp_im = v; return 0; }
-static int g_pp_ri = -1;   // -1: environment FRMAP_PP_RI; 1: fragment reads interleaved with the MFMAs (RI = true) where the layout allows
-extern "C" int frmap_conv_pp_ri(int v) { g_pp_ri = v; return 0; }
-static bool pp_ri_on() {
-  static int env = -1;
-  if (env < 0) env = pp_env("FRMAP_PP_RI", 0);
-  return (g_pp_ri >= 0 ? g_pp_ri : env) != 0;
-}
-
-// RI = true launcher (plain layers): slab ring of 5 in the shared-buffer layouts
-template <typename TT, int MI, int WM, int NHP, int KS>
-static int pp_launch_ri(const PPParams& p, hipStream_t st) {
-  auto kern = conv3x3_pp_kernel<TT, MI, WM, NHP, KS, false, false, false, true>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  const int wb = (KS == 2 ? 2 : 8 / WM) * 64 * 64;
-  int lds = KS * (2 * NHP * (8 / KS) * 1024 + (KS == 1 ? 5 : 4) * wb);
-  const int scratch = 8 * 16 * (4 * 64 + 16);
-  const int xch = KS == 2 ? 4 * MI * 4 * 1024 : 0;
-  if (lds < scratch) lds = scratch;
-  if (lds < xch) lds = xch;
-  hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename TT, int MI, int WM, int NHP, int KS, bool DS = false>
-static int pp_launch(const PPParams& p, hipStream_t st) {
-  static int im_env = -1;
-  if (im_env < 0) im_env = pp_env("FRMAP_PP_IM", 0);
-  const bool im = !DS && (g_pp_im >= 0 ? g_pp_im : im_env) != 0;
-  typedef void (*kern_t)(const PPParams);
-  kern_t kern;
-  if constexpr (DS) kern = conv3x3_pp_kernel<TT, MI, WM, NHP, KS, true, false>;
-  else kern = im ? (kern_t)conv3x3_pp_kernel<TT, MI, WM, NHP, KS, false, true> : (kern_t)conv3x3_pp_kernel<TT, MI, WM, NHP, KS, false, false>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  const int wb = (KS == 2 ? 2 : 8 / WM) * 64 * 64;
-  int lds = KS * (2 * NHP * (8 / KS) * 1024 + 4 * wb) + (DS ? ((WM * MI + 7) / 8) * 8192 : 0);
-  const int scratch = 8 * 16 * (4 * 64 + 16);
-  const int xch = KS == 2 ? 4 * MI * 4 * 1024 : 0;
-  if (lds < scratch) lds = scratch;
-  if (lds < xch) lds = xch;
-  hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-// (in == nullptr: plan only - returns the layout the layer would take: 1 = 224 px x 256 ch, 2 = 448 px x 128 ch,
-//  3 = 224 px x 128 ch with the wave groups splitting K, 0 = not taken.)
-// Returns 1 if the layer was launched on conv3x3_pp_kernel, 0 if the shape is not taken (caller falls through to the
-// first-generation kernels), negative on a launch error.
-int frmap_conv3x3_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                     int Wi, int Cin, int Cout, int relu, int dtype, hipStream_t st, const FrmapPPShortcut* ds) {
-  static int on = -1, force_px = 0, force_bn = 0, min_cin = 128, min_tiles = 200;
-  if (on < 0) {
-    min_tiles = pp_env("FRMAP_PP_MIN_TILES", 200);  // fewer tiles than this leave CUs idle: the first-generation kernels' smaller tiles win
-    min_cin = pp_env("FRMAP_PP_MIN_CIN", 128);   // Cin = 64 layers keep the weights-resident wave kernel by default
-    on = pp_env("FRMAP_CONV_PP", 1);
-    force_px = pp_env("FRMAP_PP_TILE_PX", 0);
-    force_bn = pp_env("FRMAP_PP_BN", 0);
-  }
-  constexpr int MI = 7;
-  if (g_pp_on >= 0 ? !g_pp_on : (!on || Cin < min_cin)) return 0;   // (forced on by the hook: every Cin % 32 == 0)
-  if (Cin % 32 || Cin > 1024 || Cout % 128) return 0;
-  const long long Mll = (long long)B * Hi * Wi;
-  if (Mll >= (1ll << 31) || (long long)B * Hi * Wi * Cin * 2 >= (1ll << 46)) return 0;
-  PPParams p;
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = residual; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-  p.M = (int)Mll; p.HoWo = Hi * Wi; p.Hp = Hi + 2; p.Wp = Wi + 2;
-  // LDS pitch of a halo row (pixels).  A 16-pixel MFMA fragment that wraps an output row continues Wp - Wi + 1 pixels
-  // further on; with Wp = Wi (mod 8) that keeps the fragment's 16-byte slots on distinct banks (the swizzle repeats every 8
-  // pixels).  Columns past Wi + 1 are just more zero padding for the DMA.  (A/B: FRMAP_PP_PITCH)
-  static int pitch_env = -1;
-  if (pitch_env < 0) pitch_env = pp_env("FRMAP_PP_PITCH", 0);
-  const bool wide_pitch = (g_pp_pitch >= 0 ? g_pp_pitch : pitch_env) != 0;
-  if (wide_pitch) { while (p.Wp % 8 != Wi % 8) ++p.Wp; }
-  const bool ri_want = pp_ri_on() && ds == nullptr;   // RI form (plain layers): fragment reads under the MFMAs
+// kernel arguments over an M x Cin x Cout problem whose pixels are (Ho x Wo) maps with rows of pitch q.Wp inside (Hp x Wp) padded
+// maps (1x1: the output geometry, no padding); the match GEMM, the shortcut and the pool add their fields
+static PPParams pp_params(const ConvPlan& q, const void* in, const void* w, int N, int Hi, int Wi, int Cin, int Cout, int Ho, int Wo,
+                          int Hp) {
+  PPParams p{};
+  p.in = in; p.wpk = w;
+  p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout;
+  p.M = N * Ho * Wo; p.HoWo = Ho * Wo; p.Hp = Hp; p.Wp = q.Wp;
   p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)Wi);
+  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)Wo); p.dWo2 = frmap_div_make(1u);
   p.nchunks = Cin / 32;
-  p.ds_in = nullptr; p.ds_w = nullptr; p.ds_Hi = p.ds_Wi = p.ds_Cin = p.ds_stride = p.dsc = 0;
-  const bool has_ds = ds != nullptr;
-  if (has_ds) {
-    if (residual || ds->Cin <= 0 || ds->Cin % 32 || ds->stride < 1 || (ds->Hi - 1) / ds->stride + 1 != Hi ||
-        (ds->Wi - 1) / ds->stride + 1 != Wi || (long long)B * ds->Hi * ds->Wi * ds->Cin * 2 >= (1ll << 46))
-      return 0;
-    // A/B switch FRMAP_CONV_PP_DS (on): with the last main chunk peeled (no shortcut DMA in the other chunks) the fused form
-    // runs 64.8 / 52.9 us at 28x28 / 14x14 (256 faces) against the first generation's 72.4 / 68.4
-    static int ds_on = -1;
-    if (ds_on < 0) ds_on = pp_env("FRMAP_CONV_PP_DS", 1);
-    if (g_pp_ds >= 0) ds_on = g_pp_ds;
-    if (!ds_on && g_pp_on < 0) return 0;
-    p.ds_in = ds->in; p.ds_w = ds->w; p.ds_Hi = ds->Hi; p.ds_Wi = ds->Wi; p.ds_Cin = ds->Cin; p.ds_stride = ds->stride;
-    p.dsc = ds->Cin / 32;
-  }
-  // A layout = (pixels a tile can hold, channel tile, split-K groups).  Pixels per tile: whole images when they fit
-  // (7x7: 4 per 224, 14x14: 1), else whole rows - a divisor of the image height when one is within 1/8 of the capacity
-  // (28 rows, capacity 16 rows: 14), so tiles do not straddle images.  Returns the halo pieces (KB / waves) needed, 0 = no fit.
-  auto plan = [&](int cap, int bn, int ks, int& tile_px, int& mtiles, int& ntiles) -> int {
-    if (Wi > cap || Cout % bn || (ks == 2 && (Cin / 32) % 2)) return 0;
-    if (Hi * Wi <= cap) tile_px = (cap / (Hi * Wi)) * Hi * Wi;
-    else {
-      int rows = cap / Wi;
-      for (int r = rows; r * 8 >= rows * 7 && r >= 1; --r)
-        if (Hi % r == 0) { rows = r; break; }
-      tile_px = rows * Wi;
-    }
-    if (force_px > 0 && force_px <= cap) tile_px = force_px;
-    if (g_pp_px > 0 && g_pp_px <= cap) tile_px = g_pp_px;
-    mtiles = (int)((Mll + tile_px - 1) / tile_px);
-    ntiles = Cout / bn;
-    const long long hbytes = (long long)pp_max_rows(Mll, tile_px, Hi * Wi, Wi, p.Hp, 3) * p.Wp * 64;
-    if (hbytes / 64 >= 65536) return 0;
-    const int per = (8 / ks) * 1024;                           // bytes one "piece per wave" adds to the image
-    const int nhp = (int)((hbytes + per - 1) / per);
-    return nhp <= (ks == 2 ? 6 : 5) ? nhp : 0;
-  };
-  // candidates: 224 px x 256 ch; 448 px x 128 ch; split-K 224 px x 128 ch (twice the tiles of either)
-  int bn_pref = Cout % 256 == 0 ? 256 : 128;
-  if (force_bn == 128 || force_bn == 256) bn_pref = (force_bn == 256 && Cout % 256) ? 128 : force_bn;
-  if (g_pp_bn == 128 || g_pp_bn == 256) bn_pref = (g_pp_bn == 256 && Cout % 256) ? 128 : g_pp_bn;
-  int tpx = 0, mtl = 0, ntl = 0, ks = 1, bn = bn_pref;
-  int nhp = plan(bn == 256 ? 2 * MI * 16 : 4 * MI * 16, bn, 1, tpx, mtl, ntl);
-  const bool inv = frmap_batch_invariant() != 0;   // layout from the per-image geometry alone: no tile-count rules, no split-K
-  const bool want_ks2 = !has_ds && !inv && (g_pp_ks == 2 || (g_pp_ks < 0 && (!nhp || (long long)mtl * ntl < min_tiles)));
-  if (want_ks2 && g_pp_ks != 1) {
-    int t2 = 0, m2 = 0, n2 = 0;
-    const int nhp2 = plan(2 * MI * 16, 128, 2, t2, m2, n2);
-    if (nhp2 && (g_pp_ks == 2 || !nhp || (long long)m2 * n2 > (long long)mtl * ntl)) {
-      nhp = nhp2; tpx = t2; mtl = m2; ntl = n2; ks = 2; bn = 128;
-    }
-  }
-  if (!nhp) return 0;
-  p.tile_px = tpx; p.mtiles = mtl; p.ntiles = ntl;
-  if (!inv && g_pp_on < 0 && (long long)mtl * ntl < min_tiles / 2) return 0;   // too few tiles even with split-K: the smaller first-generation tiles win
-  if (!inv && has_ds && (long long)mtl * ntl < min_tiles && g_pp_on < 0) return 0;   // (no split-K form of the shortcut kernel)
-  if (!in) return ks == 2 ? 3 : (bn == 256 ? 1 : 2);                   // plan-only query (frmap_conv3x3_pp_layout)
-  int rc;
-  if (has_ds) {   // pixel-split layouts only; the 448-pixel layout needs the 40 KB halo buffers to hold a gather image
-#define PPD_GO(TT)                                                                                                       \
-  (bn == 256 ? (nhp <= 3 ? pp_launch<TT, MI, 2, 3, 1, true>(p, st) : pp_launch<TT, MI, 2, 5, 1, true>(p, st))              \
-             : pp_launch<TT, MI, 4, 5, 1, true>(p, st))
-    rc = dtype == FRMAP_BF16 ? PPD_GO(BF16) : PPD_GO(F16);
-#undef PPD_GO
-    return rc ? rc : 1;
-  }
-  // (the RI form of the split-K layout with 6 halo pieces needs 258 VGPRs: it would spill inside the DMA-counted loop, so that
-  //  one layout keeps the burst-read form; csrc/build.sh rejects any *_pp_kernel with scratch)
-  if (ri_want && !(ks == 2 && nhp > 4)) {
-#define PPR_GO(TT)                                                                                              \
-  (ks == 2 ? pp_launch_ri<TT, MI, 2, 4, 2>(p, st)                                                               \
-   : bn == 256 ? (nhp <= 3 ? pp_launch_ri<TT, MI, 2, 3, 1>(p, st) : pp_launch_ri<TT, MI, 2, 5, 1>(p, st))        \
-               : (nhp <= 3 ? pp_launch_ri<TT, MI, 4, 3, 1>(p, st) : pp_launch_ri<TT, MI, 4, 5, 1>(p, st)))
-    rc = dtype == FRMAP_BF16 ? PPR_GO(BF16) : PPR_GO(F16);
-#undef PPR_GO
-    return rc ? rc : 1;
-  }
-#define PP_GO(TT)                                                                                               \
-  (ks == 2 ? (nhp <= 4 ? pp_launch<TT, MI, 2, 4, 2>(p, st) : pp_launch<TT, MI, 2, 6, 2>(p, st))                  \
-   : bn == 256 ? (nhp <= 3 ? pp_launch<TT, MI, 2, 3, 1>(p, st) : pp_launch<TT, MI, 2, 5, 1>(p, st))              \
-               : (nhp <= 3 ? pp_launch<TT, MI, 4, 3, 1>(p, st) : pp_launch<TT, MI, 4, 5, 1>(p, st)))
-  rc = dtype == FRMAP_BF16 ? PP_GO(BF16) : PP_GO(F16);
-#undef PP_GO
-  return rc ? rc : 1;
+  p.tile_px = q.tile_px; p.mtiles = q.mtiles; p.ntiles = q.ntiles;
+  return p;
 }
 
-// ------------------------------------------------------------------------------------------------
-// conv3x3 s1 p1 + shift (+ReLU) + MaxPool2d(2, 2) on the ping-pong kernel (PL = true).  Takes maps whose row pairs tile a
-// wave's 112-pixel slice (Wi in {2, 4, 8, 14, 28, 56}, even Hi), Cin % 32 == 0, Cout % 128 == 0; tiles are WM whole slices.
-// 1 = launched, 0 = shape not taken, < 0 = error; in == nullptr: plan only.
-// ------------------------------------------------------------------------------------------------
-template <typename TT, int WM, int NHP>
-static int pp_launch_pool(const PPParams& p, hipStream_t st) {
-  auto kern = conv3x3_pp_kernel<TT, 7, WM, NHP, 1, false, false, true>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  const int wb = (8 / WM) * 64 * 64;
-  int lds = 2 * NHP * 8 * 1024 + 4 * wb;
-  const int scratch = 8 * 16 * (4 * 64 + 16);
-  if (lds < scratch) lds = scratch;
-  hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
+template <typename TT, int WM, int NHP, int KS>
+static const void* pp_kernel_3x3(const ConvPlan& q) {
+  if constexpr (KS == 1 && !(WM == 4 && NHP == 3)) {
+    if (q.DS) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, true, false>;
+  }
+  if constexpr (KS == 1) {
+    if (q.PL) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false, true>;
+  }
+  if constexpr (NHP != 6) {
+    if (q.RI) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false, false, true>;
+  }
+  return q.IM ? (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, true> : (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false>;
+}
+// the instantiation of a plan (conv layers; the match GEMM's modes have their own argument types: pp_match_launch)
+template <typename TT>
+static const void* pp_kernel(const ConvPlan& q) {
+  const int key = q.WM * 100 + q.NHP * 10 + q.KS;
+  switch (q.kernel) {
+    case CK_PP:
+      switch (key) {
+        case 231: return pp_kernel_3x3<TT, 2, 3, 1>(q);
+        case 251: return pp_kernel_3x3<TT, 2, 5, 1>(q);
+        case 431: return pp_kernel_3x3<TT, 4, 3, 1>(q);
+        case 451: return pp_kernel_3x3<TT, 4, 5, 1>(q);
+        case 242: return pp_kernel_3x3<TT, 2, 4, 2>(q);
+        case 262: return pp_kernel_3x3<TT, 2, 6, 2>(q);
+      }
+      return nullptr;
+    case CK_PP_S2:
+      switch (key) {
+        case 211: return (const void*)conv3x3s2_pp_kernel<TT, 7, 2, 1>;
+        case 221: return (const void*)conv3x3s2_pp_kernel<TT, 7, 2, 2>;
+        case 411: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 1>;
+        case 421: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 2>;
+        case 441: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 4>;
+      }
+      return nullptr;
+    case CK_PP_1X1:
+      if (q.KS == 2) return (const void*)conv1x1_pp_kernel<TT, 7, 2, 2>;
+      return q.WM == 4 ? (const void*)conv1x1_pp_kernel<TT, 7, 4, 1> : (const void*)conv1x1_pp_kernel<TT, 7, 2, 1>;
+  }
+  return nullptr;
+}
+
+template <typename P>
+static int pp_launch(const void* kern, const ConvPlan& q, int lds, const P& p, hipStream_t st) {
+  FRMAP_REQUIRE(kern, "conv_pp: no kernel for plan %d (WM %d, NHP %d, KS %d)", q.kernel, q.WM, q.NHP, q.KS);
+  if (frmap_big_lds(kern, 160 * 1024)) return -2;
+  void* args[] = {(void*)&p};
+  (void)hipLaunchKernel(kern, dim3(q.mtiles * q.ntiles), dim3(512), args, lds, st);
   FRMAP_LAUNCH_CHECK();
   return 0;
 }
 
-int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shift, void* out, int B, int Hi, int Wi, int Cin,
-                          int Cout, int relu, int dtype, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_CONV_PP_POOL", 1);
-  if (g_pp_on >= 0 ? !g_pp_on : !on) return 0;
-  if (Hi % 2 || Wi % 2 || 112 % (2 * Wi) || Cin % 32 || Cin > 1024 || Cout % 128) return 0;
-  const long long Mll = (long long)B * Hi * Wi;
-  if (Mll >= (1ll << 31) || (long long)B * Hi * Wi * Cin * 2 >= (1ll << 46)) return 0;
-  PPParams p;
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = nullptr; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-  p.M = (int)Mll; p.HoWo = Hi * Wi; p.Hp = Hi + 2; p.Wp = Wi + 2;
-  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)Wi);
-  p.nchunks = Cin / 32;
-  p.ds_in = nullptr; p.ds_w = nullptr; p.ds_Hi = p.ds_Wi = p.ds_Cin = p.ds_stride = p.dsc = 0;
-  p.Wo2 = Wi / 2; p.dWo2 = frmap_div_make((uint32_t)p.Wo2);
-  int bn = Cout % 256 == 0 ? 256 : 128;
-  if (g_pp_bn == 128 || g_pp_bn == 256) bn = (g_pp_bn == 256 && Cout % 256) ? 128 : g_pp_bn;
-  int nhp = 0;
-  for (int attempt = 0; attempt < 2 && !nhp; ++attempt) {
-    const int tile_px = (bn == 256 ? 2 : 4) * 112;
-    const long long hbytes = (long long)pp_max_rows(Mll, tile_px, Hi * Wi, Wi, p.Hp, 3) * p.Wp * 64;
-    const int n = (int)((hbytes + 8191) / 8192);
-    if (hbytes / 64 < 65536 && n <= 5) { nhp = n; p.tile_px = tile_px; }
-    else bn = bn == 256 ? 128 : 256;   // the other layout (a wider tile has fewer halo rows per pixel, a narrower one fewer rows)
-    if (!nhp && Cout % bn) break;
+int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, const void* w_packed, const float* shift,
+                         const void* residual, void* out, const void* ds_in, const void* ds_w, int relu, int dtype, hipStream_t st) {
+  // 3x3 stride 1: (Hi + 2) x Wp padded maps; stride 2: half-resolution maps with a top / left border; 1x1: the output geometry
+  const int Ho = L.Ho(), Wo = L.Wo(), Hp = q.kernel == CK_PP ? L.Hi + 2 : (q.kernel == CK_PP_S2 ? Ho + 1 : Ho);
+  PPParams p = pp_params(q, in, w_packed, L.B, L.Hi, L.Wi, L.Cin, L.Cout, Ho, Wo, Hp);
+  p.shift = shift; p.res = residual; p.out = out; p.relu = relu;
+  if (q.kernel == CK_PP_1X1) p.ds_stride = L.stride;
+  if (q.DS) {
+    p.ds_in = ds_in; p.ds_w = ds_w; p.ds_Hi = L.ds_Hi; p.ds_Wi = L.ds_Wi; p.ds_Cin = L.ds_Cin; p.ds_stride = L.ds_stride;
+    p.dsc = L.ds_Cin / 32;
   }
-  if (!nhp) return 0;
-  p.mtiles = (int)((Mll + p.tile_px - 1) / p.tile_px); p.ntiles = Cout / bn;
-  if (!in) return 1;
-  int rc;
-#define PPP_GO(TT)                                                                                      \
-  (bn == 256 ? (nhp <= 3 ? pp_launch_pool<TT, 2, 3>(p, st) : pp_launch_pool<TT, 2, 5>(p, st))           \
-             : (nhp <= 3 ? pp_launch_pool<TT, 4, 3>(p, st) : pp_launch_pool<TT, 4, 5>(p, st)))
-  rc = dtype == FRMAP_BF16 ? PPP_GO(BF16) : PPP_GO(F16);
-#undef PPP_GO
-  return rc ? rc : 1;
-}
-
-// ------------------------------------------------------------------------------------------------
-// 1x1 conv / Linear launcher (conv1x1_pp_kernel): 1 = launched, 0 = shape not taken, < 0 = error; in == nullptr: plan only
-// (returns the layout: 1 = 224 px x 256 ch, 2 = 448 px x 128 ch, 3 = 224 px x 128 ch split-K)
-// ------------------------------------------------------------------------------------------------
-template <typename TT, int WM, int KS, int MM = MATCH_NONE>
-static int pp1_launch(const typename PPArg<MM>::type& p, hipStream_t st) {
-  constexpr int MI = 7;
-  auto kern = conv1x1_pp_kernel<TT, MI, WM, KS, MM>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  constexpr int CAP = (KS == 2 ? 2 : WM) * MI * 16, GW = 8 / KS, NGP = (CAP / 16 + GW - 1) / GW;
-  const int wb = (KS == 2 ? 2 : 8 / WM) * 64 * 64;
-  int lds = KS * (3 * NGP * GW * 1024 + 4 * wb);
-  const int scratch = 8 * 16 * (4 * 64 + 16);
-  const int xch = KS == 2 ? 4 * MI * 4 * 1024 : 0;
-  if (lds < scratch) lds = scratch;
-  if (lds < xch) lds = xch;
-  if (MM == MATCH_HIST && lds < VERIFY_LDS_GEMM) lds = VERIFY_LDS_GEMM;
-  if (MM == MATCH_JOIN && lds < 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES)) lds = 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES);   // queues | output buffers
-  hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                     int Wi, int Cin, int Cout, int stride, int relu, int dtype, hipStream_t st) {
-  static int on = -1, min_tiles = 200;
-  if (on < 0) {
-    on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_CONV_PP_1X1", 1);
-    min_tiles = pp_env("FRMAP_PP_MIN_TILES", 200);
-  }
-  if (g_pp_on >= 0 ? !g_pp_on : !on) return 0;
-  if (frmap_batch_invariant() && g_pp_on < 0) return 0;   // (its layout is a rounds x time estimate over the tile count: the first-generation kernel's is not)
-  if (Cin % 32 || Cin > 16384 || Cout % 128 || stride < 1) return 0;
-  const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-  const long long Mll = (long long)B * Ho * Wo;
-  if (Mll >= (1ll << 31) || (long long)B * Hi * Wi * Cin * 2 >= (1ll << 46)) return 0;
-  PPParams p;
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = residual; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-  p.M = (int)Mll; p.HoWo = Ho * Wo; p.Hp = Ho; p.Wp = Wo;          // (output geometry: the kernel needs no padded map)
-  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)Wo);
-  p.nchunks = Cin / 32;
-  p.ds_in = nullptr; p.ds_w = nullptr; p.ds_Hi = p.ds_Wi = p.ds_Cin = p.dsc = 0; p.ds_stride = stride;
-  p.Wo2 = 0; p.dWo2 = frmap_div_make(1u);
-  // layouts: 1 = 224 px x 256 ch, 2 = 448 px x 128 ch, 3 = split-K 224 px x 128 ch.  One workgroup per CU, so what counts is
-  // ROUNDS x time per tile: est = ceil(tiles / CUs) x (k-steps per group x 0.6 us + 7.5 us of prologue and epilogue); 280 tiles
-  // on 256 CUs are two rounds.  The first-generation kernel (small tiles, two workgroups per CU) is modelled at 470 TFLOP/s.
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  auto est_us = [&](int lay) -> double {
-    if (lay == 1 && Cout % 256) return 1e30;
-    if (lay == 3 && p.nchunks % 2) return 1e30;
-    const int px = lay == 2 ? 448 : 224, bn = lay == 1 ? 256 : 128;
-    const long long tiles = ((Mll + px - 1) / px) * (Cout / bn);
-    const long long rounds = (tiles + ncu - 1) / ncu;
-    return (double)rounds * ((lay == 3 ? p.nchunks / 2 : p.nchunks) * 0.6 + 7.5);
-  };
-  int layout = 0;
-  double best = 1e30;
-  for (int lay = 1; lay <= 3; ++lay) {
-    if (g_pp_bn == 256 && g_pp_ks != 2 && lay != 1 && Cout % 256 == 0) continue;   // forced by the tuning hook
-    if (g_pp_bn == 128 && g_pp_ks == 1 && lay != 2) continue;
-    if (g_pp_ks == 2 && lay != 3 && p.nchunks % 2 == 0) continue;
-    const double e = est_us(lay);
-    if (e < best) { best = e; layout = lay; }
-  }
-  if (!layout || best >= 1e30) return 0;
-  if (g_pp_on < 0) {
-    const double gen1_us = 2.0 * (double)Mll * Cin * Cout / 470e6;
-    if (best > 0.9 * gen1_us || min_tiles < 0) return 0;   // (a clear win only: AttentionNet's 640-channel q/k/v conv is 140 tiles - 29 us here, 19 there)
-  }
-  p.tile_px = layout == 2 ? 448 : 224;
-  p.mtiles = (int)((Mll + p.tile_px - 1) / p.tile_px);
-  p.ntiles = Cout / (layout == 1 ? 256 : 128);
-  if (!in) return layout;
-  int rc;
-#define PP1_GO(TT) (layout == 1 ? pp1_launch<TT, 2, 1>(p, st) : layout == 2 ? pp1_launch<TT, 4, 1>(p, st) : pp1_launch<TT, 2, 2>(p, st))
-  rc = dtype == FRMAP_BF16 ? PP1_GO(BF16) : PP1_GO(F16);
-#undef PP1_GO
-  return rc ? rc : 1;
+  if (q.PL) { p.Wo2 = L.Wi / 2; p.dWo2 = frmap_div_make((uint32_t)p.Wo2); }
+  return pp_launch(dtype == FRMAP_BF16 ? pp_kernel<BF16>(q) : pp_kernel<F16>(q), q, q.lds_bytes, p, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1261,143 +985,71 @@ int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, c
 // the FrmapVerifyGemm; MATCH_JOIN: `out` = the FrmapRadiusGemm.  1 = launched, 0 = shape not taken, < 0 = error; probes3 == nullptr:
 // plan only.
 // ------------------------------------------------------------------------------------------------
+template <int MM>
+static int pp_match_launch(const ConvPlan& q, const typename PPArg<MM>::type& p, hipStream_t st) {
+  int lds = q.lds_bytes;   // the mode's queues / output buffers overlay the GEMM's buffers
+  if (MM == MATCH_HIST && lds < VERIFY_LDS_GEMM) lds = VERIFY_LDS_GEMM;
+  if (MM == MATCH_JOIN && lds < 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES)) lds = 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES);
+  const void* kern = q.WM == 4 ? (const void*)conv1x1_pp_kernel<F16, 7, 4, 1, MM> : (const void*)conv1x1_pp_kernel<F16, 7, 2, 1, MM>;
+  return pp_launch(kern, q, lds, p, st);
+}
+
 int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
                      int P, int G, int D, hipStream_t st) {
   const int K3 = 3 * D, Gpad = (G + 255) / 256 * 256;
   const FrmapVerifyGemm* v = mode == MATCH_HIST ? (const FrmapVerifyGemm*)out : nullptr;
   if (K3 % 32 || K3 > 16384 || P <= 0 || G <= 0 || (v && (v->T < 1 || v->T > VERIFY_MAX_T))) return 0;
   if (!probes3) return 1;
-  PPHistParams p;   // (MATCH_TOP1 / MATCH_TOPR launch its PPParams part)
-  memset(&p, 0, sizeof(p));
-  p.in = probes3; p.wpk = gallery_packed;
-  p.N = P; p.Hi = 1; p.Wi = 1; p.Cin = K3; p.Cout = Gpad;
-  p.M = P; p.HoWo = 1; p.Hp = 1; p.Wp = 1;
-  p.magic_Wp = frmap_magic(1u); p.magic_Hp = frmap_magic(1u);
-  p.dHoWo = frmap_div_make(1u); p.dWo = frmap_div_make(1u); p.dWo2 = frmap_div_make(1u);
-  p.nchunks = K3 / 32; p.ds_stride = 1;
+  const ConvPlan q = match_gemm_plan(P, Gpad);
+  PPHistParams p{};   // (MATCH_TOP1 / MATCH_TOPR launch its PPParams part)
+  static_cast<PPParams&>(p) = pp_params(q, probes3, gallery_packed, P, 1, 1, K3, Gpad, 1, 1, 1);
+  p.ds_stride = 1;
   p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_G = G; p.m_D = D;
-  if (v) {
-    p.h_A = v->A; p.h_B = v->B; p.h_lab_a = v->lab_a; p.h_lab_b = v->lab_b; p.h_tab = v->tab; p.h_hist = v->hist;
-    p.h_rescored = v->rescored; p.h_row0 = v->row0; p.h_T = v->T;
-  } else {
-    p.m_records = out;
-  }
-  // 224 probes x 256 gallery rows per tile, or 448 x 128 when that fills the CUs better (one round either way at 1024 probes)
-  const long long t1 = ((P + 223) / 224) * (long long)(Gpad / 256), t2 = ((P + 447) / 448) * (long long)(Gpad / 128);
-  const long long r1 = (t1 + 255) / 256, r2 = (t2 + 255) / 256;   // rounds on 256 CUs (a tile costs the same in both layouts)
-  const bool wide = r2 < r1 || (r2 == r1 && t2 > t1);             // same rounds: the layout that occupies more CUs
-  p.tile_px = wide ? 448 : 224;
-  p.mtiles = (P + p.tile_px - 1) / p.tile_px;
-  p.ntiles = Gpad / (wide ? 128 : 256);
+  int rc;
   if (mode == MATCH_JOIN) {
     const FrmapRadiusGemm* r = (const FrmapRadiusGemm*)out;
-    PPJoinParams pj;
-    memset(&pj, 0, sizeof(pj));
+    PPJoinParams pj{};
     static_cast<PPParams&>(pj) = p;
-    pj.m_records = nullptr;
     pj.j_A = r->A; pj.j_B = r->B; pj.j_lab_a = r->lab_a; pj.j_lab_b = r->lab_b; pj.j_out = r->out; pj.j_rescored = r->rescored;
     pj.j_hi = r->hi; pj.j_row0 = r->row0; pj.j_filter = r->filter;
-    const int rcj = wide ? pp1_launch<F16, 4, 1, MATCH_JOIN>(pj, st) : pp1_launch<F16, 2, 1, MATCH_JOIN>(pj, st);
-    return rcj ? rcj : 1;
+    rc = pp_match_launch<MATCH_JOIN>(q, pj, st);
+  } else if (v) {
+    p.h_A = v->A; p.h_B = v->B; p.h_lab_a = v->lab_a; p.h_lab_b = v->lab_b; p.h_tab = v->tab; p.h_hist = v->hist;
+    p.h_rescored = v->rescored; p.h_row0 = v->row0; p.h_T = v->T;
+    rc = pp_match_launch<MATCH_HIST>(q, p, st);
+  } else {
+    p.m_records = out;
+    rc = mode == MATCH_TOPR ? pp_match_launch<MATCH_TOPR>(q, static_cast<const PPParams&>(p), st)
+                            : pp_match_launch<MATCH_TOP1>(q, static_cast<const PPParams&>(p), st);
   }
-  const int rc = mode == MATCH_TOPR ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOPR>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOPR>(p, st))
-                 : mode == MATCH_TOP1 ? (wide ? pp1_launch<F16, 4, 1, MATCH_TOP1>(p, st) : pp1_launch<F16, 2, 1, MATCH_TOP1>(p, st))
-                                      : (wide ? pp1_launch<F16, 4, 1, MATCH_HIST>(p, st) : pp1_launch<F16, 2, 1, MATCH_HIST>(p, st));
   return rc ? rc : 1;
 }
+
+// ------------------------------------------------------------------------------------------------
+// layout queries: what the planner's candidate answers for the shape (1 = 224 px x 256 ch, 2 = 448 px x 128 ch, 3 = 224 px x
+// 128 ch with the wave groups splitting K; pooled: 1 = taken; 0 = not taken)
+// ------------------------------------------------------------------------------------------------
+static bool pp_query_ok(int B, int Hi, int Wi, int Cin, int Cout) { return B > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0; }
+static bool pp_inv() { return frmap_batch_invariant() != 0; }
 
 extern "C" int frmap_conv1x1_pp_layout(int B, int Hi, int Wi, int Cin, int Cout, int stride) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return frmap_conv1x1_pp(nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, stride, 0, FRMAP_BF16, nullptr);
+  if (!pp_query_ok(B, Hi, Wi, Cin, Cout)) return 0;
+  return plan_pp_1x1(ConvLayer{B, Hi, Wi, Cin, Cout, 1, stride, 0, FUSE_NONE, 0, 0, 0, 0}, conv_tuning(), frmap_cu_count(), pp_inv()).layout;
 }
-
 extern "C" int frmap_conv3x3_pp_pool_layout(int B, int Hi, int Wi, int Cin, int Cout) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return frmap_conv3x3_pp_pool(nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, 0, FRMAP_BF16, nullptr);
+  if (!pp_query_ok(B, Hi, Wi, Cin, Cout)) return 0;
+  return plan_pp_pool(ConvLayer{B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_POOL2, 0, 0, 0, 0}, conv_tuning(), pp_inv()).taken();
 }
-
 extern "C" int frmap_conv3x3_pp_layout(int B, int Hi, int Wi, int Cin, int Cout) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return frmap_conv3x3_pp(nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, 0, FRMAP_BF16, nullptr, nullptr);
+  if (!pp_query_ok(B, Hi, Wi, Cin, Cout)) return 0;
+  return plan_pp_3x3(ConvLayer{B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_NONE, 0, 0, 0, 0}, conv_tuning(), pp_inv()).layout;
 }
-
 // the same question for the layer with a fused 1x1 stride-s projection shortcut (frmap_conv_igemm_ds)
 extern "C" int frmap_conv3x3_pp_ds_layout(int B, int Hi, int Wi, int Cin, int Cout, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  const FrmapPPShortcut d = {nullptr, nullptr, ds_Hi, ds_Wi, ds_Cin, ds_stride};
-  return frmap_conv3x3_pp(nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, 0, FRMAP_BF16, nullptr, &d);
+  if (!pp_query_ok(B, Hi, Wi, Cin, Cout)) return 0;
+  return plan_pp_3x3(ConvLayer{B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_SHORTCUT, ds_Hi, ds_Wi, ds_Cin, ds_stride}, conv_tuning(), pp_inv()).layout;
 }
-
-// ------------------------------------------------------------------------------------------------
-// stride-2 launcher (conv3x3s2_pp_kernel)
-// ------------------------------------------------------------------------------------------------
-template <typename TT, int MI, int WM, int NHP2>
-static int pp2_launch(const PPParams& p, hipStream_t st) {
-  auto kern = conv3x3s2_pp_kernel<TT, MI, WM, NHP2>;
-  if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
-  int lds = 4 * NHP2 * 8192 + 4 * (8 / WM) * 64 * 64;
-  const int scratch = 8 * 16 * (4 * 64 + 16);
-  if (lds < scratch) lds = scratch;
-  hipLaunchKernelGGL(kern, dim3(p.mtiles * p.ntiles), dim3(512), lds, st, p);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-// 3x3 stride-2 pad-1 layer: 1 = launched on conv3x3s2_pp_kernel, 0 = shape not taken, < 0 = error (in == nullptr: plan only)
-int frmap_conv3x3s2_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                       int Wi, int Cin, int Cout, int relu, int dtype, hipStream_t st) {
-  static int on = -1, min_tiles = 200, min_cin = 64;
-  if (on < 0) {
-    min_tiles = pp_env("FRMAP_PP_MIN_TILES", 200);
-    min_cin = pp_env("FRMAP_PP_S2_MIN_CIN", 64);
-    on = pp_env("FRMAP_CONV_PP", 1) && pp_env("FRMAP_CONV_PP_S2", 1);
-  }
-  constexpr int MI = 7;
-  if (g_pp_on >= 0 ? !g_pp_on : (!on || Cin < min_cin)) return 0;
-  if (Hi % 2 || Wi % 2 || Cin % 32 || Cin > 1024 || Cout % 128) return 0;
-  const int Ho = Hi / 2, Wo = Wi / 2;
-  const long long Mll = (long long)B * Ho * Wo;
-  if (Mll >= (1ll << 31) || (long long)B * Hi * Wi * Cin * 2 >= (1ll << 46) || (long long)Hi * Wi * Cin * 2 >= (1ll << 31)) return 0;
-  int bn = Cout % 256 == 0 ? 256 : 128;
-  if (g_pp_bn == 128 || g_pp_bn == 256) bn = (g_pp_bn == 256 && Cout % 256) ? 128 : g_pp_bn;
-  const int cap = (bn == 256 ? 2 : 4) * MI * 16;
-  if (Wo > cap) return 0;
-  int tile_px;
-  if (Ho * Wo <= cap) tile_px = (cap / (Ho * Wo)) * Ho * Wo;
-  else {
-    int rows = cap / Wo;
-    for (int r = rows; r * 8 >= rows * 7 && r >= 1; --r)
-      if (Ho % r == 0) { rows = r; break; }
-    tile_px = rows * Wo;
-  }
-  if (g_pp_px > 0 && g_pp_px <= cap) tile_px = g_pp_px;
-  PPParams p;
-  p.in = in; p.wpk = w_packed; p.shift = shift; p.res = residual; p.out = out;
-  p.N = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
-  p.M = (int)Mll; p.HoWo = Ho * Wo; p.Hp = Ho + 1; p.Wp = Wo + 1;   // half-resolution maps carry a top / left border only
-  p.magic_Wp = frmap_magic((uint32_t)p.Wp); p.magic_Hp = frmap_magic((uint32_t)p.Hp);
-  p.dHoWo = frmap_div_make((uint32_t)p.HoWo); p.dWo = frmap_div_make((uint32_t)Wo);
-  p.nchunks = Cin / 32;
-  p.tile_px = tile_px;
-  p.mtiles = (int)((Mll + tile_px - 1) / tile_px);
-  p.ntiles = Cout / bn;
-  const long long hbytes = (long long)pp_max_rows(Mll, tile_px, Ho * Wo, Wo, p.Hp, 2) * p.Wp * 64;
-  if (hbytes / 64 >= 65536) return 0;
-  const int need = (int)((hbytes + 8191) / 8192);
-  const int nhp = need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 0));
-  if (!nhp || (nhp == 4 && bn == 256)) return 0;                       // (4 x 32 KB images + 4 x 16 KB slabs would not fit)
-  if (!frmap_batch_invariant() && g_pp_on < 0 && (long long)p.mtiles * p.ntiles < min_tiles) return 0;
-  if (!in) return bn == 256 ? 1 : 2;
-  int rc;
-#define PP2_GO(TT)                                                                                                  \
-  (bn == 256 ? (nhp == 1 ? pp2_launch<TT, MI, 2, 1>(p, st) : pp2_launch<TT, MI, 2, 2>(p, st))                        \
-             : (nhp == 1 ? pp2_launch<TT, MI, 4, 1>(p, st) : nhp == 2 ? pp2_launch<TT, MI, 4, 2>(p, st) : pp2_launch<TT, MI, 4, 4>(p, st)))
-  rc = dtype == FRMAP_BF16 ? PP2_GO(BF16) : PP2_GO(F16);
-#undef PP2_GO
-  return rc ? rc : 1;
-}
-
 extern "C" int frmap_conv3x3s2_pp_layout(int B, int Hi, int Wi, int Cin, int Cout) {
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return frmap_conv3x3s2_pp(nullptr, nullptr, nullptr, nullptr, nullptr, B, Hi, Wi, Cin, Cout, 0, FRMAP_BF16, nullptr);
+  if (!pp_query_ok(B, Hi, Wi, Cin, Cout)) return 0;
+  return plan_pp_s2(ConvLayer{B, Hi, Wi, Cin, Cout, 3, 2, 1, FUSE_NONE, 0, 0, 0, 0}, conv_tuning(), pp_inv()).layout;
 }

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/frmap_hip.h"
+#include "conv_plan.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
@@ -750,23 +751,12 @@ int frmap_big_lds(const void* kern, int bytes);
 int frmap_stem_s2d(const float* x_nchw, const unsigned char* x_u8, const float* mean3, const float* std3, const void* w_packed_c3,
                    const float* shift, void* out, int B, int Hi, int Wi, int dtype, hipStream_t st);
 int frmap_batch_invariant();   // 1: planners must not look at the batch size (c_api.cpp)
-// second-generation 3x3 stride-1 kernel (conv_pp.hip): 1 = launched, 0 = shape not taken, < 0 = error
-struct FrmapPPShortcut {  // fused 1x1 projection shortcut: out += W . x[n, oy * stride, ox * stride, :]
-  const void* in;
-  const void* w;  // packed as a 1x1 conv
-  int Hi, Wi, Cin, stride;
-};
-int frmap_conv3x3_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                     int Wi, int Cin, int Cout, int relu, int dtype, hipStream_t st, const FrmapPPShortcut* ds);
-// the same for 3x3 stride-2 pad-1 layers with even input sizes (conv3x3s2_pp_kernel)
-int frmap_conv3x3s2_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                       int Wi, int Cin, int Cout, int relu, int dtype, hipStream_t st);
-// conv3x3 s1 p1 + MaxPool2d(2, 2) on the same pipeline (conv3x3_pp_kernel<..., PL = true>)
-int frmap_conv3x3_pp_pool(const void* in, const void* w_packed, const float* shift, void* out, int B, int Hi, int Wi, int Cin,
-                          int Cout, int relu, int dtype, hipStream_t st);
-// 1x1 conv / Linear on the LDS-DMA ping-pong pipeline (conv1x1_pp_kernel): 1 = launched, 0 = not taken, < 0 = error
-int frmap_conv1x1_pp(const void* in, const void* w_packed, const float* shift, const void* residual, void* out, int B, int Hi,
-                     int Wi, int Cin, int Cout, int stride, int relu, int dtype, hipStream_t st);
+int frmap_cu_count();          // compute units of the current device (asked once; 256 where the runtime cannot say)
+// the conv planner (conv_plan.h) with this process's tuning, CU count and batch-invariant flag (conv_igemm.hip)
+ConvPlan frmap_conv_plan(const ConvLayer& L);
+// launches a layer the planner gave to the second generation (conv_pp.hip: CK_PP, CK_PP_S2, CK_PP_1X1); 0 or an error
+int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, const void* w_packed, const float* shift,
+                         const void* residual, void* out, const void* ds_in, const void* ds_w, int relu, int dtype, hipStream_t st);
 // what the verification counts' match GEMM (MATCH_HIST) takes besides the operands:
 // tab: t [T] | lo [T] | hi [T] (fp32, device); hist: u64 [2][T + 1] accumulated into; rescored: u64 += pairs re-scored exactly
 struct FrmapVerifyGemm {

@@ -188,15 +188,11 @@ const char* dt_name(int dtype) { return dtype == FRMAP_BF16 ? "BF16" : "F16"; }
 void conv(Run& r, const PackedConv& c, const void* in, int Hi, int Wi, const void* residual, void* out, int relu) {
   if (r.rc) return;
   const int Ho = (Hi + 2 * c.pad - c.k) / c.stride + 1, Wo = (Wi + 2 * c.pad - c.k) / c.stride + 1;
+  // the label is the planner's: the kernel that runs (a layer the planner refuses fails in the call below)
   const char* name = "conv_igemm_kernel<%s>";
-  if (c.k == 3 && c.stride == 1) {
-    if (frmap_conv3x3_pp_layout(r.B, Hi, Wi, c.cin, c.cout)) name = "conv3x3_pp_kernel<%s>";
-    else if (c.cin == 64 && Hi % 8 == 0 && Wi % 8 == 0) name = "conv3x3_c64_wave_kernel<%s>";
-    else name = "conv3x3_fast_kernel<%s, false>";
-  } else if (c.k == 3 && c.stride == 2) {
-    name = frmap_conv3x3s2_pp_layout(r.B, Hi, Wi, c.cin, c.cout) ? "conv3x3s2_pp_kernel<%s>" : "conv3x3s2_fast_kernel<%s>";
-  } else if (c.k == 1) {
-    name = (c.cin >= 128 && frmap_conv1x1_pp_layout(r.B, Hi, Wi, c.cin, c.cout, c.stride)) ? "conv1x1_pp_kernel<%s>" : "conv1x1_kernel<%s>";
+  if (r.m->trace && !r.dry) {
+    const ConvPlan q = frmap_conv_plan(ConvLayer{r.B, Hi, Wi, c.cin, c.cout, c.k, c.stride, c.pad, residual ? FUSE_RESIDUAL : FUSE_NONE, 0, 0, 0, 0});
+    if (q.taken()) name = q.label;
   }
   const double M = (double)r.B * Ho * Wo;
   Traced t(r, name, 2.0 * M * c.cout * c.cin * c.k * c.k,
@@ -259,8 +255,11 @@ MapOut trunk_features(Run& r, const void* x, int x_kind, int H, int W, char* slo
       void* dst = last ? final_out : third;
       if (!r.rc) {
         const double M = (double)r.B * ho * wo;
-        const char* name = frmap_conv3x3_pp_ds_layout(r.B, ho, wo, b.c2.cin, b.c2.cout, h, w, b.ds.cin, b.ds.stride)
-                               ? "conv3x3_pp_kernel<%s, DS>" : "conv3x3_fast_kernel<%s, true>";
+        const char* name = "conv3x3_fast_kernel<%s, true>";
+        if (m->trace && !r.dry) {
+          const ConvPlan q = frmap_conv_plan(ConvLayer{r.B, ho, wo, b.c2.cin, b.c2.cout, 3, 1, 1, FUSE_SHORTCUT, h, w, b.ds.cin, b.ds.stride});
+          if (q.taken()) name = q.label;
+        }
         Traced t(r, name, 2.0 * M * b.c2.cout * (b.c2.cin * 9 + b.ds.cin),
                  2.0 * (M * b.c2.cin + M * b.c2.cout + (double)b.c2.cout * b.c2.cin * 9 + (double)b.c2.cout * b.ds.cin + M * b.ds.cin));
         r.rc = frmap_conv_igemm_ds(hb, b.c2.wpk, b.fshift, xin, b.ds.wpk, dst, r.B, ho, wo, b.c2.cin, b.c2.cout, h, w, b.ds.cin,

@@ -249,7 +249,9 @@ def test_track_entry_points_are_declared_and_bound():
         assert hasattr(_lib.load(), sym)
     assert _lib.ABI_VERSION == 10 and _lib.load().frmap_abi_version() == 10
     build = open(os.path.join(ROOT, "facerecognition-multiarchitecture-pipeline_amd", "csrc", "build.sh")).read()
-    assert " track.hip " in build and "track_rule.h -nt" in build
+    # track.hip is compiled, and an edit of track_rule.h (any header next to the sources) rebuilds the objects
+    assert " track.hip " in build and 'for h in *.h ../../include/frmap_hip.h' in build and '[ "$h" -nt "$o" ]' in build
+    assert os.path.isfile(os.path.join(ROOT, "facerecognition-multiarchitecture-pipeline_amd", "csrc", "track_rule.h"))
 
 
 def _hex(v):

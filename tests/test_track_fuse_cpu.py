@@ -241,7 +241,10 @@ def test_track_fuse_entry_points_are_declared_and_bound():
         assert hasattr(_lib.load(), sym)
     assert _lib.ABI_VERSION == 10 and _lib.load().frmap_abi_version() == 10
     build = open(os.path.join(ROOT, "facerecognition-multiarchitecture-pipeline_amd", "csrc", "build.sh")).read()
-    assert " track_fuse.hip " in build and "track_fuse_rule.h -nt" in build and "track_fuse_twin.h -nt" in build
+    # track_fuse.hip is compiled, and an edit of its rule or twin header (any header next to the sources) rebuilds the objects
+    assert " track_fuse.hip " in build and 'for h in *.h ../../include/frmap_hip.h' in build and '[ "$h" -nt "$o" ]' in build
+    for h in ("track_fuse_rule.h", "track_fuse_twin.h"):
+        assert os.path.isfile(os.path.join(ROOT, "facerecognition-multiarchitecture-pipeline_amd", "csrc", h))
     for name in ("track_fuse_state", "track_fuse", "track_fuse_host"):
         assert callable(getattr(ops, name))
     assert matching.TrackTemplates is __import__("frmap_amd").TrackTemplates
