@@ -401,8 +401,13 @@ extern "C" size_t frmap_model_workspace_bytes(const frmap_model* m, int B, int H
   if (!m || B <= 0 || H <= 0 || W <= 0) return 0;
   const size_t heads = 2 * align256((size_t)B * 512 * sizeof(float)) + 256;
   if (m->kind >= KIND_BASELINE) {   // the families' bump arena, sized by running their forward without launching
-    Run r{const_cast<frmap_model*>(m), nullptr, B, "", 0, true};
-    const size_t fam = frmap_family_forward(r, nullptr, FRMAP_INPUT_F32_NCHW, H, W, FRMAP_OUT_LOGITS, nullptr, nullptr, nullptr, nullptr);
+    // (for both input kinds: the call that asks has none, and a siamese tower takes uint8 rows of W % 4 != 0 unfused, through more buffers)
+    size_t fam = 0;
+    for (int kind : {FRMAP_INPUT_F32_NCHW, FRMAP_INPUT_U8_HWC}) {
+      Run r{const_cast<frmap_model*>(m), nullptr, B, "", 0, true};
+      const size_t f = frmap_family_forward(r, nullptr, kind, H, W, FRMAP_OUT_LOGITS, nullptr, nullptr, nullptr, nullptr);
+      fam = f > fam ? f : fam;
+    }
     if (m->kind == KIND_HYBRID) return 3 * act_slot_bytes(B, H, W) + align256((size_t)B * 49 * 512 * 2) + fam + heads;
     return fam + heads;
   }

@@ -1221,7 +1221,12 @@ class ModelHandle:
         x = _dev(x, "model_forward.x")
         kind, B, H, W = self._geometry(x)
         with torch.cuda.device(x.device):
-            if what == OUT_TRUNK_MAP:
+            if what == OUT_TRUNK_MAP and self.model_type == "baseline":      # three conv + MaxPool2d(2) stages, 128 channels
+                out = torch.empty((B, H // 2 // 2 // 2, W // 2 // 2 // 2, 128), dtype=self.dtype, device=x.device)
+            elif what == OUT_TRUNK_MAP and self.model_type == "siamese":     # 7x7 stride 2, then three MaxPool2d(2), 512 channels
+                hc, wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+                out = torch.empty((B, hc // 2 // 2 // 2, wc // 2 // 2 // 2, 512), dtype=self.dtype, device=x.device)
+            elif what == OUT_TRUNK_MAP:
                 hq, wq = stem_pool_dims(H, W)
                 for _ in range(3):
                     hq, wq = (hq - 1) // 2 + 1, (wq - 1) // 2 + 1

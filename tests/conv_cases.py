@@ -507,8 +507,12 @@ DEV = "cuda"
 U8_MEAN = U8_STD = (1.0 / 255, 1.0 / 255, 1.0 / 255)      # (u / 255 - mean) / std = u - 1 for the bytes 0, 1, 2
 
 
-def _nhwc(t, dtype):
-    return t.permute(0, 2, 3, 1).contiguous().to(dtype).to(DEV)
+def _to_dev(t):
+    return t.to(DEV)
+
+
+def _nhwc(t, dtype, place=_to_dev):
+    return place(t.permute(0, 2, 3, 1).contiguous().to(dtype))
 
 
 def _sync(what):
@@ -540,10 +544,12 @@ def query_path(lib, ops, case):
     raise ValueError(name)
 
 
-def run_case(case, o, dtype, also_unfused=False):
+def run_case(case, o, dtype, also_unfused=False, place=None):
     """Launch the case's kernel on operand dict `o` (values `dtype` represents exactly) and return the output as a CPU NCHW tensor
     in `dtype`.  Asserts the path the case is about where a query exists, and restores the process-wide tuning hooks.
-    `also_unfused`: for the fused-pool ops, returns (fused, two-launch) outputs."""
+    `also_unfused`: for the fused-pool ops, returns (fused, two-launch) outputs.  `place`: how a CPU operand reaches the device
+    (None: a plain copy; `guard.Guard.place` puts it between guard bands)."""
+    place = place or _to_dev
     from frmap_amd import _lib, ops
     lib = _lib.load()
     try:
@@ -554,17 +560,17 @@ def run_case(case, o, dtype, also_unfused=False):
         if case.query is not None:
             got = query_path(lib, ops, case)
             assert got in case.query[1], (case.name, case.query[0], "answers", got, "wanted", case.query[1])
-        sh = o["shift"].float().to(DEV)
+        sh = place(o["shift"].float())
         y2 = None
         if case.op in ("conv", "ds", "pool2"):
-            x, wpk = _nhwc(o["x"], dtype), ops.pack_conv_weight(o["w"].float().to(DEV), dtype)
+            x, wpk = _nhwc(o["x"], dtype, place), ops.pack_conv_weight(place(o["w"].float()), dtype)
             if case.op == "conv":
-                r = _nhwc(o["r"], dtype) if o.get("r") is not None else None
+                r = _nhwc(o["r"], dtype, place) if o.get("r") is not None else None
                 y = ops.conv_igemm(x, wpk, sh, case.Cout, case.k, case.stride, case_pad(case), case.act, r)
             elif case.op == "ds":
-                xd = _nhwc(o["xd"], dtype)
+                xd = _nhwc(o["xd"], dtype, place)
                 assert ops.conv_ds_supported(case.B, case.H, case.W, case.Cin, case.Cout, xd.shape[1], xd.shape[2], case.ds[0], case.ds[1])
-                y = ops.conv_igemm_ds(x, wpk, sh, case.Cout, xd, ops.pack_conv_weight(o["wd"].float().to(DEV), dtype), case.ds[1], case.act)
+                y = ops.conv_igemm_ds(x, wpk, sh, case.Cout, xd, ops.pack_conv_weight(place(o["wd"].float()), dtype), case.ds[1], case.act)
             else:
                 y = ops.conv_igemm_pool2(x, wpk, sh, case.Cout, case.act)
                 if also_unfused:
@@ -572,7 +578,7 @@ def run_case(case, o, dtype, also_unfused=False):
         elif case.op in ("c3", "c3pool2"):
             x4 = torch.zeros((case.B, case.H, case.W, 4), dtype=dtype)
             x4[..., :3] = o["x"].permute(0, 2, 3, 1).to(dtype)
-            x4, wpk = x4.to(DEV), ops.pack_conv_weight_c3(o["w"].float().to(DEV), dtype)
+            x4, wpk = place(x4), ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
             if case.op == "c3":
                 y = ops.conv_small_cin(x4, wpk, sh, case.Cout, case.k, case.stride, case_pad(case), True)
             else:
@@ -580,11 +586,11 @@ def run_case(case, o, dtype, also_unfused=False):
                 if also_unfused:
                     y2 = ops.maxpool(ops.conv_small_cin(x4, wpk, sh, case.Cout, 3, 1, 1, True), 2, 2, 0)
         elif case.op in ("stem3", "stem2"):
-            wpk = ops.pack_conv_weight_c3(o["w"].float().to(DEV), dtype)
-            y = ops.stem7x7_maxpool(o["x"].float().to(DEV), wpk, sh, dtype, pool3=case.op == "stem3")
+            wpk = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
+            y = ops.stem7x7_maxpool(place(o["x"].float()), wpk, sh, dtype, pool3=case.op == "stem3")
         elif case.op in ("stem3u8", "stem2u8"):
-            wpk = ops.pack_conv_weight_c3(o["w"].float().to(DEV), dtype)
-            y = ops.stem7x7_maxpool_u8(o["u8"].to(DEV), wpk, sh, o["mean"], o["std"], dtype, pool3=case.op == "stem3u8")
+            wpk = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
+            y = ops.stem7x7_maxpool_u8(place(o["u8"]), wpk, sh, o["mean"], o["std"], dtype, pool3=case.op == "stem3u8")
         else:
             raise ValueError(case.op)
         _sync(case.name)
@@ -618,16 +624,18 @@ def gpu_operands(case, family, dtype):
     return o
 
 
-def run_linear(lc, o, dtype):
-    """`ops.linear_mfma` on operands x [M,K], w [N,K], shift, r; asserts that split-K is (not) taken as the case says."""
+def run_linear(lc, o, dtype, place=None):
+    """`ops.linear_mfma` on operands x [M,K], w [N,K], shift, r; asserts that split-K is (not) taken as the case says.
+    `place`: as `run_case`."""
+    place = place or _to_dev
     from frmap_amd import _lib, ops
     lib = _lib.load()
     assert (lib.frmap_linear_mfma_workspace_bytes(lc.M, lc.K, lc.N) > 0) == lc.split, (lc.name, "split-K")
     if lc.name == "linear-smallest-splitk":
         assert lib.frmap_linear_mfma_workspace_bytes(lc.M, lc.K - 32, lc.N) == 0, "a smaller K splits"
-    wpk = ops.pack_conv_weight(o["w"].float().view(lc.N, lc.K, 1, 1).to(DEV), dtype)
-    r = o["r"].to(dtype).to(DEV) if o.get("r") is not None else None
-    y = ops.linear_mfma(o["x"].to(dtype).to(DEV), wpk, o["shift"].float().to(DEV), lc.N, lc.act, r)
+    wpk = ops.pack_conv_weight(place(o["w"].float().view(lc.N, lc.K, 1, 1)), dtype)
+    r = place(o["r"].to(dtype)) if o.get("r") is not None else None
+    y = ops.linear_mfma(place(o["x"].to(dtype)), wpk, place(o["shift"].float()), lc.N, lc.act, r)
     _sync(lc.name)
     return y.cpu()
 
