@@ -678,12 +678,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvPara
         for (int q = 1; q < 4; ++q) {
           const f32x4_t a2 = *(const f32x4_t*)(src + q * PITCH), b2 = *(const f32x4_t*)(src + q * PITCH + 16);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { a[e] = fmaxf(a[e], a2[e]); b[e] = fmaxf(b[e], b2[e]); }
+          for (int e = 0; e < 4; ++e) { a[e] = frmap_max(a[e], a2[e]); b[e] = frmap_max(b[e], b2[e]); }
         }
         float v[8] = {a[0] + sh[0], a[1] + sh[1], a[2] + sh[2], a[3] + sh[3], b[0] + sh[4], b[1] + sh[5], b[2] + sh[6], b[3] + sh[7]};
         if (p.relu == 1) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+          for (int e = 0; e < 8; ++e) v[e] = frmap_relu(v[e]);
         }
         ov[mp >> 1] = pack8<TT>(v);
       }
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvPara
           }
           if (p.relu == 1) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+            for (int e = 0; e < 8; ++e) v[e] = frmap_relu(v[e]);
           } else if (p.relu == 2) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752f));
@@ -1110,7 +1110,7 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ slab, int kspli
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      if (act == 1) v[e] = fmaxf(v[e], 0.f);
+      if (act == 1) v[e] = frmap_relu(v[e]);
       else if (act == 2) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752f));
     }
     *(u32x2_t*)(out + i) = pack4<TT>(v[0], v[1], v[2], v[3]);

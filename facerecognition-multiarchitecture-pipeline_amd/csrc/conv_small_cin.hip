@@ -130,7 +130,9 @@ __global__ __launch_bounds__(256, 2) void conv_small_cin_kernel(const SmallCinPa
     const int e = ks * 32 + g * 8;
     int kh = e / KR;
     const int off = e - kh * KR;
-    if (kh >= KH) kh = 0;  // zero-weight pad k-groups: read any staged (finite) data
+    // zero-weight pad k-groups (3x3: k >= 48) re-read row kh = 0 of the same pixel.  The data need not be finite: a NaN / inf
+    // there times the zero weight is NaN - the declared in-image halo of this kernel ("Non-finite values")
+    if (kh >= KH) kh = 0;
     koff[ks] = kh * p.Wl * 8 + off * 2;
   }
   const int woff = lr * WPITCH + g * 16;

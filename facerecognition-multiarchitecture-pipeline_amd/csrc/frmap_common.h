@@ -65,6 +65,14 @@ __device__ __forceinline__ u32x4_t pack8(const float* f) {
   return r;
 }
 
+// NaN-propagating maxima (IEEE 754-2019 maximum: NaN if either operand is NaN, maximum(-0, +0) = +0) for every ReLU and
+// max-pool between the input and the embedding: `F.relu` and `nn.MaxPool2d` return NaN for a NaN, `fmaxf(NaN, 0)` returns 0
+// and the matcher's non-finite guards would never see the value ("Non-finite values").  One v_maximum3_f32 each.
+// The matcher's own bound logic keeps fminf / fmaxf: its NaN rules rely on them.
+__device__ __forceinline__ float frmap_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float frmap_max3(float a, float b, float c) { return frmap_max(frmap_max(a, b), c); }
+__device__ __forceinline__ float frmap_relu(float v) { return frmap_max(v, 0.f); }
+
 // ------------------------------------------------------------------------------------------------
 // Top-1 gallery match (compare_faces, /root/reference/src/app.py:58-63) behind a GEMM: candidate records.
 //
@@ -618,8 +626,13 @@ __device__ __forceinline__ void conv_epilogue(const f32x4_t (&acc)[MI][NI], char
           for (int e = 0; e < 8; ++e) v[e] += r[e];
         }
         if (relu == 1) {
+          // frmap_relu on two 4-vectors: written element by element the same instructions cost conv3x3_pp_kernel<.., MI = 7, RI>
+          // one spilled register (csrc/build.sh's no-scratch check)
+          f32x4_t lo4 = {v[0], v[1], v[2], v[3]}, hi4 = {v[4], v[5], v[6], v[7]};
+          const f32x4_t z4 = {0.f, 0.f, 0.f, 0.f};
+          lo4 = __builtin_elementwise_maximum(lo4, z4); hi4 = __builtin_elementwise_maximum(hi4, z4);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+          for (int e = 0; e < 4; ++e) { v[e] = lo4[e]; v[4 + e] = hi4[e]; }
         } else if (relu == 2) {  // exact (erf) GELU, nn.GELU() default
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = 0.5f * v[e] * (1.0f + erff(v[e] * 0.70710678118654752f));
@@ -664,14 +677,14 @@ __device__ __forceinline__ void conv_epilogue_pool2(const f32x4_t (&acc)[MI][NI]
     for (int q = 1; q < 4; ++q) {
       const f32x4_t a2 = *(const f32x4_t*)(src + q * PITCH), b2 = *(const f32x4_t*)(src + q * PITCH + 16);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { a[e] = fmaxf(a[e], a2[e]); b[e] = fmaxf(b[e], b2[e]); }
+      for (int e = 0; e < 4; ++e) { a[e] = frmap_max(a[e], a2[e]); b[e] = frmap_max(b[e], b2[e]); }
     }
     const int mp = mp_wave0 + mi * 4 + win;
     if (active && mp < MP) {
       float v[8] = {a[0] + sh[0], a[1] + sh[1], a[2] + sh[2], a[3] + sh[3], b[0] + sh[4], b[1] + sh[5], b[2] + sh[6], b[3] + sh[7]};
       if (relu == 1) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+        for (int e = 0; e < 8; ++e) v[e] = frmap_relu(v[e]);
       }
       *(u32x4_t*)(out + (size_t)mp * Cout + co0 + part * 8) = pack8<TT>(v);
     }

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
       if (MODE == MODE_LINEAR) {
         if (valid) {
           float v = dot * wscale + wshift;
-          if (ep.relu) v = fmaxf(v, 0.f);
+          if (ep.relu) v = frmap_relu(v);
           ep.out[(size_t)b * N + n] = v;
         }
       } else if (MODE == MODE_COS) {
@@ -272,7 +272,7 @@ __global__ void row_stats_kernel(const float* __restrict__ x, float* __restrict_
     s1 += __shfl_xor(s1, o, 64);
   }
   if (lane == 0) {
-    if (mode == 0) out[r] = 1.0f / fmaxf(sqrtf(s2), eps);
+    if (mode == 0) out[r] = 1.0f / frmap_max(sqrtf(s2), eps);
     else { out[2 * r] = s2; out[2 * r + 1] = s1; }
   }
 }
@@ -287,7 +287,7 @@ __global__ void l2_normalize_kernel(const float* __restrict__ x, float* __restri
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-  const float denom = fmaxf(sqrtf(s2), eps);
+  const float denom = frmap_max(sqrtf(s2), eps);
   for (int k = lane; k < D; k += 64) out[(size_t)r * D + k] = x[(size_t)r * D + k] / denom;
 }
 
@@ -431,7 +431,8 @@ __global__ __launch_bounds__(256) void gap_norm_match_kernel(const typename TT::
         for (int j = 0; j < 8; ++j) a[j] += f[j];
       }
     }
-    {  // the last (< 16) rows of this subset: loads first (rows past the end re-read the last one with weight 0)
+    {  // the last (< 16) rows of this subset: loads first (rows past the end re-read the last one and are replaced by zeros:
+       // a select, not a weight of 0 - the last row may hold an infinity, and inf * 0 = NaN)
       u32x4_t r[16];
       const int n = s < HW ? (HW - 1 - s) / nparts + 1 : 0;
 #pragma unroll
@@ -439,10 +440,9 @@ __global__ __launch_bounds__(256) void gap_norm_match_kernel(const typename TT::
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         float f[8];
-        unpack8<TT>(r[q], f);
-        const float wq = q < n ? 1.0f : 0.0f;
+        unpack8<TT>(q < n ? r[q] : (u32x4_t){0u, 0u, 0u, 0u}, f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = fmaf(wq, f[j], a[j]);
+        for (int j = 0; j < 8; ++j) a[j] += f[j];
       }
     }
 #pragma unroll
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(256) void gap_norm_match_kernel(const typename TT::
   if (lane == 0) s_red[wave] = ss;
   __syncthreads();
   if (normalize) {
-    const float denom = fmaxf(sqrtf(s_red[0] + s_red[1] + s_red[2] + s_red[3]), eps);
+    const float denom = frmap_max(sqrtf(s_red[0] + s_red[1] + s_red[2] + s_red[3]), eps);
     for (int k = tid; k < C; k += 256) s_e[k] = s_e[k] / denom;
     __syncthreads();
   }
@@ -594,14 +594,26 @@ __global__ __launch_bounds__(256) void gap_linear_norm_kernel(const typename TT:
           ra[q] = *(const u32x4_t*)(sa + o);
           rb[q] = *(const u32x4_t*)(sb + o);
         }
+        if (s0 + 7 * nsub < HW) {   // all 8 rows exist (every trip but a subset's last): plain adds
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          float va[8], vb[8];
-          unpack8<TT>(ra[q], va);
-          unpack8<TT>(rb[q], vb);
-          const float wq = s0 + q * nsub < HW ? 1.0f : 0.0f;
+          for (int q = 0; q < 8; ++q) {
+            float va[8], vb[8];
+            unpack8<TT>(ra[q], va);
+            unpack8<TT>(rb[q], vb);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { a[j] = fmaf(wq, va[j], a[j]); c[j] = fmaf(wq, vb[j], c[j]); }
+            for (int j = 0; j < 8; ++j) { a[j] += va[j]; c[j] += vb[j]; }
+          }
+        } else {   // rows past the end re-read the last one and are replaced by zeros: a select, not a weight of 0 - the last
+                   // row may hold an infinity, and inf * 0 = NaN
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            float va[8], vb[8];
+            const bool live = s0 + q * nsub < HW;
+            unpack8<TT>(live ? ra[q] : (u32x4_t){0u, 0u, 0u, 0u}, va);
+            unpack8<TT>(live ? rb[q] : (u32x4_t){0u, 0u, 0u, 0u}, vb);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { a[j] += va[j]; c[j] += vb[j]; }
+          }
         }
       }
       if (nsub == 1) {
@@ -681,7 +693,7 @@ __global__ __launch_bounds__(256) void gap_linear_norm_kernel(const typename TT:
 #pragma unroll
     for (int f = 0; f < FB; ++f) {
       acc[j][f] = acc[j][f] * sc + sh;
-      if (relu) acc[j][f] = fmaxf(acc[j][f], 0.f);
+      if (relu) acc[j][f] = frmap_relu(acc[j][f]);
       ss[f] += acc[j][f] * acc[j][f];
     }
   }
@@ -698,7 +710,7 @@ __global__ __launch_bounds__(256) void gap_linear_norm_kernel(const typename TT:
 #pragma unroll
   for (int f = 0; f < FB; ++f) {
     if (b0 + f >= B) break;
-    const float denom = fmaxf(sqrtf(s_red[f * 4] + s_red[f * 4 + 1] + s_red[f * 4 + 2] + s_red[f * 4 + 3]), eps);
+    const float denom = frmap_max(sqrtf(s_red[f * 4] + s_red[f * 4 + 1] + s_red[f * 4 + 2] + s_red[f * 4 + 3]), eps);
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
       const size_t o = (size_t)(b0 + f) * N + j * 256 + tid;

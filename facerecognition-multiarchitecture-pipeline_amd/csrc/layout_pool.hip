@@ -162,7 +162,7 @@ __global__ void maxpool_kernel(const typename TT::elem* __restrict__ in, typenam
         float f[8];
         unpack8<TT>(*(const u32x4_t*)(in + (((size_t)n * H + iy) * W + ix) * C + c8 * 8), f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], f[j]);
+        for (int j = 0; j < 8; ++j) m[j] = frmap_max(m[j], f[j]);
       }
     }
     *(u32x4_t*)(out + i * 8) = pack8<TT>(m);

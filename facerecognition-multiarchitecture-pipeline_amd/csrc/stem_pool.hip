@@ -293,11 +293,11 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
           for (int e = 0; e < 4; ++e) {
             float m;
             if (POOL3) {
-              m = fmaxf(fmaxf(acc[2 * pr][ni][e], acc[2 * pr + 1][ni][e]), acc[2 * pr + 2][ni][e]);  // rows
-              m = fmaxf(m, fmaxf(row_down<1>(m), row_down<2>(m)));                                     // columns
+              m = frmap_max3(acc[2 * pr][ni][e], acc[2 * pr + 1][ni][e], acc[2 * pr + 2][ni][e]);  // rows
+              m = frmap_max3(m, row_down<1>(m), row_down<2>(m));                                     // columns
             } else {
-              m = fmaxf(acc[2 * pr][ni][e], acc[2 * pr + 1][ni][e]);
-              m = fmaxf(m, row_down<1>(m));
+              m = frmap_max(acc[2 * pr][ni][e], acc[2 * pr + 1][ni][e]);
+              m = frmap_max(m, row_down<1>(m));
             }
             v[e] = m;
           }
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
           float o[8] = {a[0] + s0[0], a[1] + s0[1], a[2] + s0[2], a[3] + s0[3],
                         b[0] + s1[0], b[1] + s1[1], b[2] + s1[2], b[3] + s1[3]};
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = fmaxf(o[e], 0.f);
+          for (int e = 0; e < 8; ++e) o[e] = frmap_relu(o[e]);
           *(u32x4_t*)(outp + (((size_t)n * p.Hq + py) * p.Wq + px) * 64 + part * 8) = pack8<TT>(o);
         }
       }

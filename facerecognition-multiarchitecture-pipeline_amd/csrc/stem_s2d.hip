@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void stem_s2d_kernel(const StemS2DParams p)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float top = pr == 0 ? carry[ni][e] : acc[2 * pr - 1][ni][e];
-              v[e] = fmaxf(fmaxf(top, acc[2 * pr][ni][e]), acc[2 * pr + 1][ni][e]);           // rows 2 py - 1, 2 py, 2 py + 1
+              v[e] = frmap_max3(top, acc[2 * pr][ni][e], acc[2 * pr + 1][ni][e]);           // rows 2 py - 1, 2 py, 2 py + 1
             }
             *(f32x4_t*)(scratch + lr * kPitch + ni * 64 + g * 16) = v;
           }
@@ -314,8 +314,8 @@ __global__ __launch_bounds__(256, 2) void stem_s2d_kernel(const StemS2DParams p)
             float o[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              o[e] = fmaxf(fmaxf(fmaxf(c0[0][e], c0[1][e]), c0[2][e]), 0.f);
-              o[4 + e] = fmaxf(fmaxf(fmaxf(c1[0][e], c1[1][e]), c1[2][e]), 0.f);
+              o[e] = frmap_relu(frmap_max3(c0[0][e], c0[1][e], c0[2][e]));
+              o[4 + e] = frmap_relu(frmap_max3(c1[0][e], c1[1][e], c1[2][e]));
             }
             *(u32x4_t*)(outp + (((size_t)n * p.Hq + py) * p.Wq + px) * 64 + part * 8) = pack8<TT>(o);
           }

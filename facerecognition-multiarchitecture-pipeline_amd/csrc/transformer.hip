@@ -291,13 +291,14 @@ __global__ __launch_bounds__(256) void mean_layernorm_kernel(const typename TT::
         u32x4_t r[7];
 #pragma unroll
         for (int u = 0; u < 7; ++u) r[u] = *(const u32x4_t*)(src + (size_t)min(l0 + u * nsub, L - 1) * D);
+        const bool full = l0 + 6 * nsub < L;   // all 7 tokens exist (every trip but a subset's last): plain adds
 #pragma unroll
         for (int u = 0; u < 7; ++u) {
           float v[8];
-          unpack8<TT>(r[u], v);
-          const float w = l0 + u * nsub < L ? 1.0f : 0.0f;
+          // tokens past the end re-read the last one and are replaced by zeros: a select, not a weight of 0 (inf * 0 = NaN)
+          unpack8<TT>(full || l0 + u * nsub < L ? r[u] : (u32x4_t){0u, 0u, 0u, 0u}, v);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) a[j] = fmaf(w, v[j], a[j]);
+          for (int j = 0; j < 8; ++j) a[j] += v[j];
         }
       }
 #pragma unroll

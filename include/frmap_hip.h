@@ -222,6 +222,9 @@ int frmap_pack_conv_weight_c3(const float* w_oihw, void* w_packed, int Cout, int
  *   BaselineNet conv1 3x3 s1 p1 -> 32     (src/face_models.py:21-22,38)
  * Implicit GEMM on v_mfma_f32_16x16x32 with the K axis laid along (kw, c) of each kernel row.
  * out: NHWC B×Ho×Wo×Cout in `dtype`.  Cout in {32, 64}.
+ * Non-finite input ("Non-finite values"): a NaN / inf pixel makes every output of its receptive field NaN / inf as
+ * in PyTorch (the ReLU keeps NaN) and may also make NaN the outputs whose zero-weight pad taps read it (same image, one pixel
+ * column beside the field; 3x3: the output row below as well); no other output and no other image changes by a bit.
  * ------------------------------------------------------------------------------------------- */
 int frmap_conv_small_cin(const void* in_nhwc4, const void* w_packed, const float* shift, void* out,
                          int B, int Hi, int Wi, int Cout, int KH, int KW, int stride, int pad,
@@ -230,7 +233,7 @@ int frmap_conv_small_cin(const void* in_nhwc4, const void* w_packed, const float
  * `self.pool(F.relu(self.bn1(self.conv1(x))))` (src/face_models.py:38) in one launch.  The kernel walks
  * its output pixels in pool-major order (4 consecutive pixels = one 2x2 window), so the pooled value is
  * a max over 4 accumulator rows; the 32×H×W conv map never reaches HBM.  Even Hi, Wi.
- * out: B×(Hi/2)×(Wi/2)×32. */
+ * out: B×(Hi/2)×(Wi/2)×32.  Non-finite values: as frmap_conv_small_cin followed by frmap_maxpool, bit for bit. */
 int frmap_conv_small_cin_pool2(const void* in_nhwc4, const void* w_packed, const float* shift, void* out,
                                int B, int Hi, int Wi, int Cout, int relu, int dtype, void* stream);
 
@@ -240,6 +243,10 @@ int frmap_conv_small_cin_pool2(const void* in_nhwc4, const void* w_packed, const
  * Replaces conv1/bn1/relu/maxpool of torchvision resnet18 (src/face_models.py:67,463,658) plus the
  * input layout cast.  w_packed_c3: from frmap_pack_conv_weight_c3(…, 64, 7, 7).  Needs Wi <= ~224
  * (pooled width <= 56); wider inputs use frmap_pack_input + frmap_conv_small_cin + frmap_maxpool.
+ * Non-finite input (all four stem entry points): a NaN / inf pixel, or an fp32 pixel beyond the range of `dtype`, reaches every
+ * pooled output whose window holds a conv position of its receptive field, as nn.ReLU + nn.MaxPool2d propagate it (a window
+ * keeps a NaN, drops a -inf), and may make NaN the windows holding a conv position whose zero-weight pad tap reads it (one pixel
+ * column / row beside the field, same image).  Nothing else changes by a bit; a NaN / inf `shift` reaches its channel.
  * ------------------------------------------------------------------------------------------- */
 int frmap_stem7x7_maxpool(const float* x_nchw, const void* w_packed_c3, const float* shift, void* out,
                           int B, int Hi, int Wi, int dtype, void* stream);
@@ -272,13 +279,18 @@ int frmap_stem7x7_maxpool_u8(const unsigned char* x_u8_hwc, const float* mean3_h
  *   shift    : fp32 [Cout]   (beta - mean*scale [+ bias*scale])
  *   residual : B×Ho×Wo×Cout (dtype) or NULL
  *   out      : B×Ho×Wo×Cout (dtype),  Ho = (Hi + 2*pad - K)/stride + 1
+ * Non-finite values (this entry point, _pool2, _ds and frmap_linear_mfma): a NaN / inf element of `in`, `residual` or `ds_in`
+ * gives every output of its receptive field the class (NaN, +inf, -inf, finite) of the same op in PyTorch - ReLU keeps NaN and
+ * maps -inf to exactly 0, a value beyond the range of `dtype` is stored as inf - and changes no other output, and no other
+ * image, by a bit.
  * ------------------------------------------------------------------------------------------- */
 int frmap_conv_igemm(const void* in, const void* w_packed, const float* shift, const void* residual,
                      void* out, int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int pad,
                      int relu, int dtype, void* stream);
 /* conv 3x3 s1 p1 + shift (+ReLU) + MaxPool2d(2, 2) in one launch: BaselineNet conv2/conv3 blocks
  * (src/face_models.py:39-40) and SiameseNet's conv -> BN -> ReLU -> MaxPool2d(2) runs (:121-141).
- * relu in {0, 1} (the max is taken before shift + activation, which is exact for monotonic ones).
+ * relu in {0, 1} (the max is taken before shift + activation, which is exact for monotonic ones; it keeps a NaN and drops a
+ * -inf like nn.MaxPool2d, so the result holds the bits of frmap_conv_igemm + frmap_maxpool for non-finite operands too).
  * out: B×(Hi/2)×(Wi/2)×Cout.  frmap_conv_igemm_pool2_supported: 1 when the shape is taken (even Hi and Wi,
  * Cin % 32 == 0, Cout % 64 == 0, the tile's input rows fit LDS); otherwise run frmap_conv_igemm +
  * frmap_maxpool. */
@@ -351,6 +363,8 @@ int frmap_linear_mfma(const void* x, const void* w_packed, const float* shift, c
  *                          avgpool)
  *   frmap_avgpool_adaptive: AdaptiveAvgPool2d((OH,OW)) -> `dtype` B×OH×OW×C
  *                          (src/face_models.py:142), windows [floor(i*H/OH), ceil((i+1)*H/OH))
+ * Non-finite input: frmap_maxpool returns NaN for a window that holds a NaN and drops a -inf (nn.MaxPool2d); the average pools
+ * return the sum's NaN / inf.  Only the windows that hold the element change.
  * ------------------------------------------------------------------------------------------- */
 int frmap_maxpool(const void* in, void* out, int B, int H, int W, int C, int k, int stride, int pad,
                   int dtype, void* stream);
@@ -366,6 +380,9 @@ int frmap_avgpool_adaptive(const void* in, void* out, int B, int H, int W, int C
  *   frmap_l2_normalize_f32 : F.normalize(x, p=2, dim=1, eps) = x / max(||x||, eps)
  *                      (src/face_models.py:179,525,590)
  *   frmap_cast_to_f32 / frmap_cast_from_f32 : dtype <-> fp32 element casts for head glue
+ * Non-finite input: frmap_linear_f32's ReLU keeps NaN (relu(-inf) = 0); frmap_l2_normalize_f32 makes a row with a NaN all NaN
+ * and a row with an infinity 0 except NaN at the infinity, as F.normalize; the casts keep NaN and the infinities and round a
+ * value beyond the range of `dtype` to inf.  Other rows are untouched.
  * ------------------------------------------------------------------------------------------- */
 int frmap_linear_f32(const float* x, const float* w, const float* scale, const float* shift,
                      float* out, int B, int K, int N, int relu, void* stream);
@@ -540,7 +557,9 @@ int frmap_match_radius_packed(const float* a, const int32_t* label_a, int P, con
  * AdaptiveAvgPool2d(1) of the trunk map (face_models.py:100) -> optional F.normalize(eps) -> compare_faces' scan
  * (src/app.py:58-64) exactly as frmap_match_top1 does it for G <= 64.
  *   map : [B][HW][C] (dtype) trunk output (NHWC);  gallery : fp32 [G][C], 0 <= G <= 64
- *   emb_out : fp32 [B][C] pooled (and normalised, if asked) embedding, or NULL;  other outputs as frmap_match_top1. */
+ *   emb_out : fp32 [B][C] pooled (and normalised, if asked) embedding, or NULL;  other outputs as frmap_match_top1.
+ * A face whose map holds a NaN / inf gets the NaN / inf embedding F.normalize would give (a NaN norm makes the row NaN) and is
+ * declined: idx -1, dist +inf, id -1.  Other faces keep their answers bit for bit. */
 int frmap_gap_norm_match(const void* map, const float* gallery, float* emb_out, int32_t* idx_out, float* dist_out,
                          int32_t* id_or_unknown_out, int32_t* packed_out, float thresh, int normalize, float eps,
                          int B, int HW, int C, int G, int dtype, void* stream);
@@ -549,7 +568,8 @@ int frmap_gap_norm_match(const void* map, const float* gallery, float* emb_out, 
  *   ArcFaceNet (src/face_models.py:573-590): embedding (no bias) + bn, relu = 0;
  *   BaselineNet (:41-46, 51-60): F.relu(self.fc1(pooled)), relu = 1 (pre_out = the reference's un-normalised embedding).
  * wt: the Linear weight transposed, fp32 [K][N], N in {256, 512}; pre_out / emb_out: fp32 [B][N] un-normalised /
- * unit-norm embeddings (either may be NULL). */
+ * unit-norm embeddings (either may be NULL).  A NaN / inf in a face's map makes that face's pre_out / emb_out rows NaN / inf as in
+ * PyTorch (the ReLU and the normalisation keep NaN); other faces keep their bits. */
 int frmap_gap_linear_norm(const void* map, const float* wt, const float* scale, const float* shift, float* pre_out,
                           float* emb_out, float eps, int B, int HW, int K, int N, int relu, int dtype, void* stream);
 int frmap_cosine_logits(const float* x, const float* w, float* logits_out, int32_t* argmax_out,
