@@ -30,7 +30,7 @@ done
 # is a vector-memory access the count does not know about (stale LDS could be read).  Every *_pp_kernel must therefore compile
 # without scratch: check the resource-usage remarks of conv_pp.hip (one extra, parallel, compile; FRMAP_SKIP_SPILL_CHECK=1 skips it).
 spill_pid=""
-if [ "${FRMAP_SKIP_SPILL_CHECK:-0}" != "1" ] && { [ ! -f .pp_spill_ok ] || [ conv_pp.hip -nt .pp_spill_ok ] || [ frmap_common.h -nt .pp_spill_ok ] || [ conv_plan.h -nt .pp_spill_ok ]; }; then
+if [ "${FRMAP_SKIP_SPILL_CHECK:-0}" != "1" ] && { [ ! -f .pp_spill_ok ] || [ conv_pp.hip -nt .pp_spill_ok ] || [ frmap_common.h -nt .pp_spill_ok ] || [ match_device.h -nt .pp_spill_ok ] || [ conv_plan.h -nt .pp_spill_ok ]; }; then
   ( $HIPCC $FLAGS -Rpass-analysis=kernel-resource-usage -c conv_pp.hip -o /dev/null 2> .pp_remarks.txt || exit 1
     python3 - <<'PY' || exit 1
 import re, sys

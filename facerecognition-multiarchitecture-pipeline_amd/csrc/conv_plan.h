@@ -119,7 +119,7 @@ int conv_ds_supported(const ConvLayer& L, const ConvTuning& t, bool inv);
 // frmap_linear_mfma: K slices of the split-K form (1 = none).  Batch-invariant: that of a single row tile for every M, so the
 // fp32 summation order does not depend on the batch.
 int linear_ksplit(int M, int K, int N, bool inv);
-// frmap_match_gemm: 224 probes x 256 gallery rows per tile, or 448 x 128 when that fills the CUs better
+// the match GEMM (frmap_match_gemm_*, conv_pp.hip): 224 probes x 256 gallery rows per tile, or 448 x 128 when that fills the CUs better
 ConvPlan match_gemm_plan(int P, int Gpad);
 
 // most halo rows any tile touches (memoised); extra = 3 for stride 1, 2 for the half-resolution maps of stride 2

@@ -25,7 +25,7 @@
 //   otherwise drain vmcnt(0) ahead of every LDS read that may alias an outstanding LDS-DMA write), so every wait on it
 //   is hand-counted; the number of DMA instructions per phase is static (slabs / halo pieces past the end of the
 //   problem are fetched from valid dummy addresses into buffers nobody reads).
-#include "frmap_common.h"
+#include "match_device.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -51,34 +51,19 @@ struct PPParams {
   // fused MaxPool2d(2, 2) (PL = true): each wave's 112-pixel slice (whole row pairs) is walked in pool-major order
   int Wo2;         // Wi / 2
   FrmapDiv dWo2;
-  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR / MATCH_HIST / MATCH_JOIN> (gallery match, frmap_match_gemm): per-row statistics, records
+  // conv1x1_pp_kernel<..., MM = MATCH_TOP1 / MATCH_TOPR / MATCH_HIST / MATCH_JOIN> (gallery match, frmap_match_gemm_*): per-row statistics, records
   const float* m_stat_a;        // [M][4] = (sum a^2, sum a, 1 / row scale, error band) of the fp32 probes
   const float* m_stat_w;        // [G][4] of the fp32 gallery rows
-  void* m_records;              // [Cout / 64][M] candidate records (MatchRec or MatchRecK, frmap_common.h), one writer each
+  void* m_records;              // [Cout / 64][M] candidate records (MatchRec or MatchRecK, match_device.h), one writer each
   int m_G, m_D;                 // real gallery rows (Cout is padded to 256), embedding width
 };
-// conv1x1_pp_kernel<..., MATCH_HIST> (verification counts) takes these: exact operands, labels, the threshold table, the counts.
-// A type of its own, so that every other instantiation keeps PPParams' layout (and its kernarg offsets) unchanged.
+// conv1x1_pp_kernel<..., MATCH_HIST> (verification counts) and <..., MATCH_JOIN> (threshold search) take their mode's arguments
+// (match_device.h) too.  Types of their own, so that every other instantiation keeps PPParams' layout (and its kernarg offsets) unchanged.
 struct PPHistParams : PPParams {
-  const float* h_A;             // fp32 [M][D] (the probes)
-  const float* h_B;             // fp32 [G][D] (the gallery rows)
-  const int32_t* h_lab_a;
-  const int32_t* h_lab_b;
-  const float* h_tab;           // t [T] | lo [T] | hi [T]
-  unsigned long long* h_hist;   // [2][T + 1]
-  unsigned long long* h_rescored;
-  int h_row0, h_T;
+  FrmapVerifyGemm v;
 };
-// conv1x1_pp_kernel<..., MATCH_JOIN> (threshold search): exact operands, labels and filter, the threshold's bracket, the pair list.
 struct PPJoinParams : PPParams {
-  const float* j_A;             // fp32 [M][D] (the probes)
-  const float* j_B;             // fp32 [G][D] (the gallery rows)
-  const int32_t* j_lab_a;       // (null when j_filter == 0)
-  const int32_t* j_lab_b;
-  RadiusOut j_out;
-  unsigned long long* j_rescored;
-  float j_hi;                   // the smallest fp32 >= next_up(thresh)^2
-  int j_row0, j_filter;
+  FrmapRadiusGemm r;
 };
 template <int MM> struct PPArg { using type = PPParams; };
 template <> struct PPArg<MATCH_HIST> { using type = PPHistParams; };
@@ -87,8 +72,8 @@ template <> struct PPArg<MATCH_JOIN> { using type = PPJoinParams; };
 // one contiguous band of tile rows, so the top band's XCD would keep ~all of its work while the bottom band's has ~none; there the
 // tiles are dealt round-robin instead (block b runs on XCD b % 8), which gives every XCD the same share of live tiles.
 __device__ __forceinline__ bool pp_hist_self(const PPParams&) { return false; }
-__device__ __forceinline__ bool pp_hist_self(const PPHistParams& p) { return p.h_row0 >= 0; }
-__device__ __forceinline__ bool pp_hist_self(const PPJoinParams& p) { return p.j_row0 >= 0; }
+__device__ __forceinline__ bool pp_hist_self(const PPHistParams& p) { return p.v.row0 >= 0; }
+__device__ __forceinline__ bool pp_hist_self(const PPJoinParams& p) { return p.r.row0 >= 0; }
 
 __device__ __attribute__((aligned(4096))) unsigned int g_pp_zero[1024];
 
@@ -535,15 +520,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const PPParams p) {
 // KS = 2: 224 px x 128 ch with the two wave groups splitting K (own buffers; accumulators merged through LDS) for outputs with
 // few tiles (Linear 2048 -> 512 over 12 544 tokens: 224 tiles instead of 112).
 // ================================================================================================
-// MM = MATCH_TOP1: top-1 gallery match (frmap_match_gemm): the GEMM is probes x gallery rows in split fp16 operands, each lane
+// MM = MATCH_TOP1: top-1 gallery match (frmap_match_gemm_records): the GEMM is probes x gallery rows in split fp16 operands, each lane
 // forms the expanded squared F.pairwise_distance of its 16 gallery rows with its error band, the column's four lanes meet
 // through two shuffles, one candidate record per probe and 64-row slot (match_epilogue_records).
 // MM = MATCH_TOPR: the same GEMM with the top-k search's records (match_epilogue_topr: R = 4 rows per slot + the rest bound).
 // MM = MATCH_HIST: verification counts (match_epilogue_hist): certain pairs binned in LDS, the rest queued per wave in LDS and
-// re-scored exactly by the wave itself (verify_drain_queue), then one 64-bit atomicAdd per non-zero bin of the workgroup.  In self
+// re-scored exactly by the wave itself (pair_drain_queue), then one 64-bit atomicAdd per non-zero bin of the workgroup.  In self
 // mode a tile with no pair above the diagonal exits before its first DMA.
 // MM = MATCH_JOIN: threshold search (match_epilogue_join): pairs certainly beyond the threshold are dropped, the rest queued per
-// wave in LDS, re-scored exactly by the wave itself and the accepted ones listed (radius_drain_queue).  Self mode as MATCH_HIST.
+// wave in LDS, re-scored exactly by the wave itself and the accepted ones listed (the same drain, RadiusSink).  Self mode as MATCH_HIST.
 template <typename TT, int MI, int WM, int KS, int MM = MATCH_NONE>
 __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg<MM>::type p) {
   constexpr int NI = 4, WN = KS == 2 ? 2 : 8 / WM;
@@ -572,10 +557,10 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg
   const int mt = L / p.ntiles, nt = L - mt * p.ntiles;
   const int m0 = mt * p.tile_px, mend = min(m0 + p.tile_px, p.M);
   if constexpr (MM == MATCH_HIST) {
-    if (p.h_row0 >= 0 && nt * BN + BN - 1 <= p.h_row0 + m0) return;   // (whole workgroup, before any DMA or barrier)
+    if (p.v.row0 >= 0 && nt * BN + BN - 1 <= p.v.row0 + m0) return;   // (whole workgroup, before any DMA or barrier)
   }
   if constexpr (MM == MATCH_JOIN) {
-    if (p.j_row0 >= 0 && nt * BN + BN - 1 <= p.j_row0 + m0) return;
+    if (p.r.row0 >= 0 && nt * BN + BN - 1 <= p.r.row0 + m0) return;
   }
   const int nst = p.nchunks / KS;            // k-steps this group walks (KS = 2: chunk = grp + 2 * step)
 
@@ -679,37 +664,37 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pp_kernel(const typename PPArg
     __syncthreads();
     if (grp == 1) return;
   }
-  if constexpr (MM == MATCH_HIST) {
-    unsigned* hist = (unsigned*)(smem + VERIFY_LDS_HIST);
-    float* tl = (float*)(smem + VERIFY_LDS_T);
-    const int T = p.h_T, nb = 2 * (T + 1);
-    for (int i = tid; i < nb; i += 512) hist[i] = 0u;
-    for (int i = tid; i < 3 * T; i += 512) tl[(i / T) * VERIFY_MAX_T + i % T] = p.h_tab[i];
-    __syncthreads();
-    const int b_base = m0 + mslice * (MI * 16), n0 = nt * BN + wn * 64;
-    unsigned short* queue = (unsigned short*)(smem + VERIFY_LDS_Q) + wave * VERIFY_QCAP;
-    const int cnt = match_epilogue_hist<MI>(acc, b_base, mend, n0, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.h_lab_a, p.h_lab_b,
-                                            p.h_row0, (const float*)(smem + VERIFY_LDS_LO), (const float*)(smem + VERIFY_LDS_HI),
-                                            hist, queue, T, lane);
-    verify_drain_queue(queue, cnt, b_base, n0, p.h_A, p.h_B, p.h_lab_a, p.h_lab_b, p.m_D, tl, hist, T, lane);
-    if (lane == 0 && cnt) atomicAdd(p.h_rescored, (unsigned long long)cnt);
-    __syncthreads();
-    for (int i = tid; i < nb; i += 512)
-      if (hist[i]) atomicAdd(p.h_hist + i, (unsigned long long)hist[i]);
-    return;
-  } else if constexpr (MM == MATCH_JOIN) {
-    // (every wave is past its last read of the LDS tiles and no DMA is in flight: a queue and an output buffer per wave take their place)
-    const int b_base = m0 + mslice * (MI * 16), n0 = nt * BN + wn * 64;
-    unsigned short* queue = (unsigned short*)smem + wave * VERIFY_QCAP;
-    const int cnt = match_epilogue_join<MI>(acc, b_base, mend, n0, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w, p.j_lab_a, p.j_lab_b,
-                                            p.j_row0, p.j_filter, p.j_hi, queue, lane);
-    int* obuf = (int*)(smem + 8 * VERIFY_QCAP * 2 + wave * RADIUS_OB_BYTES);
-    radius_drain_queue(queue, cnt, b_base, n0, p.j_A, p.j_B, p.m_D, p.j_out, obuf, lane);
-    if (lane == 0 && cnt) atomicAdd(p.j_rescored, (unsigned long long)cnt);
-    return;
-  } else if constexpr (MM != MATCH_NONE) {
-    match_epilogue<MM, MI>(acc, m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w,
-                           p.m_records, lane);
+  if constexpr (MM != MATCH_NONE) {
+    // (every wave is past its last read of the LDS tiles and no DMA is in flight: the modes' tables, queues and buffers take their place)
+    const MatchTile t = {m0 + mslice * (MI * 16), mend, nt * BN + wn * 64, p.m_G, p.m_D, p.M, p.m_stat_a, p.m_stat_w};
+    if constexpr (MM == MATCH_HIST) {
+      unsigned* hist = (unsigned*)(smem + VERIFY_LDS_HIST);
+      float* tl = (float*)(smem + VERIFY_LDS_T);
+      const int T = p.v.T, nb = 2 * (T + 1);
+      for (int i = tid; i < nb; i += 512) hist[i] = 0u;
+      for (int i = tid; i < 3 * T; i += 512) tl[(i / T) * VERIFY_MAX_T + i % T] = p.v.tab[i];
+      __syncthreads();
+      unsigned short* queue = (unsigned short*)(smem + VERIFY_LDS_Q) + wave * VERIFY_QCAP;
+      const int cnt = match_epilogue_hist<MI>(acc, t, p.v, (const float*)(smem + VERIFY_LDS_LO), (const float*)(smem + VERIFY_LDS_HI),
+                                              hist, queue, lane);
+      VerifySink sink = {p.v.lab_a, p.v.lab_b, tl, hist, T};
+      pair_drain_queue(queue, cnt, t.b_base, t.n0, p.v.A, p.v.B, p.m_D, lane, sink);
+      if (lane == 0 && cnt) atomicAdd(p.v.rescored, (unsigned long long)cnt);
+      __syncthreads();
+      for (int i = tid; i < nb; i += 512)
+        if (hist[i]) atomicAdd(p.v.hist + i, (unsigned long long)hist[i]);
+    } else if constexpr (MM == MATCH_JOIN) {
+      unsigned short* queue = (unsigned short*)smem + wave * VERIFY_QCAP;
+      const int cnt = match_epilogue_join<MI>(acc, t, p.r, queue, lane);
+      RadiusSink sink = {p.r.out, (int*)(smem + 8 * VERIFY_QCAP * 2 + wave * RADIUS_OB_BYTES), nullptr, nullptr, 0, 0};
+      pair_drain_queue(queue, cnt, t.b_base, t.n0, p.r.A, p.r.B, p.m_D, lane, sink);
+      sink.flush(lane);
+      if (lane == 0 && cnt) atomicAdd(p.r.rescored, (unsigned long long)cnt);
+    } else if constexpr (MM == MATCH_TOP1) {
+      match_epilogue_records<MI>(acc, t, (MatchRec*)p.m_records, lane);
+    } else {
+      match_epilogue_topr<MI>(acc, t, (MatchRecK*)p.m_records, lane);
+    }
     return;
   }
   conv_epilogue<TT, MI, NI>(acc, smem + (KS == 2 ? q : wave) * (16 * (NI * 64 + 16)), m0 + mslice * (MI * 16), mend, p.Cout,
@@ -981,12 +966,24 @@ int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, 
 // The split-fp16 match GEMM of the packed match entry points (head_match.hip) on the same kernel: probes3 = fp16 [P][3 D] rows
 // (a_hi | a_hi | a_lo), gallery_packed = the G gallery rows (g_hi | g_lo | g_hi) in conv-weight order, padded to Gpad = 256-row
 // groups (match_pack_gallery_kernel), K3 = 3 D; every row carries its own power-of-two scale, whose inverse is the third float of
-// its statistics record.  mode MATCH_TOP1 / MATCH_TOPR: `out` = MatchRec / MatchRecK records [Gpad / 64][P]; MATCH_HIST: `out` =
-// the FrmapVerifyGemm; MATCH_JOIN: `out` = the FrmapRadiusGemm.  1 = launched, 0 = shape not taken, < 0 = error; probes3 == nullptr:
-// plan only.
+// its statistics record.  One typed entry point per mode (match_device.h).
 // ------------------------------------------------------------------------------------------------
-template <int MM>
-static int pp_match_launch(const ConvPlan& q, const typename PPArg<MM>::type& p, hipStream_t st) {
+bool frmap_match_gemm_takes(int P, int G, int D, int T) {
+  const int K3 = 3 * D;
+  return !(K3 % 32 || K3 > 16384 || P <= 0 || G <= 0 || T < 1 || T > VERIFY_MAX_T);
+}
+
+// the plan, the mode's kernel arguments (their PPParams part filled in here, the mode's own by `fill`) and the launch
+template <int MM, typename Fill>
+static int pp_match_launch(const char* what, const FrmapMatchGemm& g, int T, hipStream_t st, Fill&& fill) {
+  FRMAP_REQUIRE(frmap_match_gemm_takes(g.P, g.G, g.D, T), "%s: the match GEMM does not take P=%d G=%d D=%d T=%d", what, g.P, g.G, g.D, T);
+  const int Gpad = (g.G + 255) / 256 * 256;
+  const ConvPlan q = match_gemm_plan(g.P, Gpad);
+  typename PPArg<MM>::type p{};
+  static_cast<PPParams&>(p) = pp_params(q, g.probes3, g.gallery_packed, g.P, 1, 1, 3 * g.D, Gpad, 1, 1, 1);
+  p.ds_stride = 1;
+  p.m_stat_a = g.stat_a; p.m_stat_w = g.stat_w; p.m_G = g.G; p.m_D = g.D;
+  fill(p);
   int lds = q.lds_bytes;   // the mode's queues / output buffers overlay the GEMM's buffers
   if (MM == MATCH_HIST && lds < VERIFY_LDS_GEMM) lds = VERIFY_LDS_GEMM;
   if (MM == MATCH_JOIN && lds < 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES)) lds = 8 * (VERIFY_QCAP * 2 + RADIUS_OB_BYTES);
@@ -994,35 +991,17 @@ static int pp_match_launch(const ConvPlan& q, const typename PPArg<MM>::type& p,
   return pp_launch(kern, q, lds, p, st);
 }
 
-int frmap_match_gemm(int mode, const void* probes3, const void* gallery_packed, const float* stat_a, const float* stat_w, void* out,
-                     int P, int G, int D, hipStream_t st) {
-  const int K3 = 3 * D, Gpad = (G + 255) / 256 * 256;
-  const FrmapVerifyGemm* v = mode == MATCH_HIST ? (const FrmapVerifyGemm*)out : nullptr;
-  if (K3 % 32 || K3 > 16384 || P <= 0 || G <= 0 || (v && (v->T < 1 || v->T > VERIFY_MAX_T))) return 0;
-  if (!probes3) return 1;
-  const ConvPlan q = match_gemm_plan(P, Gpad);
-  PPHistParams p{};   // (MATCH_TOP1 / MATCH_TOPR launch its PPParams part)
-  static_cast<PPParams&>(p) = pp_params(q, probes3, gallery_packed, P, 1, 1, K3, Gpad, 1, 1, 1);
-  p.ds_stride = 1;
-  p.m_stat_a = stat_a; p.m_stat_w = stat_w; p.m_G = G; p.m_D = D;
-  int rc;
-  if (mode == MATCH_JOIN) {
-    const FrmapRadiusGemm* r = (const FrmapRadiusGemm*)out;
-    PPJoinParams pj{};
-    static_cast<PPParams&>(pj) = p;
-    pj.j_A = r->A; pj.j_B = r->B; pj.j_lab_a = r->lab_a; pj.j_lab_b = r->lab_b; pj.j_out = r->out; pj.j_rescored = r->rescored;
-    pj.j_hi = r->hi; pj.j_row0 = r->row0; pj.j_filter = r->filter;
-    rc = pp_match_launch<MATCH_JOIN>(q, pj, st);
-  } else if (v) {
-    p.h_A = v->A; p.h_B = v->B; p.h_lab_a = v->lab_a; p.h_lab_b = v->lab_b; p.h_tab = v->tab; p.h_hist = v->hist;
-    p.h_rescored = v->rescored; p.h_row0 = v->row0; p.h_T = v->T;
-    rc = pp_match_launch<MATCH_HIST>(q, p, st);
-  } else {
-    p.m_records = out;
-    rc = mode == MATCH_TOPR ? pp_match_launch<MATCH_TOPR>(q, static_cast<const PPParams&>(p), st)
-                            : pp_match_launch<MATCH_TOP1>(q, static_cast<const PPParams&>(p), st);
-  }
-  return rc ? rc : 1;
+int frmap_match_gemm_records(const FrmapMatchGemm& g, MatchRec* recs, hipStream_t st) {
+  return pp_match_launch<MATCH_TOP1>("match_gemm_records", g, 1, st, [&](PPParams& p) { p.m_records = recs; });
+}
+int frmap_match_gemm_records(const FrmapMatchGemm& g, MatchRecK* recs, hipStream_t st) {
+  return pp_match_launch<MATCH_TOPR>("match_gemm_records", g, 1, st, [&](PPParams& p) { p.m_records = recs; });
+}
+int frmap_match_gemm_hist(const FrmapMatchGemm& g, const FrmapVerifyGemm& v, hipStream_t st) {
+  return pp_match_launch<MATCH_HIST>("match_gemm_hist", g, v.T, st, [&](PPHistParams& p) { p.v = v; });
+}
+int frmap_match_gemm_join(const FrmapMatchGemm& g, const FrmapRadiusGemm& r, hipStream_t st) {
+  return pp_match_launch<MATCH_JOIN>("match_gemm_join", g, 1, st, [&](PPJoinParams& p) { p.r = r; });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,7 +14,11 @@
 // (pitch 33 floats -> conflict-free column reads), wave w owns columns [32w, 32w+32) and both
 // 32-row halves.  fp32 in, fp32 accumulate: bitwise an fmaf chain, so arg-min / arg-max decisions
 // are taken on true fp32 scores.
-#include "frmap_common.h"
+//
+// The matcher's device code (records, bounds, the exact re-score, the pair feed of the verification counts and the threshold search)
+// and its interface to the split-fp16 match GEMM of conv_pp.hip are in match_device.h; the workspace of every match operation is
+// laid out by one function here (top1_ws, topk_ws, verify_ws, radius_ws), which its *_workspace_bytes and its entry points share.
+#include "match_device.h"
 #include <type_traits>
 
 enum { MODE_LINEAR = 0, MODE_COS = 1, MODE_ARC = 2, MODE_DIST = 3 };
@@ -50,11 +54,11 @@ __device__ __forceinline__ float f32_unordered(unsigned int k) {
   return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
-// min (or max) of `v` over the 32 lanes of this lane's half-wave, and the LOWEST lane of the half holding it.
-// Four DPP steps inside each 16-lane row (quad xor 1, xor 2, half-mirror, mirror), one cross-row exchange,
+// min (or max) of `v` over the 32 lanes of this lane's half-wave (half_wave_reduce), and the LOWEST lane of the half holding it
+// (half_wave_best).  Four DPP steps inside each 16-lane row (quad xor 1, xor 2, half-mirror, mirror), one cross-row exchange,
 // then a ballot + find-first: ~10 instructions per reduced row where a 64-bit (value, index) butterfly took ~30.
 template <bool MAX>
-__device__ __forceinline__ float half_wave_best(float v, int lk, int& first_li) {
+__device__ __forceinline__ float half_wave_reduce(float v) {
   auto comb = [](float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); };
   auto dpp = [](float x, auto ctrl) {
     const int i = __builtin_bit_cast(int, x);
@@ -65,26 +69,18 @@ __device__ __forceinline__ float half_wave_best(float v, int lk, int& first_li) 
   m = comb(m, dpp(m, std::integral_constant<int, 0x4E>{}));   // quad_perm [2,3,0,1]
   m = comb(m, dpp(m, std::integral_constant<int, 0x141>{}));  // row_half_mirror
   m = comb(m, dpp(m, std::integral_constant<int, 0x140>{}));  // row_mirror
-  m = comb(m, __shfl_xor(m, 16, 64));
+  return comb(m, __shfl_xor(m, 16, 64));
+}
+template <bool MAX>
+__device__ __forceinline__ float half_wave_best(float v, int lk, int& first_li) {
+  const float m = half_wave_reduce<MAX>(v);
   const unsigned long long hit = __ballot(v == m);
   const unsigned half = lk ? (unsigned)(hit >> 32) : (unsigned)hit;
   first_li = __ffs(half) - 1;  // >= 0: the lane(s) that contributed m are in the mask
   return m;
 }
-
-// plain minimum over the 32 lanes of this lane's half-wave (same DPP ladder, no index)
-__device__ __forceinline__ float half_wave_min(float v) {
-  auto dpp = [](float x, auto ctrl) {
-    const int i = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, decltype(ctrl)::value, 0xF, 0xF, false));
-  };
-  float m = v;
-  m = fminf(m, dpp(m, std::integral_constant<int, 0xB1>{}));
-  m = fminf(m, dpp(m, std::integral_constant<int, 0x4E>{}));
-  m = fminf(m, dpp(m, std::integral_constant<int, 0x141>{}));
-  m = fminf(m, dpp(m, std::integral_constant<int, 0x140>{}));
-  return fminf(m, __shfl_xor(m, 16, 64));
-}
+// plain minimum over the 32 lanes of this lane's half-wave (no index)
+__device__ __forceinline__ float half_wave_min(float v) { return half_wave_reduce<false>(v); }
 
 template <int MODE>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restrict__ A, const float* __restrict__ W,
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
         if (valid) {
           const float eps = 1e-6f, kf = (float)K, keps = kf * eps * eps;
           const float sa2 = ep.stat_a[2 * b];
-          const float d2 = sa2 + wn2 - 2.f * dot + 2.f * eps * (ep.stat_a[2 * b + 1] - wsum) + keps;
+          const float d2 = match_expanded_d2(sa2, ep.stat_a[2 * b + 1], wn2, wsum, dot, keps);
           const float dl = match_kappa(K) * (match_band(sa2, kf) + wband + keps);
           L = d2 - dl; U = d2 + dl;
         }
@@ -296,13 +292,21 @@ __global__ void fill_u64_kernel(unsigned long long* p, int n, unsigned long long
   if (i < n) p[i] = v;
 }
 
-// match_exact_d2 (the exact distance every re-score uses) lives in frmap_common.h.
+// the end of every top-1 match: row `besti` (-1: none) at distance d, the row or -1 under the threshold, and both packed
+__device__ __forceinline__ void match_write_top1(int b, int besti, float d, float thresh, int32_t* __restrict__ idx_out,
+                                                 float* __restrict__ dist_out, int32_t* __restrict__ id_thr_out,
+                                                 int32_t* __restrict__ packed_out) {
+  idx_out[b] = besti; dist_out[b] = d;
+  const int idt = (besti >= 0 && d <= thresh) ? besti : -1;
+  if (id_thr_out) id_thr_out[b] = idt;
+  if (packed_out) { packed_out[2 * b] = idt; packed_out[2 * b + 1] = __float_as_int(d); }
+}
 
-// One wave per probe.  Reads the probe's candidate records (frmap_common.h: MatchRec [nslots][B], slot = slot_w consecutive
+// One wave per probe.  Reads the probe's candidate records (match_device.h: MatchRec [nslots][B], slot = slot_w consecutive
 // gallery rows), takes ug = min over slots of `up`, and re-scores with the exact distance every slot whose lo1 <= ug: the
 // slot's single candidate row when its second-best bound lies outside the band, every row of the slot otherwise.  Slots and
 // rows are visited in ascending order and only a strictly smaller distance replaces the best one, so the result is the
-// FIRST row attaining the minimum of the exact distance: compare_faces' loop (/root/reference/src/app.py:58-63).
+// FIRST row attaining the minimum of the exact distance: compare_faces' loop (app.py:58-63).
 __global__ void match_finalize_rec_kernel(const float* __restrict__ emb, const float* __restrict__ gal,
                                           const MatchRec* __restrict__ recs, int nslots, int slot_w,
                                           int32_t* __restrict__ idx_out, float* __restrict__ dist_out,
@@ -338,13 +342,8 @@ __global__ void match_finalize_rec_kernel(const float* __restrict__ emb, const f
       }
     }
   }
-  if (lane == 0) {
-    const float d = besti >= 0 ? (float)sqrt(best) : INFINITY;
-    idx_out[b] = besti; dist_out[b] = d;
-    const int idt = (besti >= 0 && d <= thresh) ? besti : -1;
-    if (id_thr_out) id_thr_out[b] = idt;
-    if (packed_out) { packed_out[2 * b] = idt; packed_out[2 * b + 1] = __float_as_int(d); }
-  }
+  if (lane == 0)
+    match_write_top1(b, besti, besti >= 0 ? (float)sqrt(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
 }
 
 // Small galleries (the demo's handful of enrolled faces, the 36-ID benchmark gallery): one wave per
@@ -388,13 +387,7 @@ __global__ __launch_bounds__(256) void match_small_kernel(const float* __restric
     for (int w = 1; w < 4; ++w)
       if (s_best[w] < best || (s_best[w] == best && s_idx[w] < besti)) { best = s_best[w]; besti = s_idx[w]; }
     const bool any = besti != 0x7FFFFFFF;
-    const float d = any ? sqrtf(best) : INFINITY;
-    const int bi = any ? besti : -1;
-    idx_out[b] = bi;
-    dist_out[b] = d;
-    const int idt = (any && d <= thresh) ? bi : -1;
-    if (id_thr_out) id_thr_out[b] = idt;
-    if (packed_out) { packed_out[2 * b] = idt; packed_out[2 * b + 1] = __float_as_int(d); }
+    match_write_top1(b, any ? besti : -1, any ? sqrtf(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
   }
 }
 
@@ -520,13 +513,7 @@ __global__ __launch_bounds__(256) void gap_norm_match_kernel(const typename TT::
     for (int w = 1; w < 4; ++w)
       if (s_red[w] < best || (s_red[w] == best && s_idx[w] < besti)) { best = s_red[w]; besti = s_idx[w]; }
     const bool any = besti != 0x7FFFFFFF;
-    const float d = any ? sqrtf(best) : INFINITY;
-    const int bi = any ? besti : -1;
-    idx_out[b] = bi;
-    dist_out[b] = d;
-    const int idt = (any && d <= thresh) ? bi : -1;
-    if (id_thr_out) id_thr_out[b] = idt;
-    if (packed_out) { packed_out[2 * b] = idt; packed_out[2 * b + 1] = __float_as_int(d); }
+    match_write_top1(b, any ? besti : -1, any ? sqrtf(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
   }
 }
 
@@ -850,6 +837,45 @@ extern "C" int frmap_pairwise_distance(const float* a, const float* b, float* di
   return 0;
 }
 
+static size_t align256_sz(size_t n) { return (n + 255) / 256 * 256; }
+static size_t ws_count(int n) { return n > 0 ? (size_t)n : 0; }
+
+// workspace of frmap_match_top1 (the fp32 GEMM: slots of 32 rows, one per wave's columns; statistics [.][2]):
+//   records [4 * ceil(G / 128)][B] | probe statistics [B][2] | gallery statistics [G][2]
+// and of frmap_match_top1_packed (slots of 64 rows; Gpad = G rounded up to 256: the GEMM's padded rows write never-candidate records):
+//   records [Gpad / 64][B] | probe statistics [B][4]
+struct Top1Ws {
+  MatchRec* recs;
+  float* stat_a;
+  float* stat_w;   // (unpacked only)
+  int nslots, slot_w;
+  char* end;
+};
+static Top1Ws top1_ws(void* ws, int B, int G, bool packed) {
+  const size_t b = ws_count(B), g = ws_count(G);
+  Top1Ws w;
+  w.slot_w = packed ? 64 : 32;
+  w.nslots = (int)(packed ? (g + 255) / 256 * 4 : (g + 127) / 128 * 4);
+  char* c = (char*)ws;
+  w.recs = (MatchRec*)c; c += sizeof(MatchRec) * b * w.nslots;
+  w.stat_a = (float*)c; c += (packed ? 16 : 8) * b;
+  w.stat_w = (float*)c; c += packed ? 0 : 8 * g;
+  w.end = c;
+  return w;
+}
+// one size for both: the unpacked layout never has fewer slots, and 8 B bytes more make room for the packed one's wider statistics
+extern "C" size_t frmap_match_workspace_bytes(int B, int G) {
+  return (size_t)(top1_ws(nullptr, B, G, false).end - (char*)nullptr) + 8 * ws_count(B) + 256;
+}
+
+static int match_finalize_rec(const float* emb, const float* gallery, const Top1Ws& w, int32_t* idx_out, float* dist_out,
+                              int32_t* id_or_unknown_out, int32_t* packed_out, float thresh, int B, int G, int D, hipStream_t st) {
+  hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)w.recs, w.nslots,
+                     w.slot_w, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t* idx_out, float* dist_out,
                                 int32_t* id_or_unknown_out, int32_t* packed_out, float thresh, void* workspace,
                                 int B, int G, int D, void* stream) {
@@ -863,27 +889,15 @@ extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t*
     FRMAP_LAUNCH_CHECK();
     return 0;
   }
-  if (G <= 0) {
-    hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)nullptr, 0, 32,
-                       idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, 0, D);
-    FRMAP_LAUNCH_CHECK();
-    return 0;
+  const Top1Ws w = top1_ws(G > 0 ? workspace : nullptr, B, G, false);   // (G == 0: no slots, no record is read)
+  if (G > 0) {
+    hipLaunchKernelGGL(row_stats_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, w.stat_a, B, D, 1, 0.f);
+    hipLaunchKernelGGL(row_stats_kernel, dim3(waves_blocks(G)), dim3(256), 0, st, gallery, w.stat_w, G, D, 1, 0.f);
+    GemmEpi ep = {};
+    ep.stat_a = w.stat_a; ep.stat_w = w.stat_w; ep.recs = w.recs;
+    if (int rc = launch_gemm<MODE_DIST>(emb, gallery, B, G, D, ep, st)) return rc;
   }
-  // workspace (frmap_match_workspace_bytes): records [4 * ceil(G / 128)][B] | probe statistics [B][2] | gallery statistics [G][2]
-  const int nslots = 4 * ((G + 127) / 128);
-  MatchRec* recs = (MatchRec*)workspace;
-  float* stat_a = (float*)(recs + (size_t)nslots * B);
-  float* stat_w = stat_a + 2 * (size_t)B;
-  hipLaunchKernelGGL(row_stats_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, stat_a, B, D, 1, 0.f);
-  hipLaunchKernelGGL(row_stats_kernel, dim3(waves_blocks(G)), dim3(256), 0, st, gallery, stat_w, G, D, 1, 0.f);
-  GemmEpi ep = {};
-  ep.stat_a = stat_a; ep.stat_w = stat_w; ep.recs = recs;
-  int rc = launch_gemm<MODE_DIST>(emb, gallery, B, G, D, ep, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)recs, nslots, 32,
-                     idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
+  return match_finalize_rec(emb, gallery, w, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -897,7 +911,7 @@ extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t*
 // ------------------------------------------------------------------------------------------------
 // Each row gets its own power-of-two scale S (largest |x| of the row lands in [2^13, 2^14): nothing overflows fp16, lo stays
 // out of the fp16 subnormals for every element within 2^-11 of the row maximum, and scaling by a power of two is exact);
-// statistics record of a row: (sum x^2, sum x, 1 / S, band(x) = the row's share of the expanded distance's error bound, frmap_common.h).
+// statistics record of a row: (sum x^2, sum x, 1 / S, band(x) = the row's share of the expanded distance's error bound, match_device.h).
 __device__ __forceinline__ float match_row_scale(float amax) {
   if (!(amax > 0.f) || isinf(amax)) return 1.f;
   int e;
@@ -983,7 +997,7 @@ extern "C" int frmap_match_pack_gallery(const float* gallery, void* packed_out, 
   return match_pack_rows(gallery, packed_out, stat_w_out, 0, G, G, D, (hipStream_t)stream);
 }
 
-// incremental enrolment (/root/reference/src/app.py:428-436 appends one identity): rows [row_lo, row_hi) of the gallery were
+// incremental enrolment (app.py:428-436 appends one identity): rows [row_lo, row_hi) of the gallery were
 // written (appended: row_hi == G, the new row count; or edited in place); only their statistics and 64-row tiles are re-packed.
 // packed_out / stat_w_out must have been sized for at least G rows (frmap_match_gallery_pack_bytes(capacity, D), [capacity][4]).
 extern "C" int frmap_match_pack_gallery_rows(const float* gallery, void* packed_out, float* stat_w_out, int row_lo, int row_hi,
@@ -994,14 +1008,14 @@ extern "C" int frmap_match_pack_gallery_rows(const float* gallery, void* packed_
   return match_pack_rows(gallery, packed_out, stat_w_out, row_lo, row_hi, G, D, (hipStream_t)stream);
 }
 
-// The packed entry points' GEMM step: probe statistics [P][4] and fp16 split [P][3 D] (match_row_prep_kernel), then the split-fp16
-// GEMM in `mode` (frmap_match_gemm).  1 = launched, < 0 = error, 0 = the GEMM does not take the shape and nothing was launched:
-// the entry point then answers as its unpacked twin does, from the workspace it was given (same exact re-score, same answer).
-static int match_packed_gemm(int mode, const float* a, const void* packed, const float* stat_w, float* stat_a, void* split, void* out,
-                             int P, int G, int D, hipStream_t st) {
-  if (!frmap_match_gemm(mode, nullptr, packed, stat_a, stat_w, out, P, G, D, st)) return 0;
-  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(P)), dim3(256), 0, st, a, stat_a, (_Float16*)split, P, D);
-  return frmap_match_gemm(mode, split, packed, stat_a, stat_w, out, P, G, D, st);
+// The packed entry points' first step: whether the split-fp16 GEMM takes the shape and, if so, the probe statistics g.stat_a [P][4]
+// and fp16 split g.probes3 [P][3 D] (match_row_prep_kernel).  true: the caller launches its mode's GEMM (frmap_match_gemm_*);
+// false: nothing was launched and the entry point answers as its unpacked twin does, from the workspace it was given (same exact
+// re-score, same answer).
+static bool match_packed_prep(const float* a, const FrmapMatchGemm& g, hipStream_t st, int T = 1) {
+  if (!frmap_match_gemm_takes(g.P, g.G, g.D, T)) return false;
+  hipLaunchKernelGGL(match_row_prep_kernel, dim3(waves_blocks(g.P)), dim3(256), 0, st, a, (float*)g.stat_a, (_Float16*)g.probes3, g.P, g.D);
+  return true;
 }
 
 // frmap_match_top1 for a prepared gallery (same outputs, same contract).  workspace: frmap_match_workspace_bytes(B, G)
@@ -1012,22 +1026,12 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
   FRMAP_REQUIRE(emb && gallery && gallery_packed && stat_w && idx_out && dist_out && workspace && probe_split, "match_top1_packed: null pointer");
   FRMAP_REQUIRE(B > 0 && G > 0 && D > 0 && D % 32 == 0, "match_top1_packed: bad shape B=%d G=%d D=%d", B, G, D);
   hipStream_t st = (hipStream_t)stream;
-  // workspace: records [Gpad / 64][B] (Gpad = G rounded up to 256: the GEMM's padded rows write never-candidate records) | statistics [B][4]
-  const int nslots = (G + 255) / 256 * 4;
-  MatchRec* recs = (MatchRec*)workspace;
-  float* stat_a = (float*)(recs + (size_t)nslots * B);
-  const int rc = match_packed_gemm(MATCH_TOP1, emb, gallery_packed, stat_w, stat_a, probe_split, recs, B, G, D, st);
-  if (rc < 0) return rc;
-  if (!rc) return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, workspace, B, G, D, stream);
-  hipLaunchKernelGGL(match_finalize_rec_kernel, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, (const MatchRec*)recs, nslots, 64,
-                     idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" size_t frmap_match_workspace_bytes(int B, int G) {
-  const size_t b = B > 0 ? (size_t)B : 0, g = G > 0 ? (size_t)G : 0;
-  return 16 * b * (4 * ((g + 127) / 128)) + 16 * b + 8 * g + 256;
+  const Top1Ws w = top1_ws(workspace, B, G, true);
+  const FrmapMatchGemm g = {probe_split, gallery_packed, w.stat_a, stat_w, B, G, D};
+  if (!match_packed_prep(emb, g, st))
+    return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, workspace, B, G, D, stream);
+  if (int rc = frmap_match_gemm_records(g, w.recs, st)) return rc;
+  return match_finalize_rec(emb, gallery, w, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, B, G, D, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1093,7 +1097,7 @@ __global__ void match_topk_scan_kernel(const float* __restrict__ emb, const floa
   topk_write<BY_LABEL>(ld, lr, ll, b, k, lane, idx_out, dist_out, label_out);
 }
 
-// Prepared galleries: the records of conv1x1_pp_kernel<..., MATCH_TOPR> (frmap_common.h: MatchRecK [nslots][B]).
+// Prepared galleries: the records of conv1x1_pp_kernel<..., MATCH_TOPR> (match_device.h: MatchRecK [nslots][B]).
 //   tau = the k-th smallest listed U (identity mode: the k-th smallest, over distinct labels, of the per-label min of listed U);
 //         +inf when the records name fewer than k rows (labels).
 //   re-score with match_exact_d2 every listed row with L <= tau, and every row of a slot whose rest bound is <= tau.
@@ -1175,16 +1179,30 @@ __global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
   if (i < n) p[i] = v;
 }
 
-static size_t align256_sz(size_t n) { return (n + 255) / 256 * 256; }
-
 // workspace of frmap_match_topk[_packed]: [ top-R records [Gpad / 64][B] | probe statistics [B][4] ] or, for k = 1 in entry mode,
 // the top-1 path's own workspace (frmap_match_workspace_bytes) - whichever is larger - then the probes' fp16 split [B][3 D].
+struct TopkWs {
+  MatchRecK* recs;
+  float* stat_a;
+  void* split;
+  int nslots;
+  char* end;
+};
+static TopkWs topk_ws(void* ws, int B, int G, int D) {
+  const size_t b = ws_count(B), g = ws_count(G), d = ws_count(D);
+  TopkWs w;
+  w.nslots = (int)((g + 255) / 256 * 4);
+  char* c = (char*)ws;
+  w.recs = (MatchRecK*)c; c += align256_sz(sizeof(MatchRecK) * b * w.nslots);
+  w.stat_a = (float*)c; c += align256_sz(16 * b);
+  char* top1_end = (char*)ws + align256_sz(frmap_match_workspace_bytes(B, G));
+  w.split = c > top1_end ? c : top1_end;
+  w.end = (char*)w.split + align256_sz(2 * b * 3 * d);
+  return w;
+}
 extern "C" size_t frmap_match_topk_workspace_bytes(int B, int G, int D, int k) {
   (void)k;
-  const size_t b = B > 0 ? (size_t)B : 0, g = G > 0 ? (size_t)G : 0, d = D > 0 ? (size_t)D : 0;
-  const size_t recs = align256_sz(sizeof(MatchRecK) * b * ((g + 255) / 256 * 4)) + align256_sz(16 * b);
-  const size_t top1 = align256_sz(frmap_match_workspace_bytes(B, G));
-  return (recs > top1 ? recs : top1) + align256_sz(2 * b * 3 * d) + 256;
+  return (size_t)(topk_ws(nullptr, B, G, D).end - (char*)nullptr) + 256;
 }
 
 static int topk_check(const char* what, const float* emb, const float* gallery, int32_t* idx_out, float* dist_out, void* workspace,
@@ -1228,26 +1246,22 @@ extern "C" int frmap_match_topk_packed(const float* emb, const float* gallery, c
   FRMAP_REQUIRE(gallery_packed && stat_w, "match_topk_packed: null pointer");
   FRMAP_REQUIRE(G > 0 && D % 32 == 0, "match_topk_packed: bad shape B=%d G=%d D=%d (G > 0, D %% 32 == 0)", B, G, D);
   hipStream_t st = (hipStream_t)stream;
-  const size_t recs_b = align256_sz(sizeof(MatchRecK) * (size_t)B * ((G + 255) / 256 * 4));
-  const size_t top1_b = align256_sz(frmap_match_workspace_bytes(B, G));
-  void* split = (char*)workspace + ((recs_b + align256_sz(16 * (size_t)B)) > top1_b ? recs_b + align256_sz(16 * (size_t)B) : top1_b);
+  const TopkWs w = topk_ws(workspace, B, G, D);
   if (k == 1 && !labels) {
     const int rc = frmap_match_top1_packed(emb, gallery, gallery_packed, stat_w, idx_out, dist_out, nullptr, nullptr, INFINITY,
-                                           workspace, split, B, G, D, stream);
+                                           workspace, w.split, B, G, D, stream);
     return rc ? rc : frmap_match_topk_fill_labels(label_out, B, st);
   }
-  const int nslots = (G + 255) / 256 * 4;
-  MatchRecK* recs = (MatchRecK*)workspace;
-  float* stat_a = (float*)((char*)workspace + recs_b);
-  const int rc = match_packed_gemm(MATCH_TOPR, emb, gallery_packed, stat_w, stat_a, split, recs, B, G, D, st);
-  if (rc < 0) return rc;
-  if (!rc) return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, workspace, B, G, D, k, stream);
+  const FrmapMatchGemm g = {w.split, gallery_packed, w.stat_a, stat_w, B, G, D};
+  if (!match_packed_prep(emb, g, st))
+    return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, workspace, B, G, D, k, stream);
+  if (int rc = frmap_match_gemm_records(g, w.recs, st)) return rc;
   if (labels)
     hipLaunchKernelGGL(match_topk_finalize_kernel<true>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels,
-                       (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
+                       (const MatchRecK*)w.recs, w.nslots, idx_out, dist_out, label_out, B, G, D, k);
   else
     hipLaunchKernelGGL(match_topk_finalize_kernel<false>, dim3(waves_blocks(B)), dim3(256), 0, st, emb, gallery, labels,
-                       (const MatchRecK*)recs, nslots, idx_out, dist_out, label_out, B, G, D, k);
+                       (const MatchRecK*)w.recs, w.nslots, idx_out, dist_out, label_out, B, G, D, k);
   FRMAP_LAUNCH_CHECK();
   return 0;
 }
@@ -1266,16 +1280,23 @@ struct VerifyWs {
   float* tab;
   float* stat_a;
   void* split;
+  char* end;
 };
 static VerifyWs verify_ws(void* ws, int P, int D, int T) {
+  const size_t p = ws_count(P), d = ws_count(D), t = T < 1 ? 1 : T > VERIFY_MAX_T ? VERIFY_MAX_T : (size_t)T;
   VerifyWs w;
   char* c = (char*)ws;
-  w.hist = (unsigned long long*)c; c += align256_sz(16 * (size_t)(T + 1));
+  w.hist = (unsigned long long*)c; c += align256_sz(16 * (t + 1));
   w.misc = (unsigned long long*)c; c += 256;
-  w.tab = (float*)c; c += align256_sz(12 * (size_t)T);
-  w.stat_a = (float*)c; c += align256_sz(16 * (size_t)P);
-  w.split = c;
+  w.tab = (float*)c; c += align256_sz(12 * t);
+  w.stat_a = (float*)c; c += align256_sz(16 * p);
+  w.split = c; c += align256_sz(6 * p * d);
+  w.end = c;
   return w;
+}
+extern "C" size_t frmap_verify_workspace_bytes(int P, int Q, int D, int T) {
+  (void)Q;
+  return (size_t)(verify_ws(nullptr, P, D, T).end - (char*)nullptr) + 256;
 }
 
 // one workgroup: zero the bins, check the thresholds (finite, >= 0, strictly ascending) and bracket each one in d2 space:
@@ -1301,42 +1322,22 @@ __global__ __launch_bounds__(1024) void verify_prep_kernel(const float* __restri
   if (tid == 0) { misc[0] = 0ull; misc[1] = (unsigned long long)bad; }
 }
 
-// Exact scan: one workgroup = VS_PB rows of A x VS_QB rows of B; each wave scores 8 pairs at a time with match_exact_d2's arithmetic
-// and bins them in the workgroup's LDS histogram.
-constexpr int VS_PB = 8, VS_QB = 512;
+// Exact scan: one workgroup = VS_PB rows of A x VS_QB rows of B; each wave scores PAIR_NB pairs at a time with match_exact_d2's
+// arithmetic (pair_scan_block) and bins them in the workgroup's LDS histogram.
 __global__ __launch_bounds__(256) void verify_scan_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                           const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b,
                                                           int P, int Q, int D, int row0, const float* __restrict__ tab, int T,
                                                           unsigned long long* __restrict__ hist_g) {
   __shared__ unsigned hist[2 * (VERIFY_MAX_T + 1)];
   __shared__ float tl[VERIFY_MAX_T];
-  const int i0 = blockIdx.x * VS_PB, j0 = blockIdx.y * VS_QB;
-  const int jlast = min(j0 + VS_QB, Q) - 1;
-  if (row0 >= 0 && jlast <= row0 + i0) return;     // self mode: nothing above the diagonal here
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (pair_block_below_diagonal(blockIdx.x * VS_PB, blockIdx.y * VS_QB, Q, row0)) return;
+  const int tid = threadIdx.x;
   const int nb = 2 * (T + 1);
   for (int i = tid; i < nb; i += 256) hist[i] = 0u;
   for (int i = tid; i < T; i += 256) tl[i] = tab[i];
   __syncthreads();
-  constexpr int NB = 8;
-  for (int base = wave * NB; base < VS_PB * VS_QB; base += 4 * NB) {
-    const float* pa[NB];
-    const float* pb[NB];
-    bool valid[NB], gen[NB], any = false;
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const int i = i0 + (base + q) / VS_QB, j = j0 + (base + q) % VS_QB;
-      valid[q] = i < P && j < Q && (row0 < 0 || row0 + i < j);
-      any |= valid[q];
-      const int ic = min(i, P - 1), jc = min(j, Q - 1);
-      pa[q] = A + (size_t)ic * D; pb[q] = B + (size_t)jc * D;
-      gen[q] = lab_a[ic] == lab_b[jc];
-    }
-    if (!any) continue;                               // (wave-uniform)
-    double d2[NB];
-    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
-    verify_bin_pairs<NB>(d2, valid, gen, tl, hist, T, lane);
-  }
+  VerifySink sink = {lab_a, lab_b, tl, hist, T};
+  pair_scan_block(A, B, P, Q, D, row0, sink);
   __syncthreads();
   for (int i = tid; i < nb; i += 256)
     if (hist[i]) atomicAdd(hist_g + i, (unsigned long long)hist[i]);
@@ -1366,13 +1367,6 @@ __global__ __launch_bounds__(1024) void verify_finalize_kernel(const unsigned lo
   if (k0 < T) accepted[(size_t)c * T + k0] = bad ? ~0ull : before + v0;
   if (k0 + 1 < T) accepted[(size_t)c * T + k0 + 1] = bad ? ~0ull : before + v0 + v1;
   if (c == 0 && tid == 0 && rescored_out) *rescored_out = bad ? ~0ull : misc[0];
-}
-
-extern "C" size_t frmap_verify_workspace_bytes(int P, int Q, int D, int T) {
-  (void)Q;
-  const size_t p = P > 0 ? (size_t)P : 0, d = D > 0 ? (size_t)D : 0;
-  const size_t t = T < 1 ? 1 : T > VERIFY_MAX_T ? VERIFY_MAX_T : (size_t)T;
-  return align256_sz(16 * (t + 1)) + 256 + align256_sz(12 * t) + align256_sz(16 * p) + align256_sz(6 * p * d) + 256;
 }
 
 static int verify_check(const char* what, const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q,
@@ -1426,11 +1420,13 @@ extern "C" int frmap_verify_counts_packed(const float* a, const int32_t* label_a
   hipStream_t st = (hipStream_t)stream;
   const VerifyWs w = verify_ws(workspace, P, D, T);
   hipLaunchKernelGGL(verify_prep_kernel, dim3(1), dim3(1024), 0, st, thresholds, T, w.tab, w.hist, w.misc);
-  FrmapVerifyGemm v = {a, b, label_a, label_b, w.tab, w.hist, w.misc, a_row0, T};
-  const int taken = match_packed_gemm(MATCH_HIST, a, b_packed, stat_w, w.stat_a, w.split, &v, P, Q, D, st);
-  if (taken < 0) return taken;
-  if (!taken)
-    if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) return rc;
+  const FrmapMatchGemm g = {w.split, b_packed, w.stat_a, stat_w, P, Q, D};
+  if (match_packed_prep(a, g, st, T)) {
+    const FrmapVerifyGemm v = {a, b, label_a, label_b, w.tab, w.hist, w.misc, a_row0, T};
+    if (int rc = frmap_match_gemm_hist(g, v, st)) return rc;
+  } else if (int rc = verify_scan(a, label_a, P, b, label_b, Q, D, a_row0, w, T, st)) {
+    return rc;
+  }
   return verify_finish(w, T, accepted_out, rescored_out, st);
 }
 
@@ -1445,14 +1441,21 @@ struct RadiusWs {
   unsigned long long* misc;
   float* stat_a;
   void* split;
+  char* end;
 };
-static RadiusWs radius_ws(void* ws, int P) {
+static RadiusWs radius_ws(void* ws, int P, int D) {
+  const size_t p = ws_count(P), d = ws_count(D);
   RadiusWs w;
   char* c = (char*)ws;
   w.misc = (unsigned long long*)c; c += 256;
-  w.stat_a = (float*)c; c += align256_sz(16 * (size_t)P);
-  w.split = c;
+  w.stat_a = (float*)c; c += align256_sz(16 * p);
+  w.split = c; c += align256_sz(6 * p * d);
+  w.end = c;
   return w;
+}
+extern "C" size_t frmap_match_radius_workspace_bytes(int P, int Q, int D) {
+  (void)Q;
+  return (size_t)(radius_ws(nullptr, P, D).end - (char*)nullptr) + 256;
 }
 
 __global__ void radius_prep_kernel(int32_t* __restrict__ count, int P, unsigned long long* __restrict__ total,
@@ -1462,46 +1465,16 @@ __global__ void radius_prep_kernel(int32_t* __restrict__ count, int P, unsigned 
   if (i0 == 0) { *total = 0ull; *rescored = 0ull; }
 }
 
-// Exact scan, the shape of verify_scan_kernel: one workgroup = VS_PB rows of A x VS_QB rows of B, each wave scores 8 pairs at a time
-// with match_exact_d2's arithmetic and lists the accepted ones (radius_emit, the GEMM path's own emit step).
+// Exact scan, the shape of verify_scan_kernel (the same pair_scan_block): the accepted pairs are listed by RadiusSink, the GEMM
+// path's own emit step.
 __global__ __launch_bounds__(256) void radius_scan_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                           const int32_t* __restrict__ lab_a, const int32_t* __restrict__ lab_b,
                                                           int P, int Q, int D, int row0, int filter, RadiusOut o) {
-  const int i0 = blockIdx.x * VS_PB, j0 = blockIdx.y * VS_QB;
-  const int jlast = min(j0 + VS_QB, Q) - 1;
-  if (row0 >= 0 && jlast <= row0 + i0) return;     // self mode: nothing above the diagonal here
+  if (pair_block_below_diagonal(blockIdx.x * VS_PB, blockIdx.y * VS_QB, Q, row0)) return;
   __shared__ int s_obuf[4][3 * RADIUS_OB];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int* obuf = s_obuf[wave];
-  int w = 0;
-  constexpr int NB = 8;
-  for (int base = wave * NB; base < VS_PB * VS_QB; base += 4 * NB) {
-    const float* pa[NB];
-    const float* pb[NB];
-    bool valid[NB], any = false;
-    int pi[NB], pj[NB];
-#pragma unroll
-    for (int q = 0; q < NB; ++q) {
-      const int i = i0 + (base + q) / VS_QB, j = j0 + (base + q) % VS_QB;
-      valid[q] = i < P && j < Q && (row0 < 0 || row0 + i < j);
-      const int ic = min(i, P - 1), jc = min(j, Q - 1);
-      if (filter && valid[q]) valid[q] = radius_filter_ok(filter, lab_a[ic], lab_b[jc]);
-      any |= valid[q];
-      pi[q] = ic; pj[q] = jc;
-      pa[q] = A + (size_t)ic * D; pb[q] = B + (size_t)jc * D;
-    }
-    if (!any) continue;                               // (wave-uniform)
-    double d2[NB];
-    match_exact_d2_n<NB>(pa, pb, D, lane, d2);
-    radius_emit<NB>(d2, valid, pi, pj, o, obuf, w, lane);
-  }
-  radius_flush(o, obuf, w, lane);
-}
-
-extern "C" size_t frmap_match_radius_workspace_bytes(int P, int Q, int D) {
-  (void)Q;
-  const size_t p = P > 0 ? (size_t)P : 0, d = D > 0 ? (size_t)D : 0;
-  return 256 + align256_sz(16 * p) + align256_sz(6 * p * d) + 256;
+  RadiusSink sink = {o, s_obuf[threadIdx.x >> 6], lab_a, lab_b, filter, 0};
+  pair_scan_block(A, B, P, Q, D, row0, sink);
+  sink.flush(threadIdx.x & 63);
 }
 
 static int radius_check(const char* what, const float* a, const int32_t* label_a, int P, const float* b, const int32_t* label_b, int Q,
@@ -1543,7 +1516,7 @@ extern "C" int frmap_match_radius(const float* a, const int32_t* label_a, int P,
                             dist_out, capacity, workspace))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const RadiusWs w = radius_ws(workspace, P);
+  const RadiusWs w = radius_ws(workspace, P, D);
   if (int rc = radius_prep(count_out, P, total_out, rescored_out ? (unsigned long long*)rescored_out : w.misc, st)) return rc;
   const RadiusOut o = {count_out, (unsigned long long*)total_out, pair_out, dist_out, capacity, thresh};
   return radius_scan(a, label_a, P, b, label_b, Q, D, a_row0, pair_filter, o, st);
@@ -1559,7 +1532,7 @@ extern "C" int frmap_match_radius_packed(const float* a, const int32_t* label_a,
   FRMAP_REQUIRE(b_packed && stat_w, "match_radius_packed: null pointer");
   FRMAP_REQUIRE(Q > 0 && D % 32 == 0, "match_radius_packed: bad shape Q=%d D=%d (Q > 0, D %% 32 == 0)", Q, D);
   hipStream_t st = (hipStream_t)stream;
-  const RadiusWs w = radius_ws(workspace, P);
+  const RadiusWs w = radius_ws(workspace, P, D);
   unsigned long long* resc = rescored_out ? (unsigned long long*)rescored_out : w.misc;
   if (int rc = radius_prep(count_out, P, total_out, resc, st)) return rc;
   const RadiusOut o = {count_out, (unsigned long long*)total_out, pair_out, dist_out, capacity, thresh};
@@ -1567,11 +1540,10 @@ extern "C" int frmap_match_radius_packed(const float* a, const int32_t* label_a,
   const double u = (double)nextafterf(thresh, INFINITY), u2 = u * u;
   float hi = (float)u2;
   if ((double)hi < u2) hi = nextafterf(hi, INFINITY);
-  FrmapRadiusGemm r = {a, b, label_a, label_b, o, resc, hi, a_row0, pair_filter};
-  const int taken = match_packed_gemm(MATCH_JOIN, a, b_packed, stat_w, w.stat_a, w.split, &r, P, Q, D, st);
-  if (taken < 0) return taken;
-  if (!taken) return radius_scan(a, label_a, P, b, label_b, Q, D, a_row0, pair_filter, o, st);
-  return 0;
+  const FrmapMatchGemm g = {w.split, b_packed, w.stat_a, stat_w, P, Q, D};
+  if (!match_packed_prep(a, g, st)) return radius_scan(a, label_a, P, b, label_b, Q, D, a_row0, pair_filter, o, st);
+  const FrmapRadiusGemm r = {a, b, label_a, label_b, o, resc, hi, a_row0, pair_filter};
+  return frmap_match_gemm_join(g, r, st);
 }
 
 extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits_out, int32_t* argmax_out,

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "model_api.h"
+#include "match_device.h"   // frmap_match_topk_fill_labels
 
 namespace {
 

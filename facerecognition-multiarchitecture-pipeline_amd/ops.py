@@ -657,6 +657,40 @@ def verify_thresholds(thresholds, device) -> torch.Tensor:
     return t
 
 
+def _pair_operands(op: str, a, labels_a, b, labels_b, a_row0, absent: dict):
+    """The ``a / b / labels / a_row0`` modes of `verify_counts` and `match_radius`: ``(a, la, b, lb, row0)`` as the C entry points
+    take them (int32 labels or None; row0 = -1 in cross mode; self mode over ``a``: b = a, lb = la, row0 = 0).  ``absent[what]``:
+    the ValueError text for a missing ``what`` (labels_a / labels_b), or None where it may be missing."""
+    a = _dev(a, f"{op}.a", torch.float32)
+    if a.dim() != 2:
+        raise ValueError(f"{op}: a must be [P, D]")
+    P, D = int(a.shape[0]), int(a.shape[1])
+
+    def labels(t, n, what):
+        if t is None and what in absent:
+            if absent[what] is not None:
+                raise ValueError(absent[what])
+            return None
+        t = _dev(t, f"{op}.{what}").to(torch.int32).reshape(-1)
+        if t.shape[0] != n:
+            raise ValueError(f"{op}: {what} must hold {n} labels, got {t.shape[0]}")
+        return t
+
+    la = labels(labels_a, P, "labels_a")
+    if b is None:
+        if labels_b is not None or a_row0 not in (None, 0):
+            raise ValueError(f"{op}: self mode over `a` (b=None) takes no labels_b / a_row0")
+        return a, la, a, la, 0
+    b = _dev(b, f"{op}.b", torch.float32)
+    if b.dim() != 2 or int(b.shape[1]) != D:
+        raise ValueError(f"{op}: b must be [Q, {D}]")
+    lb = labels(labels_b, int(b.shape[0]), "labels_b")
+    row0 = -1 if a_row0 is None else int(a_row0)
+    if a_row0 is not None and not (row0 >= 0 and row0 + P <= int(b.shape[0])):
+        raise ValueError(f"{op}: a_row0={row0} with {P} rows is not a block of b's {int(b.shape[0])} rows")
+    return a, la, b, lb, row0
+
+
 def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Optional[torch.Tensor] = None,
                   labels_b: Optional[torch.Tensor] = None, *, a_row0: Optional[int] = None, prepared: Optional[MatchPack] = None,
                   return_rescored: bool = False):
@@ -671,30 +705,9 @@ def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Option
     Outside graph capture the thresholds are checked on the host (`verify_thresholds`): host values are uploaded with a blocking
     copy and device values read back, so each call synchronises the stream once.  A caller that repeats calls on fixed device
     thresholds and wants them asynchronous calls the C entry points (`frmap_verify_counts[_packed]`) after checking them once."""
-    a = _dev(a, "verify_counts.a", torch.float32)
-    if a.dim() != 2:
-        raise ValueError("verify_counts: a must be [P, D]")
-    P, D = int(a.shape[0]), int(a.shape[1])
-    la = _dev(labels_a, "verify_counts.labels_a").to(torch.int32).reshape(-1)
-    if la.shape[0] != P:
-        raise ValueError(f"verify_counts: labels_a must hold {P} labels, got {la.shape[0]}")
-    if b is None:
-        if labels_b is not None or a_row0 not in (None, 0):
-            raise ValueError("verify_counts: self mode over `a` (b=None) takes no labels_b / a_row0")
-        b, lb, row0 = a, la, 0
-    else:
-        b = _dev(b, "verify_counts.b", torch.float32)
-        if b.dim() != 2 or int(b.shape[1]) != D:
-            raise ValueError(f"verify_counts: b must be [Q, {D}]")
-        if labels_b is None:
-            raise ValueError("verify_counts: labels_b is required with b")
-        lb = _dev(labels_b, "verify_counts.labels_b").to(torch.int32).reshape(-1)
-        if lb.shape[0] != b.shape[0]:
-            raise ValueError(f"verify_counts: labels_b must hold {int(b.shape[0])} labels, got {lb.shape[0]}")
-        row0 = -1 if a_row0 is None else int(a_row0)
-        if a_row0 is not None and not (row0 >= 0 and row0 + P <= int(b.shape[0])):
-            raise ValueError(f"verify_counts: a_row0={row0} with {P} rows is not a block of b's {int(b.shape[0])} rows")
-    Q = int(b.shape[0])
+    a, la, b, lb, row0 = _pair_operands("verify_counts", a, labels_a, b, labels_b, a_row0,
+                                        {"labels_b": "verify_counts: labels_b is required with b"})
+    (P, D), Q = a.shape, int(b.shape[0])
     thr = verify_thresholds(thresholds, a.device)
     T = int(thr.shape[0])
     lib = _lib.load()
@@ -736,41 +749,15 @@ def match_radius(a: torch.Tensor, thresh: float, b: Optional[torch.Tensor] = Non
     ``return_rescored``: also int64 [1] = the pairs the GEMM path scored exactly, appended to either result.
     Path choice as `verify_counts`: a ``prepared`` B of >= `MATCH_MFMA_MIN_G` rows with D % 32 == 0 runs on the fp16 MFMA GEMM, whose
     epilogue drops the pairs certainly beyond the threshold and re-scores the rest; everything else on an exact scan.  Same answer."""
-    a = _dev(a, "match_radius.a", torch.float32)
-    if a.dim() != 2:
-        raise ValueError("match_radius: a must be [P, D]")
-    P, D = int(a.shape[0]), int(a.shape[1])
     if which not in _RADIUS_WHICH:
         raise ValueError(f"match_radius: which must be 'all', 'same' or 'different', got {which!r}")
     filt = _RADIUS_WHICH[which]
     thresh = float(thresh)
     if not 0.0 <= thresh <= float(np.finfo(np.float32).max):          # (NaN fails both; the library takes an fp32)
         raise ValueError(f"match_radius: thresh must be finite and >= 0, got {thresh}")
-
-    def labels(t, n, what):
-        if t is None:
-            if filt:
-                raise ValueError(f"match_radius: which={which!r} needs {what}")
-            return None
-        t = _dev(t, f"match_radius.{what}").to(torch.int32).reshape(-1)
-        if t.shape[0] != n:
-            raise ValueError(f"match_radius: {what} must hold {n} labels, got {t.shape[0]}")
-        return t
-
-    la = labels(labels_a, P, "labels_a")
-    if b is None:
-        if labels_b is not None or a_row0 not in (None, 0):
-            raise ValueError("match_radius: self mode over `a` (b=None) takes no labels_b / a_row0")
-        b, lb, row0 = a, la, 0
-    else:
-        b = _dev(b, "match_radius.b", torch.float32)
-        if b.dim() != 2 or int(b.shape[1]) != D:
-            raise ValueError(f"match_radius: b must be [Q, {D}]")
-        lb = labels(labels_b, int(b.shape[0]), "labels_b")
-        row0 = -1 if a_row0 is None else int(a_row0)
-        if a_row0 is not None and not (row0 >= 0 and row0 + P <= int(b.shape[0])):
-            raise ValueError(f"match_radius: a_row0={row0} with {P} rows is not a block of b's {int(b.shape[0])} rows")
-    Q = int(b.shape[0])
+    a, la, b, lb, row0 = _pair_operands("match_radius", a, labels_a, b, labels_b, a_row0, {
+        what: f"match_radius: which={which!r} needs {what}" if filt else None for what in ("labels_a", "labels_b")})
+    (P, D), Q = a.shape, int(b.shape[0])
     if capacity is not None and int(capacity) < 0:
         raise ValueError(f"match_radius: capacity={capacity} must be >= 0")
     lib = _lib.load()

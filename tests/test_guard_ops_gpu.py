@@ -4,7 +4,8 @@ wrapper allocates between bands of 0xFF.. and of 0x5A..; `check()` passes and al
 times.  The layout / pool / cast cases are also compared with a float64 CPU reference (`test_kernels_gpu.py::test_pools`'
 tolerances); what the other kernels compute is tested in their own files.  One positive control at the end.
 
-Workspace fields (first write / first read, read from `head_match.hip`, `frmap_common.h`, `conv_pp.hip`):
+Workspace fields (first write / first read, read from `head_match.hip`, `match_device.h`, `conv_pp.hip`; each operation's fields
+are laid out by one function of `head_match.hip` - `top1_ws`, `topk_ws`, `verify_ws`, `radius_ws` - that its `*_workspace_bytes` shares):
   cosine_logits   keys u64 [B]           `fill_u64_kernel` (0) before the GEMM / atomicMax in the GEMM, then `argkey_finalize_kernel`
                   inv_a [B], inv_w [C]   `row_stats_kernel` x 2 / the GEMM's epilogue
   arcmargin_eval  mm u32 [2]             `minmax_init_kernel` / atomicMax, atomicMin in the GEMM (integers), `minmax_finalize_kernel`

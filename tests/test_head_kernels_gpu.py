@@ -2,7 +2,8 @@
 they switch paths, against float64 references; tolerances are the ones the older tests use for the same op.
 
 * `gap_norm_match`: the sixteen-loads-in-flight pooling loop (HW > 15 row subsets), one and two scan passes (G <= 40 < G), G = 1,
-  64 and 0, C >= 2048 (one subset, a loop over channel groups), C / 8 that does not divide 256, ties across waves and passes;
+  64 and 0, C >= 2048 (one subset, a loop over channel groups), C / 8 that does not divide 256, ties across waves and passes
+  (its last step, `match_write_top1`, is the one `match_small_kernel` and `match_finalize_rec_kernel` end in);
 * `gemm_nt_f32_kernel` through `linear_f32`, `cosine_logits` and `arcmargin_eval`: the K tail (K % 32 != 0), several row blocks,
   fewer than 128 columns, first-index-wins of the arg-max inside a wave, across waves and across workgroups;
 * `gap_linear_norm` at K / 8 = 24 (idle lanes) and K = 8; `softmax_argmax`, `pairwise_distance`, `l2_normalize` at widths below,
