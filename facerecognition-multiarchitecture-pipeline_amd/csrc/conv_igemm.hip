@@ -1120,8 +1120,14 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ slab, int kspli
 // ------------------------------------------------------------------------------------------------
 // host side: conv_plan.h decides which kernel runs; this only validates, fills ConvParams and launches
 // ------------------------------------------------------------------------------------------------
-static ConvPlan plan_of(const ConvLayer& L) { return conv_plan(L, conv_tuning(), frmap_cu_count(), frmap_batch_invariant() != 0); }
+static ConvPlan plan_of(const ConvLayer& L) { return conv_plan_launch(L, conv_tuning(), frmap_cu_count(), frmap_batch_invariant() != 0); }
 ConvPlan frmap_conv_plan(const ConvLayer& L) { return plan_of(L); }
+extern "C" int frmap_conv3x3_pp_tile_px(int B, int Hi, int Wi, int Cin, int Cout, int stride, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride) {
+  if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64 || (stride != 1 && stride != 2)) return 0;
+  if (ds_Cin > 0 && (stride != 1 || !frmap_conv_igemm_ds_supported(B, Hi, Wi, Cin, Cout, ds_Hi, ds_Wi, ds_Cin, ds_stride))) return 0;
+  const ConvPlan q = plan_of(ConvLayer{B, Hi, Wi, Cin, Cout, 3, stride, 1, ds_Cin > 0 ? FUSE_SHORTCUT : FUSE_NONE, ds_Hi, ds_Wi, ds_Cin, ds_stride});
+  return q.kernel == CK_PP || q.kernel == CK_PP_S2 ? q.tile_px : 0;
+}
 
 struct ConvPtrs {  // shortcut: ds_in / ds_w (FUSE_SHORTCUT); split-K: slab
   const void* in; const void* w; const float* shift; const void* res; void* out;

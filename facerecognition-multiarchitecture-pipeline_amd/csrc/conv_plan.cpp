@@ -33,6 +33,7 @@ ConvTuning& conv_tuning() {
     v.min_cin = env_int("FRMAP_PP_MIN_CIN", 128);
     v.s2_min_cin = env_int("FRMAP_PP_S2_MIN_CIN", 64);
     v.tile_px = env_int("FRMAP_PP_TILE_PX", 0);
+    v.fill = env_int("FRMAP_PP_FILL", 1);
     v.bn = env_int("FRMAP_PP_BN", 0);
     v.pitch = env_int("FRMAP_PP_PITCH", 0);
     v.ri = env_int("FRMAP_PP_RI", 0);
@@ -161,6 +162,26 @@ static int pp_bn(int Cout, int forced_env, int forced_hook) {
 }
 static bool pp_sizes_fit(long long M, long long in_elems) { return M < (1ll << 31) && in_elems * 2 < (1ll << 46); }
 
+// The instantiations conv_pp.hip builds, by halo size.  Stride 1: pieces of (8 / ks) KB per wave, at most 5 in the shared-buffer
+// layouts and 6 with split-K (0 = no fit); classes NHP 3 / 5, split-K 4 / 6.  The shortcut form's halo buffers also hold a gather
+// image: the 448-pixel layout (bn = 128) needs the 40 KB buffers of NHP = 5 for it.
+static int pp_halo_pieces(long long hbytes, int ks) {
+  const int per = (8 / ks) * 1024;
+  const int nhp = (int)((hbytes + per - 1) / per);
+  return nhp <= (ks == 2 ? 6 : 5) ? nhp : 0;
+}
+static int pp_nhp_class(int nhp, int ks, int bn, bool has_ds) {
+  if (has_ds) return bn == 256 && nhp <= 3 ? 3 : 5;
+  return ks == 2 ? (nhp <= 4 ? 4 : 6) : (nhp <= 3 ? 3 : 5);
+}
+// Stride 2: four sub-position images of NHP x 8 KB; NHP in {1, 2, 4}, and 4 only with bn = 128 (4 x 32 KB images + 4 x 16 KB
+// slabs would not fit).  0 = no fit.
+static int pp_s2_nhp_class(long long hbytes, int bn) {
+  const int need = (int)((hbytes + 8191) / 8192);
+  const int nhp = need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 0));
+  return nhp == 4 && bn == 256 ? 0 : nhp;
+}
+
 // ------------------------------------------------------------------------------------------------
 // second generation (conv_pp.hip)
 // ------------------------------------------------------------------------------------------------
@@ -194,9 +215,7 @@ ConvPlan plan_pp_3x3(const ConvLayer& L, const ConvTuning& t, bool inv) {
     const long long hbytes = (long long)pp_max_rows(Mll, tile_px, Hi * Wi, Wi, Hp, 3, inv) * Wp * 64;
     if (hbytes / 64 >= 65536) return 0;
     hbytes_out = (int)hbytes;
-    const int per = (8 / ks) * 1024;                           // bytes one "piece per wave" adds to the image
-    const int nhp = (int)((hbytes + per - 1) / per);
-    return nhp <= (ks == 2 ? 6 : 5) ? nhp : 0;
+    return pp_halo_pieces(hbytes, ks);
   };
   // candidates: 224 px x 256 ch; 448 px x 128 ch; split-K 224 px x 128 ch (twice the tiles of either)
   int tpx = 0, mtl = 0, ntl = 0, hby = 0, ks = 1, bn = pp_bn(Cout, t.bn, t.h_bn);
@@ -217,16 +236,13 @@ ConvPlan plan_pp_3x3(const ConvLayer& L, const ConvTuning& t, bool inv) {
   q.tile_px = tpx; q.mtiles = mtl; q.ntiles = ntl; q.Wp = Wp; q.halo_bytes = hby;
   q.layout = ks == 2 ? 3 : (bn == 256 ? 1 : 2);
   q.WM = bn == 256 || ks == 2 ? 2 : 4;
-  if (has_ds) {   // pixel-split layouts only; the 448-pixel layout needs the 40 KB halo buffers to hold a gather image
-    q.NHP = bn == 256 && nhp <= 3 ? 3 : 5;
-    return finish(q, "conv3x3_pp_kernel<%s, DS>");
-  }
+  q.NHP = pp_nhp_class(nhp, ks, bn, has_ds);
+  if (has_ds) return finish(q, "conv3x3_pp_kernel<%s, DS>");   // pixel-split layouts only
   // RI form (plain layers): fragment reads under the MFMAs.  (The RI form of the split-K layout with 6 halo pieces needs 258
   // VGPRs: it would spill inside the DMA-counted loop, so that one layout keeps the burst-read form; csrc/build.sh rejects any
   // *_pp_kernel with scratch)
   q.RI = ConvTuning::pick(t.h_ri, t.ri) != 0 && !(ks == 2 && nhp > 4);
   q.IM = !q.RI && ConvTuning::pick(t.h_im, t.im) != 0;
-  q.NHP = ks == 2 ? (nhp <= 4 ? 4 : 6) : (nhp <= 3 ? 3 : 5);
   return finish(q, "conv3x3_pp_kernel<%s>");
 }
 
@@ -252,9 +268,8 @@ ConvPlan plan_pp_s2(const ConvLayer& L, const ConvTuning& t, bool inv) {
   const long long hbytes = (long long)pp_max_rows(Mll, tile_px, Ho * Wo, Wo, Ho + 1, 2, inv) * q.Wp * 64;
   if (hbytes / 64 >= 65536) return q;
   q.halo_bytes = (int)hbytes;
-  const int need = (int)((hbytes + 8191) / 8192);
-  q.NHP = need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 0));
-  if (!q.NHP || (q.NHP == 4 && bn == 256)) return q;                       // (4 x 32 KB images + 4 x 16 KB slabs would not fit)
+  q.NHP = pp_s2_nhp_class(hbytes, bn);
+  if (!q.NHP) return q;
   if (!inv && !t.forced() && (long long)q.mtiles * q.ntiles < t.min_tiles) return q;
   q.kernel = CK_PP_S2;
   q.layout = bn == 256 ? 1 : 2;
@@ -484,6 +499,46 @@ ConvPlan conv_plan(const ConvLayer& L, const ConvTuning& t, int cus, bool inv) {
   q = plan_wave(L, t, cus);
   if (!q.taken()) q = plan_fast(L, t);
   return q.taken() ? q : g;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fill step (conv_plan.h): after the cascade has decided, on the image-aligned tiles, what runs and in which layout
+// ------------------------------------------------------------------------------------------------
+ConvPlan conv_fill(const ConvLayer& L, const ConvPlan& q0, const ConvTuning& t, bool inv) {
+  if (!t.fill || (q0.kernel != CK_PP && q0.kernel != CK_PP_S2) || q0.PL) return q0;   // switched off; (pooled slices are whole row pairs)
+  const bool s2 = q0.kernel == CK_PP_S2;
+  const int Ho = s2 ? L.Hi / 2 : L.Hi, Wo = s2 ? L.Wi / 2 : L.Wi, Hp = s2 ? Ho + 1 : Ho + 2;
+  const int bn = q0.KS == 2 || q0.WM == 4 ? 128 : 256;
+  if (bn == 256) return q0;   // 224 x 256 layouts (>= 200 tiles: 256 faces a stream): measured no faster filled (stride 1 +1.3 %, shortcut -0.4 %, stride 2 +0.7 %)
+  // (A/B: FRMAP_PP_FILL >= 2 is a mask of the forms to fill: 2 = 448 x 128 plain / residual, 4 = with the shortcut, 8 = split-K, 16 = stride 2)
+  if (t.fill >= 2 && !(t.fill & (s2 ? 16 : (q0.DS ? 4 : (q0.KS == 2 ? 8 : 2))))) return q0;
+  const int cap = (q0.KS == 2 || q0.WM == 2 ? 2 : 4) * q0.MI * 16;
+  // a forced tile stays, where pp_tile_px applied the value: the hook's everywhere, FRMAP_PP_TILE_PX at stride 1, neither above the capacity
+  if ((t.h_px > 0 && t.h_px <= cap) || (!s2 && t.tile_px > 0 && t.tile_px <= cap)) return q0;
+  const long long M = (long long)L.B * Ho * Wo;
+  // Stride 1 tries the full capacity only: a smaller fill keeps padding MFMAs and still pays the straddle's extra halo pieces
+  // (7x7 split-K tiles: 224 pixels would take a seventh piece, 210 fit the six they have and stay out).  Stride 2 has no
+  // instantiation for the halo of a full tile (five 8 KB pieces at 28x28): the largest size that fits.
+  for (int rows = cap / Wo; rows * Wo > q0.tile_px && (s2 || rows == cap / Wo); --rows) {
+    ConvPlan q = q0;
+    q.tile_px = rows * Wo;
+    q.mtiles = (int)((M + q.tile_px - 1) / q.tile_px);
+    const long long hbytes = (long long)pp_max_rows(M, q.tile_px, Ho * Wo, Wo, Hp, s2 ? 2 : 3, inv) * q.Wp * 64;
+    if (hbytes / 64 >= 65536) continue;
+    q.halo_bytes = (int)hbytes;
+    if (s2) {
+      q.NHP = pp_s2_nhp_class(hbytes, bn);
+      if (!q.NHP) continue;
+    } else {
+      const int nhp = pp_halo_pieces(hbytes, q.KS);
+      if (!nhp || (q.RI && q.KS == 2 && nhp > 4)) continue;                           // (no RI form with 6 halo pieces: keep the form)
+      q.NHP = pp_nhp_class(nhp, q.KS, bn, q.DS);
+    }
+    q = finish(q, q0.label);
+    if (q.lds_bytes > LDS_MAX) continue;
+    return q;
+  }
+  return q0;
 }
 
 // FRMAP_DS_UNFUSE_SMALL=1 (A/B switch) answers 0 where the second-generation kernel would take the plain 3x3 layer and the

@@ -46,6 +46,8 @@ struct ConvTuning {
   int min_cin;          // FRMAP_PP_MIN_CIN (128): Cin = 64 layers keep the wave kernel
   int s2_min_cin;       // FRMAP_PP_S2_MIN_CIN (64)
   int tile_px, bn;      // FRMAP_PP_TILE_PX, FRMAP_PP_BN (0 = heuristic; 3x3 stride 1 only)
+  int fill;             // FRMAP_PP_FILL (1): conv_fill enlarges the image-aligned tiles towards the layout's capacity; 0 = off;
+                        // A/B: a mask from 2 up fills 2 = 448 x 128 plain, 4 = with the shortcut, 8 = split-K, 16 = stride 2 only
   int pitch;            // FRMAP_PP_PITCH (0): conflict-free halo pitch
   int ri;               // FRMAP_PP_RI (0): fragment reads interleaved with the MFMAs
   int im;               // FRMAP_PP_IM (0): measured 4-6 % slower than issuing the DMA in the LOAD segments
@@ -112,6 +114,19 @@ ConvPlan plan_generic(const ConvLayer& L);                                 // 1x
 
 // the cascade of the table above; a layer must be one the entry points accept (K, stride, pad, Cin % 32, Cout % 64, sizes)
 ConvPlan conv_plan(const ConvLayer& L, const ConvTuning& t, int cus, bool inv);
+
+// THE FILL STEP.  conv_plan sizes a second-generation tile as whole images, or as a divisor of the image height (pp_tile_px):
+// 392 of 448 pixels on 28x28 maps, 196 of 224 on 14x14 and 7x7 maps, while every wave still issues its full 7 x 4 MFMAs per
+// k-step, the rest on clamped duplicate pixels (12.5 % of them).  The kernels take tiles that straddle images, so conv_fill
+// enlarges the tile of a plan conv_plan has TAKEN (kernel, layout, split-K and every tile-count gate stay as decided on the
+// image-aligned tile: the public layout queries answer as before) to the largest whole-row size <= the layout's capacity whose
+// halo (pp_max_rows at the new size) still fits an instantiation that exists and 160 KB of LDS, and recomputes mtiles, nblocks,
+// halo_bytes, NHP and lds_bytes.  Output elements keep their k order: the results are bit-identical.  Left as they are: the
+// pooled form (its slices are whole row pairs), the 1x1 / match plans, a tile forced by FRMAP_PP_TILE_PX or the tuning hook, a
+// plan that no larger size fits, the 224 px x 256 ch layouts (measured no faster filled: DESIGN.md), and everything when
+// FRMAP_PP_FILL=0.  The launchers plan with conv_plan_launch.
+ConvPlan conv_fill(const ConvLayer& L, const ConvPlan& q, const ConvTuning& t, bool inv);
+inline ConvPlan conv_plan_launch(const ConvLayer& L, const ConvTuning& t, int cus, bool inv) { return conv_fill(L, conv_plan(L, t, cus, inv), t, inv); }
 
 // 1 = frmap_conv_igemm_ds takes the layer fused (and fusing is not switched off)
 int conv_ds_supported(const ConvLayer& L, const ConvTuning& t, bool inv);

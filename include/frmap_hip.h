@@ -329,6 +329,11 @@ int frmap_conv3x3_pp_layout(int B, int Hi, int Wi, int Cin, int Cout);
 int frmap_conv3x3s2_pp_layout(int B, int Hi, int Wi, int Cin, int Cout);
 /* ... and for frmap_conv_igemm_ds (3x3 stride-1 layer with a fused 1x1 stride-s projection shortcut): 0 / 1 / 2. */
 int frmap_conv3x3_pp_ds_layout(int B, int Hi, int Wi, int Cin, int Cout, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride);
+/* Output pixels per tile of the launch frmap_conv_igemm (ds_Cin == 0; stride 1 or 2) or frmap_conv_igemm_ds (ds_Cin > 0) makes
+ * for a 3x3 pad-1 layer on a second-generation kernel; 0 = another kernel runs it.  The layouts above say how many pixels a
+ * tile can hold; the launch fills it with whole rows as far as the halo allows (FRMAP_PP_FILL=0, or a tile size forced through
+ * frmap_conv_pp_tuning: whole images, or a divisor of the image height). */
+int frmap_conv3x3_pp_tile_px(int B, int Hi, int Wi, int Cin, int Cout, int stride, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride);
 
 /* A 3x3 stride-1 pad-1 convolution with a ResNet projection shortcut folded in (BasicBlock.conv2 + bn2 + downsample
  * [conv1x1 stride s + bn] + add + ReLU of the first block of a stage, torchvision resnet.py via face_models.py:67):
