@@ -1181,6 +1181,7 @@ static int conv_launch(const ConvPlan& q, const ConvParams& p, int dtype, hipStr
   const conv_kern_t kern = dtype == FRMAP_BF16 ? conv_kernel<BF16>(q) : conv_kernel<F16>(q);
   FRMAP_REQUIRE(kern, "conv_igemm: no kernel for plan %d", q.kernel);
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
+  FRMAP_REQUIRE(FRMAP_GRID_FITS(q.nblocks, q.kernel == CK_WAVE ? 512 : 256), "conv_igemm: %d workgroups exceed the grid", q.nblocks);
   hipLaunchKernelGGL(kern, dim3(q.nblocks), dim3(q.kernel == CK_WAVE ? 512 : 256), q.lds_bytes, st, p);
   FRMAP_LAUNCH_CHECK();
   return 0;

@@ -472,7 +472,30 @@ static ConvPlan plan_pool2(const ConvLayer& L, const ConvTuning& t, int cus, boo
   return q.taken() ? q : plan_generic(L);
 }
 
+static ConvPlan conv_cascade(const ConvLayer& L, const ConvTuning& t, int cus, bool inv);
+
+// threads of a plan's workgroup (the launchers' block sizes)
+static int plan_threads(const ConvPlan& q) { return q.kernel == CK_WAVE || q.kernel >= CK_PP ? 512 : 256; }
+
 ConvPlan conv_plan(const ConvLayer& L, const ConvTuning& t, int cus, bool inv) {
+  ConvPlan q{};
+  // every kernel numbers output pixels in an int.  The launchers refuse such a layer before they plan; the public queries plan
+  // without a launcher in front of them, and the grid arithmetic below is 32-bit
+  if ((long long)L.B * L.Ho() * L.Wo() >= (1ll << 31)) {
+    snprintf(q.error, sizeof(q.error), "conv_igemm: too many output pixels");
+    return q;
+  }
+  q = conv_cascade(L, t, cus, inv);
+  // a grid holds fewer than 2^32 threads (FRMAP_GRID_FITS, frmap_common.h): a larger one is cut down without an error
+  if (q.taken() && (long long)q.nblocks * plan_threads(q) >= (1ll << 32)) {
+    ConvPlan e{};
+    snprintf(e.error, sizeof(e.error), "conv_igemm: %d workgroups of %d threads exceed the grid (shard the batch)", q.nblocks, plan_threads(q));
+    return e;
+  }
+  return q;
+}
+
+static ConvPlan conv_cascade(const ConvLayer& L, const ConvTuning& t, int cus, bool inv) {
   ConvPlan q{};
   if (L.fuse == FUSE_POOL2) return plan_pool2(L, t, cus, inv);
   const bool live = t.debug == 0;
@@ -555,8 +578,9 @@ int conv_ds_supported(const ConvLayer& L, const ConvTuning& t, bool inv) {
 }
 
 int linear_ksplit(int M, int K, int N, bool inv) {
-  const int tiles = (inv ? 1 : (M + 255) / 256) * (N / 64), nchunks = K / 32;
-  int ks = 384 / (tiles > 0 ? tiles : 1);
+  const long long tiles = (inv ? 1ll : ((long long)M + 255) / 256) * (N / 64);
+  const int nchunks = K / 32;
+  int ks = (int)(384 / (tiles > 0 ? tiles : 1));
   if (ks > nchunks / 4) ks = nchunks / 4;
   return ks < 2 ? 1 : ks;
 }

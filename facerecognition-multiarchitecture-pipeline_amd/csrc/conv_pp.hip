@@ -941,6 +941,7 @@ template <typename P>
 static int pp_launch(const void* kern, const ConvPlan& q, int lds, const P& p, hipStream_t st) {
   FRMAP_REQUIRE(kern, "conv_pp: no kernel for plan %d (WM %d, NHP %d, KS %d)", q.kernel, q.WM, q.NHP, q.KS);
   if (frmap_big_lds(kern, 160 * 1024)) return -2;
+  FRMAP_REQUIRE(FRMAP_GRID_FITS((long long)q.mtiles * q.ntiles, 512), "conv_pp: %d x %d workgroups exceed the grid", q.mtiles, q.ntiles);
   void* args[] = {(void*)&p};
   (void)hipLaunchKernel(kern, dim3(q.mtiles * q.ntiles), dim3(512), args, lds, st);
   FRMAP_LAUNCH_CHECK();

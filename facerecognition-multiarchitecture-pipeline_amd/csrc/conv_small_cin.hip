@@ -210,6 +210,7 @@ static int launch_small(SmallCinParams& p, hipStream_t st) {
   int lds = (int)hb + wbytes;
   const int scratch = 4 * 16 * (NI * 64 + 16);  // epilogue transpose region (4 waves)
   if (lds < scratch) lds = scratch;
+  FRMAP_REQUIRE(FRMAP_GRID_FITS(p.nblocks, 256), "conv_small_cin: %d workgroups exceed the grid", p.nblocks);
   hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds, st, p);
   FRMAP_LAUNCH_CHECK();
   return 0;

@@ -294,6 +294,13 @@ int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, 
       return -1;                        \
     }                                   \
   } while (0)
+// A grid holds fewer than 2^32 threads per dimension: the dispatch packet counts work-items in 32 bits, and a larger grid is cut down
+// modulo 2^32 WITHOUT an error (seen on gfx950: a launch of 2^34 + 1024 threads ran 1024 of them and left the rest of its output
+// unwritten).  Every launcher whose grid grows with the batch states the limit that follows and checks it before the launch.
+#define FRMAP_GRID_FITS(blocks, threads) ((long long)(blocks) > 0 && (long long)(blocks) * (long long)(threads) < (1ll << 32))
+#define FRMAP_GRID_ROWS_MAX ((1 << 26) - 4)   // one wave (64 threads) per row, four rows a workgroup
+#define FRMAP_GRID_WG256_MAX ((1 << 24) - 1)  // one 256-thread workgroup per item
+
 #define FRMAP_LAUNCH_CHECK()                                           \
   do {                                                                 \
     hipError_t e__ = hipGetLastError();                                \

@@ -245,6 +245,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
 
 template <int MODE>
 static int launch_gemm(const float* A, const float* W, int B, int N, int K, const GemmEpi& ep, hipStream_t st) {
+  // (rows ride on the grid's y axis: 65535 tiles of 64)
+  FRMAP_REQUIRE((B + 63) / 64 <= 65535, "fp32 GEMM: %d rows exceed the grid (at most %d)", B, 65535 * 64);
   dim3 grid((N + 127) / 128, (B + 63) / 64);
   hipLaunchKernelGGL(gemm_nt_f32_kernel<MODE>, grid, dim3(256), 0, st, A, W, B, N, K, ep);
   FRMAP_LAUNCH_CHECK();
@@ -523,6 +525,7 @@ extern "C" int frmap_gap_norm_match(const void* map, const float* gallery, float
   FRMAP_REQUIRE(map && idx_out && dist_out, "gap_norm_match: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "gap_norm_match: bad dtype");
   FRMAP_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 8 == 0 && C <= 4096, "gap_norm_match: bad shape B=%d HW=%d C=%d", B, HW, C);
+  FRMAP_REQUIRE(B <= FRMAP_GRID_WG256_MAX, "gap_norm_match: %d faces exceed the grid (at most %d)", B, FRMAP_GRID_WG256_MAX);
   FRMAP_REQUIRE(G >= 0 && G <= 64 && (G == 0 || gallery), "gap_norm_match: gallery of 0..64 rows expected (got %d)", G);
   const int c8 = C / 8, nparts = c8 < 256 ? 256 / c8 : 1;
   const size_t lds = (size_t)(C + 8 + nparts * C) * sizeof(float);
@@ -815,6 +818,7 @@ extern "C" int frmap_linear_f32(const float* x, const float* w, const float* sca
 extern "C" int frmap_l2_normalize_f32(const float* x, float* out, int B, int D, float eps, void* stream) {
   FRMAP_REQUIRE(x && out, "l2_normalize: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0, "l2_normalize: bad shape");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "l2_normalize: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(l2_normalize_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, x, out, B, D, eps);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -823,6 +827,7 @@ extern "C" int frmap_l2_normalize_f32(const float* x, float* out, int B, int D, 
 extern "C" int frmap_softmax_argmax(const float* logits, float* probs_out, int32_t* pred_out, int B, int C, void* stream) {
   FRMAP_REQUIRE(logits && (probs_out || pred_out), "softmax_argmax: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0, "softmax_argmax: bad shape");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "softmax_argmax: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(softmax_argmax_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, logits, probs_out, pred_out, B, C);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -832,6 +837,7 @@ extern "C" int frmap_pairwise_distance(const float* a, const float* b, float* di
                                        int B, int D, void* stream) {
   FRMAP_REQUIRE(a && b && dist_out, "pairwise_distance: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0, "pairwise_distance: bad shape");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "pairwise_distance: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(pairwise_distance_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, a, b, dist_out, same_out, thresh, B, D);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -882,6 +888,8 @@ extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t*
   FRMAP_REQUIRE(emb && idx_out && dist_out && workspace, "match_top1: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0 && D % 4 == 0 && G >= 0, "match_top1: bad shape B=%d G=%d D=%d", B, G, D);
   FRMAP_REQUIRE(G == 0 || gallery, "match_top1: null gallery");
+  // (G <= 64: one workgroup a probe; else one wave a probe and a gallery row)
+  FRMAP_REQUIRE(B <= (G <= 64 ? FRMAP_GRID_WG256_MAX : FRMAP_GRID_ROWS_MAX) && G <= FRMAP_GRID_ROWS_MAX, "match_top1: B=%d or G=%d exceeds the grid", B, G);
   hipStream_t st = (hipStream_t)stream;
   if (G > 0 && G <= 64) {
     hipLaunchKernelGGL(match_small_kernel, dim3(B), dim3(256), 0, st, emb, gallery, idx_out, dist_out,
@@ -994,6 +1002,7 @@ static int match_pack_rows(const float* gallery, void* packed_out, float* stat_w
 extern "C" int frmap_match_pack_gallery(const float* gallery, void* packed_out, float* stat_w_out, int G, int D, void* stream) {
   FRMAP_REQUIRE(gallery && packed_out && stat_w_out, "match_pack_gallery: null pointer");
   FRMAP_REQUIRE(G > 0 && D > 0 && D % 32 == 0, "match_pack_gallery: bad shape G=%d D=%d (D %% 32 == 0)", G, D);
+  FRMAP_REQUIRE(G <= FRMAP_GRID_ROWS_MAX, "match_pack_gallery: %d rows exceed the grid (at most %d)", G, FRMAP_GRID_ROWS_MAX);
   return match_pack_rows(gallery, packed_out, stat_w_out, 0, G, G, D, (hipStream_t)stream);
 }
 
@@ -1025,6 +1034,7 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
                                        float thresh, void* workspace, void* probe_split, int B, int G, int D, void* stream) {
   FRMAP_REQUIRE(emb && gallery && gallery_packed && stat_w && idx_out && dist_out && workspace && probe_split, "match_top1_packed: null pointer");
   FRMAP_REQUIRE(B > 0 && G > 0 && D > 0 && D % 32 == 0, "match_top1_packed: bad shape B=%d G=%d D=%d", B, G, D);
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "match_top1_packed: %d probes exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   const Top1Ws w = top1_ws(workspace, B, G, true);
   const FrmapMatchGemm g = {probe_split, gallery_packed, w.stat_a, stat_w, B, G, D};
@@ -1211,6 +1221,8 @@ static int topk_check(const char* what, const float* emb, const float* gallery, 
   FRMAP_REQUIRE(k >= 1 && k <= 64, "%s: k=%d out of range (1 <= k <= 64)", what, k);
   FRMAP_REQUIRE(B > 0 && D > 0 && D % 4 == 0 && G >= 0, "%s: bad shape B=%d G=%d D=%d", what, B, G, D);
   FRMAP_REQUIRE(G == 0 || gallery, "%s: null gallery", what);
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && G <= FRMAP_GRID_ROWS_MAX, "%s: B=%d or G=%d exceeds the grid (at most %d rows)", what, B, G,
+                FRMAP_GRID_ROWS_MAX);
   return 0;
 }
 
@@ -1550,6 +1562,7 @@ extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits
                                    void* workspace, int B, int C, int D, float s, void* stream) {
   FRMAP_REQUIRE(x && w && workspace && (logits_out || argmax_out), "cosine_logits: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0 && D > 0 && D % 4 == 0, "cosine_logits: bad shape");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && C <= FRMAP_GRID_ROWS_MAX, "cosine_logits: B=%d or C=%d exceeds the grid (at most %d rows)", B, C, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* keys = (unsigned long long*)workspace;
   float* inv_a = (float*)(keys + B);
@@ -1574,6 +1587,7 @@ extern "C" int frmap_arcmargin_eval(const float* x, const float* w, const int64_
                                     int easy_margin, void* stream) {
   FRMAP_REQUIRE(x && w && label && logits_out && workspace, "arcmargin_eval: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0 && D > 0 && D % 4 == 0, "arcmargin_eval: bad shape");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && C <= FRMAP_GRID_ROWS_MAX, "arcmargin_eval: B=%d or C=%d exceeds the grid (at most %d rows)", B, C, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   unsigned int* mm = (unsigned int*)workspace;
   float* inv_a = (float*)workspace + 4;

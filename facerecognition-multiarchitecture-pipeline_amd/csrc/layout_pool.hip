@@ -224,6 +224,8 @@ extern "C" int frmap_avgpool_global(const void* in, float* out, int B, int HW, i
   FRMAP_REQUIRE(in && out, "avgpool_global: null pointer");
   FRMAP_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 8 == 0, "avgpool_global: bad shape");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "avgpool_global: bad dtype");
+  FRMAP_REQUIRE((long long)B * (C / 8) <= FRMAP_GRID_ROWS_MAX, "avgpool_global: B C / 8 = %lld waves exceed the grid (at most %d)",
+                (long long)B * (C / 8), FRMAP_GRID_ROWS_MAX);
   const int waves = B * (C / 8);
   const int blocks = (waves + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
@@ -271,6 +273,7 @@ extern "C" int frmap_avgpool_adaptive(const void* in, void* out, int B, int H, i
   FRMAP_REQUIRE(B > 0 && H > 0 && W > 0 && C % 8 == 0 && OH > 0 && OW > 0, "avgpool_adaptive: bad shape");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "avgpool_adaptive: bad dtype");
   const size_t total = (size_t)B * OH * OW * (C / 8);
+  FRMAP_REQUIRE(total + 255 < (1ull << 32), "avgpool_adaptive: %zu output groups exceed the grid (fewer than 2^32 threads)", total);
   const int blocks = (int)((total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FRMAP_BF16)

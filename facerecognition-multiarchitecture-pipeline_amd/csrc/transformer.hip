@@ -253,7 +253,8 @@ extern "C" int frmap_mha_tokens(const void* qkv, void* out, int B, int L, int D,
   FRMAP_REQUIRE(qkv && out, "mha_tokens: null pointer");
   FRMAP_REQUIRE(B > 0 && L > 0 && L <= 64 && H > 0 && D == H * 128, "mha_tokens: need L <= 64 and head dim 128 (D=%d H=%d L=%d)", D, H, L);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "mha_tokens: bad dtype");
-  FRMAP_REQUIRE((long long)B * H < (1ll << 31), "mha_tokens: too many heads");
+  FRMAP_REQUIRE((long long)B * H <= FRMAP_GRID_WG256_MAX, "mha_tokens: B H = %lld workgroups exceed the grid (at most %d)", (long long)B * H,
+                FRMAP_GRID_WG256_MAX);
   const int lds = 2 * 64 * 272 + 128 * 144 + 4 * 16 * 144 + 4 * 16 * 272;
   hipStream_t st = (hipStream_t)stream;
   const void* kern = dtype == FRMAP_BF16 ? (const void*)mha_tokens_kernel<BF16> : (const void*)mha_tokens_kernel<F16>;
@@ -351,6 +352,7 @@ extern "C" int frmap_mean_layernorm(const void* t, const float* gamma, const flo
                                     int D, float eps, int dtype, void* stream) {
   FRMAP_REQUIRE(t && gamma && beta && out, "mean_layernorm: null pointer");
   FRMAP_REQUIRE(B > 0 && L > 0 && D > 0 && D <= 1024, "mean_layernorm: bad shape (D <= 1024)");
+  FRMAP_REQUIRE(B <= FRMAP_GRID_WG256_MAX, "mean_layernorm: %d faces exceed the grid (at most %d)", B, FRMAP_GRID_WG256_MAX);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "mean_layernorm: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FRMAP_BF16)
@@ -541,6 +543,7 @@ extern "C" int frmap_cnn_attention(const void* qkv, const void* x, const float* 
   FRMAP_REQUIRE(out_map || out_pool, "cnn_attention: no output requested");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "cnn_attention: bad dtype");
   FRMAP_REQUIRE(B > 0 && H > 0 && W > 0 && H * W <= 64, "cnn_attention: need 1 <= H*W <= 64 (got %dx%d)", H, W);
+  FRMAP_REQUIRE(B <= FRMAP_GRID_WG256_MAX, "cnn_attention: %d images exceed the grid (at most %d)", B, FRMAP_GRID_WG256_MAX);
   FRMAP_REQUIRE(Cq > 0 && Cq <= 128 && Cq % 8 == 0, "cnn_attention: Cq=%d must be a multiple of 8, <= 128", Cq);
   FRMAP_REQUIRE(C == 256 || C == 512, "cnn_attention: C=%d must be 256 or 512", C);
   FRMAP_REQUIRE(KS > 0 && KS % 2 == 1 && KS <= 15, "cnn_attention: odd spatial kernel size <= 15 expected (got %d)", KS);

@@ -16,6 +16,7 @@ whose weights are subnormal), an fp32 emulation of the kernels' arithmetic with 
 tables of the two GPU files and the code that runs a case through the C ABI.
 """
 import math
+import zlib
 from collections import namedtuple
 
 import torch
@@ -465,7 +466,11 @@ def exact_n_nz(case):
 
 
 def case_seed(case):
-    return 7000 + 13 * [c.name for c in CONV_CASES + GELU_CASES].index(case.name)
+    """A table entry's seed by its position; a case from another table (`big_cases.py`) by a checksum of its name."""
+    names = [c.name for c in CONV_CASES + GELU_CASES]
+    if case.name in names:
+        return 7000 + 13 * names.index(case.name)
+    return 9000 + 13 * (zlib.crc32(case.name.encode()) % 4096)
 
 
 def case_pad(case):
@@ -544,12 +549,40 @@ def query_path(lib, ops, case):
     raise ValueError(name)
 
 
-def run_case(case, o, dtype, also_unfused=False, place=None):
-    """Launch the case's kernel on operand dict `o` (values `dtype` represents exactly) and return the output as a CPU NCHW tensor
-    in `dtype`.  Asserts the path the case is about where a query exists, and restores the process-wide tuning hooks.
-    `also_unfused`: for the fused-pool ops, returns (fused, two-launch) outputs.  `place`: how a CPU operand reaches the device
-    (None: a plain copy; `guard.Guard.place` puts it between guard bands)."""
+def device_operands(case, o, dtype, place=None):
+    """The operands of a case on the device, as its launch takes them (`place`: how a CPU tensor gets there): the shift, the NHWC
+    activations (`x`, `r`, `xd`; `x4` for the Cin = 3 kernels; the stems' fp32 NCHW `x` or uint8 `u8` with `mean`, `std`) and the
+    packed weights (`wpk`, `wdpk`).  Every activation keeps the batch as its first dimension."""
     place = place or _to_dev
+    from frmap_amd import ops
+    d = {"sh": place(o["shift"].float())}
+    if case.op in ("conv", "ds", "pool2"):
+        d["x"], d["wpk"] = _nhwc(o["x"], dtype, place), ops.pack_conv_weight(place(o["w"].float()), dtype)
+        if case.op == "conv" and o.get("r") is not None:
+            d["r"] = _nhwc(o["r"], dtype, place)
+        if case.op == "ds":
+            d["xd"] = _nhwc(o["xd"], dtype, place)
+            d["wdpk"] = ops.pack_conv_weight(place(o["wd"].float()), dtype)
+    elif case.op in ("c3", "c3pool2"):
+        x4 = torch.zeros(tuple(o["x"].shape[i] for i in (0, 2, 3)) + (4,), dtype=dtype)
+        x4[..., :3] = o["x"].permute(0, 2, 3, 1).to(dtype)
+        d["x4"], d["wpk"] = place(x4), ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
+    elif case.op in ("stem3", "stem2"):
+        d["wpk"] = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
+        d["x"] = place(o["x"].float())
+    elif case.op in ("stem3u8", "stem2u8"):
+        d["wpk"] = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
+        d["u8"], d["mean"], d["std"] = place(o["u8"]), o["mean"], o["std"]
+    else:
+        raise ValueError(case.op)
+    return d
+
+
+def launch_case(case, d, dtype, also_unfused=False):
+    """Launch the case's kernel on the device operands `d` (`device_operands`; `case.B` is the batch of the tensors in `d`) and
+    return the output as it lies on the device, NHWC in `dtype` (`also_unfused`: for the fused-pool ops, the (fused, two-launch)
+    outputs).  Asserts the path the case is about where a query exists, waits for the launches and restores the process-wide
+    tuning hooks."""
     from frmap_amd import _lib, ops
     lib = _lib.load()
     try:
@@ -560,45 +593,46 @@ def run_case(case, o, dtype, also_unfused=False, place=None):
         if case.query is not None:
             got = query_path(lib, ops, case)
             assert got in case.query[1], (case.name, case.query[0], "answers", got, "wanted", case.query[1])
-        sh = place(o["shift"].float())
+        sh, wpk = d["sh"], d["wpk"]
         y2 = None
-        if case.op in ("conv", "ds", "pool2"):
-            x, wpk = _nhwc(o["x"], dtype, place), ops.pack_conv_weight(place(o["w"].float()), dtype)
-            if case.op == "conv":
-                r = _nhwc(o["r"], dtype, place) if o.get("r") is not None else None
-                y = ops.conv_igemm(x, wpk, sh, case.Cout, case.k, case.stride, case_pad(case), case.act, r)
-            elif case.op == "ds":
-                xd = _nhwc(o["xd"], dtype, place)
-                assert ops.conv_ds_supported(case.B, case.H, case.W, case.Cin, case.Cout, xd.shape[1], xd.shape[2], case.ds[0], case.ds[1])
-                y = ops.conv_igemm_ds(x, wpk, sh, case.Cout, xd, ops.pack_conv_weight(place(o["wd"].float()), dtype), case.ds[1], case.act)
-            else:
-                y = ops.conv_igemm_pool2(x, wpk, sh, case.Cout, case.act)
-                if also_unfused:
-                    y2 = ops.maxpool(ops.conv_igemm(x, wpk, sh, case.Cout, 3, 1, 1, case.act), 2, 2, 0)
-        elif case.op in ("c3", "c3pool2"):
-            x4 = torch.zeros((case.B, case.H, case.W, 4), dtype=dtype)
-            x4[..., :3] = o["x"].permute(0, 2, 3, 1).to(dtype)
-            x4, wpk = place(x4), ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
-            if case.op == "c3":
-                y = ops.conv_small_cin(x4, wpk, sh, case.Cout, case.k, case.stride, case_pad(case), True)
-            else:
-                y = ops.conv_small_cin_pool2(x4, wpk, sh, case.Cout, True)
-                if also_unfused:
-                    y2 = ops.maxpool(ops.conv_small_cin(x4, wpk, sh, case.Cout, 3, 1, 1, True), 2, 2, 0)
+        if case.op == "conv":
+            y = ops.conv_igemm(d["x"], wpk, sh, case.Cout, case.k, case.stride, case_pad(case), case.act, d.get("r"))
+        elif case.op == "ds":
+            xd = d["xd"]
+            assert ops.conv_ds_supported(case.B, case.H, case.W, case.Cin, case.Cout, xd.shape[1], xd.shape[2], case.ds[0], case.ds[1])
+            y = ops.conv_igemm_ds(d["x"], wpk, sh, case.Cout, xd, d["wdpk"], case.ds[1], case.act)
+        elif case.op == "pool2":
+            y = ops.conv_igemm_pool2(d["x"], wpk, sh, case.Cout, case.act)
+            if also_unfused:
+                y2 = ops.maxpool(ops.conv_igemm(d["x"], wpk, sh, case.Cout, 3, 1, 1, case.act), 2, 2, 0)
+        elif case.op == "c3":
+            y = ops.conv_small_cin(d["x4"], wpk, sh, case.Cout, case.k, case.stride, case_pad(case), True)
+        elif case.op == "c3pool2":
+            y = ops.conv_small_cin_pool2(d["x4"], wpk, sh, case.Cout, True)
+            if also_unfused:
+                y2 = ops.maxpool(ops.conv_small_cin(d["x4"], wpk, sh, case.Cout, 3, 1, 1, True), 2, 2, 0)
         elif case.op in ("stem3", "stem2"):
-            wpk = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
-            y = ops.stem7x7_maxpool(place(o["x"].float()), wpk, sh, dtype, pool3=case.op == "stem3")
+            y = ops.stem7x7_maxpool(d["x"], wpk, sh, dtype, pool3=case.op == "stem3")
         elif case.op in ("stem3u8", "stem2u8"):
-            wpk = ops.pack_conv_weight_c3(place(o["w"].float()), dtype)
-            y = ops.stem7x7_maxpool_u8(place(o["u8"]), wpk, sh, o["mean"], o["std"], dtype, pool3=case.op == "stem3u8")
+            y = ops.stem7x7_maxpool_u8(d["u8"], wpk, sh, d["mean"], d["std"], dtype, pool3=case.op == "stem3u8")
         else:
             raise ValueError(case.op)
         _sync(case.name)
-        y = y.cpu().permute(0, 3, 1, 2)
-        return (y, y2.cpu().permute(0, 3, 1, 2)) if also_unfused and y2 is not None else y
+        return (y, y2) if also_unfused and y2 is not None else y
     finally:
         lib.frmap_conv_pp_tuning(-1, -1, -1)
         lib.frmap_conv_pp_ri(-1)
+
+
+def run_case(case, o, dtype, also_unfused=False, place=None):
+    """Launch the case's kernel on operand dict `o` (values `dtype` represents exactly) and return the output as a CPU NCHW tensor
+    in `dtype`.  Asserts the path the case is about where a query exists, and restores the process-wide tuning hooks.
+    `also_unfused`: for the fused-pool ops, returns (fused, two-launch) outputs.  `place`: how a CPU operand reaches the device
+    (None: a plain copy; `guard.Guard.place` puts it between guard bands)."""
+    y = launch_case(case, device_operands(case, o, dtype, place), dtype, also_unfused)
+    if isinstance(y, tuple):
+        return tuple(t.cpu().permute(0, 3, 1, 2) for t in y)
+    return y.cpu().permute(0, 3, 1, 2)
 
 
 def u8_operands(case, dtype, exact):

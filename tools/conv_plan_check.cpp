@@ -11,7 +11,8 @@
 //   * lds_bytes <= 160 KB, <= 80 KB where the plan counts on two workgroups per CU; halo_bytes / 64 < 65536; grid > 0
 //   * a shortcut plan exists exactly where ds_supported answers 1, a pooled plan exactly where pool2_form != 0, of the form's family
 //   * the candidates' layouts, the forms and the split-K slices are the library's answers
-// A failed check is a line "FAIL ..." on stdout and exit status 1.  Without input it checks three layers of its own.
+// A failed check is a line "FAIL ..." on stdout and exit status 1.  Without input it checks three layers of its own.  With the
+// argument "big" it reads layers and sweeps their batch past the 32-bit marks (below).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -100,8 +101,93 @@ static void record(int cus, bool inv, const ConvTuning& t, int B, int H, int W, 
   CHECK(((q.layout >= 2) || (q.layout == 1 && Ci <= 96)) == (a[6] != 0), "pool2_supported %d, form %d", a[6], q.layout);
 }
 
-int main() {
+// ------------------------------------------------------------------------------------------------
+// Large batches ("conv_plan_check big < layers"): one layer per record,
+//   enable tile_px bn  B H W Cin Cout K stride pad fuse ds_Hi ds_Wi ds_Cin ds_stride
+// planned at its own batch (printed as "big <record> <kernel> ...": tests/test_conv_plan_cpu.py compares the kernel with the one
+// the large-tensor tests name) and then at every batch of a sweep: the smallest at which the input passes 2^31, 2^32 and 2^33
+// bytes, and the batches that put M = B Ho Wo just under, at and just beyond 2^31.  Every int of every plan must equal the same
+// quantity computed in 64 bits (under -fsanitize=undefined an overflow on the way aborts the program); a plan's grid holds fewer
+// than 2^32 threads; from M = 2^31 on, the limit every launcher states, there is no plan.
+// ------------------------------------------------------------------------------------------------
+static void big_check(const char* what, const ConvLayer& L, const ConvTuning& t, int cus, bool inv) {
+  const long long M = (long long)L.B * L.Ho() * L.Wo(), two31 = 1ll << 31;
+  const ConvPlan q = conv_plan_launch(L, t, cus, inv);
+  ++g_plans;
+  if (M >= two31) {
+    CHECK(!q.taken(), "B=%d M=%lld >= 2^31, yet a plan %s", L.B, M, kernel_name(q.kernel));
+    return;
+  }
+  if (!q.taken()) return;
+  const long long ntiles = q.kernel >= CK_PP ? L.Cout / (q.KS == 2 || q.WM == 4 ? 128 : 256) : L.Cout / 64;
+  CHECK(q.ntiles == ntiles, "B=%d ntiles %d, in 64 bits %lld", L.B, q.ntiles, ntiles);
+  long long nblocks = 0;
+  if (q.kernel >= CK_PP) {
+    const long long mtiles = (M + q.tile_px - 1) / q.tile_px;
+    CHECK(q.tile_px > 0 && q.mtiles == mtiles, "B=%d mtiles %d, in 64 bits %lld", L.B, q.mtiles, mtiles);
+    nblocks = mtiles * ntiles;
+  } else if (q.kernel == CK_WAVE) {
+    const long long total = (long long)L.B * (L.Hi / 8) * (L.Wi / 8);
+    long long per = cus / ntiles;
+    if (per < 1) per = 1;
+    if (per > (total + 7) / 8) per = (total + 7) / 8;
+    CHECK(total < two31, "B=%d the wave kernel's patch count %lld does not fit an int", L.B, total);
+    nblocks = per * ntiles;
+  } else {
+    // (the pooled generic form walks pixels in pool-major order: the same count)
+    nblocks = ((M + q.BM - 1) / q.BM) * ntiles * (q.ksplit > 1 ? q.ksplit : 1);
+  }
+  CHECK(nblocks * (q.kernel == CK_WAVE || q.kernel >= CK_PP ? 512 : 256) < 2 * two31, "B=%d %s grid %lld exceeds 2^32 threads", L.B, kernel_name(q.kernel), nblocks);
+  CHECK(nblocks > 0 && nblocks < two31 && q.nblocks == nblocks, "B=%d %s grid %d, in 64 bits %lld", L.B, kernel_name(q.kernel), q.nblocks, nblocks);
+  CHECK(q.halo_bytes >= 0 && q.halo_bytes / 64 < 65536 && q.lds_bytes > 0 && q.lds_bytes <= 160 * 1024, "B=%d halo %d lds %d", L.B, q.halo_bytes, q.lds_bytes);
+  if (q.kernel == CK_WAVE)
+    CHECK((long long)L.Hi * L.Wi * L.Cin * 2 < two31, "B=%d the wave kernel took an image of %lld bytes", L.B, (long long)L.Hi * L.Wi * L.Cin * 2);
+  if (q.kernel == CK_FAST || q.kernel == CK_S2_FAST)   // tile-relative byte offsets of the register-prefetch kernels: 31 bits
+    CHECK((256 / ((long long)L.Ho() * L.Wo()) + 3) * L.Hi * L.Wi * L.Cin * 2 < two31, "B=%d %s took offsets past 31 bits", L.B, kernel_name(q.kernel));
+  if (q.kernel == CK_PP_S2) CHECK((long long)L.Hi * L.Wi * L.Cin * 2 < two31, "B=%d conv3x3s2_pp_kernel took an image past 2^31 bytes", L.B);
+}
+
+static int big_main(const ConvTuning& base) {
+  int v[16], n = 0;
+  long records = 0;
+  const int cus = 256;
+  while (scanf("%d", &v[n]) == 1) {
+    if (++n < 16) continue;
+    n = 0;
+    ConvTuning t = base;
+    t.set_tuning(v[0], v[1], v[2]);
+    ConvLayer L = {v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12], v[13], v[14], v[15]};
+    const char* what = "big";
+    const ConvPlan q = conv_plan_launch(L, t, cus, false);
+    printf("big %ld %s B=%d %dx%d Cin=%d Cout=%d K=%d s=%d fuse=%d layout=%d tile_px=%d mtiles=%d ntiles=%d nblocks=%d%s%s\n", records,
+           kernel_name(q.kernel), L.B, L.Hi, L.Wi, L.Cin, L.Cout, L.K, L.stride, L.fuse, q.layout, q.tile_px, q.mtiles, q.ntiles, q.nblocks,
+           q.taken() ? "" : " error=", q.taken() ? "" : q.error);
+    big_check(what, L, t, cus, false);
+    const long long in_bytes = (long long)L.Hi * L.Wi * L.Cin * 2, howo = (long long)L.Ho() * L.Wo(), two31 = 1ll << 31;
+    long long bs[9] = {(two31 + in_bytes - 1) / in_bytes + 1, (2 * two31 + in_bytes - 1) / in_bytes + 1, (4 * two31 + in_bytes - 1) / in_bytes + 1,
+                       (two31 - 1) / howo, (two31 + howo - 1) / howo, (two31 + howo - 1) / howo + 1, two31 - 1, 1, 2};
+    for (int i = 0; i < 9; ++i) {
+      if (bs[i] < 1 || bs[i] >= two31) continue;
+      L.B = (int)bs[i];
+      for (int inv = 0; inv < 2; ++inv) {
+        big_check(what, L, t, cus, inv != 0);
+        // the candidates behind the public queries take M and the byte counts in 64 bits themselves
+        const ConvPlan c = L.fuse == FUSE_POOL2 ? plan_pp_pool(L, t, inv != 0)
+                           : L.K == 1 ? plan_pp_1x1(L, t, cus, inv != 0) : L.stride == 2 ? plan_pp_s2(L, t, inv != 0) : plan_pp_3x3(L, t, inv != 0);
+        CHECK(!c.taken() || (long long)L.B * howo < two31, "B=%d a second-generation candidate took M >= 2^31", L.B);
+        if (L.K == 1) { const int ks = linear_ksplit(L.B, L.Cin, L.Cout, inv != 0); CHECK(ks >= 1, "linear_ksplit %d", ks); }
+      }
+    }
+    ++records;
+  }
+  if (n) { fprintf(stderr, "conv_plan_check: input ends inside a record\n"); return 2; }
+  printf("conv_plan_check: %ld large-batch records, %ld plans, %d failed checks\n", records, g_plans, g_fail);
+  return g_fail ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
   ConvTuning base = conv_tuning();   // environment defaults, hooks unset
+  if (argc > 1 && !strcmp(argv[1], "big")) return big_main(base);
   int v[22], n = 0;
   long records = 0;
   while (scanf("%d", &v[n]) == 1) {
