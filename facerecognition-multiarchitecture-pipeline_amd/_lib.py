@@ -40,6 +40,10 @@ PROTOTYPES = {
     "frmap_resize_coeffs_host": (_i, [_i, _i, _vp, _vp, _vp]),
     "frmap_align_crop_resize_u8": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "frmap_align_warp_host": (_i, [_vp, _i, _i, C.c_longlong, _vp, _i, _i, _i, _i, _i, _vp]),
+    "frmap_crop_resize_yuv": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "frmap_align_crop_resize_yuv": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "frmap_yuv_to_rgb_host": (_i, [_vp, _vp, _vp, _i, _i, C.c_longlong, C.c_longlong, _i, _i, _vp]),
+    "frmap_yuv_align_warp_host": (_i, [_vp, _vp, _vp, _i, _i, C.c_longlong, C.c_longlong, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "frmap_track_state_bytes": (_sz, [_i, _i]),
     "frmap_track_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "frmap_track_step_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp]),

@@ -1,5 +1,5 @@
-// What the frame kernels (crop_resize.hip, align_crop.hip) share: the device records they take - frames and regions of interest -
-// and the launch shape both derive from the size bounds of a call.  Not part of the public ABI as types - include/frmap_hip.h
+// What the frame kernels (crop_resize.hip, align_crop.hip, yuv_crop.hip) share: the device records they take - frames and regions
+// of interest - and the launch shape all derive from the size bounds of a call.  Not part of the public ABI as types - include/frmap_hip.h
 // states the records' layout in words.
 #pragma once
 
@@ -8,6 +8,13 @@ struct FrmapFrame {            // mirrored by resize.py (24 bytes)
   int H, W;
   long long pitch;             // bytes from one row to the next, >= 3 * W
 };
+struct FrmapYuvFrame {         // mirrored by resize.py (56 bytes): one 4:2:0 frame of 8-bit samples (yuv_pixel.h has the rule)
+  unsigned long long y, u, v;  // device addresses of sample (0, 0) of each plane; chroma planes are ceil(H/2) x ceil(W/2)
+  int H, W;
+  long long y_pitch, c_pitch;  // bytes from one row to the next: >= W, >= c_step * ceil(W/2)
+  int c_step;                  // bytes from one chroma sample to the next in its row: 1 = planar (I420, YV12), 2 = interleaved
+  int csc;                     // row of the conversion table: 0 bt601 limited, 1 bt601 full, 2 bt709 limited, 3 bt709 full
+};                             // NV12: v = u + 1, c_step = 2; NV21: u = v + 1, c_step = 2
 struct FrmapRoi {              // mirrored by resize.py (20 bytes)
   int frame, x1, y1, x2, y2;   // rows [y1, y2), columns [x1, x2) of frames[frame]
 };

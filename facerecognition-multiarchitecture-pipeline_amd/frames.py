@@ -3,7 +3,8 @@
 the reference's dataset step (`src/data_prep.py:69-106`): the eye-line rotation, its matrix, the margin rule - and the loop's IoU
 tracker (`app.py:126-147, 183-247`: `box_iou`, `track_boxes`), the readable statement of the rule `ops.track_step` runs for many
 streams in one launch - and the templates of its tracks (`fuse_tracks`: a track's embeddings pooled into a decayed sum and a
-weight, the rule `ops.track_fuse` runs).  Pure host code; the detector itself (MTCNN) is outside this package.
+weight, the rule `ops.track_fuse` runs) - and the conversion rule of 4:2:0 YUV frames (`YUV_COEFFS`, `yuv_to_rgb`: what the YUV
+crop kernels compute per pixel).  Pure host code; the detector itself (MTCNN) is outside this package.
 
 The tracker departs from the reference in two places.  (a) The IoU is float64 arithmetic on the detector's float32 coordinates,
 nothing fused: the reference mixes `np.float32` rows with Python floats from `tolist()`, so which of its operations run in float32
@@ -20,6 +21,57 @@ import numpy as np
 
 DET_THRESH = 0.9                       # `app.py:18`
 TRACKING_THRESHOLD = 0.3               # `app.py:29`
+
+
+def _yuv_row(kr: float, kb: float, full_range: bool) -> Tuple[int, int, int, int, int, int]:
+    """One row of `YUV_COEFFS` from ``(Kr, Kb)``: float64 coefficients of R = Y' + rv V', G = Y' + gu U' + gv V', B = Y' + bu U',
+    luma scaled by 255/219 (offset 16) and chroma by 255/224 for limited range, each as ``floor(c * 65536 + 0.5)``."""
+    kg = 1.0 - kr - kb
+    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    q = lambda c: int(math.floor(c * 65536.0 + 0.5))
+    return (0 if full_range else 16, q(sy), q(2.0 * (1.0 - kr) * sc), q(-2.0 * kb * (1.0 - kb) / kg * sc),
+            q(-2.0 * kr * (1.0 - kr) / kg * sc), q(2.0 * (1.0 - kb) * sc))
+
+
+YUV_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+# csc code -> (y_off, cy, rv, gu, gv, bu): the table of csrc/yuv_pixel.h.  csc = 2 * (standard is bt709) + full_range.
+YUV_COEFFS = {2 * si + int(fr): _yuv_row(*YUV_KR_KB[std], fr) for si, std in enumerate(("bt601", "bt709")) for fr in (False, True)}
+assert YUV_COEFFS == {0: (16, 76309, 104597, -25675, -53279, 132201), 1: (0, 65536, 91881, -22553, -46802, 116130),
+                      2: (16, 76309, 117489, -13975, -34925, 138438), 3: (0, 65536, 103206, -12276, -30679, 121609)}
+
+
+def yuv_csc(standard: str = "bt601", full_range: bool = False) -> int:
+    """The ``csc`` code of a (standard, range) pair: the row of `YUV_COEFFS`."""
+    if standard not in YUV_KR_KB:
+        raise ValueError(f"yuv: standard must be 'bt601' or 'bt709', got {standard!r}")
+    return 2 * int(standard == "bt709") + int(bool(full_range))
+
+
+def yuv_to_rgb(y, u, v, standard: str = "bt601", full_range: bool = False) -> np.ndarray:
+    """A 4:2:0 frame of 8-bit samples as uint8 RGB ``[H, W, 3]``: the readable statement of the rule the YUV crop kernels apply per
+    pixel (`resize.crop_resize_u8` on a `resize.YuvFrame` equals the same call on this array, bit for bit).
+
+    ``y``: uint8 ``[H, W]``; ``u``, ``v``: uint8 ``[ceil(H/2), ceil(W/2)]``, arrays of any strides (the two halves of an NV12
+    plane, say).  Pixel ``(x, y)`` takes chroma sample ``(x >> 1, y >> 1)`` - nearest replication, no interpolation.  Colour is
+    16-bit fixed point in int32 with the row ``(y_off, cy, rv, gu, gv, bu)`` of `YUV_COEFFS` and an arithmetic shift:
+
+        ``R = clip8((cy (Y - y_off) + rv (V - 128) + 32768) >> 16)``
+        ``G = clip8((cy (Y - y_off) + gu (U - 128) + gv (V - 128) + 32768) >> 16)``
+        ``B = clip8((cy (Y - y_off) + bu (U - 128) + 32768) >> 16)``
+
+    which is at most 1 away from ``clip(floor(float64 formula + 0.5))`` for every ``(Y, U, V)``."""
+    y, u, v = np.asarray(y), np.asarray(u), np.asarray(v)
+    if y.dtype != np.uint8 or u.dtype != np.uint8 or v.dtype != np.uint8 or y.ndim != 2 or u.ndim != 2 or v.ndim != 2:
+        raise ValueError("yuv_to_rgb: y, u and v must be uint8 planes")
+    H, W = y.shape
+    if H < 1 or W < 1 or u.shape != ((H + 1) // 2, (W + 1) // 2) or v.shape != u.shape:
+        raise ValueError(f"yuv_to_rgb: a {H}x{W} luma plane needs chroma planes of {(H + 1) // 2}x{(W + 1) // 2}, got {u.shape} and {v.shape}")
+    y_off, cy, rv, gu, gv, bu = YUV_COEFFS[yuv_csc(standard, full_range)]
+    yi, xi = np.arange(H)[:, None] >> 1, np.arange(W)[None, :] >> 1
+    l = cy * (y.astype(np.int32) - y_off) + 32768
+    uu, vv = u[yi, xi].astype(np.int32) - 128, v[yi, xi].astype(np.int32) - 128
+    rgb = np.stack([l + rv * vv, l + gu * uu + gv * vv, l + bu * uu], axis=-1) >> 16          # (numpy's >> on int32 is arithmetic)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
 
 
 def clip_boxes(boxes, probs, frame_shape: Sequence[int], det_thresh: float = DET_THRESH) -> Tuple[np.ndarray, np.ndarray]:

@@ -437,7 +437,8 @@ def embed_and_match(model, x: torch.Tensor, gallery, thresh: float = REC_THRESH,
 
 
 def _frame_list(frames) -> list:
-    """``[S, H, W, 3]`` (array or tensor) or a sequence of H×W×3 frames -> the list of frames, each checked to be H×W×3."""
+    """``[S, H, W, 3]`` (array or tensor) or a sequence of H×W×3 frames -> the list of frames, each checked to be H×W×3 (a
+    `resize.YuvFrame` says so of the frame it converts to)."""
     fl = list(frames.unbind(0) if isinstance(frames, torch.Tensor) else frames) if getattr(frames, "ndim", 0) == 4 else list(frames)
     for f in fl:
         if len(f.shape) != 3 or f.shape[2] != 3:
@@ -535,8 +536,8 @@ def embed_boxes(model, frame, boxes, probs=None, size=(160, 160), mean=(.5, .5, 
                 det_thresh: float = _frames.DET_THRESH, landmarks=None, margin: float = 0.0):
     """The embed half of the reference's frame loop (`app.py:224-241`) for all boxes of one frame at once: `frames.clip_boxes` →
     one crop + BGR→RGB + Resize launch on the frame (`resize.crop_resize_u8`; a host frame is uploaded once) → ToTensor +
-    Normalize → ONE ``model(x)`` under ``no_grad``.  ``frame``: H×W×3 uint8 BGR (cv2), host or device; ``boxes`` / ``probs``: the
-    detector's output.  Returns ``(embeddings [n, D] on the device, kept int64 [n])``: row i is what
+    Normalize → ONE ``model(x)`` under ``no_grad``.  ``frame``: H×W×3 uint8 BGR (cv2), host or device, or a `resize.YuvFrame`
+    (an NV12 / NV21 / I420 frame: the crop launch converts the pixels it reads); ``boxes`` / ``probs``: the detector's output.  Returns ``(embeddings [n, D] on the device, kept int64 [n])``: row i is what
     ``get_embedding(frame[y1:y2, x1:x2], model)`` returns for box ``kept[i]`` (to the bit under `ops.set_batch_invariant`; to
     rounding otherwise, as for any batch); boxes below ``det_thresh`` or empty after clipping are absent.
 
@@ -849,7 +850,9 @@ def identify_streams(model, frames, boxes, refs, tracker: Optional[StreamTracker
     carries the match records and the track ids.  A model reaches its rate at hundreds of faces and a frame holds a handful: S
     calls of `identify_boxes` pay S times the launch latency for what this does once.
 
-    ``frames``: a sequence of H×W×3 uint8 BGR frames of any sizes, or ``[S, H, W, 3]``, host or device.  ``boxes`` / ``probs`` /
+    ``frames``: a sequence of H×W×3 uint8 BGR frames of any sizes, or ``[S, H, W, 3]``, host or device - or a sequence of
+    `resize.YuvFrame`s (NV12 / NV21 / I420, `resize.nv12_frame` ...; not mixed with packed frames): the crop launch then converts
+    each pixel a filter tap reads, and the step equals the step on the converted frames bit for bit.  ``boxes`` / ``probs`` /
     ``landmarks``: one entry per stream (``None``: no detection in that frame; ``probs=None`` / ``landmarks=None``: none for any
     stream).  ``tracker``: a `StreamTracker` of S streams on the model's device, stepped once; its ``det_thresh`` is the step's
     (``det_thresh``, if given, must equal it; without a tracker it defaults to `frames.DET_THRESH`).  With a tracker the

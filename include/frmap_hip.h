@@ -124,6 +124,46 @@ int frmap_align_crop_resize_u8(const void* frames, int n_frames, const int32_t* 
 int frmap_align_warp_host(const unsigned char* frame, int H, int W, long long pitch, const double* mat6, int x1, int y1, int x2,
                           int y2, int bgr, unsigned char* out);
 
+/* Face crops straight from 4:2:0 YUV frames with 8-bit samples (NV12 / NV21 decoder surfaces, planar I420 / YV12) in one launch:
+ * output i is bit-identical to frmap_crop_resize_u8 on the frame CONVERTED to RGB by this rule, and no RGB frame is written:
+ *   chroma : pixel (x, y) takes chroma sample (x >> 1, y >> 1) - nearest replication; the chroma planes are ceil(H/2) x ceil(W/2)
+ *   colour : int32, arithmetic shift, clip8 = clamp to [0, 255], the pixel rounded to uint8 RGB before any filter tap reads it
+ *              R = clip8((cy (Y - y_off) + rv (V - 128) + 32768) >> 16)
+ *              G = clip8((cy (Y - y_off) + gu (U - 128) + gv (V - 128) + 32768) >> 16)
+ *              B = clip8((cy (Y - y_off) + bu (U - 128) + 32768) >> 16)
+ *            csc  standard, range    y_off     cy      rv      gu      gv      bu      (each floor(c * 65536 + 0.5) of its float64
+ *             0   bt601, limited       16   76309  104597  -25675  -53279  132201       value from (Kr, Kb) and the range scaling;
+ *             1   bt601, full           0   65536   91881  -22553  -46802  116130       at most 1 away from the rounded float64
+ *             2   bt709, limited       16   76309  117489  -13975  -34925  138438       formula, for every (Y, U, V))
+ *             3   bt709, full           0   65536  103206  -12276  -30679  121609
+ *   frames : n_frames records of 56 bytes in device memory, in this order: uint64 y, u, v (device addresses of sample (0, 0) of
+ *            the luma and the two chroma planes); int32 H, W; int64 y_pitch, c_pitch (bytes per row of the luma plane and of a
+ *            chroma plane: >= W, >= c_step * ceil(W/2)); int32 c_step (bytes from one chroma sample to the next in its row: 1 =
+ *            planar, 2 = interleaved); int32 csc (the table's row).  NV12: v = u + 1, c_step = 2.  NV21: u = v + 1, c_step = 2.
+ *            I420 / YV12: three planes, c_step = 1.  Frames of one call may differ in size, layout and csc.  Odd H and W are allowed.
+ *   rois, out, max_roi_h, max_roi_w : as frmap_crop_resize_u8 (there is no bgr flag: the output is RGB).
+ * Device records are NOT validated by this call: the kernel skips a record - its output stays unwritten, nothing is read or
+ * written outside the buffers - whose frame index is out of range, whose ROI is empty or leaves the frame, whose frame has a null
+ * plane, c_step outside {1, 2}, csc outside [0, 4), y_pitch < W or c_pitch < c_step * ceil(W/2), or whose window exceeds
+ * max_roi_*.  Supported reductions, the tall-ROI exception and the host-side rejections are those of frmap_crop_resize_u8. */
+int frmap_crop_resize_yuv(const void* frames, int n_frames, const int32_t* rois, unsigned char* out, int N, int out_h, int out_w,
+                          int max_roi_h, int max_roi_w, void* stream);
+/* frmap_align_crop_resize_u8 on YUV frames: bit-identical to it on the converted frame.  The four corner pixels of each bilinear
+ * warp sample are converted to uint8 RGB first, Pillow's float64 warp then runs on those; a sample outside the frame is RGB
+ * (0, 0, 0).  frames: the 56-byte records above; mats: as frmap_align_crop_resize_u8 (a non-finite entry: the record is skipped). */
+int frmap_align_crop_resize_yuv(const void* frames, int n_frames, const int32_t* rois, const double* mats, unsigned char* out, int N,
+                                int out_h, int out_w, int max_roi_h, int max_roi_w, void* stream);
+/* The conversion the YUV kernels apply per pixel, from the same function compiled for the CPU (HOST pointers; no GPU needed):
+ * the whole H x W frame as out_rgb [H][W][3].  Null pointers, H or W < 1, c_step outside {1, 2}, csc outside [0, 4) and a pitch
+ * below its row are rejected before anything is written. */
+int frmap_yuv_to_rgb_host(const unsigned char* y, const unsigned char* u, const unsigned char* v, int H, int W, long long y_pitch,
+                          long long c_pitch, int c_step, int csc, unsigned char* out_rgb);
+/* frmap_align_warp_host for a YUV frame: rows [y1, y2), columns [x1, x2) of Image.rotate's output for the converted frame, written
+ * as [y2 - y1][x2 - x1][3] RGB.  Rejections: those of frmap_yuv_to_rgb_host and of frmap_align_warp_host. */
+int frmap_yuv_align_warp_host(const unsigned char* y, const unsigned char* u, const unsigned char* v, int H, int W, long long y_pitch,
+                              long long c_pitch, int c_step, int csc, const double* mat6, int x1, int y1, int x2, int y2,
+                              unsigned char* out);
+
 /* The frame loop's IoU tracker (src/app.py:126-147, 183-247: process_webcam's face_id that survives from frame to frame), one
  * launch for n_streams independent streams (cameras, or clips stepped together), the per-stream state resident on the device.
  * One step of one stream, given its n = counts[s] detections in the detector's order and its frame's size (H, W):
