@@ -225,13 +225,27 @@ class ResNet18(nn.Module):
         raise RuntimeError("ResNet18 is a parameter container; inference runs through the owning HIP module")
 
 
+HANDLE_BN_EPS = 1e-5      # the eps `frmap_model_finalize` folds every BatchNorm with (include/frmap_hip.h)
+
+
+def _check_handle_eps(owner: nn.Module) -> None:
+    """A `state_dict` does not carry `eps`, so a model handle cannot see it: refuse a module whose BatchNorm has another one
+    instead of computing other numbers than the Python planner (which folds with `bn.eps`) without a word."""
+    for name, mod in owner.named_modules():
+        if isinstance(mod, (nn.BatchNorm1d, nn.BatchNorm2d)) and mod.eps != HANDLE_BN_EPS:
+            raise ValueError(f"{type(owner).__name__}.{name}: BatchNorm eps = {mod.eps:g}, but the model handle folds with eps = "
+                             f"{HANDLE_BN_EPS:g} (frmap_model_finalize); set FRMAP_PY_PLAN=1 to plan this module in Python")
+
+
 class _TrunkPlan:
     """ResNet-18 trunk (and, for 'cnn' / 'arcface', the heads) on a MODEL HANDLE of the C ABI (`frmap_model_*`,
     csrc/model_api.cpp): BatchNorm folding, weight packing and the per-layer kernel plan live in the library; this class only
     hands over the tensors under the reference's ``state_dict`` key names and asks for outputs."""
 
     def __init__(self, model_type: str, state: Dict[str, torch.Tensor], num_classes: int, dtype: torch.dtype,
-                 mean=IMAGENET_MEAN, std=IMAGENET_STD):
+                 mean=IMAGENET_MEAN, std=IMAGENET_STD, owner: Optional[nn.Module] = None):
+        if owner is not None:
+            _check_handle_eps(owner)
         self.dtype = dtype
         self.handle = ops.ModelHandle(model_type, state, num_classes, dtype, mean, std)
 
@@ -243,11 +257,11 @@ class _TrunkPlan:
         return self.handle.forward(x, ops.OUT_POOLED)  # fp32 B×512
 
 
-def _trunk_plan(rn: "ResNet18", dtype: torch.dtype, mean, std):
+def _trunk_plan(rn: "ResNet18", dtype: torch.dtype, mean, std, owner: Optional[nn.Module] = None):
     """The bare trunk of HybridNet / AttentionNet: a 'resnet18_trunk' handle, or the Python planner under FRMAP_PY_PLAN=1."""
     if _PY_PLAN:
         return _PyTrunkPlan(rn, dtype, mean, std)
-    return _TrunkPlan("resnet18_trunk", dict(rn.state_dict()), 0, dtype, mean, std)
+    return _TrunkPlan("resnet18_trunk", dict(rn.state_dict()), 0, dtype, mean, std, owner=owner or rn)
 
 
 class _PyTrunkPlan:
@@ -320,7 +334,7 @@ class BaselineNet(_HipModule):
 
     def _build_plan(self, dtype):
         if not _PY_PLAN and _HEAD_FUSE and _POOL_FUSE:
-            return _TrunkPlan("baseline", dict(self.state_dict()), self.fc2.out_features, dtype, self.input_mean, self.input_std)
+            return _TrunkPlan("baseline", dict(self.state_dict()), self.fc2.out_features, dtype, self.input_mean, self.input_std, owner=self)
         return {"c1": _PackedConv(self.conv1, self.bn1, dtype), "c2": _PackedConv(self.conv2, self.bn2, dtype),
                 "c3": _PackedConv(self.conv3, self.bn3, dtype), "fc1_t": self.fc1.weight.detach().float().t().contiguous()}
 
@@ -389,7 +403,7 @@ class ResNetTransfer(_HipModule):
             return _PyTrunkPlan(self.resnet, dtype, self.input_mean, self.input_std)
         fc = self.resnet.fc[1]
         return _TrunkPlan("cnn", {f"resnet.{k}": v for k, v in self.resnet.state_dict().items()}, fc.out_features, dtype,
-                          self.input_mean, self.input_std)
+                          self.input_mean, self.input_std, owner=self)
 
     def model_handle(self):
         """The `frmap_model` behind this module (None under FRMAP_PY_PLAN=1): `matching.embed_and_match` runs on it in one call."""
@@ -444,7 +458,7 @@ class SiameseNet(_HipModule):
 
     def _build_plan(self, dtype):
         if not _PY_PLAN and _POOL_FUSE:
-            return _TrunkPlan("siamese", dict(self.state_dict()), 0, dtype, self.input_mean, self.input_std)
+            return _TrunkPlan("siamese", dict(self.state_dict()), 0, dtype, self.input_mean, self.input_std, owner=self)
         c = self.conv
         # fc.1 consumes the NCHW flatten (index c*36 + s, `face_models.py:171`); our pooled tensor is
         # NHWC (index s*512 + c): permute the weight's input axis once here.
@@ -594,13 +608,13 @@ class ArcFaceNet(_HipModule):
         scale, shift = _bn_scale_shift(self.bn)
         if _PY_PLAN or not _HEAD_FUSE:
             trunk = _PyTrunkPlan(self.backbone, dtype, self.input_mean, self.input_std) if _PY_PLAN else \
-                _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std)
+                _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std, owner=self)
         else:
             state = {f"backbone.{k}": v for k, v in self.backbone.state_dict().items()}
             state.update({"embedding.weight": self.embedding.weight, "val_classifier.weight": self.val_classifier.weight,
                           "val_classifier.bias": self.val_classifier.bias})
             state.update({f"bn.{k}": v for k, v in self.bn.state_dict().items()})
-            trunk = _TrunkPlan("arcface", state, self.val_classifier.out_features, dtype, self.input_mean, self.input_std)
+            trunk = _TrunkPlan("arcface", state, self.val_classifier.out_features, dtype, self.input_mean, self.input_std, owner=self)
         return {"trunk": trunk, "bn_scale": scale, "bn_shift": shift,
                 "wt": self.embedding.weight.detach().float().t().contiguous()}   # [K][N] for the fused head
 
@@ -690,11 +704,11 @@ class HybridNet(_HipModule):
 
     def _build_plan(self, dtype):
         if not _PY_PLAN:
-            return _TrunkPlan("hybrid", dict(self.state_dict()), self.fc.out_features, dtype, self.input_mean, self.input_std)
+            return _TrunkPlan("hybrid", dict(self.state_dict()), self.fc.out_features, dtype, self.input_mean, self.input_std, owner=self)
         tr = self.transformer
         f32 = lambda t: t.detach().float().contiguous()
         return {
-            "trunk": _trunk_plan(self.cnn, dtype, self.input_mean, self.input_std),
+            "trunk": _trunk_plan(self.cnn, dtype, self.input_mean, self.input_std, owner=self),
             "pos": f32(self.pos_encoding).view(self.seq_len, self.fdim),
             "n1": (f32(tr.norm1.weight), f32(tr.norm1.bias)), "n2": (f32(tr.norm2.weight), f32(tr.norm2.bias)),
             "nf": (f32(self.norm.weight), f32(self.norm.bias)),
@@ -789,7 +803,7 @@ class AttentionNet(_HipModule):
         a = self.attention
         w = torch.cat([a.query.weight, a.key.weight, a.value.weight], dim=0).detach().float()
         bias = torch.cat([a.query.bias, a.key.bias, a.value.bias], dim=0).detach().float()
-        return {"trunk": _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std), "qkv": ops.pack_conv_weight(w.contiguous(), dtype),
+        return {"trunk": _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std, owner=self), "qkv": ops.pack_conv_weight(w.contiguous(), dtype),
                 "qkv_bias": bias.contiguous(), "cq": a.query.weight.shape[0], "cqkv": w.shape[0],
                 "gamma": a.gamma.detach().float().contiguous(),
                 "sw": a.spatial_attention.conv.weight.detach().float().contiguous(),

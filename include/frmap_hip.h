@@ -639,6 +639,9 @@ int frmap_arcmargin_eval(const float* x, const float* w, const int64_t* label, f
  *                            not use (ignored: training head, num_batches_tracked), -1 = wrong size.
  *   frmap_model_finalize     folds every eval-mode BatchNorm into its conv / linear (fp32), packs the weights into the kernels'
  *                            layout, fixes the layer plan; fails naming the first missing tensor.  Synchronises `stream` once.
+ *                            The fold is scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale (+ bias *
+ *                            scale) with eps = 1e-5 ALWAYS: a state_dict does not carry eps, so a checkpoint of a module built with
+ *                            another BatchNorm eps must be planned by the caller (the Python surface refuses such a module).
  *                            After it the handle is immutable: any thread / stream may run forwards on it concurrently.
  *   frmap_model_forward      x: FRMAP_INPUT_F32_NCHW = fp32 [B][3][H][W] (the reference's tensor) or FRMAP_INPUT_U8_HWC = uint8
  *                            [B][H][W][3] (ToTensor + Normalize applied inside the stem, src/testing.py:99-104);
