@@ -1,4 +1,4 @@
-// What the frame kernels (crop_resize.hip, align_crop.hip, yuv_crop.hip) share: the device records they take - frames and regions
+// What the frame kernels (crop_device.h's body; crop_resize.hip, yuv_crop.hip) share: the device records they take - frames and regions
 // of interest - and the launch shape all derive from the size bounds of a call.  Not part of the public ABI as types - include/frmap_hip.h
 // states the records' layout in words.
 #pragma once

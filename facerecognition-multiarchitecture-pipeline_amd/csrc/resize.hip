@@ -10,8 +10,10 @@
 // part: one workgroup = `rows_per_block` output rows of one image; it runs the horizontal pass for exactly the input rows
 // those output rows touch into an LDS image (4 bytes per pixel), then the vertical pass out of LDS.  Images of different
 // sizes share one launch (per-image descriptor: byte offset, size, table offsets).  Byte-granular global reads: the step is
-// HBM / latency bound and small next to the embed step (the output is 150 KB per face).
+// HBM / latency bound and small next to the embed step (the output is 150 KB per face).  The sum of one output sample and the
+// 3-byte store are the crop kernels' (resize_coeffs.h, rgb_pixel.h); the kernel stays its own: host tables, a 2-D grid.
 #include "frmap_common.h"
+#include "resize_coeffs.h"
 
 struct FrmapResizeItem {       // mirrored by resize.py (numpy structured dtype, 40 bytes)
   unsigned long long src_off;  // byte offset of the image (HWC uint8 RGB, row stride W * 3) in the source pool
@@ -19,11 +21,6 @@ struct FrmapResizeItem {       // mirrored by resize.py (numpy structured dtype,
   int bx_off, kx_off, ksx;     // int32 offsets into `tables`: bounds [out_w][2] = (first input column, taps), coefficients [out_w][ksx]; ksx = 0: width unchanged
   int by_off, ky_off, ksy;     // the same for rows; ksy = 0: height unchanged
 };
-
-__device__ __forceinline__ int resize_clip8(int v) {
-  v >>= 22;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 __global__ __launch_bounds__(256) void resize_bilinear_u8_kernel(const unsigned char* __restrict__ pool, const FrmapResizeItem* __restrict__ items,
                                                                  const int* __restrict__ tables, unsigned char* __restrict__ out,
@@ -51,16 +48,13 @@ __global__ __launch_bounds__(256) void resize_bilinear_u8_kernel(const unsigned 
     if (it.ksx) {
       const int xmin = bx[2 * xx], cnt = bx[2 * xx + 1];
       const int* k = kx + xx * it.ksx;
-      int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+      FrmapResizeSum s;
       const unsigned char* p = rowp + (size_t)xmin * 3;
-      for (int x = 0; x < cnt; ++x) {
-        const int w = k[x];
-        s0 += (int)p[3 * x] * w; s1 += (int)p[3 * x + 1] * w; s2 += (int)p[3 * x + 2] * w;
-      }
-      v = (unsigned)resize_clip8(s0) | ((unsigned)resize_clip8(s1) << 8) | ((unsigned)resize_clip8(s2) << 16);
+      for (int x = 0; x < cnt; ++x) s.tap(frmap_rgb_pack(p[3 * x], p[3 * x + 1], p[3 * x + 2]), k[x]);
+      v = s.pixel();
     } else {
       const unsigned char* p = rowp + (size_t)xx * 3;
-      v = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+      v = frmap_rgb_pack(p[0], p[1], p[2]);
     }
     s_tmp[idx] = v;
   }
@@ -73,18 +67,13 @@ __global__ __launch_bounds__(256) void resize_bilinear_u8_kernel(const unsigned 
     if (it.ksy) {
       const int ymin = by[2 * yy] - row_first, cnt = by[2 * yy + 1];
       const int* k = ky + yy * it.ksy;
-      int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-      for (int y = 0; y < cnt; ++y) {
-        const unsigned t = s_tmp[(ymin + y) * out_w + xx];
-        const int w = k[y];
-        s0 += (int)(t & 255u) * w; s1 += (int)((t >> 8) & 255u) * w; s2 += (int)((t >> 16) & 255u) * w;
-      }
-      v = (unsigned)resize_clip8(s0) | ((unsigned)resize_clip8(s1) << 8) | ((unsigned)resize_clip8(s2) << 16);
+      FrmapResizeSum s;
+      for (int y = 0; y < cnt; ++y) s.tap(s_tmp[(ymin + y) * out_w + xx], k[y]);
+      v = s.pixel();
     } else {
       v = s_tmp[ry * out_w + xx];
     }
-    unsigned char* o = dst + ((size_t)yy * out_w + xx) * 3;
-    o[0] = (unsigned char)(v & 255u); o[1] = (unsigned char)((v >> 8) & 255u); o[2] = (unsigned char)((v >> 16) & 255u);
+    frmap_rgb_store3(dst + ((size_t)yy * out_w + xx) * 3, v);
   }
 }
 

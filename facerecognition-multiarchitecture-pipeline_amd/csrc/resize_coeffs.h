@@ -1,6 +1,7 @@
 // Pillow's bilinear filter taps for one axis (libImaging/Resample.c: precompute_coeffs with the bilinear filter, support 1, box =
-// the whole axis, then normalize_coeffs_8bpc), one output sample at a time, for the host and the device alike: the crop kernel
-// (crop_resize.hip) builds its tables with it in LDS and frmap_resize_coeffs_host runs the same text on the CPU.  Not part of the
+// the whole axis, then normalize_coeffs_8bpc), one output sample at a time, for the host and the device alike: the crop body
+// (crop_device.h) builds its tables with it in LDS and frmap_resize_coeffs_host runs the same text on the CPU.  At the end, the
+// integer sum of one output sample that both resize kernels (resize.hip, crop_device.h) run over those taps.  Not part of the
 // public ABI.
 //
 // The integers must equal Pillow's, so the float64 operation order is Pillow's and nothing may be fused: hipcc contracts a * b + c
@@ -10,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include "rgb_pixel.h"
 
 constexpr int FRMAP_RESIZE_PRECISION_BITS = 32 - 8 - 2;
 
@@ -62,3 +65,17 @@ __host__ __device__ inline void frmap_resize_taps(const FrmapResizeAxis& a, int 
   *first = xmin;
   *taps = xmax;
 }
+
+// One output sample of Resample.c's horizontal or vertical 8-bit pass: three int32 sums started at half an output
+// unit, a tap adds pixel * coefficient per channel, the result is shifted (arithmetic) and clipped to [0, 255].
+struct FrmapResizeSum {
+  int s0 = 1 << (FRMAP_RESIZE_PRECISION_BITS - 1), s1 = 1 << (FRMAP_RESIZE_PRECISION_BITS - 1), s2 = 1 << (FRMAP_RESIZE_PRECISION_BITS - 1);
+  __device__ __forceinline__ void tap(unsigned t, int w) {   // t = R | G << 8 | B << 16
+    s0 += (int)(t & 255u) * w; s1 += (int)((t >> 8) & 255u) * w; s2 += (int)((t >> 16) & 255u) * w;
+  }
+  static __device__ __forceinline__ unsigned clip8(int v) {
+    v >>= FRMAP_RESIZE_PRECISION_BITS;
+    return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+  }
+  __device__ __forceinline__ unsigned pixel() const { return frmap_rgb_pack(clip8(s0), clip8(s1), clip8(s2)); }
+};

@@ -21,7 +21,7 @@ from . import frames as _frames
 PRECISION_BITS = 32 - 8 - 2
 ITEM_DTYPE = np.dtype([("src_off", "<u8"), ("H", "<i4"), ("W", "<i4"), ("bx_off", "<i4"), ("kx_off", "<i4"), ("ksx", "<i4"),
                        ("by_off", "<i4"), ("ky_off", "<i4"), ("ksy", "<i4")])   # FrmapResizeItem (csrc/resize.hip), 40 bytes
-FRAME_DTYPE = np.dtype([("base", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])   # FrmapFrame (csrc/crop_resize.hip), 24 bytes
+FRAME_DTYPE = np.dtype([("base", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])   # FrmapFrame (csrc/frame_records.h), 24 bytes
 YUV_FRAME_DTYPE = np.dtype([("y", "<u8"), ("u", "<u8"), ("v", "<u8"), ("H", "<i4"), ("W", "<i4"), ("y_pitch", "<i8"), ("c_pitch", "<i8"),
                             ("c_step", "<i4"), ("csc", "<i4")])                            # FrmapYuvFrame (csrc/frame_records.h), 56 bytes
 
@@ -319,24 +319,31 @@ def _frame_records(fr) -> np.ndarray:
     return desc
 
 
-def _crop_resize_yuv(fr, dev, r, out_h: int, out_w: int) -> torch.Tensor:
-    """`crop_resize_u8` for `YuvFrame`s already on ``dev``: one upload of records and one launch of the YUV kernel."""
+def _crop_launches(what: str, fr, dev, r, m, out_h: int, out_w: int, bgr: bool) -> torch.Tensor:
+    """What `crop_resize_u8` (``m`` None) and `align_crop_resize_u8` (``m`` float64 ``[N, 6]``) do with checked arguments, for packed
+    frames and `YuvFrame`s on ``dev`` alike: records | (matrices) | rois in one upload and one launch for the ROIs that keep Pillow's
+    usual pass order; a ROI more than 100x taller than wide whose height shrinks takes the other order - the kernel cuts it out
+    at its own size (both axes copied: the crop itself, converted, rotated, RGB) and `resize_bilinear_u8` resizes that."""
     N = r.shape[0]
+    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     if N == 0:
-        return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+        return out
+    yuv = isinstance(fr[0], YuvFrame)
     h, w = r[:, 4] - r[:, 2], r[:, 3] - r[:, 1]
     tall = (h > 100 * w) & (out_h < h)
-    desc = _frame_records(fr).view(np.int32)
+    desc = _frame_records(fr).view(np.uint8)
+    entry = getattr(_lib.load(), ("frmap_crop_resize" if m is None else "frmap_align_crop_resize") + ("_yuv" if yuv else "_u8"))
 
     def launch(sel, dst, oh, ow):
-        host = np.concatenate([desc, r[sel].astype(np.int32).reshape(-1)])                     # one upload: frames | rois
-        tab = torch.from_numpy(host).to(dev, non_blocking=True)
+        # the records are 24 (YUV: 56) and 48 bytes, so the doubles stay 8-byte aligned
+        mats = [] if m is None else [m[sel].view(np.uint8).reshape(-1)]
+        tab = torch.from_numpy(np.concatenate([desc] + mats + [r[sel].astype(np.int32).view(np.uint8).reshape(-1)])).to(dev, non_blocking=True)
+        p_m = tab.data_ptr() + desc.nbytes
+        p_r = p_m + 48 * len(sel) * len(mats)
+        args = [tab.data_ptr(), len(fr), p_r] + [p_m] * len(mats) + [dst.data_ptr(), len(sel), oh, ow, int(h[sel].max()), int(w[sel].max())]
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().frmap_crop_resize_yuv(tab.data_ptr(), len(fr), tab.data_ptr() + 4 * desc.size, dst.data_ptr(), len(sel),
-                                                         oh, ow, int(h[sel].max()), int(w[sel].max()),
-                                                         torch.cuda.current_stream().cuda_stream), "crop_resize_u8")
+            _lib.check(entry(*args, *([] if yuv else [int(bool(bgr))]), torch.cuda.current_stream().cuda_stream), what)
 
-    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     keep = np.flatnonzero(~tall)
     if keep.size:
         dst = out if keep.size == N else torch.empty((keep.size, out_h, out_w, 3), dtype=torch.uint8, device=dev)
@@ -345,7 +352,7 @@ def _crop_resize_yuv(fr, dev, r, out_h: int, out_w: int) -> torch.Tensor:
             out[torch.from_numpy(keep).to(dev)] = dst
     for i in np.flatnonzero(tall):
         crop = torch.empty((1, int(h[i]), int(w[i]), 3), dtype=torch.uint8, device=dev)
-        launch(np.array([i]), crop, int(h[i]), int(w[i]))       # size == ROI size: the converted crop itself
+        launch(np.array([i]), crop, int(h[i]), int(w[i]))
         out[int(i)] = resize_bilinear_u8([crop[0]], (out_h, out_w), dev)[0]
     return out
 
@@ -360,40 +367,14 @@ def crop_resize_u8(frames, rois, size: Tuple[int, int] = (160, 160), bgr: bool =
     ``(x1, y1, x2, y2)`` in frame 0, or ``[N, 5]`` with a leading frame index; a ROI that is empty or leaves its frame raises
     ``ValueError``.  ``bgr``: the frames are BGR (cv2) and come out RGB.  The filter taps are computed by the kernel
     (`frmap_crop_resize_u8`): no table per box size is built on the host.  A ROI more than 100x taller than wide whose height shrinks
-    takes Pillow's other pass order and goes through `resize_bilinear_u8` on its slice.
+    takes Pillow's other pass order: the kernel cuts it out at its own size and `resize_bilinear_u8` resizes that.
 
     ``frames`` may also be a `YuvFrame` (NV12, NV21, I420; `nv12_frame` ...) or a sequence of them, of any sizes, layouts and colour
     standards, host or device: crop i is then bit-identical to this function on ``frames.yuv_to_rgb`` of the frame, computed by
     `frmap_crop_resize_yuv` in the same single launch, each filter tap converting the pixel it reads - no RGB frame is written.
-    ``bgr`` is ignored for YUV frames.  A sequence that mixes YUV and packed frames raises ``ValueError``.  A tall ROI of a YUV frame
-    is cut out at its own size by the YUV kernel and resized by `resize_bilinear_u8`."""
+    ``bgr`` is ignored for YUV frames.  A sequence that mixes YUV and packed frames raises ``ValueError``."""
     out_h, out_w, fr, dev, r = _frames_and_rois("crop_resize_u8", frames, rois, size, device)
-    if isinstance(fr[0], YuvFrame):
-        return _crop_resize_yuv(fr, dev, r, out_h, out_w)
-    N = r.shape[0]
-    if N == 0:
-        return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    fi, x1, y1, x2, y2 = r.T
-    h, w = y2 - y1, x2 - x1
-    tall = (h > 100 * w) & (out_h < h)
-    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    keep = np.flatnonzero(~tall)
-    if keep.size:
-        desc = _frame_records(fr)
-        nd = desc.nbytes // 4
-        host = np.concatenate([desc.view(np.int32), r[keep].astype(np.int32).reshape(-1)])     # one upload: frames | rois
-        tab = torch.from_numpy(host).to(dev, non_blocking=True)
-        dst = out if keep.size == N else torch.empty((keep.size, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().frmap_crop_resize_u8(tab.data_ptr(), len(fr), tab.data_ptr() + 4 * nd, dst.data_ptr(), int(keep.size),
-                                                        out_h, out_w, int(h[keep].max()), int(w[keep].max()), int(bool(bgr)),
-                                                        torch.cuda.current_stream().cuda_stream), "crop_resize_u8")
-        if dst is not out:
-            out[torch.from_numpy(keep).to(dev)] = dst
-    for i in np.flatnonzero(tall):
-        a = fr[fi[i]][y1[i]:y2[i], x1[i]:x2[i]].cpu().numpy()
-        out[int(i)] = resize_bilinear_u8([a[:, :, ::-1] if bgr else a], (out_h, out_w), dev)[0]
-    return out
+    return _crop_launches("crop_resize_u8", fr, dev, r, None, out_h, out_w, bgr)
 
 
 def align_crop_resize_u8(frames, rois, matrices, size: Tuple[int, int] = (160, 160), bgr: bool = False, device="cuda") -> torch.Tensor:
@@ -419,7 +400,6 @@ def align_crop_resize_u8(frames, rois, matrices, size: Tuple[int, int] = (160, 1
     ``frames.yuv_to_rgb`` of the frame (`frmap_align_crop_resize_yuv`: the four corner pixels of a warp sample are converted first,
     what rotates in from outside is RGB 0).  ``bgr`` is ignored for YUV frames; mixing YUV and packed frames raises ``ValueError``."""
     out_h, out_w, fr, dev, r = _frames_and_rois("align_crop_resize_u8", frames, rois, size, device)
-    yuv = isinstance(fr[0], YuvFrame)
     N = r.shape[0]
     m = np.ascontiguousarray(matrices.detach().cpu().numpy() if isinstance(matrices, torch.Tensor) else matrices, dtype=np.float64)
     if m.size == 0:
@@ -428,36 +408,4 @@ def align_crop_resize_u8(frames, rois, matrices, size: Tuple[int, int] = (160, 1
         raise ValueError(f"align_crop_resize_u8: matrices must have shape [{N}, 6], one per ROI, got {tuple(m.shape)}")
     if not np.isfinite(m).all():
         raise ValueError(f"align_crop_resize_u8: matrix {int(np.flatnonzero(~np.isfinite(m).all(1))[0])} has a non-finite entry")
-    if N == 0:
-        return torch.empty((0, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    h, w = r[:, 4] - r[:, 2], r[:, 3] - r[:, 1]
-    tall = (h > 100 * w) & (out_h < h)
-    desc = _frame_records(fr).view(np.uint8)
-
-    def launch(sel, dst, oh, ow):
-        # one upload: frames | matrices | rois (the records are 24 (YUV: 56) and 48 bytes, so the doubles stay 8-byte aligned)
-        host = np.concatenate([desc, m[sel].view(np.uint8).reshape(-1), r[sel].astype(np.int32).view(np.uint8).reshape(-1)])
-        tab = torch.from_numpy(host).to(dev, non_blocking=True)
-        p_m = tab.data_ptr() + desc.nbytes
-        with torch.cuda.device(dev):
-            if yuv:
-                _lib.check(_lib.load().frmap_align_crop_resize_yuv(tab.data_ptr(), len(fr), p_m + 48 * len(sel), p_m, dst.data_ptr(),
-                                                                   len(sel), oh, ow, int(h[sel].max()), int(w[sel].max()),
-                                                                   torch.cuda.current_stream().cuda_stream), "align_crop_resize_u8")
-                return
-            _lib.check(_lib.load().frmap_align_crop_resize_u8(tab.data_ptr(), len(fr), p_m + 48 * len(sel), p_m, dst.data_ptr(), len(sel),
-                                                              oh, ow, int(h[sel].max()), int(w[sel].max()), int(bool(bgr)),
-                                                              torch.cuda.current_stream().cuda_stream), "align_crop_resize_u8")
-
-    out = torch.empty((N, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    keep = np.flatnonzero(~tall)
-    if keep.size:
-        dst = out if keep.size == N else torch.empty((keep.size, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-        launch(keep, dst, out_h, out_w)
-        if dst is not out:
-            out[torch.from_numpy(keep).to(dev)] = dst
-    for i in np.flatnonzero(tall):
-        crop = torch.empty((1, int(h[i]), int(w[i]), 3), dtype=torch.uint8, device=dev)
-        launch(np.array([i]), crop, int(h[i]), int(w[i]))       # size == ROI size: the rotated crop itself (RGB already)
-        out[int(i)] = resize_bilinear_u8([crop[0]], (out_h, out_w), dev)[0]
-    return out
+    return _crop_launches("align_crop_resize_u8", fr, dev, r, m, out_h, out_w, bgr)

@@ -1,6 +1,7 @@
-"""What the aligned-crop tests share: Pillow's `Image.rotate(angle, BILINEAR, center=c)` restated in numpy (the arithmetic
-`frmap_align_warp_host` and the kernel run - Geometry.c's affine transform with the bilinear filter on an 8-bit RGB image), the
-Pillow chain an aligned crop must equal, and the angle / centre lists of the issue.  Not a test module."""
+"""What the crop tests share: the Pillow resize a plain crop must equal; Pillow's `Image.rotate(angle, BILINEAR, center=c)`
+restated in numpy (the arithmetic `frmap_align_warp_host` and the kernel run - Geometry.c's affine transform with the bilinear
+filter on an 8-bit RGB image); the Pillow chain an aligned crop must equal; the angle / centre lists of the aligned-crop tests.
+Not a test module."""
 import math
 
 import numpy as np
@@ -20,6 +21,15 @@ def pil_matrix(angle, center):
     m[2] += cx
     m[5] += cy
     return m
+
+
+def pil_crop(frame, roi, out_h, out_w, bgr=False):
+    """The contract of a plain crop: the installed Pillow's bilinear resize of the frame's slice (BGR frames come out RGB)."""
+    x1, y1, x2, y2 = roi
+    a = frame[y1:y2, x1:x2]
+    if bgr:
+        a = a[:, :, ::-1]
+    return np.asarray(Image.fromarray(np.ascontiguousarray(a)).resize((out_w, out_h), Image.BILINEAR))
 
 
 def pil_rotate(rgb, angle, center):

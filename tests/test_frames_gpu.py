@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import frmap_amd  # noqa: E402
 from frmap_amd import _lib, frames, matching, ops, resize, synth  # noqa: E402
+from align_cases import pil_crop as _pil  # noqa: E402
 from test_configs_gpu import DIST_BOUND  # noqa: E402  (the project's gate on a distance's error per compute dtype)
 
 DEV = "cuda"
@@ -19,14 +20,6 @@ _rng = np.random.default_rng(20240611)
 F720 = (0.75 * np.kron(_rng.integers(0, 256, (45, 80, 3)), np.ones((16, 16, 1))) + 0.25 * _rng.integers(0, 256, (720, 1280, 3))).astype(np.uint8)
 F1080 = _rng.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)
 F1080[:, :, 0] = (np.add.outer(np.arange(1080), np.arange(1920)) // 9 % 256).astype(np.uint8)
-
-
-def _pil(frame, roi, out_h, out_w, bgr):
-    x1, y1, x2, y2 = roi
-    a = frame[y1:y2, x1:x2]
-    if bgr:
-        a = a[:, :, ::-1]
-    return np.asarray(Image.fromarray(np.ascontiguousarray(a)).resize((out_w, out_h), Image.BILINEAR))
 
 
 def _edge_rois(out_h, out_w):

@@ -1,6 +1,6 @@
-// The YUV pixel functions of the crop kernels (csrc/yuv_pixel.h: the conversion and the YUV form of the warp pixel, the text the
-// kernels compile) under the address and undefined-behaviour sanitizers, as a stand-alone host program: no Python, no GPU;
-// host-only work, not for a machine with a GPU.  Build and run from the repository root:
+// The pixel functions of the crop kernels (csrc/yuv_pixel.h: the conversion; csrc/rgb_pixel.h: the warp pixel every source shares
+// and the read of a packed frame - the text the kernels compile) under the address and undefined-behaviour sanitizers, as a
+// stand-alone host program: no Python, no GPU; host-only work, not for a machine with a GPU.  Build and run from the repository root:
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan -Ifacerecognition-multiarchitecture-pipeline_amd/csrc tools/yuv_check.cpp -o /tmp/yuv_check && /tmp/yuv_check
 //
 // Every plane lives in a heap buffer of EXACTLY the size the record states ((rows - 1) * pitch + the bytes of the last row), so a
@@ -9,7 +9,9 @@
 // The conversion is compared with the formula written out a second time here; the warp with the identity matrix must be the
 // conversion, with matrices that throw every sample outside the frame it must be zero, and with tilted ones (samples on every
 // clamped edge and outside) it must equal Pillow's bilinear arithmetic applied to the converted frame.  Bad arguments must be
-// refused with the output untouched.  Prints "yuv_check passed" and returns 0, or says what differed and returns 1.
+// refused with the output untouched.  The packed source: the same warp, matrices and ROIs over the converted picture held as a
+// packed RGB and a packed BGR buffer of exactly the stated size, tight and padded pitch, against the same reference.  Prints
+// "yuv_check passed" and returns 0, or says what differed and returns 1.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -72,7 +74,7 @@ static void reference_rgb(const Frame& f, std::vector<unsigned char>& out) {
     }
 }
 
-// Pillow's affine transform with the bilinear filter on the converted frame (align_crop.hip's arithmetic), written on the RGB array
+// Pillow's affine transform with the bilinear filter on the converted frame (rgb_pixel.h's arithmetic), written a second time on the RGB array
 static void reference_warp(const std::vector<unsigned char>& rgb, int H, int W, const double* m, int x, int y, unsigned char* o) {
   o[0] = o[1] = o[2] = 0;
   const double xo = x + 0.5, yo = y + 0.5;
@@ -95,6 +97,8 @@ static void reference_warp(const std::vector<unsigned char>& rgb, int H, int W, 
   }
 }
 
+static int g_packed = 0;   // packed-source cases run: frame x matrix x ROI x (RGB | BGR) x (tight | padded)
+
 static int fail(const char* what, const Frame& f) {
   printf("yuv_check: %s (frame %d x %d, c_step %d, v first %d, csc %d, pitches %lld / %lld)\n", what, f.H, f.W, f.c_step, (int)f.v_first,
          f.csc, f.y_pitch, f.c_pitch);
@@ -106,6 +110,21 @@ static int check_frame(const Frame& f) {
   reference_rgb(f, want);
   if (frmap_yuv_to_rgb_twin(f.y.data(), f.u(), f.v(), f.H, f.W, f.y_pitch, f.c_pitch, f.c_step, f.csc, got.data())) return fail("conversion refused", f);
   if (got != want) return fail("conversion differs from the formula", f);
+  // the packed source's four buffers: the converted picture as RGB and as BGR, rows of a tight and of a padded `pitch`, each
+  // buffer ending with the last pixel of its last row
+  struct Packed { std::vector<unsigned char> bytes; long long pitch; int c0; };
+  std::vector<Packed> packed;
+  for (int variant = 0; variant < 4; ++variant) {
+    Packed pk;
+    pk.c0 = variant & 1 ? 2 : 0;
+    pk.pitch = 3LL * f.W + (variant & 2 ? 7 : 0);
+    pk.bytes.resize((size_t)((f.H - 1) * pk.pitch + 3LL * f.W));
+    for (int y = 0; y < f.H; ++y)
+      for (int x = 0; x < f.W; ++x)
+        for (int c = 0; c < 3; ++c)
+          pk.bytes[(size_t)(y * pk.pitch + 3LL * x + (c == 1 ? 1 : (c == 0 ? pk.c0 : 2 - pk.c0)))] = want[((size_t)y * f.W + x) * 3 + c];
+    packed.push_back(pk);
+  }
   const double cx = f.W / 2.0, cy = f.H / 2.0;
   const double mats[][6] = {
       {1.0, 0.0, 0.0, 0.0, 1.0, 0.0},                                          // identity: the conversion itself
@@ -140,6 +159,15 @@ static int check_frame(const Frame& f) {
               const unsigned char w0 = mi == 0 ? want[((size_t)y * f.W + x) * 3 + c] : 0;
               if (out[((size_t)(y - r[1]) * w + (x - r[0])) * 3 + c] != w0) return fail("identity / all-outside warp is not the conversion / zero", f);
             }
+      for (const Packed& pk : packed)                                          // the packed source, against the same reference
+        for (int y = r[1]; y < r[3]; ++y)
+          for (int x = r[0]; x < r[2]; ++x) {
+            unsigned char o[3], g[3];
+            reference_warp(want, f.H, f.W, m, x, y, o);
+            frmap_rgb_store3(g, frmap_warp_pixel(f.H, f.W, m, x, y, FrmapPackedFetch{pk.bytes.data(), pk.pitch, pk.c0}));
+            if (memcmp(o, g, 3) != 0) return fail("packed warp differs from the warp of the converted frame", f);
+          }
+      g_packed += 4;
     }
   return 0;
 }
@@ -193,6 +221,6 @@ int main() {
           ++frames;
         }
   if (check_rejections()) return 1;
-  printf("yuv_check passed: %d frames\n", frames);
+  printf("yuv_check passed: %d frames, %d packed warp cases\n", frames, g_packed);
   return 0;
 }
