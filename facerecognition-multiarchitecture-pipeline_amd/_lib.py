@@ -65,6 +65,7 @@ PROTOTYPES = {
     "frmap_conv_pp_pitch": (_i, [_i]),
     "frmap_conv_pp_ds": (_i, [_i]),
     "frmap_conv_pp_im": (_i, [_i]),
+    "frmap_conv_wave_start": (_i, [_i]),
     "frmap_conv1x1_pp_layout": (_i, [_i, _i, _i, _i, _i, _i]),
     "frmap_conv3x3_pp_layout": (_i, [_i, _i, _i, _i, _i]),
     "frmap_conv3x3s2_pp_layout": (_i, [_i, _i, _i, _i, _i]),

@@ -501,7 +501,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fast_kernel(const ConvParams p
 // conv3, face_models.py:39-40): the patch's pixels are walked in pool-major order (fragment row i of pixel group mi =
 // window i >> 2 of pooled row mi, pixel i & 3 of it), the transpose takes the max over each window's 4 scratch rows and
 // the tile leaves 2 packed pieces (its 4x4 pooled patch) instead of 8.
-template <typename TT, int NCH = 2, bool POOL = false>
+//
+// EARLY = how a workgroup starts (ConvTuning::wstart).  false: the slab copy waits for each of its 16-byte pieces in turn (9 memory
+// latencies in a row for two chunks), then the barrier, and only then the first tile's halo loads are issued: 10 latencies before
+// the first MFMA, and they are LOADED latencies when another stream's kernel has the memory system busy.  true: the first
+// tile's halo loads are issued first and every piece of the slab right behind them, so nearly all of it is in flight at once (the
+// compiler holds the ninth piece back: two latencies).  The tile loop is the same: outputs are bit-identical.  Step +2.4 to +3.8 %
+// in the default two-stream mode, 1 - 2.5 % on a lone launch (DESIGN.md "Measured (layer-1 load pipeline)").
+template <typename TT, int NCH = 2, bool POOL = false, bool EARLY = true>
 __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvParams p) {
   constexpr int MI = 4, NI = 4, TAPS = 9, NH = 7, NO = POOL ? 2 : 8, NG = TAPS * NI, NL = NO + NH;
   constexpr int PITCH = NI * 64 + 16, HALO = 10 * 16 * 64;
@@ -532,13 +539,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvPara
   int rnd = 0;
   int T = tile_of(0);
 
-  {  // the resident weight slab of channel tile nt (both chunks, all taps), already in LDS-image order
-    const char* wsrc = (const char*)p.wpk + (size_t)nt * wbytes;
-    for (int o = tid * 16; o < wbytes; o += 512 * 16) *(u32x4_t*)(wl + o) = *(const u32x4_t*)(wsrc + o);
-  }
-  __syncthreads();
-  if (T < 0) return;
-
   const int woff = (lr << 6) + ((g ^ (((lr >> 2) & 1) << 1)) << 4);
   const elem* inp = (const elem*)p.in;
   const int img_bytes = p.Hi * p.Wi * p.Cin * (int)sizeof(elem);
@@ -549,11 +549,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvPara
   const int io_lane = POOL ? (int)(lane >> 5) * row_out + ((((lane >> 3) & 3) * p.Cout + co0 + (lane & 7) * 8) * (int)sizeof(elem))
                            : ((lane >> 3) * p.Cout + co0 + (lane & 7) * 8) * (int)sizeof(elem);
   const int io_step = POOL ? 2 * row_out : row_out;   // byte step between pieces
-  float sh[8];
-  {
-    const f32x4_t s0 = *(const f32x4_t*)(p.shift + co0 + (lane & 7) * 8), s1 = *(const f32x4_t*)(p.shift + co0 + (lane & 7) * 8 + 4);
-    sh[0] = s0[0]; sh[1] = s0[1]; sh[2] = s0[2]; sh[3] = s0[3]; sh[4] = s1[0]; sh[5] = s1[1]; sh[6] = s1[2]; sh[7] = s1[3];
-  }
   // fragment row i of pixel group mi = output pixel (mi*2 + (i >> 3), i & 7) of the patch = halo pixel (+kh, +kw)
   int A[MI];
 #pragma unroll
@@ -586,9 +581,36 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_wave_kernel(const ConvPara
     return __builtin_amdgcn_make_buffer_rsrc((void*)((const elem*)base + el), (short)0, live ? (POOL ? 4 : 8) * row_out : 0, 0x00020000);
   };
 
-  setup_load(T, true);
+  auto first_halo = [&](int t, bool live) {  // chunk 0 of the first tile
+    setup_load(t, live);
 #pragma unroll
-  for (int u = 0; u < NH; ++u) hv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)soff[u], 0, 0);
+    for (int u = 0; u < NH; ++u) hv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)soff[u], 0, 0);
+  };
+  // (a wave without a tile issues them through an empty descriptor: nothing is read; it still has to reach the barrier)
+  if (EARLY) first_halo(T < 0 ? 0 : T, T >= 0);
+  {  // the resident weight slab of channel tile nt (both chunks, all taps), already in LDS-image order
+    const char* wsrc = (const char*)p.wpk + (size_t)nt * wbytes;
+    if (EARLY) {
+      constexpr int NW = (wbytes + 512 * 16 - 1) / (512 * 16);   // pieces per thread (NCH = 1: the last one for half the threads)
+      u32x4_t wv[NW];
+#pragma unroll
+      for (int u = 0; u < NW; ++u) wv[u] = *(const u32x4_t*)(wsrc + min(tid * 16 + u * (512 * 16), wbytes - 16));
+#pragma unroll
+      for (int u = 0; u < NW; ++u)
+        if (tid * 16 + u * (512 * 16) < wbytes) *(u32x4_t*)(wl + tid * 16 + u * (512 * 16)) = wv[u];
+    } else {
+      for (int o = tid * 16; o < wbytes; o += 512 * 16) *(u32x4_t*)(wl + o) = *(const u32x4_t*)(wsrc + o);
+    }
+  }
+  __syncthreads();
+  if (T < 0) return;
+
+  float sh[8];
+  {
+    const f32x4_t s0 = *(const f32x4_t*)(p.shift + co0 + (lane & 7) * 8), s1 = *(const f32x4_t*)(p.shift + co0 + (lane & 7) * 8 + 4);
+    sh[0] = s0[0]; sh[1] = s0[1]; sh[2] = s0[2]; sh[3] = s0[3]; sh[4] = s1[0]; sh[5] = s1[1]; sh[6] = s1[2]; sh[7] = s1[3];
+  }
+  if (!EARLY) first_halo(T, true);
   int p_n = -1, p_by = 0, p_bx = 0;  // the tile whose packed outputs sit in ov[]
 
   for (; T >= 0; T = tile_of(++rnd)) {
@@ -1122,6 +1144,7 @@ __global__ void splitk_finalize_kernel(const float* __restrict__ slab, int kspli
 // ------------------------------------------------------------------------------------------------
 static ConvPlan plan_of(const ConvLayer& L) { return conv_plan_launch(L, conv_tuning(), frmap_cu_count(), frmap_batch_invariant() != 0); }
 ConvPlan frmap_conv_plan(const ConvLayer& L) { return plan_of(L); }
+extern "C" int frmap_conv_wave_start(int v) { conv_tuning().h_wstart = v; return 0; }   // conv3x3_c64_wave_kernel<.., EARLY>; -1 = FRMAP_WAVE_START
 extern "C" int frmap_conv3x3_pp_tile_px(int B, int Hi, int Wi, int Cin, int Cout, int stride, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride) {
   if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64 || (stride != 1 && stride != 2)) return 0;
   if (ds_Cin > 0 && (stride != 1 || !frmap_conv_igemm_ds_supported(B, Hi, Wi, Cin, Cout, ds_Hi, ds_Wi, ds_Cin, ds_stride))) return 0;
@@ -1158,6 +1181,11 @@ static ConvParams conv_params(const ConvLayer& L, const ConvPlan& q, const ConvP
 }
 
 typedef void (*conv_kern_t)(const ConvParams);
+template <typename TT, bool EARLY>
+static conv_kern_t wave_kernel(const ConvPlan& q) {
+  if (!q.POOL) return conv3x3_c64_wave_kernel<TT, 2, false, EARLY>;
+  return q.NCH == 2 ? conv3x3_c64_wave_kernel<TT, 2, true, EARLY> : conv3x3_c64_wave_kernel<TT, 1, true, EARLY>;
+}
 template <typename TT>
 static conv_kern_t conv_kernel(const ConvPlan& q) {
   switch (q.kernel) {
@@ -1167,9 +1195,7 @@ static conv_kern_t conv_kernel(const ConvPlan& q) {
       if (q.BM == 256) return q.SWZ == 1 ? conv_igemm_kernel<TT, 256, 3, 1> : conv_igemm_kernel<TT, 256, 3, 2>;
       return q.SWZ == 1 ? conv_igemm_kernel<TT, 128, 3, 1> : conv_igemm_kernel<TT, 128, 3, 2>;
     case CK_1X1: return q.CKS == 4 ? conv1x1_kernel<TT, 4> : (q.CKS == 2 ? conv1x1_kernel<TT, 2> : conv1x1_kernel<TT, 1>);
-    case CK_WAVE:
-      if (!q.POOL) return conv3x3_c64_wave_kernel<TT, 2, false>;
-      return q.NCH == 2 ? conv3x3_c64_wave_kernel<TT, 2, true> : conv3x3_c64_wave_kernel<TT, 1, true>;
+    case CK_WAVE: return q.EARLY ? wave_kernel<TT, true>(q) : wave_kernel<TT, false>(q);
     case CK_FAST: return q.DS ? conv3x3_fast_kernel<TT, true> : conv3x3_fast_kernel<TT, false>;
     case CK_S2_SPLIT: return conv3x3s2_split_kernel<TT>;
     case CK_S2_FAST: return conv3x3s2_fast_kernel<TT>;

@@ -38,7 +38,8 @@ ConvTuning& conv_tuning() {
     v.pitch = env_int("FRMAP_PP_PITCH", 0);
     v.ri = env_int("FRMAP_PP_RI", 0);
     v.im = env_int("FRMAP_PP_IM", 0);
-    v.h_on = v.h_px = v.h_bn = v.h_ks = v.h_ds = v.h_pitch = v.h_im = v.h_ri = -1;
+    v.wstart = env_int("FRMAP_WAVE_START", 1);
+    v.h_on = v.h_px = v.h_bn = v.h_ks = v.h_ds = v.h_pitch = v.h_im = v.h_ri = v.h_wstart = -1;
     return v;
   }();
   return t;
@@ -375,6 +376,7 @@ ConvPlan plan_wave(const ConvLayer& L, const ConvTuning& t, int cus) {
   if (per < 1) per = 1;
   if (per > (total + 7) / 8) per = (total + 7) / 8;
   q.kernel = CK_WAVE; q.NCH = L.Cin / 32; q.POOL = pool; q.KS = 3;
+  q.EARLY = ConvTuning::pick(t.h_wstart, t.wstart) != 0;
   q.nblocks = per * ntiles; q.ntiles = ntiles;
   q.Wp = L.Wi + 2;
   q.layout = pool ? 2 : 0;

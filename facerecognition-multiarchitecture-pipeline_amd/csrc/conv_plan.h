@@ -30,7 +30,7 @@
 #include <stdint.h>
 
 // Every knob of the planners: environment values (read once, on first use of conv_tuning()) and the run-time hooks
-// (frmap_conv_pp_tuning / _ri / _pitch / _ds / _im write here; -1 = not set, the environment or the heuristic decides).
+// (frmap_conv_pp_tuning / _ri / _pitch / _ds / _im and frmap_conv_wave_start write here; -1 = not set, the environment or the heuristic decides).
 struct ConvTuning {
   int debug;            // FRMAP_CONV_DEBUG (0): timing ablations of conv_igemm_kernel; any value keeps every other kernel out
   int s2fast;           // FRMAP_CONV_S2FAST (1)
@@ -51,7 +51,9 @@ struct ConvTuning {
   int pitch;            // FRMAP_PP_PITCH (0): conflict-free halo pitch
   int ri;               // FRMAP_PP_RI (0): fragment reads interleaved with the MFMAs
   int im;               // FRMAP_PP_IM (0): measured 4-6 % slower than issuing the DMA in the LOAD segments
-  int h_on, h_px, h_bn, h_ks, h_ds, h_pitch, h_im, h_ri;   // hooks
+  int wstart;           // FRMAP_WAVE_START (1): conv3x3_c64_wave_kernel issues its first tile's halo loads and every piece of the
+                        // weight slab at once (0: the slab piece by piece, then the halo; A/B and tests)
+  int h_on, h_px, h_bn, h_ks, h_ds, h_pitch, h_im, h_ri, h_wstart;   // hooks
 
   void set_tuning(int enable, int px, int bn_) {   // frmap_conv_pp_tuning; bn 1282 = the 128-channel tile with split-K
     h_on = enable;
@@ -91,6 +93,7 @@ struct ConvPlan {
   int BM, KS, SWZ, CKS, NCH;       // first generation (KS: taps per side there, split-K groups in the second generation)
   int MI, WM, NHP;                 // second generation
   bool DS, IM, PL, RI, POOL;
+  bool EARLY;                      // wave kernel: ConvTuning::wstart
   int tile_px, mtiles, ntiles;     // second generation: grid = mtiles * ntiles
   int nblocks;                     // the grid, every family
   int halo_bytes, Wp, lds_bytes, ksplit;

@@ -362,6 +362,10 @@ int frmap_conv_pp_ri(int v);
 int frmap_conv_pp_pitch(int v);
 int frmap_conv_pp_ds(int v);
 int frmap_conv_pp_im(int v);
+/* A/B and test hook of the layer-1 kernel's start-up (conv3x3_c64_wave_kernel, with or without the fused pool): 1 = the first
+ * tile's halo loads and every piece of the resident weight slab are issued at once, 0 = the slab piece by piece, then the halo
+ * (the form before), -1 = environment (FRMAP_WAVE_START, default 1).  The tile loop is the same: outputs are bit-identical. */
+int frmap_conv_wave_start(int v);
 /* Which layout frmap_conv_igemm gives a 3x3 stride-1 pad-1 layer without a fused shortcut: 0 = a first-generation
  * kernel; conv3x3_pp_kernel with 1 = 224 px x 256 ch tiles, 2 = 448 px x 128 ch, 3 = 224 px x 128 ch split-K. */
 int frmap_conv3x3_pp_layout(int B, int Hi, int Wi, int Cin, int Cout);
