@@ -122,6 +122,90 @@ PROTOTYPES = {
     "frmap_model_destroy": (None, [_vp]),
 }
 
+# Pointer alignment of every device-pointer argument of every launching entry point (include/frmap_hip.h, Conventions, "pointer
+# alignment"): entry point -> {argument: (class, bytes)}.  `bytes` is what the launcher rejects below - the widest access a kernel
+# behind it makes through the pointer; where the launcher picks a narrower path for some shapes (odd H * W, D % 512 != 0, ...) this is
+# the widest of them, so a tensor that meets it is accepted whatever the shape.  A class's default is in ALIGN_CLASS (None: the
+# element size); an argument that departs from it has its own note in the header.  tests/test_place_cpu.py compares both with the header.
+ALIGN_CLASS = {
+    "tensor": 16,      # activations, residuals, packed weights / galleries, fp16 splits and outputs in `dtype`
+    "vector": 16,      # fp32 per-channel vectors of the MFMA kernels (shift; pos / gamma / beta of add_pos_layernorm)
+    "matrix": 16,      # fp32 matrices a GEMM, the exact re-score or the tracker reads in float4 pieces (rows are multiples of 4)
+    "element": None,   # everything walked element by element
+    "record": 8,       # records with 8-byte fields or int32 pairs
+    "workspace": 16,   # scratch and state buffers
+}
+_T, _V, _M, _R, _W = ("tensor", 16), ("vector", 16), ("matrix", 16), ("record", 8), ("workspace", 16)
+_W256 = ("workspace", 256)
+_E1, _E2, _E4, _E8 = (("element", n) for n in (1, 2, 4, 8))
+_TOP1_OUT = {"idx_out": _E4, "dist_out": _E4, "id_or_unknown_out": _E4, "packed_out": _E4}
+_PAIRS = {"a": _M, "label_a": _E4, "b": _M, "label_b": _E4}
+_CROP = {"frames": _R, "rois": _E4, "out": _E1}
+_STEM = {"w_packed_c3": _T, "shift": _V, "out": _T}
+ALIGNMENT = {
+    "frmap_pack_input_nchw_f32": {"x_nchw": _E4, "out_nhwc4": ("tensor", 8)},
+    "frmap_normalize_u8_hwc": {"img_u8": _E1, "out_nchw_f32": _E4, "out_nhwc4": ("tensor", 8)},
+    "frmap_resize_bilinear_u8": {"src_pool": _E1, "items": _R, "tables": _E4, "out": _E1},
+    "frmap_crop_resize_u8": _CROP,
+    "frmap_align_crop_resize_u8": {"frames": _R, "rois": _E4, "mats": _R, "out": _E1},
+    "frmap_crop_resize_yuv": _CROP,
+    "frmap_align_crop_resize_yuv": {"frames": _R, "rois": _E4, "mats": _R, "out": _E1},
+    "frmap_track_step": {"state": _W, "boxes": _M, "probs": _E4, "counts": _E4, "frame_hw": _E4, "ids_out": _E4, "rois_out": ("record", 16)},
+    "frmap_track_fuse": {"state": _W, "ids": _E4, "counts": _E4, "emb": _M, "rows": _R, "fused": _M, "frames_out": _E4},
+    "frmap_pack_conv_weight": {"w_oihw": _E4, "w_packed": ("tensor", 2)},
+    "frmap_pack_conv_weight_c3": {"w_oihw": _E4, "w_packed": ("tensor", 2)},
+    "frmap_conv_small_cin": {"in_nhwc4": ("tensor", 8), "w_packed": _T, "shift": _V, "out": _T},
+    "frmap_conv_small_cin_pool2": {"in_nhwc4": ("tensor", 8), "w_packed": _T, "shift": _V, "out": _T},
+    "frmap_stem7x7_maxpool": {"x_nchw": _E4, **_STEM},
+    "frmap_stem7x7_maxpool2": {"x_nchw": _E4, **_STEM},
+    "frmap_stem7x7_maxpool_u8": {"x_u8_hwc": ("element", 4), **_STEM},
+    "frmap_conv_igemm": {"in": _T, "w_packed": _T, "shift": _V, "residual": _T, "out": _T},
+    "frmap_conv_igemm_pool2": {"in": _T, "w_packed": _T, "shift": _V, "out": _T},
+    "frmap_conv_igemm_ds": {"in": _T, "w_packed": _T, "shift": _V, "ds_in": _T, "ds_w_packed": _T, "out": _T},
+    "frmap_linear_mfma": {"x": _T, "w_packed": _T, "shift": _V, "residual": _T, "out": _T, "workspace": _W},
+    "frmap_maxpool": {"in": _T, "out": _T},
+    "frmap_avgpool_global": {"in": _T, "out_f32": _E4},
+    "frmap_avgpool_adaptive": {"in": _T, "out": _T},
+    "frmap_linear_f32": {"x": _M, "w": _M, "scale": _E4, "shift": _E4, "out": _E4},
+    "frmap_l2_normalize_f32": {"x": _E4, "out": _E4},
+    "frmap_cast_to_f32": {"in": _E2, "out": _E4},
+    "frmap_cast_from_f32": {"in": _E4, "out": _E2},
+    "frmap_add_pos_layernorm": {"x": _T, "pos": _V, "gamma": _V, "beta": _V, "t_out": _T, "y_out": _T},
+    "frmap_mha_tokens": {"qkv": _T, "out": _T},
+    "frmap_mean_layernorm": {"t": _T, "gamma": _E4, "beta": _E4, "out_f32": _E4},
+    "frmap_cnn_attention": {"qkv": _T, "x": _T, "gamma": _E4, "spatial_w": _E4, "spatial_b": _E4, "out_map": ("tensor", 4), "out_pool": _E4},
+    "frmap_softmax_argmax": {"logits": _E4, "probs_out": _E4, "pred_out": _E4},
+    "frmap_pairwise_distance": {"a": _E4, "b": _E4, "dist_out": _E4, "same_out": _E4},
+    "frmap_match_top1": {"emb": _M, "gallery": _M, **_TOP1_OUT, "workspace": _W},
+    "frmap_match_pack_gallery": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
+    "frmap_match_pack_gallery_rows": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
+    "frmap_match_top1_packed": {"emb": _M, "gallery": _M, "gallery_packed": _T, "stat_w": _M, **_TOP1_OUT, "workspace": _W, "probe_split": _T},
+    "frmap_match_topk": {"emb": _M, "gallery": _M, "labels": _E4, "idx_out": _E4, "dist_out": _E4, "label_out": _E4, "workspace": _W256},
+    "frmap_match_topk_packed": {"emb": _M, "gallery": _M, "gallery_packed": _T, "stat_w": _M, "labels": _E4, "idx_out": _E4, "dist_out": _E4,
+                                "label_out": _E4, "workspace": _W256},
+    "frmap_verify_counts": {**_PAIRS, "thresholds": _E4, "accepted_out": _E8, "rescored_out": _E8, "workspace": _W256},
+    "frmap_verify_counts_packed": {"a": _M, "label_a": _E4, "b": _M, "b_packed": _T, "stat_w": _M, "label_b": _E4, "thresholds": _E4,
+                                   "accepted_out": _E8, "rescored_out": _E8, "workspace": _W256},
+    "frmap_match_radius": {**_PAIRS, "count_out": _E4, "total_out": _E8, "pair_out": _R, "dist_out": _E4, "rescored_out": _E8,
+                           "workspace": _W256},
+    "frmap_match_radius_packed": {"a": _M, "label_a": _E4, "b": _M, "b_packed": _T, "stat_w": _M, "label_b": _E4, "count_out": _E4,
+                                  "total_out": _E8, "pair_out": _R, "dist_out": _E4, "rescored_out": _E8, "workspace": _W256},
+    "frmap_gap_norm_match": {"map": _T, "gallery": _M, "emb_out": _E4, **_TOP1_OUT},
+    "frmap_gap_linear_norm": {"map": _T, "wt": _E4, "scale": _E4, "shift": _E4, "pre_out": _E4, "emb_out": _E4},
+    "frmap_cosine_logits": {"x": _M, "w": _M, "logits_out": _E4, "argmax_out": _E4, "workspace": _W},
+    "frmap_arcmargin_eval": {"x": _M, "w": _M, "label": _E8, "logits_out": _E4, "minmax_out": _E4, "workspace": _W},
+    "frmap_model_forward": {"x": ("element", 4), "out": _T, "workspace": _W256},
+    "frmap_model_embed_and_match": {"x": ("element", 4), "gallery": _M, "gallery_packed": _T, "gallery_stat": _M, **_TOP1_OUT, "emb_out": _M,
+                                    "workspace": _W256},
+    "frmap_model_embed_and_search": {"x": ("element", 4), "gallery": _M, "gallery_packed": _T, "gallery_stat": _M, "labels": _E4, "idx_out": _E4,
+                                     "dist_out": _E4, "label_out": _E4, "emb_out": _M, "workspace": _W256},
+}
+
+
+def align_of(entry: str, arg: str) -> int:
+    """Bytes a tensor handed to `entry` as `arg` must be aligned to (KeyError for a name the header does not have)."""
+    return ALIGNMENT[entry][arg][1]
+
 
 def lib_available() -> bool:
     return os.path.isfile(LIB_PATH)

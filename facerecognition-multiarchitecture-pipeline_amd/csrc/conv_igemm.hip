@@ -1219,8 +1219,23 @@ static int conv_run(const ConvLayer& L, const ConvPlan& q, const ConvPtrs& a, in
   return conv_launch(q, conv_params(L, q, a, relu, L.fuse == FUSE_POOL2 ? 0 : conv_tuning().debug), dtype, st);
 }
 
-static int conv_igemm_impl(const ConvLayer& L, const ConvPtrs& a, int relu, int dtype, void* stream) {
+// every operand is read or written in 16-byte pieces: LDS-DMA and buffer loads of `in`, `ds_in` and the packed weights, the
+// epilogue's f32x4 loads of `shift` and its 16-byte residual loads and output stores (frmap_common.h: conv_epilogue)
+static int conv_require_aligned(const char* who, const ConvPtrs& a, const char* in_name = "in") {
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.in, 16, in_name);
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.w, 16, "w_packed");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.shift, 16, "shift");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.res, 16, "residual");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.out, 16, "out");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.ds_in, 16, "ds_in");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.ds_w, 16, "ds_w_packed");
+  FRMAP_REQUIRE_ALIGNED_AS(who, a.slab, 16, "workspace");
+  return 0;
+}
+
+static int conv_igemm_impl(const char* who, const ConvLayer& L, const ConvPtrs& a, int relu, int dtype, void* stream) {
   FRMAP_REQUIRE(a.in && a.w && a.shift && a.out, "conv_igemm: null pointer");
+  if (int rc = conv_require_aligned(who, a)) return rc;
   FRMAP_REQUIRE(L.K == 1 || L.K == 3, "conv_igemm: kernel size %d not supported (1 or 3)", L.K);
   FRMAP_REQUIRE(L.stride == 1 || L.stride == 2, "conv_igemm: stride %d not supported", L.stride);
   FRMAP_REQUIRE((L.K == 3 && L.pad == 1) || (L.K == 1 && L.pad == 0), "conv_igemm: pad %d with K=%d not supported", L.pad, L.K);
@@ -1240,7 +1255,7 @@ extern "C" int frmap_conv_igemm(const void* in, const void* w_packed, const floa
                                 void* out, int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int pad,
                                 int relu, int dtype, void* stream) {
   const ConvLayer L = {B, Hi, Wi, Cin, Cout, K, stride, pad, residual ? FUSE_RESIDUAL : FUSE_NONE, 0, 0, 0, 0};
-  return conv_igemm_impl(L, ConvPtrs{in, w_packed, shift, residual, out, nullptr, nullptr, nullptr}, relu, dtype, stream);
+  return conv_igemm_impl("conv_igemm", L, ConvPtrs{in, w_packed, shift, residual, out, nullptr, nullptr, nullptr}, relu, dtype, stream);
 }
 
 extern "C" int frmap_conv_igemm_ds_supported(int B, int Hi, int Wi, int Cin, int Cout, int ds_Hi, int ds_Wi, int ds_Cin,
@@ -1254,7 +1269,7 @@ extern "C" int frmap_conv_igemm_ds(const void* in, const void* w_packed, const f
                                    int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride, int relu, int dtype, void* stream) {
   FRMAP_REQUIRE(ds_in && ds_w_packed, "conv_igemm_ds: null shortcut pointer");
   const ConvLayer L = {B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_SHORTCUT, ds_Hi, ds_Wi, ds_Cin, ds_stride};
-  return conv_igemm_impl(L, ConvPtrs{in, w_packed, shift, nullptr, out, ds_in, ds_w_packed, nullptr}, relu, dtype, stream);
+  return conv_igemm_impl("conv_igemm_ds", L, ConvPtrs{in, w_packed, shift, nullptr, out, ds_in, ds_w_packed, nullptr}, relu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1279,6 +1294,7 @@ extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, cons
   FRMAP_REQUIRE(in && w_packed && shift && out, "conv_igemm_pool2: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm_pool2: bad dtype %d", dtype);
   FRMAP_REQUIRE(relu == 0 || relu == 1, "conv_igemm_pool2: activation %d does not commute with the max", relu);
+  if (int rc = conv_require_aligned("conv_igemm_pool2", ConvPtrs{in, w_packed, shift, nullptr, out, nullptr, nullptr, nullptr})) return rc;
   const ConvLayer L = {B, Hi, Wi, Cin, Cout, 3, 1, 1, FUSE_POOL2, 0, 0, 0, 0};
   const ConvPlan q = plan_of(L);
   FRMAP_REQUIRE(q.taken(),
@@ -1305,6 +1321,7 @@ extern "C" int frmap_linear_mfma(const void* x, const void* w_packed, const floa
   FRMAP_REQUIRE(x && w_packed && shift && out, "linear_mfma: null pointer");
   FRMAP_REQUIRE(M > 0 && K > 0 && K % 32 == 0 && N > 0 && N % 64 == 0, "linear_mfma: need K %% 32 == 0 and N %% 64 == 0 (M=%d K=%d N=%d)", M, K, N);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "linear_mfma: bad dtype");
+  if (int rc = conv_require_aligned("linear_mfma", ConvPtrs{x, w_packed, shift, residual, out, nullptr, nullptr, (float*)workspace}, "x")) return rc;
   const int ks = linear_ksplit(M, K, N, frmap_batch_invariant() != 0);
   if (ks == 1) return frmap_conv_igemm(x, w_packed, shift, residual, out, M, 1, 1, K, N, 1, 1, 0, act, dtype, stream);
   FRMAP_REQUIRE(workspace, "linear_mfma: workspace required (frmap_linear_mfma_workspace_bytes)");

@@ -221,6 +221,11 @@ static int small_cin_impl(const void* in_nhwc4, const void* w_packed, const floa
                           int relu, int dtype, bool pool, void* stream) {
   FRMAP_REQUIRE(in_nhwc4 && w_packed && shift && out, "conv_small_cin: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_small_cin: bad dtype %d", dtype);
+  // NHWC4 pixels are staged 8 bytes at a time; the weight image, `shift` and the output go through 16-byte accesses
+  FRMAP_REQUIRE_ALIGNED_AS("conv_small_cin", in_nhwc4, 8, "in_nhwc4");
+  FRMAP_REQUIRE_ALIGNED_AS("conv_small_cin", w_packed, 16, "w_packed");
+  FRMAP_REQUIRE_ALIGNED_AS("conv_small_cin", shift, 16, "shift");
+  FRMAP_REQUIRE_ALIGNED_AS("conv_small_cin", out, 16, "out");
   const bool stem7 = (KH == 7 && KW == 7 && stride == 2 && pad == 3 && Cout == 64);
   const bool first3 = (KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cout == 32);
   FRMAP_REQUIRE(stem7 || first3, "conv_small_cin: unsupported geometry k=%dx%d s=%d p=%d Cout=%d", KH, KW, stride,

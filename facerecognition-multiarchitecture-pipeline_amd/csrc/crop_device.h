@@ -128,6 +128,9 @@ int frmap_crop_launch(const char* name, const void* kernel, bool need_mats, cons
   if (N == 0) return 0;
   FRMAP_REQUIRE(frames && rois && out && (mats || !need_mats), "%s: null pointer", name);
   FRMAP_REQUIRE(((uintptr_t)mats & 7) == 0, "%s: mats must be 8-byte aligned", name);
+  // (the frame records start with uint64 plane addresses; the ROI records are int32; the output is byte-addressed)
+  FRMAP_REQUIRE_ALIGNED_AS(name, frames, 8, "frames");
+  FRMAP_REQUIRE_ALIGNED_AS(name, rois, 4, "rois");
   FRMAP_REQUIRE(n_frames > 0 && out_h > 0 && out_w > 0 && out_h <= 65536 && out_w <= 65536 && max_roi_h > 0 && max_roi_w > 0 &&
                     max_roi_h <= (1 << 24) && max_roi_w <= (1 << 24),
                 "%s: bad shape", name);

@@ -294,6 +294,14 @@ int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, 
       return -1;                        \
     }                                   \
   } while (0)
+// Pointer alignment (include/frmap_hip.h, Conventions): `bytes` (a power of two) is the widest access any kernel behind the entry
+// point makes through `ptr` - a 16-byte vector load, store or LDS-DMA fetch, an 8-byte record, or one element.  A pointer below it
+// is rejected like any other bad argument, before any HIP call; NULL passes (an optional argument is checked when it is given).
+// `name` is the argument as the header spells it; the entry point is the enclosing function ("frmap_" dropped), or `who` where
+// several entry points share the checks.
+#define FRMAP_REQUIRE_ALIGNED_AS(who, ptr, bytes, name)                                                                     \
+  FRMAP_REQUIRE(((uintptr_t)(ptr) & (uintptr_t)((bytes) - 1)) == 0, "%s: %s must be %d-byte aligned", who, name, (int)(bytes))
+#define FRMAP_REQUIRE_ALIGNED(ptr, bytes, name) FRMAP_REQUIRE_ALIGNED_AS(__func__ + 6, ptr, bytes, name)
 // A grid holds fewer than 2^32 threads per dimension: the dispatch packet counts work-items in 32 bits, and a larger grid is cut down
 // modulo 2^32 WITHOUT an error (seen on gfx950: a launch of 2^34 + 1024 threads ran 1024 of them and left the rest of its output
 // unwritten).  Every launcher whose grid grows with the batch states the limit that follows and checks it before the launch.

@@ -527,6 +527,14 @@ extern "C" int frmap_gap_norm_match(const void* map, const float* gallery, float
   FRMAP_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 8 == 0 && C <= 4096, "gap_norm_match: bad shape B=%d HW=%d C=%d", B, HW, C);
   FRMAP_REQUIRE(B <= FRMAP_GRID_WG256_MAX, "gap_norm_match: %d faces exceed the grid (at most %d)", B, FRMAP_GRID_WG256_MAX);
   FRMAP_REQUIRE(G >= 0 && G <= 64 && (G == 0 || gallery), "gap_norm_match: gallery of 0..64 rows expected (got %d)", G);
+  // the map and the gallery rows (C % 8 == 0) are read in 16-byte pieces; every output is written element by element
+  FRMAP_REQUIRE_ALIGNED(map, 16, "map");
+  FRMAP_REQUIRE_ALIGNED(gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED(emb_out, 4, "emb_out");
+  FRMAP_REQUIRE_ALIGNED(idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED(dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED(id_or_unknown_out, 4, "id_or_unknown_out");
+  FRMAP_REQUIRE_ALIGNED(packed_out, 4, "packed_out");
   const int c8 = C / 8, nparts = c8 < 256 ? 256 / c8 : 1;
   const size_t lds = (size_t)(C + 8 + nparts * C) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
@@ -719,6 +727,12 @@ extern "C" int frmap_gap_linear_norm(const void* map, const float* wt, const flo
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "gap_linear_norm: bad dtype");
   FRMAP_REQUIRE(B > 0 && HW > 0 && K > 0 && K % 8 == 0 && K <= 2048, "gap_linear_norm: bad shape B=%d HW=%d K=%d", B, HW, K);
   FRMAP_REQUIRE(N == 256 || N == 512, "gap_linear_norm: N=%d not supported (256 or 512)", N);
+  FRMAP_REQUIRE_ALIGNED(map, 16, "map");
+  FRMAP_REQUIRE_ALIGNED(wt, 4, "wt");
+  FRMAP_REQUIRE_ALIGNED(scale, 4, "scale");
+  FRMAP_REQUIRE_ALIGNED(shift, 4, "shift");
+  FRMAP_REQUIRE_ALIGNED(pre_out, 4, "pre_out");
+  FRMAP_REQUIRE_ALIGNED(emb_out, 4, "emb_out");
   constexpr int FB = 8;
   const int c8n = K / 8, nsubh = c8n >= 64 ? 1 : 64 / c8n;
   const size_t lds = (size_t)(K * FB + FB * 4 + (nsubh > 1 ? FB * nsubh * K : 0)) * sizeof(float);
@@ -810,6 +824,12 @@ extern "C" int frmap_linear_f32(const float* x, const float* w, const float* sca
                                 int B, int K, int N, int relu, void* stream) {
   FRMAP_REQUIRE(x && w && out, "linear_f32: null pointer");
   FRMAP_REQUIRE(B > 0 && K > 0 && N > 0 && K % 4 == 0, "linear_f32: bad shape B=%d K=%d N=%d (K %% 4 == 0)", B, K, N);
+  // (gemm_nt_f32_kernel stages both operands with float4 loads)
+  FRMAP_REQUIRE_ALIGNED(x, 16, "x");
+  FRMAP_REQUIRE_ALIGNED(w, 16, "w");
+  FRMAP_REQUIRE_ALIGNED(scale, 4, "scale");
+  FRMAP_REQUIRE_ALIGNED(shift, 4, "shift");
+  FRMAP_REQUIRE_ALIGNED(out, 4, "out");
   GemmEpi ep = {};
   ep.scale = scale; ep.shift = shift; ep.relu = relu; ep.out = out;
   return launch_gemm<MODE_LINEAR>(x, w, B, N, K, ep, (hipStream_t)stream);
@@ -818,6 +838,8 @@ extern "C" int frmap_linear_f32(const float* x, const float* w, const float* sca
 extern "C" int frmap_l2_normalize_f32(const float* x, float* out, int B, int D, float eps, void* stream) {
   FRMAP_REQUIRE(x && out, "l2_normalize: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0, "l2_normalize: bad shape");
+  FRMAP_REQUIRE_ALIGNED(x, 4, "x");
+  FRMAP_REQUIRE_ALIGNED(out, 4, "out");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "l2_normalize: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(l2_normalize_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, x, out, B, D, eps);
   FRMAP_LAUNCH_CHECK();
@@ -827,6 +849,9 @@ extern "C" int frmap_l2_normalize_f32(const float* x, float* out, int B, int D, 
 extern "C" int frmap_softmax_argmax(const float* logits, float* probs_out, int32_t* pred_out, int B, int C, void* stream) {
   FRMAP_REQUIRE(logits && (probs_out || pred_out), "softmax_argmax: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0, "softmax_argmax: bad shape");
+  FRMAP_REQUIRE_ALIGNED(logits, 4, "logits");
+  FRMAP_REQUIRE_ALIGNED(probs_out, 4, "probs_out");
+  FRMAP_REQUIRE_ALIGNED(pred_out, 4, "pred_out");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "softmax_argmax: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(softmax_argmax_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, logits, probs_out, pred_out, B, C);
   FRMAP_LAUNCH_CHECK();
@@ -837,6 +862,10 @@ extern "C" int frmap_pairwise_distance(const float* a, const float* b, float* di
                                        int B, int D, void* stream) {
   FRMAP_REQUIRE(a && b && dist_out, "pairwise_distance: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0, "pairwise_distance: bad shape");
+  FRMAP_REQUIRE_ALIGNED(a, 4, "a");
+  FRMAP_REQUIRE_ALIGNED(b, 4, "b");
+  FRMAP_REQUIRE_ALIGNED(dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED(same_out, 4, "same_out");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "pairwise_distance: %d rows exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipLaunchKernelGGL(pairwise_distance_kernel, dim3(waves_blocks(B)), dim3(256), 0, (hipStream_t)stream, a, b, dist_out, same_out, thresh, B, D);
   FRMAP_LAUNCH_CHECK();
@@ -888,6 +917,14 @@ extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t*
   FRMAP_REQUIRE(emb && idx_out && dist_out && workspace, "match_top1: null pointer");
   FRMAP_REQUIRE(B > 0 && D > 0 && D % 4 == 0 && G >= 0, "match_top1: bad shape B=%d G=%d D=%d", B, G, D);
   FRMAP_REQUIRE(G == 0 || gallery, "match_top1: null gallery");
+  // the GEMM and the exact re-score read probe and gallery rows as float4 (D % 4 == 0); the workspace starts with 16-byte records
+  FRMAP_REQUIRE_ALIGNED(emb, 16, "emb");
+  FRMAP_REQUIRE_ALIGNED(gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED(idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED(dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED(id_or_unknown_out, 4, "id_or_unknown_out");
+  FRMAP_REQUIRE_ALIGNED(packed_out, 4, "packed_out");
+  FRMAP_REQUIRE_ALIGNED(workspace, 16, "workspace");
   // (G <= 64: one workgroup a probe; else one wave a probe and a gallery row)
   FRMAP_REQUIRE(B <= (G <= 64 ? FRMAP_GRID_WG256_MAX : FRMAP_GRID_ROWS_MAX) && G <= FRMAP_GRID_ROWS_MAX, "match_top1: B=%d or G=%d exceeds the grid", B, G);
   hipStream_t st = (hipStream_t)stream;
@@ -1002,6 +1039,9 @@ static int match_pack_rows(const float* gallery, void* packed_out, float* stat_w
 extern "C" int frmap_match_pack_gallery(const float* gallery, void* packed_out, float* stat_w_out, int G, int D, void* stream) {
   FRMAP_REQUIRE(gallery && packed_out && stat_w_out, "match_pack_gallery: null pointer");
   FRMAP_REQUIRE(G > 0 && D > 0 && D % 32 == 0, "match_pack_gallery: bad shape G=%d D=%d (D %% 32 == 0)", G, D);
+  FRMAP_REQUIRE_ALIGNED(gallery, 4, "gallery");
+  FRMAP_REQUIRE_ALIGNED(packed_out, 2, "packed_out");
+  FRMAP_REQUIRE_ALIGNED(stat_w_out, 4, "stat_w_out");
   FRMAP_REQUIRE(G <= FRMAP_GRID_ROWS_MAX, "match_pack_gallery: %d rows exceed the grid (at most %d)", G, FRMAP_GRID_ROWS_MAX);
   return match_pack_rows(gallery, packed_out, stat_w_out, 0, G, G, D, (hipStream_t)stream);
 }
@@ -1014,6 +1054,9 @@ extern "C" int frmap_match_pack_gallery_rows(const float* gallery, void* packed_
   FRMAP_REQUIRE(gallery && packed_out && stat_w_out, "match_pack_gallery_rows: null pointer");
   FRMAP_REQUIRE(G > 0 && D > 0 && D % 32 == 0 && row_lo >= 0 && row_lo < row_hi && row_hi <= G,
                 "match_pack_gallery_rows: bad range [%d, %d) of G=%d D=%d", row_lo, row_hi, G, D);
+  FRMAP_REQUIRE_ALIGNED(gallery, 4, "gallery");
+  FRMAP_REQUIRE_ALIGNED(packed_out, 2, "packed_out");
+  FRMAP_REQUIRE_ALIGNED(stat_w_out, 4, "stat_w_out");
   return match_pack_rows(gallery, packed_out, stat_w_out, row_lo, row_hi, G, D, (hipStream_t)stream);
 }
 
@@ -1034,6 +1077,16 @@ extern "C" int frmap_match_top1_packed(const float* emb, const float* gallery, c
                                        float thresh, void* workspace, void* probe_split, int B, int G, int D, void* stream) {
   FRMAP_REQUIRE(emb && gallery && gallery_packed && stat_w && idx_out && dist_out && workspace && probe_split, "match_top1_packed: null pointer");
   FRMAP_REQUIRE(B > 0 && G > 0 && D > 0 && D % 32 == 0, "match_top1_packed: bad shape B=%d G=%d D=%d", B, G, D);
+  FRMAP_REQUIRE_ALIGNED(emb, 16, "emb");
+  FRMAP_REQUIRE_ALIGNED(gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED(gallery_packed, 16, "gallery_packed");
+  FRMAP_REQUIRE_ALIGNED(stat_w, 16, "stat_w");
+  FRMAP_REQUIRE_ALIGNED(idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED(dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED(id_or_unknown_out, 4, "id_or_unknown_out");
+  FRMAP_REQUIRE_ALIGNED(packed_out, 4, "packed_out");
+  FRMAP_REQUIRE_ALIGNED(workspace, 16, "workspace");
+  FRMAP_REQUIRE_ALIGNED(probe_split, 16, "probe_split");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX, "match_top1_packed: %d probes exceed the grid (at most %d)", B, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   const Top1Ws w = top1_ws(workspace, B, G, true);
@@ -1221,6 +1274,11 @@ static int topk_check(const char* what, const float* emb, const float* gallery, 
   FRMAP_REQUIRE(k >= 1 && k <= 64, "%s: k=%d out of range (1 <= k <= 64)", what, k);
   FRMAP_REQUIRE(B > 0 && D > 0 && D % 4 == 0 && G >= 0, "%s: bad shape B=%d G=%d D=%d", what, B, G, D);
   FRMAP_REQUIRE(G == 0 || gallery, "%s: null gallery", what);
+  FRMAP_REQUIRE_ALIGNED_AS(what, emb, 16, "emb");
+  FRMAP_REQUIRE_ALIGNED_AS(what, gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED_AS(what, idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, workspace, 256, "workspace");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && G <= FRMAP_GRID_ROWS_MAX, "%s: B=%d or G=%d exceeds the grid (at most %d rows)", what, B, G,
                 FRMAP_GRID_ROWS_MAX);
   return 0;
@@ -1236,6 +1294,8 @@ int frmap_match_topk_fill_labels(int32_t* label_out, int n, hipStream_t st) {
 extern "C" int frmap_match_topk(const float* emb, const float* gallery, const int32_t* labels, int32_t* idx_out, float* dist_out,
                                 int32_t* label_out, void* workspace, int B, int G, int D, int k, void* stream) {
   if (int rc = topk_check("match_topk", emb, gallery, idx_out, dist_out, workspace, B, G, D, k)) return rc;
+  FRMAP_REQUIRE_ALIGNED(labels, 4, "labels");
+  FRMAP_REQUIRE_ALIGNED(label_out, 4, "label_out");
   hipStream_t st = (hipStream_t)stream;
   if (k == 1 && !labels) {
     const int rc = frmap_match_top1(emb, gallery, idx_out, dist_out, nullptr, nullptr, INFINITY, workspace, B, G, D, stream);
@@ -1256,6 +1316,10 @@ extern "C" int frmap_match_topk_packed(const float* emb, const float* gallery, c
                                        void* workspace, int B, int G, int D, int k, void* stream) {
   if (int rc = topk_check("match_topk_packed", emb, gallery, idx_out, dist_out, workspace, B, G, D, k)) return rc;
   FRMAP_REQUIRE(gallery_packed && stat_w, "match_topk_packed: null pointer");
+  FRMAP_REQUIRE_ALIGNED(gallery_packed, 16, "gallery_packed");
+  FRMAP_REQUIRE_ALIGNED(stat_w, 16, "stat_w");
+  FRMAP_REQUIRE_ALIGNED(labels, 4, "labels");
+  FRMAP_REQUIRE_ALIGNED(label_out, 4, "label_out");
   FRMAP_REQUIRE(G > 0 && D % 32 == 0, "match_topk_packed: bad shape B=%d G=%d D=%d (G > 0, D %% 32 == 0)", B, G, D);
   hipStream_t st = (hipStream_t)stream;
   const TopkWs w = topk_ws(workspace, B, G, D);
@@ -1388,6 +1452,13 @@ static int verify_check(const char* what, const float* a, const int32_t* label_a
   FRMAP_REQUIRE(P >= 0 && Q >= 0 && D > 0 && D % 4 == 0, "%s: bad shape P=%d Q=%d D=%d (D %% 4 == 0)", what, P, Q, D);
   FRMAP_REQUIRE(P == 0 || (a && label_a), "%s: null A or its labels", what);
   FRMAP_REQUIRE(Q == 0 || (b && label_b), "%s: null B or its labels", what);
+  FRMAP_REQUIRE_ALIGNED_AS(what, a, 16, "a");
+  FRMAP_REQUIRE_ALIGNED_AS(what, label_a, 4, "label_a");
+  FRMAP_REQUIRE_ALIGNED_AS(what, b, 16, "b");
+  FRMAP_REQUIRE_ALIGNED_AS(what, label_b, 4, "label_b");
+  FRMAP_REQUIRE_ALIGNED_AS(what, thresholds, 4, "thresholds");
+  FRMAP_REQUIRE_ALIGNED_AS(what, accepted_out, 8, "accepted_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, workspace, 256, "workspace");
   FRMAP_REQUIRE(a_row0 == -1 || (a_row0 >= 0 && (long long)a_row0 + P <= Q),
                 "%s: a_row0=%d with P=%d is not a block of B's %d rows (-1: cross mode)", what, a_row0, P, Q);
   return 0;
@@ -1413,6 +1484,7 @@ extern "C" int frmap_verify_counts(const float* a, const int32_t* label_a, int P
                                    int a_row0, const float* thresholds, int T, uint64_t* accepted_out, uint64_t* rescored_out,
                                    void* workspace, void* stream) {
   if (int rc = verify_check("verify_counts", a, label_a, P, b, label_b, Q, D, a_row0, thresholds, T, accepted_out, workspace)) return rc;
+  FRMAP_REQUIRE_ALIGNED(rescored_out, 8, "rescored_out");
   FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "verify_counts: Q=%d too large for one call (shard B)", Q);
   hipStream_t st = (hipStream_t)stream;
   const VerifyWs w = verify_ws(workspace, P, D, T);
@@ -1427,6 +1499,9 @@ extern "C" int frmap_verify_counts_packed(const float* a, const int32_t* label_a
   if (int rc = verify_check("verify_counts_packed", a, label_a, P, b, label_b, Q, D, a_row0, thresholds, T, accepted_out, workspace))
     return rc;
   FRMAP_REQUIRE(b_packed && stat_w, "verify_counts_packed: null pointer");
+  FRMAP_REQUIRE_ALIGNED(b_packed, 16, "b_packed");
+  FRMAP_REQUIRE_ALIGNED(stat_w, 16, "stat_w");
+  FRMAP_REQUIRE_ALIGNED(rescored_out, 8, "rescored_out");
   FRMAP_REQUIRE(Q > 0 && D % 32 == 0, "verify_counts_packed: bad shape Q=%d D=%d (Q > 0, D %% 32 == 0)", Q, D);
   FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "verify_counts_packed: Q=%d too large for one call (shard B)", Q);
   hipStream_t st = (hipStream_t)stream;
@@ -1499,6 +1574,15 @@ static int radius_check(const char* what, const float* a, const int32_t* label_a
   FRMAP_REQUIRE(P == 0 || (a && count_out && (label_a || !pair_filter)), "%s: null A, its labels or count_out", what);
   FRMAP_REQUIRE(Q == 0 || (b && (label_b || !pair_filter)), "%s: null B or its labels", what);
   FRMAP_REQUIRE(capacity >= 0 && (capacity == 0 || (pair_out && dist_out)), "%s: capacity=%lld needs pair_out and dist_out", what, capacity);
+  FRMAP_REQUIRE_ALIGNED_AS(what, a, 16, "a");
+  FRMAP_REQUIRE_ALIGNED_AS(what, label_a, 4, "label_a");
+  FRMAP_REQUIRE_ALIGNED_AS(what, b, 16, "b");
+  FRMAP_REQUIRE_ALIGNED_AS(what, label_b, 4, "label_b");
+  FRMAP_REQUIRE_ALIGNED_AS(what, count_out, 4, "count_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, total_out, 8, "total_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, pair_out, 8, "pair_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED_AS(what, workspace, 256, "workspace");
   FRMAP_REQUIRE(a_row0 == -1 || (a_row0 >= 0 && (long long)a_row0 + P <= Q),
                 "%s: a_row0=%d with P=%d is not a block of B's %d rows (-1: cross mode)", what, a_row0, P, Q);
   FRMAP_REQUIRE((Q + VS_QB - 1) / VS_QB <= 65535, "%s: Q=%d too large for one call (shard B)", what, Q);
@@ -1527,6 +1611,7 @@ extern "C" int frmap_match_radius(const float* a, const int32_t* label_a, int P,
   if (int rc = radius_check("match_radius", a, label_a, P, b, label_b, Q, D, a_row0, thresh, pair_filter, count_out, total_out, pair_out,
                             dist_out, capacity, workspace))
     return rc;
+  FRMAP_REQUIRE_ALIGNED(rescored_out, 8, "rescored_out");
   hipStream_t st = (hipStream_t)stream;
   const RadiusWs w = radius_ws(workspace, P, D);
   if (int rc = radius_prep(count_out, P, total_out, rescored_out ? (unsigned long long*)rescored_out : w.misc, st)) return rc;
@@ -1542,6 +1627,9 @@ extern "C" int frmap_match_radius_packed(const float* a, const int32_t* label_a,
                             pair_out, dist_out, capacity, workspace))
     return rc;
   FRMAP_REQUIRE(b_packed && stat_w, "match_radius_packed: null pointer");
+  FRMAP_REQUIRE_ALIGNED(b_packed, 16, "b_packed");
+  FRMAP_REQUIRE_ALIGNED(stat_w, 16, "stat_w");
+  FRMAP_REQUIRE_ALIGNED(rescored_out, 8, "rescored_out");
   FRMAP_REQUIRE(Q > 0 && D % 32 == 0, "match_radius_packed: bad shape Q=%d D=%d (Q > 0, D %% 32 == 0)", Q, D);
   hipStream_t st = (hipStream_t)stream;
   const RadiusWs w = radius_ws(workspace, P, D);
@@ -1562,6 +1650,11 @@ extern "C" int frmap_cosine_logits(const float* x, const float* w, float* logits
                                    void* workspace, int B, int C, int D, float s, void* stream) {
   FRMAP_REQUIRE(x && w && workspace && (logits_out || argmax_out), "cosine_logits: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0 && D > 0 && D % 4 == 0, "cosine_logits: bad shape");
+  FRMAP_REQUIRE_ALIGNED(x, 16, "x");
+  FRMAP_REQUIRE_ALIGNED(w, 16, "w");
+  FRMAP_REQUIRE_ALIGNED(logits_out, 4, "logits_out");
+  FRMAP_REQUIRE_ALIGNED(argmax_out, 4, "argmax_out");
+  FRMAP_REQUIRE_ALIGNED(workspace, 16, "workspace");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && C <= FRMAP_GRID_ROWS_MAX, "cosine_logits: B=%d or C=%d exceeds the grid (at most %d rows)", B, C, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* keys = (unsigned long long*)workspace;
@@ -1587,6 +1680,12 @@ extern "C" int frmap_arcmargin_eval(const float* x, const float* w, const int64_
                                     int easy_margin, void* stream) {
   FRMAP_REQUIRE(x && w && label && logits_out && workspace, "arcmargin_eval: null pointer");
   FRMAP_REQUIRE(B > 0 && C > 0 && D > 0 && D % 4 == 0, "arcmargin_eval: bad shape");
+  FRMAP_REQUIRE_ALIGNED(x, 16, "x");
+  FRMAP_REQUIRE_ALIGNED(w, 16, "w");
+  FRMAP_REQUIRE_ALIGNED(label, 8, "label");
+  FRMAP_REQUIRE_ALIGNED(logits_out, 4, "logits_out");
+  FRMAP_REQUIRE_ALIGNED(minmax_out, 4, "minmax_out");
+  FRMAP_REQUIRE_ALIGNED(workspace, 16, "workspace");
   FRMAP_REQUIRE(B <= FRMAP_GRID_ROWS_MAX && C <= FRMAP_GRID_ROWS_MAX, "arcmargin_eval: B=%d or C=%d exceeds the grid (at most %d rows)", B, C, FRMAP_GRID_ROWS_MAX);
   hipStream_t st = (hipStream_t)stream;
   unsigned int* mm = (unsigned int*)workspace;

@@ -38,7 +38,11 @@ __global__ void pack_input_scalar_kernel(const float* __restrict__ x, typename T
 extern "C" int frmap_pack_input_nchw_f32(const float* x, void* out, int B, int H, int W, int dtype, void* stream) {
   FRMAP_REQUIRE(x && out, "pack_input: null pointer");
   FRMAP_REQUIRE(B > 0 && H > 0 && W > 0, "pack_input: empty input");
-  if ((H * W) % 2 != 0) {
+  // the one-pixel path needs the element size of x and one 8-byte pixel of out; the float2 / 16-byte path is taken when H * W is
+  // even (every plane then starts where x does) AND x is 8-byte, out 16-byte aligned.  Both convert element by element: same bits.
+  FRMAP_REQUIRE_ALIGNED(x, 4, "x_nchw");
+  FRMAP_REQUIRE_ALIGNED(out, 8, "out_nhwc4");
+  if (((long long)H * W) % 2 != 0 || ((uintptr_t)x & 7) != 0 || ((uintptr_t)out & 15) != 0) {
     FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "pack_input: bad dtype");
     const size_t HW1 = (size_t)H * W, npix = (size_t)B * HW1;
     const int blocks1 = (int)((npix + 255) / 256 < 16384 ? (npix + 255) / 256 : 16384);
@@ -91,6 +95,8 @@ extern "C" int frmap_pack_conv_weight(const float* w, void* out, int Cout, int C
   FRMAP_REQUIRE(Cin % 32 == 0 && Cout % 64 == 0 && KH == KW && (KH == 1 || KH == 3),
                 "pack_conv_weight: unsupported shape Cout=%d Cin=%d K=%dx%d", Cout, Cin, KH, KW);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "pack_conv_weight: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(w, 4, "w_oihw");
+  FRMAP_REQUIRE_ALIGNED(out, 2, "w_packed");
   const size_t total = (size_t)Cout * Cin * KH * KW;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipStream_t st = (hipStream_t)stream;
@@ -121,6 +127,8 @@ extern "C" int frmap_pack_conv_weight_c3(const float* w, void* out, int Cout, in
   FRMAP_REQUIRE(w && out, "pack_conv_weight_c3: null pointer");
   FRMAP_REQUIRE((KH == 7 && KW == 7) || (KH == 3 && KW == 3), "pack_conv_weight_c3: unsupported kernel %dx%d", KH, KW);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "pack_conv_weight_c3: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(w, 4, "w_oihw");
+  FRMAP_REQUIRE_ALIGNED(out, 2, "w_packed");
   const int KR = (KW * 4 > 16) ? 32 : 16;
   const int pitch = frmap_small_cin_kpad(KH, KW);
   const int blocks = (Cout * pitch + 255) / 256;
@@ -174,6 +182,8 @@ extern "C" int frmap_maxpool(const void* in, void* out, int B, int H, int W, int
   FRMAP_REQUIRE(in && out, "maxpool: null pointer");
   FRMAP_REQUIRE(C % 8 == 0 && k >= 1 && stride >= 1 && pad >= 0 && pad * 2 <= k, "maxpool: bad geometry");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "maxpool: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(in, 16, "in");
+  FRMAP_REQUIRE_ALIGNED(out, 16, "out");
   const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
   FRMAP_REQUIRE(B > 0 && Ho > 0 && Wo > 0, "maxpool: empty output");
   const size_t total = (size_t)B * Ho * Wo * (C / 8);
@@ -224,6 +234,8 @@ extern "C" int frmap_avgpool_global(const void* in, float* out, int B, int HW, i
   FRMAP_REQUIRE(in && out, "avgpool_global: null pointer");
   FRMAP_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 8 == 0, "avgpool_global: bad shape");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "avgpool_global: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(in, 16, "in");
+  FRMAP_REQUIRE_ALIGNED(out, 4, "out_f32");
   FRMAP_REQUIRE((long long)B * (C / 8) <= FRMAP_GRID_ROWS_MAX, "avgpool_global: B C / 8 = %lld waves exceed the grid (at most %d)",
                 (long long)B * (C / 8), FRMAP_GRID_ROWS_MAX);
   const int waves = B * (C / 8);
@@ -272,6 +284,8 @@ extern "C" int frmap_avgpool_adaptive(const void* in, void* out, int B, int H, i
   FRMAP_REQUIRE(in && out, "avgpool_adaptive: null pointer");
   FRMAP_REQUIRE(B > 0 && H > 0 && W > 0 && C % 8 == 0 && OH > 0 && OW > 0, "avgpool_adaptive: bad shape");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "avgpool_adaptive: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(in, 16, "in");
+  FRMAP_REQUIRE_ALIGNED(out, 16, "out");
   const size_t total = (size_t)B * OH * OW * (C / 8);
   FRMAP_REQUIRE(total + 255 < (1ull << 32), "avgpool_adaptive: %zu output groups exceed the grid (fewer than 2^32 threads)", total);
   const int blocks = (int)((total + 255) / 256);
@@ -303,6 +317,8 @@ __global__ void cast_from_f32_kernel(const float* __restrict__ in, typename TT::
 extern "C" int frmap_cast_to_f32(const void* in, float* out, size_t n, int dtype, void* stream) {
   FRMAP_REQUIRE(in && out, "cast_to_f32: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "cast_to_f32: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(in, 2, "in");
+  FRMAP_REQUIRE_ALIGNED(out, 4, "out");
   if (n == 0) return 0;
   const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   hipStream_t st = (hipStream_t)stream;
@@ -316,6 +332,8 @@ extern "C" int frmap_cast_to_f32(const void* in, float* out, size_t n, int dtype
 extern "C" int frmap_cast_from_f32(const float* in, void* out, size_t n, int dtype, void* stream) {
   FRMAP_REQUIRE(in && out, "cast_from_f32: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "cast_from_f32: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(in, 4, "in");
+  FRMAP_REQUIRE_ALIGNED(out, 2, "out");
   if (n == 0) return 0;
   const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
   hipStream_t st = (hipStream_t)stream;
@@ -363,6 +381,8 @@ extern "C" int frmap_normalize_u8_hwc(const unsigned char* img, float* out_nchw_
   FRMAP_REQUIRE(B > 0 && H > 0 && W > 0, "normalize_u8_hwc: empty input");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "normalize_u8_hwc: bad dtype");
   FRMAP_REQUIRE(std3_host[0] != 0.f && std3_host[1] != 0.f && std3_host[2] != 0.f, "normalize_u8_hwc: zero std");
+  FRMAP_REQUIRE_ALIGNED(out_nchw_f32, 4, "out_nchw_f32");
+  FRMAP_REQUIRE_ALIGNED(out_nhwc4, 8, "out_nhwc4");
   const size_t HW = (size_t)H * W, npix = (size_t)B * HW;
   const int blocks = (int)((npix + 255) / 256 < 16384 ? (npix + 255) / 256 : 16384);
   hipStream_t st = (hipStream_t)stream;

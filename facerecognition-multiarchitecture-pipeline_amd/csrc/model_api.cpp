@@ -290,6 +290,26 @@ int check_ready(const frmap_model* m, const char* what) {
   return 0;
 }
 
+// What the first kernel of a forward reads x with: an fp32 image goes to a stem or to pack_input, which take any element-aligned
+// tensor (and pick their 16-byte paths from the pointer); a uint8 image goes to the fused uint8 stem, which reads 4 pixels as three
+// dwords, where that stem takes the shape (as trunk_features / frmap_family_forward decide it), else to the byte-wise normalise kernel.
+int model_x_align(const frmap_model* m, int x_kind, int H, int W) {
+  if (x_kind == FRMAP_INPUT_F32_NCHW) return 4;
+  if (W % 4 != 0 || m->kind == KIND_BASELINE) return 1;
+  const int Wc = (W + 6 - 7) / 2 + 1;
+  if (m->kind == KIND_SIAMESE) return Wc / 2 <= 64 ? 4 : 1;
+  return (Wc + 2 - 3) / 2 + 1 <= 56 ? 4 : 1;
+}
+
+// The carve-outs of a workspace are cut at multiples of 256 bytes from its (256-byte aligned) start: checked where a call begins,
+// before anything is launched, rather than left to the launchers further down.
+int check_carving(const frmap_model* m, const char* what, int B, int H, int W) {
+  // (the activation slots and the family arena; the heads and the match workspace start at frmap_model_workspace_bytes)
+  FRMAP_REQUIRE(act_slot_bytes(B, H, W) % 256 == 0 && frmap_model_workspace_bytes(m, B, H, W) % 256 == 0,
+                "%s: internal error: a workspace carve-out is not a multiple of 256 bytes", what);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int frmap_model_create(frmap_model** out, const char* model_type, int num_classes, int dtype) {
@@ -428,6 +448,12 @@ extern "C" int frmap_model_forward(frmap_model* m, const void* x, int x_kind, in
   FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_forward: bad input kind %d", x_kind);
   FRMAP_REQUIRE(what >= FRMAP_OUT_TRUNK_MAP && what <= FRMAP_OUT_LOGITS, "model_forward: bad output selector %d", what);
   FRMAP_REQUIRE(m->kind != KIND_TRUNK || what <= FRMAP_OUT_POOLED, "model_forward: a bare trunk has no embedding / logits head");
+  // x: model_x_align; the trunk map is stored in 16-byte pieces, the fp32 outputs element by element; the arena is carved in
+  // 256-byte steps (check_carving; Arena::take rounds every piece up to 256)
+  FRMAP_REQUIRE_ALIGNED_AS("model_forward", x, model_x_align(m, x_kind, H, W), "x");
+  if (int rc = check_carving(m, "model_forward", B, H, W)) return rc;
+  FRMAP_REQUIRE_ALIGNED_AS("model_forward", out, what == FRMAP_OUT_TRUNK_MAP ? 16 : 4, "out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_forward", workspace, 256, "workspace");
   Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
   if (m->kind == KIND_BASELINE || m->kind == KIND_SIAMESE) {
     FRMAP_REQUIRE(what != FRMAP_OUT_POOLED, "model_forward: '%s' has no pooled-trunk output", m->kind == KIND_BASELINE ? "baseline" : "siamese");
@@ -532,6 +558,18 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
   FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_match: a bare trunk has no embedding");
   FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_match: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
   FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_match: bad input kind %d", x_kind);
+  // (x as frmap_model_forward; the matcher reads the gallery, its pack and emb_out - the probes - in 16-byte pieces)
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", x, model_x_align(m, x_kind, H, W), "x");
+  if (int rc = check_carving(m, "model_embed_and_match", B, H, W)) return rc;
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery_packed, 16, "gallery_packed");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery_stat, 16, "gallery_stat");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", id_or_unknown_out, 4, "id_or_unknown_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", packed_out, 4, "packed_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", emb_out, 16, "emb_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", workspace, 256, "workspace");
   Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
   char* match_ws = (char*)workspace + frmap_model_workspace_bytes(m, B, H, W);
   const int D = m->kind >= KIND_BASELINE ? frmap_model_embedding_dim(m) : 512;
@@ -582,6 +620,17 @@ extern "C" int frmap_model_embed_and_search(frmap_model* m, const void* x, int x
   FRMAP_REQUIRE(k >= 1 && k <= 64, "model_embed_and_search: k=%d out of range (1 <= k <= 64)", k);
   FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_search: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
   FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_search: bad input kind %d", x_kind);
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", x, model_x_align(m, x_kind, H, W), "x");
+  if (int rc = check_carving(m, "model_embed_and_search", B, H, W)) return rc;
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery, 16, "gallery");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery_packed, 16, "gallery_packed");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery_stat, 16, "gallery_stat");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", labels, 4, "labels");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", idx_out, 4, "idx_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", dist_out, 4, "dist_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", label_out, 4, "label_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", emb_out, 16, "emb_out");
+  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", workspace, 256, "workspace");
   if (k == 1 && !labels) {   // the top-1 step itself: same embedding, same match, bit for bit
     const int rc = frmap_model_embed_and_match(m, x, x_kind, B, H, W, gallery, gallery_packed, gallery_stat, G, INFINITY, normalize,
                                                idx_out, dist_out, nullptr, nullptr, emb_out, workspace, stream);

@@ -84,6 +84,9 @@ __global__ __launch_bounds__(256) void resize_bilinear_u8_kernel(const unsigned 
 extern "C" int frmap_resize_bilinear_u8(const unsigned char* src_pool, const void* items, const int* tables, unsigned char* out,
                                         int B, int out_h, int out_w, int rows_per_block, int lds_rows, void* stream) {
   FRMAP_REQUIRE(src_pool && items && tables && out, "resize_bilinear_u8: null pointer");
+  // (the 40-byte item records start with a uint64; the images and the output are byte-addressed)
+  FRMAP_REQUIRE_ALIGNED(items, 8, "items");
+  FRMAP_REQUIRE_ALIGNED(tables, 4, "tables");
   FRMAP_REQUIRE(B > 0 && B <= 65535 && out_h > 0 && out_w > 0 && rows_per_block > 0 && lds_rows > 0, "resize_bilinear_u8: bad shape");
   const size_t lds = (size_t)lds_rows * out_w * sizeof(unsigned int);
   FRMAP_REQUIRE(lds <= 160 * 1024, "resize_bilinear_u8: %d rows x %d columns do not fit in LDS (use fewer rows per block)", lds_rows, out_w);

@@ -325,6 +325,13 @@ static int stem_launch(const float* x_nchw, const unsigned char* x_u8, const flo
   FRMAP_REQUIRE((x_nchw || x_u8) && w_packed_c3 && shift && out, "%s: null pointer", who);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "%s: bad dtype %d", who, dtype);
   FRMAP_REQUIRE(B > 0 && Hi >= 7 && Wi >= 7 && (long long)Hi * Wi * 12 < 0x7FFFFF00ll, "%s: bad input size", who);
+  // the fp32 image needs its element size only: a tensor that is not 16-byte aligned takes the scalar staging path below (and
+  // stem_s2d.hip declines it); the weight image, `shift` and the output go through 16-byte accesses
+  FRMAP_REQUIRE_ALIGNED_AS(who, x_nchw, 4, "x_nchw");
+  FRMAP_REQUIRE_ALIGNED_AS(who, x_u8, 4, "x_u8_hwc");   // (12 bytes = 4 pixels are read as three dwords)
+  FRMAP_REQUIRE_ALIGNED_AS(who, w_packed_c3, 16, "w_packed_c3");
+  FRMAP_REQUIRE_ALIGNED_AS(who, shift, 16, "shift");
+  FRMAP_REQUIRE_ALIGNED_AS(who, out, 16, "out");
   StemPoolParams p;
   p.x = x_nchw; p.x8 = x_u8; p.wpk = w_packed_c3; p.shift = shift; p.out = out;
   for (int c = 0; c < 3; ++c) { p.mean[c] = mean3 ? mean3[c] : 0.f; p.std[c] = std3 ? std3[c] : 1.f; }

@@ -169,6 +169,10 @@ extern "C" int frmap_track_step(void* state, const float* boxes, const float* pr
   FRMAP_REQUIRE(state && boxes && counts && frame_hw && ids_out && rois_out, "track_step: null pointer");
   FRMAP_REQUIRE((((uintptr_t)state | (uintptr_t)boxes | (uintptr_t)rois_out) & 15) == 0,
                 "track_step: state, boxes and rois_out must be 16-byte aligned");
+  FRMAP_REQUIRE_ALIGNED(probs, 4, "probs");
+  FRMAP_REQUIRE_ALIGNED(counts, 4, "counts");
+  FRMAP_REQUIRE_ALIGNED(frame_hw, 4, "frame_hw");
+  FRMAP_REQUIRE_ALIGNED(ids_out, 4, "ids_out");
   FRMAP_REQUIRE(n_streams <= 0x7fffffff / FRMAP_TRACK_MAX_BOXES, "track_step: %d streams exceed the grid", n_streams);
   hipLaunchKernelGGL(track_step_kernel, dim3((unsigned)((n_streams + TRACK_WAVES - 1) / TRACK_WAVES)), dim3(64 * TRACK_WAVES), 0,
                      (hipStream_t)stream, state, boxes, probs, counts, frame_hw, n_streams, max_boxes, (float)det_thresh, iou_thresh,

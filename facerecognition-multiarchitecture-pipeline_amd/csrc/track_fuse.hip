@@ -188,6 +188,9 @@ extern "C" int frmap_track_fuse(void* state, const int32_t* ids, const int32_t* 
   FRMAP_REQUIRE(emb != fused || n_rows == 0, "track_fuse: fused must not be emb");
   FRMAP_REQUIRE((((uintptr_t)state | (uintptr_t)emb | (uintptr_t)fused) & 15) == 0 && ((uintptr_t)rows & 7) == 0,
                 "track_fuse: state, emb and fused must be 16-byte aligned, rows 8-byte aligned");
+  FRMAP_REQUIRE_ALIGNED(ids, 4, "ids");
+  FRMAP_REQUIRE_ALIGNED(counts, 4, "counts");
+  FRMAP_REQUIRE_ALIGNED(frames_out, 4, "frames_out");
   FRMAP_REQUIRE(n_streams <= 0x7fffffff / FRMAP_TRACK_MAX_BOXES, "track_fuse: %d streams exceed the grid", n_streams);
   hipLaunchKernelGGL(track_fuse_kernel, dim3((unsigned)n_streams), dim3(64 * FUSE_WAVES), 0, (hipStream_t)stream, state, ids, counts,
                      emb, rows, n_rows, n_streams, max_boxes, dim, decay, fused, frames_out);

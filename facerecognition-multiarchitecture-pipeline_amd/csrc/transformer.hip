@@ -118,6 +118,15 @@ extern "C" int frmap_add_pos_layernorm(const void* x, const float* pos, const fl
   FRMAP_REQUIRE(x && gamma && beta && y_out, "add_pos_layernorm: null pointer");
   FRMAP_REQUIRE(B > 0 && L > 0 && D > 0 && D % 64 == 0 && D <= 1024, "add_pos_layernorm: bad shape (D %% 64 == 0, D <= 1024)");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "add_pos_layernorm: bad dtype");
+  {   // D % 512 == 0 takes the 16-byte path through every operand, any other D the element-wise one
+    const int wide = D % 512 == 0;
+    FRMAP_REQUIRE_ALIGNED(x, wide ? 16 : 2, "x");
+    FRMAP_REQUIRE_ALIGNED(pos, wide ? 16 : 4, "pos");
+    FRMAP_REQUIRE_ALIGNED(gamma, wide ? 16 : 4, "gamma");
+    FRMAP_REQUIRE_ALIGNED(beta, wide ? 16 : 4, "beta");
+    FRMAP_REQUIRE_ALIGNED(t_out, wide ? 16 : 2, "t_out");
+    FRMAP_REQUIRE_ALIGNED(y_out, wide ? 16 : 2, "y_out");
+  }
   const long long rows = (long long)B * L;
   FRMAP_REQUIRE(rows < (1ll << 31) / 64, "add_pos_layernorm: too many tokens");
   const int blocks = (int)((rows + 3) / 4);
@@ -253,6 +262,8 @@ extern "C" int frmap_mha_tokens(const void* qkv, void* out, int B, int L, int D,
   FRMAP_REQUIRE(qkv && out, "mha_tokens: null pointer");
   FRMAP_REQUIRE(B > 0 && L > 0 && L <= 64 && H > 0 && D == H * 128, "mha_tokens: need L <= 64 and head dim 128 (D=%d H=%d L=%d)", D, H, L);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "mha_tokens: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(qkv, 16, "qkv");
+  FRMAP_REQUIRE_ALIGNED(out, 16, "out");
   FRMAP_REQUIRE((long long)B * H <= FRMAP_GRID_WG256_MAX, "mha_tokens: B H = %lld workgroups exceed the grid (at most %d)", (long long)B * H,
                 FRMAP_GRID_WG256_MAX);
   const int lds = 2 * 64 * 272 + 128 * 144 + 4 * 16 * 144 + 4 * 16 * 272;
@@ -354,6 +365,10 @@ extern "C" int frmap_mean_layernorm(const void* t, const float* gamma, const flo
   FRMAP_REQUIRE(B > 0 && L > 0 && D > 0 && D <= 1024, "mean_layernorm: bad shape (D <= 1024)");
   FRMAP_REQUIRE(B <= FRMAP_GRID_WG256_MAX, "mean_layernorm: %d faces exceed the grid (at most %d)", B, FRMAP_GRID_WG256_MAX);
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "mean_layernorm: bad dtype");
+  FRMAP_REQUIRE_ALIGNED(t, D % 8 == 0 ? 16 : 2, "t");   // (the 16-byte token loads, or the element-wise walk)
+  FRMAP_REQUIRE_ALIGNED(gamma, 4, "gamma");
+  FRMAP_REQUIRE_ALIGNED(beta, 4, "beta");
+  FRMAP_REQUIRE_ALIGNED(out, 4, "out_f32");
   hipStream_t st = (hipStream_t)stream;
   if (dtype == FRMAP_BF16)
     hipLaunchKernelGGL(mean_layernorm_kernel<BF16>, dim3(B), dim3(256), 0, st, (const __bf16*)t, gamma, beta, out, L, D, eps);
@@ -547,6 +562,14 @@ extern "C" int frmap_cnn_attention(const void* qkv, const void* x, const float* 
   FRMAP_REQUIRE(Cq > 0 && Cq <= 128 && Cq % 8 == 0, "cnn_attention: Cq=%d must be a multiple of 8, <= 128", Cq);
   FRMAP_REQUIRE(C == 256 || C == 512, "cnn_attention: C=%d must be 256 or 512", C);
   FRMAP_REQUIRE(KS > 0 && KS % 2 == 1 && KS <= 15, "cnn_attention: odd spatial kernel size <= 15 expected (got %d)", KS);
+  // qkv and x are staged in 16-byte pieces; the map is stored two channels (C = 512) or one (C = 256) per thread
+  FRMAP_REQUIRE_ALIGNED(qkv, 16, "qkv");
+  FRMAP_REQUIRE_ALIGNED(x, 16, "x");
+  FRMAP_REQUIRE_ALIGNED(gamma, 4, "gamma");
+  FRMAP_REQUIRE_ALIGNED(spatial_w, 4, "spatial_w");
+  FRMAP_REQUIRE_ALIGNED(spatial_b, 4, "spatial_b");
+  FRMAP_REQUIRE_ALIGNED(out_map, 4, "out_map");
+  FRMAP_REQUIRE_ALIGNED(out_pool, 4, "out_pool");
   CnnAttnParams p;
   p.qkv = qkv; p.x = x; p.gamma = gamma; p.sw = spatial_w; p.sb = spatial_b; p.out_map = out_map; p.out_pool = out_pool;
   p.B = B; p.H = H; p.W = W; p.L = H * W; p.Cq = Cq; p.C = C; p.KS = KS;

@@ -45,14 +45,32 @@ def _on_operand_device(fn):
     return guarded
 
 
-def _dev(t: torch.Tensor, what: str, dtype=None) -> torch.Tensor:
+def _dev(t: torch.Tensor, what: str, dtype=None, arg=None, owned: bool = False) -> torch.Tensor:
+    """A tensor as the library takes it: on the GPU, of ``dtype``, contiguous and aligned as the header asks of ``arg`` =
+    ``(entry point, argument)`` of `_lib.ALIGNMENT` (no ``arg``: 16 bytes, the most any operand needs).  An operand that is not
+    contiguous or starts below that alignment - a view with a storage offset such as ``flat[1:]``, a row slice of a ``[B, 35]`` matrix -
+    is copied; ``owned`` (a tensor the call writes: a state, a caller-supplied output) cannot be, and raises ``ValueError``."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise RuntimeError(f"{what}: tensor is on {t.device}; the HIP path needs GPU tensors (no CPU fallback)")
     if dtype is not None and t.dtype != dtype:
         raise TypeError(f"{what}: expected dtype {dtype}, got {t.dtype}")
+    need = 16 if arg is None else _lib.align_of(*arg)
+    if t.numel() and t.data_ptr() % need:
+        if owned:
+            raise ValueError(f"{what}: a tensor the call writes must be {need}-byte aligned (data_ptr() % {need} = {t.data_ptr() % need})")
+        return t.clone(memory_format=torch.contiguous_format)
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _ptr(keep: list, t: torch.Tensor, what: str, dtype=None, arg=None) -> int:
+    """The address of ``_dev(t, ...)`` for an operand used by its address only.  `_dev` may have made a copy: it goes into ``keep``,
+    which the caller holds until its launch is enqueued - a temporary dropped right after ``data_ptr()`` hands its block to the next
+    copy, and two operands of one call would then share an address."""
+    t = _dev(t, what, dtype, arg)
+    keep.append(t)
+    return t.data_ptr()
 
 
 def dt_code(dtype: torch.dtype) -> int:
@@ -71,7 +89,7 @@ def set_batch_invariant(on: Optional[bool]) -> None:
 
 def pack_input(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """fp32 NCHW B×3×H×W -> NHWC4 (zero 4th channel) in ``dtype``."""
-    x = _dev(x, "pack_input.x", torch.float32)
+    x = _dev(x, "pack_input.x", torch.float32, ("frmap_pack_input_nchw_f32", "x_nchw"))
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f"expected B×3×H×W input, got {tuple(x.shape)}")
     B, _, H, W = x.shape
@@ -82,7 +100,7 @@ def pack_input(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 def pack_conv_weight(w_folded: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    w = _dev(w_folded, "pack_conv_weight.w", torch.float32)
+    w = _dev(w_folded, "pack_conv_weight.w", torch.float32, ("frmap_pack_conv_weight", "w_oihw"))
     Cout, Cin, KH, KW = w.shape
     out = torch.empty((Cout * Cin * KH * KW,), dtype=dtype, device=w.device)
     _lib.check(_lib.load().frmap_pack_conv_weight(w.data_ptr(), out.data_ptr(), Cout, Cin, KH, KW, dt_code(dtype),
@@ -91,7 +109,7 @@ def pack_conv_weight(w_folded: torch.Tensor, dtype: torch.dtype) -> torch.Tensor
 
 
 def pack_conv_weight_c3(w_folded: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    w = _dev(w_folded, "pack_conv_weight_c3.w", torch.float32)
+    w = _dev(w_folded, "pack_conv_weight_c3.w", torch.float32, ("frmap_pack_conv_weight_c3", "w_oihw"))
     Cout, Cin, KH, KW = w.shape
     if Cin != 3:
         raise ValueError("pack_conv_weight_c3: Cin must be 3")
@@ -104,14 +122,15 @@ def pack_conv_weight_c3(w_folded: torch.Tensor, dtype: torch.dtype) -> torch.Ten
 
 def conv_small_cin(x4: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: int, k: int, stride: int,
                    pad: int, relu: bool) -> torch.Tensor:
-    x4 = _dev(x4, "conv_small_cin.x")
+    keep = []
+    x4 = _dev(x4, "conv_small_cin.x", None, ("frmap_conv_small_cin", "in_nhwc4"))
     B, H, W, C = x4.shape
     if C != 4:
         raise ValueError("conv_small_cin: input must be NHWC4")
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     out = torch.empty((B, Ho, Wo, Cout), dtype=x4.dtype, device=x4.device)
-    _lib.check(_lib.load().frmap_conv_small_cin(x4.data_ptr(), _dev(wpk, "wpk").data_ptr(),
-                                                _dev(shift, "shift", torch.float32).data_ptr(), out.data_ptr(),
+    _lib.check(_lib.load().frmap_conv_small_cin(x4.data_ptr(), _ptr(keep, wpk, "wpk"),
+                                                _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                 B, H, W, Cout, k, k, stride, pad, int(relu), dt_code(x4.dtype),
                                                 _stream()), "conv_small_cin")
     return out
@@ -119,15 +138,16 @@ def conv_small_cin(x4: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cou
 
 def conv_small_cin_pool2(x4: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: int, relu: bool) -> torch.Tensor:
     """3x3 s1 p1 conv (Cin = 3 as NHWC4) + shift (+ReLU) + MaxPool2d(2, 2) in one launch (`face_models.py:38`)."""
-    x4 = _dev(x4, "conv_small_cin_pool2.x")
+    keep = []
+    x4 = _dev(x4, "conv_small_cin_pool2.x", None, ("frmap_conv_small_cin_pool2", "in_nhwc4"))
     B, H, W, C = x4.shape
     if C != 4:
         raise ValueError("conv_small_cin_pool2: input must be NHWC4")
     if H % 2 or W % 2:
         raise ValueError("conv_small_cin_pool2: H and W must be even")
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=x4.dtype, device=x4.device)
-    _lib.check(_lib.load().frmap_conv_small_cin_pool2(x4.data_ptr(), _dev(wpk, "wpk").data_ptr(),
-                                                      _dev(shift, "shift", torch.float32).data_ptr(), out.data_ptr(),
+    _lib.check(_lib.load().frmap_conv_small_cin_pool2(x4.data_ptr(), _ptr(keep, wpk, "wpk"),
+                                                      _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                       B, H, W, Cout, int(relu), dt_code(x4.dtype), _stream()),
                "conv_small_cin_pool2")
     return out
@@ -142,7 +162,8 @@ def stem7x7_maxpool(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, dty
                     pool3: bool = True) -> torch.Tensor:
     """fp32 NCHW -> conv7x7 s2 + shift + ReLU -> maxpool (3x3 s2 p1 if ``pool3`` else 2x2 s2) -> NHWC
     B×Hq×Wq×64 (``dtype``)."""
-    x = _dev(x, "stem7x7_maxpool.x", torch.float32)
+    keep = []
+    x = _dev(x, "stem7x7_maxpool.x", torch.float32, ("frmap_stem7x7_maxpool", "x_nchw"))
     B, C, H, W = x.shape
     if C != 3:
         raise ValueError("stem7x7_maxpool: expected 3 input channels")
@@ -152,8 +173,8 @@ def stem7x7_maxpool(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, dty
         Hq, Wq = ((H + 6 - 7) // 2 + 1) // 2, ((W + 6 - 7) // 2 + 1) // 2
     out = torch.empty((B, Hq, Wq, 64), dtype=dtype, device=x.device)
     fn = _lib.load().frmap_stem7x7_maxpool if pool3 else _lib.load().frmap_stem7x7_maxpool2
-    _lib.check(fn(x.data_ptr(), _dev(wpk, "wpk", dtype).data_ptr(),
-                                                 _dev(shift, "shift", torch.float32).data_ptr(), out.data_ptr(),
+    _lib.check(fn(x.data_ptr(), _ptr(keep, wpk, "wpk", dtype),
+                                                 _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                  B, H, W, dt_code(dtype), _stream()), "stem7x7_maxpool")
     return out
 
@@ -162,10 +183,11 @@ def stem7x7_maxpool_u8(x_u8: torch.Tensor, wpk: torch.Tensor, shift: torch.Tenso
                        pool3: bool = True) -> torch.Tensor:
     """uint8 HWC B×H×W×3 (RGB) -> ToTensor + Normalize(mean, std) -> conv7x7 s2 + shift + ReLU -> maxpool -> NHWC
     B×Hq×Wq×64 (``dtype``): the fused stem fed by the image bytes themselves (needs W % 4 == 0)."""
+    keep = []
     import ctypes as C
     if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8 or x_u8.dim() != 4 or x_u8.shape[3] != 3:
         raise TypeError("stem7x7_maxpool_u8: expected a uint8 tensor of shape [B, H, W, 3]")
-    x_u8 = _dev(x_u8, "stem7x7_maxpool_u8.x")
+    x_u8 = _dev(x_u8, "stem7x7_maxpool_u8.x", None, ("frmap_stem7x7_maxpool_u8", "x_u8_hwc"))
     B, H, W, _ = x_u8.shape
     if pool3:
         Hq, Wq = stem_pool_dims(H, W)
@@ -174,8 +196,8 @@ def stem7x7_maxpool_u8(x_u8: torch.Tensor, wpk: torch.Tensor, shift: torch.Tenso
     out = torch.empty((B, Hq, Wq, 64), dtype=dtype, device=x_u8.device)
     m = (C.c_float * 3)(*[float(v) for v in mean])
     sd = (C.c_float * 3)(*[float(v) for v in std])
-    _lib.check(_lib.load().frmap_stem7x7_maxpool_u8(x_u8.data_ptr(), m, sd, _dev(wpk, "wpk", dtype).data_ptr(),
-                                                    _dev(shift, "shift", torch.float32).data_ptr(), out.data_ptr(),
+    _lib.check(_lib.load().frmap_stem7x7_maxpool_u8(x_u8.data_ptr(), m, sd, _ptr(keep, wpk, "wpk", dtype),
+                                                    _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                     B, H, W, int(bool(pool3)), dt_code(dtype), _stream()), "stem7x7_maxpool_u8")
     return out
 
@@ -183,6 +205,7 @@ def stem7x7_maxpool_u8(x_u8: torch.Tensor, wpk: torch.Tensor, shift: torch.Tenso
 def conv_igemm(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: int, k: int, stride: int, pad: int,
                relu, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``relu``: False/0 none, True/1 ReLU, 2 exact GELU."""
+    keep = []
     x = _dev(x, "conv_igemm.x")
     B, H, W, Cin = x.shape
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
@@ -197,8 +220,8 @@ def conv_igemm(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: in
         raise ValueError("conv_igemm: packed weight does not match Cout*Cin*k*k / dtype")
     if shift.numel() != Cout:
         raise ValueError("conv_igemm: shift must have Cout elements")
-    _lib.check(_lib.load().frmap_conv_igemm(x.data_ptr(), _dev(wpk, "wpk").data_ptr(),
-                                            _dev(shift, "shift", torch.float32).data_ptr(), res_ptr, out.data_ptr(),
+    _lib.check(_lib.load().frmap_conv_igemm(x.data_ptr(), _ptr(keep, wpk, "wpk"),
+                                            _ptr(keep, shift, "shift", torch.float32), res_ptr, out.data_ptr(),
                                             B, H, W, Cin, Cout, k, stride, pad, int(relu), dt_code(x.dtype),
                                             _stream()), "conv_igemm")
     return out
@@ -223,6 +246,7 @@ def conv_pool2_form(B: int, H: int, W: int, Cin: int, Cout: int) -> int:
 def conv_igemm_pool2(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: int, relu) -> torch.Tensor:
     """conv 3x3 s1 p1 + shift (+ReLU) + MaxPool2d(2, 2) in one launch (`face_models.py:39-40,121-141`); the conv map
     never reaches HBM.  Raises ``ValueError`` for shapes `conv_pool2_supported` rejects."""
+    keep = []
     x = _dev(x, "conv_igemm_pool2.x")
     B, H, W, Cin = x.shape
     if wpk.numel() != Cout * Cin * 9 or wpk.dtype != x.dtype:
@@ -230,8 +254,8 @@ def conv_igemm_pool2(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Co
     if shift.numel() != Cout:
         raise ValueError("conv_igemm_pool2: shift must have Cout elements")
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.load().frmap_conv_igemm_pool2(x.data_ptr(), _dev(wpk, "wpk").data_ptr(),
-                                                  _dev(shift, "shift", torch.float32).data_ptr(), out.data_ptr(),
+    _lib.check(_lib.load().frmap_conv_igemm_pool2(x.data_ptr(), _ptr(keep, wpk, "wpk"),
+                                                  _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                   B, H, W, Cin, Cout, int(relu), dt_code(x.dtype), _stream()),
                "conv_igemm_pool2")
     return out
@@ -252,6 +276,7 @@ def conv_igemm_ds(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout:
                   ds_stride: int, relu) -> torch.Tensor:
     """``act(conv3x3_s1_p1(x) + conv1x1_stride(x_ds) + shift)`` — a BasicBlock's second conv with its projection
     shortcut folded in (``shift`` = both folded BatchNorm shifts added).  Check ``conv_ds_supported`` first."""
+    keep = []
     x = _dev(x, "conv_igemm_ds.x")
     x_ds = _dev(x_ds, "conv_igemm_ds.x_ds", x.dtype)
     B, H, W, Cin = x.shape
@@ -261,9 +286,9 @@ def conv_igemm_ds(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout:
     if shift.numel() != Cout:
         raise ValueError("conv_igemm_ds: shift must have Cout elements")
     out = torch.empty((B, H, W, Cout), dtype=x.dtype, device=x.device)
-    _lib.check(_lib.load().frmap_conv_igemm_ds(x.data_ptr(), _dev(wpk, "wpk").data_ptr(),
-                                               _dev(shift, "shift", torch.float32).data_ptr(), x_ds.data_ptr(),
-                                               _dev(wpk_ds, "wpk_ds").data_ptr(), out.data_ptr(), B, H, W, Cin, Cout,
+    _lib.check(_lib.load().frmap_conv_igemm_ds(x.data_ptr(), _ptr(keep, wpk, "wpk"),
+                                               _ptr(keep, shift, "shift", torch.float32), x_ds.data_ptr(),
+                                               _ptr(keep, wpk_ds, "wpk_ds"), out.data_ptr(), B, H, W, Cin, Cout,
                                                Hd, Wd, Cd, ds_stride, int(relu), dt_code(x.dtype), _stream()), "conv_igemm_ds")
     return out
 
@@ -271,6 +296,7 @@ def conv_igemm_ds(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout:
 def linear_mfma(x2d: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, N: int, act=0,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``act(x · Wᵀ + shift [+ residual])`` on the MFMA conv kernel (split-K when the output is small)."""
+    keep = []
     x2d = _dev(x2d, "linear_mfma.x")
     M, K = x2d.shape
     out = torch.empty((M, N), dtype=x2d.dtype, device=x2d.device)
@@ -285,7 +311,7 @@ def linear_mfma(x2d: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, N: in
         rp = residual.data_ptr()
     if wpk.numel() != N * K or wpk.dtype != x2d.dtype:
         raise ValueError("linear_mfma: packed weight does not match N*K / dtype")
-    _lib.check(lib.frmap_linear_mfma(x2d.data_ptr(), _dev(wpk, "wpk").data_ptr(), _dev(shift, "shift", torch.float32).data_ptr(),
+    _lib.check(lib.frmap_linear_mfma(x2d.data_ptr(), _ptr(keep, wpk, "wpk"), _ptr(keep, shift, "shift", torch.float32),
                                      rp, out.data_ptr(), ws.data_ptr() if ws is not None else 0, M, K, N, int(act),
                                      dt_code(x2d.dtype), _stream()), "linear_mfma")
     return out
@@ -321,6 +347,7 @@ def avgpool_adaptive(x: torch.Tensor, OH: int, OW: int) -> torch.Tensor:
 
 def linear_f32(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
                shift: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    keep = []
     x = _dev(x, "linear_f32.x", torch.float32)
     w = _dev(w, "linear_f32.w", torch.float32)
     B, K = x.shape
@@ -328,15 +355,15 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] =
     if K != K2:
         raise ValueError(f"linear_f32: x is B×{K} but w is N×{K2}")
     out = torch.empty((B, N), dtype=torch.float32, device=x.device)
-    sp = _dev(scale, "scale", torch.float32).data_ptr() if scale is not None else 0
-    hp = _dev(shift, "shift", torch.float32).data_ptr() if shift is not None else 0
+    sp = _ptr(keep, scale, "scale", torch.float32, ("frmap_linear_f32", "scale")) if scale is not None else 0
+    hp = _ptr(keep, shift, "shift", torch.float32, ("frmap_linear_f32", "shift")) if shift is not None else 0
     _lib.check(_lib.load().frmap_linear_f32(x.data_ptr(), w.data_ptr(), sp, hp, out.data_ptr(), B, K, N, int(relu),
                                             _stream()), "linear_f32")
     return out
 
 
 def l2_normalize(x: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
-    x = _dev(x, "l2_normalize.x", torch.float32)
+    x = _dev(x, "l2_normalize.x", torch.float32, ("frmap_l2_normalize_f32", "x"))
     B, D = x.shape
     out = torch.empty_like(x)
     _lib.check(_lib.load().frmap_l2_normalize_f32(x.data_ptr(), out.data_ptr(), B, D, float(eps), _stream()),
@@ -345,7 +372,7 @@ def l2_normalize(x: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
 
 
 def cast_to_f32(x: torch.Tensor) -> torch.Tensor:
-    x = _dev(x, "cast_to_f32.x")
+    x = _dev(x, "cast_to_f32.x", None, ("frmap_cast_to_f32", "in"))
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().frmap_cast_to_f32(x.data_ptr(), out.data_ptr(), x.numel(), dt_code(x.dtype), _stream()),
                "cast_to_f32")
@@ -353,7 +380,7 @@ def cast_to_f32(x: torch.Tensor) -> torch.Tensor:
 
 
 def cast_from_f32(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    x = _dev(x, "cast_from_f32.x", torch.float32)
+    x = _dev(x, "cast_from_f32.x", torch.float32, ("frmap_cast_from_f32", "in"))
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
     _lib.check(_lib.load().frmap_cast_from_f32(x.data_ptr(), out.data_ptr(), x.numel(), dt_code(dtype), _stream()),
                "cast_from_f32")
@@ -363,13 +390,14 @@ def cast_from_f32(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 def add_pos_layernorm(x: torch.Tensor, pos: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
                       eps: float = 1e-5, want_sum: bool = False):
     """x: [B, L, D] tokens.  Returns (t, y): t = x + pos (None unless want_sum), y = LayerNorm(t)."""
+    keep = []
     x = _dev(x, "add_pos_layernorm.x")
     B, L, D = x.shape
     y = torch.empty_like(x)
     t = torch.empty_like(x) if want_sum else None
     _lib.check(_lib.load().frmap_add_pos_layernorm(
-        x.data_ptr(), _dev(pos, "pos", torch.float32).data_ptr() if pos is not None else 0,
-        _dev(gamma, "gamma", torch.float32).data_ptr(), _dev(beta, "beta", torch.float32).data_ptr(),
+        x.data_ptr(), _ptr(keep, pos, "pos", torch.float32) if pos is not None else 0,
+        _ptr(keep, gamma, "gamma", torch.float32), _ptr(keep, beta, "beta", torch.float32),
         t.data_ptr() if t is not None else 0, y.data_ptr(), B, L, D, float(eps), dt_code(x.dtype), _stream()),
         "add_pos_layernorm")
     return t, y
@@ -386,11 +414,12 @@ def mha_tokens(qkv: torch.Tensor, H: int) -> torch.Tensor:
 
 
 def mean_layernorm(t: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    keep = []
     t = _dev(t, "mean_layernorm.t")
     B, L, D = t.shape
     out = torch.empty((B, D), dtype=torch.float32, device=t.device)
-    _lib.check(_lib.load().frmap_mean_layernorm(t.data_ptr(), _dev(gamma, "gamma", torch.float32).data_ptr(),
-                                                _dev(beta, "beta", torch.float32).data_ptr(), out.data_ptr(), B, L, D,
+    _lib.check(_lib.load().frmap_mean_layernorm(t.data_ptr(), _ptr(keep, gamma, "gamma", torch.float32, ("frmap_mean_layernorm", "gamma")),
+                                                _ptr(keep, beta, "beta", torch.float32, ("frmap_mean_layernorm", "beta")), out.data_ptr(), B, L, D,
                                                 float(eps), dt_code(t.dtype), _stream()), "mean_layernorm")
     return out
 
@@ -399,19 +428,20 @@ def cnn_attention(qkv: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, spati
                   Cq: int, want_map: bool = False, want_pool: bool = True):
     """AttentionNet's attention block (`face_models.py:194-262`) on an NHWC trunk map ``x`` [B,H,W,C] given the packed
     q|k|v projection ``qkv`` [B,H,W,2*Cq+C].  Returns (map [B,H,W,C] | None, pooled fp32 [B,C] | None)."""
+    keep = []
     x = _dev(x, "cnn_attention.x")
     qkv = _dev(qkv, "cnn_attention.qkv", x.dtype)
     B, H, W, C = x.shape
     if tuple(qkv.shape) != (B, H, W, 2 * Cq + C):
         raise ValueError(f"cnn_attention: qkv shape {tuple(qkv.shape)} != {(B, H, W, 2 * Cq + C)}")
-    sw = _dev(spatial_w, "spatial_w", torch.float32)
+    sw = _dev(spatial_w, "spatial_w", torch.float32, ("frmap_cnn_attention", "spatial_w"))
     KS = sw.shape[-1]
     if sw.numel() != 2 * KS * KS:
         raise ValueError("cnn_attention: spatial_w must be [1][2][KS][KS]")
     om = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device) if want_map else None
     op = torch.empty((B, C), dtype=torch.float32, device=x.device) if want_pool else None
-    _lib.check(_lib.load().frmap_cnn_attention(qkv.data_ptr(), x.data_ptr(), _dev(gamma, "gamma", torch.float32).data_ptr(),
-                                               sw.data_ptr(), _dev(spatial_b, "spatial_b", torch.float32).data_ptr(),
+    _lib.check(_lib.load().frmap_cnn_attention(qkv.data_ptr(), x.data_ptr(), _ptr(keep, gamma, "gamma", torch.float32, ("frmap_cnn_attention", "gamma")),
+                                               sw.data_ptr(), _ptr(keep, spatial_b, "spatial_b", torch.float32, ("frmap_cnn_attention", "spatial_b")),
                                                om.data_ptr() if om is not None else 0, op.data_ptr() if op is not None else 0,
                                                B, H, W, Cq, C, KS, dt_code(x.dtype), _stream()), "cnn_attention")
     return om, op
@@ -422,7 +452,7 @@ def normalize_u8(img: torch.Tensor, mean, std, want_nchw: bool = True, nhwc4_dty
     import ctypes as C
     if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
         raise TypeError("normalize_u8: expected a uint8 tensor of shape [B, H, W, 3]")
-    img = _dev(img, "normalize_u8.img")
+    img = _dev(img, "normalize_u8.img", None, ("frmap_normalize_u8_hwc", "img_u8"))
     B, H, W, _ = img.shape
     o1 = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device) if want_nchw else None
     o2 = torch.empty((B, H, W, 4), dtype=nhwc4_dtype, device=img.device) if nhwc4_dtype is not None else None
@@ -436,7 +466,7 @@ def normalize_u8(img: torch.Tensor, mean, std, want_nchw: bool = True, nhwc4_dty
 
 
 def softmax_argmax(logits: torch.Tensor, want_probs: bool = True):
-    logits = _dev(logits, "softmax_argmax.logits", torch.float32)
+    logits = _dev(logits, "softmax_argmax.logits", torch.float32, ("frmap_softmax_argmax", "logits"))
     B, Cc = logits.shape
     probs = torch.empty_like(logits) if want_probs else None
     pred = torch.empty((B,), dtype=torch.int32, device=logits.device)
@@ -446,8 +476,8 @@ def softmax_argmax(logits: torch.Tensor, want_probs: bool = True):
 
 
 def pairwise_distance(a: torch.Tensor, b: torch.Tensor, thresh: Optional[float] = None):
-    a = _dev(a, "pairwise_distance.a", torch.float32)
-    b = _dev(b, "pairwise_distance.b", torch.float32)
+    a = _dev(a, "pairwise_distance.a", torch.float32, ("frmap_pairwise_distance", "a"))
+    b = _dev(b, "pairwise_distance.b", torch.float32, ("frmap_pairwise_distance", "b"))
     if a.shape != b.shape or a.dim() != 2:
         raise ValueError("pairwise_distance: need two [B, D] tensors of the same shape")
     B, D = a.shape
@@ -480,7 +510,7 @@ def _packed_buf(packed, B: int, device):
     if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.int32 and tuple(packed.shape) == (B, 2)
             and packed.is_contiguous()):
         raise ValueError(f"packed output must be a contiguous int32 [{B}, 2] device tensor")
-    return packed
+    return _dev(packed, "packed", torch.int32, ("frmap_match_top1", "packed_out"), owned=True)     # (caller-owned: never copied)
 
 
 class MatchPack:
@@ -490,7 +520,7 @@ class MatchPack:
     __slots__ = ("packed", "stat_w", "G", "D", "capacity", "src_ptr", "src_version", "ready")
 
     def __init__(self, gallery: torch.Tensor, capacity: Optional[int] = None):
-        gallery = _dev(gallery, "match_prepare.gallery", torch.float32)
+        gallery = _dev(gallery, "match_prepare.gallery", torch.float32, ("frmap_match_pack_gallery", "gallery"))
         self.G, self.D = int(gallery.shape[0]), int(gallery.shape[1])
         self.capacity = max(int(capacity or 0), self.G)
         lib = _lib.load()
@@ -504,7 +534,7 @@ class MatchPack:
 
     def update_rows(self, gallery: torch.Tensor, row_lo: int, row_hi: int) -> None:
         """``gallery`` (same storage, now G rows) had rows [row_lo, row_hi) appended or edited: re-pack those rows only."""
-        gallery = _dev(gallery, "match_update.gallery", torch.float32)
+        gallery = _dev(gallery, "match_update.gallery", torch.float32, ("frmap_match_pack_gallery_rows", "gallery"))
         G = int(gallery.shape[0])
         if gallery.data_ptr() != self.src_ptr or gallery.shape[1] != self.D or G > self.capacity:
             raise ValueError("MatchPack.update_rows: not the gallery storage this pack was built from (or beyond its capacity)")
@@ -559,11 +589,11 @@ def match_top1(emb: torch.Tensor, gallery: torch.Tensor, thresh: Optional[float]
     G = int(gallery.shape[0]) if gallery is not None else 0
     gptr = 0
     if G > 0:
-        gallery = _dev(gallery, "match_top1.gallery", torch.float32)
+        src, gallery = gallery, _dev(gallery, "match_top1.gallery", torch.float32)
         if gallery.shape[1] != D:
             raise ValueError(f"match_top1: embedding dim {D} != gallery dim {gallery.shape[1]}")
         gptr = gallery.data_ptr()
-    prepared = _usable_pack(prepared, gallery, D, "match_top1")
+    prepared = _usable_pack(prepared, src if G > 0 else gallery, D, "match_top1")
     idx = torch.empty((B,), dtype=torch.int32, device=emb.device)
     dist = torch.empty((B,), dtype=torch.float32, device=emb.device)
     ws = _match_workspace(B, G, emb.device)       # candidate records + per-probe statistics
@@ -603,12 +633,12 @@ def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, label
     G = int(gallery.shape[0]) if gallery is not None else 0
     gptr = lptr = 0
     if G > 0:
-        gallery = _dev(gallery, "match_topk.gallery", torch.float32)
+        src, gallery = gallery, _dev(gallery, "match_topk.gallery", torch.float32)
         if gallery.shape[1] != D:
             raise ValueError(f"match_topk: embedding dim {D} != gallery dim {gallery.shape[1]}")
         gptr = gallery.data_ptr()
     if labels is not None:
-        labels = _dev(labels, "match_topk.labels", torch.int32)
+        labels = _dev(labels, "match_topk.labels", torch.int32, ("frmap_match_topk", "labels"))
         if tuple(labels.shape) != (G,):
             raise ValueError(f"match_topk: labels must be int32 [{G}], got {tuple(labels.shape)}")
         lptr = labels.data_ptr() if G > 0 else 0
@@ -620,7 +650,7 @@ def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, label
     if labels is not None and G == 0:
         lptr = ws.data_ptr()          # (identity mode on an empty gallery: a non-null labels pointer keeps the mode)
     lbp = lab.data_ptr() if lab is not None else 0
-    prepared = _usable_pack(prepared, gallery, D, "match_topk")
+    prepared = _usable_pack(prepared, src if G > 0 else gallery, D, "match_topk")
     if prepared is not None:
         _lib.check(lib.frmap_match_topk_packed(emb.data_ptr(), gptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lptr,
                                                idx.data_ptr(), dist.data_ptr(), lbp, ws.data_ptr(), B, G, D, k, _stream()),
@@ -705,6 +735,7 @@ def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Option
     Outside graph capture the thresholds are checked on the host (`verify_thresholds`): host values are uploaded with a blocking
     copy and device values read back, so each call synchronises the stream once.  A caller that repeats calls on fixed device
     thresholds and wants them asynchronous calls the C entry points (`frmap_verify_counts[_packed]`) after checking them once."""
+    src = a if b is None else b
     a, la, b, lb, row0 = _pair_operands("verify_counts", a, labels_a, b, labels_b, a_row0,
                                         {"labels_b": "verify_counts: labels_b is required with b"})
     (P, D), Q = a.shape, int(b.shape[0])
@@ -717,7 +748,7 @@ def verify_counts(a: torch.Tensor, labels_a: torch.Tensor, thresholds, b: Option
     aptr, laptr = (a.data_ptr(), la.data_ptr()) if P else (0, 0)
     bptr, lbptr = (b.data_ptr(), lb.data_ptr()) if Q else (0, 0)
     rptr = resc.data_ptr() if resc is not None else 0
-    prepared = _usable_pack(prepared, b, D, "verify_counts")
+    prepared = _usable_pack(prepared, src, D, "verify_counts")
     if prepared is not None:
         _lib.check(lib.frmap_verify_counts_packed(aptr, laptr, P, bptr, prepared.packed.data_ptr(), prepared.stat_w.data_ptr(), lbptr,
                                                   Q, D, row0, thr.data_ptr(), T, out.data_ptr(), rptr, ws.data_ptr(), _stream()),
@@ -755,6 +786,7 @@ def match_radius(a: torch.Tensor, thresh: float, b: Optional[torch.Tensor] = Non
     thresh = float(thresh)
     if not 0.0 <= thresh <= float(np.finfo(np.float32).max):          # (NaN fails both; the library takes an fp32)
         raise ValueError(f"match_radius: thresh must be finite and >= 0, got {thresh}")
+    src = a if b is None else b
     a, la, b, lb, row0 = _pair_operands("match_radius", a, labels_a, b, labels_b, a_row0, {
         what: f"match_radius: which={which!r} needs {what}" if filt else None for what in ("labels_a", "labels_b")})
     (P, D), Q = a.shape, int(b.shape[0])
@@ -769,7 +801,7 @@ def match_radius(a: torch.Tensor, thresh: float, b: Optional[torch.Tensor] = Non
     aptr, laptr = (a.data_ptr(), la.data_ptr() if la is not None else 0) if P else (0, 0)
     bptr, lbptr = (b.data_ptr(), lb.data_ptr() if lb is not None else 0) if Q else (0, 0)
     rptr = resc.data_ptr() if resc is not None else 0
-    prepared = _usable_pack(prepared, b, D, "match_radius")
+    prepared = _usable_pack(prepared, src, D, "match_radius")
 
     def call(cap):
         pairs = torch.empty((cap, 2), dtype=torch.int32, device=dev)
@@ -800,17 +832,18 @@ def gap_linear_norm(fmap: torch.Tensor, wt: torch.Tensor, scale: Optional[torch.
                     eps: float = 1e-12, want_pre: bool = False, relu: bool = False):
     """ArcFaceNet head in one launch (`face_models.py:573-590`): global average pool of the NHWC trunk map [B,H,W,K] ->
     Linear (``wt`` = weight transposed, fp32 [K][N]) -> folded BatchNorm1d -> L2-normalise.  Returns ``(emb, pre | None)``."""
+    keep = []
     fmap = _dev(fmap, "gap_linear_norm.map")
     B, H, W, K = fmap.shape
-    wt = _dev(wt, "gap_linear_norm.wt", torch.float32)
+    wt = _dev(wt, "gap_linear_norm.wt", torch.float32, ("frmap_gap_linear_norm", "wt"))
     if wt.dim() != 2 or wt.shape[0] != K or not wt.is_contiguous():
         raise ValueError(f"gap_linear_norm: wt must be a contiguous [{K}][N] matrix")
     N = int(wt.shape[1])
     emb = torch.empty((B, N), dtype=torch.float32, device=fmap.device)
     pre = torch.empty((B, N), dtype=torch.float32, device=fmap.device) if want_pre else None
     _lib.check(_lib.load().frmap_gap_linear_norm(fmap.data_ptr(), wt.data_ptr(),
-                                                 _dev(scale, "scale", torch.float32).data_ptr() if scale is not None else 0,
-                                                 _dev(shift, "shift", torch.float32).data_ptr() if shift is not None else 0,
+                                                 _ptr(keep, scale, "scale", torch.float32, ("frmap_gap_linear_norm", "scale")) if scale is not None else 0,
+                                                 _ptr(keep, shift, "shift", torch.float32, ("frmap_gap_linear_norm", "shift")) if shift is not None else 0,
                                                  pre.data_ptr() if pre is not None else 0, emb.data_ptr(), float(eps),
                                                  B, H * W, K, N, int(bool(relu)), dt_code(fmap.dtype), _stream()), "gap_linear_norm")
     return emb, pre
@@ -861,7 +894,7 @@ def arcmargin_eval(x: torch.Tensor, w: torch.Tensor, label: torch.Tensor, s: flo
                    easy_margin: bool = False, want_minmax: bool = False):
     x = _dev(x, "arcmargin_eval.x", torch.float32)
     w = _dev(w, "arcmargin_eval.w", torch.float32)
-    label = _dev(label, "arcmargin_eval.label", torch.int64)
+    label = _dev(label, "arcmargin_eval.label", torch.int64, ("frmap_arcmargin_eval", "label"))
     B, D = x.shape
     Cc = w.shape[0]
     if label.numel() != B:
@@ -951,10 +984,10 @@ def track_step(state: torch.Tensor, boxes: torch.Tensor, probs: Optional[torch.T
     the `frames.clip_boxes` crop of every box with an id, 0 elsewhere.  ``counts`` is device data: the kernel clamps it to
     ``[0, max_boxes]``; a caller that has it on the host checks it there (`matching.StreamTracker` does)."""
     boxes = _dev(boxes, "track_step.boxes", torch.float32)
-    probs = None if probs is None else _dev(probs, "track_step.probs", torch.float32)
-    counts = _dev(counts, "track_step.counts", torch.int32)
-    frame_hw = _dev(frame_hw, "track_step.frame_hw", torch.int32)
-    state = _dev(state, "track_step.state", torch.uint8)
+    probs = None if probs is None else _dev(probs, "track_step.probs", torch.float32, ("frmap_track_step", "probs"))
+    counts = _dev(counts, "track_step.counts", torch.int32, ("frmap_track_step", "counts"))
+    frame_hw = _dev(frame_hw, "track_step.frame_hw", torch.int32, ("frmap_track_step", "frame_hw"))
+    state = _dev(state, "track_step.state", torch.uint8, ("frmap_track_step", "state"), owned=True)
     if boxes.dim() != 3 or boxes.shape[2] != 4:
         raise ValueError(f"track_step: boxes must be float32 [S, max_boxes, 4], got {tuple(boxes.shape)}")
     S, M = int(boxes.shape[0]), int(boxes.shape[1])
@@ -1073,9 +1106,9 @@ def track_fuse(state: torch.Tensor, ids: torch.Tensor, counts: torch.Tensor, emb
     ``counts``, passes a row that names no detection through and touches no other stream's slots whatever ``rows`` holds.
     ``fused[r]`` is the template of row r's track after this step and ``frames[r]`` its weight; rows that are passed through
     (`frames.fuse_tracks`) come back as they came with ``frames[r] = 0``."""
-    state = _dev(state, "track_fuse.state", torch.uint8)
-    ids = _dev(ids, "track_fuse.ids", torch.int32)
-    counts = _dev(counts, "track_fuse.counts", torch.int32)
+    state = _dev(state, "track_fuse.state", torch.uint8, ("frmap_track_fuse", "state"), owned=True)
+    ids = _dev(ids, "track_fuse.ids", torch.int32, ("frmap_track_fuse", "ids"))
+    counts = _dev(counts, "track_fuse.counts", torch.int32, ("frmap_track_fuse", "counts"))
     emb = _dev(emb, "track_fuse.emb", torch.float32)
     if ids.dim() != 2 or emb.dim() != 2 or tuple(counts.shape) != (ids.shape[0],):
         raise ValueError(f"track_fuse: ids must be int32 [S, max_boxes], counts [S] and emb float32 [N, D]; got {tuple(ids.shape)}, "
@@ -1098,7 +1131,7 @@ def track_fuse(state: torch.Tensor, ids: torch.Tensor, counts: torch.Tensor, emb
             raise ValueError("track_fuse: host_counts must be [S] values in [0, max_boxes]")
         _fuse_check_rows("track_fuse", rows, host_counts, S)
         rows = torch.from_numpy(rows).to(emb.device, non_blocking=True)
-    rows = _dev(rows, "track_fuse.rows", torch.int32)
+    rows = _dev(rows, "track_fuse.rows", torch.int32, ("frmap_track_fuse", "rows"))
     if tuple(rows.shape) != (N, 2):
         raise ValueError(f"track_fuse: rows must be int32 [{N}, 2], got {tuple(rows.shape)}")
     if N > S * M:
@@ -1205,7 +1238,7 @@ class ModelHandle:
         return IN_F32_NCHW, x.shape[0], x.shape[2], x.shape[3]
 
     def forward(self, x: torch.Tensor, what: int) -> torch.Tensor:
-        x = _dev(x, "model_forward.x")
+        x = _dev(x, "model_forward.x", None, ("frmap_model_forward", "x"))
         kind, B, H, W = self._geometry(x)
         with torch.cuda.device(x.device):
             if what == OUT_TRUNK_MAP and self.model_type == "baseline":      # three conv + MaxPool2d(2) stages, 128 channels
@@ -1228,17 +1261,17 @@ class ModelHandle:
     def embed_and_match(self, x: torch.Tensor, gallery: Optional[torch.Tensor], prepared, thresh: float, normalize: bool,
                         packed=False, want_emb: bool = False):
         """One C call: forward + top-1 match.  Returns (idx, dist, ids, packed | None, emb | None)."""
-        x = _dev(x, "model_embed_and_match.x")
+        x = _dev(x, "model_embed_and_match.x", None, ("frmap_model_embed_and_match", "x"))
         kind, B, H, W = self._geometry(x)
         G = int(gallery.shape[0]) if gallery is not None else 0
         with torch.cuda.device(x.device):
             gptr = ppk = pst = 0
             if G:
-                gallery = _dev(gallery, "model_embed_and_match.gallery", torch.float32)
+                src, gallery = gallery, _dev(gallery, "model_embed_and_match.gallery", torch.float32)
                 if gallery.shape[1] != self.embedding_dim:
                     raise ValueError(f"embed_and_match: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
                 gptr = gallery.data_ptr()
-                if _usable_pack(prepared, gallery, self.embedding_dim, "embed_and_match") is not None:
+                if _usable_pack(prepared, src, self.embedding_dim, "embed_and_match") is not None:
                     ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
             idx = torch.empty((B,), dtype=torch.int32, device=x.device)
             dist = torch.empty((B,), dtype=torch.float32, device=x.device)
@@ -1256,7 +1289,7 @@ class ModelHandle:
     def embed_and_search(self, x: torch.Tensor, gallery: Optional[torch.Tensor], prepared, k: int, labels: Optional[torch.Tensor] = None,
                          normalize: bool = False, want_emb: bool = False):
         """One C call: forward + exact top-k search (`match_topk`).  Returns (idx [B, k], dist [B, k], label [B, k] | None, emb | None)."""
-        x = _dev(x, "model_embed_and_search.x")
+        x = _dev(x, "model_embed_and_search.x", None, ("frmap_model_embed_and_search", "x"))
         kind, B, H, W = self._geometry(x)
         k = int(k)
         if not 1 <= k <= MATCH_TOPK_MAX:
@@ -1265,14 +1298,14 @@ class ModelHandle:
         with torch.cuda.device(x.device):
             gptr = ppk = pst = lptr = 0
             if G:
-                gallery = _dev(gallery, "model_embed_and_search.gallery", torch.float32)
+                src, gallery = gallery, _dev(gallery, "model_embed_and_search.gallery", torch.float32)
                 if gallery.shape[1] != self.embedding_dim:
                     raise ValueError(f"embed_and_search: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
                 gptr = gallery.data_ptr()
-                if _usable_pack(prepared, gallery, self.embedding_dim, "embed_and_search") is not None:
+                if _usable_pack(prepared, src, self.embedding_dim, "embed_and_search") is not None:
                     ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
             if labels is not None:
-                labels = _dev(labels, "model_embed_and_search.labels", torch.int32)
+                labels = _dev(labels, "model_embed_and_search.labels", torch.int32, ("frmap_model_embed_and_search", "labels"))
                 if tuple(labels.shape) != (G,):
                     raise ValueError(f"embed_and_search: labels must be int32 [{G}]")
             idx = torch.empty((B, k), dtype=torch.int32, device=x.device)

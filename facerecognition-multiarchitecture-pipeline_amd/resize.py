@@ -340,6 +340,9 @@ def _crop_launches(what: str, fr, dev, r, m, out_h: int, out_w: int, bgr: bool) 
         tab = torch.from_numpy(np.concatenate([desc] + mats + [r[sel].astype(np.int32).view(np.uint8).reshape(-1)])).to(dev, non_blocking=True)
         p_m = tab.data_ptr() + desc.nbytes
         p_r = p_m + 48 * len(sel) * len(mats)
+        name = entry.__name__
+        for arg, ptr in (("frames", tab.data_ptr()), ("rois", p_r)) + ((("mats", p_m),) if mats else ()):     # (this upload's own layout)
+            assert ptr % _lib.align_of(name, arg) == 0, (name, arg, ptr)
         args = [tab.data_ptr(), len(fr), p_r] + [p_m] * len(mats) + [dst.data_ptr(), len(sel), oh, ow, int(h[sel].max()), int(w[sel].max())]
         with torch.cuda.device(dev):
             _lib.check(entry(*args, *([] if yuv else [int(bool(bgr))]), torch.cuda.current_stream().cuda_stream), what)

@@ -16,6 +16,24 @@
  *   - `dtype`: FRMAP_BF16 or FRMAP_F16 = storage + MFMA input type of activations / packed conv
  *     weights (accumulation is always fp32); heads and matching are fp32 throughout;
  *   - activations are NHWC ("channels last"), C a multiple of 32 for frmap_conv_igemm;
+ *   - pointer alignment: a device pointer must be aligned to the widest access a kernel makes through it.  A call whose pointers
+ *     meet the alignment below computes the same bits wherever its buffers start; a pointer below it is rejected (-1, the text
+ *     names the entry point, the argument and the bytes) before any launch.  NULL for an optional argument is not checked.
+ *     By class of pointer:
+ *       tensors in `dtype` (activations, residuals, packed weights, packed galleries, fp16 splits, outputs): 16-byte aligned
+ *         (every kernel moves them as 8-element vectors, LDS-DMA fetches included);
+ *       fp32 per-channel vectors of the MFMA kernels (`shift` of the convolutions, the stems and frmap_linear_mfma; pos / gamma /
+ *         beta of frmap_add_pos_layernorm): 16-byte aligned (read four channels at a time);
+ *       fp32 matrices that a GEMM, the exact re-score or the tracker reads in rows of float4 - emb, gallery, a, b, stat_w,
+ *         gallery_stat, emb_out of the model calls, x and w of frmap_linear_f32 / frmap_cosine_logits / frmap_arcmargin_eval,
+ *         boxes, fused (their row lengths are multiples of 4, or the kernel takes the tail element by element): 16-byte aligned;
+ *       everything walked element by element - the fp32 operands and outputs of the other heads (any row length D), per-probe
+ *         results (idx_out, dist_out, id_or_unknown_out, packed_out, label_out, count_out ...), int32 / int64 labels, counts and
+ *         ids, uint64 counters, uint8 images, the casts: the element size (1, 2, 4 or 8 bytes);
+ *       records with 8-byte fields or int32 pairs (frames, items, mats, rows, pair_out): 8-byte aligned;
+ *       workspaces and state buffers: 16-byte aligned, 256-byte aligned where the entry point says so.
+ *     An argument that departs from its class says so where it is declared.  Where a launcher has a narrower path for some
+ *     shapes (odd H * W, D % 512 != 0) it accepts the narrower alignment there; the figure given is the one that always serves.
  *   - threading / devices (the reference calls model(x) from a daemon thread while the main thread
  *     matches, src/app.py:331-335,639): every entry point may be called from any host thread; like
  *     every HIP launch it targets the calling thread's CURRENT device, so the caller makes the
@@ -52,13 +70,15 @@ const char* frmap_last_error(void);
 /* ---------------------------------------------------------------------------------------------
  * Input layout: fp32 NCHW B×3×H×W  ->  NHWC4 (3 channels + one zero channel) in `dtype`.
  * Replaces the implicit layout the reference feeds nn.Conv2d with (src/testing.py:99-104,251).
+ * x_nchw needs its element size and out_nhwc4 is 8-byte aligned (one pixel per store): with an even H * W, x_nchw 8-byte and
+ * out_nhwc4 16-byte aligned the launcher takes the path that moves two pixels at a time, otherwise the one-pixel path.  Same bits.
  * ------------------------------------------------------------------------------------------- */
 int frmap_pack_input_nchw_f32(const float* x_nchw, void* out_nhwc4, int B, int H, int W,
                               int dtype, void* stream);
 
 /* uint8 HWC RGB B×H×W×3 -> ToTensor (u/255) + Normalize ((x-mean)/std), src/testing.py:99-104,
  * src/app.py:39-42.  Writes fp32 NCHW (out_nchw_f32) and/or NHWC4 `dtype` (out_nhwc4); either may be
- * NULL.  mean3_host / std3_host: 3 floats each in HOST memory. */
+ * NULL.  mean3_host / std3_host: 3 floats each in HOST memory.  out_nhwc4: 8-byte aligned (one pixel = 8 bytes per store). */
 int frmap_normalize_u8_hwc(const unsigned char* img_u8, float* out_nchw_f32, void* out_nhwc4, int B, int H,
                            int W, const float* mean3_host, const float* std3_host, int dtype, void* stream);
 
@@ -70,7 +90,7 @@ int frmap_normalize_u8_hwc(const unsigned char* img_u8, float* out_nchw_f32, voi
  * with offsets (int32 elements) into `tables` of the per-axis bounds [out][2] = (first input sample, taps) and coefficients
  * [out][ks] (ks = 0: that axis keeps its size) - built by the host in float64 with Pillow's operation order
  * (resize.py:bilinear_coeffs).  out: B x out_h x out_w x 3 uint8.  One workgroup resizes rows_per_block output rows;
- * lds_rows = the most input rows one workgroup touches (lds_rows * out_w * 4 bytes of LDS). */
+ * lds_rows = the most input rows one workgroup touches (lds_rows * out_w * 4 bytes of LDS).  src_pool and out are byte-addressed. */
 int frmap_resize_bilinear_u8(const unsigned char* src_pool, const void* items, const int* tables, unsigned char* out,
                              int B, int out_h, int out_w, int rows_per_block, int lds_rows, void* stream);
 
@@ -248,6 +268,7 @@ int frmap_track_fuse_host(void* state, const int32_t* ids, const int32_t* counts
  *                                 KH == KW in {1,3});  out elems = Cout*Cin*KH*KW
  *   frmap_pack_conv_weight_c3   : for frmap_conv_small_cin  (Cin == 3);  out elems =
  *                                 Cout * frmap_small_cin_kpad(KH, KW)
+ * The packers write w_packed element by element: 2-byte aligned serves here; the convolutions that read it need 16.
  * ------------------------------------------------------------------------------------------- */
 int frmap_pack_conv_weight(const float* w_oihw, void* w_packed, int Cout, int Cin, int KH, int KW,
                            int dtype, void* stream);
@@ -261,7 +282,7 @@ int frmap_pack_conv_weight_c3(const float* w_oihw, void* w_packed, int Cout, int
  *                                          src/face_models.py:67,463,658; face_models.py:115-117)
  *   BaselineNet conv1 3x3 s1 p1 -> 32     (src/face_models.py:21-22,38)
  * Implicit GEMM on v_mfma_f32_16x16x32 with the K axis laid along (kw, c) of each kernel row.
- * out: NHWC B×Ho×Wo×Cout in `dtype`.  Cout in {32, 64}.
+ * out: NHWC B×Ho×Wo×Cout in `dtype`.  Cout in {32, 64}.  in_nhwc4: 8-byte aligned (pixels are staged one 8-byte pixel at a time).
  * Non-finite input ("Non-finite values"): a NaN / inf pixel makes every output of its receptive field NaN / inf as
  * in PyTorch (the ReLU keeps NaN) and may also make NaN the outputs whose zero-weight pad taps read it (same image, one pixel
  * column beside the field; 3x3: the output row below as well); no other output and no other image changes by a bit.
@@ -273,7 +294,8 @@ int frmap_conv_small_cin(const void* in_nhwc4, const void* w_packed, const float
  * `self.pool(F.relu(self.bn1(self.conv1(x))))` (src/face_models.py:38) in one launch.  The kernel walks
  * its output pixels in pool-major order (4 consecutive pixels = one 2x2 window), so the pooled value is
  * a max over 4 accumulator rows; the 32×H×W conv map never reaches HBM.  Even Hi, Wi.
- * out: B×(Hi/2)×(Wi/2)×32.  Non-finite values: as frmap_conv_small_cin followed by frmap_maxpool, bit for bit. */
+ * out: B×(Hi/2)×(Wi/2)×32.  Non-finite values: as frmap_conv_small_cin followed by frmap_maxpool, bit for bit.
+ * in_nhwc4: 8-byte aligned, as frmap_conv_small_cin. */
 int frmap_conv_small_cin_pool2(const void* in_nhwc4, const void* w_packed, const float* shift, void* out,
                                int B, int Hi, int Wi, int Cout, int relu, int dtype, void* stream);
 
@@ -283,6 +305,10 @@ int frmap_conv_small_cin_pool2(const void* in_nhwc4, const void* w_packed, const
  * Replaces conv1/bn1/relu/maxpool of torchvision resnet18 (src/face_models.py:67,463,658) plus the
  * input layout cast.  w_packed_c3: from frmap_pack_conv_weight_c3(…, 64, 7, 7).  Needs Wi <= ~224
  * (pooled width <= 56); wider inputs use frmap_pack_input + frmap_conv_small_cin + frmap_maxpool.
+ * x_nchw needs its element size only (4 bytes): a 16-byte aligned tensor with Wi % 4 == 0 is staged with 16-byte loads (and takes
+ * the second-generation kernel), any other through the scalar staging path of the first-generation kernel.  frmap_stem7x7_maxpool2
+ * gives the same bits either way; frmap_stem7x7_maxpool sums a pixel's products in another order in its two kernels, so the same
+ * image at a 4-byte and at a 16-byte aligned address may differ in the last place of a few outputs (both within one rounding).
  * Non-finite input (all four stem entry points): a NaN / inf pixel, or an fp32 pixel beyond the range of `dtype`, reaches every
  * pooled output whose window holds a conv position of its receptive field, as nn.ReLU + nn.MaxPool2d propagate it (a window
  * keeps a NaN, drops a -inf), and may make NaN the windows holding a conv position whose zero-weight pad tap reads it (one pixel
@@ -300,7 +326,7 @@ int frmap_stem7x7_maxpool2(const float* x_nchw, const void* w_packed_c3, const f
  * staged, through a per-channel 256-entry table rounded to `dtype` exactly as
  * frmap_normalize_u8_hwc + the fp32 entry points would — the 602 KB/face fp32 tensor never exists
  * (SURVEY.md §8f row 1).  pool3 != 0: MaxPool2d(3,2,1) (ResNet stem); 0: MaxPool2d(2,2) (Siamese).
- * Needs Wi % 4 == 0 and a 4-byte aligned tensor. */
+ * Needs Wi % 4 == 0 and x_u8_hwc 4-byte aligned (4 pixels = 12 bytes are read as three dwords). */
 int frmap_stem7x7_maxpool_u8(const unsigned char* x_u8_hwc, const float* mean3_host, const float* std3_host,
                              const void* w_packed_c3, const float* shift, void* out, int B, int Hi, int Wi,
                              int pool3, int dtype, void* stream);
@@ -465,7 +491,7 @@ int frmap_mean_layernorm(const void* t, const float* gamma, const float* beta, f
  *   spatial_w : device fp32 [2][KS][KS], spatial_b: device float[1]  (SpatialAttention.conv, :199; pad KS/2)
  *   out_map   : [B][H*W][C] (dtype) = (gamma * softmax(q k^T) v + x) * sigmoid(conv([mean_c, max_c]))  or NULL
  *   out_pool  : fp32 [B][C] = mean over the H*W positions of that map (AdaptiveAvgPool2d(1))            or NULL
- *   H*W <= 64, Cq <= 128 (multiple of 8), C in {256, 512}, KS odd.
+ *   H*W <= 64, Cq <= 128 (multiple of 8), C in {256, 512}, KS odd.  out_map: 4-byte aligned (stored two channels at a time).
  * ------------------------------------------------------------------------------------------- */
 int frmap_cnn_attention(const void* qkv, const void* x, const float* gamma, const float* spatial_w,
                         const float* spatial_b, void* out_map, float* out_pool, int B, int H, int W, int Cq,
@@ -515,14 +541,16 @@ int frmap_match_top1(const float* emb, const float* gallery, int32_t* idx_out, f
  * numbers (hi = fp16(S x), lo = fp16(S x - hi)); one K = 3 D GEMM accumulates a_hi.g_hi + a_hi.g_lo + a_lo.g_hi in
  * fp32 (the fp32 dot product to ~2^-22).  frmap_match_pack_gallery prepares a gallery ONCE: packed_out
  * (frmap_match_gallery_pack_bytes(G, D) bytes) and stat_w_out [G][4]; D % 32 == 0.  Each row is scaled by its own power
- * of two before the split, so any finite magnitude is safe.  frmap_match_top1_packed: workspace =
+ * of two before the split, so any finite magnitude is safe.  The packer writes packed_out element by element (2-byte aligned serves
+ * there; every call that reads the pack needs it and stat_w 16-byte aligned).  frmap_match_top1_packed: workspace =
  * frmap_match_workspace_bytes(B, G) bytes, probe_split = B * 3 * D fp16 of scratch; `gallery` is still the fp32 matrix
  * (candidates are re-scored from it). */
 size_t frmap_match_gallery_pack_bytes(int G, int D);
 int frmap_match_pack_gallery(const float* gallery, void* packed_out, float* stat_w_out, int G, int D, void* stream);
 /* Incremental enrolment (src/app.py:428-436 appends one identity and re-saves): rows [row_lo, row_hi) of a gallery that now
  * holds G rows were appended (row_hi == G) or edited in place; only their statistics and the 64-row tiles they touch are
- * re-packed.  packed_out / stat_w_out must be sized for the gallery's CAPACITY (>= G rows). */
+ * re-packed.  packed_out / stat_w_out must be sized for the gallery's CAPACITY (>= G rows).  As in frmap_match_pack_gallery the
+ * packer itself takes packed_out 2-byte aligned; the calls that read the pack need 16. */
 int frmap_match_pack_gallery_rows(const float* gallery, void* packed_out, float* stat_w_out, int row_lo, int row_hi,
                                   int G, int D, void* stream);
 int frmap_match_top1_packed(const float* emb, const float* gallery, const void* gallery_packed, const float* stat_w,
@@ -661,6 +689,12 @@ int frmap_arcmargin_eval(const float* x, const float* w, const int64_t* label, f
  *                                                   'hybrid': fc; 'siamese': none (rejected)
  *                            (TRUNK_MAP / POOLED are the ResNet trunk's outputs: 'cnn', 'arcface', 'hybrid', 'resnet18_trunk'.)
  *                            workspace: frmap_model_workspace_bytes(m, B, H, W) bytes, 256-byte aligned, caller-owned.
+ *                            x: 4-byte aligned for both input kinds - fp32: its element size, whatever the family and the size
+ *                            (the stems and the layout kernel pick their wider paths from the pointer); uint8: where the fused
+ *                            uint8 stem takes the image (W % 4 == 0 and a ResNet trunk up to ~224 wide or a siamese tower up to
+ *                            ~256 wide); a uint8 image that goes through the byte-wise normalise kernel may start anywhere;
+ *                            out: 16-byte aligned for FRMAP_OUT_TRUNK_MAP, 4 for the fp32 outputs.  The same x and workspace rules
+ *                            hold for the two calls below, whose workspace is 256-byte aligned as well.
  *                            Nothing is allocated, freed or synchronised; all launches go to `stream`.
  *   frmap_model_embed_and_match  forward + compare_faces for every face (src/app.py:44,50-64): embedding (L2-normalised first if
  *                            `normalize`, for models whose embedding is not unit-norm) -> first arg-min of ||e - g + 1e-6||_2

@@ -22,6 +22,16 @@ the two results must be bit-identical to each other and to an unguarded call on 
 an element left unwritten differs between the fills, and so does a value that leaked in from a band or a workspace field that
 was assumed clean.
 
+PLACEMENT (`shifted`).  A guard may be given a placement rule, `shift(dtype, kind, who)` -> bytes: the payload of that allocation
+then starts at 256 k + shift instead of 256 k (`kind` is "operand" or "empty", `who` the function that asked, as `describe()`
+prints it; the shift is a multiple of the element size and below 256).  No rule - the default - is a shift of 0: the payload
+starts 256-byte aligned, as every guard test has it.  `min_placement(requirement)` turns a requirement in bytes,
+`requirement(dtype, kind, who)` -> A (a power of two), into the rule "aligned to A and not to 2 A" (shift A; 0 for A >= 256).
+THE SECOND RULE: `shifted(run, ..., requirement=)` takes the unguarded aligned call as the reference and runs `run(place)` under
+each fill with every operand, output and workspace placed by `min_placement(requirement)`; both runs pass `check()` and both
+results equal the reference bit for bit.  A kernel that rounds an address down to its vector width, takes its vector path from
+the shape alone or assumes a 256-byte aligned base reads or writes other bytes at such a placement: the bands or the bits show it.
+
 BAND.  At least the largest output tile any planned kernel stores, so that a whole misplaced tile still lands in a band.  The
 planner's second-generation layouts (`conv_plan.cpp`: `pp_bn`, `plan_pp_3x3`, `plan_pp_1x1`, `match_gemm_plan`) are 224 pixels
 x 256 channels and 448 pixels x 128 channels; the first generation's are 256 pixels (`BM`) x 64 channels.  The largest is
@@ -77,26 +87,31 @@ class _Alloc:
 
 
 class Guard:
-    def __init__(self, fill, band=BAND, device="cuda"):
+    def __init__(self, fill, band=BAND, device="cuda", shift=None):
         if not 0 <= int(fill) <= 255 or int(band) < 1:
             raise ValueError("Guard: fill is one byte, band at least one byte")
         self.fill, self.band, self.device = int(fill), int(band), torch.device(device)
+        self.shift = shift                       # the placement rule (module docstring); None: every payload 256-byte aligned
         self.allocs = []
 
     # -------------------------------------------------------------------------------------------------------------------
     def _alloc(self, shape, dtype, kind, who):
         shape = _shape((shape,)) if not isinstance(shape, int) else (int(shape),)
-        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-        # (ALIGN - 1 spare bytes: the allocator's own alignment may be weaker than 256; they lengthen the front band)
-        raw = torch.empty((self.band + nbytes + self.band + ALIGN - 1,), dtype=torch.uint8, device=self.device)
+        esize = torch.empty((), dtype=dtype).element_size()
+        nbytes = int(np.prod(shape, dtype=np.int64)) * esize
+        shift = int(self.shift(dtype, kind, who)) if self.shift is not None else 0
+        if not 0 <= shift < ALIGN or shift % esize:
+            raise ValueError("Guard: a placement shift is a multiple of the element size in [0, %d), got %d for %s" % (ALIGN, shift, dtype))
+        # (ALIGN - 1 spare bytes: the allocator's own alignment may be weaker than 256; they and the shift lengthen the front band)
+        raw = torch.empty((self.band + nbytes + self.band + ALIGN - 1 + shift,), dtype=torch.uint8, device=self.device)
         raw.fill_(self.fill)
-        off = self.band + (-(raw.data_ptr() + self.band)) % ALIGN
+        off = self.band + (-(raw.data_ptr() + self.band)) % ALIGN + shift
         raw = raw[:off + nbytes + self.band]
         a = _Alloc()
         a.order, a.raw, a.off, a.nbytes, a.shape, a.dtype, a.who, a.kind, a.cpu = len(self.allocs), raw, off, nbytes, shape, dtype, who, kind, None
         self.allocs.append(a)
         payload = raw[off:off + nbytes].view(dtype).view(shape) if nbytes else torch.empty(shape, dtype=dtype, device=self.device)
-        assert nbytes == 0 or payload.data_ptr() % ALIGN == 0
+        assert nbytes == 0 or payload.data_ptr() % ALIGN == shift
         return a, payload
 
     def empty(self, shape, dtype, who=None):
@@ -264,4 +279,43 @@ def two_fills(run, modules=(), device="cuda", band=BAND, canon=None, what=""):
                           "outside the operands): %s" % (what, k, FILLS[0], FILLS[1], d)
         d = first_difference(got[FILLS[0]][k], ref[k])
         assert d is None, "%s: result %d of the guarded runs differs from the unguarded call: %s" % (what, k, d)
+    return ref
+
+
+# -----------------------------------------------------------------------------------------------------------------------
+# the second rule: placement
+# -----------------------------------------------------------------------------------------------------------------------
+def min_placement(requirement):
+    """The placement rule "aligned to A and not to 2 A" for A = `requirement(dtype, kind, who)` bytes (a power of two; an int
+    serves for a constant): the payload starts at 256 k + A.  A >= 256 keeps the 256-byte aligned start (a guard cannot promise more)."""
+    def shift(dtype, kind, who):
+        a = int(requirement(dtype, kind, who)) if callable(requirement) else int(requirement)
+        if a < 1 or a & (a - 1):
+            raise ValueError("min_placement: a requirement is a power of two, got %d" % a)
+        return a if a < ALIGN else 0
+    return shift
+
+
+def shifted(run, modules=(), device="cuda", band=BAND, canon=None, what="", requirement=16):
+    """THE SECOND RULE.  `run(place)` as in `two_fills`.  The reference is the unguarded call (`place` = a plain copy to `device`:
+    the allocator's own alignment).  Under each fill every operand `run` places, and every output and workspace the patched
+    `modules` allocate, starts at the minimum alignment `requirement` gives it (`min_placement`); each run passes `check()` and
+    its results hold the reference's bits, tensor by tensor.  Returns the reference as a flat list of CPU tensors."""
+    canon = canon or (lambda r: r)
+    dev = torch.device(device)
+    ref = run(lambda t: t.to(dev, copy=True))
+    if dev.type == "cuda":
+        Guard(0, 1, dev)._sync()
+    ref = canon(_flat(ref))
+    for fill in FILLS:
+        g = Guard(fill, band, dev, shift=min_placement(requirement))
+        with g.patch(*modules):
+            res = run(g.place)
+        g.check()
+        got = canon(_flat(res))
+        assert len(got) == len(ref), (what, "fill 0x%02X returned %d results, the aligned call %d" % (fill, len(got), len(ref)))
+        for k in range(len(ref)):
+            d = first_difference(got[k], ref[k])
+            assert d is None, "%s: result %d under fill 0x%02X, every buffer at its minimum alignment, differs from the aligned " \
+                              "call: %s" % (what, k, fill, d)
     return ref
