@@ -71,6 +71,9 @@ PROTOTYPES = {
     "frmap_conv3x3s2_pp_layout": (_i, [_i, _i, _i, _i, _i]),
     "frmap_conv3x3_pp_ds_layout": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "frmap_conv3x3_pp_tile_px": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "frmap_conv_plan_key": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _i]),
+    "frmap_conv_plan_keys": (_i, [_i, C.c_char_p, _i]),
+    "frmap_conv_plan_selfcheck": (_i, []),
     "frmap_conv_igemm_ds_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "frmap_conv_igemm_ds": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "frmap_linear_mfma_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -24,6 +24,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <set>
+#include <string>
+#include <vector>
+
 struct ConvParams {
   const void* in;
   const void* wpk;
@@ -1180,31 +1184,57 @@ static ConvParams conv_params(const ConvLayer& L, const ConvPlan& q, const ConvP
   return p;
 }
 
+// The instantiations of this file: the key of conv_plan.h beside its two function pointers.  conv_kernel looks a plan's key up
+// here, so the name the queries report is the name of the row that is launched.
 typedef void (*conv_kern_t)(const ConvParams);
-template <typename TT, bool EARLY>
-static conv_kern_t wave_kernel(const ConvPlan& q) {
-  if (!q.POOL) return conv3x3_c64_wave_kernel<TT, 2, false, EARLY>;
-  return q.NCH == 2 ? conv3x3_c64_wave_kernel<TT, 2, true, EARLY> : conv3x3_c64_wave_kernel<TT, 1, true, EARLY>;
+struct ConvKernelRow { const char* key; conv_kern_t bf16, f16; };
+#define CONV_ROW(key, kern, ...) {key, kern<BF16, ##__VA_ARGS__>, kern<F16, ##__VA_ARGS__>}
+static const ConvKernelRow CONV_KERNELS[] = {
+    CONV_ROW("conv_igemm_kernel<256,1,1>", conv_igemm_kernel, 256, 1, 1),
+    CONV_ROW("conv_igemm_kernel<256,3,1>", conv_igemm_kernel, 256, 3, 1),
+    CONV_ROW("conv_igemm_kernel<256,3,2>", conv_igemm_kernel, 256, 3, 2),
+    CONV_ROW("conv_igemm_kernel<128,3,1>", conv_igemm_kernel, 128, 3, 1),
+    CONV_ROW("conv_igemm_kernel<128,3,2>", conv_igemm_kernel, 128, 3, 2),
+    CONV_ROW("conv_igemm_kernel<256,3,1,POOL>", conv_igemm_kernel, 256, 3, 1, true),
+    CONV_ROW("conv_igemm_kernel<128,3,1,POOL>", conv_igemm_kernel, 128, 3, 1, true),
+    CONV_ROW("conv1x1_kernel<1>", conv1x1_kernel, 1),
+    CONV_ROW("conv1x1_kernel<2>", conv1x1_kernel, 2),
+    CONV_ROW("conv1x1_kernel<4>", conv1x1_kernel, 4),
+    CONV_ROW("conv3x3_c64_wave_kernel<2>", conv3x3_c64_wave_kernel, 2, false, false),
+    CONV_ROW("conv3x3_c64_wave_kernel<2,EARLY>", conv3x3_c64_wave_kernel, 2, false, true),
+    CONV_ROW("conv3x3_c64_wave_kernel<2,POOL>", conv3x3_c64_wave_kernel, 2, true, false),
+    CONV_ROW("conv3x3_c64_wave_kernel<2,POOL,EARLY>", conv3x3_c64_wave_kernel, 2, true, true),
+    CONV_ROW("conv3x3_c64_wave_kernel<1,POOL>", conv3x3_c64_wave_kernel, 1, true, false),
+    CONV_ROW("conv3x3_c64_wave_kernel<1,POOL,EARLY>", conv3x3_c64_wave_kernel, 1, true, true),
+    CONV_ROW("conv3x3_fast_kernel<>", conv3x3_fast_kernel, false),
+    CONV_ROW("conv3x3_fast_kernel<DS>", conv3x3_fast_kernel, true),
+    CONV_ROW("conv3x3s2_split_kernel<>", conv3x3s2_split_kernel),
+    CONV_ROW("conv3x3s2_fast_kernel<>", conv3x3s2_fast_kernel),
+};
+#undef CONV_ROW
+static const int N_CONV_KERNELS = (int)(sizeof(CONV_KERNELS) / sizeof(CONV_KERNELS[0]));
+
+// the row of a plan's key (resolved once per key: by_index[i] is the row of conv_plan_keys()[i], null = not of this file)
+static const ConvKernelRow* conv_kernel_row(const ConvPlan& q) {
+  static const std::vector<const ConvKernelRow*> by_index = [] {
+    int n = 0;
+    const char* const* keys = conv_plan_keys(&n);
+    std::vector<const ConvKernelRow*> v((size_t)n, nullptr);
+    for (int i = 0; i < n; ++i)
+      for (const ConvKernelRow& r : CONV_KERNELS)
+        if (!strcmp(r.key, keys[i])) { v[(size_t)i] = &r; break; }
+    return v;
+  }();
+  const int i = conv_plan_key_index(q);
+  return i < 0 ? nullptr : by_index[(size_t)i];
 }
-template <typename TT>
-static conv_kern_t conv_kernel(const ConvPlan& q) {
-  switch (q.kernel) {
-    case CK_IGEMM:
-      if (q.POOL) return q.BM == 256 ? conv_igemm_kernel<TT, 256, 3, 1, true> : conv_igemm_kernel<TT, 128, 3, 1, true>;
-      if (q.KS == 1) return conv_igemm_kernel<TT, 256, 1, 1>;
-      if (q.BM == 256) return q.SWZ == 1 ? conv_igemm_kernel<TT, 256, 3, 1> : conv_igemm_kernel<TT, 256, 3, 2>;
-      return q.SWZ == 1 ? conv_igemm_kernel<TT, 128, 3, 1> : conv_igemm_kernel<TT, 128, 3, 2>;
-    case CK_1X1: return q.CKS == 4 ? conv1x1_kernel<TT, 4> : (q.CKS == 2 ? conv1x1_kernel<TT, 2> : conv1x1_kernel<TT, 1>);
-    case CK_WAVE: return q.EARLY ? wave_kernel<TT, true>(q) : wave_kernel<TT, false>(q);
-    case CK_FAST: return q.DS ? conv3x3_fast_kernel<TT, true> : conv3x3_fast_kernel<TT, false>;
-    case CK_S2_SPLIT: return conv3x3s2_split_kernel<TT>;
-    case CK_S2_FAST: return conv3x3s2_fast_kernel<TT>;
-    default: return nullptr;
-  }
+static conv_kern_t conv_kernel(const ConvPlan& q, int dtype) {
+  const ConvKernelRow* r = conv_kernel_row(q);
+  return !r ? nullptr : (dtype == FRMAP_BF16 ? r->bf16 : r->f16);
 }
 
 static int conv_launch(const ConvPlan& q, const ConvParams& p, int dtype, hipStream_t st) {
-  const conv_kern_t kern = dtype == FRMAP_BF16 ? conv_kernel<BF16>(q) : conv_kernel<F16>(q);
+  const conv_kern_t kern = conv_kernel(q, dtype);
   FRMAP_REQUIRE(kern, "conv_igemm: no kernel for plan %d", q.kernel);
   if (frmap_big_lds((const void*)kern, 160 * 1024)) return -2;
   FRMAP_REQUIRE(FRMAP_GRID_FITS(q.nblocks, q.kernel == CK_WAVE ? 512 : 256), "conv_igemm: %d workgroups exceed the grid", q.nblocks);
@@ -1233,19 +1263,25 @@ static int conv_require_aligned(const char* who, const ConvPtrs& a, const char* 
   return 0;
 }
 
-static int conv_igemm_impl(const char* who, const ConvLayer& L, const ConvPtrs& a, int relu, int dtype, void* stream) {
-  FRMAP_REQUIRE(a.in && a.w && a.shift && a.out, "conv_igemm: null pointer");
-  if (int rc = conv_require_aligned(who, a)) return rc;
+// the layers frmap_conv_igemm / frmap_conv_igemm_ds accept
+static int conv_require_layer(const ConvLayer& L) {
   FRMAP_REQUIRE(L.K == 1 || L.K == 3, "conv_igemm: kernel size %d not supported (1 or 3)", L.K);
   FRMAP_REQUIRE(L.stride == 1 || L.stride == 2, "conv_igemm: stride %d not supported", L.stride);
   FRMAP_REQUIRE((L.K == 3 && L.pad == 1) || (L.K == 1 && L.pad == 0), "conv_igemm: pad %d with K=%d not supported", L.pad, L.K);
   FRMAP_REQUIRE(L.Cin > 0 && L.Cin % 32 == 0, "conv_igemm: Cin=%d must be a multiple of 32", L.Cin);
   FRMAP_REQUIRE(L.Cout > 0 && L.Cout % 64 == 0, "conv_igemm: Cout=%d must be a multiple of 64", L.Cout);
-  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm: bad dtype %d", dtype);
   FRMAP_REQUIRE(L.B > 0 && L.Hi > 0 && L.Wi > 0, "conv_igemm: empty input");
   FRMAP_REQUIRE(L.Ho() > 0 && L.Wo() > 0, "conv_igemm: empty output");
   FRMAP_REQUIRE((long long)L.B * L.Ho() * L.Wo() < (1ll << 31), "conv_igemm: too many output pixels");
   FRMAP_REQUIRE(L.Wi + 2 * L.pad < 32768 && L.Hi + 2 * L.pad < 32768, "conv_igemm: image too large");
+  return 0;
+}
+
+static int conv_igemm_impl(const char* who, const ConvLayer& L, const ConvPtrs& a, int relu, int dtype, void* stream) {
+  FRMAP_REQUIRE(a.in && a.w && a.shift && a.out, "conv_igemm: null pointer");
+  if (int rc = conv_require_aligned(who, a)) return rc;
+  FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "conv_igemm: bad dtype %d", dtype);
+  if (int rc = conv_require_layer(L)) return rc;
   const ConvPlan q = plan_of(L);
   FRMAP_REQUIRE(q.taken(), "%s", q.error);
   return conv_run(L, q, a, relu, dtype, (hipStream_t)stream);
@@ -1301,6 +1337,66 @@ extern "C" int frmap_conv_igemm_pool2(const void* in, const void* w_packed, cons
                 "conv_igemm_pool2: shape B=%d %dx%d Cin=%d Cout=%d not taken (even H and W, Cin %% 32 == 0, Cout %% 64 == 0, rows fit LDS)",
                 B, Hi, Wi, Cin, Cout);
   return conv_run(L, q, ConvPtrs{in, w_packed, shift, nullptr, out, nullptr, nullptr, nullptr}, relu, dtype, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Which instantiation runs a layer (conv_plan.h, "THE KEY"): read-only queries, nothing is launched
+// ------------------------------------------------------------------------------------------------
+// fuse: 0 = none, 1 = residual, 2 = fused shortcut (frmap_conv_igemm_ds), 3 = fused 2x2 max-pool (frmap_conv_igemm_pool2; K = 3,
+// stride 1).  Plans exactly as the launchers do, under the tuning, hooks, CU count and batch-invariant flag in force.
+extern "C" int frmap_conv_plan_key(int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int fuse, int ds_Hi, int ds_Wi,
+                                   int ds_Cin, int ds_stride, char* buf, int n) {
+  if (buf && n > 0) buf[0] = 0;
+  FRMAP_REQUIRE(fuse >= FUSE_NONE && fuse <= FUSE_POOL2, "conv_plan_key: fuse %d is not 0 .. 3", fuse);
+  FRMAP_REQUIRE(fuse < FUSE_SHORTCUT || (K == 3 && stride == 1), "conv_plan_key: fuse %d needs K = 3 and stride 1", fuse);
+  const bool ds = fuse == FUSE_SHORTCUT;
+  const ConvLayer L = {B, Hi, Wi, Cin, Cout, K, stride, K / 2, fuse, ds ? ds_Hi : 0, ds ? ds_Wi : 0, ds ? ds_Cin : 0, ds ? ds_stride : 0};
+  if (fuse != FUSE_POOL2) {
+    if (conv_require_layer(L)) return 0;
+  }
+  const ConvPlan q = plan_of(L);
+  if (!q.taken()) {
+    if (fuse == FUSE_POOL2) frmap_set_error("conv_igemm_pool2: shape B=%d %dx%d Cin=%d Cout=%d not taken", B, Hi, Wi, Cin, Cout);
+    else frmap_set_error("%s", q.error);
+    return 0;
+  }
+  const char* key = conv_plan_key(q);
+  if (!key[0]) frmap_set_error("conv_plan_key: no instantiation for plan %d", q.kernel);
+  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", key);
+  return (int)strlen(key);
+}
+
+// the number of keys; 0 <= index < that: key `index` copied into buf
+extern "C" int frmap_conv_plan_keys(int index, char* buf, int n) {
+  int count = 0;
+  const char* const* keys = conv_plan_keys(&count);
+  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", index >= 0 && index < count ? keys[index] : "");
+  return count;
+}
+
+// Every key selects a plan whose key it is, both launch tables answer it for both data types with a pointer of its own, and the
+// tables hold no row beyond the keys.  0, or -1 with the first failure as the error text.
+extern "C" int frmap_conv_plan_selfcheck(void) {
+  int count = 0;
+  const char* const* keys = conv_plan_keys(&count);
+  std::set<const void*> seen;
+  std::set<std::string> names;
+  for (int i = 0; i < count; ++i) {
+    ConvPlan q{};
+    FRMAP_REQUIRE(names.insert(keys[i]).second, "conv_plan_selfcheck: key %s is listed twice", keys[i]);
+    FRMAP_REQUIRE(conv_plan_from_key(keys[i], &q), "conv_plan_selfcheck: key %s selects no plan", keys[i]);
+    FRMAP_REQUIRE(conv_plan_key_index(q) == i, "conv_plan_selfcheck: the plan of key %s has key '%s'", keys[i], conv_plan_key(q));
+    for (int dtype : {FRMAP_BF16, FRMAP_F16}) {
+      const void* kern = q.kernel >= CK_PP ? frmap_conv_pp_kernel(q, dtype) : (const void*)conv_kernel(q, dtype);
+      FRMAP_REQUIRE(kern, "conv_plan_selfcheck: no kernel for key %s, dtype %d", keys[i], dtype);
+      FRMAP_REQUIRE((q.kernel >= CK_PP ? (const void*)conv_kernel(q, dtype) : frmap_conv_pp_kernel(q, dtype)) == nullptr,
+                    "conv_plan_selfcheck: both launch tables answer key %s", keys[i]);
+      FRMAP_REQUIRE(seen.insert(kern).second, "conv_plan_selfcheck: key %s, dtype %d shares its kernel with another key", keys[i], dtype);
+    }
+  }
+  FRMAP_REQUIRE(N_CONV_KERNELS + frmap_conv_pp_kernel_rows() == count, "conv_plan_selfcheck: %d + %d table rows for %d keys",
+                N_CONV_KERNELS, frmap_conv_pp_kernel_rows(), count);
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

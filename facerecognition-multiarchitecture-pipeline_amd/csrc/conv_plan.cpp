@@ -566,6 +566,151 @@ ConvPlan conv_fill(const ConvLayer& L, const ConvPlan& q0, const ConvTuning& t, 
   return q0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the key (conv_plan.h): one name per instantiation, beside the plan fields that select it
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum KeyFlag { F_NONE = 0, F_DS, F_IM, F_PL, F_RI, F_POOL, F_EARLY, F_POOL_EARLY };
+struct KeyRow {
+  const char* key;
+  int kernel, a, b, c, d;   // template arguments in the kernel's order (below); unused ones 0
+  int flag;                 // KeyFlag
+};
+// CK_IGEMM: BM, KS, SWZ | CK_1X1: CKS | CK_WAVE: NCH | CK_PP: MI, WM, NHP, KS | CK_PP_S2: MI, WM, NHP | CK_PP_1X1: MI, WM, KS
+const KeyRow KEY_ROWS[] = {
+    {"conv_igemm_kernel<256,1,1>", CK_IGEMM, 256, 1, 1, 0, F_NONE},
+    {"conv_igemm_kernel<256,3,1>", CK_IGEMM, 256, 3, 1, 0, F_NONE},
+    {"conv_igemm_kernel<256,3,2>", CK_IGEMM, 256, 3, 2, 0, F_NONE},
+    {"conv_igemm_kernel<128,3,1>", CK_IGEMM, 128, 3, 1, 0, F_NONE},
+    {"conv_igemm_kernel<128,3,2>", CK_IGEMM, 128, 3, 2, 0, F_NONE},
+    {"conv_igemm_kernel<256,3,1,POOL>", CK_IGEMM, 256, 3, 1, 0, F_POOL},
+    {"conv_igemm_kernel<128,3,1,POOL>", CK_IGEMM, 128, 3, 1, 0, F_POOL},
+    {"conv1x1_kernel<1>", CK_1X1, 1, 0, 0, 0, F_NONE},
+    {"conv1x1_kernel<2>", CK_1X1, 2, 0, 0, 0, F_NONE},
+    {"conv1x1_kernel<4>", CK_1X1, 4, 0, 0, 0, F_NONE},
+    {"conv3x3_c64_wave_kernel<2>", CK_WAVE, 2, 0, 0, 0, F_NONE},
+    {"conv3x3_c64_wave_kernel<2,EARLY>", CK_WAVE, 2, 0, 0, 0, F_EARLY},
+    {"conv3x3_c64_wave_kernel<2,POOL>", CK_WAVE, 2, 0, 0, 0, F_POOL},
+    {"conv3x3_c64_wave_kernel<2,POOL,EARLY>", CK_WAVE, 2, 0, 0, 0, F_POOL_EARLY},
+    {"conv3x3_c64_wave_kernel<1,POOL>", CK_WAVE, 1, 0, 0, 0, F_POOL},
+    {"conv3x3_c64_wave_kernel<1,POOL,EARLY>", CK_WAVE, 1, 0, 0, 0, F_POOL_EARLY},
+    {"conv3x3_fast_kernel<>", CK_FAST, 0, 0, 0, 0, F_NONE},
+    {"conv3x3_fast_kernel<DS>", CK_FAST, 0, 0, 0, 0, F_DS},
+    {"conv3x3s2_split_kernel<>", CK_S2_SPLIT, 0, 0, 0, 0, F_NONE},
+    {"conv3x3s2_fast_kernel<>", CK_S2_FAST, 0, 0, 0, 0, F_NONE},
+    // 224 px x 256 ch
+    {"conv3x3_pp_kernel<7,2,3,1>", CK_PP, 7, 2, 3, 1, F_NONE},
+    {"conv3x3_pp_kernel<7,2,3,1,DS>", CK_PP, 7, 2, 3, 1, F_DS},
+    {"conv3x3_pp_kernel<7,2,3,1,IM>", CK_PP, 7, 2, 3, 1, F_IM},
+    {"conv3x3_pp_kernel<7,2,3,1,PL>", CK_PP, 7, 2, 3, 1, F_PL},
+    {"conv3x3_pp_kernel<7,2,3,1,RI>", CK_PP, 7, 2, 3, 1, F_RI},
+    {"conv3x3_pp_kernel<7,2,5,1>", CK_PP, 7, 2, 5, 1, F_NONE},
+    {"conv3x3_pp_kernel<7,2,5,1,DS>", CK_PP, 7, 2, 5, 1, F_DS},
+    {"conv3x3_pp_kernel<7,2,5,1,IM>", CK_PP, 7, 2, 5, 1, F_IM},
+    {"conv3x3_pp_kernel<7,2,5,1,PL>", CK_PP, 7, 2, 5, 1, F_PL},
+    {"conv3x3_pp_kernel<7,2,5,1,RI>", CK_PP, 7, 2, 5, 1, F_RI},
+    // 448 px x 128 ch (the shortcut form needs the buffers of NHP = 5: pp_nhp_class)
+    {"conv3x3_pp_kernel<7,4,3,1>", CK_PP, 7, 4, 3, 1, F_NONE},
+    {"conv3x3_pp_kernel<7,4,3,1,IM>", CK_PP, 7, 4, 3, 1, F_IM},
+    {"conv3x3_pp_kernel<7,4,3,1,PL>", CK_PP, 7, 4, 3, 1, F_PL},
+    {"conv3x3_pp_kernel<7,4,3,1,RI>", CK_PP, 7, 4, 3, 1, F_RI},
+    {"conv3x3_pp_kernel<7,4,5,1>", CK_PP, 7, 4, 5, 1, F_NONE},
+    {"conv3x3_pp_kernel<7,4,5,1,DS>", CK_PP, 7, 4, 5, 1, F_DS},
+    {"conv3x3_pp_kernel<7,4,5,1,IM>", CK_PP, 7, 4, 5, 1, F_IM},
+    {"conv3x3_pp_kernel<7,4,5,1,PL>", CK_PP, 7, 4, 5, 1, F_PL},
+    {"conv3x3_pp_kernel<7,4,5,1,RI>", CK_PP, 7, 4, 5, 1, F_RI},
+    // split-K 224 px x 128 ch: plain layers only, no RI form with 6 halo pieces (plan_pp_3x3)
+    {"conv3x3_pp_kernel<7,2,4,2>", CK_PP, 7, 2, 4, 2, F_NONE},
+    {"conv3x3_pp_kernel<7,2,4,2,IM>", CK_PP, 7, 2, 4, 2, F_IM},
+    {"conv3x3_pp_kernel<7,2,4,2,RI>", CK_PP, 7, 2, 4, 2, F_RI},
+    {"conv3x3_pp_kernel<7,2,6,2>", CK_PP, 7, 2, 6, 2, F_NONE},
+    {"conv3x3_pp_kernel<7,2,6,2,IM>", CK_PP, 7, 2, 6, 2, F_IM},
+    {"conv3x3s2_pp_kernel<7,2,1>", CK_PP_S2, 7, 2, 1, 0, F_NONE},
+    {"conv3x3s2_pp_kernel<7,2,2>", CK_PP_S2, 7, 2, 2, 0, F_NONE},
+    {"conv3x3s2_pp_kernel<7,4,1>", CK_PP_S2, 7, 4, 1, 0, F_NONE},
+    {"conv3x3s2_pp_kernel<7,4,2>", CK_PP_S2, 7, 4, 2, 0, F_NONE},
+    {"conv3x3s2_pp_kernel<7,4,4>", CK_PP_S2, 7, 4, 4, 0, F_NONE},
+    {"conv1x1_pp_kernel<7,2,1>", CK_PP_1X1, 7, 2, 1, 0, F_NONE},
+    {"conv1x1_pp_kernel<7,4,1>", CK_PP_1X1, 7, 4, 1, 0, F_NONE},
+    {"conv1x1_pp_kernel<7,2,2>", CK_PP_1X1, 7, 2, 2, 0, F_NONE},
+};
+constexpr int N_KEYS = (int)(sizeof(KEY_ROWS) / sizeof(KEY_ROWS[0]));
+
+// a plan in the terms of a row: {kernel, a, b, c, d, flag}; flag -1 = a combination of flags no kernel has
+KeyRow row_of(const ConvPlan& q) {
+  KeyRow r{"", q.kernel, 0, 0, 0, 0, F_NONE};
+  switch (q.kernel) {
+    case CK_IGEMM:
+      r.a = q.BM; r.b = q.KS; r.c = q.SWZ; r.flag = q.POOL ? F_POOL : F_NONE;
+      break;
+    case CK_1X1: r.a = q.CKS; break;
+    case CK_WAVE:
+      r.a = q.NCH; r.flag = q.POOL ? (q.EARLY ? F_POOL_EARLY : F_POOL) : (q.EARLY ? F_EARLY : F_NONE);
+      break;
+    case CK_FAST: r.flag = q.DS ? F_DS : F_NONE; break;
+    case CK_S2_SPLIT: case CK_S2_FAST: break;
+    case CK_PP:
+      r.a = q.MI; r.b = q.WM; r.c = q.NHP; r.d = q.KS;
+      r.flag = (int)q.DS + (int)q.IM + (int)q.PL + (int)q.RI > 1 ? -1 : (q.DS ? F_DS : (q.IM ? F_IM : (q.PL ? F_PL : (q.RI ? F_RI : F_NONE))));
+      break;
+    case CK_PP_S2: r.a = q.MI; r.b = q.WM; r.c = q.NHP; break;
+    case CK_PP_1X1: r.a = q.MI; r.b = q.WM; r.c = q.KS; break;
+    default: r.kernel = CK_NONE; break;
+  }
+  return r;
+}
+}  // namespace
+
+int conv_plan_key_index(const ConvPlan& q) {
+  const KeyRow r = row_of(q);
+  if (r.kernel == CK_NONE) return -1;
+  for (int i = 0; i < N_KEYS; ++i) {
+    const KeyRow& k = KEY_ROWS[i];
+    if (k.kernel == r.kernel && k.a == r.a && k.b == r.b && k.c == r.c && k.d == r.d && k.flag == r.flag) return i;
+  }
+  return -1;
+}
+const char* conv_plan_key(const ConvPlan& q) {
+  const int i = conv_plan_key_index(q);
+  return i < 0 ? "" : KEY_ROWS[i].key;
+}
+int conv_plan_key(const ConvPlan& q, char* buf, int n) {
+  const char* key = conv_plan_key(q);
+  if (buf && n > 0) snprintf(buf, (size_t)n, "%s", key);
+  return (int)strlen(key);
+}
+const char* const* conv_plan_keys(int* count) {
+  static const std::array<const char*, N_KEYS> keys = [] {
+    std::array<const char*, N_KEYS> v{};
+    for (int i = 0; i < N_KEYS; ++i) v[i] = KEY_ROWS[i].key;
+    return v;
+  }();
+  if (count) *count = N_KEYS;
+  return keys.data();
+}
+bool conv_plan_from_key(const char* key, ConvPlan* q) {
+  for (int i = 0; i < N_KEYS; ++i) {
+    const KeyRow& k = KEY_ROWS[i];
+    if (strcmp(k.key, key)) continue;
+    ConvPlan p{};
+    p.kernel = k.kernel;
+    switch (k.kernel) {
+      case CK_IGEMM: p.BM = k.a; p.KS = k.b; p.SWZ = k.c; break;
+      case CK_1X1: p.CKS = k.a; break;
+      case CK_WAVE: p.NCH = k.a; break;
+      case CK_PP: p.MI = k.a; p.WM = k.b; p.NHP = k.c; p.KS = k.d; break;
+      case CK_PP_S2: p.MI = k.a; p.WM = k.b; p.NHP = k.c; break;
+      case CK_PP_1X1: p.MI = k.a; p.WM = k.b; p.KS = k.c; break;
+    }
+    p.DS = k.flag == F_DS; p.IM = k.flag == F_IM; p.PL = k.flag == F_PL; p.RI = k.flag == F_RI;
+    p.POOL = k.flag == F_POOL || k.flag == F_POOL_EARLY;
+    p.EARLY = k.flag == F_EARLY || k.flag == F_POOL_EARLY;
+    *q = p;
+    return true;
+  }
+  return false;
+}
+
 // FRMAP_DS_UNFUSE_SMALL=1 (A/B switch) answers 0 where the second-generation kernel would take the plain 3x3 layer and the
 // maps are small (14x14 / 7x7), so the caller runs the shortcut as its own 1x1 launch and feeds it as the residual.
 int conv_ds_supported(const ConvLayer& L, const ConvTuning& t, bool inv) {

@@ -131,6 +131,19 @@ ConvPlan conv_plan(const ConvLayer& L, const ConvTuning& t, int cus, bool inv);
 ConvPlan conv_fill(const ConvLayer& L, const ConvPlan& q, const ConvTuning& t, bool inv);
 inline ConvPlan conv_plan_launch(const ConvLayer& L, const ConvTuning& t, int cus, bool inv) { return conv_fill(L, conv_plan(L, t, cus, inv), t, inv); }
 
+// THE KEY.  Every instantiation the launchers can dispatch has one canonical name, without the data type: the kernel and the
+// template arguments the plan decides, flags by name where they are set - "conv_igemm_kernel<128,3,2>",
+// "conv3x3_pp_kernel<7,2,5,1,DS>" (MI, WM, NHP, KS, then one of DS / IM / PL / RI), "conv3x3_c64_wave_kernel<1,POOL,EARLY>",
+// "conv3x3s2_split_kernel<>".  The list of the keys is the table KEY_ROWS of conv_plan.cpp: a key beside the plan fields that
+// select it.  The launchers' tables (conv_igemm.hip: CONV_KERNELS, conv_pp.hip: PP_KERNELS) hold the same keys beside the
+// bf16 and fp16 function pointers and dispatch through them, so a name and a pointer cannot drift apart unseen:
+// frmap_conv_plan_selfcheck walks the list.  (The match GEMM's modes are not conv layers and have no key.)
+int conv_plan_key_index(const ConvPlan& q);                 // index into conv_plan_keys(), -1 = not taken / no such instantiation
+const char* conv_plan_key(const ConvPlan& q);               // the key, "" = not taken / no such instantiation
+int conv_plan_key(const ConvPlan& q, char* buf, int n);     // the same copied into buf (always terminated); returns its length
+const char* const* conv_plan_keys(int* count);              // every key that exists
+bool conv_plan_from_key(const char* key, ConvPlan* q);      // the plan fields that select `key` (nothing else set); false = no such key
+
 // 1 = frmap_conv_igemm_ds takes the layer fused (and fusing is not switched off)
 int conv_ds_supported(const ConvLayer& L, const ConvTuning& t, bool inv);
 

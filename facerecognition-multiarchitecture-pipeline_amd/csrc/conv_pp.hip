@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include <utility>
+#include <vector>
 
 struct PPParams {
   const void* in;
@@ -893,48 +894,53 @@ static PPParams pp_params(const ConvPlan& q, const void* in, const void* w, int 
   return p;
 }
 
-template <typename TT, int WM, int NHP, int KS>
-static const void* pp_kernel_3x3(const ConvPlan& q) {
-  if constexpr (KS == 1 && !(WM == 4 && NHP == 3)) {
-    if (q.DS) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, true, false>;
-  }
-  if constexpr (KS == 1) {
-    if (q.PL) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false, true>;
-  }
-  if constexpr (NHP != 6) {
-    if (q.RI) return (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false, false, true>;
-  }
-  return q.IM ? (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, true> : (const void*)conv3x3_pp_kernel<TT, 7, WM, NHP, KS, false, false>;
-}
-// the instantiation of a plan (conv layers; the match GEMM's modes have their own argument types: pp_match_launch)
-template <typename TT>
-static const void* pp_kernel(const ConvPlan& q) {
-  const int key = q.WM * 100 + q.NHP * 10 + q.KS;
-  switch (q.kernel) {
-    case CK_PP:
-      switch (key) {
-        case 231: return pp_kernel_3x3<TT, 2, 3, 1>(q);
-        case 251: return pp_kernel_3x3<TT, 2, 5, 1>(q);
-        case 431: return pp_kernel_3x3<TT, 4, 3, 1>(q);
-        case 451: return pp_kernel_3x3<TT, 4, 5, 1>(q);
-        case 242: return pp_kernel_3x3<TT, 2, 4, 2>(q);
-        case 262: return pp_kernel_3x3<TT, 2, 6, 2>(q);
-      }
-      return nullptr;
-    case CK_PP_S2:
-      switch (key) {
-        case 211: return (const void*)conv3x3s2_pp_kernel<TT, 7, 2, 1>;
-        case 221: return (const void*)conv3x3s2_pp_kernel<TT, 7, 2, 2>;
-        case 411: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 1>;
-        case 421: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 2>;
-        case 441: return (const void*)conv3x3s2_pp_kernel<TT, 7, 4, 4>;
-      }
-      return nullptr;
-    case CK_PP_1X1:
-      if (q.KS == 2) return (const void*)conv1x1_pp_kernel<TT, 7, 2, 2>;
-      return q.WM == 4 ? (const void*)conv1x1_pp_kernel<TT, 7, 4, 1> : (const void*)conv1x1_pp_kernel<TT, 7, 2, 1>;
-  }
-  return nullptr;
+// The instantiations of the conv layers: the key of conv_plan.h beside its two function pointers (the match GEMM's modes have
+// their own argument types and no key: pp_match_launch).  frmap_conv_pp_kernel looks a plan's key up here.
+// conv3x3_pp_kernel<TT, MI, WM, NHP, KS, DS, IM, PL, RI>
+struct PPKernelRow { const char* key; const void* bf16; const void* f16; };
+#define PP_ROW(key, kern, ...) {key, (const void*)kern<BF16, __VA_ARGS__>, (const void*)kern<F16, __VA_ARGS__>}
+#define PP_3X3(layout, ...) PP_ROW("conv3x3_pp_kernel<" layout ">", conv3x3_pp_kernel, __VA_ARGS__, false, false, false, false), \
+                            PP_ROW("conv3x3_pp_kernel<" layout ",IM>", conv3x3_pp_kernel, __VA_ARGS__, false, true, false, false)
+#define PP_3X3_DS(layout, ...) PP_ROW("conv3x3_pp_kernel<" layout ",DS>", conv3x3_pp_kernel, __VA_ARGS__, true, false, false, false)
+#define PP_3X3_PL(layout, ...) PP_ROW("conv3x3_pp_kernel<" layout ",PL>", conv3x3_pp_kernel, __VA_ARGS__, false, false, true, false)
+#define PP_3X3_RI(layout, ...) PP_ROW("conv3x3_pp_kernel<" layout ",RI>", conv3x3_pp_kernel, __VA_ARGS__, false, false, false, true)
+static const PPKernelRow PP_KERNELS[] = {
+    PP_3X3("7,2,3,1", 7, 2, 3, 1), PP_3X3_DS("7,2,3,1", 7, 2, 3, 1), PP_3X3_PL("7,2,3,1", 7, 2, 3, 1), PP_3X3_RI("7,2,3,1", 7, 2, 3, 1),
+    PP_3X3("7,2,5,1", 7, 2, 5, 1), PP_3X3_DS("7,2,5,1", 7, 2, 5, 1), PP_3X3_PL("7,2,5,1", 7, 2, 5, 1), PP_3X3_RI("7,2,5,1", 7, 2, 5, 1),
+    PP_3X3("7,4,3,1", 7, 4, 3, 1), PP_3X3_PL("7,4,3,1", 7, 4, 3, 1), PP_3X3_RI("7,4,3,1", 7, 4, 3, 1),   // (shortcut: NHP = 5 only)
+    PP_3X3("7,4,5,1", 7, 4, 5, 1), PP_3X3_DS("7,4,5,1", 7, 4, 5, 1), PP_3X3_PL("7,4,5,1", 7, 4, 5, 1), PP_3X3_RI("7,4,5,1", 7, 4, 5, 1),
+    PP_3X3("7,2,4,2", 7, 2, 4, 2), PP_3X3_RI("7,2,4,2", 7, 2, 4, 2),   // split-K: plain layers only
+    PP_3X3("7,2,6,2", 7, 2, 6, 2),                                     // (an RI form would spill: conv_plan.cpp)
+    PP_ROW("conv3x3s2_pp_kernel<7,2,1>", conv3x3s2_pp_kernel, 7, 2, 1),
+    PP_ROW("conv3x3s2_pp_kernel<7,2,2>", conv3x3s2_pp_kernel, 7, 2, 2),
+    PP_ROW("conv3x3s2_pp_kernel<7,4,1>", conv3x3s2_pp_kernel, 7, 4, 1),
+    PP_ROW("conv3x3s2_pp_kernel<7,4,2>", conv3x3s2_pp_kernel, 7, 4, 2),
+    PP_ROW("conv3x3s2_pp_kernel<7,4,4>", conv3x3s2_pp_kernel, 7, 4, 4),
+    PP_ROW("conv1x1_pp_kernel<7,2,1>", conv1x1_pp_kernel, 7, 2, 1),
+    PP_ROW("conv1x1_pp_kernel<7,4,1>", conv1x1_pp_kernel, 7, 4, 1),
+    PP_ROW("conv1x1_pp_kernel<7,2,2>", conv1x1_pp_kernel, 7, 2, 2),
+};
+#undef PP_3X3_RI
+#undef PP_3X3_PL
+#undef PP_3X3_DS
+#undef PP_3X3
+#undef PP_ROW
+int frmap_conv_pp_kernel_rows() { return (int)(sizeof(PP_KERNELS) / sizeof(PP_KERNELS[0])); }
+
+// the instantiation of a plan (resolved once per key: by_index[i] is the row of conv_plan_keys()[i], null = not of this file)
+const void* frmap_conv_pp_kernel(const ConvPlan& q, int dtype) {
+  static const std::vector<const PPKernelRow*> by_index = [] {
+    int n = 0;
+    const char* const* keys = conv_plan_keys(&n);
+    std::vector<const PPKernelRow*> v((size_t)n, nullptr);
+    for (int i = 0; i < n; ++i)
+      for (const PPKernelRow& r : PP_KERNELS)
+        if (!strcmp(r.key, keys[i])) { v[(size_t)i] = &r; break; }
+    return v;
+  }();
+  const int i = conv_plan_key_index(q);
+  const PPKernelRow* r = i < 0 ? nullptr : by_index[(size_t)i];
+  return !r ? nullptr : (dtype == FRMAP_BF16 ? r->bf16 : r->f16);
 }
 
 template <typename P>
@@ -960,7 +966,7 @@ int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, 
     p.dsc = L.ds_Cin / 32;
   }
   if (q.PL) { p.Wo2 = L.Wi / 2; p.dWo2 = frmap_div_make((uint32_t)p.Wo2); }
-  return pp_launch(dtype == FRMAP_BF16 ? pp_kernel<BF16>(q) : pp_kernel<F16>(q), q, q.lds_bytes, p, st);
+  return pp_launch(frmap_conv_pp_kernel(q, dtype), q, q.lds_bytes, p, st);
 }
 
 // ------------------------------------------------------------------------------------------------

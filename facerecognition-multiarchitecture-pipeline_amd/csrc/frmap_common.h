@@ -287,6 +287,9 @@ ConvPlan frmap_conv_plan(const ConvLayer& L);
 // launches a layer the planner gave to the second generation (conv_pp.hip: CK_PP, CK_PP_S2, CK_PP_1X1); 0 or an error
 int frmap_conv_pp_launch(const ConvLayer& L, const ConvPlan& q, const void* in, const void* w_packed, const float* shift,
                          const void* residual, void* out, const void* ds_in, const void* ds_w, int relu, int dtype, hipStream_t st);
+// the second generation's launch table (conv_pp.hip: PP_KERNELS): the kernel of a plan's key (null: none), and its row count
+const void* frmap_conv_pp_kernel(const ConvPlan& q, int dtype);
+int frmap_conv_pp_kernel_rows();
 #define FRMAP_REQUIRE(cond, ...)        \
   do {                                  \
     if (!(cond)) {                      \

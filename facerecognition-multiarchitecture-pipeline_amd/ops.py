@@ -227,6 +227,40 @@ def conv_igemm(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: in
     return out
 
 
+FUSE_NONE, FUSE_RESIDUAL, FUSE_SHORTCUT, FUSE_POOL2 = 0, 1, 2, 3
+
+
+def conv_plan_key(B: int, H: int, W: int, Cin: int, Cout: int, k: int = 3, stride: int = 1, fuse: int = FUSE_NONE,
+                  ds: Optional[tuple] = None) -> str:
+    """The kernel instantiation `conv_igemm` (fuse 0 / 1: without / with a residual), `conv_igemm_ds` (fuse 2, ``ds`` = (dsH, dsW,
+    dsCin, ds_stride)) or `conv_igemm_pool2` (fuse 3) launches for the layer under the tuning and hooks now in force, by its
+    canonical name without the data type (`frmap_conv_plan_key`), e.g. ``"conv3x3_pp_kernel<7,2,5,1,DS>"``; ``""`` where the
+    launcher would refuse the layer (the reason is `frmap_last_error`).  Nothing is launched; no GPU is needed."""
+    import ctypes as C
+    buf = C.create_string_buffer(96)
+    dsH, dsW, dsC, sd = ds if ds is not None else (0, 0, 0, 0)
+    n = _lib.load().frmap_conv_plan_key(B, H, W, Cin, Cout, k, stride, fuse, dsH, dsW, dsC, sd, buf, len(buf))
+    if n < 0:
+        _lib.check(n, "conv_plan_key")
+    return buf.value.decode()
+
+
+def conv_plan_keys() -> list:
+    """Every key `conv_plan_key` can answer: one per kernel instantiation the conv launchers can dispatch."""
+    import ctypes as C
+    lib, buf = _lib.load(), C.create_string_buffer(96)
+    out = []
+    for i in range(lib.frmap_conv_plan_keys(-1, buf, len(buf))):
+        lib.frmap_conv_plan_keys(i, buf, len(buf))
+        out.append(buf.value.decode())
+    return out
+
+
+def conv_plan_selfcheck() -> None:
+    """Raises unless the launch tables hold a kernel of its own for every (key, data type) (`frmap_conv_plan_selfcheck`)."""
+    _lib.check(_lib.load().frmap_conv_plan_selfcheck(), "conv_plan_selfcheck")
+
+
 _pool2_cache: dict = {}
 
 

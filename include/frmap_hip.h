@@ -404,6 +404,23 @@ int frmap_conv3x3_pp_ds_layout(int B, int Hi, int Wi, int Cin, int Cout, int ds_
  * tile can hold; the launch fills it with whole rows as far as the halo allows (FRMAP_PP_FILL=0, or a tile size forced through
  * frmap_conv_pp_tuning: whole images, or a divisor of the image height). */
 int frmap_conv3x3_pp_tile_px(int B, int Hi, int Wi, int Cin, int Cout, int stride, int ds_Hi, int ds_Wi, int ds_Cin, int ds_stride);
+/* Which kernel instantiation runs a layer.  Every instantiation the conv launchers can dispatch has one canonical name (its
+ * key): the kernel and the template arguments its plan decides, without the data type, e.g. "conv_igemm_kernel<128,3,2>",
+ * "conv3x3_pp_kernel<7,2,5,1,DS>", "conv3x3_c64_wave_kernel<1,POOL,EARLY>".  The launchers dispatch through a table of
+ * {key, bf16 kernel, fp16 kernel}, so the key a query reports is the row a launch uses.  Read-only; nothing is launched and
+ * no GPU is needed.
+ * frmap_conv_plan_key: the key of the launch frmap_conv_igemm (fuse 0 = no residual, 1 = residual), frmap_conv_igemm_ds
+ * (fuse 2; K = 3, stride 1; ds_* as there, else ignored) or frmap_conv_igemm_pool2 (fuse 3; K = 3, stride 1) makes for the
+ * layer under the tuning, hooks, CU count and batch-invariant flag then in force; pad = K / 2.  The key is copied into buf
+ * (n bytes, always terminated) and its length returned; where no plan is taken or the launcher would refuse the layer the
+ * answer is "" (0), with the reason in frmap_last_error(); -1 for a fuse out of range.
+ * frmap_conv_plan_keys: the number of keys that exist; for 0 <= index < that, key `index` is copied into buf.
+ * frmap_conv_plan_selfcheck: 0 when every key selects a plan that has this key, the launch tables hold a kernel of its own
+ * for every (key, data type) and no row beyond the keys; else -1 with the first failure in frmap_last_error(). */
+int frmap_conv_plan_key(int B, int Hi, int Wi, int Cin, int Cout, int K, int stride, int fuse, int ds_Hi, int ds_Wi, int ds_Cin,
+                        int ds_stride, char* buf, int n);
+int frmap_conv_plan_keys(int index, char* buf, int n);
+int frmap_conv_plan_selfcheck(void);
 
 /* A 3x3 stride-1 pad-1 convolution with a ResNet projection shortcut folded in (BasicBlock.conv2 + bn2 + downsample
  * [conv1x1 stride s + bn] + add + ReLU of the first block of a stage, torchvision resnet.py via face_models.py:67):

@@ -13,7 +13,9 @@ Two instruments, neither with a tuned tolerance:
 Contents: float64 references (tap loops and explicit window maxima: independent of `F.conv2d` / `F.max_pool2d` / `F.gelu`,
 which the CPU test compares them with), operand builders (exact integers, Gaussian, post-ReLU, the fp16 pair x 2^12 / w 2^-12
 whose weights are subnormal), an fp32 emulation of the kernels' arithmetic with switches that break it on purpose, the case
-tables of the two GPU files and the code that runs a case through the C ABI.
+tables of the two GPU files and the code that runs a case through the C ABI.  Every conv-family case names the kernel
+instantiation it is about (`key`); `launch_case` asserts it before the launch and `test_conv_census_cpu.py` holds that the tables
+together reach every instantiation there is.
 """
 import math
 import zlib
@@ -146,6 +148,14 @@ def one_rounding_ratio(y, want, S, dtype, lip=1.0):
     return float(((y.double() - want).abs() / bound).max())
 
 
+def assert_sharp(want, S, dtype, what=""):
+    """The sharpness condition of `assert_one_rounding`, on the float64 reference alone (no kernel): the accumulation allowance at
+    the largest S is at most a quarter of the rounding term at the mean output.  Returns the ratio of the two."""
+    slack = C_ACC * EPS32 * float(S.max()) / (UNIT[dtype] * float(want.abs().mean()) / 4)
+    assert slack <= 1.0, (what, "case drowns the rounding term: c 2^-24 max S = %.3f x (u mean|ref| / 4)" % slack)
+    return slack
+
+
 def assert_one_rounding(y, ref, S, dtype, act=ACT_NONE, what=""):
     """`|y - act(ref)| <= u |act(ref)| + c 2^-24 S` (GELU: the second term times 1.13) on every element; `ref` is the float64
     pre-activation (for a pooled op: the pooled activation, with act = ACT_NONE).  Also asserts that the case keeps the rule
@@ -154,8 +164,7 @@ def assert_one_rounding(y, ref, S, dtype, act=ACT_NONE, what=""):
     want = act64(ref, act)
     assert tuple(y.shape) == tuple(want.shape), (what, tuple(y.shape), tuple(want.shape))
     u = UNIT[dtype]
-    slack = C_ACC * EPS32 * float(S.max()) / (u * float(want.abs().mean()) / 4)
-    assert slack <= 1.0, (what, "case drowns the rounding term: c 2^-24 max S = %.3f x (u mean|ref| / 4)" % slack)
+    assert_sharp(want, S, dtype, what)
     ratio = one_rounding_ratio(y, want, S, dtype, GELU_LIP if act == ACT_GELU else 1.0)
     if not ratio <= 1.0:
         err = (y.double() - want).abs() / (u * want.abs() + (GELU_LIP if act == ACT_GELU else 1.0) * C_ACC * EPS32 * S)
@@ -348,12 +357,15 @@ def emulate_conv(o, dtype, stride=1, pad=None, act=ACT_NONE, *, chunk_round=Fals
 # ------------------------------------------------------------------------------------------------------------------------------
 # case tables of the GPU files: the smallest entries of the tables in `test_kernels_gpu.py` for every kernel variant they force
 # ------------------------------------------------------------------------------------------------------------------------------
-Case = namedtuple("Case", "name file op B H W Cin Cout k stride res act tune ri ds query")
+# key: the kernel instantiation the case is about (`ops.conv_plan_key`, asserted just before the launch; None: no conv plan - the
+# Cin = 3 and stem kernels).  im / pitch / wstart: frmap_conv_pp_im / frmap_conv_pp_pitch / frmap_conv_wave_start (None: not set).
+Case = namedtuple("Case", "name file op B H W Cin Cout k stride res act tune ri ds query key im pitch wstart", defaults=(None,) * 4)
 PP_OFF = (0, -1, -1)       # frmap_conv_pp_tuning arguments: first-generation kernels only
 
 
-def _c(name, file, op, B, H, W, Cin, Cout, k=3, stride=1, res=False, act=ACT_RELU, tune=None, ri=None, ds=None, query=None):
-    return Case(name, file, op, B, H, W, Cin, Cout, k, stride, res, act, tune, ri, ds, query)
+def _c(name, file, op, B, H, W, Cin, Cout, k=3, stride=1, res=False, act=ACT_RELU, tune=None, ri=None, ds=None, query=None,
+       key=None, im=None, pitch=None, wstart=None):
+    return Case(name, file, op, B, H, W, Cin, Cout, k, stride, res, act, tune, ri, ds, query, key, im, pitch, wstart)
 
 
 IG, PP, SC, ST, S2D = "conv_igemm.hip", "conv_pp.hip", "conv_small_cin.hip", "stem_pool.hip", "stem_s2d.hip"
@@ -364,53 +376,55 @@ CONV_CASES = [
     # ---- conv_igemm.hip (frmap_conv_pp_tuning(0, -1, -1)) ----
     # (by the dispatcher's arithmetic the 10x6 and 7x7 maps, listed as "generic" in test_kernels_gpu.py, fit the register-prefetch
     #  kernel's 10 halo pieces per thread; the generic kernel takes halos past that: the 112-pixel-wide map)
-    _c("wave-1patch", IG, "conv", 1, 8, 8, 64, 64, act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("wave-2tiles", IG, "conv", 3, 16, 24, 64, 128, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("regprefetch", IG, "conv", 2, 20, 56, 64, 64, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("g1-odd-10x6", IG, "conv", 2, 10, 6, 32, 64, act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("g1-c512-7x7", IG, "conv", 9, 7, 7, 512, 512, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("generic-112x112", IG, "conv", 1, 112, 112, 32, 64, tune=PP_OFF, query=("conv3x3_pp", (0,))),   # halo past the register-prefetch limit
-    _c("s2-split", IG, "conv", 4, 8, 6, 32, 128, stride=2, tune=PP_OFF, query=("conv3x3s2_pp", (0,))),
-    _c("s2-split-c256", IG, "conv", 2, 14, 14, 256, 512, stride=2, res=True, tune=PP_OFF, query=("conv3x3s2_pp", (0,))),
-    _c("s2-oddH", IG, "conv", 3, 7, 10, 64, 128, stride=2, res=True, tune=PP_OFF, query=("conv3x3s2_pp", (0,))),
-    _c("1x1-gather-c64", IG, "conv", 2, 56, 56, 64, 128, k=1, stride=2, act=ACT_NONE, tune=PP_OFF, query=("conv1x1_pp", (0,))),
-    _c("1x1-gather-c128", IG, "conv", 2, 28, 28, 128, 256, k=1, stride=2, act=ACT_NONE, tune=PP_OFF, query=("conv1x1_pp", (0,))),
-    _c("1x1-stage1", IG, "conv", 4, 13, 9, 160, 640, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,))),
+    _c("wave-1patch", IG, "conv", 1, 8, 8, 64, 64, act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_c64_wave_kernel<2,EARLY>"),
+    _c("wave-2tiles", IG, "conv", 3, 16, 24, 64, 128, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_c64_wave_kernel<2,EARLY>"),
+    _c("regprefetch", IG, "conv", 2, 20, 56, 64, 64, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_fast_kernel<>"),
+    _c("g1-odd-10x6", IG, "conv", 2, 10, 6, 32, 64, act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_fast_kernel<>"),
+    _c("g1-c512-7x7", IG, "conv", 9, 7, 7, 512, 512, res=True, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_fast_kernel<>"),
+    _c("generic-112x112", IG, "conv", 1, 112, 112, 32, 64, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv_igemm_kernel<256,3,1>"),   # halo past the register-prefetch limit
+    _c("s2-split", IG, "conv", 4, 8, 6, 32, 128, stride=2, tune=PP_OFF, query=("conv3x3s2_pp", (0,)), key="conv3x3s2_split_kernel<>"),
+    _c("s2-split-c256", IG, "conv", 2, 14, 14, 256, 512, stride=2, res=True, tune=PP_OFF, query=("conv3x3s2_pp", (0,)), key="conv3x3s2_fast_kernel<>"),
+    _c("s2-oddH", IG, "conv", 3, 7, 10, 64, 128, stride=2, res=True, tune=PP_OFF, query=("conv3x3s2_pp", (0,)), key="conv_igemm_kernel<256,3,2>"),
+    _c("1x1-gather-c64", IG, "conv", 2, 56, 56, 64, 128, k=1, stride=2, act=ACT_NONE, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv_igemm_kernel<256,1,1>"),
+    _c("1x1-gather-c128", IG, "conv", 2, 28, 28, 128, 256, k=1, stride=2, act=ACT_NONE, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv1x1_kernel<4>"),
+    _c("1x1-stage1", IG, "conv", 4, 13, 9, 160, 640, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv1x1_kernel<1>"),
     # one k-step.  `frmap_conv_igemm` sends Cin < 128 to the first-generation 1x1 kernel whatever the tuning hook says (the
     # `Cin >= 128` test sits in front of `frmap_conv1x1_pp`), so the single-k-step path of `conv1x1_pp_kernel` cannot be reached
     # through the C ABI: `frmap_conv1x1_pp_layout` answers 2 for this shape under `frmap_conv_pp_tuning(1, -1, 256)`, but the kernel
     # that runs is this one.  No path assertion is made that the library cannot keep.
-    _c("1x1-c32-1kstep", IG, "conv", 300, 1, 1, 32, 128, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,))),
-    _c("linear-as-1x1", IG, "conv", 37, 1, 1, 1024, 512, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,))),
-    _c("g1-shortcut-3x5", IG, "ds", 1, 3, 5, 256, 128, ds=(256, 2), tune=PP_OFF, query=("conv3x3_pp_ds", (0,))),
-    _c("g1-shortcut-10x6", IG, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp_ds", (0,))),
+    _c("1x1-c32-1kstep", IG, "conv", 300, 1, 1, 32, 128, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv_igemm_kernel<256,1,1>"),
+    _c("linear-as-1x1", IG, "conv", 37, 1, 1, 1024, 512, k=1, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv1x1_kernel<4>"),
+    _c("g1-shortcut-3x5", IG, "ds", 1, 3, 5, 256, 128, ds=(256, 2), tune=PP_OFF, query=("conv3x3_pp_ds", (0,)), key="conv3x3_fast_kernel<DS>"),
+    _c("g1-shortcut-10x6", IG, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_NONE, tune=PP_OFF, query=("conv3x3_pp_ds", (0,)), key="conv3x3_fast_kernel<DS>"),
     # ---- conv_pp.hip, 3x3 stride 1 ----
-    _c("pp-bn128-ri0", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 128), ri=0, query=("conv3x3_pp", (2,))),
-    _c("pp-bn128-ri1", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 128), ri=1, query=("conv3x3_pp", (2,))),
-    _c("pp-bn256-ri0", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 256), ri=0, query=("conv3x3_pp", (1,))),
-    _c("pp-bn256-ri1", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 256), ri=1, query=("conv3x3_pp", (1,))),
-    _c("pp-splitk-ri0", PP, "conv", 2, 20, 12, 64, 128, tune=(1, -1, 1282), ri=0, query=("conv3x3_pp", (3,))),
-    _c("pp-splitk-ri1", PP, "conv", 2, 20, 12, 64, 128, tune=(1, -1, 1282), ri=1, query=("conv3x3_pp", (3,))),
-    _c("pp-splitk-res", PP, "conv", 3, 13, 17, 128, 256, res=True, act=ACT_NONE, tune=(1, -1, 1282), ri=0, query=("conv3x3_pp", (3,))),
-    _c("pp-px37-bn256", PP, "conv", 33, 7, 7, 128, 256, res=True, tune=(1, 37, 256), ri=0, query=("conv3x3_pp", (1,))),
-    _c("pp-px37-splitk", PP, "conv", 33, 7, 7, 128, 256, res=True, tune=(1, 37, 1282), ri=1, query=("conv3x3_pp", (3,))),
-    _c("pp-1chunk", PP, "conv", 7, 5, 3, 32, 128, res=True, act=ACT_NONE, tune=(1, -1, -1), ri=0, query=("conv3x3_pp", (2,))),
+    _c("pp-bn128-ri0", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 128), ri=0, query=("conv3x3_pp", (2,)), key="conv3x3_pp_kernel<7,4,5,1>"),
+    _c("pp-bn128-ri1", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 128), ri=1, query=("conv3x3_pp", (2,)), key="conv3x3_pp_kernel<7,4,5,1,RI>"),
+    _c("pp-bn256-ri0", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 256), ri=0, query=("conv3x3_pp", (1,)), key="conv3x3_pp_kernel<7,2,3,1>"),
+    _c("pp-bn256-ri1", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=(1, -1, 256), ri=1, query=("conv3x3_pp", (1,)), key="conv3x3_pp_kernel<7,2,3,1,RI>"),
+    _c("pp-splitk-ri0", PP, "conv", 2, 20, 12, 64, 128, tune=(1, -1, 1282), ri=0, query=("conv3x3_pp", (3,)), key="conv3x3_pp_kernel<7,2,6,2>"),
+    # asks for interleaved reads and does NOT get them: with six halo pieces that form would spill (plan_pp_3x3), the planner
+    # declines and the key is pp-splitk-ri0's.  The case holds the decline; split-K with the request honoured is cx-splitk4-ri1.
+    _c("pp-splitk-ri1", PP, "conv", 2, 20, 12, 64, 128, tune=(1, -1, 1282), ri=1, query=("conv3x3_pp", (3,)), key="conv3x3_pp_kernel<7,2,6,2>"),
+    _c("pp-splitk-res", PP, "conv", 3, 13, 17, 128, 256, res=True, act=ACT_NONE, tune=(1, -1, 1282), ri=0, query=("conv3x3_pp", (3,)), key="conv3x3_pp_kernel<7,2,6,2>"),
+    _c("pp-px37-bn256", PP, "conv", 33, 7, 7, 128, 256, res=True, tune=(1, 37, 256), ri=0, query=("conv3x3_pp", (1,)), key="conv3x3_pp_kernel<7,2,3,1>"),
+    _c("pp-px37-splitk", PP, "conv", 33, 7, 7, 128, 256, res=True, tune=(1, 37, 1282), ri=1, query=("conv3x3_pp", (3,)), key="conv3x3_pp_kernel<7,2,4,2,RI>"),
+    _c("pp-1chunk", PP, "conv", 7, 5, 3, 32, 128, res=True, act=ACT_NONE, tune=(1, -1, -1), ri=0, query=("conv3x3_pp", (2,)), key="conv3x3_pp_kernel<7,4,3,1>"),
     # ---- conv_pp.hip, stride 2 / fused shortcut / 1x1 ----
-    _c("pp-s2-2x2", PP, "conv", 1, 2, 2, 64, 128, stride=2, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,))),
-    _c("pp-s2-8x6", PP, "conv", 4, 8, 6, 32, 128, stride=2, res=True, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,))),
-    _c("pp-shortcut-3x5", PP, "ds", 1, 3, 5, 256, 128, ds=(256, 2), tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2))),
-    _c("pp-shortcut-10x6", PP, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_NONE, tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2))),
-    _c("pp1x1-layout1", PP, "conv", 3, 14, 14, 256, 256, k=1, tune=(1, -1, 256), query=("conv1x1_pp", (1,))),
-    _c("pp1x1-layout2-s2", PP, "conv", 2, 28, 28, 128, 256, k=1, stride=2, tune=(1, -1, 128), query=("conv1x1_pp", (2,))),
-    _c("pp1x1-layout3", PP, "conv", 637, 1, 1, 2048, 512, k=1, res=True, act=ACT_NONE, tune=(1, -1, 1282), query=("conv1x1_pp", (3,))),
-    _c("pp1x1-5ksteps", PP, "conv", 4, 13, 9, 160, 640, k=1, tune=(1, -1, 1282), query=("conv1x1_pp", (2,))),
+    _c("pp-s2-2x2", PP, "conv", 1, 2, 2, 64, 128, stride=2, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,)), key="conv3x3s2_pp_kernel<7,4,1>"),
+    _c("pp-s2-8x6", PP, "conv", 4, 8, 6, 32, 128, stride=2, res=True, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,)), key="conv3x3s2_pp_kernel<7,4,1>"),
+    _c("pp-shortcut-3x5", PP, "ds", 1, 3, 5, 256, 128, ds=(256, 2), tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2)), key="conv3x3_pp_kernel<7,4,5,1,DS>"),
+    _c("pp-shortcut-10x6", PP, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_NONE, tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2)), key="conv3x3_pp_kernel<7,4,5,1,DS>"),
+    _c("pp1x1-layout1", PP, "conv", 3, 14, 14, 256, 256, k=1, tune=(1, -1, 256), query=("conv1x1_pp", (1,)), key="conv1x1_pp_kernel<7,2,1>"),
+    _c("pp1x1-layout2-s2", PP, "conv", 2, 28, 28, 128, 256, k=1, stride=2, tune=(1, -1, 128), query=("conv1x1_pp", (2,)), key="conv1x1_pp_kernel<7,4,1>"),
+    _c("pp1x1-layout3", PP, "conv", 637, 1, 1, 2048, 512, k=1, res=True, act=ACT_NONE, tune=(1, -1, 1282), query=("conv1x1_pp", (3,)), key="conv1x1_pp_kernel<7,2,2>"),
+    _c("pp1x1-5ksteps", PP, "conv", 4, 13, 9, 160, 640, k=1, tune=(1, -1, 1282), query=("conv1x1_pp", (2,)), key="conv1x1_pp_kernel<7,4,1>"),
     # ---- fused 2x2 max-pool (default planning) ----
-    _c("pool2-generic", IG, "pool2", 5, 6, 6, 64, 64, query=("pool2_form", (1,))),
-    _c("pool2-wave-c32", IG, "pool2", 5, 8, 24, 32, 64, query=("pool2_form", (2,))),
-    _c("pool2-wave-c64", IG, "pool2", 3, 16, 8, 64, 192, act=ACT_NONE, query=("pool2_form", (2,))),
-    _c("pool2-pp-8x8", PP, "pool2", 3, 8, 8, 128, 128, query=("pool2_form", (3,))),
-    _c("pool2-pp-4x4", PP, "pool2", 9, 4, 4, 256, 128, act=ACT_NONE, query=("pool2_form", (3,))),
-    _c("pool2-pp-2x2", PP, "pool2", 33, 2, 2, 128, 128, query=("pool2_form", (3,))),
+    _c("pool2-generic", IG, "pool2", 5, 6, 6, 64, 64, query=("pool2_form", (1,)), key="conv_igemm_kernel<256,3,1,POOL>"),
+    _c("pool2-wave-c32", IG, "pool2", 5, 8, 24, 32, 64, query=("pool2_form", (2,)), key="conv3x3_c64_wave_kernel<1,POOL,EARLY>"),
+    _c("pool2-wave-c64", IG, "pool2", 3, 16, 8, 64, 192, act=ACT_NONE, query=("pool2_form", (2,)), key="conv3x3_c64_wave_kernel<2,POOL,EARLY>"),
+    _c("pool2-pp-8x8", PP, "pool2", 3, 8, 8, 128, 128, query=("pool2_form", (3,)), key="conv3x3_pp_kernel<7,4,3,1,PL>"),
+    _c("pool2-pp-4x4", PP, "pool2", 9, 4, 4, 256, 128, act=ACT_NONE, query=("pool2_form", (3,)), key="conv3x3_pp_kernel<7,4,3,1,PL>"),
+    _c("pool2-pp-2x2", PP, "pool2", 33, 2, 2, 128, 128, query=("pool2_form", (3,)), key="conv3x3_pp_kernel<7,4,5,1,PL>"),
     # ---- Cin = 3 ----
     _c("c3-pool2-10x14", SC, "c3pool2", 3, 10, 14, 3, 32),
     _c("c3-pool2-2x2", SC, "c3pool2", 1, 2, 2, 3, 32),
@@ -426,13 +440,68 @@ CONV_CASES = [
 
 # GELU is not exact: these run in the bound family only, one per epilogue that implements the activation
 GELU_CASES = [
-    _c("gelu-wave", IG, "conv", 1, 8, 8, 64, 64, act=ACT_GELU, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("gelu-g1-3x3", IG, "conv", 2, 13, 17, 128, 128, res=True, act=ACT_GELU, tune=PP_OFF, query=("conv3x3_pp", (0,))),
-    _c("gelu-pp-3x3", PP, "conv", 2, 13, 17, 128, 128, res=True, act=ACT_GELU, tune=(1, -1, -1), query=("conv3x3_pp", (1, 2, 3))),
-    _c("gelu-pp-splitk", PP, "conv", 2, 20, 12, 64, 128, act=ACT_GELU, tune=(1, -1, 1282), query=("conv3x3_pp", (3,))),
-    _c("gelu-pp-s2", PP, "conv", 4, 8, 6, 32, 128, stride=2, act=ACT_GELU, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,))),
-    _c("gelu-pp-shortcut", PP, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_GELU, tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2))),
-    _c("gelu-pp1x1", PP, "conv", 9, 7, 7, 1024, 384, k=1, res=True, act=ACT_GELU, tune=(1, -1, -1), query=("conv1x1_pp", (1, 2, 3))),
+    _c("gelu-wave", IG, "conv", 1, 8, 8, 64, 64, act=ACT_GELU, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_c64_wave_kernel<2,EARLY>"),
+    _c("gelu-g1-3x3", IG, "conv", 2, 13, 17, 128, 128, res=True, act=ACT_GELU, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv3x3_fast_kernel<>"),
+    # (the 128-channel tile forced: left to the planner this shape takes split-K and repeats gelu-pp-splitk)
+    _c("gelu-pp-3x3", PP, "conv", 2, 13, 17, 128, 128, res=True, act=ACT_GELU, tune=(1, -1, 128), query=("conv3x3_pp", (2,)), key="conv3x3_pp_kernel<7,4,5,1>"),
+    _c("gelu-pp-splitk", PP, "conv", 2, 20, 12, 64, 128, act=ACT_GELU, tune=(1, -1, 1282), query=("conv3x3_pp", (3,)), key="conv3x3_pp_kernel<7,2,6,2>"),
+    _c("gelu-pp-s2", PP, "conv", 4, 8, 6, 32, 128, stride=2, act=ACT_GELU, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,)), key="conv3x3s2_pp_kernel<7,4,1>"),
+    _c("gelu-pp-shortcut", PP, "ds", 4, 10, 6, 64, 128, ds=(32, 2), act=ACT_GELU, tune=(1, -1, -1), query=("conv3x3_pp_ds", (1, 2)), key="conv3x3_pp_kernel<7,4,5,1,DS>"),
+    _c("gelu-pp1x1", PP, "conv", 9, 7, 7, 1024, 384, k=1, res=True, act=ACT_GELU, tune=(1, -1, -1), query=("conv1x1_pp", (1, 2, 3)), key="conv1x1_pp_kernel<7,2,2>"),
+]
+
+# ---- the census table: one sharp case for every instantiation the tables above do not reach (`test_conv_census_cpu.py` holds the
+# union of keys against `ops.conv_plan_keys()`), and the two shipped options no case above switches on: FRMAP_PP_IM (DMA issued
+# between the MFMAs) and FRMAP_PP_PITCH (conflict-free halo pitch).  Shapes: the smallest that reach the key with two tiles or a
+# partial last one where the kernel has tiles; every entry names its key, which `launch_case` asserts on the device.
+P3 = "conv3x3_pp_kernel"
+_B256, _B128, _SPLITK = (1, -1, 256), (1, -1, 128), (1, -1, 1282)
+CENSUS_CASES = [
+    # 224 px x 256 ch with more than three halo pieces: 5x5 maps, 8 images in a 200-pixel tile (8 x 7 + 3 halo rows of 7 pixels)
+    _c("cx-pp251", PP, "conv", 9, 5, 5, 128, 256, res=True, tune=_B256, ri=0, query=("conv3x3_pp", (1,)), key=P3 + "<7,2,5,1>"),
+    _c("cx-pp251-ri", PP, "conv", 9, 5, 5, 128, 256, res=True, tune=_B256, ri=1, query=("conv3x3_pp", (1,)), key=P3 + "<7,2,5,1,RI>"),
+    _c("cx-pp251-ds", PP, "ds", 9, 5, 5, 128, 256, ds=(64, 2), tune=_B256, query=("conv3x3_pp_ds", (1,)), key=P3 + "<7,2,5,1,DS>"),
+    _c("cx-pp251-pl", PP, "pool2", 20, 4, 4, 128, 256, query=("pool2_form", (3,)), key=P3 + "<7,2,5,1,PL>"),
+    _c("cx-pp231-pl", PP, "pool2", 5, 8, 8, 128, 256, act=ACT_NONE, query=("pool2_form", (3,)), key=P3 + "<7,2,3,1,PL>"),
+    # the same operands as cx-pp251 in the 448 px x 128 ch layout
+    _c("cx-pp451-5x5", PP, "conv", 9, 5, 5, 128, 256, res=True, tune=_B128, ri=0, query=("conv3x3_pp", (2,)), key=P3 + "<7,4,5,1>"),
+    _c("cx-pp431-ri", PP, "conv", 7, 5, 3, 32, 128, res=True, act=ACT_NONE, tune=(1, -1, -1), ri=1, query=("conv3x3_pp", (2,)), key=P3 + "<7,4,3,1,RI>"),
+    # split-K with four halo pieces, where interleaved reads are honoured (at six the planner declines them: pp-splitk-ri1)
+    _c("cx-splitk4-ri0", PP, "conv", 9, 14, 14, 256, 256, tune=(1, 196, 1282), ri=0, query=("conv3x3_pp", (3,)), key=P3 + "<7,2,4,2>"),
+    _c("cx-splitk4-ri1", PP, "conv", 9, 14, 14, 256, 256, tune=(1, 196, 1282), ri=1, query=("conv3x3_pp", (3,)), key=P3 + "<7,2,4,2,RI>"),
+    # stride 2
+    _c("cx-s2pp-721", PP, "conv", 4, 8, 6, 32, 256, stride=2, res=True, tune=(1, -1, -1), query=("conv3x3s2_pp", (1,)), key="conv3x3s2_pp_kernel<7,2,1>"),
+    _c("cx-s2pp-742", PP, "conv", 3, 16, 16, 32, 128, stride=2, tune=(1, -1, -1), query=("conv3x3s2_pp", (2,)), key="conv3x3s2_pp_kernel<7,4,2>"),
+    # first generation: the 128-pixel generic tiles (rows too wide for 256 pixels' halo) and the two-chunk 1x1 stage
+    _c("cx-igemm128", IG, "conv", 1, 1, 220, 32, 64, tune=PP_OFF, query=("conv3x3_pp", (0,)), key="conv_igemm_kernel<128,3,1>"),
+    _c("cx-igemm128-s2", IG, "conv", 1, 7, 300, 32, 64, stride=2, act=ACT_NONE, tune=PP_OFF, query=("conv3x3s2_pp", (0,)), key="conv_igemm_kernel<128,3,2>"),
+    _c("cx-igemm128-pool", IG, "pool2", 1, 4, 120, 96, 64, query=("pool2_form", (1,)), key="conv_igemm_kernel<128,3,1,POOL>"),
+    _c("cx-1x1-cks2", IG, "conv", 4, 13, 9, 192, 128, k=1, res=True, tune=PP_OFF, query=("conv1x1_pp", (0,)), key="conv1x1_kernel<2>"),
+    # the wave kernel's start-up form 0 (nothing resident early) on the exact family, all three instantiations
+    _c("cx-wave-late", IG, "conv", 3, 16, 24, 64, 128, res=True, tune=PP_OFF, wstart=0, query=("conv3x3_pp", (0,)), key="conv3x3_c64_wave_kernel<2>"),
+    _c("cx-wave-late-pool-c32", IG, "pool2", 5, 8, 24, 32, 64, wstart=0, query=("pool2_form", (2,)), key="conv3x3_c64_wave_kernel<1,POOL>"),
+    _c("cx-wave-late-pool-c64", IG, "pool2", 3, 16, 8, 64, 192, act=ACT_NONE, wstart=0, query=("pool2_form", (2,)), key="conv3x3_c64_wave_kernel<2,POOL>"),
+    # FRMAP_PP_IM = 1 on every (WM, NHP, KS) layout: the shapes of pp-bn256-ri0, cx-pp251, pp-1chunk, pp-bn128-ri0, cx-splitk4-ri0, pp-splitk-ri0
+    _c("cx-im-231", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=_B256, ri=0, im=1, query=("conv3x3_pp", (1,)), key=P3 + "<7,2,3,1,IM>"),
+    _c("cx-im-251", PP, "conv", 9, 5, 5, 128, 256, res=True, tune=_B256, ri=0, im=1, query=("conv3x3_pp", (1,)), key=P3 + "<7,2,5,1,IM>"),
+    _c("cx-im-431", PP, "conv", 7, 5, 3, 32, 128, res=True, act=ACT_NONE, tune=(1, -1, -1), ri=0, im=1, query=("conv3x3_pp", (2,)), key=P3 + "<7,4,3,1,IM>"),
+    _c("cx-im-451", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=_B128, ri=0, im=1, query=("conv3x3_pp", (2,)), key=P3 + "<7,4,5,1,IM>"),
+    _c("cx-im-242", PP, "conv", 9, 14, 14, 256, 256, tune=(1, 196, 1282), ri=0, im=1, query=("conv3x3_pp", (3,)), key=P3 + "<7,2,4,2,IM>"),
+    _c("cx-im-262", PP, "conv", 2, 20, 12, 64, 128, tune=_SPLITK, ri=0, im=1, query=("conv3x3_pp", (3,)), key=P3 + "<7,2,6,2,IM>"),
+    # FRMAP_PP_PITCH = 1: Wp grows from Wi + 2 to the next value that is Wi (mod 8), and the halo with it.  NHP class after / before:
+    # All three on 14x14 maps in 196-pixel tiles, Wp 16 -> 22, 16 halo rows: 16 KB -> 22 KB.  NHP class before / after:
+    #   cx-pitch-plain   224 px x 256 ch, 8 KB pieces: 3 / 3        (the twin without it: pp-bn256-ri0)
+    #   cx-pitch-ds      the same layout with the fused shortcut: 3 / 3   (cx-pp231-ds)
+    #   cx-pitch-splitk  split-K, 4 KB pieces: 4 / 6                (cx-splitk4-ri0; on 20x12 maps, 6 before, a seventh piece does not
+    #                    exist and the planner leaves split-K)
+    _c("cx-pitch-plain", PP, "conv", 5, 14, 14, 256, 256, res=True, tune=_B256, ri=0, pitch=1, query=("conv3x3_pp", (1,)), key=P3 + "<7,2,3,1>"),
+    _c("cx-pitch-ds", PP, "ds", 3, 14, 14, 128, 256, ds=(64, 2), tune=_B256, pitch=1, query=("conv3x3_pp_ds", (1,)), key=P3 + "<7,2,3,1,DS>"),
+    _c("cx-pitch-splitk", PP, "conv", 9, 14, 14, 256, 256, tune=(1, 196, 1282), ri=0, pitch=1, query=("conv3x3_pp", (3,)), key=P3 + "<7,2,6,2>"),
+    # reached before by the Gaussian operands of test_conv_fill_gpu.py only: the shortcut form with three halo pieces and the stride-2
+    # layouts of 14x14 and 28x28 output maps
+    _c("cx-pp231-ds", PP, "ds", 3, 14, 14, 128, 256, ds=(64, 2), tune=_B256, query=("conv3x3_pp_ds", (1,)), key=P3 + "<7,2,3,1,DS>"),
+    _c("cx-s2pp-722", PP, "conv", 3, 28, 28, 64, 256, stride=2, res=True, tune=_B256, query=("conv3x3s2_pp", (1,)), key="conv3x3s2_pp_kernel<7,2,2>"),
+    _c("cx-s2pp-744", PP, "conv", 2, 56, 56, 32, 128, stride=2, act=ACT_NONE, tune=_B128, query=("conv3x3s2_pp", (2,)), key="conv3x3s2_pp_kernel<7,4,4>"),
 ]
 
 # linear_mfma: M, K, N, act, residual, split-K expected.  Split-K is taken when min(384 / tiles, (K / 32) / 4) >= 2
@@ -448,16 +517,26 @@ LINEAR_FILE = IG
 
 # pairs of cases that run the same operands on two generations, or with and without interleaved fragment reads: the exact family
 # requires their outputs to agree bit for bit
+# (pp-splitk-ri0 / -ri1: the planner declines interleaved reads at six halo pieces, so both run conv3x3_pp_kernel<7,2,6,2> - their
+#  keys say so - and the pair holds a kernel to itself; the pair on which the request is honoured is cx-splitk4-ri0 / -ri1)
 SAME_BITS = [("pp-bn128-ri0", "pp-bn128-ri1"), ("pp-bn256-ri0", "pp-bn256-ri1"), ("pp-bn128-ri0", "pp-bn256-ri0"),
              ("pp-splitk-ri0", "pp-splitk-ri1"), ("pp-px37-bn256", "pp-px37-splitk"), ("g1-shortcut-3x5", "pp-shortcut-3x5"),
              ("g1-shortcut-10x6", "pp-shortcut-10x6"), ("1x1-gather-c128", "pp1x1-layout2-s2"), ("1x1-stage1", "pp1x1-5ksteps")]
+# the census pairs: asserted bit-identical on the exact operands and on Gaussian ones.  The planner's comments say none of these
+# changes the k order of an output element: DMA issue order (IM), halo pitch, read placement (RI), pixel split against pixel split.
+CENSUS_SAME_BITS = [
+    ("pp-bn256-ri0", "cx-im-231"), ("cx-pp251", "cx-im-251"), ("pp-1chunk", "cx-im-431"), ("pp-bn128-ri0", "cx-im-451"),
+    ("cx-splitk4-ri0", "cx-im-242"), ("pp-splitk-ri0", "cx-im-262"),
+    ("pp-bn256-ri0", "cx-pitch-plain"), ("cx-pp231-ds", "cx-pitch-ds"), ("cx-splitk4-ri0", "cx-pitch-splitk"),
+    ("cx-splitk4-ri0", "cx-splitk4-ri1"), ("cx-pp251", "cx-pp451-5x5"),
+]
 
-# one subnormal-weight case per kernel file (fp16)
-SUBNORMAL_CASES = ["g1-c512-7x7", "pp-splitk-res", "c3-3x3", "stem-pool3-odd", "stem-s2d-pool3"]
+# one subnormal-weight case per kernel file (fp16), and one on an instantiation of conv_pp.hip the census table added
+SUBNORMAL_CASES = ["g1-c512-7x7", "pp-splitk-res", "c3-3x3", "stem-pool3-odd", "stem-s2d-pool3", "cx-pp251-ds"]
 
 
 def case_by_name(name):
-    return next(c for c in CONV_CASES + GELU_CASES if c.name == name)
+    return next(c for c in CONV_CASES + GELU_CASES + CENSUS_CASES if c.name == name)
 
 
 def exact_n_nz(case):
@@ -529,6 +608,57 @@ def _sync(what):
         pytest.exit(f"{what}: the GPU reported {e}; stopping the session", returncode=3)
 
 
+CONV_OPS = ("conv", "ds", "pool2")      # the ops the conv planner plans (`ops.conv_plan_key`)
+
+
+def case_ds(case):
+    """(dsH, dsW, dsCin, ds_stride) of the shortcut's input map as `exact_operands` / `float_operands` build it."""
+    dsC, sd = case.ds
+    return (case.H - 1) * sd + 1 + (sd - 1), (case.W - 1) * sd + 1 + (sd - 1), dsC, sd
+
+
+def set_hooks(lib, case):
+    """The process-wide hooks of a case; `reset_hooks` in a `finally` takes them back."""
+    if case.tune is not None:
+        assert lib.frmap_conv_pp_tuning(*case.tune) == 0
+    for value, hook in ((case.ri, lib.frmap_conv_pp_ri), (case.im, lib.frmap_conv_pp_im), (case.pitch, lib.frmap_conv_pp_pitch),
+                        (case.wstart, lib.frmap_conv_wave_start)):
+        if value is not None:
+            assert hook(value) == 0
+
+
+def reset_hooks(lib, case=None):
+    """(`frmap_conv_wave_start` only where the case set it: `test_conv_wave_pipeline_gpu.py` sets it around its launches)"""
+    lib.frmap_conv_pp_tuning(-1, -1, -1)
+    lib.frmap_conv_pp_ri(-1)
+    lib.frmap_conv_pp_im(-1)
+    lib.frmap_conv_pp_pitch(-1)
+    lib.frmap_conv_pp_ds(-1)
+    if case is not None and case.wstart is not None:
+        lib.frmap_conv_wave_start(-1)
+
+
+def plan_key(ops, case):
+    """`ops.conv_plan_key` of the case's launch under the hooks now in force (needs no GPU)."""
+    if case.op == "ds":
+        return ops.conv_plan_key(case.B, case.H, case.W, case.Cin, case.Cout, 3, 1, ops.FUSE_SHORTCUT, case_ds(case))
+    if case.op == "pool2":
+        return ops.conv_plan_key(case.B, case.H, case.W, case.Cin, case.Cout, 3, 1, ops.FUSE_POOL2)
+    assert case.op == "conv", case.op
+    return ops.conv_plan_key(case.B, case.H, case.W, case.Cin, case.Cout, case.k, case.stride, ops.FUSE_RESIDUAL if case.res else ops.FUSE_NONE)
+
+
+def planned_key(case):
+    """The key of the case's launch under its own hooks, which are reset afterwards: what `launch_case` asserts, without a launch."""
+    from frmap_amd import _lib, ops
+    lib = _lib.load()
+    try:
+        set_hooks(lib, case)
+        return plan_key(ops, case)
+    finally:
+        reset_hooks(lib, case)
+
+
 def query_path(lib, ops, case):
     """The answer of the case's layout / form query under the tuning now in force."""
     B, H, W, Cin, Cout = case.B, case.H, case.W, case.Cin, case.Cout
@@ -586,13 +716,13 @@ def launch_case(case, d, dtype, also_unfused=False):
     from frmap_amd import _lib, ops
     lib = _lib.load()
     try:
-        if case.tune is not None:
-            assert lib.frmap_conv_pp_tuning(*case.tune) == 0
-        if case.ri is not None:
-            lib.frmap_conv_pp_ri(case.ri)
+        set_hooks(lib, case)
         if case.query is not None:
             got = query_path(lib, ops, case)
             assert got in case.query[1], (case.name, case.query[0], "answers", got, "wanted", case.query[1])
+        if case.key is not None:       # the instantiation this launch dispatches, on this device's CU count
+            got = plan_key(ops, case)
+            assert got == case.key, (case.name, "launches", got, "the table says", case.key)
         sh, wpk = d["sh"], d["wpk"]
         y2 = None
         if case.op == "conv":
@@ -620,8 +750,7 @@ def launch_case(case, d, dtype, also_unfused=False):
         _sync(case.name)
         return (y, y2) if also_unfused and y2 is not None else y
     finally:
-        lib.frmap_conv_pp_tuning(-1, -1, -1)
-        lib.frmap_conv_pp_ri(-1)
+        reset_hooks(lib, case)
 
 
 def run_case(case, o, dtype, also_unfused=False, place=None):

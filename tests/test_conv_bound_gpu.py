@@ -33,7 +33,7 @@ def _check(case, family, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
-@pytest.mark.parametrize("name", [c.name for c in cc.CONV_CASES + cc.GELU_CASES])
+@pytest.mark.parametrize("name", [c.name for c in cc.CONV_CASES + cc.GELU_CASES + cc.CENSUS_CASES])
 def test_conv_one_rounding(name, dtype):
     case = cc.case_by_name(name)
     for family in ("gauss", "relu"):

@@ -7,7 +7,9 @@ Covers conv_igemm.hip (wave-autonomous, register-prefetch, generic, stride-2 spl
 Linear as 1x1, the first-generation fused shortcut, the fused 2x2 pool's generic and wave forms, linear_mfma with and without
 split-K), conv_pp.hip (3x3 with 128 / 256-channel tiles and split-K, interleaved reads on and off, a forced tile of 37 pixels, one
 32-channel chunk; stride 2; fused shortcut; 1x1 layouts 1 / 2 / 3, one k-step, an odd k-step count; the fused pool), conv_small_cin.hip,
-stem_pool.hip and stem_s2d.hip (fp32 and uint8 entries), each with its path asserted where the library has a query for it.  Where two
+stem_pool.hip and stem_s2d.hip (fp32 and uint8 entries), each with its path asserted where the library has a query for it, and
+the census table (`conv_cases.CENSUS_CASES`: every instantiation the cases above do not reach), each with the kernel instantiation
+it launches asserted by name (`ops.conv_plan_key`).  Where two
 generations, two layouts or a fused and a two-launch path compute the same layer, their outputs must also agree bit for bit.
 """
 import pytest
@@ -21,7 +23,7 @@ DTYPES = [torch.float16, torch.bfloat16]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["fp16", "bf16"])
-@pytest.mark.parametrize("name", [c.name for c in cc.CONV_CASES])
+@pytest.mark.parametrize("name", [c.name for c in cc.CONV_CASES + cc.CENSUS_CASES])
 def test_conv_exact_integers(name, dtype):
     case = cc.case_by_name(name)
     o = cc.gpu_operands(case, "exact", dtype)

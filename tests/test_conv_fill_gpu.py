@@ -22,23 +22,25 @@ from frmap_amd import _lib, ops  # noqa: E402
 DTYPES = [torch.float16, torch.bfloat16]
 DT_IDS = ["fp16", "bf16"]
 
-# (case, filled tile, image-aligned tile, tile the planner picks by itself).  tune = (1, -1, bn): layout forced on, tile left to the planner.
+# (case, filled tile, image-aligned tile, tile the planner picks by itself, key of the filled run, key of the image-aligned run: the
+# kernel instantiations `ops.conv_plan_key` names - a larger tile can take more halo pieces).  tune = (1, -1, bn): layout forced on,
+# tile left to the planner.
 _c = cc._c
 FILL_CASES = [
     # 224 x 256 layout: 1764 px = 7.875 tiles of 224, up to three images per tile
-    (_c("fill-224x256-res", cc.PP, "conv", 9, 14, 14, 128, 256, res=True, tune=(1, -1, 256), query=("conv3x3_pp", (1,))), 224, 196, 196),
+    (_c("fill-224x256-res", cc.PP, "conv", 9, 14, 14, 128, 256, res=True, tune=(1, -1, 256), query=("conv3x3_pp", (1,))), 224, 196, 196, "conv3x3_pp_kernel<7,2,3,1>", "conv3x3_pp_kernel<7,2,3,1>"),
     # 448 x 128 layout: 3920 px = 8.75 tiles of 448
-    (_c("fill-448x128", cc.PP, "conv", 5, 28, 28, 128, 128, act=cc.ACT_NONE, tune=(1, -1, 128), query=("conv3x3_pp", (2,))), 448, 392, 448),
-    (_c("fill-448x128-res", cc.PP, "conv", 5, 28, 28, 128, 128, res=True, tune=(1, -1, 128), query=("conv3x3_pp", (2,))), 448, 392, 448),
+    (_c("fill-448x128", cc.PP, "conv", 5, 28, 28, 128, 128, act=cc.ACT_NONE, tune=(1, -1, 128), query=("conv3x3_pp", (2,))), 448, 392, 448, "conv3x3_pp_kernel<7,4,5,1>", "conv3x3_pp_kernel<7,4,5,1>"),
+    (_c("fill-448x128-res", cc.PP, "conv", 5, 28, 28, 128, 128, res=True, tune=(1, -1, 128), query=("conv3x3_pp", (2,))), 448, 392, 448, "conv3x3_pp_kernel<7,4,5,1>", "conv3x3_pp_kernel<7,4,5,1>"),
     # split-K 224 x 128: six halo pieces in place of four
-    (_c("fill-splitk", cc.PP, "conv", 9, 14, 14, 256, 256, tune=(1, -1, 1282), query=("conv3x3_pp", (3,))), 224, 196, 224),
+    (_c("fill-splitk", cc.PP, "conv", 9, 14, 14, 256, 256, tune=(1, -1, 1282), query=("conv3x3_pp", (3,))), 224, 196, 224, "conv3x3_pp_kernel<7,2,6,2>", "conv3x3_pp_kernel<7,2,4,2>"),
     # fused shortcut from a 28x28x128 map (224 x 256) and from a 56x56x64 map (448 x 128), stride 2
-    (_c("fill-shortcut-14", cc.PP, "ds", 9, 14, 14, 256, 256, ds=(128, 2), tune=(1, -1, 256), query=("conv3x3_pp_ds", (1,))), 224, 196, 196),
-    (_c("fill-shortcut-28", cc.PP, "ds", 5, 28, 28, 128, 128, ds=(64, 2), tune=(1, -1, 128), query=("conv3x3_pp_ds", (2,))), 448, 392, 448),
+    (_c("fill-shortcut-14", cc.PP, "ds", 9, 14, 14, 256, 256, ds=(128, 2), tune=(1, -1, 256), query=("conv3x3_pp_ds", (1,))), 224, 196, 196, "conv3x3_pp_kernel<7,2,3,1,DS>", "conv3x3_pp_kernel<7,2,3,1,DS>"),
+    (_c("fill-shortcut-28", cc.PP, "ds", 5, 28, 28, 128, 128, ds=(64, 2), tune=(1, -1, 128), query=("conv3x3_pp_ds", (2,))), 448, 392, 448, "conv3x3_pp_kernel<7,4,5,1,DS>", "conv3x3_pp_kernel<7,4,5,1,DS>"),
     # stride 2, 28x28x128 -> 14x14x256 (224 x 256 layout): 15 rows are the largest tile whose halo fits the two 8 KB pieces there are
     # stride 2, 56x56x64 -> 28x28x128 (448 x 128 layout, filled by default): 15 rows = 420 px, 3920 px = 9.33 tiles
-    (_c("fill-stride2-448x128", cc.PP, "conv", 5, 56, 56, 64, 128, stride=2, tune=(1, -1, 128), query=("conv3x3s2_pp", (2,))), 420, 392, 420),
-    (_c("fill-stride2", cc.PP, "conv", 9, 28, 28, 128, 256, stride=2, tune=(1, -1, 256), query=("conv3x3s2_pp", (1,))), 210, 196, 196),
+    (_c("fill-stride2-448x128", cc.PP, "conv", 5, 56, 56, 64, 128, stride=2, tune=(1, -1, 128), query=("conv3x3s2_pp", (2,))), 420, 392, 420, "conv3x3s2_pp_kernel<7,4,4>", "conv3x3s2_pp_kernel<7,4,4>"),
+    (_c("fill-stride2", cc.PP, "conv", 9, 28, 28, 128, 256, stride=2, tune=(1, -1, 256), query=("conv3x3s2_pp", (1,))), 210, 196, 196, "conv3x3s2_pp_kernel<7,2,2>", "conv3x3s2_pp_kernel<7,2,2>"),
 ]
 
 
@@ -57,13 +59,22 @@ def _planned_tile(case, px):
         lib.frmap_conv_pp_tuning(-1, -1, -1)
 
 
+def fill_runs(entry):
+    """(case of the filled run, case of the image-aligned run) of a FILL_CASES entry, each with its tile and its key."""
+    case, filled_px, aligned_px, own_px, key_filled, key_aligned = entry
+    first = case._replace(key=key_filled)
+    if own_px != filled_px:                    # a layout the fill step skips: the filled size through the hook
+        first = first._replace(tune=(case.tune[0], filled_px, case.tune[2]))
+    return first, case._replace(tune=(case.tune[0], aligned_px, case.tune[2]), key=key_aligned)
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
-@pytest.mark.parametrize("case,filled_px,aligned_px,own_px", FILL_CASES, ids=[c[0].name for c in FILL_CASES])
-def test_filled_tiles_compute_what_image_aligned_tiles_compute(case, filled_px, aligned_px, own_px, dtype):
+@pytest.mark.parametrize("entry", FILL_CASES, ids=[c[0].name for c in FILL_CASES])
+def test_filled_tiles_compute_what_image_aligned_tiles_compute(entry, dtype):
+    case, filled_px, aligned_px, own_px = entry[:4]
     assert _planned_tile(case, -1) == own_px, (case.name, "the planner's own tile", _planned_tile(case, -1), "expected", own_px)
     assert _planned_tile(case, aligned_px) == aligned_px, (case.name, "the hook did not force the image-aligned tile")
-    if own_px != filled_px:                    # a layout the fill step skips: the filled size through the hook
-        case = case._replace(tune=(case.tune[0], filled_px, case.tune[2]))
+    case, aligned = fill_runs(entry)           # (a layout the fill step skips: the filled size through the hook)
     own = _planned_tile(case, case.tune[1])
     assert own == filled_px, (case.name, "tile of the first run", own, "expected", filled_px)
     Ho, Wo = case.H // case.stride, case.W // case.stride
@@ -77,12 +88,10 @@ def test_filled_tiles_compute_what_image_aligned_tiles_compute(case, filled_px, 
     # the filled run, three times between guard bands (unguarded, 0xFF, 0x5A): same bits, bands untouched
     y, = guard.two_fills(lambda place: cc.run_case(case, o, dtype, place=place), [ops], what=case.name)
     # the image-aligned run
-    aligned = case._replace(tune=(case.tune[0], aligned_px, case.tune[2]))
     try:
         y0 = cc.run_case(aligned, o, dtype)
     finally:
-        _lib.load().frmap_conv_pp_tuning(-1, -1, -1)
-        _lib.load().frmap_conv_pp_ri(-1)
+        cc.reset_hooks(_lib.load())
     assert y.dtype == dtype and y0.dtype == dtype
     d = guard.first_difference(y.contiguous(), y0.contiguous())
     assert torch.equal(y, y0), f"{case.name}: tiles of {own} px and of {aligned_px} px differ: {d}"

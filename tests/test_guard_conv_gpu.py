@@ -1,7 +1,7 @@
 """GPU: every conv-family kernel between guard bands (`guard.py`): it writes all of its output and nothing else, and its result
 does not depend on a byte outside its operands.
 
-Every entry of `conv_cases.CONV_CASES` (exact-integer operands), `GELU_CASES` (their float operands) and `LINEAR_CASES`, in fp16
+Every entry of `conv_cases.CONV_CASES` and `CENSUS_CASES` (exact-integer operands), `GELU_CASES` (their float operands) and `LINEAR_CASES`, in fp16
 and bf16, runs through `conv_cases.run_case` / `run_linear` three times: unguarded, and with every operand, output and
 workspace between bands of 0xFF.. (NaN) and of 0x5A.. (203.25 in fp16).  `Guard.check()` must pass and the three outputs must
 hold the same bits.  What the values ARE is the business of `test_conv_exact_gpu.py` / `test_conv_bound_gpu.py`.  The weight
@@ -30,7 +30,7 @@ DT_IDS = ["fp16", "bf16"]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
-@pytest.mark.parametrize("case", cc.CONV_CASES, ids=[c.name for c in cc.CONV_CASES])
+@pytest.mark.parametrize("case", cc.CONV_CASES + cc.CENSUS_CASES, ids=[c.name for c in cc.CONV_CASES + cc.CENSUS_CASES])
 def test_conv_case_is_guarded(case, dtype):
     o = cc.gpu_operands(case, "exact", dtype)
     fused_pool = case.op in ("pool2", "c3pool2")        # (their two-launch twin runs between the same bands)

@@ -1,7 +1,7 @@
 """GPU: one non-finite element into every conv-family kernel; the rules of `poison.py` on what comes out ("Non-finite
 values": no swallowing, no finite-but-wrong output, strict batch isolation, the receptive field and nothing else).
 
-Every entry of `conv_cases.CONV_CASES`, `GELU_CASES` and `LINEAR_CASES`, fp16 and bf16, on the Gaussian operands of the bound family
+Every entry of `conv_cases.CONV_CASES`, `GELU_CASES`, `CENSUS_CASES` and `LINEAR_CASES`, fp16 and bf16, on the Gaussian operands of the bound family
 (no weight is exactly zero: asserted).  A case runs once clean, then once per poison: every position of `poison.positions` in x
 and, where the case has them, in the residual and in the fused shortcut's input.  The first-layer and stem cases (Cin = 3: one
 case per kernel, and the home of the halos below) run all three kinds (NaN, +inf, -inf) at every position.  For the MFMA conv
@@ -42,7 +42,7 @@ import poison  # noqa: E402
 
 DTYPES = [torch.float16, torch.bfloat16]
 DT_IDS = ["fp16", "bf16"]
-ALL_CASES = cc.CONV_CASES + cc.GELU_CASES
+ALL_CASES = cc.CONV_CASES + cc.GELU_CASES + cc.CENSUS_CASES      # (appended: the kind rotation of the earlier entries stays)
 POOL_OF = {"pool2": (2, 2, 0), "c3pool2": (2, 2, 0), "stem3": (3, 2, 1), "stem2": (2, 2, 0), "stem3u8": (3, 2, 1), "stem2u8": (2, 2, 0)}
 
 
@@ -168,7 +168,7 @@ def test_conv_case_propagates(case, dtype):
             assert d is None, "%s: the fused conv + pool differs from the two-launch path on the poisoned operands: %s" % (what, d)
 
 
-OVERFLOW_CASES = [c for c in cc.CONV_CASES if not c.op.endswith("u8")]
+OVERFLOW_CASES = [c for c in cc.CONV_CASES + cc.CENSUS_CASES if not c.op.endswith("u8")]
 OVERFLOW_X, OVERFLOW_W = 32768.0, 8.0
 
 

@@ -11,6 +11,7 @@
 //   * lds_bytes <= 160 KB, <= 80 KB where the plan counts on two workgroups per CU; halo_bytes / 64 < 65536; grid > 0
 //   * a shortcut plan exists exactly where ds_supported answers 1, a pooled plan exactly where pool2_form != 0, of the form's family
 //   * the candidates' layouts, the forms and the split-K slices are the library's answers
+//   * the plan, and the plan the fill step makes of it, has a key (conv_plan.h: an instantiation that exists) of its own kernel
 // A failed check is a line "FAIL ..." on stdout and exit status 1.  Without input it checks three layers of its own.  With the
 // argument "big" it reads layers and sweeps their batch past the 32-bit marks (below).
 #include <stdio.h>
@@ -54,6 +55,13 @@ static ConvPlan planned(const char* what, const ConvLayer& L, const ConvTuning& 
   CHECK(q.nblocks > 0, "grid %d", q.nblocks);
   CHECK(q.kernel < CK_PP || (q.mtiles > 0 && q.ntiles > 0 && q.tile_px > 0), "tiles %d x %d of %d px", q.mtiles, q.ntiles, q.tile_px);
   CHECK(q.label && strstr(q.label, kernel_name(q.kernel)) == q.label, "label %s", q.label ? q.label : "(null)");
+  // every plan, before and after the fill step, names an instantiation that exists, of the plan's kernel; the key selects it back
+  for (const ConvPlan& k : {q, conv_fill(L, q, t, inv)}) {
+    const char* key = conv_plan_key(k);
+    ConvPlan back{};
+    CHECK(key[0] && strstr(key, kernel_name(k.kernel)) == key && key[strlen(kernel_name(k.kernel))] == '<', "key '%s' of a %s plan", key, kernel_name(k.kernel));
+    CHECK(conv_plan_from_key(key, &back) && conv_plan_key_index(back) == conv_plan_key_index(k), "key '%s' does not select its plan back", key);
+  }
   return q;
 }
 
