@@ -92,6 +92,9 @@ PROTOTYPES = {
     "frmap_normalize_u8_hwc": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _vp]),
     "frmap_softmax_argmax": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "frmap_pairwise_distance": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "frmap_classify_tally_words": (_sz, [_i, _i, _i, _i]),
+    "frmap_classify_tally": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frmap_classify_tally_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "frmap_head_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_top1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
@@ -179,6 +182,8 @@ ALIGNMENT = {
     "frmap_cnn_attention": {"qkv": _T, "x": _T, "gamma": _E4, "spatial_w": _E4, "spatial_b": _E4, "out_map": ("tensor", 4), "out_pool": _E4},
     "frmap_softmax_argmax": {"logits": _E4, "probs_out": _E4, "pred_out": _E4},
     "frmap_pairwise_distance": {"a": _E4, "b": _E4, "dist_out": _E4, "same_out": _E4},
+    "frmap_classify_tally": {"logits": _E4, "labels": _E4, "state": _E8, "row_pred_out": _E4, "row_rank_out": _E4, "row_conf_out": _E4,
+                             "row_loss_out": _E4},
     "frmap_match_top1": {"emb": _M, "gallery": _M, **_TOP1_OUT, "workspace": _W},
     "frmap_match_pack_gallery": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
     "frmap_match_pack_gallery_rows": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},

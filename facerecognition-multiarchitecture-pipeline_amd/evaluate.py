@@ -9,7 +9,9 @@
 * evaluation step — `src/testing.py:255-283`: forward → softmax → arg-max, with the ArcFace branch
   scoring embeddings against the class centres (`:264-269`; `hyperparameter_tuning.py:1038-1046`);
 * Siamese verification — `src/testing.py:170-177`: ``dist = pairwise_distance(out1, out2)``,
-  ``pred = dist < 0.5``.
+  ``pred = dist < 0.5``;
+* the accumulate step of that loop and the metric block of `src/advanced_metrics.py` from exact integers kept on the device —
+  `ClassificationTally`, `evaluate_stream`, `metrics_from_tally` (one launch per batch, no copy, one synchronisation at the end).
 """
 from __future__ import annotations
 
@@ -337,6 +339,295 @@ def evaluate_model(model, model_type: str, test_data, class_names: Optional[Sequ
             json.dump({"model_type": model_type, "model_name": model_name or model_type, "dataset": dataset_name,
                        "metrics": metrics, "class_names": list(class_names)}, f, indent=2)
     return model_results
+
+
+# ------------------------------------------------------------------------------------------------
+# The classification tally: the accumulate step of `src/testing.py:278-283` and the metric block of `src/advanced_metrics.py`
+# (per-class precision / recall / F1, the enhanced confusion matrix, expected / maximum calibration error) from exact integers
+# kept on the device (`ops.classify_tally`), as `verification_metrics` does for pairs.  The rule below is the specification; its
+# integer half is csrc/tally_rule.h, which the kernel and its host twin compile.
+# ------------------------------------------------------------------------------------------------
+TALLY_HEADER_WORDS = 8
+TALLY_LOSS_CLAMP, TALLY_LOSS_SCALE, TALLY_CONF_SCALE = 65536.0, float(2 ** 24), float(2 ** 32)
+
+
+def tally_layout(C: int, ranks: int = 6, n_bins: int = 10, confusion: bool = True) -> dict:
+    """name -> slice of the uint64 state: an 8-word header (``rows, ignored, nonfinite, correct, loss_q``, three reserved zero
+    words), then ``rank_hist`` [ranks], ``support`` / ``predicted`` / ``hit`` [C], ``bin_count`` / ``bin_correct`` / ``bin_conf_q``
+    [n_bins] and, when kept, ``confusion`` [C * C] (row = label, column = prediction).  ``"words"`` -> the total."""
+    out = {name: slice(k, k + 1) for k, name in enumerate(ops.TALLY_HEADER)}
+    at = TALLY_HEADER_WORDS
+    for name, n in [("rank_hist", ranks), ("support", C), ("predicted", C), ("hit", C), ("bin_count", n_bins), ("bin_correct", n_bins),
+                    ("bin_conf_q", n_bins)] + ([("confusion", C * C)] if confusion else []):
+        out[name] = slice(at, at + int(n))
+        at += int(n)
+    out["words"] = at
+    return out
+
+
+def tally_edges(n_bins: int) -> np.ndarray:
+    """The bin edges as the kernel forms them: ``edge_k = k * (1 / (n_bins - 1))`` in float64, the last one 1.0, the single edge of
+    ``n_bins == 1`` 0 - bit for bit ``np.linspace(0, 1, n_bins)`` for n_bins 1 ... 1024 (tested)."""
+    if n_bins == 1:
+        return np.zeros(1, np.float64)
+    e = np.arange(n_bins, dtype=np.float64) * (1.0 / float(n_bins - 1))
+    e[-1] = 1.0
+    return e
+
+
+def tally_row_rule(logits, labels):
+    """The integer half of the row rule: ``(pred int32, rank int32, why int8)`` per row.  ``why`` 1: the label is outside
+    ``[0, C)`` - the row is ignored whatever its logits are; 2: a logit is NaN or infinite; 0: counted.  Declined rows have
+    pred = rank = -1.  ``pred`` is the first arg-max; ``rank = #{c : z[c] > z[y]} + #{c < y : z[c] == z[y]}``, so rank == 0 iff
+    pred == y.  fp32 comparisons only: exact on any machine."""
+    z = np.asarray(logits, dtype=np.float32)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    B, C = z.shape
+    why = np.zeros(B, np.int8)
+    why[(y < 0) | (y >= C)] = 1
+    why[(why == 0) & ~np.isfinite(z).all(axis=1)] = 2
+    pred, rank = np.full(B, -1, np.int32), np.full(B, -1, np.int32)
+    ok = why == 0
+    if ok.any():
+        zc, yc = z[ok], y[ok]
+        zy = zc[np.arange(len(yc)), yc][:, None]
+        pred[ok] = zc.argmax(axis=1)                                           # (numpy's arg-max is the first one)
+        rank[ok] = (zc > zy).sum(axis=1) + ((zc == zy) & (np.arange(C)[None, :] < yc[:, None])).sum(axis=1)
+    return pred, rank, why
+
+
+def tally_rows_reference(logits, labels):
+    """The row records in float64: ``(pred, rank, conf, loss)`` with ``conf = 1 / sum_c exp(z[c] - z[pred])`` and
+    ``loss = max(0, log sum_c exp(z[c] - z[pred]) + (z[pred] - z[y]))`` (NaN for declined rows) - what the kernel's fp32 values
+    are measured against."""
+    z = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    pred, rank, why = tally_row_rule(logits, labels)
+    conf, loss = np.full(len(y), np.nan), np.full(len(y), np.nan)
+    ok = why == 0
+    if ok.any():
+        zc, yc = z[ok], y[ok]
+        mx = zc.max(axis=1)
+        s = np.exp(zc - mx[:, None]).sum(axis=1)
+        conf[ok] = 1.0 / s
+        loss[ok] = np.maximum(0.0, np.log(s) + (mx - zc[np.arange(len(yc)), yc]))
+    return pred, rank, conf, loss
+
+
+def tally_rule(logits, labels, row_conf, row_loss, ranks: int = 6, n_bins: int = 10, confusion: bool = True, state=None):
+    """THE ACCUMULATION RULE in numpy: add the rows to a uint64 state (a fresh one if ``state`` is None) and return
+    ``(state, pred, rank)``.  ``row_conf`` / ``row_loss`` are the rows' fp32 confidence and loss (the device's own values: the
+    rule is defined on their bits); pred and rank come from `tally_row_rule`.
+
+    A declined row adds 1 to ``ignored`` (label outside [0, C)) or ``nonfinite`` and nothing else.  A counted row adds:
+    ``rows += 1``, ``correct += (rank == 0)``, ``loss_q += rint(min(float64(loss), 65536) * 2^24)``;
+    ``rank_hist[min(rank, ranks - 1)] += 1``; ``support[y] += 1``, ``predicted[pred] += 1``, ``hit[y] += (rank == 0)``; with
+    ``b = np.digitize(float64(conf), tally_edges(n_bins)) - 1`` (the reference's rule: n_bins EDGES, so only conf == 1.0 reaches
+    the last bin) ``bin_count[b] += 1``, ``bin_correct[b] += (rank == 0)``, ``bin_conf_q[b] += rint(float64(conf) * 2^32)``; and
+    ``confusion[y * C + pred] += 1`` where the matrix is kept.  Integers only: the state does not depend on the order of the rows
+    or on how they are split into calls.  ``loss_q`` overflows after 2^24 rows at the clamp, 2^34 rows of losses below 64."""
+    z = np.asarray(logits, dtype=np.float32)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    B, C = z.shape
+    conf = np.asarray(row_conf, dtype=np.float32).astype(np.float64).reshape(-1)
+    loss = np.asarray(row_loss, dtype=np.float32).astype(np.float64).reshape(-1)
+    lay = tally_layout(C, ranks, n_bins, confusion)
+    if state is None:
+        state = np.zeros(lay["words"], np.uint64)
+    assert state.dtype == np.uint64 and state.shape == (lay["words"],)
+    pred, rank, why = tally_row_rule(z, y)
+    ok = why == 0
+    one = np.uint64(1)
+    state[1] += np.uint64(int((why == 1).sum()))
+    state[2] += np.uint64(int((why == 2).sum()))
+    yc, pc, rc, cc, lc = y[ok], pred[ok].astype(np.int64), rank[ok].astype(np.int64), conf[ok], loss[ok]
+    right = (rc == 0).astype(np.uint64)
+    state[0] += np.uint64(len(yc))
+    state[3] += np.uint64(int(right.sum()))
+    state[4] += np.rint(np.minimum(lc, TALLY_LOSS_CLAMP) * TALLY_LOSS_SCALE).astype(np.uint64).sum(dtype=np.uint64)
+    b = np.digitize(cc, tally_edges(n_bins)) - 1
+    np.add.at(state, lay["rank_hist"].start + np.minimum(rc, ranks - 1), one)
+    np.add.at(state, lay["support"].start + yc, one)
+    np.add.at(state, lay["predicted"].start + pc, one)
+    np.add.at(state, lay["hit"].start + yc, right)
+    np.add.at(state, lay["bin_count"].start + b, one)
+    np.add.at(state, lay["bin_correct"].start + b, right)
+    np.add.at(state, lay["bin_conf_q"].start + b, np.rint(cc * TALLY_CONF_SCALE).astype(np.uint64))
+    if confusion:
+        np.add.at(state, lay["confusion"].start + yc * C + pc, one)
+    return state, pred, rank
+
+
+def tally_counts(state, C: int, ranks: int = 6, n_bins: int = 10, confusion: bool = True) -> dict:
+    """A state (uint64 / int64 words, numpy) as integers by name: the five header counters as Python ints, ``rank_hist``,
+    ``support``, ``predicted``, ``hit``, ``bin_count``, ``bin_correct`` as int64 arrays, ``bin_conf_q`` as uint64 and
+    ``confusion`` as an int64 ``[C, C]`` matrix (row = label, column = prediction) or None where it is not kept."""
+    a = np.ascontiguousarray(state).view(np.uint64).reshape(-1)
+    lay = tally_layout(C, ranks, n_bins, confusion)
+    if a.size != lay["words"]:
+        raise ValueError(f"tally_counts: {a.size} words, C = {C}, ranks = {ranks}, n_bins = {n_bins}, confusion = {confusion} have {lay['words']}")
+    out = {name: int(a[k]) for k, name in enumerate(ops.TALLY_HEADER)}
+    for name in ("rank_hist", "support", "predicted", "hit", "bin_count", "bin_correct"):
+        out[name] = a[lay[name]].astype(np.int64)
+    out["bin_conf_q"] = a[lay["bin_conf_q"]].copy()
+    out["confusion"] = a[lay["confusion"]].astype(np.int64).reshape(C, C) if confusion else None
+    return out
+
+
+def metrics_from_tally(counts: dict, class_names: Optional[Sequence[str]] = None) -> dict:
+    """Float64 metrics from the integers of a tally (`tally_counts` / `ClassificationTally.counts`).  With no counted row every
+    ratio over the rows is NaN; nothing raises.
+
+    * ``accuracy`` = correct / rows; ``precision`` / ``recall`` / ``f1``: sklearn's ``average='weighted'`` with ``zero_division=0``
+      (per class hit / predicted, hit / support, 2 hit / (predicted + support), 0 where the denominator is 0; weights = support);
+    * ``top_k``: ``{k: fraction of rows with rank < k}`` for 1 <= k < ranks (the last cell of the rank histogram pools every rank
+      from ranks - 1 on);
+    * ``loss``: the PER-SAMPLE mean of the fp32 row losses (from the 2^-24 fixed point).  `evaluate_model`'s ``test_loss`` is the
+      mean of the batch means (`testing.py:275-276,327`): the two differ when the last batch is short;
+    * ``per_class``: `advanced_metrics.calculate_per_class_metrics`'s fields except ``roc_auc`` (which needs every score), for
+      every class 0 ... C - 1 (the reference, through sklearn, numbers only the classes that occur in the labels or predictions);
+    * ``confusion``: `advanced_metrics.create_enhanced_confusion_matrix`'s dict (``misclassified_to``: the top 3 by fraction,
+      ties in class order), None where the matrix was not kept;
+    * ``calibration``: `advanced_metrics.expected_calibration_error`'s dict - empty bins read 0, the ECE weights are
+      bin_count / rows, the MCE is the maximum over all bins;
+    * ``rows`` / ``ignored`` / ``nonfinite``: the counted and the declined rows."""
+    support = np.asarray(counts["support"], dtype=np.float64)
+    predicted = np.asarray(counts["predicted"], dtype=np.float64)
+    hit = np.asarray(counts["hit"], dtype=np.float64)
+    C, rows = len(support), int(counts["rows"])
+    names = [str(i) for i in range(C)] if class_names is None else list(class_names)
+    nan = float("nan")
+
+    def ratio(num, den):
+        return np.divide(num, den, out=np.zeros_like(num, dtype=np.float64), where=den > 0)
+    prec, rec, f1 = ratio(hit, predicted), ratio(hit, support), ratio(2.0 * hit, predicted + support)
+    total = float(support.sum())
+    weighted = (lambda v: float((v * support).sum() / total)) if rows else (lambda v: nan)
+    rank_hist = np.asarray(counts["rank_hist"], dtype=np.int64)
+    m = {"rows": rows, "ignored": int(counts["ignored"]), "nonfinite": int(counts["nonfinite"]),
+         "accuracy": int(counts["correct"]) / rows if rows else nan,
+         "precision": weighted(prec), "recall": weighted(rec), "f1": weighted(f1),
+         "top_k": {k: (int(rank_hist[:k].sum()) / rows if rows else nan) for k in range(1, len(rank_hist))},
+         "loss": int(counts["loss_q"]) / TALLY_LOSS_SCALE / rows if rows else nan}
+    m["per_class"] = {names[i]: {"precision": float(prec[i]), "recall": float(rec[i]), "f1": float(f1[i]), "support": int(support[i]),
+                                 "accuracy": float(rec[i])} for i in range(min(C, len(names)))}
+    cm = counts.get("confusion")
+    if cm is None:
+        m["confusion"] = None
+    else:
+        cm = np.asarray(cm, dtype=np.int64).reshape(C, C)
+        rows_total, cols_total = cm.sum(axis=1), cm.sum(axis=0)
+        info = {}
+        for i in range(min(C, len(names))):
+            tp = int(cm[i, i])
+            mis = [(names[j], float(cm[i, j] / rows_total[i])) for j in range(min(C, len(names))) if j != i and cm[i, j] > 0] if rows_total[i] > 0 else []
+            mis.sort(key=lambda x: x[1], reverse=True)                         # (stable: ties stay in class order)
+            info[names[i]] = {"true_positives": tp, "false_positives": int(cols_total[i]) - tp, "false_negatives": int(rows_total[i]) - tp,
+                              "precision": float(tp / cols_total[i]) if cols_total[i] > 0 else 0.0,
+                              "recall": float(tp / rows_total[i]) if rows_total[i] > 0 else 0.0,
+                              "support": int(rows_total[i]), "misclassified_to": mis[:3]}
+        m["confusion"] = {"matrix": cm.tolist(), "class_names": names, "class_statistics": info}
+    bc = np.asarray(counts["bin_count"], dtype=np.float64)
+    acc_b = ratio(np.asarray(counts["bin_correct"], dtype=np.float64), bc)
+    conf_b = ratio(np.asarray(counts["bin_conf_q"]).astype(np.float64) / TALLY_CONF_SCALE, bc)
+    gap = np.abs(acc_b - conf_b)
+    m["calibration"] = {"expected_calibration_error": float((gap * (bc / rows)).sum()) if rows else nan,
+                        "maximum_calibration_error": float(gap.max()), "bin_accuracies": acc_b.tolist(),
+                        "bin_confidences": conf_b.tolist(), "bin_counts": bc.tolist(), "n_bins": len(bc)}
+    return m
+
+
+class ClassificationTally:
+    """A device-resident classification tally: `update` adds a batch of logits and labels in one launch (`ops.classify_tally`) with
+    no copy and no synchronisation, `counts` / `metrics` make the one device-to-host copy at the end.  ``confusion=None`` keeps the
+    confusion matrix when ``num_classes <= 2048`` (32 MiB of state at most)."""
+
+    def __init__(self, num_classes: int, ranks: int = 6, n_bins: int = 10, confusion: Optional[bool] = None, device="cuda"):
+        self.num_classes, self.ranks, self.n_bins = int(num_classes), int(ranks), int(n_bins)
+        self.confusion = self.num_classes <= 2048 if confusion is None else bool(confusion)
+        self.layout = ops.classify_tally_layout(self.num_classes, self.ranks, self.n_bins, self.confusion)   # (refuses a bad shape)
+        self.state = torch.zeros((ops.classify_tally_words(self.num_classes, self.ranks, self.n_bins, self.confusion),),
+                                 dtype=torch.int64, device=device)
+
+    def _shape(self):
+        return self.num_classes, self.ranks, self.n_bins, self.confusion
+
+    def update(self, logits: torch.Tensor, labels) -> "ClassificationTally":
+        """Add ``logits`` float32 ``[B, C]`` (on the tally's device) and ``labels`` ``[B]`` (any integer tensor or sequence; a
+        label outside ``[0, C)`` declines its row).  No synchronisation; an empty batch is a no-op."""
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes:
+            raise ValueError(f"ClassificationTally.update: logits {tuple(logits.shape)} for {self.num_classes} classes")
+        if logits.shape[0] == 0:
+            return self
+        labels = torch.as_tensor(labels)
+        if labels.dtype != torch.int32:                                        # (a wide label must not wrap into the range)
+            labels = labels.to(torch.int64).clamp(-1, self.num_classes).to(torch.int32)
+        ops.classify_tally(logits, labels.to(self.state.device, non_blocking=True), self.state, self.ranks, self.n_bins, self.confusion)
+        return self
+
+    def merge(self, other: "ClassificationTally") -> "ClassificationTally":
+        """Integer add of another tally with the same layout (another rank's, another shard's): the result is the tally of the
+        rows of both, whatever their order."""
+        if self._shape() != other._shape():
+            raise ValueError(f"ClassificationTally.merge: layouts differ ({self._shape()} and {other._shape()})")
+        self.state += other.state.to(self.state.device)
+        return self
+
+    def reset(self) -> "ClassificationTally":
+        self.state.zero_()
+        return self
+
+    def counts(self) -> dict:
+        """The one device-to-host copy: the integers by name (`tally_counts`)."""
+        return tally_counts(self.state.cpu().numpy(), *self._shape())
+
+    def metrics(self, class_names: Optional[Sequence[str]] = None) -> dict:
+        return metrics_from_tally(self.counts(), class_names)
+
+
+def evaluate_stream(model, model_type: str, test_data, num_classes: Optional[int] = None, class_names: Optional[Sequence[str]] = None,
+                    batch_size: int = 32, ranks: int = 6, n_bins: int = 10,
+                    arcface_classifier: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, device="cuda") -> dict:
+    """The loop of `evaluate_model` with a `ClassificationTally` in place of the host lists: every batch is forward -> one
+    `ops.classify_tally` launch, nothing is copied back and nothing waits until the single synchronisation at the end.
+    ``test_data``, ``arcface_classifier`` and the arcface logits (cosine against the class centres, or the given classifier) are
+    `evaluate_model`'s; ``num_classes`` defaults to the width of the first batch's logits.  Returns `metrics_from_tally`'s dict.
+    The one-vs-rest ROC / PR AUCs are NOT returned - they need every score of every sample: use `evaluate_model` for those, and for
+    the reference's JSON files.  ``model_type == 'siamese'`` raises ``ValueError`` (pairs are `verification_metrics`' business)."""
+    import os
+    if model_type == 'siamese':
+        raise ValueError("evaluate_stream tallies classifications; siamese pairs go through evaluate_model or verification_metrics")
+    if isinstance(test_data, (str, os.PathLike)):
+        samples, classes = image_folder(str(test_data))
+        if not samples:
+            raise FileNotFoundError(f"Found 0 files in subfolders of: {test_data}")
+        class_names = list(classes) if class_names is None else list(class_names)
+        batches = _folder_batches(samples, batch_size, device)
+    else:
+        batches = iter(test_data)
+    if model.training:
+        model.eval()
+    tally = None
+    with torch.no_grad():
+        for images, labels in batches:
+            images = images.to(device)
+            if model_type == 'arcface':
+                emb = model(images)
+                if arcface_classifier is not None:
+                    w, b = arcface_classifier
+                    outputs = ops.linear_f32(emb, w.to(device).float(), None, None if b is None else b.to(device).float())
+                else:
+                    outputs, _ = ops.cosine_logits(emb, model.arcface.weight.detach(), s=1.0, want_argmax=False)
+            else:
+                outputs = model(images)
+            outputs = outputs.float()
+            if tally is None:
+                tally = ClassificationTally(int(outputs.shape[1]) if num_classes is None else int(num_classes), ranks, n_bins,
+                                            device=outputs.device)
+            tally.update(outputs, labels)
+    if tally is None:
+        raise ValueError("evaluate_stream: the test set is empty")
+    return tally.metrics(class_names)                                          # the one synchronisation: the state's copy to the host
 
 
 # ------------------------------------------------------------------------------------------------

@@ -524,6 +524,95 @@ def pairwise_distance(a: torch.Tensor, b: torch.Tensor, thresh: Optional[float] 
     return dist, same
 
 
+# ------------------------------------------------------------------------------------------------
+# classification tally (`frmap_classify_tally*`, csrc/classify_tally.hip; the rule is `evaluate.tally_rule`)
+# ------------------------------------------------------------------------------------------------
+TALLY_HEADER = ("rows", "ignored", "nonfinite", "correct", "loss_q")     # words 0 .. 4 of the 8-word header
+TALLY_MAX_RANKS = TALLY_MAX_BINS = 1024
+TALLY_MAX_CONFUSION_CLASSES = 4096
+
+
+def classify_tally_words(C: int, ranks: int = 6, n_bins: int = 10, confusion: bool = True) -> int:
+    """uint64 words of a tally state (`frmap_classify_tally_words`); ``ValueError`` for a shape the launcher refuses."""
+    n = int(_lib.load().frmap_classify_tally_words(int(C), int(ranks), int(n_bins), int(bool(confusion))))
+    if n == 0:
+        raise ValueError(f"classify_tally: unsupported C = {C}, ranks = {ranks}, n_bins = {n_bins}, confusion = {confusion} (C >= 1, ranks "
+                         f"and n_bins in 1 ... {TALLY_MAX_RANKS}, a kept confusion matrix up to C = {TALLY_MAX_CONFUSION_CLASSES})")
+    return n
+
+
+def classify_tally_layout(C: int, ranks: int = 6, n_bins: int = 10, confusion: bool = True) -> dict:
+    """name -> slice of the state, in the order of the state: the five header counters (one word each), ``rank_hist`` [ranks],
+    ``support`` / ``predicted`` / ``hit`` [C], ``bin_count`` / ``bin_correct`` / ``bin_conf_q`` [n_bins] and, when kept,
+    ``confusion`` [C * C] (row = label, column = prediction)."""
+    words = classify_tally_words(C, ranks, n_bins, confusion)
+    out = {name: slice(k, k + 1) for k, name in enumerate(TALLY_HEADER)}
+    at = 8
+    for name, n in (("rank_hist", ranks), ("support", C), ("predicted", C), ("hit", C), ("bin_count", n_bins), ("bin_correct", n_bins),
+                    ("bin_conf_q", n_bins)) + ((("confusion", C * C),) if confusion else ()):
+        out[name] = slice(at, at + int(n))
+        at += int(n)
+    assert at == words, (at, words)
+    return out
+
+
+def classify_tally(logits: torch.Tensor, labels: torch.Tensor, state: Optional[torch.Tensor] = None, ranks: int = 6, n_bins: int = 10,
+                   confusion: bool = True, want_rows: bool = False):
+    """Add a batch to a classification tally in one launch on the current stream (`frmap_classify_tally`; nothing is copied or
+    synchronised).  ``logits`` float32 ``[B, C]``, ``labels`` int32 ``[B]`` (a label outside ``[0, C)`` declines its row, and so
+    does a non-finite logit); ``state``: an int64 tensor of `classify_tally_words` words from an earlier call with the same ``C``,
+    ``ranks``, ``n_bins`` and ``confusion`` (updated in place), or ``None`` for a fresh, zeroed one.  Returns the state, or with
+    ``want_rows`` ``(state, (pred int32, rank int32, conf float32, loss float32))``, the row records of the rule."""
+    # (a non-contiguous operand is copied by `_dev`; the copies live in these names until the launch is enqueued)
+    logits = _dev(logits, "classify_tally.logits", torch.float32, ("frmap_classify_tally", "logits"))
+    labels = _dev(labels, "classify_tally.labels", torch.int32, ("frmap_classify_tally", "labels"))
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError(f"classify_tally: logits [B, C] and labels [B] expected, got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    B, Cc = int(logits.shape[0]), int(logits.shape[1])
+    words = classify_tally_words(Cc, ranks, n_bins, confusion)
+    if state is None:
+        state = torch.zeros((words,), dtype=torch.int64, device=logits.device)
+    else:
+        state = _dev(state, "classify_tally.state", torch.int64, ("frmap_classify_tally", "state"), owned=True)
+        if state.dim() != 1 or state.numel() != words or not state.is_contiguous():
+            raise ValueError(f"classify_tally: state holds {state.numel()} words, C = {Cc}, ranks = {ranks}, n_bins = {n_bins}, "
+                             f"confusion = {bool(confusion)} need {words}")
+    rows = None
+    if want_rows:
+        rows = (torch.empty((B,), dtype=torch.int32, device=logits.device), torch.empty((B,), dtype=torch.int32, device=logits.device),
+                torch.empty((B,), dtype=torch.float32, device=logits.device), torch.empty((B,), dtype=torch.float32, device=logits.device))
+    _lib.check(_lib.load().frmap_classify_tally(logits.data_ptr(), labels.data_ptr(), B, Cc, int(ranks), int(n_bins), int(bool(confusion)),
+                                                state.data_ptr(), *((t.data_ptr() for t in rows) if want_rows else (0, 0, 0, 0)), _stream()),
+               "classify_tally")
+    return (state, rows) if want_rows else state
+
+
+def classify_tally_host(logits, labels, row_conf, row_loss, state: Optional[np.ndarray] = None, ranks: int = 6, n_bins: int = 10,
+                        confusion: bool = True):
+    """The accumulation of `classify_tally` on the CPU over numpy arrays (`frmap_classify_tally_host`: the kernel's rule header
+    compiled for the host; no GPU).  ``row_conf`` / ``row_loss`` float32 ``[B]`` are INPUTS (the device's own row records, or any
+    values to be tallied); pred and rank are computed from the logits.  ``state``: a writable uint64 array (updated in place) or
+    ``None`` for a fresh one.  Returns ``(state, pred int32, rank int32)``."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    row_conf = np.ascontiguousarray(row_conf, dtype=np.float32)
+    row_loss = np.ascontiguousarray(row_loss, dtype=np.float32)
+    if logits.ndim != 2 or labels.shape != (logits.shape[0],) or row_conf.shape != labels.shape or row_loss.shape != labels.shape:
+        raise ValueError("classify_tally_host: logits [B, C] and labels, row_conf, row_loss [B] expected")
+    B, Cc = logits.shape
+    words = classify_tally_words(Cc, ranks, n_bins, confusion)
+    if state is None:
+        state = np.zeros((words,), np.uint64)
+    if not (isinstance(state, np.ndarray) and state.dtype == np.uint64 and state.flags.c_contiguous and state.flags.writeable
+            and state.shape == (words,)):
+        raise ValueError(f"classify_tally_host: state must be a writable contiguous uint64 array of {words} words")
+    pred, rank = np.empty((B,), np.int32), np.empty((B,), np.int32)
+    _lib.check(_lib.load().frmap_classify_tally_host(logits.ctypes.data, labels.ctypes.data, B, Cc, int(ranks), int(n_bins),
+                                                     int(bool(confusion)), state.ctypes.data, pred.ctypes.data, rank.ctypes.data,
+                                                     row_conf.ctypes.data, row_loss.ctypes.data), "classify_tally_host")
+    return state, pred, rank
+
+
 def _workspace(B: int, Cc: int, device) -> torch.Tensor:
     n = _lib.load().frmap_head_workspace_bytes(B, Cc)
     return torch.empty(((n + 15) // 16) * 2, dtype=torch.int64, device=device)
@@ -1211,7 +1300,7 @@ for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_sma
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
               "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
-              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse"):
+              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse", "classify_tally"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
 

@@ -544,6 +544,49 @@ int frmap_softmax_argmax(const float* logits, float* probs_out, int32_t* pred_ou
 int frmap_pairwise_distance(const float* a, const float* b, float* dist_out, int32_t* same_out, float thresh,
                             int B, int D, void* stream);
 
+/* Classification tally: the accumulate step of the evaluation loop (src/testing.py:278-283) and the counts behind the metric
+ * block of src/advanced_metrics.py (per-class precision / recall / F1, the enhanced confusion matrix, expected / maximum
+ * calibration error), kept on the device as exact integers.  One launch per batch adds the batch into `state`; nothing is
+ * copied or synchronised until the caller reads the state.  The host derives every figure from the integers in float64.
+ *
+ * The rule, for row i with fp32 logits z[0 .. C) and int32 label y:
+ *   declined : y < 0 or y >= C: the row adds 1 to `ignored` and nothing else, whatever its logits are.  Otherwise, if any z[c]
+ *              is NaN, +inf or -inf: it adds 1 to `nonfinite` and nothing else.  Row records of a declined row: pred = rank = -1,
+ *              conf = loss = NaN.
+ *   counted  : pred = the first arg-max (the smallest index among the maxima);
+ *              rank = #{c : z[c] > z[y]} + #{c < y : z[c] == z[y]}, so rank == 0 iff pred == y (fp32 comparisons: exact);
+ *              conf = 1 / sum_c exp(z[c] - z[pred]) and loss = max(0, log sum_c exp(z[c] - z[pred]) + (z[pred] - z[y])) in fp32:
+ *              the device's own values; everything below is defined on their fp32 bits.
+ *   bin      : np.digitize(conf, np.linspace(0, 1, n_bins)) - 1, the reference's rule (n_bins EDGES, so only conf == 1.0 falls
+ *              in the last bin): edge_k = 1.0 for k == n_bins - 1, else (double)k * (1.0 / (double)(n_bins - 1)); the single edge of
+ *              n_bins == 1 is 0; bin = #{k : edge_k <= (double)conf} - 1.
+ *   adds     : rows += 1, correct += (rank == 0), loss_q += llrint(min((double)loss, 65536.0) * 2^24);
+ *              rank_hist[min(rank, R - 1)] += 1; support[y] += 1, predicted[pred] += 1, hit[y] += (rank == 0);
+ *              bin_count[b] += 1, bin_correct[b] += (rank == 0), bin_conf_q[b] += llrint((double)conf * 2^32);
+ *              confusion[y * C + pred] += 1 with keep_confusion.
+ *   Integer adds only (64-bit atomics): a state holds the same bits for any order of the rows and any split into launches.
+ * state : uint64 words, zeroed by the caller before the first launch: an 8-word header (rows, ignored, nonfinite, correct, loss_q,
+ *         three reserved words that stay zero), then rank_hist[R], support[C], predicted[C], hit[C], bin_count[n_bins],
+ *         bin_correct[n_bins], bin_conf_q[n_bins] and, with keep_confusion, confusion[C * C].  The words-query takes no stream,
+ *         returns the number of WORDS, and 0 for arguments the launcher would refuse.  loss_q reaches 2^64 after 2^24 rows at the
+ *         clamp and after 2^34 rows of losses below 64; bin_conf_q after 2^32 rows.
+ * Refused (-1, the text names the argument): B < 1 or above 2^26 - 4 (one wavefront per row); C < 1; R or n_bins outside
+ * 1 ... 1024; keep_confusion with C > 4096 (the matrix alone would be 128 MiB of state).
+ * logits [B][C] fp32, labels [B] int32; row_pred_out / row_rank_out int32 [B] and row_conf_out / row_loss_out fp32 [B] are optional
+ * (NULL skips them).  Every pointer is walked element by element: logits, labels and the four row outputs need their element size
+ * (4), state the size of a uint64 counter (8).
+ * The host form is the same accumulation compiled for the CPU (host pointers, no stream, B = 0 allowed): it computes pred and rank
+ * from the logits itself, while row_conf_host and row_loss_host are INPUTS - the device's own values, so that the two states can be
+ * compared word for word; it refuses a counted row whose conf is outside [0, 1] or whose loss is negative or NaN, with the
+ * state untouched. */
+size_t frmap_classify_tally_words(int C, int R, int n_bins, int keep_confusion);
+int frmap_classify_tally(const float* logits, const int32_t* labels, int B, int C, int R, int n_bins, int keep_confusion,
+                         uint64_t* state, int32_t* row_pred_out, int32_t* row_rank_out, float* row_conf_out, float* row_loss_out,
+                         void* stream);
+int frmap_classify_tally_host(const float* logits_host, const int32_t* labels_host, int B, int C, int R, int n_bins,
+                              int keep_confusion, uint64_t* state_host, int32_t* row_pred_host, int32_t* row_rank_host,
+                              const float* row_conf_host, const float* row_loss_host);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
