@@ -11,7 +11,9 @@
 * Siamese verification — `src/testing.py:170-177`: ``dist = pairwise_distance(out1, out2)``,
   ``pred = dist < 0.5``;
 * the accumulate step of that loop and the metric block of `src/advanced_metrics.py` from exact integers kept on the device —
-  `ClassificationTally`, `evaluate_stream`, `metrics_from_tally` (one launch per batch, no copy, one synchronisation at the end).
+  `ClassificationTally`, `evaluate_stream`, `metrics_from_tally` (one launch per batch, no copy, one synchronisation at the end);
+* the one-vs-rest ROC AUC and average precision of that metric block (`testing.py:296-312`, `advanced_metrics.py:85-100`) from
+  exact pair counts over a score store kept on the device - `OvrScores`, `ovr_rank_rule`, `ovr_metrics`, `evaluate_stream(auc=True)`.
 """
 from __future__ import annotations
 
@@ -484,7 +486,8 @@ def metrics_from_tally(counts: dict, class_names: Optional[Sequence[str]] = None
       from ranks - 1 on);
     * ``loss``: the PER-SAMPLE mean of the fp32 row losses (from the 2^-24 fixed point).  `evaluate_model`'s ``test_loss`` is the
       mean of the batch means (`testing.py:275-276,327`): the two differ when the last batch is short;
-    * ``per_class``: `advanced_metrics.calculate_per_class_metrics`'s fields except ``roc_auc`` (which needs every score), for
+    * ``per_class``: `advanced_metrics.calculate_per_class_metrics`'s fields except ``roc_auc``, which is no function of these
+      counts (`ovr_metrics` gives it, and `evaluate_stream(auc=True)` puts it here), for
       every class 0 ... C - 1 (the reference, through sklearn, numbers only the classes that occur in the labels or predictions);
     * ``confusion``: `advanced_metrics.create_enhanced_confusion_matrix`'s dict (``misclassified_to``: the top 3 by fraction,
       ties in class order), None where the matrix was not kept;
@@ -587,27 +590,35 @@ class ClassificationTally:
 
 def evaluate_stream(model, model_type: str, test_data, num_classes: Optional[int] = None, class_names: Optional[Sequence[str]] = None,
                     batch_size: int = 32, ranks: int = 6, n_bins: int = 10,
-                    arcface_classifier: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, device="cuda") -> dict:
+                    arcface_classifier: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, device="cuda", auc: bool = False) -> dict:
     """The loop of `evaluate_model` with a `ClassificationTally` in place of the host lists: every batch is forward -> one
     `ops.classify_tally` launch, nothing is copied back and nothing waits until the single synchronisation at the end.
     ``test_data``, ``arcface_classifier`` and the arcface logits (cosine against the class centres, or the given classifier) are
     `evaluate_model`'s; ``num_classes`` defaults to the width of the first batch's logits.  Returns `metrics_from_tally`'s dict.
-    The one-vs-rest ROC / PR AUCs are NOT returned - they need every score of every sample: use `evaluate_model` for those, and for
-    the reference's JSON files.  ``model_type == 'siamese'`` raises ``ValueError`` (pairs are `verification_metrics`' business)."""
+    ``auc=True`` adds the one-vs-rest ROC AUC and average precision of `evaluate_model`'s metric block: every batch then also runs
+    `ops.softmax_argmax` and appends the probabilities - the bits `evaluate_model` copies to the host - to an `OvrScores` store on
+    the device (two more launches a batch, still no copy and no wait; the store's capacity is the folder's sample count where that
+    is known), and the returned dict gains ``roc_auc`` and ``pr_auc`` (`ovr_metrics`: NaN where a class has no sample, as
+    `evaluate_model` reports) and ``roc_auc`` / ``average_precision`` inside every ``per_class`` entry.  The store declines a row
+    on its probabilities, the tally on its logits: a row with a -inf logit has finite probabilities and is counted by the store
+    alone.  ``auc=False``: no extra launch, the same dict as ever.  `evaluate_model` remains the way to the reference's JSON files.
+    ``model_type == 'siamese'`` raises ``ValueError`` (pairs are `verification_metrics`' business)."""
     import os
     if model_type == 'siamese':
         raise ValueError("evaluate_stream tallies classifications; siamese pairs go through evaluate_model or verification_metrics")
+    known_rows = None
     if isinstance(test_data, (str, os.PathLike)):
         samples, classes = image_folder(str(test_data))
         if not samples:
             raise FileNotFoundError(f"Found 0 files in subfolders of: {test_data}")
         class_names = list(classes) if class_names is None else list(class_names)
         batches = _folder_batches(samples, batch_size, device)
+        known_rows = len(samples)
     else:
         batches = iter(test_data)
     if model.training:
         model.eval()
-    tally = None
+    tally = ovr = None
     with torch.no_grad():
         for images, labels in batches:
             images = images.to(device)
@@ -625,9 +636,188 @@ def evaluate_stream(model, model_type: str, test_data, num_classes: Optional[int
                 tally = ClassificationTally(int(outputs.shape[1]) if num_classes is None else int(num_classes), ranks, n_bins,
                                             device=outputs.device)
             tally.update(outputs, labels)
+            if auc:
+                if ovr is None:
+                    ovr = OvrScores(tally.num_classes, OVR_DEFAULT_CAPACITY if known_rows is None else known_rows, device=outputs.device)
+                ovr.update(ops.softmax_argmax(outputs)[0], labels)
     if tally is None:
         raise ValueError("evaluate_stream: the test set is empty")
-    return tally.metrics(class_names)                                          # the one synchronisation: the state's copy to the host
+    m = tally.metrics(class_names)                                             # the one synchronisation: the state's copy to the host
+    if auc:
+        o = ovr.metrics(class_names)                                           # (and the one copy of the counts)
+        m["roc_auc"], m["pr_auc"] = o["roc_auc"], o["pr_auc"]
+        for name, entry in m["per_class"].items():
+            entry["roc_auc"], entry["average_precision"] = o["per_class"][name]["roc_auc"], o["per_class"][name]["average_precision"]
+    return m
+
+
+# ------------------------------------------------------------------------------------------------
+# One-vs-rest ROC AUC and average precision (`src/testing.py:296-312`: ``roc_auc_score(multi_class='ovr')`` and
+# ``average_precision_score``; the per-class ``roc_auc`` of `src/advanced_metrics.py:85-100`) without a sort and without the
+# scores on the host.  Every counted row is a positive of exactly one class, its own label; three integers per row - how many
+# rows of its class, and of the other classes, score at least as high in that class's column, and how many of the others tie
+# with it - decide both curves for that class.  The device keeps the scores (`OvrScores`, `ops.ovr_append`) and counts the pairs
+# (`ops.ovr_rank_counts`); the rule below is the specification, csrc/ovr_rule.h what the kernel and its host twin compile.
+# ------------------------------------------------------------------------------------------------
+OVR_DEFAULT_CAPACITY = 4096
+
+
+def ovr_stored_labels(scores, labels) -> np.ndarray:
+    """The label a score store keeps for each row of ``scores`` ``[N, C]``: the label if it lies in ``[0, C)`` and every score of
+    the row is finite; -1 for a label outside the range, whatever the scores are; -2 for a NaN or an infinity under a valid label
+    (the tally's two kinds of declined row)."""
+    z = np.asarray(scores, dtype=np.float32)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    out = np.where((y < 0) | (y >= z.shape[1]), -1, y)
+    out[(out >= 0) & ~np.isfinite(z).all(axis=1)] = -2
+    return out.astype(np.int32)
+
+
+def ovr_rank_rule(scores, labels):
+    """THE COUNTING RULE in numpy, on ``scores`` float32 ``[N, C]`` (row-major) and ``labels`` ``[N]``: returns
+    ``(ge_same, ge_other, eq_other, why)``, three uint64 ``[N]`` arrays and an int8 one.  ``why`` 1: the label is outside
+    ``[0, C)`` (a stored -1 or -2 lands here too); 2: a score of the row is NaN or infinite; 0: counted.  For a counted row i with
+    label y_i and ``s_i = scores[i, y_i]``, over the counted rows j (j == i included):
+
+    * ``ge_same[i]``  = #{j : y_j == y_i and scores[j, y_i] >= s_i} (so >= 1),
+    * ``ge_other[i]`` = #{j : y_j != y_i and scores[j, y_i] >= s_i},
+    * ``eq_other[i]`` = #{j : y_j != y_i and scores[j, y_i] == s_i}.
+
+    A declined row gets 0, 0, 0 and takes part in nobody's count.  fp32 IEEE comparisons (-0.0 equals +0.0, a denormal is not
+    zero): exact integers that do not depend on the order of the rows or on how they were split into appends."""
+    z = np.asarray(scores, dtype=np.float32)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    N, C = z.shape
+    why = np.zeros(N, np.int8)
+    why[(y < 0) | (y >= C)] = 1
+    why[(why == 0) & ~np.isfinite(z).all(axis=1)] = 2
+    ok = why == 0
+    ge_same, ge_other, eq_other = (np.zeros(N, np.uint64) for _ in range(3))
+    for c in np.unique(y[ok]):
+        pos = np.nonzero(ok & (y == c))[0]
+        same, other = z[pos, c], z[ok & (y != c), c]
+        for lo in range(0, len(pos), 1024):                                   # (1024 positives at a time bound the temporaries)
+            s = same[lo:lo + 1024, None]
+            ge_same[pos[lo:lo + 1024]] = (same[None, :] >= s).sum(axis=1)
+            ge_other[pos[lo:lo + 1024]] = (other[None, :] >= s).sum(axis=1)
+            eq_other[pos[lo:lo + 1024]] = (other[None, :] == s).sum(axis=1)
+    return ge_same, ge_other, eq_other, why
+
+
+def ovr_metrics(labels, ge_same, ge_other, eq_other, num_classes: int, class_names: Optional[Sequence[str]] = None) -> dict:
+    """Float64 one-vs-rest metrics from the integers of `ovr_rank_rule` / `ops.ovr_rank_counts` and the STORED labels
+    (`ovr_stored_labels`: -1 ignored, -2 non-finite; any other value outside ``[0, num_classes)`` reads as ignored).  With P_c
+    positives and N_c = rows - P_c negatives of class c:
+
+    * ``roc_auc[c] = (sum_i (N_c - ge_other[i]) + 1/2 sum_i eq_other[i]) / (P_c N_c)`` over the positives i of c - the
+      Mann-Whitney form of the trapezoid under ``roc_curve``, ties at one half - NaN if P_c == 0 or N_c == 0.  Both sums are
+      integers; the quotient is rounded once;
+    * ``average_precision[c] = (sum_i ge_same[i] / (ge_same[i] + ge_other[i])) / P_c`` - sklearn's step-wise sum: positives that
+      share a threshold each contribute that threshold's precision - NaN if P_c == 0.  The sum runs in row order.
+
+    Returns ``per_class`` ``{name: {roc_auc, average_precision, support}}`` for every class 0 ... C - 1, ``roc_auc`` and ``pr_auc``,
+    the plain means over all C classes - ``roc_auc_score(multi_class='ovr')`` and the multiclass ``average_precision_score`` - each
+    NaN as soon as one class has no defined value (sklearn raises there, and `evaluate_model` reports NaN), and ``rows`` /
+    ``ignored`` / ``nonfinite``."""
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    C = int(num_classes)
+    a, b, e = (np.asarray(v).reshape(-1).astype(np.uint64) for v in (ge_same, ge_other, eq_other))   # (int64 words wrap back)
+    if not (len(a) == len(b) == len(e) == len(y)):
+        raise ValueError(f"ovr_metrics: {len(y)} labels and {len(a)}, {len(b)}, {len(e)} counts")
+    names = [str(i) for i in range(C)] if class_names is None else list(class_names)
+    counted = np.nonzero((y >= 0) & (y < C))[0]
+    rows, nonfinite = len(counted), int((y == -2).sum())
+    order = counted[np.argsort(y[counted], kind="stable")]                    # by class, in row order inside a class
+    support = np.bincount(y[counted], minlength=C)
+    ends = np.cumsum(support)
+    nan = float("nan")
+    roc, ap = np.full(C, nan), np.full(C, nan)
+    for c in range(C):
+        P, Nn = int(support[c]), rows - int(support[c])
+        if P == 0:
+            continue
+        i = order[ends[c] - P: ends[c]]
+        ga, gb = a[i].astype(np.float64), b[i].astype(np.float64)
+        ap[c] = float(np.cumsum(ga / (ga + gb))[-1]) / P                      # (cumsum adds in order)
+        if Nn:
+            below = P * Nn - int(b[i].sum(dtype=np.uint64))                   # (integer sums, each at most P_c N_c)
+            roc[c] = (2 * below + int(e[i].sum(dtype=np.uint64))) / (2 * P * Nn)   # (Python integers: one rounding)
+    per_class = {names[c]: {"roc_auc": float(roc[c]), "average_precision": float(ap[c]), "support": int(support[c])}
+                 for c in range(min(C, len(names)))}
+    return {"rows": rows, "ignored": len(y) - rows - nonfinite, "nonfinite": nonfinite, "per_class": per_class,
+            "roc_auc": float(np.cumsum(roc)[-1] / C) if C and not np.isnan(roc).any() else nan,
+            "pr_auc": float(np.cumsum(ap)[-1] / C) if C and not np.isnan(ap).any() else nan}
+
+
+class OvrScores:
+    """A device-resident score store: `update` appends a batch of scores and labels in one launch (`ops.ovr_append`) with no copy
+    to the host and no synchronisation; `rank_counts` / `metrics` run the one count (`ops.ovr_rank_counts`) and make the one
+    device-to-host copy at the end.  The store is ``[num_classes, capacity]`` float32, class-major; past the capacity it grows by
+    doubling, with a device copy of the rows held.  4 ``num_classes`` bytes per row: 100 000 rows of 36 classes are 14 MB, of
+    10 000 classes 4 GB."""
+
+    def __init__(self, num_classes: int, capacity: int = OVR_DEFAULT_CAPACITY, device="cuda"):
+        self.num_classes, self.rows = int(num_classes), 0
+        if self.num_classes < 1 or int(capacity) < 1:
+            raise ValueError(f"OvrScores: num_classes = {num_classes} and capacity = {capacity} must be at least 1")
+        self.store = torch.empty((self.num_classes, int(capacity)), dtype=torch.float32, device=device)
+        self.labels = torch.empty((int(capacity),), dtype=torch.int32, device=device)
+
+    @property
+    def capacity(self) -> int:
+        return int(self.labels.shape[0])
+
+    def _reserve(self, rows: int) -> None:
+        if rows <= self.capacity:
+            return
+        cap = max(2 * self.capacity, rows)
+        store = torch.empty((self.num_classes, cap), dtype=torch.float32, device=self.store.device)
+        labels = torch.empty((cap,), dtype=torch.int32, device=self.store.device)
+        store[:, :self.rows] = self.store[:, :self.rows]
+        labels[:self.rows] = self.labels[:self.rows]
+        self.store, self.labels = store, labels
+
+    def update(self, scores: torch.Tensor, labels) -> "OvrScores":
+        """Append ``scores`` float32 ``[B, C]`` (on the store's device) and ``labels`` ``[B]`` (any integer tensor or sequence; a
+        label outside ``[0, C)`` declines its row, and so does a non-finite score).  No synchronisation; an empty batch is a no-op."""
+        if scores.dim() != 2 or scores.shape[1] != self.num_classes:
+            raise ValueError(f"OvrScores.update: scores {tuple(scores.shape)} for {self.num_classes} classes")
+        B = int(scores.shape[0])
+        if B == 0:
+            return self
+        labels = torch.as_tensor(labels)
+        if labels.dtype != torch.int32:                                        # (a wide label must not wrap into the range)
+            labels = labels.to(torch.int64).clamp(-1, self.num_classes).to(torch.int32)
+        self._reserve(self.rows + B)
+        ops.ovr_append(scores, labels.to(self.store.device, non_blocking=True), self.store, self.labels, self.rows)
+        self.rows += B
+        return self
+
+    def merge(self, other: "OvrScores") -> "OvrScores":
+        """The rows of both, this store's first (another rank's or another shard's store; a device copy)."""
+        if other.num_classes != self.num_classes:
+            raise ValueError(f"OvrScores.merge: {self.num_classes} and {other.num_classes} classes")
+        n = other.rows
+        self._reserve(self.rows + n)
+        self.store[:, self.rows:self.rows + n] = other.store[:, :n].to(self.store.device)
+        self.labels[self.rows:self.rows + n] = other.labels[:n].to(self.store.device)
+        self.rows += n
+        return self
+
+    def reset(self) -> "OvrScores":
+        self.rows = 0
+        return self
+
+    def rank_counts(self):
+        """One count and the one device-to-host copy: ``(stored labels int32, ge_same, ge_other, eq_other uint64)`` of the rows held."""
+        if self.rows == 0:
+            return (np.zeros(0, np.int32),) + tuple(np.zeros(0, np.uint64) for _ in range(3))
+        counts = ops.ovr_rank_counts(self.store, self.labels, self.rows)
+        host = torch.stack((self.labels[:self.rows].to(torch.int64),) + tuple(counts)).cpu().numpy()
+        return (host[0].astype(np.int32),) + tuple(host[k].view(np.uint64) for k in (1, 2, 3))
+
+    def metrics(self, class_names: Optional[Sequence[str]] = None) -> dict:
+        return ovr_metrics(*self.rank_counts(), self.num_classes, class_names)
 
 
 # ------------------------------------------------------------------------------------------------

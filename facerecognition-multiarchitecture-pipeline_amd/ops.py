@@ -613,6 +613,75 @@ def classify_tally_host(logits, labels, row_conf, row_loss, state: Optional[np.n
     return state, pred, rank
 
 
+# ------------------------------------------------------------------------------------------------
+# one-vs-rest rank counts (`frmap_ovr_*`, csrc/ovr_rank.hip; the rule is `evaluate.ovr_rank_rule`)
+# ------------------------------------------------------------------------------------------------
+OVR_IGNORED, OVR_NONFINITE = -1, -2         # the stored label of a declined row
+
+
+def _ovr_store(what: str, entry: str, store: torch.Tensor, store_labels: torch.Tensor, written: bool):
+    """A score store as the library takes it, and its ``(C, capacity)``: ``store`` float32 ``[C, capacity]`` class-major,
+    ``store_labels`` int32 ``[capacity]``.  A store the call writes must be contiguous and aligned as it stands."""
+    if written and not (isinstance(store, torch.Tensor) and isinstance(store_labels, torch.Tensor) and store.is_contiguous()
+                        and store_labels.is_contiguous()):
+        raise ValueError(f"{what}: store and store_labels are written in place and must be contiguous tensors")
+    store = _dev(store, f"{what}.store", torch.float32, (entry, "store"), owned=written)
+    store_labels = _dev(store_labels, f"{what}.store_labels", torch.int32, (entry, "store_labels"), owned=written)
+    if store.dim() != 2 or store_labels.dim() != 1 or store_labels.shape[0] != store.shape[1] or store.shape[0] < 1:
+        raise ValueError(f"{what}: store [C, capacity] and store_labels [capacity] expected, got {tuple(store.shape)} and "
+                         f"{tuple(store_labels.shape)}")
+    return store, store_labels, int(store.shape[0]), int(store.shape[1])
+
+
+def ovr_append(scores: torch.Tensor, labels: torch.Tensor, store: torch.Tensor, store_labels: torch.Tensor, first: int) -> None:
+    """Append a batch to a score store in one launch on the current stream (`frmap_ovr_append`; nothing is copied back or
+    synchronised).  ``scores`` float32 ``[B, C]``, ``labels`` int32 ``[B]``; ``store`` float32 ``[C, capacity]`` (class-major) and
+    ``store_labels`` int32 ``[capacity]`` are written in place at rows ``[first, first + B)``: ``store[c, first + b] = scores[b, c]``,
+    ``store_labels[first + b]`` = the label, or -1 for a label outside ``[0, C)``, or -2 for a non-finite score under a valid label."""
+    keep = []
+    store, store_labels, Cc, cap = _ovr_store("ovr_append", "frmap_ovr_append", store, store_labels, True)
+    ps = _ptr(keep, scores, "ovr_append.scores", torch.float32, ("frmap_ovr_append", "scores"))
+    pl = _ptr(keep, labels, "ovr_append.labels", torch.int32, ("frmap_ovr_append", "labels"))
+    scores, labels = keep
+    if scores.dim() != 2 or labels.dim() != 1 or labels.shape[0] != scores.shape[0] or scores.shape[1] != Cc:
+        raise ValueError(f"ovr_append: scores [B, {Cc}] and labels [B] expected, got {tuple(scores.shape)} and {tuple(labels.shape)}")
+    _lib.check(_lib.load().frmap_ovr_append(ps, pl, int(scores.shape[0]), Cc, store.data_ptr(), store_labels.data_ptr(), cap, int(first),
+                                            _stream()), "ovr_append")
+
+
+def ovr_rank_counts(store: torch.Tensor, store_labels: torch.Tensor, n: int):
+    """The three exact integers of every row ``i < n`` of a score store (`frmap_ovr_rank_counts`: memsets and one launch on the
+    current stream, no synchronisation): ``(ge_same, ge_other, eq_other)``, int64 ``[n]`` each (uint64 words) - over the counted
+    rows j < n, those of i's class (i included) / of another class whose score in i's class column is >= i's, and those of another
+    class whose score there equals i's.  A declined row (stored label < 0) gets 0, 0, 0 and takes part in nobody's count."""
+    # (a non-contiguous store is copied by `_dev`; the copies live in these names until the launch is enqueued)
+    store, store_labels, Cc, cap = _ovr_store("ovr_rank_counts", "frmap_ovr_rank_counts", store, store_labels, False)
+    n = int(n)
+    if not 0 <= n <= cap:
+        raise ValueError(f"ovr_rank_counts: n = {n} rows of a store of capacity {cap}")
+    out = tuple(torch.empty((n,), dtype=torch.int64, device=store.device) for _ in range(3))
+    if n:
+        _lib.check(_lib.load().frmap_ovr_rank_counts(store.data_ptr(), store_labels.data_ptr(), n, cap, Cc, out[0].data_ptr(),
+                                                     out[1].data_ptr(), out[2].data_ptr(), _stream()), "ovr_rank_counts")
+    return out
+
+
+def ovr_rank_counts_host(store, store_labels, n: Optional[int] = None):
+    """`ovr_rank_counts` on the CPU over numpy arrays (`frmap_ovr_rank_counts_host`: the kernel's rule header compiled for the
+    host; no GPU).  ``store`` float32 ``[C, capacity]``, ``store_labels`` int32 ``[capacity]``; ``n`` defaults to the capacity.
+    Returns ``(ge_same, ge_other, eq_other)`` as uint64 ``[n]`` arrays."""
+    store = np.ascontiguousarray(store, dtype=np.float32)
+    store_labels = np.ascontiguousarray(store_labels, dtype=np.int32)
+    if store.ndim != 2 or store.shape[0] < 1 or store_labels.shape != (store.shape[1],):
+        raise ValueError("ovr_rank_counts_host: store [C, capacity] and store_labels [capacity] expected")
+    Cc, cap = store.shape
+    n = cap if n is None else int(n)
+    out = tuple(np.empty((max(n, 0),), np.uint64) for _ in range(3))
+    _lib.check(_lib.load().frmap_ovr_rank_counts_host(store.ctypes.data if cap else None, store_labels.ctypes.data if cap else None, n, cap,
+                                                      Cc, *(o.ctypes.data if n > 0 else None for o in out)), "ovr_rank_counts_host")
+    return out
+
+
 def _workspace(B: int, Cc: int, device) -> torch.Tensor:
     n = _lib.load().frmap_head_workspace_bytes(B, Cc)
     return torch.empty(((n + 15) // 16) * 2, dtype=torch.int64, device=device)
@@ -1300,7 +1369,8 @@ for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_sma
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
               "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
-              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse", "classify_tally"):
+              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse", "classify_tally",
+              "ovr_append", "ovr_rank_counts"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
 

@@ -587,6 +587,50 @@ int frmap_classify_tally_host(const float* logits_host, const int32_t* labels_ho
                               int keep_confusion, uint64_t* state_host, int32_t* row_pred_host, int32_t* row_rank_host,
                               const float* row_conf_host, const float* row_loss_host);
 
+/* One-vs-rest rank counts: the exact one-vs-rest ROC AUC and average precision of the reference's metric block
+ * (src/testing.py:296-312: roc_auc_score(multi_class='ovr'), average_precision_score) and the per-class roc_auc of
+ * src/advanced_metrics.py:85-100, without a sort and without a copy of the scores to the host.  Every batch is appended to a
+ * score store on the device; one count at the end gives every row three exact integers, from which the host derives both
+ * curves' areas in float64 (evaluate.ovr_metrics).
+ *
+ * The score store, caller-owned: store = fp32 [C][capacity], CLASS-MAJOR (the count streams column c for all positives of c, and
+ * that read must be contiguous); store_labels = int32 [capacity].  capacity and first are 64-bit and all index arithmetic is.
+ * frmap_ovr_append writes rows [first, first + B): store[c * capacity + first + b] = scores[b][c] (transposed through LDS: the
+ * read and the write are both coalesced) and store_labels[first + b] =
+ *   the label : if it lies in [0, C) and every score of the row is finite;
+ *   -1        : for a label outside [0, C), whatever the scores are;
+ *   -2        : for a NaN, +inf or -inf among the scores of a row whose label is in range.
+ * These are the two kinds of declined row of frmap_classify_tally, so rows / ignored / nonfinite agree with a tally fed the same
+ * batches.  Nothing outside rows [first, first + B) of the C columns and of the labels is written.
+ * Refused (-1, the text names the argument): B < 1 or above 2^26 - 4; C < 1; first < 0; first + B > capacity.
+ *
+ * frmap_ovr_rank_counts, over rows [0, n) of the store.  A row with a stored label in [0, C) is COUNTED.  A counted row i is a
+ * positive of exactly one class, y_i; with s_i = store[y_i][i], over the counted rows j < n (j == i included):
+ *   ge_same[i]  = #{ j : y_j == y_i and store[y_i][j] >= s_i }      (>= 1)
+ *   ge_other[i] = #{ j : y_j != y_i and store[y_i][j] >= s_i }
+ *   eq_other[i] = #{ j : y_j != y_i and store[y_i][j] == s_i }
+ * A declined row gets 0, 0, 0 and takes part in nobody's count.  The comparisons are IEEE fp32 comparisons made AS FLOATS WITH
+ * DENORMALS HONOURED (no integer key): -0.0 equals +0.0, a denormal is not zero, NaN compares false.  With P_c positives and
+ * N_c = rows - P_c negatives of class c, in float64 on the host:
+ *   roc_auc[c]           = (sum_{i in c} (N_c - ge_other[i]) + 1/2 sum_{i in c} eq_other[i]) / (P_c N_c)
+ *   average_precision[c] = (sum_{i in c} ge_same[i] / (ge_same[i] + ge_other[i])) / P_c
+ * - the Mann-Whitney form of the trapezoid under roc_curve with ties at one half, and sklearn's step-wise sum.
+ * ge_same_out / ge_other_out / eq_other_out: uint64 [n] each.  The call writes every word of [0, n) itself (three memset nodes,
+ * then one kernel that adds with 64-bit integer atomics; no floating-point atomic): the caller does not pre-zero them.  Exact
+ * integers: the same store gives the same words on every run, whatever the split into appends; rows in another order give the
+ * same integers per row.  n^2 comparisons whatever C is.  No scratch, nothing allocated or synchronised.
+ * Refused (-1, the text names the argument): n < 1 or above 2^31 - 1; n > capacity; C < 1 or above 2^24 - 1 (one workgroup per
+ * class and segment).
+ * Every pointer is walked element by element: scores, labels, store and store_labels need their element size (4), ge_same_out,
+ * ge_other_out and eq_other_out the size of a uint64 counter (8).
+ * The host form is the same count compiled for the CPU (host pointers, no stream, n = 0 allowed). */
+int frmap_ovr_append(const float* scores, const int32_t* labels, int B, int C, float* store, int32_t* store_labels,
+                     long long capacity, long long first, void* stream);
+int frmap_ovr_rank_counts(const float* store, const int32_t* store_labels, long long n, long long capacity, int C,
+                          uint64_t* ge_same_out, uint64_t* ge_other_out, uint64_t* eq_other_out, void* stream);
+int frmap_ovr_rank_counts_host(const float* store_host, const int32_t* store_labels_host, long long n, long long capacity, int C,
+                               uint64_t* ge_same_host, uint64_t* ge_other_host, uint64_t* eq_other_host);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
