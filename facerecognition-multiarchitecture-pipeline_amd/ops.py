@@ -32,7 +32,9 @@ def _on_operand_device(fn):
     @functools.wraps(fn)
     def guarded(*args, **kwargs):
         dev = None
-        for v in args:
+        for v in args + tuple(kwargs.values()):
+            if isinstance(v, MatchPack):           # (a prepared gallery is an operand too: its buffers are what the kernel reads)
+                v = getattr(v, "packed", None)     # (None inside its own constructor)
             if isinstance(v, torch.Tensor) and v.is_cuda:
                 if dev is None:
                     dev = v.device
@@ -49,7 +51,8 @@ def _dev(t: torch.Tensor, what: str, dtype=None, arg=None, owned: bool = False) 
     """A tensor as the library takes it: on the GPU, of ``dtype``, contiguous and aligned as the header asks of ``arg`` =
     ``(entry point, argument)`` of `_lib.ALIGNMENT` (no ``arg``: 16 bytes, the most any operand needs).  An operand that is not
     contiguous or starts below that alignment - a view with a storage offset such as ``flat[1:]``, a row slice of a ``[B, 35]`` matrix -
-    is copied; ``owned`` (a tensor the call writes: a state, a caller-supplied output) cannot be, and raises ``ValueError``."""
+    is copied; ``owned`` (a tensor the call writes: a state, a caller-supplied output) cannot be - the update would land in the copy -
+    and raises ``ValueError`` in either case."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
     if not t.is_cuda:
@@ -61,7 +64,26 @@ def _dev(t: torch.Tensor, what: str, dtype=None, arg=None, owned: bool = False) 
         if owned:
             raise ValueError(f"{what}: a tensor the call writes must be {need}-byte aligned (data_ptr() % {need} = {t.data_ptr() % need})")
         return t.clone(memory_format=torch.contiguous_format)
-    return t if t.is_contiguous() else t.contiguous()
+    if t.is_contiguous():
+        return t
+    if owned:
+        raise ValueError(f"{what}: a tensor the call writes must be contiguous (shape {tuple(t.shape)}, strides {tuple(t.stride())}): "
+                         f"a copy would take the update")
+    return t.contiguous()
+
+
+def _sized(t, op: str, name: str, shape, dtype=None) -> None:
+    """Check an operand whose extent the library takes from ANOTHER operand's shape or from a scalar argument (a shift of ``Cout``
+    values, a ``pos`` of ``[L, D]``): the library sees a bare pointer and would read past the end of a short one.  A tensor on the
+    GPU (``RuntimeError``) of ``dtype`` (``TypeError``) and exactly ``shape`` (``ValueError``), before any pointer is taken."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{op}: {name}: expected a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{op}: {name} is on {t.device}; the HIP path needs GPU tensors (no CPU fallback)")
+    if dtype is not None and t.dtype != dtype:
+        raise TypeError(f"{op}: {name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(int(v) for v in shape):
+        raise ValueError(f"{op}: {name} must be {list(int(v) for v in shape)}, got {list(t.shape)}")
 
 
 def _ptr(keep: list, t: torch.Tensor, what: str, dtype=None, arg=None) -> int:
@@ -128,6 +150,8 @@ def conv_small_cin(x4: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cou
     if C != 4:
         raise ValueError("conv_small_cin: input must be NHWC4")
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    _sized(wpk, "conv_small_cin", "wpk", (Cout * _lib.load().frmap_small_cin_kpad(k, k),), x4.dtype)     # (`pack_conv_weight_c3`'s rows)
+    _sized(shift, "conv_small_cin", "shift", (Cout,), torch.float32)
     out = torch.empty((B, Ho, Wo, Cout), dtype=x4.dtype, device=x4.device)
     _lib.check(_lib.load().frmap_conv_small_cin(x4.data_ptr(), _ptr(keep, wpk, "wpk"),
                                                 _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
@@ -145,7 +169,9 @@ def conv_small_cin_pool2(x4: torch.Tensor, wpk: torch.Tensor, shift: torch.Tenso
         raise ValueError("conv_small_cin_pool2: input must be NHWC4")
     if H % 2 or W % 2:
         raise ValueError("conv_small_cin_pool2: H and W must be even")
-    out = torch.empty((B, H // 2, W // 2, Cout), dtype=x4.dtype, device=x4.device)
+    _sized(wpk, "conv_small_cin_pool2", "wpk", (Cout * _lib.load().frmap_small_cin_kpad(3, 3),), x4.dtype)
+    _sized(shift, "conv_small_cin_pool2", "shift", (Cout,), torch.float32)
+    out =torch.empty((B, H // 2, W // 2, Cout), dtype=x4.dtype, device=x4.device)
     _lib.check(_lib.load().frmap_conv_small_cin_pool2(x4.data_ptr(), _ptr(keep, wpk, "wpk"),
                                                       _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                       B, H, W, Cout, int(relu), dt_code(x4.dtype), _stream()),
@@ -171,8 +197,10 @@ def stem7x7_maxpool(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, dty
         Hq, Wq = stem_pool_dims(H, W)
     else:
         Hq, Wq = ((H + 6 - 7) // 2 + 1) // 2, ((W + 6 - 7) // 2 + 1) // 2
+    _sized(wpk, "stem7x7_maxpool", "wpk", (64 * _lib.load().frmap_small_cin_kpad(7, 7),), dtype)
+    _sized(shift, "stem7x7_maxpool", "shift", (64,), torch.float32)
     out = torch.empty((B, Hq, Wq, 64), dtype=dtype, device=x.device)
-    fn = _lib.load().frmap_stem7x7_maxpool if pool3 else _lib.load().frmap_stem7x7_maxpool2
+    fn =_lib.load().frmap_stem7x7_maxpool if pool3 else _lib.load().frmap_stem7x7_maxpool2
     _lib.check(fn(x.data_ptr(), _ptr(keep, wpk, "wpk", dtype),
                                                  _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
                                                  B, H, W, dt_code(dtype), _stream()), "stem7x7_maxpool")
@@ -193,6 +221,8 @@ def stem7x7_maxpool_u8(x_u8: torch.Tensor, wpk: torch.Tensor, shift: torch.Tenso
         Hq, Wq = stem_pool_dims(H, W)
     else:
         Hq, Wq = ((H + 6 - 7) // 2 + 1) // 2, ((W + 6 - 7) // 2 + 1) // 2
+    _sized(wpk, "stem7x7_maxpool_u8", "wpk", (64 * _lib.load().frmap_small_cin_kpad(7, 7),), dtype)
+    _sized(shift, "stem7x7_maxpool_u8", "shift", (64,), torch.float32)
     out = torch.empty((B, Hq, Wq, 64), dtype=dtype, device=x_u8.device)
     m = (C.c_float * 3)(*[float(v) for v in mean])
     sd = (C.c_float * 3)(*[float(v) for v in std])
@@ -216,10 +246,8 @@ def conv_igemm(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout: in
         if tuple(residual.shape) != tuple(out.shape):
             raise ValueError(f"conv_igemm: residual shape {tuple(residual.shape)} != output {tuple(out.shape)}")
         res_ptr = residual.data_ptr()
-    if wpk.numel() != Cout * Cin * k * k or wpk.dtype != x.dtype:
-        raise ValueError("conv_igemm: packed weight does not match Cout*Cin*k*k / dtype")
-    if shift.numel() != Cout:
-        raise ValueError("conv_igemm: shift must have Cout elements")
+    _sized(wpk, "conv_igemm", "wpk", (Cout * Cin * k * k,), x.dtype)
+    _sized(shift, "conv_igemm", "shift", (Cout,), torch.float32)
     _lib.check(_lib.load().frmap_conv_igemm(x.data_ptr(), _ptr(keep, wpk, "wpk"),
                                             _ptr(keep, shift, "shift", torch.float32), res_ptr, out.data_ptr(),
                                             B, H, W, Cin, Cout, k, stride, pad, int(relu), dt_code(x.dtype),
@@ -283,10 +311,8 @@ def conv_igemm_pool2(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Co
     keep = []
     x = _dev(x, "conv_igemm_pool2.x")
     B, H, W, Cin = x.shape
-    if wpk.numel() != Cout * Cin * 9 or wpk.dtype != x.dtype:
-        raise ValueError("conv_igemm_pool2: packed weight does not match Cout*Cin*9 / dtype")
-    if shift.numel() != Cout:
-        raise ValueError("conv_igemm_pool2: shift must have Cout elements")
+    _sized(wpk, "conv_igemm_pool2", "wpk", (Cout * Cin * 9,), x.dtype)
+    _sized(shift, "conv_igemm_pool2", "shift", (Cout,), torch.float32)
     out = torch.empty((B, H // 2, W // 2, Cout), dtype=x.dtype, device=x.device)
     _lib.check(_lib.load().frmap_conv_igemm_pool2(x.data_ptr(), _ptr(keep, wpk, "wpk"),
                                                   _ptr(keep, shift, "shift", torch.float32), out.data_ptr(),
@@ -313,12 +339,15 @@ def conv_igemm_ds(x: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, Cout:
     keep = []
     x = _dev(x, "conv_igemm_ds.x")
     x_ds = _dev(x_ds, "conv_igemm_ds.x_ds", x.dtype)
+    if x.dim() != 4 or x_ds.dim() != 4:
+        raise ValueError(f"conv_igemm_ds: x and x_ds must be NHWC maps, got {list(x.shape)} and {list(x_ds.shape)}")
     B, H, W, Cin = x.shape
     Bd, Hd, Wd, Cd = x_ds.shape
-    if Bd != B or wpk.numel() != Cout * Cin * 9 or wpk_ds.numel() != Cout * Cd or wpk.dtype != x.dtype or wpk_ds.dtype != x.dtype:
-        raise ValueError("conv_igemm_ds: operand shapes / dtypes do not match")
-    if shift.numel() != Cout:
-        raise ValueError("conv_igemm_ds: shift must have Cout elements")
+    if Bd != B:
+        raise ValueError(f"conv_igemm_ds: x_ds holds {Bd} images, x {B}")
+    _sized(wpk, "conv_igemm_ds", "wpk", (Cout * Cin * 9,), x.dtype)
+    _sized(wpk_ds, "conv_igemm_ds", "wpk_ds", (Cout * Cd,), x.dtype)
+    _sized(shift, "conv_igemm_ds", "shift", (Cout,), torch.float32)
     out = torch.empty((B, H, W, Cout), dtype=x.dtype, device=x.device)
     _lib.check(_lib.load().frmap_conv_igemm_ds(x.data_ptr(), _ptr(keep, wpk, "wpk"),
                                                _ptr(keep, shift, "shift", torch.float32), x_ds.data_ptr(),
@@ -343,8 +372,8 @@ def linear_mfma(x2d: torch.Tensor, wpk: torch.Tensor, shift: torch.Tensor, N: in
         if tuple(residual.shape) != (M, N):
             raise ValueError("linear_mfma: residual must be [M, N]")
         rp = residual.data_ptr()
-    if wpk.numel() != N * K or wpk.dtype != x2d.dtype:
-        raise ValueError("linear_mfma: packed weight does not match N*K / dtype")
+    _sized(wpk, "linear_mfma", "wpk", (N * K,), x2d.dtype)
+    _sized(shift, "linear_mfma", "shift", (N,), torch.float32)
     _lib.check(lib.frmap_linear_mfma(x2d.data_ptr(), _ptr(keep, wpk, "wpk"), _ptr(keep, shift, "shift", torch.float32),
                                      rp, out.data_ptr(), ws.data_ptr() if ws is not None else 0, M, K, N, int(act),
                                      dt_code(x2d.dtype), _stream()), "linear_mfma")
@@ -384,11 +413,17 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] =
     keep = []
     x = _dev(x, "linear_f32.x", torch.float32)
     w = _dev(w, "linear_f32.w", torch.float32)
+    if x.dim() != 2 or w.dim() != 2:
+        raise ValueError(f"linear_f32: x [B, K] and w [N, K] expected, got {list(x.shape)} and {list(w.shape)}")
     B, K = x.shape
     N, K2 = w.shape
     if K != K2:
         raise ValueError(f"linear_f32: x is B×{K} but w is N×{K2}")
-    out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    if scale is not None:
+        _sized(scale, "linear_f32", "scale", (N,), torch.float32)
+    if shift is not None:
+        _sized(shift, "linear_f32", "shift", (N,), torch.float32)
+    out =torch.empty((B, N), dtype=torch.float32, device=x.device)
     sp = _ptr(keep, scale, "scale", torch.float32, ("frmap_linear_f32", "scale")) if scale is not None else 0
     hp = _ptr(keep, shift, "shift", torch.float32, ("frmap_linear_f32", "shift")) if shift is not None else 0
     _lib.check(_lib.load().frmap_linear_f32(x.data_ptr(), w.data_ptr(), sp, hp, out.data_ptr(), B, K, N, int(relu),
@@ -427,6 +462,10 @@ def add_pos_layernorm(x: torch.Tensor, pos: Optional[torch.Tensor], gamma: torch
     keep = []
     x = _dev(x, "add_pos_layernorm.x")
     B, L, D = x.shape
+    if pos is not None:
+        _sized(pos, "add_pos_layernorm", "pos", (L, D), torch.float32)
+    _sized(gamma, "add_pos_layernorm", "gamma", (D,), torch.float32)
+    _sized(beta, "add_pos_layernorm", "beta", (D,), torch.float32)
     y = torch.empty_like(x)
     t = torch.empty_like(x) if want_sum else None
     _lib.check(_lib.load().frmap_add_pos_layernorm(
@@ -439,8 +478,10 @@ def add_pos_layernorm(x: torch.Tensor, pos: Optional[torch.Tensor], gamma: torch
 
 def mha_tokens(qkv: torch.Tensor, H: int) -> torch.Tensor:
     qkv = _dev(qkv, "mha_tokens.qkv")
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise ValueError(f"mha_tokens: qkv must be [B, L, 3 D] (q | k | v), got {list(qkv.shape)}")
     B, L, D3 = qkv.shape
-    D = D3 // 3
+    D = D3 // 3          # (D = 128 H is the launcher's to refuse: it is given both)
     out = torch.empty((B, L, D), dtype=qkv.dtype, device=qkv.device)
     _lib.check(_lib.load().frmap_mha_tokens(qkv.data_ptr(), out.data_ptr(), B, L, D, H, dt_code(qkv.dtype), _stream()),
                "mha_tokens")
@@ -451,6 +492,8 @@ def mean_layernorm(t: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
     keep = []
     t = _dev(t, "mean_layernorm.t")
     B, L, D = t.shape
+    _sized(gamma, "mean_layernorm", "gamma", (D,), torch.float32)
+    _sized(beta, "mean_layernorm", "beta", (D,), torch.float32)
     out = torch.empty((B, D), dtype=torch.float32, device=t.device)
     _lib.check(_lib.load().frmap_mean_layernorm(t.data_ptr(), _ptr(keep, gamma, "gamma", torch.float32, ("frmap_mean_layernorm", "gamma")),
                                                 _ptr(keep, beta, "beta", torch.float32, ("frmap_mean_layernorm", "beta")), out.data_ptr(), B, L, D,
@@ -472,6 +515,8 @@ def cnn_attention(qkv: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, spati
     KS = sw.shape[-1]
     if sw.numel() != 2 * KS * KS:
         raise ValueError("cnn_attention: spatial_w must be [1][2][KS][KS]")
+    _sized(gamma, "cnn_attention", "gamma", (1,), torch.float32)
+    _sized(spatial_b, "cnn_attention", "spatial_b", (1,), torch.float32)
     om = torch.empty((B, H, W, C), dtype=x.dtype, device=x.device) if want_map else None
     op = torch.empty((B, C), dtype=torch.float32, device=x.device) if want_pool else None
     _lib.check(_lib.load().frmap_cnn_attention(qkv.data_ptr(), x.data_ptr(), _ptr(keep, gamma, "gamma", torch.float32, ("frmap_cnn_attention", "gamma")),
@@ -513,7 +558,7 @@ def pairwise_distance(a: torch.Tensor, b: torch.Tensor, thresh: Optional[float] 
     a = _dev(a, "pairwise_distance.a", torch.float32, ("frmap_pairwise_distance", "a"))
     b = _dev(b, "pairwise_distance.b", torch.float32, ("frmap_pairwise_distance", "b"))
     if a.shape != b.shape or a.dim() != 2:
-        raise ValueError("pairwise_distance: need two [B, D] tensors of the same shape")
+        raise ValueError(f"pairwise_distance: a and b must be two [B, D] tensors of the same shape, got {list(a.shape)} and {list(b.shape)}")
     B, D = a.shape
     dist = torch.empty((B,), dtype=torch.float32, device=a.device)
     same = torch.empty((B,), dtype=torch.int32, device=a.device) if thresh is not None else None
@@ -699,8 +744,8 @@ def _packed_buf(packed, B: int, device):
         return None
     if packed is True:
         return torch.empty((B, 2), dtype=torch.int32, device=device)
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.int32 and tuple(packed.shape) == (B, 2)
-            and packed.is_contiguous()):
+    _sized(packed, "match", "packed", (B, 2), torch.int32)
+    if not packed.is_contiguous():
         raise ValueError(f"packed output must be a contiguous int32 [{B}, 2] device tensor")
     return _dev(packed, "packed", torch.int32, ("frmap_match_top1", "packed_out"), owned=True)     # (caller-owned: never copied)
 
@@ -709,16 +754,19 @@ class MatchPack:
     """A gallery prepared for the MFMA match path (`frmap_match_pack_gallery`): the fp32 rows split into fp16 (hi, lo)
     pairs in the GEMM kernel's operand order, plus the per-row statistics of the expanded distance.  ``capacity`` > G
     leaves room for `update_rows` (incremental enrolment: only the touched 64-row tiles are re-packed)."""
-    __slots__ = ("packed", "stat_w", "G", "D", "capacity", "src_ptr", "src_version", "ready")
+    __slots__ = ("packed", "stat_w", "G", "D", "capacity", "src_ptr", "src_version", "src_stride", "ready")
 
     def __init__(self, gallery: torch.Tensor, capacity: Optional[int] = None):
-        gallery = _dev(gallery, "match_prepare.gallery", torch.float32, ("frmap_match_pack_gallery", "gallery"))
+        src, gallery = gallery, _dev(gallery, "match_prepare.gallery", torch.float32, ("frmap_match_pack_gallery", "gallery"))
+        if gallery.dim() != 2:
+            raise ValueError(f"match_prepare: gallery must be [G, D], got {list(gallery.shape)}")
         self.G, self.D = int(gallery.shape[0]), int(gallery.shape[1])
         self.capacity = max(int(capacity or 0), self.G)
         lib = _lib.load()
         self.packed = torch.empty((lib.frmap_match_gallery_pack_bytes(self.capacity, self.D),), dtype=torch.uint8, device=gallery.device)
         self.stat_w = torch.empty((self.capacity, 4), dtype=torch.float32, device=gallery.device)
-        self.src_ptr, self.src_version = gallery.data_ptr(), gallery._version
+        # (the CALLER's tensor is what `matches` recognises, not a copy `_dev` made of a strided or misaligned one)
+        self.src_ptr, self.src_version, self.src_stride = src.data_ptr(), src._version, tuple(src.stride())
         _lib.check(lib.frmap_match_pack_gallery(gallery.data_ptr(), self.packed.data_ptr(), self.stat_w.data_ptr(), self.G, self.D,
                                                 _stream()), "match_pack_gallery")
         self.ready = torch.cuda.Event()
@@ -726,14 +774,14 @@ class MatchPack:
 
     def update_rows(self, gallery: torch.Tensor, row_lo: int, row_hi: int) -> None:
         """``gallery`` (same storage, now G rows) had rows [row_lo, row_hi) appended or edited: re-pack those rows only."""
-        gallery = _dev(gallery, "match_update.gallery", torch.float32, ("frmap_match_pack_gallery_rows", "gallery"))
+        src, gallery = gallery, _dev(gallery, "match_update.gallery", torch.float32, ("frmap_match_pack_gallery_rows", "gallery"))
         G = int(gallery.shape[0])
-        if gallery.data_ptr() != self.src_ptr or gallery.shape[1] != self.D or G > self.capacity:
+        if src.data_ptr() != self.src_ptr or tuple(src.stride()) != self.src_stride or gallery.shape[1] != self.D or G > self.capacity:
             raise ValueError("MatchPack.update_rows: not the gallery storage this pack was built from (or beyond its capacity)")
         torch.cuda.current_stream().wait_event(self.ready)
         _lib.check(_lib.load().frmap_match_pack_gallery_rows(gallery.data_ptr(), self.packed.data_ptr(), self.stat_w.data_ptr(),
                                                              int(row_lo), int(row_hi), G, self.D, _stream()), "match_pack_gallery_rows")
-        self.G, self.src_version = G, gallery._version
+        self.G, self.src_version = G, src._version
         self.ready = torch.cuda.Event()
         self.ready.record()
 
@@ -741,7 +789,7 @@ class MatchPack:
         torch.cuda.current_stream().wait_event(self.ready)
 
     def matches(self, gallery: torch.Tensor) -> bool:
-        return (gallery.data_ptr() == self.src_ptr and gallery._version == self.src_version and
+        return (gallery.data_ptr() == self.src_ptr and gallery._version == self.src_version and tuple(gallery.stride()) == self.src_stride and
                 tuple(gallery.shape) == (self.G, self.D) and gallery.device == self.packed.device)
 
 
@@ -777,13 +825,15 @@ def match_top1(emb: torch.Tensor, gallery: torch.Tensor, thresh: Optional[float]
     with ``packed`` a fourth: int32[B, 2] = (id-or-unknown, bits of dist), the all-gather record.
     ``prepared`` (`match_prepare(gallery)`): run the gallery scan on the fp16 MFMA pipe (same contract)."""
     emb = _dev(emb, "match_top1.emb", torch.float32)
+    if emb.dim() != 2:
+        raise ValueError(f"match_top1: emb must be [B, D], got {list(emb.shape)}")
     B, D = emb.shape
     G = int(gallery.shape[0]) if gallery is not None else 0
     gptr = 0
     if G > 0:
         src, gallery = gallery, _dev(gallery, "match_top1.gallery", torch.float32)
-        if gallery.shape[1] != D:
-            raise ValueError(f"match_top1: embedding dim {D} != gallery dim {gallery.shape[1]}")
+        if gallery.dim() != 2 or gallery.shape[1] != D:
+            raise ValueError(f"match_top1: gallery must be [G, {D}] (the embedding dim), got {list(gallery.shape)}")
         gptr = gallery.data_ptr()
     prepared = _usable_pack(prepared, src if G > 0 else gallery, D, "match_top1")
     idx = torch.empty((B,), dtype=torch.int32, device=emb.device)
@@ -826,8 +876,8 @@ def match_topk(emb: torch.Tensor, gallery: Optional[torch.Tensor], k: int, label
     gptr = lptr = 0
     if G > 0:
         src, gallery = gallery, _dev(gallery, "match_topk.gallery", torch.float32)
-        if gallery.shape[1] != D:
-            raise ValueError(f"match_topk: embedding dim {D} != gallery dim {gallery.shape[1]}")
+        if gallery.dim() != 2 or gallery.shape[1] != D:
+            raise ValueError(f"match_topk: gallery must be [G, {D}] (the embedding dim), got {list(gallery.shape)}")
         gptr = gallery.data_ptr()
     if labels is not None:
         labels = _dev(labels, "match_topk.labels", torch.int32, ("frmap_match_topk", "labels"))
@@ -893,10 +943,12 @@ def _pair_operands(op: str, a, labels_a, b, labels_b, a_row0, absent: dict):
             if absent[what] is not None:
                 raise ValueError(absent[what])
             return None
-        t = _dev(t, f"{op}.{what}").to(torch.int32).reshape(-1)
-        if t.shape[0] != n:
-            raise ValueError(f"{op}: {what} must hold {n} labels, got {t.shape[0]}")
-        return t
+        t = _dev(t, f"{op}.{what}")
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{op}: {what} must be int32 or int64, got {t.dtype}")
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"{op}: {what} must hold {n} labels as [{n}], got {list(t.shape)}")
+        return t.to(torch.int32)
 
     la = labels(labels_a, P, "labels_a")
     if b is None:
@@ -1031,7 +1083,11 @@ def gap_linear_norm(fmap: torch.Tensor, wt: torch.Tensor, scale: Optional[torch.
     if wt.dim() != 2 or wt.shape[0] != K or not wt.is_contiguous():
         raise ValueError(f"gap_linear_norm: wt must be a contiguous [{K}][N] matrix")
     N = int(wt.shape[1])
-    emb = torch.empty((B, N), dtype=torch.float32, device=fmap.device)
+    if scale is not None:
+        _sized(scale, "gap_linear_norm", "scale", (N,), torch.float32)
+    if shift is not None:
+        _sized(shift, "gap_linear_norm", "shift", (N,), torch.float32)
+    emb =torch.empty((B, N), dtype=torch.float32, device=fmap.device)
     pre = torch.empty((B, N), dtype=torch.float32, device=fmap.device) if want_pre else None
     _lib.check(_lib.load().frmap_gap_linear_norm(fmap.data_ptr(), wt.data_ptr(),
                                                  _ptr(keep, scale, "scale", torch.float32, ("frmap_gap_linear_norm", "scale")) if scale is not None else 0,
@@ -1051,8 +1107,8 @@ def gap_norm_match(fmap: torch.Tensor, gallery: torch.Tensor, thresh: Optional[f
     gptr = 0
     if G > 0:
         gallery = _dev(gallery, "gap_norm_match.gallery", torch.float32)
-        if gallery.shape[1] != Cc:
-            raise ValueError(f"gap_norm_match: map channels {Cc} != gallery dim {gallery.shape[1]}")
+        if gallery.dim() != 2 or gallery.shape[1] != Cc:
+            raise ValueError(f"gap_norm_match: gallery must be [G, {Cc}] (the map's channels), got {list(gallery.shape)}")
         gptr = gallery.data_ptr()
     idx = torch.empty((B,), dtype=torch.int32, device=fmap.device)
     dist = torch.empty((B,), dtype=torch.float32, device=fmap.device)
@@ -1071,6 +1127,8 @@ def cosine_logits(x: torch.Tensor, w: torch.Tensor, s: float = 1.0, want_logits:
                   want_argmax: bool = True):
     x = _dev(x, "cosine_logits.x", torch.float32)
     w = _dev(w, "cosine_logits.w", torch.float32)
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError(f"cosine_logits: x [B, D] and w [C, D] expected, got {list(x.shape)} and {list(w.shape)}")
     B, D = x.shape
     Cc = w.shape[0]
     logits = torch.empty((B, Cc), dtype=torch.float32, device=x.device) if want_logits else None
@@ -1087,10 +1145,12 @@ def arcmargin_eval(x: torch.Tensor, w: torch.Tensor, label: torch.Tensor, s: flo
     x = _dev(x, "arcmargin_eval.x", torch.float32)
     w = _dev(w, "arcmargin_eval.w", torch.float32)
     label = _dev(label, "arcmargin_eval.label", torch.int64, ("frmap_arcmargin_eval", "label"))
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise ValueError(f"arcmargin_eval: x [B, D] and w [C, D] expected, got {list(x.shape)} and {list(w.shape)}")
     B, D = x.shape
     Cc = w.shape[0]
-    if label.numel() != B:
-        raise ValueError("arcmargin_eval: one label per row required")
+    if tuple(label.shape) != (B,):
+        raise ValueError(f"arcmargin_eval: label must be [{B}], one per row of x, got {list(label.shape)}")
     out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     mm = torch.empty((2,), dtype=torch.float32, device=x.device) if want_minmax else None
     ws = _workspace(B, Cc, x.device)
@@ -1185,6 +1245,8 @@ def track_step(state: torch.Tensor, boxes: torch.Tensor, probs: Optional[torch.T
     S, M = int(boxes.shape[0]), int(boxes.shape[1])
     if (probs is not None and tuple(probs.shape) != (S, M)) or tuple(counts.shape) != (S,) or tuple(frame_hw.shape) != (S, 2):
         raise ValueError("track_step: probs [S, max_boxes], counts [S] and frame_hw [S, 2] must match boxes")
+    if state.dim() != 1:
+        raise ValueError(f"track_step: state must be a flat uint8 buffer (`track_state`), got {list(state.shape)}")
     if state.numel() < track_state_bytes(S, M):
         raise ValueError(f"track_step: state holds {state.numel()} bytes, {S} streams of {M} boxes need {track_state_bytes(S, M)}")
     ids = torch.empty((S, M), dtype=torch.int32, device=boxes.device)
@@ -1309,6 +1371,8 @@ def track_fuse(state: torch.Tensor, ids: torch.Tensor, counts: torch.Tensor, emb
     N, D = int(emb.shape[0]), int(emb.shape[1])
     if not (0.0 < float(np.float32(decay)) <= 1.0):
         raise ValueError(f"track_fuse: decay = {decay} is outside (0, 1]")
+    if state.dim() != 1:
+        raise ValueError(f"track_fuse: state must be a flat uint8 buffer (`track_fuse_state`), got {list(state.shape)}")
     if state.numel() < track_fuse_state_bytes(S, M, D):
         raise ValueError(f"track_fuse: state holds {state.numel()} bytes, {S} streams of {M} boxes of {D} values need "
                          f"{track_fuse_state_bytes(S, M, D)}")
@@ -1368,11 +1432,13 @@ def track_fuse_host(state: np.ndarray, ids, counts, emb, rows, decay: float = 1.
 for _name in ("pack_input", "pack_conv_weight", "pack_conv_weight_c3", "conv_small_cin", "stem7x7_maxpool", "stem7x7_maxpool_u8", "conv_igemm",
               "conv_igemm_ds", "linear_mfma", "maxpool", "avgpool_global", "avgpool_adaptive", "linear_f32", "l2_normalize",
               "cast_to_f32", "cast_from_f32", "add_pos_layernorm", "mha_tokens", "mean_layernorm", "cnn_attention",
-              "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "gap_norm_match", "cosine_logits",
-              "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step", "track_fuse", "classify_tally",
-              "ovr_append", "ovr_rank_counts"):
+              "normalize_u8", "softmax_argmax", "pairwise_distance", "match_top1", "match_topk", "verify_counts", "match_radius",
+              "gap_norm_match", "cosine_logits", "arcmargin_eval", "conv_small_cin_pool2", "conv_igemm_pool2", "gap_linear_norm", "track_step",
+              "track_fuse", "classify_tally", "ovr_append", "ovr_rank_counts"):
     globals()[_name] = _on_operand_device(globals()[_name])
 del _name
+MatchPack.__init__ = _on_operand_device(MatchPack.__init__)          # (`match_prepare` is decorated where it is defined)
+MatchPack.update_rows = _on_operand_device(MatchPack.update_rows)
 
 
 # ------------------------------------------------------------------------------------------------

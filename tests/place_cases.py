@@ -1,6 +1,6 @@
 """Where a buffer starts: helpers of the pointer-alignment tests (`test_place_cpu.py`, `test_place_*_gpu.py`).
 
-A plain helper module like `conv_cases.py` and `guard.py` (no fixture, no setting).  Three things live here.
+A plain helper module like `conv_cases.py` and `guard.py` (no fixture, no setting).  Four things live here.
 
 THE REQUIREMENT (`requirement`).  `guard.shifted` places every buffer "aligned to A and not to 2 A"; A comes from this function of
 an allocation's dtype, kind and caller.  The guard sees a tensor, not the C argument it will become, so A is the LARGEST alignment
@@ -27,6 +27,11 @@ REJECTIONS (`misaligned_calls`).  For every entry point and every pointer argume
 the smallest valid call with that one pointer moved by half the requirement (`REJECT_CALLS` builds the argument lists; a test
 supplies the memory).  CPU and GPU files share the table: with host dummy pointers the call must be refused all the same, because
 the refusal comes before any HIP call.
+
+VIEWS (`offset_rule` / `mirror_offset`, `strided_rule` / `mirror_strided`).  The guard tests once more with every placed operand a
+contiguous view one element into its allocation (`test_place_*_gpu.py`), or a strided view of a wider tensor (`test_operands_gpu.py`;
+the views themselves are `operand_cases.strided_view` / `permuted_view`): the binding copies what it cannot pass on, and the result
+holds the bits of the call on clones.
 """
 import contextlib
 import inspect
@@ -68,7 +73,7 @@ def requirement(dtype, kind, who):
     return WRAPPER.get((who, dtype), EMPTY[dtype])
 
 
-CALLS = {"shifted": 0, "offset": 0}      # how often a substituted rule ran: a mirrored test that never reaches it tests nothing
+CALLS = {"shifted": 0, "offset": 0, "strided": 0}      # how often a substituted rule ran: a mirrored test that never reaches it tests nothing
 
 
 def shifted_rule(run, modules=(), device="cuda", band=guard.BAND, canon=None, what=""):
@@ -265,6 +270,71 @@ def mirror_offset(module, name):
             return fn(*args, **kwargs)
     test.__name__ = test.__qualname__ = name
     test.__doc__ = "`%s.%s` with every tensor input a contiguous view one element into its allocation." % (module.__name__, name)
+    test.__signature__ = inspect.signature(fn)
+    test.pytestmark = list(getattr(fn, "pytestmark", []))
+    return test
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the binding: operands that are strided views (`operand_cases.strided_view`, `permuted_view`)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def strided_rule(run, modules=(), device="cuda", band=None, canon=None, what=""):
+    """With the signature of `guard.two_fills`: `run` on plain copies (the call on `.clone()`s) and with EVERY placed operand a strided
+    view of a wider tensor (`wide[..., ::2]`: the binding copies each, and all the copies of one call are alive at once); where `run`
+    placed a 4-D operand, once more with every 4-D operand the `permute(0, 2, 3, 1)` view of a tensor laid out the other way round
+    (what a torch user has in hand for an NHWC map) and the others strided.  The results hold the same bits.  An operand the call
+    WRITES is not placed by any guard test (the states come from `ops.track_state` / `ops.track_fuse_state` inside `run`), so it keeps
+    its own form.  Nothing is guarded: what the wrapper allocates is the allocator's."""
+    import operand_cases as oc
+    CALLS["strided"] += 1
+    canon = canon or (lambda r: r)
+    dev = torch.device(device)
+    seen = {"n": 0, "4d": 0}
+
+    def strided(t):
+        seen["n"] += 1
+        seen["4d"] += t.dim() == 4
+        return oc.strided_view(t, dev)
+
+    def permuted(t):
+        return oc.permuted_view(t, dev) if t.dim() == 4 else oc.strided_view(t, dev)
+    ref = canon(guard._flat(run(lambda t: t.to(dev, copy=True))))
+    forms = [("strided views (wide[..., ::2])", strided)]
+    got = [canon(guard._flat(run(strided)))]
+    assert seen["n"] > 0, "%s: the case placed no operand: nothing was strided" % what
+    if seen["4d"]:
+        forms.append(("permute(0, 2, 3, 1) views of its 4-D operands", permuted))
+        got.append(canon(guard._flat(run(permuted))))
+    guard.Guard(0, 1, dev)._sync()
+    for (form, _), res in zip(forms, got):
+        assert len(res) == len(ref), (what, form, len(res), len(ref))
+        for k in range(len(ref)):
+            d = guard.first_difference(res[k], ref[k])
+            assert d is None, "%s: result %d on %s differs from the call on their clones: %s" % (what, k, form, d)
+    return ref
+
+
+@contextlib.contextmanager
+def on_strided_views():
+    """Inside the block `guard.two_fills` is `strided_rule`; the block must have reached it at least once."""
+    saved, before = guard.two_fills, CALLS["strided"]
+    guard.two_fills = strided_rule
+    try:
+        yield
+    finally:
+        guard.two_fills = saved
+    assert CALLS["strided"] > before, "the guard test never called guard.two_fills: no operand was strided"
+
+
+def mirror_strided(module, name):
+    """The guard test `module.name` with every placed operand a strided view (`strided_rule`)."""
+    fn = getattr(module, name)
+
+    def test(*args, **kwargs):
+        with on_strided_views():
+            return fn(*args, **kwargs)
+    test.__name__ = test.__qualname__ = name
+    test.__doc__ = "`%s.%s` with every tensor input a strided view of a wider tensor." % (module.__name__, name)
     test.__signature__ = inspect.signature(fn)
     test.pytestmark = list(getattr(fn, "pytestmark", []))
     return test
