@@ -9,12 +9,12 @@ built library, or with host tensors, raises.
 """
 from .face_models import (MODEL_TYPES, ArcFaceNet, ArcMarginProduct, AttentionNet, BaselineNet, EnsembleModel, HybridNet,
                           ResNetTransfer, SiameseNet, create_ensemble, get_model, set_default_compute_dtype)
-from . import evaluate, frames
+from . import evaluate, frames, head_fit
 from .matching import (REC_THRESH, Gallery, GraphedEmbedMatch, get_embedding, compare_faces, embed_and_match, load_refs, match_batch, save_refs,
                        search_radius, compare_faces_all, duplicate_pairs, cluster_embeddings, embed_boxes, identify_boxes, StreamTracker, TrackTemplates, embed_streams,
                        identify_streams)
 
 __all__ = ["MODEL_TYPES", "get_model", "BaselineNet", "ResNetTransfer", "SiameseNet", "ArcFaceNet",
            "ArcMarginProduct", "HybridNet", "AttentionNet", "EnsembleModel", "create_ensemble", "set_default_compute_dtype", "compare_faces", "load_refs",
-           "save_refs", "evaluate", "embed_and_match", "match_batch", "Gallery", "GraphedEmbedMatch", "get_embedding", "REC_THRESH", "frames", "embed_boxes", "identify_boxes",
+           "save_refs", "evaluate", "embed_and_match", "match_batch", "Gallery", "GraphedEmbedMatch", "get_embedding", "REC_THRESH", "frames", "head_fit", "embed_boxes", "identify_boxes",
            "StreamTracker", "TrackTemplates", "embed_streams", "identify_streams"]

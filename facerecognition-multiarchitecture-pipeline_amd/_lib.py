@@ -98,6 +98,10 @@ PROTOTYPES = {
     "frmap_ovr_append": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.c_longlong, C.c_longlong, _vp]),
     "frmap_ovr_rank_counts": (_i, [_vp, _vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp, _vp]),
     "frmap_ovr_rank_counts_host": (_i, [_vp, _vp, C.c_longlong, C.c_longlong, _i, _vp, _vp, _vp]),
+    "frmap_head_fit_state_bytes": (_sz, [_i, _i, _i]),
+    "frmap_head_fit_workspace_bytes": (_sz, [_i, _i, _i]),
+    "frmap_head_fit_step": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _vp]),
+    "frmap_head_fit_step_host": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i]),
     "frmap_head_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_top1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
@@ -189,6 +193,7 @@ ALIGNMENT = {
                              "row_loss_out": _E4},
     "frmap_ovr_append": {"scores": _E4, "labels": _E4, "store": _E4, "store_labels": _E4},
     "frmap_ovr_rank_counts": {"store": _E4, "store_labels": _E4, "ge_same_out": _E8, "ge_other_out": _E8, "eq_other_out": _E8},
+    "frmap_head_fit_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep": _E1, "w": _E4, "b": _E4, "state": _E8, "workspace": _E4},
     "frmap_match_top1": {"emb": _M, "gallery": _M, **_TOP1_OUT, "workspace": _W},
     "frmap_match_pack_gallery": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
     "frmap_match_pack_gallery_rows": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},

@@ -1,0 +1,213 @@
+// One training step of a linear softmax classifier over cached features (head_fit.step_rule is the rule in plain numpy), for the
+// host and the device alike: head_fit.hip's kernels and the host twin (head_fit_twin.h, frmap_head_fit_step_host) run this text; a
+// plain C++ compiler takes it too (tools/head_fit_check.cpp).  Not part of the public ABI.
+//
+// Operands: x [N, D] fp32 (the cached features), labels [N] int32, rows [B] int32 (indices into x and labels; NULL: 0 .. B-1),
+// keep [B, D] uint8 or NULL (a dropout mask over the BATCH rows), keep_scale = 1 / (1 - p), w [C, D] and b [C] fp32.
+//   x'       = keep ? (keep[i][k] ? fl(x * keep_scale) : +0) : x                           one rounding
+//   declined   batch row i is declined - it contributes nothing - when rows[i] is outside [0, N), or its label is outside [0, C),
+//              or any of its D features is NaN or an infinity (the features themselves: a dropped one counts).  n = the batch
+//              rows that are not declined.  n == 0: no weight, moment or step count changes; only the workspace is written.
+//   z[i][c]  = dot_k(x'[i][k], w[c][k]) + b[c]                                              (declined: the row of z is +0)
+//   softmax    in FLOAT64 from the fp32 logits: m = max_c z, s = sum_c exp(z - m), p = exp(z - m) / s, lse = log(s), -log p[c] =
+//              lse - (z[c] - m); pred = the first arg-max
+//   target     y_off = ls / C, y_on = (1 - ls) + y_off (ls == 0: exactly 0 and 1)
+//   row loss = fp32(max(0, -log p[label])); with ls > 0: fp32(max(0, (1 - ls) (-log p[label]) + y_off sum_c (-log p[c])))
+//              (declined: NaN)
+//   g[i][c]  = fp32((p - y) / n)                                                             (declined: the row of g is +0)
+//   dw[c][d] = dot_i(g[i][c], x'[i][d]), db[c] = dot_i(g[i][c], 1), declined rows taken as g = x' = +0
+//   update     torch.optim.Adam / AdamW on every w[c][d] and b[c] (frmap_head_fit_adam below), t += 1 first
+//   figures    rows += n, correct += #(pred == label), loss_q += the tally's fixed point of the row loss (tally_rule.h: clamp 65536,
+//              scale 2^24): exact integer adds
+//
+// SUMMATION ORDER.  dot_k(a, b) over k = 0 .. K-1 (K = D forward, K = B backward) is cut at the multiples of FRMAP_HEAD_FIT_CHAIN:
+//   s = +0;  for every chain j = 0, 1, ...: c = +0; for k = j CHAIN .. min((j + 1) CHAIN, K) - 1 ascending: c = fmaf(a_k, b_k, c);  s = s + c
+// and the bias is added last, z = s + b.  Nothing depends on the grid, the device or the tiling: the fp32-input MFMA of gfx950 is
+// bit for bit this fmaf chain over its two k, so a 32 x 32 tile on the matrix cores and a ragged edge on plain fmaf lanes agree.
+// A chain never holds -0 (it starts at +0 and an exact zero sum rounds to +0), so a zero-padded k is a no-op.
+// The softmax sums (s, and the smoothing sum) are float64 and the device's own: a wavefront adds them lane by lane and then across
+// lanes, the twin serially, and exp / log are each side's library - parts in 2^53 before the one rounding to fp32, so g and the
+// row loss of the two sides differ in a rare last bit at most.  Everything downstream of g is defined on g's fp32 bits.
+//
+// STATE (frmap_head_fit_state_bytes; all-zero bytes = fresh): eight uint64 words - t, n of the step in flight, and the epoch figures
+// rows, correct, loss_q, three reserved - then fp32 m_w [C D], v_w [C D], m_b [C], v_b [C] and, with AMSGrad, vmax_w [C D], vmax_b [C].
+// WORKSPACE (frmap_head_fit_workspace_bytes): fp32 z [B C], g [B C], row_loss [B], then int32 row_src [B]: the row of x a batch row
+// reads, or -1 for a declined one.
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "tally_rule.h"   // FRMAP_TRACK_HD, frmap_tally_finite_bits, frmap_tally_loss_q
+
+constexpr int FRMAP_HEAD_FIT_CHAIN = 128;
+constexpr int FRMAP_HEAD_FIT_MAX_C = 65536;              // classes (the softmax kernel gives a wavefront to a row; the grid of the update)
+constexpr int FRMAP_HEAD_FIT_MAX_D = 65536;
+constexpr int FRMAP_HEAD_FIT_MAX_B = 1 << 20;            // batch rows of one step
+constexpr int FRMAP_HEAD_FIT_DECOUPLED = 1, FRMAP_HEAD_FIT_AMSGRAD = 2, FRMAP_HEAD_FIT_CLEAR = 4;   // bits of `flags`
+constexpr int FRMAP_HEAD_FIT_HEADER = 8;
+constexpr int FRMAP_HEAD_FIT_T = 0, FRMAP_HEAD_FIT_N = 1, FRMAP_HEAD_FIT_ROWS = 2, FRMAP_HEAD_FIT_CORRECT = 3, FRMAP_HEAD_FIT_LOSS_Q = 4;
+
+FRMAP_TRACK_HD inline bool frmap_head_fit_shape_ok(int D, int C) {
+  return D >= 1 && D <= FRMAP_HEAD_FIT_MAX_D && C >= 1 && C <= FRMAP_HEAD_FIT_MAX_C;
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_state_size(int D, int C, int amsgrad) {
+  const size_t per = (size_t)C * (size_t)D + (size_t)C;
+  return (((size_t)FRMAP_HEAD_FIT_HEADER * 8 + 4 * per * (amsgrad ? 3 : 2)) + 7) & ~(size_t)7;
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_workspace_size(int B, int C) { return 4 * (2 * (size_t)B * (size_t)C + 2 * (size_t)B); }
+
+struct FrmapHeadFitState {
+  uint64_t* head;
+  float *m_w, *v_w, *m_b, *v_b, *vmax_w, *vmax_b;
+};
+FRMAP_TRACK_HD inline FrmapHeadFitState frmap_head_fit_state(void* state, int D, int C, int amsgrad) {
+  FrmapHeadFitState s;
+  const size_t cd = (size_t)C * (size_t)D;
+  s.head = (uint64_t*)state;
+  s.m_w = (float*)(s.head + FRMAP_HEAD_FIT_HEADER);
+  s.v_w = s.m_w + cd;
+  s.m_b = s.v_w + cd;
+  s.v_b = s.m_b + C;
+  s.vmax_w = amsgrad ? s.v_b + C : nullptr;
+  s.vmax_b = amsgrad ? s.vmax_w + cd : nullptr;
+  return s;
+}
+struct FrmapHeadFitWork {
+  float *z, *g, *row_loss;
+  int32_t* row_src;
+};
+FRMAP_TRACK_HD inline FrmapHeadFitWork frmap_head_fit_work(void* workspace, int B, int C) {
+  FrmapHeadFitWork k;
+  k.z = (float*)workspace;
+  k.g = k.z + (size_t)B * (size_t)C;
+  k.row_loss = k.g + (size_t)B * (size_t)C;
+  k.row_src = (int32_t*)(k.row_loss + B);
+  return k;
+}
+
+struct FrmapHeadFitHyper {
+  float lr, beta1, beta2, eps, weight_decay, label_smoothing;
+};
+
+// x' of one feature; `kept` < 0: no mask
+FRMAP_TRACK_HD inline float frmap_head_fit_xp(float x, int kept, float keep_scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (kept < 0) return x;
+  return kept ? x * keep_scale : 0.0f;
+}
+
+// The softmax half of a row, in FLOAT64 from the fp32 logits and rounded to fp32 once at the end: g and the row loss are then
+// within one fp32 unit in the last place of their exact values whatever library evaluates exp and log, and the order of the two
+// sums moves them by parts in 2^53.
+struct FrmapHeadFitTarget {
+  double y_on, y_off, one_minus_ls;
+};
+FRMAP_TRACK_HD inline FrmapHeadFitTarget frmap_head_fit_target(float ls, int C) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  FrmapHeadFitTarget t;
+  t.one_minus_ls = 1.0 - (double)ls;
+  t.y_off = ls > 0.0f ? (double)ls / (double)C : 0.0;
+  t.y_on = t.one_minus_ls + t.y_off;
+  return t;
+}
+// exp(z - m) of one logit against the row maximum
+FRMAP_TRACK_HD inline double frmap_head_fit_exp(float z, float m) { return exp((double)z - (double)m); }
+// -log p of one class: lse - (z - m) with lse = log(sum_c exp(z[c] - m))
+FRMAP_TRACK_HD inline double frmap_head_fit_nl(double lse, float z, float m) { return lse - ((double)z - (double)m); }
+// the row loss from -log p of the label and, with smoothing, the sum over the classes of -log p
+FRMAP_TRACK_HD inline float frmap_head_fit_loss(double nl_label, double nl_sum, float ls, const FrmapHeadFitTarget& t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double l = nl_label;
+  if (ls > 0.0f) {
+    const double a = t.one_minus_ls * nl_label, b = t.y_off * nl_sum;
+    l = a + b;
+  }
+  return (float)(l > 0.0 ? l : (l == l ? 0.0 : l));       // max(0, l); a NaN stays one
+}
+FRMAP_TRACK_HD inline float frmap_head_fit_g(double e, double s, double y, uint64_t n) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double p = e / s;
+  const double d = p - y;
+  return (float)(d / (double)n);
+}
+
+// The scalars of step t (the count AFTER its increment) that every element shares.  beta^t is a product of squarings in double, so
+// the host and the device form the same bits; the corrections are rounded to fp32 once.
+struct FrmapHeadFitAdam {
+  float step_size, bc2_sqrt, omb1, omb2, beta2, eps, wd, decay;
+  int decoupled, amsgrad;
+};
+FRMAP_TRACK_HD inline double frmap_head_fit_powi(double base, uint64_t t) {
+  double r = 1.0, p = base;
+  while (t) {
+    if (t & 1) r = r * p;
+    p = p * p;
+    t >>= 1;
+  }
+  return r;
+}
+FRMAP_TRACK_HD inline FrmapHeadFitAdam frmap_head_fit_adam_scalars(uint64_t t, const FrmapHeadFitHyper& h, int flags) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  FrmapHeadFitAdam a;
+  const float bc1 = (float)(1.0 - frmap_head_fit_powi((double)h.beta1, t));
+  const float bc2 = (float)(1.0 - frmap_head_fit_powi((double)h.beta2, t));
+  a.step_size = h.lr / bc1;
+  a.bc2_sqrt = sqrtf(bc2);
+  a.omb1 = 1.0f - h.beta1;
+  a.omb2 = 1.0f - h.beta2;
+  a.beta2 = h.beta2;
+  a.eps = h.eps;
+  a.wd = h.weight_decay;
+  const float lw = h.lr * h.weight_decay;
+  a.decay = 1.0f - lw;
+  a.decoupled = (flags & FRMAP_HEAD_FIT_DECOUPLED) ? 1 : 0;
+  a.amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
+  return a;
+}
+// torch.optim.Adam / AdamW on one parameter with gradient `grad`, every operation fp32 and rounded once:
+//   coupled    grad = fma(wd, p, grad)                         decoupled   p = p * (1 - lr wd)
+//   m = fma(1 - beta1, grad - m, m)                            (exp_avg.lerp_)
+//   v = fma(1 - beta2, grad * grad, v * beta2)                 (mul_ then addcmul_)
+//   vhat = amsgrad ? (vmax = max(vmax, v)) : v
+//   p = fma(-step_size, m / (sqrt(vhat) / sqrt(1 - beta2^t) + eps), p),  step_size = lr / (1 - beta1^t)
+FRMAP_TRACK_HD inline void frmap_head_fit_adam(const FrmapHeadFitAdam& a, float grad, float* p_io, float* m_io, float* v_io, float* vmax_io) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float p = *p_io, m = *m_io, v = *v_io;
+  if (a.decoupled) {
+    p = p * a.decay;
+  } else if (a.wd != 0.0f) {
+    grad = fmaf(a.wd, p, grad);
+  }
+  const float diff = grad - m;
+  m = fmaf(a.omb1, diff, m);
+  const float vb = v * a.beta2;
+  const float gg = grad * grad;
+  v = fmaf(a.omb2, gg, vb);
+  float vhat = v;
+  if (a.amsgrad) {
+    const float old = *vmax_io;
+    vhat = old > v ? old : v;
+    *vmax_io = vhat;
+  }
+  const float r = sqrtf(vhat);
+  const float q = r / a.bc2_sqrt;
+  const float denom = q + a.eps;
+  const float u = m / denom;
+  p = fmaf(-a.step_size, u, p);
+  *p_io = p;
+  *m_io = m;
+  *v_io = v;
+}

@@ -631,6 +631,53 @@ int frmap_ovr_rank_counts(const float* store, const int32_t* store_labels, long 
 int frmap_ovr_rank_counts_host(const float* store_host, const int32_t* store_labels_host, long long n, long long capacity, int C,
                                uint64_t* ge_same_host, uint64_t* ge_other_host, uint64_t* eq_other_host);
 
+/* Head fitting: one training step of a linear softmax classifier (the nn.Linear(512, C) of ResNetTransfer's frozen phase, of
+ * two-phase ArcFace training and of src/testing.py:134-136) over CACHED trunk features.  Softmax regression on a [B, D] view of a
+ * cached [N, D] matrix with a torch.optim.Adam / AdamW update: one small memset and three launches on the caller's stream,
+ * nothing copied to the host, nothing allocated.  No backward pass through a trunk exists here.
+ *
+ * Operands: x [N][D] fp32, labels [N] int32, rows [B] int32 (indices into x and labels; NULL: rows 0 .. B-1 - a mini-batch is a
+ * view of the cache), keep [B][D] uint8 or NULL (a dropout mask over the batch rows) with keep_scale = 1 / (1 - p), w [C][D] and
+ * b [C] fp32, updated in place.  flags: 1 = decoupled weight decay (AdamW; else the coupled L2 of Adam), 2 = AMSGrad, 4 = clear
+ * the epoch figures first.
+ * The rule:
+ *   x'       = keep ? (keep[i][k] ? x * keep_scale : 0) : x, one rounding
+ *   declined : a batch row whose rows entry is outside [0, N), whose label is outside [0, C) or any of whose D features is NaN or
+ *              an infinity contributes nothing; n counts the others, on the device.  n == 0 changes no weight and no moment and
+ *              does not advance t.
+ *   z = x' w^T + b;  p = softmax(z), max-subtracted;  y = (1 - ls) onehot + ls / C;  row loss = -sum y log p;  g = (p - y) / n:
+ *   the softmax, the loss and g are evaluated in float64 from the fp32 logits and rounded to fp32 once;
+ *   dw = g^T x', db = sum over the rows of g;  then Adam / AdamW with the bias corrections of step t, every operation fp32 and
+ *   rounded once (fmaf where torch fuses: lerp_, addcmul_, addcdiv_).
+ *   Summation order: every dot product (length D forward, length B backward) is cut at the multiples of 128; a chain is fmaf from
+ *   +0 in ascending k, the chains are added in ascending order from +0, the bias last.  The fp32-input MFMA of gfx950 is that fmaf
+ *   chain bit for bit, so full 32 x 32 tiles run on the matrix cores and ragged edges on plain fmaf lanes with the same bits;
+ *   nothing depends on the grid or the device.  The same operands give the same bits on every run: no floating-point atomic.
+ * state : frmap_head_fit_state_bytes bytes, zeroed by the caller before the first step: eight uint64 words - t, n of the last step,
+ *         and the epoch figures rows, correct, loss_q (the tally's fixed point: clamp 65536, scale 2^24), three reserved - then fp32
+ *         m_w [C][D], v_w [C][D], m_b [C], v_b [C] and, sized for AMSGrad, vmax_w [C][D], vmax_b [C].  t lives here, so a captured
+ *         step replays correctly.
+ * workspace : exactly frmap_head_fit_workspace_bytes bytes: fp32 z [B][C], g [B][C], row_loss [B] (NaN for a declined row, whose
+ *         rows of z and g are +0), int32 row_src [B] (the row of x read, -1 for a declined row).  D does not enter the size.
+ * The size queries take no stream and return 0 for arguments the launcher would refuse.
+ * Refused (-1, the text names the argument): N < 1; B < 1 or above 2^20; D < 1 or above 65536; C < 1 or above 65536 (one
+ * wavefront per row of the softmax; the grid of the update); unknown flag bits.
+ * Every pointer is walked element by element: x, labels, rows, w, b and workspace need their element size (4), keep 1, state the
+ * size of a uint64 counter (8).
+ * The host form is the same step compiled for the CPU (host pointers, no stream; its workspace holds the same z, g, row_loss and
+ * row_src).  With given_g != 0 the z, g and row_loss of the workspace are INPUTS - the device's own, whose exp / log are not the
+ * C library's - and the figures, dw, db and the update are computed from them, so that weights and moments can be compared with
+ * the device's word for word. */
+size_t frmap_head_fit_state_bytes(int D, int C, int amsgrad);
+size_t frmap_head_fit_workspace_bytes(int B, int D, int C);
+int frmap_head_fit_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale, float* w,
+                        float* b, void* state, void* workspace, int N, int B, int D, int C, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, float label_smoothing, int flags, void* stream);
+int frmap_head_fit_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,
+                             float keep_scale, float* w_host, float* b_host, void* state_host, void* workspace_host, int N, int B,
+                             int D, int C, float lr, float beta1, float beta2, float eps, float weight_decay, float label_smoothing,
+                             int flags, int given_g);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
