@@ -17,8 +17,11 @@
 // constant `same` (three compares and three adds a pair).  Every thread compares its positive against the chunk: all lanes read
 // the same LDS address, a broadcast.  A batch of at most 64 positives is given to all four wavefronts, a quarter of the chunk
 // each.  The three partial counts (32-bit: a segment is shorter than 2^31) go to the row's words as
-// 64-bit integer atomic adds, zero amounts not issued; the words are zeroed by three memset nodes ahead of the kernel in the same
-// call.  Integer adds only: the words are the same bits on every run.  Every column is addressed as store + (size_t) c * capacity.
+// 64-bit integer atomic adds, zero amounts not issued; the words are zeroed by one small kernel ahead of the count in the same
+// call.  A launch, not hipMemsetAsync: captured into a graph, the three memset nodes did not replay reliably - from the second or
+// third replay on every word came back as a page-aligned address plus the right count, as if filled with a stale pattern - while a kernel node
+// replays as it was launched (tests/test_stream_ops_gpu.py keeps the case).  Integer adds only: the words are the same bits on
+// every run.  Every column is addressed as store + (size_t) c * capacity.
 // Comparisons are fp32 compares with the default denormal mode (denormals kept); no flush-to-zero flag is given to this file.
 #include "frmap_common.h"
 #include "ovr_rule.h"
@@ -79,6 +82,15 @@ __global__ __launch_bounds__(OVR_THREADS) void ovr_append_kernel(const float* __
 
 __device__ __forceinline__ void ovr_add(uint64_t* p, unsigned v) {
   __hip_atomic_fetch_add((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(OVR_THREADS) void ovr_zero_kernel(uint64_t* __restrict__ ge_same, uint64_t* __restrict__ ge_other,
+                                                               uint64_t* __restrict__ eq_other, long long n) {
+  for (long long i = (long long)blockIdx.x * OVR_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * OVR_THREADS) {
+    ge_same[i] = 0;
+    ge_other[i] = 0;
+    eq_other[i] = 0;
+  }
 }
 
 __global__ __launch_bounds__(OVR_THREADS) void ovr_rank_kernel(const float* __restrict__ store, const int32_t* __restrict__ store_labels,
@@ -224,14 +236,10 @@ extern "C" int frmap_ovr_rank_counts(const float* store, const int32_t* store_la
   if (S > chunks) S = chunks;
   const long long seg_len = ((chunks + S - 1) / S) * OVR_CHUNK;
   S = (n + seg_len - 1) / seg_len;                         // (no empty segment)
-  uint64_t* outs[3] = {ge_same_out, ge_other_out, eq_other_out};
-  for (uint64_t* o : outs) {
-    const hipError_t e = hipMemsetAsync(o, 0, (size_t)n * sizeof(uint64_t), (hipStream_t)stream);
-    if (e != hipSuccess) {
-      frmap_set_error("ovr_rank_counts: zeroing an output failed: %s", hipGetErrorString(e));
-      return -2;
-    }
-  }
+  const long long zero_blocks = (n + OVR_THREADS - 1) / OVR_THREADS;
+  hipLaunchKernelGGL(ovr_zero_kernel, dim3((unsigned)(zero_blocks < OVR_TARGET_BLOCKS ? zero_blocks : OVR_TARGET_BLOCKS)), dim3(OVR_THREADS), 0,
+                     (hipStream_t)stream, ge_same_out, ge_other_out, eq_other_out, n);
+  FRMAP_LAUNCH_CHECK();
   hipLaunchKernelGGL(ovr_rank_kernel, dim3((unsigned)((long long)C * S)), dim3(OVR_THREADS), 0, (hipStream_t)stream, store, store_labels,
                      (int)n, capacity, C, (int)S, seg_len, ge_same_out, ge_other_out, eq_other_out);
   FRMAP_LAUNCH_CHECK();

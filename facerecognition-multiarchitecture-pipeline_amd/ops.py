@@ -695,7 +695,7 @@ def ovr_append(scores: torch.Tensor, labels: torch.Tensor, store: torch.Tensor, 
 
 
 def ovr_rank_counts(store: torch.Tensor, store_labels: torch.Tensor, n: int):
-    """The three exact integers of every row ``i < n`` of a score store (`frmap_ovr_rank_counts`: memsets and one launch on the
+    """The three exact integers of every row ``i < n`` of a score store (`frmap_ovr_rank_counts`: two launches on the
     current stream, no synchronisation): ``(ge_same, ge_other, eq_other)``, int64 ``[n]`` each (uint64 words) - over the counted
     rows j < n, those of i's class (i included) / of another class whose score in i's class column is >= i's, and those of another
     class whose score there equals i's.  A declined row (stored label < 0) gets 0, 0, 0 and takes part in nobody's count."""

@@ -615,7 +615,7 @@ int frmap_classify_tally_host(const float* logits_host, const int32_t* labels_ho
  *   roc_auc[c]           = (sum_{i in c} (N_c - ge_other[i]) + 1/2 sum_{i in c} eq_other[i]) / (P_c N_c)
  *   average_precision[c] = (sum_{i in c} ge_same[i] / (ge_same[i] + ge_other[i])) / P_c
  * - the Mann-Whitney form of the trapezoid under roc_curve with ties at one half, and sklearn's step-wise sum.
- * ge_same_out / ge_other_out / eq_other_out: uint64 [n] each.  The call writes every word of [0, n) itself (three memset nodes,
+ * ge_same_out / ge_other_out / eq_other_out: uint64 [n] each.  The call writes every word of [0, n) itself (one kernel that zeroes,
  * then one kernel that adds with 64-bit integer atomics; no floating-point atomic): the caller does not pre-zero them.  Exact
  * integers: the same store gives the same words on every run, whatever the split into appends; rows in another order give the
  * same integers per row.  n^2 comparisons whatever C is.  No scratch, nothing allocated or synchronised.

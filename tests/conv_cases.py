@@ -708,11 +708,11 @@ def device_operands(case, o, dtype, place=None):
     return d
 
 
-def launch_case(case, d, dtype, also_unfused=False):
+def launch_case(case, d, dtype, also_unfused=False, sync=True):
     """Launch the case's kernel on the device operands `d` (`device_operands`; `case.B` is the batch of the tensors in `d`) and
     return the output as it lies on the device, NHWC in `dtype` (`also_unfused`: for the fused-pool ops, the (fused, two-launch)
-    outputs).  Asserts the path the case is about where a query exists, waits for the launches and restores the process-wide
-    tuning hooks."""
+    outputs).  Asserts the path the case is about where a query exists, waits for the launches (`sync=False`: does not - the
+    stream tests launch a case while its operands are late, or into a graph) and restores the process-wide tuning hooks."""
     from frmap_amd import _lib, ops
     lib = _lib.load()
     try:
@@ -747,7 +747,8 @@ def launch_case(case, d, dtype, also_unfused=False):
             y = ops.stem7x7_maxpool_u8(d["u8"], wpk, sh, d["mean"], d["std"], dtype, pool3=case.op == "stem3u8")
         else:
             raise ValueError(case.op)
-        _sync(case.name)
+        if sync:
+            _sync(case.name)
         return (y, y2) if also_unfused and y2 is not None else y
     finally:
         reset_hooks(lib, case)

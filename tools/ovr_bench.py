@@ -9,7 +9,7 @@ Per batch: B = 1024 rows of C in {36, 1000, 10 000} logits (`synth.randn * 3`, t
             probabilities, the [B, C] logits (for the loss) and the [B] predictions, into pageable host memory as `.cpu()` does
 At the end: the count at (N, C) in {(1764, 36), (100 000, 36), (100 000, 10 000)} on a store of probability rows (uniform
 draws divided by their row sums, made on the device, every class present in the labels).
-  count     one `ovr_rank_counts` call (three memsets and the kernel); N^2 / time is the pair rate
+  count     one `ovr_rank_counts` call (the zeroing kernel and the count); N^2 / time is the pair rate
   finish    host clock around `OvrScores.metrics()`: the count, the one copy of labels and counts, `ovr_metrics` in float64
   sklearn   host clock around `roc_auc_score(multi_class='ovr')` + `average_precision_score` on the same scores, copied to the
             host first (not timed).  Where `--sklearn-budget` seconds would be exceeded (estimated from the first classes), the two
