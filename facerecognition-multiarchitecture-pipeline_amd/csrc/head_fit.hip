@@ -20,6 +20,12 @@
 // edge: fewer than 32 rows or columns) runs the same chains as plain fmaf lanes over the same staged operands.  No float atomics,
 // no dependency between workgroups inside a launch.
 //
+// frmap_head_fit_group_step runs H independent heads over one cache (head_fit_rule.h, GROUPS): one small kernel zeroes every head's n
+// (and, with `clear`, its figures) - a kernel, not H strided memsets, so that a captured step holds one node for it -, then the same
+// three kernel bodies with the head as blockIdx.z, each head reading its row of the device-resident hyper table where the single
+// step takes scalars by value.  Head h gets the bits of the single step on its slices.  Flag 8 (evaluate only) stops after the
+// softmax kernel, which then leaves t alone.
+//
 // LDS per workgroup: 4 x 2 x 32 x 33 floats of staging (pitch 33: the 32 lanes of an operand read 32 different banks) and
 // 4 x 1024 floats of partial tiles = 50 176 bytes; the registers of the staging loads keep two workgroups a compute unit resident.
 #include "frmap_common.h"
@@ -208,12 +214,13 @@ struct HfUpdateOp {
   }
 };
 
-// (two wavefronts a SIMD: the 48 loads a lane keeps in flight cost registers, and a third resident workgroup would spill them)
-__global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void head_fit_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ labels,
-                                                                        const int32_t* __restrict__ rows, const uint8_t* __restrict__ keep,
-                                                                        float keep_scale, const float* __restrict__ w,
-                                                                        const float* __restrict__ b, uint64_t* state, float* __restrict__ z,
-                                                                        int32_t* __restrict__ row_src, int N, int B, int D, int C) {
+// The bodies of the three kernels are device functions over ALREADY-OFFSET pointers and by-value scalars: the single step's kernels
+// hand them their arguments, the grouped step's kernels (blockIdx.z = the head) the slices of their head and its row of the hyper
+// table.  The x and y of the grid mean the same in both, so head h of a group runs the instructions of the single step.
+__device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, const int32_t* __restrict__ labels, const int32_t* __restrict__ rows,
+                                               const uint8_t* __restrict__ keep, float keep_scale, const float* __restrict__ w,
+                                               const float* __restrict__ b, uint64_t* state, float* __restrict__ z,
+                                               int32_t* __restrict__ row_src, int N, int B, int D, int C) {
   __shared__ HfSmem sm;
   __shared__ int s_src[HF_T];        // the row of x behind tile row i; -1: outside the batch, the cache or the label range
   __shared__ int s_bad[HF_T];        // a non-finite feature was staged for tile row i
@@ -255,9 +262,40 @@ __global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2
   }
 }
 
-__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_softmax_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ row_src,
-                                                                         uint64_t* state, const float* __restrict__ z, float* __restrict__ g,
-                                                                         float* __restrict__ row_loss, int B, int C, float ls) {
+// (two wavefronts a SIMD: the 48 loads a lane keeps in flight cost registers, and a third resident workgroup would spill them)
+__global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void head_fit_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ labels,
+                                                                        const int32_t* __restrict__ rows, const uint8_t* __restrict__ keep,
+                                                                        float keep_scale, const float* __restrict__ w,
+                                                                        const float* __restrict__ b, uint64_t* state, float* __restrict__ z,
+                                                                        int32_t* __restrict__ row_src, int N, int B, int D, int C) {
+  hf_logits_body(x, labels, rows, keep, keep_scale, w, b, state, z, row_src, N, B, D, C);
+}
+
+// where head h of a group keeps its operands: H single-head operands each, the states `stride` bytes apart
+struct HfGroup {
+  size_t stride, work;       // bytes from one head's state / workspace to the next
+  int B, D, C;
+  __device__ __forceinline__ const int32_t* rows(const int32_t* p, int h) const { return p + (size_t)h * (size_t)B; }
+  __device__ __forceinline__ const uint8_t* keep(const uint8_t* p, int h) const { return p ? p + (size_t)h * (size_t)B * (size_t)D : nullptr; }
+  __device__ __forceinline__ float* w(float* p, int h) const { return p + (size_t)h * (size_t)C * (size_t)D; }
+  __device__ __forceinline__ float* b(float* p, int h) const { return p + (size_t)h * (size_t)C; }
+  __device__ __forceinline__ void* state(void* p, int h) const { return (char*)p + (size_t)h * stride; }
+  __device__ __forceinline__ FrmapHeadFitWork workspace(void* p, int h) const { return frmap_head_fit_work((char*)p + (size_t)h * work, B, C); }
+};
+
+__global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void head_fit_group_logits_kernel(
+    const float* __restrict__ x, const int32_t* __restrict__ labels, const int32_t* __restrict__ rows, const uint8_t* __restrict__ keep,
+    const float* __restrict__ hyper, float* w, float* b, void* state, void* workspace, HfGroup gr, int N) {
+  const int h = blockIdx.z;
+  const FrmapHeadFitWork wk = gr.workspace(workspace, h);
+  hf_logits_body(x, labels, gr.rows(rows, h), gr.keep(keep, h), hyper[(size_t)h * FRMAP_HEAD_FIT_HYPER_COLS + FRMAP_HEAD_FIT_HYPER_KEEP_SCALE],
+                 gr.w(w, h), gr.b(b, h), (uint64_t*)gr.state(state, h), wk.z, wk.row_src, N, gr.B, gr.D, gr.C);
+}
+
+// `evaluate`: the figures only - t stays
+__device__ __forceinline__ void hf_softmax_body(const int32_t* __restrict__ labels, const int32_t* __restrict__ row_src, uint64_t* state,
+                                                const float* __restrict__ z, float* __restrict__ g, float* __restrict__ row_loss, int B, int C,
+                                                float ls, bool evaluate) {
   __shared__ unsigned long long s_fig[HF_WAVES][2];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const uint64_t n = state[FRMAP_HEAD_FIT_N];
@@ -316,16 +354,28 @@ __global__ __launch_bounds__(64 * HF_WAVES) void head_fit_softmax_kernel(const i
   }
   // nobody reads t or `rows` in this launch: the update kernel finds the step count already advanced
   if (blockIdx.x == 0 && threadIdx.x == 0 && n) {
-    state[FRMAP_HEAD_FIT_T] += 1;
+    if (!evaluate) state[FRMAP_HEAD_FIT_T] += 1;
     state[FRMAP_HEAD_FIT_ROWS] += n;
   }
 }
 
-__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_update_kernel(const float* __restrict__ x, const uint8_t* __restrict__ keep,
-                                                                        float keep_scale, float* __restrict__ w, float* __restrict__ b,
-                                                                        void* state, const float* __restrict__ g,
-                                                                        const int32_t* __restrict__ row_src, int B, int D, int C,
-                                                                        FrmapHeadFitHyper h, int flags) {
+__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_softmax_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ row_src,
+                                                                         uint64_t* state, const float* __restrict__ z, float* __restrict__ g,
+                                                                         float* __restrict__ row_loss, int B, int C, float ls) {
+  hf_softmax_body(labels, row_src, state, z, g, row_loss, B, C, ls, false);
+}
+
+__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_group_softmax_kernel(const int32_t* __restrict__ labels, const float* __restrict__ hyper,
+                                                                               void* state, void* workspace, HfGroup gr, int evaluate) {
+  const int h = blockIdx.z;
+  const FrmapHeadFitWork wk = gr.workspace(workspace, h);
+  hf_softmax_body(labels, (const int32_t*)wk.row_src, (uint64_t*)gr.state(state, h), (const float*)wk.z, wk.g, wk.row_loss, gr.B, gr.C,
+                  hyper[(size_t)h * FRMAP_HEAD_FIT_HYPER_COLS + 5], evaluate != 0);
+}
+
+__device__ __forceinline__ void hf_update_body(const float* __restrict__ x, const uint8_t* __restrict__ keep, float keep_scale,
+                                               float* __restrict__ w, float* __restrict__ b, void* state, const float* __restrict__ g,
+                                               const int32_t* __restrict__ row_src, int B, int D, int C, const FrmapHeadFitHyper& h, int flags) {
   __shared__ HfSmem sm;
   const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
   const FrmapHeadFitState st = frmap_head_fit_state(state, D, C, amsgrad);
@@ -360,6 +410,35 @@ __global__ __launch_bounds__(64 * HF_WAVES) void head_fit_update_kernel(const fl
       frmap_head_fit_adam(a, tot[q], w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
     }
   }
+}
+
+__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_update_kernel(const float* __restrict__ x, const uint8_t* __restrict__ keep,
+                                                                        float keep_scale, float* __restrict__ w, float* __restrict__ b,
+                                                                        void* state, const float* __restrict__ g,
+                                                                        const int32_t* __restrict__ row_src, int B, int D, int C,
+                                                                        FrmapHeadFitHyper h, int flags) {
+  hf_update_body(x, keep, keep_scale, w, b, state, g, row_src, B, D, C, h, flags);
+}
+
+__global__ __launch_bounds__(64 * HF_WAVES) void head_fit_group_update_kernel(const float* __restrict__ x, const uint8_t* __restrict__ keep,
+                                                                              const float* __restrict__ hyper, float* w, float* b, void* state,
+                                                                              void* workspace, HfGroup gr, int flags) {
+  const int h = blockIdx.z;
+  const float* r = hyper + (size_t)h * FRMAP_HEAD_FIT_HYPER_COLS;
+  const FrmapHeadFitHyper hy = {r[0], r[1], r[2], r[3], r[4], r[5]};
+  const FrmapHeadFitWork wk = gr.workspace(workspace, h);
+  hf_update_body(x, gr.keep(keep, h), r[FRMAP_HEAD_FIT_HYPER_KEEP_SCALE], gr.w(w, h), gr.b(b, h), gr.state(state, h), (const float*)wk.g,
+                 (const int32_t*)wk.row_src, gr.B, gr.D, gr.C, hy, flags);
+}
+
+// n of the step in flight of every head and, with `clear`, the three epoch figures behind it: one thread a head (a kernel, not H
+// strided memset nodes, so that a captured step holds one node for it whatever H is)
+__global__ __launch_bounds__(256) void head_fit_group_clear_kernel(void* state, size_t stride, int H, int clear) {
+  const int h = blockIdx.x * 256 + threadIdx.x;
+  if (h >= H) return;
+  uint64_t* head = (uint64_t*)((char*)state + (size_t)h * stride);
+  head[FRMAP_HEAD_FIT_N] = 0;
+  if (clear) head[FRMAP_HEAD_FIT_ROWS] = head[FRMAP_HEAD_FIT_CORRECT] = head[FRMAP_HEAD_FIT_LOSS_Q] = 0;
 }
 
 extern "C" size_t frmap_head_fit_state_bytes(int D, int C, int amsgrad) {
@@ -421,5 +500,64 @@ extern "C" int frmap_head_fit_step_host(const float* x_host, const int32_t* labe
   const char* why = frmap_head_fit_step_twin(x_host, labels_host, rows_host, keep_host, keep_scale, w_host, b_host, state_host,
                                              workspace_host, N, B, D, C, h, flags, given_g);
   FRMAP_REQUIRE(!why, "head_fit_step_host: %s (N = %d, B = %d, D = %d, C = %d, flags = %d)", why, N, B, D, C, flags);
+  return 0;
+}
+
+extern "C" size_t frmap_head_fit_group_state_stride(int D, int C, int amsgrad) {
+  if (!frmap_head_fit_shape_ok(D, C)) return 0;
+  return frmap_head_fit_group_stride(D, C, amsgrad);
+}
+
+extern "C" size_t frmap_head_fit_group_state_bytes(int H, int D, int C, int amsgrad) {
+  if (!frmap_head_fit_shape_ok(D, C) || H < 1 || H > FRMAP_HEAD_FIT_MAX_H) return 0;
+  return (size_t)H * frmap_head_fit_group_stride(D, C, amsgrad);
+}
+
+extern "C" size_t frmap_head_fit_group_workspace_bytes(int H, int B, int D, int C) {
+  if (H < 1 || H > FRMAP_HEAD_FIT_MAX_H) return 0;
+  return (size_t)H * frmap_head_fit_workspace_bytes(B, D, C);
+}
+
+extern "C" int frmap_head_fit_group_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, const float* hyper,
+                                         float* w, float* b, void* state, void* workspace, int N, int H, int B, int D, int C, int flags,
+                                         void* stream) {
+  const char* why = frmap_head_fit_group_refusal(x, labels, rows, keep, hyper, w, b, state, workspace, N, H, B, D, C, flags);
+  FRMAP_REQUIRE(!why, "head_fit_group_step: %s (N = %d, H = %d, B = %d, D = %d, C = %d, flags = %d)", why, N, H, B, D, C, flags);
+  FRMAP_REQUIRE_ALIGNED(x, 4, "x");
+  FRMAP_REQUIRE_ALIGNED(labels, 4, "labels");
+  FRMAP_REQUIRE_ALIGNED(rows, 4, "rows");
+  FRMAP_REQUIRE_ALIGNED(hyper, 4, "hyper");
+  FRMAP_REQUIRE_ALIGNED(w, 4, "w");
+  FRMAP_REQUIRE_ALIGNED(b, 4, "b");
+  FRMAP_REQUIRE_ALIGNED(state, 8, "state");
+  FRMAP_REQUIRE_ALIGNED(workspace, 4, "workspace");
+  const hipStream_t st = (hipStream_t)stream;
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0, evaluate = (flags & FRMAP_HEAD_FIT_EVAL) ? 1 : 0;
+  const HfGroup gr = {frmap_head_fit_group_stride(D, C, amsgrad), frmap_head_fit_workspace_size(B, C), B, D, C};
+  hipLaunchKernelGGL(head_fit_group_clear_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, state, gr.stride, H,
+                     (flags & FRMAP_HEAD_FIT_CLEAR) ? 1 : 0);
+  FRMAP_LAUNCH_CHECK();
+  // the grids of the single step, with the head as the slowest dimension (H <= 4096: within a grid's z)
+  const int tb = (B + HF_T - 1) / HF_T, tc = (C + HF_T - 1) / HF_T, td = (D + HF_T - 1) / HF_T;
+  hipLaunchKernelGGL(head_fit_group_logits_kernel, dim3((unsigned)tc, (unsigned)tb, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, labels, rows, keep,
+                     hyper, w, b, state, workspace, gr, N);
+  FRMAP_LAUNCH_CHECK();
+  const int want = (B + HF_WAVES - 1) / HF_WAVES;
+  hipLaunchKernelGGL(head_fit_group_softmax_kernel, dim3((unsigned)(want < HF_SOFTMAX_MAX_BLOCKS ? want : HF_SOFTMAX_MAX_BLOCKS), 1u, (unsigned)H),
+                     dim3(64 * HF_WAVES), 0, st, labels, hyper, state, workspace, gr, evaluate);
+  FRMAP_LAUNCH_CHECK();
+  if (evaluate) return 0;
+  hipLaunchKernelGGL(head_fit_group_update_kernel, dim3((unsigned)td + 1, (unsigned)tc, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, keep, hyper, w, b,
+                     state, workspace, gr, flags);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int frmap_head_fit_group_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,
+                                              const float* hyper_host, float* w_host, float* b_host, void* state_host, void* workspace_host,
+                                              int N, int H, int B, int D, int C, int flags, int given_g) {
+  const char* why = frmap_head_fit_group_step_twin(x_host, labels_host, rows_host, keep_host, hyper_host, w_host, b_host, state_host,
+                                                   workspace_host, N, H, B, D, C, flags, given_g);
+  FRMAP_REQUIRE(!why, "head_fit_group_step_host: %s (N = %d, H = %d, B = %d, D = %d, C = %d, flags = %d)", why, N, H, B, D, C, flags);
   return 0;
 }

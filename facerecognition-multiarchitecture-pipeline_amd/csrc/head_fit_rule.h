@@ -29,6 +29,14 @@
 // lanes, the twin serially, and exp / log are each side's library - parts in 2^53 before the one rounding to fp32, so g and the
 // row loss of the two sides differ in a rare last bit at most.  Everything downstream of g is defined on g's fp32 bits.
 //
+// GROUPS (frmap_head_fit_group_step).  H independent heads over ONE cache: x and labels are shared; rows [H][B], keep [H][B][D],
+// w [H][C][D], b [H][C], the states (frmap_head_fit_group_stride bytes apart: the single size rounded up to 8, so that every
+// header stays 8-aligned; padding bytes are never touched) and the workspaces (back to back) are H single-head operands each.
+// The scalars a single step takes by value are row h of hyper [H][8] fp32 in the memory the step runs on: lr, beta1, beta2, eps,
+// weight_decay, label_smoothing, keep_scale, 0.  Head h of a grouped step has the bits of the single step on head h's slices.
+// FRMAP_HEAD_FIT_EVAL (bit 8, groups only): logits, softmax and figures - n is written, rows / correct / loss_q are added to - and
+// nothing else: t, the weights and the moments stay.
+//
 // STATE (frmap_head_fit_state_bytes; all-zero bytes = fresh): eight uint64 words - t, n of the step in flight, and the epoch figures
 // rows, correct, loss_q, three reserved - then fp32 m_w [C D], v_w [C D], m_b [C], v_b [C] and, with AMSGrad, vmax_w [C D], vmax_b [C].
 // WORKSPACE (frmap_head_fit_workspace_bytes): fp32 z [B C], g [B C], row_loss [B], then int32 row_src [B]: the row of x a batch row
@@ -56,6 +64,25 @@ FRMAP_TRACK_HD inline size_t frmap_head_fit_state_size(int D, int C, int amsgrad
   return (((size_t)FRMAP_HEAD_FIT_HEADER * 8 + 4 * per * (amsgrad ? 3 : 2)) + 7) & ~(size_t)7;
 }
 FRMAP_TRACK_HD inline size_t frmap_head_fit_workspace_size(int B, int C) { return 4 * (2 * (size_t)B * (size_t)C + 2 * (size_t)B); }
+
+// groups of heads (the comment at the top, GROUPS)
+constexpr int FRMAP_HEAD_FIT_EVAL = 8;                   // bit of `flags`, grouped step only
+constexpr int FRMAP_HEAD_FIT_MAX_H = 4096;
+constexpr int FRMAP_HEAD_FIT_HYPER_COLS = 8;             // lr, beta1, beta2, eps, weight_decay, label_smoothing, keep_scale, 0
+constexpr int FRMAP_HEAD_FIT_HYPER_KEEP_SCALE = 6;
+static_assert(sizeof(size_t) == 8, "the offsets of a group are size_t products of h, the stride and the extents: 64 bits");
+FRMAP_TRACK_HD inline size_t frmap_head_fit_group_stride(int D, int C, int amsgrad) {
+  return (frmap_head_fit_state_size(D, C, amsgrad) + 7) & ~(size_t)7;
+}
+// whether every byte count of a group (the states, the workspaces, w, keep) is a product that 64 bits hold
+inline bool frmap_head_fit_group_fits(int H, int B, int D, int C, int amsgrad) {
+  unsigned long long states = 0, works = 0, wb = 0, kb = 0, bd = 0;
+  if (__builtin_mul_overflow((unsigned long long)H, (unsigned long long)frmap_head_fit_group_stride(D, C, amsgrad), &states)) return false;
+  if (__builtin_mul_overflow((unsigned long long)H, (unsigned long long)frmap_head_fit_workspace_size(B, C), &works)) return false;
+  if (__builtin_mul_overflow((unsigned long long)H * 4ull, (unsigned long long)C * (unsigned long long)D, &wb)) return false;
+  if (__builtin_mul_overflow((unsigned long long)B, (unsigned long long)D, &bd) || __builtin_mul_overflow((unsigned long long)H, bd, &kb)) return false;
+  return true;
+}
 
 struct FrmapHeadFitState {
   uint64_t* head;

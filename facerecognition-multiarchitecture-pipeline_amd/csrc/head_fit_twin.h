@@ -3,6 +3,8 @@
 // (the device's own, whose exp / log are not the C library's), and the figures, the gradient GEMM and the update run on them, so
 // that the twin's weights and moments can be compared with the kernel's word for word.  Plain C++: the library compiles it into
 // frmap_head_fit_step_host, tools/head_fit_check.cpp into a stand-alone program.
+// frmap_head_fit_group_step_twin is the grouped step (head_fit_rule.h, GROUPS): this twin on the slices of every head, with the
+// stride, the hyper table and flag 8 of the device's (frmap_head_fit_group_step_host, tools/head_fit_group_check.cpp).
 #pragma once
 #include "head_fit_rule.h"
 
@@ -36,10 +38,11 @@ inline int32_t frmap_head_fit_row_src(const float* x, const int32_t* labels, con
   return (int32_t)r;
 }
 
-// NULL, or why the call is refused (nothing written then)
-inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
-                                            float* w, float* b, void* state, void* workspace, int N, int B, int D, int C,
-                                            const FrmapHeadFitHyper& h, int flags, int given_g) {
+// NULL, or why the call is refused (nothing written then).  `flags` may carry FRMAP_HEAD_FIT_EVAL (the grouped step's bit 8): the
+// forward half and the figures only.
+inline const char* frmap_head_fit_step_twin_any(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
+                                                float* w, float* b, void* state, void* workspace, int N, int B, int D, int C,
+                                                const FrmapHeadFitHyper& h, int flags, int given_g) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -48,7 +51,7 @@ inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* label
   if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
   if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
   if (!x || !labels || !w || !b || !state || !workspace) return "null pointer";
-  if (flags & ~7) return "unknown flag bits";
+  if (flags & ~15) return "unknown flag bits";
   const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
   const FrmapHeadFitState st = frmap_head_fit_state(state, D, C, amsgrad);
   const FrmapHeadFitWork wk = frmap_head_fit_work(workspace, B, C);
@@ -105,7 +108,7 @@ inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* label
   st.head[FRMAP_HEAD_FIT_ROWS] += n;
   st.head[FRMAP_HEAD_FIT_CORRECT] += correct;
   st.head[FRMAP_HEAD_FIT_LOSS_Q] += loss_q;
-  if (n == 0) return nullptr;
+  if (n == 0 || (flags & FRMAP_HEAD_FIT_EVAL)) return nullptr;
   st.head[FRMAP_HEAD_FIT_T] += 1;
   const FrmapHeadFitAdam a = frmap_head_fit_adam_scalars(st.head[FRMAP_HEAD_FIT_T], h, flags);
   auto gg = [&](int i, int c) -> float { return wk.row_src[i] < 0 ? 0.0f : wk.g[(size_t)i * (size_t)C + c]; };
@@ -117,6 +120,59 @@ inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* label
     }
     const float db = frmap_head_fit_dot(B, [&](int i) { return gg(i, c); }, [](int) { return 1.0f; });
     frmap_head_fit_adam(a, db, b + c, st.m_b + c, st.v_b + c, amsgrad ? st.vmax_b + c : nullptr);
+  }
+  return nullptr;
+}
+
+// the single step: bits 1, 2 and 4 of `flags`
+inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
+                                            float* w, float* b, void* state, void* workspace, int N, int B, int D, int C,
+                                            const FrmapHeadFitHyper& h, int flags, int given_g) {
+  if (flags & ~7) return "unknown flag bits";
+  return frmap_head_fit_step_twin_any(x, labels, rows, keep, keep_scale, w, b, state, workspace, N, B, D, C, h, flags, given_g);
+}
+
+// what a grouped call is refused for, before anything is read or written: NULL, or the text (it names the argument)
+inline const char* frmap_head_fit_group_refusal(const void* x, const void* labels, const void* rows, const void* keep, const void* hyper,
+                                                const void* w, const void* b, const void* state, const void* workspace, int N, int H, int B,
+                                                int D, int C, int flags) {
+  if (H < 1 || H > FRMAP_HEAD_FIT_MAX_H) return "H is outside [1, 4096]";
+  if (N < 1) return "N is below 1";
+  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
+  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
+  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
+  if (flags & ~15) return "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 8 evaluate only)";
+  if (!rows) return "rows is NULL (a grouped step takes the rows of every head)";
+  if (!hyper) return "hyper is NULL";
+  if (!x || !labels || !w || !b || !state || !workspace) return "null pointer (x, labels, w, b, state and workspace are required)";
+  if (keep && (flags & FRMAP_HEAD_FIT_EVAL)) return "keep is given with flag 8 (evaluate only takes no dropout mask)";
+  if (!frmap_head_fit_group_fits(H, B, D, C, (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0)) return "H, B, D, C give a byte count past 64 bits";
+  return nullptr;
+}
+
+// the hyper-parameters of head h: row h of the table, the values the single step takes by value
+inline FrmapHeadFitHyper frmap_head_fit_group_hyper(const float* hyper, int h, float* keep_scale) {
+  const float* r = hyper + (size_t)h * FRMAP_HEAD_FIT_HYPER_COLS;
+  const FrmapHeadFitHyper hy = {r[0], r[1], r[2], r[3], r[4], r[5]};
+  *keep_scale = r[FRMAP_HEAD_FIT_HYPER_KEEP_SCALE];
+  return hy;
+}
+
+// The grouped step: the single twin on the slices of every head, in ascending h.  `given_g` per head as in the single twin.
+inline const char* frmap_head_fit_group_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep,
+                                                  const float* hyper, float* w, float* b, void* state, void* workspace, int N, int H, int B,
+                                                  int D, int C, int flags, int given_g) {
+  const char* why = frmap_head_fit_group_refusal(x, labels, rows, keep, hyper, w, b, state, workspace, N, H, B, D, C, flags);
+  if (why) return why;
+  const size_t stride = frmap_head_fit_group_stride(D, C, (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0), work = frmap_head_fit_workspace_size(B, C);
+  const size_t cd = (size_t)C * (size_t)D, bd = (size_t)B * (size_t)D;
+  for (int h = 0; h < H; ++h) {
+    float keep_scale;
+    const FrmapHeadFitHyper hy = frmap_head_fit_group_hyper(hyper, h, &keep_scale);
+    why = frmap_head_fit_step_twin_any(x, labels, rows + (size_t)h * (size_t)B, keep ? keep + (size_t)h * bd : nullptr, keep_scale,
+                                       w + (size_t)h * cd, b + (size_t)h * (size_t)C, (char*)state + (size_t)h * stride,
+                                       (char*)workspace + (size_t)h * work, N, B, D, C, hy, flags, given_g);
+    if (why) return why;
   }
   return nullptr;
 }

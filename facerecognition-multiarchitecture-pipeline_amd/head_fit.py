@@ -12,9 +12,13 @@ through a convolution exists here, and none is planned.
 * `step` / `step_host` - the step on device tensors / on numpy arrays through the host twin.
 * `LinearHead` - weight, bias, optimiser state and workspace on the device.
 * `cache_features`, `fit_head` - from a folder of images to a fitted head.
+* `group_step` / `group_step_host` / `group_step_rule`, `HeadGroup` - ``H`` independent heads over one cache advanced by one call
+  (`frmap_head_fit_group_step`): head ``h`` has the bits of `step` on its slices; the hyper-parameters are a table on the device.
+* `kfold_rows`, `cross_validate`, `sweep_heads` - the reference's cross-validation (`src/cross_validation.py`) and the frozen-trunk
+  part of its parameter search (`src/hyperparameter_tuning.py`) on one cache, every fold / trial a head of one group.
 
 Out of scope: gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
-``ArcMarginProduct``, anything that trains a convolution.
+``ArcMarginProduct``, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
 from __future__ import annotations
 
@@ -32,6 +36,9 @@ CHAIN = 128                       # FRMAP_HEAD_FIT_CHAIN: where the dot products
 MAX_C = MAX_D = 65536
 MAX_B = 1 << 20
 DECOUPLED, AMSGRAD, CLEAR = 1, 2, 4
+EVAL = 8                          # grouped step only: figures, no update
+MAX_H = 4096                      # heads of one group
+HYPER_COLUMNS = ("lr", "beta1", "beta2", "eps", "weight_decay", "label_smoothing", "keep_scale")     # of the [H, 8] table; column 7 is 0
 HEADER = ("t", "n", "rows", "correct", "loss_q")     # words 0 .. 4 of the 8-word header
 LOSS_CLAMP, LOSS_SCALE = 65536.0, 16777216.0         # the tally's fixed point (csrc/tally_rule.h)
 F32 = np.float32
@@ -547,3 +554,441 @@ def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10
             tally.update(head.logits(val[0]), val[1])
             history["val"].append(tally.metrics())
     return head, history
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# groups of heads: H independent heads over one cache, advanced by one call
+# ---------------------------------------------------------------------------------------------------------------------------------
+def group_state_stride(D: int, C: int, amsgrad: bool = False) -> int:
+    """Bytes from head h's state to head h + 1's (`frmap_head_fit_group_state_stride`): `state_bytes` rounded up to 8."""
+    n = int(_lib.load().frmap_head_fit_group_state_stride(int(D), int(C), int(bool(amsgrad))))
+    if n == 0:
+        raise ValueError(f"head_fit: unsupported D = {D}, C = {C} (D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
+    return n
+
+
+def group_state_bytes(H: int, D: int, C: int, amsgrad: bool = False) -> int:
+    """Bytes of the states of ``H`` heads (`frmap_head_fit_group_state_bytes`): ``H`` strides."""
+    n = int(_lib.load().frmap_head_fit_group_state_bytes(int(H), int(D), int(C), int(bool(amsgrad))))
+    if n == 0:
+        raise ValueError(f"head_fit: unsupported H = {H}, D = {D}, C = {C} (H in 1 ... {MAX_H}, D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
+    return n
+
+
+def group_workspace_bytes(H: int, B: int, D: int, C: int) -> int:
+    """Bytes of the workspaces of ``H`` heads stepping ``B`` rows each (`frmap_head_fit_group_workspace_bytes`)."""
+    n = int(_lib.load().frmap_head_fit_group_workspace_bytes(int(H), int(B), int(D), int(C)))
+    if n == 0:
+        raise ValueError(f"head_fit: unsupported H = {H}, B = {B}, D = {D}, C = {C} (H in 1 ... {MAX_H}, B in 1 ... {MAX_B}, "
+                         f"D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
+    return n
+
+
+def _per_head(v, H: int, name: str) -> np.ndarray:
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full((H,), float(a))
+    if a.shape != (H,):
+        raise ValueError(f"head_fit: {name} must be a scalar or a sequence of {H} values, got shape {a.shape}")
+    return a
+
+
+def hyper_table(H: int, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, label_smoothing=0.0, keep_scale=1.0) -> np.ndarray:
+    """The float32 ``[H, 8]`` table a grouped step reads (`HYPER_COLUMNS`, a zero last): every value a scalar or one per head,
+    rounded to float32 the way the single step's by-value arguments are."""
+    cols = (lr, beta1, beta2, eps, weight_decay, label_smoothing, keep_scale)
+    t = np.zeros((int(H), 8), np.float32)
+    for k, (name, v) in enumerate(zip(HYPER_COLUMNS, cols)):
+        t[:, k] = _per_head(v, int(H), name).astype(np.float32)
+    return t
+
+
+def _group_flags(decoupled, amsgrad, clear, evaluate) -> int:
+    return _flags(decoupled, amsgrad, clear) | (EVAL if evaluate else 0)
+
+
+def group_step_rule(x, labels, w, b, states, rows, keep=None, *, hyper, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
+                    evaluate: bool = False, dtype=np.float64, given=None) -> list:
+    """The grouped step in numpy: ``H`` calls of `step_rule`, head ``h`` on ``w[h]``, ``b[h]``, ``states[h]`` (a rule state or
+    ``None``), ``rows[h]``, ``keep[h]`` and row ``h`` of ``hyper`` (`hyper_table`).  ``evaluate``: the weights, the moments and ``t``
+    of the returned dicts are the inputs'; only ``n`` and the figures are the step's.  Returns the list of `step_rule` results."""
+    hyper = np.asarray(hyper, np.float32)
+    H = len(w)
+    if hyper.shape != (H, 8) or len(rows) != H:
+        raise ValueError(f"head_fit.group_step_rule: hyper [{H}, 8] and rows [{H}, B] expected")
+    out = []
+    for h in range(H):
+        hy = hyper[h]
+        st = None if states is None else states[h]
+        r = step_rule(x, labels, w[h], b[h], st, rows[h], None if keep is None else keep[h], float(hy[6]), lr=float(hy[0]),
+                      beta1=float(hy[1]), beta2=float(hy[2]), eps=float(hy[3]), weight_decay=float(hy[4]), label_smoothing=float(hy[5]),
+                      decoupled=decoupled, amsgrad=amsgrad, clear=clear, dtype=dtype, given=None if given is None else given[h])
+        if evaluate:
+            D, C = np.asarray(w[h]).shape[1], np.asarray(w[h]).shape[0]
+            old = {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in (st or fresh_state(D, C, amsgrad, dtype)).items()}
+            for k in ("n", "rows", "correct", "loss_q"):
+                old[k] = r["state"][k]
+            r["w"], r["b"], r["state"] = np.array(w[h], dtype), np.array(b[h], dtype), old
+        out.append(r)
+    return out
+
+
+def group_step_host(x, labels, rows, hyper, w, b, state: np.ndarray, workspace: Optional[np.ndarray] = None, keep=None, *,
+                    decoupled: bool = False, amsgrad: bool = False, clear: bool = False, evaluate: bool = False, given_g: bool = False):
+    """The grouped step on the CPU over numpy arrays (`frmap_head_fit_group_step_host`: the single host step looped over the heads).
+    ``rows`` int32 ``[H, B]``, ``hyper`` float32 ``[H, 8]`` (`hyper_table`), ``w`` ``[H, C, D]``, ``b`` ``[H, C]`` and ``state`` (uint8,
+    `group_state_bytes` bytes, 8-byte aligned) are updated IN PLACE; ``workspace`` (uint8, exactly `group_workspace_bytes` bytes, or
+    ``None`` for a fresh one) receives every head's z, g, row_loss and row_src; ``keep`` uint8 ``[H, B, D]`` or ``None``.  Returns the
+    workspace."""
+    op = "head_fit.group_step_host"
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if x.ndim != 2 or labels.shape != (x.shape[0],):
+        raise ValueError(f"{op}: x [N, D] and labels [N] expected")
+    N, D = x.shape
+    for name, t, dt in (("w", w, np.float32), ("b", b, np.float32), ("state", state, np.uint8)):
+        if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
+            raise ValueError(f"{op}: {name} must be a writable contiguous {np.dtype(dt).name} array")
+    if w.ndim != 3 or w.shape[2] != D or b.shape != w.shape[:2]:
+        raise ValueError(f"{op}: w [H, C, {D}] and b [H, C] expected, got {w.shape} and {b.shape}")
+    H, C = int(w.shape[0]), int(w.shape[1])
+    if rows is None:
+        raise ValueError(f"{op}: rows [H, B] is required")
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    if rows.ndim != 2 or rows.shape[0] != H:
+        raise ValueError(f"{op}: rows must be [{H}, B], got {rows.shape}")
+    B = int(rows.shape[1])
+    if hyper is None:
+        raise ValueError(f"{op}: hyper [H, 8] is required")
+    hyper = np.ascontiguousarray(hyper, dtype=np.float32)
+    if hyper.shape != (H, 8):
+        raise ValueError(f"{op}: hyper must be [{H}, 8], got {hyper.shape}")
+    if keep is not None:
+        if evaluate:
+            raise ValueError(f"{op}: keep cannot be given with evaluate=True")
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.shape != (H, B, D):
+            raise ValueError(f"{op}: keep must be [{H}, {B}, {D}], got {keep.shape}")
+    nstate = group_state_bytes(H, D, C, amsgrad)
+    if state.shape != (nstate,) or state.ctypes.data % 8:
+        raise ValueError(f"{op}: state must be {nstate} bytes, 8-byte aligned")
+    nbytes = group_workspace_bytes(H, B, D, C)
+    if workspace is None:
+        if given_g:
+            raise ValueError(f"{op}: given_g needs the workspace that holds z, g and row_loss")
+        workspace = np.zeros((nbytes,), np.uint8)
+    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
+            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
+        raise ValueError(f"{op}: workspace must be a writable uint8 array of exactly {nbytes} bytes")
+    _lib.check(_lib.load().frmap_head_fit_group_step_host(x.ctypes.data, labels.ctypes.data, rows.ctypes.data,
+                                                          keep.ctypes.data if keep is not None else 0, hyper.ctypes.data, w.ctypes.data,
+                                                          b.ctypes.data, state.ctypes.data, workspace.ctypes.data, N, H, B, D, C,
+                                                          _group_flags(decoupled, amsgrad, clear, evaluate), int(bool(given_g))), op)
+    return workspace
+
+
+@ops._on_operand_device
+def group_step(x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, hyper: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
+               state: torch.Tensor, workspace: torch.Tensor, keep: Optional[torch.Tensor] = None, *, decoupled: bool = False,
+               amsgrad: bool = False, clear: bool = False, evaluate: bool = False) -> None:
+    """One step of ``H`` heads on the current stream (`frmap_head_fit_group_step`; nothing is copied or synchronised).  ``x`` float32
+    ``[N, D]`` and ``labels`` int32 ``[N]`` are shared; ``w`` float32 ``[H, C, D]`` and ``b`` ``[H, C]`` (updated in place), ``rows``
+    int32 ``[H, B]`` (an entry outside ``[0, N)`` declines that batch row), ``hyper`` float32 ``[H, 8]`` ON THE DEVICE
+    (`hyper_table`), ``state`` uint8 of `group_state_bytes` bytes (zeros = fresh), ``workspace`` uint8 of exactly
+    `group_workspace_bytes` bytes, ``keep`` uint8 ``[H, B, D]`` or ``None``.  ``evaluate``: figures only (flag 8; no ``keep``).
+    Every extent that depends on another operand is checked here, before the library sees a pointer."""
+    op, entry = "head_fit.group_step", "frmap_head_fit_group_step"
+    x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
+    N, D = int(x.shape[0]), int(x.shape[1])
+    if not isinstance(w, torch.Tensor) or w.dim() != 3:
+        raise ValueError(f"{op}: w [H, C, D] expected, got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
+    H, C = int(w.shape[0]), int(w.shape[1])
+    _sized(w, op, "w", (H, C, D), torch.float32)
+    _sized(labels, op, "labels", (N,), torch.int32)
+    _sized(b, op, "b", (H, C), torch.float32)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
+        raise ValueError(f"{op}: rows [H, B] expected, got {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
+    B = int(rows.shape[1])
+    _sized(rows, op, "rows", (H, B), torch.int32)
+    _sized(hyper, op, "hyper", (H, 8), torch.float32)
+    if keep is not None:
+        if evaluate:
+            raise ValueError(f"{op}: keep cannot be given with evaluate=True (flag 8 takes no dropout mask)")
+        _sized(keep, op, "keep", (H, B, D), torch.uint8)
+    _sized(state, op, "state", (group_state_bytes(H, D, C, amsgrad),), torch.uint8)
+    _sized(workspace, op, "workspace", (group_workspace_bytes(H, B, D, C),), torch.uint8)
+    held = []                                                   # copies `_dev` made live until the launch is enqueued
+    labels = _dev(labels, f"{op}.labels", torch.int32, (entry, "labels"))
+    rows = _dev(rows, f"{op}.rows", torch.int32, (entry, "rows"))
+    hyper = _dev(hyper, f"{op}.hyper", torch.float32, (entry, "hyper"))
+    keep = None if keep is None else _dev(keep, f"{op}.keep", torch.uint8, (entry, "keep"))
+    held += [x, labels, rows, hyper, keep]
+    w = _dev(w, f"{op}.w", torch.float32, (entry, "w"), owned=True)
+    b = _dev(b, f"{op}.b", torch.float32, (entry, "b"), owned=True)
+    state = _dev(state, f"{op}.state", torch.uint8, (entry, "state"), owned=True)
+    workspace = _dev(workspace, f"{op}.workspace", torch.uint8, (entry, "workspace"), owned=True)
+    _lib.check(_lib.load().frmap_head_fit_group_step(x.data_ptr(), labels.data_ptr(), rows.data_ptr(), keep.data_ptr() if keep is not None else 0,
+                                                     hyper.data_ptr(), w.data_ptr(), b.data_ptr(), state.data_ptr(), workspace.data_ptr(),
+                                                     N, H, B, D, C, _group_flags(decoupled, amsgrad, clear, evaluate), _stream()), op)
+    del held
+
+
+class HeadGroup:
+    """``H`` linear softmax heads ``[C, D]`` over one cache, with their Adam states, workspaces and the device-resident hyper table
+    (`group_step`).  The heads are initialised as ``H`` consecutive `LinearHead` objects would be from ``generator``; with ``shared_init``
+    all of them start from head 0's draw (a parameter sweep compares settings, not initialisations)."""
+
+    def __init__(self, H: int, D: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None,
+                 shared_init: bool = False):
+        self.H, self.D, self.C, self.amsgrad = int(H), int(D), int(C), bool(amsgrad)
+        nbytes = group_state_bytes(self.H, self.D, self.C, self.amsgrad)          # (refuses a bad shape)
+        self.stride = group_state_stride(self.D, self.C, self.amsgrad)
+        bound = 1.0 / math.sqrt(self.D)
+        ws, bs = [], []
+        for h in range(self.H):
+            if h == 0 or not shared_init:
+                w = (torch.rand((self.C, self.D), generator=generator, dtype=torch.float32) * 2 - 1) * bound
+                b = (torch.rand((self.C,), generator=generator, dtype=torch.float32) * 2 - 1) * bound
+            ws.append(w)
+            bs.append(b)
+        self.device = torch.device(device)
+        self.weight, self.bias = torch.stack(ws).to(self.device), torch.stack(bs).to(self.device)
+        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
+        self.hyper = torch.zeros((self.H, 8), dtype=torch.float32, device=self.device)
+        self._hyper_host = np.zeros((self.H, 8), np.float32)
+        self._workspaces = {}
+        self._clear = True
+
+    def _workspace(self, B: int) -> torch.Tensor:
+        ws = self._workspaces.get(B)
+        if ws is None:
+            ws = self._workspaces[B] = torch.empty((group_workspace_bytes(self.H, B, self.D, self.C),), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def set_hyper(self, table: np.ndarray) -> "HeadGroup":
+        """Write the hyper table (`hyper_table`) with one host-to-device copy, and only when a value changed."""
+        table = np.ascontiguousarray(table, np.float32)
+        if table.shape != (self.H, 8):
+            raise ValueError(f"HeadGroup.set_hyper: a [{self.H}, 8] table expected, got {table.shape}")
+        if not np.array_equal(table.view(np.uint32), self._hyper_host.view(np.uint32)):
+            self.hyper.copy_(torch.from_numpy(table))
+            self._hyper_host = table.copy()
+        return self
+
+    def new_epoch(self) -> "HeadGroup":
+        """The next `step` or `evaluate` clears every head's epoch figures first."""
+        self._clear = True
+        return self
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, keep: Optional[torch.Tensor] = None, *, lr,
+             weight_decay=0.0, dropout=0.0, label_smoothing=0.0, beta1=0.9, beta2=0.999, eps=1e-8, decoupled: bool = False) -> "HeadGroup":
+        """One step of every head over its rows ``rows[h]`` of the cache (`group_step`).  Every hyper-parameter is a scalar or a
+        sequence of ``H`` values; ``keep``: a uint8 ``[H, B, D]`` dropout mask, head ``h``'s scaled by ``1 / (1 - dropout[h])``.  No
+        synchronisation beyond the table's copy when a value changed."""
+        keep_scale = 1.0 / (1.0 - _per_head(dropout, self.H, "dropout")) if keep is not None else 1.0
+        self.set_hyper(hyper_table(self.H, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                                   label_smoothing=label_smoothing, keep_scale=keep_scale))
+        B = int(rows.shape[1]) if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 1
+        group_step(x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), keep, decoupled=decoupled,
+                   amsgrad=self.amsgrad, clear=self._clear)
+        self._clear = False
+        return self
+
+    def evaluate(self, x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor) -> "HeadGroup":
+        """Add the figures of rows ``rows[h]`` under every head's current weights (flag 8): nothing else changes.  The loss is the
+        training loss of the table's ``label_smoothing``."""
+        B = int(rows.shape[1]) if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 1
+        group_step(x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), None, amsgrad=self.amsgrad,
+                   clear=self._clear, evaluate=True)
+        self._clear = False
+        return self
+
+    def epoch_figures(self) -> list:
+        """ONE host copy of the ``H`` headers: per head what `LinearHead.epoch_figures` returns."""
+        words = self.state.view(self.H, self.stride)[:, :64].cpu().numpy().view(np.uint64)
+        out = []
+        for h in range(self.H):
+            fig = figures_of({name: words[h, k] for k, name in enumerate(HEADER)})
+            fig["t"] = int(words[h, 0])
+            out.append(fig)
+        return out
+
+    def head(self, h: int) -> LinearHead:
+        """Head ``h`` as a `LinearHead` whose ``weight``, ``bias`` and ``state`` are VIEWS of the group's memory: `logits`,
+        `state_dict`, `load_into` and `as_classifier` read the group's weights, and a single `step` on it continues head ``h``'s fit."""
+        if not 0 <= int(h) < self.H:
+            raise IndexError(f"HeadGroup.head: {h} is outside 0 ... {self.H - 1}")
+        h = int(h)
+        one = LinearHead.__new__(LinearHead)
+        one.D, one.C, one.amsgrad, one.device = self.D, self.C, self.amsgrad, self.device
+        one.weight, one.bias = self.weight[h], self.bias[h]
+        one.state = self.state[h * self.stride: h * self.stride + state_bytes(self.D, self.C, self.amsgrad)]
+        one._workspaces, one._clear = {}, False
+        return one
+
+
+def kfold_rows(N: int, n_folds: int = 5, seed: int = 42) -> list:
+    """Per fold ``(train_idx, val_idx)`` as ascending int32 arrays: the split of
+    ``sklearn.model_selection.KFold(n_folds, shuffle=True, random_state=seed).split(range(N))``, the reference's splitter
+    (`src/cross_validation.py:97`), index for index, in numpy: ``RandomState(seed).shuffle(arange(N))``; fold ``k`` validates on
+    the next ``N // n_folds`` shuffled indices (one more for the first ``N % n_folds`` folds)."""
+    N, k = int(N), int(n_folds)
+    if k < 2 or k > N:
+        raise ValueError(f"head_fit.kfold_rows: n_folds = {k} must be in 2 ... N = {N}")
+    idx = np.arange(N)
+    np.random.RandomState(int(seed)).shuffle(idx)
+    sizes = np.full((k,), N // k, dtype=np.int64)
+    sizes[: N % k] += 1
+    out, at = [], 0
+    for size in sizes:
+        mask = np.zeros((N,), bool)
+        mask[idx[at: at + size]] = True
+        out.append((np.flatnonzero(~mask).astype(np.int32), np.flatnonzero(mask).astype(np.int32)))
+        at += int(size)
+    return out
+
+
+def _generators(generator, device):
+    """(the CPU generator the heads are drawn from, the device generator of permutations and masks) of `fit_head`'s convention."""
+    head_gen = generator if generator is not None and generator.device.type == "cpu" else None
+    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
+    if generator is not None and dev_gen is None:
+        dev_gen = torch.Generator(device=device)
+        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
+    return head_gen, dev_gen
+
+
+def padded_rows(index_sets, batch_size: int, device) -> torch.Tensor:
+    """int32 ``[H, nb * batch_size]`` on ``device``: row ``h`` is ``index_sets[h]`` (a device int32 vector) followed by -1 up to a
+    common whole number ``nb`` of batches."""
+    B = int(batch_size)
+    nb = max(1, max(-(-int(t.shape[0]) // B) for t in index_sets))
+    out = torch.full((len(index_sets), nb * B), -1, dtype=torch.int32, device=device)
+    for h, t in enumerate(index_sets):
+        out[h, : t.shape[0]] = t
+    return out
+
+
+def epoch_rows(index_sets, batch_size: int, generator=None) -> torch.Tensor:
+    """One epoch's training rows: a fresh device permutation of every head's index set, in the order of the heads, padded with -1
+    (`padded_rows`)."""
+    dev = index_sets[0].device
+    return padded_rows([t[torch.randperm(int(t.shape[0]), device=dev, generator=generator)] for t in index_sets], batch_size, dev)
+
+
+def draw_keep(H: int, B: int, D: int, dropout, device, generator=None) -> torch.Tensor:
+    """A fresh uint8 ``[H, B, D]`` dropout mask: one uniform draw, kept where it is at least ``dropout`` (a number, or a tensor
+    already on ``device`` that broadcasts against ``[H, B, D]``: nothing is uploaded here)."""
+    return (torch.rand((H, B, D), device=device, generator=generator) >= dropout).to(torch.uint8)
+
+
+def _run_epoch(group, feats, labels, rows_all, B, D, dropout, dev_gen, step_kw):
+    """All training batches of one epoch; returns the epoch's figures (the one host copy)."""
+    use_keep = float(dropout) > 0
+    group.new_epoch()
+    for lo in range(0, int(rows_all.shape[1]), B):
+        keep = draw_keep(group.H, B, D, float(dropout), feats.device, dev_gen) if use_keep else None
+        group.step(feats, labels, rows_all[:, lo: lo + B].contiguous(), keep, dropout=dropout, **step_kw)
+    return group.epoch_figures()
+
+
+def _run_eval(group, feats, labels, rows_all, B):
+    group.new_epoch()
+    for lo in range(0, int(rows_all.shape[1]), B):
+        group.evaluate(feats, labels, rows_all[:, lo: lo + B].contiguous())
+    return group.epoch_figures()
+
+
+def cross_validate(feats: torch.Tensor, labels: torch.Tensor, n_folds: int = 5, epochs: int = 15, batch_size: int = 32, seed: int = 42,
+                   lr: float = 1e-3, weight_decay: float = 1e-4, dropout: float = 0.1, label_smoothing: float = 0.0, decoupled: bool = False,
+                   amsgrad: bool = False, num_classes: Optional[int] = None, generator: Optional[torch.Generator] = None) -> dict:
+    """K-fold cross-validation of a head over cached features, all folds in one `HeadGroup` (the reference's
+    `src/cross_validation.py` with the trunk frozen: 5 folds x 15 epochs at batch 32, `KFold(shuffle=True, random_state=seed)`).
+    Per epoch: one device permutation per fold over that fold's training rows (`epoch_rows`), fresh masks (`draw_keep`), all folds'
+    training steps in grouped calls, then grouped `evaluate` calls over the validation rows - two figure copies an epoch and no
+    other host copy inside it.  Returns the reference's dict (``n_folds``, ``fold_results`` with ``fold`` from 1 and
+    ``best_validation_accuracy``, ``mean_accuracy``, ``std_accuracy`` = ``np.mean`` / ``np.std``) plus ``history``: per fold the
+    lists ``train_loss``, ``train_acc``, ``val_loss``, ``val_acc``; and ``group``, the fitted `HeadGroup`."""
+    if feats.dim() != 2:
+        raise ValueError(f"head_fit.cross_validate: feats [N, D] expected, got {tuple(feats.shape)}")
+    N, D, B = int(feats.shape[0]), int(feats.shape[1]), int(batch_size)
+    C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
+    H = int(n_folds)
+    folds = kfold_rows(N, H, seed)
+    head_gen, dev_gen = _generators(generator, feats.device)
+    group = HeadGroup(H, D, C, feats.device, amsgrad=amsgrad, generator=head_gen)
+    train = [torch.from_numpy(tr).to(feats.device) for tr, _ in folds]
+    val_rows = padded_rows([torch.from_numpy(va).to(feats.device) for _, va in folds], B, feats.device)
+    step_kw = dict(lr=lr, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
+    history = [{"train_loss": [], "train_acc": [], "val_loss": [], "val_acc": []} for _ in range(H)]
+    best = [0.0] * H
+    for _ in range(int(epochs)):
+        tfig = _run_epoch(group, feats, labels, epoch_rows(train, B, dev_gen), B, D, dropout, dev_gen, step_kw)
+        vfig = _run_eval(group, feats, labels, val_rows, B)
+        for h in range(H):
+            history[h]["train_loss"].append(tfig[h]["loss"])
+            history[h]["train_acc"].append(tfig[h]["accuracy"])
+            history[h]["val_loss"].append(vfig[h]["loss"])
+            history[h]["val_acc"].append(vfig[h]["accuracy"])
+            if vfig[h]["accuracy"] > best[h]:
+                best[h] = vfig[h]["accuracy"]
+    fold_results = [{"fold": h + 1, "best_validation_accuracy": best[h]} for h in range(H)]
+    acc = [r["best_validation_accuracy"] for r in fold_results]
+    return {"n_folds": H, "fold_results": fold_results, "mean_accuracy": float(np.mean(acc)), "std_accuracy": float(np.std(acc)),
+            "history": history, "group": group}
+
+
+def sweep_heads(feats: torch.Tensor, labels: torch.Tensor, val_feats: torch.Tensor, val_labels: torch.Tensor, trials, epochs: int = 10,
+                batch_size: int = 32, decoupled: bool = False, amsgrad: bool = False, num_classes: Optional[int] = None,
+                generator: Optional[torch.Generator] = None) -> dict:
+    """A parameter sweep over cached features (the frozen-trunk part of the reference's `src/hyperparameter_tuning.py`): one head
+    per trial in one `HeadGroup`.  ``trials``: a list of dicts over ``lr``, ``weight_decay``, ``dropout``, ``label_smoothing``
+    (missing keys: `fit_head`'s defaults).  All trials start from the same weights (``shared_init``) and see the same rows in the
+    same permutation and the same uniform draw behind their masks.  The validation rows are appended to the cache so that one grouped
+    `evaluate` reads them.  The sampler, pruner and schedulers of the reference stay with the caller, who supplies the trials.
+    Returns ``{"trials": [{"params", "val_acc": [...], "val_loss": [...], "best_validation_accuracy"}], "best_trial": index,
+    "best_params", "group"}``; ties go to the earlier trial."""
+    trials = [dict(t) for t in trials]
+    H = len(trials)
+    if H < 1:
+        raise ValueError("head_fit.sweep_heads: at least one trial expected")
+    unknown = sorted({k for t in trials for k in t} - {"lr", "weight_decay", "dropout", "label_smoothing"})
+    if unknown:
+        raise ValueError(f"head_fit.sweep_heads: a trial may set lr, weight_decay, dropout and label_smoothing, not {unknown}")
+    defaults = {"lr": 1e-3, "weight_decay": 1e-4, "dropout": 0.1, "label_smoothing": 0.0}
+    col = {k: [float(t.get(k, v)) for t in trials] for k, v in defaults.items()}
+    N, D, B = int(feats.shape[0]), int(feats.shape[1]), int(batch_size)
+    C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
+    cache = torch.cat([feats, val_feats]).contiguous()
+    cache_labels = torch.cat([labels, val_labels]).to(torch.int32).contiguous()
+    head_gen, dev_gen = _generators(generator, feats.device)
+    group = HeadGroup(H, D, C, feats.device, amsgrad=amsgrad, generator=head_gen, shared_init=True)
+    val_one = torch.arange(N, N + int(val_feats.shape[0]), dtype=torch.int32, device=feats.device)
+    val_rows = padded_rows([val_one] * H, B, feats.device)
+    step_kw = dict(lr=col["lr"], weight_decay=col["weight_decay"], label_smoothing=col["label_smoothing"], decoupled=decoupled)
+    out = [{"params": {k: col[k][h] for k in defaults}, "val_acc": [], "val_loss": [], "train_acc": [], "train_loss": []} for h in range(H)]
+    use_keep = any(p > 0 for p in col["dropout"])
+    drop = torch.tensor(col["dropout"], dtype=torch.float32, device=feats.device).reshape(H, 1, 1)
+    for _ in range(int(epochs)):
+        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
+        rows_all = padded_rows([perm] * H, B, feats.device)
+        group.new_epoch()
+        for lo in range(0, int(rows_all.shape[1]), B):
+            keep = None
+            if use_keep:                                          # one uniform draw for all trials: they differ in the threshold only
+                u = torch.rand((B, D), device=feats.device, generator=dev_gen)
+                keep = (u[None] >= drop).to(torch.uint8)
+            group.step(cache, cache_labels, rows_all[:, lo: lo + B].contiguous(), keep, dropout=col["dropout"], **step_kw)
+        tfig = group.epoch_figures()
+        vfig = _run_eval(group, cache, cache_labels, val_rows, B)
+        for h in range(H):
+            out[h]["train_acc"].append(tfig[h]["accuracy"])
+            out[h]["train_loss"].append(tfig[h]["loss"])
+            out[h]["val_acc"].append(vfig[h]["accuracy"])
+            out[h]["val_loss"].append(vfig[h]["loss"])
+    for t in out:
+        t["best_validation_accuracy"] = max(t["val_acc"]) if t["val_acc"] else float("nan")
+    best = max(range(H), key=lambda h: (out[h]["best_validation_accuracy"], -out[h]["val_loss"][-1] if out[h]["val_loss"] else 0.0, -h))
+    return {"trials": out, "best_trial": best, "best_params": out[best]["params"], "group": group}

@@ -678,6 +678,39 @@ int frmap_head_fit_step_host(const float* x_host, const int32_t* labels_host, co
                              int D, int C, float lr, float beta1, float beta2, float eps, float weight_decay, float label_smoothing,
                              int flags, int given_g);
 
+/* Head fitting in groups: H independent heads over ONE cache advanced by one call - the folds of a cross-validation, the trials
+ * of a parameter sweep.  Head h of a grouped step has exactly the bits of frmap_head_fit_step run on head h's slices alone: the
+ * rule, the 128-long chains and the tile code are the single step's; the head is the slowest dimension of every grid.
+ * Shared by all heads: x [N][D], labels [N].  Per head, H single-head operands back to back: rows [H][B] (required: an entry
+ * outside [0, N), -1 say, declines that batch row - the padding of a head with fewer rows than B), keep [H][B][D] or NULL for all
+ * heads, w [H][C][D], b [H][C], the states frmap_head_fit_group_state_stride bytes apart (the single size rounded up to a multiple
+ * of 8, so that every head's uint64 header is 8-aligned; padding bytes are neither read nor written), the workspaces
+ * frmap_head_fit_workspace_bytes apart.
+ * hyper [H][8] fp32 in DEVICE memory: lr, beta1, beta2, eps, weight_decay, label_smoothing, keep_scale, 0.  The kernels read a
+ * head's row where the single step takes its scalars by value (the same fp32 values give the same bits), so a learning rate is
+ * changed by writing the table on the stream and a captured step replays with what the table holds at replay time.
+ * flags: 1, 2 and 4 as in the single step, for the whole group (2 decides the state size); 8 = evaluate only: logits, softmax and
+ * figures - every head's n is written and its rows, correct and loss_q are added to; t, w, b and the moments are not touched - and
+ * keep must be NULL.  The figures a training step adds are those of its weights BEFORE the update, so an evaluate call adds what a
+ * training step on a copy of the head would.
+ * Launches: one small kernel that zeroes every head's n (with 4: its three figures too) - no memset nodes -, then the three kernels
+ * of the single step (two with flag 8).  A head whose rows are all declined changes nothing of its own and keeps its t while its
+ * neighbours proceed.
+ * Refused (-1, the text names the argument): H outside [1, 4096]; the single step's limits on N, B, D, C; rows or hyper NULL;
+ * flag bits above 15; keep with flag 8.  The size queries return 0 for arguments the launcher would refuse.
+ * x, labels, rows, hyper, w, b and workspace need their element size (4), keep 1, state the size of a uint64 counter (8).
+ * The host form loops the single host step over the heads with the same stride and table (host pointers, flag 8 included);
+ * given_g means per head what it means there. */
+size_t frmap_head_fit_group_state_stride(int D, int C, int amsgrad);
+size_t frmap_head_fit_group_state_bytes(int H, int D, int C, int amsgrad);
+size_t frmap_head_fit_group_workspace_bytes(int H, int B, int D, int C);
+int frmap_head_fit_group_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, const float* hyper,
+                              float* w, float* b, void* state, void* workspace, int N, int H, int B, int D, int C, int flags,
+                              void* stream);
+int frmap_head_fit_group_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,
+                                   const float* hyper_host, float* w_host, float* b_host, void* state_host, void* workspace_host,
+                                   int N, int H, int B, int D, int C, int flags, int given_g);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
