@@ -107,6 +107,12 @@ PROTOTYPES = {
     "frmap_head_fit_group_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "frmap_head_fit_group_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "frmap_head_fit_group_step_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i]),
+    "frmap_head_fit_hidden_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "frmap_head_fit_hidden_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "frmap_head_fit_hidden_step": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f,
+                                        _i, _vp]),
+    "frmap_head_fit_hidden_step_host": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                                             _f, _i, _i]),
     "frmap_head_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_top1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
@@ -201,6 +207,8 @@ ALIGNMENT = {
     "frmap_head_fit_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep": _E1, "w": _E4, "b": _E4, "state": _E8, "workspace": _E4},
     "frmap_head_fit_group_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep": _E1, "hyper": _E4, "w": _E4, "b": _E4, "state": _E8,
                                   "workspace": _E4},
+    "frmap_head_fit_hidden_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep1": _E1, "keep2": _E1, "w1": _E4, "b1": _E4, "w2": _E4, "b2": _E4,
+                                   "state": _E8, "workspace": _E4},
     "frmap_match_top1": {"emb": _M, "gallery": _M, **_TOP1_OUT, "workspace": _W},
     "frmap_match_pack_gallery": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
     "frmap_match_pack_gallery_rows": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},

@@ -41,6 +41,29 @@
 // rows, correct, loss_q, three reserved - then fp32 m_w [C D], v_w [C D], m_b [C], v_b [C] and, with AMSGrad, vmax_w [C D], vmax_b [C].
 // WORKSPACE (frmap_head_fit_workspace_bytes): fp32 z [B C], g [B C], row_loss [B], then int32 row_src [B]: the row of x a batch row
 // reads, or -1 for a declined one.
+//
+// HIDDEN LAYER (frmap_head_fit_hidden_step; head_fit.hidden_step_rule in numpy).  Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C): plain
+// backpropagation through one ReLU.  x, labels and rows are the linear step's; keep1 [B, D] / keep1_scale mask the input, keep2 [B, Hd] /
+// keep2_scale the hidden layer; the parameters are w1 [Hd, D], b1 [Hd], w2 [C, Hd], b2 [C].
+//   x'       = frmap_head_fit_xp(x, keep1, keep1_scale)
+//   a[i][j]  = dot_k(x'[i][k], w1[j][k]) + b1[j]                              chain order over D, bias last
+//   h[i][j]  = a > 0 ? a : (a != a ? a : +0)                                  a NaN stays one; -0 and negatives give +0
+//   lab[i]   = labels[rows[i]], or -1 where layer 1 declines row i (row index outside [0, N), label outside [0, C), a non-finite
+//              feature); the h row of such a row is +0.  row_src1[i] is the row of x read, or -1.
+//   layer 2  = the linear step's forward half on (x := h [B, Hd], labels := lab [B], rows := NULL, keep := keep2, w2, b2):
+//              h' = xp(h, keep2, keep2_scale), z, the float64 softmax, the row loss, g = (p - y) / n, the figures.  It declines a row
+//              whose lab is -1 or whose h holds a non-finite value.  n is ITS count: the one n of the step.
+//   s[i][j]  = dot_c(g[i][c], w2[c][j])                                       chain order over C, w2 BEFORE its update
+//   da[i][j] = (row i counted by layer 2) && h[i][j] > 0 && kept2[i][j] ? fl(s * keep2_scale) : +0      (no mask: s itself)
+//   dw2, db2 = the linear step's on (g, h');  dw1[j][d] = dot_i(da[i][j], x'[i][d]), db1[j] = dot_i(da[i][j], 1), the rows that
+//              layer 1 declined taken as da = x' = +0
+//   update   = frmap_head_fit_adam on all four with the same hyper-parameters and the same t (one optimiser over four tensors).
+//              n == 0: nothing changes but the workspace.
+// HIDDEN STATE (frmap_head_fit_hidden_state_bytes): the single layout for (D, Hd), then the single layout for (Hd, C); both are
+// multiples of 8 and all-zero bytes are a fresh state.  The second part is a valid state of the linear step on (h, lab): its header
+// carries t, n and the epoch figures.  The first part's t and n are copies written by the step; its figure words stay 0.
+// HIDDEN WORKSPACE (frmap_head_fit_hidden_workspace_bytes): fp32 h [B Hd], da [B Hd], int32 lab [B], row_src1 [B], then the single
+// workspace for (B, Hd -> C).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -237,4 +260,39 @@ FRMAP_TRACK_HD inline void frmap_head_fit_adam(const FrmapHeadFitAdam& a, float 
   *p_io = p;
   *m_io = m;
   *v_io = v;
+}
+
+// the hidden-layer step (the comment at the top, HIDDEN LAYER)
+FRMAP_TRACK_HD inline bool frmap_head_fit_hidden_shape_ok(int D, int Hd, int C) {
+  return frmap_head_fit_shape_ok(D, Hd) && frmap_head_fit_shape_ok(Hd, C);
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_hidden_state_size(int D, int Hd, int C, int amsgrad) {
+  return frmap_head_fit_state_size(D, Hd, amsgrad) + frmap_head_fit_state_size(Hd, C, amsgrad);
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_hidden_workspace_size(int B, int Hd, int C) {
+  return 4 * (2 * (size_t)B * (size_t)Hd + 2 * (size_t)B) + frmap_head_fit_workspace_size(B, C);
+}
+struct FrmapHeadFitHiddenWork {
+  float *h, *da;
+  int32_t *lab, *row_src1;
+  void* layer2;              // the single workspace for (B, Hd -> C)
+};
+FRMAP_TRACK_HD inline FrmapHeadFitHiddenWork frmap_head_fit_hidden_work(void* workspace, int B, int Hd) {
+  FrmapHeadFitHiddenWork k;
+  k.h = (float*)workspace;
+  k.da = k.h + (size_t)B * (size_t)Hd;
+  k.lab = (int32_t*)(k.da + (size_t)B * (size_t)Hd);
+  k.row_src1 = k.lab + B;
+  k.layer2 = (void*)(k.row_src1 + B);
+  return k;
+}
+// h of one pre-activation: a NaN stays one; -0 and negatives give +0
+FRMAP_TRACK_HD inline float frmap_head_fit_relu(float a) { return a > 0.0f ? a : (a != a ? a : 0.0f); }
+// da of one hidden unit from s = dot_c(g, w2); `kept` < 0: no mask
+FRMAP_TRACK_HD inline float frmap_head_fit_da(float s, float h, int kept, float keep_scale, bool counted) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (!counted || !(h > 0.0f) || kept == 0) return 0.0f;
+  return kept < 0 ? s : s * keep_scale;
 }

@@ -5,6 +5,8 @@
 // frmap_head_fit_step_host, tools/head_fit_check.cpp into a stand-alone program.
 // frmap_head_fit_group_step_twin is the grouped step (head_fit_rule.h, GROUPS): this twin on the slices of every head, with the
 // stride, the hyper table and flag 8 of the device's (frmap_head_fit_group_step_host, tools/head_fit_group_check.cpp).
+// frmap_head_fit_hidden_step_twin is the hidden-layer step (head_fit_rule.h, HIDDEN LAYER): layer 1 by frmap_head_fit_dot, all of
+// layer 2 by this twin on (h, lab, keep2) (frmap_head_fit_hidden_step_host, tools/head_fit_hidden_check.cpp).
 #pragma once
 #include "head_fit_rule.h"
 
@@ -173,6 +175,94 @@ inline const char* frmap_head_fit_group_step_twin(const float* x, const int32_t*
                                        w + (size_t)h * cd, b + (size_t)h * (size_t)C, (char*)state + (size_t)h * stride,
                                        (char*)workspace + (size_t)h * work, N, B, D, C, hy, flags, given_g);
     if (why) return why;
+  }
+  return nullptr;
+}
+
+// what a hidden-layer call is refused for, before anything is read or written: NULL, or the text (it names the argument)
+inline const char* frmap_head_fit_hidden_refusal(const void* x, const void* labels, const void* w1, const void* b1, const void* w2, const void* b2,
+                                                 const void* state, const void* workspace, int N, int B, int D, int Hd, int C, int flags) {
+  if (N < 1) return "N is below 1";
+  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
+  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
+  if (Hd < 1 || Hd > FRMAP_HEAD_FIT_MAX_D) return "Hd is outside [1, 65536]";
+  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
+  if (flags & ~7) return "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear)";
+  if (!x || !labels || !w1 || !b1 || !w2 || !b2 || !state || !workspace)
+    return "null pointer (x, labels, w1, b1, w2, b2, state and workspace are required)";
+  return nullptr;
+}
+
+// The hidden-layer step (head_fit_rule.h, HIDDEN LAYER): layer 1 forward by frmap_head_fit_dot, the single twin on (h, lab, keep2)
+// for all of layer 2, then da against the w2 from BEFORE that update and layer 1's update.  `given_g` as in the single twin: z, g
+// and row_loss of the layer-2 workspace are inputs.
+inline const char* frmap_head_fit_hidden_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep1,
+                                                   float keep1_scale, const uint8_t* keep2, float keep2_scale, float* w1, float* b1, float* w2,
+                                                   float* b2, void* state, void* workspace, int N, int B, int D, int Hd, int C,
+                                                   const FrmapHeadFitHyper& h, int flags, int given_g) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const char* why = frmap_head_fit_hidden_refusal(x, labels, w1, b1, w2, b2, state, workspace, N, B, D, Hd, C, flags);
+  if (why) return why;
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
+  void* state2 = (char*)state + frmap_head_fit_state_size(D, Hd, amsgrad);
+  const FrmapHeadFitState st1 = frmap_head_fit_state(state, D, Hd, amsgrad);
+  const FrmapHeadFitState st2 = frmap_head_fit_state(state2, Hd, C, amsgrad);
+  const FrmapHeadFitHiddenWork wk = frmap_head_fit_hidden_work(workspace, B, Hd);
+  const FrmapHeadFitWork wk2 = frmap_head_fit_work(wk.layer2, B, C);
+  auto xp = [&](int i, int k) -> float {                  // x' of batch row i (declined by layer 1: +0)
+    const int32_t r = wk.row_src1[i];
+    if (r < 0) return 0.0f;
+    return frmap_head_fit_xp(x[(size_t)r * (size_t)D + k], keep1 ? (int)keep1[(size_t)i * (size_t)D + k] : -1, keep1_scale);
+  };
+  for (int i = 0; i < B; ++i) {
+    const int32_t r = wk.row_src1[i] = frmap_head_fit_row_src(x, labels, rows, i, N, D, C);
+    wk.lab[i] = r < 0 ? -1 : labels[r];
+    float* hr = wk.h + (size_t)i * (size_t)Hd;
+    for (int j = 0; j < Hd; ++j) {
+      if (r < 0) {
+        hr[j] = 0.0f;
+        continue;
+      }
+      const float* wj = w1 + (size_t)j * (size_t)D;
+      const float s = frmap_head_fit_dot(D, [&](int k) { return xp(i, k); }, [&](int k) { return wj[k]; });
+      hr[j] = frmap_head_fit_relu(s + b1[j]);
+    }
+  }
+  // s needs w2 as it is before layer 2's update
+  const size_t n_w2 = (size_t)C * (size_t)Hd;
+  float* w2_old = new float[n_w2];
+  for (size_t k = 0; k < n_w2; ++k) w2_old[k] = w2[k];
+  why = frmap_head_fit_step_twin(wk.h, wk.lab, nullptr, keep2, keep2_scale, w2, b2, state2, wk.layer2, B, B, Hd, C, h, flags, given_g);
+  if (why) {
+    delete[] w2_old;
+    return why;
+  }
+  for (int i = 0; i < B; ++i) {
+    const bool counted = wk2.row_src[i] >= 0;
+    const float* gr = wk2.g + (size_t)i * (size_t)C;
+    for (int j = 0; j < Hd; ++j) {
+      const size_t at = (size_t)i * (size_t)Hd + j;
+      const float s = frmap_head_fit_dot(C, [&](int c) { return gr[c]; }, [&](int c) { return w2_old[(size_t)c * (size_t)Hd + j]; });
+      wk.da[at] = frmap_head_fit_da(s, wk.h[at], keep2 ? (int)keep2[at] : -1, keep2_scale, counted);
+    }
+  }
+  delete[] w2_old;
+  const uint64_t n = st2.head[FRMAP_HEAD_FIT_N];
+  st1.head[FRMAP_HEAD_FIT_T] = st2.head[FRMAP_HEAD_FIT_T];
+  st1.head[FRMAP_HEAD_FIT_N] = n;
+  if (n == 0) return nullptr;
+  const FrmapHeadFitAdam a = frmap_head_fit_adam_scalars(st1.head[FRMAP_HEAD_FIT_T], h, flags);
+  auto dd = [&](int i, int j) -> float { return wk.row_src1[i] < 0 ? 0.0f : wk.da[(size_t)i * (size_t)Hd + j]; };
+  for (int j = 0; j < Hd; ++j) {
+    for (int d = 0; d < D; ++d) {
+      const float dw = frmap_head_fit_dot(B, [&](int i) { return dd(i, j); }, [&](int i) { return xp(i, d); });
+      const size_t at = (size_t)j * (size_t)D + d;
+      frmap_head_fit_adam(a, dw, w1 + at, st1.m_w + at, st1.v_w + at, amsgrad ? st1.vmax_w + at : nullptr);
+    }
+    const float db = frmap_head_fit_dot(B, [&](int i) { return dd(i, j); }, [](int) { return 1.0f; });
+    frmap_head_fit_adam(a, db, b1 + j, st1.m_b + j, st1.v_b + j, amsgrad ? st1.vmax_b + j : nullptr);
   }
   return nullptr;
 }

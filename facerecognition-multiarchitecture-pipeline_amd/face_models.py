@@ -361,6 +361,25 @@ class BaselineNet(_HipModule):
     def get_embedding(self, x):
         return self._embed(x)[0]
 
+    def pooled_features(self, x):
+        """fp32 ``[B, 128]``: the output of ``adaptive_pool``, the input of ``fc1`` - what `head_fit.cache_features(layer="pooled")`
+        caches so that a `head_fit.HiddenHead` can fit ``fc1`` / ``fc2``.  The per-op route (three conv + pool launches and the
+        global average pool) on a plan of its own; the model handle is not touched."""
+        x = self._check_input(x)
+        sig = self._signature()
+        if getattr(self, "_pooled_plan", None) is None or sig != self._pooled_sig:
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError(f"{type(self).__name__} is on {dev}; move it to the GPU (.to('cuda')) — the HIP path has no CPU fallback")
+            with torch.no_grad():
+                self._pooled_plan = tuple(_PackedConv(c, b, self.compute_dtype) for c, b in
+                                          ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)))
+            self._pooled_sig = self._signature()
+        x = self._as_nhwc4(x)
+        for conv in self._pooled_plan:
+            x = conv.pooled(x)
+        return ops.avgpool_global(x)
+
     def unit_embedding(self, x):
         """``F.normalize(get_embedding(x))`` (what `embed_and_match(normalize=True)` matches on) without a second launch."""
         pre, emb = self._embed(x)

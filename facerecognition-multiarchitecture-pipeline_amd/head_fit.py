@@ -17,7 +17,12 @@ through a convolution exists here, and none is planned.
 * `kfold_rows`, `cross_validate`, `sweep_heads` - the reference's cross-validation (`src/cross_validation.py`) and the frozen-trunk
   part of its parameter search (`src/hyperparameter_tuning.py`) on one cache, every fold / trial a head of one group.
 
-Out of scope: gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
+* `hidden_step_rule` / `hidden_step_host` / `hidden_step`, `HiddenHead` - one step of ``Linear(D, Hd) -> ReLU -> dropout ->
+  Linear(Hd, C)`` (`frmap_head_fit_hidden_step`): layer 2 is `step` on the hidden activations, layer 1 plain backpropagation through
+  the ReLU, one Adam over the four tensors.  `HiddenHead.embed` is a new embedding layer on a frozen trunk; for ``BaselineNet`` it
+  is the model's own ``fc1`` (`cache_features(layer="pooled")`, `fit_head(hidden=512)`, `HiddenHead.load_into`).
+
+Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
 ``ArcMarginProduct``, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
 from __future__ import annotations
@@ -489,18 +494,25 @@ def _batches(data, batch_size, device):
     return iter(data)
 
 
-def cache_features(model, model_type: str, data, batch_size: int = 256, device="cuda"):
+def cache_features(model, model_type: str, data, batch_size: int = 256, device="cuda", layer: str = "embedding"):
     """Embed a training set once: ``[N, D]`` float32 features and ``[N]`` int32 labels on the device, through the model's EVAL-mode
     ``get_embedding`` (the deployed trunk; the reference's frozen phase still runs BatchNorm in training mode - DESIGN.md §4).
-    ``data``: an image folder (one sub-directory per class) or an iterable of ``(images, labels)`` batches."""
+    ``data``: an image folder (one sub-directory per class) or an iterable of ``(images, labels)`` batches.
+    ``layer="pooled"`` (``BaselineNet`` only): cache the ``[N, 128]`` input of ``fc1`` (`BaselineNet.pooled_features`) instead, for a
+    `HiddenHead` that fits ``fc1`` and ``fc2``."""
     if model_type == 'siamese':
         raise ValueError("head_fit: a siamese model has no classifier head to fit (pairs are verification_metrics' business)")
+    if layer not in ("embedding", "pooled"):
+        raise ValueError(f"head_fit.cache_features: layer must be 'embedding' or 'pooled', got {layer!r}")
+    if layer == "pooled" and type(model).__name__ != "BaselineNet":
+        raise ValueError(f"head_fit.cache_features: layer='pooled' is BaselineNet's (the input of its fc1), got {type(model).__name__}")
+    embed = model.pooled_features if layer == "pooled" else model.get_embedding
     if model.training:
         model.eval()
     feats, labs = [], []
     with torch.no_grad():
         for images, labels in _batches(data, batch_size, device):
-            emb = model.get_embedding(images.to(device))
+            emb = embed(images.to(device))
             feats.append(emb.float().reshape(images.shape[0], -1).clone())
             labs.append(torch.as_tensor(labels).to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).to(device, non_blocking=True))
     if not feats:
@@ -510,17 +522,26 @@ def cache_features(model, model_type: str, data, batch_size: int = 256, device="
 
 def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3,
              weight_decay: float = 1e-4, dropout: float = 0.1, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
-             generator: Optional[torch.Generator] = None, num_classes: Optional[int] = None, device="cuda"):
+             generator: Optional[torch.Generator] = None, num_classes: Optional[int] = None, device="cuda", hidden: Optional[int] = None,
+             hidden_dropout: float = 0.5):
     """Fit a `LinearHead` on the frozen model's features.  The training set is embedded once (`cache_features`); every epoch then
     draws a fresh device permutation as ``rows`` and fresh dropout masks from ``generator`` (a generator on ``device``; ``None``:
     the device's default) and steps through it ``batch_size`` rows at a time with no host copy inside the epoch; the epoch's figures
     are one 64-byte copy at its end.  With ``val_data`` every epoch's validation logits go through `evaluate.ClassificationTally`.
     The defaults are the reference's for ``cnn`` (`src/training.py:184, 352`: Adam, lr 1e-3, weight decay 1e-4, Dropout(0.1));
     ``decoupled=True, amsgrad=True, label_smoothing=0.05`` are its ArcFace settings (`:341-348`).  Returns ``(head, history)`` with
-    ``history = {"train_loss": [...], "train_acc": [...], "val": [metrics dict per epoch]}``."""
+    ``history = {"train_loss": [...], "train_acc": [...], "val": [metrics dict per epoch]}``.
+
+    ``hidden=Hd``: fit a `HiddenHead` ``Linear(D, Hd) -> ReLU -> Dropout(hidden_dropout) -> Linear(Hd, C)`` instead, with ``dropout`` on
+    its input and a second mask draw per step for the hidden layer.  For a ``BaselineNet`` the cache is then its pooled ``[N, 128]``
+    features (`cache_features(layer="pooled")`), so that ``hidden=512`` fits its own ``fc1`` / ``fc2`` (`HiddenHead.load_into`); for
+    every other model it is the embedding, and ``w1`` a learned projection of it."""
     from . import evaluate
     if model_type == 'siamese':
         raise ValueError("head_fit: a siamese model has no classifier head to fit (pairs are verification_metrics' business)")
+    if hidden is not None:
+        return _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size, lr, weight_decay, dropout, label_smoothing,
+                                decoupled, amsgrad, generator, num_classes, device, int(hidden), float(hidden_dropout))
     feats, labels = cache_features(model, model_type, train_data, device=device)
     N, D = int(feats.shape[0]), int(feats.shape[1])
     C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
@@ -546,6 +567,46 @@ def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10
                 keep = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8)
             head.step(feats, labels, rows, keep, lr=lr, dropout=dropout, weight_decay=weight_decay, label_smoothing=label_smoothing,
                       decoupled=decoupled)
+        fig = head.epoch_figures()
+        history["train_loss"].append(fig["loss"])
+        history["train_acc"].append(fig["accuracy"])
+        if val is not None:
+            tally = evaluate.ClassificationTally(C, device=feats.device)
+            tally.update(head.logits(val[0]), val[1])
+            history["val"].append(tally.metrics())
+    return head, history
+
+
+def _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size, lr, weight_decay, dropout, label_smoothing, decoupled,
+                     amsgrad, generator, num_classes, device, hidden, hidden_dropout):
+    """`fit_head(hidden=...)`: `fit_head`'s loop on a `HiddenHead`, with a second mask draw."""
+    from . import evaluate
+    layer = "pooled" if type(model).__name__ == "BaselineNet" else "embedding"
+    feats, labels = cache_features(model, model_type, train_data, device=device, layer=layer)
+    N, D = int(feats.shape[0]), int(feats.shape[1])
+    C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
+    head_gen = generator if generator is not None and generator.device.type == "cpu" else None
+    head = HiddenHead(D, hidden, C, feats.device, amsgrad=amsgrad, generator=head_gen)
+    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
+    if generator is not None and dev_gen is None:
+        dev_gen = torch.Generator(device=feats.device)
+        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
+    val = None
+    if val_data is not None:
+        val = cache_features(model, model_type, val_data, device=device, layer=layer)
+    history = {"train_loss": [], "train_acc": [], "val": []}
+    for _ in range(int(epochs)):
+        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, int(batch_size)):
+            rows = perm[lo: lo + int(batch_size)]
+            keep1 = keep2 = None
+            if dropout > 0:
+                keep1 = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8)
+            if hidden_dropout > 0:
+                keep2 = (torch.rand((rows.shape[0], hidden), device=feats.device, generator=dev_gen) >= hidden_dropout).to(torch.uint8)
+            head.step(feats, labels, rows, keep1, keep2, lr=lr, dropout1=dropout, dropout2=hidden_dropout, weight_decay=weight_decay,
+                      label_smoothing=label_smoothing, decoupled=decoupled)
         fig = head.epoch_figures()
         history["train_loss"].append(fig["loss"])
         history["train_acc"].append(fig["accuracy"])
@@ -992,3 +1053,365 @@ def sweep_heads(feats: torch.Tensor, labels: torch.Tensor, val_feats: torch.Tens
         t["best_validation_accuracy"] = max(t["val_acc"]) if t["val_acc"] else float("nan")
     best = max(range(H), key=lambda h: (out[h]["best_validation_accuracy"], -out[h]["val_loss"][-1] if out[h]["val_loss"] else 0.0, -h))
     return {"trials": out, "best_trial": best, "best_params": out[best]["params"], "group": group}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# a head with one hidden layer: Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def hidden_state_bytes(D: int, Hd: int, C: int, amsgrad: bool = False) -> int:
+    """Bytes of the state of a hidden-layer head (`frmap_head_fit_hidden_state_bytes`): `state_bytes` of (D, Hd), then of (Hd, C)."""
+    n = int(_lib.load().frmap_head_fit_hidden_state_bytes(int(D), int(Hd), int(C), int(bool(amsgrad))))
+    if n == 0:
+        raise ValueError(f"head_fit: unsupported D = {D}, Hd = {Hd}, C = {C} (each in 1 ... {MAX_D})")
+    return n
+
+
+def hidden_workspace_bytes(B: int, D: int, Hd: int, C: int) -> int:
+    """Bytes of the workspace of a hidden-layer step of ``B`` rows (`frmap_head_fit_hidden_workspace_bytes`)."""
+    n = int(_lib.load().frmap_head_fit_hidden_workspace_bytes(int(B), int(D), int(Hd), int(C)))
+    if n == 0:
+        raise ValueError(f"head_fit: unsupported B = {B}, D = {D}, Hd = {Hd}, C = {C} (B in 1 ... {MAX_B}, D, Hd, C in 1 ... {MAX_D})")
+    return n
+
+
+def hidden_state_views(state: np.ndarray, D: int, Hd: int, C: int, amsgrad: bool = False) -> dict:
+    """``{"layer1": state_views of (D, Hd), "layer2": state_views of (Hd, C)}`` into a host copy of a hidden state."""
+    raw = np.ascontiguousarray(state).view(np.uint8).reshape(-1)
+    n1 = state_bytes(D, Hd, amsgrad)
+    return {"layer1": state_views(raw[:n1], D, Hd, amsgrad), "layer2": state_views(raw[n1: n1 + state_bytes(Hd, C, amsgrad)], Hd, C, amsgrad)}
+
+
+def hidden_workspace_views(workspace: np.ndarray, B: int, Hd: int, C: int) -> dict:
+    """h, da [B, Hd] (float32), lab, row_src1 [B] (int32) and z, g, row_loss, row_src (layer 2's `workspace_views`) of a host copy."""
+    raw = np.ascontiguousarray(workspace).view(np.uint8).reshape(-1)
+    at = 8 * B * Hd
+    out = {"h": raw[: 4 * B * Hd].view(np.float32).reshape(B, Hd), "da": raw[4 * B * Hd: at].view(np.float32).reshape(B, Hd),
+           "lab": raw[at: at + 4 * B].view(np.int32), "row_src1": raw[at + 4 * B: at + 8 * B].view(np.int32)}
+    out.update(workspace_views(raw[at + 8 * B:], B, C))
+    return out
+
+
+def _adam_rule(p, grad, st: dict, km: str, kv: str, kx: str, t: int, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, f32):
+    """The update of `step_rule` on one tensor; returns the new parameter, ``st`` is updated in place."""
+    if f32:
+        a = adam_scalars32(t, lr, beta1, beta2, eps, weight_decay)
+        p, st[km], st[kv], vm = adam32(a, grad, p, st[km], st[kv], st.get(kx), decoupled, amsgrad)
+        if amsgrad:
+            st[kx] = vm
+        return p
+    p = np.array(p, np.float64)
+    if decoupled:
+        p *= 1.0 - lr * weight_decay
+    elif weight_decay != 0:
+        grad = grad + weight_decay * p
+    st[km] = st[km] + (1.0 - beta1) * (grad - st[km])
+    st[kv] = st[kv] * beta2 + (1.0 - beta2) * grad * grad
+    vhat = st[kv]
+    if amsgrad:
+        st[kx] = np.maximum(st[kx], st[kv])
+        vhat = st[kx]
+    denom = np.sqrt(vhat) / math.sqrt(1.0 - beta2 ** t) + eps
+    p += -(lr / (1.0 - beta1 ** t)) * (st[km] / denom)
+    return p
+
+
+def hidden_step_rule(x, labels, w1, b1, w2, b2, state: Optional[dict] = None, rows=None, keep1=None, keep1_scale: float = 1.0, keep2=None,
+                     keep2_scale: float = 1.0, *, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                     weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+                     clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
+    """One training step of Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C), the specification (csrc/head_fit_rule.h, HIDDEN LAYER).
+
+    Layer 1's forward and its declined rows are computed here; all of layer 2 is `step_rule` on ``(h, lab, keep2)``; ``da`` is formed
+    against the ``w2`` from BEFORE that update, and layer 1's update uses layer 2's ``t`` and ``n``.  ``dtype`` and ``given`` as in
+    `step_rule` (``given`` holds layer 2's ``z``, ``g`` and ``row_loss``).  ``state``: ``{"layer1": ..., "layer2": ...}`` of
+    `fresh_state` dicts for (D, Hd) and (Hd, C), or ``None``.
+
+    Nothing is modified: returns ``{"w1", "b1", "w2", "b2", "state", "h", "lab", "row_src1", "da", "z", "g", "row_loss", "row_src",
+    "dw1", "db1", "dw2", "db2", "n", "loss"}`` with new arrays."""
+    f32 = np.dtype(dtype) == np.dtype(np.float32)
+    x = np.asarray(x, F32 if f32 else np.float64)
+    w1, b1 = np.array(w1, dtype), np.array(b1, dtype)
+    w2_old = np.array(w2, dtype)
+    labels = np.asarray(labels).astype(np.int64)
+    N, D = x.shape
+    Hd, C = w1.shape[0], w2_old.shape[0]
+    if rows is None:
+        rows = np.arange(len(keep1) if keep1 is not None else (len(keep2) if keep2 is not None else (N if batch is None else int(batch))),
+                         dtype=np.int64)
+    else:
+        rows = np.asarray(rows).astype(np.int64)
+    B = len(rows)
+    state = state or {"layer1": fresh_state(D, Hd, amsgrad, dtype), "layer2": fresh_state(Hd, C, amsgrad, dtype)}
+    st1 = {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in state["layer1"].items()}
+    row_src1 = np.full((B,), -1, np.int32)
+    for i, r in enumerate(rows):
+        if 0 <= r < N and 0 <= labels[r] < C and np.isfinite(x[r]).all():
+            row_src1[i] = r
+    ok1 = row_src1 >= 0
+    lab = np.where(ok1, labels[np.clip(row_src1, 0, N - 1)], -1).astype(np.int32)
+    xp = np.zeros((B, D), x.dtype)
+    xp[ok1] = x[row_src1[ok1]]
+    if keep1 is not None:
+        kept = np.asarray(keep1).astype(bool)
+        scaled = (xp * F32(keep1_scale)).astype(F32) if f32 else xp * float(keep1_scale)
+        xp = np.where(kept, scaled, 0).astype(x.dtype)
+        xp[~ok1] = 0
+    with np.errstate(all="ignore"):
+        a = (dot32(xp[:, None, :], w1[None, :, :]) + b1[None, :]).astype(F32) if f32 else xp @ w1.T + b1[None, :]
+        h = np.where(a > 0, a, np.where(np.isnan(a), a, 0)).astype(dtype)
+    h[~ok1] = 0
+    r2 = step_rule(h, lab, w2_old, b2, state["layer2"], None, keep2, keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                   weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled, amsgrad=amsgrad, clear=clear,
+                   dtype=dtype, given=given, batch=B)
+    ok2 = r2["row_src"] >= 0
+    g = np.where(ok2[:, None], r2["g"], 0).astype(dtype)
+    with np.errstate(all="ignore"):
+        s = dot32(g[:, None, :], w2_old.T[None, :, :]) if f32 else g @ w2_old
+        live = ok2[:, None] & (h > 0)
+        if keep2 is not None:
+            live = live & np.asarray(keep2).astype(bool)
+            s = (s * F32(keep2_scale)).astype(F32) if f32 else s * float(keep2_scale)
+        da = np.where(live, s, 0).astype(dtype)
+        dz = np.where(ok1[:, None], da, 0).astype(dtype)
+        if f32:
+            dw1 = dot32(dz.T[:, None, :], xp.T[None, :, :])
+            db1 = dot32(dz.T, np.ones((1, B), F32))
+        else:
+            dw1, db1 = dz.T @ xp, dz.sum(axis=0)
+    n = r2["n"]
+    st1["t"], st1["n"] = r2["state"]["t"], n
+    if n:
+        kw = dict(t=st1["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
+                  f32=f32)
+        w1 = _adam_rule(w1, dw1, st1, "m_w", "v_w", "vmax_w", **kw)
+        b1 = _adam_rule(b1, db1, st1, "m_b", "v_b", "vmax_b", **kw)
+    out = {"w1": w1, "b1": b1, "w2": r2["w"], "b2": r2["b"], "state": {"layer1": st1, "layer2": r2["state"]}, "h": h, "lab": lab,
+           "row_src1": row_src1, "da": da, "dw1": dw1, "db1": db1, "dw2": r2["dw"], "db2": r2["db"]}
+    for k in ("z", "g", "row_loss", "row_src", "n", "loss"):
+        out[k] = r2[k]
+    return out
+
+
+def _host_array(op, name, t, dt):
+    if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
+        raise ValueError(f"{op}: {name} must be a writable contiguous {np.dtype(dt).name} array")
+
+
+def hidden_step_host(x, labels, w1, b1, w2, b2, state: np.ndarray, workspace: Optional[np.ndarray] = None, rows=None, keep1=None,
+                     keep1_scale: float = 1.0, keep2=None, keep2_scale: float = 1.0, *, lr: float = 1e-3, beta1: float = 0.9,
+                     beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0,
+                     decoupled: bool = False, amsgrad: bool = False, clear: bool = False, given_g: bool = False,
+                     batch: Optional[int] = None):
+    """The hidden-layer step on the CPU over numpy arrays (`frmap_head_fit_hidden_step_host`; no GPU).  ``w1`` [Hd, D], ``b1`` [Hd],
+    ``w2`` [C, Hd], ``b2`` [C] (float32) and ``state`` (uint8, `hidden_state_bytes` bytes, 8-byte aligned) are updated IN PLACE;
+    ``workspace`` (uint8, exactly `hidden_workspace_bytes` bytes, or ``None`` for a fresh one) receives h, da, lab, row_src1 and
+    layer 2's z, g, row_loss and row_src - with ``given_g`` the z, g and row_loss in it are inputs.  Returns the workspace."""
+    op = "head_fit.hidden_step_host"
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if x.ndim != 2 or labels.shape != (x.shape[0],):
+        raise ValueError(f"{op}: x [N, D] and labels [N] expected")
+    N, D = x.shape
+    for name, t, dt in (("w1", w1, np.float32), ("b1", b1, np.float32), ("w2", w2, np.float32), ("b2", b2, np.float32),
+                        ("state", state, np.uint8)):
+        _host_array(op, name, t, dt)
+    if w1.ndim != 2 or w1.shape[1] != D or b1.shape != (w1.shape[0],):
+        raise ValueError(f"{op}: w1 [Hd, {D}] and b1 [Hd] expected, got {w1.shape} and {b1.shape}")
+    Hd = w1.shape[0]
+    if w2.ndim != 2 or w2.shape[1] != Hd or b2.shape != (w2.shape[0],):
+        raise ValueError(f"{op}: w2 [C, {Hd}] and b2 [C] expected, got {w2.shape} and {b2.shape}")
+    C = w2.shape[0]
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.ndim != 1:
+            raise ValueError(f"{op}: rows [B] expected")
+    B = len(rows) if rows is not None else (len(keep1) if keep1 is not None else (len(keep2) if keep2 is not None else (
+        N if batch is None else int(batch))))
+    if keep1 is not None:
+        keep1 = np.ascontiguousarray(keep1, dtype=np.uint8)
+        if keep1.shape != (B, D):
+            raise ValueError(f"{op}: keep1 must be [{B}, {D}], got {keep1.shape}")
+    if keep2 is not None:
+        keep2 = np.ascontiguousarray(keep2, dtype=np.uint8)
+        if keep2.shape != (B, Hd):
+            raise ValueError(f"{op}: keep2 must be [{B}, {Hd}], got {keep2.shape}")
+    if rows is None and B > N:
+        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    nstate = hidden_state_bytes(D, Hd, C, amsgrad)
+    if state.shape != (nstate,) or state.ctypes.data % 8:
+        raise ValueError(f"{op}: state must be {nstate} bytes, 8-byte aligned")
+    nbytes = hidden_workspace_bytes(B, D, Hd, C)
+    if workspace is None:
+        if given_g:
+            raise ValueError(f"{op}: given_g needs the workspace that holds z, g and row_loss")
+        workspace = np.zeros((nbytes,), np.uint8)
+    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
+            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
+        raise ValueError(f"{op}: workspace must be a writable uint8 array of exactly {nbytes} bytes")
+    _lib.check(_lib.load().frmap_head_fit_hidden_step_host(
+        x.ctypes.data, labels.ctypes.data, rows.ctypes.data if rows is not None else 0, keep1.ctypes.data if keep1 is not None else 0,
+        float(keep1_scale), keep2.ctypes.data if keep2 is not None else 0, float(keep2_scale), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
+        b2.ctypes.data, state.ctypes.data, workspace.ctypes.data, N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps),
+        float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
+    return workspace
+
+
+@ops._on_operand_device
+def hidden_step(x: torch.Tensor, labels: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                state: torch.Tensor, workspace: torch.Tensor, rows: Optional[torch.Tensor] = None, keep1: Optional[torch.Tensor] = None,
+                keep1_scale: float = 1.0, keep2: Optional[torch.Tensor] = None, keep2_scale: float = 1.0, *, lr: float = 1e-3,
+                beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0,
+                decoupled: bool = False, amsgrad: bool = False, clear: bool = False, batch: Optional[int] = None) -> None:
+    """One hidden-layer training step on the current stream (`frmap_head_fit_hidden_step`; nothing is copied or synchronised).
+    ``x`` float32 ``[N, D]``, ``labels`` int32 ``[N]``, ``w1`` ``[Hd, D]``, ``b1`` ``[Hd]``, ``w2`` ``[C, Hd]``, ``b2`` ``[C]`` float32
+    (updated in place), ``state`` uint8 of `hidden_state_bytes` bytes (zeros = fresh), ``workspace`` uint8 of exactly
+    `hidden_workspace_bytes` bytes, ``rows`` int32 ``[B]`` or ``None`` (rows ``0 .. B-1``; ``B`` is then a mask's row count, else
+    ``batch``, else ``N``), ``keep1`` uint8 ``[B, D]`` and ``keep2`` uint8 ``[B, Hd]`` or ``None``.  Every extent that depends on another
+    operand is checked here, before the library sees a pointer."""
+    op, entry = "head_fit.hidden_step", "frmap_head_fit_hidden_step"
+    x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
+    N, D = int(x.shape[0]), int(x.shape[1])
+    _sized(labels, op, "labels", (N,), torch.int32)
+    _sized(w1, op, "w1", (w1.shape[0] if isinstance(w1, torch.Tensor) and w1.dim() == 2 else -1, D), torch.float32)
+    Hd = int(w1.shape[0])
+    _sized(b1, op, "b1", (Hd,), torch.float32)
+    _sized(w2, op, "w2", (w2.shape[0] if isinstance(w2, torch.Tensor) and w2.dim() == 2 else -1, Hd), torch.float32)
+    C = int(w2.shape[0])
+    _sized(b2, op, "b2", (C,), torch.float32)
+    if rows is not None:
+        if isinstance(rows, torch.Tensor) and rows.dim() != 1:
+            raise ValueError(f"{op}: rows [B] expected, got {tuple(rows.shape)}")
+        rows = _dev(rows, f"{op}.rows", torch.int32, (entry, "rows"))
+        B = int(rows.shape[0])
+    elif isinstance(keep1, torch.Tensor) and keep1.dim() == 2:
+        B = int(keep1.shape[0])
+    elif isinstance(keep2, torch.Tensor) and keep2.dim() == 2:
+        B = int(keep2.shape[0])
+    else:
+        B = N if batch is None else int(batch)
+    if rows is None and B > N:
+        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    if keep1 is not None:
+        _sized(keep1, op, "keep1", (B, D), torch.uint8)
+    if keep2 is not None:
+        _sized(keep2, op, "keep2", (B, Hd), torch.uint8)
+    _sized(state, op, "state", (hidden_state_bytes(D, Hd, C, amsgrad),), torch.uint8)
+    _sized(workspace, op, "workspace", (hidden_workspace_bytes(B, D, Hd, C),), torch.uint8)
+    held = []                                                   # copies `_dev` made live until the launch is enqueued
+    labels = _dev(labels, f"{op}.labels", torch.int32, (entry, "labels"))
+    keep1 = None if keep1 is None else _dev(keep1, f"{op}.keep1", torch.uint8, (entry, "keep1"))
+    keep2 = None if keep2 is None else _dev(keep2, f"{op}.keep2", torch.uint8, (entry, "keep2"))
+    held += [x, labels, rows, keep1, keep2]
+    w1 = _dev(w1, f"{op}.w1", torch.float32, (entry, "w1"), owned=True)
+    b1 = _dev(b1, f"{op}.b1", torch.float32, (entry, "b1"), owned=True)
+    w2 = _dev(w2, f"{op}.w2", torch.float32, (entry, "w2"), owned=True)
+    b2 = _dev(b2, f"{op}.b2", torch.float32, (entry, "b2"), owned=True)
+    state = _dev(state, f"{op}.state", torch.uint8, (entry, "state"), owned=True)
+    workspace = _dev(workspace, f"{op}.workspace", torch.uint8, (entry, "workspace"), owned=True)
+    _lib.check(_lib.load().frmap_head_fit_hidden_step(
+        x.data_ptr(), labels.data_ptr(), rows.data_ptr() if rows is not None else 0, keep1.data_ptr() if keep1 is not None else 0,
+        float(keep1_scale), keep2.data_ptr() if keep2 is not None else 0, float(keep2_scale), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+        b2.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps),
+        float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), _stream()), op)
+    del held
+
+
+class HiddenHead:
+    """``Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C)`` on the device with its Adam state and a workspace: the ``fc1`` / ``fc2`` of
+    the reference's ``BaselineNet`` over its pooled features, or a learned ``D -> Hd`` projection of any cached feature.  Both layers
+    are initialised as consecutive ``nn.Linear(D, Hd)`` and ``nn.Linear(Hd, C)`` would be from ``generator`` (a CPU
+    ``torch.Generator``; ``None``: torch's default).  `embed` is the new embedding layer: it feeds `matching.Gallery`,
+    `evaluate.verification_metrics` and `frames.identify_streams` like any other embedding."""
+
+    def __init__(self, D: int, Hd: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
+        self.D, self.Hd, self.C, self.amsgrad = int(D), int(Hd), int(C), bool(amsgrad)
+        nbytes = hidden_state_bytes(self.D, self.Hd, self.C, self.amsgrad)          # (refuses a bad shape)
+        self.device = torch.device(device)
+        params = []
+        for fan_out, fan_in in ((self.Hd, self.D), (self.C, self.Hd)):
+            bound = 1.0 / math.sqrt(fan_in)
+            params.append(((torch.rand((fan_out, fan_in), generator=generator, dtype=torch.float32) * 2 - 1) * bound).to(self.device))
+            params.append(((torch.rand((fan_out,), generator=generator, dtype=torch.float32) * 2 - 1) * bound).to(self.device))
+        self.w1, self.b1, self.w2, self.b2 = params
+        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
+        self._state2_at = state_bytes(self.D, self.Hd, self.amsgrad)
+        self._workspaces = {}
+        self._clear = True
+
+    def _workspace(self, B: int) -> torch.Tensor:
+        ws = self._workspaces.get(B)
+        if ws is None:
+            ws = self._workspaces[B] = torch.empty((hidden_workspace_bytes(B, self.D, self.Hd, self.C),), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def new_epoch(self) -> "HiddenHead":
+        """The next `step` clears the epoch figures first."""
+        self._clear = True
+        return self
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor, rows: Optional[torch.Tensor] = None, keep1: Optional[torch.Tensor] = None,
+             keep2: Optional[torch.Tensor] = None, *, lr: float, dropout1: float = 0.0, dropout2: float = 0.0,
+             keep1_scale: Optional[float] = None, keep2_scale: Optional[float] = None, beta1: float = 0.9, beta2: float = 0.999,
+             eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False) -> "HiddenHead":
+        """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`hidden_step`).  ``keep1`` / ``keep2``: uint8 ``[B, D]`` /
+        ``[B, Hd]`` dropout masks on the input / the hidden layer, scaled by ``1 / (1 - dropout1)`` / ``1 / (1 - dropout2)`` unless a
+        scale is given.  No synchronisation."""
+        if keep1_scale is None:
+            keep1_scale = 1.0 / (1.0 - float(dropout1)) if keep1 is not None else 1.0
+        if keep2_scale is None:
+            keep2_scale = 1.0 / (1.0 - float(dropout2)) if keep2 is not None else 1.0
+        B = int(x.shape[0])
+        for t, dim in ((rows, 1), (keep1, 2), (keep2, 2)):
+            if isinstance(t, torch.Tensor) and t.dim() == dim:
+                B = int(t.shape[0])
+                break
+        hidden_step(x, labels, self.w1, self.b1, self.w2, self.b2, self.state, self._workspace(B), rows, keep1, keep1_scale, keep2,
+                    keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing,
+                    decoupled=decoupled, amsgrad=self.amsgrad, clear=self._clear)
+        self._clear = False
+        return self
+
+    def epoch_figures(self) -> dict:
+        """The one host copy (layer 2's header): rows, correct, accuracy and mean loss since the last `new_epoch`, and ``t``."""
+        words = self.state[self._state2_at: self._state2_at + 64].cpu().numpy().view(np.uint64)
+        out = figures_of({name: words[k] for k, name in enumerate(HEADER)})
+        out["t"] = int(words[0])
+        return out
+
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """``relu(x w1^T + b1)``: the embedding the fitted first layer produces from cached-feature rows ``x`` ``[B, D]``."""
+        return ops.linear_f32(x, self.w1, None, self.b1, relu=True)
+
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_f32(self.embed(x), self.w2, None, self.b2)
+
+    def state_dict(self) -> dict:
+        return {"fc1.weight": self.w1.detach().clone(), "fc1.bias": self.b1.detach().clone(), "fc2.weight": self.w2.detach().clone(),
+                "fc2.bias": self.b2.detach().clone()}
+
+    def classifier(self) -> LinearHead:
+        """Layer 2 as a `LinearHead` whose ``weight``, ``bias`` and ``state`` are VIEWS of this head's memory (the second part of the
+        state is a valid single-step state): its `logits` and `as_classifier` take `embed` outputs."""
+        one = LinearHead.__new__(LinearHead)
+        one.D, one.C, one.amsgrad, one.device = self.Hd, self.C, self.amsgrad, self.device
+        one.weight, one.bias = self.w2, self.b2
+        one.state = self.state[self._state2_at: self._state2_at + state_bytes(self.Hd, self.C, self.amsgrad)]
+        one._workspaces, one._clear = {}, False
+        return one
+
+    def load_into(self, model) -> None:
+        """Copy both layers into ``fc1`` / ``fc2`` of a ``BaselineNet`` of matching shapes, in place (the model's plan watches the
+        parameters' versions: the next forward rebuilds)."""
+        fc1, fc2 = getattr(model, "fc1", None), getattr(model, "fc2", None)
+        if type(model).__name__ != "BaselineNet" or not isinstance(fc1, torch.nn.Linear) or not isinstance(fc2, torch.nn.Linear):
+            raise ValueError(f"HiddenHead.load_into: a BaselineNet expected, got {type(model).__name__}")
+        for name, layer, shape in (("fc1", fc1, (self.Hd, self.D)), ("fc2", fc2, (self.C, self.Hd))):
+            if tuple(layer.weight.shape) != shape:
+                raise ValueError(f"HiddenHead.load_into: {name} is {list(layer.weight.shape)}, the head's layer is {list(shape)}")
+        with torch.no_grad():
+            fc1.weight.copy_(self.w1)
+            fc1.bias.copy_(self.b1)
+            fc2.weight.copy_(self.w2)
+            fc2.bias.copy_(self.b2)

@@ -711,6 +711,57 @@ int frmap_head_fit_group_step_host(const float* x_host, const int32_t* labels_ho
                                    const float* hyper_host, float* w_host, float* b_host, void* state_host, void* workspace_host,
                                    int N, int H, int B, int D, int C, int flags, int given_g);
 
+/* Head fitting with one hidden layer: one training step of Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C) (the fc1 / fc2 of the
+ * reference's BaselineNet, src/face_models.py:16-60; a learned projection on any other cached feature) over CACHED trunk features:
+ * plain backpropagation through one ReLU with one Adam / AdamW optimiser over the four tensors.  One small memset and six launches
+ * on the caller's stream, nothing copied to the host, nothing allocated, no floating-point atomic.
+ *
+ * Operands: x, labels and rows as in frmap_head_fit_step; keep1 [B][D] uint8 or NULL with keep1_scale masks the input, keep2
+ * [B][Hd] uint8 or NULL with keep2_scale the hidden layer; w1 [Hd][D], b1 [Hd], w2 [C][Hd], b2 [C] fp32, updated in place.
+ * flags: 1 | 2 | 4 as in the single step.
+ * The rule (every dot product is the single step's: fmaf chains from +0 cut at the multiples of 128, the chains added ascending):
+ *   x'       = keep1 ? (keep1[i][k] ? x * keep1_scale : 0) : x, one rounding
+ *   a[i][j]  = dot_k(x'[i][k], w1[j][k]) + b1[j]                     (chain order over D, the bias last)
+ *   h[i][j]  = a > 0 ? a : (a != a ? a : +0)                         (a NaN stays one; -0 and negatives give +0)
+ *   lab[i]   = labels[rows[i]], or -1 where layer 1 declines row i (row index outside [0, N), label outside [0, C), a non-finite
+ *              feature); the h row of such a row is +0
+ *   layer 2  = the forward half of frmap_head_fit_step on (x := h [B][Hd], labels := lab [B], rows := NULL, keep := keep2, w2, b2):
+ *              z, the float64 softmax, the row loss, g = (p - y) / n and the figures.  It declines a row whose lab is -1 or whose
+ *              h holds a non-finite value; n is ITS count, the one n of the step.
+ *   s[i][j]  = dot_c(g[i][c], w2[c][j])                              (chain order over C, w2 BEFORE its update)
+ *   da[i][j] = (row i counted by layer 2) && h[i][j] > 0 && keep2[i][j] ? s * keep2_scale : +0, one rounding (no mask: s itself)
+ *   dw2, db2 = the single step's on (g, h');  dw1[j][d] = dot_i(da[i][j], x'[i][d]), db1[j] = dot_i(da[i][j], 1)
+ *   update   = Adam / AdamW on all four tensors with the same hyper-parameters and the same t.  n == 0 changes nothing but the
+ *              workspace.
+ * Launches: the memset of layer 2's n (with 4: its figures); layer 1 forward (the logits tile walk with the ReLU epilogue: h, lab,
+ * row_src1); the single step's logits and softmax kernels on (h, lab); back (da, a workgroup per 32 x 32 tile over all C, on the
+ * matrix cores where the tile is full; one thread copies t and n into layer 1's state); the single step's update kernel on layer 2,
+ * then on layer 1 with g := da.  w2 is not updated before da is written: the stream order gives that.
+ * state : frmap_head_fit_hidden_state_bytes bytes, zeroed by the caller before the first step: the single step's layout for
+ *         (D, Hd), then the single step's layout for (Hd, C); both are multiples of 8.  The second part is a valid state of
+ *         frmap_head_fit_step on (h, lab): its header carries t, n and the epoch figures.  The first part's t and n are copies
+ *         written by the step; its figure words stay 0.
+ * workspace : exactly frmap_head_fit_hidden_workspace_bytes bytes: fp32 h [B][Hd], da [B][Hd], int32 lab [B], row_src1 [B], then
+ *         the single step's workspace for (B, Hd -> C).
+ * The size queries take no stream and return 0 for arguments the launcher would refuse.
+ * Refused (-1, the text names the argument): N < 1; B < 1 or above 2^20; D, Hd or C < 1 or above 65536; flag bits above 7; a
+ * required pointer that is NULL.  All address arithmetic is size_t.
+ * Every pointer is walked element by element: x, labels, rows, w1, b1, w2, b2 and workspace need their element size (4), keep1
+ * and keep2 1, state the size of a uint64 counter (8).
+ * The host form is the same step compiled for the CPU (host pointers, no stream); given_g != 0 takes z, g and row_loss of the
+ * layer-2 workspace as INPUTS, as in frmap_head_fit_step_host. */
+size_t frmap_head_fit_hidden_state_bytes(int D, int Hd, int C, int amsgrad);
+size_t frmap_head_fit_hidden_workspace_bytes(int B, int D, int Hd, int C);
+int frmap_head_fit_hidden_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep1, float keep1_scale,
+                               const uint8_t* keep2, float keep2_scale, float* w1, float* b1, float* w2, float* b2, void* state,
+                               void* workspace, int N, int B, int D, int Hd, int C, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, float label_smoothing, int flags, void* stream);
+int frmap_head_fit_hidden_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep1_host,
+                                    float keep1_scale, const uint8_t* keep2_host, float keep2_scale, float* w1_host, float* b1_host,
+                                    float* w2_host, float* b2_host, void* state_host, void* workspace_host, int N, int B, int D, int Hd,
+                                    int C, float lr, float beta1, float beta2, float eps, float weight_decay, float label_smoothing,
+                                    int flags, int given_g);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
