@@ -19,6 +19,7 @@
 // and its interface to the split-fp16 match GEMM of conv_pp.hip are in match_device.h; the workspace of every match operation is
 // laid out by one function here (top1_ws, topk_ws, verify_ws, radius_ws), which its *_workspace_bytes and its entry points share.
 #include "match_device.h"
+#include "match_scale_rule.h"
 #include <type_traits>
 
 enum { MODE_LINEAR = 0, MODE_COS = 1, MODE_ARC = 2, MODE_DIST = 3 };
@@ -205,6 +206,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float* __restric
           const float d2 = match_expanded_d2(sa2, ep.stat_a[2 * b + 1], wn2, wsum, dot, keps);
           const float dl = match_kappa(K) * (match_band(sa2, kf) + wband + keps);
           L = d2 - dl; U = d2 + dl;
+          match_unbounded(L, U);   // no finite bound (a squared norm past fp32, NaN): in band, the exact re-score decides
         }
         int fl;
         const float l1 = half_wave_best<false>(L, lk, fl);
@@ -348,40 +350,31 @@ __global__ void match_finalize_rec_kernel(const float* __restrict__ emb, const f
     match_write_top1(b, besti, besti >= 0 ? (float)sqrt(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
 }
 
-// Small galleries (the demo's handful of enrolled faces, the 36-ID benchmark gallery): one wave per
-// probe walks the gallery directly with the exact F.pairwise_distance arithmetic — no GEMM
-// expansion, no atomics, one launch.  lane owns dims lane, lane+64, ...
+// Small galleries (the demo's handful of enrolled faces, the 36-ID benchmark gallery): one workgroup per probe walks the gallery
+// directly with the exact distance of every other path (match_exact_d2: fp32 elements, squares summed in float64, so a difference
+// whose fp32 square would overflow - rows around 2^64 and beyond - still has its finite distance) - no GEMM expansion, no atomics,
+// one launch.
 __global__ __launch_bounds__(256) void match_small_kernel(const float* __restrict__ emb, const float* __restrict__ gal,
                                                           int32_t* __restrict__ idx_out, float* __restrict__ dist_out,
                                                           int32_t* __restrict__ id_thr_out, int32_t* __restrict__ packed_out,
                                                           float thresh, int B, int G, int D) {
-  // one workgroup per probe; wave w scores gallery rows 8w..8w+7, 8(w+4).. (8 rows per pass so their
-  // loads are independent); the four waves' (best, index) pairs meet in LDS, lowest index wins ties
-  __shared__ float s_best[4];
+  // wave w scores gallery rows 8w..8w+7, 8(w+4).. (8 rows per pass so their loads are independent); the four waves'
+  // (best, index) pairs meet in LDS, lowest index wins ties
+  __shared__ double s_best[4];
   __shared__ int s_idx[4];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float best = INFINITY;
+  double best = INFINITY;
   int besti = 0x7FFFFFFF;
   for (int g0 = wave * 8; g0 < G; g0 += 32) {
-    float s2[8];
+    const float* pa[8];
+    const float* pg[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s2[j] = 0.f;
-    for (int k = lane; k < D; k += 64) {
-      const float e = emb[(size_t)b * D + k];
+    for (int j = 0; j < 8; ++j) { pa[j] = emb + (size_t)b * D; pg[j] = gal + (size_t)min(g0 + j, G - 1) * D; }
+    double d2[8];
+    match_exact_d2_n<8>(pa, pg, D, lane, d2);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int gi = min(g0 + j, G - 1);
-        const float d = (e - gal[(size_t)gi * D + k]) + 1e-6f;
-        s2[j] += d * d;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = s2[j];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      if (g0 + j < G && v < best) { best = v; besti = g0 + j; }  // strict <: first minimum within this wave's rows
-    }
+    for (int j = 0; j < 8; ++j)
+      if (g0 + j < G && d2[j] < best) { best = d2[j]; besti = g0 + j; }  // strict <: first minimum within this wave's rows
   }
   if (lane == 0) { s_best[wave] = best; s_idx[wave] = besti; }
   __syncthreads();
@@ -389,7 +382,7 @@ __global__ __launch_bounds__(256) void match_small_kernel(const float* __restric
     for (int w = 1; w < 4; ++w)
       if (s_best[w] < best || (s_best[w] == best && s_idx[w] < besti)) { best = s_best[w]; besti = s_idx[w]; }
     const bool any = besti != 0x7FFFFFFF;
-    match_write_top1(b, any ? besti : -1, any ? sqrtf(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
+    match_write_top1(b, any ? besti : -1, any ? (float)sqrt(best) : INFINITY, thresh, idx_out, dist_out, id_thr_out, packed_out);
   }
 }
 
@@ -954,15 +947,10 @@ extern "C" int frmap_match_top1(const float* emb, const float* gallery, int32_t*
 // of the fp32 path, so the result has the same contract: first minimum of the expanded distance, exact
 // F.pairwise_distance of the winner.  The gallery is split and laid out in the kernel's weight order ONCE per gallery.
 // ------------------------------------------------------------------------------------------------
-// Each row gets its own power-of-two scale S (largest |x| of the row lands in [2^13, 2^14): nothing overflows fp16, lo stays
-// out of the fp16 subnormals for every element within 2^-11 of the row maximum, and scaling by a power of two is exact);
+// Each row gets its own power-of-two scale S (match_scale_rule.h: the largest |x| of a row at or above the cut 2^-113 lands in
+// [2^13, 2^14), S and 1 / S are finite, normal powers of two for every row): nothing overflows fp16, lo stays out of the fp16
+// subnormals for every element within 2^-11 of the row maximum, and scaling by a power of two is exact;
 // statistics record of a row: (sum x^2, sum x, 1 / S, band(x) = the row's share of the expanded distance's error bound, match_device.h).
-__device__ __forceinline__ float match_row_scale(float amax) {
-  if (!(amax > 0.f) || isinf(amax)) return 1.f;
-  int e;
-  frexpf(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
-  return ldexpf(1.f, 14 - e);       // amax * S in [2^13, 2^14)
-}
 
 // one wave per row: statistics + (probes) the split row (a_hi | a_hi | a_lo)
 __global__ void match_row_prep_kernel(const float* __restrict__ x, float* __restrict__ stat4, _Float16* __restrict__ split3,
@@ -979,7 +967,7 @@ __global__ void match_row_prep_kernel(const float* __restrict__ x, float* __rest
   for (int o = 32; o > 0; o >>= 1) {
     s2 += __shfl_xor(s2, o, 64); s1 += __shfl_xor(s1, o, 64); amax = fmaxf(amax, __shfl_xor(amax, o, 64));
   }
-  const float S = match_row_scale(amax);
+  const float S = frmap_match_row_scale(amax);
   if (lane == 0) {
     stat4[4 * (size_t)r] = s2; stat4[4 * (size_t)r + 1] = s1; stat4[4 * (size_t)r + 2] = 1.0f / S;
     stat4[4 * (size_t)r + 3] = match_band(s2, (float)D);
@@ -1007,7 +995,7 @@ __global__ void match_pack_gallery_kernel(const float* __restrict__ gal, const f
     const int k3 = chunk * 32 + cg * 8 + j, row = ntile * 64 + cl;
     const int part = k3 / D, k = k3 - part * D;        // gallery side: (g_hi | g_lo | g_hi)
     float v = 0.f;
-    if (row < G) v = gal[(size_t)row * D + k] * (1.0f / stat4[4 * (size_t)row + 2]);   // (S is a power of two: 1 / (1 / S) is exact)
+    if (row < G) v = gal[(size_t)row * D + k] * (1.0f / stat4[4 * (size_t)row + 2]);   // (S and 1 / S are normal powers of two: 1 / (1 / S) is S)
     const _Float16 hi = (_Float16)v;
     out[e] = part == 1 ? (_Float16)(v - (float)hi) : hi;
   }

@@ -35,6 +35,17 @@ __device__ __forceinline__ float match_expanded_d2(float a2, float as, float w2,
   const float d2 = a2 + w2 - 2.f * dot + 2.f * eps * (as - ws) + keps;
   return d2;
 }
+// A pair WITHOUT a bound.  The expanded form says nothing once it leaves fp32: a row whose squared norm overflows (norm above about
+// 1.8e19) has sum x^2 = band = +inf, so d2 and delta are +inf and L = inf - inf is NaN; two norms that are finite but whose sum is
+// not give d2 = U = +inf with a finite delta, a "lower bound" of +inf above an exact distance that is finite; a row with a NaN
+// or an infinity in it gives NaN.  The exact distance of the first two kinds is finite (fp32 differences, squares summed in float64),
+// and the documented answer lists them.  U = d2 + delta is finite only if d2 and delta both are, and then so is L: whenever U is not
+// finite the pair's bounds become (-inf, +inf), the honest ones.  Every epilogue then treats it as in band and the exact re-score
+// decides: a record lists it first (lo = -inf <= every tau, up = +inf never lowers a tau), the verification counts queue it
+// (not sure), the threshold search keeps it (-inf is not > hi).  No NaN ever reaches a record, an fminf chain or a compare.
+__device__ __forceinline__ void match_unbounded(float& L, float& U) {
+  if (!__builtin_isfinite(U)) { L = -INFINITY; U = INFINITY; }
+}
 
 enum MatchMode { MATCH_NONE = 0, MATCH_TOP1 = 1, MATCH_TOPR = 2, MATCH_HIST = 3, MATCH_JOIN = 4 };   // MATCH_HIST: verification counts, MATCH_JOIN: threshold search
 
@@ -49,7 +60,8 @@ struct MatchTile {
 
 // The bound walk of the four match epilogues over a wave's MI*16 x 64 block, one probe row (mi) at a time:
 //   row_begin(b) -> the pointer this row's gallery statistics are read through (stat_w, or an opaque copy of it: match_epilogue_hist)
-//   pair(b, n, code, L, U): L <= exact d2 <= U of probe b and gallery row n; code = the pair's place in the block as the queues
+//   pair(b, n, code, L, U): L <= exact d2 <= U of probe b and gallery row n, (-inf, +inf) where the expanded form has no finite
+//                           bound (match_unbounded), never NaN; code = the pair's place in the block as the queues
 //                           hold it, (probe row << 6) | gallery row.  b and n may lie past the problem (their loads are clamped).
 //   row_end(b)
 // The gallery-row statistics are re-read per (mi, ni) block (L1 hits) instead of being held for the whole epilogue, so the live set
@@ -74,7 +86,9 @@ __device__ __forceinline__ void match_walk(const f32x4_t (&acc)[MI][4], const Ma
         const f32x4_t sw = *(const f32x4_t*)(sw_p + 4 * (size_t)min(n, t.G - 1));
         const float d2 = match_expanded_d2(a2, as, sw[0], sw[1], acc[mi][ni][j] * ai * sw[2], keps);
         const float dl = kap * (ab + sw[3]);
-        pair(b, n, ((mi * 16 + lr) << 6) | (ni * 16 + 4 * g + j), d2 - dl, d2 + dl);
+        float L = d2 - dl, U = d2 + dl;
+        match_unbounded(L, U);
+        pair(b, n, ((mi * 16 + lr) << 6) | (ni * 16 + 4 * g + j), L, U);
       }
     }
     row_end(b);
@@ -135,7 +149,8 @@ struct __attribute__((aligned(16))) MatchRecK {   // 64 bytes
 };
 
 // insert (L, n, U) into an ascending R-list; what falls off (or L itself) lowers `rest`.  Strict compares: an equal L goes after,
-// and a NaN L is never listed nor counted.
+// and L is never NaN (match_unbounded): a pair without a bound comes as (-inf, +inf), is listed ahead of every bounded one and, once
+// the list is full of its kind, pulls `rest` down to -inf, so the finalize re-scores the whole slot.
 __device__ __forceinline__ void match_topr_insert(float (&lo)[MATCH_R], int (&ix)[MATCH_R], float (&up)[MATCH_R], float& rest,
                                                   float L, int n, float U) {
   rest = fminf(rest, L < lo[MATCH_R - 1] ? lo[MATCH_R - 1] : L);
@@ -381,7 +396,7 @@ struct FrmapVerifyGemm {
 
 // Epilogue of conv1x1_pp_kernel<..., MATCH_HIST>: pair (probe b = A row, gallery row n = B row) has L <= d2 <= U.  With the host's
 // brackets (d2 <= lo_k => dist <= t_k, d2 > hi_k => dist > t_k, both ascending) the pair's bin is certain when kU = the first k with
-// U <= lo_k has L > hi_{kU - 1} (or kU = 0), with L and U finite: then d2 <= lo_kU and d2 > hi_k for every k < kU.  Certain pairs are
+// U <= lo_k has L > hi_{kU - 1} (or kU = 0) - which no pair without a bound, (-inf, +inf), ever has: then d2 <= lo_kU and d2 > hi_k for every k < kU.  Certain pairs are
 // binned at once; the others go to this wave's LDS queue and are re-scored by pair_drain_queue.  Returns the queue length (wave-uniform).
 template <int MI>
 __device__ __forceinline__ int match_epilogue_hist(const f32x4_t (&acc)[MI][4], const MatchTile& t, const FrmapVerifyGemm& v,
@@ -412,7 +427,8 @@ __device__ __forceinline__ int match_epilogue_hist(const f32x4_t (&acc)[MI][4], 
         bool sure = false;
         if (valid) {
           const int k = verify_bin(lo_lds, T, U);
-          sure = __builtin_isfinite(L) && __builtin_isfinite(U) && (k == 0 || L > hi_lds[k - 1]);
+          // (a pair without a bound is never sure: its U = +inf is above every lo_k, so k = T >= 1, and its L = -inf is not > hi_{T-1})
+          sure = k == 0 || L > hi_lds[k - 1];
           if (sure) {
             const int key = (la == lb_p[min(n, t.G - 1)] ? 0 : T + 1) + k;
             if (key != rk) {
@@ -520,8 +536,8 @@ struct FrmapRadiusGemm {
 // Epilogue of conv1x1_pp_kernel<..., MATCH_JOIN>: a pair with L > hi has (float)sqrt(d2) > thresh and is dropped at once, like a
 // pair outside the problem, on or below the diagonal (self mode) or filtered out by its labels.  Every other pair - surely accepted
 // or undecided: the list carries the exact distance, so both need the exact d2 - goes to this wave's LDS queue (the layout of
-// match_epilogue_hist's: it holds the wave's whole 112 x 64 block).  A NaN bound is never > hi: such a pair is re-scored and rejected
-// there.  Returns the queue length.
+// match_epilogue_hist's: it holds the wave's whole 112 x 64 block).  A pair without a bound (L = -inf) is never > hi: it is re-scored
+// and accepted or rejected there on its exact distance.  Returns the queue length.
 template <int MI>
 __device__ __forceinline__ int match_epilogue_join(const f32x4_t (&acc)[MI][4], const MatchTile& t, const FrmapRadiusGemm& r,
                                                    unsigned short* queue, int lane) {

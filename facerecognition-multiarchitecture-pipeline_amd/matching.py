@@ -232,8 +232,8 @@ def search_batch(emb: torch.Tensor, gallery, k: int, by: str = "entry"):
 def compare_faces_topk(emb, refs, thresh, k: int, by: str = "entry"):
     """compare_faces' candidate list: at most ``k`` ``(name, dist, idx)`` with ``dist <= thresh``, ascending by (dist, idx).
     ``by="name"`` lists each person once (their nearest enrolment).  ``refs``: a refs list or a `Gallery`.  Element 0 is
-    compare_faces' answer whenever that is a name (distances are the exact float64-summed ones; on galleries of <= 64 rows
-    compare_faces sums in fp32 and the two can differ in the last bit), and the list is empty when it says "Unknown".
+    compare_faces' answer whenever that is a name (distances are the exact float64-summed ones, as compare_faces'
+    own on every gallery size), and the list is empty when it says "Unknown".
     One device -> host copy."""
     if emb is None or refs is None or len(refs) == 0:
         return []
@@ -352,7 +352,7 @@ def threshold_for_far(gallery, far: float, thresholds=None) -> Tuple[Optional[fl
     impostor pairs of ``gallery`` (a `Gallery` or a refs list; identities = `Gallery.labels`) would be accepted, and the share of
     genuine pairs accepted there: ``(threshold, tar)``, or ``(None, None)`` when no threshold qualifies.  Exact counts over every
     unordered pair of enrolments (`ops.verify_counts`, self mode).  The threshold can be passed straight to `compare_faces`
-    (distances are compared the same way; on galleries of <= 64 rows compare_faces sums in fp32 and can differ in the last bit)."""
+    (distances are compared the same way)."""
     from . import evaluate
     g = _as_gallery(gallery, "cuda")
     if len(g) < 2:

@@ -523,7 +523,10 @@ int frmap_cnn_attention(const void* qkv, const void* x, const float* gamma, cons
  *                      dist +inf.  id_or_unknown_out (optional int32[B]) = idx if dist <= thresh else -1
  *                      (compare_faces' "Unknown", src/app.py:64).  packed_out (optional int32[B][2]) =
  *                      {id_or_unknown, bits of dist}: the 8-byte record the multi-GPU all-gather ships.
- *                      G <= 64 takes a one-launch exact scan.  G > 64: a GEMM scores every pair by the
+ *                      The distance is the exact one everywhere: elements (e_i - g_i) + 1e-6 in fp32,
+ *                      squares summed in float64, dist = (float)sqrt; a row whose distance is NaN or
+ *                      +inf never wins (all rows so: idx -1, dist +inf).
+ *                      G <= 64 takes a one-launch exact scan with that arithmetic.  G > 64: a GEMM scores every pair by the
  *                      expanded squared distance WITH a worst-case rounding bound, and every gallery row
  *                      that could be the minimiser within that bound is re-scored with the exact
  *                      ||(e - g) + 1e-6||_2 (float64 accumulation); the first row attaining the exact
@@ -776,7 +779,15 @@ int frmap_match_top1(const float* emb, const float* gallery, int32_t* idx_out, f
  * numbers (hi = fp16(S x), lo = fp16(S x - hi)); one K = 3 D GEMM accumulates a_hi.g_hi + a_hi.g_lo + a_lo.g_hi in
  * fp32 (the fp32 dot product to ~2^-22).  frmap_match_pack_gallery prepares a gallery ONCE: packed_out
  * (frmap_match_gallery_pack_bytes(G, D) bytes) and stat_w_out [G][4]; D % 32 == 0.  Each row is scaled by its own power
- * of two before the split, so any finite magnitude is safe.  The packer writes packed_out element by element (2-byte aligned serves
+ * of two S before the split (csrc/match_scale_rule.h).  Magnitude range: every finite fp32 row, subnormals and the zero row
+ * included, alone or mixed with any other in one call, gets the documented exact answer.  S, 1 / S and every fp16 element of the
+ * pack are finite for every row; 1 / S is a normal power of two.  A row whose largest |x| is at least the cut 2^-113 has it scaled
+ * into [2^13, 2^14); below the cut S stays at 2^126 and the row's low halves lose bits, an error far inside the rounding bound the
+ * epilogue already allows.  Past the overflow of an fp32 squared norm (a row norm above about 1.8e19, 2^64) the expanded distance of
+ * every pair of that row has no finite bound: such a pair is kept as a candidate by every epilogue (top-1, top-k, verification
+ * counts, threshold search) and decided by its exact distance, which is finite as long as the fp32 differences are (|e_i - g_i| up
+ * to FLT_MAX) and reported as long as its fp32 cast is; calls dominated by such rows run at the speed of the exact scan.  The
+ * unpacked entry points give the same answers over the same range.  The packer writes packed_out element by element (2-byte aligned serves
  * there; every call that reads the pack needs it and stat_w 16-byte aligned).  frmap_match_top1_packed: workspace =
  * frmap_match_workspace_bytes(B, G) bytes, probe_split = B * 3 * D fp16 of scratch; `gallery` is still the fp32 matrix
  * (candidates are re-scored from it). */
@@ -867,7 +878,8 @@ int frmap_match_radius_packed(const float* a, const int32_t* label_a, int P, con
 
 /* The tail of the ResNet-18 ('cnn') embed-and-match step for small galleries in ONE launch, one workgroup per face:
  * AdaptiveAvgPool2d(1) of the trunk map (face_models.py:100) -> optional F.normalize(eps) -> compare_faces' scan
- * (src/app.py:58-64) exactly as frmap_match_top1 does it for G <= 64.
+ * (src/app.py:58-64): the first strict minimum, as frmap_match_top1 for G <= 64, but with the squares summed in fp32 (pooled 16-bit
+ * maps are nowhere near the 2^64 at which an fp32 square overflows; a row whose fp32 sum does overflow is never the winner).
  *   map : [B][HW][C] (dtype) trunk output (NHWC);  gallery : fp32 [G][C], 0 <= G <= 64
  *   emb_out : fp32 [B][C] pooled (and normalised, if asked) embedding, or NULL;  other outputs as frmap_match_top1.
  * A face whose map holds a NaN / inf gets the NaN / inf embedding F.normalize would give (a NaN norm makes the row NaN) and is
