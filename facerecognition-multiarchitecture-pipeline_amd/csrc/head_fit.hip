@@ -28,8 +28,9 @@
 //
 // LDS per workgroup: 4 x 2 x 32 x 33 floats of staging (pitch 33: the 32 lanes of an operand read 32 different banks) and
 // 4 x 1024 floats of partial tiles = 50 176 bytes; the registers of the staging loads keep two workgroups a compute unit resident.
-// The tile walk, the operand loaders and the three kernel bodies are head_fit_device.h, shared with head_fit_hidden.hip.
-#include "head_fit_device.h"
+// The tile walk, the operand loaders and the three kernel bodies are head_fit_device.h, shared with head_fit_hidden.hip; so are the
+// refusals (frmap_head_fit_refusal, head_fit_twin.h: the twins begin with the same list) and the grid arithmetic (head_fit_launch.h).
+#include "head_fit_launch.h"
 
 // (two wavefronts a SIMD: the 48 loads a lane keeps in flight cost registers, and a third resident workgroup would spill them)
 __global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void head_fit_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ labels,
@@ -119,13 +120,8 @@ extern "C" size_t frmap_head_fit_workspace_bytes(int B, int D, int C) {
 extern "C" int frmap_head_fit_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale, float* w,
                                    float* b, void* state, void* workspace, int N, int B, int D, int C, float lr, float beta1, float beta2,
                                    float eps, float weight_decay, float label_smoothing, int flags, void* stream) {
-  FRMAP_REQUIRE(N >= 1, "head_fit_step: N = %d is below 1", N);
-  FRMAP_REQUIRE(B >= 1 && B <= FRMAP_HEAD_FIT_MAX_B, "head_fit_step: B = %d is outside [1, %d]", B, FRMAP_HEAD_FIT_MAX_B);
-  FRMAP_REQUIRE(D >= 1 && D <= FRMAP_HEAD_FIT_MAX_D, "head_fit_step: D = %d is outside [1, %d]", D, FRMAP_HEAD_FIT_MAX_D);
-  FRMAP_REQUIRE(C >= 1 && C <= FRMAP_HEAD_FIT_MAX_C, "head_fit_step: C = %d is outside [1, %d]", C, FRMAP_HEAD_FIT_MAX_C);
-  FRMAP_REQUIRE((flags & ~7) == 0, "head_fit_step: flags = %d has unknown bits (1 decoupled, 2 amsgrad, 4 clear)", flags);
-  FRMAP_REQUIRE(x && labels && w && b && state && workspace,
-                "head_fit_step: null pointer (x, labels, w, b, state and workspace are required)");
+  const char* why = frmap_head_fit_linear_refusal(x, labels, w, b, state, workspace, N, B, D, C, flags, 7);
+  FRMAP_REQUIRE(!why, "head_fit_step: %s (N = %d, B = %d, D = %d, C = %d, flags = %d)", why, N, B, D, C, flags);
   FRMAP_REQUIRE_ALIGNED(x, 4, "x");
   FRMAP_REQUIRE_ALIGNED(labels, 4, "labels");
   FRMAP_REQUIRE_ALIGNED(rows, 4, "rows");
@@ -142,16 +138,14 @@ extern "C" int frmap_head_fit_step(const float* x, const int32_t* labels, const 
     frmap_set_error("head_fit_step: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
     return -2;
   }
-  const int tb = (B + HF_T - 1) / HF_T, tc = (C + HF_T - 1) / HF_T, td = (D + HF_T - 1) / HF_T;
-  hipLaunchKernelGGL(head_fit_logits_kernel, dim3((unsigned)tc, (unsigned)tb), dim3(64 * HF_WAVES), 0, st, x, labels, rows, keep, keep_scale,
+  const unsigned tb = hf_tiles(B), tc = hf_tiles(C), td = hf_tiles(D);
+  hipLaunchKernelGGL(head_fit_logits_kernel, dim3(tc, tb), dim3(64 * HF_WAVES), 0, st, x, labels, rows, keep, keep_scale,
                      (const float*)w, (const float*)b, head, wk.z, wk.row_src, N, B, D, C);
   FRMAP_LAUNCH_CHECK();
-  const int want = (B + HF_WAVES - 1) / HF_WAVES;
-  hipLaunchKernelGGL(head_fit_softmax_kernel, dim3((unsigned)(want < HF_SOFTMAX_MAX_BLOCKS ? want : HF_SOFTMAX_MAX_BLOCKS)),
-                     dim3(64 * HF_WAVES), 0, st, labels, (const int32_t*)wk.row_src, head, (const float*)wk.z, wk.g, wk.row_loss, B, C,
-                     label_smoothing);
+  hipLaunchKernelGGL(head_fit_softmax_kernel, dim3(hf_softmax_blocks(B)), dim3(64 * HF_WAVES), 0, st, labels, (const int32_t*)wk.row_src, head,
+                     (const float*)wk.z, wk.g, wk.row_loss, B, C, label_smoothing);
   FRMAP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_fit_update_kernel, dim3((unsigned)td + 1, (unsigned)tc), dim3(64 * HF_WAVES), 0, st, x, keep, keep_scale, w, b, state,
+  hipLaunchKernelGGL(head_fit_update_kernel, dim3(td + 1, tc), dim3(64 * HF_WAVES), 0, st, x, keep, keep_scale, w, b, state,
                      (const float*)wk.g, (const int32_t*)wk.row_src, B, D, C, h, flags);
   FRMAP_LAUNCH_CHECK();
   return 0;
@@ -203,16 +197,15 @@ extern "C" int frmap_head_fit_group_step(const float* x, const int32_t* labels, 
                      (flags & FRMAP_HEAD_FIT_CLEAR) ? 1 : 0);
   FRMAP_LAUNCH_CHECK();
   // the grids of the single step, with the head as the slowest dimension (H <= 4096: within a grid's z)
-  const int tb = (B + HF_T - 1) / HF_T, tc = (C + HF_T - 1) / HF_T, td = (D + HF_T - 1) / HF_T;
-  hipLaunchKernelGGL(head_fit_group_logits_kernel, dim3((unsigned)tc, (unsigned)tb, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, labels, rows, keep,
-                     hyper, w, b, state, workspace, gr, N);
+  const unsigned tb = hf_tiles(B), tc = hf_tiles(C), td = hf_tiles(D);
+  hipLaunchKernelGGL(head_fit_group_logits_kernel, dim3(tc, tb, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, labels, rows, keep, hyper, w, b, state,
+                     workspace, gr, N);
   FRMAP_LAUNCH_CHECK();
-  const int want = (B + HF_WAVES - 1) / HF_WAVES;
-  hipLaunchKernelGGL(head_fit_group_softmax_kernel, dim3((unsigned)(want < HF_SOFTMAX_MAX_BLOCKS ? want : HF_SOFTMAX_MAX_BLOCKS), 1u, (unsigned)H),
-                     dim3(64 * HF_WAVES), 0, st, labels, hyper, state, workspace, gr, evaluate);
+  hipLaunchKernelGGL(head_fit_group_softmax_kernel, dim3(hf_softmax_blocks(B), 1u, (unsigned)H), dim3(64 * HF_WAVES), 0, st, labels, hyper, state,
+                     workspace, gr, evaluate);
   FRMAP_LAUNCH_CHECK();
   if (evaluate) return 0;
-  hipLaunchKernelGGL(head_fit_group_update_kernel, dim3((unsigned)td + 1, (unsigned)tc, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, keep, hyper, w, b,
+  hipLaunchKernelGGL(head_fit_group_update_kernel, dim3(td + 1, tc, (unsigned)H), dim3(64 * HF_WAVES), 0, st, x, keep, hyper, w, b,
                      state, workspace, gr, flags);
   FRMAP_LAUNCH_CHECK();
   return 0;

@@ -16,7 +16,7 @@
 // gives it.  No grid barrier, no flags between workgroups, no float atomics; integer atomics only where the shared bodies have them.
 // The three wrappers around the shared bodies are this file's own kernels: the bits are the linear step's (tests/
 // test_head_fit_hidden_gpu.py compares them kernel against kernel), and head_fit.hip's code object does not change with this file.
-#include "head_fit_device.h"
+#include "head_fit_launch.h"
 
 __global__ __launch_bounds__(64 * HF_WAVES) __attribute__((amdgpu_waves_per_eu(2))) void head_fit_hidden_logits_kernel(
     const float* __restrict__ x, const int32_t* __restrict__ labels, const uint8_t* __restrict__ keep, float keep_scale, const float* __restrict__ w,
@@ -139,27 +139,26 @@ extern "C" int frmap_head_fit_hidden_step(const float* x, const int32_t* labels,
     frmap_set_error("head_fit_hidden_step: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
     return -2;
   }
-  const int tb = (B + HF_T - 1) / HF_T, tc = (C + HF_T - 1) / HF_T, td = (D + HF_T - 1) / HF_T, th = (Hd + HF_T - 1) / HF_T;
+  const unsigned tb = hf_tiles(B), tc = hf_tiles(C), td = hf_tiles(D), th = hf_tiles(Hd);
   const dim3 block(64 * HF_WAVES);
-  hipLaunchKernelGGL(head_fit_hidden_forward_kernel, dim3((unsigned)th, (unsigned)tb), block, 0, st, x, labels, rows, keep1, keep1_scale,
+  hipLaunchKernelGGL(head_fit_hidden_forward_kernel, dim3(th, tb), block, 0, st, x, labels, rows, keep1, keep1_scale,
                      (const float*)w1, (const float*)b1, wk.h, wk.row_src1, wk.lab, N, B, D, Hd, C);
   FRMAP_LAUNCH_CHECK();
   // layer 2 forward: the single step's two kernels on (h, lab), N = B, rows = NULL
-  hipLaunchKernelGGL(head_fit_hidden_logits_kernel, dim3((unsigned)tc, (unsigned)tb), block, 0, st, (const float*)wk.h, (const int32_t*)wk.lab,
+  hipLaunchKernelGGL(head_fit_hidden_logits_kernel, dim3(tc, tb), block, 0, st, (const float*)wk.h, (const int32_t*)wk.lab,
                      keep2, keep2_scale, (const float*)w2, (const float*)b2, head2, wk2.z, wk2.row_src, B, Hd, C);
   FRMAP_LAUNCH_CHECK();
-  const int want = (B + HF_WAVES - 1) / HF_WAVES;
-  hipLaunchKernelGGL(head_fit_hidden_softmax_kernel, dim3((unsigned)(want < HF_SOFTMAX_MAX_BLOCKS ? want : HF_SOFTMAX_MAX_BLOCKS)), block, 0, st,
+  hipLaunchKernelGGL(head_fit_hidden_softmax_kernel, dim3(hf_softmax_blocks(B)), block, 0, st,
                      (const int32_t*)wk.lab, (const int32_t*)wk2.row_src, head2, (const float*)wk2.z, wk2.g, wk2.row_loss, B, C, label_smoothing);
   FRMAP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_fit_hidden_back_kernel, dim3((unsigned)th, (unsigned)tb), block, 0, st, (const float*)wk2.g, (const float*)w2,
+  hipLaunchKernelGGL(head_fit_hidden_back_kernel, dim3(th, tb), block, 0, st, (const float*)wk2.g, (const float*)w2,
                      (const float*)wk.h, keep2, keep2_scale, (const int32_t*)wk2.row_src, wk.da, head1, (const uint64_t*)head2, B, Hd, C);
   FRMAP_LAUNCH_CHECK();
   // w2 changes only now, after da was written from it
-  hipLaunchKernelGGL(head_fit_hidden_update_kernel, dim3((unsigned)th + 1, (unsigned)tc), block, 0, st, (const float*)wk.h, keep2, keep2_scale, w2, b2,
+  hipLaunchKernelGGL(head_fit_hidden_update_kernel, dim3(th + 1, tc), block, 0, st, (const float*)wk.h, keep2, keep2_scale, w2, b2,
                      state2, (const float*)wk2.g, (const int32_t*)wk2.row_src, B, Hd, C, h, flags);
   FRMAP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_fit_hidden_update_kernel, dim3((unsigned)td + 1, (unsigned)th), block, 0, st, x, keep1, keep1_scale, w1, b1, state,
+  hipLaunchKernelGGL(head_fit_hidden_update_kernel, dim3(td + 1, th), block, 0, st, x, keep1, keep1_scale, w1, b1, state,
                      (const float*)wk.da, (const int32_t*)wk.row_src1, B, D, Hd, h, flags);
   FRMAP_LAUNCH_CHECK();
   return 0;

@@ -40,6 +40,32 @@ inline int32_t frmap_head_fit_row_src(const float* x, const int32_t* labels, con
   return (int32_t)r;
 }
 
+// What a head-fitting call is refused for, before anything is read or written: NULL, or the text (it names the argument).  This is
+// the ONE list of the checks every step shares - the launchers and the twins of the single, the grouped and the hidden-layer step all
+// begin with it, so that what the device refuses is what the twin refuses -, in this order: N, B, D, C, the flag bits outside
+// `allowed` (7; 15 where FRMAP_HEAD_FIT_EVAL is a flag of the call), the `n_required` pointers that may not be NULL (`null_text`
+// lists them).
+inline const char* frmap_head_fit_refusal(int N, int B, int D, int C, int flags, int allowed, const void* const* required, int n_required,
+                                          const char* null_text) {
+  if (N < 1) return "N is below 1";
+  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
+  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
+  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
+  if (flags & ~allowed)
+    return (allowed & FRMAP_HEAD_FIT_EVAL) ? "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 8 evaluate only)"
+                                           : "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear)";
+  for (int k = 0; k < n_required; ++k)
+    if (!required[k]) return null_text;
+  return nullptr;
+}
+
+// the same for the operands of a linear head, single or grouped
+inline const char* frmap_head_fit_linear_refusal(const void* x, const void* labels, const void* w, const void* b, const void* state,
+                                                 const void* workspace, int N, int B, int D, int C, int flags, int allowed) {
+  const void* const required[] = {x, labels, w, b, state, workspace};
+  return frmap_head_fit_refusal(N, B, D, C, flags, allowed, required, 6, "null pointer (x, labels, w, b, state and workspace are required)");
+}
+
 // NULL, or why the call is refused (nothing written then).  `flags` may carry FRMAP_HEAD_FIT_EVAL (the grouped step's bit 8): the
 // forward half and the figures only.
 inline const char* frmap_head_fit_step_twin_any(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
@@ -48,12 +74,7 @@ inline const char* frmap_head_fit_step_twin_any(const float* x, const int32_t* l
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  if (N < 1) return "N is below 1";
-  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
-  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
-  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
-  if (!x || !labels || !w || !b || !state || !workspace) return "null pointer";
-  if (flags & ~15) return "unknown flag bits";
+  if (const char* why = frmap_head_fit_linear_refusal(x, labels, w, b, state, workspace, N, B, D, C, flags, 15)) return why;
   const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
   const FrmapHeadFitState st = frmap_head_fit_state(state, D, C, amsgrad);
   const FrmapHeadFitWork wk = frmap_head_fit_work(workspace, B, C);
@@ -130,23 +151,18 @@ inline const char* frmap_head_fit_step_twin_any(const float* x, const int32_t* l
 inline const char* frmap_head_fit_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
                                             float* w, float* b, void* state, void* workspace, int N, int B, int D, int C,
                                             const FrmapHeadFitHyper& h, int flags, int given_g) {
-  if (flags & ~7) return "unknown flag bits";
+  if (const char* why = frmap_head_fit_linear_refusal(x, labels, w, b, state, workspace, N, B, D, C, flags, 7)) return why;
   return frmap_head_fit_step_twin_any(x, labels, rows, keep, keep_scale, w, b, state, workspace, N, B, D, C, h, flags, given_g);
 }
 
-// what a grouped call is refused for, before anything is read or written: NULL, or the text (it names the argument)
+// what a grouped call is refused for: the shared list, then what only a group has
 inline const char* frmap_head_fit_group_refusal(const void* x, const void* labels, const void* rows, const void* keep, const void* hyper,
                                                 const void* w, const void* b, const void* state, const void* workspace, int N, int H, int B,
                                                 int D, int C, int flags) {
+  if (const char* why = frmap_head_fit_linear_refusal(x, labels, w, b, state, workspace, N, B, D, C, flags, 15)) return why;
   if (H < 1 || H > FRMAP_HEAD_FIT_MAX_H) return "H is outside [1, 4096]";
-  if (N < 1) return "N is below 1";
-  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
-  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
-  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
-  if (flags & ~15) return "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 8 evaluate only)";
   if (!rows) return "rows is NULL (a grouped step takes the rows of every head)";
   if (!hyper) return "hyper is NULL";
-  if (!x || !labels || !w || !b || !state || !workspace) return "null pointer (x, labels, w, b, state and workspace are required)";
   if (keep && (flags & FRMAP_HEAD_FIT_EVAL)) return "keep is given with flag 8 (evaluate only takes no dropout mask)";
   if (!frmap_head_fit_group_fits(H, B, D, C, (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0)) return "H, B, D, C give a byte count past 64 bits";
   return nullptr;
@@ -179,17 +195,14 @@ inline const char* frmap_head_fit_group_step_twin(const float* x, const int32_t*
   return nullptr;
 }
 
-// what a hidden-layer call is refused for, before anything is read or written: NULL, or the text (it names the argument)
+// what a hidden-layer call is refused for: the shared list, then what only it has
 inline const char* frmap_head_fit_hidden_refusal(const void* x, const void* labels, const void* w1, const void* b1, const void* w2, const void* b2,
                                                  const void* state, const void* workspace, int N, int B, int D, int Hd, int C, int flags) {
-  if (N < 1) return "N is below 1";
-  if (B < 1 || B > FRMAP_HEAD_FIT_MAX_B) return "B is outside [1, 2^20]";
-  if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
+  const void* const required[] = {x, labels, w1, b1, w2, b2, state, workspace};
+  if (const char* why = frmap_head_fit_refusal(N, B, D, C, flags, 7, required, 8,
+                                               "null pointer (x, labels, w1, b1, w2, b2, state and workspace are required)"))
+    return why;
   if (Hd < 1 || Hd > FRMAP_HEAD_FIT_MAX_D) return "Hd is outside [1, 65536]";
-  if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
-  if (flags & ~7) return "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear)";
-  if (!x || !labels || !w1 || !b1 || !w2 || !b2 || !state || !workspace)
-    return "null pointer (x, labels, w1, b1, w2, b2, state and workspace are required)";
   return nullptr;
 }
 

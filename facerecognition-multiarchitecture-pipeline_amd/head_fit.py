@@ -22,6 +22,13 @@ through a convolution exists here, and none is planned.
   the ReLU, one Adam over the four tensors.  `HiddenHead.embed` is a new embedding layer on a frozen trunk; for ``BaselineNet`` it
   is the model's own ``fc1`` (`cache_features(layer="pooled")`, `fit_head(hidden=512)`, `HiddenHead.load_into`).
 
+Structure: the three steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the seven
+size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk of the device steps and `_host_cache`, `_host_layer`,
+`_host_batch`, `_host_mask` and `_host_buffers` that of the host steps, after which a step lists its operands once and calls the library;
+`_rule_batch` (declined rows, the masked input) and `_adam_rule` are shared by the numpy rules; `_Head` holds the workspace cache, the
+pending clear and the epoch figures of `LinearHead`, `HeadGroup` and `HiddenHead`, `_linear_init` their ``nn.Linear`` draws, and
+`LinearHead._over` makes a head of views; `fit_head` is one loop over a head and its ``(width, dropout)`` mask specs.
+
 Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
 ``ArcMarginProduct``, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
@@ -52,20 +59,26 @@ F32 = np.float32
 # ---------------------------------------------------------------------------------------------------------------------------------
 # sizes and layouts
 # ---------------------------------------------------------------------------------------------------------------------------------
+_H_IN, _B_IN, _DC_IN = f"H in 1 ... {MAX_H}, ", f"B in 1 ... {MAX_B}, ", f"D in 1 ... {MAX_D}, C in 1 ... {MAX_C}"
+
+
+def _size(entry: str, limits: str, names: str, *args) -> int:
+    """What the library's size function ``entry(*args)`` returns; 0 is a shape the launcher refuses: ``names`` are the extents among
+    ``args`` that the message gives, ``limits`` what it says of them."""
+    n = int(getattr(_lib.load(), entry)(*args))
+    if n == 0:
+        raise ValueError("head_fit: unsupported " + ", ".join(f"{k} = {v}" for k, v in zip(names.split(), args)) + f" ({limits})")
+    return n
+
+
 def state_bytes(D: int, C: int, amsgrad: bool = False) -> int:
     """Bytes of an optimiser state (`frmap_head_fit_state_bytes`); ``ValueError`` for a shape the launcher refuses."""
-    n = int(_lib.load().frmap_head_fit_state_bytes(int(D), int(C), int(bool(amsgrad))))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported D = {D}, C = {C} (D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
-    return n
+    return _size("frmap_head_fit_state_bytes", _DC_IN, "D C", int(D), int(C), int(bool(amsgrad)))
 
 
 def workspace_bytes(B: int, D: int, C: int) -> int:
     """Bytes of the workspace of a step of ``B`` rows (`frmap_head_fit_workspace_bytes`)."""
-    n = int(_lib.load().frmap_head_fit_workspace_bytes(int(B), int(D), int(C)))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported B = {B}, D = {D}, C = {C} (B in 1 ... {MAX_B}, D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
-    return n
+    return _size("frmap_head_fit_workspace_bytes", _B_IN + _DC_IN, "B D C", int(B), int(D), int(C))
 
 
 def state_layout(D: int, C: int, amsgrad: bool = False) -> dict:
@@ -194,6 +207,58 @@ def loss_q(row_loss) -> int:
     return int(np.rint(l * LOSS_SCALE).astype(np.uint64).sum(dtype=np.uint64))
 
 
+def _copy_state(st: dict, dtype) -> dict:
+    """A rule state with its moments copied as ``dtype`` and its header words as ints."""
+    return {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in st.items()}
+
+
+def _adam_rule(p, grad, st: dict, which: str, t: int, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, f32):
+    """The update of the rule on one tensor (``which``: "w" or "b", the suffix of its moments in ``st``): `adam32` in float32 mode,
+    the formulas as torch evaluates them in float64.  Returns the new parameter; ``st`` is updated in place."""
+    km, kv, kx = "m_" + which, "v_" + which, "vmax_" + which
+    if f32:
+        a = adam_scalars32(t, lr, beta1, beta2, eps, weight_decay)
+        p, st[km], st[kv], vm = adam32(a, grad, p, st[km], st[kv], st.get(kx), decoupled, amsgrad)
+        if amsgrad:
+            st[kx] = vm
+        return p
+    p = np.array(p, np.float64)
+    if decoupled:
+        p *= 1.0 - lr * weight_decay
+    elif weight_decay != 0:
+        grad = grad + weight_decay * p
+    st[km] = st[km] + (1.0 - beta1) * (grad - st[km])
+    st[kv] = st[kv] * beta2 + (1.0 - beta2) * grad * grad
+    vhat = st[kv]
+    if amsgrad:
+        st[kx] = np.maximum(st[kx], st[kv])
+        vhat = st[kx]
+    denom = np.sqrt(vhat) / math.sqrt(1.0 - beta2 ** t) + eps
+    p += -(lr / (1.0 - beta1 ** t)) * (st[km] / denom)
+    return p
+
+
+def _rule_batch(x, labels, C: int, rows, B: int, keep, keep_scale, f32: bool):
+    """``(row_src, ok, x')`` of a batch of the rule: ``rows`` (``None``: rows ``0 .. B-1``) with -1 where a row is declined - outside
+    the cache, a label outside ``[0, C)``, a non-finite feature -, that as a mask, and the ``[B, D]`` input with ``keep`` applied and
+    scaled (a declined row is zeros)."""
+    N, D = x.shape
+    rows = np.arange(B, dtype=np.int64) if rows is None else np.asarray(rows).astype(np.int64)
+    row_src = np.full((len(rows),), -1, np.int32)
+    for i, r in enumerate(rows):
+        if 0 <= r < N and 0 <= labels[r] < C and np.isfinite(x[r]).all():
+            row_src[i] = r
+    ok = row_src >= 0
+    xp = np.zeros((len(rows), D), x.dtype)
+    xp[ok] = x[row_src[ok]]
+    if keep is not None:
+        kept = np.asarray(keep).astype(bool)
+        scaled = (xp * F32(keep_scale)).astype(F32) if f32 else xp * float(keep_scale)
+        xp = np.where(kept, scaled, 0).astype(x.dtype)
+        xp[~ok] = 0
+    return row_src, ok, xp
+
+
 def step_rule(x, labels, w, b, state: Optional[dict] = None, rows=None, keep=None, keep_scale: float = 1.0, *, lr: float = 1e-3,
               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0,
               decoupled: bool = False, amsgrad: bool = False, clear: bool = False, dtype=np.float64, given: Optional[dict] = None,
@@ -216,29 +281,15 @@ def step_rule(x, labels, w, b, state: Optional[dict] = None, rows=None, keep=Non
     labels = np.asarray(labels).astype(np.int64)
     N, D = x.shape
     C = w.shape[0]
-    if rows is None:                                   # rows 0 .. B-1: B is the mask's, else `batch`, else the whole cache
-        rows = np.arange(len(keep) if keep is not None else (N if batch is None else int(batch)), dtype=np.int64)
-    else:
-        rows = np.asarray(rows).astype(np.int64)
-    B = len(rows)
-    st = {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in (state or fresh_state(D, C, amsgrad, dtype)).items()}
+    st = _copy_state(state or fresh_state(D, C, amsgrad, dtype), dtype)
     if clear:
         st["rows"] = st["correct"] = st["loss_q"] = 0
-    # declined rows
-    row_src = np.full((B,), -1, np.int32)
-    for i, r in enumerate(rows):
-        if 0 <= r < N and 0 <= labels[r] < C and np.isfinite(x[r]).all():
-            row_src[i] = r
-    ok = row_src >= 0
+    # rows 0 .. B-1 without `rows`: B is the mask's, else `batch`, else the whole cache
+    row_src, ok, xp = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), keep,
+                                  keep_scale, f32)
+    B = len(row_src)
     n = int(ok.sum())
     st["n"] = n
-    xp = np.zeros((B, D), x.dtype)
-    xp[ok] = x[row_src[ok]]
-    if keep is not None:
-        kept = np.asarray(keep).astype(bool)
-        scaled = (xp * F32(keep_scale)).astype(F32) if f32 else xp * float(keep_scale)
-        xp = np.where(kept, scaled, 0).astype(x.dtype)
-        xp[~ok] = 0
     y = np.where(ok, labels[np.clip(row_src, 0, N - 1)], 0)
     ls = F32(label_smoothing) if f32 else float(label_smoothing)
     with np.errstate(all="ignore"):
@@ -277,27 +328,9 @@ def step_rule(x, labels, w, b, state: Optional[dict] = None, rows=None, keep=Non
     out["dw"], out["db"] = dw, db
     if n:
         st["t"] += 1
-        t = st["t"]
-        if f32:
-            a = adam_scalars32(t, lr, beta1, beta2, eps, weight_decay)
-            w, st["m_w"], st["v_w"], vm = adam32(a, dw, w, st["m_w"], st["v_w"], st.get("vmax_w"), decoupled, amsgrad)
-            b, st["m_b"], st["v_b"], vb = adam32(a, db, b, st["m_b"], st["v_b"], st.get("vmax_b"), decoupled, amsgrad)
-            if amsgrad:
-                st["vmax_w"], st["vmax_b"] = vm, vb
-        else:
-            for p, grad, km, kv, kx in ((w, dw, "m_w", "v_w", "vmax_w"), (b, db, "m_b", "v_b", "vmax_b")):
-                if decoupled:
-                    p *= 1.0 - lr * weight_decay
-                elif weight_decay != 0:
-                    grad = grad + weight_decay * p
-                st[km] = st[km] + (1.0 - beta1) * (grad - st[km])
-                st[kv] = st[kv] * beta2 + (1.0 - beta2) * grad * grad
-                vhat = st[kv]
-                if amsgrad:
-                    st[kx] = np.maximum(st[kx], st[kv])
-                    vhat = st[kx]
-                denom = np.sqrt(vhat) / math.sqrt(1.0 - beta2 ** t) + eps
-                p += -(lr / (1.0 - beta1 ** t)) * (st[km] / denom)
+        kw = dict(t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
+                  f32=f32)
+        w, b = _adam_rule(w, dw, st, "w", **kw), _adam_rule(b, db, st, "b", **kw)
     out["w"], out["b"], out["state"] = w, b, st
     return out
 
@@ -309,6 +342,75 @@ def _flags(decoupled, amsgrad, clear) -> int:
     return (DECOUPLED if decoupled else 0) | (AMSGRAD if amsgrad else 0) | (CLEAR if clear else 0)
 
 
+def _host_cache(op, x, labels):
+    """``(x, labels, N, D)`` of a host step: the cache as contiguous float32 ``[N, D]`` and int32 ``[N]``."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if x.ndim != 2 or labels.shape != (x.shape[0],):
+        raise ValueError(f"{op}: x [N, D] and labels [N] expected")
+    return x, labels, x.shape[0], x.shape[1]
+
+
+def _host_array(op, name, t, dt):
+    if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
+        raise ValueError(f"{op}: {name} must be a writable contiguous {np.dtype(dt).name} array")
+
+
+def _host_layer(op, wname, bname, w, b, lead, fan_out, fan_in):
+    """The leading extents of ``w [*lead, fan_out, fan_in]`` with ``b [*lead, fan_out]``, both writable float32 (``lead``, ``fan_out``:
+    the letters of the message)."""
+    _host_array(op, wname, w, np.float32)
+    _host_array(op, bname, b, np.float32)
+    if w.ndim != len(lead) + 2 or w.shape[-1] != fan_in or b.shape != w.shape[:-1]:
+        at = "".join(k + ", " for k in lead) + fan_out
+        raise ValueError(f"{op}: {wname} [{at}, {fan_in}] and {bname} [{at}] expected, got {w.shape} and {b.shape}")
+    return w.shape[:-1]
+
+
+def _host_batch(op, N, rows, masks, batch):
+    """``(rows, B)`` of a single-head host step: ``rows`` as int32 ``[B]``; without it B is the first mask's row count, else
+    ``batch``, else N, and at most N."""
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.ndim != 1:
+            raise ValueError(f"{op}: rows [B] expected")
+        return rows, len(rows)
+    B = next((len(m) for m in masks if m is not None), N if batch is None else int(batch))
+    if B > N:
+        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    return None, B
+
+
+def _host_mask(op, name, keep, shape):
+    if keep is None:
+        return None
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    if keep.shape != shape:
+        raise ValueError(f"{op}: {name} must be {list(shape)}, got {keep.shape}")
+    return keep
+
+
+def _host_buffers(op, state, nstate, workspace, nbytes, given_g):
+    """The state is ``nstate`` bytes, 8-byte aligned; the workspace exactly ``nbytes`` bytes, 4-byte aligned, or ``None`` for a fresh
+    one, which ``given_g`` cannot take.  Returns the workspace."""
+    _host_array(op, "state", state, np.uint8)
+    if state.shape != (nstate,) or state.ctypes.data % 8:
+        raise ValueError(f"{op}: state must be {nstate} bytes, 8-byte aligned")
+    if workspace is None:
+        if given_g:
+            raise ValueError(f"{op}: given_g needs the workspace that holds z, g and row_loss")
+        workspace = np.zeros((nbytes,), np.uint8)
+    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
+            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
+        raise ValueError(f"{op}: workspace must be a writable uint8 array of exactly {nbytes} bytes")
+    return workspace
+
+
+def _at(a) -> int:
+    """The address of a host array, 0 for ``None``."""
+    return 0 if a is None else a.ctypes.data
+
+
 def step_host(x, labels, w, b, state: np.ndarray, workspace: Optional[np.ndarray] = None, rows=None, keep=None, keep_scale: float = 1.0, *,
               lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
               label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False, clear: bool = False, given_g: bool = False,
@@ -317,49 +419,67 @@ def step_host(x, labels, w, b, state: np.ndarray, workspace: Optional[np.ndarray
     ``w`` [C, D], ``b`` [C] (float32) and ``state`` (uint8, `state_bytes` bytes) are updated IN PLACE; ``workspace`` (uint8, exactly
     `workspace_bytes` bytes, or ``None`` for a fresh one) receives z, g, row_loss and row_src - with ``given_g`` its z, g and
     row_loss are inputs.  ``batch``: B when neither ``rows`` nor ``keep`` gives it (default N).  Returns the workspace."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    if x.ndim != 2 or labels.shape != (x.shape[0],):
-        raise ValueError("head_fit.step_host: x [N, D] and labels [N] expected")
-    N, D = x.shape
-    for name, t, dt in (("w", w, np.float32), ("b", b, np.float32), ("state", state, np.uint8)):
-        if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
-            raise ValueError(f"head_fit.step_host: {name} must be a writable contiguous {np.dtype(dt).name} array")
-    if w.ndim != 2 or w.shape[1] != D or b.shape != (w.shape[0],):
-        raise ValueError(f"head_fit.step_host: w [C, {D}] and b [C] expected, got {w.shape} and {b.shape}")
-    C = w.shape[0]
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        if rows.ndim != 1:
-            raise ValueError("head_fit.step_host: rows [B] expected")
-    B = len(rows) if rows is not None else (len(keep) if keep is not None else (N if batch is None else int(batch)))
-    if keep is not None:
-        keep = np.ascontiguousarray(keep, dtype=np.uint8)
-        if keep.shape != (B, D):
-            raise ValueError(f"head_fit.step_host: keep must be [{B}, {D}], got {keep.shape}")
-    if rows is None and B > N:
-        raise ValueError(f"head_fit.step_host: {B} batch rows without `rows` exceed the {N} cached rows")
-    if state.shape != (state_bytes(D, C, amsgrad),) or state.ctypes.data % 8:
-        raise ValueError(f"head_fit.step_host: state must be {state_bytes(D, C, amsgrad)} bytes, 8-byte aligned")
-    nbytes = workspace_bytes(B, D, C)
-    if workspace is None:
-        if given_g:
-            raise ValueError("head_fit.step_host: given_g needs the workspace that holds z, g and row_loss")
-        workspace = np.zeros((nbytes,), np.uint8)
-    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
-            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
-        raise ValueError(f"head_fit.step_host: workspace must be a writable uint8 array of exactly {nbytes} bytes")
-    _lib.check(_lib.load().frmap_head_fit_step_host(x.ctypes.data, labels.ctypes.data, rows.ctypes.data if rows is not None else 0,
-                                                    keep.ctypes.data if keep is not None else 0, float(keep_scale), w.ctypes.data,
-                                                    b.ctypes.data, state.ctypes.data, workspace.ctypes.data, N, B, D, C, float(lr),
-                                                    float(beta1), float(beta2), float(eps), float(weight_decay), float(label_smoothing),
-                                                    _flags(decoupled, amsgrad, clear), int(bool(given_g))), "head_fit.step_host")
+    op = "head_fit.step_host"
+    x, labels, N, D = _host_cache(op, x, labels)
+    C, = _host_layer(op, "w", "b", w, b, "", "C", D)
+    rows, B = _host_batch(op, N, rows, (keep,), batch)
+    keep = _host_mask(op, "keep", keep, (B, D))
+    workspace = _host_buffers(op, state, state_bytes(D, C, amsgrad), workspace, workspace_bytes(B, D, C), given_g)
+    _lib.check(_lib.load().frmap_head_fit_step_host(_at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w), _at(b), _at(state),
+                                                    _at(workspace), N, B, D, C, float(lr), float(beta1), float(beta2), float(eps),
+                                                    float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear),
+                                                    int(bool(given_g))), op)
     return workspace
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the step on the device
 # ---------------------------------------------------------------------------------------------------------------------------------
+def _cache(op, entry, x, labels):
+    """``(x, N, D)`` of a device step: the cache ``x`` as the library takes it, float32 ``[N, D]``, with ``labels`` int32 ``[N]``."""
+    x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
+    N, D = int(x.shape[0]), int(x.shape[1])
+    _sized(labels, op, "labels", (N,), torch.int32)
+    return x, N, D
+
+
+def _layer(w, b, op, wname, bname, fan_in) -> int:
+    """``fan_out`` of a layer ``w [fan_out, fan_in]``, ``b [fan_out]`` (float32)."""
+    _sized(w, op, wname, (w.shape[0] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1, fan_in), torch.float32)
+    _sized(b, op, bname, (int(w.shape[0]),), torch.float32)
+    return int(w.shape[0])
+
+
+def _batch(op, entry, N, rows, masks, batch):
+    """``(rows, B)`` of a single-head device step: ``rows`` int32 ``[B]`` as the library takes it; without it the rows are
+    ``0 .. B-1`` with B the first ``[B, .]`` mask's row count, else ``batch``, else N, and at most N."""
+    if rows is not None:
+        if isinstance(rows, torch.Tensor) and rows.dim() != 1:
+            raise ValueError(f"{op}: rows [B] expected, got {tuple(rows.shape)}")
+        rows = _dev(rows, f"{op}.rows", torch.int32, (entry, "rows"))
+        return rows, int(rows.shape[0])
+    B = N if batch is None else int(batch)
+    for m in masks:
+        if isinstance(m, torch.Tensor) and m.dim() == 2:
+            B = int(m.shape[0])
+            break
+    if B > N:
+        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    return None, B
+
+
+def _operand(t, op, entry, name, dtype, owned=False):
+    """`_dev` of the operand ``name`` (``None`` stays ``None``).  A read-only operand may come back as a copy, which the caller's name
+    for it holds until the launch is enqueued; an ``owned`` one - the call writes it - is refused instead."""
+    return None if t is None else _dev(t, f"{op}.{name}", dtype, (entry, name), owned=owned)
+
+
+def _dev_at(t) -> int:
+    return 0 if t is None else t.data_ptr()
+
+
 @ops._on_operand_device
 def step(x: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, b: torch.Tensor, state: torch.Tensor, workspace: torch.Tensor,
          rows: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, *, lr: float = 1e-3,
@@ -370,73 +490,97 @@ def step(x: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, b: torch.Tensor
     `state_bytes` bytes (zeros = fresh; updated in place), ``workspace`` uint8 of exactly `workspace_bytes` bytes (written),
     ``rows`` int32 ``[B]`` or ``None`` (rows ``0 .. B-1``; ``B`` is then ``keep``'s row count, else ``batch``, else ``N``), ``keep`` uint8 ``[B, D]``
     or ``None``.  Every extent that depends on another operand is checked here, before the library sees a pointer."""
-    op = "head_fit.step"
-    x = _dev(x, f"{op}.x", torch.float32, ("frmap_head_fit_step", "x"))
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
-    N, D = int(x.shape[0]), int(x.shape[1])
-    _sized(labels, op, "labels", (N,), torch.int32)
-    _sized(w, op, "w", (w.shape[0] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1, D), torch.float32)
-    C = int(w.shape[0])
-    _sized(b, op, "b", (C,), torch.float32)
-    if rows is not None:
-        if isinstance(rows, torch.Tensor) and rows.dim() != 1:
-            raise ValueError(f"{op}: rows [B] expected, got {tuple(rows.shape)}")
-        rows = _dev(rows, f"{op}.rows", torch.int32, ("frmap_head_fit_step", "rows"))
-        B = int(rows.shape[0])
-    elif keep is not None and isinstance(keep, torch.Tensor) and keep.dim() == 2:
-        B = int(keep.shape[0])
-    else:
-        B = N if batch is None else int(batch)
-    if rows is None and B > N:
-        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    op, entry = "head_fit.step", "frmap_head_fit_step"
+    x, N, D = _cache(op, entry, x, labels)
+    C = _layer(w, b, op, "w", "b", D)
+    rows, B = _batch(op, entry, N, rows, (keep,), batch)
     if keep is not None:
         _sized(keep, op, "keep", (B, D), torch.uint8)
     _sized(state, op, "state", (state_bytes(D, C, amsgrad),), torch.uint8)
     _sized(workspace, op, "workspace", (workspace_bytes(B, D, C),), torch.uint8)
-    held = []                                                   # copies `_dev` made live until the launch is enqueued
-    labels = _dev(labels, f"{op}.labels", torch.int32, ("frmap_head_fit_step", "labels"))
-    keep = None if keep is None else _dev(keep, f"{op}.keep", torch.uint8, ("frmap_head_fit_step", "keep"))
-    held += [x, labels, rows, keep]
-    w = _dev(w, f"{op}.w", torch.float32, ("frmap_head_fit_step", "w"), owned=True)
-    b = _dev(b, f"{op}.b", torch.float32, ("frmap_head_fit_step", "b"), owned=True)
-    state = _dev(state, f"{op}.state", torch.uint8, ("frmap_head_fit_step", "state"), owned=True)
-    workspace = _dev(workspace, f"{op}.workspace", torch.uint8, ("frmap_head_fit_step", "workspace"), owned=True)
-    _lib.check(_lib.load().frmap_head_fit_step(x.data_ptr(), labels.data_ptr(), rows.data_ptr() if rows is not None else 0,
-                                               keep.data_ptr() if keep is not None else 0, float(keep_scale), w.data_ptr(), b.data_ptr(),
-                                               state.data_ptr(), workspace.data_ptr(), N, B, D, C, float(lr), float(beta1), float(beta2),
-                                               float(eps), float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear),
-                                               _stream()), op)
-    del held
+    labels = _operand(labels, op, entry, "labels", torch.int32)
+    keep = _operand(keep, op, entry, "keep", torch.uint8)
+    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _lib.check(_lib.load().frmap_head_fit_step(x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w.data_ptr(),
+                                               b.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, C, float(lr), float(beta1),
+                                               float(beta2), float(eps), float(weight_decay), float(label_smoothing),
+                                               _flags(decoupled, amsgrad, clear), _stream()), op)
 
 
-class LinearHead:
+def _linear_init(fan_out: int, fan_in: int, generator):
+    """``(w, b)`` of an ``nn.Linear(fan_in, fan_out)`` on the CPU (Kaiming-uniform with a = sqrt(5): both uniform in ±1/sqrt(fan_in)),
+    two draws from ``generator``, the weight first."""
+    bound = 1.0 / math.sqrt(fan_in)
+    w = (torch.rand((fan_out, fan_in), generator=generator, dtype=torch.float32) * 2 - 1) * bound
+    b = (torch.rand((fan_out,), generator=generator, dtype=torch.float32) * 2 - 1) * bound
+    return w, b
+
+
+def _figures(words) -> dict:
+    """`figures_of` the 8 words of a state's header, and the step count ``t``."""
+    out = figures_of({name: words[k] for k, name in enumerate(HEADER)})
+    out["t"] = int(words[0])
+    return out
+
+
+class _Head:
+    """What the heads share: ``state`` on ``device``, a workspace per batch size (`_workspace_bytes` is the head's own), the pending
+    clear of the epoch figures, and their one host copy.  ``_header_at``: where the 64-byte header with the figures sits in ``state``."""
+    _header_at = 0
+
+    def _start(self, state: torch.Tensor, device, clear: bool = True):
+        self.state, self.device, self._workspaces, self._clear = state, device, {}, clear
+
+    def _workspace(self, B: int) -> torch.Tensor:
+        ws = self._workspaces.get(B)
+        if ws is None:
+            ws = self._workspaces[B] = torch.empty((self._workspace_bytes(B),), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def new_epoch(self):
+        """The next `step` (or `evaluate`) clears the epoch figures first."""
+        self._clear = True
+        return self
+
+    def _run(self, fn, *operands, **kw):
+        """One library step ``fn`` with the head's ``amsgrad`` and its pending clear, which only an accepted call spends."""
+        fn(*operands, amsgrad=self.amsgrad, clear=self._clear, **kw)
+        self._clear = False
+        return self
+
+    def epoch_figures(self) -> dict:
+        """The one host copy: rows, correct, accuracy and mean loss since the last `new_epoch`, and the step count ``t``."""
+        return _figures(self.state[self._header_at: self._header_at + 64].cpu().numpy().view(np.uint64))
+
+
+class LinearHead(_Head):
     """A linear softmax classifier ``[C, D]`` on the device with its Adam state and a workspace.  ``weight`` / ``bias`` are
     initialised as ``nn.Linear`` does (Kaiming-uniform with a = sqrt(5): both uniform in ±1/sqrt(D)) from ``generator`` (a CPU
     ``torch.Generator``; ``None``: torch's default)."""
 
     def __init__(self, D: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
-        self.D, self.C, self.amsgrad = int(D), int(C), bool(amsgrad)
-        nbytes = state_bytes(self.D, self.C, self.amsgrad)          # (refuses a bad shape)
-        bound = 1.0 / math.sqrt(self.D)
-        w = (torch.rand((self.C, self.D), generator=generator, dtype=torch.float32) * 2 - 1) * bound
-        b = (torch.rand((self.C,), generator=generator, dtype=torch.float32) * 2 - 1) * bound
-        self.device = torch.device(device)
-        self.weight, self.bias = w.to(self.device), b.to(self.device)
-        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
-        self._workspaces = {}
-        self._clear = True
+        nbytes = state_bytes(int(D), int(C), bool(amsgrad))          # (refuses a bad shape)
+        w, b = _linear_init(int(C), int(D), generator)
+        device = torch.device(device)
+        self._adopt(w.to(device), b.to(device), torch.zeros((nbytes,), dtype=torch.uint8, device=device), amsgrad, device, True)
 
-    def _workspace(self, B: int) -> torch.Tensor:
-        ws = self._workspaces.get(B)
-        if ws is None:
-            ws = self._workspaces[B] = torch.empty((workspace_bytes(B, self.D, self.C),), dtype=torch.uint8, device=self.device)
-        return ws
+    def _adopt(self, weight, bias, state, amsgrad, device, clear):
+        self.C, self.D, self.amsgrad = int(weight.shape[0]), int(weight.shape[1]), bool(amsgrad)
+        self.weight, self.bias = weight, bias
+        self._start(state, device, clear)
 
-    def new_epoch(self) -> "LinearHead":
-        """The next `step` clears the epoch figures first."""
-        self._clear = True
-        return self
+    @classmethod
+    def _over(cls, weight, bias, state, amsgrad, device) -> "LinearHead":
+        """A head whose ``weight`` ``[C, D]``, ``bias`` and ``state`` are the given tensors - views of a larger head's memory - with no
+        clear pending."""
+        one = cls.__new__(cls)
+        one._adopt(weight, bias, state, amsgrad, device, False)
+        return one
+
+    def _workspace_bytes(self, B: int) -> int:
+        return workspace_bytes(B, self.D, self.C)
 
     def step(self, x: torch.Tensor, labels: torch.Tensor, rows: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, *,
              lr: float, keep_scale: Optional[float] = None, dropout: float = 0.0, beta1: float = 0.9, beta2: float = 0.999,
@@ -447,18 +591,8 @@ class LinearHead:
             keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
         B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
             int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
-        step(x, labels, self.weight, self.bias, self.state, self._workspace(B), rows, keep, keep_scale, lr=lr, beta1=beta1, beta2=beta2,
-             eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled, amsgrad=self.amsgrad,
-             clear=self._clear)
-        self._clear = False
-        return self
-
-    def epoch_figures(self) -> dict:
-        """The one host copy: rows, correct, accuracy and mean loss since the last `new_epoch`, and the step count ``t``."""
-        words = self.state[:64].cpu().numpy().view(np.uint64)
-        out = figures_of({name: words[k] for k, name in enumerate(HEADER)})
-        out["t"] = int(words[0])
-        return out
+        return self._run(step, x, labels, self.weight, self.bias, self.state, self._workspace(B), rows, keep, keep_scale, lr=lr, beta1=beta1,
+                         beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
 
     def logits(self, x: torch.Tensor) -> torch.Tensor:
         return ops.linear_f32(x, self.weight, None, self.bias)
@@ -520,6 +654,21 @@ def cache_features(model, model_type: str, data, batch_size: int = 256, device="
     return torch.cat(feats).contiguous(), torch.cat(labs).contiguous()
 
 
+def _head_generator(generator):
+    """The generator heads are drawn from: ``generator`` when it is a CPU one, else torch's default (``None``)."""
+    return generator if generator is not None and generator.device.type == "cpu" else None
+
+
+def _generators(generator, device):
+    """``(_head_generator, the device generator of permutations and masks)``: ``generator`` itself when it lives on a device; for a CPU
+    one a fresh generator on ``device`` seeded by ONE ``randint(0, 2**62)`` draw from it, taken here; ``None`` for ``None``."""
+    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
+    if generator is not None and dev_gen is None:
+        dev_gen = torch.Generator(device=device)
+        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
+    return _head_generator(generator), dev_gen
+
+
 def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3,
              weight_decay: float = 1e-4, dropout: float = 0.1, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
              generator: Optional[torch.Generator] = None, num_classes: Optional[int] = None, device="cuda", hidden: Optional[int] = None,
@@ -539,58 +688,19 @@ def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10
     from . import evaluate
     if model_type == 'siamese':
         raise ValueError("head_fit: a siamese model has no classifier head to fit (pairs are verification_metrics' business)")
-    if hidden is not None:
-        return _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size, lr, weight_decay, dropout, label_smoothing,
-                                decoupled, amsgrad, generator, num_classes, device, int(hidden), float(hidden_dropout))
-    feats, labels = cache_features(model, model_type, train_data, device=device)
-    N, D = int(feats.shape[0]), int(feats.shape[1])
-    C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
-    head_gen = None
-    if generator is not None and generator.device.type == "cpu":
-        head_gen = generator
-    head = LinearHead(D, C, feats.device, amsgrad=amsgrad, generator=head_gen)
-    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
-    if generator is not None and dev_gen is None:
-        dev_gen = torch.Generator(device=feats.device)
-        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
-    val = None
-    if val_data is not None:
-        val = cache_features(model, model_type, val_data, device=device)
-    history = {"train_loss": [], "train_acc": [], "val": []}
-    for _ in range(int(epochs)):
-        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
-        head.new_epoch()
-        for lo in range(0, N, int(batch_size)):
-            rows = perm[lo: lo + int(batch_size)]
-            keep = None
-            if dropout > 0:
-                keep = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8)
-            head.step(feats, labels, rows, keep, lr=lr, dropout=dropout, weight_decay=weight_decay, label_smoothing=label_smoothing,
-                      decoupled=decoupled)
-        fig = head.epoch_figures()
-        history["train_loss"].append(fig["loss"])
-        history["train_acc"].append(fig["accuracy"])
-        if val is not None:
-            tally = evaluate.ClassificationTally(C, device=feats.device)
-            tally.update(head.logits(val[0]), val[1])
-            history["val"].append(tally.metrics())
-    return head, history
-
-
-def _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size, lr, weight_decay, dropout, label_smoothing, decoupled,
-                     amsgrad, generator, num_classes, device, hidden, hidden_dropout):
-    """`fit_head(hidden=...)`: `fit_head`'s loop on a `HiddenHead`, with a second mask draw."""
-    from . import evaluate
-    layer = "pooled" if type(model).__name__ == "BaselineNet" else "embedding"
+    layer = "pooled" if hidden is not None and type(model).__name__ == "BaselineNet" else "embedding"
     feats, labels = cache_features(model, model_type, train_data, device=device, layer=layer)
     N, D = int(feats.shape[0]), int(feats.shape[1])
     C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
-    head_gen = generator if generator is not None and generator.device.type == "cpu" else None
-    head = HiddenHead(D, hidden, C, feats.device, amsgrad=amsgrad, generator=head_gen)
-    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
-    if generator is not None and dev_gen is None:
-        dev_gen = torch.Generator(device=feats.device)
-        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
+    # the head is drawn first, then the device generator's seed; per step one mask per (width, dropout), in this order
+    if hidden is None:
+        head = LinearHead(D, C, feats.device, amsgrad=amsgrad, generator=_head_generator(generator))
+        masks, drop_kw = [(D, dropout)], dict(dropout=dropout)
+    else:
+        hidden, hidden_dropout = int(hidden), float(hidden_dropout)
+        head = HiddenHead(D, hidden, C, feats.device, amsgrad=amsgrad, generator=_head_generator(generator))
+        masks, drop_kw = [(D, dropout), (hidden, hidden_dropout)], dict(dropout1=dropout, dropout2=hidden_dropout)
+    dev_gen = _generators(generator, feats.device)[1]
     val = None
     if val_data is not None:
         val = cache_features(model, model_type, val_data, device=device, layer=layer)
@@ -600,13 +710,10 @@ def _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size
         head.new_epoch()
         for lo in range(0, N, int(batch_size)):
             rows = perm[lo: lo + int(batch_size)]
-            keep1 = keep2 = None
-            if dropout > 0:
-                keep1 = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8)
-            if hidden_dropout > 0:
-                keep2 = (torch.rand((rows.shape[0], hidden), device=feats.device, generator=dev_gen) >= hidden_dropout).to(torch.uint8)
-            head.step(feats, labels, rows, keep1, keep2, lr=lr, dropout1=dropout, dropout2=hidden_dropout, weight_decay=weight_decay,
-                      label_smoothing=label_smoothing, decoupled=decoupled)
+            keeps = [(torch.rand((rows.shape[0], width), device=feats.device, generator=dev_gen) >= p).to(torch.uint8) if p > 0 else None
+                     for width, p in masks]
+            head.step(feats, labels, rows, *keeps, lr=lr, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled,
+                      **drop_kw)
         fig = head.epoch_figures()
         history["train_loss"].append(fig["loss"])
         history["train_acc"].append(fig["accuracy"])
@@ -622,27 +729,17 @@ def _fit_hidden_head(model, model_type, train_data, val_data, epochs, batch_size
 # ---------------------------------------------------------------------------------------------------------------------------------
 def group_state_stride(D: int, C: int, amsgrad: bool = False) -> int:
     """Bytes from head h's state to head h + 1's (`frmap_head_fit_group_state_stride`): `state_bytes` rounded up to 8."""
-    n = int(_lib.load().frmap_head_fit_group_state_stride(int(D), int(C), int(bool(amsgrad))))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported D = {D}, C = {C} (D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
-    return n
+    return _size("frmap_head_fit_group_state_stride", _DC_IN, "D C", int(D), int(C), int(bool(amsgrad)))
 
 
 def group_state_bytes(H: int, D: int, C: int, amsgrad: bool = False) -> int:
     """Bytes of the states of ``H`` heads (`frmap_head_fit_group_state_bytes`): ``H`` strides."""
-    n = int(_lib.load().frmap_head_fit_group_state_bytes(int(H), int(D), int(C), int(bool(amsgrad))))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported H = {H}, D = {D}, C = {C} (H in 1 ... {MAX_H}, D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
-    return n
+    return _size("frmap_head_fit_group_state_bytes", _H_IN + _DC_IN, "H D C", int(H), int(D), int(C), int(bool(amsgrad)))
 
 
 def group_workspace_bytes(H: int, B: int, D: int, C: int) -> int:
     """Bytes of the workspaces of ``H`` heads stepping ``B`` rows each (`frmap_head_fit_group_workspace_bytes`)."""
-    n = int(_lib.load().frmap_head_fit_group_workspace_bytes(int(H), int(B), int(D), int(C)))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported H = {H}, B = {B}, D = {D}, C = {C} (H in 1 ... {MAX_H}, B in 1 ... {MAX_B}, "
-                         f"D in 1 ... {MAX_D}, C in 1 ... {MAX_C})")
-    return n
+    return _size("frmap_head_fit_group_workspace_bytes", _H_IN + _B_IN + _DC_IN, "H B D C", int(H), int(B), int(D), int(C))
 
 
 def _per_head(v, H: int, name: str) -> np.ndarray:
@@ -686,7 +783,7 @@ def group_step_rule(x, labels, w, b, states, rows, keep=None, *, hyper, decouple
                       decoupled=decoupled, amsgrad=amsgrad, clear=clear, dtype=dtype, given=None if given is None else given[h])
         if evaluate:
             D, C = np.asarray(w[h]).shape[1], np.asarray(w[h]).shape[0]
-            old = {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in (st or fresh_state(D, C, amsgrad, dtype)).items()}
+            old = _copy_state(st or fresh_state(D, C, amsgrad, dtype), dtype)
             for k in ("n", "rows", "correct", "loss_q"):
                 old[k] = r["state"][k]
             r["w"], r["b"], r["state"] = np.array(w[h], dtype), np.array(b[h], dtype), old
@@ -702,17 +799,8 @@ def group_step_host(x, labels, rows, hyper, w, b, state: np.ndarray, workspace: 
     ``None`` for a fresh one) receives every head's z, g, row_loss and row_src; ``keep`` uint8 ``[H, B, D]`` or ``None``.  Returns the
     workspace."""
     op = "head_fit.group_step_host"
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    if x.ndim != 2 or labels.shape != (x.shape[0],):
-        raise ValueError(f"{op}: x [N, D] and labels [N] expected")
-    N, D = x.shape
-    for name, t, dt in (("w", w, np.float32), ("b", b, np.float32), ("state", state, np.uint8)):
-        if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
-            raise ValueError(f"{op}: {name} must be a writable contiguous {np.dtype(dt).name} array")
-    if w.ndim != 3 or w.shape[2] != D or b.shape != w.shape[:2]:
-        raise ValueError(f"{op}: w [H, C, {D}] and b [H, C] expected, got {w.shape} and {b.shape}")
-    H, C = int(w.shape[0]), int(w.shape[1])
+    x, labels, N, D = _host_cache(op, x, labels)
+    H, C = _host_layer(op, "w", "b", w, b, "H", "C", D)
     if rows is None:
         raise ValueError(f"{op}: rows [H, B] is required")
     rows = np.ascontiguousarray(rows, dtype=np.int32)
@@ -724,27 +812,13 @@ def group_step_host(x, labels, rows, hyper, w, b, state: np.ndarray, workspace: 
     hyper = np.ascontiguousarray(hyper, dtype=np.float32)
     if hyper.shape != (H, 8):
         raise ValueError(f"{op}: hyper must be [{H}, 8], got {hyper.shape}")
-    if keep is not None:
-        if evaluate:
-            raise ValueError(f"{op}: keep cannot be given with evaluate=True")
-        keep = np.ascontiguousarray(keep, dtype=np.uint8)
-        if keep.shape != (H, B, D):
-            raise ValueError(f"{op}: keep must be [{H}, {B}, {D}], got {keep.shape}")
-    nstate = group_state_bytes(H, D, C, amsgrad)
-    if state.shape != (nstate,) or state.ctypes.data % 8:
-        raise ValueError(f"{op}: state must be {nstate} bytes, 8-byte aligned")
-    nbytes = group_workspace_bytes(H, B, D, C)
-    if workspace is None:
-        if given_g:
-            raise ValueError(f"{op}: given_g needs the workspace that holds z, g and row_loss")
-        workspace = np.zeros((nbytes,), np.uint8)
-    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
-            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
-        raise ValueError(f"{op}: workspace must be a writable uint8 array of exactly {nbytes} bytes")
-    _lib.check(_lib.load().frmap_head_fit_group_step_host(x.ctypes.data, labels.ctypes.data, rows.ctypes.data,
-                                                          keep.ctypes.data if keep is not None else 0, hyper.ctypes.data, w.ctypes.data,
-                                                          b.ctypes.data, state.ctypes.data, workspace.ctypes.data, N, H, B, D, C,
-                                                          _group_flags(decoupled, amsgrad, clear, evaluate), int(bool(given_g))), op)
+    if keep is not None and evaluate:
+        raise ValueError(f"{op}: keep cannot be given with evaluate=True")
+    keep = _host_mask(op, "keep", keep, (H, B, D))
+    workspace = _host_buffers(op, state, group_state_bytes(H, D, C, amsgrad), workspace, group_workspace_bytes(H, B, D, C), given_g)
+    _lib.check(_lib.load().frmap_head_fit_group_step_host(_at(x), _at(labels), _at(rows), _at(keep), _at(hyper), _at(w), _at(b), _at(state),
+                                                          _at(workspace), N, H, B, D, C, _group_flags(decoupled, amsgrad, clear, evaluate),
+                                                          int(bool(given_g))), op)
     return workspace
 
 
@@ -759,15 +833,11 @@ def group_step(x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, hyper:
     `group_workspace_bytes` bytes, ``keep`` uint8 ``[H, B, D]`` or ``None``.  ``evaluate``: figures only (flag 8; no ``keep``).
     Every extent that depends on another operand is checked here, before the library sees a pointer."""
     op, entry = "head_fit.group_step", "frmap_head_fit_group_step"
-    x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
-    N, D = int(x.shape[0]), int(x.shape[1])
+    x, N, D = _cache(op, entry, x, labels)
     if not isinstance(w, torch.Tensor) or w.dim() != 3:
         raise ValueError(f"{op}: w [H, C, D] expected, got {tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__}")
     H, C = int(w.shape[0]), int(w.shape[1])
     _sized(w, op, "w", (H, C, D), torch.float32)
-    _sized(labels, op, "labels", (N,), torch.int32)
     _sized(b, op, "b", (H, C), torch.float32)
     if not isinstance(rows, torch.Tensor) or rows.dim() != 2:
         raise ValueError(f"{op}: rows [H, B] expected, got {tuple(rows.shape) if isinstance(rows, torch.Tensor) else type(rows).__name__}")
@@ -780,23 +850,18 @@ def group_step(x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, hyper:
         _sized(keep, op, "keep", (H, B, D), torch.uint8)
     _sized(state, op, "state", (group_state_bytes(H, D, C, amsgrad),), torch.uint8)
     _sized(workspace, op, "workspace", (group_workspace_bytes(H, B, D, C),), torch.uint8)
-    held = []                                                   # copies `_dev` made live until the launch is enqueued
-    labels = _dev(labels, f"{op}.labels", torch.int32, (entry, "labels"))
-    rows = _dev(rows, f"{op}.rows", torch.int32, (entry, "rows"))
-    hyper = _dev(hyper, f"{op}.hyper", torch.float32, (entry, "hyper"))
-    keep = None if keep is None else _dev(keep, f"{op}.keep", torch.uint8, (entry, "keep"))
-    held += [x, labels, rows, hyper, keep]
-    w = _dev(w, f"{op}.w", torch.float32, (entry, "w"), owned=True)
-    b = _dev(b, f"{op}.b", torch.float32, (entry, "b"), owned=True)
-    state = _dev(state, f"{op}.state", torch.uint8, (entry, "state"), owned=True)
-    workspace = _dev(workspace, f"{op}.workspace", torch.uint8, (entry, "workspace"), owned=True)
-    _lib.check(_lib.load().frmap_head_fit_group_step(x.data_ptr(), labels.data_ptr(), rows.data_ptr(), keep.data_ptr() if keep is not None else 0,
-                                                     hyper.data_ptr(), w.data_ptr(), b.data_ptr(), state.data_ptr(), workspace.data_ptr(),
-                                                     N, H, B, D, C, _group_flags(decoupled, amsgrad, clear, evaluate), _stream()), op)
-    del held
+    labels, rows = _operand(labels, op, entry, "labels", torch.int32), _operand(rows, op, entry, "rows", torch.int32)
+    hyper = _operand(hyper, op, entry, "hyper", torch.float32)
+    keep = _operand(keep, op, entry, "keep", torch.uint8)
+    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _lib.check(_lib.load().frmap_head_fit_group_step(x.data_ptr(), labels.data_ptr(), rows.data_ptr(), _dev_at(keep), hyper.data_ptr(),
+                                                     w.data_ptr(), b.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, H, B, D, C,
+                                                     _group_flags(decoupled, amsgrad, clear, evaluate), _stream()), op)
 
 
-class HeadGroup:
+class HeadGroup(_Head):
     """``H`` linear softmax heads ``[C, D]`` over one cache, with their Adam states, workspaces and the device-resident hyper table
     (`group_step`).  The heads are initialised as ``H`` consecutive `LinearHead` objects would be from ``generator``; with ``shared_init``
     all of them start from head 0's draw (a parameter sweep compares settings, not initialisations)."""
@@ -806,27 +871,17 @@ class HeadGroup:
         self.H, self.D, self.C, self.amsgrad = int(H), int(D), int(C), bool(amsgrad)
         nbytes = group_state_bytes(self.H, self.D, self.C, self.amsgrad)          # (refuses a bad shape)
         self.stride = group_state_stride(self.D, self.C, self.amsgrad)
-        bound = 1.0 / math.sqrt(self.D)
-        ws, bs = [], []
+        drawn = []
         for h in range(self.H):
-            if h == 0 or not shared_init:
-                w = (torch.rand((self.C, self.D), generator=generator, dtype=torch.float32) * 2 - 1) * bound
-                b = (torch.rand((self.C,), generator=generator, dtype=torch.float32) * 2 - 1) * bound
-            ws.append(w)
-            bs.append(b)
-        self.device = torch.device(device)
-        self.weight, self.bias = torch.stack(ws).to(self.device), torch.stack(bs).to(self.device)
-        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
-        self.hyper = torch.zeros((self.H, 8), dtype=torch.float32, device=self.device)
+            drawn.append(_linear_init(self.C, self.D, generator) if h == 0 or not shared_init else drawn[0])
+        device = torch.device(device)
+        self.weight, self.bias = torch.stack([w for w, _ in drawn]).to(device), torch.stack([b for _, b in drawn]).to(device)
+        self.hyper = torch.zeros((self.H, 8), dtype=torch.float32, device=device)
         self._hyper_host = np.zeros((self.H, 8), np.float32)
-        self._workspaces = {}
-        self._clear = True
+        self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
 
-    def _workspace(self, B: int) -> torch.Tensor:
-        ws = self._workspaces.get(B)
-        if ws is None:
-            ws = self._workspaces[B] = torch.empty((group_workspace_bytes(self.H, B, self.D, self.C),), dtype=torch.uint8, device=self.device)
-        return ws
+    def _workspace_bytes(self, B: int) -> int:
+        return group_workspace_bytes(self.H, B, self.D, self.C)
 
     def set_hyper(self, table: np.ndarray) -> "HeadGroup":
         """Write the hyper table (`hyper_table`) with one host-to-device copy, and only when a value changed."""
@@ -838,11 +893,6 @@ class HeadGroup:
             self._hyper_host = table.copy()
         return self
 
-    def new_epoch(self) -> "HeadGroup":
-        """The next `step` or `evaluate` clears every head's epoch figures first."""
-        self._clear = True
-        return self
-
     def step(self, x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, keep: Optional[torch.Tensor] = None, *, lr,
              weight_decay=0.0, dropout=0.0, label_smoothing=0.0, beta1=0.9, beta2=0.999, eps=1e-8, decoupled: bool = False) -> "HeadGroup":
         """One step of every head over its rows ``rows[h]`` of the cache (`group_step`).  Every hyper-parameter is a scalar or a
@@ -852,42 +902,28 @@ class HeadGroup:
         self.set_hyper(hyper_table(self.H, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
                                    label_smoothing=label_smoothing, keep_scale=keep_scale))
         B = int(rows.shape[1]) if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 1
-        group_step(x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), keep, decoupled=decoupled,
-                   amsgrad=self.amsgrad, clear=self._clear)
-        self._clear = False
-        return self
+        return self._run(group_step, x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), keep,
+                         decoupled=decoupled)
 
     def evaluate(self, x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor) -> "HeadGroup":
         """Add the figures of rows ``rows[h]`` under every head's current weights (flag 8): nothing else changes.  The loss is the
         training loss of the table's ``label_smoothing``."""
         B = int(rows.shape[1]) if isinstance(rows, torch.Tensor) and rows.dim() == 2 else 1
-        group_step(x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), None, amsgrad=self.amsgrad,
-                   clear=self._clear, evaluate=True)
-        self._clear = False
-        return self
+        return self._run(group_step, x, labels, rows, self.hyper, self.weight, self.bias, self.state, self._workspace(B), None, evaluate=True)
 
     def epoch_figures(self) -> list:
         """ONE host copy of the ``H`` headers: per head what `LinearHead.epoch_figures` returns."""
         words = self.state.view(self.H, self.stride)[:, :64].cpu().numpy().view(np.uint64)
-        out = []
-        for h in range(self.H):
-            fig = figures_of({name: words[h, k] for k, name in enumerate(HEADER)})
-            fig["t"] = int(words[h, 0])
-            out.append(fig)
-        return out
+        return [_figures(words[h]) for h in range(self.H)]
 
     def head(self, h: int) -> LinearHead:
         """Head ``h`` as a `LinearHead` whose ``weight``, ``bias`` and ``state`` are VIEWS of the group's memory: `logits`,
         `state_dict`, `load_into` and `as_classifier` read the group's weights, and a single `step` on it continues head ``h``'s fit."""
         if not 0 <= int(h) < self.H:
             raise IndexError(f"HeadGroup.head: {h} is outside 0 ... {self.H - 1}")
-        h = int(h)
-        one = LinearHead.__new__(LinearHead)
-        one.D, one.C, one.amsgrad, one.device = self.D, self.C, self.amsgrad, self.device
-        one.weight, one.bias = self.weight[h], self.bias[h]
-        one.state = self.state[h * self.stride: h * self.stride + state_bytes(self.D, self.C, self.amsgrad)]
-        one._workspaces, one._clear = {}, False
-        return one
+        at = int(h) * self.stride
+        return LinearHead._over(self.weight[int(h)], self.bias[int(h)], self.state[at: at + state_bytes(self.D, self.C, self.amsgrad)],
+                                self.amsgrad, self.device)
 
 
 def kfold_rows(N: int, n_folds: int = 5, seed: int = 42) -> list:
@@ -909,16 +945,6 @@ def kfold_rows(N: int, n_folds: int = 5, seed: int = 42) -> list:
         out.append((np.flatnonzero(~mask).astype(np.int32), np.flatnonzero(mask).astype(np.int32)))
         at += int(size)
     return out
-
-
-def _generators(generator, device):
-    """(the CPU generator the heads are drawn from, the device generator of permutations and masks) of `fit_head`'s convention."""
-    head_gen = generator if generator is not None and generator.device.type == "cpu" else None
-    dev_gen = generator if generator is not None and generator.device.type != "cpu" else None
-    if generator is not None and dev_gen is None:
-        dev_gen = torch.Generator(device=device)
-        dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=generator).item()))
-    return head_gen, dev_gen
 
 
 def padded_rows(index_sets, batch_size: int, device) -> torch.Tensor:
@@ -1060,18 +1086,12 @@ def sweep_heads(feats: torch.Tensor, labels: torch.Tensor, val_feats: torch.Tens
 # ---------------------------------------------------------------------------------------------------------------------------------
 def hidden_state_bytes(D: int, Hd: int, C: int, amsgrad: bool = False) -> int:
     """Bytes of the state of a hidden-layer head (`frmap_head_fit_hidden_state_bytes`): `state_bytes` of (D, Hd), then of (Hd, C)."""
-    n = int(_lib.load().frmap_head_fit_hidden_state_bytes(int(D), int(Hd), int(C), int(bool(amsgrad))))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported D = {D}, Hd = {Hd}, C = {C} (each in 1 ... {MAX_D})")
-    return n
+    return _size("frmap_head_fit_hidden_state_bytes", f"each in 1 ... {MAX_D}", "D Hd C", int(D), int(Hd), int(C), int(bool(amsgrad)))
 
 
 def hidden_workspace_bytes(B: int, D: int, Hd: int, C: int) -> int:
     """Bytes of the workspace of a hidden-layer step of ``B`` rows (`frmap_head_fit_hidden_workspace_bytes`)."""
-    n = int(_lib.load().frmap_head_fit_hidden_workspace_bytes(int(B), int(D), int(Hd), int(C)))
-    if n == 0:
-        raise ValueError(f"head_fit: unsupported B = {B}, D = {D}, Hd = {Hd}, C = {C} (B in 1 ... {MAX_B}, D, Hd, C in 1 ... {MAX_D})")
-    return n
+    return _size("frmap_head_fit_hidden_workspace_bytes", _B_IN + f"D, Hd, C in 1 ... {MAX_D}", "B D Hd C", int(B), int(D), int(Hd), int(C))
 
 
 def hidden_state_views(state: np.ndarray, D: int, Hd: int, C: int, amsgrad: bool = False) -> dict:
@@ -1089,30 +1109,6 @@ def hidden_workspace_views(workspace: np.ndarray, B: int, Hd: int, C: int) -> di
            "lab": raw[at: at + 4 * B].view(np.int32), "row_src1": raw[at + 4 * B: at + 8 * B].view(np.int32)}
     out.update(workspace_views(raw[at + 8 * B:], B, C))
     return out
-
-
-def _adam_rule(p, grad, st: dict, km: str, kv: str, kx: str, t: int, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, f32):
-    """The update of `step_rule` on one tensor; returns the new parameter, ``st`` is updated in place."""
-    if f32:
-        a = adam_scalars32(t, lr, beta1, beta2, eps, weight_decay)
-        p, st[km], st[kv], vm = adam32(a, grad, p, st[km], st[kv], st.get(kx), decoupled, amsgrad)
-        if amsgrad:
-            st[kx] = vm
-        return p
-    p = np.array(p, np.float64)
-    if decoupled:
-        p *= 1.0 - lr * weight_decay
-    elif weight_decay != 0:
-        grad = grad + weight_decay * p
-    st[km] = st[km] + (1.0 - beta1) * (grad - st[km])
-    st[kv] = st[kv] * beta2 + (1.0 - beta2) * grad * grad
-    vhat = st[kv]
-    if amsgrad:
-        st[kx] = np.maximum(st[kx], st[kv])
-        vhat = st[kx]
-    denom = np.sqrt(vhat) / math.sqrt(1.0 - beta2 ** t) + eps
-    p += -(lr / (1.0 - beta1 ** t)) * (st[km] / denom)
-    return p
 
 
 def hidden_step_rule(x, labels, w1, b1, w2, b2, state: Optional[dict] = None, rows=None, keep1=None, keep1_scale: float = 1.0, keep2=None,
@@ -1135,27 +1131,12 @@ def hidden_step_rule(x, labels, w1, b1, w2, b2, state: Optional[dict] = None, ro
     labels = np.asarray(labels).astype(np.int64)
     N, D = x.shape
     Hd, C = w1.shape[0], w2_old.shape[0]
-    if rows is None:
-        rows = np.arange(len(keep1) if keep1 is not None else (len(keep2) if keep2 is not None else (N if batch is None else int(batch))),
-                         dtype=np.int64)
-    else:
-        rows = np.asarray(rows).astype(np.int64)
-    B = len(rows)
     state = state or {"layer1": fresh_state(D, Hd, amsgrad, dtype), "layer2": fresh_state(Hd, C, amsgrad, dtype)}
-    st1 = {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in state["layer1"].items()}
-    row_src1 = np.full((B,), -1, np.int32)
-    for i, r in enumerate(rows):
-        if 0 <= r < N and 0 <= labels[r] < C and np.isfinite(x[r]).all():
-            row_src1[i] = r
-    ok1 = row_src1 >= 0
+    st1 = _copy_state(state["layer1"], dtype)
+    masks = [len(k) for k in (keep1, keep2) if k is not None]
+    row_src1, ok1, xp = _rule_batch(x, labels, C, rows, masks[0] if masks else (N if batch is None else int(batch)), keep1, keep1_scale, f32)
+    B = len(row_src1)
     lab = np.where(ok1, labels[np.clip(row_src1, 0, N - 1)], -1).astype(np.int32)
-    xp = np.zeros((B, D), x.dtype)
-    xp[ok1] = x[row_src1[ok1]]
-    if keep1 is not None:
-        kept = np.asarray(keep1).astype(bool)
-        scaled = (xp * F32(keep1_scale)).astype(F32) if f32 else xp * float(keep1_scale)
-        xp = np.where(kept, scaled, 0).astype(x.dtype)
-        xp[~ok1] = 0
     with np.errstate(all="ignore"):
         a = (dot32(xp[:, None, :], w1[None, :, :]) + b1[None, :]).astype(F32) if f32 else xp @ w1.T + b1[None, :]
         h = np.where(a > 0, a, np.where(np.isnan(a), a, 0)).astype(dtype)
@@ -1183,18 +1164,12 @@ def hidden_step_rule(x, labels, w1, b1, w2, b2, state: Optional[dict] = None, ro
     if n:
         kw = dict(t=st1["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
                   f32=f32)
-        w1 = _adam_rule(w1, dw1, st1, "m_w", "v_w", "vmax_w", **kw)
-        b1 = _adam_rule(b1, db1, st1, "m_b", "v_b", "vmax_b", **kw)
+        w1, b1 = _adam_rule(w1, dw1, st1, "w", **kw), _adam_rule(b1, db1, st1, "b", **kw)
     out = {"w1": w1, "b1": b1, "w2": r2["w"], "b2": r2["b"], "state": {"layer1": st1, "layer2": r2["state"]}, "h": h, "lab": lab,
            "row_src1": row_src1, "da": da, "dw1": dw1, "db1": db1, "dw2": r2["dw"], "db2": r2["db"]}
     for k in ("z", "g", "row_loss", "row_src", "n", "loss"):
         out[k] = r2[k]
     return out
-
-
-def _host_array(op, name, t, dt):
-    if not (isinstance(t, np.ndarray) and t.dtype == dt and t.flags.c_contiguous and t.flags.writeable):
-        raise ValueError(f"{op}: {name} must be a writable contiguous {np.dtype(dt).name} array")
 
 
 def hidden_step_host(x, labels, w1, b1, w2, b2, state: np.ndarray, workspace: Optional[np.ndarray] = None, rows=None, keep1=None,
@@ -1207,52 +1182,16 @@ def hidden_step_host(x, labels, w1, b1, w2, b2, state: np.ndarray, workspace: Op
     ``workspace`` (uint8, exactly `hidden_workspace_bytes` bytes, or ``None`` for a fresh one) receives h, da, lab, row_src1 and
     layer 2's z, g, row_loss and row_src - with ``given_g`` the z, g and row_loss in it are inputs.  Returns the workspace."""
     op = "head_fit.hidden_step_host"
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    labels = np.ascontiguousarray(labels, dtype=np.int32)
-    if x.ndim != 2 or labels.shape != (x.shape[0],):
-        raise ValueError(f"{op}: x [N, D] and labels [N] expected")
-    N, D = x.shape
-    for name, t, dt in (("w1", w1, np.float32), ("b1", b1, np.float32), ("w2", w2, np.float32), ("b2", b2, np.float32),
-                        ("state", state, np.uint8)):
-        _host_array(op, name, t, dt)
-    if w1.ndim != 2 or w1.shape[1] != D or b1.shape != (w1.shape[0],):
-        raise ValueError(f"{op}: w1 [Hd, {D}] and b1 [Hd] expected, got {w1.shape} and {b1.shape}")
-    Hd = w1.shape[0]
-    if w2.ndim != 2 or w2.shape[1] != Hd or b2.shape != (w2.shape[0],):
-        raise ValueError(f"{op}: w2 [C, {Hd}] and b2 [C] expected, got {w2.shape} and {b2.shape}")
-    C = w2.shape[0]
-    if rows is not None:
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        if rows.ndim != 1:
-            raise ValueError(f"{op}: rows [B] expected")
-    B = len(rows) if rows is not None else (len(keep1) if keep1 is not None else (len(keep2) if keep2 is not None else (
-        N if batch is None else int(batch))))
-    if keep1 is not None:
-        keep1 = np.ascontiguousarray(keep1, dtype=np.uint8)
-        if keep1.shape != (B, D):
-            raise ValueError(f"{op}: keep1 must be [{B}, {D}], got {keep1.shape}")
-    if keep2 is not None:
-        keep2 = np.ascontiguousarray(keep2, dtype=np.uint8)
-        if keep2.shape != (B, Hd):
-            raise ValueError(f"{op}: keep2 must be [{B}, {Hd}], got {keep2.shape}")
-    if rows is None and B > N:
-        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
-    nstate = hidden_state_bytes(D, Hd, C, amsgrad)
-    if state.shape != (nstate,) or state.ctypes.data % 8:
-        raise ValueError(f"{op}: state must be {nstate} bytes, 8-byte aligned")
-    nbytes = hidden_workspace_bytes(B, D, Hd, C)
-    if workspace is None:
-        if given_g:
-            raise ValueError(f"{op}: given_g needs the workspace that holds z, g and row_loss")
-        workspace = np.zeros((nbytes,), np.uint8)
-    if not (isinstance(workspace, np.ndarray) and workspace.dtype == np.uint8 and workspace.flags.c_contiguous and workspace.flags.writeable
-            and workspace.shape == (nbytes,) and workspace.ctypes.data % 4 == 0):
-        raise ValueError(f"{op}: workspace must be a writable uint8 array of exactly {nbytes} bytes")
+    x, labels, N, D = _host_cache(op, x, labels)
+    Hd, = _host_layer(op, "w1", "b1", w1, b1, "", "Hd", D)
+    C, = _host_layer(op, "w2", "b2", w2, b2, "", "C", Hd)
+    rows, B = _host_batch(op, N, rows, (keep1, keep2), batch)
+    keep1, keep2 = _host_mask(op, "keep1", keep1, (B, D)), _host_mask(op, "keep2", keep2, (B, Hd))
+    workspace = _host_buffers(op, state, hidden_state_bytes(D, Hd, C, amsgrad), workspace, hidden_workspace_bytes(B, D, Hd, C), given_g)
     _lib.check(_lib.load().frmap_head_fit_hidden_step_host(
-        x.ctypes.data, labels.ctypes.data, rows.ctypes.data if rows is not None else 0, keep1.ctypes.data if keep1 is not None else 0,
-        float(keep1_scale), keep2.ctypes.data if keep2 is not None else 0, float(keep2_scale), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
-        b2.ctypes.data, state.ctypes.data, workspace.ctypes.data, N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps),
-        float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
+        _at(x), _at(labels), _at(rows), _at(keep1), float(keep1_scale), _at(keep2), float(keep2_scale), _at(w1), _at(b1), _at(w2), _at(b2),
+        _at(state), _at(workspace), N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        float(label_smoothing), _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
     return workspace
 
 
@@ -1269,56 +1208,29 @@ def hidden_step(x: torch.Tensor, labels: torch.Tensor, w1: torch.Tensor, b1: tor
     ``batch``, else ``N``), ``keep1`` uint8 ``[B, D]`` and ``keep2`` uint8 ``[B, Hd]`` or ``None``.  Every extent that depends on another
     operand is checked here, before the library sees a pointer."""
     op, entry = "head_fit.hidden_step", "frmap_head_fit_hidden_step"
-    x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
-    N, D = int(x.shape[0]), int(x.shape[1])
-    _sized(labels, op, "labels", (N,), torch.int32)
-    _sized(w1, op, "w1", (w1.shape[0] if isinstance(w1, torch.Tensor) and w1.dim() == 2 else -1, D), torch.float32)
-    Hd = int(w1.shape[0])
-    _sized(b1, op, "b1", (Hd,), torch.float32)
-    _sized(w2, op, "w2", (w2.shape[0] if isinstance(w2, torch.Tensor) and w2.dim() == 2 else -1, Hd), torch.float32)
-    C = int(w2.shape[0])
-    _sized(b2, op, "b2", (C,), torch.float32)
-    if rows is not None:
-        if isinstance(rows, torch.Tensor) and rows.dim() != 1:
-            raise ValueError(f"{op}: rows [B] expected, got {tuple(rows.shape)}")
-        rows = _dev(rows, f"{op}.rows", torch.int32, (entry, "rows"))
-        B = int(rows.shape[0])
-    elif isinstance(keep1, torch.Tensor) and keep1.dim() == 2:
-        B = int(keep1.shape[0])
-    elif isinstance(keep2, torch.Tensor) and keep2.dim() == 2:
-        B = int(keep2.shape[0])
-    else:
-        B = N if batch is None else int(batch)
-    if rows is None and B > N:
-        raise ValueError(f"{op}: {B} batch rows without `rows` exceed the {N} cached rows")
+    x, N, D = _cache(op, entry, x, labels)
+    Hd = _layer(w1, b1, op, "w1", "b1", D)
+    C = _layer(w2, b2, op, "w2", "b2", Hd)
+    rows, B = _batch(op, entry, N, rows, (keep1, keep2), batch)
     if keep1 is not None:
         _sized(keep1, op, "keep1", (B, D), torch.uint8)
     if keep2 is not None:
         _sized(keep2, op, "keep2", (B, Hd), torch.uint8)
     _sized(state, op, "state", (hidden_state_bytes(D, Hd, C, amsgrad),), torch.uint8)
     _sized(workspace, op, "workspace", (hidden_workspace_bytes(B, D, Hd, C),), torch.uint8)
-    held = []                                                   # copies `_dev` made live until the launch is enqueued
-    labels = _dev(labels, f"{op}.labels", torch.int32, (entry, "labels"))
-    keep1 = None if keep1 is None else _dev(keep1, f"{op}.keep1", torch.uint8, (entry, "keep1"))
-    keep2 = None if keep2 is None else _dev(keep2, f"{op}.keep2", torch.uint8, (entry, "keep2"))
-    held += [x, labels, rows, keep1, keep2]
-    w1 = _dev(w1, f"{op}.w1", torch.float32, (entry, "w1"), owned=True)
-    b1 = _dev(b1, f"{op}.b1", torch.float32, (entry, "b1"), owned=True)
-    w2 = _dev(w2, f"{op}.w2", torch.float32, (entry, "w2"), owned=True)
-    b2 = _dev(b2, f"{op}.b2", torch.float32, (entry, "b2"), owned=True)
-    state = _dev(state, f"{op}.state", torch.uint8, (entry, "state"), owned=True)
-    workspace = _dev(workspace, f"{op}.workspace", torch.uint8, (entry, "workspace"), owned=True)
+    labels = _operand(labels, op, entry, "labels", torch.int32)
+    keep1, keep2 = _operand(keep1, op, entry, "keep1", torch.uint8), _operand(keep2, op, entry, "keep2", torch.uint8)
+    w1, b1 = _operand(w1, op, entry, "w1", torch.float32, True), _operand(b1, op, entry, "b1", torch.float32, True)
+    w2, b2 = _operand(w2, op, entry, "w2", torch.float32, True), _operand(b2, op, entry, "b2", torch.float32, True)
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
     _lib.check(_lib.load().frmap_head_fit_hidden_step(
-        x.data_ptr(), labels.data_ptr(), rows.data_ptr() if rows is not None else 0, keep1.data_ptr() if keep1 is not None else 0,
-        float(keep1_scale), keep2.data_ptr() if keep2 is not None else 0, float(keep2_scale), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-        b2.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps),
-        float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), _stream()), op)
-    del held
+        x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep1), float(keep1_scale), _dev_at(keep2), float(keep2_scale), w1.data_ptr(),
+        b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, Hd, C, float(lr), float(beta1),
+        float(beta2), float(eps), float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), _stream()), op)
 
 
-class HiddenHead:
+class HiddenHead(_Head):
     """``Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C)`` on the device with its Adam state and a workspace: the ``fc1`` / ``fc2`` of
     the reference's ``BaselineNet`` over its pooled features, or a learned ``D -> Hd`` projection of any cached feature.  Both layers
     are initialised as consecutive ``nn.Linear(D, Hd)`` and ``nn.Linear(Hd, C)`` would be from ``generator`` (a CPU
@@ -1328,28 +1240,14 @@ class HiddenHead:
     def __init__(self, D: int, Hd: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
         self.D, self.Hd, self.C, self.amsgrad = int(D), int(Hd), int(C), bool(amsgrad)
         nbytes = hidden_state_bytes(self.D, self.Hd, self.C, self.amsgrad)          # (refuses a bad shape)
-        self.device = torch.device(device)
-        params = []
-        for fan_out, fan_in in ((self.Hd, self.D), (self.C, self.Hd)):
-            bound = 1.0 / math.sqrt(fan_in)
-            params.append(((torch.rand((fan_out, fan_in), generator=generator, dtype=torch.float32) * 2 - 1) * bound).to(self.device))
-            params.append(((torch.rand((fan_out,), generator=generator, dtype=torch.float32) * 2 - 1) * bound).to(self.device))
-        self.w1, self.b1, self.w2, self.b2 = params
-        self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
-        self._state2_at = state_bytes(self.D, self.Hd, self.amsgrad)
-        self._workspaces = {}
-        self._clear = True
+        device = torch.device(device)
+        layers = [_linear_init(self.Hd, self.D, generator), _linear_init(self.C, self.Hd, generator)]
+        self.w1, self.b1, self.w2, self.b2 = (t.to(device) for layer in layers for t in layer)
+        self._header_at = state_bytes(self.D, self.Hd, self.amsgrad)              # the figures are layer 2's: the second part of the state
+        self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
 
-    def _workspace(self, B: int) -> torch.Tensor:
-        ws = self._workspaces.get(B)
-        if ws is None:
-            ws = self._workspaces[B] = torch.empty((hidden_workspace_bytes(B, self.D, self.Hd, self.C),), dtype=torch.uint8, device=self.device)
-        return ws
-
-    def new_epoch(self) -> "HiddenHead":
-        """The next `step` clears the epoch figures first."""
-        self._clear = True
-        return self
+    def _workspace_bytes(self, B: int) -> int:
+        return hidden_workspace_bytes(B, self.D, self.Hd, self.C)
 
     def step(self, x: torch.Tensor, labels: torch.Tensor, rows: Optional[torch.Tensor] = None, keep1: Optional[torch.Tensor] = None,
              keep2: Optional[torch.Tensor] = None, *, lr: float, dropout1: float = 0.0, dropout2: float = 0.0,
@@ -1367,18 +1265,9 @@ class HiddenHead:
             if isinstance(t, torch.Tensor) and t.dim() == dim:
                 B = int(t.shape[0])
                 break
-        hidden_step(x, labels, self.w1, self.b1, self.w2, self.b2, self.state, self._workspace(B), rows, keep1, keep1_scale, keep2,
-                    keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing,
-                    decoupled=decoupled, amsgrad=self.amsgrad, clear=self._clear)
-        self._clear = False
-        return self
-
-    def epoch_figures(self) -> dict:
-        """The one host copy (layer 2's header): rows, correct, accuracy and mean loss since the last `new_epoch`, and ``t``."""
-        words = self.state[self._state2_at: self._state2_at + 64].cpu().numpy().view(np.uint64)
-        out = figures_of({name: words[k] for k, name in enumerate(HEADER)})
-        out["t"] = int(words[0])
-        return out
+        return self._run(hidden_step, x, labels, self.w1, self.b1, self.w2, self.b2, self.state, self._workspace(B), rows, keep1, keep1_scale,
+                         keep2, keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                         label_smoothing=label_smoothing, decoupled=decoupled)
 
     def embed(self, x: torch.Tensor) -> torch.Tensor:
         """``relu(x w1^T + b1)``: the embedding the fitted first layer produces from cached-feature rows ``x`` ``[B, D]``."""
@@ -1394,12 +1283,8 @@ class HiddenHead:
     def classifier(self) -> LinearHead:
         """Layer 2 as a `LinearHead` whose ``weight``, ``bias`` and ``state`` are VIEWS of this head's memory (the second part of the
         state is a valid single-step state): its `logits` and `as_classifier` take `embed` outputs."""
-        one = LinearHead.__new__(LinearHead)
-        one.D, one.C, one.amsgrad, one.device = self.Hd, self.C, self.amsgrad, self.device
-        one.weight, one.bias = self.w2, self.b2
-        one.state = self.state[self._state2_at: self._state2_at + state_bytes(self.Hd, self.C, self.amsgrad)]
-        one._workspaces, one._clear = {}, False
-        return one
+        at = self._header_at
+        return LinearHead._over(self.w2, self.b2, self.state[at: at + state_bytes(self.Hd, self.C, self.amsgrad)], self.amsgrad, self.device)
 
     def load_into(self, model) -> None:
         """Copy both layers into ``fc1`` / ``fc2`` of a ``BaselineNet`` of matching shapes, in place (the model's plan watches the

@@ -289,3 +289,60 @@ def test_fit_head_end_to_end(tmp_path, calibrated_sd):
     assert own["rows"] == m["rows"] == 32 and m["accuracy"] == own["accuracy"] and hist2["train_acc"][-1] >= 0.9
     with pytest.raises(ValueError, match="siamese"):
         hf.fit_head(None, "siamese", root)
+
+
+class _FlatTrunk:
+    """A trunk by duck typing (not a ``BaselineNet``): the embedding of an image is the image, flattened."""
+    training = False
+
+    def eval(self):
+        return self
+
+    def get_embedding(self, im):
+        return im.reshape(im.shape[0], -1)
+
+
+@pytest.mark.parametrize("hidden", [None, 5], ids=["linear", "hidden"])
+def test_fit_head_draws_in_the_documented_order(hidden):
+    """`fit_head` against the same fit replayed by hand, N = 20, D = 8, C = 3, batches of 8 (the last one has 4 rows), 2 epochs: the head
+    from the CPU generator, then the device generator's seed from it; per epoch one `randperm`; per batch the input mask's `rand`,
+    then (hidden) the hidden mask's; `head.step`.  Every weight, bias, the whole state and the history are equal."""
+    rng = np.random.default_rng(9)
+    data = [(torch.from_numpy(rng.standard_normal((n, 2, 2, 2)).astype(F32)), torch.from_numpy(rng.integers(0, 3, n))) for n in (12, 8)]
+    data[0][1][:3] = torch.tensor([0, 1, 2])
+    trunk, kw = _FlatTrunk(), dict(lr=1e-2, weight_decay=1e-4, label_smoothing=0.05, decoupled=True)
+    epochs, batch, dropout, hidden_dropout = 2, 8, 0.25, 0.5
+    got, hist = hf.fit_head(trunk, "cnn", data, epochs=epochs, batch_size=batch, dropout=dropout, amsgrad=True, device=DEV, hidden=hidden,
+                            hidden_dropout=hidden_dropout, generator=torch.Generator().manual_seed(21), **kw)
+    feats, labels = hf.cache_features(trunk, "cnn", data, device=DEV)
+    N, D = feats.shape
+    assert (N, D, int(labels.max()) + 1) == (20, 8, 3)
+    gen = torch.Generator().manual_seed(21)
+    if hidden is None:
+        head = hf.LinearHead(D, 3, DEV, amsgrad=True, generator=gen)
+    else:
+        head = hf.HiddenHead(D, hidden, 3, DEV, amsgrad=True, generator=gen)
+    dev_gen = torch.Generator(device=DEV)
+    dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=gen).item()))
+    want = {"train_loss": [], "train_acc": [], "val": []}
+    sizes = []
+    for _ in range(epochs):
+        perm = torch.randperm(N, device=DEV, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, batch):
+            rows = perm[lo: lo + batch]
+            sizes.append(int(rows.shape[0]))
+            keep = (torch.rand((rows.shape[0], D), device=DEV, generator=dev_gen) >= dropout).to(torch.uint8)
+            if hidden is None:
+                head.step(feats, labels, rows, keep, dropout=dropout, **kw)
+            else:
+                keep2 = (torch.rand((rows.shape[0], hidden), device=DEV, generator=dev_gen) >= hidden_dropout).to(torch.uint8)
+                head.step(feats, labels, rows, keep, keep2, dropout1=dropout, dropout2=hidden_dropout, **kw)
+        fig = head.epoch_figures()
+        want["train_loss"].append(fig["loss"])
+        want["train_acc"].append(fig["accuracy"])
+    assert sizes == [8, 8, 4] * epochs
+    assert type(got) is type(head)
+    for name in ("weight", "bias", "state") if hidden is None else ("w1", "b1", "w2", "b2", "state"):
+        assert torch.equal(getattr(got, name), getattr(head, name)), name
+    assert hist == want and len(hist["train_loss"]) == epochs and got.epoch_figures()["t"] == 3 * epochs

@@ -378,7 +378,7 @@ SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-stat
 @pytest.mark.skipif(torch.cuda.is_available(), reason="a sanitizer build is host-only work: nothing of it runs on a machine with a GPU")
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++ to build the stand-alone sanitizer program with")
 def test_group_twin_is_sanitizer_clean_as_a_stand_alone_program(tmp_path):
-    """tools/head_fit_group_check.cpp (its own `main`, head_fit_twin.h and the two rule headers, nothing else) built with
+    """tools/head_fit_group_check.cpp (its own `main`, head_fit_twin.h, the two rule headers and tools/head_fit_check_common.h, nothing else) built with
     -fsanitize=address,undefined (runtimes linked statically) and run directly as a child process: it sweeps the table of
     `fit_group_cases` with every buffer a heap block of exactly its size, and exits 0."""
     probe = tmp_path / "probe.cpp"

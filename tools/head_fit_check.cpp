@@ -1,5 +1,5 @@
-// The head-fitting step's host twin (csrc/head_fit_twin.h + head_fit_rule.h + tally_rule.h, nothing else) as a stand-alone
-// program, for a build with the address and undefined-behaviour sanitizers:
+// The head-fitting step's host twin (csrc/head_fit_twin.h + head_fit_rule.h + tally_rule.h and the check programs' own
+// head_fit_check_common.h, nothing else) as a stand-alone program, for a build with the address and undefined-behaviour sanitizers:
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I<csrc> tools/head_fit_check.cpp -o check && ./check
 // It sweeps B x D x C (the grid of tests/fit_cases.py) for three steps each, the optional operands and the optimiser flags taken
 // from the case's index, over batches that hold one row of each declined kind.  Every buffer is a heap block of exactly its size -
@@ -8,41 +8,8 @@
 // the same bytes; a step through `rows` must equal the step on the gathered copy; a step re-run with given_g on its own workspace
 // must give the same weights and state; a batch of declined rows only must leave weights, moments and t untouched; refused calls
 // must write nothing.  Exit status 0 and "self check passed" on success.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
-#include "head_fit_twin.h"
-
-#define CHECK(cond, ...)                          \
-  do {                                            \
-    if (!(cond)) {                                \
-      fprintf(stderr, "FAILED %s: ", #cond);      \
-      fprintf(stderr, __VA_ARGS__);               \
-      fprintf(stderr, "\n");                      \
-      exit(1);                                    \
-    }                                             \
-  } while (0)
-
-static uint32_t g_seed = 12345u;
-static uint32_t rnd() {
-  g_seed = g_seed * 1664525u + 1013904223u;
-  return g_seed >> 8;
-}
-static float small() { return (float)((int)(rnd() % 129) - 64) / 64.0f; }
-
-template <class T>
-struct Block {          // exactly n elements on the heap
-  T* p;
-  size_t n;
-  explicit Block(size_t n_) : p((T*)calloc(n_ ? n_ : 1, sizeof(T))), n(n_) { CHECK(p, "calloc"); }
-  Block(const Block& o) : p((T*)malloc((o.n ? o.n : 1) * sizeof(T))), n(o.n) { memcpy(p, o.p, o.n * sizeof(T)); }
-  Block& operator=(const Block&) = delete;
-  ~Block() { free(p); }
-  bool same(const Block& o) const { return n == o.n && memcmp(p, o.p, n * sizeof(T)) == 0; }
-};
+#define CHECK_SEED 12345u
+#include "head_fit_check_common.h"
 
 struct Problem {
   int N, B, D, C;

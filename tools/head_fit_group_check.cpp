@@ -1,5 +1,5 @@
-// The grouped head-fitting step's host twin (csrc/head_fit_twin.h + head_fit_rule.h + tally_rule.h, nothing else) as a stand-alone
-// program, for a build with the address and undefined-behaviour sanitizers:
+// The grouped head-fitting step's host twin (csrc/head_fit_twin.h + head_fit_rule.h + tally_rule.h and the check programs' own
+// head_fit_check_common.h, nothing else) as a stand-alone program, for a build with the address and undefined-behaviour sanitizers:
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -I<csrc> tools/head_fit_group_check.cpp -o check && ./check
 // It sweeps heads x shapes (the table of tests/fit_group_cases.py) for three steps each, masks / decoupled decay / AMSGrad taken
 // from the case's index, per-head hyper-parameters all different, head h's rows ending in min(h, B - 1) entries of -1.  Every
@@ -12,42 +12,8 @@
 //     first; two calls accumulate;
 //   * refused calls write nothing.
 // Exit status 0 and "self check passed" on success.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "head_fit_twin.h"
-
-#define CHECK(cond, ...)                          \
-  do {                                            \
-    if (!(cond)) {                                \
-      fprintf(stderr, "FAILED %s: ", #cond);      \
-      fprintf(stderr, __VA_ARGS__);               \
-      fprintf(stderr, "\n");                      \
-      exit(1);                                    \
-    }                                             \
-  } while (0)
-
-static uint32_t g_seed = 2468u;
-static uint32_t rnd() {
-  g_seed = g_seed * 1664525u + 1013904223u;
-  return g_seed >> 8;
-}
-static float small() { return (float)((int)(rnd() % 129) - 64) / 64.0f; }
-
-template <class T>
-struct Block {          // exactly n elements on the heap
-  T* p;
-  size_t n;
-  explicit Block(size_t n_, int fill = 0) : p((T*)malloc((n_ ? n_ : 1) * sizeof(T))), n(n_) {
-    CHECK(p, "malloc");
-    memset(p, fill, (n_ ? n_ : 1) * sizeof(T));
-  }
-  Block(const Block& o) : p((T*)malloc((o.n ? o.n : 1) * sizeof(T))), n(o.n) { memcpy(p, o.p, o.n * sizeof(T)); }
-  Block& operator=(const Block&) = delete;
-  ~Block() { free(p); }
-  bool same(const Block& o) const { return n == o.n && memcmp(p, o.p, n * sizeof(T)) == 0; }
-};
+#define CHECK_SEED 2468u
+#include "head_fit_check_common.h"
 
 struct Problem {
   int N, H, B, D, C;
