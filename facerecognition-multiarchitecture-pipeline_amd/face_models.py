@@ -17,6 +17,7 @@ no eager / CPU fallback.  Training (`face_models.py:527-572`, losses `:725-782`)
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, List, Optional, Tuple
@@ -57,6 +58,21 @@ _HEAD_FUSE = os.environ.get("FRMAP_HEAD_FUSE", "1") != "0"   # A/B switch: 0 = A
 _POOL_FUSE = os.environ.get("FRMAP_POOL_FUSE", "1") != "0"   # A/B switch: 0 = conv and 2x2 max-pool as two launches
 
 
+@contextlib.contextmanager
+def planned_in_python(on: bool = True):
+    """Plans BUILT inside are per-op (`on`) or on the model handle, as under FRMAP_PY_PLAN=1 / 0; a plan that exists keeps its route."""
+    global _PY_PLAN
+    old, _PY_PLAN = _PY_PLAN, bool(on)
+    try:
+        yield
+    finally:
+        _PY_PLAN = old
+
+
+# Every per-op forward below takes an optional recorder `rec`.  After each step it is called as `rec(name, stored, by, inputs)`: the step's
+# name, the tensor the step stored, the packed object (or, where there is none, the `ops` function) that computed it, and that
+# one's input tensors - what tests/test_model_twin_gpu.py needs to hold every step to its float64 twin.  Without one a step costs
+# the `is None` test.
 class _PackedConv:
     __slots__ = ("wpk", "shift", "cout", "k", "stride", "pad", "small")
 
@@ -78,16 +94,23 @@ class _PackedConv:
             return ops.conv_small_cin(x, self.wpk, self.shift, self.cout, self.k, self.stride, self.pad, relu)
         return ops.conv_igemm(x, self.wpk, self.shift, self.cout, self.k, self.stride, self.pad, relu, residual)
 
-    def pooled(self, x: torch.Tensor, relu: bool = True) -> torch.Tensor:
+    def pooled(self, x: torch.Tensor, relu: bool = True, rec=None, name: str = "") -> torch.Tensor:
         """conv + shift (+ReLU) + MaxPool2d(2, 2) (`face_models.py:38-40,121-141`): one launch when the kernels take the
-        shape (the conv map never reaches HBM), conv + pool kernels otherwise."""
+        shape (the conv map never reaches HBM; step `name+pool2`), conv + pool kernels otherwise (steps `name`, `name.pool2`)."""
         B, H, W, C = x.shape
         fusable = self.k == 3 and self.stride == 1 and self.pad == 1 and H % 2 == 0 and W % 2 == 0 and _POOL_FUSE
-        if fusable and self.small and self.cout == 32:
-            return ops.conv_small_cin_pool2(x, self.wpk, self.shift, self.cout, relu)
-        if fusable and not self.small and ops.conv_pool2_supported(B, H, W, C, self.cout):
-            return ops.conv_igemm_pool2(x, self.wpk, self.shift, self.cout, relu)
-        return ops.maxpool(self(x, relu), 2, 2, 0)
+        if fusable and (self.cout == 32 if self.small else ops.conv_pool2_supported(B, H, W, C, self.cout)):
+            fused = ops.conv_small_cin_pool2 if self.small else ops.conv_igemm_pool2
+            y = fused(x, self.wpk, self.shift, self.cout, relu)
+            if rec is not None:
+                rec(name + "+pool2", y, self, (x,))
+            return y
+        c = self(x, relu)
+        y = ops.maxpool(c, 2, 2, 0)
+        if rec is not None:
+            rec(name, c, self, (x,))
+            rec(name + ".pool2", y, ops.maxpool, (c,))
+        return y
 
 
 class _PackedLinearAsConv:
@@ -114,12 +137,13 @@ class _PackedLinearAsConv:
 # --------------------------------------------------------------------------------------------
 class _HipModule(nn.Module):
     """nn.Module whose inference runs on the HIP kernels.  The packed-weight "plan" is rebuilt
-    whenever a parameter/buffer is replaced, moved or modified in place (tensor version counters)."""
+    whenever a parameter/buffer is replaced, moved or modified in place (tensor version counters).  A plan is the family's
+    own model handle (`_TrunkPlan`) where the A/B switches allow it and the family's per-op plan otherwise (`_build_plan`); the
+    public methods ask it for `embedding` / `logits` / `features` / `pooled` / `unit_embedding` and either kind answers."""
 
     def __init__(self):
         super().__init__()
-        self._plan = None
-        self._plan_sig = None
+        self._plans = {}          # per_op -> (plan, the signature it was built from)
         self.compute_dtype = _DEFAULT_DTYPE
         # uint8 HWC inputs (B×H×W×3 RGB, what `transforms.Resize` leaves, `src/testing.py:99-100`) are normalised on the
         # device: ToTensor + Normalize(mean, std) of `src/testing.py:101-104` (ImageNet statistics by default)
@@ -134,7 +158,7 @@ class _HipModule(nn.Module):
     def set_compute_dtype(self, dtype: torch.dtype):
         ops.dt_code(dtype)
         self.compute_dtype = dtype
-        self._plan = None
+        self._plans.clear()
         return self
 
     def _signature(self):
@@ -143,20 +167,31 @@ class _HipModule(nn.Module):
             sig.append((t.data_ptr(), t._version))
         return tuple(sig)
 
-    def _get_plan(self):
+    def _get_plan(self, per_op: bool = False):
+        """The plan the switches choose, or with `per_op` the family's per-op plan whatever they say (the other one is not touched)."""
         sig = self._signature()
-        if self._plan is None or sig != self._plan_sig:
+        cached = self._plans.get(per_op)
+        if cached is None or sig != cached[1]:
             dev = next(self.parameters()).device
             if dev.type != "cuda":
                 raise RuntimeError(f"{type(self).__name__} is on {dev}; move it to the GPU (.to('cuda')) — "
                                    "the HIP path has no CPU fallback")
             with torch.no_grad():
-                self._plan = self._build_plan(self.compute_dtype)
-            self._plan_sig = self._signature()
-        return self._plan
+                plan = self._build_plan(self.compute_dtype, per_op)
+            self._plans[per_op] = cached = (plan, self._signature())
+        return cached[0]
 
-    def _build_plan(self, dtype):  # pragma: no cover - abstract
+    def _build_plan(self, dtype, per_op=False):  # pragma: no cover - abstract
         raise NotImplementedError
+
+    def model_handle(self):
+        """The `frmap_model` of this family behind the module, on which `matching.embed_and_match` runs in one call; None when
+        the plan is per-op (FRMAP_PY_PLAN=1, a fusing switch off, AttentionNet) - a bare-trunk handle inside such a plan is not it."""
+        return self._get_plan().handle
+
+    def get_embedding(self, x):
+        x = self._check_input(x)
+        return self._get_plan().embedding(x)
 
     def _check_input(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 NCHW B×3×H×W (the reference's tensor) or uint8 HWC B×H×W×3 (the image bytes; normalised on the device)."""
@@ -173,11 +208,19 @@ class _HipModule(nn.Module):
             return x
         return x.float() if x.dtype != torch.float32 else x
 
-    def _as_nhwc4(self, x: torch.Tensor) -> torch.Tensor:
-        """First-layer operand of the unfused paths: NHWC4 in the compute dtype from either input kind."""
-        if x.dtype == torch.uint8:
-            return ops.normalize_u8(x, self.input_mean, self.input_std, want_nchw=False, nhwc4_dtype=self.compute_dtype)[1]
-        return ops.pack_input(x, self.compute_dtype)
+    def _as_nhwc4(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        return _nhwc4(x, self.compute_dtype, self.input_mean, self.input_std, rec)
+
+
+def _nhwc4(x: torch.Tensor, dtype: torch.dtype, mean, std, rec=None) -> torch.Tensor:
+    """First-layer operand of the unfused paths (step `pack_input`): NHWC4 in the compute dtype from either input kind."""
+    if x.dtype == torch.uint8:
+        x4 = ops.normalize_u8(x, mean, std, want_nchw=False, nhwc4_dtype=dtype)[1]
+    else:
+        x4 = ops.pack_input(x, dtype)
+    if rec is not None:
+        rec("pack_input", x4, ops.normalize_u8 if x.dtype == torch.uint8 else ops.pack_input, (x,))
+    return x4
 
 
 # --------------------------------------------------------------------------------------------
@@ -238,7 +281,7 @@ def _check_handle_eps(owner: nn.Module) -> None:
 
 
 class _TrunkPlan:
-    """ResNet-18 trunk (and, for 'cnn' / 'arcface', the heads) on a MODEL HANDLE of the C ABI (`frmap_model_*`,
+    """A family, or the bare ResNet-18 trunk ('resnet18_trunk'), on a MODEL HANDLE of the C ABI (`frmap_model_*`,
     csrc/model_api.cpp): BatchNorm folding, weight packing and the per-layer kernel plan live in the library; this class only
     hands over the tensors under the reference's ``state_dict`` key names and asks for outputs."""
 
@@ -249,12 +292,26 @@ class _TrunkPlan:
         self.dtype = dtype
         self.handle = ops.ModelHandle(model_type, state, num_classes, dtype, mean, std)
 
-    def features(self, x: torch.Tensor) -> torch.Tensor:
-        """fp32 NCHW (or uint8 HWC) → NHWC B×7×7×512 (for 224² input) in the compute dtype."""
-        return self.handle.forward(x, ops.OUT_TRUNK_MAP)
+    def _out(self, x: torch.Tensor, what: int, rec=None) -> torch.Tensor:
+        if rec is not None:
+            raise ValueError("a model handle stores no per-step tensors to record: build the plan under planned_in_python()")
+        return self.handle.forward(x, what)
 
-    def pooled(self, x: torch.Tensor) -> torch.Tensor:
-        return self.handle.forward(x, ops.OUT_POOLED)  # fp32 B×512
+    def features(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        """fp32 NCHW (or uint8 HWC) → NHWC B×7×7×512 (for 224² input) in the compute dtype."""
+        return self._out(x, ops.OUT_TRUNK_MAP, rec)
+
+    def pooled(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        return self._out(x, ops.OUT_POOLED, rec)  # fp32 B×512
+
+    def embedding(self, x: torch.Tensor) -> torch.Tensor:
+        return self.handle.forward(x, ops.OUT_EMBEDDING)
+
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        return self.handle.forward(x, ops.OUT_LOGITS)
+
+    def unit_embedding(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.l2_normalize(self.embedding(x), 1e-12)
 
 
 def _trunk_plan(rn: "ResNet18", dtype: torch.dtype, mean, std, owner: Optional[nn.Module] = None):
@@ -268,9 +325,12 @@ class _PyTrunkPlan:
     """The same trunk planned in Python, one C-ABI op per call (`FRMAP_PY_PLAN=1`): the A/B twin of the model handle - same
     launches on the same folded weights, bit-identical outputs (tests/test_model_cabi_gpu.py) - and the path per-op tools wrap."""
 
-    def __init__(self, rn: ResNet18, dtype: torch.dtype, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    handle = None     # (no model handle: `_HipModule.model_handle`)
+
+    def __init__(self, rn: ResNet18, dtype: torch.dtype, mean=IMAGENET_MEAN, std=IMAGENET_STD, fc: Optional[nn.Linear] = None):
         self.dtype = dtype
         self.mean, self.std = mean, std
+        self.fc = fc      # 'cnn': the classifier over the pooled map
         self.stem = _PackedConv(rn.conv1, rn.bn1, dtype)
         self.blocks = []
         for li in range(1, 5):
@@ -281,40 +341,109 @@ class _PyTrunkPlan:
                 fshift = (c2.shift + ds.shift).contiguous() if ds is not None else None
                 self.blocks.append((_PackedConv(blk.conv1, blk.bn1, dtype), c2, ds, fshift))
 
-    def features(self, x: torch.Tensor) -> torch.Tensor:
+    def features(self, x: torch.Tensor, rec=None) -> torch.Tensor:
         """fp32 NCHW (or uint8 HWC) → NHWC B×7×7×512 (for 224² input) in the compute dtype."""
-        if x.dtype == torch.uint8:
-            H, W = x.shape[1], x.shape[2]
-            if ops.stem_pool_dims(H, W)[1] <= 56 and W % 4 == 0:
-                # the fused stem reads the image bytes; ToTensor + Normalize happen while its rows are staged
+        u8, img = x.dtype == torch.uint8, x
+        H, W = (x.shape[1], x.shape[2]) if u8 else (x.shape[2], x.shape[3])
+        if ops.stem_pool_dims(H, W)[1] <= 56 and (not u8 or W % 4 == 0):     # fused stem, one kernel
+            if u8:   # it reads the image bytes; ToTensor + Normalize happen while its rows are staged
                 x = ops.stem7x7_maxpool_u8(x, self.stem.wpk, self.stem.shift, self.mean, self.std, self.dtype)
             else:
-                x4 = ops.normalize_u8(x, self.mean, self.std, want_nchw=False, nhwc4_dtype=self.dtype)[1]
-                x = ops.maxpool(self.stem(x4, relu=True), 3, 2, 1)
-        elif ops.stem_pool_dims(x.shape[2], x.shape[3])[1] <= 56:
-            x = ops.stem7x7_maxpool(x, self.stem.wpk, self.stem.shift, self.dtype)   # fused stem, one kernel
-        else:  # wider than the fused kernel's 8 column strips
-            x = ops.maxpool(self.stem(ops.pack_input(x, self.dtype), relu=True), 3, 2, 1)
-        for c1, c2, ds, fshift in self.blocks:
-            if ds is None:
-                x = c2(c1(x, relu=True), relu=True, residual=x)
-                continue
+                x = ops.stem7x7_maxpool(x, self.stem.wpk, self.stem.shift, self.dtype)
+            if rec is not None:
+                rec("stem+pool3", x, self.stem, (img,))
+        else:  # wider than the fused kernel's 8 column strips (or bytes whose rows are no multiple of 4)
+            x4 = _nhwc4(x, self.dtype, self.mean, self.std, rec)
+            c = self.stem(x4, relu=True)
+            x = ops.maxpool(c, 3, 2, 1)
+            if rec is not None:
+                rec("stem", c, self.stem, (x4,))
+                rec("stem.pool3", x, ops.maxpool, (c,))
+        for i, (c1, c2, ds, fshift) in enumerate(self.blocks):
             h = c1(x, relu=True)
-            B, Hh, Wh, Ch = h.shape
-            if ds.k == 1 and ops.conv_ds_supported(B, Hh, Wh, Ch, c2.cout, x.shape[1], x.shape[2], x.shape[3], ds.stride):
-                # conv2 + bn2 + projection shortcut + add + ReLU in one launch (the shortcut as extra K stages)
-                x = ops.conv_igemm_ds(h, c2.wpk, fshift, c2.cout, x, ds.wpk, ds.stride, True)
+            fused = ds is not None and ds.k == 1 and ops.conv_ds_supported(*h.shape, c2.cout, *x.shape[1:], ds.stride)
+            if fused:   # conv2 + bn2 + projection shortcut + add + ReLU in one launch (the shortcut as extra K stages)
+                y = ops.conv_igemm_ds(h, c2.wpk, fshift, c2.cout, x, ds.wpk, ds.stride, True)
             else:
-                x = c2(h, relu=True, residual=ds(x, relu=False))
+                res = x if ds is None else ds(x, relu=False)
+                y = c2(h, relu=True, residual=res)
+            if rec is not None:
+                name = f"layer{i // 2 + 1}.{i % 2}."
+                rec(name + "conv1", h, c1, (x,))
+                if fused:
+                    rec(name + "conv2+ds", y, (c2, ds), (h, x))
+                else:
+                    if ds is not None:
+                        rec(name + "downsample", res, ds, (x,))
+                    rec(name + "conv2", y, c2, (h, res))
+            x = y
         return x
 
-    def pooled(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.avgpool_global(self.features(x))  # fp32 B×512
+    def pooled(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        f = self.features(x, rec)
+        y = ops.avgpool_global(f)  # fp32 B×512
+        if rec is not None:
+            rec("avgpool", y, ops.avgpool_global, (f,))
+        return y
+
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_f32(self.pooled(x), self.fc.weight.detach(), None, self.fc.bias.detach())
+
+
+class _PerOpPlan(dict):
+    """A family planned in Python: its packed operands by name (a dict: bench.py's roofline pass looks up "trunk") and, in the
+    subclasses, the family's one per-op forward over them, `embedding(x, rec=None)`."""
+    handle = None     # (no model handle of the family's own: `_HipModule.model_handle`)
+
+    def __init__(self, m: nn.Module, fc: Optional[nn.Linear] = None, **operands):
+        super().__init__(operands)
+        self.m, self.fc = m, fc      # the owning module; its classifier over the embedding
+
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_f32(self.embedding(x), self.fc.weight.detach(), None, self.fc.bias.detach())
 
 
 # --------------------------------------------------------------------------------------------
 # a2  BaselineNet
 # --------------------------------------------------------------------------------------------
+class _PyBaselinePlan(_PerOpPlan):
+    def __init__(self, m: "BaselineNet", dtype: torch.dtype):
+        super().__init__(m, m.fc2, c1=_PackedConv(m.conv1, m.bn1, dtype), c2=_PackedConv(m.conv2, m.bn2, dtype),
+                         c3=_PackedConv(m.conv3, m.bn3, dtype), fc1_t=m.fc1.weight.detach().float().t().contiguous())
+
+    def pooled_map(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        x = self.m._as_nhwc4(x, rec)
+        for key, name in (("c1", "conv1"), ("c2", "conv2"), ("c3", "conv3")):   # self.pool(F.relu(self.bn1(self.conv1(x)))), `face_models.py:38-40`
+            x = self[key].pooled(x, rec=rec, name=name)
+        return x
+
+    def pooled(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.avgpool_global(self.pooled_map(x))
+
+    def embed(self, x: torch.Tensor, rec=None):
+        """-> (embedding as the reference returns it, its unit-norm copy or None)."""
+        x, fc1 = self.pooled_map(x, rec), self.m.fc1
+        if _HEAD_FUSE:   # adaptive_pool + fc1 + ReLU (`face_models.py:41-46`) in one launch, the unit-norm copy for the matcher with it
+            emb, pre = ops.gap_linear_norm(x, self["fc1_t"], None, fc1.bias.detach(), 1e-12, want_pre=True, relu=True)
+            if rec is not None:
+                rec("fc1+relu", pre, ops.gap_linear_norm, (x,))
+                rec("fc1+relu.unit", emb, ops.gap_linear_norm, (x,))
+            return pre, emb
+        f = ops.avgpool_global(x)
+        pre = ops.linear_f32(f, fc1.weight.detach(), None, fc1.bias.detach(), relu=True)
+        if rec is not None:
+            rec("avgpool", f, ops.avgpool_global, (x,))
+            rec("fc1+relu", pre, ops.linear_f32, (f,))
+        return pre, None
+
+    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        return self.embed(x, rec)[0]
+
+    def unit_embedding(self, x: torch.Tensor) -> torch.Tensor:
+        pre, emb = self.embed(x)
+        return emb if emb is not None else ops.l2_normalize(pre, 1e-12)
+
+
 class BaselineNet(_HipModule):
     """`face_models.py:16-60`."""
 
@@ -332,65 +461,25 @@ class BaselineNet(_HipModule):
         self.fc2 = nn.Linear(512, num_classes)
         self.dropout = nn.Dropout(0.5)
 
-    def _build_plan(self, dtype):
-        if not _PY_PLAN and _HEAD_FUSE and _POOL_FUSE:
-            return _TrunkPlan("baseline", dict(self.state_dict()), self.fc2.out_features, dtype, self.input_mean, self.input_std, owner=self)
-        return {"c1": _PackedConv(self.conv1, self.bn1, dtype), "c2": _PackedConv(self.conv2, self.bn2, dtype),
-                "c3": _PackedConv(self.conv3, self.bn3, dtype), "fc1_t": self.fc1.weight.detach().float().t().contiguous()}
-
-    def model_handle(self):
-        p = self._get_plan()
-        return p.handle if isinstance(p, _TrunkPlan) else None
-
-    def _embed(self, x):
-        """-> (embedding as the reference returns it, its unit-norm copy or None)."""
-        x = self._check_input(x)
-        p = self._get_plan()
-        if isinstance(p, _TrunkPlan):
-            return p.handle.forward(x, ops.OUT_EMBEDDING), None
-        x = self._as_nhwc4(x)
-        x = p["c1"].pooled(x)      # self.pool(F.relu(self.bn1(self.conv1(x)))), `face_models.py:38`
-        x = p["c2"].pooled(x)
-        x = p["c3"].pooled(x)
-        if _HEAD_FUSE:   # adaptive_pool + fc1 + ReLU (`face_models.py:41-46`) in one launch, the unit-norm copy for the matcher with it
-            emb, pre = ops.gap_linear_norm(x, p["fc1_t"], None, self.fc1.bias.detach(), 1e-12, want_pre=True, relu=True)
-            return pre, emb
-        f = ops.avgpool_global(x)
-        return ops.linear_f32(f, self.fc1.weight.detach(), None, self.fc1.bias.detach(), relu=True), None
-
-    def get_embedding(self, x):
-        return self._embed(x)[0]
+    def _build_plan(self, dtype, per_op=False):
+        if per_op or _PY_PLAN or not (_HEAD_FUSE and _POOL_FUSE):
+            return _PyBaselinePlan(self, dtype)
+        return _TrunkPlan("baseline", dict(self.state_dict()), self.fc2.out_features, dtype, self.input_mean, self.input_std, owner=self)
 
     def pooled_features(self, x):
         """fp32 ``[B, 128]``: the output of ``adaptive_pool``, the input of ``fc1`` - what `head_fit.cache_features(layer="pooled")`
         caches so that a `head_fit.HiddenHead` can fit ``fc1`` / ``fc2``.  The per-op route (three conv + pool launches and the
-        global average pool) on a plan of its own; the model handle is not touched."""
+        global average pool) on the per-op plan, whatever the switches say; the model handle is not touched."""
         x = self._check_input(x)
-        sig = self._signature()
-        if getattr(self, "_pooled_plan", None) is None or sig != self._pooled_sig:
-            dev = next(self.parameters()).device
-            if dev.type != "cuda":
-                raise RuntimeError(f"{type(self).__name__} is on {dev}; move it to the GPU (.to('cuda')) — the HIP path has no CPU fallback")
-            with torch.no_grad():
-                self._pooled_plan = tuple(_PackedConv(c, b, self.compute_dtype) for c, b in
-                                          ((self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)))
-            self._pooled_sig = self._signature()
-        x = self._as_nhwc4(x)
-        for conv in self._pooled_plan:
-            x = conv.pooled(x)
-        return ops.avgpool_global(x)
+        return self._get_plan(per_op=True).pooled(x)
 
     def unit_embedding(self, x):
         """``F.normalize(get_embedding(x))`` (what `embed_and_match(normalize=True)` matches on) without a second launch."""
-        pre, emb = self._embed(x)
-        return emb if emb is not None else ops.l2_normalize(pre, 1e-12)
+        x = self._check_input(x)
+        return self._get_plan().unit_embedding(x)
 
     def forward(self, x):
-        h = self.model_handle()
-        if h is not None:
-            return h.forward(self._check_input(x), ops.OUT_LOGITS)
-        e = self.get_embedding(x)
-        return ops.linear_f32(e, self.fc2.weight.detach(), None, self.fc2.bias.detach())
+        return self._get_plan().logits(self._check_input(x))
 
 
 # --------------------------------------------------------------------------------------------
@@ -417,25 +506,16 @@ class ResNetTransfer(_HipModule):
         for param in self.resnet.parameters():
             param.requires_grad = True
 
-    def _build_plan(self, dtype):
-        if _PY_PLAN:
-            return _PyTrunkPlan(self.resnet, dtype, self.input_mean, self.input_std)
+    def _build_plan(self, dtype, per_op=False):
         fc = self.resnet.fc[1]
+        if per_op or _PY_PLAN:
+            return _PyTrunkPlan(self.resnet, dtype, self.input_mean, self.input_std, fc=fc)
         return _TrunkPlan("cnn", {f"resnet.{k}": v for k, v in self.resnet.state_dict().items()}, fc.out_features, dtype,
                           self.input_mean, self.input_std, owner=self)
 
-    def model_handle(self):
-        """The `frmap_model` behind this module (None under FRMAP_PY_PLAN=1): `matching.embed_and_match` runs on it in one call."""
-        p = self._get_plan()
-        return p.handle if isinstance(p, _TrunkPlan) else None
-
     def forward(self, x):
         x = self._check_input(x)
-        p = self._get_plan()
-        if isinstance(p, _TrunkPlan):
-            return p.handle.forward(x, ops.OUT_LOGITS)
-        fc = self.resnet.fc[1]
-        return ops.linear_f32(p.pooled(x), fc.weight.detach(), None, fc.bias.detach())
+        return self._get_plan().logits(x)
 
     def trunk_map(self, x):
         """The NHWC trunk output whose global average pool is ``get_embedding`` (`face_models.py:98-102`); lets
@@ -451,6 +531,59 @@ class ResNetTransfer(_HipModule):
 # --------------------------------------------------------------------------------------------
 # a6  SiameseNet
 # --------------------------------------------------------------------------------------------
+class _PySiamesePlan(_PerOpPlan):
+    def __init__(self, m: "SiameseNet", dtype: torch.dtype):
+        c, fc = m.conv, m.fc
+        # fc.1 consumes the NCHW flatten (index c*36 + s, `face_models.py:171`); our pooled tensor is
+        # NHWC (index s*512 + c): permute the weight's input axis once here.
+        w1 = fc[1].weight.detach().float().view(1024, 512, 36).permute(0, 2, 1).reshape(1024, 36 * 512)
+        super().__init__(m, None,    # convs: (packed conv + BatchNorm, a MaxPool2d(2) follows), named by CONVS
+                         convs=[(_PackedConv(c[i], c[i + 1], dtype), pool) for i, pool in
+                                ((0, True), (4, False), (7, True), (11, False), (14, True), (18, False))],
+                         fc1=_PackedLinearAsConv(w1, fc[1].bias, fc[2], dtype), fc2=_PackedLinearAsConv(fc[5].weight, fc[5].bias, fc[6], dtype),
+                         fc3=_PackedLinearAsConv(fc[8].weight, fc[8].bias, None, dtype))
+
+    CONVS = ("conv.0", "conv.4", "conv.7", "conv.11", "conv.14", "conv.18")     # step names: the layers' indices in `conv`
+    FCS = (("fc.1", "fc1", True), ("fc.5", "fc2", True), ("fc.8", "fc3", False))  # (step name, operand, ReLU): Linear -> BN -> ReLU twice, Linear
+
+    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        m, convs, names = self.m, self["convs"], self.CONVS
+        u8, img = x.dtype == torch.uint8, x
+        Wi = x.shape[2] if u8 else x.shape[3]
+        if ((Wi + 6 - 7) // 2 + 1) // 2 <= 64 and (not u8 or Wi % 4 == 0):   # fused conv.0-3: 7x7 conv + bias + BN + ReLU + MaxPool2d(2,2)
+            stem = convs[0][0]
+            if u8:
+                x = ops.stem7x7_maxpool_u8(x, stem.wpk, stem.shift, m.input_mean, m.input_std, m.compute_dtype, pool3=False)
+            else:
+                x = ops.stem7x7_maxpool(x, stem.wpk, stem.shift, m.compute_dtype, pool3=False)
+            if rec is not None:
+                rec("conv.0+pool2", x, stem, (img,))
+            convs, names = convs[1:], names[1:]
+        else:
+            x = m._as_nhwc4(x, rec)
+        for name, (conv, pool) in zip(names, convs):     # conv -> BN -> ReLU (-> MaxPool2d(2)), `face_models.py:121-146`
+            if pool:
+                x = conv.pooled(x, rec=rec, name=name)
+                continue
+            xin, x = x, conv(x, relu=True)
+            if rec is not None:
+                rec(name, x, conv, (xin,))
+        a = ops.avgpool_adaptive(x, 6, 6)  # NHWC B×6×6×512
+        if rec is not None:
+            rec("avgpool6x6", a, ops.avgpool_adaptive, (x,))
+        feats = a.view(a.shape[0], -1)
+        for name, key, relu in self.FCS:
+            fin, feats = feats, self[key](feats, relu=relu)
+            if rec is not None:
+                rec(name, feats, self[key], (fin,))
+        f32 = ops.cast_to_f32(feats)
+        y = ops.l2_normalize(f32, 1e-12)
+        if rec is not None:
+            rec("cast_f32", f32, ops.cast_to_f32, (feats,))
+            rec("normalize", y, ops.l2_normalize, (f32,))
+        return y
+
+
 class SiameseNet(_HipModule):
     """`face_models.py:104-192`."""
 
@@ -475,56 +608,18 @@ class SiameseNet(_HipModule):
         )
         self.debug_shapes = {}
 
-    def _build_plan(self, dtype):
-        if not _PY_PLAN and _POOL_FUSE:
-            return _TrunkPlan("siamese", dict(self.state_dict()), 0, dtype, self.input_mean, self.input_std, owner=self)
-        c = self.conv
-        # fc.1 consumes the NCHW flatten (index c*36 + s, `face_models.py:171`); our pooled tensor is
-        # NHWC (index s*512 + c): permute the weight's input axis once here.
-        w1 = self.fc[1].weight.detach().float().view(1024, 512, 36).permute(0, 2, 1).reshape(1024, 36 * 512)
-        return {
-            "convs": [(_PackedConv(c[0], c[1], dtype), True), (_PackedConv(c[4], c[5], dtype), False),
-                      (_PackedConv(c[7], c[8], dtype), True), (_PackedConv(c[11], c[12], dtype), False),
-                      (_PackedConv(c[14], c[15], dtype), True), (_PackedConv(c[18], c[19], dtype), False)],
-            "fc1": _PackedLinearAsConv(w1, self.fc[1].bias, self.fc[2], dtype),
-            "fc2": _PackedLinearAsConv(self.fc[5].weight, self.fc[5].bias, self.fc[6], dtype),
-            "fc3": _PackedLinearAsConv(self.fc[8].weight, self.fc[8].bias, None, dtype),
-        }
-
-    def model_handle(self):
-        p = self._get_plan()
-        return p.handle if isinstance(p, _TrunkPlan) else None
+    def _build_plan(self, dtype, per_op=False):
+        if per_op or _PY_PLAN or not _POOL_FUSE:
+            return _PySiamesePlan(self, dtype)
+        return _TrunkPlan("siamese", dict(self.state_dict()), 0, dtype, self.input_mean, self.input_std, owner=self)
 
     def forward_one(self, x):
         x = self._check_input(x)
-        p = self._get_plan()
-        batch_size = x.size(0)
-        self.debug_shapes["input"] = x.shape
-        if isinstance(p, _TrunkPlan):   # the whole tower is one call on the model handle; the reference's shape log is static
-            self.debug_shapes.update(after_conv=torch.Size((batch_size, 512, 6, 6)), flattened=torch.Size((batch_size, 512 * 6 * 6)),
-                                     before_norm=torch.Size((batch_size, 256)))
-            return p.handle.forward(x, ops.OUT_EMBEDDING)
-        convs = p["convs"]
-        u8 = x.dtype == torch.uint8
-        Wi = x.shape[2] if u8 else x.shape[3]
-        if ((Wi + 6 - 7) // 2 + 1) // 2 <= 64 and (not u8 or Wi % 4 == 0):   # fused conv.0-3: 7x7 conv + bias + BN + ReLU + MaxPool2d(2,2)
-            if u8:
-                x = ops.stem7x7_maxpool_u8(x, convs[0][0].wpk, convs[0][0].shift, self.input_mean, self.input_std,
-                                           self.compute_dtype, pool3=False)
-            else:
-                x = ops.stem7x7_maxpool(x, convs[0][0].wpk, convs[0][0].shift, self.compute_dtype, pool3=False)
-            convs = convs[1:]
-        else:
-            x = self._as_nhwc4(x)
-        for conv, pool in convs:     # conv -> BN -> ReLU (-> MaxPool2d(2)), `face_models.py:121-146`
-            x = conv.pooled(x) if pool else conv(x, relu=True)
-        x = ops.avgpool_adaptive(x, 6, 6)  # NHWC B×6×6×512
-        self.debug_shapes["after_conv"] = torch.Size((batch_size, 512, 6, 6))
-        feats = x.view(batch_size, -1)
-        self.debug_shapes["flattened"] = feats.shape
-        feats = p["fc3"](p["fc2"](p["fc1"](feats, relu=True), relu=True), relu=False)
-        self.debug_shapes["before_norm"] = feats.shape
-        return ops.l2_normalize(ops.cast_to_f32(feats), 1e-12)
+        p, B = self._get_plan(), x.size(0)
+        # the reference's shape log is static (the adaptive pool fixes 6 x 6): on the model handle the whole tower is one call
+        self.debug_shapes.update(input=x.shape, after_conv=torch.Size((B, 512, 6, 6)), flattened=torch.Size((B, 512 * 6 * 6)),
+                                 before_norm=torch.Size((B, 256)))
+        return p.embedding(x)
 
     def forward(self, x1, x2):
         return self.forward_one(x1), self.forward_one(x2)
@@ -588,6 +683,29 @@ class ArcMarginProduct(nn.Module):
                 'easy_margin_used': self.easy_margin_used if self.easy_margin else False}
 
 
+class _PyArcFacePlan(_PerOpPlan):
+    def __init__(self, m: "ArcFaceNet", dtype: torch.dtype):
+        scale, shift = _bn_scale_shift(m.bn)
+        super().__init__(m, None, trunk=_trunk_plan(m.backbone, dtype, m.input_mean, m.input_std, owner=m), bn_scale=scale, bn_shift=shift,
+                         wt=m.embedding.weight.detach().float().t().contiguous())   # [K][N] for the fused head
+
+    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        if _HEAD_FUSE and self["wt"].shape[1] in (256, 512):
+            # avgpool + embedding + bn + F.normalize (`face_models.py:584-590`) in one launch
+            f = self["trunk"].features(x, rec)
+            y = ops.gap_linear_norm(f, self["wt"], self["bn_scale"], self["bn_shift"], 1e-12)[0]
+            if rec is not None:
+                rec("embedding+bn+normalize", y, ops.gap_linear_norm, (f,))
+            return y
+        f = self["trunk"].pooled(x, rec)
+        pre = ops.linear_f32(f, self.m.embedding.weight.detach(), self["bn_scale"], self["bn_shift"])
+        y = ops.l2_normalize(pre, 1e-12)
+        if rec is not None:
+            rec("embedding+bn", pre, ops.linear_f32, (f,))
+            rec("normalize", y, ops.l2_normalize, (pre,))
+        return y
+
+
 class ArcFaceNet(_HipModule):
     """`face_models.py:447-613` (eval branch `:573-582`, ``get_embedding`` `:584-590`)."""
 
@@ -623,40 +741,15 @@ class ArcFaceNet(_HipModule):
     def set_max_grad_norm(self, max_norm):
         self.max_grad_norm = max_norm
 
-    def _build_plan(self, dtype):
-        scale, shift = _bn_scale_shift(self.bn)
-        if _PY_PLAN or not _HEAD_FUSE:
-            trunk = _PyTrunkPlan(self.backbone, dtype, self.input_mean, self.input_std) if _PY_PLAN else \
-                _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std, owner=self)
-        else:
-            state = {f"backbone.{k}": v for k, v in self.backbone.state_dict().items()}
-            state.update({"embedding.weight": self.embedding.weight, "val_classifier.weight": self.val_classifier.weight,
-                          "val_classifier.bias": self.val_classifier.bias})
-            state.update({f"bn.{k}": v for k, v in self.bn.state_dict().items()})
-            trunk = _TrunkPlan("arcface", state, self.val_classifier.out_features, dtype, self.input_mean, self.input_std, owner=self)
-        return {"trunk": trunk, "bn_scale": scale, "bn_shift": shift,
-                "wt": self.embedding.weight.detach().float().t().contiguous()}   # [K][N] for the fused head
-
-    def model_handle(self):
-        t = self._get_plan()["trunk"]
-        return t.handle if isinstance(t, _TrunkPlan) and t.handle.model_type == "arcface" else None
-
-    def _pre_norm(self, x):
-        p = self._get_plan()
-        f = p["trunk"].pooled(x)
-        return ops.linear_f32(f, self.embedding.weight.detach(), p["bn_scale"], p["bn_shift"])
-
-    def get_embedding(self, x):
-        x = self._check_input(x)
-        p = self._get_plan()
-        h = self.model_handle()
-        if h is not None:
-            # avgpool + embedding + bn + F.normalize (`face_models.py:584-590`): the handle's head, one launch after the trunk
-            return h.forward(x, ops.OUT_EMBEDDING)
-        if _HEAD_FUSE and p["wt"].shape[1] in (256, 512):
-            # avgpool + embedding + bn + F.normalize (`face_models.py:584-590`) in one launch
-            return ops.gap_linear_norm(p["trunk"].features(x), p["wt"], p["bn_scale"], p["bn_shift"], 1e-12)[0]
-        return ops.l2_normalize(self._pre_norm(x), 1e-12)
+    def _build_plan(self, dtype, per_op=False):
+        if per_op or _PY_PLAN or not _HEAD_FUSE:
+            return _PyArcFacePlan(self, dtype)
+        # avgpool + embedding + bn + F.normalize (`face_models.py:584-590`): the handle's head, one launch after the trunk
+        state = {f"backbone.{k}": v for k, v in self.backbone.state_dict().items()}
+        state.update({"embedding.weight": self.embedding.weight, "val_classifier.weight": self.val_classifier.weight,
+                      "val_classifier.bias": self.val_classifier.bias})
+        state.update({f"bn.{k}": v for k, v in self.bn.state_dict().items()})
+        return _TrunkPlan("arcface", state, self.val_classifier.out_features, dtype, self.input_mean, self.input_std, owner=self)
 
     def forward(self, x, labels=None):
         if self.training:
@@ -667,8 +760,8 @@ class ArcFaceNet(_HipModule):
         # `face_models.py:576`: the classifier rows are re-normalised in place on every eval call
         if self.val_classifier.weight.is_cuda:
             self.val_classifier.weight.data.copy_(ops.l2_normalize(self.val_classifier.weight.data, 1e-12))
-            if self._plan is not None:
-                self._plan_sig = self._signature()   # the plan does not depend on the classifier rows: no rebuild for this write
+            sig = self._signature()   # the plan does not depend on the classifier rows: no rebuild for this write
+            self._plans = {k: (plan, sig) for k, (plan, _) in self._plans.items()}
         if labels is not None:
             return ops.linear_f32(emb, self.val_classifier.weight.detach(), None, self.val_classifier.bias.detach())
         return emb
@@ -705,6 +798,50 @@ class TransformerBlock(nn.Module):
         raise RuntimeError("TransformerBlock is a parameter container; inference runs through HybridNet")
 
 
+class _HybridHandlePlan(_TrunkPlan):
+    def embedding(self, x: torch.Tensor) -> torch.Tensor:
+        try:
+            return super().embedding(x)
+        except ValueError as e:   # (the handle rejects maps that are not 49 tokens with the same message)
+            raise ValueError(str(e).split(": ", 1)[-1]) from None
+
+
+class _PyHybridPlan(_PerOpPlan):
+    def __init__(self, m: "HybridNet", dtype: torch.dtype):
+        tr = m.transformer
+        f32 = lambda t: t.detach().float().contiguous()
+        super().__init__(
+            m, m.fc, trunk=_trunk_plan(m.cnn, dtype, m.input_mean, m.input_std, owner=m), pos=f32(m.pos_encoding).view(m.seq_len, m.fdim),
+            n1=(f32(tr.norm1.weight), f32(tr.norm1.bias)), n2=(f32(tr.norm2.weight), f32(tr.norm2.bias)), nf=(f32(m.norm.weight), f32(m.norm.bias)),
+            qkv=_PackedLinearAsConv(tr.attention.in_proj_weight, tr.attention.in_proj_bias, None, dtype),
+            proj=_PackedLinearAsConv(tr.attention.out_proj.weight, tr.attention.out_proj.bias, None, dtype),
+            ff1=_PackedLinearAsConv(tr.ff[0].weight, tr.ff[0].bias, None, dtype), ff2=_PackedLinearAsConv(tr.ff[3].weight, tr.ff[3].bias, None, dtype))
+
+    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        """`face_models.py:705-721`: trunk (no pool) → +pos → pre-LN transformer block → token mean → LN."""
+        f = self["trunk"].features(x, rec)               # NHWC B×7×7×512 == tokens [B][49][512]
+        B, Hh, Ww, D = f.shape
+        L = Hh * Ww
+        if L != self.m.seq_len:
+            raise ValueError(f"HybridNet expects a {self.m.seq_len}-token feature map (224×224 input), got {L}")
+        t, n1 = ops.add_pos_layernorm(f.view(B, L, D), self["pos"], *self["n1"], want_sum=True)
+        qkv = self["qkv"](n1.view(B * L, D), relu=0)
+        att = ops.mha_tokens(qkv.view(B, L, 3 * D), self.m.transformer.attention.num_heads)
+        t2 = self["proj"](att.view(B * L, D), relu=0, residual=t.view(B * L, D))          # x + attn_out
+        _, n2 = ops.add_pos_layernorm(t2.view(B, L, D), None, *self["n2"])
+        hdn = self["ff1"](n2.view(B * L, D), relu=2)                                       # Linear → GELU
+        t3 = self["ff2"](hdn, relu=0, residual=t2)                                          # x + ff_out
+        y = ops.mean_layernorm(t3.view(B, L, D), *self["nf"])
+        if rec is not None:
+            for step in (("tokens+pos", t, ops.add_pos_layernorm, (f,)), ("norm1", n1, ops.add_pos_layernorm, (f,)),
+                         ("in_proj", qkv, self["qkv"], (n1.view(B * L, D),)), ("mha", att, ops.mha_tokens, (qkv,)),
+                         ("out_proj+res", t2, self["proj"], (att.view(B * L, D), t)), ("norm2", n2, ops.add_pos_layernorm, (t2,)),
+                         ("ff.0+gelu", hdn, self["ff1"], (n2.view(B * L, D),)), ("ff.3+res", t3, self["ff2"], (hdn, t2)),
+                         ("mean+norm", y, ops.mean_layernorm, (t3,))):
+                rec(*step)
+        return y
+
+
 class HybridNet(_HipModule):
     """`face_models.py:650-721`."""
 
@@ -721,55 +858,13 @@ class HybridNet(_HipModule):
         self.norm = nn.LayerNorm(self.fdim)
         self.fc = nn.Linear(self.fdim, num_classes)
 
-    def _build_plan(self, dtype):
-        if not _PY_PLAN:
-            return _TrunkPlan("hybrid", dict(self.state_dict()), self.fc.out_features, dtype, self.input_mean, self.input_std, owner=self)
-        tr = self.transformer
-        f32 = lambda t: t.detach().float().contiguous()
-        return {
-            "trunk": _trunk_plan(self.cnn, dtype, self.input_mean, self.input_std, owner=self),
-            "pos": f32(self.pos_encoding).view(self.seq_len, self.fdim),
-            "n1": (f32(tr.norm1.weight), f32(tr.norm1.bias)), "n2": (f32(tr.norm2.weight), f32(tr.norm2.bias)),
-            "nf": (f32(self.norm.weight), f32(self.norm.bias)),
-            "qkv": _PackedLinearAsConv(tr.attention.in_proj_weight, tr.attention.in_proj_bias, None, dtype),
-            "proj": _PackedLinearAsConv(tr.attention.out_proj.weight, tr.attention.out_proj.bias, None, dtype),
-            "ff1": _PackedLinearAsConv(tr.ff[0].weight, tr.ff[0].bias, None, dtype),
-            "ff2": _PackedLinearAsConv(tr.ff[3].weight, tr.ff[3].bias, None, dtype),
-        }
-
-    def get_embedding(self, x):
-        """`face_models.py:705-721`: trunk (no pool) → +pos → pre-LN transformer block → token mean → LN."""
-        x = self._check_input(x)
-        p = self._get_plan()
-        if isinstance(p, _TrunkPlan):
-            try:
-                return p.handle.forward(x, ops.OUT_EMBEDDING)
-            except ValueError as e:   # (the handle rejects maps that are not 49 tokens with the same message)
-                raise ValueError(str(e).split(": ", 1)[-1]) from None
-        f = p["trunk"].features(x)                       # NHWC B×7×7×512 == tokens [B][49][512]
-        B, Hh, Ww, D = f.shape
-        L = Hh * Ww
-        if L != self.seq_len:
-            raise ValueError(f"HybridNet expects a {self.seq_len}-token feature map (224×224 input), got {L}")
-        t, n1 = ops.add_pos_layernorm(f.view(B, L, D), p["pos"], *p["n1"], want_sum=True)
-        qkv = p["qkv"](n1.view(B * L, D), relu=0)
-        att = ops.mha_tokens(qkv.view(B, L, 3 * D), self.transformer.attention.num_heads)
-        t2 = p["proj"](att.view(B * L, D), relu=0, residual=t.view(B * L, D))          # x + attn_out
-        _, n2 = ops.add_pos_layernorm(t2.view(B, L, D), None, *p["n2"])
-        hdn = p["ff1"](n2.view(B * L, D), relu=2)                                       # Linear → GELU
-        t3 = p["ff2"](hdn, relu=0, residual=t2)                                          # x + ff_out
-        return ops.mean_layernorm(t3.view(B, L, D), *p["nf"])
-
-    def model_handle(self):
-        p = self._get_plan()
-        return p.handle if isinstance(p, _TrunkPlan) else None
+    def _build_plan(self, dtype, per_op=False):
+        if per_op or _PY_PLAN:
+            return _PyHybridPlan(self, dtype)
+        return _HybridHandlePlan("hybrid", dict(self.state_dict()), self.fc.out_features, dtype, self.input_mean, self.input_std, owner=self)
 
     def forward(self, x):
-        h = self.model_handle()
-        if h is not None:
-            return h.forward(self._check_input(x), ops.OUT_LOGITS)
-        e = self.get_embedding(x)
-        return ops.linear_f32(e, self.fc.weight.detach(), None, self.fc.bias.detach())
+        return self._get_plan().logits(self._check_input(x))
 
 
 # --------------------------------------------------------------------------------------------
@@ -805,6 +900,30 @@ class AttentionModule(nn.Module):
         raise RuntimeError("AttentionModule is a parameter container here; run AttentionNet on the GPU")
 
 
+class _PyAttentionPlan(_PerOpPlan):
+    def __init__(self, m: "AttentionNet", dtype: torch.dtype):
+        a = m.attention
+        w = torch.cat([a.query.weight, a.key.weight, a.value.weight], dim=0).detach().float()
+        bias = torch.cat([a.query.bias, a.key.bias, a.value.bias], dim=0).detach().float()
+        super().__init__(m, m.fc, trunk=_trunk_plan(m.backbone, dtype, m.input_mean, m.input_std, owner=m),
+                         qkv=ops.pack_conv_weight(w.contiguous(), dtype), qkv_bias=bias.contiguous(), cq=a.query.weight.shape[0], cqkv=w.shape[0],
+                         gamma=a.gamma.detach().float().contiguous(), sw=a.spatial_attention.conv.weight.detach().float().contiguous(),
+                         sb=a.spatial_attention.conv.bias.detach().float().contiguous())
+
+    def attend(self, x: torch.Tensor, want_map: bool, rec=None):
+        """-> (the attended map or None, its global average pool)."""
+        f = self["trunk"].features(x, rec)                                                    # NHWC B×H×W×512
+        qkv = ops.conv_igemm(f, self["qkv"], self["qkv_bias"], self["cqkv"], 1, 1, 0, 0)        # q | k | v  (+bias)
+        out = ops.cnn_attention(qkv, f, self["gamma"], self["sw"], self["sb"], self["cq"], want_map=want_map, want_pool=True)
+        if rec is not None:
+            rec("attention.qkv", qkv, ops.conv_igemm, (f,))
+            rec("attention.pool", out[1], ops.cnn_attention, (qkv, f))
+        return out
+
+    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+        return self.attend(x, False, rec)[1]
+
+
 class AttentionNet(_HipModule):
     """`face_models.py:264-295`: ResNet-18 trunk (no pool) → AttentionModule → global average pool → fc.
     q/k/v are ONE 1x1 conv (the three weight matrices stacked along Cout, biases as its shift); everything after it
@@ -818,34 +937,18 @@ class AttentionNet(_HipModule):
         self.gap = nn.AdaptiveAvgPool2d(1)
         self.fc = nn.Linear(512, num_classes)
 
-    def _build_plan(self, dtype):
-        a = self.attention
-        w = torch.cat([a.query.weight, a.key.weight, a.value.weight], dim=0).detach().float()
-        bias = torch.cat([a.query.bias, a.key.bias, a.value.bias], dim=0).detach().float()
-        return {"trunk": _trunk_plan(self.backbone, dtype, self.input_mean, self.input_std, owner=self), "qkv": ops.pack_conv_weight(w.contiguous(), dtype),
-                "qkv_bias": bias.contiguous(), "cq": a.query.weight.shape[0], "cqkv": w.shape[0],
-                "gamma": a.gamma.detach().float().contiguous(),
-                "sw": a.spatial_attention.conv.weight.detach().float().contiguous(),
-                "sb": a.spatial_attention.conv.bias.detach().float().contiguous()}
-
-    def _attend(self, x, want_map):
-        x = self._check_input(x)
-        p = self._get_plan()
-        f = p["trunk"].features(x)                                                   # NHWC B×H×W×512
-        qkv = ops.conv_igemm(f, p["qkv"], p["qkv_bias"], p["cqkv"], 1, 1, 0, 0)        # q | k | v  (+bias)
-        return ops.cnn_attention(qkv, f, p["gamma"], p["sw"], p["sb"], p["cq"], want_map=want_map, want_pool=True)
-
-    def get_embedding(self, x):
-        """`face_models.py:284-288`."""
-        return self._attend(x, False)[1]
+    def _build_plan(self, dtype, per_op=False):   # (no 'attention' handle family: the trunk on a handle, the head per-op)
+        return _PyAttentionPlan(self, dtype)
 
     def forward(self, x):
-        """`face_models.py:276-282`."""
-        return ops.linear_f32(self.get_embedding(x), self.fc.weight.detach(), None, self.fc.bias.detach())
+        """`face_models.py:276-282` (``get_embedding``: `:284-288`)."""
+        x = self._check_input(x)
+        return self._get_plan().logits(x)
 
     def attention_map(self, x):
         """The attended map the module hands to the pooling, NCHW-logical (stored NHWC): B×H×W×512."""
-        return self._attend(x, True)[0]
+        x = self._check_input(x)
+        return self._get_plan().attend(x, True)[0]
 
     def get_attention_params(self):
         self.attention.gamma_value = float(self.attention.gamma.detach().cpu().item())

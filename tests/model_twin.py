@@ -168,12 +168,22 @@ def to_twin_layout(y):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# the six models.  `plan`: which launches the HIP path fuses at this shape (the GPU test reads it off the planner's queries):
+# the six models.  `plan`: which launches the HIP path fuses at this shape (the GPU test reads it off the recorded step names, `plan_flags`):
 #   stem_fused   the 7x7 stem and its max-pool are one launch                    (trunk families, siamese)
 #   ds_fused     (layer2.0, layer3.0, layer4.0): conv2 + shortcut in one launch   (trunk families)
 #   pool_fused   per pooled conv, in order: conv + MaxPool2d(2, 2) in one launch  (baseline: 3, siamese: conv.7, conv.14 [, conv.0])
 # ------------------------------------------------------------------------------------------------------------------------------
 DEFAULT_PLAN = {"stem_fused": True, "ds_fused": (True, True, True), "pool_fused": (True, True, True)}
+
+
+def plan_flags(names):
+    """The plan a walk took, read off its step names (the HIP path's recorded ones or a twin's): a `stem+pool3` / `conv.0+pool2`
+    step is a fused stem, `conv2+ds` against `downsample` a fused shortcut, `+pool2` against `.pool2` a fused pooled conv (siamese's
+    conv.0 is the stem, not one of these).  A flag the family has no step for comes out False / empty."""
+    names = list(names)
+    return {"stem_fused": "stem+pool3" in names or "conv.0+pool2" in names,
+            "ds_fused": tuple(n.endswith("conv2+ds") for n in names if n.endswith(("conv2+ds", "downsample"))),
+            "pool_fused": tuple(n.endswith("+pool2") for n in names if n.endswith(("+pool2", ".pool2")) and not n.startswith("conv.0"))}
 
 
 def _conv_pool2(tape, name, x, w, sh, stride, pad, fused, bn=None):

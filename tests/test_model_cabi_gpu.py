@@ -3,7 +3,7 @@ package (`examples/cabi_model_client.py`, run in a subprocess: ctypes + a device
 
   * the reference-generated goldens `tests/golden/cnn.npz` / `arcface.npz` (outputs of the reference's own classes),
   * config 2's oracle top-1 (cnn, 256 faces, 36-ID enrolment gallery) and a 10 000-ID arcface match,
-  * the Python planner (`face_models._PyTrunkPlan`, FRMAP_PY_PLAN=1: one C-ABI op per call): same kernels in the same order on
+  * the per-op plans (`face_models._PyTrunkPlan` / `_Py*Plan`, FRMAP_PY_PLAN=1: one C-ABI op per call): same kernels in the same order on
     the same folded weights => bit-identical outputs; and the default Python surface, which is itself a client of the handle.
 """
 import os
@@ -46,12 +46,8 @@ def _py_model(mt, sd, dtype, py_plan=False):
     m = frmap_amd.get_model(mt, 36)
     m.load_state_dict(sd)
     m = m.to(DEV).eval().set_compute_dtype(dtype)
-    old = fm._PY_PLAN
-    fm._PY_PLAN = bool(py_plan)
-    try:
+    with fm.planned_in_python(py_plan):
         m._get_plan()
-    finally:
-        fm._PY_PLAN = old
     assert (m.model_handle() is None) == bool(py_plan)
     return m
 

@@ -230,13 +230,34 @@ def test_accumulation_order_moves_the_twin_by_less_than_2x(mt, kind, dtype, cali
 def test_handle_plan_refuses_a_batchnorm_with_another_eps(mt, layer):
     m = frmap_amd.get_model(mt, 36).eval()
     m.get_submodule(layer).eps = 1e-3
-    old = fm._PY_PLAN
-    fm._PY_PLAN = False
-    try:
-        with pytest.raises(ValueError, match=layer.replace(".", r"\.") + r".*eps"):
-            m._build_plan(torch.float16)
-    finally:
-        fm._PY_PLAN = old
+    with fm.planned_in_python(False), pytest.raises(ValueError, match=layer.replace(".", r"\.") + r".*eps"):
+        m._build_plan(torch.float16)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the plan flags the GPU test hands the twin are read off step names
+# ------------------------------------------------------------------------------------------------------------------------------
+def _plans(mt):
+    """Every plan the HIP path can take for the family (only the flags it has steps for)."""
+    ds = [(a, b, c) for a in (True, False) for b in (True, False) for c in (True, False)]
+    if mt == "baseline":
+        return [{"pool_fused": pf} for pf in ds]
+    if mt == "siamese":
+        return [{"stem_fused": s, "pool_fused": pf} for s in (True, False) for pf in sorted({d[:2] for d in ds})]
+    if mt == "hybrid":          # (needs its 49 tokens, a 224 x 224 input: the plan of its GPU cases)
+        return [{"stem_fused": True, "ds_fused": ds[0]}]
+    return [{"stem_fused": s, "ds_fused": d} for s in (True, False) for d in (ds if mt == "cnn" else ds[:1] + ds[-1:])]
+
+
+@pytest.mark.parametrize("mt", mw.MODELS)
+def test_plan_flags_are_read_off_the_step_names(mt):
+    """`mw.plan_flags` on the names the twin records under a plan gives that plan back, for every plan the GPU test's cases can
+    meet (the names depend on the plan alone, so a small input serves)."""
+    sd = frmap_amd.synth.synth_state_dict(frmap_amd.synth.shapes_of(frmap_amd.get_model(mt, 36)), 8900)
+    x = _x(mt, None if mt == "hybrid" else (1, 32, 32))
+    for plan in _plans(mt):
+        names = [s.name for s in mw.run(mt, sd, x, torch.float16, plan)]
+        assert mw.plan_flags(names) == {"stem_fused": False, "ds_fused": (), "pool_fused": (), **plan}, (plan, names)
 
 
 def test_header_states_the_eps_the_handle_folds_with():

@@ -255,6 +255,27 @@ def test_state_dict_reload_invalidates_plan(calibrated_sd):
         m(x)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("H,W", [(64, 64), (30, 22)])
+def test_pooled_features_is_the_per_op_plan_beside_the_handle(H, W, dtype, calibrated_sd):
+    """`BaselineNet.pooled_features`: the global average pool of the third pooled conv's output as the per-op forward records
+    it (fused at 64 x 64, conv and pool apart at 30 x 22), on a plan that follows the weights and leaves the model handle alone."""
+    from frmap_amd import ops
+    m = _model("baseline", calibrated_sd("baseline"), dtype)
+    x = synth.randn(9100 + H, (3, 3, H, W), "pooled.x").to(DEV)
+    handle, stored = m.model_handle(), {}
+    assert handle is not None
+    with torch.no_grad():
+        got = m.pooled_features(x)
+        assert m.model_handle() is handle
+        m._get_plan(per_op=True).embedding(x, lambda name, t, by, ins: stored.__setitem__(name, t))
+        third = stored["conv3+pool2" if (H, W) == (64, 64) else "conv3.pool2"]
+        assert got.shape == (3, 128) and torch.equal(got, ops.avgpool_global(third))
+        m.conv2.weight.mul_(0.5)                # in-place edit: version counter bump -> re-pack
+        assert not torch.equal(m.pooled_features(x), got)
+    torch.cuda.synchronize()
+
+
 def test_eval_step_and_siamese_verify(gold_dir, calibrated_sd):
     """The callers around the path: testing.py's forward→softmax→argmax step, the
     ArcFace class-centre scoring, and the Siamese dist<0.5 decision, against the CPU oracle."""
