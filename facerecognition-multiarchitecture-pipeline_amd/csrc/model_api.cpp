@@ -11,6 +11,9 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
+#include <initializer_list>
+
 #include "model_api.h"
 #include "match_device.h"   // frmap_match_topk_fill_labels
 
@@ -54,10 +57,6 @@ bool canonical_key(int kind, const std::string& key, std::string* out) {
   return out->compare(0, 9, "trunk.fc.") != 0;
 }
 
-void add_bn(std::map<std::string, size_t>& want, const std::string& p, int c) {
-  want[p + ".weight"] = c; want[p + ".bias"] = c; want[p + ".running_mean"] = c; want[p + ".running_var"] = c;
-}
-
 std::map<std::string, size_t> expected_tensors(const frmap_model* m) {
   std::map<std::string, size_t> want;
   if (m->kind == KIND_BASELINE || m->kind == KIND_SIAMESE) {
@@ -65,7 +64,7 @@ std::map<std::string, size_t> expected_tensors(const frmap_model* m) {
     return want;
   }
   want["trunk.conv1.weight"] = 64 * 3 * 7 * 7;
-  add_bn(want, "trunk.bn1", 64);
+  frmap_add_bn(&want, "trunk.bn1", 64);
   int inpl = 64;
   for (int li = 0; li < 4; ++li) {
     const int planes = kStagePlanes[li];
@@ -73,12 +72,12 @@ std::map<std::string, size_t> expected_tensors(const frmap_model* m) {
       const std::string p = "trunk.layer" + std::to_string(li + 1) + "." + std::to_string(bi);
       const int cin = bi == 0 ? inpl : planes;
       want[p + ".conv1.weight"] = (size_t)planes * cin * 9;
-      add_bn(want, p + ".bn1", planes);
+      frmap_add_bn(&want, p + ".bn1", planes);
       want[p + ".conv2.weight"] = (size_t)planes * planes * 9;
-      add_bn(want, p + ".bn2", planes);
+      frmap_add_bn(&want, p + ".bn2", planes);
       if (bi == 0 && li > 0) {
         want[p + ".downsample.0.weight"] = (size_t)planes * cin;
-        add_bn(want, p + ".downsample.1", planes);
+        frmap_add_bn(&want, p + ".downsample.1", planes);
       }
     }
     inpl = planes;
@@ -88,7 +87,7 @@ std::map<std::string, size_t> expected_tensors(const frmap_model* m) {
     want["fc.bias"] = m->num_classes;
   } else if (m->kind == KIND_ARCFACE) {
     want["embedding.weight"] = 512 * 512;
-    add_bn(want, "bn", 512);
+    frmap_add_bn(&want, "bn", 512);
     want["val_classifier.weight"] = (size_t)m->num_classes * 512;
     want["val_classifier.bias"] = m->num_classes;
   } else if (m->kind == KIND_HYBRID) {
@@ -154,7 +153,7 @@ int frmap_model_pack(frmap_model* m, const std::string& wkey, const std::string&
   return rc;
 }
 
-frmap_traced::frmap_traced(frmap_run& r_, const char* fmt, double flop, double bytes) : r(r_), on(r_.m->trace && !r_.dry) {
+frmap_traced::frmap_traced(frmap_run& r_, const char* fmt, double flop, double bytes) : r(r_), on(fmt && r_.m->trace && !r_.dry) {
   if (!on) return;
   snprintf(rec.kernel, sizeof(rec.kernel), fmt, r.dt);
   rec.flop = flop; rec.bytes = bytes;
@@ -173,12 +172,6 @@ namespace {
 auto& dev_alloc = frmap_model_dev_alloc;
 auto& dev_upload = frmap_model_dev_upload;
 auto& bn_fold = frmap_model_bn_fold;
-int pack_conv(frmap_model* m, const std::string& wkey, const std::string& bnkey, int cout, int cin, int k, int stride, int pad,
-              PackedConv* pc, std::vector<float>* shift_host, hipStream_t st) {
-  const int rc = frmap_model_pack(m, wkey, "", bnkey, cout, cin, k, stride, pad, pc, st);
-  if (shift_host) *shift_host = pc->shift_host;
-  return rc;
-}
 
 // ---- one forward ------------------------------------------------------------------------------------------------------
 using Run = frmap_run;
@@ -202,43 +195,27 @@ void conv(Run& r, const PackedConv& c, const void* in, int Hi, int Wi, const voi
 }
 
 // ResNet-18 trunk: x (fp32 NCHW or uint8 HWC) -> NHWC [B][h][w][512] map in `dtype`.  `slots`: three activation buffers of
-// slot_bytes(B, H, W) each.  The last block writes into `final_out` when given.  Returns the map's location and size.
+// `slot` bytes each (ModelWs).  The last block writes into `final_out` when given.  Returns the map's location and size.
 struct MapOut { void* p; int h, w; };
-
-size_t act_slot_bytes(int B, int H, int W) {
-  const int Hc = (H - 1) / 2 + 1, Wc = (W - 1) / 2 + 1;
-  const size_t conv_out = (size_t)B * Hc * Wc * 64 * 2, in4 = (size_t)B * H * W * 4 * 2;
-  const size_t s = conv_out > in4 ? conv_out : in4;
-  return (s + 255) / 256 * 256;
-}
 
 MapOut trunk_features(Run& r, const void* x, int x_kind, int H, int W, char* slots, size_t slot, void* final_out) {
   frmap_model* m = r.m;
   void* buf[3] = {slots, slots + slot, slots + 2 * slot};
-  const int Hc = (H + 6 - 7) / 2 + 1, Wc = (W + 6 - 7) / 2 + 1;
-  const int Hq = (Hc + 2 - 3) / 2 + 1, Wq = (Wc + 2 - 3) / 2 + 1;
+  const StemRoute s = frmap_stem_route(m->kind, x_kind, H, W);
   int cur = 0;
-  const double stem_flop = 2.0 * r.B * Hc * Wc * 64 * 147;
-  const double stem_out = (double)r.B * Hq * Wq * 64 * 2;
-  if (x_kind == 1) {
-    if (Wq <= 56 && W % 4 == 0) {
-      Traced t(r, ((uintptr_t)x & 3) == 0 ? "stem_s2d_kernel<%s, U8>" : "stem_pool_u8_kernel<%s>", stem_flop, (double)r.B * H * W * 3 + stem_out);
-      r.rc = frmap_stem7x7_maxpool_u8((const unsigned char*)x, m->mean, m->stdv, m->stem.wpk, m->stem.shift, buf[0], r.B, H, W, 1, m->dtype, r.st);
-    } else {
-      r.rc = frmap_normalize_u8_hwc((const unsigned char*)x, nullptr, buf[1], r.B, H, W, m->mean, m->stdv, m->dtype, r.st);
-      if (!r.rc) r.rc = frmap_conv_small_cin(buf[1], m->stem.wpk, m->stem.shift, buf[2], r.B, H, W, 64, 7, 7, 2, 3, 1, m->dtype, r.st);
-      if (!r.rc) r.rc = frmap_maxpool(buf[2], buf[0], r.B, Hc, Wc, 64, 3, 2, 1, m->dtype, r.st);
-    }
-  } else if (Wq <= 56) {
-    // (stem_s2d.hip takes 16-byte aligned tensors with W % 4 == 0; stem_pool.hip the rest)
-    Traced t(r, (W % 4 == 0 && ((uintptr_t)x & 15) == 0) ? "stem_s2d_kernel<%s>" : "stem_pool_kernel<%s>", stem_flop, (double)r.B * H * W * 3 * 4 + stem_out);
+  const double stem_flop = 2.0 * r.B * s.Hc * s.Wc * 64 * 147;
+  const double stem_out = (double)r.B * s.Hp * s.Wp * 64 * 2;
+  // (the labels mirror the launchers, which take their 16-byte paths from the pointer: stem_s2d.hip, else stem_pool.hip)
+  if (s.route == STEM_U8) {
+    Traced t(r, ((uintptr_t)x & 3) == 0 ? "stem_s2d_kernel<%s, U8>" : "stem_pool_u8_kernel<%s>", stem_flop, (double)r.B * H * W * 3 + stem_out);
+    r.rc = frmap_stem7x7_maxpool_u8((const unsigned char*)x, m->mean, m->stdv, m->stem.wpk, m->stem.shift, buf[0], r.B, H, W, 1, m->dtype, r.st);
+  } else if (s.route == STEM_POOL3) {
+    Traced t(r, (s.w4 && ((uintptr_t)x & 15) == 0) ? "stem_s2d_kernel<%s>" : "stem_pool_kernel<%s>", stem_flop, (double)r.B * H * W * 3 * 4 + stem_out);
     r.rc = frmap_stem7x7_maxpool((const float*)x, m->stem.wpk, m->stem.shift, buf[0], r.B, H, W, m->dtype, r.st);
-  } else {  // wider than the fused kernel's column strips
-    r.rc = frmap_pack_input_nchw_f32((const float*)x, buf[1], r.B, H, W, m->dtype, r.st);
-    if (!r.rc) r.rc = frmap_conv_small_cin(buf[1], m->stem.wpk, m->stem.shift, buf[2], r.B, H, W, 64, 7, 7, 2, 3, 1, m->dtype, r.st);
-    if (!r.rc) r.rc = frmap_maxpool(buf[2], buf[0], r.B, Hc, Wc, 64, 3, 2, 1, m->dtype, r.st);
+  } else {  // wider than the fused kernel's column strips, or uint8 rows that are no whole 4-pixel groups
+    frmap_stem_unfused(r, m->stem, x, x_kind, H, W, s, buf[1], buf[2], buf[0]);
   }
-  int h = Hq, w = Wq;
+  int h = s.Hp, w = s.Wp;
   for (int bi = 0; bi < 8 && !r.rc; ++bi) {
     const Block& b = m->blocks[bi];
     const bool last = bi == 7 && final_out;
@@ -290,39 +267,112 @@ int check_ready(const frmap_model* m, const char* what) {
   return 0;
 }
 
-// What the first kernel of a forward reads x with: an fp32 image goes to a stem or to pack_input, which take any element-aligned
-// tensor (and pick their 16-byte paths from the pointer); a uint8 image goes to the fused uint8 stem, which reads 4 pixels as three
-// dwords, where that stem takes the shape (as trunk_features / frmap_family_forward decide it), else to the byte-wise normalise kernel.
-int model_x_align(const frmap_model* m, int x_kind, int H, int W) {
-  if (x_kind == FRMAP_INPUT_F32_NCHW) return 4;
-  if (W % 4 != 0 || m->kind == KIND_BASELINE) return 1;
-  const int Wc = (W + 6 - 7) / 2 + 1;
-  if (m->kind == KIND_SIAMESE) return Wc / 2 <= 64 ? 4 : 1;
-  return (Wc + 2 - 3) / 2 + 1 <= 56 ? 4 : 1;
+// The caller's workspace: where each part starts, in bytes from its 256-byte aligned start, in the order the parts lie.  Nothing else
+// adds a size to `workspace`: the three *_workspace_bytes functions return these totals, the forwards take their pointers from here.
+struct ModelWs {
+  size_t slot;                 // the ResNet trunk's three activation slots at 0, slot, 2 * slot ('baseline' / 'siamese' have none: 0)
+  size_t tokens;               // hybrid: the trunk's [B][49][512] map, the token block's input
+  size_t arena;                // the families' bump arena (Arena::take, 256-byte steps)
+  size_t scratch0, scratch1;   // fp32 [B][512] each: a pooled row / an embedding in front of a head or of the matcher
+  size_t model_end;            // 256 spare bytes behind scratch1; frmap_model_workspace_bytes
+  size_t match;                // = model_end: the top-1 matcher's workspace, or a search's top-k workspace
+  size_t split;                // behind the top-1 workspace: the probes' fp16 split [B][3 x 512]
+  size_t match_end;            // frmap_model_match_workspace_bytes
+  size_t search_end;           // frmap_model_search_workspace_bytes: the top-1 step (k = 1) or the top-k workspace, the larger
+  bool carved256;              // what the launchers take as tensors is cut at multiples of 256 bytes
+};
+
+ModelWs model_ws(const frmap_model* m, int B, int H, int W, int G, int k) {
+  ModelWs L{};
+  if (!m || B <= 0) return L;
+  if (H > 0 && W > 0) {
+    if (m->kind != KIND_BASELINE && m->kind != KIND_SIAMESE) {   // a slot: the 7x7 conv's output or the NHWC4 input, the larger
+      const size_t conv_out = (size_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * 64 * 2, in4 = (size_t)B * H * W * 4 * 2;
+      L.slot = align256(std::max(conv_out, in4));
+    }
+    L.tokens = 3 * L.slot;
+    L.arena = L.tokens + (m->kind == KIND_HYBRID ? align256((size_t)B * 49 * 512 * 2) : 0);
+    // the arena is sized by running the families' forward without launching, for both input kinds (the call that asks has none, and
+    // a siamese tower takes uint8 rows that are no whole 4-pixel groups unfused, through more buffers); Arena::take rounds every
+    // piece up to 256
+    size_t fam = 0;
+    Run dry{const_cast<frmap_model*>(m), nullptr, B, "", 0, true};
+    for (int kind : {FRMAP_INPUT_F32_NCHW, FRMAP_INPUT_U8_HWC})
+      if (m->kind >= KIND_BASELINE) fam = std::max(fam, frmap_family_forward(dry, nullptr, kind, H, W, FRMAP_OUT_LOGITS, nullptr, nullptr, nullptr, nullptr));
+    const size_t row = align256((size_t)B * 512 * sizeof(float));
+    L.scratch0 = L.arena + fam; L.scratch1 = L.scratch0 + row; L.model_end = L.scratch1 + row + 256;
+  }
+  L.match = L.model_end;
+  L.split = L.match + align256(frmap_match_workspace_bytes(B, G));
+  L.match_end = L.split + align256((size_t)B * 3 * 512 * 2);
+  L.search_end = std::max(L.match_end, L.match + align256(frmap_match_topk_workspace_bytes(B, G, frmap_model_embedding_dim(m), k)));
+  L.carved256 = L.slot % 256 == 0 && L.model_end % 256 == 0;
+  return L;
 }
 
-// The carve-outs of a workspace are cut at multiples of 256 bytes from its (256-byte aligned) start: checked where a call begins,
-// before anything is launched, rather than left to the launchers further down.
-int check_carving(const frmap_model* m, const char* what, int B, int H, int W) {
-  // (the activation slots and the family arena; the heads and the match workspace start at frmap_model_workspace_bytes)
-  FRMAP_REQUIRE(act_slot_bytes(B, H, W) % 256 == 0 && frmap_model_workspace_bytes(m, B, H, W) % 256 == 0,
-                "%s: internal error: a workspace carve-out is not a multiple of 256 bytes", what);
+// One request to a handle, as the three entry points describe it; check_call refuses it before anything is launched.
+struct ModelCall {
+  const char* who;
+  const frmap_model* m;
+  const void* x;
+  int x_kind, B, H, W, what;       // what: a forward's output selector; a match / search call wants the embedding
+  bool match = false;              // embed_and_match / embed_and_search: G and gallery count
+  int G = 0;
+  const void* gallery = nullptr;
+  bool search = false;             // embed_and_search: k counts
+  int k = 0;
+  bool forwards = true;            // false: the call hands the forward on (a search with k = 1 and no labels), whose check then reports
+};
+struct PtrArg { const void* p; int bytes; const char* name; bool required; };   // one pointer argument and its alignment
+
+// In this order: the handle, null pointers, the shape, the input kind, the selector, x's alignment (what the first kernel reads x
+// with: the stem route), the workspace layout, the alignment of the entry point's own pointers, hybrid's 49 tokens.
+int check_call(const ModelCall& c, std::initializer_list<PtrArg> args, ModelWs* L) {
+  const frmap_model* m = c.m;
+  if (int rc = check_ready(m, c.who)) return rc;
+  bool present = c.x != nullptr;
+  for (const PtrArg& a : args) present = present && (a.p || !a.required);
+  FRMAP_REQUIRE(present, "%s: null pointer", c.who);
+  const bool shape = c.B > 0 && c.H >= 7 && c.W >= 7;
+  if (c.match) {
+    FRMAP_REQUIRE(m->kind != KIND_TRUNK, "%s: a bare trunk has no embedding", c.who);
+    FRMAP_REQUIRE(!c.search || (c.k >= 1 && c.k <= 64), "%s: k=%d out of range (1 <= k <= 64)", c.who, c.k);
+    FRMAP_REQUIRE(shape && c.G >= 0 && (c.G == 0 || c.gallery), "%s: bad shape B=%d H=%d W=%d G=%d", c.who, c.B, c.H, c.W, c.G);
+  } else {
+    FRMAP_REQUIRE(shape, "%s: bad shape B=%d H=%d W=%d", c.who, c.B, c.H, c.W);
+  }
+  FRMAP_REQUIRE(c.x_kind == FRMAP_INPUT_F32_NCHW || c.x_kind == FRMAP_INPUT_U8_HWC, "%s: bad input kind %d", c.who, c.x_kind);
+  FRMAP_REQUIRE(c.what >= FRMAP_OUT_TRUNK_MAP && c.what <= FRMAP_OUT_LOGITS, "%s: bad output selector %d", c.who, c.what);
+  FRMAP_REQUIRE(m->kind != KIND_TRUNK || c.what <= FRMAP_OUT_POOLED, "%s: a bare trunk has no embedding / logits head", c.who);
+  const StemRoute s = frmap_stem_route(m->kind, c.x_kind, c.H, c.W);
+  FRMAP_REQUIRE_ALIGNED_AS(c.who, c.x, s.x_align(c.x_kind), "x");
+  *L = model_ws(m, c.B, c.H, c.W, c.G, c.k);
+  FRMAP_REQUIRE(L->carved256, "%s: internal error: a workspace carve-out is not a multiple of 256 bytes", c.who);
+  for (const PtrArg& a : args) FRMAP_REQUIRE_ALIGNED_AS(c.who, a.p, a.bytes, a.name);
+  if (m->kind == KIND_HYBRID && c.what >= FRMAP_OUT_EMBEDDING && c.forwards) {   // the token block takes the trunk's 7 x 7 map
+    int th = s.Hp, tw = s.Wp;
+    for (int i = 0; i < 3; ++i) { th = (th - 1) / 2 + 1; tw = (tw - 1) / 2 + 1; }
+    FRMAP_REQUIRE(th * tw == 49, "%s: HybridNet expects a 49-token feature map (224x224 input), got %d", c.who, th * tw);
+  }
   return 0;
 }
+
+const struct { const char* name; int kind; } kKinds[] = {{"baseline", KIND_BASELINE}, {"cnn", KIND_CNN}, {"siamese", KIND_SIAMESE},
+                                                         {"arcface", KIND_ARCFACE}, {"hybrid", KIND_HYBRID}, {"resnet18_trunk", KIND_TRUNK}};
+const char* kind_name(int kind) { for (const auto& e : kKinds) if (e.kind == kind) return e.name; return "?"; }
 
 }  // namespace
 
 extern "C" int frmap_model_create(frmap_model** out, const char* model_type, int num_classes, int dtype) {
   FRMAP_REQUIRE(out && model_type, "model_create: null pointer");
   FRMAP_REQUIRE(dtype == FRMAP_BF16 || dtype == FRMAP_F16, "model_create: bad dtype %d", dtype);
-  int kind;
-  if (!strcmp(model_type, "cnn")) kind = KIND_CNN;
-  else if (!strcmp(model_type, "arcface")) kind = KIND_ARCFACE;
-  else if (!strcmp(model_type, "resnet18_trunk")) kind = KIND_TRUNK;
-  else if (!strcmp(model_type, "baseline")) kind = KIND_BASELINE;
-  else if (!strcmp(model_type, "siamese")) kind = KIND_SIAMESE;
-  else if (!strcmp(model_type, "hybrid")) kind = KIND_HYBRID;
-  else { frmap_set_error("Invalid model type: %s (model handles exist for 'baseline', 'cnn', 'siamese', 'arcface', 'hybrid', 'resnet18_trunk')", model_type); return -1; }
+  int kind = -1;
+  std::string known;
+  for (const auto& e : kKinds) {
+    if (!strcmp(model_type, e.name)) kind = e.kind;
+    known += std::string(known.empty() ? "'" : ", '") + e.name + "'";
+  }
+  FRMAP_REQUIRE(kind >= 0, "Invalid model type: %s (model handles exist for %s)", model_type, known.c_str());
   FRMAP_REQUIRE(kind == KIND_TRUNK || kind == KIND_SIAMESE || num_classes > 0, "model_create: num_classes=%d", num_classes);
   frmap_model* m = new (std::nothrow) frmap_model();
   FRMAP_REQUIRE(m, "model_create: out of host memory");
@@ -365,7 +415,7 @@ extern "C" int frmap_model_finalize(frmap_model* m, void* stream) {
   for (const auto& kv : expected_tensors(m))
     FRMAP_REQUIRE(m->raw.count(kv.first), "model_finalize: tensor %s was never loaded", kv.first.c_str());
   const bool has_trunk = m->kind != KIND_BASELINE && m->kind != KIND_SIAMESE;
-  int rc = has_trunk ? pack_conv(m, "trunk.conv1.weight", "trunk.bn1", 64, 3, 7, 2, 3, &m->stem, nullptr, st) : 0;
+  int rc = has_trunk ? frmap_model_pack(m, "trunk.conv1.weight", "", "trunk.bn1", 64, 3, 7, 2, 3, &m->stem, st) : 0;
   int inpl = 64;
   for (int li = 0; li < 4 && !rc && has_trunk; ++li) {
     const int planes = kStagePlanes[li];
@@ -373,13 +423,13 @@ extern "C" int frmap_model_finalize(frmap_model* m, void* stream) {
       Block& b = m->blocks[li * 2 + bi];
       const std::string p = "trunk.layer" + std::to_string(li + 1) + "." + std::to_string(bi);
       const int cin = bi == 0 ? inpl : planes, stride = (bi == 0 && li > 0) ? 2 : 1;
-      std::vector<float> s2, sd;
-      rc = pack_conv(m, p + ".conv1.weight", p + ".bn1", planes, cin, 3, stride, 1, &b.c1, nullptr, st);
-      if (!rc) rc = pack_conv(m, p + ".conv2.weight", p + ".bn2", planes, planes, 3, 1, 1, &b.c2, &s2, st);
+      rc = frmap_model_pack(m, p + ".conv1.weight", "", p + ".bn1", planes, cin, 3, stride, 1, &b.c1, st);
+      if (!rc) rc = frmap_model_pack(m, p + ".conv2.weight", "", p + ".bn2", planes, planes, 3, 1, 1, &b.c2, st);
       if (!rc && bi == 0 && li > 0) {
         b.has_ds = true;
-        rc = pack_conv(m, p + ".downsample.0.weight", p + ".downsample.1", planes, cin, 1, stride, 0, &b.ds, &sd, st);
-        for (int i = 0; i < planes; ++i) s2[i] += sd[i];
+        rc = frmap_model_pack(m, p + ".downsample.0.weight", "", p + ".downsample.1", planes, cin, 1, stride, 0, &b.ds, st);
+        std::vector<float> s2 = b.c2.shift_host;
+        for (size_t i = 0; i < b.ds.shift_host.size(); ++i) s2[i] += b.ds.shift_host[i];
         b.fshift = dev_upload(m, s2);
         if (!rc && !b.fshift) rc = -2;
       }
@@ -394,11 +444,7 @@ extern "C" int frmap_model_finalize(frmap_model* m, void* stream) {
   if (!rc && m->kind == KIND_ARCFACE) {
     std::vector<float> scale, shift;
     bn_fold(m, "bn", 512, &scale, &shift);
-    const auto& w = m->raw.at("embedding.weight");     // [N][K] -> [K][N] for the fused head kernel
-    std::vector<float> wt(w.size());
-    for (int n = 0; n < 512; ++n)
-      for (int k = 0; k < 512; ++k) wt[(size_t)k * 512 + n] = w[(size_t)n * 512 + k];
-    m->emb_wt = dev_upload(m, wt);
+    m->emb_wt = dev_upload(m, frmap_transposed(m->raw.at("embedding.weight"), 512, 512));   // for the fused head kernel
     m->bn_scale = dev_upload(m, scale);
     m->bn_shift = dev_upload(m, shift);
     float* cls = dev_upload(m, m->raw.at("val_classifier.weight"));
@@ -418,70 +464,39 @@ extern "C" int frmap_model_finalize(frmap_model* m, void* stream) {
 
 extern "C" int frmap_model_embedding_dim(const frmap_model* m) { return !m ? 0 : m->kind == KIND_SIAMESE ? 256 : 512; }
 
-extern "C" size_t frmap_model_workspace_bytes(const frmap_model* m, int B, int H, int W) {
-  if (!m || B <= 0 || H <= 0 || W <= 0) return 0;
-  const size_t heads = 2 * align256((size_t)B * 512 * sizeof(float)) + 256;
-  if (m->kind >= KIND_BASELINE) {   // the families' bump arena, sized by running their forward without launching
-    // (for both input kinds: the call that asks has none, and a siamese tower takes uint8 rows of W % 4 != 0 unfused, through more buffers)
-    size_t fam = 0;
-    for (int kind : {FRMAP_INPUT_F32_NCHW, FRMAP_INPUT_U8_HWC}) {
-      Run r{const_cast<frmap_model*>(m), nullptr, B, "", 0, true};
-      const size_t f = frmap_family_forward(r, nullptr, kind, H, W, FRMAP_OUT_LOGITS, nullptr, nullptr, nullptr, nullptr);
-      fam = f > fam ? f : fam;
-    }
-    if (m->kind == KIND_HYBRID) return 3 * act_slot_bytes(B, H, W) + align256((size_t)B * 49 * 512 * 2) + fam + heads;
-    return fam + heads;
-  }
-  return 3 * act_slot_bytes(B, H, W) + heads;
-}
+extern "C" size_t frmap_model_workspace_bytes(const frmap_model* m, int B, int H, int W) { return model_ws(m, B, H, W, 0, 0).model_end; }
 
-extern "C" size_t frmap_model_match_workspace_bytes(const frmap_model* m, int B, int H, int W, int G) {
-  if (!m || B <= 0) return 0;
-  return frmap_model_workspace_bytes(m, B, H, W) + align256(frmap_match_workspace_bytes(B, G)) + align256((size_t)B * 3 * 512 * 2);   // (+ the probes' fp16 split)
-}
+extern "C" size_t frmap_model_match_workspace_bytes(const frmap_model* m, int B, int H, int W, int G) { return model_ws(m, B, H, W, G, 0).match_end; }
+extern "C" size_t frmap_model_search_workspace_bytes(const frmap_model* m, int B, int H, int W, int G, int k) { return model_ws(m, B, H, W, G, k).search_end; }
 
 extern "C" int frmap_model_forward(frmap_model* m, const void* x, int x_kind, int B, int H, int W, int what, void* out,
                                    void* workspace, void* stream) {
-  if (int rc = check_ready(m, "model_forward")) return rc;
-  FRMAP_REQUIRE(x && out && workspace, "model_forward: null pointer");
-  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7, "model_forward: bad shape B=%d H=%d W=%d", B, H, W);
-  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_forward: bad input kind %d", x_kind);
-  FRMAP_REQUIRE(what >= FRMAP_OUT_TRUNK_MAP && what <= FRMAP_OUT_LOGITS, "model_forward: bad output selector %d", what);
-  FRMAP_REQUIRE(m->kind != KIND_TRUNK || what <= FRMAP_OUT_POOLED, "model_forward: a bare trunk has no embedding / logits head");
-  // x: model_x_align; the trunk map is stored in 16-byte pieces, the fp32 outputs element by element; the arena is carved in
-  // 256-byte steps (check_carving; Arena::take rounds every piece up to 256)
-  FRMAP_REQUIRE_ALIGNED_AS("model_forward", x, model_x_align(m, x_kind, H, W), "x");
-  if (int rc = check_carving(m, "model_forward", B, H, W)) return rc;
-  FRMAP_REQUIRE_ALIGNED_AS("model_forward", out, what == FRMAP_OUT_TRUNK_MAP ? 16 : 4, "out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_forward", workspace, 256, "workspace");
+  // the trunk map is stored in 16-byte pieces, the fp32 outputs element by element
+  ModelWs L;
+  if (int rc = check_call(ModelCall{"model_forward", m, x, x_kind, B, H, W, what},
+                          {{out, what == FRMAP_OUT_TRUNK_MAP ? 16 : 4, "out", true}, {workspace, 256, "workspace", true}}, &L))
+    return rc;
   Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
-  if (m->kind == KIND_BASELINE || m->kind == KIND_SIAMESE) {
-    FRMAP_REQUIRE(what != FRMAP_OUT_POOLED, "model_forward: '%s' has no pooled-trunk output", m->kind == KIND_BASELINE ? "baseline" : "siamese");
-    FRMAP_REQUIRE(m->kind != KIND_SIAMESE || what != FRMAP_OUT_LOGITS, "model_forward: 'siamese' has no classifier head (forward(x1, x2) = two embeddings)");
-    frmap_family_forward(r, x, x_kind, H, W, what, out, nullptr, (char*)workspace, nullptr);
-    return r.rc;
-  }
-  const size_t slot = act_slot_bytes(B, H, W);
   char* ws = (char*)workspace;
-  float* scratch0 = (float*)(ws + 3 * slot);
-  if (m->kind == KIND_HYBRID && what >= FRMAP_OUT_EMBEDDING) {
-    {   // (checked BEFORE anything is launched: a rejected call launches nothing)
-      int th = ((H + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1, tw = ((W + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1;
-      for (int i = 0; i < 3; ++i) { th = (th - 1) / 2 + 1; tw = (tw - 1) / 2 + 1; }
-      FRMAP_REQUIRE(th * tw == 49, "model_forward: HybridNet expects a 49-token feature map (224x224 input), got %d", th * tw);
-    }
-    void* tmap = ws + 3 * slot;
-    const MapOut hm = trunk_features(r, x, x_kind, H, W, ws, slot, tmap);
-    if (r.rc) return r.rc;
-    (void)hm;
-    frmap_family_forward(r, nullptr, x_kind, H, W, what, out, nullptr, ws + 3 * slot + align256((size_t)B * 49 * 512 * 2), tmap);
+  if (m->kind == KIND_BASELINE || m->kind == KIND_SIAMESE) {
+    FRMAP_REQUIRE(what != FRMAP_OUT_POOLED, "model_forward: '%s' has no pooled-trunk output", kind_name(m->kind));
+    FRMAP_REQUIRE(what != FRMAP_OUT_LOGITS || m->kind != KIND_SIAMESE,
+                  "model_forward: '%s' has no classifier head (forward(x1, x2) = two embeddings)", kind_name(m->kind));
+    frmap_family_forward(r, x, x_kind, H, W, what, out, nullptr, ws + L.arena, nullptr);
     return r.rc;
   }
-  const MapOut map = trunk_features(r, x, x_kind, H, W, ws, slot, what == FRMAP_OUT_TRUNK_MAP ? out : nullptr);
+  float* scratch0 = (float*)(ws + L.scratch0);
+  if (m->kind == KIND_HYBRID && what >= FRMAP_OUT_EMBEDDING) {
+    void* tmap = ws + L.tokens;
+    trunk_features(r, x, x_kind, H, W, ws, L.slot, tmap);
+    if (r.rc) return r.rc;
+    frmap_family_forward(r, nullptr, x_kind, H, W, what, out, nullptr, ws + L.arena, tmap);
+    return r.rc;
+  }
+  const MapOut map = trunk_features(r, x, x_kind, H, W, ws, L.slot, what == FRMAP_OUT_TRUNK_MAP ? out : nullptr);
   if (r.rc) return r.rc;
   const int HW = map.h * map.w;
   if (what == FRMAP_OUT_TRUNK_MAP) return 0;
-  FRMAP_REQUIRE(m->kind != KIND_HYBRID || what == FRMAP_OUT_POOLED, "model_forward: bad output selector");
   const bool arc = m->kind == KIND_ARCFACE;
   if (what == FRMAP_OUT_POOLED || (!arc && what == FRMAP_OUT_EMBEDDING))
     return frmap_avgpool_global(map.p, (float*)out, B, HW, 512, m->dtype, r.st);
@@ -501,40 +516,27 @@ extern "C" int frmap_model_forward(frmap_model* m, const void* x, int x_kind, in
 }
 
 // The embedding compare_faces matches (src/app.py:44,50-57) for every model kind but the 'cnn' small-gallery fused path: written to
-// emb_out (or a workspace slot) and returned in *emb.  0, or the error code with the error text set.
-static int model_match_embedding(Run& r, const void* x, int x_kind, int H, int W, int normalize, float* emb_out, char* ws, float** emb_ptr) {
+// emb_out (or scratch0) and returned in *emb.  0, or the error code with the error text set.
+static int model_match_embedding(Run& r, const void* x, int x_kind, int H, int W, int normalize, float* emb_out, char* ws, const ModelWs& L,
+                                 float** emb_ptr) {
   frmap_model* m = r.m;
   const int B = r.B;
-  const size_t slot = act_slot_bytes(B, H, W);
+  float* scratch0 = (float*)(ws + L.scratch0);
+  float* scratch1 = (float*)(ws + L.scratch1);
+  float* emb = *emb_ptr = emb_out ? emb_out : scratch0;
   if (m->kind >= KIND_BASELINE) {
     // the family forward fills the embedding the matcher needs: its unit-norm copy when `normalize`, else what get_embedding returns
-    const size_t model_ws = frmap_model_workspace_bytes(m, B, H, W);
-    float* e0 = (float*)(ws + model_ws - 2 * align256((size_t)B * 512 * sizeof(float)) - 256);
-    float* e1 = e0 + align256((size_t)B * 512 * sizeof(float)) / sizeof(float);
-    float* emb = emb_out ? emb_out : e0;
-    if (m->kind == KIND_HYBRID) {
-      int th = ((H + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1, tw = ((W + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1;
-      for (int i = 0; i < 3; ++i) { th = (th - 1) / 2 + 1; tw = (tw - 1) / 2 + 1; }
-      FRMAP_REQUIRE(th * tw == 49, "model_embed_and_match: HybridNet expects a 49-token feature map (224x224 input), got %d", th * tw);
-      void* tmap = ws + 3 * slot;
-      trunk_features(r, x, x_kind, H, W, ws, slot, tmap);
-      if (r.rc) return r.rc;
-      frmap_family_forward(r, nullptr, x_kind, H, W, FRMAP_OUT_EMBEDDING, normalize ? e1 : emb, normalize ? emb : nullptr,
-                           ws + 3 * slot + align256((size_t)B * 49 * 512 * 2), tmap);
-    } else if (m->kind == KIND_BASELINE) {
-      frmap_family_forward(r, x, x_kind, H, W, FRMAP_OUT_EMBEDDING, normalize ? e1 : emb, normalize ? emb : nullptr, ws, nullptr);
-    } else {
-      frmap_family_forward(r, x, x_kind, H, W, FRMAP_OUT_EMBEDDING, emb, nullptr, ws, nullptr);   // (already unit-norm)
-    }
-    *emb_ptr = emb;
+    // (siamese's is already unit-norm)
+    const bool unit = normalize && m->kind != KIND_SIAMESE;
+    void* tmap = m->kind == KIND_HYBRID ? ws + L.tokens : nullptr;   // hybrid: the trunk first, its map the token block's input
+    if (tmap) trunk_features(r, x, x_kind, H, W, ws, L.slot, tmap);
+    if (r.rc) return r.rc;
+    frmap_family_forward(r, tmap ? nullptr : x, x_kind, H, W, FRMAP_OUT_EMBEDDING, unit ? scratch1 : emb, unit ? emb : nullptr, ws + L.arena, tmap);
     return r.rc;
   }
-  float* scratch0 = (float*)(ws + 3 * slot);
-  float* scratch1 = (float*)(ws + 3 * slot + align256((size_t)B * 512 * sizeof(float)));
-  const MapOut map = trunk_features(r, x, x_kind, H, W, ws, slot, nullptr);
+  const MapOut map = trunk_features(r, x, x_kind, H, W, ws, L.slot, nullptr);
   if (r.rc) return r.rc;
   const int HW = map.h * map.w;
-  float* emb = emb_out ? emb_out : scratch0;
   if (m->kind == KIND_CNN) {
     r.rc = frmap_avgpool_global(map.p, normalize ? scratch1 : emb, B, HW, 512, m->dtype, r.st);
     if (!r.rc && normalize) r.rc = frmap_l2_normalize_f32(scratch1, emb, B, 512, 1e-12f, r.st);
@@ -542,7 +544,6 @@ static int model_match_embedding(Run& r, const void* x, int x_kind, int H, int W
     Traced t(r, "gap_linear_norm_kernel<%s>", 2.0 * B * 512 * 512, 2.0 * B * HW * 512 + 4.0 * 512 * 512 + 4.0 * B * 512);
     r.rc = frmap_gap_linear_norm(map.p, m->emb_wt, m->bn_scale, m->bn_shift, nullptr, emb, 1e-12f, B, HW, 512, 512, 0, m->dtype, r.st);
   }
-  *emb_ptr = emb;
   return r.rc;
 }
 
@@ -553,30 +554,19 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
                                            const void* gallery_packed, const float* gallery_stat, int G, float thresh,
                                            int normalize, int32_t* idx_out, float* dist_out, int32_t* id_or_unknown_out,
                                            int32_t* packed_out, float* emb_out, void* workspace, void* stream) {
-  if (int rc = check_ready(m, "model_embed_and_match")) return rc;
-  FRMAP_REQUIRE(x && idx_out && dist_out && workspace, "model_embed_and_match: null pointer");
-  FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_match: a bare trunk has no embedding");
-  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_match: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
-  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_match: bad input kind %d", x_kind);
-  // (x as frmap_model_forward; the matcher reads the gallery, its pack and emb_out - the probes - in 16-byte pieces)
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", x, model_x_align(m, x_kind, H, W), "x");
-  if (int rc = check_carving(m, "model_embed_and_match", B, H, W)) return rc;
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery, 16, "gallery");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery_packed, 16, "gallery_packed");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", gallery_stat, 16, "gallery_stat");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", idx_out, 4, "idx_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", dist_out, 4, "dist_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", id_or_unknown_out, 4, "id_or_unknown_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", packed_out, 4, "packed_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", emb_out, 16, "emb_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_match", workspace, 256, "workspace");
+  // (the matcher reads the gallery, its pack and emb_out - the probes - in 16-byte pieces)
+  ModelWs L;
+  if (int rc = check_call(ModelCall{"model_embed_and_match", m, x, x_kind, B, H, W, FRMAP_OUT_EMBEDDING, true, G, gallery},
+                          {{gallery, 16, "gallery"}, {gallery_packed, 16, "gallery_packed"}, {gallery_stat, 16, "gallery_stat"},
+                           {idx_out, 4, "idx_out", true}, {dist_out, 4, "dist_out", true}, {id_or_unknown_out, 4, "id_or_unknown_out"},
+                           {packed_out, 4, "packed_out"}, {emb_out, 16, "emb_out"}, {workspace, 256, "workspace", true}}, &L))
+    return rc;
   Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
-  char* match_ws = (char*)workspace + frmap_model_workspace_bytes(m, B, H, W);
-  const int D = m->kind >= KIND_BASELINE ? frmap_model_embedding_dim(m) : 512;
+  char* ws = (char*)workspace;
+  const int D = frmap_model_embedding_dim(m);
   if (m->kind == KIND_CNN && G <= 64) {
     // pool + (normalise) + compare_faces' scan in one launch, one workgroup per face
-    const size_t slot = act_slot_bytes(B, H, W);
-    const MapOut map = trunk_features(r, x, x_kind, H, W, (char*)workspace, slot, nullptr);
+    const MapOut map = trunk_features(r, x, x_kind, H, W, ws, L.slot, nullptr);
     if (r.rc) return r.rc;
     const int HW = map.h * map.w;
     Traced t(r, "gap_norm_match_kernel<%s>", 2.0 * B * 512 * G, 2.0 * B * HW * 512 + 4.0 * G * 512 + 16.0 * B);
@@ -584,75 +574,45 @@ extern "C" int frmap_model_embed_and_match(frmap_model* m, const void* x, int x_
                                 1e-12f, B, HW, 512, G, m->dtype, r.st);
   }
   float* emb = nullptr;
-  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
-  if (m->kind >= KIND_BASELINE) {
-    if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
-      void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
-      return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
-                                     match_ws, split, B, G, D, r.st);
-    }
-    return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
-  }
-  if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
-    void* split = match_ws + align256(frmap_match_workspace_bytes(B, G));
-    Traced t(r, "match_top1 (conv1x1_pp_kernel<F16, MATCH> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 16.0 * B);
+  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, ws, L, &emb)) return rc;
+  // the caller's pack, else the scan (the family kinds' match is not traced)
+  const bool pack = gallery_packed && gallery_stat && match_use_pack(G, D);
+  Traced t(r, m->kind >= KIND_BASELINE ? nullptr : pack ? "match_top1 (conv1x1_pp_kernel<F16, MATCH> + finalize)" : "match_top1 (gemm_nt_f32_kernel + finalize)",
+           (pack ? 6.0 : 2.0) * B * D * G, 4.0 * B * D + (pack ? 6.0 : 4.0) * G * D + 16.0 * B);
+  if (pack)
     return frmap_match_top1_packed(emb, gallery, gallery_packed, gallery_stat, idx_out, dist_out, id_or_unknown_out, packed_out, thresh,
-                                   match_ws, split, B, G, D, r.st);
-  }
-  Traced t(r, "match_top1 (gemm_nt_f32_kernel + finalize)", 2.0 * B * D * G, 4.0 * B * D + 4.0 * G * D + 16.0 * B);
-  return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, match_ws, B, G, D, r.st);
-}
-
-extern "C" size_t frmap_model_search_workspace_bytes(const frmap_model* m, int B, int H, int W, int G, int k) {
-  if (!m || B <= 0) return 0;
-  const size_t a = frmap_model_match_workspace_bytes(m, B, H, W, G);
-  const size_t b = frmap_model_workspace_bytes(m, B, H, W) + align256(frmap_match_topk_workspace_bytes(B, G, frmap_model_embedding_dim(m), k));
-  return a > b ? a : b;
+                                   ws + L.match, ws + L.split, B, G, D, r.st);
+  return frmap_match_top1(emb, gallery, idx_out, dist_out, id_or_unknown_out, packed_out, thresh, ws + L.match, B, G, D, r.st);
 }
 
 extern "C" int frmap_model_embed_and_search(frmap_model* m, const void* x, int x_kind, int B, int H, int W, const float* gallery,
                                             const void* gallery_packed, const float* gallery_stat, const int32_t* labels, int G,
                                             int k, int normalize, int32_t* idx_out, float* dist_out, int32_t* label_out,
                                             float* emb_out, void* workspace, void* stream) {
-  if (int rc = check_ready(m, "model_embed_and_search")) return rc;
-  FRMAP_REQUIRE(x && idx_out && dist_out && workspace, "model_embed_and_search: null pointer");
-  FRMAP_REQUIRE(m->kind != KIND_TRUNK, "model_embed_and_search: a bare trunk has no embedding");
-  FRMAP_REQUIRE(k >= 1 && k <= 64, "model_embed_and_search: k=%d out of range (1 <= k <= 64)", k);
-  FRMAP_REQUIRE(B > 0 && H >= 7 && W >= 7 && G >= 0 && (G == 0 || gallery), "model_embed_and_search: bad shape B=%d H=%d W=%d G=%d", B, H, W, G);
-  FRMAP_REQUIRE(x_kind == FRMAP_INPUT_F32_NCHW || x_kind == FRMAP_INPUT_U8_HWC, "model_embed_and_search: bad input kind %d", x_kind);
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", x, model_x_align(m, x_kind, H, W), "x");
-  if (int rc = check_carving(m, "model_embed_and_search", B, H, W)) return rc;
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery, 16, "gallery");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery_packed, 16, "gallery_packed");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", gallery_stat, 16, "gallery_stat");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", labels, 4, "labels");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", idx_out, 4, "idx_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", dist_out, 4, "dist_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", label_out, 4, "label_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", emb_out, 16, "emb_out");
-  FRMAP_REQUIRE_ALIGNED_AS("model_embed_and_search", workspace, 256, "workspace");
-  if (k == 1 && !labels) {   // the top-1 step itself: same embedding, same match, bit for bit
+  const bool top1 = k == 1 && !labels;   // the top-1 step itself: same embedding, same match, bit for bit
+  ModelWs L;
+  if (int rc = check_call(ModelCall{"model_embed_and_search", m, x, x_kind, B, H, W, FRMAP_OUT_EMBEDDING, true, G, gallery, true, k, !top1},
+                          {{gallery, 16, "gallery"}, {gallery_packed, 16, "gallery_packed"}, {gallery_stat, 16, "gallery_stat"},
+                           {labels, 4, "labels"}, {idx_out, 4, "idx_out", true}, {dist_out, 4, "dist_out", true},
+                           {label_out, 4, "label_out"}, {emb_out, 16, "emb_out"}, {workspace, 256, "workspace", true}}, &L))
+    return rc;
+  if (top1) {
     const int rc = frmap_model_embed_and_match(m, x, x_kind, B, H, W, gallery, gallery_packed, gallery_stat, G, INFINITY, normalize,
                                                idx_out, dist_out, nullptr, nullptr, emb_out, workspace, stream);
     if (rc || !label_out) return rc;
     return frmap_match_topk_fill_labels(label_out, B, (hipStream_t)stream);
   }
   Run r{m, (hipStream_t)stream, B, dt_name(m->dtype)};
-  char* match_ws = (char*)workspace + frmap_model_workspace_bytes(m, B, H, W);
+  char* ws = (char*)workspace;
   const int D = frmap_model_embedding_dim(m);
-  if (m->kind == KIND_HYBRID) {   // (checked before anything is launched)
-    int th = ((H + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1, tw = ((W + 6 - 7) / 2 + 1 + 2 - 3) / 2 + 1;
-    for (int i = 0; i < 3; ++i) { th = (th - 1) / 2 + 1; tw = (tw - 1) / 2 + 1; }
-    FRMAP_REQUIRE(th * tw == 49, "model_embed_and_search: HybridNet expects a 49-token feature map (224x224 input), got %d", th * tw);
-  }
   float* emb = nullptr;
-  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, (char*)workspace, &emb)) return rc;
+  if (int rc = model_match_embedding(r, x, x_kind, H, W, normalize, emb_out, ws, L, &emb)) return rc;
   if (gallery_packed && gallery_stat && match_use_pack(G, D)) {
     Traced t(r, "match_topk (conv1x1_pp_kernel<F16, MATCH_TOPR> + finalize)", 6.0 * B * D * G, 4.0 * B * D + 6.0 * G * D + 64.0 * B * k);
-    return frmap_match_topk_packed(emb, gallery, gallery_packed, gallery_stat, labels, idx_out, dist_out, label_out, match_ws, B, G, D, k, r.st);
+    return frmap_match_topk_packed(emb, gallery, gallery_packed, gallery_stat, labels, idx_out, dist_out, label_out, ws + L.match, B, G, D, k, r.st);
   }
   Traced t(r, "match_topk (exact scan)", 2.0 * B * D * G, 4.0 * B * D + 4.0 * G * D + 8.0 * B * k);
-  return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, match_ws, B, G, D, k, r.st);
+  return frmap_match_topk(emb, gallery, labels, idx_out, dist_out, label_out, ws + L.match, B, G, D, k, r.st);
 }
 
 extern "C" int frmap_model_trace(frmap_model* m, int enable) {

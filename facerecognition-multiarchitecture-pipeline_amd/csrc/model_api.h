@@ -55,7 +55,6 @@ struct frmap_model {
   std::vector<TraceRec> recs;
 };
 
-
 // helpers shared by the two files (model_api.cpp)
 void* frmap_model_dev_alloc(frmap_model* m, size_t bytes);
 float* frmap_model_dev_upload(frmap_model* m, const std::vector<float>& v);
@@ -63,8 +62,19 @@ void frmap_model_bn_fold(const frmap_model* m, const std::string& p, int c, std:
 // fold (optional) BatchNorm `bnkey` and (optional) bias `bkey` into an OIHW conv / [N][K] linear weight and pack it
 int frmap_model_pack(frmap_model* m, const std::string& wkey, const std::string& bkey, const std::string& bnkey, int cout, int cin,
                      int k, int stride, int pad, PackedConv* pc, hipStream_t st, const std::vector<float>* w_override = nullptr);
+// the four tensors of a BatchNorm with `c` channels under prefix `p`
+inline void frmap_add_bn(std::map<std::string, size_t>* want, const std::string& p, int c) {
+  (*want)[p + ".weight"] = c; (*want)[p + ".bias"] = c; (*want)[p + ".running_mean"] = c; (*want)[p + ".running_var"] = c;
+}
+// a Linear weight [N][K] as [K][N], the order the pool + Linear + normalise head reads
+inline std::vector<float> frmap_transposed(const std::vector<float>& w, int N, int K) {
+  std::vector<float> wt(w.size());
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k) wt[(size_t)k * N + n] = w[(size_t)n * K + k];
+  return wt;
+}
 
-// per-launch trace (frmap_model_trace): brackets one launch with events
+// per-launch trace (frmap_model_trace): brackets one launch with events (`fmt` null: a launch that is not traced)
 struct frmap_run {
   frmap_model* m;
   hipStream_t st;
@@ -81,9 +91,26 @@ struct frmap_traced {
   ~frmap_traced();
 };
 
+// Which kernels take the 7x7 stride-2 conv + max-pool in front of a ResNet trunk (3x3 pool, stride 2, pad 1) or of the siamese
+// tower (MaxPool2d(2)): decided here alone, from the model kind, the input kind and the image size.  The launchers behind a fused
+// route still pick their 16-byte paths from the pointer (stem_s2d.hip takes 16-byte aligned tensors with `w4`).
+enum { STEM_POOL3 = 0, STEM_POOL2 = 1, STEM_U8 = 2, STEM_UNFUSED = 3 };
+struct StemRoute {
+  int route, pool;      // STEM_*; the pool window (3 or 2)
+  int Hc, Wc, Hp, Wp;   // the conv's output and the pooled map
+  bool w4;              // rows of whole 4-pixel groups
+  // what the first kernel reads x with: the fused uint8 stem reads 4 pixels as three dwords, the byte-wise normalise kernel bytes;
+  // an fp32 image goes to a stem or to pack_input, which take any element-aligned tensor
+  int x_align(int x_kind) const { return x_kind == FRMAP_INPUT_F32_NCHW || route == STEM_U8 ? 4 : 1; }
+};
+StemRoute frmap_stem_route(int kind, int x_kind, int H, int W);
+// the unfused route: NHWC4 input -> x4, 7x7 conv -> full, max-pool -> out (three buffers of the caller's)
+void frmap_stem_unfused(frmap_run& r, const PackedConv& c, const void* x, int x_kind, int H, int W, const StemRoute& s, void* x4,
+                        void* full, void* out);
+
 // model_families.cpp
 void frmap_family_expected(const frmap_model* m, std::map<std::string, size_t>* want);
-bool frmap_family_key(int kind, const std::string& key, std::string* out);
+bool frmap_family_key(int kind, const std::string& key, std::string* out);   // (the caller has dropped num_batches_tracked)
 int frmap_family_finalize(frmap_model* m, hipStream_t st);
 // forward of 'baseline' / 'siamese' / the token block of 'hybrid'; returns bytes of workspace used (dry run: needed)
 size_t frmap_family_forward(frmap_run& r, const void* x, int x_kind, int H, int W, int what, void* out, float* unit_out, char* ws,

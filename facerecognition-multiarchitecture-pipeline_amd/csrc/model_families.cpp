@@ -14,10 +14,6 @@
 
 namespace {
 
-void add_bn(std::map<std::string, size_t>* want, const std::string& p, int c) {
-  (*want)[p + ".weight"] = c; (*want)[p + ".bias"] = c; (*want)[p + ".running_mean"] = c; (*want)[p + ".running_var"] = c;
-}
-
 // siamese tower: (conv index in nn.Sequential, bn index, Cin, Cout, MaxPool2d(2) after it)
 struct SiaConv { int ci, bi, cin, cout; bool pool; };
 const SiaConv kSia[6] = {{0, 1, 3, 64, true}, {4, 5, 64, 128, false}, {7, 8, 128, 128, true},
@@ -64,13 +60,11 @@ void* conv3(frmap_run& r, Arena& a, const PackedConv& c, const void* in, int& H,
   return out;
 }
 
-void* nhwc4_input(frmap_run& r, Arena& a, const void* x, int x_kind, int H, int W) {
-  void* x4 = a.take((size_t)r.B * H * W * 4 * 2);
+void nhwc4_input(frmap_run& r, const void* x, int x_kind, int H, int W, void* x4) {   // x4: B * H * W * 4 elements
   if (x_kind == FRMAP_INPUT_U8_HWC)
     GO(frmap_normalize_u8_hwc((const unsigned char*)x, nullptr, x4, r.B, H, W, r.m->mean, r.m->stdv, r.m->dtype, r.st));
   else
     GO(frmap_pack_input_nchw_f32((const float*)x, x4, r.B, H, W, r.m->dtype, r.st));
-  return x4;
 }
 
 void* linear(frmap_run& r, Arena& a, const PackedConv& l, const void* x2d, int M, int act, const void* residual) {
@@ -85,8 +79,27 @@ void* linear(frmap_run& r, Arena& a, const PackedConv& l, const void* x2d, int M
 
 }  // namespace
 
+StemRoute frmap_stem_route(int kind, int x_kind, int H, int W) {
+  StemRoute s;
+  const bool u8 = x_kind == FRMAP_INPUT_U8_HWC, sia = kind == KIND_SIAMESE;
+  s.Hc = (H + 6 - 7) / 2 + 1; s.Wc = (W + 6 - 7) / 2 + 1;
+  s.pool = sia ? 2 : 3;
+  s.Hp = sia ? s.Hc / 2 : (s.Hc + 2 - 3) / 2 + 1; s.Wp = sia ? s.Wc / 2 : (s.Wc + 2 - 3) / 2 + 1;
+  s.w4 = W % 4 == 0;
+  // the fused kernels work on column strips of the pooled map, and the uint8 one on whole 4-pixel groups; 'baseline' has no stem
+  const bool fused = kind != KIND_BASELINE && (sia ? s.Wp <= 64 : s.Wp <= 56) && (!u8 || s.w4);
+  s.route = !fused ? STEM_UNFUSED : u8 ? STEM_U8 : sia ? STEM_POOL2 : STEM_POOL3;
+  return s;
+}
+
+void frmap_stem_unfused(frmap_run& r, const PackedConv& c, const void* x, int x_kind, int H, int W, const StemRoute& s, void* x4,
+                        void* full, void* out) {
+  nhwc4_input(r, x, x_kind, H, W, x4);
+  GO(frmap_conv_small_cin(x4, c.wpk, c.shift, full, r.B, H, W, 64, 7, 7, 2, 3, 1, r.m->dtype, r.st));
+  GO(frmap_maxpool(full, out, r.B, s.Hc, s.Wc, 64, s.pool, 2, s.pool == 3 ? 1 : 0, r.m->dtype, r.st));
+}
+
 bool frmap_family_key(int kind, const std::string& key, std::string* out) {
-  if (key.size() > 19 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0) return false;
   if (kind == KIND_HYBRID) {
     if (key.compare(0, 4, "cnn.") == 0) {
       if (key.compare(0, 7, "cnn.fc.") == 0) return false;
@@ -107,7 +120,7 @@ void frmap_family_expected(const frmap_model* m, std::map<std::string, size_t>* 
       const std::string n = std::to_string(i);
       (*want)["conv" + n + ".weight"] = (size_t)ch[i] * ch[i - 1] * 9;
       (*want)["conv" + n + ".bias"] = ch[i];
-      add_bn(want, "bn" + n, ch[i]);
+      frmap_add_bn(want, "bn" + n, ch[i]);
     }
     (*want)["fc1.weight"] = 512 * 128; (*want)["fc1.bias"] = 512;
     (*want)["fc2.weight"] = (size_t)m->num_classes * 512; (*want)["fc2.bias"] = m->num_classes;
@@ -116,10 +129,10 @@ void frmap_family_expected(const frmap_model* m, std::map<std::string, size_t>* 
       const int k = c.cin == 3 ? 7 : 3;
       (*want)["conv." + std::to_string(c.ci) + ".weight"] = (size_t)c.cout * c.cin * k * k;
       (*want)["conv." + std::to_string(c.ci) + ".bias"] = c.cout;
-      add_bn(want, "conv." + std::to_string(c.bi), c.cout);
+      frmap_add_bn(want, "conv." + std::to_string(c.bi), c.cout);
     }
-    (*want)["fc.1.weight"] = (size_t)1024 * 18432; (*want)["fc.1.bias"] = 1024; add_bn(want, "fc.2", 1024);
-    (*want)["fc.5.weight"] = 512 * 1024; (*want)["fc.5.bias"] = 512; add_bn(want, "fc.6", 512);
+    (*want)["fc.1.weight"] = (size_t)1024 * 18432; (*want)["fc.1.bias"] = 1024; frmap_add_bn(want, "fc.2", 1024);
+    (*want)["fc.5.weight"] = 512 * 1024; (*want)["fc.5.bias"] = 512; frmap_add_bn(want, "fc.6", 512);
     (*want)["fc.8.weight"] = 256 * 512; (*want)["fc.8.bias"] = 256;
   } else if (m->kind == KIND_HYBRID) {
     (*want)["pos_encoding"] = 49 * 512;
@@ -142,11 +155,7 @@ int frmap_family_finalize(frmap_model* m, hipStream_t st) {
       const std::string n = std::to_string(i);
       rc = frmap_model_pack(m, "conv" + n + ".weight", "conv" + n + ".bias", "bn" + n, ch[i], ch[i - 1], 3, 1, 1, &m->convs[i - 1], st);
     }
-    const auto& w = m->raw.at("fc1.weight");   // [512][128] -> [128][512] for the pool + Linear + normalise head
-    std::vector<float> wt(w.size());
-    for (int n = 0; n < 512; ++n)
-      for (int k = 0; k < 128; ++k) wt[(size_t)k * 512 + n] = w[(size_t)n * 128 + k];
-    m->head_wt = frmap_model_dev_upload(m, wt);
+    m->head_wt = frmap_model_dev_upload(m, frmap_transposed(m->raw.at("fc1.weight"), 512, 128));
     m->head_b = frmap_model_dev_upload(m, m->raw.at("fc1.bias"));
     m->fc_w = frmap_model_dev_upload(m, m->raw.at("fc2.weight"));
     m->fc_b = frmap_model_dev_upload(m, m->raw.at("fc2.bias"));
@@ -198,7 +207,8 @@ size_t frmap_family_forward(frmap_run& r, const void* x, int x_kind, int H, int 
   const int B = r.B;
   if (m->kind == KIND_BASELINE) {
     int h = H, w = W;
-    void* x4 = nhwc4_input(r, a, x, x_kind, H, W);
+    void* x4 = a.take((size_t)B * H * W * 4 * 2);
+    nhwc4_input(r, x, x_kind, H, W, x4);
     void* c1;
     if (H % 2 == 0 && W % 2 == 0) {   // self.pool(F.relu(self.bn1(self.conv1(x)))) in one launch (face_models.py:38)
       c1 = a.take((size_t)B * (H / 2) * (W / 2) * 32 * 2);
@@ -228,26 +238,24 @@ size_t frmap_family_forward(frmap_run& r, const void* x, int x_kind, int H, int 
     return a.off;
   }
   if (m->kind == KIND_SIAMESE) {
-    int h, w;
+    const StemRoute s = frmap_stem_route(KIND_SIAMESE, x_kind, H, W);
+    const size_t pooled_bytes = (size_t)B * s.Hp * s.Wp * 64 * 2;
     void* cur;
-    const int Wc = (W + 6 - 7) / 2 + 1, Hc = (H + 6 - 7) / 2 + 1;
-    int first = 1;
-    if (Wc / 2 <= 64 && (x_kind != FRMAP_INPUT_U8_HWC || W % 4 == 0)) {   // conv.0-3 fused: 7x7 conv + bias + BN + ReLU + MaxPool2d(2, 2)
-      cur = a.take((size_t)B * (Hc / 2) * (Wc / 2) * 64 * 2);
-      frmap_traced t(r, "stem_pool_kernel<%s> (2x2 pool)", 2.0 * B * Hc * Wc * 64 * 147, (double)B * H * W * 3 * 4 + (double)B * (Hc / 2) * (Wc / 2) * 64 * 2);
-      if (x_kind == FRMAP_INPUT_U8_HWC)
+    if (s.route != STEM_UNFUSED) {   // conv.0-3 fused: 7x7 conv + bias + BN + ReLU + MaxPool2d(2, 2)
+      cur = a.take(pooled_bytes);
+      frmap_traced t(r, "stem_pool_kernel<%s> (2x2 pool)", 2.0 * B * s.Hc * s.Wc * 64 * 147, (double)B * H * W * 3 * 4 + (double)pooled_bytes);
+      if (s.route == STEM_U8)
         GO(frmap_stem7x7_maxpool_u8((const unsigned char*)x, m->mean, m->stdv, m->convs[0].wpk, m->convs[0].shift, cur, B, H, W, 0, m->dtype, r.st));
       else
         GO(frmap_stem7x7_maxpool2((const float*)x, m->convs[0].wpk, m->convs[0].shift, cur, B, H, W, m->dtype, r.st));
     } else {
-      void* x4 = nhwc4_input(r, a, x, x_kind, H, W);
-      void* full = a.take((size_t)B * Hc * Wc * 64 * 2);
-      GO(frmap_conv_small_cin(x4, m->convs[0].wpk, m->convs[0].shift, full, B, H, W, 64, 7, 7, 2, 3, 1, m->dtype, r.st));
-      cur = a.take((size_t)B * (Hc / 2) * (Wc / 2) * 64 * 2);
-      GO(frmap_maxpool(full, cur, B, Hc, Wc, 64, 2, 2, 0, m->dtype, r.st));
+      void* x4 = a.take((size_t)B * H * W * 4 * 2);
+      void* full = a.take((size_t)B * s.Hc * s.Wc * 64 * 2);
+      cur = a.take(pooled_bytes);
+      frmap_stem_unfused(r, m->convs[0], x, x_kind, H, W, s, x4, full, cur);
     }
-    h = Hc / 2; w = Wc / 2;
-    for (int i = first; i < 6; ++i) cur = conv3(r, a, m->convs[i], cur, h, w, kSia[i].pool);   // face_models.py:121-146
+    int h = s.Hp, w = s.Wp;
+    for (int i = 1; i < 6; ++i) cur = conv3(r, a, m->convs[i], cur, h, w, kSia[i].pool);   // face_models.py:121-146
     if (what == FRMAP_OUT_TRUNK_MAP) {
       if (!r.dry && !r.rc) r.rc = hipMemcpyAsync(out, cur, (size_t)B * h * w * 512 * 2, hipMemcpyDeviceToDevice, r.st) == hipSuccess ? 0 : -2;
       return a.off;

@@ -1496,6 +1496,19 @@ class ModelHandle:
             return IN_U8_HWC, x.shape[0], x.shape[1], x.shape[2]
         return IN_F32_NCHW, x.shape[0], x.shape[2], x.shape[3]
 
+    def _gallery(self, op: str, gallery: Optional[torch.Tensor], prepared):
+        """(G, the gallery as the library reads it - the caller keeps it until the call is queued -, its pointer, packed pointer, stat
+        pointer) of a match call; the pack only where it is this gallery's."""
+        if gallery is None or not int(gallery.shape[0]):
+            return 0, None, 0, 0, 0
+        src, gallery = gallery, _dev(gallery, f"model_{op}.gallery", torch.float32)
+        if gallery.shape[1] != self.embedding_dim:
+            raise ValueError(f"{op}: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
+        ppk = pst = 0
+        if _usable_pack(prepared, src, self.embedding_dim, op) is not None:
+            ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
+        return int(gallery.shape[0]), gallery, gallery.data_ptr(), ppk, pst
+
     def forward(self, x: torch.Tensor, what: int) -> torch.Tensor:
         x = _dev(x, "model_forward.x", None, ("frmap_model_forward", "x"))
         kind, B, H, W = self._geometry(x)
@@ -1522,16 +1535,8 @@ class ModelHandle:
         """One C call: forward + top-1 match.  Returns (idx, dist, ids, packed | None, emb | None)."""
         x = _dev(x, "model_embed_and_match.x", None, ("frmap_model_embed_and_match", "x"))
         kind, B, H, W = self._geometry(x)
-        G = int(gallery.shape[0]) if gallery is not None else 0
         with torch.cuda.device(x.device):
-            gptr = ppk = pst = 0
-            if G:
-                src, gallery = gallery, _dev(gallery, "model_embed_and_match.gallery", torch.float32)
-                if gallery.shape[1] != self.embedding_dim:
-                    raise ValueError(f"embed_and_match: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
-                gptr = gallery.data_ptr()
-                if _usable_pack(prepared, src, self.embedding_dim, "embed_and_match") is not None:
-                    ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
+            G, gallery, gptr, ppk, pst = self._gallery("embed_and_match", gallery, prepared)
             idx = torch.empty((B,), dtype=torch.int32, device=x.device)
             dist = torch.empty((B,), dtype=torch.float32, device=x.device)
             ids = torch.empty((B,), dtype=torch.int32, device=x.device)
@@ -1553,16 +1558,9 @@ class ModelHandle:
         k = int(k)
         if not 1 <= k <= MATCH_TOPK_MAX:
             raise ValueError(f"embed_and_search: k={k} out of range (1 <= k <= {MATCH_TOPK_MAX})")
-        G = int(gallery.shape[0]) if gallery is not None else 0
         with torch.cuda.device(x.device):
-            gptr = ppk = pst = lptr = 0
-            if G:
-                src, gallery = gallery, _dev(gallery, "model_embed_and_search.gallery", torch.float32)
-                if gallery.shape[1] != self.embedding_dim:
-                    raise ValueError(f"embed_and_search: embedding dim {self.embedding_dim} != gallery dim {gallery.shape[1]}")
-                gptr = gallery.data_ptr()
-                if _usable_pack(prepared, src, self.embedding_dim, "embed_and_search") is not None:
-                    ppk, pst = prepared.packed.data_ptr(), prepared.stat_w.data_ptr()
+            G, gallery, gptr, ppk, pst = self._gallery("embed_and_search", gallery, prepared)
+            lptr = 0
             if labels is not None:
                 labels = _dev(labels, "model_embed_and_search.labels", torch.int32, ("frmap_model_embed_and_search", "labels"))
                 if tuple(labels.shape) != (G,):

@@ -3,27 +3,21 @@ reached through `ops.ModelHandle`, so that the workspace is exactly `frmap_model
 the rear band at its last byte.  Expected values are the unguarded call's bits (the two-fill rule); model parity is tested in
 `test_models_gpu.py` / `test_model_cabi_gpu.py`.  Weights live in memory the library allocates for itself (not guarded).
 
-How `model_api.cpp` / `model_families.cpp` cut the workspace (first write / first read, read from the code):
-  slots 0..2 [act_slot_bytes each]   ResNet trunks.  slot 0: the fused stem (or max-pool of the unfused one) writes it; slot 1:
-                                     `pack_input` / `normalize_u8_hwc` (NHWC4 input, B H W 8 bytes = the slot's `in4` term);
-                                     slot 2: the 7x7 conv of the unfused stem (B Hc Wc 128 bytes = the `conv_out` term).  Each
-                                     block reads `buf[cur]`, writes the other two; every later map is at most half of `conv_out`.
-  token map [B 49 512 x 2]           hybrid: the last trunk block writes it (`final_out`) / `add_pos_layernorm` reads it
-  family arena [fam]                 bump arena (`Arena::take`, 256-byte steps), sized by the same code run dry: every buffer is
-                                     an output of the launch that follows its `take` and an input of later launches only.
-                                     `linear` takes its split-K slab from the arena at `frmap_linear_mfma_workspace_bytes`.
-  heads: scratch0, scratch1 [B 512 x 4 each, 256-aligned] + 256   cnn logits: `avgpool_global` writes scratch0 / `linear_f32`
-                                     reads; arcface logits: `gap_linear_norm` writes / `linear_f32` reads; match: scratch1 =
-                                     pooled, scratch0 = its unit-norm copy.  Families find them by subtracting from the end of
-                                     `frmap_model_workspace_bytes` (e0, e1): the arena ends where they begin.
-  match workspace                    at `frmap_model_workspace_bytes`: `frmap_match_workspace_bytes(B, G)` (256-aligned), then the
-                                     probes' fp16 split [B][3 x 512]; search: `frmap_match_topk_workspace_bytes`.  Fields as
-                                     `test_guard_ops_gpu.py` lists them.
-No field is read before it is written.  ONE SIZING ERROR was found by this reading and is fixed here: the dry run that sizes the
-family arena ran for fp32 input only, while a siamese tower takes uint8 rows of W % 4 != 0 through the unfused stem (NHWC4 input
-+ full-resolution conv map + pooled map instead of one pooled map): `frmap_model_workspace_bytes` was too small for that call.
-It now takes the larger of the two input kinds (`test_siamese_u8_unfused_stem`).  And `ops.ModelHandle.forward` sized a
-baseline / siamese trunk map as a ResNet's [B, 7, 7, 512]; it is [B, 28, 28, 128] / [B, 14, 14, 512] at 224 x 224.
+The workspace is cut as `ModelWs` in `model_api.cpp` states it (one struct, filled by `model_ws`, read by the three
+`*_workspace_bytes` functions and by every forward).  Which launch first writes and first reads each field:
+  slot 0..2     ResNet trunks.  slot 0: the fused stem (or the max-pool of the unfused one) writes it; slot 1: `pack_input` /
+                `normalize_u8_hwc` (NHWC4 input); slot 2: the 7x7 conv of the unfused stem.  Each block reads `buf[cur]` and
+                writes the other two; every later map is at most half of the 7x7 conv's.
+  tokens        hybrid: the last trunk block writes it (`final_out`) / `add_pos_layernorm` reads it
+  arena         `Arena::take`: every buffer is an output of the launch that follows its `take` and an input of later launches
+                only; `linear` takes its split-K slab from the arena at `frmap_linear_mfma_workspace_bytes`.  Sized by the same
+                code run dry for both input kinds: a siamese tower takes uint8 rows of W % 4 != 0 through the unfused stem,
+                through more buffers than the fp32 call of the same size (`test_siamese_u8_unfused_stem`).
+  scratch0, 1   cnn logits: `avgpool_global` writes scratch0 / `linear_f32` reads; arcface logits: `gap_linear_norm` writes /
+                `linear_f32` reads; match: scratch1 = the pooled row or the family's own embedding, scratch0 = its unit-norm copy
+  match, split  the matcher's fields as `test_guard_ops_gpu.py` lists them; the split is written by the packed top-1's first launch
+No field is read before it is written.  A baseline / siamese trunk map is [B, 28, 28, 128] / [B, 14, 14, 512] at 224 x 224, not a
+ResNet's [B, 7, 7, 512] (`ops.ModelHandle.forward` sizes it).
 """
 import pytest
 import torch
