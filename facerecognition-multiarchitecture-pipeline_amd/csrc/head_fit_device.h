@@ -1,7 +1,7 @@
 // The device code that the head-fitting translation units share (head_fit.hip: the linear step and its groups; head_fit_hidden.hip:
-// the hidden-layer step): the tile walk of both GEMMs, its operand loaders and the bodies of the three kernels.  The kernels themselves
-// (`__global__`) stay with their launchers: a code object holds the kernels of ONE of the two files, so adding a kernel to one file
-// leaves the other file's code object - LDS layout, register allocation, instructions - as it is.
+// the hidden-layer step; head_fit_pair.hip: the pair step): the tile walk of both GEMMs, its operand loaders and the bodies of the three
+// kernels.  The kernels themselves (`__global__`) stay with their launchers: a code object holds the kernels of ONE of the files, so
+// adding a kernel to one file leaves the other files' code objects - LDS layout, register allocation, instructions - as they are.
 #pragma once
 #include "frmap_common.h"
 #include "head_fit_rule.h"
@@ -196,11 +196,16 @@ struct HfUpdateOp {
 // HIDDEN: the first layer of the hidden-layer step - the same tile walk over w = w1 [C = Hd, D] with the ReLU epilogue; a label is
 // in range below CL (the class count, where C is the hidden width), `lab` receives the label of a counted row or -1, and nothing is
 // counted into any state.
-template <bool HIDDEN>
+// HF_PAIR_ROWS: the forward of the pair step (head_fit_pair.hip) - no label is read or checked, the identity epilogue, nothing counted;
+// batch row i reads rows[i] below `split` and rows_hi[i - split] from there on.  (MODE was a bool: false / true still name the first two.)
+constexpr int HF_LINEAR = 0, HF_HIDDEN = 1, HF_PAIR_ROWS = 2;
+template <int MODE>
 __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, const int32_t* __restrict__ labels, const int32_t* __restrict__ rows,
                                                const uint8_t* __restrict__ keep, float keep_scale, const float* __restrict__ w,
                                                const float* __restrict__ b, uint64_t* state, float* __restrict__ z,
-                                               int32_t* __restrict__ row_src, int32_t* __restrict__ lab, int N, int B, int D, int C, int CL) {
+                                               int32_t* __restrict__ row_src, int32_t* __restrict__ lab, int N, int B, int D, int C, int CL,
+                                               const int32_t* __restrict__ rows_hi = nullptr, int split = 0) {
+  constexpr bool HIDDEN = MODE == HF_HIDDEN;
   __shared__ HfSmem sm;
   __shared__ int s_src[HF_T];        // the row of x behind tile row i; -1: outside the batch, the cache or the label range
   __shared__ int s_bad[HF_T];        // a non-finite feature was staged for tile row i
@@ -210,10 +215,15 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
     int src = -1;
     const int i = b0 + tid;
     if (i < B) {
-      const long long r = rows ? (long long)rows[i] : (long long)i;
-      if (r >= 0 && r < (long long)N) {
-        const int y = labels[r];
-        if (y >= 0 && y < (HIDDEN ? CL : C)) src = (int)r;
+      if (MODE == HF_PAIR_ROWS) {
+        const long long r = (long long)(i < split ? rows[i] : rows_hi[i - split]);
+        if (r >= 0 && r < (long long)N) src = (int)r;
+      } else {
+        const long long r = rows ? (long long)rows[i] : (long long)i;
+        if (r >= 0 && r < (long long)N) {
+          const int y = labels[r];
+          if (y >= 0 && y < (HIDDEN ? CL : C)) src = (int)r;
+        }
       }
     }
     s_src[tid] = src;
@@ -238,6 +248,7 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
     const bool in = tid < HF_T && b0 + tid < B;
     const bool counted = in && s_src[tid] >= 0 && s_bad[tid] == 0;
     if (in) row_src[b0 + tid] = counted ? s_src[tid] : -1;
+    if (MODE == HF_PAIR_ROWS) return;
     if (HIDDEN) {
       if (in) lab[b0 + tid] = counted ? labels[s_src[tid]] : -1;
       return;

@@ -64,6 +64,28 @@
 // carries t, n and the epoch figures.  The first part's t and n are copies written by the step; its figure words stay 0.
 // HIDDEN WORKSPACE (frmap_head_fit_hidden_workspace_bytes): fp32 h [B Hd], da [B Hd], int32 lab [B], row_src1 [B], then the single
 // workspace for (B, Hd -> C).
+//
+// PAIR (frmap_head_fit_pair_step; head_fit.pair_step_rule in numpy).  A contrastive head x -> normalize(x w^T + b) over PAIRS of cached
+// rows: left [P], right [P] int32 rows of x, differ [P] int32 (0: the same identity, pulled together; 1: different, pushed apart up
+// to `margin`), keep [2P, D] uint8 or NULL with keep_scale, w [E, D], b [E], the floats margin, w_same, w_diff, accept.
+//   batch      2P rows: row i < P reads left[i], row P + i reads right[i].  A row is declined when its index is outside [0, N) or
+//              any of its D features is non-finite (no label is read).
+//   a[i][e]  = dot_k(x'[i][k], w[e][k]) + b[e]                          chain order over D, bias last; a declined row is +0
+//   counted    pair p is counted iff both of its rows are and differ[p] is 0 or 1; n = the counted pairs.  An uncounted pair has
+//              row_src = -1 on BOTH its rows, +0 rows of ga, NaN in pair_loss and dist.  n == 0: nothing changes but the workspace.
+//   loss       per counted pair in FLOAT64 from the fp32 a, rounded to fp32 once (the stance of the softmax half):
+//              s = max(||a||, 1e-12), u = a_l / s_l, v = a_r / s_r                 (F.normalize)
+//              delta = (u - v) + 1e-6, d0 = ||delta||, d = max(d0, 1e-8)           (F.pairwise_distance, then the clamp)
+//              pair_loss = differ ? w_diff max(margin - d, 0)^2 : w_same d^2;  dist = d
+//              q = (differ ? -2 w_diff max(margin - d, 0) : 2 w_same d) / n, 0 where d0 < 1e-8;  gd = q delta / d0
+//              ga_l = (gd - u (u . gd)) / s_l where ||a_l|| > 1e-12, else gd / 1e-12;  ga_r the same with -gd and v
+//   figures    rows += n, correct += #((dist < accept) == (differ == 0)) on the fp32 dist, loss_q += the fixed point of pair_loss
+//   update     the linear step's on (x, keep, g := ga, row_src) with B := 2P, C := E: dw = ga^T x', db = sum ga, Adam, t += 1 first
+// The float64 sums (||a||^2 of both rows, then ||delta||^2, u . delta, v . delta) are each side's own order, as the softmax sums are:
+// parts in 2^53 before the one rounding, so ga, pair_loss and dist of the two sides differ in a rare last bit at most.  Everything
+// downstream of ga is defined on ga's fp32 bits.
+// PAIR STATE: the single layout for (D, E).  PAIR WORKSPACE (frmap_head_fit_pair_workspace_bytes): fp32 a [2P E], ga [2P E],
+// pair_loss [P], dist [P], then int32 row_src [2P].
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -295,4 +317,91 @@ FRMAP_TRACK_HD inline float frmap_head_fit_da(float s, float h, int kept, float 
 #endif
   if (!counted || !(h > 0.0f) || kept == 0) return 0.0f;
   return kept < 0 ? s : s * keep_scale;
+}
+
+// the pair step (the comment at the top, PAIR)
+constexpr int FRMAP_HEAD_FIT_MAX_P = FRMAP_HEAD_FIT_MAX_B / 2;      // pairs of one step: 2P batch rows
+FRMAP_TRACK_HD inline bool frmap_head_fit_pair_shape_ok(int P, int D, int E) {
+  return frmap_head_fit_shape_ok(D, E) && P >= 1 && P <= FRMAP_HEAD_FIT_MAX_P;
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_pair_workspace_size(int P, int E) {
+  return 4 * (4 * (size_t)P * (size_t)E + 4 * (size_t)P);
+}
+struct FrmapHeadFitPairWork {
+  float *a, *ga, *pair_loss, *dist;
+  int32_t* row_src;
+};
+FRMAP_TRACK_HD inline FrmapHeadFitPairWork frmap_head_fit_pair_work(void* workspace, int P, int E) {
+  FrmapHeadFitPairWork k;
+  const size_t pe2 = 2 * (size_t)P * (size_t)E;
+  k.a = (float*)workspace;
+  k.ga = k.a + pe2;
+  k.pair_loss = k.ga + pe2;
+  k.dist = k.pair_loss + P;
+  k.row_src = (int32_t*)(k.dist + P);
+  return k;
+}
+struct FrmapHeadFitPairHyper {
+  float margin, w_same, w_diff, accept;
+};
+// delta of one element from the two rows' values and norms, with u and v
+FRMAP_TRACK_HD inline double frmap_head_fit_pair_delta(float al, float ar, double sl, double sr, double* u, double* v) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  *u = (double)al / sl;
+  *v = (double)ar / sr;
+  const double uv = *u - *v;
+  return uv + 1e-6;
+}
+// What the elements of a pair share, from the five float64 sums: nl2 = sum a_l^2, nr2 = sum a_r^2, dd = sum delta^2, ud = u . delta,
+// vd = v . delta.  ga_l[e] = cl (delta - u ud) (or cl delta where ||a_l|| <= 1e-12: cl then carries 1 / 1e-12), ga_r[e] = cr (delta - v vd).
+struct FrmapHeadFitPair {
+  double sl, sr, ud, vd, cl, cr;
+  int l_free, r_free;        // the row's norm is above 1e-12: the normalisation has a gradient of its own
+  float loss, dist;
+};
+FRMAP_TRACK_HD inline void frmap_head_fit_pair_norms(double nl2, double nr2, FrmapHeadFitPair* p) {
+  const double l = sqrt(nl2), r = sqrt(nr2);
+  p->l_free = l > 1e-12 ? 1 : 0;
+  p->r_free = r > 1e-12 ? 1 : 0;
+  p->sl = l > 1e-12 ? l : (l == l ? 1e-12 : l);              // max(l, 1e-12); a NaN stays one
+  p->sr = r > 1e-12 ? r : (r == r ? 1e-12 : r);
+}
+FRMAP_TRACK_HD inline void frmap_head_fit_pair_scalars(double dd, double ud, double vd, int differ, uint64_t n, const FrmapHeadFitPairHyper& h,
+                                                       FrmapHeadFitPair* p) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d0 = sqrt(dd);
+  const double d = d0 > 1e-8 ? d0 : (d0 == d0 ? 1e-8 : d0);
+  double loss, q;
+  if (differ) {
+    const double gap = (double)h.margin - d;
+    const double m = gap > 0.0 ? gap : (gap == gap ? 0.0 : gap);
+    loss = (double)h.w_diff * (m * m);
+    q = -2.0 * (double)h.w_diff * m;
+  } else {
+    loss = (double)h.w_same * (d * d);
+    q = 2.0 * (double)h.w_same * d;
+  }
+  q = q / (double)n;
+  const double c = d0 < 1e-8 ? 0.0 : q / d0;
+  p->ud = ud;
+  p->vd = vd;
+  p->cl = c / p->sl;
+  p->cr = -c / p->sr;
+  p->loss = (float)loss;
+  p->dist = (float)d;
+}
+FRMAP_TRACK_HD inline void frmap_head_fit_pair_ga(float al, float ar, const FrmapHeadFitPair& p, float* gl, float* gr) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double u, v;
+  const double delta = frmap_head_fit_pair_delta(al, ar, p.sl, p.sr, &u, &v);
+  const double tl = p.l_free ? delta - u * p.ud : delta;
+  const double tr = p.r_free ? delta - v * p.vd : delta;
+  *gl = (float)(p.cl * tl);
+  *gr = (float)(p.cr * tr);
 }

@@ -7,6 +7,8 @@
 // stride, the hyper table and flag 8 of the device's (frmap_head_fit_group_step_host, tools/head_fit_group_check.cpp).
 // frmap_head_fit_hidden_step_twin is the hidden-layer step (head_fit_rule.h, HIDDEN LAYER): layer 1 by frmap_head_fit_dot, all of
 // layer 2 by this twin on (h, lab, keep2) (frmap_head_fit_hidden_step_host, tools/head_fit_hidden_check.cpp).
+// frmap_head_fit_pair_step_twin is the pair step (head_fit_rule.h, PAIR): the projection and the update by frmap_head_fit_dot, the
+// float64 loss and gradient of every pair in between (frmap_head_fit_pair_step_host, tools/head_fit_pair_check.cpp).
 #pragma once
 #include "head_fit_rule.h"
 
@@ -276,6 +278,129 @@ inline const char* frmap_head_fit_hidden_step_twin(const float* x, const int32_t
     }
     const float db = frmap_head_fit_dot(B, [&](int i) { return dd(i, j); }, [](int) { return 1.0f; });
     frmap_head_fit_adam(a, db, b1 + j, st1.m_b + j, st1.v_b + j, amsgrad ? st1.vmax_b + j : nullptr);
+  }
+  return nullptr;
+}
+
+// what a pair call is refused for: the shared list in its order - N, P (where the others have B: 2P batch rows), D, E (where they have C),
+// the flag bits, the required pointers
+inline const char* frmap_head_fit_pair_refusal(const void* x, const void* left, const void* right, const void* differ, const void* w, const void* b,
+                                               const void* state, const void* workspace, int N, int P, int D, int E, int flags) {
+  const bool p_ok = P >= 1 && P <= FRMAP_HEAD_FIT_MAX_P, e_ok = E >= 1 && E <= FRMAP_HEAD_FIT_MAX_C;
+  if (N >= 1) {
+    if (!p_ok) return "P is outside [1, 2^19]";
+    if (D >= 1 && D <= FRMAP_HEAD_FIT_MAX_D && !e_ok) return "E is outside [1, 65536]";
+  }
+  const void* const required[] = {x, left, right, differ, w, b, state, workspace};
+  return frmap_head_fit_refusal(N, p_ok ? 2 * P : 1, D, e_ok ? E : 1, flags, 7, required, 8,
+                                "null pointer (x, left, right, differ, w, b, state and workspace are required)");
+}
+
+// the row of x that a batch row of the pair step reads through index r, or -1 where it is declined (no label is read)
+inline int32_t frmap_head_fit_pair_row_src(const float* x, int32_t r, int N, int D) {
+  if (r < 0 || r >= N) return -1;
+  for (int k = 0; k < D; ++k) {
+    uint32_t u;
+    __builtin_memcpy(&u, x + (size_t)r * (size_t)D + k, 4);
+    if (!frmap_tally_finite_bits(u)) return -1;
+  }
+  return r;
+}
+
+// The pair step (head_fit_rule.h, PAIR): the projection by frmap_head_fit_dot, the counting, the float64 loss and gradient of every
+// counted pair with serial sums, the figures, then the linear step's gradient GEMM and update on (ga, row_src) over the 2P rows.
+// `given_g`: a, ga, pair_loss and dist of the workspace are INPUTS (the device's own); row_src, n, the figures and the update are
+// computed from them.
+inline const char* frmap_head_fit_pair_step_twin(const float* x, const int32_t* left, const int32_t* right, const int32_t* differ,
+                                                 const uint8_t* keep, float keep_scale, float* w, float* b, void* state, void* workspace, int N,
+                                                 int P, int D, int E, const FrmapHeadFitPairHyper& ph, const FrmapHeadFitHyper& h, int flags,
+                                                 int given_g) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (const char* why = frmap_head_fit_pair_refusal(x, left, right, differ, w, b, state, workspace, N, P, D, E, flags)) return why;
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0, B = 2 * P;
+  const FrmapHeadFitState st = frmap_head_fit_state(state, D, E, amsgrad);
+  const FrmapHeadFitPairWork wk = frmap_head_fit_pair_work(workspace, P, E);
+  if (flags & FRMAP_HEAD_FIT_CLEAR) st.head[FRMAP_HEAD_FIT_ROWS] = st.head[FRMAP_HEAD_FIT_CORRECT] = st.head[FRMAP_HEAD_FIT_LOSS_Q] = 0;
+  for (int i = 0; i < B; ++i) wk.row_src[i] = frmap_head_fit_pair_row_src(x, i < P ? left[i] : right[i - P], N, D);
+  auto xp = [&](int i, int k) -> float {                  // x' of batch row i (declined: +0)
+    const int32_t r = wk.row_src[i];
+    if (r < 0) return 0.0f;
+    return frmap_head_fit_xp(x[(size_t)r * (size_t)D + k], keep ? (int)keep[(size_t)i * (size_t)D + k] : -1, keep_scale);
+  };
+  if (!given_g) {
+    for (int i = 0; i < B; ++i) {                         // (before the gate: a row of an uncounted pair keeps its projection)
+      float* ar = wk.a + (size_t)i * (size_t)E;
+      for (int e = 0; e < E; ++e) {
+        if (wk.row_src[i] < 0) {
+          ar[e] = 0.0f;
+          continue;
+        }
+        const float* we = w + (size_t)e * (size_t)D;
+        const float s = frmap_head_fit_dot(D, [&](int k) { return xp(i, k); }, [&](int k) { return we[k]; });
+        ar[e] = s + b[e];
+      }
+    }
+  }
+  uint64_t n = 0;
+  for (int p = 0; p < P; ++p) {
+    const bool counted = wk.row_src[p] >= 0 && wk.row_src[P + p] >= 0 && (differ[p] == 0 || differ[p] == 1);
+    if (!counted) wk.row_src[p] = wk.row_src[P + p] = -1;
+    n += counted ? 1 : 0;
+  }
+  st.head[FRMAP_HEAD_FIT_N] = n;
+  uint64_t correct = 0, loss_q = 0;
+  for (int p = 0; p < P; ++p) {
+    const float* al = wk.a + (size_t)p * (size_t)E;
+    const float* ar = wk.a + (size_t)(P + p) * (size_t)E;
+    float* gl = wk.ga + (size_t)p * (size_t)E;
+    float* gr = wk.ga + (size_t)(P + p) * (size_t)E;
+    if (wk.row_src[p] < 0) {
+      if (!given_g) {
+        for (int e = 0; e < E; ++e) gl[e] = gr[e] = 0.0f;
+        wk.pair_loss[p] = wk.dist[p] = __builtin_nanf("");
+      }
+      continue;
+    }
+    if (!given_g) {
+      FrmapHeadFitPair pr;
+      double nl2 = 0.0, nr2 = 0.0, dd = 0.0, ud = 0.0, vd = 0.0;
+      for (int e = 0; e < E; ++e) {
+        nl2 = nl2 + (double)al[e] * (double)al[e];
+        nr2 = nr2 + (double)ar[e] * (double)ar[e];
+      }
+      frmap_head_fit_pair_norms(nl2, nr2, &pr);
+      for (int e = 0; e < E; ++e) {
+        double u, v;
+        const double delta = frmap_head_fit_pair_delta(al[e], ar[e], pr.sl, pr.sr, &u, &v);
+        dd = dd + delta * delta;
+        ud = ud + u * delta;
+        vd = vd + v * delta;
+      }
+      frmap_head_fit_pair_scalars(dd, ud, vd, differ[p], n, ph, &pr);
+      for (int e = 0; e < E; ++e) frmap_head_fit_pair_ga(al[e], ar[e], pr, gl + e, gr + e);
+      wk.pair_loss[p] = pr.loss;
+      wk.dist[p] = pr.dist;
+    }
+    correct += ((wk.dist[p] < ph.accept) == (differ[p] == 0)) ? 1 : 0;
+    loss_q += frmap_tally_loss_q(wk.pair_loss[p]);
+  }
+  st.head[FRMAP_HEAD_FIT_ROWS] += n;
+  st.head[FRMAP_HEAD_FIT_CORRECT] += correct;
+  st.head[FRMAP_HEAD_FIT_LOSS_Q] += loss_q;
+  if (n == 0) return nullptr;
+  st.head[FRMAP_HEAD_FIT_T] += 1;
+  const FrmapHeadFitAdam a = frmap_head_fit_adam_scalars(st.head[FRMAP_HEAD_FIT_T], h, flags);
+  auto gg = [&](int i, int e) -> float { return wk.row_src[i] < 0 ? 0.0f : wk.ga[(size_t)i * (size_t)E + e]; };
+  for (int e = 0; e < E; ++e) {
+    for (int d = 0; d < D; ++d) {
+      const float dw = frmap_head_fit_dot(B, [&](int i) { return gg(i, e); }, [&](int i) { return xp(i, d); });
+      const size_t at = (size_t)e * (size_t)D + d;
+      frmap_head_fit_adam(a, dw, w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
+    }
+    const float db = frmap_head_fit_dot(B, [&](int i) { return gg(i, e); }, [](int) { return 1.0f; });
+    frmap_head_fit_adam(a, db, b + e, st.m_b + e, st.v_b + e, amsgrad ? st.vmax_b + e : nullptr);
   }
   return nullptr;
 }

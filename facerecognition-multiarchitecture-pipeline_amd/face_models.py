@@ -546,7 +546,8 @@ class _PySiamesePlan(_PerOpPlan):
     CONVS = ("conv.0", "conv.4", "conv.7", "conv.11", "conv.14", "conv.18")     # step names: the layers' indices in `conv`
     FCS = (("fc.1", "fc1", True), ("fc.5", "fc2", True), ("fc.8", "fc3", False))  # (step name, operand, ReLU): Linear -> BN -> ReLU twice, Linear
 
-    def embedding(self, x: torch.Tensor, rec=None) -> torch.Tensor:
+    def embedding(self, x: torch.Tensor, rec=None, last_fc: int = 3) -> torch.Tensor:
+        """``last_fc=2``: stop before ``fc.8`` and return its fp32 ``[B, 512]`` input (`SiameseNet.fc_hidden_features`)."""
         m, convs, names = self.m, self["convs"], self.CONVS
         u8, img = x.dtype == torch.uint8, x
         Wi = x.shape[2] if u8 else x.shape[3]
@@ -572,10 +573,12 @@ class _PySiamesePlan(_PerOpPlan):
         if rec is not None:
             rec("avgpool6x6", a, ops.avgpool_adaptive, (x,))
         feats = a.view(a.shape[0], -1)
-        for name, key, relu in self.FCS:
+        for name, key, relu in self.FCS[:last_fc]:
             fin, feats = feats, self[key](feats, relu=relu)
             if rec is not None:
                 rec(name, feats, self[key], (fin,))
+        if last_fc < len(self.FCS):
+            return ops.cast_to_f32(feats)
         f32 = ops.cast_to_f32(feats)
         y = ops.l2_normalize(f32, 1e-12)
         if rec is not None:
@@ -623,6 +626,13 @@ class SiameseNet(_HipModule):
 
     def forward(self, x1, x2):
         return self.forward_one(x1), self.forward_one(x2)
+
+    def fc_hidden_features(self, x):
+        """fp32 ``[B, 512]``: the output of ``fc.5`` + BatchNorm + ReLU, the input of the last layer ``fc.8`` - what
+        `head_fit.cache_embeddings(layer="fc_hidden")` caches so that a `head_fit.PairHead` can fit ``fc.8``.  On the per-op plan,
+        whatever the switches say; the model handle is not touched."""
+        x = self._check_input(x)
+        return self._get_plan(per_op=True).embedding(x, last_fc=2)
 
     def get_embedding(self, x):
         return self.forward_one(x)

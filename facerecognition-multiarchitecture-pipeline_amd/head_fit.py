@@ -22,7 +22,14 @@ through a convolution exists here, and none is planned.
   the ReLU, one Adam over the four tensors.  `HiddenHead.embed` is a new embedding layer on a frozen trunk; for ``BaselineNet`` it
   is the model's own ``fc1`` (`cache_features(layer="pooled")`, `fit_head(hidden=512)`, `HiddenHead.load_into`).
 
-Structure: the three steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the seven
+* `pair_step_rule` / `pair_step_host` / `pair_step`, `PairHead`, `draw_pairs`, `cache_embeddings`, `fit_pair_head` - one step of a
+  contrastive projection ``x -> normalize(x w^T + b)`` over PAIRS of cached rows (`frmap_head_fit_pair_step`) with the reference's
+  ``ContrastiveLoss`` (`src/face_models.py:725-774`): the one objective here trained on distances, and so the fit that accepts a siamese
+  model.  ``differ`` is the loss's own label: 1 = different identities, pushed apart.  The reference's ``SiameseDataset`` hands that
+  loss 1 for SAME-class pairs; that is not reproduced - callers derive ``differ`` from identity labels (`draw_pairs`).  For a
+  ``SiameseNet`` the head is its own last layer ``fc.8`` (`cache_embeddings(layer="fc_hidden")`, `PairHead.load_into`).
+
+Structure: the steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the seven
 size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk of the device steps and `_host_cache`, `_host_layer`,
 `_host_batch`, `_host_mask` and `_host_buffers` that of the host steps, after which a step lists its operands once and calls the library;
 `_rule_batch` (declined rows, the masked input) and `_adam_rule` are shared by the numpy rules; `_Head` holds the workspace cache, the
@@ -30,7 +37,7 @@ pending clear and the epoch figures of `LinearHead`, `HeadGroup` and `HiddenHead
 `LinearHead._over` makes a head of views; `fit_head` is one loop over a head and its ``(width, dropout)`` mask specs.
 
 Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
-``ArcMarginProduct``, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
+``ArcMarginProduct``, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
 from __future__ import annotations
 
@@ -343,8 +350,13 @@ def _flags(decoupled, amsgrad, clear) -> int:
 
 
 def _host_cache(op, x, labels):
-    """``(x, labels, N, D)`` of a host step: the cache as contiguous float32 ``[N, D]`` and int32 ``[N]``."""
+    """``(x, labels, N, D)`` of a host step: the cache as contiguous float32 ``[N, D]`` and int32 ``[N]`` (``labels=None``: a step
+    that reads no labels)."""
     x = np.ascontiguousarray(x, dtype=np.float32)
+    if labels is None:
+        if x.ndim != 2:
+            raise ValueError(f"{op}: x [N, D] expected")
+        return x, None, x.shape[0], x.shape[1]
     labels = np.ascontiguousarray(labels, dtype=np.int32)
     if x.ndim != 2 or labels.shape != (x.shape[0],):
         raise ValueError(f"{op}: x [N, D] and labels [N] expected")
@@ -436,12 +448,14 @@ def step_host(x, labels, w, b, state: np.ndarray, workspace: Optional[np.ndarray
 # the step on the device
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _cache(op, entry, x, labels):
-    """``(x, N, D)`` of a device step: the cache ``x`` as the library takes it, float32 ``[N, D]``, with ``labels`` int32 ``[N]``."""
+    """``(x, N, D)`` of a device step: the cache ``x`` as the library takes it, float32 ``[N, D]``, with ``labels`` int32 ``[N]``
+    (``None``: a step that reads no labels)."""
     x = _dev(x, f"{op}.x", torch.float32, (entry, "x"))
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError(f"{op}: x [N, D] expected, got {tuple(x.shape)}")
     N, D = int(x.shape[0]), int(x.shape[1])
-    _sized(labels, op, "labels", (N,), torch.int32)
+    if labels is not None:
+        _sized(labels, op, "labels", (N,), torch.int32)
     return x, N, D
 
 
@@ -640,7 +654,13 @@ def cache_features(model, model_type: str, data, batch_size: int = 256, device="
         raise ValueError(f"head_fit.cache_features: layer must be 'embedding' or 'pooled', got {layer!r}")
     if layer == "pooled" and type(model).__name__ != "BaselineNet":
         raise ValueError(f"head_fit.cache_features: layer='pooled' is BaselineNet's (the input of its fc1), got {type(model).__name__}")
-    embed = model.pooled_features if layer == "pooled" else model.get_embedding
+    return _cache_rows("head_fit.cache_features", model, model.pooled_features if layer == "pooled" else model.get_embedding, data,
+                       batch_size, device)
+
+
+def _cache_rows(op, model, embed, data, batch_size, device):
+    """The loop of `cache_features` and `cache_embeddings`: ``embed`` of every batch of ``data`` in eval mode, as float32 ``[N, D]``
+    with the labels as int32 ``[N]``, both on the device."""
     if model.training:
         model.eval()
     feats, labs = [], []
@@ -650,8 +670,21 @@ def cache_features(model, model_type: str, data, batch_size: int = 256, device="
             feats.append(emb.float().reshape(images.shape[0], -1).clone())
             labs.append(torch.as_tensor(labels).to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).to(device, non_blocking=True))
     if not feats:
-        raise ValueError("head_fit.cache_features: the data set is empty")
+        raise ValueError(f"{op}: the data set is empty")
     return torch.cat(feats).contiguous(), torch.cat(labs).contiguous()
+
+
+def cache_embeddings(model, data, batch_size: int = 256, device="cuda", layer: str = "embedding"):
+    """`cache_features` for a head that needs no classifier - a `PairHead` - and so for a siamese model too: ``[N, D]`` float32 rows and
+    ``[N]`` int32 identity labels on the device.  ``layer="embedding"``: the model's ``get_embedding``; ``layer="fc_hidden"``
+    (``SiameseNet`` only): the ``[N, 512]`` input of its last layer ``fc.8`` (`SiameseNet.fc_hidden_features`), so that a
+    ``PairHead(512, 256)`` fits that layer itself (`PairHead.load_into`)."""
+    if layer not in ("embedding", "fc_hidden"):
+        raise ValueError(f"head_fit.cache_embeddings: layer must be 'embedding' or 'fc_hidden', got {layer!r}")
+    if layer == "fc_hidden" and type(model).__name__ != "SiameseNet":
+        raise ValueError(f"head_fit.cache_embeddings: layer='fc_hidden' is SiameseNet's (the input of its fc.8), got {type(model).__name__}")
+    return _cache_rows("head_fit.cache_embeddings", model, model.fc_hidden_features if layer == "fc_hidden" else model.get_embedding, data,
+                       batch_size, device)
 
 
 def _head_generator(generator):
@@ -1300,3 +1333,313 @@ class HiddenHead(_Head):
             fc1.bias.copy_(self.b1)
             fc2.weight.copy_(self.w2)
             fc2.bias.copy_(self.b2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# a contrastive pair head: pairs of cached rows in, an embedding x -> normalize(x w^T + b) out
+# ---------------------------------------------------------------------------------------------------------------------------------
+MAX_P = MAX_B // 2                # pairs of one step: 2P batch rows
+_PDE_IN = f"P in 1 ... {MAX_P}, D in 1 ... {MAX_D}, E in 1 ... {MAX_C}"
+NORM_EPS, DIST_EPS, DIST_MIN = 1e-12, 1e-6, 1e-8      # F.normalize, F.pairwise_distance, the loss's clamp
+
+
+def pair_state_bytes(D: int, E: int, amsgrad: bool = False) -> int:
+    """Bytes of the state of a pair head (`frmap_head_fit_pair_state_bytes`): `state_bytes` of (D, E)."""
+    return _size("frmap_head_fit_pair_state_bytes", f"D in 1 ... {MAX_D}, E in 1 ... {MAX_C}", "D E", int(D), int(E), int(bool(amsgrad)))
+
+
+def pair_workspace_bytes(P: int, D: int, E: int) -> int:
+    """Bytes of the workspace of a pair step of ``P`` pairs (`frmap_head_fit_pair_workspace_bytes`)."""
+    return _size("frmap_head_fit_pair_workspace_bytes", _PDE_IN, "P D E", int(P), int(D), int(E))
+
+
+def pair_workspace_views(workspace: np.ndarray, P: int, E: int) -> dict:
+    """a [2P, E], ga [2P, E], pair_loss [P], dist [P] (float32) and row_src [2P] (int32) of a host copy of a pair workspace."""
+    raw = np.ascontiguousarray(workspace).view(np.uint8).reshape(-1)
+    nf = 4 * P * E + 2 * P
+    f = raw[: 4 * nf].view(np.float32)
+    return {"a": f[: 2 * P * E].reshape(2 * P, E), "ga": f[2 * P * E: 4 * P * E].reshape(2 * P, E), "pair_loss": f[4 * P * E: 4 * P * E + P],
+            "dist": f[4 * P * E + P:], "row_src": raw[4 * nf: 4 * nf + 8 * P].view(np.int32)}
+
+
+def pair_loss_rule(al, ar, differ, n: int, margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2):
+    """The float64 half of the pair rule (csrc/head_fit_rule.h, PAIR) on rows ``al``, ``ar`` ``[P, E]`` with ``differ`` ``[P]`` in
+    {0, 1}: ``(pair_loss [P], dist [P], ga_l [P, E], ga_r [P, E])`` in float64, the gradients those of ``sum(pair_loss) / n``."""
+    al, ar = np.asarray(al, np.float64), np.asarray(ar, np.float64)
+    dif = np.asarray(differ).astype(bool)
+    with np.errstate(all="ignore"):
+        nl, nr = np.sqrt((al * al).sum(axis=1)), np.sqrt((ar * ar).sum(axis=1))
+        sl, sr = np.maximum(nl, NORM_EPS)[:, None], np.maximum(nr, NORM_EPS)[:, None]
+        u, v = al / sl, ar / sr
+        delta = (u - v) + DIST_EPS
+        d0 = np.sqrt((delta * delta).sum(axis=1))
+        d = np.maximum(d0, DIST_MIN)
+        gap = np.maximum(float(margin) - d, 0.0)
+        loss = np.where(dif, float(w_diff) * gap * gap, float(w_same) * d * d)
+        q = np.where(dif, -2.0 * float(w_diff) * gap, 2.0 * float(w_same) * d) / float(max(n, 1))
+        c = np.where(d0 < DIST_MIN, 0.0, q / np.where(d0 > 0, d0, 1.0))[:, None]
+        ud, vd = (u * delta).sum(axis=1, keepdims=True), (v * delta).sum(axis=1, keepdims=True)
+        gl = (c / sl) * np.where((nl > NORM_EPS)[:, None], delta - u * ud, delta)
+        gr = (-c / sr) * np.where((nr > NORM_EPS)[:, None], delta - v * vd, delta)
+    return loss, d, gl, gr
+
+
+def pair_step_rule(x, left, right, differ, w, b, state: Optional[dict] = None, keep=None, keep_scale: float = 1.0, *, margin: float = 2.0,
+                   w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                   eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
+                   dtype=np.float64, given: Optional[dict] = None) -> dict:
+    """One training step of the pair head, the specification (csrc/head_fit_rule.h, PAIR; include/frmap_hip.h, "Head fitting on pairs").
+
+    ``dtype=np.float64``: the formulas in float64, as torch evaluates ``F.linear`` -> ``F.normalize`` -> ``F.pairwise_distance`` -> the
+    clamp and the two weighted terms -> ``optim.Adam`` / ``AdamW``.  ``dtype=np.float32``: the projection and both update GEMMs by
+    `dot32`, the update by `adam32`, and the loss half in float64 from the float32 ``a`` (and the float32 values of ``margin``,
+    ``w_same``, ``w_diff`` and ``accept``: the library takes them as fp32), rounded once - what the host twin computes,
+    word for word but for a rare last bit of ``ga``, ``pair_loss`` and ``dist`` (the order of the float64 sums).  ``given``: ``{"a",
+    "ga", "pair_loss", "dist"}`` to take as they are.
+
+    Nothing is modified: returns ``{"w", "b", "state", "a", "ga", "pair_loss", "dist", "row_src", "dw", "db", "n", "loss"}``."""
+    f32 = np.dtype(dtype) == np.dtype(np.float32)
+    x = np.asarray(x, F32 if f32 else np.float64)
+    w, b = np.array(w, dtype), np.array(b, dtype)
+    N, D = x.shape
+    E = w.shape[0]
+    left, right, differ = (np.asarray(t).astype(np.int64).reshape(-1) for t in (left, right, differ))
+    P = len(left)
+    st = _copy_state(state or fresh_state(D, E, amsgrad, dtype), dtype)
+    if clear:
+        st["rows"] = st["correct"] = st["loss_q"] = 0
+    if f32:                                                           # (the library takes them as fp32 and widens those values)
+        margin, w_same, w_diff = (float(F32(v)) for v in (margin, w_same, w_diff))
+    idx = np.concatenate([left, right])
+    row_ok = np.array([0 <= r < N and bool(np.isfinite(x[r]).all()) for r in idx])
+    src = np.where(row_ok, idx, -1).astype(np.int32)
+
+    def masked(ok):
+        xp = np.zeros((2 * P, D), x.dtype)
+        xp[ok] = x[src[ok]]
+        if keep is not None:
+            scaled = (xp * F32(keep_scale)).astype(F32) if f32 else xp * float(keep_scale)
+            xp = np.where(np.asarray(keep).astype(bool), scaled, 0).astype(x.dtype)
+            xp[~ok] = 0
+        return xp
+    with np.errstate(all="ignore"):
+        if given is not None:
+            a = np.array(given["a"], dtype)
+        else:
+            xr = masked(row_ok)
+            a = (dot32(xr[:, None, :], w[None, :, :]) + b[None, :]).astype(F32) if f32 else xr @ w.T + b[None, :]
+            a[~row_ok] = 0
+    pair_ok = row_ok[:P] & row_ok[P:] & ((differ == 0) | (differ == 1))
+    ok = np.concatenate([pair_ok, pair_ok])
+    row_src = np.where(ok, src, -1).astype(np.int32)
+    n = int(pair_ok.sum())
+    st["n"] = n
+    if given is not None:
+        ga, pair_loss, dist = (np.array(given[k], dtype) for k in ("ga", "pair_loss", "dist"))
+    else:
+        loss64, d64, gl, gr = pair_loss_rule(a[:P], a[P:], differ == 1, n, margin, w_same, w_diff)
+        ga = np.concatenate([gl, gr]).astype(dtype)
+        ga[~ok] = 0
+        pair_loss, dist = loss64.astype(dtype), d64.astype(dtype)
+        pair_loss[~pair_ok] = np.nan
+        dist[~pair_ok] = np.nan
+    acc = F32(accept) if f32 else float(accept)
+    st["rows"] += n
+    st["correct"] += int((pair_ok & ((dist < acc) == (differ == 0))).sum())
+    st["loss_q"] += loss_q(pair_loss[pair_ok])
+    xp = masked(ok)
+    gz = np.where(ok[:, None], ga, 0).astype(dtype)
+    with np.errstate(all="ignore"):
+        if f32:
+            dw = dot32(gz.T[:, None, :], xp.T[None, :, :])
+            db = dot32(gz.T, np.ones((1, 2 * P), F32))
+        else:
+            dw, db = gz.T @ xp, gz.sum(axis=0)
+    out = {"a": a, "ga": ga, "pair_loss": pair_loss, "dist": dist, "row_src": row_src, "dw": dw, "db": db, "n": n,
+           "loss": float(pair_loss[pair_ok].astype(np.float64).mean()) if n else float("nan")}
+    if n:
+        st["t"] += 1
+        kw = dict(t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
+                  f32=f32)
+        w, b = _adam_rule(w, dw, st, "w", **kw), _adam_rule(b, db, st, "b", **kw)
+    out["w"], out["b"], out["state"] = w, b, st
+    return out
+
+
+def pair_step_host(x, left, right, differ, w, b, state: np.ndarray, workspace: Optional[np.ndarray] = None, keep=None, keep_scale: float = 1.0, *,
+                   margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5, lr: float = 1e-3, beta1: float = 0.9,
+                   beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+                   clear: bool = False, given_g: bool = False):
+    """The pair step on the CPU over numpy arrays (`frmap_head_fit_pair_step_host`; no GPU).  ``w`` [E, D], ``b`` [E] (float32) and
+    ``state`` (uint8, `pair_state_bytes` bytes, 8-byte aligned) are updated IN PLACE; ``workspace`` (uint8, exactly
+    `pair_workspace_bytes` bytes, or ``None`` for a fresh one) receives a, ga, pair_loss, dist and row_src - with ``given_g`` its a, ga,
+    pair_loss and dist are inputs.  Returns the workspace."""
+    op = "head_fit.pair_step_host"
+    x, _, N, D = _host_cache(op, x, None)
+    E, = _host_layer(op, "w", "b", w, b, "", "E", D)
+    left, right, differ = (np.ascontiguousarray(t, dtype=np.int32) for t in (left, right, differ))
+    if left.ndim != 1 or right.shape != left.shape or differ.shape != left.shape:
+        raise ValueError(f"{op}: left [P], right [P] and differ [P] expected, got {left.shape}, {right.shape} and {differ.shape}")
+    P = len(left)
+    keep = _host_mask(op, "keep", keep, (2 * P, D))
+    workspace = _host_buffers(op, state, pair_state_bytes(D, E, amsgrad), workspace, pair_workspace_bytes(P, D, E), given_g)
+    _lib.check(_lib.load().frmap_head_fit_pair_step_host(
+        _at(x), _at(left), _at(right), _at(differ), _at(keep), float(keep_scale), _at(w), _at(b), _at(state), _at(workspace), N, P, D, E,
+        float(margin), float(w_same), float(w_diff), float(accept), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
+    return workspace
+
+
+@ops._on_operand_device
+def pair_step(x: torch.Tensor, left: torch.Tensor, right: torch.Tensor, differ: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
+              state: torch.Tensor, workspace: torch.Tensor, keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, *,
+              margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5, lr: float = 1e-3, beta1: float = 0.9,
+              beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+              clear: bool = False) -> None:
+    """One pair training step on the current stream (`frmap_head_fit_pair_step`; nothing is copied or synchronised).  ``x`` float32
+    ``[N, D]`` (the cache), ``left`` / ``right`` int32 ``[P]`` rows of it, ``differ`` int32 ``[P]`` (0: the same identity, 1: different),
+    ``w`` float32 ``[E, D]`` and ``b`` ``[E]`` (updated in place), ``state`` uint8 of `pair_state_bytes` bytes (zeros = fresh),
+    ``workspace`` uint8 of exactly `pair_workspace_bytes` bytes, ``keep`` uint8 ``[2P, D]`` or ``None``.  Every extent that depends on
+    another operand is checked here, before the library sees a pointer."""
+    op, entry = "head_fit.pair_step", "frmap_head_fit_pair_step"
+    x, N, D = _cache(op, entry, x, None)
+    E = _layer(w, b, op, "w", "b", D)
+    if not isinstance(left, torch.Tensor) or left.dim() != 1:
+        raise ValueError(f"{op}: left [P] expected, got {tuple(left.shape) if isinstance(left, torch.Tensor) else type(left).__name__}")
+    P = int(left.shape[0])
+    _sized(left, op, "left", (P,), torch.int32)
+    _sized(right, op, "right", (P,), torch.int32)
+    _sized(differ, op, "differ", (P,), torch.int32)
+    if keep is not None:
+        _sized(keep, op, "keep", (2 * P, D), torch.uint8)
+    _sized(state, op, "state", (pair_state_bytes(D, E, amsgrad),), torch.uint8)
+    _sized(workspace, op, "workspace", (pair_workspace_bytes(P, D, E),), torch.uint8)
+    left, right, differ = (_operand(t, op, entry, k, torch.int32) for t, k in ((left, "left"), (right, "right"), (differ, "differ")))
+    keep = _operand(keep, op, entry, "keep", torch.uint8)
+    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _lib.check(_lib.load().frmap_head_fit_pair_step(
+        x.data_ptr(), left.data_ptr(), right.data_ptr(), differ.data_ptr(), _dev_at(keep), float(keep_scale), w.data_ptr(), b.data_ptr(),
+        state.data_ptr(), workspace.data_ptr(), N, P, D, E, float(margin), float(w_same), float(w_diff), float(accept), float(lr), float(beta1),
+        float(beta2), float(eps), float(weight_decay), _flags(decoupled, amsgrad, clear), _stream()), op)
+
+
+class PairHead(_Head):
+    """A contrastive projection ``x -> normalize(x w^T + b)``, ``[E, D]``, on the device with its Adam state and a workspace: the last
+    layer ``fc.8`` of the reference's ``SiameseNet`` over its hidden features, or a learned projection of any cached embedding, fitted
+    on pairs with the reference's ``ContrastiveLoss``.  ``weight`` / ``bias`` are drawn as a ``LinearHead(D, E)``'s would be.  `embed`
+    feeds `matching.Gallery`, `evaluate.verification_metrics`, `frames.identify_streams` and `matching.compare_faces`."""
+
+    def __init__(self, D: int, E: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
+        self.D, self.E, self.amsgrad = int(D), int(E), bool(amsgrad)
+        nbytes = pair_state_bytes(self.D, self.E, self.amsgrad)          # (refuses a bad shape)
+        w, b = _linear_init(self.E, self.D, generator)
+        device = torch.device(device)
+        self.weight, self.bias = w.to(device), b.to(device)
+        self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
+
+    def _workspace_bytes(self, P: int) -> int:
+        return pair_workspace_bytes(P, self.D, self.E)
+
+    def step(self, x: torch.Tensor, left: torch.Tensor, right: torch.Tensor, differ: torch.Tensor, keep: Optional[torch.Tensor] = None, *,
+             lr: float, margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5,
+             keep_scale: Optional[float] = None, dropout: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+             weight_decay: float = 0.0, decoupled: bool = False) -> "PairHead":
+        """One step over the pairs ``(left[p], right[p])`` of rows of the cache ``x`` (`pair_step`); ``differ[p]`` is 1 where the two
+        rows are of different identities.  ``keep``: a uint8 ``[2P, D]`` dropout mask (the left rows, then the right rows), scaled by
+        ``keep_scale`` (default ``1 / (1 - dropout)``).  The defaults are the reference's loss (margin 2.0, 0.8 on same pairs, 1.2 on
+        different ones) and its accept rule (distance below 0.5).  No synchronisation."""
+        if keep_scale is None:
+            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
+        P = int(left.shape[0]) if isinstance(left, torch.Tensor) and left.dim() == 1 else 1
+        return self._run(pair_step, x, left, right, differ, self.weight, self.bias, self.state, self._workspace(P), keep, keep_scale,
+                         margin=margin, w_same=w_same, w_diff=w_diff, accept=accept, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                         weight_decay=weight_decay, decoupled=decoupled)
+
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """``normalize(x w^T + b)``: the unit-norm embedding of cached-feature rows ``x`` ``[B, D]``."""
+        return ops.l2_normalize(ops.linear_f32(x, self.weight, None, self.bias), 1e-12)
+
+    def state_dict(self) -> dict:
+        return {"weight": self.weight.detach().clone(), "bias": self.bias.detach().clone()}
+
+    def load_into(self, model) -> None:
+        """Copy the head into ``fc.8`` of a ``SiameseNet`` in place - a ``[256, 512]`` head over `SiameseNet.fc_hidden_features` (the
+        model's plan watches the parameters' versions: the next forward rebuilds)."""
+        fc = getattr(model, "fc", None)
+        if type(model).__name__ != "SiameseNet" or not isinstance(fc, torch.nn.Sequential):
+            raise ValueError(f"PairHead.load_into: a SiameseNet expected, got {type(model).__name__}")
+        if tuple(fc[8].weight.shape) != (self.E, self.D):
+            raise ValueError(f"PairHead.load_into: fc.8 is {list(fc[8].weight.shape)}, the head is {[self.E, self.D]}")
+        with torch.no_grad():
+            fc[8].weight.copy_(self.weight)
+            fc[8].bias.copy_(self.bias)
+
+
+def draw_pairs(labels: torch.Tensor, P: int, generator: Optional[torch.Generator] = None):
+    """``(left, right, differ)``, int32 ``[P]`` on ``labels``' device, with no host copy: ``P`` anchors uniform over the rows; each gets,
+    with probability 1/2, a partner uniform among the OTHER rows of its class (``differ = 0``), and otherwise - or when its class has
+    one member, where the reference's sampler would spin - a partner uniform among the rows of other classes (``differ = 1``).  The
+    labels are sorted once and everything else is arithmetic on class offsets.  ``left != right`` always; with a single class every
+    pair is a same pair.  ``generator`` lives on ``labels``' device."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.is_floating_point():
+        raise ValueError("head_fit.draw_pairs: labels must be an integer tensor [N]")
+    N, P, dev = int(labels.shape[0]), int(P), labels.device
+    if N < 2 or P < 1:
+        raise ValueError(f"head_fit.draw_pairs: at least two rows and one pair expected, got N = {N}, P = {P}")
+    sl, order = torch.sort(labels.to(torch.int64), stable=True)
+    pos = torch.arange(N, device=dev)
+    first = torch.ones((N,), dtype=torch.bool, device=dev)
+    first[1:] = sl[1:] != sl[:-1]
+    last = torch.ones((N,), dtype=torch.bool, device=dev)
+    last[:-1] = first[1:]
+    start = torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), 0).values               # of the class of every sorted position
+    end = torch.flip(torch.cummin(torch.flip(torch.where(last, pos + 1, torch.full_like(pos, N)), (0,)), 0).values, (0,))
+    anchor = torch.randint(0, N, (P,), device=dev, generator=generator)
+    u = torch.rand((3, P), device=dev, generator=generator, dtype=torch.float64)
+    s, cnt = start[anchor], (end - start)[anchor]
+    others = N - cnt
+    same = ((u[0] < 0.5) & (cnt > 1)) | (others == 0)
+    k_same = torch.minimum((u[1] * (cnt - 1)).to(torch.int64), (cnt - 2).clamp(min=0))
+    p_same = s + k_same
+    p_same = p_same + (p_same >= anchor).to(torch.int64)                                          # (skip the anchor itself)
+    k_diff = torch.minimum((u[2] * others).to(torch.int64), (others - 1).clamp(min=0))
+    p_diff = torch.where(k_diff < s, k_diff, k_diff + cnt)                                        # (skip the anchor's class)
+    partner = torch.where(same, p_same, p_diff).clamp(0, N - 1)
+    return order[anchor].to(torch.int32), order[partner].to(torch.int32), (~same).to(torch.int32)
+
+
+def fit_pair_head(model, train_data, val_data=None, epochs: int = 10, batch_pairs: int = 32, lr: float = 1e-3, weight_decay: float = 1e-4,
+                  dropout: float = 0.0, margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5,
+                  layer: str = "embedding", embed_dim: Optional[int] = None, decoupled: bool = False, amsgrad: bool = False,
+                  generator: Optional[torch.Generator] = None, device="cuda"):
+    """Fit a `PairHead` on the frozen model's features with the reference's contrastive objective (`src/training.py:484-490`).  The
+    training set is embedded once (`cache_embeddings`); every step then draws ``batch_pairs`` pairs (`draw_pairs`) and, with
+    ``dropout``, a mask on the device, ``ceil(N / batch_pairs)`` steps an epoch with no host copy inside it; the epoch's figures are one
+    64-byte copy at its end.  With ``val_data`` every epoch's `evaluate.verification_metrics` of ``head.embed`` on the validation
+    rows.  ``layer="fc_hidden"`` (a ``SiameseNet``): the cache is the input of its ``fc.8`` and the head ``[256, 512]``, that layer
+    itself (`PairHead.load_into`); otherwise the head projects the model's embedding to ``embed_dim`` (default: its own width).
+    Returns ``(head, history)`` with ``history = {"train_loss": [...], "train_acc": [...], "val": [metrics dict per epoch]}``."""
+    from . import evaluate
+    feats, labels = cache_embeddings(model, train_data, device=device, layer=layer)
+    N, D = int(feats.shape[0]), int(feats.shape[1])
+    E = int(embed_dim) if embed_dim is not None else (256 if layer == "fc_hidden" else D)
+    head_gen, dev_gen = _generators(generator, feats.device)
+    head = PairHead(D, E, feats.device, amsgrad=amsgrad, generator=head_gen)
+    val = cache_embeddings(model, val_data, device=device, layer=layer) if val_data is not None else None
+    P = int(batch_pairs)
+    history = {"train_loss": [], "train_acc": [], "val": []}
+    for _ in range(int(epochs)):
+        head.new_epoch()
+        for _ in range((N + P - 1) // P):
+            left, right, differ = draw_pairs(labels, P, dev_gen)
+            keep = (torch.rand((2 * P, D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
+            head.step(feats, left, right, differ, keep, lr=lr, margin=margin, w_same=w_same, w_diff=w_diff, accept=accept, dropout=dropout,
+                      weight_decay=weight_decay, decoupled=decoupled)
+        fig = head.epoch_figures()
+        history["train_loss"].append(fig["loss"])
+        history["train_acc"].append(fig["accuracy"])
+        if val is not None:
+            history["val"].append(evaluate.verification_metrics(head.embed(val[0]), val[1]))
+    return head, history

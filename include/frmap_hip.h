@@ -765,6 +765,56 @@ int frmap_head_fit_hidden_step_host(const float* x_host, const int32_t* labels_h
                                     int C, float lr, float beta1, float beta2, float eps, float weight_decay, float label_smoothing,
                                     int flags, int given_g);
 
+/* Head fitting on pairs: one training step of a contrastive head x -> normalize(x w^T + b) over PAIRS of cached rows - the objective
+ * of the reference's Siamese family (ContrastiveLoss(margin 2.0, pos_weight 1.2, neg_weight 0.8), src/face_models.py:725-774) with the
+ * trunk frozen; for a SiameseNet w and b are its own last layer fc.8.  One small memset and four launches on the caller's stream,
+ * nothing copied to the host, nothing allocated, no floating-point atomic.
+ *
+ * Operands: x [N][D] fp32 (the cache); left [P], right [P] int32 rows of x; differ [P] int32: 0 = the same identity (pulled
+ * together), 1 = different identities (pushed apart up to margin) - the loss's own meaning of its label (the reference's
+ * SiameseDataset hands it 1 for SAME-class pairs; callers here derive differ from identity labels); keep [2P][D] uint8 or NULL with
+ * keep_scale (a dropout mask over the 2P batch rows); w [E][D], b [E] fp32, updated in place; margin, w_same (the weight of a
+ * differ = 0 pair), w_diff (of a differ = 1 pair), accept (the distance below which a pair counts as accepted in the figures).
+ * flags: 1 | 2 | 4 as in frmap_head_fit_step.
+ * The rule (dot products are the single step's: fmaf chains from +0 cut at the multiples of 128, the chains added ascending):
+ *   batch    : 2P rows; row i < P reads left[i], row P + i reads right[i].  A row whose index is outside [0, N) or any of whose D
+ *              features is NaN or an infinity is declined.
+ *   a[i][e]  = dot_k(x'[i][k], w[e][k]) + b[e], the bias last; the a row of a declined row is +0
+ *   counted  : pair p is counted iff both of its rows are and differ[p] is 0 or 1; n counts them, on the device.  An uncounted pair
+ *              has row_src = -1 on both its rows, +0 rows of ga and NaN in pair_loss and dist.  n == 0 changes no weight and no
+ *              moment and does not advance t.
+ *   per counted pair, in float64 from the fp32 a and rounded to fp32 once:
+ *              s = max(||a||, 1e-12), u = a_l / s_l, v = a_r / s_r;  delta = (u - v) + 1e-6, d0 = ||delta||, d = max(d0, 1e-8)
+ *              pair_loss = differ ? w_diff max(margin - d, 0)^2 : w_same d^2;  dist = d
+ *              q = (differ ? -2 w_diff max(margin - d, 0) : 2 w_same d) / n, 0 where d0 < 1e-8;  gd = q delta / d0
+ *              ga_l = (gd - u (u . gd)) / s_l where ||a_l|| > 1e-12, else gd / 1e-12;  ga_r the same with -gd and v
+ *   figures  : rows += n, correct += #((dist < accept) == (differ == 0)) on the fp32 dist, loss_q += the fixed point of pair_loss
+ *   update   : dw = ga^T x' over the 2P rows, db = sum ga, Adam / AdamW: the single step's update with B := 2P, C := E.
+ * Launches: the memset of n (with 4: the figures); forward (the logits tile walk, identity epilogue, no labels: a, row_src); gate
+ * (a thread per pair: marks uncounted pairs, one integer atomic per wavefront into n); pair (a wavefront per pair: float64 wavefront
+ * sums, ga, pair_loss, dist; at most two integer atomics per workgroup; advances t when n > 0); the single step's update kernel.
+ * state : frmap_head_fit_pair_state_bytes bytes = the single step's layout for (D, E), zeroed by the caller before the first step.
+ * workspace : exactly frmap_head_fit_pair_workspace_bytes bytes: fp32 a [2P][E], ga [2P][E], pair_loss [P], dist [P], int32
+ *         row_src [2P].  D does not enter the size.
+ * The size queries take no stream and return 0 for arguments the launcher would refuse.
+ * Refused (-1, the text names the argument): N < 1; P < 1 or above 2^19 (2P batch rows); D or E < 1 or above 65536; flag bits above
+ * 7; a required pointer that is NULL.
+ * Every pointer is walked element by element: x, left, right, differ, w, b and workspace need their element size (4), keep 1,
+ * state the size of a uint64 counter (8).
+ * The host form is the same step compiled for the CPU (host pointers, no stream); given_g != 0 takes a, ga, pair_loss and dist of the
+ * workspace as INPUTS - the device's own - and computes row_src, n, the figures, dw, db and the update from them. */
+size_t frmap_head_fit_pair_state_bytes(int D, int E, int amsgrad);
+size_t frmap_head_fit_pair_workspace_bytes(int P, int D, int E);
+int frmap_head_fit_pair_step(const float* x, const int32_t* left, const int32_t* right, const int32_t* differ, const uint8_t* keep,
+                             float keep_scale, float* w, float* b, void* state, void* workspace, int N, int P, int D, int E,
+                             float margin, float w_same, float w_diff, float accept, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int flags, void* stream);
+int frmap_head_fit_pair_step_host(const float* x_host, const int32_t* left_host, const int32_t* right_host, const int32_t* differ_host,
+                                  const uint8_t* keep_host, float keep_scale, float* w_host, float* b_host, void* state_host,
+                                  void* workspace_host, int N, int P, int D, int E, float margin, float w_same, float w_diff,
+                                  float accept, float lr, float beta1, float beta2, float eps, float weight_decay, int flags,
+                                  int given_g);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
