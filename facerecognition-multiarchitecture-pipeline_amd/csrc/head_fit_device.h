@@ -1,5 +1,5 @@
 // The device code that the head-fitting translation units share (head_fit.hip: the linear step and its groups; head_fit_hidden.hip:
-// the hidden-layer step; head_fit_pair.hip: the pair step): the tile walk of both GEMMs, its operand loaders and the bodies of the three
+// the hidden-layer step; head_fit_pair.hip: the pair step; head_fit_margin.hip: the margin step): the tile walk of both GEMMs, its operand loaders and the bodies of the three
 // kernels.  The kernels themselves (`__global__`) stay with their launchers: a code object holds the kernels of ONE of the files, so
 // adding a kernel to one file leaves the other files' code objects - LDS layout, register allocation, instructions - as they are.
 #pragma once
@@ -198,7 +198,8 @@ struct HfUpdateOp {
 // counted into any state.
 // HF_PAIR_ROWS: the forward of the pair step (head_fit_pair.hip) - no label is read or checked, the identity epilogue, nothing counted;
 // batch row i reads rows[i] below `split` and rows_hi[i - split] from there on.  (MODE was a bool: false / true still name the first two.)
-constexpr int HF_LINEAR = 0, HF_HIDDEN = 1, HF_PAIR_ROWS = 2;
+// HF_MARGIN: the forward of the margin step (head_fit_margin.hip) - HF_LINEAR's labels, row_src and count of n, but no bias is read or added.
+constexpr int HF_LINEAR = 0, HF_HIDDEN = 1, HF_PAIR_ROWS = 2, HF_MARGIN = 3;
 template <int MODE>
 __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, const int32_t* __restrict__ labels, const int32_t* __restrict__ rows,
                                                const uint8_t* __restrict__ keep, float keep_scale, const float* __restrict__ w,
@@ -241,6 +242,7 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
     if (b0 + i < B && c0 + j < C) {
       const bool declined = s_src[i] < 0 || s_bad[i] != 0;
       if (HIDDEN) z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : frmap_head_fit_relu(tot[q] + b[c0 + j]);
+      else if (MODE == HF_MARGIN) z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : tot[q];
       else z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : tot[q] + b[c0 + j];
     }
   }
@@ -360,6 +362,44 @@ __device__ __forceinline__ void hf_update_body(const float* __restrict__ x, cons
     if (c < C && d < D) {
       const size_t at = (size_t)c * (size_t)D + d;
       frmap_head_fit_adam(a, tot[q], w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
+    }
+  }
+}
+
+// The update of the margin step (head_fit_rule.h, MARGIN): the tile (c0, d0) of w as in hf_update_body - the chains A = dot_i(g, x') -,
+// then the one-column chain k = dot_i(h, 1) of the tile's 32 classes (every D-tile of a class row repeats it: B x 32 reads instead of a
+// launch and a dependency across tiles; thread (i, 0) holds k of class c0 + i and hands it to its row through LDS), the combination
+// frmap_head_fit_margin_dw with rw and Adam.  There is no bias and no bias column of workgroups.
+__device__ __forceinline__ void hf_margin_update_body(const float* __restrict__ x, const uint8_t* __restrict__ keep, float keep_scale,
+                                                      float* __restrict__ w, void* state, const float* __restrict__ g, const float* __restrict__ hm,
+                                                      const float* __restrict__ rw, const int32_t* __restrict__ row_src, int B, int D, int C,
+                                                      const FrmapHeadFitHyper& h, int flags) {
+  __shared__ HfSmem sm;
+  __shared__ float s_k[HF_T];
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
+  const FrmapHeadFitState st = frmap_head_fit_state(state, D, C, amsgrad);
+  if (st.head[FRMAP_HEAD_FIT_N] == 0) return;                      // every row declined: no weight, no moment changes (uniform)
+  const FrmapHeadFitAdam a = frmap_head_fit_adam_scalars(st.head[FRMAP_HEAD_FIT_T], h, flags);
+  const int tid = threadIdx.x;
+  const int d0 = blockIdx.x * HF_T, c0 = blockIdx.y * HF_T;
+  const int vi = C - c0 < HF_T ? C - c0 : HF_T, vj = D - d0 < HF_T ? D - d0 : HF_T;
+  float tot[4], kk[4];
+  const HfUpdateOp op = {x, keep, g, row_src, keep_scale, c0, d0, D, C, 0};
+  hf_tile_chains<false, false>(sm, B, vi < HF_T || vj < HF_T, vi, vj, op, tot);
+  const HfUpdateOp ones = {x, keep, hm, row_src, keep_scale, c0, 0, D, C, 1};
+  hf_tile_chains<false, false>(sm, B, vi < HF_T, vi, 1, ones, kk);
+  if ((tid & 31) == 0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s_k[(tid >> 5) + 8 * q] = kk[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = (tid >> 5) + 8 * q, c = c0 + i, d = d0 + (tid & 31);
+    if (c < C && d < D) {
+      const size_t at = (size_t)c * (size_t)D + d;
+      const float dw = frmap_head_fit_margin_dw(tot[q], s_k[i], rw[c], w[at]);
+      frmap_head_fit_adam(a, dw, w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
     }
   }
 }

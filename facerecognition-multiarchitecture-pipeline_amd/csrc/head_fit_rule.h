@@ -86,6 +86,30 @@
 // downstream of ga is defined on ga's fp32 bits.
 // PAIR STATE: the single layout for (D, E).  PAIR WORKSPACE (frmap_head_fit_pair_workspace_bytes): fp32 a [2P E], ga [2P E],
 // pair_loss [P], dist [P], then int32 row_src [2P].
+//
+// MARGIN (frmap_head_fit_margin_step; head_fit.margin_step_rule in numpy).  The class centres w [C, D] of an ArcFace margin head
+// (the reference's ArcMarginProduct, src/face_models.py:297-429) under softmax cross-entropy: x, labels, rows, keep / keep_scale and the
+// declined rows are the linear step's; there is NO bias.  The scalars are s (the effective scale), m (the effective margin: the
+// schedule that produces them is host code, head_fit.margin_schedule), ls and the Adam scalars; FRMAP_HEAD_FIT_EASY_MARGIN (bit 16 of
+// `flags`) selects the easy margin.
+//   z[i][c]  = dot_k(x'[i][k], w[c][k])                                 chain order over D, no bias; a declined row is +0
+//   rx[i]    = fp32(1 / max(||x'_i||, 1e-12)), rw[c] = fp32(1 / max(||w_c||, 1e-12)): the squared norms are FLOAT64 sums of the fp32
+//              elements (each side's own order), the reciprocal rounded to fp32 once; rx of a declined row is +0.  Everything below
+//              is defined on the fp32 bits of z, rx and rw, in FLOAT64 up to the one rounding of cosv, g, h and the row loss.
+//   cos      = (z rx[i]) rw[c];  cs = clamp(cos, LO, HI), inside = LO <= cos <= HI, with LO, HI the fp32 roundings of -+(1 - 1e-7)
+//   target y : theta = acos(cs);  standard: theta + m >= CAP ? (out = cos(CAP), dfac = 0)
+//                                                            : (out = cos(theta + m), dfac = inside sin(theta + m) / sin(theta)), CAP the
+//              fp32 value of pi - 1e-4 (a NaN is not capped and stays one);
+//              easy margin: cs > 0 ? (out = cos(theta + m), dfac as above) : (out = cs, dfac = inside).  Others: out = cs, dfac = inside.
+//   l        = s out;  pred = the first arg-max of l;  softmax, -log p and the row loss from l as the linear step forms them from z
+//   q        = (s (p - y)) / n;  gcos = q dfac;  g[i][c] = fp32(gcos rx[i]), h[i][c] = fp32(gcos cos)      (declined: +0 rows)
+//   cosv     = fp32(cs)                                                  (for inspection; nothing reads it)
+//   dw[c][d] = fl(fl(rw[c] A) - fl(fl(fl(rw[c] rw[c]) k[c]) w[c][d])), A = dot_i(g[i][c], x'[i][d]), k[c] = dot_i(h[i][c], 1); the
+//              second term is absent where rw[c] is not below fp32(1e12), the reciprocal of the clamped norm (torch's clamp_min passes
+//              no gradient there)
+//   update     frmap_head_fit_adam on every w[c][d], t += 1 first; figures as in the linear step.  n == 0: only the workspace is written.
+// MARGIN STATE: the single layout for (D, C); the bias moments stay zero.  MARGIN WORKSPACE (frmap_head_fit_margin_workspace_bytes):
+// fp32 z [B C], cosv [B C], g [B C], h [B C], row_loss [B], rx [B], rw [C], then int32 row_src [B].
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -404,4 +428,104 @@ FRMAP_TRACK_HD inline void frmap_head_fit_pair_ga(float al, float ar, const Frma
   const double tr = p.r_free ? delta - v * p.vd : delta;
   *gl = (float)(p.cl * tl);
   *gr = (float)(p.cr * tr);
+}
+
+// the margin step (the comment at the top, MARGIN)
+constexpr int FRMAP_HEAD_FIT_EASY_MARGIN = 16;           // bit of `flags`, margin step only
+constexpr float FRMAP_HEAD_FIT_MARGIN_HI = (float)(1.0 - 1e-7);                  // the clamp bound of the cosine, as fp32
+constexpr float FRMAP_HEAD_FIT_MARGIN_CAP = (float)(3.14159265358979323846 - 1e-4);   // the largest theta + m, as fp32
+constexpr float FRMAP_HEAD_FIT_MARGIN_RMAX = (float)(1.0 / 1e-12);               // the reciprocal of a clamped norm
+FRMAP_TRACK_HD inline size_t frmap_head_fit_margin_workspace_size(int B, int C) {
+  return 4 * (4 * (size_t)B * (size_t)C + 3 * (size_t)B + (size_t)C);
+}
+struct FrmapHeadFitMarginWork {
+  float *z, *cosv, *g, *h, *row_loss, *rx, *rw;
+  int32_t* row_src;
+};
+FRMAP_TRACK_HD inline FrmapHeadFitMarginWork frmap_head_fit_margin_work(void* workspace, int B, int C) {
+  FrmapHeadFitMarginWork k;
+  const size_t bc = (size_t)B * (size_t)C;
+  k.z = (float*)workspace;
+  k.cosv = k.z + bc;
+  k.g = k.cosv + bc;
+  k.h = k.g + bc;
+  k.row_loss = k.h + bc;
+  k.rx = k.row_loss + B;
+  k.rw = k.rx + B;
+  k.row_src = (int32_t*)(k.rw + C);
+  return k;
+}
+// 1 / max(sqrt(sq), 1e-12) from the float64 sum of squares of a row, rounded to fp32 once
+FRMAP_TRACK_HD inline float frmap_head_fit_margin_rnorm(double sq) {
+  const double r = sqrt(sq);
+  return (float)(1.0 / (r > 1e-12 ? r : (r == r ? 1e-12 : r)));
+}
+// the cosine of one element before the clamp
+FRMAP_TRACK_HD inline double frmap_head_fit_margin_cos(float z, float rx, float rw) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double a = (double)z * (double)rx;
+  return a * (double)rw;
+}
+// the clamped cosine; *inside: the clamp passes a gradient (bounds included).  A NaN stays one, outside.
+FRMAP_TRACK_HD inline double frmap_head_fit_margin_clamp(double c, int* inside) {
+  const double hi = (double)FRMAP_HEAD_FIT_MARGIN_HI, lo = -hi;
+  *inside = (c >= lo && c <= hi) ? 1 : 0;
+  return c < lo ? lo : (c > hi ? hi : c);
+}
+// out and dfac of the TARGET element of a row from its clamped cosine
+FRMAP_TRACK_HD inline void frmap_head_fit_margin_target(double cs, int inside, float m, int easy, double* out, double* dfac) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double in = inside ? 1.0 : 0.0;
+  if (easy && !(cs > 0.0)) {
+    *out = cs;
+    *dfac = in;
+    return;
+  }
+  const double theta = acos(cs);
+  const double tm = theta + (double)m;
+  if (!easy && tm >= (double)FRMAP_HEAD_FIT_MARGIN_CAP) {                // (a NaN is not capped: it stays one, as torch.minimum keeps it)
+    *out = cos((double)FRMAP_HEAD_FIT_MARGIN_CAP);
+    *dfac = 0.0;
+    return;
+  }
+  *out = cos(tm);
+  const double ratio = sin(tm) / sin(theta);
+  *dfac = in * ratio;
+}
+// the logit of one element: the target's `out_y`, else the clamped cosine, times s
+FRMAP_TRACK_HD inline double frmap_head_fit_margin_logit(double cs, bool target, double out_y, float s) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return (double)s * (target ? out_y : cs);
+}
+// g and h of one element: e = exp(l - max), sum = the row's sum of them, y the smoothed target, dfac the element's
+FRMAP_TRACK_HD inline void frmap_head_fit_margin_gh(double e, double sum, double y, float s, uint64_t n, double dfac, float rx, double cosine,
+                                                    float* g, float* h) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double p = e / sum;
+  const double d = p - y;
+  const double sd = (double)s * d;
+  const double q = sd / (double)n;
+  const double gcos = q * dfac;
+  *g = (float)(gcos * (double)rx);
+  *h = (float)(gcos * cosine);
+}
+// dw of one weight from the two chains A = dot_i(g, x') and k = dot_i(h, 1)
+FRMAP_TRACK_HD inline float frmap_head_fit_margin_dw(float A, float k, float rw, float w) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float t1 = rw * A;
+  if (!(rw < FRMAP_HEAD_FIT_MARGIN_RMAX)) return t1;
+  const float r2 = rw * rw;
+  const float t2 = r2 * k;
+  const float t3 = t2 * w;
+  return t1 - t3;
 }

@@ -54,8 +54,9 @@ inline const char* frmap_head_fit_refusal(int N, int B, int D, int C, int flags,
   if (D < 1 || D > FRMAP_HEAD_FIT_MAX_D) return "D is outside [1, 65536]";
   if (C < 1 || C > FRMAP_HEAD_FIT_MAX_C) return "C is outside [1, 65536]";
   if (flags & ~allowed)
-    return (allowed & FRMAP_HEAD_FIT_EVAL) ? "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 8 evaluate only)"
-                                           : "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear)";
+    return (allowed & FRMAP_HEAD_FIT_EVAL)          ? "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 8 evaluate only)"
+           : (allowed & FRMAP_HEAD_FIT_EASY_MARGIN) ? "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear, 16 easy margin)"
+                                                    : "flags has unknown bits (1 decoupled, 2 amsgrad, 4 clear)";
   for (int k = 0; k < n_required; ++k)
     if (!required[k]) return null_text;
   return nullptr;
@@ -401,6 +402,127 @@ inline const char* frmap_head_fit_pair_step_twin(const float* x, const int32_t* 
     }
     const float db = frmap_head_fit_dot(B, [&](int i) { return gg(i, e); }, [](int) { return 1.0f; });
     frmap_head_fit_adam(a, db, b + e, st.m_b + e, st.v_b + e, amsgrad ? st.vmax_b + e : nullptr);
+  }
+  return nullptr;
+}
+
+// what a margin call is refused for: the shared list (there is no bias; bit 16 of the flags is the easy margin)
+struct FrmapHeadFitMarginHyper {
+  float s, m;
+};
+inline const char* frmap_head_fit_margin_refusal(const void* x, const void* labels, const void* w, const void* state, const void* workspace, int N,
+                                                 int B, int D, int C, int flags) {
+  const void* const required[] = {x, labels, w, state, workspace};
+  return frmap_head_fit_refusal(N, B, D, C, flags, 7 | FRMAP_HEAD_FIT_EASY_MARGIN, required, 5,
+                                "null pointer (x, labels, w, state and workspace are required)");
+}
+
+// The margin step (head_fit_rule.h, MARGIN): z by frmap_head_fit_dot, the norms and the float64 margin softmax of every counted row
+// with serial sums, the figures, then the two chains over B, the combination and the update.  `given_g`: z, cosv, g, h, row_loss, rx
+// and rw of the workspace are INPUTS (the device's own); row_src, n, the figures (the arg-max from the given z, rx and rw), dw and the
+// update are computed from them.
+inline const char* frmap_head_fit_margin_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep,
+                                                   float keep_scale, float* w, void* state, void* workspace, int N, int B, int D, int C,
+                                                   const FrmapHeadFitMarginHyper& mh, const FrmapHeadFitHyper& h, int flags, int given_g) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (const char* why = frmap_head_fit_margin_refusal(x, labels, w, state, workspace, N, B, D, C, flags)) return why;
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0, easy = (flags & FRMAP_HEAD_FIT_EASY_MARGIN) ? 1 : 0;
+  const FrmapHeadFitState st = frmap_head_fit_state(state, D, C, amsgrad);
+  const FrmapHeadFitMarginWork wk = frmap_head_fit_margin_work(workspace, B, C);
+  if (flags & FRMAP_HEAD_FIT_CLEAR) st.head[FRMAP_HEAD_FIT_ROWS] = st.head[FRMAP_HEAD_FIT_CORRECT] = st.head[FRMAP_HEAD_FIT_LOSS_Q] = 0;
+  uint64_t n = 0;
+  for (int i = 0; i < B; ++i) {
+    wk.row_src[i] = frmap_head_fit_row_src(x, labels, rows, i, N, D, C);
+    n += wk.row_src[i] >= 0 ? 1 : 0;
+  }
+  st.head[FRMAP_HEAD_FIT_N] = n;
+  auto xp = [&](int i, int k) -> float {                  // x' of batch row i (declined: +0)
+    const int32_t r = wk.row_src[i];
+    if (r < 0) return 0.0f;
+    return frmap_head_fit_xp(x[(size_t)r * (size_t)D + k], keep ? (int)keep[(size_t)i * (size_t)D + k] : -1, keep_scale);
+  };
+  if (!given_g) {
+    for (int c = 0; c < C; ++c) {
+      double sq = 0.0;
+      for (int k = 0; k < D; ++k) sq = sq + (double)w[(size_t)c * (size_t)D + k] * (double)w[(size_t)c * (size_t)D + k];
+      wk.rw[c] = frmap_head_fit_margin_rnorm(sq);
+    }
+  }
+  const FrmapHeadFitTarget tg = frmap_head_fit_target(h.label_smoothing, C);
+  uint64_t correct = 0, loss_q = 0;
+  for (int i = 0; i < B; ++i) {
+    const size_t at = (size_t)i * (size_t)C;
+    float *z = wk.z + at, *cv = wk.cosv + at, *g = wk.g + at, *hh = wk.h + at;
+    const int32_t r = wk.row_src[i];
+    if (r < 0) {
+      if (!given_g) {
+        for (int c = 0; c < C; ++c) z[c] = cv[c] = g[c] = hh[c] = 0.0f;
+        wk.row_loss[i] = __builtin_nanf("");
+        wk.rx[i] = 0.0f;
+      }
+      continue;
+    }
+    const int32_t y = labels[r];
+    if (!given_g) {
+      double sq = 0.0;
+      for (int k = 0; k < D; ++k) sq = sq + (double)xp(i, k) * (double)xp(i, k);
+      wk.rx[i] = frmap_head_fit_margin_rnorm(sq);
+      for (int c = 0; c < C; ++c) {
+        const float* wc = w + (size_t)c * (size_t)D;
+        z[c] = frmap_head_fit_dot(D, [&](int k) { return xp(i, k); }, [&](int k) { return wc[k]; });
+      }
+    }
+    const float rxi = wk.rx[i];
+    int inside_y;
+    double out_y, dfac_y;
+    const double cs_y = frmap_head_fit_margin_clamp(frmap_head_fit_margin_cos(z[y], rxi, wk.rw[y]), &inside_y);
+    frmap_head_fit_margin_target(cs_y, inside_y, mh.m, easy, &out_y, &dfac_y);
+    auto logit = [&](int c, double* cosine, int* inside) -> double {
+      *cosine = frmap_head_fit_margin_cos(z[c], rxi, wk.rw[c]);
+      return frmap_head_fit_margin_logit(frmap_head_fit_margin_clamp(*cosine, inside), c == y, out_y, mh.s);
+    };
+    double cosine, mx = -INFINITY;
+    int inside, pred = 0x7FFFFFFF;
+    for (int c = 0; c < C; ++c) {
+      const double l = logit(c, &cosine, &inside);
+      if (l > mx) { mx = l; pred = c; }
+    }
+    if (!given_g) {
+      double sum = 0.0;
+      for (int c = 0; c < C; ++c) sum = sum + exp(logit(c, &cosine, &inside) - mx);
+      const double lse = log(sum);
+      double nl_sum = 0.0;
+      if (h.label_smoothing > 0.0f)
+        for (int c = 0; c < C; ++c) nl_sum = nl_sum + (lse - (logit(c, &cosine, &inside) - mx));
+      wk.row_loss[i] = frmap_head_fit_loss(lse - (logit(y, &cosine, &inside) - mx), nl_sum, h.label_smoothing, tg);
+      for (int c = 0; c < C; ++c) {
+        const double l = logit(c, &cosine, &inside);
+        int in2;
+        cv[c] = (float)frmap_head_fit_margin_clamp(cosine, &in2);
+        frmap_head_fit_margin_gh(exp(l - mx), sum, c == y ? tg.y_on : tg.y_off, mh.s, n, c == y ? dfac_y : (inside ? 1.0 : 0.0), rxi, cosine, g + c,
+                                 hh + c);
+      }
+    }
+    correct += pred == y ? 1 : 0;
+    loss_q += frmap_tally_loss_q(wk.row_loss[i]);
+  }
+  st.head[FRMAP_HEAD_FIT_ROWS] += n;
+  st.head[FRMAP_HEAD_FIT_CORRECT] += correct;
+  st.head[FRMAP_HEAD_FIT_LOSS_Q] += loss_q;
+  if (n == 0) return nullptr;
+  st.head[FRMAP_HEAD_FIT_T] += 1;
+  const FrmapHeadFitAdam a = frmap_head_fit_adam_scalars(st.head[FRMAP_HEAD_FIT_T], h, flags);
+  auto gg = [&](const float* m, int i, int c) -> float { return wk.row_src[i] < 0 ? 0.0f : m[(size_t)i * (size_t)C + c]; };
+  for (int c = 0; c < C; ++c) {
+    const float k = frmap_head_fit_dot(B, [&](int i) { return gg(wk.h, i, c); }, [](int) { return 1.0f; });
+    for (int d = 0; d < D; ++d) {
+      const float A = frmap_head_fit_dot(B, [&](int i) { return gg(wk.g, i, c); }, [&](int i) { return xp(i, d); });
+      const size_t at = (size_t)c * (size_t)D + d;
+      const float dw = frmap_head_fit_margin_dw(A, k, wk.rw[c], w[at]);
+      frmap_head_fit_adam(a, dw, w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
+    }
   }
   return nullptr;
 }

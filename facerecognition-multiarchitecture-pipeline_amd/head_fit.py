@@ -29,6 +29,13 @@ through a convolution exists here, and none is planned.
   loss 1 for SAME-class pairs; that is not reproduced - callers derive ``differ`` from identity labels (`draw_pairs`).  For a
   ``SiameseNet`` the head is its own last layer ``fc.8`` (`cache_embeddings(layer="fc_hidden")`, `PairHead.load_into`).
 
+* `margin_step_rule` / `margin_step_host` / `margin_step`, `MarginHead`, `margin_schedule`, `fit_margin_head` - one step of the class
+  centres of an ArcFace margin head (`frmap_head_fit_margin_step`): the reference's ``ArcMarginProduct`` in training mode
+  (`src/face_models.py:297-429`) under cross-entropy, the objective the flagship model is trained with, over cached normalised
+  embeddings (`cache_embeddings`).  The step takes the effective scale and margin as scalars; the warm-up schedule that produces them is
+  host arithmetic (`margin_schedule`).  `MarginHead.load_into` writes ``arcface.weight`` of an ``ArcFaceNet``, which
+  `evaluate.evaluate_model`, `evaluate_stream` and `arcface_validate` score against.
+
 Structure: the steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the seven
 size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk of the device steps and `_host_cache`, `_host_layer`,
 `_host_batch`, `_host_mask` and `_host_buffers` that of the host steps, after which a step lists its operands once and calls the library;
@@ -36,8 +43,7 @@ size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk
 pending clear and the epoch figures of `LinearHead`, `HeadGroup` and `HiddenHead`, `_linear_init` their ``nn.Linear`` draws, and
 `LinearHead._over` makes a head of views; `fit_head` is one loop over a head and its ``(width, dropout)`` mask specs.
 
-Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), the margin schedule of
-``ArcMarginProduct``, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
+Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), groups of margin heads, training ``embedding`` / ``bn`` of an ``ArcFaceNet``, the reference's backward-hook gradient clipping, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
 from __future__ import annotations
 
@@ -1642,4 +1648,334 @@ def fit_pair_head(model, train_data, val_data=None, epochs: int = 10, batch_pair
         history["train_acc"].append(fig["accuracy"])
         if val is not None:
             history["val"].append(evaluate.verification_metrics(head.embed(val[0]), val[1]))
+    return head, history
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# an ArcFace margin head: cached embeddings in, the class centres of `ArcFaceNet.arcface.weight` out
+# ---------------------------------------------------------------------------------------------------------------------------------
+EASY_MARGIN = 16                  # FRMAP_HEAD_FIT_EASY_MARGIN: bit of the margin step's flags
+MARGIN_HI = float(F32(1.0 - 1e-7))                 # the clamp bound of the cosine as the library holds it (fp32)
+MARGIN_CAP = float(F32(math.pi - 1e-4))            # the reference's torch.tensor(math.pi - 1e-4): a float32 in every dtype
+MARGIN_RMAX = F32(1.0 / 1e-12)                     # the fp32 reciprocal of a clamped norm
+
+
+def margin_state_bytes(D: int, C: int, amsgrad: bool = False) -> int:
+    """Bytes of the state of a margin head (`frmap_head_fit_margin_state_bytes`): `state_bytes` of (D, C); the bias moments stay zero,
+    so `state_views` reads it."""
+    return _size("frmap_head_fit_margin_state_bytes", _DC_IN, "D C", int(D), int(C), int(bool(amsgrad)))
+
+
+def margin_workspace_bytes(B: int, D: int, C: int) -> int:
+    """Bytes of the workspace of a margin step of ``B`` rows (`frmap_head_fit_margin_workspace_bytes`)."""
+    return _size("frmap_head_fit_margin_workspace_bytes", _B_IN + _DC_IN, "B D C", int(B), int(D), int(C))
+
+
+def margin_workspace_views(workspace: np.ndarray, B: int, C: int) -> dict:
+    """z, cosv, g, h [B, C], row_loss [B], rx [B], rw [C] (float32) and row_src [B] (int32) of a host copy of a margin workspace."""
+    raw = np.ascontiguousarray(workspace).view(np.uint8).reshape(-1)
+    nf = 4 * B * C + 2 * B + C
+    f = raw[: 4 * nf].view(np.float32)
+    out = {k: f[j * B * C: (j + 1) * B * C].reshape(B, C) for j, k in enumerate(("z", "cosv", "g", "h"))}
+    at = 4 * B * C
+    out.update(row_loss=f[at: at + B], rx=f[at + B: at + 2 * B], rw=f[at + 2 * B: at + 2 * B + C],
+               row_src=raw[4 * nf: 4 * nf + 4 * B].view(np.int32))
+    return out
+
+
+def margin_schedule(epoch: int, s: float = 32.0, m: float = 0.5, warm_up_epochs: int = 10, warm_up: bool = True):
+    """``(m_eff, s_eff)`` of training epoch ``epoch``: the arithmetic of the reference's ``ArcMarginProduct`` in training mode
+    (`src/face_models.py:336-348, 369, 401-409`).  ``margin_factor = min(0.9, (epoch / warm_up_epochs)^2)`` and ``scale_factor =
+    min(0.8, 0.3 + 0.5 epoch / warm_up_epochs)`` inside the warm-up, 0.9 and 0.8 after it; ``m_eff = m margin_factor``; ``s_eff =
+    min(s, 24) min(0.8, scale_factor)``, times ``(0.8 - 0.5 margin_factor)`` when ``m > 0.4``.  ``warm_up=False`` leaves the factors at
+    the module's initial 0.0 and 0.3, as ``use_warm_up=False`` does.  The reference's randomly printed "hard cap" (`:415-418`) multiplies
+    the output by 1, and no schedule reaches its threshold of 20 (``s_eff <= 24 x 0.8 = 19.2``): it is not restated."""
+    margin_factor, scale_factor = 0.0, 0.3
+    if warm_up:
+        if epoch < warm_up_epochs:
+            progress = epoch / warm_up_epochs
+            margin_factor = min(0.9, progress * progress)
+            scale_factor = min(0.8, 0.3 + 0.5 * progress)
+        else:
+            margin_factor, scale_factor = 0.9, 0.8
+    m_eff = m * margin_factor
+    s_eff = min(s, 24.0) * min(0.8, scale_factor)
+    if m > 0.4:
+        s_eff = s_eff * (0.8 - 0.5 * margin_factor)
+    return m_eff, s_eff
+
+
+def margin_logits_rule(z, rx, rw, y, s: float, m: float, easy_margin: bool = False, f32: bool = False):
+    """The float64 half of the margin rule up to the logits (csrc/head_fit_rule.h, MARGIN) on ``z [B, C]``, ``rx [B]``, ``rw [C]`` and the
+    targets ``y [B]``: ``{"cos", "cs", "inside", "theta_m", "out", "l", "dfac"}`` in float64 (``theta_m``: theta + m of every target).
+    ``f32``: the clamp bounds are the fp32 roundings, as in the library; else the doubles ``1 - 1e-7``."""
+    z, rx, rw = (np.asarray(t).astype(np.float64) for t in (z, rx, rw))
+    B, C = z.shape
+    hi = MARGIN_HI if f32 else 1.0 - 1e-7
+    rows = np.arange(B)
+    with np.errstate(all="ignore"):
+        cos = (z * rx[:, None]) * rw[None, :]
+        inside = (cos >= -hi) & (cos <= hi)
+        cs = np.where(cos < -hi, -hi, np.where(cos > hi, hi, cos))
+        out, dfac = cs.copy(), inside.astype(np.float64)
+        cy, iy = cs[rows, y], inside[rows, y].astype(np.float64)
+        theta = np.arccos(cy)
+        tm = theta + float(m)
+        ratio = np.sin(tm) / np.sin(theta)
+        if easy_margin:
+            take = cy > 0
+            out[rows, y] = np.where(take, np.cos(tm), cy)
+            dfac[rows, y] = np.where(take, iy * ratio, iy)
+        else:
+            capped = tm >= MARGIN_CAP                                    # (a NaN is not capped: it stays one, as torch.minimum keeps it)
+            out[rows, y] = np.where(capped, math.cos(MARGIN_CAP), np.cos(tm))
+            dfac[rows, y] = np.where(capped, 0.0, iy * ratio)
+        return {"cos": cos, "cs": cs, "inside": inside, "theta_m": tm, "out": out, "l": float(s) * out, "dfac": dfac}
+
+
+def margin_step_rule(x, labels, w, state: Optional[dict] = None, rows=None, keep=None, keep_scale: float = 1.0, *, s: float, m: float,
+                     easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                     weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+                     clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
+    """One training step of the margin head, the specification (csrc/head_fit_rule.h, MARGIN; include/frmap_hip.h, "Head fitting with a
+    margin").
+
+    ``dtype=np.float64``: the formulas in float64 as torch evaluates the reference's ``F.normalize`` -> ``F.linear`` -> ``clamp`` ->
+    ``acos`` -> ``minimum`` / ``where`` -> ``cross_entropy(label_smoothing=)`` -> ``optim.Adam`` / ``AdamW`` (the cosine is
+    ``z / (|x'| |w|)`` on raw dot products: the same value).  ``dtype=np.float32``: z and both chains over B by `dot32`, rx and rw
+    rounded to float32 once, the margin softmax in float64 from those float32 values (and the float32 values of ``s``, ``m`` and the
+    bounds) with cosv, g, h and the row loss rounded once, the combination of dw in float32 products, `adam32` - what the host twin
+    computes, word for word but for a rare last bit of rx, rw, cosv, g, h and the row loss.  ``given``: ``{"z", "rx", "rw", "cosv", "g",
+    "h", "row_loss"}`` to take as they are.
+
+    Nothing is modified: returns ``{"w", "state", "z", "rx", "rw", "cosv", "g", "h", "row_loss", "row_src", "pred", "dw", "n", "loss"}``
+    and the float64 intermediates of `margin_logits_rule` under ``"detail"``."""
+    f32 = np.dtype(dtype) == np.dtype(np.float32)
+    x = np.asarray(x, F32 if f32 else np.float64)
+    w = np.array(w, dtype)
+    labels = np.asarray(labels).astype(np.int64)
+    N, D = x.shape
+    C = w.shape[0]
+    st = _copy_state(state or fresh_state(D, C, amsgrad, dtype), dtype)
+    if clear:
+        st["rows"] = st["correct"] = st["loss_q"] = 0
+    row_src, ok, xp = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), keep,
+                                  keep_scale, f32)
+    B = len(row_src)
+    n = int(ok.sum())
+    st["n"] = n
+    y = np.where(ok, labels[np.clip(row_src, 0, N - 1)], 0)
+    if f32:
+        s, m, ls = float(F32(s)), float(F32(m)), float(F32(label_smoothing))
+    else:
+        s, m, ls = float(s), float(m), float(label_smoothing)
+    with np.errstate(all="ignore"):
+        if given is not None:
+            z, rx, rw = (np.array(given[k], dtype) for k in ("z", "rx", "rw"))
+        else:
+            z = dot32(xp[:, None, :], w[None, :, :]).astype(F32) if f32 else xp @ w.T
+            z[~ok] = 0
+            nx = np.sqrt((xp.astype(np.float64) ** 2).sum(axis=1))
+            nw = np.sqrt((w.astype(np.float64) ** 2).sum(axis=1))
+            rx = (1.0 / np.maximum(nx, NORM_EPS)).astype(dtype)
+            rw = (1.0 / np.maximum(nw, NORM_EPS)).astype(dtype)
+            rx[~ok] = 0
+        det = margin_logits_rule(z, rx, rw, y, s, m, easy_margin, f32)
+        l = det["l"]
+        pred = np.where(np.isnan(l).all(axis=1), -1, np.argmax(np.where(np.isnan(l), -np.inf, l), axis=1))
+        if given is not None:
+            cosv, g, h, row_loss = (np.array(given[k], dtype) for k in ("cosv", "g", "h", "row_loss"))
+        else:
+            mx = l.max(axis=1, keepdims=True)
+            e = np.exp(l - mx)
+            sm = e.sum(axis=1, keepdims=True)
+            nl = np.log(sm) - (l - mx)
+            nll = nl[np.arange(B), y]
+            off = ls / C if ls > 0 else 0.0
+            row_loss = (1.0 - ls) * nll + off * nl.sum(axis=1) if ls > 0 else nll
+            row_loss = np.where(row_loss > 0, row_loss, np.where(np.isnan(row_loss), row_loss, 0)).astype(dtype)
+            t64 = np.full((B, C), off)
+            t64[np.arange(B), y] = (1.0 - ls) + off
+            gcos = ((s * ((e / sm) - t64)) / float(max(n, 1))) * det["dfac"]
+            g = (gcos * rx.astype(np.float64)[:, None]).astype(dtype)
+            h = (gcos * det["cos"]).astype(dtype)
+            cosv = det["cs"].astype(dtype)
+            for a in (g, h, cosv):
+                a[~ok] = 0
+            row_loss[~ok] = np.nan
+    st["rows"] += n
+    st["correct"] += int((ok & (pred == y)).sum())
+    st["loss_q"] += loss_q(row_loss[ok])
+    gz, hz = np.where(ok[:, None], g, 0).astype(dtype), np.where(ok[:, None], h, 0).astype(dtype)
+    with np.errstate(all="ignore"):
+        if f32:
+            A = dot32(gz.T[:, None, :], xp.T[None, :, :])
+            k = dot32(hz.T, np.ones((1, B), F32))
+            rw32 = rw.astype(F32)
+            free = rw32 < MARGIN_RMAX
+            t1 = (rw32[:, None] * A).astype(F32)
+            t3 = (((rw32 * rw32).astype(F32) * k).astype(F32)[:, None] * w).astype(F32)
+            dw = np.where(free[:, None], (t1 - t3).astype(F32), t1)
+        else:
+            nw = np.sqrt((w * w).sum(axis=1))
+            free = nw > NORM_EPS
+            dw = rw[:, None] * (gz.T @ xp) - np.where(free, rw * rw * hz.sum(axis=0), 0.0)[:, None] * w
+    out = {"z": z, "rx": rx, "rw": rw, "cosv": cosv, "g": g, "h": h, "row_loss": row_loss, "row_src": row_src, "pred": pred, "dw": dw,
+           "n": n, "detail": det, "ok": ok, "y": y, "loss": float(row_loss[ok].astype(np.float64).mean()) if n else float("nan")}
+    if n:
+        st["t"] += 1
+        w = _adam_rule(w, dw, st, "w", t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                       decoupled=decoupled, amsgrad=amsgrad, f32=f32)
+    out["w"], out["state"] = w, st
+    return out
+
+
+def _margin_flags(decoupled, amsgrad, clear, easy_margin) -> int:
+    return _flags(decoupled, amsgrad, clear) | (EASY_MARGIN if easy_margin else 0)
+
+
+def margin_step_host(x, labels, w, state: np.ndarray, workspace: Optional[np.ndarray] = None, rows=None, keep=None, keep_scale: float = 1.0, *,
+                     s: float, m: float, easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
+                     eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False,
+                     amsgrad: bool = False, clear: bool = False, given_g: bool = False, batch: Optional[int] = None):
+    """The margin step on the CPU over numpy arrays (`frmap_head_fit_margin_step_host`; no GPU).  ``w`` [C, D] (float32) and ``state``
+    (uint8, `margin_state_bytes` bytes, 8-byte aligned) are updated IN PLACE; ``workspace`` (uint8, exactly `margin_workspace_bytes`
+    bytes, or ``None`` for a fresh one) receives z, cosv, g, h, row_loss, rx, rw and row_src - with ``given_g`` all but row_src are
+    inputs.  Returns the workspace."""
+    op = "head_fit.margin_step_host"
+    x, labels, N, D = _host_cache(op, x, labels)
+    _host_array(op, "w", w, np.float32)
+    if w.ndim != 2 or w.shape[1] != D:
+        raise ValueError(f"{op}: w [C, {D}] expected, got {w.shape}")
+    C = int(w.shape[0])
+    rows, B = _host_batch(op, N, rows, (keep,), batch)
+    keep = _host_mask(op, "keep", keep, (B, D))
+    workspace = _host_buffers(op, state, margin_state_bytes(D, C, amsgrad), workspace, margin_workspace_bytes(B, D, C), given_g)
+    _lib.check(_lib.load().frmap_head_fit_margin_step_host(
+        _at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w), _at(state), _at(workspace), N, B, D, C, float(s), float(m),
+        float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        _margin_flags(decoupled, amsgrad, clear, easy_margin), int(bool(given_g))), op)
+    return workspace
+
+
+@ops._on_operand_device
+def margin_step(x: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, state: torch.Tensor, workspace: torch.Tensor,
+                rows: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, *, s: float, m: float,
+                easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
+                batch: Optional[int] = None) -> None:
+    """One margin training step on the current stream (`frmap_head_fit_margin_step`; nothing is copied or synchronised).  ``x`` float32
+    ``[N, D]`` (the cache), ``labels`` int32 ``[N]``, ``w`` float32 ``[C, D]`` (updated in place), ``state`` uint8 of
+    `margin_state_bytes` bytes (zeros = fresh), ``workspace`` uint8 of exactly `margin_workspace_bytes` bytes, ``rows`` int32 ``[B]`` or
+    ``None``, ``keep`` uint8 ``[B, D]`` or ``None``; ``s`` and ``m`` are the effective scale and margin of this step
+    (`margin_schedule`).  Every extent that depends on another operand is checked here, before the library sees a pointer."""
+    op, entry = "head_fit.margin_step", "frmap_head_fit_margin_step"
+    x, N, D = _cache(op, entry, x, labels)
+    _sized(w, op, "w", (w.shape[0] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1, D), torch.float32)
+    C = int(w.shape[0])
+    rows, B = _batch(op, entry, N, rows, (keep,), batch)
+    if keep is not None:
+        _sized(keep, op, "keep", (B, D), torch.uint8)
+    _sized(state, op, "state", (margin_state_bytes(D, C, amsgrad),), torch.uint8)
+    _sized(workspace, op, "workspace", (margin_workspace_bytes(B, D, C),), torch.uint8)
+    labels = _operand(labels, op, entry, "labels", torch.int32)
+    keep = _operand(keep, op, entry, "keep", torch.uint8)
+    w = _operand(w, op, entry, "w", torch.float32, True)
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _lib.check(_lib.load().frmap_head_fit_margin_step(
+        x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w.data_ptr(), state.data_ptr(), workspace.data_ptr(),
+        N, B, D, C, float(s), float(m), float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        _margin_flags(decoupled, amsgrad, clear, easy_margin), _stream()), op)
+
+
+class MarginHead(_Head):
+    """The class centres ``[C, D]`` of an ArcFace margin head on the device with their Adam state and a workspace: the ``weight`` of the
+    reference's ``ArcMarginProduct``, initialised as it is (``xavier_normal_`` with gain sqrt(2), `src/face_models.py:326`) from
+    ``generator`` (a CPU ``torch.Generator``; ``None``: torch's default).  `cosines` is what `evaluate.evaluate_model`,
+    `evaluate_stream` and `arcface_validate` score with; `load_into` hands the centres to an ``ArcFaceNet``."""
+
+    def __init__(self, D: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
+        self.D, self.C, self.amsgrad = int(D), int(C), bool(amsgrad)
+        nbytes = margin_state_bytes(self.D, self.C, self.amsgrad)          # (refuses a bad shape)
+        std = math.sqrt(2.0) * math.sqrt(2.0 / (self.D + self.C))
+        w = torch.empty((self.C, self.D), dtype=torch.float32).normal_(0.0, std, generator=generator)
+        device = torch.device(device)
+        self.weight = w.to(device)
+        self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
+
+    def _workspace_bytes(self, B: int) -> int:
+        return margin_workspace_bytes(B, self.D, self.C)
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor, rows: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, *,
+             lr: float, s: float, m: float, easy_margin: bool = False, label_smoothing: float = 0.0, keep_scale: Optional[float] = None,
+             dropout: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+             decoupled: bool = False) -> "MarginHead":
+        """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`margin_step`) at the effective scale ``s`` and margin ``m``.
+        ``keep``: a uint8 ``[B, D]`` dropout mask, scaled by ``keep_scale`` (default ``1 / (1 - dropout)``; the scale cancels in the
+        cosine).  No synchronisation."""
+        if keep_scale is None:
+            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
+        B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
+            int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
+        return self._run(margin_step, x, labels, self.weight, self.state, self._workspace(B), rows, keep, keep_scale, s=s, m=m,
+                         easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                         label_smoothing=label_smoothing, decoupled=decoupled)
+
+    def cosines(self, x: torch.Tensor) -> torch.Tensor:
+        """The cosine of every row of ``x`` ``[B, D]`` with every class centre, ``[B, C]`` (`ops.cosine_logits`)."""
+        return self.logits(x, 1.0)
+
+    def logits(self, x: torch.Tensor, s: float = 1.0) -> torch.Tensor:
+        """``s`` times `cosines`: the reference's eval-mode output without its margin (arg-max and ranks do not depend on ``s``)."""
+        return ops.cosine_logits(x, self.weight, s=float(s), want_argmax=False)[0]
+
+    def state_dict(self) -> dict:
+        return {"weight": self.weight.detach().clone()}
+
+    def load_into(self, model) -> None:
+        """Copy the centres into ``arcface.weight`` of an ``ArcFaceNet`` in place; any other class and any other shape is refused."""
+        arc = getattr(model, "arcface", None)
+        if type(model).__name__ != "ArcFaceNet" or not isinstance(getattr(arc, "weight", None), torch.Tensor):
+            raise ValueError(f"MarginHead.load_into: an ArcFaceNet expected, got {type(model).__name__}")
+        if tuple(arc.weight.shape) != (self.C, self.D):
+            raise ValueError(f"MarginHead.load_into: arcface.weight is {list(arc.weight.shape)}, the head is {[self.C, self.D]}")
+        with torch.no_grad():
+            arc.weight.copy_(self.weight)
+
+
+def fit_margin_head(model, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3, weight_decay: float = 1e-4,
+                    s: float = 32.0, m: float = 0.5, easy_margin: bool = False, warm_up: bool = True, dropout: float = 0.0,
+                    label_smoothing: float = 0.05, decoupled: bool = True, amsgrad: bool = True,
+                    generator: Optional[torch.Generator] = None, num_classes: Optional[int] = None, device="cuda"):
+    """Fit a `MarginHead` on the frozen model's embeddings with the reference's ArcFace objective.  The training set is embedded once
+    (`cache_embeddings`: the model's normalised embedding; a dropout mask on it reproduces the head input of the reference's training
+    mode, since a normalisation follows); epoch ``e`` runs at `margin_schedule(e, s, m)`; every epoch draws a fresh device permutation
+    as ``rows`` (and masks, with ``dropout``) and steps through it with no host copy inside the epoch.  The defaults are the reference's
+    ArcFace settings (`src/training.py:340-348`: AdamW, AMSGrad, label smoothing 0.05).  With ``val_data`` every epoch's validation
+    ``head.logits`` go through `evaluate.ClassificationTally`.  Returns ``(head, history)`` in `fit_head`'s shape."""
+    from . import evaluate
+    feats, labels = cache_embeddings(model, train_data, device=device)
+    N, D = int(feats.shape[0]), int(feats.shape[1])
+    C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
+    head_gen, dev_gen = _generators(generator, feats.device)
+    head = MarginHead(D, C, feats.device, amsgrad=amsgrad, generator=head_gen)
+    val = cache_embeddings(model, val_data, device=device) if val_data is not None else None
+    history = {"train_loss": [], "train_acc": [], "val": []}
+    for epoch in range(int(epochs)):
+        m_eff, s_eff = margin_schedule(epoch, s, m, warm_up=warm_up)
+        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, int(batch_size)):
+            rows = perm[lo: lo + int(batch_size)]
+            keep = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
+            head.step(feats, labels, rows, keep, lr=lr, s=s_eff, m=m_eff, easy_margin=easy_margin, label_smoothing=label_smoothing,
+                      dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)
+        fig = head.epoch_figures()
+        history["train_loss"].append(fig["loss"])
+        history["train_acc"].append(fig["accuracy"])
+        if val is not None:
+            tally = evaluate.ClassificationTally(C, device=feats.device)
+            tally.update(head.logits(val[0], min(s, 24.0)), val[1])
+            history["val"].append(tally.metrics())
     return head, history

@@ -815,6 +815,52 @@ int frmap_head_fit_pair_step_host(const float* x_host, const int32_t* left_host,
                                   float accept, float lr, float beta1, float beta2, float eps, float weight_decay, int flags,
                                   int given_g);
 
+/* Head fitting with a margin: one training step of the class centres w [C][D] of an ArcFace margin head (the reference's
+ * ArcMarginProduct, src/face_models.py:297-429) under softmax cross-entropy with the trunk frozen - the weight that
+ * frmap_cosine_logits scores against.  One small memset and four launches on the caller's stream, nothing copied to the host, nothing
+ * allocated, no floating-point atomic.
+ *
+ * Operands: x, labels, rows, keep / keep_scale as in frmap_head_fit_step (the cache should hold the model's embeddings); w [C][D]
+ * fp32, updated in place; there is no bias.  s, m: the EFFECTIVE scale and margin of this step (the reference's warm-up schedule is
+ * host arithmetic: head_fit.margin_schedule).  flags: 1 | 2 | 4 as in frmap_head_fit_step, 16 = easy margin.
+ * The rule (dot products are the single step's chains; declined rows are the single step's):
+ *   z[i][c]  = dot_k(x'[i][k], w[c][k]); the z row of a declined row is +0
+ *   rx[i]    = fp32(1 / max(||x'_i||, 1e-12)), rw[c] = fp32(1 / max(||w_c||, 1e-12)), the squared norms summed in float64; rx of a
+ *              declined row is +0.  From here in float64 on the fp32 z, rx, rw, rounded to fp32 once:
+ *   cos      = (z rx[i]) rw[c];  cs = clamp(cos, -HI, HI), inside = -HI <= cos <= HI, HI = fp32(1 - 1e-7)
+ *   target   : theta = acos(cs); theta + m >= CAP = fp32(pi - 1e-4) ? out = cos(CAP), dfac = 0
+ *              : out = cos(theta + m), dfac = inside sin(theta + m) / sin(theta).  Easy margin: cs > 0 ? the margin branch (no cap)
+ *              : out = cs, dfac = inside.
+ *   others   : out = cs, dfac = inside
+ *   l = s out; softmax, row loss (label smoothing as in the single step), pred = the first arg-max of l
+ *   q = s (p - y) / n;  g[i][c] = fp32(q dfac rx[i]);  h[i][c] = fp32(q dfac cos);  cosv[i][c] = fp32(cs)
+ *   dw[c][d] = rw[c] dot_i(g[i][c], x'[i][d]) - rw[c]^2 dot_i(h[i][c], 1) w[c][d], every product and the difference rounded once; the
+ *              second term is absent where rw[c] is not below fp32(1e12) (a clamped norm)
+ *   update   : Adam / AdamW on w as in the single step; figures as in the single step; n == 0 changes nothing but the workspace.
+ * Launches: the memset of n (with 4: the figures); logits (the tile walk without a bias: z, row_src, n); norms (a wavefront per row
+ * of the batch and of w: rx, rw; independent of the launch before); margin softmax (a wavefront per row: cosv, g, h, row_loss, the
+ * figures; advances t when n > 0); update (a 32 x 32 tile of w per workgroup: both chains over B, the combination, Adam).
+ * state : frmap_head_fit_margin_state_bytes bytes = the single step's layout for (D, C) (the bias moments stay zero), zeroed by the
+ *         caller before the first step.
+ * workspace : exactly frmap_head_fit_margin_workspace_bytes bytes: fp32 z [B][C], cosv [B][C], g [B][C], h [B][C], row_loss [B],
+ *         rx [B], rw [C], int32 row_src [B].  D does not enter the size.
+ * The size queries take no stream and return 0 for arguments the launcher would refuse.
+ * Refused (-1, the text names the argument): N < 1; B < 1 or above 2^20; D or C < 1 or above 65536; flag bits outside 1 | 2 | 4 | 16; a
+ * required pointer that is NULL (rows and keep may be).
+ * Every pointer is walked element by element: x, labels, rows, w and workspace need their element size (4), keep 1, state the size
+ * of a uint64 counter (8).
+ * The host form is the same step compiled for the CPU (host pointers, no stream); given_g != 0 takes z, cosv, g, h, row_loss, rx and
+ * rw of the workspace as INPUTS - the device's own - and computes row_src, n, the figures, dw and the update from them. */
+size_t frmap_head_fit_margin_state_bytes(int D, int C, int amsgrad);
+size_t frmap_head_fit_margin_workspace_bytes(int B, int D, int C);
+int frmap_head_fit_margin_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale, float* w,
+                               void* state, void* workspace, int N, int B, int D, int C, float s, float m, float label_smoothing, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, int flags, void* stream);
+int frmap_head_fit_margin_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,
+                                    float keep_scale, float* w_host, void* state_host, void* workspace_host, int N, int B, int D, int C,
+                                    float s, float m, float label_smoothing, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, int flags, int given_g);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
