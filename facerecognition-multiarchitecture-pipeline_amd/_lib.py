@@ -122,6 +122,12 @@ PROTOTYPES = {
     "frmap_head_fit_margin_workspace_bytes": (_sz, [_i, _i, _i]),
     "frmap_head_fit_margin_step": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _vp]),
     "frmap_head_fit_margin_step_host": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, _i]),
+    "frmap_head_fit_embed_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "frmap_head_fit_embed_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "frmap_head_fit_embed_step": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f,
+                                       _f, _f, _f, _f, _i, _vp]),
+    "frmap_head_fit_embed_step_host": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                                            _f, _f, _f, _f, _f, _i, _i]),
     "frmap_head_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_workspace_bytes": (_sz, [_i, _i]),
     "frmap_match_top1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
@@ -221,6 +227,8 @@ ALIGNMENT = {
     "frmap_head_fit_pair_step": {"x": _E4, "left": _E4, "right": _E4, "differ": _E4, "keep": _E1, "w": _E4, "b": _E4, "state": _E8,
                                  "workspace": _E4},
     "frmap_head_fit_margin_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep": _E1, "w": _E4, "state": _E8, "workspace": _E4},
+    "frmap_head_fit_embed_step": {"x": _E4, "labels": _E4, "rows": _E4, "keep": _E1, "w1": _E4, "gamma": _E4, "beta": _E4, "running_mean": _E4,
+                                  "running_var": _E4, "wc": _E4, "state": _E8, "workspace": _E4},
     "frmap_match_top1": {"emb": _M, "gallery": _M, **_TOP1_OUT, "workspace": _W},
     "frmap_match_pack_gallery": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},
     "frmap_match_pack_gallery_rows": {"gallery": _E4, "packed_out": ("tensor", 2), "stat_w_out": _E4},

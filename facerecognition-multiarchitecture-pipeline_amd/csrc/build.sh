@@ -7,7 +7,7 @@ OUT=../libfrmap_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-unused-value"
 objs=()
 pids=()
-for f in conv_igemm.hip conv_pp.hip conv_small_cin.hip stem_pool.hip stem_s2d.hip layout_pool.hip transformer.hip head_match.hip resize.hip crop_resize.hip yuv_crop.hip track.hip track_fuse.hip classify_tally.hip ovr_rank.hip head_fit.hip head_fit_hidden.hip head_fit_pair.hip head_fit_margin.hip c_api.cpp conv_plan.cpp model_api.cpp model_families.cpp; do
+for f in conv_igemm.hip conv_pp.hip conv_small_cin.hip stem_pool.hip stem_s2d.hip layout_pool.hip transformer.hip head_match.hip resize.hip crop_resize.hip yuv_crop.hip track.hip track_fuse.hip classify_tally.hip ovr_rank.hip head_fit.hip head_fit_hidden.hip head_fit_pair.hip head_fit_margin.hip head_fit_embed.hip c_api.cpp conv_plan.cpp model_api.cpp model_families.cpp; do
   o="build_${f%.*}.o"
   stale=0
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ]; then stale=1; fi

@@ -1,5 +1,5 @@
 // The device code that the head-fitting translation units share (head_fit.hip: the linear step and its groups; head_fit_hidden.hip:
-// the hidden-layer step; head_fit_pair.hip: the pair step; head_fit_margin.hip: the margin step): the tile walk of both GEMMs, its operand loaders and the bodies of the three
+// the hidden-layer step; head_fit_pair.hip: the pair step; head_fit_margin.hip: the margin step; head_fit_embed.hip: the embedding step): the tile walk of both GEMMs, its operand loaders and the bodies of the three
 // kernels.  The kernels themselves (`__global__`) stay with their launchers: a code object holds the kernels of ONE of the files, so
 // adding a kernel to one file leaves the other files' code objects - LDS layout, register allocation, instructions - as they are.
 #pragma once
@@ -199,14 +199,16 @@ struct HfUpdateOp {
 // HF_PAIR_ROWS: the forward of the pair step (head_fit_pair.hip) - no label is read or checked, the identity epilogue, nothing counted;
 // batch row i reads rows[i] below `split` and rows_hi[i - split] from there on.  (MODE was a bool: false / true still name the first two.)
 // HF_MARGIN: the forward of the margin step (head_fit_margin.hip) - HF_LINEAR's labels, row_src and count of n, but no bias is read or added.
-constexpr int HF_LINEAR = 0, HF_HIDDEN = 1, HF_PAIR_ROWS = 2, HF_MARGIN = 3;
+// HF_EMBED: the first layer of the embedding step (head_fit_embed.hip) - HF_HIDDEN's labels (in range below CL), lab and row_src and no
+// count, with HF_MARGIN's epilogue: no bias is read or added and there is no ReLU.
+constexpr int HF_LINEAR = 0, HF_HIDDEN = 1, HF_PAIR_ROWS = 2, HF_MARGIN = 3, HF_EMBED = 4;
 template <int MODE>
 __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, const int32_t* __restrict__ labels, const int32_t* __restrict__ rows,
                                                const uint8_t* __restrict__ keep, float keep_scale, const float* __restrict__ w,
                                                const float* __restrict__ b, uint64_t* state, float* __restrict__ z,
                                                int32_t* __restrict__ row_src, int32_t* __restrict__ lab, int N, int B, int D, int C, int CL,
                                                const int32_t* __restrict__ rows_hi = nullptr, int split = 0) {
-  constexpr bool HIDDEN = MODE == HF_HIDDEN;
+  constexpr bool HIDDEN = MODE == HF_HIDDEN, LAB = MODE == HF_HIDDEN || MODE == HF_EMBED;
   __shared__ HfSmem sm;
   __shared__ int s_src[HF_T];        // the row of x behind tile row i; -1: outside the batch, the cache or the label range
   __shared__ int s_bad[HF_T];        // a non-finite feature was staged for tile row i
@@ -223,7 +225,7 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
         const long long r = rows ? (long long)rows[i] : (long long)i;
         if (r >= 0 && r < (long long)N) {
           const int y = labels[r];
-          if (y >= 0 && y < (HIDDEN ? CL : C)) src = (int)r;
+          if (y >= 0 && y < (LAB ? CL : C)) src = (int)r;
         }
       }
     }
@@ -242,7 +244,7 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
     if (b0 + i < B && c0 + j < C) {
       const bool declined = s_src[i] < 0 || s_bad[i] != 0;
       if (HIDDEN) z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : frmap_head_fit_relu(tot[q] + b[c0 + j]);
-      else if (MODE == HF_MARGIN) z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : tot[q];
+      else if (MODE == HF_MARGIN || MODE == HF_EMBED) z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : tot[q];
       else z[(size_t)(b0 + i) * (size_t)C + c0 + j] = declined ? 0.0f : tot[q] + b[c0 + j];
     }
   }
@@ -251,7 +253,7 @@ __device__ __forceinline__ void hf_logits_body(const float* __restrict__ x, cons
     const bool counted = in && s_src[tid] >= 0 && s_bad[tid] == 0;
     if (in) row_src[b0 + tid] = counted ? s_src[tid] : -1;
     if (MODE == HF_PAIR_ROWS) return;
-    if (HIDDEN) {
+    if (LAB) {
       if (in) lab[b0 + tid] = counted ? labels[s_src[tid]] : -1;
       return;
     }

@@ -167,6 +167,41 @@ __global__ __launch_bounds__(64 * HF_WAVES) void head_fit_margin_update_kernel(c
   hf_margin_update_body(x, keep, keep_scale, w, state, g, hm, rw, row_src, B, D, C, h, flags);
 }
 
+// the two halves of the launcher (head_fit_launch.h): frmap_head_fit_margin_step runs them back to back, the embedding step around its own kernels
+int frmap_head_fit_margin_forward_launch(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
+                                         const float* w, uint64_t* head, void* workspace, int N, int B, int D, int C, float s, float m,
+                                         float label_smoothing, int flags, hipStream_t st, const char* who) {
+  const FrmapHeadFitMarginWork wk = frmap_head_fit_margin_work(workspace, B, C);
+  // n of the step in flight, and with `clear` the three epoch figures behind it (words 1 .. 4 of the header)
+  if (hipMemsetAsync(head + FRMAP_HEAD_FIT_N, 0, (flags & FRMAP_HEAD_FIT_CLEAR) ? 32 : 8, st) != hipSuccess) {
+    frmap_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(hipGetLastError()));
+    return -2;
+  }
+  const unsigned tb = hf_tiles(B), tc = hf_tiles(C);
+  const dim3 block(64 * HF_WAVES);
+  hipLaunchKernelGGL(head_fit_margin_logits_kernel, dim3(tc, tb), block, 0, st, x, labels, rows, keep, keep_scale, w, head, wk.z, wk.row_src, N, B,
+                     D, C);
+  FRMAP_LAUNCH_CHECK();
+  // (B + C <= 2^20 + 2^16: hf_softmax_blocks takes it)
+  hipLaunchKernelGGL(head_fit_margin_norms_kernel, dim3(hf_softmax_blocks(B + C)), block, 0, st, x, labels, rows, keep, keep_scale, w, wk.rx, wk.rw,
+                     N, B, D, C);
+  FRMAP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_fit_margin_softmax_kernel, dim3(hf_softmax_blocks(B)), block, 0, st, labels, (const int32_t*)wk.row_src, head,
+                     (const float*)wk.z, (const float*)wk.rx, (const float*)wk.rw, wk.cosv, wk.g, wk.h, wk.row_loss, B, C, s, m, label_smoothing,
+                     (flags & FRMAP_HEAD_FIT_EASY_MARGIN) ? 1 : 0);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
+int frmap_head_fit_margin_update_launch(const float* x, const uint8_t* keep, float keep_scale, float* w, void* state, void* workspace, int B,
+                                        int D, int C, const FrmapHeadFitHyper& h, int flags, hipStream_t st) {
+  const FrmapHeadFitMarginWork wk = frmap_head_fit_margin_work(workspace, B, C);
+  hipLaunchKernelGGL(head_fit_margin_update_kernel, dim3(hf_tiles(D), hf_tiles(C)), dim3(64 * HF_WAVES), 0, st, x, keep, keep_scale, w, state,
+                     (const float*)wk.g, (const float*)wk.h, (const float*)wk.rw, (const int32_t*)wk.row_src, B, D, C, h, flags);
+  FRMAP_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" size_t frmap_head_fit_margin_state_bytes(int D, int C, int amsgrad) {
   if (!frmap_head_fit_shape_ok(D, C)) return 0;
   return frmap_head_fit_state_size(D, C, amsgrad);
@@ -189,32 +224,11 @@ extern "C" int frmap_head_fit_margin_step(const float* x, const int32_t* labels,
   FRMAP_REQUIRE_ALIGNED(w, 4, "w");
   FRMAP_REQUIRE_ALIGNED(state, 8, "state");
   FRMAP_REQUIRE_ALIGNED(workspace, 4, "workspace");
-  const hipStream_t st = (hipStream_t)stream;
-  uint64_t* head = (uint64_t*)state;
-  const FrmapHeadFitMarginWork wk = frmap_head_fit_margin_work(workspace, B, C);
   const FrmapHeadFitHyper h = {lr, beta1, beta2, eps, weight_decay, label_smoothing};
-  // n of the step in flight, and with `clear` the three epoch figures behind it (words 1 .. 4 of the header)
-  if (hipMemsetAsync(head + FRMAP_HEAD_FIT_N, 0, (flags & FRMAP_HEAD_FIT_CLEAR) ? 32 : 8, st) != hipSuccess) {
-    frmap_set_error("head_fit_margin_step: hipMemsetAsync failed: %s", hipGetErrorString(hipGetLastError()));
-    return -2;
-  }
-  const unsigned tb = hf_tiles(B), tc = hf_tiles(C), td = hf_tiles(D);
-  const dim3 block(64 * HF_WAVES);
-  hipLaunchKernelGGL(head_fit_margin_logits_kernel, dim3(tc, tb), block, 0, st, x, labels, rows, keep, keep_scale, (const float*)w, head, wk.z,
-                     wk.row_src, N, B, D, C);
-  FRMAP_LAUNCH_CHECK();
-  // (B + C <= 2^20 + 2^16: hf_softmax_blocks takes it)
-  hipLaunchKernelGGL(head_fit_margin_norms_kernel, dim3(hf_softmax_blocks(B + C)), block, 0, st, x, labels, rows, keep, keep_scale, (const float*)w,
-                     wk.rx, wk.rw, N, B, D, C);
-  FRMAP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_fit_margin_softmax_kernel, dim3(hf_softmax_blocks(B)), block, 0, st, labels, (const int32_t*)wk.row_src, head,
-                     (const float*)wk.z, (const float*)wk.rx, (const float*)wk.rw, wk.cosv, wk.g, wk.h, wk.row_loss, B, C, s, m, label_smoothing,
-                     (flags & FRMAP_HEAD_FIT_EASY_MARGIN) ? 1 : 0);
-  FRMAP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_fit_margin_update_kernel, dim3(td, tc), block, 0, st, x, keep, keep_scale, w, state, (const float*)wk.g,
-                     (const float*)wk.h, (const float*)wk.rw, (const int32_t*)wk.row_src, B, D, C, h, flags);
-  FRMAP_LAUNCH_CHECK();
-  return 0;
+  const int rc = frmap_head_fit_margin_forward_launch(x, labels, rows, keep, keep_scale, w, (uint64_t*)state, workspace, N, B, D, C, s, m,
+                                                      label_smoothing, flags, (hipStream_t)stream, "head_fit_margin_step");
+  if (rc) return rc;
+  return frmap_head_fit_margin_update_launch(x, keep, keep_scale, w, state, workspace, B, D, C, h, flags, (hipStream_t)stream);
 }
 
 extern "C" int frmap_head_fit_margin_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,

@@ -110,6 +110,46 @@
 //   update     frmap_head_fit_adam on every w[c][d], t += 1 first; figures as in the linear step.  n == 0: only the workspace is written.
 // MARGIN STATE: the single layout for (D, C); the bias moments stay zero.  MARGIN WORKSPACE (frmap_head_fit_margin_workspace_bytes):
 // fp32 z [B C], cosv [B C], g [B C], h [B C], row_loss [B], rx [B], rw [C], then int32 row_src [B].
+//
+// EMBED (frmap_head_fit_embed_step; head_fit.embed_step_rule in numpy).  The embedding layer of an ArcFace model with the trunk frozen,
+// x -> x w1^T -> BatchNorm1d in TRAINING mode -> dropout -> F.normalize -> ArcMarginProduct -> cross-entropy (the first phase of the
+// reference's two-phase training, src/training.py:374-377, 683-700, src/face_models.py:492-498, 511-535), over cached POOLED trunk
+// features: x, labels and rows are the linear step's; keep [B, E] / keep_scale is the dropout BEHIND the BatchNorm (the reference's
+// position); the parameters are w1 [E, D] (no bias), gamma, beta, running_mean, running_var [E] and the class centres wc [C, E]; the
+// scalars bn_eps, bn_momentum, s, m, ls and the Adam scalars; flags 1 | 2 | 4 | 16 with the margin step's meaning.
+//   declined   layer 1 declines batch row i as the linear step does (row index, label outside [0, C), a non-finite feature):
+//              lab[i] = -1 and row_src1[i] = -1, else the label and the row of x.  n1 = the rows that remain.
+//   a[i][j]  = dot_k(x[i][k], w1[j][k])                                  chain order over D, no bias; a declined row is +0
+//   batch statistics, per column j over the n1 counted rows, in FLOAT64 from the fp32 a (each side's own summation order):
+//              mean = (sum_i a) / n1;  var = (sum_i (a - mean)^2) / n1, the second pass against the float64 mean;
+//              mean32 = fp32(mean), rstd = fp32(1 / sqrt(var + bn_eps)), uvar = fp32((var n1) / (n1 - 1)): one rounding each.
+//              n1 < 2: no statistic exists (torch refuses one value per channel); mean32 = rstd = uvar = +0 and every ah, y' is +0.
+//   ah[i][j] = fp32(((double)a - (double)mean32) (double)rstd)            float64 on the fp32 bits, one rounding
+//   y[i][j]  = fl(fl(gamma[j] ah) + beta[j]);  y' = kept ? fl(y keep_scale) : +0 (no mask: y);  declined rows of ah and y' are +0
+//   margin   = the margin step's forward half on (x := y' [B, E], labels := lab [B], rows := NULL, keep := NULL, w := wc): z, rx,
+//              rw, cosv, g, h, row_loss and the figures of the step are frmap_head_fit_margin_step's on those operands, bit for bit.
+//              Its count is n2; it declines a row whose lab is -1 or whose y' holds a non-finite value; its g and h carry 1 / n2.
+//   taken      the step is TAKEN iff n1 >= 2 and n2 == n1 (all or nothing: a non-finite y' has poisoned a whole column).  A step that
+//              is not taken writes the workspace and nothing else: no parameter, moment, running statistic, epoch figure or t moves;
+//              the word n of the three headers is 0 after it.  CHOSEN HERE: bit 4 (clear) zeroes the epoch figures either way, as
+//              the caller asked; da of a step that is not taken is all +0; gy, dbeta and dgamma are still written.
+//   gy'[i][e]= fl(S - fl(fl(fl(rx_i rx_i) k_i) y'[i][e])),  S = dot_c(gw[i][c], wc[c][e]) chained over C with gw = fl(g[i][c] rw[c])
+//              and wc BEFORE its update, k_i = dot_c(h[i][c], 1) chained over C; the second term is absent where rx_i is not below
+//              fp32(1e12) (the mirror of frmap_head_fit_margin_dw).  gy = kept ? fl(gy' keep_scale) : +0 (no mask: gy').
+//              CHOSEN HERE: a row the margin stage did not count has gy = +0, and gy (after the gate) is what the workspace keeps.
+//   dbeta[j] = dot_i(gy[i][j], 1), dgamma[j] = dot_i(gy[i][j], ah[i][j])   chain order over B, rows declined by layer 1 taken as +0
+//   da[i][j] = fp32((gamma_j rstd_j) ((gy - dbeta_j / n1) - ah (dgamma_j / n1)))   float64 on the fp32 bits in exactly this
+//              association (frmap_head_fit_bn_da), gamma BEFORE its update; declined rows are +0
+//   dw1[j][d]= dot_i(da[i][j], x[i][d]);  dwc = the margin step's own on (y', g, h, rw)
+//   update     frmap_head_fit_adam on w1, gamma (gradient dgamma), beta (gradient dbeta) and wc with the same hyper-parameters and
+//              the same t: one optimiser over four tensors, weight decay on all four as the reference's one parameter group has it.
+//              running_mean = fl(fl(fl(1 - mom) rm) + fl(mom mean32)); running_var likewise with uvar.
+// EMBED STATE (frmap_head_fit_embed_state_bytes; all-zero bytes = fresh): three single layouts back to back, each a multiple of 8 -
+// (D, E) for w1 (its bias moments stay zero), (1, E) for gamma as the "weight" and beta as the "bias", and (E, C), a valid MARGIN
+// STATE of the centres whose header carries t, n and the epoch figures.  The first two headers carry copies of t and n; the second
+// one also serves the margin forward half as the header of the step in flight and has zero figure words between steps.
+// EMBED WORKSPACE (frmap_head_fit_embed_workspace_bytes): fp32 a, ah, y', gy, da [B E], mean32, rstd, uvar, dbeta, dgamma [E], int32
+// lab [B], row_src1 [B], n1 and one padding word, then the margin workspace for (B, C).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -528,4 +568,122 @@ FRMAP_TRACK_HD inline float frmap_head_fit_margin_dw(float A, float k, float rw,
   const float t2 = r2 * k;
   const float t3 = t2 * w;
   return t1 - t3;
+}
+
+// the embedding step (the comment at the top, EMBED)
+FRMAP_TRACK_HD inline bool frmap_head_fit_embed_shape_ok(int D, int E, int C) {
+  return frmap_head_fit_shape_ok(D, E) && frmap_head_fit_shape_ok(E, C) && E <= FRMAP_HEAD_FIT_MAX_D;
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_embed_state_size(int D, int E, int C, int amsgrad) {
+  return frmap_head_fit_state_size(D, E, amsgrad) + frmap_head_fit_state_size(1, E, amsgrad) + frmap_head_fit_state_size(E, C, amsgrad);
+}
+FRMAP_TRACK_HD inline size_t frmap_head_fit_embed_workspace_size(int B, int E, int C) {
+  return 4 * (5 * (size_t)B * (size_t)E + 5 * (size_t)E + 2 * (size_t)B + 2) + frmap_head_fit_margin_workspace_size(B, C);
+}
+struct FrmapHeadFitEmbedState {
+  void *linear, *bn, *margin;            // the single layouts for (D, E), (1, E) and (E, C)
+};
+FRMAP_TRACK_HD inline FrmapHeadFitEmbedState frmap_head_fit_embed_state(void* state, int D, int E, int C, int amsgrad) {
+  FrmapHeadFitEmbedState s;
+  (void)C;
+  s.linear = state;
+  s.bn = (char*)state + frmap_head_fit_state_size(D, E, amsgrad);
+  s.margin = (char*)s.bn + frmap_head_fit_state_size(1, E, amsgrad);
+  return s;
+}
+struct FrmapHeadFitEmbedWork {
+  float *a, *ah, *yp, *gy, *da, *mean32, *rstd, *uvar, *dbeta, *dgamma;
+  int32_t *lab, *row_src1, *n1;
+  void* margin;              // the margin workspace for (B, C)
+};
+FRMAP_TRACK_HD inline FrmapHeadFitEmbedWork frmap_head_fit_embed_work(void* workspace, int B, int E) {
+  FrmapHeadFitEmbedWork k;
+  const size_t be = (size_t)B * (size_t)E;
+  k.a = (float*)workspace;
+  k.ah = k.a + be;
+  k.yp = k.ah + be;
+  k.gy = k.yp + be;
+  k.da = k.gy + be;
+  k.mean32 = k.da + be;
+  k.rstd = k.mean32 + E;
+  k.uvar = k.rstd + E;
+  k.dbeta = k.uvar + E;
+  k.dgamma = k.dbeta + E;
+  k.lab = (int32_t*)(k.dgamma + E);
+  k.row_src1 = k.lab + B;
+  k.n1 = k.row_src1 + B;
+  k.margin = (void*)(k.n1 + 2);
+  return k;
+}
+struct FrmapHeadFitBnHyper {
+  float eps, momentum;
+};
+struct FrmapHeadFitBnStats {
+  float mean32, rstd, uvar;
+};
+// the three statistics of a column from its float64 mean and its float64 sum of squared deviations over n1 >= 2 rows
+FRMAP_TRACK_HD inline FrmapHeadFitBnStats frmap_head_fit_bn_stats(double mean, double sq, uint64_t n1, float eps) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  FrmapHeadFitBnStats s;
+  const double var = sq / (double)n1;
+  const double ve = var + (double)eps;
+  const double vn = var * (double)n1;
+  s.mean32 = (float)mean;
+  s.rstd = (float)(1.0 / sqrt(ve));
+  s.uvar = (float)(vn / (double)(n1 - 1));
+  return s;
+}
+FRMAP_TRACK_HD inline float frmap_head_fit_bn_ah(float a, float mean32, float rstd) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d = (double)a - (double)mean32;
+  return (float)(d * (double)rstd);
+}
+// y' of one element: the affine map, then the dropout behind it (`kept` < 0: no mask)
+FRMAP_TRACK_HD inline float frmap_head_fit_bn_y(float ah, float gamma, float beta, int kept, float keep_scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float t = gamma * ah;
+  const float y = t + beta;
+  return frmap_head_fit_xp(y, kept, keep_scale);
+}
+// gy of one element from the two chains S = dot_c(g rw, wc) and k = dot_c(h, 1)
+FRMAP_TRACK_HD inline float frmap_head_fit_embed_gy(float S, float k, float rx, float yp, int kept, float keep_scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float gyp = S;
+  if (rx < FRMAP_HEAD_FIT_MARGIN_RMAX) {
+    const float r2 = rx * rx;
+    const float t2 = r2 * k;
+    const float t3 = t2 * yp;
+    gyp = S - t3;
+  }
+  if (kept < 0) return gyp;
+  return kept ? gyp * keep_scale : 0.0f;
+}
+FRMAP_TRACK_HD inline float frmap_head_fit_bn_da(float gy, float ah, float gamma, float rstd, float dbeta, float dgamma, uint64_t n1) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double gs = (double)gamma * (double)rstd;
+  const double mb = (double)dbeta / (double)n1;
+  const double mg = (double)dgamma / (double)n1;
+  const double u = (double)gy - mb;
+  const double v = (double)ah * mg;
+  const double t = u - v;
+  return (float)(gs * t);
+}
+FRMAP_TRACK_HD inline float frmap_head_fit_bn_running(float r, float stat, float momentum) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float omm = 1.0f - momentum;
+  const float p = omm * r;
+  const float q = momentum * stat;
+  return p + q;
 }

@@ -9,6 +9,10 @@
 // layer 2 by this twin on (h, lab, keep2) (frmap_head_fit_hidden_step_host, tools/head_fit_hidden_check.cpp).
 // frmap_head_fit_pair_step_twin is the pair step (head_fit_rule.h, PAIR): the projection and the update by frmap_head_fit_dot, the
 // float64 loss and gradient of every pair in between (frmap_head_fit_pair_step_host, tools/head_fit_pair_check.cpp).
+// frmap_head_fit_margin_step_twin is the margin step (head_fit_rule.h, MARGIN; frmap_head_fit_margin_step_host, tools/head_fit_margin_check.cpp).
+// frmap_head_fit_embed_step_twin is the embedding step (head_fit_rule.h, EMBED): layer 1 and every chain by frmap_head_fit_dot, the batch
+// statistics with serial float64 sums, the margin twin on (y', lab) for the margin stage (frmap_head_fit_embed_step_host,
+// tools/head_fit_embed_check.cpp).
 #pragma once
 #include "head_fit_rule.h"
 
@@ -522,6 +526,152 @@ inline const char* frmap_head_fit_margin_step_twin(const float* x, const int32_t
       const size_t at = (size_t)c * (size_t)D + d;
       const float dw = frmap_head_fit_margin_dw(A, k, wk.rw[c], w[at]);
       frmap_head_fit_adam(a, dw, w + at, st.m_w + at, st.v_w + at, amsgrad ? st.vmax_w + at : nullptr);
+    }
+  }
+  return nullptr;
+}
+
+// what an embedding call is refused for: the shared list (bit 16 of the flags is the easy margin), then what only it has
+inline const char* frmap_head_fit_embed_refusal(const void* x, const void* labels, const void* w1, const void* gamma, const void* beta,
+                                                const void* running_mean, const void* running_var, const void* wc, const void* state,
+                                                const void* workspace, int N, int B, int D, int E, int C, int flags) {
+  const void* const required[] = {x, labels, w1, gamma, beta, running_mean, running_var, wc, state, workspace};
+  if (const char* why = frmap_head_fit_refusal(N, B, D, C, flags, 7 | FRMAP_HEAD_FIT_EASY_MARGIN, required, 10,
+                                               "null pointer (x, labels, w1, gamma, beta, running_mean, running_var, wc, state and workspace are required)"))
+    return why;
+  if (E < 1 || E > FRMAP_HEAD_FIT_MAX_D) return "E is outside [1, 65536]";
+  return nullptr;
+}
+
+// The embedding step (head_fit_rule.h, EMBED): layer 1 by frmap_head_fit_dot, the batch statistics with serial float64 sums, the margin
+// twin on (y', lab) for the whole margin stage - on the real centres and their state, which are put back where the step is not taken -,
+// then gy against the wc from BEFORE that update, the two chains over B, da and the updates.  `given` is a bit mask of the float64
+// stages to take from the workspace as INPUTS (the device's own): 1 = mean32, rstd, uvar and ah; 2 = the margin stage, as the margin
+// twin's given_g takes it; 4 = da.
+inline const char* frmap_head_fit_embed_step_twin(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale,
+                                                  float* w1, float* gamma, float* beta, float* running_mean, float* running_var, float* wc,
+                                                  void* state, void* workspace, int N, int B, int D, int E, int C, const FrmapHeadFitBnHyper& bh,
+                                                  const FrmapHeadFitMarginHyper& mh, const FrmapHeadFitHyper& h, int flags, int given) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const char* why = frmap_head_fit_embed_refusal(x, labels, w1, gamma, beta, running_mean, running_var, wc, state, workspace, N, B, D, E, C, flags);
+  if (why) return why;
+  if (given & ~7) return "given has unknown bits (1 statistics and ah, 2 the margin stage, 4 da)";
+  const int amsgrad = (flags & FRMAP_HEAD_FIT_AMSGRAD) ? 1 : 0;
+  const FrmapHeadFitEmbedState es = frmap_head_fit_embed_state(state, D, E, C, amsgrad);
+  const FrmapHeadFitState st1 = frmap_head_fit_state(es.linear, D, E, amsgrad);
+  const FrmapHeadFitState st2 = frmap_head_fit_state(es.bn, 1, E, amsgrad);
+  const FrmapHeadFitState st3 = frmap_head_fit_state(es.margin, E, C, amsgrad);
+  const FrmapHeadFitEmbedWork wk = frmap_head_fit_embed_work(workspace, B, E);
+  const FrmapHeadFitMarginWork mw = frmap_head_fit_margin_work(wk.margin, B, C);
+  uint64_t n1 = 0;
+  for (int i = 0; i < B; ++i) {
+    const int32_t r = wk.row_src1[i] = frmap_head_fit_row_src(x, labels, rows, i, N, D, C);
+    wk.lab[i] = r < 0 ? -1 : labels[r];
+    n1 += r >= 0 ? 1 : 0;
+    float* ar = wk.a + (size_t)i * (size_t)E;
+    for (int j = 0; j < E; ++j) {
+      if (r < 0) {
+        ar[j] = 0.0f;
+        continue;
+      }
+      const float* xr = x + (size_t)r * (size_t)D;
+      const float* wj = w1 + (size_t)j * (size_t)D;
+      ar[j] = frmap_head_fit_dot(D, [&](int k) { return xr[k]; }, [&](int k) { return wj[k]; });
+    }
+  }
+  wk.n1[0] = (int32_t)n1;
+  wk.n1[1] = 0;
+  const bool live = n1 >= 2;
+  for (int j = 0; j < E; ++j) {
+    if (!(given & 1)) {
+      FrmapHeadFitBnStats bs = {0.0f, 0.0f, 0.0f};
+      if (live) {
+        double s = 0.0, q = 0.0;
+        for (int i = 0; i < B; ++i)
+          if (wk.row_src1[i] >= 0) s = s + (double)wk.a[(size_t)i * (size_t)E + j];
+        const double mean = s / (double)n1;
+        for (int i = 0; i < B; ++i) {
+          if (wk.row_src1[i] < 0) continue;
+          const double d = (double)wk.a[(size_t)i * (size_t)E + j] - mean;
+          q = q + d * d;
+        }
+        bs = frmap_head_fit_bn_stats(mean, q, n1, bh.eps);
+      }
+      wk.mean32[j] = bs.mean32;
+      wk.rstd[j] = bs.rstd;
+      wk.uvar[j] = bs.uvar;
+    }
+    for (int i = 0; i < B; ++i) {
+      const size_t at = (size_t)i * (size_t)E + j;
+      const bool counted = live && wk.row_src1[i] >= 0;
+      if (!(given & 1)) wk.ah[at] = counted ? frmap_head_fit_bn_ah(wk.a[at], wk.mean32[j], wk.rstd[j]) : 0.0f;
+      wk.yp[at] = counted ? frmap_head_fit_bn_y(wk.ah[at], gamma[j], beta[j], keep ? (int)keep[at] : -1, keep_scale) : 0.0f;
+    }
+  }
+  // the margin stage on the real centres and their state; both are put back where the step is not taken
+  const size_t n_wc = (size_t)C * (size_t)E, n_st3 = frmap_head_fit_state_size(E, C, amsgrad);
+  float* wc_old = new float[n_wc];
+  unsigned char* st3_old = new unsigned char[n_st3];
+  for (size_t k = 0; k < n_wc; ++k) wc_old[k] = wc[k];
+  __builtin_memcpy(st3_old, es.margin, n_st3);
+  why = frmap_head_fit_margin_step_twin(wk.yp, wk.lab, nullptr, nullptr, 1.0f, wc, es.margin, wk.margin, B, B, E, C, mh, h, flags, (given & 2) ? 1 : 0);
+  if (why) {
+    delete[] wc_old;
+    delete[] st3_old;
+    return why;
+  }
+  const uint64_t n2 = st3.head[FRMAP_HEAD_FIT_N];
+  const bool taken = live && n2 == n1;
+  if (!taken) {
+    for (size_t k = 0; k < n_wc; ++k) wc[k] = wc_old[k];
+    __builtin_memcpy(es.margin, st3_old, n_st3);
+    if (flags & FRMAP_HEAD_FIT_CLEAR) st3.head[FRMAP_HEAD_FIT_ROWS] = st3.head[FRMAP_HEAD_FIT_CORRECT] = st3.head[FRMAP_HEAD_FIT_LOSS_Q] = 0;
+    st3.head[FRMAP_HEAD_FIT_N] = 0;
+  }
+  delete[] st3_old;
+  const uint64_t n = taken ? n1 : 0, t = st3.head[FRMAP_HEAD_FIT_T];
+  st1.head[FRMAP_HEAD_FIT_T] = st2.head[FRMAP_HEAD_FIT_T] = t;
+  st1.head[FRMAP_HEAD_FIT_N] = st2.head[FRMAP_HEAD_FIT_N] = n;
+  st2.head[FRMAP_HEAD_FIT_ROWS] = st2.head[FRMAP_HEAD_FIT_CORRECT] = st2.head[FRMAP_HEAD_FIT_LOSS_Q] = 0;
+  for (int i = 0; i < B; ++i) {
+    const float* gr = mw.g + (size_t)i * (size_t)C;
+    const float* hr = mw.h + (size_t)i * (size_t)C;
+    const bool counted2 = mw.row_src[i] >= 0;
+    const float k = frmap_head_fit_dot(C, [&](int c) { return hr[c]; }, [](int) { return 1.0f; });
+    for (int e = 0; e < E; ++e) {
+      const size_t at = (size_t)i * (size_t)E + e;
+      const float S = frmap_head_fit_dot(C, [&](int c) { return gr[c] * mw.rw[c]; }, [&](int c) { return wc_old[(size_t)c * (size_t)E + e]; });
+      wk.gy[at] = counted2 ? frmap_head_fit_embed_gy(S, k, mw.rx[i], wk.yp[at], keep ? (int)keep[at] : -1, keep_scale) : 0.0f;
+    }
+  }
+  delete[] wc_old;
+  const FrmapHeadFitAdam ad = frmap_head_fit_adam_scalars(t, h, flags);
+  auto gyv = [&](int i, int j) -> float { return wk.row_src1[i] < 0 ? 0.0f : wk.gy[(size_t)i * (size_t)E + j]; };
+  auto ahv = [&](int i, int j) -> float { return wk.row_src1[i] < 0 ? 0.0f : wk.ah[(size_t)i * (size_t)E + j]; };
+  for (int j = 0; j < E; ++j) {
+    const float db = wk.dbeta[j] = frmap_head_fit_dot(B, [&](int i) { return gyv(i, j); }, [](int) { return 1.0f; });
+    const float dg = wk.dgamma[j] = frmap_head_fit_dot(B, [&](int i) { return gyv(i, j); }, [&](int i) { return ahv(i, j); });
+    if (!(given & 4)) {
+      for (int i = 0; i < B; ++i) {
+        const size_t at = (size_t)i * (size_t)E + j;
+        wk.da[at] = (n && wk.row_src1[i] >= 0) ? frmap_head_fit_bn_da(wk.gy[at], wk.ah[at], gamma[j], wk.rstd[j], db, dg, n) : 0.0f;
+      }
+    }
+    if (!n) continue;
+    frmap_head_fit_adam(ad, dg, gamma + j, st2.m_w + j, st2.v_w + j, amsgrad ? st2.vmax_w + j : nullptr);
+    frmap_head_fit_adam(ad, db, beta + j, st2.m_b + j, st2.v_b + j, amsgrad ? st2.vmax_b + j : nullptr);
+    running_mean[j] = frmap_head_fit_bn_running(running_mean[j], wk.mean32[j], bh.momentum);
+    running_var[j] = frmap_head_fit_bn_running(running_var[j], wk.uvar[j], bh.momentum);
+  }
+  if (!n) return nullptr;
+  auto dd = [&](int i, int j) -> float { return wk.row_src1[i] < 0 ? 0.0f : wk.da[(size_t)i * (size_t)E + j]; };
+  for (int j = 0; j < E; ++j) {
+    for (int d = 0; d < D; ++d) {
+      const float dw = frmap_head_fit_dot(B, [&](int i) { return dd(i, j); }, [&](int i) { return wk.row_src1[i] < 0 ? 0.0f : x[(size_t)wk.row_src1[i] * (size_t)D + d]; });
+      const size_t at = (size_t)j * (size_t)D + d;
+      frmap_head_fit_adam(ad, dw, w1 + at, st1.m_w + at, st1.v_w + at, amsgrad ? st1.vmax_w + at : nullptr);
     }
   }
   return nullptr;

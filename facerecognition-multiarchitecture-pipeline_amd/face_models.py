@@ -761,6 +761,13 @@ class ArcFaceNet(_HipModule):
         state.update({f"bn.{k}": v for k, v in self.bn.state_dict().items()})
         return _TrunkPlan("arcface", state, self.val_classifier.out_features, dtype, self.input_mean, self.input_std, owner=self)
 
+    def pooled_features(self, x):
+        """fp32 ``[B, 512]``: the globally pooled trunk output, the input of ``embedding`` - what
+        `head_fit.cache_features(layer="pooled")` caches so that a `head_fit.EmbedHead` can fit ``embedding``, ``bn`` and the class
+        centres.  The per-op plan's ``trunk.pooled``, whatever the switches say; the model's own handle is not touched."""
+        x = self._check_input(x)
+        return self._get_plan(per_op=True)["trunk"].pooled(x)
+
     def forward(self, x, labels=None):
         if self.training:
             if labels is None:

@@ -36,14 +36,22 @@ through a convolution exists here, and none is planned.
   host arithmetic (`margin_schedule`).  `MarginHead.load_into` writes ``arcface.weight`` of an ``ArcFaceNet``, which
   `evaluate.evaluate_model`, `evaluate_stream` and `arcface_validate` score against.
 
-Structure: the steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the seven
+* `embed_step_rule` / `embed_step_host` / `embed_step`, `EmbedHead`, `fit_embed_head` - one step of the embedding layer of an
+  ``ArcFaceNet`` with the trunk frozen (`frmap_head_fit_embed_step`): ``Linear(512, 512, bias=False)`` -> ``BatchNorm1d`` in TRAINING
+  mode (batch statistics, running statistics and its backward pass) -> dropout -> normalize -> the margin head -> cross-entropy, one
+  Adam over ``embedding.weight``, ``bn.weight``, ``bn.bias`` and ``arcface.weight`` - the first phase of the reference's two-phase
+  ArcFace training (`src/training.py:374-377, 683-700`) over cached POOLED trunk features (`cache_features(layer="pooled")`,
+  `ArcFaceNet.pooled_features`).  `EmbedHead.embed` is the deployed arithmetic (running statistics); `EmbedHead.load_into` writes the
+  six tensors, after which the model's own ``get_embedding`` produces the fitted embedding.
+
+Structure: the steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the
 size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk of the device steps and `_host_cache`, `_host_layer`,
 `_host_batch`, `_host_mask` and `_host_buffers` that of the host steps, after which a step lists its operands once and calls the library;
 `_rule_batch` (declined rows, the masked input) and `_adam_rule` are shared by the numpy rules; `_Head` holds the workspace cache, the
 pending clear and the epoch figures of `LinearHead`, `HeadGroup` and `HiddenHead`, `_linear_init` their ``nn.Linear`` draws, and
 `LinearHead._over` makes a head of views; `fit_head` is one loop over a head and its ``(width, dropout)`` mask specs.
 
-Out of scope: groups of hidden heads, ``BatchNorm1d`` in a head, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), groups of margin heads, training ``embedding`` / ``bn`` of an ``ArcFaceNet``, the reference's backward-hook gradient clipping, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
+Out of scope: groups of hidden heads, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), groups of margin and embedding heads, training-mode BatchNorm in the trunk, the reference's backward-hook gradient clipping, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
 from __future__ import annotations
 
@@ -652,14 +660,16 @@ def cache_features(model, model_type: str, data, batch_size: int = 256, device="
     """Embed a training set once: ``[N, D]`` float32 features and ``[N]`` int32 labels on the device, through the model's EVAL-mode
     ``get_embedding`` (the deployed trunk; the reference's frozen phase still runs BatchNorm in training mode - DESIGN.md §4).
     ``data``: an image folder (one sub-directory per class) or an iterable of ``(images, labels)`` batches.
-    ``layer="pooled"`` (``BaselineNet`` only): cache the ``[N, 128]`` input of ``fc1`` (`BaselineNet.pooled_features`) instead, for a
-    `HiddenHead` that fits ``fc1`` and ``fc2``."""
+    ``layer="pooled"`` (``BaselineNet`` and ``ArcFaceNet`` only): cache the ``[N, 128]`` input of ``fc1`` (`BaselineNet.pooled_features`)
+    instead, for a `HiddenHead` that fits ``fc1`` and ``fc2``, or the ``[N, 512]`` input of ``embedding`` (`ArcFaceNet.pooled_features`),
+    for an `EmbedHead` that fits ``embedding``, ``bn`` and the class centres."""
     if model_type == 'siamese':
         raise ValueError("head_fit: a siamese model has no classifier head to fit (pairs are verification_metrics' business)")
     if layer not in ("embedding", "pooled"):
         raise ValueError(f"head_fit.cache_features: layer must be 'embedding' or 'pooled', got {layer!r}")
-    if layer == "pooled" and type(model).__name__ != "BaselineNet":
-        raise ValueError(f"head_fit.cache_features: layer='pooled' is BaselineNet's (the input of its fc1), got {type(model).__name__}")
+    if layer == "pooled" and type(model).__name__ not in ("BaselineNet", "ArcFaceNet"):
+        raise ValueError(f"head_fit.cache_features: layer='pooled' is BaselineNet's (the input of its fc1) and ArcFaceNet's (the input of "
+                         f"its embedding), got {type(model).__name__}")
     return _cache_rows("head_fit.cache_features", model, model.pooled_features if layer == "pooled" else model.get_embedding, data,
                        batch_size, device)
 
@@ -1978,4 +1988,393 @@ def fit_margin_head(model, train_data, val_data=None, epochs: int = 10, batch_si
             tally = evaluate.ClassificationTally(C, device=feats.device)
             tally.update(head.logits(val[0], min(s, 24.0)), val[1])
             history["val"].append(tally.metrics())
+    return head, history
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the embedding layer of an ArcFace model: pooled trunk features in; `embedding`, `bn` and `arcface.weight` out
+# ---------------------------------------------------------------------------------------------------------------------------------
+GIVEN_STATS, GIVEN_MARGIN, GIVEN_DA = 1, 2, 4      # bits of `given` of `embed_step_host`: the float64 stages taken from the workspace
+_DEC_IN = f"D, E, C in 1 ... {MAX_D}"
+
+
+def embed_state_bytes(D: int, E: int, C: int, amsgrad: bool = False) -> int:
+    """Bytes of the state of an embedding head (`frmap_head_fit_embed_state_bytes`): `state_bytes` of (D, E), of (1, E) - gamma as the
+    weight, beta as the bias - and of (E, C), the margin state of the centres."""
+    return _size("frmap_head_fit_embed_state_bytes", _DEC_IN, "D E C", int(D), int(E), int(C), int(bool(amsgrad)))
+
+
+def embed_workspace_bytes(B: int, D: int, E: int, C: int) -> int:
+    """Bytes of the workspace of an embedding step of ``B`` rows (`frmap_head_fit_embed_workspace_bytes`)."""
+    return _size("frmap_head_fit_embed_workspace_bytes", _B_IN + _DEC_IN, "B D E C", int(B), int(D), int(E), int(C))
+
+
+def embed_state_parts(D: int, E: int, C: int, amsgrad: bool = False) -> dict:
+    """name -> (byte offset, bytes) of the three parts of an embedding state."""
+    n1, n2, n3 = state_bytes(D, E, amsgrad), state_bytes(1, E, amsgrad), state_bytes(E, C, amsgrad)
+    assert n1 + n2 + n3 == embed_state_bytes(D, E, C, amsgrad)
+    return {"linear": (0, n1), "bn": (n1, n2), "margin": (n1 + n2, n3)}
+
+
+def embed_state_views(state: np.ndarray, D: int, E: int, C: int, amsgrad: bool = False) -> dict:
+    """``{"linear": state_views of (D, E), "bn": of (1, E), "margin": of (E, C)}`` into a host copy of an embedding state."""
+    raw = np.ascontiguousarray(state).view(np.uint8).reshape(-1)
+    dims = {"linear": (D, E), "bn": (1, E), "margin": (E, C)}
+    return {k: state_views(raw[at: at + n], *dims[k], amsgrad) for k, (at, n) in embed_state_parts(D, E, C, amsgrad).items()}
+
+
+def embed_workspace_views(workspace: np.ndarray, B: int, E: int, C: int) -> dict:
+    """a, ah, yp, gy, da [B, E], mean32, rstd, uvar, dbeta, dgamma [E] (float32), lab, row_src1 [B], n1 (int32) and, under
+    ``"margin"``, `margin_workspace_views` of the margin stage, of a host copy of an embedding workspace."""
+    raw = np.ascontiguousarray(workspace).view(np.uint8).reshape(-1)
+    f = raw[: 4 * (5 * B * E + 5 * E)].view(np.float32)
+    out = {k: f[j * B * E: (j + 1) * B * E].reshape(B, E) for j, k in enumerate(("a", "ah", "yp", "gy", "da"))}
+    out.update({k: f[5 * B * E + j * E: 5 * B * E + (j + 1) * E] for j, k in enumerate(("mean32", "rstd", "uvar", "dbeta", "dgamma"))})
+    at = 4 * (5 * B * E + 5 * E)
+    out.update(lab=raw[at: at + 4 * B].view(np.int32), row_src1=raw[at + 4 * B: at + 8 * B].view(np.int32),
+               n1=raw[at + 8 * B: at + 8 * B + 4].view(np.int32), margin=margin_workspace_views(raw[at + 8 * B + 8:], B, C))
+    return out
+
+
+def embed_fresh_state(D: int, E: int, C: int, amsgrad: bool = False, dtype=np.float64) -> dict:
+    """A state of `embed_step_rule`: ``{"linear", "bn", "margin"}`` of `fresh_state` dicts for (D, E), (1, E) and (E, C)."""
+    return {"linear": fresh_state(D, E, amsgrad, dtype), "bn": fresh_state(1, E, amsgrad, dtype), "margin": fresh_state(E, C, amsgrad, dtype)}
+
+
+def embed_step_rule(x, labels, w1, gamma, beta, running_mean, running_var, wc, state: Optional[dict] = None, rows=None, keep=None,
+                    keep_scale: float = 1.0, *, bn_eps: float = 1e-5, bn_momentum: float = 0.1, s: float, m: float,
+                    easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                    weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+                    clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
+    """One training step of the embedding head, the specification (csrc/head_fit_rule.h, EMBED; include/frmap_hip.h, "Head fitting of an
+    embedding layer").
+
+    ``dtype=np.float64``: the formulas in float64 as torch evaluates ``F.linear`` -> ``nn.BatchNorm1d`` in training mode -> the mask ->
+    `margin_step_rule`'s chain -> one ``optim.Adam`` / ``AdamW`` over the four tensors.  ``dtype=np.float32``: a, S, k and the chains
+    over B by `dot32`; the batch statistics, ah and da in float64 from float32 values and rounded once; the margin stage is
+    `margin_step_rule` in float32 on ``(y', lab)``; `adam32` - what the host twin computes, word for word but for a rare last bit of the
+    float64 stages.  ``given``: any of ``{"mean32", "rstd", "uvar", "ah"}`` (together), ``"margin"`` (`margin_step_rule`'s ``given``)
+    and ``"da"`` to take as they are.  ``state``: `embed_fresh_state`'s shape, or ``None``.
+
+    Nothing is modified: returns the new ``w1, gamma, beta, running_mean, running_var, wc, state`` and ``a, lab, row_src1, n1, n2, taken,
+    mean32, rstd, uvar, ah, yp, gy, dbeta, dgamma, da, dw1, loss`` with the margin stage's own result under ``"margin"``."""
+    f32 = np.dtype(dtype) == np.dtype(np.float32)
+    given = given or {}
+    x = np.asarray(x, F32 if f32 else np.float64)
+    w1, gamma, beta, rm, rv = (np.array(t, dtype) for t in (w1, gamma, beta, running_mean, running_var))
+    wc_old = np.array(wc, dtype)
+    labels = np.asarray(labels).astype(np.int64)
+    N, D = x.shape
+    E, C = w1.shape[0], wc_old.shape[0]
+    state = state or embed_fresh_state(D, E, C, amsgrad, dtype)
+    row_src1, ok1, xz = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), None, 1.0, f32)
+    B = len(row_src1)
+    n1 = int(ok1.sum())
+    live = n1 >= 2
+    lab = np.where(ok1, labels[np.clip(row_src1, 0, N - 1)], -1).astype(np.int32)
+    kept = np.asarray(keep).astype(bool) if keep is not None else None
+    with np.errstate(all="ignore"):
+        a = dot32(xz[:, None, :], w1[None, :, :]).astype(F32) if f32 else xz @ w1.T
+        a[~ok1] = 0
+        a64 = a.astype(np.float64)
+        if "ah" in given:
+            mean32, rstd, uvar, ah = (np.array(given[k], dtype) for k in ("mean32", "rstd", "uvar", "ah"))
+        elif not live:
+            mean32, rstd, uvar, ah = np.zeros(E, dtype), np.zeros(E, dtype), np.zeros(E, dtype), np.zeros((B, E), dtype)
+        else:
+            mean = a64[ok1].sum(axis=0) / n1
+            var = ((a64[ok1] - mean) ** 2).sum(axis=0) / n1
+            mean32 = mean.astype(dtype)
+            rstd = (1.0 / np.sqrt(var + float(F32(bn_eps) if f32 else bn_eps))).astype(dtype)
+            uvar = ((var * n1) / (n1 - 1)).astype(dtype)
+            ah = ((a64 - (mean32.astype(np.float64) if f32 else mean)) * rstd.astype(np.float64)).astype(dtype)
+            ah[~ok1] = 0
+        y = (gamma[None, :] * ah).astype(dtype) + beta[None, :]
+        yp = y.astype(dtype)
+        if kept is not None:
+            yp = np.where(kept, (y * (F32(keep_scale) if f32 else float(keep_scale))).astype(dtype), 0).astype(dtype)
+        yp[~ok1] = 0
+        if not live:
+            yp[:] = 0
+    r2 = margin_step_rule(yp, lab, wc_old, state["margin"], None, None, 1.0, s=s, m=m, easy_margin=easy_margin, lr=lr, beta1=beta1,
+                          beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled,
+                          amsgrad=amsgrad, clear=clear, dtype=dtype, given=given.get("margin"), batch=B)
+    n2, ok2 = r2["n"], r2["ok"]
+    taken = live and n2 == n1
+    n = n1 if taken else 0
+    gz, hz = np.where(ok2[:, None], r2["g"], 0).astype(dtype), np.where(ok2[:, None], r2["h"], 0).astype(dtype)
+    rx, rw = np.asarray(r2["rx"], dtype), np.asarray(r2["rw"], dtype)
+    with np.errstate(all="ignore"):
+        if f32:
+            gw = (gz * rw[None, :]).astype(F32)
+            S = dot32(gw[:, None, :], wc_old.T[None, :, :])
+            k = dot32(hz, np.ones((1, C), F32))
+            t3 = (((rx * rx).astype(F32) * k).astype(F32)[:, None] * yp).astype(F32)
+            gyp = np.where((rx < MARGIN_RMAX)[:, None], (S - t3).astype(F32), S)
+            gy = gyp if kept is None else np.where(kept, (gyp * F32(keep_scale)).astype(F32), 0)
+        else:
+            free = rx < 1.0 / NORM_EPS
+            gyp = (gz * rw[None, :]) @ wc_old - np.where(free, rx * rx * hz.sum(axis=1), 0.0)[:, None] * yp
+            gy = gyp if kept is None else np.where(kept, gyp * float(keep_scale), 0)
+        gy = np.where(ok2[:, None], gy, 0).astype(dtype)
+        gyz, ahz = np.where(ok1[:, None], gy, 0).astype(dtype), np.where(ok1[:, None], ah, 0).astype(dtype)
+        if f32:
+            dbeta = dot32(gyz.T, np.ones((1, B), F32))
+            dgamma = dot32(gyz.T, ahz.T)
+        else:
+            dbeta, dgamma = gyz.sum(axis=0), (gyz * ahz).sum(axis=0)
+        if "da" in given:
+            da = np.array(given["da"], dtype)
+        elif not taken:
+            da = np.zeros((B, E), dtype)
+        else:
+            g64, r64, b64, d64 = (t.astype(np.float64) for t in (gamma, rstd, dbeta, dgamma))
+            da = ((g64 * r64)[None, :] * ((gy.astype(np.float64) - (b64 / n1)[None, :]) - ah.astype(np.float64) * (d64 / n1)[None, :])).astype(dtype)
+            da[~ok1] = 0
+        daz = np.where(ok1[:, None], da, 0).astype(dtype)
+        dw1 = dot32(daz.T[:, None, :], xz.T[None, :, :]) if f32 else daz.T @ xz
+    st1, st2 = _copy_state(state["linear"], dtype), _copy_state(state["bn"], dtype)
+    if taken:
+        st3, wc_new = r2["state"], r2["w"]
+        kw = dict(t=st3["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad, f32=f32)
+        w1 = _adam_rule(w1, dw1, st1, "w", **kw)
+        gamma = _adam_rule(gamma[:, None], dgamma[:, None], st2, "w", **kw)[:, 0]
+        beta = _adam_rule(beta, dbeta, st2, "b", **kw)
+        if f32:
+            mom = F32(bn_momentum)
+            omm = F32(F32(1) - mom)
+            rm = (omm * rm).astype(F32) + (mom * mean32).astype(F32)
+            rv = (omm * rv).astype(F32) + (mom * uvar).astype(F32)
+        else:
+            rm = (1.0 - bn_momentum) * rm + bn_momentum * mean32
+            rv = (1.0 - bn_momentum) * rv + bn_momentum * uvar
+    else:
+        st3, wc_new = _copy_state(state["margin"], dtype), wc_old
+        if clear:
+            st3["rows"] = st3["correct"] = st3["loss_q"] = 0
+        st3["n"] = 0
+    for st in (st1, st2):
+        st["t"], st["n"] = st3["t"], n
+    return {"w1": w1, "gamma": gamma, "beta": beta, "running_mean": rm, "running_var": rv, "wc": wc_new,
+            "state": {"linear": st1, "bn": st2, "margin": st3}, "a": a, "lab": lab, "row_src1": row_src1, "n1": n1, "n2": n2, "taken": taken,
+            "mean32": mean32, "rstd": rstd, "uvar": uvar, "ah": ah, "yp": yp, "gy": gy, "dbeta": dbeta, "dgamma": dgamma, "da": da, "dw1": dw1,
+            "loss": r2["loss"], "margin": r2}
+
+
+def _host_vectors(op, E, **vectors):
+    for name, v in vectors.items():
+        _host_array(op, name, v, np.float32)
+        if v.shape != (E,):
+            raise ValueError(f"{op}: {name} [{E}] expected, got {v.shape}")
+
+
+def embed_step_host(x, labels, w1, gamma, beta, running_mean, running_var, wc, state: np.ndarray, workspace: Optional[np.ndarray] = None,
+                    rows=None, keep=None, keep_scale: float = 1.0, *, bn_eps: float = 1e-5, bn_momentum: float = 0.1, s: float, m: float,
+                    easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                    weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
+                    clear: bool = False, given: int = 0, batch: Optional[int] = None):
+    """The embedding step on the CPU over numpy arrays (`frmap_head_fit_embed_step_host`; no GPU).  ``w1`` [E, D], ``gamma``, ``beta``,
+    ``running_mean``, ``running_var`` [E], ``wc`` [C, E] (float32) and ``state`` (uint8, `embed_state_bytes` bytes, 8-byte aligned) are
+    updated IN PLACE; ``workspace`` (uint8, exactly `embed_workspace_bytes` bytes, or ``None`` for a fresh one) receives every
+    intermediate (`embed_workspace_views`).  ``given``: bits `GIVEN_STATS` | `GIVEN_MARGIN` | `GIVEN_DA` - the float64 stages whose
+    outputs in the workspace are inputs.  Returns the workspace."""
+    op = "head_fit.embed_step_host"
+    x, labels, N, D = _host_cache(op, x, labels)
+    for name, t in (("w1", w1), ("wc", wc)):
+        _host_array(op, name, t, np.float32)
+    if w1.ndim != 2 or w1.shape[1] != D:
+        raise ValueError(f"{op}: w1 [E, {D}] expected, got {w1.shape}")
+    E = int(w1.shape[0])
+    if wc.ndim != 2 or wc.shape[1] != E:
+        raise ValueError(f"{op}: wc [C, {E}] expected, got {wc.shape}")
+    C = int(wc.shape[0])
+    _host_vectors(op, E, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
+    rows, B = _host_batch(op, N, rows, (keep,), batch)
+    keep = _host_mask(op, "keep", keep, (B, E))
+    workspace = _host_buffers(op, state, embed_state_bytes(D, E, C, amsgrad), workspace, embed_workspace_bytes(B, D, E, C), bool(given))
+    _lib.check(_lib.load().frmap_head_fit_embed_step_host(
+        _at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w1), _at(gamma), _at(beta), _at(running_mean), _at(running_var),
+        _at(wc), _at(state), _at(workspace), N, B, D, E, C, float(bn_eps), float(bn_momentum), float(s), float(m), float(label_smoothing),
+        float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), _margin_flags(decoupled, amsgrad, clear, easy_margin),
+        int(given)), op)
+    return workspace
+
+
+@ops._on_operand_device
+def embed_step(x: torch.Tensor, labels: torch.Tensor, w1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+               running_var: torch.Tensor, wc: torch.Tensor, state: torch.Tensor, workspace: torch.Tensor, rows: Optional[torch.Tensor] = None,
+               keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0, *, bn_eps: float = 1e-5, bn_momentum: float = 0.1, s: float,
+               m: float, easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+               weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
+               batch: Optional[int] = None) -> None:
+    """One embedding training step on the current stream (`frmap_head_fit_embed_step`; nothing is copied or synchronised).  ``x`` float32
+    ``[N, D]`` (the cache of pooled features), ``labels`` int32 ``[N]``, ``w1`` ``[E, D]``, ``gamma``, ``beta``, ``running_mean``,
+    ``running_var`` ``[E]`` and ``wc`` ``[C, E]`` float32 (updated in place), ``state`` uint8 of `embed_state_bytes` bytes (zeros = fresh),
+    ``workspace`` uint8 of exactly `embed_workspace_bytes` bytes, ``rows`` int32 ``[B]`` or ``None``, ``keep`` uint8 ``[B, E]`` or ``None``
+    (the dropout behind the BatchNorm); ``s`` and ``m`` are the effective scale and margin of this step (`margin_schedule`).  Every
+    extent that depends on another operand is checked here, before the library sees a pointer."""
+    op, entry = "head_fit.embed_step", "frmap_head_fit_embed_step"
+    x, N, D = _cache(op, entry, x, labels)
+    _sized(w1, op, "w1", (w1.shape[0] if isinstance(w1, torch.Tensor) and w1.dim() == 2 else -1, D), torch.float32)
+    E = int(w1.shape[0])
+    _sized(wc, op, "wc", (wc.shape[0] if isinstance(wc, torch.Tensor) and wc.dim() == 2 else -1, E), torch.float32)
+    C = int(wc.shape[0])
+    vectors = {"gamma": gamma, "beta": beta, "running_mean": running_mean, "running_var": running_var}
+    for name, t in vectors.items():
+        _sized(t, op, name, (E,), torch.float32)
+    rows, B = _batch(op, entry, N, rows, (keep,), batch)
+    if keep is not None:
+        _sized(keep, op, "keep", (B, E), torch.uint8)
+    _sized(state, op, "state", (embed_state_bytes(D, E, C, amsgrad),), torch.uint8)
+    _sized(workspace, op, "workspace", (embed_workspace_bytes(B, D, E, C),), torch.uint8)
+    labels = _operand(labels, op, entry, "labels", torch.int32)
+    keep = _operand(keep, op, entry, "keep", torch.uint8)
+    w1, wc = _operand(w1, op, entry, "w1", torch.float32, True), _operand(wc, op, entry, "wc", torch.float32, True)
+    gamma, beta, running_mean, running_var = (_operand(t, op, entry, name, torch.float32, True) for name, t in vectors.items())
+    state = _operand(state, op, entry, "state", torch.uint8, True)
+    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _lib.check(_lib.load().frmap_head_fit_embed_step(
+        x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w1.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+        running_mean.data_ptr(), running_var.data_ptr(), wc.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, E, C, float(bn_eps),
+        float(bn_momentum), float(s), float(m), float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        _margin_flags(decoupled, amsgrad, clear, easy_margin), _stream()), op)
+
+
+class EmbedHead(_Head):
+    """``Linear(D, E, bias=False) -> BatchNorm1d(E) -> dropout -> normalize -> margin`` on the device with its Adam state and a workspace:
+    the ``embedding``, ``bn`` and ``arcface`` of the reference's ``ArcFaceNet`` over its pooled trunk features
+    (`cache_features(layer="pooled")`).  A new head starts as those modules do (``nn.Linear`` and the margin's ``xavier_normal_`` draws
+    from ``generator``, gamma 1, beta 0, running statistics 0 and 1); `from_model` starts from a model's own tensors.  `embed` is the
+    deployed embedding - the RUNNING statistics, as `ArcFaceNet.get_embedding` applies them."""
+
+    def __init__(self, D: int, E: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None,
+                 bn_eps: float = 1e-5, bn_momentum: float = 0.1):
+        w1 = _linear_init(int(E), int(D), generator)[0]
+        std = math.sqrt(2.0) * math.sqrt(2.0 / (int(E) + int(C)))
+        wc = torch.empty((int(C), int(E)), dtype=torch.float32).normal_(0.0, std, generator=generator)
+        self._adopt(w1, torch.ones(int(E)), torch.zeros(int(E)), torch.zeros(int(E)), torch.ones(int(E)), wc, device, amsgrad, bn_eps, bn_momentum)
+
+    def _adopt(self, w1, gamma, beta, running_mean, running_var, wc, device, amsgrad, bn_eps, bn_momentum):
+        self.E, self.D, self.C, self.amsgrad = int(w1.shape[0]), int(w1.shape[1]), int(wc.shape[0]), bool(amsgrad)
+        self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
+        nbytes = embed_state_bytes(self.D, self.E, self.C, self.amsgrad)           # (refuses a bad shape)
+        device = torch.device(device)
+        self.w1, self.gamma, self.beta, self.running_mean, self.running_var, self.wc = (
+            t.detach().to(device=device, dtype=torch.float32).clone().contiguous() for t in (w1, gamma, beta, running_mean, running_var, wc))
+        self._header_at = embed_state_parts(self.D, self.E, self.C, self.amsgrad)["margin"][0]    # the figures are the margin state's
+        self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
+
+    @classmethod
+    def from_model(cls, model, device=None, amsgrad: bool = False) -> "EmbedHead":
+        """A head that starts from ``embedding.weight``, ``bn`` and ``arcface.weight`` of an ``ArcFaceNet`` (copies: the model changes
+        only through `load_into`)."""
+        emb, bn, arc = (getattr(model, k, None) for k in ("embedding", "bn", "arcface"))
+        if type(model).__name__ != "ArcFaceNet" or not isinstance(emb, torch.nn.Linear) or not isinstance(bn, torch.nn.BatchNorm1d) or \
+                not isinstance(getattr(arc, "weight", None), torch.Tensor):
+            raise ValueError(f"EmbedHead.from_model: an ArcFaceNet expected, got {type(model).__name__}")
+        if emb.bias is not None:
+            raise ValueError("EmbedHead.from_model: embedding has a bias; the head has none")
+        one = cls.__new__(cls)
+        one._adopt(emb.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, arc.weight, device if device is not None else emb.weight.device,
+                   amsgrad, bn.eps, 0.1 if bn.momentum is None else bn.momentum)
+        return one
+
+    def _workspace_bytes(self, B: int) -> int:
+        return embed_workspace_bytes(B, self.D, self.E, self.C)
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor, rows: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, *,
+             lr: float, s: float, m: float, easy_margin: bool = False, label_smoothing: float = 0.0, keep_scale: Optional[float] = None,
+             dropout: float = 0.0, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+             decoupled: bool = False) -> "EmbedHead":
+        """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`embed_step`) at the effective scale ``s`` and margin ``m``.
+        ``keep``: a uint8 ``[B, E]`` dropout mask behind the BatchNorm, scaled by ``keep_scale`` (default ``1 / (1 - dropout)``).  No
+        synchronisation."""
+        if keep_scale is None:
+            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
+        B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
+            int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
+        return self._run(embed_step, x, labels, self.w1, self.gamma, self.beta, self.running_mean, self.running_var, self.wc, self.state,
+                         self._workspace(B), rows, keep, keep_scale, bn_eps=self.bn_eps, bn_momentum=self.bn_momentum, s=s, m=m,
+                         easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                         label_smoothing=label_smoothing, decoupled=decoupled)
+
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """``normalize(bn_eval(x w1^T))`` of pooled-feature rows ``x`` ``[B, D]`` with the RUNNING statistics: the arithmetic of the
+        deployed ``ArcFaceNet.get_embedding`` behind its trunk (`ops.linear_f32` with the folded scale and shift, `ops.l2_normalize`)."""
+        scale = self.gamma / torch.sqrt(self.running_var + self.bn_eps)
+        shift = self.beta - self.running_mean * scale
+        return ops.l2_normalize(ops.linear_f32(x, self.w1, scale.contiguous(), shift.contiguous()), 1e-12)
+
+    def centres(self) -> "MarginHead":
+        """The class centres as a `MarginHead` whose ``weight`` and ``state`` are VIEWS of this head's memory (the last part of the
+        state is a valid margin state): its `cosines` and `logits` take `embed` outputs."""
+        at, n = embed_state_parts(self.D, self.E, self.C, self.amsgrad)["margin"]
+        one = MarginHead.__new__(MarginHead)
+        one.D, one.C, one.amsgrad, one.weight = self.E, self.C, self.amsgrad, self.wc
+        one._start(self.state[at: at + n], self.device, False)
+        return one
+
+    def state_dict(self) -> dict:
+        return {"embedding.weight": self.w1.detach().clone(), "bn.weight": self.gamma.detach().clone(), "bn.bias": self.beta.detach().clone(),
+                "bn.running_mean": self.running_mean.detach().clone(), "bn.running_var": self.running_var.detach().clone(),
+                "arcface.weight": self.wc.detach().clone()}
+
+    def load_into(self, model) -> None:
+        """Copy the six tensors into ``embedding.weight``, ``bn.weight``, ``bn.bias``, ``bn.running_mean``, ``bn.running_var`` and
+        ``arcface.weight`` of an ``ArcFaceNet`` in place and advance ``bn.num_batches_tracked`` by the steps taken since the last
+        `load_into` (one host copy of the step count); any other class and any other shape is refused by name.  The model's plan
+        watches its parameters and buffers: the next forward rebuilds."""
+        emb, bn, arc = (getattr(model, k, None) for k in ("embedding", "bn", "arcface"))
+        if type(model).__name__ != "ArcFaceNet" or not isinstance(emb, torch.nn.Linear) or not isinstance(bn, torch.nn.BatchNorm1d) or \
+                not isinstance(getattr(arc, "weight", None), torch.Tensor):
+            raise ValueError(f"EmbedHead.load_into: an ArcFaceNet expected, got {type(model).__name__}")
+        pairs = (("embedding.weight", emb.weight, self.w1), ("bn.weight", bn.weight, self.gamma), ("bn.bias", bn.bias, self.beta),
+                 ("bn.running_mean", bn.running_mean, self.running_mean), ("bn.running_var", bn.running_var, self.running_var),
+                 ("arcface.weight", arc.weight, self.wc))
+        for name, dst, src in pairs:
+            if not isinstance(dst, torch.Tensor) or tuple(dst.shape) != tuple(src.shape):
+                raise ValueError(f"EmbedHead.load_into: {name} is {list(dst.shape) if isinstance(dst, torch.Tensor) else None}, "
+                                 f"the head's is {list(src.shape)}")
+        t = self.epoch_figures()["t"]
+        with torch.no_grad():
+            for _, dst, src in pairs:
+                dst.copy_(src)
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked += t - getattr(self, "_loaded_t", 0)
+        self._loaded_t = t
+
+
+def fit_embed_head(model, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3, weight_decay: float = 1e-4,
+                   dropout: float = 0.2, s: float = 32.0, m: float = 0.5, easy_margin: bool = False, warm_up: bool = True,
+                   label_smoothing: float = 0.05, decoupled: bool = True, amsgrad: bool = True,
+                   generator: Optional[torch.Generator] = None, device="cuda"):
+    """Fit ``embedding``, ``bn`` and the class centres of a frozen ``ArcFaceNet`` with the reference's ArcFace objective: the first phase
+    of its two-phase training on the device.  The pooled trunk features of the training set are cached once
+    (`cache_features(layer="pooled")`); the head starts from the model's own tensors (`EmbedHead.from_model`; the class count is the
+    model's); epoch ``e`` runs at `margin_schedule(e, s, m)`; every epoch draws a fresh device permutation as ``rows`` and, with
+    ``dropout``, a mask per step, and steps through it with no host copy inside the epoch.  A trailing batch of one row is a step that
+    is not taken (BatchNorm has no statistics of one row).  The defaults are the reference's ArcFace settings (`src/training.py:340-348`;
+    ``dropout_rate=0.2``).  With ``val_data`` every epoch's validation accuracy is the arg-max of `ops.cosine_logits` of `EmbedHead.embed`
+    against the centres.  The model is not changed: call ``head.load_into(model)``.  Returns ``(head, history)`` in `fit_head`'s shape."""
+    feats, labels = cache_features(model, "arcface", train_data, device=device, layer="pooled")
+    N = int(feats.shape[0])
+    head = EmbedHead.from_model(model, feats.device, amsgrad=amsgrad)
+    _, dev_gen = _generators(generator, feats.device)
+    val = cache_features(model, "arcface", val_data, device=device, layer="pooled") if val_data is not None else None
+    history = {"train_loss": [], "train_acc": [], "val": []}
+    for epoch in range(int(epochs)):
+        m_eff, s_eff = margin_schedule(epoch, s, m, warm_up=warm_up)
+        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, int(batch_size)):
+            rows = perm[lo: lo + int(batch_size)]
+            keep = (torch.rand((rows.shape[0], head.E), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
+            head.step(feats, labels, rows, keep, lr=lr, s=s_eff, m=m_eff, easy_margin=easy_margin, label_smoothing=label_smoothing,
+                      dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)
+        fig = head.epoch_figures()
+        history["train_loss"].append(fig["loss"])
+        history["train_acc"].append(fig["accuracy"])
+        if val is not None:
+            pred = ops.cosine_logits(head.embed(val[0]), head.wc, s=1.0, want_logits=False, want_argmax=True)[1]
+            history["val"].append({"accuracy": float((pred.to(torch.int64) == val[1].to(torch.int64)).float().mean().item())})
     return head, history

@@ -861,6 +861,56 @@ int frmap_head_fit_margin_step_host(const float* x_host, const int32_t* labels_h
                                     float s, float m, float label_smoothing, float lr, float beta1, float beta2, float eps,
                                     float weight_decay, int flags, int given_g);
 
+/* Head fitting of an embedding layer: one training step of x -> x w1^T -> BatchNorm1d (TRAINING mode) -> dropout -> normalize ->
+ * ArcMarginProduct -> cross-entropy with the trunk frozen - the `embedding`, `bn` and `arcface` tensors of the reference's ArcFaceNet
+ * under one optimiser, the first phase of its two-phase training (src/training.py:374-377, 683-700, src/face_models.py:492-498,
+ * 511-535) - over cached POOLED trunk features.  One small memset and ten launches on the caller's stream, nothing copied to the
+ * host, nothing allocated, no floating-point atomic.
+ *
+ * Operands: x, labels, rows as in frmap_head_fit_step (the cache should hold the pooled trunk features); keep [B][E] uint8 or NULL
+ * with keep_scale: the dropout BEHIND the BatchNorm; w1 [E][D] (no bias), gamma, beta, running_mean, running_var [E] and the class
+ * centres wc [C][E], all fp32 and updated in place; bn_eps, bn_momentum: BatchNorm1d's; s, m: the effective scale and margin as in
+ * frmap_head_fit_margin_step.  flags: 1 | 2 | 4 | 16 as there.
+ * The rule (dot products are the single step's chains; layer 1 declines rows as the single step does, n1 remain):
+ *   a[i][j]  = dot_k(x[i][k], w1[j][k]); a declined row is +0
+ *   per column over the n1 counted rows, in float64 from the fp32 a: mean, var = sum (a - mean)^2 / n1 (two passes);
+ *              mean32 = fp32(mean), rstd = fp32(1 / sqrt(var + bn_eps)), uvar = fp32(var n1 / (n1 - 1)); all +0 where n1 < 2
+ *   ah       = fp32((a - mean32) rstd) in float64 on the fp32 bits;  y = fl(fl(gamma ah) + beta);  y' = kept ? fl(y keep_scale) : +0
+ *   margin   : frmap_head_fit_margin_step's forward half on (x := y', labels := lab, rows := NULL, keep := NULL, w := wc), bit for
+ *              bit; its count is n2
+ *   taken    : iff n1 >= 2 and n2 == n1.  A step that is not taken writes the workspace and nothing else - no parameter, moment,
+ *              running statistic, epoch figure or step count moves (bit 4 still clears the figures); word n of the headers is 0.
+ *   gy       = gate (S - rx^2 k y'), S = dot_c(fl(g rw[c]), wc[c][e]) with wc before its update, k = dot_c(h, 1), every product and
+ *              the difference rounded once; the second term is absent where rx is not below fp32(1e12)
+ *   dbeta    = dot_i(gy, 1), dgamma = dot_i(gy, ah);  da = fp32((gamma rstd) ((gy - dbeta / n1) - ah (dgamma / n1))) in float64
+ *   dw1      = dot_i(da[i][j], x[i][d]);  dwc = the margin step's own
+ *   update   : Adam / AdamW on w1, gamma, beta and wc with one t;  running_mean = fl(fl((1 - mom) rm) + fl(mom mean32)), running_var
+ *              likewise with uvar.
+ * state : frmap_head_fit_embed_state_bytes bytes, zeroed by the caller before the first step: the single step's layout for (D, E),
+ *         for (1, E) (gamma as the weight, beta as the bias) and for (E, C), each a multiple of 8.  The last part is a valid state of
+ *         frmap_head_fit_margin_step for the centres: its header carries t, n and the epoch figures.
+ * workspace : exactly frmap_head_fit_embed_workspace_bytes bytes: fp32 a, ah, y', gy, da [B][E], mean32, rstd, uvar, dbeta, dgamma
+ *         [E], int32 lab [B], row_src1 [B], n1 and one padding word, then the margin workspace for (B, C).  D does not enter the size.
+ * The size queries take no stream and return 0 for arguments the launcher would refuse.
+ * Refused (-1, the text names the argument): N < 1; B < 1 or above 2^20; D, E or C < 1 or above 65536; flag bits outside
+ * 1 | 2 | 4 | 16; a required pointer that is NULL (rows and keep may be).
+ * Every pointer is walked element by element: x, labels, rows, w1, gamma, beta, running_mean, running_var, wc and workspace need
+ * their element size (4), keep 1, state the size of a uint64 counter (8).
+ * The host form is the same step compiled for the CPU (host pointers, no stream).  `given` is a bit mask of the float64 stages whose
+ * outputs in the workspace are INPUTS - the device's own: 1 = mean32, rstd, uvar and ah; 2 = the margin stage (z, cosv, g, h, row_loss,
+ * rx, rw, as given_g of frmap_head_fit_margin_step_host); 4 = da.  Other bits are refused. */
+size_t frmap_head_fit_embed_state_bytes(int D, int E, int C, int amsgrad);
+size_t frmap_head_fit_embed_workspace_bytes(int B, int D, int E, int C);
+int frmap_head_fit_embed_step(const float* x, const int32_t* labels, const int32_t* rows, const uint8_t* keep, float keep_scale, float* w1,
+                              float* gamma, float* beta, float* running_mean, float* running_var, float* wc, void* state, void* workspace,
+                              int N, int B, int D, int E, int C, float bn_eps, float bn_momentum, float s, float m, float label_smoothing,
+                              float lr, float beta1, float beta2, float eps, float weight_decay, int flags, void* stream);
+int frmap_head_fit_embed_step_host(const float* x_host, const int32_t* labels_host, const int32_t* rows_host, const uint8_t* keep_host,
+                                   float keep_scale, float* w1_host, float* gamma_host, float* beta_host, float* running_mean_host,
+                                   float* running_var_host, float* wc_host, void* state_host, void* workspace_host, int N, int B, int D,
+                                   int E, int C, float bn_eps, float bn_momentum, float s, float m, float label_smoothing, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int flags, int given);
+
 /* Scratch frmap_cosine_logits / frmap_arcmargin_eval need (device, caller-owned, >= this many bytes, 16-byte
  * aligned). */
 size_t frmap_head_workspace_bytes(int B, int C);
