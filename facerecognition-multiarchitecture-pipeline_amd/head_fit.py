@@ -44,12 +44,16 @@ through a convolution exists here, and none is planned.
   `ArcFaceNet.pooled_features`).  `EmbedHead.embed` is the deployed arithmetic (running statistics); `EmbedHead.load_into` writes the
   six tensors, after which the model's own ``get_embedding`` produces the fitted embedding.
 
-Structure: the steps differ in their operands, and everything around the operands exists once.  `_size` stands behind the
-size functions; `_cache`, `_layer`, `_batch` and `_operand` are the operand walk of the device steps and `_host_cache`, `_host_layer`,
-`_host_batch`, `_host_mask` and `_host_buffers` that of the host steps, after which a step lists its operands once and calls the library;
-`_rule_batch` (declined rows, the masked input) and `_adam_rule` are shared by the numpy rules; `_Head` holds the workspace cache, the
-pending clear and the epoch figures of `LinearHead`, `HeadGroup` and `HiddenHead`, `_linear_init` their ``nn.Linear`` draws, and
-`LinearHead._over` makes a head of views; `fit_head` is one loop over a head and its ``(width, dropout)`` mask specs.
+Structure: the steps differ in their operands, and everything around the operands exists once.  The numpy rules - the specification -
+are `head_fit_rules`, which imports neither torch nor the library; every name of it is re-exported here.  `_size` stands behind the size
+functions.  `_cache`, `_layer`, `_batch`, `_mask`, `_buffers` and `_reads` are the operand walk of the device steps and `_host_cache`,
+`_host_layer`, `_host_batch`, `_host_mask` and `_host_buffers` that of the host steps: every size is checked before the first operand is
+converted, after which a step calls the library, its Adam scalars from `_adam`.  `_Head` holds the workspace cache, the pending clear,
+the epoch figures, the default mask scale and the batch-row count of every head; `_linear_init` and `_margin_init` are their draws,
+`_arcface_parts` and `_load` what their `load_into` methods share, and `LinearHead._over` makes a head of views.  `_fit` is the one epoch
+loop (history, `new_epoch`, `epoch_figures`, the validation hook) and `_row_epochs` the row-based epoch (a permutation, one mask per
+``(width, dropout)`` spec, `head.step`) of `fit_head`, `fit_margin_head` and `fit_embed_head`; `fit_pair_head` brings its own epoch to
+`_fit`.  The ORDER OF DRAWS of a fit is behaviour and stands in its docstring: `fit_head` draws the head first, the others the seed.
 
 Out of scope: groups of hidden heads, more than one hidden layer, gradient clipping, learning-rate schedulers (the caller passes ``lr`` per step), groups of margin and embedding heads, training-mode BatchNorm in the trunk, the reference's backward-hook gradient clipping, triplet loss, in-batch mining and groups of pair heads, anything that trains a convolution, Optuna's sampler, pruner and schedulers (the caller supplies the trials).
 """
@@ -63,9 +67,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .head_fit_rules import (CHAIN, DIST_EPS, DIST_MIN, F32, LOSS_CLAMP, LOSS_SCALE, MARGIN_CAP, MARGIN_HI, MARGIN_RMAX,  # noqa: F401
+                             NORM_EPS, _adam_rule, _copy_state, _powi, _rule_batch, adam32, adam_scalars32, dot32, embed_fresh_state,
+                             embed_step_rule, fma32, fresh_state, group_step_rule, hidden_step_rule, loss_q, margin_logits_rule,
+                             margin_schedule, margin_step_rule, pair_loss_rule, pair_step_rule, step_rule)
 from .ops import _dev, _sized, _stream
 
-CHAIN = 128                       # FRMAP_HEAD_FIT_CHAIN: where the dot products are cut
 MAX_C = MAX_D = 65536
 MAX_B = 1 << 20
 DECOUPLED, AMSGRAD, CLEAR = 1, 2, 4
@@ -73,8 +80,6 @@ EVAL = 8                          # grouped step only: figures, no update
 MAX_H = 4096                      # heads of one group
 HYPER_COLUMNS = ("lr", "beta1", "beta2", "eps", "weight_decay", "label_smoothing", "keep_scale")     # of the [H, 8] table; column 7 is 0
 HEADER = ("t", "n", "rows", "correct", "loss_q")     # words 0 .. 4 of the 8-word header
-LOSS_CLAMP, LOSS_SCALE = 65536.0, 16777216.0         # the tally's fixed point (csrc/tally_rule.h)
-F32 = np.float32
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -140,227 +145,15 @@ def figures_of(head_words) -> dict:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the rule
-# ---------------------------------------------------------------------------------------------------------------------------------
-def fma32(a, b, c):
-    """fmaf on float32 arrays, correctly rounded: the product of two float32 is exact in float64; the float64 sum is rounded TO ODD
-    (the error of the addition, exact by TwoSum, decides the last bit), and a round-to-odd value of 53 bits rounds to the right 24."""
-    a, b, c = np.broadcast_arrays(np.asarray(a, F32), np.asarray(b, F32), np.asarray(c, F32))
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        s = p + c
-        bb = s - p
-        err = (p - (s - bb)) + (c - bb)
-        bits = s.view(np.int64).copy()
-        fix = np.isfinite(s) & np.isfinite(err) & (err != 0) & ((bits & 1) == 0)
-        away = (err > 0) == (s > 0)                     # the exact sum lies further from zero than s
-        bits = np.where(fix, bits + np.where(away, 1, -1), bits)
-        return bits.view(np.float64).astype(F32)
-
-
-def dot32(a, b):
-    """The rule's dot product over the LAST axis of float32 arrays ``a`` and ``b`` (broadcast against each other): chains of `fma32`
-    from +0 cut at the multiples of `CHAIN`, the chains added in ascending order from +0."""
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    K = a.shape[-1]
-    shape = np.broadcast_shapes(a.shape[:-1], b.shape[:-1])
-    s = np.zeros(shape, F32)
-    for k0 in range(0, K, CHAIN):
-        c = np.zeros(shape, F32)
-        for k in range(k0, min(k0 + CHAIN, K)):
-            c = fma32(a[..., k], b[..., k], c)
-        s = s + c
-    return s
-
-
-def _powi(base: float, t: int) -> float:
-    r, p = 1.0, float(base)
-    while t:
-        if t & 1:
-            r = r * p
-        p = p * p
-        t >>= 1
-    return r
-
-
-def adam_scalars32(t: int, lr, beta1, beta2, eps, weight_decay) -> dict:
-    """The per-step scalars of `frmap_head_fit_adam_scalars`: beta^t by squarings in float64, everything else float32."""
-    lr, beta1, beta2, eps, wd = (F32(v) for v in (lr, beta1, beta2, eps, weight_decay))
-    bc1 = F32(1.0 - _powi(float(beta1), t))
-    bc2 = F32(1.0 - _powi(float(beta2), t))
-    return {"step_size": F32(lr / bc1), "bc2_sqrt": np.sqrt(bc2), "omb1": F32(F32(1) - beta1), "omb2": F32(F32(1) - beta2), "beta2": beta2,
-            "eps": eps, "wd": wd, "decay": F32(F32(1) - F32(lr * wd))}
-
-
-def adam32(a: dict, grad, p, m, v, vmax, decoupled: bool, amsgrad: bool):
-    """`frmap_head_fit_adam` on float32 arrays; returns ``(p, m, v, vmax)``."""
-    grad, p, m, v = (np.asarray(t, F32) for t in (grad, p, m, v))
-    with np.errstate(all="ignore"):
-        if decoupled:
-            p = p * a["decay"]
-        elif a["wd"] != 0:
-            grad = fma32(a["wd"], p, grad)
-        m = fma32(a["omb1"], grad - m, m)
-        v = fma32(a["omb2"], grad * grad, v * a["beta2"])
-        vhat = v
-        if amsgrad:
-            vmax = np.where(vmax > v, vmax, v).astype(F32)
-            vhat = vmax
-        u = m / (np.sqrt(vhat) / a["bc2_sqrt"] + a["eps"])
-        p = fma32(-a["step_size"], u, p)
-    return p.astype(F32), m.astype(F32), v.astype(F32), vmax
-
-
-def fresh_state(D: int, C: int, amsgrad: bool = False, dtype=np.float64) -> dict:
-    """An optimiser state of the rule: the header integers and zero moments of ``dtype``."""
-    st = {"t": 0, "n": 0, "rows": 0, "correct": 0, "loss_q": 0, "m_w": np.zeros((C, D), dtype), "v_w": np.zeros((C, D), dtype),
-          "m_b": np.zeros((C,), dtype), "v_b": np.zeros((C,), dtype)}
-    if amsgrad:
-        st["vmax_w"], st["vmax_b"] = np.zeros((C, D), dtype), np.zeros((C,), dtype)
-    return st
-
-
-def loss_q(row_loss) -> int:
-    """The tally's fixed point of float32 row losses, summed: llrint(min(loss, 65536) * 2^24), a NaN taken at the clamp."""
-    l = np.asarray(row_loss, F32).astype(np.float64)
-    l = np.where(l < LOSS_CLAMP, l, LOSS_CLAMP)
-    return int(np.rint(l * LOSS_SCALE).astype(np.uint64).sum(dtype=np.uint64))
-
-
-def _copy_state(st: dict, dtype) -> dict:
-    """A rule state with its moments copied as ``dtype`` and its header words as ints."""
-    return {k: (np.array(v, dtype) if isinstance(v, np.ndarray) else int(v)) for k, v in st.items()}
-
-
-def _adam_rule(p, grad, st: dict, which: str, t: int, lr, beta1, beta2, eps, weight_decay, decoupled, amsgrad, f32):
-    """The update of the rule on one tensor (``which``: "w" or "b", the suffix of its moments in ``st``): `adam32` in float32 mode,
-    the formulas as torch evaluates them in float64.  Returns the new parameter; ``st`` is updated in place."""
-    km, kv, kx = "m_" + which, "v_" + which, "vmax_" + which
-    if f32:
-        a = adam_scalars32(t, lr, beta1, beta2, eps, weight_decay)
-        p, st[km], st[kv], vm = adam32(a, grad, p, st[km], st[kv], st.get(kx), decoupled, amsgrad)
-        if amsgrad:
-            st[kx] = vm
-        return p
-    p = np.array(p, np.float64)
-    if decoupled:
-        p *= 1.0 - lr * weight_decay
-    elif weight_decay != 0:
-        grad = grad + weight_decay * p
-    st[km] = st[km] + (1.0 - beta1) * (grad - st[km])
-    st[kv] = st[kv] * beta2 + (1.0 - beta2) * grad * grad
-    vhat = st[kv]
-    if amsgrad:
-        st[kx] = np.maximum(st[kx], st[kv])
-        vhat = st[kx]
-    denom = np.sqrt(vhat) / math.sqrt(1.0 - beta2 ** t) + eps
-    p += -(lr / (1.0 - beta1 ** t)) * (st[km] / denom)
-    return p
-
-
-def _rule_batch(x, labels, C: int, rows, B: int, keep, keep_scale, f32: bool):
-    """``(row_src, ok, x')`` of a batch of the rule: ``rows`` (``None``: rows ``0 .. B-1``) with -1 where a row is declined - outside
-    the cache, a label outside ``[0, C)``, a non-finite feature -, that as a mask, and the ``[B, D]`` input with ``keep`` applied and
-    scaled (a declined row is zeros)."""
-    N, D = x.shape
-    rows = np.arange(B, dtype=np.int64) if rows is None else np.asarray(rows).astype(np.int64)
-    row_src = np.full((len(rows),), -1, np.int32)
-    for i, r in enumerate(rows):
-        if 0 <= r < N and 0 <= labels[r] < C and np.isfinite(x[r]).all():
-            row_src[i] = r
-    ok = row_src >= 0
-    xp = np.zeros((len(rows), D), x.dtype)
-    xp[ok] = x[row_src[ok]]
-    if keep is not None:
-        kept = np.asarray(keep).astype(bool)
-        scaled = (xp * F32(keep_scale)).astype(F32) if f32 else xp * float(keep_scale)
-        xp = np.where(kept, scaled, 0).astype(x.dtype)
-        xp[~ok] = 0
-    return row_src, ok, xp
-
-
-def step_rule(x, labels, w, b, state: Optional[dict] = None, rows=None, keep=None, keep_scale: float = 1.0, *, lr: float = 1e-3,
-              beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0,
-              decoupled: bool = False, amsgrad: bool = False, clear: bool = False, dtype=np.float64, given: Optional[dict] = None,
-              batch: Optional[int] = None) -> dict:
-    """One training step, the specification (module docstring; the formulas are those of include/frmap_hip.h, "Head fitting").
-
-    ``dtype=np.float64``: the formulas in float64, as torch evaluates them (``nn.Linear`` + ``F.cross_entropy`` + ``optim.Adam`` /
-    ``AdamW``).  ``dtype=np.float32``: every operation float32 in the order of csrc/head_fit_rule.h - `dot32` for both GEMMs, `adam32` for the
-    update; the softmax, the row loss and g in float64 from the float32 logits and rounded once - which is what the host twin
-    computes bit for bit (up to a rare last bit of g and the loss where the C library's exp / log and numpy's differ).  ``given``: ``{"z", "g", "row_loss"}`` to take as they are (float32 mode: the device's or the twin's own)
-    instead of computing them, the way `frmap_head_fit_step_host` takes them with ``given_g``.
-
-    ``batch``: the number of batch rows B when neither ``rows`` nor ``keep`` gives it (default: the whole cache).
-
-    Nothing is modified: returns ``{"w", "b", "state", "z", "g", "row_loss", "row_src", "dw", "db", "n", "loss"}`` with new arrays;
-    ``loss`` is the mean row loss of the counted rows (NaN when all are declined)."""
-    f32 = np.dtype(dtype) == np.dtype(np.float32)
-    x = np.asarray(x, F32 if f32 else np.float64)
-    w, b = np.array(w, dtype), np.array(b, dtype)
-    labels = np.asarray(labels).astype(np.int64)
-    N, D = x.shape
-    C = w.shape[0]
-    st = _copy_state(state or fresh_state(D, C, amsgrad, dtype), dtype)
-    if clear:
-        st["rows"] = st["correct"] = st["loss_q"] = 0
-    # rows 0 .. B-1 without `rows`: B is the mask's, else `batch`, else the whole cache
-    row_src, ok, xp = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), keep,
-                                  keep_scale, f32)
-    B = len(row_src)
-    n = int(ok.sum())
-    st["n"] = n
-    y = np.where(ok, labels[np.clip(row_src, 0, N - 1)], 0)
-    ls = F32(label_smoothing) if f32 else float(label_smoothing)
-    with np.errstate(all="ignore"):
-        if given is not None:
-            z, g, row_loss = (np.array(given[k], dtype) for k in ("z", "g", "row_loss"))
-        else:
-            z = (dot32(xp[:, None, :], w[None, :, :]) + b[None, :]).astype(F32) if f32 else xp @ w.T + b[None, :]
-            z[~ok] = 0
-            # the softmax half is float64 in both modes (csrc/head_fit_rule.h): the float32 mode rounds g and the loss once
-            z64 = z.astype(np.float64)
-            m = z64.max(axis=1, keepdims=True)
-            e = np.exp(z64 - m)
-            s = e.sum(axis=1, keepdims=True)
-            nl = np.log(s) - (z64 - m)                               # -log p, per class
-            nll = nl[np.arange(B), y]
-            ls64, off64 = float(ls), (float(ls) / C if ls > 0 else 0.0)
-            row_loss = (1.0 - ls64) * nll + off64 * nl.sum(axis=1) if ls > 0 else nll
-            row_loss = np.where(row_loss > 0, row_loss, np.where(np.isnan(row_loss), row_loss, 0)).astype(dtype)
-            t64 = np.full((B, C), off64)
-            t64[np.arange(B), y] = (1.0 - ls64) + off64
-            g = (((e / s) - t64) / float(max(n, 1))).astype(dtype)
-            g[~ok] = 0
-            row_loss[~ok] = np.nan
-    pred = z.argmax(axis=1)
-    st["rows"] += n
-    st["correct"] += int((ok & (pred == y)).sum())
-    st["loss_q"] += loss_q(row_loss[ok])
-    out = {"z": z, "g": g, "row_loss": row_loss, "row_src": row_src, "n": n,
-           "loss": float(row_loss[ok].astype(np.float64).mean()) if n else float("nan")}
-    gz = np.where(ok[:, None], g, 0).astype(dtype)
-    if f32:
-        dw = dot32(gz.T[:, None, :], xp.T[None, :, :])
-        db = dot32(gz.T, np.ones((1, B), F32))
-    else:
-        dw, db = gz.T @ xp, gz.sum(axis=0)
-    out["dw"], out["db"] = dw, db
-    if n:
-        st["t"] += 1
-        kw = dict(t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
-                  f32=f32)
-        w, b = _adam_rule(w, dw, st, "w", **kw), _adam_rule(b, db, st, "b", **kw)
-    out["w"], out["b"], out["state"] = w, b, st
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
 # the host twin
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _flags(decoupled, amsgrad, clear) -> int:
     return (DECOUPLED if decoupled else 0) | (AMSGRAD if amsgrad else 0) | (CLEAR if clear else 0)
+
+
+def _adam(lr, beta1, beta2, eps, weight_decay):
+    """The five Adam scalars as every step, host or device, hands them to the library by value."""
+    return float(lr), float(beta1), float(beta2), float(eps), float(weight_decay)
 
 
 def _host_cache(op, x, labels):
@@ -452,9 +245,8 @@ def step_host(x, labels, w, b, state: np.ndarray, workspace: Optional[np.ndarray
     keep = _host_mask(op, "keep", keep, (B, D))
     workspace = _host_buffers(op, state, state_bytes(D, C, amsgrad), workspace, workspace_bytes(B, D, C), given_g)
     _lib.check(_lib.load().frmap_head_fit_step_host(_at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w), _at(b), _at(state),
-                                                    _at(workspace), N, B, D, C, float(lr), float(beta1), float(beta2), float(eps),
-                                                    float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear),
-                                                    int(bool(given_g))), op)
+                                                    _at(workspace), N, B, D, C, *_adam(lr, beta1, beta2, eps, weight_decay),
+                                                    float(label_smoothing), _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
     return workspace
 
 
@@ -504,6 +296,26 @@ def _operand(t, op, entry, name, dtype, owned=False):
     return None if t is None else _dev(t, f"{op}.{name}", dtype, (entry, name), owned=owned)
 
 
+def _mask(op, name, keep, shape):
+    """An optional uint8 dropout mask is exactly ``shape`` (the device side of `_host_mask`)."""
+    if keep is not None:
+        _sized(keep, op, name, shape, torch.uint8)
+
+
+def _buffers(op, entry, state, nstate, workspace, nbytes, **written):
+    """The device side of `_host_buffers`, last of a step's size checks: the state is uint8 of ``nstate`` bytes, the workspace of exactly
+    ``nbytes``.  Then `_operand` of both and of every other named tensor the call writes: none is copied, the caller's are the operands."""
+    _sized(state, op, "state", (nstate,), torch.uint8)
+    _sized(workspace, op, "workspace", (nbytes,), torch.uint8)
+    for name, t in dict(written, state=state, workspace=workspace).items():
+        _operand(t, op, entry, name, None, True)
+
+
+def _reads(op, entry, **named):
+    """`_operand` of every named operand the call only reads, in the order given; `_sized` has checked its dtype and extent."""
+    return [_operand(t, op, entry, name, None) for name, t in named.items()]
+
+
 def _dev_at(t) -> int:
     return 0 if t is None else t.data_ptr()
 
@@ -522,18 +334,12 @@ def step(x: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, b: torch.Tensor
     x, N, D = _cache(op, entry, x, labels)
     C = _layer(w, b, op, "w", "b", D)
     rows, B = _batch(op, entry, N, rows, (keep,), batch)
-    if keep is not None:
-        _sized(keep, op, "keep", (B, D), torch.uint8)
-    _sized(state, op, "state", (state_bytes(D, C, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (workspace_bytes(B, D, C),), torch.uint8)
-    labels = _operand(labels, op, entry, "labels", torch.int32)
-    keep = _operand(keep, op, entry, "keep", torch.uint8)
-    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _mask(op, "keep", keep, (B, D))
+    _buffers(op, entry, state, state_bytes(D, C, amsgrad), workspace, workspace_bytes(B, D, C), w=w, b=b)
+    labels, keep = _reads(op, entry, labels=labels, keep=keep)
     _lib.check(_lib.load().frmap_head_fit_step(x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w.data_ptr(),
-                                               b.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, C, float(lr), float(beta1),
-                                               float(beta2), float(eps), float(weight_decay), float(label_smoothing),
+                                               b.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, C,
+                                               *_adam(lr, beta1, beta2, eps, weight_decay), float(label_smoothing),
                                                _flags(decoupled, amsgrad, clear), _stream()), op)
 
 
@@ -544,6 +350,33 @@ def _linear_init(fan_out: int, fan_in: int, generator):
     w = (torch.rand((fan_out, fan_in), generator=generator, dtype=torch.float32) * 2 - 1) * bound
     b = (torch.rand((fan_out,), generator=generator, dtype=torch.float32) * 2 - 1) * bound
     return w, b
+
+
+def _margin_init(C: int, D: int, generator):
+    """The ``[C, D]`` class centres of an ``ArcMarginProduct`` on the CPU (``xavier_normal_`` with gain sqrt(2),
+    `src/face_models.py:326`): one draw from ``generator``."""
+    std = math.sqrt(2.0) * math.sqrt(2.0 / (D + C))
+    return torch.empty((C, D), dtype=torch.float32).normal_(0.0, std, generator=generator)
+
+
+def _arcface_parts(who: str, model):
+    """``(embedding, bn, arcface)`` of an ``ArcFaceNet``; any other class, and one without these modules, is refused in ``who``'s name."""
+    emb, bn, arc = (getattr(model, k, None) for k in ("embedding", "bn", "arcface"))
+    if type(model).__name__ != "ArcFaceNet" or not isinstance(emb, torch.nn.Linear) or not isinstance(bn, torch.nn.BatchNorm1d) or \
+            not isinstance(getattr(arc, "weight", None), torch.Tensor):
+        raise ValueError(f"{who}: an ArcFaceNet expected, got {type(model).__name__}")
+    return emb, bn, arc
+
+
+def _load(who: str, mine: str, pairs) -> None:
+    """What the `load_into` methods share: every ``(name, dst, src)`` of ``pairs`` has equal shapes - else ``"<who>: <name> is <dst's>,
+    <mine> is <src's>"`` -, and only then every ``src`` is copied into its ``dst``, outside autograd.  ``name=None``: a bias, unchecked."""
+    for name, dst, src in pairs:
+        if name is not None and (not isinstance(dst, torch.Tensor) or tuple(dst.shape) != tuple(src.shape)):
+            raise ValueError(f"{who}: {name} is {list(dst.shape) if isinstance(dst, torch.Tensor) else None}, {mine} is {list(src.shape)}")
+    with torch.no_grad():
+        for _, dst, src in pairs:
+            dst.copy_(src)
 
 
 def _figures(words) -> dict:
@@ -582,6 +415,19 @@ class _Head:
         """The one host copy: rows, correct, accuracy and mean loss since the last `new_epoch`, and the step count ``t``."""
         return _figures(self.state[self._header_at: self._header_at + 64].cpu().numpy().view(np.uint64))
 
+    @staticmethod
+    def _keep_scale(keep_scale, keep, dropout):
+        """The scale of the mask ``keep``: ``keep_scale`` when given, else ``1 / (1 - dropout)`` with a mask and 1 without one."""
+        return keep_scale if keep_scale is not None else (1.0 / (1.0 - float(dropout)) if keep is not None else 1.0)
+
+    @staticmethod
+    def _batch_rows(x, rows, *masks) -> int:
+        """B of a row-based step: ``rows``' length, else the first ``[B, .]`` mask's row count, else ``x``'s."""
+        for t, dim in ((rows, 1),) + tuple((m, 2) for m in masks):
+            if isinstance(t, torch.Tensor) and t.dim() == dim:
+                return int(t.shape[0])
+        return int(x.shape[0])
+
 
 class LinearHead(_Head):
     """A linear softmax classifier ``[C, D]`` on the device with its Adam state and a workspace.  ``weight`` / ``bias`` are
@@ -615,12 +461,9 @@ class LinearHead(_Head):
              eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False) -> "LinearHead":
         """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`step`).  ``keep``: a uint8 ``[B, D]`` dropout mask, scaled by
         ``keep_scale`` (default ``1 / (1 - dropout)``).  No synchronisation."""
-        if keep_scale is None:
-            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
-        B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
-            int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
-        return self._run(step, x, labels, self.weight, self.bias, self.state, self._workspace(B), rows, keep, keep_scale, lr=lr, beta1=beta1,
-                         beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
+        return self._run(step, x, labels, self.weight, self.bias, self.state, self._workspace(self._batch_rows(x, rows, keep)), rows, keep,
+                         self._keep_scale(keep_scale, keep, dropout), lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+                         label_smoothing=label_smoothing, decoupled=decoupled)
 
     def logits(self, x: torch.Tensor) -> torch.Tensor:
         return ops.linear_f32(x, self.weight, None, self.bias)
@@ -634,9 +477,7 @@ class LinearHead(_Head):
         fc = getattr(getattr(model, "resnet", None), "fc", None)
         if not isinstance(fc, torch.nn.Sequential) or tuple(fc[1].weight.shape) != (self.C, self.D):
             raise ValueError(f"LinearHead.load_into: a ResNetTransfer with a [{self.C}, {self.D}] classifier expected")
-        with torch.no_grad():
-            fc[1].weight.copy_(self.weight)
-            fc[1].bias.copy_(self.bias)
+        _load("LinearHead.load_into", "the head", ((None, fc[1].weight, self.weight), (None, fc[1].bias, self.bias)))
 
     def as_classifier(self):
         """The ``(w, b)`` pair `evaluate.evaluate_model` / `evaluate_stream` take as ``arcface_classifier``."""
@@ -718,6 +559,46 @@ def _generators(generator, device):
     return _head_generator(generator), dev_gen
 
 
+def _fit(head, epochs, run_epoch, validate=None):
+    """The epoch loop of every fit.  Per epoch: `new_epoch`, ``run_epoch(epoch)`` - the steps, with no host copy -, the one copy of the
+    epoch's figures and, with ``validate``, ``validate(head)`` as its entry of ``history["val"]``.  Returns ``(head, history)``; no draws."""
+    history = {"train_loss": [], "train_acc": [], "val": []}
+    for epoch in range(int(epochs)):
+        head.new_epoch()
+        run_epoch(epoch)
+        fig = head.epoch_figures()
+        history["train_loss"].append(fig["loss"])
+        history["train_acc"].append(fig["accuracy"])
+        if validate is not None:
+            history["val"].append(validate(head))
+    return head, history
+
+
+def _row_epochs(head, feats, labels, batch_size, masks, dev_gen, step_kw):
+    """The ``run_epoch`` of a row-based fit.  Per epoch ``step_kw(epoch)``, the keyword arguments of that epoch's steps, then ONE
+    ``randperm`` of the cached rows from ``dev_gen``; per batch of ``batch_size`` permuted rows (the last one may be shorter) one
+    ``rand`` per ``(width, p)`` of ``masks``, in their order - none for ``p == 0``, where the mask is ``None`` -, then `head.step`."""
+    N, B = int(feats.shape[0]), int(batch_size)
+
+    def run_epoch(epoch):
+        kw = step_kw(epoch)
+        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
+        for lo in range(0, N, B):
+            rows = perm[lo: lo + B]
+            keeps = [(torch.rand((rows.shape[0], width), device=feats.device, generator=dev_gen) >= p).to(torch.uint8) if p > 0 else None
+                     for width, p in masks]
+            head.step(feats, labels, rows, *keeps, **kw)
+    return run_epoch
+
+
+def _tally(C, logits, labels) -> dict:
+    """The validation of a classifier fit: the metrics of an `evaluate.ClassificationTally` over ``logits`` and ``labels``."""
+    from . import evaluate
+    tally = evaluate.ClassificationTally(C, device=logits.device)
+    tally.update(logits, labels)
+    return tally.metrics()
+
+
 def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3,
              weight_decay: float = 1e-4, dropout: float = 0.1, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
              generator: Optional[torch.Generator] = None, num_classes: Optional[int] = None, device="cuda", hidden: Optional[int] = None,
@@ -733,15 +614,18 @@ def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10
     ``hidden=Hd``: fit a `HiddenHead` ``Linear(D, Hd) -> ReLU -> Dropout(hidden_dropout) -> Linear(Hd, C)`` instead, with ``dropout`` on
     its input and a second mask draw per step for the hidden layer.  For a ``BaselineNet`` the cache is then its pooled ``[N, 128]``
     features (`cache_features(layer="pooled")`), so that ``hidden=512`` fits its own ``fc1`` / ``fc2`` (`HiddenHead.load_into`); for
-    every other model it is the embedding, and ``w1`` a learned projection of it."""
-    from . import evaluate
+    every other model it is the embedding, and ``w1`` a learned projection of it.
+
+    Order of draws: the head from the CPU ``generator`` FIRST, then the device generator's seed from it (`fit_margin_head`,
+    `fit_embed_head` and `fit_pair_head` draw the seed first: the two orders differ and both are kept, since either change would alter
+    every fitted head of a given seed); per epoch one ``randperm``; per batch the input mask's ``rand``, then the hidden mask's; a mask
+    with ``p == 0`` is not drawn."""
     if model_type == 'siamese':
         raise ValueError("head_fit: a siamese model has no classifier head to fit (pairs are verification_metrics' business)")
     layer = "pooled" if hidden is not None and type(model).__name__ == "BaselineNet" else "embedding"
     feats, labels = cache_features(model, model_type, train_data, device=device, layer=layer)
-    N, D = int(feats.shape[0]), int(feats.shape[1])
+    D = int(feats.shape[1])
     C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
-    # the head is drawn first, then the device generator's seed; per step one mask per (width, dropout), in this order
     if hidden is None:
         head = LinearHead(D, C, feats.device, amsgrad=amsgrad, generator=_head_generator(generator))
         masks, drop_kw = [(D, dropout)], dict(dropout=dropout)
@@ -750,27 +634,10 @@ def fit_head(model, model_type: str, train_data, val_data=None, epochs: int = 10
         head = HiddenHead(D, hidden, C, feats.device, amsgrad=amsgrad, generator=_head_generator(generator))
         masks, drop_kw = [(D, dropout), (hidden, hidden_dropout)], dict(dropout1=dropout, dropout2=hidden_dropout)
     dev_gen = _generators(generator, feats.device)[1]
-    val = None
-    if val_data is not None:
-        val = cache_features(model, model_type, val_data, device=device, layer=layer)
-    history = {"train_loss": [], "train_acc": [], "val": []}
-    for _ in range(int(epochs)):
-        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
-        head.new_epoch()
-        for lo in range(0, N, int(batch_size)):
-            rows = perm[lo: lo + int(batch_size)]
-            keeps = [(torch.rand((rows.shape[0], width), device=feats.device, generator=dev_gen) >= p).to(torch.uint8) if p > 0 else None
-                     for width, p in masks]
-            head.step(feats, labels, rows, *keeps, lr=lr, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled,
-                      **drop_kw)
-        fig = head.epoch_figures()
-        history["train_loss"].append(fig["loss"])
-        history["train_acc"].append(fig["accuracy"])
-        if val is not None:
-            tally = evaluate.ClassificationTally(C, device=feats.device)
-            tally.update(head.logits(val[0]), val[1])
-            history["val"].append(tally.metrics())
-    return head, history
+    val = cache_features(model, model_type, val_data, device=device, layer=layer) if val_data is not None else None
+    kw = dict(lr=lr, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled, **drop_kw)
+    return _fit(head, epochs, _row_epochs(head, feats, labels, batch_size, masks, dev_gen, lambda epoch: kw),
+                None if val is None else lambda head: _tally(C, head.logits(val[0]), val[1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -812,32 +679,6 @@ def hyper_table(H: int, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.
 
 def _group_flags(decoupled, amsgrad, clear, evaluate) -> int:
     return _flags(decoupled, amsgrad, clear) | (EVAL if evaluate else 0)
-
-
-def group_step_rule(x, labels, w, b, states, rows, keep=None, *, hyper, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
-                    evaluate: bool = False, dtype=np.float64, given=None) -> list:
-    """The grouped step in numpy: ``H`` calls of `step_rule`, head ``h`` on ``w[h]``, ``b[h]``, ``states[h]`` (a rule state or
-    ``None``), ``rows[h]``, ``keep[h]`` and row ``h`` of ``hyper`` (`hyper_table`).  ``evaluate``: the weights, the moments and ``t``
-    of the returned dicts are the inputs'; only ``n`` and the figures are the step's.  Returns the list of `step_rule` results."""
-    hyper = np.asarray(hyper, np.float32)
-    H = len(w)
-    if hyper.shape != (H, 8) or len(rows) != H:
-        raise ValueError(f"head_fit.group_step_rule: hyper [{H}, 8] and rows [{H}, B] expected")
-    out = []
-    for h in range(H):
-        hy = hyper[h]
-        st = None if states is None else states[h]
-        r = step_rule(x, labels, w[h], b[h], st, rows[h], None if keep is None else keep[h], float(hy[6]), lr=float(hy[0]),
-                      beta1=float(hy[1]), beta2=float(hy[2]), eps=float(hy[3]), weight_decay=float(hy[4]), label_smoothing=float(hy[5]),
-                      decoupled=decoupled, amsgrad=amsgrad, clear=clear, dtype=dtype, given=None if given is None else given[h])
-        if evaluate:
-            D, C = np.asarray(w[h]).shape[1], np.asarray(w[h]).shape[0]
-            old = _copy_state(st or fresh_state(D, C, amsgrad, dtype), dtype)
-            for k in ("n", "rows", "correct", "loss_q"):
-                old[k] = r["state"][k]
-            r["w"], r["b"], r["state"] = np.array(w[h], dtype), np.array(b[h], dtype), old
-        out.append(r)
-    return out
 
 
 def group_step_host(x, labels, rows, hyper, w, b, state: np.ndarray, workspace: Optional[np.ndarray] = None, keep=None, *,
@@ -893,18 +734,11 @@ def group_step(x: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, hyper:
     B = int(rows.shape[1])
     _sized(rows, op, "rows", (H, B), torch.int32)
     _sized(hyper, op, "hyper", (H, 8), torch.float32)
-    if keep is not None:
-        if evaluate:
-            raise ValueError(f"{op}: keep cannot be given with evaluate=True (flag 8 takes no dropout mask)")
-        _sized(keep, op, "keep", (H, B, D), torch.uint8)
-    _sized(state, op, "state", (group_state_bytes(H, D, C, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (group_workspace_bytes(H, B, D, C),), torch.uint8)
-    labels, rows = _operand(labels, op, entry, "labels", torch.int32), _operand(rows, op, entry, "rows", torch.int32)
-    hyper = _operand(hyper, op, entry, "hyper", torch.float32)
-    keep = _operand(keep, op, entry, "keep", torch.uint8)
-    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    if keep is not None and evaluate:
+        raise ValueError(f"{op}: keep cannot be given with evaluate=True (flag 8 takes no dropout mask)")
+    _mask(op, "keep", keep, (H, B, D))
+    _buffers(op, entry, state, group_state_bytes(H, D, C, amsgrad), workspace, group_workspace_bytes(H, B, D, C), w=w, b=b)
+    labels, rows, hyper, keep = _reads(op, entry, labels=labels, rows=rows, hyper=hyper, keep=keep)
     _lib.check(_lib.load().frmap_head_fit_group_step(x.data_ptr(), labels.data_ptr(), rows.data_ptr(), _dev_at(keep), hyper.data_ptr(),
                                                      w.data_ptr(), b.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, H, B, D, C,
                                                      _group_flags(decoupled, amsgrad, clear, evaluate), _stream()), op)
@@ -1160,67 +994,6 @@ def hidden_workspace_views(workspace: np.ndarray, B: int, Hd: int, C: int) -> di
     return out
 
 
-def hidden_step_rule(x, labels, w1, b1, w2, b2, state: Optional[dict] = None, rows=None, keep1=None, keep1_scale: float = 1.0, keep2=None,
-                     keep2_scale: float = 1.0, *, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                     weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
-                     clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
-    """One training step of Linear(D, Hd) -> ReLU -> dropout -> Linear(Hd, C), the specification (csrc/head_fit_rule.h, HIDDEN LAYER).
-
-    Layer 1's forward and its declined rows are computed here; all of layer 2 is `step_rule` on ``(h, lab, keep2)``; ``da`` is formed
-    against the ``w2`` from BEFORE that update, and layer 1's update uses layer 2's ``t`` and ``n``.  ``dtype`` and ``given`` as in
-    `step_rule` (``given`` holds layer 2's ``z``, ``g`` and ``row_loss``).  ``state``: ``{"layer1": ..., "layer2": ...}`` of
-    `fresh_state` dicts for (D, Hd) and (Hd, C), or ``None``.
-
-    Nothing is modified: returns ``{"w1", "b1", "w2", "b2", "state", "h", "lab", "row_src1", "da", "z", "g", "row_loss", "row_src",
-    "dw1", "db1", "dw2", "db2", "n", "loss"}`` with new arrays."""
-    f32 = np.dtype(dtype) == np.dtype(np.float32)
-    x = np.asarray(x, F32 if f32 else np.float64)
-    w1, b1 = np.array(w1, dtype), np.array(b1, dtype)
-    w2_old = np.array(w2, dtype)
-    labels = np.asarray(labels).astype(np.int64)
-    N, D = x.shape
-    Hd, C = w1.shape[0], w2_old.shape[0]
-    state = state or {"layer1": fresh_state(D, Hd, amsgrad, dtype), "layer2": fresh_state(Hd, C, amsgrad, dtype)}
-    st1 = _copy_state(state["layer1"], dtype)
-    masks = [len(k) for k in (keep1, keep2) if k is not None]
-    row_src1, ok1, xp = _rule_batch(x, labels, C, rows, masks[0] if masks else (N if batch is None else int(batch)), keep1, keep1_scale, f32)
-    B = len(row_src1)
-    lab = np.where(ok1, labels[np.clip(row_src1, 0, N - 1)], -1).astype(np.int32)
-    with np.errstate(all="ignore"):
-        a = (dot32(xp[:, None, :], w1[None, :, :]) + b1[None, :]).astype(F32) if f32 else xp @ w1.T + b1[None, :]
-        h = np.where(a > 0, a, np.where(np.isnan(a), a, 0)).astype(dtype)
-    h[~ok1] = 0
-    r2 = step_rule(h, lab, w2_old, b2, state["layer2"], None, keep2, keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
-                   weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled, amsgrad=amsgrad, clear=clear,
-                   dtype=dtype, given=given, batch=B)
-    ok2 = r2["row_src"] >= 0
-    g = np.where(ok2[:, None], r2["g"], 0).astype(dtype)
-    with np.errstate(all="ignore"):
-        s = dot32(g[:, None, :], w2_old.T[None, :, :]) if f32 else g @ w2_old
-        live = ok2[:, None] & (h > 0)
-        if keep2 is not None:
-            live = live & np.asarray(keep2).astype(bool)
-            s = (s * F32(keep2_scale)).astype(F32) if f32 else s * float(keep2_scale)
-        da = np.where(live, s, 0).astype(dtype)
-        dz = np.where(ok1[:, None], da, 0).astype(dtype)
-        if f32:
-            dw1 = dot32(dz.T[:, None, :], xp.T[None, :, :])
-            db1 = dot32(dz.T, np.ones((1, B), F32))
-        else:
-            dw1, db1 = dz.T @ xp, dz.sum(axis=0)
-    n = r2["n"]
-    st1["t"], st1["n"] = r2["state"]["t"], n
-    if n:
-        kw = dict(t=st1["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
-                  f32=f32)
-        w1, b1 = _adam_rule(w1, dw1, st1, "w", **kw), _adam_rule(b1, db1, st1, "b", **kw)
-    out = {"w1": w1, "b1": b1, "w2": r2["w"], "b2": r2["b"], "state": {"layer1": st1, "layer2": r2["state"]}, "h": h, "lab": lab,
-           "row_src1": row_src1, "da": da, "dw1": dw1, "db1": db1, "dw2": r2["dw"], "db2": r2["db"]}
-    for k in ("z", "g", "row_loss", "row_src", "n", "loss"):
-        out[k] = r2[k]
-    return out
-
-
 def hidden_step_host(x, labels, w1, b1, w2, b2, state: np.ndarray, workspace: Optional[np.ndarray] = None, rows=None, keep1=None,
                      keep1_scale: float = 1.0, keep2=None, keep2_scale: float = 1.0, *, lr: float = 1e-3, beta1: float = 0.9,
                      beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, label_smoothing: float = 0.0,
@@ -1239,8 +1012,8 @@ def hidden_step_host(x, labels, w1, b1, w2, b2, state: np.ndarray, workspace: Op
     workspace = _host_buffers(op, state, hidden_state_bytes(D, Hd, C, amsgrad), workspace, hidden_workspace_bytes(B, D, Hd, C), given_g)
     _lib.check(_lib.load().frmap_head_fit_hidden_step_host(
         _at(x), _at(labels), _at(rows), _at(keep1), float(keep1_scale), _at(keep2), float(keep2_scale), _at(w1), _at(b1), _at(w2), _at(b2),
-        _at(state), _at(workspace), N, B, D, Hd, C, float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-        float(label_smoothing), _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
+        _at(state), _at(workspace), N, B, D, Hd, C, *_adam(lr, beta1, beta2, eps, weight_decay), float(label_smoothing),
+        _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
     return workspace
 
 
@@ -1261,22 +1034,14 @@ def hidden_step(x: torch.Tensor, labels: torch.Tensor, w1: torch.Tensor, b1: tor
     Hd = _layer(w1, b1, op, "w1", "b1", D)
     C = _layer(w2, b2, op, "w2", "b2", Hd)
     rows, B = _batch(op, entry, N, rows, (keep1, keep2), batch)
-    if keep1 is not None:
-        _sized(keep1, op, "keep1", (B, D), torch.uint8)
-    if keep2 is not None:
-        _sized(keep2, op, "keep2", (B, Hd), torch.uint8)
-    _sized(state, op, "state", (hidden_state_bytes(D, Hd, C, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (hidden_workspace_bytes(B, D, Hd, C),), torch.uint8)
-    labels = _operand(labels, op, entry, "labels", torch.int32)
-    keep1, keep2 = _operand(keep1, op, entry, "keep1", torch.uint8), _operand(keep2, op, entry, "keep2", torch.uint8)
-    w1, b1 = _operand(w1, op, entry, "w1", torch.float32, True), _operand(b1, op, entry, "b1", torch.float32, True)
-    w2, b2 = _operand(w2, op, entry, "w2", torch.float32, True), _operand(b2, op, entry, "b2", torch.float32, True)
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _mask(op, "keep1", keep1, (B, D))
+    _mask(op, "keep2", keep2, (B, Hd))
+    _buffers(op, entry, state, hidden_state_bytes(D, Hd, C, amsgrad), workspace, hidden_workspace_bytes(B, D, Hd, C), w1=w1, b1=b1, w2=w2, b2=b2)
+    labels, keep1, keep2 = _reads(op, entry, labels=labels, keep1=keep1, keep2=keep2)
     _lib.check(_lib.load().frmap_head_fit_hidden_step(
         x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep1), float(keep1_scale), _dev_at(keep2), float(keep2_scale), w1.data_ptr(),
-        b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, Hd, C, float(lr), float(beta1),
-        float(beta2), float(eps), float(weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), _stream()), op)
+        b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, Hd, C,
+        *_adam(lr, beta1, beta2, eps, weight_decay), float(label_smoothing), _flags(decoupled, amsgrad, clear), _stream()), op)
 
 
 class HiddenHead(_Head):
@@ -1305,18 +1070,10 @@ class HiddenHead(_Head):
         """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`hidden_step`).  ``keep1`` / ``keep2``: uint8 ``[B, D]`` /
         ``[B, Hd]`` dropout masks on the input / the hidden layer, scaled by ``1 / (1 - dropout1)`` / ``1 / (1 - dropout2)`` unless a
         scale is given.  No synchronisation."""
-        if keep1_scale is None:
-            keep1_scale = 1.0 / (1.0 - float(dropout1)) if keep1 is not None else 1.0
-        if keep2_scale is None:
-            keep2_scale = 1.0 / (1.0 - float(dropout2)) if keep2 is not None else 1.0
-        B = int(x.shape[0])
-        for t, dim in ((rows, 1), (keep1, 2), (keep2, 2)):
-            if isinstance(t, torch.Tensor) and t.dim() == dim:
-                B = int(t.shape[0])
-                break
-        return self._run(hidden_step, x, labels, self.w1, self.b1, self.w2, self.b2, self.state, self._workspace(B), rows, keep1, keep1_scale,
-                         keep2, keep2_scale, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
-                         label_smoothing=label_smoothing, decoupled=decoupled)
+        return self._run(hidden_step, x, labels, self.w1, self.b1, self.w2, self.b2, self.state,
+                         self._workspace(self._batch_rows(x, rows, keep1, keep2)), rows, keep1, self._keep_scale(keep1_scale, keep1, dropout1),
+                         keep2, self._keep_scale(keep2_scale, keep2, dropout2), lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                         weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
 
     def embed(self, x: torch.Tensor) -> torch.Tensor:
         """``relu(x w1^T + b1)``: the embedding the fitted first layer produces from cached-feature rows ``x`` ``[B, D]``."""
@@ -1341,14 +1098,8 @@ class HiddenHead(_Head):
         fc1, fc2 = getattr(model, "fc1", None), getattr(model, "fc2", None)
         if type(model).__name__ != "BaselineNet" or not isinstance(fc1, torch.nn.Linear) or not isinstance(fc2, torch.nn.Linear):
             raise ValueError(f"HiddenHead.load_into: a BaselineNet expected, got {type(model).__name__}")
-        for name, layer, shape in (("fc1", fc1, (self.Hd, self.D)), ("fc2", fc2, (self.C, self.Hd))):
-            if tuple(layer.weight.shape) != shape:
-                raise ValueError(f"HiddenHead.load_into: {name} is {list(layer.weight.shape)}, the head's layer is {list(shape)}")
-        with torch.no_grad():
-            fc1.weight.copy_(self.w1)
-            fc1.bias.copy_(self.b1)
-            fc2.weight.copy_(self.w2)
-            fc2.bias.copy_(self.b2)
+        _load("HiddenHead.load_into", "the head's layer",
+              (("fc1", fc1.weight, self.w1), (None, fc1.bias, self.b1), ("fc2", fc2.weight, self.w2), (None, fc2.bias, self.b2)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1356,7 +1107,6 @@ class HiddenHead(_Head):
 # ---------------------------------------------------------------------------------------------------------------------------------
 MAX_P = MAX_B // 2                # pairs of one step: 2P batch rows
 _PDE_IN = f"P in 1 ... {MAX_P}, D in 1 ... {MAX_D}, E in 1 ... {MAX_C}"
-NORM_EPS, DIST_EPS, DIST_MIN = 1e-12, 1e-6, 1e-8      # F.normalize, F.pairwise_distance, the loss's clamp
 
 
 def pair_state_bytes(D: int, E: int, amsgrad: bool = False) -> int:
@@ -1378,110 +1128,6 @@ def pair_workspace_views(workspace: np.ndarray, P: int, E: int) -> dict:
             "dist": f[4 * P * E + P:], "row_src": raw[4 * nf: 4 * nf + 8 * P].view(np.int32)}
 
 
-def pair_loss_rule(al, ar, differ, n: int, margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2):
-    """The float64 half of the pair rule (csrc/head_fit_rule.h, PAIR) on rows ``al``, ``ar`` ``[P, E]`` with ``differ`` ``[P]`` in
-    {0, 1}: ``(pair_loss [P], dist [P], ga_l [P, E], ga_r [P, E])`` in float64, the gradients those of ``sum(pair_loss) / n``."""
-    al, ar = np.asarray(al, np.float64), np.asarray(ar, np.float64)
-    dif = np.asarray(differ).astype(bool)
-    with np.errstate(all="ignore"):
-        nl, nr = np.sqrt((al * al).sum(axis=1)), np.sqrt((ar * ar).sum(axis=1))
-        sl, sr = np.maximum(nl, NORM_EPS)[:, None], np.maximum(nr, NORM_EPS)[:, None]
-        u, v = al / sl, ar / sr
-        delta = (u - v) + DIST_EPS
-        d0 = np.sqrt((delta * delta).sum(axis=1))
-        d = np.maximum(d0, DIST_MIN)
-        gap = np.maximum(float(margin) - d, 0.0)
-        loss = np.where(dif, float(w_diff) * gap * gap, float(w_same) * d * d)
-        q = np.where(dif, -2.0 * float(w_diff) * gap, 2.0 * float(w_same) * d) / float(max(n, 1))
-        c = np.where(d0 < DIST_MIN, 0.0, q / np.where(d0 > 0, d0, 1.0))[:, None]
-        ud, vd = (u * delta).sum(axis=1, keepdims=True), (v * delta).sum(axis=1, keepdims=True)
-        gl = (c / sl) * np.where((nl > NORM_EPS)[:, None], delta - u * ud, delta)
-        gr = (-c / sr) * np.where((nr > NORM_EPS)[:, None], delta - v * vd, delta)
-    return loss, d, gl, gr
-
-
-def pair_step_rule(x, left, right, differ, w, b, state: Optional[dict] = None, keep=None, keep_scale: float = 1.0, *, margin: float = 2.0,
-                   w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999,
-                   eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, amsgrad: bool = False, clear: bool = False,
-                   dtype=np.float64, given: Optional[dict] = None) -> dict:
-    """One training step of the pair head, the specification (csrc/head_fit_rule.h, PAIR; include/frmap_hip.h, "Head fitting on pairs").
-
-    ``dtype=np.float64``: the formulas in float64, as torch evaluates ``F.linear`` -> ``F.normalize`` -> ``F.pairwise_distance`` -> the
-    clamp and the two weighted terms -> ``optim.Adam`` / ``AdamW``.  ``dtype=np.float32``: the projection and both update GEMMs by
-    `dot32`, the update by `adam32`, and the loss half in float64 from the float32 ``a`` (and the float32 values of ``margin``,
-    ``w_same``, ``w_diff`` and ``accept``: the library takes them as fp32), rounded once - what the host twin computes,
-    word for word but for a rare last bit of ``ga``, ``pair_loss`` and ``dist`` (the order of the float64 sums).  ``given``: ``{"a",
-    "ga", "pair_loss", "dist"}`` to take as they are.
-
-    Nothing is modified: returns ``{"w", "b", "state", "a", "ga", "pair_loss", "dist", "row_src", "dw", "db", "n", "loss"}``."""
-    f32 = np.dtype(dtype) == np.dtype(np.float32)
-    x = np.asarray(x, F32 if f32 else np.float64)
-    w, b = np.array(w, dtype), np.array(b, dtype)
-    N, D = x.shape
-    E = w.shape[0]
-    left, right, differ = (np.asarray(t).astype(np.int64).reshape(-1) for t in (left, right, differ))
-    P = len(left)
-    st = _copy_state(state or fresh_state(D, E, amsgrad, dtype), dtype)
-    if clear:
-        st["rows"] = st["correct"] = st["loss_q"] = 0
-    if f32:                                                           # (the library takes them as fp32 and widens those values)
-        margin, w_same, w_diff = (float(F32(v)) for v in (margin, w_same, w_diff))
-    idx = np.concatenate([left, right])
-    row_ok = np.array([0 <= r < N and bool(np.isfinite(x[r]).all()) for r in idx])
-    src = np.where(row_ok, idx, -1).astype(np.int32)
-
-    def masked(ok):
-        xp = np.zeros((2 * P, D), x.dtype)
-        xp[ok] = x[src[ok]]
-        if keep is not None:
-            scaled = (xp * F32(keep_scale)).astype(F32) if f32 else xp * float(keep_scale)
-            xp = np.where(np.asarray(keep).astype(bool), scaled, 0).astype(x.dtype)
-            xp[~ok] = 0
-        return xp
-    with np.errstate(all="ignore"):
-        if given is not None:
-            a = np.array(given["a"], dtype)
-        else:
-            xr = masked(row_ok)
-            a = (dot32(xr[:, None, :], w[None, :, :]) + b[None, :]).astype(F32) if f32 else xr @ w.T + b[None, :]
-            a[~row_ok] = 0
-    pair_ok = row_ok[:P] & row_ok[P:] & ((differ == 0) | (differ == 1))
-    ok = np.concatenate([pair_ok, pair_ok])
-    row_src = np.where(ok, src, -1).astype(np.int32)
-    n = int(pair_ok.sum())
-    st["n"] = n
-    if given is not None:
-        ga, pair_loss, dist = (np.array(given[k], dtype) for k in ("ga", "pair_loss", "dist"))
-    else:
-        loss64, d64, gl, gr = pair_loss_rule(a[:P], a[P:], differ == 1, n, margin, w_same, w_diff)
-        ga = np.concatenate([gl, gr]).astype(dtype)
-        ga[~ok] = 0
-        pair_loss, dist = loss64.astype(dtype), d64.astype(dtype)
-        pair_loss[~pair_ok] = np.nan
-        dist[~pair_ok] = np.nan
-    acc = F32(accept) if f32 else float(accept)
-    st["rows"] += n
-    st["correct"] += int((pair_ok & ((dist < acc) == (differ == 0))).sum())
-    st["loss_q"] += loss_q(pair_loss[pair_ok])
-    xp = masked(ok)
-    gz = np.where(ok[:, None], ga, 0).astype(dtype)
-    with np.errstate(all="ignore"):
-        if f32:
-            dw = dot32(gz.T[:, None, :], xp.T[None, :, :])
-            db = dot32(gz.T, np.ones((1, 2 * P), F32))
-        else:
-            dw, db = gz.T @ xp, gz.sum(axis=0)
-    out = {"a": a, "ga": ga, "pair_loss": pair_loss, "dist": dist, "row_src": row_src, "dw": dw, "db": db, "n": n,
-           "loss": float(pair_loss[pair_ok].astype(np.float64).mean()) if n else float("nan")}
-    if n:
-        st["t"] += 1
-        kw = dict(t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad,
-                  f32=f32)
-        w, b = _adam_rule(w, dw, st, "w", **kw), _adam_rule(b, db, st, "b", **kw)
-    out["w"], out["b"], out["state"] = w, b, st
-    return out
-
-
 def pair_step_host(x, left, right, differ, w, b, state: np.ndarray, workspace: Optional[np.ndarray] = None, keep=None, keep_scale: float = 1.0, *,
                    margin: float = 2.0, w_same: float = 0.8, w_diff: float = 1.2, accept: float = 0.5, lr: float = 1e-3, beta1: float = 0.9,
                    beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
@@ -1501,7 +1147,7 @@ def pair_step_host(x, left, right, differ, w, b, state: np.ndarray, workspace: O
     workspace = _host_buffers(op, state, pair_state_bytes(D, E, amsgrad), workspace, pair_workspace_bytes(P, D, E), given_g)
     _lib.check(_lib.load().frmap_head_fit_pair_step_host(
         _at(x), _at(left), _at(right), _at(differ), _at(keep), float(keep_scale), _at(w), _at(b), _at(state), _at(workspace), N, P, D, E,
-        float(margin), float(w_same), float(w_diff), float(accept), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        float(margin), float(w_same), float(w_diff), float(accept), *_adam(lr, beta1, beta2, eps, weight_decay),
         _flags(decoupled, amsgrad, clear), int(bool(given_g))), op)
     return workspace
 
@@ -1526,19 +1172,13 @@ def pair_step(x: torch.Tensor, left: torch.Tensor, right: torch.Tensor, differ: 
     _sized(left, op, "left", (P,), torch.int32)
     _sized(right, op, "right", (P,), torch.int32)
     _sized(differ, op, "differ", (P,), torch.int32)
-    if keep is not None:
-        _sized(keep, op, "keep", (2 * P, D), torch.uint8)
-    _sized(state, op, "state", (pair_state_bytes(D, E, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (pair_workspace_bytes(P, D, E),), torch.uint8)
-    left, right, differ = (_operand(t, op, entry, k, torch.int32) for t, k in ((left, "left"), (right, "right"), (differ, "differ")))
-    keep = _operand(keep, op, entry, "keep", torch.uint8)
-    w, b = _operand(w, op, entry, "w", torch.float32, True), _operand(b, op, entry, "b", torch.float32, True)
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _mask(op, "keep", keep, (2 * P, D))
+    _buffers(op, entry, state, pair_state_bytes(D, E, amsgrad), workspace, pair_workspace_bytes(P, D, E), w=w, b=b)
+    left, right, differ, keep = _reads(op, entry, left=left, right=right, differ=differ, keep=keep)
     _lib.check(_lib.load().frmap_head_fit_pair_step(
         x.data_ptr(), left.data_ptr(), right.data_ptr(), differ.data_ptr(), _dev_at(keep), float(keep_scale), w.data_ptr(), b.data_ptr(),
-        state.data_ptr(), workspace.data_ptr(), N, P, D, E, float(margin), float(w_same), float(w_diff), float(accept), float(lr), float(beta1),
-        float(beta2), float(eps), float(weight_decay), _flags(decoupled, amsgrad, clear), _stream()), op)
+        state.data_ptr(), workspace.data_ptr(), N, P, D, E, float(margin), float(w_same), float(w_diff), float(accept),
+        *_adam(lr, beta1, beta2, eps, weight_decay), _flags(decoupled, amsgrad, clear), _stream()), op)
 
 
 class PairHead(_Head):
@@ -1566,12 +1206,10 @@ class PairHead(_Head):
         rows are of different identities.  ``keep``: a uint8 ``[2P, D]`` dropout mask (the left rows, then the right rows), scaled by
         ``keep_scale`` (default ``1 / (1 - dropout)``).  The defaults are the reference's loss (margin 2.0, 0.8 on same pairs, 1.2 on
         different ones) and its accept rule (distance below 0.5).  No synchronisation."""
-        if keep_scale is None:
-            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
         P = int(left.shape[0]) if isinstance(left, torch.Tensor) and left.dim() == 1 else 1
-        return self._run(pair_step, x, left, right, differ, self.weight, self.bias, self.state, self._workspace(P), keep, keep_scale,
-                         margin=margin, w_same=w_same, w_diff=w_diff, accept=accept, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
-                         weight_decay=weight_decay, decoupled=decoupled)
+        return self._run(pair_step, x, left, right, differ, self.weight, self.bias, self.state, self._workspace(P), keep,
+                         self._keep_scale(keep_scale, keep, dropout), margin=margin, w_same=w_same, w_diff=w_diff, accept=accept, lr=lr,
+                         beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled)
 
     def embed(self, x: torch.Tensor) -> torch.Tensor:
         """``normalize(x w^T + b)``: the unit-norm embedding of cached-feature rows ``x`` ``[B, D]``."""
@@ -1586,11 +1224,7 @@ class PairHead(_Head):
         fc = getattr(model, "fc", None)
         if type(model).__name__ != "SiameseNet" or not isinstance(fc, torch.nn.Sequential):
             raise ValueError(f"PairHead.load_into: a SiameseNet expected, got {type(model).__name__}")
-        if tuple(fc[8].weight.shape) != (self.E, self.D):
-            raise ValueError(f"PairHead.load_into: fc.8 is {list(fc[8].weight.shape)}, the head is {[self.E, self.D]}")
-        with torch.no_grad():
-            fc[8].weight.copy_(self.weight)
-            fc[8].bias.copy_(self.bias)
+        _load("PairHead.load_into", "the head", (("fc.8", fc[8].weight, self.weight), (None, fc[8].bias, self.bias)))
 
 
 def draw_pairs(labels: torch.Tensor, P: int, generator: Optional[torch.Generator] = None):
@@ -1636,7 +1270,9 @@ def fit_pair_head(model, train_data, val_data=None, epochs: int = 10, batch_pair
     64-byte copy at its end.  With ``val_data`` every epoch's `evaluate.verification_metrics` of ``head.embed`` on the validation
     rows.  ``layer="fc_hidden"`` (a ``SiameseNet``): the cache is the input of its ``fc.8`` and the head ``[256, 512]``, that layer
     itself (`PairHead.load_into`); otherwise the head projects the model's embedding to ``embed_dim`` (default: its own width).
-    Returns ``(head, history)`` with ``history = {"train_loss": [...], "train_acc": [...], "val": [metrics dict per epoch]}``."""
+    Returns ``(head, history)`` with ``history = {"train_loss": [...], "train_acc": [...], "val": [metrics dict per epoch]}``.
+    Order of draws: the device generator's seed from the CPU ``generator`` FIRST, then the head from it (the reverse of `fit_head`,
+    kept as it is); per step `draw_pairs` (one ``randint``, one ``rand((3, P))``), then one ``rand((2P, D))`` iff ``dropout > 0``."""
     from . import evaluate
     feats, labels = cache_embeddings(model, train_data, device=device, layer=layer)
     N, D = int(feats.shape[0]), int(feats.shape[1])
@@ -1645,29 +1281,20 @@ def fit_pair_head(model, train_data, val_data=None, epochs: int = 10, batch_pair
     head = PairHead(D, E, feats.device, amsgrad=amsgrad, generator=head_gen)
     val = cache_embeddings(model, val_data, device=device, layer=layer) if val_data is not None else None
     P = int(batch_pairs)
-    history = {"train_loss": [], "train_acc": [], "val": []}
-    for _ in range(int(epochs)):
-        head.new_epoch()
+
+    def run_epoch(epoch):
         for _ in range((N + P - 1) // P):
             left, right, differ = draw_pairs(labels, P, dev_gen)
             keep = (torch.rand((2 * P, D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
             head.step(feats, left, right, differ, keep, lr=lr, margin=margin, w_same=w_same, w_diff=w_diff, accept=accept, dropout=dropout,
                       weight_decay=weight_decay, decoupled=decoupled)
-        fig = head.epoch_figures()
-        history["train_loss"].append(fig["loss"])
-        history["train_acc"].append(fig["accuracy"])
-        if val is not None:
-            history["val"].append(evaluate.verification_metrics(head.embed(val[0]), val[1]))
-    return head, history
+    return _fit(head, epochs, run_epoch, None if val is None else lambda head: evaluate.verification_metrics(head.embed(val[0]), val[1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # an ArcFace margin head: cached embeddings in, the class centres of `ArcFaceNet.arcface.weight` out
 # ---------------------------------------------------------------------------------------------------------------------------------
 EASY_MARGIN = 16                  # FRMAP_HEAD_FIT_EASY_MARGIN: bit of the margin step's flags
-MARGIN_HI = float(F32(1.0 - 1e-7))                 # the clamp bound of the cosine as the library holds it (fp32)
-MARGIN_CAP = float(F32(math.pi - 1e-4))            # the reference's torch.tensor(math.pi - 1e-4): a float32 in every dtype
-MARGIN_RMAX = F32(1.0 / 1e-12)                     # the fp32 reciprocal of a clamped norm
 
 
 def margin_state_bytes(D: int, C: int, amsgrad: bool = False) -> int:
@@ -1690,153 +1317,6 @@ def margin_workspace_views(workspace: np.ndarray, B: int, C: int) -> dict:
     at = 4 * B * C
     out.update(row_loss=f[at: at + B], rx=f[at + B: at + 2 * B], rw=f[at + 2 * B: at + 2 * B + C],
                row_src=raw[4 * nf: 4 * nf + 4 * B].view(np.int32))
-    return out
-
-
-def margin_schedule(epoch: int, s: float = 32.0, m: float = 0.5, warm_up_epochs: int = 10, warm_up: bool = True):
-    """``(m_eff, s_eff)`` of training epoch ``epoch``: the arithmetic of the reference's ``ArcMarginProduct`` in training mode
-    (`src/face_models.py:336-348, 369, 401-409`).  ``margin_factor = min(0.9, (epoch / warm_up_epochs)^2)`` and ``scale_factor =
-    min(0.8, 0.3 + 0.5 epoch / warm_up_epochs)`` inside the warm-up, 0.9 and 0.8 after it; ``m_eff = m margin_factor``; ``s_eff =
-    min(s, 24) min(0.8, scale_factor)``, times ``(0.8 - 0.5 margin_factor)`` when ``m > 0.4``.  ``warm_up=False`` leaves the factors at
-    the module's initial 0.0 and 0.3, as ``use_warm_up=False`` does.  The reference's randomly printed "hard cap" (`:415-418`) multiplies
-    the output by 1, and no schedule reaches its threshold of 20 (``s_eff <= 24 x 0.8 = 19.2``): it is not restated."""
-    margin_factor, scale_factor = 0.0, 0.3
-    if warm_up:
-        if epoch < warm_up_epochs:
-            progress = epoch / warm_up_epochs
-            margin_factor = min(0.9, progress * progress)
-            scale_factor = min(0.8, 0.3 + 0.5 * progress)
-        else:
-            margin_factor, scale_factor = 0.9, 0.8
-    m_eff = m * margin_factor
-    s_eff = min(s, 24.0) * min(0.8, scale_factor)
-    if m > 0.4:
-        s_eff = s_eff * (0.8 - 0.5 * margin_factor)
-    return m_eff, s_eff
-
-
-def margin_logits_rule(z, rx, rw, y, s: float, m: float, easy_margin: bool = False, f32: bool = False):
-    """The float64 half of the margin rule up to the logits (csrc/head_fit_rule.h, MARGIN) on ``z [B, C]``, ``rx [B]``, ``rw [C]`` and the
-    targets ``y [B]``: ``{"cos", "cs", "inside", "theta_m", "out", "l", "dfac"}`` in float64 (``theta_m``: theta + m of every target).
-    ``f32``: the clamp bounds are the fp32 roundings, as in the library; else the doubles ``1 - 1e-7``."""
-    z, rx, rw = (np.asarray(t).astype(np.float64) for t in (z, rx, rw))
-    B, C = z.shape
-    hi = MARGIN_HI if f32 else 1.0 - 1e-7
-    rows = np.arange(B)
-    with np.errstate(all="ignore"):
-        cos = (z * rx[:, None]) * rw[None, :]
-        inside = (cos >= -hi) & (cos <= hi)
-        cs = np.where(cos < -hi, -hi, np.where(cos > hi, hi, cos))
-        out, dfac = cs.copy(), inside.astype(np.float64)
-        cy, iy = cs[rows, y], inside[rows, y].astype(np.float64)
-        theta = np.arccos(cy)
-        tm = theta + float(m)
-        ratio = np.sin(tm) / np.sin(theta)
-        if easy_margin:
-            take = cy > 0
-            out[rows, y] = np.where(take, np.cos(tm), cy)
-            dfac[rows, y] = np.where(take, iy * ratio, iy)
-        else:
-            capped = tm >= MARGIN_CAP                                    # (a NaN is not capped: it stays one, as torch.minimum keeps it)
-            out[rows, y] = np.where(capped, math.cos(MARGIN_CAP), np.cos(tm))
-            dfac[rows, y] = np.where(capped, 0.0, iy * ratio)
-        return {"cos": cos, "cs": cs, "inside": inside, "theta_m": tm, "out": out, "l": float(s) * out, "dfac": dfac}
-
-
-def margin_step_rule(x, labels, w, state: Optional[dict] = None, rows=None, keep=None, keep_scale: float = 1.0, *, s: float, m: float,
-                     easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                     weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
-                     clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
-    """One training step of the margin head, the specification (csrc/head_fit_rule.h, MARGIN; include/frmap_hip.h, "Head fitting with a
-    margin").
-
-    ``dtype=np.float64``: the formulas in float64 as torch evaluates the reference's ``F.normalize`` -> ``F.linear`` -> ``clamp`` ->
-    ``acos`` -> ``minimum`` / ``where`` -> ``cross_entropy(label_smoothing=)`` -> ``optim.Adam`` / ``AdamW`` (the cosine is
-    ``z / (|x'| |w|)`` on raw dot products: the same value).  ``dtype=np.float32``: z and both chains over B by `dot32`, rx and rw
-    rounded to float32 once, the margin softmax in float64 from those float32 values (and the float32 values of ``s``, ``m`` and the
-    bounds) with cosv, g, h and the row loss rounded once, the combination of dw in float32 products, `adam32` - what the host twin
-    computes, word for word but for a rare last bit of rx, rw, cosv, g, h and the row loss.  ``given``: ``{"z", "rx", "rw", "cosv", "g",
-    "h", "row_loss"}`` to take as they are.
-
-    Nothing is modified: returns ``{"w", "state", "z", "rx", "rw", "cosv", "g", "h", "row_loss", "row_src", "pred", "dw", "n", "loss"}``
-    and the float64 intermediates of `margin_logits_rule` under ``"detail"``."""
-    f32 = np.dtype(dtype) == np.dtype(np.float32)
-    x = np.asarray(x, F32 if f32 else np.float64)
-    w = np.array(w, dtype)
-    labels = np.asarray(labels).astype(np.int64)
-    N, D = x.shape
-    C = w.shape[0]
-    st = _copy_state(state or fresh_state(D, C, amsgrad, dtype), dtype)
-    if clear:
-        st["rows"] = st["correct"] = st["loss_q"] = 0
-    row_src, ok, xp = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), keep,
-                                  keep_scale, f32)
-    B = len(row_src)
-    n = int(ok.sum())
-    st["n"] = n
-    y = np.where(ok, labels[np.clip(row_src, 0, N - 1)], 0)
-    if f32:
-        s, m, ls = float(F32(s)), float(F32(m)), float(F32(label_smoothing))
-    else:
-        s, m, ls = float(s), float(m), float(label_smoothing)
-    with np.errstate(all="ignore"):
-        if given is not None:
-            z, rx, rw = (np.array(given[k], dtype) for k in ("z", "rx", "rw"))
-        else:
-            z = dot32(xp[:, None, :], w[None, :, :]).astype(F32) if f32 else xp @ w.T
-            z[~ok] = 0
-            nx = np.sqrt((xp.astype(np.float64) ** 2).sum(axis=1))
-            nw = np.sqrt((w.astype(np.float64) ** 2).sum(axis=1))
-            rx = (1.0 / np.maximum(nx, NORM_EPS)).astype(dtype)
-            rw = (1.0 / np.maximum(nw, NORM_EPS)).astype(dtype)
-            rx[~ok] = 0
-        det = margin_logits_rule(z, rx, rw, y, s, m, easy_margin, f32)
-        l = det["l"]
-        pred = np.where(np.isnan(l).all(axis=1), -1, np.argmax(np.where(np.isnan(l), -np.inf, l), axis=1))
-        if given is not None:
-            cosv, g, h, row_loss = (np.array(given[k], dtype) for k in ("cosv", "g", "h", "row_loss"))
-        else:
-            mx = l.max(axis=1, keepdims=True)
-            e = np.exp(l - mx)
-            sm = e.sum(axis=1, keepdims=True)
-            nl = np.log(sm) - (l - mx)
-            nll = nl[np.arange(B), y]
-            off = ls / C if ls > 0 else 0.0
-            row_loss = (1.0 - ls) * nll + off * nl.sum(axis=1) if ls > 0 else nll
-            row_loss = np.where(row_loss > 0, row_loss, np.where(np.isnan(row_loss), row_loss, 0)).astype(dtype)
-            t64 = np.full((B, C), off)
-            t64[np.arange(B), y] = (1.0 - ls) + off
-            gcos = ((s * ((e / sm) - t64)) / float(max(n, 1))) * det["dfac"]
-            g = (gcos * rx.astype(np.float64)[:, None]).astype(dtype)
-            h = (gcos * det["cos"]).astype(dtype)
-            cosv = det["cs"].astype(dtype)
-            for a in (g, h, cosv):
-                a[~ok] = 0
-            row_loss[~ok] = np.nan
-    st["rows"] += n
-    st["correct"] += int((ok & (pred == y)).sum())
-    st["loss_q"] += loss_q(row_loss[ok])
-    gz, hz = np.where(ok[:, None], g, 0).astype(dtype), np.where(ok[:, None], h, 0).astype(dtype)
-    with np.errstate(all="ignore"):
-        if f32:
-            A = dot32(gz.T[:, None, :], xp.T[None, :, :])
-            k = dot32(hz.T, np.ones((1, B), F32))
-            rw32 = rw.astype(F32)
-            free = rw32 < MARGIN_RMAX
-            t1 = (rw32[:, None] * A).astype(F32)
-            t3 = (((rw32 * rw32).astype(F32) * k).astype(F32)[:, None] * w).astype(F32)
-            dw = np.where(free[:, None], (t1 - t3).astype(F32), t1)
-        else:
-            nw = np.sqrt((w * w).sum(axis=1))
-            free = nw > NORM_EPS
-            dw = rw[:, None] * (gz.T @ xp) - np.where(free, rw * rw * hz.sum(axis=0), 0.0)[:, None] * w
-    out = {"z": z, "rx": rx, "rw": rw, "cosv": cosv, "g": g, "h": h, "row_loss": row_loss, "row_src": row_src, "pred": pred, "dw": dw,
-           "n": n, "detail": det, "ok": ok, "y": y, "loss": float(row_loss[ok].astype(np.float64).mean()) if n else float("nan")}
-    if n:
-        st["t"] += 1
-        w = _adam_rule(w, dw, st, "w", t=st["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
-                       decoupled=decoupled, amsgrad=amsgrad, f32=f32)
-    out["w"], out["state"] = w, st
     return out
 
 
@@ -1863,8 +1343,8 @@ def margin_step_host(x, labels, w, state: np.ndarray, workspace: Optional[np.nda
     workspace = _host_buffers(op, state, margin_state_bytes(D, C, amsgrad), workspace, margin_workspace_bytes(B, D, C), given_g)
     _lib.check(_lib.load().frmap_head_fit_margin_step_host(
         _at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w), _at(state), _at(workspace), N, B, D, C, float(s), float(m),
-        float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-        _margin_flags(decoupled, amsgrad, clear, easy_margin), int(bool(given_g))), op)
+        float(label_smoothing), *_adam(lr, beta1, beta2, eps, weight_decay), _margin_flags(decoupled, amsgrad, clear, easy_margin),
+        int(bool(given_g))), op)
     return workspace
 
 
@@ -1884,18 +1364,12 @@ def margin_step(x: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, state: t
     _sized(w, op, "w", (w.shape[0] if isinstance(w, torch.Tensor) and w.dim() == 2 else -1, D), torch.float32)
     C = int(w.shape[0])
     rows, B = _batch(op, entry, N, rows, (keep,), batch)
-    if keep is not None:
-        _sized(keep, op, "keep", (B, D), torch.uint8)
-    _sized(state, op, "state", (margin_state_bytes(D, C, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (margin_workspace_bytes(B, D, C),), torch.uint8)
-    labels = _operand(labels, op, entry, "labels", torch.int32)
-    keep = _operand(keep, op, entry, "keep", torch.uint8)
-    w = _operand(w, op, entry, "w", torch.float32, True)
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _mask(op, "keep", keep, (B, D))
+    _buffers(op, entry, state, margin_state_bytes(D, C, amsgrad), workspace, margin_workspace_bytes(B, D, C), w=w)
+    labels, keep = _reads(op, entry, labels=labels, keep=keep)
     _lib.check(_lib.load().frmap_head_fit_margin_step(
         x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w.data_ptr(), state.data_ptr(), workspace.data_ptr(),
-        N, B, D, C, float(s), float(m), float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        N, B, D, C, float(s), float(m), float(label_smoothing), *_adam(lr, beta1, beta2, eps, weight_decay),
         _margin_flags(decoupled, amsgrad, clear, easy_margin), _stream()), op)
 
 
@@ -1908,10 +1382,8 @@ class MarginHead(_Head):
     def __init__(self, D: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None):
         self.D, self.C, self.amsgrad = int(D), int(C), bool(amsgrad)
         nbytes = margin_state_bytes(self.D, self.C, self.amsgrad)          # (refuses a bad shape)
-        std = math.sqrt(2.0) * math.sqrt(2.0 / (self.D + self.C))
-        w = torch.empty((self.C, self.D), dtype=torch.float32).normal_(0.0, std, generator=generator)
         device = torch.device(device)
-        self.weight = w.to(device)
+        self.weight = _margin_init(self.C, self.D, generator).to(device)
         self._start(torch.zeros((nbytes,), dtype=torch.uint8, device=device), device)
 
     def _workspace_bytes(self, B: int) -> int:
@@ -1924,13 +1396,9 @@ class MarginHead(_Head):
         """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`margin_step`) at the effective scale ``s`` and margin ``m``.
         ``keep``: a uint8 ``[B, D]`` dropout mask, scaled by ``keep_scale`` (default ``1 / (1 - dropout)``; the scale cancels in the
         cosine).  No synchronisation."""
-        if keep_scale is None:
-            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
-        B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
-            int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
-        return self._run(margin_step, x, labels, self.weight, self.state, self._workspace(B), rows, keep, keep_scale, s=s, m=m,
-                         easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
-                         label_smoothing=label_smoothing, decoupled=decoupled)
+        return self._run(margin_step, x, labels, self.weight, self.state, self._workspace(self._batch_rows(x, rows, keep)), rows, keep,
+                         self._keep_scale(keep_scale, keep, dropout), s=s, m=m, easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2,
+                         eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
 
     def cosines(self, x: torch.Tensor) -> torch.Tensor:
         """The cosine of every row of ``x`` ``[B, D]`` with every class centre, ``[B, C]`` (`ops.cosine_logits`)."""
@@ -1945,13 +1413,8 @@ class MarginHead(_Head):
 
     def load_into(self, model) -> None:
         """Copy the centres into ``arcface.weight`` of an ``ArcFaceNet`` in place; any other class and any other shape is refused."""
-        arc = getattr(model, "arcface", None)
-        if type(model).__name__ != "ArcFaceNet" or not isinstance(getattr(arc, "weight", None), torch.Tensor):
-            raise ValueError(f"MarginHead.load_into: an ArcFaceNet expected, got {type(model).__name__}")
-        if tuple(arc.weight.shape) != (self.C, self.D):
-            raise ValueError(f"MarginHead.load_into: arcface.weight is {list(arc.weight.shape)}, the head is {[self.C, self.D]}")
-        with torch.no_grad():
-            arc.weight.copy_(self.weight)
+        arc = _arcface_parts("MarginHead.load_into", model)[2]
+        _load("MarginHead.load_into", "the head", (("arcface.weight", arc.weight, self.weight),))
 
 
 def fit_margin_head(model, train_data, val_data=None, epochs: int = 10, batch_size: int = 32, lr: float = 1e-3, weight_decay: float = 1e-4,
@@ -1963,32 +1426,27 @@ def fit_margin_head(model, train_data, val_data=None, epochs: int = 10, batch_si
     mode, since a normalisation follows); epoch ``e`` runs at `margin_schedule(e, s, m)`; every epoch draws a fresh device permutation
     as ``rows`` (and masks, with ``dropout``) and steps through it with no host copy inside the epoch.  The defaults are the reference's
     ArcFace settings (`src/training.py:340-348`: AdamW, AMSGrad, label smoothing 0.05).  With ``val_data`` every epoch's validation
-    ``head.logits`` go through `evaluate.ClassificationTally`.  Returns ``(head, history)`` in `fit_head`'s shape."""
-    from . import evaluate
+    ``head.logits`` go through `evaluate.ClassificationTally`.  Returns ``(head, history)`` in `fit_head`'s shape.
+    Order of draws: the device generator's seed from the CPU ``generator`` FIRST, then the head from it (the reverse of `fit_head`,
+    kept as it is); per epoch one ``randperm``; per batch one ``rand`` iff ``dropout > 0``."""
     feats, labels = cache_embeddings(model, train_data, device=device)
-    N, D = int(feats.shape[0]), int(feats.shape[1])
+    D = int(feats.shape[1])
     C = int(num_classes) if num_classes is not None else int(labels.max().item()) + 1
     head_gen, dev_gen = _generators(generator, feats.device)
     head = MarginHead(D, C, feats.device, amsgrad=amsgrad, generator=head_gen)
     val = cache_embeddings(model, val_data, device=device) if val_data is not None else None
-    history = {"train_loss": [], "train_acc": [], "val": []}
-    for epoch in range(int(epochs)):
+    return _fit(head, epochs, _row_epochs(head, feats, labels, batch_size, [(D, dropout)], dev_gen,
+                                          _margin_kw(s, m, warm_up, lr=lr, easy_margin=easy_margin, label_smoothing=label_smoothing,
+                                                     dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)),
+                None if val is None else lambda head: _tally(C, head.logits(val[0], min(s, 24.0)), val[1]))
+
+
+def _margin_kw(s, m, warm_up, **kw):
+    """The per-epoch keyword arguments of a fit on the margin schedule: ``kw`` with epoch ``e``'s `margin_schedule(e, s, m)`."""
+    def step_kw(epoch):
         m_eff, s_eff = margin_schedule(epoch, s, m, warm_up=warm_up)
-        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
-        head.new_epoch()
-        for lo in range(0, N, int(batch_size)):
-            rows = perm[lo: lo + int(batch_size)]
-            keep = (torch.rand((rows.shape[0], D), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
-            head.step(feats, labels, rows, keep, lr=lr, s=s_eff, m=m_eff, easy_margin=easy_margin, label_smoothing=label_smoothing,
-                      dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)
-        fig = head.epoch_figures()
-        history["train_loss"].append(fig["loss"])
-        history["train_acc"].append(fig["accuracy"])
-        if val is not None:
-            tally = evaluate.ClassificationTally(C, device=feats.device)
-            tally.update(head.logits(val[0], min(s, 24.0)), val[1])
-            history["val"].append(tally.metrics())
-    return head, history
+        return dict(kw, s=s_eff, m=m_eff)
+    return step_kw
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -2036,131 +1494,6 @@ def embed_workspace_views(workspace: np.ndarray, B: int, E: int, C: int) -> dict
     return out
 
 
-def embed_fresh_state(D: int, E: int, C: int, amsgrad: bool = False, dtype=np.float64) -> dict:
-    """A state of `embed_step_rule`: ``{"linear", "bn", "margin"}`` of `fresh_state` dicts for (D, E), (1, E) and (E, C)."""
-    return {"linear": fresh_state(D, E, amsgrad, dtype), "bn": fresh_state(1, E, amsgrad, dtype), "margin": fresh_state(E, C, amsgrad, dtype)}
-
-
-def embed_step_rule(x, labels, w1, gamma, beta, running_mean, running_var, wc, state: Optional[dict] = None, rows=None, keep=None,
-                    keep_scale: float = 1.0, *, bn_eps: float = 1e-5, bn_momentum: float = 0.1, s: float, m: float,
-                    easy_margin: bool = False, lr: float = 1e-3, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                    weight_decay: float = 0.0, label_smoothing: float = 0.0, decoupled: bool = False, amsgrad: bool = False,
-                    clear: bool = False, dtype=np.float64, given: Optional[dict] = None, batch: Optional[int] = None) -> dict:
-    """One training step of the embedding head, the specification (csrc/head_fit_rule.h, EMBED; include/frmap_hip.h, "Head fitting of an
-    embedding layer").
-
-    ``dtype=np.float64``: the formulas in float64 as torch evaluates ``F.linear`` -> ``nn.BatchNorm1d`` in training mode -> the mask ->
-    `margin_step_rule`'s chain -> one ``optim.Adam`` / ``AdamW`` over the four tensors.  ``dtype=np.float32``: a, S, k and the chains
-    over B by `dot32`; the batch statistics, ah and da in float64 from float32 values and rounded once; the margin stage is
-    `margin_step_rule` in float32 on ``(y', lab)``; `adam32` - what the host twin computes, word for word but for a rare last bit of the
-    float64 stages.  ``given``: any of ``{"mean32", "rstd", "uvar", "ah"}`` (together), ``"margin"`` (`margin_step_rule`'s ``given``)
-    and ``"da"`` to take as they are.  ``state``: `embed_fresh_state`'s shape, or ``None``.
-
-    Nothing is modified: returns the new ``w1, gamma, beta, running_mean, running_var, wc, state`` and ``a, lab, row_src1, n1, n2, taken,
-    mean32, rstd, uvar, ah, yp, gy, dbeta, dgamma, da, dw1, loss`` with the margin stage's own result under ``"margin"``."""
-    f32 = np.dtype(dtype) == np.dtype(np.float32)
-    given = given or {}
-    x = np.asarray(x, F32 if f32 else np.float64)
-    w1, gamma, beta, rm, rv = (np.array(t, dtype) for t in (w1, gamma, beta, running_mean, running_var))
-    wc_old = np.array(wc, dtype)
-    labels = np.asarray(labels).astype(np.int64)
-    N, D = x.shape
-    E, C = w1.shape[0], wc_old.shape[0]
-    state = state or embed_fresh_state(D, E, C, amsgrad, dtype)
-    row_src1, ok1, xz = _rule_batch(x, labels, C, rows, len(keep) if keep is not None else (N if batch is None else int(batch)), None, 1.0, f32)
-    B = len(row_src1)
-    n1 = int(ok1.sum())
-    live = n1 >= 2
-    lab = np.where(ok1, labels[np.clip(row_src1, 0, N - 1)], -1).astype(np.int32)
-    kept = np.asarray(keep).astype(bool) if keep is not None else None
-    with np.errstate(all="ignore"):
-        a = dot32(xz[:, None, :], w1[None, :, :]).astype(F32) if f32 else xz @ w1.T
-        a[~ok1] = 0
-        a64 = a.astype(np.float64)
-        if "ah" in given:
-            mean32, rstd, uvar, ah = (np.array(given[k], dtype) for k in ("mean32", "rstd", "uvar", "ah"))
-        elif not live:
-            mean32, rstd, uvar, ah = np.zeros(E, dtype), np.zeros(E, dtype), np.zeros(E, dtype), np.zeros((B, E), dtype)
-        else:
-            mean = a64[ok1].sum(axis=0) / n1
-            var = ((a64[ok1] - mean) ** 2).sum(axis=0) / n1
-            mean32 = mean.astype(dtype)
-            rstd = (1.0 / np.sqrt(var + float(F32(bn_eps) if f32 else bn_eps))).astype(dtype)
-            uvar = ((var * n1) / (n1 - 1)).astype(dtype)
-            ah = ((a64 - (mean32.astype(np.float64) if f32 else mean)) * rstd.astype(np.float64)).astype(dtype)
-            ah[~ok1] = 0
-        y = (gamma[None, :] * ah).astype(dtype) + beta[None, :]
-        yp = y.astype(dtype)
-        if kept is not None:
-            yp = np.where(kept, (y * (F32(keep_scale) if f32 else float(keep_scale))).astype(dtype), 0).astype(dtype)
-        yp[~ok1] = 0
-        if not live:
-            yp[:] = 0
-    r2 = margin_step_rule(yp, lab, wc_old, state["margin"], None, None, 1.0, s=s, m=m, easy_margin=easy_margin, lr=lr, beta1=beta1,
-                          beta2=beta2, eps=eps, weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled,
-                          amsgrad=amsgrad, clear=clear, dtype=dtype, given=given.get("margin"), batch=B)
-    n2, ok2 = r2["n"], r2["ok"]
-    taken = live and n2 == n1
-    n = n1 if taken else 0
-    gz, hz = np.where(ok2[:, None], r2["g"], 0).astype(dtype), np.where(ok2[:, None], r2["h"], 0).astype(dtype)
-    rx, rw = np.asarray(r2["rx"], dtype), np.asarray(r2["rw"], dtype)
-    with np.errstate(all="ignore"):
-        if f32:
-            gw = (gz * rw[None, :]).astype(F32)
-            S = dot32(gw[:, None, :], wc_old.T[None, :, :])
-            k = dot32(hz, np.ones((1, C), F32))
-            t3 = (((rx * rx).astype(F32) * k).astype(F32)[:, None] * yp).astype(F32)
-            gyp = np.where((rx < MARGIN_RMAX)[:, None], (S - t3).astype(F32), S)
-            gy = gyp if kept is None else np.where(kept, (gyp * F32(keep_scale)).astype(F32), 0)
-        else:
-            free = rx < 1.0 / NORM_EPS
-            gyp = (gz * rw[None, :]) @ wc_old - np.where(free, rx * rx * hz.sum(axis=1), 0.0)[:, None] * yp
-            gy = gyp if kept is None else np.where(kept, gyp * float(keep_scale), 0)
-        gy = np.where(ok2[:, None], gy, 0).astype(dtype)
-        gyz, ahz = np.where(ok1[:, None], gy, 0).astype(dtype), np.where(ok1[:, None], ah, 0).astype(dtype)
-        if f32:
-            dbeta = dot32(gyz.T, np.ones((1, B), F32))
-            dgamma = dot32(gyz.T, ahz.T)
-        else:
-            dbeta, dgamma = gyz.sum(axis=0), (gyz * ahz).sum(axis=0)
-        if "da" in given:
-            da = np.array(given["da"], dtype)
-        elif not taken:
-            da = np.zeros((B, E), dtype)
-        else:
-            g64, r64, b64, d64 = (t.astype(np.float64) for t in (gamma, rstd, dbeta, dgamma))
-            da = ((g64 * r64)[None, :] * ((gy.astype(np.float64) - (b64 / n1)[None, :]) - ah.astype(np.float64) * (d64 / n1)[None, :])).astype(dtype)
-            da[~ok1] = 0
-        daz = np.where(ok1[:, None], da, 0).astype(dtype)
-        dw1 = dot32(daz.T[:, None, :], xz.T[None, :, :]) if f32 else daz.T @ xz
-    st1, st2 = _copy_state(state["linear"], dtype), _copy_state(state["bn"], dtype)
-    if taken:
-        st3, wc_new = r2["state"], r2["w"]
-        kw = dict(t=st3["t"], lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, decoupled=decoupled, amsgrad=amsgrad, f32=f32)
-        w1 = _adam_rule(w1, dw1, st1, "w", **kw)
-        gamma = _adam_rule(gamma[:, None], dgamma[:, None], st2, "w", **kw)[:, 0]
-        beta = _adam_rule(beta, dbeta, st2, "b", **kw)
-        if f32:
-            mom = F32(bn_momentum)
-            omm = F32(F32(1) - mom)
-            rm = (omm * rm).astype(F32) + (mom * mean32).astype(F32)
-            rv = (omm * rv).astype(F32) + (mom * uvar).astype(F32)
-        else:
-            rm = (1.0 - bn_momentum) * rm + bn_momentum * mean32
-            rv = (1.0 - bn_momentum) * rv + bn_momentum * uvar
-    else:
-        st3, wc_new = _copy_state(state["margin"], dtype), wc_old
-        if clear:
-            st3["rows"] = st3["correct"] = st3["loss_q"] = 0
-        st3["n"] = 0
-    for st in (st1, st2):
-        st["t"], st["n"] = st3["t"], n
-    return {"w1": w1, "gamma": gamma, "beta": beta, "running_mean": rm, "running_var": rv, "wc": wc_new,
-            "state": {"linear": st1, "bn": st2, "margin": st3}, "a": a, "lab": lab, "row_src1": row_src1, "n1": n1, "n2": n2, "taken": taken,
-            "mean32": mean32, "rstd": rstd, "uvar": uvar, "ah": ah, "yp": yp, "gy": gy, "dbeta": dbeta, "dgamma": dgamma, "da": da, "dw1": dw1,
-            "loss": r2["loss"], "margin": r2}
-
-
 def _host_vectors(op, E, **vectors):
     for name, v in vectors.items():
         _host_array(op, name, v, np.float32)
@@ -2195,8 +1528,7 @@ def embed_step_host(x, labels, w1, gamma, beta, running_mean, running_var, wc, s
     _lib.check(_lib.load().frmap_head_fit_embed_step_host(
         _at(x), _at(labels), _at(rows), _at(keep), float(keep_scale), _at(w1), _at(gamma), _at(beta), _at(running_mean), _at(running_var),
         _at(wc), _at(state), _at(workspace), N, B, D, E, C, float(bn_eps), float(bn_momentum), float(s), float(m), float(label_smoothing),
-        float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), _margin_flags(decoupled, amsgrad, clear, easy_margin),
-        int(given)), op)
+        *_adam(lr, beta1, beta2, eps, weight_decay), _margin_flags(decoupled, amsgrad, clear, easy_margin), int(given)), op)
     return workspace
 
 
@@ -2223,20 +1555,13 @@ def embed_step(x: torch.Tensor, labels: torch.Tensor, w1: torch.Tensor, gamma: t
     for name, t in vectors.items():
         _sized(t, op, name, (E,), torch.float32)
     rows, B = _batch(op, entry, N, rows, (keep,), batch)
-    if keep is not None:
-        _sized(keep, op, "keep", (B, E), torch.uint8)
-    _sized(state, op, "state", (embed_state_bytes(D, E, C, amsgrad),), torch.uint8)
-    _sized(workspace, op, "workspace", (embed_workspace_bytes(B, D, E, C),), torch.uint8)
-    labels = _operand(labels, op, entry, "labels", torch.int32)
-    keep = _operand(keep, op, entry, "keep", torch.uint8)
-    w1, wc = _operand(w1, op, entry, "w1", torch.float32, True), _operand(wc, op, entry, "wc", torch.float32, True)
-    gamma, beta, running_mean, running_var = (_operand(t, op, entry, name, torch.float32, True) for name, t in vectors.items())
-    state = _operand(state, op, entry, "state", torch.uint8, True)
-    workspace = _operand(workspace, op, entry, "workspace", torch.uint8, True)
+    _mask(op, "keep", keep, (B, E))
+    _buffers(op, entry, state, embed_state_bytes(D, E, C, amsgrad), workspace, embed_workspace_bytes(B, D, E, C), w1=w1, wc=wc, **vectors)
+    labels, keep = _reads(op, entry, labels=labels, keep=keep)
     _lib.check(_lib.load().frmap_head_fit_embed_step(
         x.data_ptr(), labels.data_ptr(), _dev_at(rows), _dev_at(keep), float(keep_scale), w1.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
         running_mean.data_ptr(), running_var.data_ptr(), wc.data_ptr(), state.data_ptr(), workspace.data_ptr(), N, B, D, E, C, float(bn_eps),
-        float(bn_momentum), float(s), float(m), float(label_smoothing), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+        float(bn_momentum), float(s), float(m), float(label_smoothing), *_adam(lr, beta1, beta2, eps, weight_decay),
         _margin_flags(decoupled, amsgrad, clear, easy_margin), _stream()), op)
 
 
@@ -2250,8 +1575,7 @@ class EmbedHead(_Head):
     def __init__(self, D: int, E: int, C: int, device="cuda", amsgrad: bool = False, generator: Optional[torch.Generator] = None,
                  bn_eps: float = 1e-5, bn_momentum: float = 0.1):
         w1 = _linear_init(int(E), int(D), generator)[0]
-        std = math.sqrt(2.0) * math.sqrt(2.0 / (int(E) + int(C)))
-        wc = torch.empty((int(C), int(E)), dtype=torch.float32).normal_(0.0, std, generator=generator)
+        wc = _margin_init(int(C), int(E), generator)
         self._adopt(w1, torch.ones(int(E)), torch.zeros(int(E)), torch.zeros(int(E)), torch.ones(int(E)), wc, device, amsgrad, bn_eps, bn_momentum)
 
     def _adopt(self, w1, gamma, beta, running_mean, running_var, wc, device, amsgrad, bn_eps, bn_momentum):
@@ -2268,10 +1592,7 @@ class EmbedHead(_Head):
     def from_model(cls, model, device=None, amsgrad: bool = False) -> "EmbedHead":
         """A head that starts from ``embedding.weight``, ``bn`` and ``arcface.weight`` of an ``ArcFaceNet`` (copies: the model changes
         only through `load_into`)."""
-        emb, bn, arc = (getattr(model, k, None) for k in ("embedding", "bn", "arcface"))
-        if type(model).__name__ != "ArcFaceNet" or not isinstance(emb, torch.nn.Linear) or not isinstance(bn, torch.nn.BatchNorm1d) or \
-                not isinstance(getattr(arc, "weight", None), torch.Tensor):
-            raise ValueError(f"EmbedHead.from_model: an ArcFaceNet expected, got {type(model).__name__}")
+        emb, bn, arc = _arcface_parts("EmbedHead.from_model", model)
         if emb.bias is not None:
             raise ValueError("EmbedHead.from_model: embedding has a bias; the head has none")
         one = cls.__new__(cls)
@@ -2289,14 +1610,10 @@ class EmbedHead(_Head):
         """One step over rows ``rows`` of the cache ``x`` / ``labels`` (`embed_step`) at the effective scale ``s`` and margin ``m``.
         ``keep``: a uint8 ``[B, E]`` dropout mask behind the BatchNorm, scaled by ``keep_scale`` (default ``1 / (1 - dropout)``).  No
         synchronisation."""
-        if keep_scale is None:
-            keep_scale = 1.0 / (1.0 - float(dropout)) if keep is not None else 1.0
-        B = int(rows.shape[0]) if isinstance(rows, torch.Tensor) and rows.dim() == 1 else (
-            int(keep.shape[0]) if isinstance(keep, torch.Tensor) and keep.dim() == 2 else int(x.shape[0]))
         return self._run(embed_step, x, labels, self.w1, self.gamma, self.beta, self.running_mean, self.running_var, self.wc, self.state,
-                         self._workspace(B), rows, keep, keep_scale, bn_eps=self.bn_eps, bn_momentum=self.bn_momentum, s=s, m=m,
-                         easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
-                         label_smoothing=label_smoothing, decoupled=decoupled)
+                         self._workspace(self._batch_rows(x, rows, keep)), rows, keep, self._keep_scale(keep_scale, keep, dropout), bn_eps=self.bn_eps,
+                         bn_momentum=self.bn_momentum, s=s, m=m, easy_margin=easy_margin, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                         weight_decay=weight_decay, label_smoothing=label_smoothing, decoupled=decoupled)
 
     def embed(self, x: torch.Tensor) -> torch.Tensor:
         """``normalize(bn_eval(x w1^T))`` of pooled-feature rows ``x`` ``[B, D]`` with the RUNNING statistics: the arithmetic of the
@@ -2324,22 +1641,14 @@ class EmbedHead(_Head):
         ``arcface.weight`` of an ``ArcFaceNet`` in place and advance ``bn.num_batches_tracked`` by the steps taken since the last
         `load_into` (one host copy of the step count); any other class and any other shape is refused by name.  The model's plan
         watches its parameters and buffers: the next forward rebuilds."""
-        emb, bn, arc = (getattr(model, k, None) for k in ("embedding", "bn", "arcface"))
-        if type(model).__name__ != "ArcFaceNet" or not isinstance(emb, torch.nn.Linear) or not isinstance(bn, torch.nn.BatchNorm1d) or \
-                not isinstance(getattr(arc, "weight", None), torch.Tensor):
-            raise ValueError(f"EmbedHead.load_into: an ArcFaceNet expected, got {type(model).__name__}")
-        pairs = (("embedding.weight", emb.weight, self.w1), ("bn.weight", bn.weight, self.gamma), ("bn.bias", bn.bias, self.beta),
-                 ("bn.running_mean", bn.running_mean, self.running_mean), ("bn.running_var", bn.running_var, self.running_var),
-                 ("arcface.weight", arc.weight, self.wc))
-        for name, dst, src in pairs:
-            if not isinstance(dst, torch.Tensor) or tuple(dst.shape) != tuple(src.shape):
-                raise ValueError(f"EmbedHead.load_into: {name} is {list(dst.shape) if isinstance(dst, torch.Tensor) else None}, "
-                                 f"the head's is {list(src.shape)}")
+        emb, bn, arc = _arcface_parts("EmbedHead.load_into", model)
+        _load("EmbedHead.load_into", "the head's",
+              (("embedding.weight", emb.weight, self.w1), ("bn.weight", bn.weight, self.gamma), ("bn.bias", bn.bias, self.beta),
+               ("bn.running_mean", bn.running_mean, self.running_mean), ("bn.running_var", bn.running_var, self.running_var),
+               ("arcface.weight", arc.weight, self.wc)))
         t = self.epoch_figures()["t"]
-        with torch.no_grad():
-            for _, dst, src in pairs:
-                dst.copy_(src)
-            if bn.num_batches_tracked is not None:
+        if bn.num_batches_tracked is not None:
+            with torch.no_grad():
                 bn.num_batches_tracked += t - getattr(self, "_loaded_t", 0)
         self._loaded_t = t
 
@@ -2355,26 +1664,19 @@ def fit_embed_head(model, train_data, val_data=None, epochs: int = 10, batch_siz
     ``dropout``, a mask per step, and steps through it with no host copy inside the epoch.  A trailing batch of one row is a step that
     is not taken (BatchNorm has no statistics of one row).  The defaults are the reference's ArcFace settings (`src/training.py:340-348`;
     ``dropout_rate=0.2``).  With ``val_data`` every epoch's validation accuracy is the arg-max of `ops.cosine_logits` of `EmbedHead.embed`
-    against the centres.  The model is not changed: call ``head.load_into(model)``.  Returns ``(head, history)`` in `fit_head`'s shape."""
+    against the centres.  The model is not changed: call ``head.load_into(model)``.  Returns ``(head, history)`` in `fit_head`'s shape.
+    Order of draws: no head is drawn (`EmbedHead.from_model`); the device generator's seed from the CPU ``generator``; per epoch one
+    ``randperm``; per batch one ``rand`` of ``[rows, E]`` iff ``dropout > 0`` - for the trailing batch of one row too, which is
+    stepped and which the library declines."""
     feats, labels = cache_features(model, "arcface", train_data, device=device, layer="pooled")
-    N = int(feats.shape[0])
     head = EmbedHead.from_model(model, feats.device, amsgrad=amsgrad)
     _, dev_gen = _generators(generator, feats.device)
     val = cache_features(model, "arcface", val_data, device=device, layer="pooled") if val_data is not None else None
-    history = {"train_loss": [], "train_acc": [], "val": []}
-    for epoch in range(int(epochs)):
-        m_eff, s_eff = margin_schedule(epoch, s, m, warm_up=warm_up)
-        perm = torch.randperm(N, device=feats.device, generator=dev_gen).to(torch.int32)
-        head.new_epoch()
-        for lo in range(0, N, int(batch_size)):
-            rows = perm[lo: lo + int(batch_size)]
-            keep = (torch.rand((rows.shape[0], head.E), device=feats.device, generator=dev_gen) >= dropout).to(torch.uint8) if dropout > 0 else None
-            head.step(feats, labels, rows, keep, lr=lr, s=s_eff, m=m_eff, easy_margin=easy_margin, label_smoothing=label_smoothing,
-                      dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)
-        fig = head.epoch_figures()
-        history["train_loss"].append(fig["loss"])
-        history["train_acc"].append(fig["accuracy"])
-        if val is not None:
-            pred = ops.cosine_logits(head.embed(val[0]), head.wc, s=1.0, want_logits=False, want_argmax=True)[1]
-            history["val"].append({"accuracy": float((pred.to(torch.int64) == val[1].to(torch.int64)).float().mean().item())})
-    return head, history
+
+    def validate(head):
+        pred = ops.cosine_logits(head.embed(val[0]), head.wc, s=1.0, want_logits=False, want_argmax=True)[1]
+        return {"accuracy": float((pred.to(torch.int64) == val[1].to(torch.int64)).float().mean().item())}
+    return _fit(head, epochs, _row_epochs(head, feats, labels, batch_size, [(head.E, dropout)], dev_gen,
+                                          _margin_kw(s, m, warm_up, lr=lr, easy_margin=easy_margin, label_smoothing=label_smoothing,
+                                                     dropout=dropout, weight_decay=weight_decay, decoupled=decoupled)),
+                validate if val is not None else None)

@@ -320,3 +320,63 @@ def test_fit_embed_head_end_to_end(tmp_path, calibrated_sd):
     assert not torch.equal(emb_before, got), "load_into did not change the model's embedding"
     assert after["rows"] == 32 and after["accuracy"] >= before["accuracy"] and after["accuracy"] >= 0.9
     assert rel <= 2 * base
+
+
+class ArcFaceNet(torch.nn.Module):
+    """An ``ArcFaceNet`` by name and attributes, as `EmbedHead.from_model` and `cache_features(layer="pooled")` ask: the pooled
+    features of an image are the image, flattened to 8; ``embedding`` 8 -> 5 without a bias, ``bn`` over 5, three class centres."""
+
+    def __init__(self):
+        super().__init__()
+        self.embedding, self.bn = torch.nn.Linear(8, 5, bias=False), torch.nn.BatchNorm1d(5)
+        self.arcface = torch.nn.Module()
+        self.arcface.weight = torch.nn.Parameter(torch.empty(3, 5).normal_(0.0, 0.5))
+
+    def pooled_features(self, im):
+        return im.reshape(im.shape[0], -1)
+
+
+def test_fit_embed_head_draws_in_the_documented_order():
+    """`fit_embed_head` against the same fit replayed by hand, N = 17, D = 8, E = 5, C = 3, batches of 8 (the last one has ONE row: it
+    is stepped and the library declines it), 2 epochs, dropout 0.25: no head draw (`EmbedHead.from_model`), then the device generator's
+    seed from the CPU generator; per epoch `margin_schedule(epoch)` and one `randperm`; per batch one mask `rand` of ``[rows, E]``;
+    `head.step`.  The six tensors, the whole state and the history are equal; ``t`` is 4, and `load_into` advances
+    ``num_batches_tracked`` by 4."""
+    rng = np.random.default_rng(9)
+    data = [(torch.from_numpy(rng.standard_normal((n, 2, 2, 2)).astype(F32)), torch.from_numpy(rng.integers(0, 3, n))) for n in (12, 5)]
+    data[0][1][:3] = torch.tensor([0, 1, 2])
+    model, kw = ArcFaceNet().to(DEV).eval(), dict(lr=1e-2, weight_decay=1e-4, label_smoothing=0.05, decoupled=True)
+    epochs, batch, dropout, s, m = 2, 8, 0.25, 32.0, 0.5
+    got, hist = hf.fit_embed_head(model, data, epochs=epochs, batch_size=batch, dropout=dropout, s=s, m=m, amsgrad=True, device=DEV,
+                                  generator=torch.Generator().manual_seed(21), **kw)
+    feats, labels = hf.cache_features(model, "arcface", data, device=DEV, layer="pooled")
+    N, D = feats.shape
+    assert (N, D, int(labels.max()) + 1) == (17, 8, 3)
+    gen = torch.Generator().manual_seed(21)
+    head = hf.EmbedHead.from_model(model, DEV, amsgrad=True)
+    assert (head.D, head.E, head.C) == (8, 5, 3)
+    dev_gen = torch.Generator(device=DEV)
+    dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=gen).item()))
+    want = {"train_loss": [], "train_acc": [], "val": []}
+    sizes = []
+    for epoch in range(epochs):
+        m_eff, s_eff = hf.margin_schedule(epoch, s, m)
+        perm = torch.randperm(N, device=DEV, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, batch):
+            rows = perm[lo: lo + batch]
+            sizes.append(int(rows.shape[0]))
+            keep = (torch.rand((rows.shape[0], head.E), device=DEV, generator=dev_gen) >= dropout).to(torch.uint8)
+            head.step(feats, labels, rows, keep, s=s_eff, m=m_eff, dropout=dropout, **kw)
+        fig = head.epoch_figures()
+        want["train_loss"].append(fig["loss"])
+        want["train_acc"].append(fig["accuracy"])
+    assert sizes == [8, 8, 1] * epochs
+    assert type(got) is type(head)
+    for name in ("w1", "gamma", "beta", "running_mean", "running_var", "wc", "state"):
+        assert torch.equal(getattr(got, name), getattr(head, name)), name
+    assert hist == want and len(hist["train_loss"]) == epochs and got.epoch_figures()["t"] == 2 * epochs == 4
+    assert hist["train_loss"] and all(np.isfinite(hist["train_loss"])) and got.epoch_figures()["rows"] == 16
+    tracked = int(model.bn.num_batches_tracked)
+    got.load_into(model)
+    assert int(model.bn.num_batches_tracked) == tracked + 4 and torch.equal(model.embedding.weight.detach(), head.w1)

@@ -373,3 +373,44 @@ def test_fit_margin_head_end_to_end(tmp_path, calibrated_sd):
     x = next(evaluate._folder_batches(evaluate.image_folder(root)[0], 8, DEV))[0]
     logits, arg = evaluate.arcface_validate(model, x)
     assert arg.tolist() == head.cosines(model.get_embedding(x).float()).argmax(1).tolist()
+
+
+def test_fit_margin_head_draws_in_the_documented_order():
+    """`fit_margin_head` against the same fit replayed by hand, N = 20, D = 8, C = 3, batches of 8 (the last one has 4 rows), 2 epochs,
+    dropout 0.25: the device generator's seed from the CPU generator FIRST, then the head from it (the reverse of `fit_head`); per epoch
+    `margin_schedule(epoch)` and one `randperm`; per batch one mask `rand`; `head.step`.  The centres, the whole state and the history
+    are equal."""
+    from test_head_fit_gpu import _FlatTrunk
+    rng = np.random.default_rng(9)
+    data = [(torch.from_numpy(rng.standard_normal((n, 2, 2, 2)).astype(F32)), torch.from_numpy(rng.integers(0, 3, n))) for n in (12, 8)]
+    data[0][1][:3] = torch.tensor([0, 1, 2])
+    trunk, kw = _FlatTrunk(), dict(lr=1e-2, weight_decay=1e-4, label_smoothing=0.05, decoupled=True)
+    epochs, batch, dropout, s, m = 2, 8, 0.25, 32.0, 0.5
+    got, hist = hf.fit_margin_head(trunk, data, epochs=epochs, batch_size=batch, dropout=dropout, s=s, m=m, amsgrad=True, device=DEV,
+                                   generator=torch.Generator().manual_seed(21), **kw)
+    feats, labels = hf.cache_embeddings(trunk, data, device=DEV)
+    N, D = feats.shape
+    assert (N, D, int(labels.max()) + 1) == (20, 8, 3)
+    gen = torch.Generator().manual_seed(21)
+    dev_gen = torch.Generator(device=DEV)
+    dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=gen).item()))
+    head = hf.MarginHead(D, 3, DEV, amsgrad=True, generator=gen)
+    want = {"train_loss": [], "train_acc": [], "val": []}
+    sizes = []
+    for epoch in range(epochs):
+        m_eff, s_eff = hf.margin_schedule(epoch, s, m)
+        perm = torch.randperm(N, device=DEV, generator=dev_gen).to(torch.int32)
+        head.new_epoch()
+        for lo in range(0, N, batch):
+            rows = perm[lo: lo + batch]
+            sizes.append(int(rows.shape[0]))
+            keep = (torch.rand((rows.shape[0], D), device=DEV, generator=dev_gen) >= dropout).to(torch.uint8)
+            head.step(feats, labels, rows, keep, s=s_eff, m=m_eff, dropout=dropout, **kw)
+        fig = head.epoch_figures()
+        want["train_loss"].append(fig["loss"])
+        want["train_acc"].append(fig["accuracy"])
+    assert sizes == [8, 8, 4] * epochs
+    assert type(got) is type(head)
+    for name in ("weight", "state"):
+        assert torch.equal(getattr(got, name), getattr(head, name)), name
+    assert hist == want and len(hist["train_loss"]) == epochs and got.epoch_figures()["t"] == 3 * epochs

@@ -369,3 +369,42 @@ def test_fit_pair_head_end_to_end(tmp_path, calibrated_sd):
     assert dist.shape == (4,) and pred.shape == (4,) and bool(torch.isfinite(dist).all())
     with pytest.raises(ValueError, match="no classifier head"):
         hf.fit_head(model, "siamese", root)
+
+
+def test_fit_pair_head_draws_in_the_documented_order():
+    """`fit_pair_head` against the same fit replayed by hand, N = 20, D = 8, E = 5, 8 pairs a step (ceil(20 / 8) = 3 steps an epoch),
+    2 epochs, dropout 0.25: the device generator's seed from the CPU generator FIRST, then the head from it (the reverse of `fit_head`);
+    per step `draw_pairs` (one `randint`, one `rand((3, P))`), then the mask's `rand((2P, D))`; `head.step`.  Weight, bias, the whole
+    state and the history are equal."""
+    from test_head_fit_gpu import _FlatTrunk
+    rng = np.random.default_rng(9)
+    data = [(torch.from_numpy(rng.standard_normal((n, 2, 2, 2)).astype(F32)), torch.from_numpy(rng.integers(0, 3, n))) for n in (12, 8)]
+    data[0][1][:3] = torch.tensor([0, 1, 2])
+    trunk, kw = _FlatTrunk(), dict(lr=1e-2, weight_decay=1e-4, decoupled=True)
+    epochs, P, dropout, E = 2, 8, 0.25, 5
+    got, hist = hf.fit_pair_head(trunk, data, epochs=epochs, batch_pairs=P, dropout=dropout, embed_dim=E, amsgrad=True, device=DEV,
+                                 generator=torch.Generator().manual_seed(21), **kw)
+    feats, labels = hf.cache_embeddings(trunk, data, device=DEV)
+    N, D = feats.shape
+    assert (N, D, int(labels.max()) + 1) == (20, 8, 3)
+    gen = torch.Generator().manual_seed(21)
+    dev_gen = torch.Generator(device=DEV)
+    dev_gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,), generator=gen).item()))
+    head = hf.PairHead(D, E, DEV, amsgrad=True, generator=gen)
+    want = {"train_loss": [], "train_acc": [], "val": []}
+    sizes = []
+    for _ in range(epochs):
+        head.new_epoch()
+        for _ in range((N + P - 1) // P):
+            left, right, differ = hf.draw_pairs(labels, P, dev_gen)
+            sizes.append(int(left.shape[0]))
+            keep = (torch.rand((2 * P, D), device=DEV, generator=dev_gen) >= dropout).to(torch.uint8)
+            head.step(feats, left, right, differ, keep, dropout=dropout, **kw)
+        fig = head.epoch_figures()
+        want["train_loss"].append(fig["loss"])
+        want["train_acc"].append(fig["accuracy"])
+    assert sizes == [8, 8, 8] * epochs
+    assert type(got) is type(head)
+    for name in ("weight", "bias", "state"):
+        assert torch.equal(getattr(got, name), getattr(head, name)), name
+    assert hist == want and len(hist["train_loss"]) == epochs and got.epoch_figures()["t"] == 3 * epochs

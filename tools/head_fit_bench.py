@@ -15,33 +15,17 @@ A machine without a GPU is refused: there is no CPU timing.
 
 Prints one JSON line per shape and writes them all to ``--out`` when given.
 """
-import argparse
-import json
 import math
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import head_fit_bench_common as common
+import torch
+import torch.nn.functional as F
 
 SHAPES = ((32, 512, 18), (256, 512, 1000), (1024, 512, 10000))
 CACHE_ROWS = 10000
 HYPER = dict(lr=1e-3, weight_decay=1e-4)
 DROPOUT = 0.1
-
-
-def _window(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
 
 
 def bench_shape(B, D, C, steps, warmup, repeats, dev):
@@ -77,19 +61,10 @@ def bench_shape(B, D, C, steps, warmup, repeats, dev):
 
     rows0 = torch.randperm(CACHE_ROWS, device=dev, generator=g)[:B].to(torch.int32)
     out = {"B": B, "D": D, "C": C, "cache_rows": CACHE_ROWS, "steps_per_window": steps, "repeats": repeats}
-    for name, step in (("ours", ours_step), ("torch", torch_step)):
-        for _ in range(warmup):
-            step(rows0)
-    per = {"ours": [], "torch": [], "ours_epoch": [], "torch_epoch": []}
-    for _ in range(repeats):                                   # the two sides alternate inside one process
-        per["ours"].append(_window(lambda: ours_step(rows0), steps))
-        per["torch"].append(_window(lambda: torch_step(rows0), steps))
-    for _ in range(max(2, repeats // 2)):
-        per["ours_epoch"].append(_window(lambda: epoch(ours_step), 1))
-        per["torch_epoch"].append(_window(lambda: epoch(torch_step), 1))
-    for k, v in per.items():
-        scale = 1e6 if "epoch" not in k else 1e3
-        out[k + ("_us" if "epoch" not in k else "_ms")] = {"median": statistics.median(v) * scale, "min": min(v) * scale, "max": max(v) * scale}
+    common.time_steps(out, lambda: ours_step(rows0), lambda: torch_step(rows0), steps, warmup, repeats)
+    epochs = common.alternate({"ours_epoch": lambda: epoch(ours_step), "torch_epoch": lambda: epoch(torch_step)}, 1, max(2, repeats // 2))
+    for k, v in epochs.items():
+        out[k + "_ms"] = common.record(v, 1e3)
     head.new_epoch().step(x, labels, rows0, None, **HYPER)
     out["loss_ours_last_step"] = head.epoch_figures()["loss"]
     out["loss_torch_last_step"] = float(last["torch"].detach())
@@ -110,33 +85,21 @@ def bench_features(dev, batch=256, batches=8, repeats=3):
     g = torch.Generator(device=dev).manual_seed(2)
     data = [(torch.randn((batch, 3, 224, 224), device=dev, generator=g), torch.zeros((batch,), dtype=torch.int64)) for _ in range(batches)]
     hf.cache_features(model, "cnn", data, device=dev)           # warm-up: plans, code objects
-    times = [_window(lambda: hf.cache_features(model, "cnn", data, device=dev), 1) for _ in range(repeats)]
+    times = [common.window(lambda: hf.cache_features(model, "cnn", data, device=dev), 1) for _ in range(repeats)]
     return {"what": "cache_features cnn fp16", "batch": batch, "faces": batch * batches, "faces_per_s": batch * batches / statistics.median(times),
             "min_faces_per_s": batch * batches / max(times), "max_faces_per_s": batch * batches / min(times)}
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--steps", type=int, default=200, help="steps per timed window")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--features", action="store_true", help="also time cache_features on a synthetic cnn model")
-    ap.add_argument("--out", default=None, help="write the JSON lines to this file as well")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("head_fit_bench: no GPU; a timing on the CPU says nothing about the device (not measured)")
-    dev = torch.device("cuda:0")
-    lines = [bench_shape(B, D, C, args.steps, args.warmup, args.repeats, dev) for B, D, C in SHAPES]
+def lines_of(args, shapes, dev):
+    for B, D, C in shapes:
+        yield bench_shape(B, D, C, args.steps, args.warmup, args.repeats, dev)
     if args.features:
-        lines.append(bench_features(dev))
-    for ln in lines:
-        print(json.dumps(ln))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for ln in lines:
-                fh.write(json.dumps(ln) + "\n")
+        yield bench_features(dev)
+
+
+def _features(ap):
+    ap.add_argument("--features", action="store_true", help="also time cache_features on a synthetic cnn model")
 
 
 if __name__ == "__main__":
-    main()
+    common.main("head_fit_bench", __doc__, SHAPES, lines_of, steps=200, steps_help="steps per timed window", more=_features)

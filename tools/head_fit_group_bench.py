@@ -14,36 +14,14 @@ without a GPU is refused: there is no CPU timing.
 
 Prints one JSON line per (shape, H) and one for the cross-validation, and writes them all to ``--out`` when given.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
+import head_fit_bench_common as common
+import torch
 
 SHAPES = ((32, 512, 18), (256, 512, 1000))
 HEADS = (1, 5, 16, 64)
 CACHE_ROWS = 10000
 HYPER = dict(lr=1e-3, weight_decay=1e-4)
 DROPOUT = 0.1
-
-
-def _window(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
-
-
-def _stat(v, scale):
-    return {"median": statistics.median(v) * scale, "min": min(v) * scale, "max": max(v) * scale}
 
 
 def bench_step(H, B, D, C, x, labels, steps, warmup, repeats, dev):
@@ -62,15 +40,9 @@ def bench_step(H, B, D, C, x, labels, steps, warmup, repeats, dev):
         for h in range(H):
             heads[h].step(x, labels, row_h[h], keep_h[h], dropout=DROPOUT, **HYPER)
 
-    for fn in (grouped, singles):
-        for _ in range(warmup):
-            fn()
-    per = {"grouped": [], "singles": []}
-    for _ in range(repeats):                                   # the two sides alternate inside one process
-        per["grouped"].append(_window(grouped, steps))
-        per["singles"].append(_window(singles, max(1, steps // H)))
+    per = common.alternate({"grouped": grouped, "singles": singles}, {"grouped": steps, "singles": max(1, steps // H)}, repeats, warmup)
     out = {"what": "step", "H": H, "B": B, "D": D, "C": C, "steps_per_window": steps, "repeats": repeats,
-           "grouped_us": _stat(per["grouped"], 1e6), "singles_us": _stat(per["singles"], 1e6)}
+           "grouped_us": common.record(per["grouped"]), "singles_us": common.record(per["singles"])}
     out["speedup"] = out["singles_us"]["median"] / out["grouped_us"]["median"]
     # beyond the run-to-run spread of the two sides: the slowest grouped window still beats the fastest window of H single steps
     out["beyond_spread"] = out["grouped_us"]["max"] < out["singles_us"]["min"]
@@ -103,47 +75,29 @@ def bench_cv(x, labels, C, repeats, dev, folds=5, epochs=15, B=32):
                 tally.update(head.logits(vx), vy)
                 tally.metrics()
 
-    grouped()
-    loops()
-    per = {"grouped": [], "loops": []}
-    for _ in range(repeats):
-        per["grouped"].append(_window(grouped, 1))
-        per["loops"].append(_window(loops, 1))
+    per = common.alternate({"grouped": grouped, "loops": loops}, 1, repeats, warmup=1)
     out = {"what": "cross_validate", "folds": folds, "epochs": epochs, "B": B, "D": D, "C": C, "cache_rows": CACHE_ROWS, "repeats": repeats,
-           "grouped_ms": _stat(per["grouped"], 1e3), "loops_ms": _stat(per["loops"], 1e3)}
+           "grouped_ms": common.record(per["grouped"], 1e3), "loops_ms": common.record(per["loops"], 1e3)}
     out["speedup"] = out["loops_ms"]["median"] / out["grouped_ms"]["median"]
     out["beyond_spread"] = out["grouped_ms"]["max"] < out["loops_ms"]["min"]
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--steps", type=int, default=200, help="grouped steps per timed window (the single side runs steps / H rounds of H)")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--no-cv", action="store_true", help="skip the cross-validation timing")
-    ap.add_argument("--out", default=None, help="write the JSON lines to this file as well")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("head_fit_group_bench: no GPU; a timing on the CPU says nothing about the device (not measured)")
-    dev = torch.device("cuda:0")
-    lines = []
-    for B, D, C in SHAPES:
+def lines_of(args, shapes, dev):
+    for B, D, C in shapes:
         g = torch.Generator(device=dev).manual_seed(B + C)
         x = torch.randn((CACHE_ROWS, D), device=dev, generator=g)
         labels = torch.randint(0, C, (CACHE_ROWS,), device=dev, generator=g, dtype=torch.int32)
         for H in HEADS:
-            lines.append(bench_step(H, B, D, C, x, labels, args.steps, args.warmup, args.repeats, dev))
-            print(json.dumps(lines[-1]), flush=True)
+            yield bench_step(H, B, D, C, x, labels, args.steps, args.warmup, args.repeats, dev)
         if not args.no_cv and (B, D, C) == SHAPES[0]:
-            lines.append(bench_cv(x, labels, C, max(2, args.repeats // 2), dev))
-            print(json.dumps(lines[-1]), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for ln in lines:
-                fh.write(json.dumps(ln) + "\n")
+            yield bench_cv(x, labels, C, max(2, args.repeats // 2), dev)
+
+
+def _no_cv(ap):
+    ap.add_argument("--no-cv", action="store_true", help="skip the cross-validation timing")
 
 
 if __name__ == "__main__":
-    main()
+    common.main("head_fit_group_bench", __doc__, SHAPES, lines_of, steps=200, more=_no_cv,
+                steps_help="grouped steps per timed window (the single side runs steps / H rounds of H)")

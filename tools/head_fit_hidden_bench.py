@@ -16,32 +16,14 @@ is no CPU timing.
 
 Prints one JSON line per shape and writes them all to ``--out`` when given.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import head_fit_bench_common as common
+import torch
+import torch.nn.functional as F
 
 SHAPES = ((32, 128, 512, 18), (32, 512, 256, 18), (256, 512, 256, 1000))
 CACHE_ROWS = 10000
 HYPER = dict(lr=1e-3, weight_decay=1e-4)
 DROPOUT1, DROPOUT2 = 0.1, 0.5
-
-
-def _window(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
 
 
 def bench_shape(B, D, Hd, C, steps, warmup, repeats, dev, only_ours=False):
@@ -75,21 +57,8 @@ def bench_shape(B, D, Hd, C, steps, warmup, repeats, dev, only_ours=False):
 
     rows0 = torch.randperm(CACHE_ROWS, device=dev, generator=g)[:B].to(torch.int32)
     out = {"B": B, "D": D, "Hd": Hd, "C": C, "cache_rows": CACHE_ROWS, "steps_per_window": steps, "repeats": repeats}
-    for step in ((ours_step,) if only_ours else (ours_step, torch_step)):
-        for _ in range(warmup):
-            step(rows0)
-    if only_ours:
-        for _ in range(steps):
-            ours_step(rows0)
-        torch.cuda.synchronize()
-        out["only"] = "ours"
+    if not common.time_steps(out, lambda: ours_step(rows0), lambda: torch_step(rows0), steps, warmup, repeats, only_ours):
         return out
-    per = {"ours": [], "torch": []}
-    for _ in range(repeats):                                   # the two sides alternate inside one process
-        per["ours"].append(_window(lambda: ours_step(rows0), steps))
-        per["torch"].append(_window(lambda: torch_step(rows0), steps))
-    for k, v in per.items():
-        out[k + "_us"] = {"median": statistics.median(v) * 1e6, "min": min(v) * 1e6, "max": max(v) * 1e6}
     head.new_epoch().step(x, labels, rows0, None, None, **HYPER)
     out["loss_ours_last_step"] = head.epoch_figures()["loss"]
     out["loss_torch_last_step"] = float(last["torch"].detach())
@@ -97,28 +66,10 @@ def bench_shape(B, D, Hd, C, steps, warmup, repeats, dev, only_ours=False):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--steps", type=int, default=500, help="back-to-back steps per timed window")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--only", choices=("ours",), default=None, help="run our side alone, untimed (for a kernel trace)")
-    ap.add_argument("--shape", type=int, default=None, choices=range(len(SHAPES)), help="one shape of the table only (its index)")
-    ap.add_argument("--out", default=None, help="write the JSON lines to this file as well")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("head_fit_hidden_bench: no GPU; a timing on the CPU says nothing about the device (not measured)")
-    dev = torch.device("cuda:0")
-    shapes = SHAPES if args.shape is None else SHAPES[args.shape: args.shape + 1]
-    lines = [bench_shape(B, D, Hd, C, args.steps, args.warmup, args.repeats, dev, args.only == "ours") for B, D, Hd, C in shapes]
-    for ln in lines:
-        print(json.dumps(ln))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for ln in lines:
-                fh.write(json.dumps(ln) + "\n")
+def lines_of(args, shapes, dev):
+    for B, D, Hd, C in shapes:
+        yield bench_shape(B, D, Hd, C, args.steps, args.warmup, args.repeats, dev, args.only == "ours")
 
 
 if __name__ == "__main__":
-    main()
+    common.main("head_fit_hidden_bench", __doc__, SHAPES, lines_of, steps=500, more=common.only_option)

@@ -15,33 +15,16 @@ spread (min .. max) are reported.  A machine without a GPU is refused: there is 
 
 Prints one JSON line per shape and writes them all to ``--out`` when given.
 """
-import argparse
-import json
 import math
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import head_fit_bench_common as common
+import torch
+import torch.nn.functional as F
 
 SHAPES = ((32, 512, 18), (256, 512, 1000), (64, 512, 10000))
 CACHE_ROWS = 10000
 HYPER = dict(lr=1e-3, weight_decay=1e-4)
 SMOOTHING = 0.05
-
-
-def _window(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n
 
 
 def bench_shape(B, D, C, steps, warmup, repeats, dev):
@@ -74,15 +57,7 @@ def bench_shape(B, D, C, steps, warmup, repeats, dev):
         last["torch"] = loss
 
     out = {"B": B, "D": D, "C": C, "cache_rows": CACHE_ROWS, "steps_per_window": steps, "repeats": repeats, "s": s_eff, "m": m_eff}
-    for step in (ours_step, torch_step):
-        for _ in range(warmup):
-            step()
-    per = {"ours": [], "torch": []}
-    for _ in range(repeats):                                   # the two sides alternate inside one process
-        per["ours"].append(_window(ours_step, steps))
-        per["torch"].append(_window(torch_step, steps))
-    for k, v in per.items():
-        out[k + "_us"] = {"median": statistics.median(v) * 1e6, "min": min(v) * 1e6, "max": max(v) * 1e6}
+    common.time_steps(out, ours_step, torch_step, steps, warmup, repeats)
     head.new_epoch()
     ours_step()
     out["loss_ours_last_step"] = head.epoch_figures()["loss"]
@@ -91,27 +66,10 @@ def bench_shape(B, D, C, steps, warmup, repeats, dev):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--steps", type=int, default=300, help="back-to-back steps per timed window")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--shape", type=int, default=None, choices=range(len(SHAPES)), help="one shape of the table only (its index)")
-    ap.add_argument("--out", default=None, help="write the JSON lines to this file as well")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("head_fit_margin_bench: no GPU; a timing on the CPU says nothing about the device (not measured)")
-    dev = torch.device("cuda:0")
-    shapes = SHAPES if args.shape is None else SHAPES[args.shape: args.shape + 1]
-    lines = [bench_shape(B, D, C, args.steps, args.warmup, args.repeats, dev) for B, D, C in shapes]
-    for ln in lines:
-        print(json.dumps(ln))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for ln in lines:
-                fh.write(json.dumps(ln) + "\n")
+def lines_of(args, shapes, dev):
+    for B, D, C in shapes:
+        yield bench_shape(B, D, C, args.steps, args.warmup, args.repeats, dev)
 
 
 if __name__ == "__main__":
-    main()
+    common.main("head_fit_margin_bench", __doc__, SHAPES, lines_of, steps=300)
